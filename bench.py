@@ -14,9 +14,19 @@ Launched by torch.distributed.run the ranks come from the environment; launched 
 the script spawns its N ranks itself (rank r -> device r mod visible devices; ranks that share a device use gloo, RCCL
 refuses two ranks on one GPU).
 
-Timed region: W warm-up steps, then exactly K steps between barrier + device sync on both sides, max over ranks.  The
-region is a few milliseconds, so it is repeated on `--repeats` fresh objects (same seeds => the same steps W..W+K from
-init each time) and the MEDIAN repeat is the headline; every repeat is listed in `ms_per_step_repeats`."""
+Timed region: W warm-up steps, then exactly K steps between barrier + device sync on both sides, max over ranks.  A plain
+run times that region once on a fresh object; `--repeats R` repeats it on R fresh objects (same seeds => the same steps
+W..W+K from init each time) and the MEDIAN repeat is the headline; every repeat is listed in `ms_per_step_repeats`.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, `--dump-outputs DIR` if given, the JSON
+line.  `--full` adds everything else, as before: five repeats by default, the roofline (an extra profiled window), late
+training, occupancy skipping, render + PSNR (and the N > 1 render gather), the offline_job leg, BASELINE configs[0] on
+the GPU, the CPU baselines, multi_object and stress_T22.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step, on rank 0, as DIR/<name>.npy (float32 /
+float64): `loss` (the value mon_object_train returned) and the parameters it leaves behind -- `params_master` (fp32
+master), `params_half` (fp16 working copy) and `params_ema` (fp16 EMA copy), both widened to float32.  Above 64 MB in
+all, the same fixed seeded sample of parameter indices is taken from each, listed in `params_sample_index`."""
 import argparse
 import json
 import os
@@ -40,7 +50,11 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5, help="independent repeats of the timed region (fresh object each); the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+            help="independent repeats of the timed region (fresh object each); the median is reported (default 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+            help="also measure everything beside the headline (roofline, late training, render, CPU baselines, multi_object, stress_T22, ...)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the timed path's outputs of its last step as DIR/<name>.npy")
     ap.add_argument("--backend", type=int, default=-1, help="-1 library default, 0 unfused, 1 fused MFMA")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
@@ -50,7 +64,10 @@ def parse_args():
     ap.add_argument("--no-sustained", action="store_true", help="skip the 45 000 further steps of the offline_job leg (~3 s)")
     ap.add_argument("--objects-per-gpu", type=int, default=4,
             help="extra (not the headline): aggregate rate of K objects trained concurrently on one GPU; 0 = skip")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def spawn_ranks(args):
@@ -139,19 +156,50 @@ def main():
         obj.train(args.warmup)
         barrier(); sync()
         t0 = time.perf_counter()
-        obj.train(args.steps)              # K iterations enqueued on the object's HIP stream, one sync at the end
+        last_loss = obj.train(args.steps)  # K iterations enqueued on the object's HIP stream, one sync at the end
         sync(); barrier()
         dt_r = own_last = time.perf_counter() - t0
         if dist is not None:
             dt_r = sharding.max_over_ranks(dist, torch, dt_r, coll_dev)
         reps.append(dt_r)
     dt = median(reps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, obj, last_loss)
     cfg = obj.cfg; L = cfg.n_levels; B = cfg.rays_per_batch * cfg.n_samples
     value = world * args.steps * B / dt
     per_rank = None; rank_devices = [device]
     if dist is not None:                   # every rank's own last-repeat time (the headline uses the max over ranks) and the device it trained on
         t = torch.tensor([own_last, float(device)], dtype=torch.float64, device=coll_dev); outs = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(outs, t); per_rank = [round(args.steps * B / float(o[0].item()), 1) for o in outs]; rank_devices = [int(o[1].item()) for o in outs]
+    out = None
+    if rank == 0:
+        out = {"metric": "ray-samples/sec (train: hash-encode->MLP->composite fwd+bwd+optimizer) per object-NeRF", "value": round(value, 1),
+               "unit": "ray-samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4),
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "fp16 params/activations, fp32 accumulate + fp32 master",
+               "data": "synthetic",
+               "config": {"workload": "OfflineNeRF-style training, 1 synthetic 'room'-like object per GPU, base.json defaults (hash L=16 F=2 T=2^16, "
+                                      "MLP 64x1), "
+                                      "R=4096 rays x S=32 samples/step, %d views 640x480 resident in HBM%s" % (args.views,
+                                              (", T overridden to 2^%d" % args.log2_hashmap_size) if args.log2_hashmap_size else ""),
+                          "objects": world, "rays_per_step": cfg.rays_per_batch, "samples_per_ray": cfg.n_samples, "backend": obj_backend(pkg, obj),
+                          "parallelism": "object-per-GPU (no training collective; %s gather-to-root of the final render%s)" % (
+                              {"nccl": "RCCL", None: "RCCL"}.get(coll_backend, coll_backend), ", device-resident crops" if coll_backend == "nccl" else ""),
+                          "launcher": "self-spawned ranks" if os.environ.get("MON_BENCH_SPAWNED")
+                                       else ("torch.distributed.run" if world > 1 else "single process"),
+                          # what the collective itself says: ranks in the process group, its backend, devices visible to this rank
+                          "ranks_in_collective": (dist.get_world_size() if dist is not None else 1),
+                          "collective_backend": (dist.get_backend() if dist is not None else None), "visible_devices": ndev,
+                          "rank_devices": rank_devices},
+               "timed_region": "median of %d independent repeats; each repeat: fresh object, %d warm-up steps, %d timed steps from init, barrier + device sync "
+                               "on both sides, max over ranks" % (len(reps), args.warmup, args.steps),
+               "ms_per_step_repeats": [round(1e3 * r / args.steps, 4) for r in reps], "per_rank_ray_samples_per_s": per_rank}
+    if not args.full:
+        if out is not None:
+            print(json.dumps(out), flush=True)
+        obj.close(); ds.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # ---- roofline of the dominant kernel: HIP events on the kernel's own stream (the object's train stream) around every launch of
     # the SAME window (a fresh object, steps W..W+K from init), un-timed because the events cost ~37 us per step between the launches.
@@ -527,27 +575,7 @@ def main():
             stress = {"value": None, "note": "failed: %s" % e}
 
     if rank == 0:
-        out = {"metric": "ray-samples/sec (train: hash-encode->MLP->composite fwd+bwd+optimizer) per object-NeRF", "value": round(value, 1),
-               "unit": "ray-samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4),
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "fp16 params/activations, fp32 accumulate + fp32 master",
-               "data": "synthetic",
-               "config": {"workload": "OfflineNeRF-style training, 1 synthetic 'room'-like object per GPU, base.json defaults (hash L=16 F=2 T=2^16, "
-                                      "MLP 64x1), "
-                                      "R=4096 rays x S=32 samples/step, %d views 640x480 resident in HBM%s" % (args.views,
-                                              (", T overridden to 2^%d" % args.log2_hashmap_size) if args.log2_hashmap_size else ""),
-                          "objects": world, "rays_per_step": cfg.rays_per_batch, "samples_per_ray": cfg.n_samples, "backend": obj_backend(pkg, obj),
-                          "parallelism": "object-per-GPU (no training collective; %s gather-to-root of the final render%s)" % (
-                              {"nccl": "RCCL", None: "RCCL"}.get(coll_backend, coll_backend), ", device-resident crops" if coll_backend == "nccl" else ""),
-                          "launcher": "self-spawned ranks" if os.environ.get("MON_BENCH_SPAWNED")
-                                       else ("torch.distributed.run" if world > 1 else "single process"),
-                          # what the collective itself says: ranks in the process group, its backend, devices visible to this rank
-                          "ranks_in_collective": (dist.get_world_size() if dist is not None else 1),
-                          "collective_backend": (dist.get_backend() if dist is not None else None), "visible_devices": ndev,
-                          "rank_devices": rank_devices},
-               "timed_region": "median of %d independent repeats; each repeat: fresh object, %d warm-up steps, %d timed steps from init, barrier + device sync "
-                               "on both sides, max over ranks" % (len(reps), args.warmup, args.steps),
-               "ms_per_step_repeats": [round(1e3 * r / args.steps, 4) for r in reps], "per_rank_ray_samples_per_s": per_rank,
-               "roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_c1": cpu_c1, "gpu_c1": gpu_c1, "cpu_baseline_render": cpu_render,
+        out.update({"roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_c1": cpu_c1, "gpu_c1": gpu_c1, "cpu_baseline_render": cpu_render,
                "offline_job": offline_job,
                "late_training": late, "late_training_with_occupancy_skipping": occ, "multi_object": multi, "stress_T22": stress,
                "pcie_inclusive": {"dataset_upload_ms": round(1e3 * upload_s, 2), "dataset_bytes": int(sc.n_views * sc.H * sc.W * 4),
@@ -561,7 +589,7 @@ def main():
                "render": render_info, "psnr_db": [round(p, 2) for p in psnrs],
                "render_gather": ("ok" if gather_note is None else "FAILED (%s): psnr_db is rank 0's own crop" % gather_note) if dist is not None else None,
                "train_steps_before_render": (late["after_steps"] + 3 * args.steps) if late else args.warmup + args.steps,
-               "final_loss": round(obj.info().last_loss, 5)}
+               "final_loss": round(obj.info().last_loss, 5)})
         print(json.dumps(out), flush=True)
     obj.close(); ds.close()
     if dist is not None:
@@ -572,6 +600,26 @@ def main():
 
 def obj_backend(pkg, obj):
     return int(obj.info().backend)
+
+
+DUMP_BYTES = 64 * 10 ** 6 - 4096         # 64 MB in all, .npy headers included
+
+
+def dump_outputs(path, obj, loss):
+    """The timed path's outputs of its last step as <path>/<name>.npy (see the module docstring)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    widen = lambda bits: bits.view(np.float16).astype(np.float32)
+    params = {"params_master": obj.get_params(0), "params_half": widen(obj.get_params(1)), "params_ema": widen(obj.get_params(2))}
+    n = params["params_master"].size
+    if 4 * len(params) * n + 8 > DUMP_BYTES:
+        k = (DUMP_BYTES - 8) // (4 * len(params) + 8)          # + the float64 index of every sampled parameter
+        idx = np.unique(np.random.default_rng(0).integers(0, n, size=k))
+        params = {name: a[idx] for name, a in params.items()}
+        params["params_sample_index"] = idx.astype(np.float64)
+    np.save(os.path.join(path, "loss.npy"), np.array([loss], np.float64))
+    for name, a in params.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 if __name__ == "__main__":

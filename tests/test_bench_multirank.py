@@ -27,7 +27,7 @@ def _json_line(out):
 @pytest.mark.gpu
 def test_two_self_spawned_ranks_report_two_gpus_and_gather_both_crops(pkg):
     assert pkg.device_count() >= 1
-    small = ["--steps", "6", "--warmup", "2", "--repeats", "2", "--no-cpu-baseline", "--objects-per-gpu", "0", "--views", "12", "--no-sustained"]
+    small = ["--steps", "6", "--warmup", "2", "--repeats", "2", "--full", "--no-cpu-baseline", "--objects-per-gpu", "0", "--views", "12", "--no-sustained"]
     r2 = _run(["--gpus", "2"] + small)
     assert r2.returncode == 0, r2.stderr[-3000:]
     j2 = _json_line(r2.stdout)
@@ -58,7 +58,7 @@ def test_eight_self_spawned_ranks_run_the_drivers_n8_command_end_to_end(pkg):
     rank r -> device r mod the visible ones, gloo when they have to share a GPU), eight objects trained, eight crops gathered to rank 0, one JSON line
     whose config says what the collective itself reported -- its world size and backend, and the device every rank trained on."""
     assert pkg.device_count() >= 1
-    r = _run(["--gpus", "8", "--steps", "4", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--objects-per-gpu", "0", "--views", "8",
+    r = _run(["--gpus", "8", "--steps", "4", "--warmup", "2", "--repeats", "1", "--full", "--no-cpu-baseline", "--objects-per-gpu", "0", "--views", "8",
               "--no-sustained", "--no-stress"], timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _json_line(r.stdout)
@@ -82,7 +82,7 @@ def test_the_drivers_launcher_command_runs_two_ranks(pkg):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "MON_BENCH_DIST_BACKEND", "MON_BENCH_SPAWNED")}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--objects-per-gpu", "0",
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--repeats", "1", "--full", "--no-cpu-baseline", "--objects-per-gpu", "0",
            "--views", "8", "--no-sustained", "--no-stress"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -109,7 +109,7 @@ def test_a_gather_that_cannot_finish_does_not_take_the_bench_line_with_it(pkg):
     """The throughput is complete before the final render is gathered; a gather that hangs or fails (here: a deadline of zero seconds) must leave the JSON line,
     with the failure named in it and rank 0's own crop scored."""
     assert pkg.device_count() >= 1
-    r = _run(["--gpus", "2", "--steps", "6", "--warmup", "2", "--repeats", "2", "--no-cpu-baseline", "--objects-per-gpu", "0", "--views", "12"],
+    r = _run(["--gpus", "2", "--steps", "6", "--warmup", "2", "--repeats", "2", "--full", "--no-cpu-baseline", "--objects-per-gpu", "0", "--views", "12"],
             env={"MON_BENCH_GATHER_TIMEOUT": "0"})
     assert r.returncode == 0, r.stderr[-3000:]
     j = _json_line(r.stdout)

@@ -199,7 +199,7 @@ def test_online_manager_errors_without_device(pkg):
         m.init()
         with pytest.raises(pkg.MonError) as e:          # CreateNeRF before DatasetInit
             m.create_nerf(1, np.eye(4, dtype=np.float32).reshape(16), [-1, -1, -1], [1, 1, 1])
-        assert e.value.code == 4
+        assert e.value.code == 5                        # MON_ERR_STATE
     assert m.get_frame_idx("0.100000") == -1
     with pytest.raises(pkg.MonError):
         m.update_nerf_bbox(3, np.zeros((1, 5), np.uint32), 1)

@@ -55,7 +55,7 @@ def _worker(rank, world, port, q):
 
 def test_gather_to_root_with_four_ranks():
     """BASELINE configs[2]'s shape in small: more ranks than two, objects spread unevenly (5 objects over 4 ranks), both gathers of _worker (root 0, root 1)."""
-    import torch.multiprocessing as mp
+    import multiprocessing as mp                     # (torch itself only in the ranks: see _in_child_process in tests/test_oracle_kat.py)
     ctx = mp.get_context("spawn"); q = ctx.Queue(); port = _free_port(); world = 4
     ps = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
     for p in ps:
@@ -68,7 +68,7 @@ def test_gather_to_root_with_four_ranks():
 
 
 def test_round_robin_map_and_gather():
-    import torch.multiprocessing as mp
+    import multiprocessing as mp
     ctx = mp.get_context("spawn"); q = ctx.Queue(); port = _free_port(); world = 2
     ps = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
     for p in ps:

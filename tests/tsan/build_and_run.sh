@@ -5,7 +5,7 @@ set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"; REPO="$HERE/../.."
 OUT="${1:-/tmp/mon_tsan}"; mkdir -p "$OUT"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
-FLAGS=(--offload-host-only -fsanitize=thread -g -O1 -std=c++17 -fPIC -x hip -ffp-contract=off -fno-math-errno -w)
+FLAGS=(--offload-host-only -fsanitize=thread -fno-gpu-sanitize -g -O1 -std=c++17 -fPIC -x hip -ffp-contract=off -fno-math-errno -w)
 SRCS=(config.cpp model.cpp c_api.cpp manager.cpp png_io.cpp mesh.cpp kernels_batch.hip kernels_net.hip kernels_net_wide.hip kernels_net_deep.hip kernels_layers.hip kernels_composite.hip kernels_optim.hip kernels_fused.hip kernels_scatter.hip kernels_render.hip kernels_tilerender.hip kernels_encode.hip kernels_step.hip kernels_bigscatter.hip kernels_mesh.hip)
 pids=()
 for s in "${SRCS[@]}"; do "$HIPCC" "${FLAGS[@]}" -c "$REPO/ro-map_amd/csrc/$s" -o "$OUT/${s%.*}.o" & pids+=($!); done
@@ -16,7 +16,7 @@ for p in "${pids[@]}"; do wait "$p"; done
 gcc -c "$OUT/fatbin_syms.c" -o "$OUT/fatbin_syms.o"
 objs=(); for s in "${SRCS[@]}"; do objs+=("$OUT/${s%.*}.o"); done
 clang=/opt/rocm/lib/llvm/bin/clang++
-"$clang" -fsanitize=thread -g -O1 -std=c++17 "$HERE/tsan_driver.cpp" "${objs[@]}" "$OUT/hip_stub.o" "$OUT/fatbin_syms.o" -o "$OUT/tsan_driver" -lz -lpthread -ldl
+"$clang" -fsanitize=thread -fno-gpu-sanitize -g -O1 -std=c++17 "$HERE/tsan_driver.cpp" "${objs[@]}" "$OUT/hip_stub.o" "$OUT/fatbin_syms.o" -o "$OUT/tsan_driver" -lz -lpthread -ldl
 cd "$REPO"
 set +e
 TSAN_OPTIONS="halt_on_error=0 exitcode=66 report_signal_unsafe=0" "$OUT/tsan_driver" ro-map_amd/configs/base.json 2> "$OUT/tsan.log" | tail -3
