@@ -165,6 +165,29 @@ typedef struct mon_render_skip_stats {
 int mon_object_render_skip_stats(mon_object* obj, int side, mon_render_skip_stats* out);
 /* The grid of the side's last skipping render: 64^3 bits, x fastest, 8192 words.  dilated = 0: before dilation.  MON_ERR_STATE before the first one. */
 int mon_object_render_occupancy(mon_object* obj, int side, int dilated, uint32_t* bits);
+/* Scene render: several objects of one device seen from one camera, composited in depth order (the reference has no such call; opt-in, new).
+ * For every pixel ray of rect (x, y, w, h; FrameId ignored) under Twc16 (column-major), each object contributes exactly the samples its own render of
+ * the same rect and pose takes: the same ray, the same 2S jittered distances t (its own sample_seed), the same alpha and colour, its render grid when
+ * render skipping is on (a dead sample has alpha 0 and colour 0).  t is the distance along the unit world ray, so the samples of all objects the ray
+ * hits are merged by t (ties: the lower index in objs) and composited front to back: w_i = alpha_i * T_i, T_0 = 1, T_{i+1} = T_i (1 - alpha_i);
+ * the first sample with T_i < 1e-4 and everything behind it get weight 0.  Outputs, h*w each (rgb 3*h*w), host pointers:
+ *   rgb      = sum w_i c_i + T_end (soft, white background, not binarised)
+ *   depth    = sum w_i t_i / |camera ray| (z-depth, as mon_object_render) where opacity > 0.5, else 0
+ *   opacity  = 1 - T_end                                                    (may be NULL)
+ *   instance = index in objs of the object with the largest summed weight where opacity > 0.5, else -1   (may be NULL)
+ * A pixel that hits no box: rgb 1, depth 0, opacity 0, instance -1.  With one object, on pixels where its own render has mask 1, rgb and depth are that
+ * render's values and instance is 0.
+ * side 0: the objects' train-side weights (EMA once trained), on the first object's train stream -- the caller serialises against the objects' training,
+ *         as for mon_object_render;
+ * side 1: each object's last published snapshot on the device's inference stream -- callable while the objects train, as mon_object_render_snapshot.
+ * Render grids: each object's own cache of that side (built here when stale; counted in its grid_builds); the objects' skip statistics are left as they
+ * were.  Returns:
+ *   MON_ERR_ARG    objs or an element, Twc16, rgb or depth NULL; n_objs 0 or above 256; rect empty; side not 0 / 1; objects on different logical devices
+ *                  or with different intrinsics
+ *   MON_ERR_STATE  an object outside the fused shapes (the layer-kernel backend); an object in the XORWOW "same inputs" render mode (rng_flags
+ *                  sample-stream bits); side 1 and an object without an inference side or with nothing published yet */
+int mon_scene_render(mon_object* const* objs, size_t n_objs, int side, mon_frame_bbox rect, const float* Twc16,
+                     float* rgb, float* depth, float* opacity, int32_t* instance);
 /* NeRF_Model::GetDensityOnGrid (nerf_model.cu:2007-2048): raw density channel on an rx*ry*rz lattice. */
 int mon_object_density_grid(mon_object* obj, int rx, int ry, int rz, float* out_host);
 
@@ -263,6 +286,9 @@ int mon_online_wait_threads_end(mon_online* mgr);                               
 int mon_online_object_info(mon_online* mgr, size_t idx, float* loss, int* train_calls, int* device, uint32_t* n_boxes);
 /* one view of RenderNeRFsTest */
 int mon_online_render(mon_online* mgr, size_t idx, mon_frame_bbox box, const float* Twc16, float* rgb, float* depth, float* mask);
+/* mon_scene_render(side 1) of every object of the manager that has published weights (the others are left out; none: the background); instance = the
+ * manager's object index.  A viewer's call: safe while the objects train.  MON_ERR_STATE when those objects span more than one device (a follow-up). */
+int mon_online_render_scene(mon_online* mgr, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity, int32_t* instance);
 /* RenderNeRFsTest(out_path, idx, stamps, boxes, Twcs, radius) -> NeRF::RenderTestImg (nerf.cu:255-404): test images + test.txt +
  * train.txt + the 60-view 360-degree video (RenderVideo, nerf_model.cu:1832-1990) + obj.ply under <out_path>/<id>/ */
 int mon_online_render_nerfs_test(mon_online* mgr, const char* out_path, size_t idx, const char* const* timestamps, const mon_frame_bbox* boxes,

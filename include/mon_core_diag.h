@@ -43,6 +43,16 @@ int mon_debug_render_jobs(mon_object* obj, int side, uint32_t* jobs);
  * builds, until called again with bits = NULL.  The tests check the renders' cell look-up against geometry through it. */
 int mon_debug_set_render_grid(mon_object* obj, int side, const uint32_t* bits);
 
+/* Scene render (mon_scene_render), its two kernels one at a time.  mon_debug_scene_samples: object k's sample lists of the scene render of rect (the same
+ * arguments), host arrays per pixel of the rect (row-major): t[64], alpha[64], rgb[64][3] and count (0: the ray missed the box; else 32 or 64, the slots
+ * written).  Any output may be NULL.  mon_debug_scene_composite: the merge-composite kernel on caller lists, n_lists x n_rays lists of up to 64 samples,
+ * ascending in t: t[n_lists][n_rays][64], alpha the same, rgb[n_lists][n_rays][64][3], count[n_lists][n_rays] (<= 64); dn[n_rays] = the camera ray norms
+ * the depth is divided by.  Outputs as mon_scene_render's, instance = list index.  n_lists <= 256. */
+int mon_debug_scene_samples(mon_object* const* objs, size_t n_objs, int side, mon_frame_bbox rect, const float* Twc16, size_t k, float* t, float* alpha,
+                            float* rgb, uint32_t* count);
+int mon_debug_scene_composite(int device, uint32_t n_rays, uint32_t n_lists, const float* t, const float* alpha, const float* rgb, const uint32_t* count,
+                              const float* dn, float* out_rgb, float* out_depth, float* out_opacity, int32_t* out_instance);
+
 #ifdef __cplusplus
 }
 #endif

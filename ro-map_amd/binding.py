@@ -128,6 +128,8 @@ _SIGS = {
     "mon_object_set_render_skip": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "mon_object_render_skip_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(MonRenderSkipStats)]),
     "mon_object_render_occupancy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "mon_scene_render": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, MonBBox, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_online_render_scene": (C.c_int, [C.c_void_p, MonBBox, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -144,6 +146,9 @@ _DIAG_SIGS = {
     "mon_debug_render_jobs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32)]),
     "mon_debug_occupancy_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "mon_debug_set_render_grid": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "mon_debug_scene_samples": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, MonBBox, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_debug_scene_composite": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -690,9 +695,54 @@ class OnlineManager:
         pose = np.ascontiguousarray(Twc16, np.float32)
         _check(lib().mon_online_render(self.h, idx, MonBBox(FrameId, x, y, h, w), _p(pose), _p(rgb), _p(depth), _p(mask))); return rgb, depth, mask
 
+    def render_scene(self, rect, Twc16):
+        """mon_online_render_scene: every object with published weights composited in depth order (a viewer's call, safe while they train);
+        returns (rgb, depth, opacity, instance = the manager's object index or -1)."""
+        box, out = _scene_outputs(rect); pose = np.ascontiguousarray(Twc16, np.float32)
+        _check(lib().mon_online_render_scene(self.h, box, _p(pose), *[_p(a) for a in out]))
+        return out
+
     def close(self):
         if self.h:
             lib().mon_online_destroy(self.h); self.h = None
+
+
+def _scene_outputs(rect):
+    FrameId, x, y, h, w = (int(v) for v in rect)
+    return MonBBox(FrameId, x, y, h, w), (np.empty((h, w, 3), np.float32), np.empty((h, w), np.float32), np.empty((h, w), np.float32),
+                                          np.empty((h, w), np.int32))
+
+
+def _handles(objects):
+    return (C.c_void_p * len(objects))(*[o.h for o in objects])
+
+
+def render_scene(objects, rect, Twc16, side=0):
+    """mon_scene_render: the objects (one device, one set of intrinsics) composited in depth order over rect = (FrameId, x, y, h, w) seen from Twc16;
+    side 0 the train-side weights, 1 the published snapshots.  Returns (rgb HxWx3, depth HxW, opacity HxW, instance HxW int32: index into objects, -1)."""
+    box, out = _scene_outputs(rect); pose = np.ascontiguousarray(Twc16, np.float32)
+    _check(lib().mon_scene_render(_handles(objects), len(objects), int(side), box, _p(pose), *[_p(a) for a in out]))
+    return out
+
+
+def scene_samples(objects, rect, Twc16, k, side=0):
+    """mon_debug_scene_samples: object k's sample lists of that scene render, per pixel: t (h, w, 64), alpha (h, w, 64), rgb (h, w, 64, 3), count (h, w)."""
+    FrameId, x, y, h, w = (int(v) for v in rect); pose = np.ascontiguousarray(Twc16, np.float32)
+    t = np.empty((h, w, 64), np.float32); a = np.empty_like(t); c = np.empty((h, w, 64, 3), np.float32); n = np.empty((h, w), np.uint32)
+    _check(diag_lib().mon_debug_scene_samples(_handles(objects), len(objects), int(side), MonBBox(FrameId, x, y, h, w), _p(pose), int(k), _p(t), _p(a),
+                                              _p(c), _p(n)))
+    return t, a, c, n
+
+
+def scene_composite(t, alpha, rgb, count, dn, device=0):
+    """mon_debug_scene_composite: the merge-composite kernel on lists t / alpha (n_lists, n_rays, 64), rgb (n_lists, n_rays, 64, 3), count (n_lists,
+    n_rays), dn (n_rays,).  Returns (rgb (n_rays, 3), depth, opacity, instance)."""
+    t = np.ascontiguousarray(t, np.float32); L, R = t.shape[:2]
+    a = np.ascontiguousarray(alpha, np.float32).reshape(L, R, 64); c = np.ascontiguousarray(rgb, np.float32).reshape(L, R, 64, 3)
+    n = np.ascontiguousarray(count, np.uint32).reshape(L, R); d = np.ascontiguousarray(dn, np.float32).reshape(R)
+    o_rgb = np.empty((R, 3), np.float32); o_d = np.empty(R, np.float32); o_o = np.empty(R, np.float32); o_i = np.empty(R, np.int32)
+    _check(diag_lib().mon_debug_scene_composite(int(device), R, L, _p(t), _p(a), _p(c), _p(n), _p(d), _p(o_rgb), _p(o_d), _p(o_o), _p(o_i)))
+    return o_rgb, o_d, o_o, o_i
 
 
 def _borrowed_object(handle):

@@ -1,5 +1,6 @@
 // c_api.cpp -- extern "C" surface declared in include/mon_core.h.
 #include <cstring>
+#include <vector>
 #include "model.h"
 #include "frag_layout.h"
 
@@ -110,6 +111,14 @@ int mon_object_render_skip_stats(mon_object* o, int side, mon_render_skip_stats*
     return model_render_skip_stats(*o->m, side, out); }
 int mon_object_render_occupancy(mon_object* o, int side, int dilated, uint32_t* bits) { REQUIRE(o, "object"); REQUIRE(bits, "bits");
     return model_render_occupancy(*o->m, side, dilated, bits); }
+int mon_scene_render(mon_object* const* objs, size_t n_objs, int side, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity,
+        int32_t* instance) {
+    REQUIRE(objs, "objs"); REQUIRE(Twc16, "Twc16"); REQUIRE(rgb, "rgb"); REQUIRE(depth, "depth");
+    if (n_objs == 0 || rect.w == 0 || rect.h == 0) { set_error("scene_render: empty object list or rect"); return MON_ERR_ARG; }
+    std::vector<Model*> ms(n_objs);
+    for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
+    return scene_render(ms.data(), n_objs, side, rect, Twc16, rgb, depth, opacity, instance, nullptr, nullptr);
+}
 int mon_object_density_grid(mon_object* o, int rx, int ry, int rz, float* out_host) { REQUIRE(o, "object");
     return model_density_grid(*o->m, rx, ry, rz, out_host); }
 int mon_object_get_config(mon_object* o, mon_config* cfg) { REQUIRE(o, "object"); REQUIRE(cfg, "cfg"); *cfg = o->m->cfg; return MON_OK; }

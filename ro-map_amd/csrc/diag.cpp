@@ -181,6 +181,49 @@ int mon_debug_render_jobs(mon_object* o, int side, uint32_t* jobs) {
 }
 int mon_debug_set_render_grid(mon_object* o, int side, const uint32_t* bits) { REQUIRE(o, "object");
     return mon::model_debug_set_render_grid(*o->m, side, bits); }
+int mon_debug_scene_samples(mon_object* const* objs, size_t n_objs, int side, mon_frame_bbox rect, const float* Twc16, size_t k, float* t, float* alpha,
+                            float* rgb, uint32_t* count) {
+    REQUIRE(objs, "objs"); REQUIRE(Twc16, "Twc16");
+    if (n_objs == 0 || k >= n_objs || rect.w == 0 || rect.h == 0) { set_error("debug_scene_samples: empty list or rect, or k out of range"); return MON_ERR_ARG; }
+    std::vector<mon::Model*> ms(n_objs);
+    for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
+    const size_t px = (size_t)rect.w * rect.h; std::vector<float> img(3 * px), dep(px);
+    const mon::SceneDump dump{ (uint32_t)k, t, alpha, rgb, count };
+    return mon::scene_render(ms.data(), n_objs, side, rect, Twc16, img.data(), dep.data(), nullptr, nullptr, nullptr, &dump);
+}
+int mon_debug_scene_composite(int device, uint32_t n_rays, uint32_t n_lists, const float* t, const float* alpha, const float* rgb, const uint32_t* count,
+                              const float* dn, float* out_rgb, float* out_depth, float* out_opacity, int32_t* out_instance) {
+    REQUIRE(t, "t"); REQUIRE(alpha, "alpha"); REQUIRE(rgb, "rgb"); REQUIRE(count, "count"); REQUIRE(dn, "dn"); REQUIRE(out_rgb, "out_rgb");
+    REQUIRE(out_depth, "out_depth"); REQUIRE(out_opacity, "out_opacity"); REQUIRE(out_instance, "out_instance");
+    if (n_rays == 0 || n_lists == 0 || n_lists > mon::kSceneMaxLists) { set_error("debug_scene_composite: %u rays, %u lists", n_rays, n_lists);
+        return MON_ERR_ARG; }
+    const size_t nl = (size_t)n_lists * n_rays, ns = nl * mon::kSceneListLen;
+    for (size_t i = 0; i < nl; ++i) if (count[i] > mon::kSceneListLen) { set_error("debug_scene_composite: count %u > 64", count[i]); return MON_ERR_ARG; }
+    std::vector<float> attr(4 * ns);
+    for (size_t i = 0; i < ns; ++i) { attr[4 * i] = alpha[i]; attr[4 * i + 1] = rgb[3 * i]; attr[4 * i + 2] = rgb[3 * i + 1]; attr[4 * i + 3] = rgb[3 * i + 2]; }
+    HIPCHECK(mon::use_device(device));
+    char* d = nullptr; const size_t b_t = ns * 4, b_a = ns * 16, b_c = nl * 4, b_dn = (size_t)n_rays * 4, b_out = (size_t)n_rays * 24;
+    HIPCHECK(hipMalloc((void**)&d, b_t + b_a + b_c + b_dn + b_out));
+    float* d_t = (float*)d; float* d_a = (float*)(d + b_t); uint32_t* d_c = (uint32_t*)(d + b_t + b_a); float* d_dn = (float*)(d + b_t + b_a + b_c);
+    float* d_out = (float*)(d + b_t + b_a + b_c + b_dn);
+    hipError_t e = hipMemcpy(d_t, t, b_t, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_a, attr.data(), b_a, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_c, count, b_c, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_dn, dn, b_dn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        mon::launch_scene_composite(nullptr, n_rays, n_lists, n_rays, d_t, d_a, d_c, d_dn, d_out, d_out + 3 * (size_t)n_rays, d_out + 4 * (size_t)n_rays,
+                reinterpret_cast<int32_t*>(d_out + 5 * (size_t)n_rays));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    std::vector<float> out(6 * (size_t)n_rays);
+    if (e == hipSuccess) e = hipMemcpy(out.data(), d_out, b_out, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIPCHECK(e);
+    std::memcpy(out_rgb, out.data(), 12 * (size_t)n_rays); std::memcpy(out_depth, out.data() + 3 * (size_t)n_rays, 4 * (size_t)n_rays);
+    std::memcpy(out_opacity, out.data() + 4 * (size_t)n_rays, 4 * (size_t)n_rays); std::memcpy(out_instance, out.data() + 5 * (size_t)n_rays, 4 * (size_t)n_rays);
+    return MON_OK;
+}
 int mon_debug_yaml_number(const char* text, const char* key, double* value) {
     REQUIRE(text, "text"); REQUIRE(key, "key"); REQUIRE(value, "value");
     if (!read_yaml_number(text, key, *value)) { set_error("config.yaml: %s missing or not a number", key); return MON_ERR_IO; }

@@ -11,7 +11,11 @@ namespace mon {
 // OCC (empty-space skipping of the render, opt-in per object; a.occ_bits = the render's grid): a sample in a dead cell issues no gathers and contributes
 // what a sample of alpha 0 contributes -- its alpha and colour are SELECTED to 0, its interval is the one it always had; a tile with no live sample
 // is skipped whole (no MLP, Tc unchanged, tlast = the tile's last t).  stats[0] += the ray's samples in live cells, stats[1] += 2S per ray in the box.
-template <int EPAD, int W, int NH, bool OCC = false>
+// EMIT (the scene render, mon_scene_render): nothing is composited; the ray's samples go out as a list for k_scene_composite.  The pointers change meaning:
+// rgb = t [ray][2S], depth = {alpha, r, g, b} [ray][2S] (float4), stats = the ray's sample count [ray] (0: missed the box; 32 per tile evaluated); mask is
+// unused.  The list stops where THIS object's transmittance ends the ray (the scene's is never larger).  A dead tile is emitted with alpha 0 and colour 0.
+// The skip counters are not touched.
+template <int EPAD, int W, int NH, bool OCC = false, bool EMIT = false>
 __global__ void __launch_bounds__(256) k_fused_render(FusedArgs a, uint32_t n_rays, uint32_t idx_base, float* __restrict__ rgb, float* __restrict__ depth,
         float* __restrict__ mask, uint32_t* __restrict__ stats) {
     using S = FusedShape<EPAD, W, NH>;
@@ -28,6 +32,7 @@ __global__ void __launch_bounds__(256) k_fused_render(FusedArgs a, uint32_t n_ra
     uint32_t n_live = 0u, n_box = 0u;                                                  // (OCC: this wave's counts, one atomic each at the end)
     for (uint32_t ray = blockIdx.x * S::WAVES + wave; ray < n_rays; ray += gridDim.x * S::WAVES) {
         float o0 = 1.f, o1 = 1.f, o2 = 1.f, od = 0.f, om_ = 0.f;
+        uint32_t n_emit = 0u;                                                           // (EMIT) samples written for this ray
         if (a.b.ray_flag[ray]) {
             const float t0 = a.b.ray_t0[ray], t1 = a.b.ray_t1[ray], dtr = (t1 - t0) / (float)S2;
             float Tc = 1.f, r0 = 0.f, r1 = 0.f, r2 = 0.f, dep = 0.f, tlast = 0.f;
@@ -56,7 +61,13 @@ __global__ void __launch_bounds__(256) k_fused_render(FusedArgs a, uint32_t n_ra
                 for (int d = 0; d < 3; ++d) { const float p = fmaf(t, a.b.ray_d[3 * ray + d], a.b.ray_o[3 * ray + d]);
                     x[d] = (p - a.oc.aabb.mn[d]) / (a.oc.aabb.mx[d] - a.oc.aabb.mn[d]); }
                 const uint32_t lw = tile ? lb1 : lb0;
-                if (OCC && lw == 0u) { tlast = lane_bcast(t, 31); continue; }           // a dead tile: alpha 0 everywhere, Tc unchanged
+                if (OCC && lw == 0u) {                                                  // a dead tile: alpha 0 everywhere, Tc unchanged
+                    if constexpr (EMIT) {
+                        if (lane < 32) { rgb[(size_t)ray * S2 + k] = t; reinterpret_cast<float4*>(depth)[(size_t)ray * S2 + k] = make_float4(0.f, 0.f, 0.f, 0.f); }
+                        n_emit += 32u;
+                    }
+                    tlast = lane_bcast(t, 31); continue;
+                }
                 const bool live = !OCC || ((lw >> n) & 1u) != 0u;
                 TileState<EPAD, W, NH> ts;
                 if constexpr (OCC) {                                                    // dead lanes issue no gathers: their features are 0
@@ -71,6 +82,10 @@ __global__ void __launch_bounds__(256) k_fused_render(FusedArgs a, uint32_t n_ra
                             c2 = OCC && !live ? 0.f : logistic_f(ts.out4[2]);                 // (selects)
                 float tprev = lane_prev(t, tlast); if (n == 0) tprev = tlast;
                 const float alpha = OCC && !live ? 0.f : 1.f - __expf(-sigma * (t - tprev)), omv = 1.f - alpha;
+                if constexpr (EMIT) {
+                    if (lane < 32) { rgb[(size_t)ray * S2 + k] = t; reinterpret_cast<float4*>(depth)[(size_t)ray * S2 + k] = make_float4(alpha, c0, c1, c2); }
+                    n_emit += 32u;
+                }
                 const float tincl = scan_mul32(omv) * Tc;
                 float T = lane_prev(tincl, Tc); if (n == 0) T = Tc;
                 const bool active = T >= kTransmittanceEps;
@@ -83,9 +98,10 @@ __global__ void __launch_bounds__(256) k_fused_render(FusedArgs a, uint32_t n_ra
             }
             if (1.f - Tc > 0.5f) { o0 = r0 + Tc; o1 = r1 + Tc; o2 = r2 + Tc; od = dep / a.b.ray_dn[ray]; om_ = 1.f; }      // :1213-1220
         }
-        if (lane == 0) { rgb[3 * ray] = o0; rgb[3 * ray + 1] = o1; rgb[3 * ray + 2] = o2; depth[ray] = od; mask[ray] = om_; }
+        if constexpr (EMIT) { if (lane == 0) stats[ray] = n_emit; }
+        else if (lane == 0) { rgb[3 * ray] = o0; rgb[3 * ray + 1] = o1; rgb[3 * ray + 2] = o2; depth[ray] = od; mask[ray] = om_; }
     }
-    if constexpr (OCC) if (lane == 0 && n_box) { atomicAdd(stats, n_live); atomicAdd(stats + 1, n_box); }
+    if constexpr (OCC && !EMIT) if (lane == 0 && n_box) { atomicAdd(stats, n_live); atomicAdd(stats + 1, n_box); }
 }
 
 // ------------------------------------------------------------------ occupancy grid (N1: forward-pass skipping, default off)
@@ -152,6 +168,128 @@ static void fused_render_t(hipStream_t s, const FusedArgs& a, uint32_t n_rays, u
     else hipLaunchKernelGGL((k_fused_render<EPAD, W, NH>), dim3(grid), dim3(256), smem, s, a, n_rays, idx_base, rgb, depth, mask, stats);
 }
 
+template <int EPAD, int W, int NH>
+static void fused_emit_t(hipStream_t s, const FusedArgs& a, uint32_t n_rays, uint32_t idx_base, float* t, float* attr, uint32_t* cnt) {
+    using S = FusedShape<EPAD, W, NH>;
+    const uint32_t smem = S::FRAG_BYTES + S::LT_BYTES;
+    uint32_t grid = (n_rays + 3) / 4; if (grid > 2048u) grid = 2048u;
+    if (a.keep_zero & 1u) hipLaunchKernelGGL((k_build_frag_image<EPAD, W, NH>), dim3((S::F_WOT * 512 + 255) / 256), dim3(256), 0, s, a.params, a.nd.L,
+            const_cast<uint16_t*>(a.frag_image), (const DevState*)nullptr);
+    if (a.occ_bits) hipLaunchKernelGGL((k_fused_render<EPAD, W, NH, true, true>), dim3(grid), dim3(256), smem, s, a, n_rays, idx_base, t, attr, nullptr, cnt);
+    else hipLaunchKernelGGL((k_fused_render<EPAD, W, NH, false, true>), dim3(grid), dim3(256), smem, s, a, n_rays, idx_base, t, attr, nullptr, cnt);
+}
+
+// ------------------------------------------------------------------ scene render: merge-composite of the objects' sample lists
+// One wavefront (= one workgroup) per pixel ray.  List k of the ray holds cnt[k * cap + ray] samples (<= 2S, ascending in t) at (k * cap + ray) * 2S:
+// t in `tl`, {alpha, r, g, b} in `attr`.  The ray's non-empty lists are compacted into LDS with their first and last t; every sample's place in the merged
+// order is counted: its index in its own list + the samples of each other list that come before it (ties to the lower list index) -- the whole list or
+// none where the t ranges do not overlap (always the case for disjoint boxes), a binary search of that list where they do.  The merged order (list, index)
+// goes to LDS, and the sequence is composited front to back in blocks of 64 with a carried transmittance.  Each half-wave scans its 32 samples as
+// k_fused_render scans a tile, and the sums are added half by half, so one object's list composites to exactly that render's arithmetic.  Per-list weight
+// sums (one wave reduction per list present in a block) give the instance.
+__global__ void __launch_bounds__(64) k_scene_composite(uint32_t n_rays, uint32_t n_lists, uint32_t cap, const float* __restrict__ tl,
+        const float4* __restrict__ attr, const uint32_t* __restrict__ cnt, const float* __restrict__ dn, float* __restrict__ out_rgb,
+        float* __restrict__ out_depth, float* __restrict__ out_opacity, int32_t* __restrict__ out_instance) {
+    constexpr uint32_t L2S = kSceneListLen;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint16_t* s_perm = reinterpret_cast<uint16_t*>(smem);                             // [L2S * n_lists] merged order: compact list << 6 | index
+    uint32_t* s_id = reinterpret_cast<uint32_t*>(smem + 2u * L2S * n_lists);          // [n_lists] compact list -> list
+    uint32_t* s_c = s_id + n_lists;                                                    // its count
+    float* s_tf = reinterpret_cast<float*>(s_c + n_lists);                             // its first t
+    float* s_tl = s_tf + n_lists;                                                      // its last t
+    float* s_w = s_tl + n_lists;                                                       // its summed weight
+    const int lane = threadIdx.x;
+    for (uint32_t ray = blockIdx.x; ray < n_rays; ray += gridDim.x) {
+        // ---- the ray's non-empty lists, in list order
+        uint32_t na = 0u, n_tot = 0u;
+        for (uint32_t g = 0; g < n_lists; g += 64u) {
+            const uint32_t k = g + (uint32_t)lane;
+            uint32_t c = k < n_lists ? cnt[(size_t)k * cap + ray] : 0u;
+            c = c < L2S ? c : L2S;
+            const unsigned long long b = __ballot(c > 0u);
+            if (c > 0u) {
+                const uint32_t pos = na + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+                const float* q = tl + ((size_t)k * cap + ray) * L2S;
+                s_id[pos] = k; s_c[pos] = c; s_tf[pos] = q[0]; s_tl[pos] = q[c - 1u]; s_w[pos] = 0.f;
+            }
+            na += (uint32_t)__popcll(b);
+            n_tot += (uint32_t)__builtin_amdgcn_readlane((int)scan_add64_u32(c), 63);
+        }
+        __syncthreads();
+        // ---- merged order: rank of every sample
+        for (uint32_t a = 0; a < na; ++a) {
+            const uint32_t c = s_c[a];
+            if ((uint32_t)lane < c) {
+                const float tv = tl[((size_t)s_id[a] * cap + ray) * L2S + lane];
+                uint32_t r = (uint32_t)lane;
+                for (uint32_t b = 0; b < na; ++b) {
+                    if (b == a) continue;
+                    const bool first = b < a;                                          // (list b's samples at an equal t come first)
+                    const uint32_t cb = s_c[b];
+                    const float lb = s_tl[b], fb = s_tf[b];
+                    if (first ? lb <= tv : lb < tv) r += cb;                           // all of list b is in front
+                    else if (first ? fb <= tv : fb < tv) {                             // part of it: count (binary search; the last one is not in front)
+                        const float* q = tl + ((size_t)s_id[b] * cap + ray) * L2S;
+                        uint32_t pos = 0u;
+                        for (uint32_t step = L2S / 2u; step; step >>= 1)
+                            if (pos + step <= cb) { const float v = q[pos + step - 1u]; if (first ? v <= tv : v < tv) pos += step; }
+                        r += pos;
+                    }
+                }
+                s_perm[r] = (uint16_t)((a << 6) | (uint32_t)lane);                     // (r <= n_tot - 1 whatever the lists hold)
+            }
+        }
+        __syncthreads();
+        // ---- front-to-back composite of the merged sequence
+        float Tc = 1.f, r0 = 0.f, r1 = 0.f, r2 = 0.f, dep = 0.f;
+        for (uint32_t base = 0; base < n_tot; base += 64u) {
+            const uint32_t p = base + (uint32_t)lane;
+            float tv = 0.f, al = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f; uint32_t a = ~0u;
+            if (p < n_tot) {
+                const uint32_t e = s_perm[p];
+                if ((e >> 6) < na) {
+                    a = e >> 6;
+                    const size_t idx = ((size_t)s_id[a] * cap + ray) * L2S + (e & 63u);
+                    const float4 v = attr[idx]; tv = tl[idx]; al = v.x; c0 = v.y; c1 = v.z; c2 = v.w;
+                }
+            }
+            const float omv = 1.f - al;
+            const float sc = scan_mul32(omv), lo = sc * Tc, mid = lane_bcast(lo, 31);
+            const float incl = lane < 32 ? lo : sc * mid;                              // (the second half-wave carries the first's transmittance)
+            float T = lane_prev(incl, Tc); if (lane == 0) T = Tc; if (lane == 32) T = mid;
+            const bool active = T >= kTransmittanceEps;
+            const unsigned long long am = __ballot(active);
+            const int nact = __popcll(am);
+            const float wgt = active ? al * T : 0.f;
+            const float x0 = scan_add32(wgt * c0), x1 = scan_add32(wgt * c1), x2 = scan_add32(wgt * c2), xd = scan_add32(wgt * tv);
+            r0 += lane_bcast(x0, 31); r1 += lane_bcast(x1, 31); r2 += lane_bcast(x2, 31); dep += lane_bcast(xd, 31);
+            r0 += lane_bcast(x0, 63); r1 += lane_bcast(x1, 63); r2 += lane_bcast(x2, 63); dep += lane_bcast(xd, 63);
+            // per-list weight sums: one reduction per list present in the block
+            unsigned long long pend = __ballot(a != ~0u && wgt != 0.f);
+            while (pend) {
+                const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)a, (int)__builtin_ctzll(pend));
+                const bool mine = a == a0;
+                const float xs = scan_add32(mine ? wgt : 0.f);
+                const float sum = lane_bcast(xs, 31) + lane_bcast(xs, 63);
+                if (lane == 0) s_w[a0] += sum;
+                pend &= ~__ballot(mine);
+            }
+            Tc = nact > 0 ? lane_bcast(incl, nact > 0 ? nact - 1 : 0) : Tc;
+            if (nact < 64) break;                                                      // transmittance ran out inside this block
+        }
+        if (lane == 0) {
+            const float op = 1.f - Tc;
+            out_rgb[3 * (size_t)ray] = r0 + Tc; out_rgb[3 * (size_t)ray + 1] = r1 + Tc; out_rgb[3 * (size_t)ray + 2] = r2 + Tc;
+            out_depth[ray] = op > 0.5f ? dep / dn[ray] : 0.f;
+            out_opacity[ray] = op;
+            int32_t inst = -1;
+            if (op > 0.5f) { float best = -1.f; for (uint32_t a = 0; a < na; ++a) if (s_w[a] > best) { best = s_w[a]; inst = (int32_t)s_id[a]; } }
+            out_instance[ray] = inst;
+        }
+        __syncthreads();
+    }
+}
+
 
 void launch_fused_render(hipStream_t s, const LevelFast& lt, const NetDims& nd, const uint16_t* params, const BatchPtrs& b, const ObjectConst& oc,
         uint32_t n_rays, uint32_t idx_base, float* rgb, float* depth, float* mask, uint16_t* frag_image, int build_image, const RenderSkipArgs& skip) {
@@ -159,6 +297,22 @@ void launch_fused_render(hipStream_t s, const LevelFast& lt, const NetDims& nd, 
     FusedArgs a{ lt, nd, oc, b, params, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, frag_image, build_image ? 1u : 0u };
     a.occ_bits = skip.bits;
     MON_FUSED_DISPATCH(fused_render_t, s, a, n_rays, idx_base, rgb, depth, mask, skip.stats);
+}
+
+
+void launch_fused_render_emit(hipStream_t s, const LevelFast& lt, const NetDims& nd, const uint16_t* params, const BatchPtrs& b, const ObjectConst& oc,
+        uint32_t n_rays, uint32_t idx_base, float* t, float* attr, uint32_t* cnt, uint16_t* frag_image, int build_image, const uint32_t* skip_bits) {
+    FusedArgs a{ lt, nd, oc, b, params, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, frag_image, build_image ? 1u : 0u };
+    a.occ_bits = skip_bits;
+    MON_FUSED_DISPATCH(fused_emit_t, s, a, n_rays, idx_base, t, attr, cnt);
+}
+
+void launch_scene_composite(hipStream_t s, uint32_t n_rays, uint32_t n_lists, uint32_t cap, const float* t, const float* attr, const uint32_t* cnt,
+        const float* dn, float* rgb, float* depth, float* opacity, int32_t* instance) {
+    if (!n_rays || !n_lists || n_lists > kSceneMaxLists) return;
+    const uint32_t grid = n_rays < 8192u ? n_rays : 8192u;
+    hipLaunchKernelGGL(k_scene_composite, dim3(grid), dim3(64), scene_composite_lds(n_lists), s, n_rays, n_lists, cap, t,
+            reinterpret_cast<const float4*>(attr), cnt, dn, rgb, depth, opacity, instance);
 }
 
 

@@ -5,6 +5,7 @@
 // One std::thread per object, object k on device k mod nGPU (nerf.cu:27-33), one dataset replica per device.
 #include <sys/stat.h>
 #include <unistd.h>
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <condition_variable>
@@ -643,6 +644,23 @@ int mon_online_render(mon_online* h, size_t idx, mon_frame_bbox box, const float
     if (model_render_snapshot(*o->model, box, Twc16, 0, rgb, depth, mask, nullptr) == MON_OK) return MON_OK;
     AnnouncedLock lm(o, o->mu_model);         // nothing published yet / no inference side: let in between two slices of a running training step
     return model_render(*o->model, box, Twc16, 0, rgb, depth, mask, 0);
+}
+// the map seen from a camera: every object with published weights, composited in depth order from the snapshots (a viewer's call, like mon_online_render)
+int mon_online_render_scene(mon_online* h, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity, int32_t* instance) {
+    REQ(h); REQ(Twc16); REQ(rgb); REQ(depth);
+    if (rect.w == 0 || rect.h == 0) { set_error("render_scene: empty rect"); return MON_ERR_ARG; }
+    std::vector<Model*> ms; std::vector<int32_t> ids;
+    const std::vector<OnlineObject*> objs = online_objects(*h->m);
+    for (size_t i = 0; i < objs.size(); ++i) if (objs[i]->model && model_has_snapshot(*objs[i]->model)) { ms.push_back(objs[i]->model); ids.push_back((int32_t)i); }
+    for (Model* m : ms) if (m->device != ms[0]->device) { set_error("render_scene: the objects span more than one device"); return MON_ERR_STATE; }
+    if (ms.empty()) {                                                     // nothing published yet: the background
+        const size_t px = (size_t)rect.w * rect.h;
+        std::fill(rgb, rgb + 3 * px, 1.f); std::fill(depth, depth + px, 0.f);
+        if (opacity) std::fill(opacity, opacity + px, 0.f);
+        if (instance) std::fill(instance, instance + px, -1);
+        return MON_OK;
+    }
+    return scene_render(ms.data(), ms.size(), 1, rect, Twc16, rgb, depth, opacity, instance, ids.data(), nullptr);
 }
 // NerfManagerOnline::RenderNeRFsTest -> NeRF::RenderTestImg, nerf.cu:255-404: <out>/<id>/{test_img,test_depth,test_mask}/<stamp>.png,
 // test.txt, train.txt (object-centric poses), 60-view video_img / video_depth, obj.ply

@@ -467,11 +467,10 @@ static int rskip_alloc(Model& m, RenderSkipSide& k) {
     HIPCHECK(hipHostMalloc((void**)&k.h_stats, 16, hipHostMallocDefault)); std::memset(k.h_stats, 0, 16);
     return MON_OK;
 }
-// before a render of `prm` (stamp `epoch`) on stream s: the grid (built through the training grid's kernels into `frag`, the side's fragment image of the
-// same weights) and the cleared counters; bits == nullptr when the switch is off
-static RenderSkipArgs rskip_begin(Model& m, RenderSkipSide& k, hipStream_t s, bool on, float alpha, const uint16_t* prm, uint64_t epoch, uint16_t* frag) {
-    k.active = false;
-    if (!on || !k.d_grid) return RenderSkipArgs{};
+// the side's grid of `prm` (stamp `epoch`) on stream s: the cached one, or built through the training grid's kernels into `frag`, the side's fragment image
+// of the same weights; nullptr when the side has no grid buffers
+static const uint32_t* rskip_grid(Model& m, RenderSkipSide& k, hipStream_t s, float alpha, const uint16_t* prm, uint64_t epoch, uint16_t* frag) {
+    if (!k.d_grid) return nullptr;
     if (!k.pinned && (!k.built || k.epoch != epoch || k.alpha != alpha)) {
         if (alpha <= 0.f) {                                              // every cell live: no density pass
             (void)hipMemsetAsync(k.d_raw, 0xff, kOccWords * 4, s); (void)hipMemsetAsync(k.d_grid, 0xff, kOccWords * 4, s);
@@ -483,6 +482,13 @@ static RenderSkipArgs rskip_begin(Model& m, RenderSkipSide& k, hipStream_t s, bo
         }
         k.built = true; k.epoch = epoch; k.alpha = alpha; ++k.builds;
     }
+    return k.d_grid;
+}
+// before a render of `prm` (stamp `epoch`) on stream s: the grid and the cleared counters; bits == nullptr when the switch is off
+static RenderSkipArgs rskip_begin(Model& m, RenderSkipSide& k, hipStream_t s, bool on, float alpha, const uint16_t* prm, uint64_t epoch, uint16_t* frag) {
+    k.active = false;
+    if (!on || !k.d_grid) return RenderSkipArgs{};
+    rskip_grid(m, k, s, alpha, prm, epoch, frag);
     (void)hipMemsetAsync(k.d_stats, 0, 16, s);
     k.active = true;
     RenderSkipArgs a; a.bits = k.d_grid; a.stats = k.d_stats; return a;
@@ -1407,6 +1413,139 @@ int model_debug_set_render_grid(Model& m, int side, const uint32_t* bits) {
         else { k.pinned = false; k.built = false; }          // the object's own grid is rebuilt by the next skipping render
         return MON_OK;
     });
+}
+
+// ---- scene render (mon_scene_render): every object's sample lists of a chunk of the rect (k_fused_render<EMIT>), then one merge-composite launch
+// Per device and side, grow-only, never freed (like the tile workspaces): the lists of one chunk for every object, the rect's outputs, their pinned staging,
+// the events that order the objects' streams in front of side 0's render.  A render holds `mu` until its stream has been synchronised.
+struct SceneWs {
+    std::mutex mu;
+    float* t = nullptr; float* attr = nullptr; uint32_t* cnt = nullptr; size_t list_cap = 0;       // [lists][cap][kSceneListLen] t, float4 attr; [lists][cap]
+    float* out = nullptr; float* h_out = nullptr; size_t out_cap = 0;                                 // rgb 3n | depth n | opacity n | instance n (int32)
+    std::vector<hipEvent_t> ev;
+};
+static std::mutex g_scene_mu; static std::map<std::pair<int, int>, SceneWs*> g_scene_ws;
+static SceneWs& scene_ws(int device, int side) {
+    std::lock_guard<std::mutex> l(g_scene_mu); SceneWs*& w = g_scene_ws[{ device, side }]; if (!w) w = new SceneWs(); return *w;
+}
+bool model_has_snapshot(Model& m) {
+    if (!m.infer) return false;
+    std::lock_guard<std::mutex> l(m.infer->mu); return m.infer->latest >= 0;
+}
+int scene_render(Model* const* ms, size_t n, int side, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity, int32_t* instance,
+                 const int32_t* ids, const SceneDump* dump) {
+    if (!ms || n == 0 || !Twc16 || !rgb || !depth || rect.w == 0 || rect.h == 0) { set_error("scene_render: null or empty argument"); return MON_ERR_ARG; }
+    if (side != 0 && side != 1) { set_error("scene_render: side must be 0 or 1"); return MON_ERR_ARG; }
+    if (n > kSceneMaxLists) { set_error("scene_render: %zu objects (at most %u)", n, kSceneMaxLists); return MON_ERR_ARG; }
+    for (size_t j = 0; j < n; ++j) if (!ms[j]) { set_error("scene_render: null object %zu", j); return MON_ERR_ARG; }
+    const Intrinsics K = ms[0]->ds->K; const int device = ms[0]->device;
+    for (size_t j = 0; j < n; ++j) {
+        const Model& m = *ms[j]; const Intrinsics& k = m.ds->K;
+        if (m.device != device) { set_error("scene_render: objects on logical devices %d and %d", device, m.device); return MON_ERR_ARG; }
+        if (k.fx != K.fx || k.fy != K.fy || k.cx != K.cx || k.cy != K.cy || k.W != K.W || k.H != K.H) {
+            set_error("scene_render: object %zu has other intrinsics", j); return MON_ERR_ARG; }
+    }
+    for (size_t j = 0; j < n; ++j) {
+        const Model& m = *ms[j];
+        if (!rskip_supported(m) || 2u * m.oc.S != kSceneListLen) { set_error("scene_render: object %zu does not run on the fused kernels", j);
+            return MON_ERR_STATE; }
+        if (m.d_xw) { set_error("scene_render: object %zu renders with the XORWOW sample stream (rng_flags)", j); return MON_ERR_STATE; }
+        if (side == 1 && !model_has_snapshot(*ms[j])) { set_error("scene_render: object %zu has no published snapshot", j); return MON_ERR_STATE; }
+    }
+    HIPCHECK(use_device(device));
+    const uint32_t n_pix = rect.w * rect.h, cap = std::min(n_pix, kRenderChunkRays), L = (uint32_t)n;
+    Mat4 pose; std::memcpy(pose.m, Twc16, 64);
+    // what each object renders from: weights, their stamp, ray buffers, fragment image, render grid
+    struct Src { const uint16_t* prm; uint64_t epoch; BatchPtrs* b; uint16_t* frag; RenderSkipSide* rs; const uint32_t* bits; };
+    std::vector<Src> src(n);
+    std::unique_lock<std::mutex> dev_lock;                              // side 1: the device's snapshot-render mutex, then the workspace's
+    // side 1: the pinned snapshots, released on every way out
+    struct Pins { std::vector<std::pair<InferState*, int>> p; ~Pins() { for (auto& q : p) { std::lock_guard<std::mutex> l(q.first->mu); --q.first->readers[q.second]; } } } pins;
+    hipStream_t s;
+    if (side == 1) {
+        InferShared* sh = ms[0]->infer->shared; dev_lock = std::unique_lock<std::mutex>(sh->mu); s = sh->stream;
+        for (size_t j = 0; j < n; ++j) {
+            Model& m = *ms[j]; InferState* is = m.infer; is->wanted.store(true); int r;
+            {   std::lock_guard<std::mutex> l(is->mu); r = is->latest;
+                // (model_render_snapshot's rule: a finished older snapshot rather than waiting for a newer copy queued behind training)
+                if (is->written[1 - r] && hipEventQuery(is->ready[r]) != hipSuccess && hipEventQuery(is->ready[1 - r]) == hipSuccess) r = 1 - r;
+                ++is->readers[r]; pins.p.emplace_back(is, r); src[j].epoch = is->epoch_of[r]; }
+            HIPCHECK(hipStreamWaitEvent(s, is->ready[r], 0));
+            src[j].prm = is->snap[r]; src[j].b = &is->rb; src[j].frag = is->frag; src[j].rs = &is->rskip;
+        }
+    }
+    SceneWs& ws = scene_ws(device, side); std::lock_guard<std::mutex> wl(ws.mu);
+    if (side == 0) {
+        // the train side as model_render picks it (EMA once trained, brought up to date), every object's pending work ordered in front of object 0's stream
+        for (size_t j = 0; j < n; ++j) { Model& m = *ms[j]; model_leave_lane(m); int rc = ensure_ema_current(m); if (rc) return rc; }
+        s = ms[0]->train_stream;
+        while (ws.ev.size() < n) { hipEvent_t e; HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ws.ev.push_back(e); }
+        for (size_t j = 0; j < n; ++j) {
+            Model& m = *ms[j];
+            if (m.train_stream != s) { HIPCHECK(hipEventRecord(ws.ev[j], m.train_stream)); HIPCHECK(hipStreamWaitEvent(s, ws.ev[j], 0)); }
+            src[j].prm = (m.h_state.step > 0) ? m.P.ema : m.P.half; src[j].epoch = m.weights_epoch; src[j].b = &m.B; src[j].frag = m.d_frag_render;
+            src[j].rs = &m.rskip;
+        }
+    }
+    // render grids: the objects' own per-side caches (built if stale); the skip counters stay those of the objects' last own renders
+    for (size_t j = 0; j < n; ++j) {
+        Model& m = *ms[j];
+        src[j].bits = m.rskip_on.load() != 0 ? rskip_grid(m, *src[j].rs, s, m.rskip_alpha.load(), src[j].prm, src[j].epoch, src[j].frag) : nullptr;
+    }
+    // workspace (grow-only; nothing of it is in flight: every user synchronised before unlocking)
+    const size_t need_lists = (size_t)L * cap;
+    if (need_lists > ws.list_cap) {
+        if (ws.t) { (void)hipFree(ws.t); (void)hipFree(ws.attr); (void)hipFree(ws.cnt); ws.t = nullptr; ws.attr = nullptr; ws.cnt = nullptr; ws.list_cap = 0; }
+        HIPCHECK(hipMalloc((void**)&ws.t, need_lists * kSceneListLen * 4)); HIPCHECK(hipMalloc((void**)&ws.attr, need_lists * kSceneListLen * 16));
+        HIPCHECK(hipMalloc((void**)&ws.cnt, need_lists * 4)); ws.list_cap = need_lists;
+    }
+    if (n_pix > ws.out_cap) {
+        if (ws.out) { (void)hipFree(ws.out); (void)hipHostFree(ws.h_out); ws.out = nullptr; ws.h_out = nullptr; ws.out_cap = 0; }
+        HIPCHECK(hipMalloc((void**)&ws.out, 24 * (size_t)n_pix)); HIPCHECK(hipHostMalloc((void**)&ws.h_out, 24 * (size_t)n_pix, hipHostMallocDefault));
+        ws.out_cap = n_pix;
+    }
+    float* o_rgb = ws.out; float* o_depth = ws.out + 3 * (size_t)n_pix; float* o_op = ws.out + 4 * (size_t)n_pix;
+    int32_t* o_inst = reinterpret_cast<int32_t*>(ws.out + 5 * (size_t)n_pix);
+    std::vector<float> d_t, d_attr; std::vector<uint32_t> d_cnt;         // mon_debug_scene_samples: one list of the whole rect
+    if (dump) { d_t.resize((size_t)n_pix * kSceneListLen); d_attr.resize((size_t)n_pix * kSceneListLen * 4); d_cnt.resize(n_pix); }
+    for (uint32_t p0 = 0; p0 < n_pix; p0 += cap) {
+        const uint32_t nc = std::min(cap, n_pix - p0);
+        for (size_t j = 0; j < n; ++j) {
+            Model& m = *ms[j]; const size_t l0 = j * (size_t)cap;
+            launch_render_rays(s, *src[j].b, K, m.oc, rect, pose, 0, p0, nc);
+            launch_fused_render_emit(s, m.lf, m.nd, src[j].prm, *src[j].b, m.oc, nc, p0 * kSceneListLen, ws.t + l0 * kSceneListLen, ws.attr + l0 * kSceneListLen * 4,
+                    ws.cnt + l0, src[j].frag, p0 == 0u, src[j].bits);
+        }
+        // (every object's ray kernel wrote the same dn: it depends on the pixel and the intrinsics only)
+        launch_scene_composite(s, nc, L, cap, ws.t, ws.attr, ws.cnt, src[0].b->ray_dn, o_rgb + 3 * (size_t)p0, o_depth + p0, o_op + p0, o_inst + p0);
+        if (dump) {
+            const size_t l0 = dump->list * (size_t)cap;
+            HIPCHECK(hipMemcpyAsync(d_t.data() + (size_t)p0 * kSceneListLen, ws.t + l0 * kSceneListLen, (size_t)nc * kSceneListLen * 4, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipMemcpyAsync(d_attr.data() + (size_t)p0 * kSceneListLen * 4, ws.attr + l0 * kSceneListLen * 4, (size_t)nc * kSceneListLen * 16,
+                    hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipMemcpyAsync(d_cnt.data() + p0, ws.cnt + l0, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipStreamSynchronize(s));
+        }
+    }
+    // results home through the pinned staging (a copy kernel on the render's stream, as the snapshot render does)
+    launch_copy_params(s, reinterpret_cast<const uint16_t*>(ws.out), reinterpret_cast<uint16_t*>(ws.h_out), (uint32_t)(12 * (size_t)n_pix));
+    HIPCHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    std::memcpy(rgb, ws.h_out, 12 * (size_t)n_pix); std::memcpy(depth, ws.h_out + 3 * (size_t)n_pix, 4 * (size_t)n_pix);
+    if (opacity) std::memcpy(opacity, ws.h_out + 4 * (size_t)n_pix, 4 * (size_t)n_pix);
+    if (instance) {
+        const int32_t* q = reinterpret_cast<const int32_t*>(ws.h_out + 5 * (size_t)n_pix);
+        for (uint32_t i = 0; i < n_pix; ++i) instance[i] = (q[i] >= 0 && ids) ? ids[q[i]] : q[i];
+    }
+    if (dump) {
+        for (size_t i = 0; i < (size_t)n_pix * kSceneListLen; ++i) {
+            if (dump->t) dump->t[i] = d_t[i];
+            if (dump->alpha) dump->alpha[i] = d_attr[4 * i];
+            if (dump->rgb) for (int c = 0; c < 3; ++c) dump->rgb[3 * i + c] = d_attr[4 * i + 1 + c];
+        }
+        if (dump->count) std::memcpy(dump->count, d_cnt.data(), 4 * (size_t)n_pix);
+    }
+    return MON_OK;
 }
 
 int model_get_params(Model& m, int which, void* dst, size_t bytes) {

@@ -321,6 +321,15 @@ void launch_fused_render(hipStream_t s, const LevelFast& lt, const NetDims& nd, 
         uint32_t n_rays, uint32_t idx_base, float* rgb, float* depth, float* mask, uint16_t* frag_image, int build_image,
         const RenderSkipArgs& skip = RenderSkipArgs{});
 void launch_build_frag_image(hipStream_t s, const uint16_t* params, const NetDims& nd, uint16_t* image);
+// Scene render (mon_scene_render, kernels_render.hip).  Sample lists of kSceneListLen (= 2S) slots, list k of ray r at (k * cap + r) * kSceneListLen:
+// t [fp32], {alpha, r, g, b} [float4], and a count per (list, ray).  k_fused_render<EMIT> writes one object's lists (skip_bits: its render grid or nullptr;
+// the skip counters are not touched); k_scene_composite merges a ray's lists by t (ties to the lower list) and composites them front to back.
+constexpr uint32_t kSceneListLen = 64, kSceneMaxLists = 256;
+constexpr uint32_t scene_composite_lds(uint32_t n_lists) { return n_lists * (2u * kSceneListLen + 20u); }
+void launch_fused_render_emit(hipStream_t s, const LevelFast& lt, const NetDims& nd, const uint16_t* params, const BatchPtrs& b, const ObjectConst& oc,
+        uint32_t n_rays, uint32_t idx_base, float* t, float* attr, uint32_t* cnt, uint16_t* frag_image, int build_image, const uint32_t* skip_bits);
+void launch_scene_composite(hipStream_t s, uint32_t n_rays, uint32_t n_lists, uint32_t cap, const float* t, const float* attr, const uint32_t* cnt,
+        const float* dn, float* rgb, float* depth, float* opacity, int32_t* instance);
 // inference on feature-planar level tiles (kernels_tilerender.hip): Render / RenderVideo, GetDensityOnGrid, mesh vertex colours
 constexpr uint32_t kTileChunkJobs = 32768;          // rays (jobs of 2S = 64 samples) per chunk of the tile render
 bool tile_render_supported(const LevelTable& lt, const NetDims& nd);
@@ -466,6 +475,12 @@ int tile_ws_skip_buffers(TileWs& ws, size_t n_pix);
 void tile_ws_weights(Model& m, TileWs& ws, hipStream_t s, const uint16_t* prm, uint64_t epoch);
 // ws.x holds n points -> ws.O (raw fp16 outputs [n][4]); caller holds ws.mu and has called tile_ws_weights
 void tile_points_forward(Model& m, TileWs& ws, hipStream_t s, uint32_t n);
+// Scene render (mon_scene_render): side 0 the train-side weights, 1 the published snapshots; ids (may be nullptr) = the instance reported for each object;
+// dump (mon_debug_scene_samples, may be nullptr) = object `list`'s sample lists of the whole rect, host arrays [pixel][kSceneListLen] (rgb x 3) + count [pixel]
+struct SceneDump { uint32_t list; float* t; float* alpha; float* rgb; uint32_t* count; };
+int scene_render(Model* const* ms, size_t n, int side, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity, int32_t* instance,
+                 const int32_t* ids, const SceneDump* dump);
+bool model_has_snapshot(Model& m);      // the object has an inference side and has published weights
 int model_publish_snapshot(Model& m);
 int model_render_snapshot(Model& m, mon_frame_bbox box, const float* pose16, int pose_is_Toc, float* rgb, float* depth, float* mask, uint32_t* snapshot_step);
 int level_table_build(const mon_config& c, LevelTable& lt, NetDims& nd, uint32_t& n_grid);
