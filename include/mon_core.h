@@ -188,6 +188,52 @@ int mon_object_render_occupancy(mon_object* obj, int side, int dilated, uint32_t
  *                  sample-stream bits); side 1 and an object without an inference side or with nothing published yet */
 int mon_scene_render(mon_object* const* objs, size_t n_objs, int side, mon_frame_bbox rect, const float* Twc16,
                      float* rgb, float* depth, float* opacity, int32_t* instance);
+/* Object pose refinement through the trained field (iNeRF-style): align the object with observed frames by following the gradient of a photometric,
+ * silhouette and depth error with respect to the 6-DoF pose Tow.
+ * Objective.  obs names frames of the object's dataset (FrameId) and pixel boxes inside them; the target of a pixel is that frame's rgb c*, its instance map
+ * m* = (instance == class_id) and its depth d* (0 where the dataset has none); the camera is the frame's Twc.  For each drawn pixel, the ray
+ * mon_object_render builds for it under the Tow evaluated, intersected with the object's box, and its 2S = 64 jittered distances t_k -- rays_per_iter = 0:
+ * the render's own jitter, so that at the object's own Tow the samples, alpha and colour of each box are those of mon_debug_scene_samples for that box;
+ * rays_per_iter > 0: counter-RNG stream 4 keyed by (seed, iteration, ray * 2S + k), the pixels drawn uniformly over the union of the boxes' pixels by
+ * stream 5 keyed by (seed, iteration, ray).  Alpha and colour as the render computes them (sigma = exp(o3), c = logistic(o0..2), alpha_k = 1 - exp(-sigma_k
+ * dt_k), the first interval from 0, the early cut at T < 1e-4):
+ *   w_k = alpha_k T_k, T_end what remains; r = sum_k w_k (c_k - c*) (the background counts as the target colour); O = 1 - T_end;
+ *   D = sum_k w_k t_k / |camera ray|
+ *   l = w_rgb m* |r|^2 / 3 + w_mask (O - m*)^2 + w_depth m* [d* > 0] Huber(D - d*),
+ *   Huber(x) = x^2 / 2 for |x| <= depth_huber, else depth_huber (|x| - depth_huber / 2)
+ *   L = mean of l over the drawn pixels (a ray that misses the box counts with O = D = r = 0)
+ * grad6 = dL/dxi at xi = 0 for Tow(xi) = exp(xi^) Tow, xi = (rho, phi), translation first.  Sample positions move as x_k(xi) = exp(xi^) x_k; every t_k and
+ * dt_k, the box intersection, the early cut and the hash-grid corners of each sample are held at their values at Tow -- only the trilinear weights inside the
+ * cell are differentiated: dL/drho = sum_k g_k, dL/dphi = sum_k x_k x g_k, g_k = dL/dx_k in the object frame.
+ * Refinement: Adam (0.9, 0.999, 1e-8) on the twist, lr_trans for rho and lr_rot for phi; each step Tow <- exp(delta^) Tow (closed-form SE(3) exponential,
+ * fp32), the rotation re-orthonormalised.  Step i evaluates with iteration = i.  Every sample is evaluated: render skipping does not apply.
+ * Defaults (mon_pose_refine_default; step sizes and step count measured on the synthetic scene): iters 100, rays_per_iter 4096,
+ * lr_trans 2e-3, lr_rot 4e-3, w_rgb 1, w_mask 1, w_depth 1, depth_huber 0.05, seed 1.
+ * (8-level grid at per-level scale 1.5, 5 degrees / 5 % of the box diagonal off: 0.12-0.15 degrees and <= 0.09 % after 100 steps; lr 1e-3 / 2e-3 over 200
+ * steps and 5e-3 / 1e-2 over 100 were no better.  On base.json's 16-level grid the gradient does not point downhill on the pose's scale: DESIGN.md 3.4d.)
+ * Read-only: nothing about the object changes (parameters, training state and RNG counters, render-skip caches and statistics, snapshot, mesh, its own Tow);
+ * the pose goes back to the caller only.  side as in mon_scene_render: 0 the train-side weights (EMA once trained) on the train stream, the caller
+ * serialises against training; 1 the published snapshot on the inference stream, callable while the object trains.  Each side has its own scratch.
+ * Returns MON_ERR_ARG for NULL obj / obs / pose / params, n_obs 0, iters < 0, side not 0 / 1, rays_per_iter above 2^22, a FrameId the dataset does not hold,
+ * a box empty or outside its frame (checked before any device work); MON_ERR_STATE for objects outside the fused shapes, the XORWOW render mode, and side 1
+ * with nothing published. */
+typedef struct mon_pose_refine_params {
+    int      iters;          /* Adam steps of mon_object_refine_pose (>= 0)                                                                         */
+    uint32_t rays_per_iter;  /* pixels drawn per evaluation, uniformly over the union of the boxes' pixels; 0 = every pixel of every box, in box order
+                                then row-major (no randomness)                                                                                        */
+    float    lr_trans;       /* Adam step size of the twist's translation part (object-frame units)                                                */
+    float    lr_rot;         /* Adam step size of the twist's rotation part (radians)                                                               */
+    float    w_rgb, w_mask, w_depth, depth_huber;   /* loss weights, Huber width of the depth term (metres)                                        */
+    uint64_t seed;           /* pixel draws and sample jitter of rays_per_iter > 0                                                                  */
+} mon_pose_refine_params;
+int mon_pose_refine_default(mon_pose_refine_params* p);
+/* One evaluation at pose Tow16 (column-major, world -> object, as mon_object_create's): loss and dL/dxi (grad6 = rho, phi; either may be NULL) */
+int mon_object_pose_loss(mon_object* obj, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params* p,
+                         uint32_t iteration, float* loss, float* grad6);
+/* p->iters Adam steps from *Tow16_inout; writes the final pose back; loss_trace[iters + 1] (may be NULL): the loss before each step and at the end.  The
+ * whole refinement is enqueued at once (the pose lives on the device between steps); the call returns when it is done. */
+int mon_object_refine_pose(mon_object* obj, int side, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, float* Tow16_inout,
+                           float* loss_trace);
 /* NeRF_Model::GetDensityOnGrid (nerf_model.cu:2007-2048): raw density channel on an rx*ry*rz lattice. */
 int mon_object_density_grid(mon_object* obj, int rx, int ry, int rz, float* out_host);
 
@@ -289,6 +335,10 @@ int mon_online_render(mon_online* mgr, size_t idx, mon_frame_bbox box, const flo
 /* mon_scene_render(side 1) of every object of the manager that has published weights (the others are left out; none: the background); instance = the
  * manager's object index.  A viewer's call: safe while the objects train.  MON_ERR_STATE when those objects span more than one device (a follow-up). */
 int mon_online_render_scene(mon_online* mgr, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity, int32_t* instance);
+/* mon_object_refine_pose(side 1) of object idx: its published snapshot, on the inference stream -- safe while the manager trains it.  MON_ERR_STATE while
+ * nothing of it has been published. */
+int mon_online_refine_pose(mon_online* mgr, size_t idx, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, float* Tow16_inout,
+                           float* loss_trace);
 /* RenderNeRFsTest(out_path, idx, stamps, boxes, Twcs, radius) -> NeRF::RenderTestImg (nerf.cu:255-404): test images + test.txt +
  * train.txt + the 60-view 360-degree video (RenderVideo, nerf_model.cu:1832-1990) + obj.ply under <out_path>/<id>/ */
 int mon_online_render_nerfs_test(mon_online* mgr, const char* out_path, size_t idx, const char* const* timestamps, const mon_frame_bbox* boxes,

@@ -53,6 +53,13 @@ int mon_debug_scene_samples(mon_object* const* objs, size_t n_objs, int side, mo
 int mon_debug_scene_composite(int device, uint32_t n_rays, uint32_t n_lists, const float* t, const float* alpha, const float* rgb, const uint32_t* count,
                               const float* dn, float* out_rgb, float* out_depth, float* out_opacity, int32_t* out_instance);
 
+/* Pose refinement (mon_object_pose_loss, the same arguments): per drawn ray of that evaluation (rays_per_iter of them, or every pixel of every box in box
+ * order), its 2S = 64 samples: x[ray][64][3] the positions in the object frame, raw[ray][64][4] the network's raw outputs, dldx[ray][64][3] = dL/dx_k in the
+ * object frame (the 1/N of the mean included).  Samples not evaluated (a missed box, the second tile behind the early cut) hold 0 (x: the position it would
+ * have, or 0 for a miss).  Any output may be NULL. */
+int mon_debug_pose_samples(mon_object* obj, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params* p,
+                           uint32_t iteration, float* x, float* raw, float* dldx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,12 @@ class MonRenderSkipStats(C.Structure):
                 ("samples_live", C.c_uint64)]
 
 
+class PoseRefineParams(C.Structure):
+    """mon_pose_refine_params (include/mon_core.h): Adam steps, rays per evaluation (0 = every box pixel), step sizes, loss weights, Huber width, seed."""
+    _fields_ = [("iters", C.c_int32), ("rays_per_iter", C.c_uint32), ("lr_trans", C.c_float), ("lr_rot", C.c_float), ("w_rgb", C.c_float),
+                ("w_mask", C.c_float), ("w_depth", C.c_float), ("depth_huber", C.c_float), ("seed", C.c_uint64)]
+
+
 class MonProfile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8)]
 
@@ -130,6 +136,11 @@ _SIGS = {
     "mon_object_render_occupancy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "mon_scene_render": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, MonBBox, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_online_render_scene": (C.c_int, [C.c_void_p, MonBBox, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_pose_refine_default": (C.c_int, [C.POINTER(PoseRefineParams)]),
+    "mon_object_pose_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32,
+            C.POINTER(C.c_float), C.c_void_p]),
+    "mon_object_refine_pose": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams), C.c_void_p, C.c_void_p]),
+    "mon_online_refine_pose": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams), C.c_void_p, C.c_void_p]),
 }
 
 
@@ -149,6 +160,8 @@ _DIAG_SIGS = {
     "mon_debug_scene_samples": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, MonBBox, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_debug_scene_composite": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_debug_pose_samples": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32, C.c_void_p,
+            C.c_void_p, C.c_void_p]),
 }
 
 
@@ -553,6 +566,28 @@ class ObjectNeRF:
         """Jobs (rays that hit the box) of the last crop the tile render evaluated on this object's device (side 0: train stream, 1: inference stream)."""
         n = C.c_uint32(0); _check(diag_lib().mon_debug_render_jobs(self.h, int(side), C.byref(n))); return n.value
 
+    def pose_loss(self, obs, Tow16, params=None, side=0, iteration=0):
+        """mon_object_pose_loss: (loss, grad6 = dL/d(rho, phi)) of pose Tow16 (column-major, world -> object) against the boxes obs [(FrameId, x, y, h, w)]."""
+        b, prm = _pose_boxes(obs), _pose_params(params); pose = np.ascontiguousarray(Tow16, np.float32).reshape(16)
+        loss = C.c_float(0); g = np.empty(6, np.float32)
+        _check(lib().mon_object_pose_loss(self.h, int(side), _p(b), b.shape[0], _p(pose), C.byref(prm), int(iteration), C.byref(loss), _p(g)))
+        return loss.value, g
+
+    def refine_pose(self, obs, Tow16, params=None, side=0):
+        """mon_object_refine_pose: params.iters Adam steps from Tow16; returns (refined Tow16, loss trace of iters + 1 values).  The object is not changed."""
+        b, prm = _pose_boxes(obs), _pose_params(params); pose = np.array(Tow16, np.float32).reshape(16)
+        trace = np.empty(prm.iters + 1, np.float32)
+        _check(lib().mon_object_refine_pose(self.h, int(side), _p(b), b.shape[0], C.byref(prm), _p(pose), _p(trace)))
+        return pose, trace
+
+    def pose_samples(self, obs, Tow16, params=None, side=0, iteration=0):
+        """mon_debug_pose_samples: per drawn ray of that evaluation, positions (n, 64, 3), raw outputs (n, 64, 4) and dL/dx (n, 64, 3), object frame."""
+        b, prm = _pose_boxes(obs), _pose_params(params); pose = np.ascontiguousarray(Tow16, np.float32).reshape(16)
+        n = int(prm.rays_per_iter) or int(sum(int(v[3]) * int(v[4]) for v in b))
+        x = np.empty((n, 64, 3), np.float32); raw = np.empty((n, 64, 4), np.float32); g = np.empty((n, 64, 3), np.float32)
+        _check(diag_lib().mon_debug_pose_samples(self.h, int(side), _p(b), b.shape[0], _p(pose), C.byref(prm), int(iteration), _p(x), _p(raw), _p(g)))
+        return x, raw, g
+
     def set_debug_dump(self, on):
         _check(lib().mon_object_set_debug_dump(self.h, int(on)))
 
@@ -702,9 +737,38 @@ class OnlineManager:
         _check(lib().mon_online_render_scene(self.h, box, _p(pose), *[_p(a) for a in out]))
         return out
 
+    def refine_pose(self, idx, obs, Tow16, params=None):
+        """mon_online_refine_pose: object idx's published snapshot, safe while the manager trains; returns (refined Tow16, loss trace)."""
+        b, prm = _pose_boxes(obs), _pose_params(params); pose = np.array(Tow16, np.float32).reshape(16)
+        trace = np.empty(prm.iters + 1, np.float32)
+        _check(lib().mon_online_refine_pose(self.h, int(idx), _p(b), b.shape[0], C.byref(prm), _p(pose), _p(trace)))
+        return pose, trace
+
     def close(self):
         if self.h:
             lib().mon_online_destroy(self.h); self.h = None
+
+
+def pose_refine_default(**overrides):
+    """mon_pose_refine_default, then any field overridden by keyword."""
+    p = PoseRefineParams(); _check(lib().mon_pose_refine_default(C.byref(p)))
+    for k, v in overrides.items():
+        if k not in dict(PoseRefineParams._fields_):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _pose_params(params):
+    if params is None:
+        return pose_refine_default()
+    if isinstance(params, dict):
+        return pose_refine_default(**params)
+    return params
+
+
+def _pose_boxes(obs):
+    return np.ascontiguousarray(obs, np.uint32).reshape(-1, 5)
 
 
 def _scene_outputs(rect):

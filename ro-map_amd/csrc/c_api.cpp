@@ -119,6 +119,33 @@ int mon_scene_render(mon_object* const* objs, size_t n_objs, int side, mon_frame
     for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
     return scene_render(ms.data(), n_objs, side, rect, Twc16, rgb, depth, opacity, instance, nullptr, nullptr);
 }
+int mon_pose_refine_default(mon_pose_refine_params* p) {
+    REQUIRE(p, "params");
+    p->iters = 100; p->rays_per_iter = 4096; p->lr_trans = 2e-3f; p->lr_rot = 4e-3f;
+    p->w_rgb = 1.f; p->w_mask = 1.f; p->w_depth = 1.f; p->depth_huber = 0.05f; p->seed = 1;
+    return MON_OK;
+}
+// every argument that can be judged without the object is judged before it is touched
+static int pose_args(const mon_object* o, int side, const mon_frame_bbox* obs, size_t n_obs, const float* pose, const mon_pose_refine_params* p) {
+    REQUIRE(o, "object"); REQUIRE(obs, "obs"); REQUIRE(pose, "pose"); REQUIRE(p, "params");
+    if (n_obs == 0) { set_error("pose: no boxes"); return MON_ERR_ARG; }
+    if (p->iters < 0) { set_error("pose: iters %d < 0", p->iters); return MON_ERR_ARG; }
+    if (side != 0 && side != 1) { set_error("pose: side %d (0 or 1)", side); return MON_ERR_ARG; }
+    return MON_OK;
+}
+int mon_object_pose_loss(mon_object* o, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params* p,
+        uint32_t iteration, float* loss, float* grad6) {
+    const int rc = pose_args(o, side, obs, n_obs, Tow16, p); if (rc) return rc;
+    return pose_refine(*o->m, side, obs, n_obs, Tow16, *p, -1, iteration, nullptr, nullptr, loss, grad6, nullptr);
+}
+int mon_object_refine_pose(mon_object* o, int side, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, float* Tow16_inout,
+        float* loss_trace) {
+    const int rc = pose_args(o, side, obs, n_obs, Tow16_inout, p); if (rc) return rc;
+    float pose[16]; std::memcpy(pose, Tow16_inout, 64);
+    const int r2 = pose_refine(*o->m, side, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr);
+    if (r2 == MON_OK) std::memcpy(Tow16_inout, pose, 64);
+    return r2;
+}
 int mon_object_density_grid(mon_object* o, int rx, int ry, int rz, float* out_host) { REQUIRE(o, "object");
     return model_density_grid(*o->m, rx, ry, rz, out_host); }
 int mon_object_get_config(mon_object* o, mon_config* cfg) { REQUIRE(o, "object"); REQUIRE(cfg, "cfg"); *cfg = o->m->cfg; return MON_OK; }

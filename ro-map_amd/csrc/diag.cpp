@@ -224,6 +224,13 @@ int mon_debug_scene_composite(int device, uint32_t n_rays, uint32_t n_lists, con
     std::memcpy(out_opacity, out.data() + 4 * (size_t)n_rays, 4 * (size_t)n_rays); std::memcpy(out_instance, out.data() + 5 * (size_t)n_rays, 4 * (size_t)n_rays);
     return MON_OK;
 }
+int mon_debug_pose_samples(mon_object* o, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params* p,
+                           uint32_t iteration, float* x, float* raw, float* dldx) {
+    REQUIRE(o, "object"); REQUIRE(obs, "obs"); REQUIRE(Tow16, "pose"); REQUIRE(p, "params");
+    if (n_obs == 0) { set_error("debug_pose_samples: no boxes"); return MON_ERR_ARG; }
+    const mon::PoseDump dump{ x, raw, dldx };
+    return mon::pose_refine(*o->m, side, obs, n_obs, Tow16, *p, -1, iteration, nullptr, nullptr, nullptr, nullptr, &dump);
+}
 int mon_debug_yaml_number(const char* text, const char* key, double* value) {
     REQUIRE(text, "text"); REQUIRE(key, "key"); REQUIRE(value, "value");
     if (!read_yaml_number(text, key, *value)) { set_error("config.yaml: %s missing or not a number", key); return MON_ERR_IO; }

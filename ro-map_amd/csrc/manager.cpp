@@ -662,6 +662,17 @@ int mon_online_render_scene(mon_online* h, mon_frame_bbox rect, const float* Twc
     }
     return scene_render(ms.data(), ms.size(), 1, rect, Twc16, rgb, depth, opacity, instance, ids.data(), nullptr);
 }
+// pose refinement of one object against new observations, from its published snapshot (a frontend's call, like mon_online_render: safe while it trains)
+int mon_online_refine_pose(mon_online* h, size_t idx, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, float* Tow16_inout,
+        float* loss_trace) {
+    REQ(h); REQ(obs); REQ(p); REQ(Tow16_inout);
+    if (n_obs == 0 || p->iters < 0) { set_error("refine_pose: no boxes or iters < 0"); return MON_ERR_ARG; }
+    OnlineObject* o = online_object(*h->m, idx); if (!o || !o->model) { set_error("NeRF Idx error ..."); return MON_ERR_ARG; }
+    float pose[16]; std::memcpy(pose, Tow16_inout, 64);
+    const int rc = pose_refine(*o->model, 1, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr);
+    if (rc == MON_OK) std::memcpy(Tow16_inout, pose, 64);
+    return rc;
+}
 // NerfManagerOnline::RenderNeRFsTest -> NeRF::RenderTestImg, nerf.cu:255-404: <out>/<id>/{test_img,test_depth,test_mask}/<stamp>.png,
 // test.txt, train.txt (object-centric poses), 60-view video_img / video_depth, obj.ply
 int mon_online_render_nerfs_test(mon_online* h, const char* out_path, size_t idx, const char* const* timestamps, const mon_frame_bbox* boxes,

@@ -757,6 +757,7 @@ int model_create(Dataset* ds, const mon_config& cfg, int class_id, const float* 
 static void drop_graph(Model& m) { if (m.graph_exec) { hipGraphExecDestroy(m.graph_exec); m.graph_exec = nullptr; m.graph_backend = -1; } }
 
 void model_mesh_free(Model& m);
+void pose_ws_free(Model& m);
 int model_destroy(Model* mp) {
     if (!mp) return MON_OK;
     Model& m = *mp; use_device(m.device);
@@ -771,6 +772,7 @@ int model_destroy(Model* mp) {
         if (is->rskip.h_stats) (void)hipHostFree(is->rskip.h_stats);
         delete is; m.infer = nullptr;
     }
+    pose_ws_free(m);
     drop_graph(m);
     if (m.tile_counted) { tile_ws_object_gone(m.device); m.tile_counted = false; }
     for (auto& e : m.ev_pool) hipEventDestroy(e);
@@ -1544,6 +1546,132 @@ int scene_render(Model* const* ms, size_t n, int side, mon_frame_bbox rect, cons
             if (dump->rgb) for (int c = 0; c < 3; ++c) dump->rgb[3 * i + c] = d_attr[4 * i + 1 + c];
         }
         if (dump->count) std::memcpy(dump->count, d_cnt.data(), 4 * (size_t)n_pix);
+    }
+    return MON_OK;
+}
+
+// ---- pose refinement (mon_object_pose_loss / mon_object_refine_pose): k_pose_rays -> k_pose_grad -> k_pose_update per evaluation, the pose in device memory
+// Per object and side, grow-only, freed with the object: a viewer (side 1) and the trainer (side 0) run at the same time.  A call holds `mu` until its stream
+// has been synchronised.
+struct PoseWs {
+    std::mutex mu;
+    float4* rec = nullptr; size_t rec_cap = 0;                                    // ray records, 4 float4 per drawn ray
+    float* out = nullptr; size_t out_cap = 0;                                     // {loss, grad6, 0} per evaluation
+    mon_frame_bbox* boxes = nullptr; uint32_t* prefix = nullptr; size_t box_cap = 0;
+    float* small = nullptr;                                                       // partials [kPoseMaxGrid][8] | pose [16] | moments [12]
+    uint16_t* frag = nullptr;                                                     // the A-fragment image, backward fragments included
+    float* dbg = nullptr; size_t dbg_cap = 0;                                     // mon_debug_pose_samples: x | raw | dL/dx of every sample
+};
+static std::mutex g_pose_mu;
+static PoseWs& pose_ws(Model& m, int side) { std::lock_guard<std::mutex> l(g_pose_mu); if (!m.pose_ws[side]) m.pose_ws[side] = new PoseWs(); return *m.pose_ws[side]; }
+void pose_ws_free(Model& m) {
+    for (int k = 0; k < 2; ++k) {
+        PoseWs* w = m.pose_ws[k]; if (!w) continue;
+        for (void* q : { (void*)w->rec, (void*)w->out, (void*)w->boxes, (void*)w->prefix, (void*)w->small, (void*)w->frag, (void*)w->dbg }) if (q) (void)hipFree(q);
+        delete w; m.pose_ws[k] = nullptr;
+    }
+}
+template <class T> static int grow_buf(T*& p, size_t& cap, size_t need) {
+    if (need <= cap && p) return MON_OK;
+    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+    HIPCHECK(hipMalloc((void**)&p, need * sizeof(T))); cap = need; return MON_OK;
+}
+uint32_t pose_n_rays(const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params& p) {
+    if (p.rays_per_iter) return p.rays_per_iter;
+    uint64_t t = 0; for (size_t i = 0; i < n_obs; ++i) t += (uint64_t)obs[i].w * obs[i].h;
+    return t > 0xffffffffull ? 0xffffffffu : (uint32_t)t;
+}
+int pose_refine(Model& m, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params& p, int iters,
+                uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const PoseDump* dump) {
+    if (!obs || n_obs == 0 || !Tow16) { set_error("pose: null or empty argument"); return MON_ERR_ARG; }
+    if (side != 0 && side != 1) { set_error("pose: side must be 0 or 1"); return MON_ERR_ARG; }
+    if (p.rays_per_iter > kPoseMaxRays) { set_error("pose: rays_per_iter %u above %u", p.rays_per_iter, kPoseMaxRays); return MON_ERR_ARG; }
+    std::vector<uint32_t> prefix(n_obs + 1, 0u);
+    for (size_t i = 0; i < n_obs; ++i) {
+        const mon_frame_bbox& b = obs[i];
+        if (b.FrameId >= m.ds->max_frames || !m.ds->present[b.FrameId]) { set_error("pose: box %zu names frame %u, which the dataset does not hold", i, b.FrameId);
+            return MON_ERR_ARG; }
+        if (b.w == 0 || b.h == 0 || (uint64_t)b.x + b.w > (uint64_t)m.ds->K.W || (uint64_t)b.y + b.h > (uint64_t)m.ds->K.H) {
+            set_error("pose: box %zu (frame %u, x %u y %u h %u w %u) empty or outside the %dx%d frame", i, b.FrameId, b.x, b.y, b.h, b.w, m.ds->K.W, m.ds->K.H);
+            return MON_ERR_ARG; }
+        prefix[i + 1] = prefix[i] + b.w * b.h;                                      // (a frame is at most 2^31 pixels; 2^22 boxes of them would not fit)
+        if ((uint64_t)prefix[i] + (uint64_t)b.w * b.h > kPoseMaxRays * 64ull) { set_error("pose: the boxes hold too many pixels"); return MON_ERR_ARG; }
+    }
+    if (!launch_pose_rays || !launch_pose_grad || !launch_pose_update || !pose_grad_grid) { set_error("pose: built without kernels_pose.hip");
+        return MON_ERR_STATE; }
+    if (!rskip_supported(m) || 2u * m.oc.S != 64u) { set_error("pose: this object does not run on the fused kernels"); return MON_ERR_STATE; }
+    if (m.d_xw) { set_error("pose: this object renders with the XORWOW sample stream (rng_flags)"); return MON_ERR_STATE; }
+    if (side == 1 && !model_has_snapshot(m)) { set_error("pose: side 1 and nothing published yet"); return MON_ERR_STATE; }
+    const uint32_t total = prefix[n_obs], n_rays = p.rays_per_iter ? p.rays_per_iter : total;
+    if (!p.rays_per_iter && total > kPoseMaxRays) { set_error("pose: %u pixels in the boxes (at most %u with rays_per_iter = 0)", total, kPoseMaxRays);
+        return MON_ERR_ARG; }
+    HIPCHECK(use_device(m.device));
+    const int n_eval = iters < 0 ? 1 : iters + 1;
+    // the weights of the side, and its stream
+    hipStream_t s; const uint16_t* prm;
+    std::unique_lock<std::mutex> dev_lock;
+    struct Pin { InferState* is = nullptr; int r = 0; ~Pin() { if (is) { std::lock_guard<std::mutex> l(is->mu); --is->readers[r]; } } } pin;
+    if (side == 1) {
+        InferState* is = m.infer; InferShared* sh = is->shared; dev_lock = std::unique_lock<std::mutex>(sh->mu); s = sh->stream;
+        is->wanted.store(true); int r;
+        {   std::lock_guard<std::mutex> l(is->mu); r = is->latest;
+            if (is->written[1 - r] && hipEventQuery(is->ready[r]) != hipSuccess && hipEventQuery(is->ready[1 - r]) == hipSuccess) r = 1 - r;
+            ++is->readers[r]; pin.is = is; pin.r = r; }
+        HIPCHECK(hipStreamWaitEvent(s, is->ready[r], 0));
+        prm = is->snap[r];
+    } else {
+        model_leave_lane(m); { const int rc = ensure_ema_current(m); if (rc) return rc; }
+        s = m.train_stream; prm = (m.h_state.step > 0) ? m.P.ema : m.P.half;
+    }
+    PoseWs& w = pose_ws(m, side); std::lock_guard<std::mutex> wl(w.mu);
+    const FragDims fd{ m.nd.Epad, m.nd.W, m.nd.NH, m.nd.L };
+    int rc;
+    size_t c_small = 0, c_frag = 0, c_prefix = 0;
+    if ((rc = grow_buf(w.rec, w.rec_cap, 4 * (size_t)n_rays)) || (rc = grow_buf(w.out, w.out_cap, 8 * (size_t)n_eval))) return rc;
+    if (n_obs > w.box_cap || !w.boxes) { c_prefix = w.box_cap; if ((rc = grow_buf(w.prefix, c_prefix, n_obs + 1)) || (rc = grow_buf(w.boxes, w.box_cap, n_obs))) return rc; }
+    if (!w.small) { if ((rc = grow_buf(w.small, c_small, (size_t)kPoseMaxGrid * 8 + 16 + 12))) return rc; }
+    if (!w.frag) { if ((rc = grow_buf(w.frag, c_frag, (size_t)fd.N_FRAGS() * 512))) return rc; }
+    float* partials = w.small; float* d_pose = w.small + (size_t)kPoseMaxGrid * 8; float* d_mom = d_pose + 16;
+    float *dx = nullptr, *draw = nullptr, *dg = nullptr;
+    if (dump) {
+        if ((rc = grow_buf(w.dbg, w.dbg_cap, (size_t)n_rays * 64 * 10))) return rc;
+        dx = w.dbg; draw = w.dbg + (size_t)n_rays * 64 * 3; dg = w.dbg + (size_t)n_rays * 64 * 7;
+    }
+    HIPCHECK(hipMemcpyAsync(w.boxes, obs, sizeof(mon_frame_bbox) * n_obs, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(w.prefix, prefix.data(), 4 * (n_obs + 1), hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(d_pose, Tow16, 64, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(d_mom, 0, 48, s));
+    const bool drawn = p.rays_per_iter != 0;
+    const uint32_t grid = pose_grad_grid(n_rays);
+    for (int it = 0; it < n_eval; ++it) {
+        const uint32_t key = iters < 0 ? iteration : (uint32_t)it;
+        PoseRayArgs ra{}; ra.boxes = w.boxes; ra.prefix = w.prefix; ra.n_obs = (uint32_t)n_obs; ra.n_rays = n_rays; ra.total = total; ra.drawn = drawn ? 1u : 0u;
+        ra.iteration = key; ra.seed = p.seed; ra.ds = m.ds->ptrs(); ra.aabb = m.oc.aabb; ra.instance_id = m.oc.instance_id; ra.pose = d_pose; ra.rec = w.rec;
+        launch_pose_rays(s, ra);
+        PoseGradArgs ga{}; ga.rec = w.rec; ga.n_rays = n_rays;
+        ga.seed = drawn ? p.seed : m.oc.sample_seed; ga.stream = drawn ? kStreamPose : (uint32_t)kStreamRender; ga.step = drawn ? key : 0u;
+        ga.w_rgb = p.w_rgb; ga.w_mask = p.w_mask; ga.w_depth = p.w_depth; ga.huber = p.depth_huber; ga.inv_n = 1.f / (float)n_rays;
+        ga.partials = partials; ga.dbg_x = dx; ga.dbg_raw = draw; ga.dbg_g = dg;
+        launch_pose_grad(s, m.lf, m.nd, m.oc, prm, w.frag, it == 0, ga);
+        launch_pose_update(s, partials, grid, 1.f / (float)n_rays, w.out, nullptr, (uint32_t)it, iters >= 0 && it < iters, p.lr_trans, p.lr_rot, d_pose, d_mom);
+    }
+    HIPCHECK(hipGetLastError());
+    std::vector<float> h_out(8 * (size_t)n_eval); float h_pose[16];
+    HIPCHECK(hipMemcpyAsync(h_out.data(), w.out, 32 * (size_t)n_eval, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(h_pose, d_pose, 64, hipMemcpyDeviceToHost, s));
+    std::vector<float> h_dbg;
+    if (dump) { h_dbg.resize((size_t)n_rays * 64 * 10); HIPCHECK(hipMemcpyAsync(h_dbg.data(), w.dbg, h_dbg.size() * 4, hipMemcpyDeviceToHost, s)); }
+    HIPCHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    if (loss) *loss = h_out[0];
+    if (grad6) for (int j = 0; j < 6; ++j) grad6[j] = h_out[1 + j];
+    if (loss_trace) for (int it = 0; it < n_eval; ++it) loss_trace[it] = h_out[8 * (size_t)it];
+    if (pose_out) std::memcpy(pose_out, h_pose, 64);
+    if (dump) {
+        const size_t ns = (size_t)n_rays * 64;
+        if (dump->x) std::memcpy(dump->x, h_dbg.data(), ns * 12);
+        if (dump->raw) std::memcpy(dump->raw, h_dbg.data() + ns * 3, ns * 16);
+        if (dump->dldx) std::memcpy(dump->dldx, h_dbg.data() + ns * 7, ns * 12);
     }
     return MON_OK;
 }

@@ -330,6 +330,31 @@ void launch_fused_render_emit(hipStream_t s, const LevelFast& lt, const NetDims&
         uint32_t n_rays, uint32_t idx_base, float* t, float* attr, uint32_t* cnt, uint16_t* frag_image, int build_image, const uint32_t* skip_bits);
 void launch_scene_composite(hipStream_t s, uint32_t n_rays, uint32_t n_lists, uint32_t cap, const float* t, const float* attr, const uint32_t* cnt,
         const float* dn, float* rgb, float* depth, float* opacity, int32_t* instance);
+// Pose refinement (mon_object_pose_loss / mon_object_refine_pose, kernels_pose.hip).  k_pose_rays: one record of 4 float4 per drawn ray from the pose in
+// device memory (pose[16], world -> object); k_pose_grad<shape>: loss and position gradient, one partial row of 8 floats {g, x x g, loss, 0} per workgroup
+// (pose_grad_grid of them); k_pose_update: the rows summed in a fixed order, x inv_n -> out[8 * it] = {loss, grad6, 0}, optionally the Adam step on pose.
+// Counter-RNG streams of the drawn rays: sample jitter (key ray * 2S + k) and pixel draws (key ray), both keyed by (seed, iteration).
+constexpr uint32_t kStreamPose = 4, kStreamPoseXY = 5;
+constexpr uint32_t kPoseMaxGrid = 1024, kPoseMaxRays = 1u << 22;
+struct PoseRayArgs {
+    const mon_frame_bbox* boxes; const uint32_t* prefix;      // the boxes and the exclusive prefix sums of their areas
+    uint32_t n_obs, n_rays, total, drawn, iteration; uint64_t seed;
+    DatasetPtrs ds; Aabb aabb; uint32_t instance_id; const float* pose; float4* rec;
+};
+struct PoseGradArgs {
+    const float4* rec; uint32_t n_rays;
+    uint64_t seed; uint32_t stream, step;                       // jitter of sample k: rand01(seed, stream, step, base + k)
+    float w_rgb, w_mask, w_depth, huber, inv_n;
+    float* partials;
+    float *dbg_x, *dbg_raw, *dbg_g;                             // mon_debug_pose_samples: [ray][2S][3 | 4 | 3], or nullptr
+};
+// (weak: the host-only ThreadSanitizer build, tests/tsan, links without kernels_pose.hip; pose_refine reports MON_ERR_STATE there)
+__attribute__((weak)) uint32_t pose_grad_grid(uint32_t n_rays);
+__attribute__((weak)) void launch_pose_rays(hipStream_t s, const PoseRayArgs& a);
+__attribute__((weak)) void launch_pose_grad(hipStream_t s, const LevelFast& lt, const NetDims& nd, const ObjectConst& oc, const uint16_t* params, uint16_t* frag_image,
+        int build_image, const PoseGradArgs& p);
+__attribute__((weak)) void launch_pose_update(hipStream_t s, const float* partials, uint32_t n_parts, float inv_n, float* out, float* trace, uint32_t it, int step, float lr_t,
+        float lr_r, float* pose, float* moments);
 // inference on feature-planar level tiles (kernels_tilerender.hip): Render / RenderVideo, GetDensityOnGrid, mesh vertex colours
 constexpr uint32_t kTileChunkJobs = 32768;          // rays (jobs of 2S = 64 samples) per chunk of the tile render
 bool tile_render_supported(const LevelTable& lt, const NetDims& nd);
@@ -435,6 +460,7 @@ struct Model {
     bool tile_ok = false;        // the inference side may run on feature-planar level tiles (tile_render_supported)
     std::atomic<int> rskip_on{ 0 }; std::atomic<float> rskip_alpha{ 1e-3f };      // render skipping: the switch (read once per render call)
     RenderSkipSide rskip;                                                             // ... and its train-stream side
+    struct PoseWs* pose_ws[2] = { nullptr, nullptr };                                // pose refinement scratch per side (model.cpp), made on first use
     uint64_t weights_epoch = 0;  // process-wide unique stamp of the weights' current content (a new one after every train call / set_params / EMA catch-up):
                                  // the tile render's per-device workspace keeps its tile image while the stamp it was built for is current
     bool next_ready = false;     // fused backend: candidates + fragment image of the coming iteration were already produced by the last k_optimizer
@@ -481,6 +507,13 @@ struct SceneDump { uint32_t list; float* t; float* alpha; float* rgb; uint32_t* 
 int scene_render(Model* const* ms, size_t n, int side, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity, int32_t* instance,
                  const int32_t* ids, const SceneDump* dump);
 bool model_has_snapshot(Model& m);      // the object has an inference side and has published weights
+// Pose refinement: iters < 0 = one evaluation (mon_object_pose_loss: loss, grad6, jitter / draws of `iteration`), else iters Adam steps from Tow16
+// (mon_object_refine_pose: the final pose into pose_out, loss_trace[iters + 1] may be nullptr).  dump (mon_debug_pose_samples, may be nullptr): per drawn ray
+// of the evaluation, host arrays [ray][2S] of positions (object frame, 3), raw outputs (4) and dL/dx (3); any of them may be nullptr.
+struct PoseDump { float* x; float* raw; float* dldx; };
+int pose_refine(Model& m, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params& p, int iters,
+                uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const PoseDump* dump);
+uint32_t pose_n_rays(const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params& p);      // rays of one evaluation
 int model_publish_snapshot(Model& m);
 int model_render_snapshot(Model& m, mon_frame_bbox box, const float* pose16, int pose_is_Toc, float* rgb, float* depth, float* mask, uint32_t* snapshot_step);
 int level_table_build(const mon_config& c, LevelTable& lt, NetDims& nd, uint32_t& n_grid);
