@@ -34,6 +34,14 @@ int mon_debug_yaml_number(const char* text, const char* key, double* value);
 /* Occupancy-grid bookkeeping of an object created with occupancy_skip (model.cpp maybe_refresh_occupancy): out[0] = iteration of the last refresh
  * (0 = none yet), out[1] = first iteration at or after which the next one is due. */
 int mon_debug_occupancy_state(mon_object* obj, uint32_t out[2]);
+/* Training's occupancy grid (64^3 bits, x fastest, 8192 words; bit n of word w = cell 32 w + n): `raw` before and `dilated` after the one-cell dilation (the
+ * grid k_fused_train uses; before the first refresh or pin both are the warm-up's all-ones grid), the raw-density threshold, and the number of live-sample
+ * lists of the level-tile chain (0: the object has none).  Any output may be NULL.  MON_ERR_STATE when the object has no grid. */
+int mon_debug_occupancy_grid(mon_object* obj, uint32_t* raw, uint32_t* dilated, float* raw_threshold, uint32_t* n_parts);
+/* Pins a caller-supplied training grid (8192 words) in place of the object's own, also before the warm-up: the grid is in use from the next iteration, the
+ * positions already sampled for it are sampled again, and no scheduled refresh replaces it.  bits = NULL unpins: before the warm-up the all-ones grid
+ * returns, afterwards a refresh is due at the next iteration.  MON_ERR_STATE when the object has no grid. */
+int mon_debug_set_train_occupancy(mon_object* obj, const uint32_t* bits);
 
 /* Tile render bookkeeping (ro-map_amd/csrc/kernels_tilerender.hip): jobs (rays that hit the object's box, 2S samples each) of the LAST crop rendered on the
  * object's device through the per-device workspace of `side` (0: train-stream renders, 1: the inference stream); what bench.py's evaluated-sample count is. */

@@ -303,6 +303,9 @@ typedef struct {
     /* NeRF_Model::Step schedule (forward_backward_compacted) instead of Step_No_Compacted; samples in the compacted batch */
     int step_variant; uint32_t n_compacted;
     orc_xwgen xw; float* xw_buf; uint32_t xw_iter;     /* xw_iter: the iteration xw_buf holds (UINT32_MAX: none) */
+    /* occupancy grid (opt-in skipping, see the occupancy section below): the grid forward_backward uses (occ_on), the per-sample live mask of the last
+     * forward_backward, the automatic refresh schedule */
+    uint32_t* occ; int occ_on, occ_auto; uint32_t occ_refreshed_iter, occ_next_refresh; uint8_t* live;
 } orc_model;
 
 static uint32_t mlp_params(int W, int NH, int Epad) { return (uint32_t)(W * Epad + (NH - 1) * W * W + ORC_OUT_PAD * W); }
@@ -358,6 +361,7 @@ orc_model* orc_create(const orc_config* c) {
     m->dO = (uint16_t*)calloc(B * ORC_OUT, 2); m->dHid = (uint16_t*)calloc(B * m->W * m->NH, 2); m->dE = (uint16_t*)calloc(B * m->Epad, 2);
     m->rgb_ray = (float*)calloc(R * 3, 4); m->depth_ray = (float*)calloc(R, 4); m->mask_ray = (float*)calloc(R, 4); m->loss_ray = (float*)calloc(R, 4);
     m->xw_iter = 0xffffffffu;
+    m->live = (uint8_t*)malloc(B); memset(m->live, 1, B);
     if (ORC_RNG_STREAM(c)) {
         xwgen_init(&m->xw, 0ull /* the generator's default seed: nerf_model.cu never sets one */, ORC_RNG_STREAM(c) == 2u, ORC_RNG_LANES(c));
         m->xw_buf = (float*)calloc((5 + (size_t)m->S) * R, 4);
@@ -370,7 +374,7 @@ void orc_destroy(orc_model* m) {
         m->ray_o, m->ray_d, m->ray_dn, m->ray_tmin, m->ray_tmax, m->target, m->target_depth, m->bgcol, m->ray_flag, m->pts, m->tdist,
         m->E, m->Hid, m->O, m->dO, m->dHid, m->dE, m->rgb_ray, m->depth_ray, m->mask_ray, m->loss_ray };
     for (size_t i = 0; i < sizeof(p) / sizeof(p[0]); ++i) free(p[i]);
-    free(m->xw.lane); free(m->xw_buf);
+    free(m->xw.lane); free(m->xw_buf); free(m->occ); free(m->live);
     free(m);
 }
 uint32_t orc_n_params(const orc_model* m) { return m->n_params; }
@@ -382,11 +386,12 @@ int orc_epad(const orc_model* m) { return m->Epad; }
 
 /* which: 0 master f32, 1 half u16, 2 ema u16, 3 m1, 4 m2, 5 steps, 6 gmlp f32, 7 ggrid f32, 8 ggrid_abs f32, 9 ggrid_h u16,
  * 10 pts, 11 tdist, 12 E, 13 Hid, 14 O, 15 dO, 16 dHid, 17 dE, 18 rgb_ray, 19 depth_ray, 20 mask_ray, 21 loss_ray,
- * 22 ray_o, 23 ray_d, 24 ray_tmin, 25 ray_tmax, 26 target, 27 target_depth, 28 bgcol, 29 ray_flag, 30 sel, 31 ray_dn */
+ * 22 ray_o, 23 ray_d, 24 ray_tmin, 25 ray_tmax, 26 target, 27 target_depth, 28 bgcol, 29 ray_flag, 30 sel, 31 ray_dn,
+ * 32 live u8 [B] (occupancy grid: the sample was evaluated in the last forward_backward) */
 const void* orc_buffer(const orc_model* m, int which) {
     const void* t[] = { m->master, m->half, m->ema, m->m1, m->m2, m->steps, m->gmlp, m->ggrid, m->ggrid_abs, m->ggrid_h,
         m->pts, m->tdist, m->E, m->Hid, m->O, m->dO, m->dHid, m->dE, m->rgb_ray, m->depth_ray, m->mask_ray, m->loss_ray,
-        m->ray_o, m->ray_d, m->ray_tmin, m->ray_tmax, m->target, m->target_depth, m->bgcol, m->ray_flag, m->sel, m->ray_dn };
+        m->ray_o, m->ray_d, m->ray_tmin, m->ray_tmax, m->target, m->target_depth, m->bgcol, m->ray_flag, m->sel, m->ray_dn, m->live };
     if (which < 0 || which >= (int)(sizeof(t) / sizeof(t[0]))) return NULL;
     return t[which];
 }
@@ -570,21 +575,22 @@ void orc_mlp_forward(const orc_model* m, const uint16_t* params, const uint16_t*
 static inline float logistic(float x) { return 1.0f / (1.0f + expf(-x)); }
 static inline float clampf(float x, float a, float b) { return x < a ? a : (x > b ? b : x); }
 
-/* VolumeRender nerf_model.cu:735-815 (one ray).  out4: fp16 [S][4]; t: [S]. */
-static void composite_ray(const uint16_t* out4, const float* t, int S, const float* bg, float* rgb, float* depth, float* mask) {
+/* VolumeRender nerf_model.cu:735-815 (one ray).  out4: fp16 [S][4]; t: [S].  live: NULL, or the occupancy grid's verdict per sample (a dead sample has
+ * alpha 0: kernels_fused.hip k_fused_train, `(!OCC || live) ? 1 - exp(-sigma dt) : 0`). */
+static void composite_ray(const uint16_t* out4, const float* t, int S, const float* bg, float* rgb, float* depth, float* mask, const uint8_t* live) {
     float T = 1.0f, r[3] = { 0, 0, 0 }, dep = 0.0f, last = 0.0f;          /* :770 last_distance = 0 (first dt measured from the origin) */
     for (int n = 0; n < S; ++n) {
         if (T < 1e-4f) break;
         float c0 = logistic(h2f(out4[4 * n])), c1 = logistic(h2f(out4[4 * n + 1])), c2 = logistic(h2f(out4[4 * n + 2]));
         float cur = t[n], dt = cur - last, sigma = expf(h2f(out4[4 * n + 3]));        /* :49 unclamped */
-        float alpha = 1.0f - expf(-sigma * dt), w = alpha * T;
+        float alpha = (live && !live[n]) ? 0.0f : 1.0f - expf(-sigma * dt), w = alpha * T;
         r[0] += w * c0; r[1] += w * c1; r[2] += w * c2; dep += w * cur; T *= (1.0f - alpha); last = cur;
     }
     rgb[0] = r[0] + T * bg[0]; rgb[1] = r[1] + T * bg[1]; rgb[2] = r[2] + T * bg[2]; *depth = dep; *mask = 1.0f - T;
 }
-/* VolumeRenderGradient_No_Compacted nerf_model.cu:817-954 (one ray).  dO pre-zeroed (:1578). */
+/* VolumeRenderGradient_No_Compacted nerf_model.cu:817-954 (one ray).  dO pre-zeroed (:1578).  live: as composite_ray; a dead sample keeps dL/dO = 0. */
 static float gradient_ray(const uint16_t* out4, const float* t, int S, int nRays, float loss_scale, int is_obj,
-                          const float* target, float target_depth, const float* rgb_ray, float depth_ray, float mask_ray, uint16_t* dO) {
+                          const float* target, float target_depth, const float* rgb_ray, float depth_ray, float mask_ray, uint16_t* dO, const uint8_t* live) {
     float g[3], lsum = 0.0f;
     for (int k = 0; k < 3; ++k) { float d = rgb_ray[k] - target[k]; lsum += d * d; g[k] = 2.0f * d; }       /* :78-84 */
     float mean_loss = lsum / 3.0f, dl_dd = 0.0f;
@@ -596,9 +602,11 @@ static float gradient_ray(const uint16_t* out4, const float* t, int S, int nRays
         float v[4]; for (int k = 0; k < 4; ++k) v[k] = h2f(out4[4 * n + k]);
         float c[3] = { logistic(v[0]), logistic(v[1]), logistic(v[2]) };
         float cur = t[n], dt = cur - last, sigma = expf(v[3]);
-        float alpha = 1.0f - expf(-sigma * dt), w = alpha * T;
+        const int dead = live && !live[n];
+        float alpha = dead ? 0.0f : 1.0f - expf(-sigma * dt), w = alpha * T;
         for (int k = 0; k < 3; ++k) r2[k] += w * c[k];
         d2 += w * cur; T *= (1.0f - alpha);
+        if (dead) { last = cur; continue; }
         float suf[3] = { rgb_ray[0] - r2[0], rgb_ray[1] - r2[1], rgb_ray[2] - r2[2] };
         for (int k = 0; k < 3; ++k) dO[4 * n + k] = f2h(ls * ((w * g[k]) * (c[k] * (1.0f - c[k]))));        /* :916-920 */
         float dsig = expf(clampf(v[3], -15.0f, 15.0f));                                                   /* :60 */
@@ -618,22 +626,29 @@ static float gradient_ray(const uint16_t* out4, const float* t, int S, int nRays
 }
 /* stage entry points for KATs */
 void orc_composite(const uint16_t* out4, const float* t, int S, const float* bg, float* rgb, float* depth, float* mask) {
-    composite_ray(out4, t, S, bg, rgb, depth, mask); }
+    composite_ray(out4, t, S, bg, rgb, depth, mask, NULL); }
 float orc_gradient(const uint16_t* out4, const float* t, int S, int nRays, float loss_scale, int is_obj, const float* target, float target_depth,
                    const float* rgb_ray, float depth_ray, float mask_ray, uint16_t* dO) {
     memset(dO, 0, (size_t)S * 4 * 2);
-    return gradient_ray(out4, t, S, nRays, loss_scale, is_obj, target, target_depth, rgb_ray, depth_ray, mask_ray, dO);
+    return gradient_ray(out4, t, S, nRays, loss_scale, is_obj, target, target_depth, rgb_ray, depth_ray, mask_ray, dO, NULL);
 }
 
 static int g_parallel_scatter = 0;
 void orc_set_parallel_scatter(int on) { g_parallel_scatter = on; }
 
 /* ------------------------------------------------------------------ Step_No_Compacted nerf_model.cu:1552-1607 */
-static void network_forward(orc_model* m) {          /* encode + MLP of every sample of m->pts (tcnn forward / inference, call sites :1557, :1509) */
+static int occ_cell_live(const uint32_t* bits, const float* x);
+/* encode + MLP of every sample of m->pts (tcnn forward / inference, call sites :1557, :1509).  occ: the occupancy grid, or NULL; a dead sample is not
+ * evaluated and keeps zero features, hidden activations and outputs (the HIP kernel's masked loads give zero features, and a bias-free MLP maps them to zero;
+ * a ray without a live sample skips the MLP altogether).  m->live records the verdicts. */
+static void network_forward(orc_model* m, const uint32_t* occ) {
     const int R = m->R, S = m->S, W = m->W, NH = m->NH, Ep = m->Epad; const size_t B = (size_t)R * S;
     const uint16_t* wt = m->half; const uint16_t* table = m->half + m->n_mlp;
     #pragma omp parallel for schedule(static)
     for (long s = 0; s < (long)B; ++s) {
+        m->live[s] = occ ? (uint8_t)occ_cell_live(occ, m->pts + 3 * s) : 1u;
+        if (!m->live[s]) { memset(m->E + (size_t)s * Ep, 0, (size_t)Ep * 2); memset(m->Hid + (size_t)s * W * NH, 0, (size_t)W * NH * 2);
+            memset(m->O + (size_t)s * 4, 0, 8); continue; }
         encode_one(m, table, m->pts + 3 * s, m->E + (size_t)s * Ep);
         mlp_forward_one(m, wt, m->E + (size_t)s * Ep, m->Hid + (size_t)s * W * NH, m->O + (size_t)s * 4);
     }
@@ -643,14 +658,16 @@ static void forward_backward_compacted(orc_model* m);
 static void forward_backward(orc_model* m) {
     if (m->step_variant) { forward_backward_compacted(m); return; }
     const int R = m->R, S = m->S; const size_t B = (size_t)R * S;
-    network_forward(m);
+    const uint32_t* occ = m->occ_on ? m->occ : NULL;
+    network_forward(m, occ);
     memset(m->dO, 0, B * 4 * 2);                                                 /* :1578 */
     #pragma omp parallel for schedule(static)
     for (long j = 0; j < R; ++j) {
         const uint16_t* o4 = m->O + (size_t)j * S * 4; const float* t = m->tdist + (size_t)j * S;
-        composite_ray(o4, t, S, m->bgcol + 3 * j, m->rgb_ray + 3 * j, m->depth_ray + j, m->mask_ray + j);
+        const uint8_t* lv = occ ? m->live + (size_t)j * S : NULL;
+        composite_ray(o4, t, S, m->bgcol + 3 * j, m->rgb_ray + 3 * j, m->depth_ray + j, m->mask_ray + j, lv);
         m->loss_ray[j] = gradient_ray(o4, t, S, R, m->cfg.loss_scale, m->ray_flag[j], m->target + 3 * j, m->target_depth[j],
-                                      m->rgb_ray + 3 * j, m->depth_ray[j], m->mask_ray[j], m->dO + (size_t)j * S * 4);
+                                      m->rgb_ray + 3 * j, m->depth_ray[j], m->mask_ray[j], m->dO + (size_t)j * S * 4, lv);
     }
     double ls = 0; for (int j = 0; j < R; ++j) ls += m->loss_ray[j];             /* SumLoss :1231-1253 + :1650-1658 */
     m->loss = (float)(ls / R);
@@ -670,7 +687,7 @@ static void forward_backward(orc_model* m) {
  * afterwards. */
 static void forward_backward_compacted(orc_model* m) {
     const int R = m->R, S = m->S; const size_t B = (size_t)R * S; const orc_config* c = &m->cfg;
-    network_forward(m);
+    network_forward(m, NULL);
     uint32_t* steps = (uint32_t*)calloc((size_t)R + 1, 4);
     float bg[3]; for (int a = 0; a < 3; ++a) bg[a] = batch_rand(m, 1, m->iter, (uint32_t)a);
     const float ls = c->loss_scale / (float)R;
@@ -721,7 +738,7 @@ static void forward_backward_compacted(orc_model* m) {
     }
     memcpy(m->pts, pc, B * 3 * 4); memcpy(m->dO, dc, B * 4 * 2); m->n_compacted = n_comp;
     free(pc); free(dc); free(steps);
-    network_forward(m);                                                          /* :1545 forward of the compacted batch (keeps E / hidden activations) */
+    network_forward(m, NULL);                                                          /* :1545 forward of the compacted batch (keeps E / hidden activations) */
     network_backward(m);                                                         /* :1547 */
 }
 
@@ -868,7 +885,9 @@ void orc_optimizer_step_with_f32(orc_model* m, const float* gmlp, const float* g
 }
 
 /* NeRF_Model::Train_Step body, nerf_model.cu:1635-1648 (one iteration). Returns n_valid. */
+static void occ_maybe_refresh(orc_model* m, uint32_t iter);
 uint32_t orc_train_step(orc_model* m) {
+    occ_maybe_refresh(m, m->iter);                                       /* (occupancy grid, opt-in: before the iteration it is due at) */
     generate_batch(m);
     m->iter++;
     if (m->n_valid == 0) return 0;
@@ -934,6 +953,91 @@ void orc_density_grid(const orc_model* m, int rx, int ry, int rz, int use_ema, f
         encode_one(m, prm + m->n_mlp, p, E); mlp_forward_one(m, prm, E, hid, o4); out[i] = h2f(o4[3]);
     }
 }
+
+/* ------------------------------------------------------------------ occupancy grid (opt-in forward-pass skipping, mon_config::occupancy_skip)
+ * The reference has no such grid (it evaluates 32 uniform samples of every ray, nerf_model.cu:536-566): this restates the rule of THIS repository,
+ *   cell look-up      device_common.h:31-40 occ_cell_live: cell = (int)(x * 64) per axis (truncation), clamped to [0, 63]; x fastest;
+ *                     bit n of word w = cell 32 w + n
+ *   threshold         model.cpp:659-672: dt = |box diagonal| / S, raw_threshold = logf(1e-3 / max(dt, 1e-6)) (alpha of one sample interval < 1e-3)
+ *   grid update       kernels_render.hip:107-160 k_occ_density: raw density (output channel 3, fp16) of the CURRENT training weights at the cell centre
+ *                     (c + 0.5) / 64, occupied when > threshold; k_occ_dilate: a cell is live when it or one of its 26 neighbours is occupied
+ *   use               kernels_fused.hip k_fused_train<OCC>: a dead sample is not evaluated (zero features, alpha 0, dL/dO 0) -- forward_backward above
+ *   schedule          model.cpp:1062-1075 maybe_refresh_occupancy, asked before every iteration (the eager path): the first refresh before iteration 256;
+ *                     then due at the first iteration >= (iter / every + 1) every, every = 32 / 128 / 512 below 512 / below 2048 / after
+ * Numerics: the HIP density sums the MLP in MFMA order, this restatement in one fmaf chain -- a cell whose density lies within a few fp16 ulp of the
+ * threshold may come out differently (the ambiguity band the GPU tests allow). */
+#define ORC_OCC_RES 64
+#define ORC_OCC_WORDS (ORC_OCC_RES * ORC_OCC_RES * ORC_OCC_RES / 32)
+#define ORC_OCC_WARMUP 256u
+#define ORC_OCC_INTERVAL 32u
+uint32_t orc_occupancy_cell(const float* x) {
+    int c[3];
+    for (int d = 0; d < 3; ++d) { const int v = (int)(x[d] * (float)ORC_OCC_RES); c[d] = v < 0 ? 0 : (v > ORC_OCC_RES - 1 ? ORC_OCC_RES - 1 : v); }
+    return ((uint32_t)c[2] * ORC_OCC_RES + (uint32_t)c[1]) * ORC_OCC_RES + (uint32_t)c[0];
+}
+static int occ_cell_live(const uint32_t* bits, const float* x) { const uint32_t cell = orc_occupancy_cell(x); return (int)((bits[cell >> 5] >> (cell & 31u)) & 1u); }
+float orc_occupancy_threshold(const orc_model* m) {
+    float diag2 = 0.0f;
+    for (int a = 0; a < 3; ++a) { const float e = m->amax[a] - m->amin[a]; diag2 += e * e; }
+    const float dt = sqrtf(diag2) / (float)m->S;
+    return logf(1e-3f / fmaxf(dt, 1e-6f));
+}
+/* one-cell dilation over all 26 neighbours (cells outside the grid count as empty); raw and out: 8192 words each, distinct */
+void orc_occupancy_dilate(const uint32_t* raw, uint32_t* out) {
+    const int N = ORC_OCC_RES;
+    #pragma omp parallel for schedule(static)
+    for (long w = 0; w < (long)ORC_OCC_WORDS; ++w) {           /* one word per iteration: no two threads write one word */
+        uint32_t acc = 0u;
+        for (int n = 0; n < 32; ++n) {
+            const long cell = 32 * w + n; const int x = (int)(cell % N), y = (int)((cell / N) % N), z = (int)(cell / ((long)N * N)); uint32_t on = 0u;
+            for (int dz = -1; dz <= 1 && !on; ++dz) for (int dy = -1; dy <= 1 && !on; ++dy) for (int dx = -1; dx <= 1 && !on; ++dx) {
+                const int a = x + dx, b = y + dy, c = z + dz;
+                if (a < 0 || a >= N || b < 0 || b >= N || c < 0 || c >= N) continue;
+                const uint32_t k = ((uint32_t)c * N + (uint32_t)b) * N + (uint32_t)a; on = (raw[k >> 5] >> (k & 31u)) & 1u;
+            }
+            acc |= on << n;
+        }
+        out[w] = acc;
+    }
+}
+/* the grid from the model's current fp16 training weights; any output may be NULL */
+void orc_occupancy_update(const orc_model* m, uint32_t* raw_bits, uint32_t* dilated_bits, float* raw_density) {
+    const int N = ORC_OCC_RES; const size_t n = (size_t)N * N * N; const float thr = orc_occupancy_threshold(m);
+    float* dens = (float*)malloc(n * 4);
+    #pragma omp parallel for schedule(static)
+    for (long cell = 0; cell < (long)n; ++cell) {
+        const int x = (int)(cell % N), y = (int)((cell / N) % N), z = (int)(cell / ((long)N * N));
+        const float p[3] = { ((float)x + 0.5f) / (float)N, ((float)y + 0.5f) / (float)N, ((float)z + 0.5f) / (float)N };
+        uint16_t E[2 * ORC_MAX_LEVELS + 16], hid[256], o4[4];
+        encode_one(m, m->half + m->n_mlp, p, E); mlp_forward_one(m, m->half, E, hid, o4); dens[cell] = h2f(o4[3]);
+    }
+    uint32_t* raw = (uint32_t*)calloc(ORC_OCC_WORDS, 4);
+    for (size_t cell = 0; cell < n; ++cell) if (dens[cell] > thr) raw[cell >> 5] |= 1u << (cell & 31u);
+    if (raw_bits) memcpy(raw_bits, raw, ORC_OCC_WORDS * 4);
+    if (dilated_bits) orc_occupancy_dilate(raw, dilated_bits);
+    if (raw_density) memcpy(raw_density, dens, n * 4);
+    free(raw); free(dens);
+}
+/* the grid forward_backward uses: a copy of bits (8192 words), or NULL = every sample live (also ends the automatic refreshes) */
+void orc_set_occupancy(orc_model* m, const uint32_t* bits) {
+    m->occ_auto = 0;
+    if (!bits) { m->occ_on = 0; return; }
+    if (!m->occ) m->occ = (uint32_t*)malloc(ORC_OCC_WORDS * 4);
+    memcpy(m->occ, bits, ORC_OCC_WORDS * 4); m->occ_on = 1;
+}
+/* the object's own grid, refreshed on the eager schedule by orc_train_step (before warm-up every sample is live) */
+void orc_set_occupancy_auto(orc_model* m, int on) {
+    m->occ_auto = on; m->occ_on = 0; m->occ_refreshed_iter = 0; m->occ_next_refresh = 0;
+    if (on && !m->occ) m->occ = (uint32_t*)malloc(ORC_OCC_WORDS * 4);
+}
+static void occ_maybe_refresh(orc_model* m, uint32_t iter) {
+    if (!m->occ_auto || iter < ORC_OCC_WARMUP || iter < m->occ_next_refresh) return;
+    orc_occupancy_update(m, NULL, m->occ, NULL);
+    const uint32_t every = ORC_OCC_INTERVAL * (iter < 512u ? 1u : iter < 2048u ? 4u : 16u);
+    m->occ_on = 1; m->occ_refreshed_iter = iter; m->occ_next_refresh = (iter / every + 1u) * every;
+}
+/* out[0] = iteration of the last refresh (0: none), out[1] = first iteration at or after which the next one is due (mon_debug_occupancy_state) */
+void orc_occupancy_state(const orc_model* m, uint32_t out[2]) { out[0] = m->occ_refreshed_iter; out[1] = m->occ_next_refresh; }
 
 /* compute_mesh_vertex_colors nerf_model.cu:2050-2069: WarpPoint (:140-144) -> inference weights -> logistic rgb (:328-339) */
 void orc_mesh_colors(const orc_model* m, const float* verts, uint32_t n, int use_ema, float* colors) {

@@ -56,7 +56,7 @@ _lib = None
 # buffer ids of orc_buffer()
 BUF = dict(master=0, half=1, ema=2, m1=3, m2=4, steps=5, gmlp=6, ggrid=7, ggrid_abs=8, ggrid_h=9, pts=10, tdist=11, E=12, Hid=13, O=14, dO=15,
            dHid=16, dE=17, rgb_ray=18, depth_ray=19, mask_ray=20, loss_ray=21, ray_o=22, ray_d=23, ray_t0=24, ray_t1=25, target=26,
-           target_depth=27, bgcol=28, ray_flag=29, sel=30, ray_dn=31)
+           target_depth=27, bgcol=28, ray_flag=29, sel=30, ray_dn=31, live=32)
 
 
 def lib():
@@ -105,6 +105,13 @@ def lib():
         L.orc_mesh_to_cpu.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.orc_mesh_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
         L.orc_set_parallel_scatter.argtypes = [C.c_int]; L.orc_advance_iter.argtypes = [C.c_void_p]
+        # occupancy grid (mon_oracle.c, occupancy section)
+        L.orc_occupancy_cell.restype = C.c_uint32; L.orc_occupancy_cell.argtypes = [C.c_void_p]
+        L.orc_occupancy_threshold.restype = C.c_float; L.orc_occupancy_threshold.argtypes = [C.c_void_p]
+        L.orc_occupancy_dilate.argtypes = [C.c_void_p, C.c_void_p]
+        L.orc_occupancy_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_set_occupancy.argtypes = [C.c_void_p, C.c_void_p]; L.orc_set_occupancy_auto.argtypes = [C.c_void_p, C.c_int]
+        L.orc_occupancy_state.argtypes = [C.c_void_p, C.c_void_p]
         # the checker's loops are small: a modest team beats one thread per hardware thread on a 256-thread host
         L.orc_set_threads(int(os.environ.get("MON_ORACLE_THREADS", min(16, os.cpu_count() or 1))))
         _lib = L
@@ -200,10 +207,33 @@ class OracleModel:
                       O=(np.uint16, B * 4), dO=(np.uint16, B * 4), dHid=(np.uint16, B * self.W * self.NH), dE=(np.uint16, B * self.Epad),
                       rgb_ray=(np.float32, R * 3), depth_ray=(np.float32, R), mask_ray=(np.float32, R), loss_ray=(np.float32, R),
                       ray_o=(np.float32, R * 3), ray_d=(np.float32, R * 3), ray_t0=(np.float32, R), ray_t1=(np.float32, R), target=(np.float32, R * 3),
-                      target_depth=(np.float32, R), bgcol=(np.float32, R * 3), ray_flag=(np.uint8, R), sel=(np.uint32, R), ray_dn=(np.float32, R))
+                      target_depth=(np.float32, R), bgcol=(np.float32, R * 3), ray_flag=(np.uint8, R), sel=(np.uint32, R), ray_dn=(np.float32, R),
+                      live=(np.uint8, B))
         dt, cnt = shapes[name]
         ptr = self.L.orc_buffer(self.h, BUF[name])
         return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dt))), shape=(cnt,)).copy()
+
+    # ---- occupancy grid (64^3 bits, x fastest, 8192 uint32 words; bit n of word w = cell 32 w + n)
+    @property
+    def occupancy_threshold(self):
+        return self.L.orc_occupancy_threshold(self.h)
+
+    def occupancy_update(self):
+        """The grid from the current fp16 training weights: (raw bits, dilated bits, raw density per cell [64^3])."""
+        raw = np.zeros(OCC_WORDS, np.uint32); dil = np.zeros(OCC_WORDS, np.uint32); dens = np.zeros(64 ** 3, np.float32)
+        self.L.orc_occupancy_update(self.h, _p(raw), _p(dil), _p(dens)); return raw, dil, dens
+
+    def set_occupancy(self, bits):
+        """forward_backward evaluates only the samples whose cell is live in `bits` (None: every sample; also ends automatic refreshes)."""
+        b = None if bits is None else np.ascontiguousarray(bits, np.uint32)
+        assert b is None or b.size == OCC_WORDS
+        self.L.orc_set_occupancy(self.h, _p(b))
+
+    def set_occupancy_auto(self, on=True):
+        self.L.orc_set_occupancy_auto(self.h, int(bool(on)))
+
+    def occupancy_state(self):
+        out = np.zeros(2, np.uint32); self.L.orc_occupancy_state(self.h, _p(out)); return int(out[0]), int(out[1])
 
     def render(self, box, pose16, pose_is_Toc=False, use_ema=True):
         FrameId, x, y, h, w = (int(v) for v in box)
@@ -230,6 +260,20 @@ class OracleModel:
         mesh["colors_f32"] = col; mesh["density"] = dens
         mesh["normals"], mesh["colors"] = mesh_to_cpu(mesh["normals_raw"], col)
         return mesh
+
+
+OCC_WORDS = 64 ** 3 // 32
+
+
+def occupancy_dilate(raw_bits):
+    r = np.ascontiguousarray(raw_bits, np.uint32); assert r.size == OCC_WORDS
+    out = np.zeros(OCC_WORDS, np.uint32); lib().orc_occupancy_dilate(_p(r), _p(out)); return out
+
+
+def occupancy_cell(x):
+    """Cell index of a warped position (occ_cell_live's look-up: truncation, clamp to [0, 63], x fastest)."""
+    p = np.ascontiguousarray(x, np.float32); assert p.size == 3
+    return int(lib().orc_occupancy_cell(_p(p)))
 
 
 def marching_cubes(density, res3, thresh, amin, amax):

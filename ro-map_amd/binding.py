@@ -156,6 +156,8 @@ _DIAG_SIGS = {
     "mon_debug_yaml_number": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.c_double)]),
     "mon_debug_render_jobs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32)]),
     "mon_debug_occupancy_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "mon_debug_occupancy_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "mon_debug_set_train_occupancy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mon_debug_set_render_grid": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mon_debug_scene_samples": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, MonBBox, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_debug_scene_composite": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -561,6 +563,19 @@ class ObjectNeRF:
 
     def occupancy_state(self):
         out = (C.c_uint32 * 2)(); _check(diag_lib().mon_debug_occupancy_state(self.h, out)); return int(out[0]), int(out[1])
+
+    def occupancy_grid(self):
+        """Training's occupancy grid: (raw bits, dilated bits, raw-density threshold, number of live-sample lists); 8192 words each, x fastest."""
+        raw = np.empty(8192, np.uint32); dil = np.empty(8192, np.uint32); thr = C.c_float(0); n_parts = C.c_uint32(0)
+        _check(diag_lib().mon_debug_occupancy_grid(self.h, _p(raw), _p(dil), C.byref(thr), C.byref(n_parts)))
+        return raw, dil, float(thr.value), int(n_parts.value)
+
+    def set_train_occupancy(self, bits):
+        """Pins a training occupancy grid (8192 words) in place of the object's own; None unpins."""
+        if bits is None:
+            _check(diag_lib().mon_debug_set_train_occupancy(self.h, None)); return
+        w = np.ascontiguousarray(bits, np.uint32); assert w.size == 8192
+        _check(diag_lib().mon_debug_set_train_occupancy(self.h, _p(w)))
 
     def render_jobs(self, side=0):
         """Jobs (rays that hit the box) of the last crop the tile render evaluated on this object's device (side 0: train stream, 1: inference stream)."""

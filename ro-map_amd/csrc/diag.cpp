@@ -167,6 +167,38 @@ int mon_debug_occupancy_state(mon_object* o, uint32_t out[2]) {
     if (!o || !o->m || !out) { mon::set_error("debug_occupancy_state: null argument"); return MON_ERR_ARG; }
     out[0] = o->m->occ_refreshed_iter; out[1] = o->m->occ_next_refresh; return MON_OK;
 }
+int mon_debug_occupancy_grid(mon_object* o, uint32_t* raw, uint32_t* dilated, float* raw_threshold, uint32_t* n_parts) {
+    if (!o || !o->m) { mon::set_error("debug_occupancy_grid: null object"); return MON_ERR_ARG; }
+    mon::Model& m = *o->m;
+    if (!m.d_occ) { mon::set_error("debug_occupancy_grid: the object has no occupancy grid"); return MON_ERR_STATE; }
+    mon::model_leave_lane(m);
+    HIPCHECK(mon::use_device(m.device)); HIPCHECK(hipStreamSynchronize(m.train_stream));
+    constexpr size_t bytes = (size_t)mon::kOccWords * 4;
+    // (nothing has written the raw grid before the first refresh or pin: the grid in use is the warm-up's all-ones one)
+    if (raw) HIPCHECK(hipMemcpy(raw, m.occ_refreshed_iter ? m.d_occ_tmp : m.d_occ, bytes, hipMemcpyDeviceToHost));
+    if (dilated) HIPCHECK(hipMemcpy(dilated, m.d_occ, bytes, hipMemcpyDeviceToHost));
+    if (raw_threshold) *raw_threshold = m.occ_raw_threshold;
+    if (n_parts) { const uint32_t B = m.oc.R * m.oc.S, spw = mon::encode_tiles_spw(B); *n_parts = m.d_live_idx ? (B + spw - 1u) / spw : 0u; }
+    return MON_OK;
+}
+int mon_debug_set_train_occupancy(mon_object* o, const uint32_t* bits) {
+    if (!o || !o->m) { mon::set_error("debug_set_train_occupancy: null object"); return MON_ERR_ARG; }
+    mon::Model& m = *o->m;
+    if (!m.d_occ) { mon::set_error("debug_set_train_occupancy: the object has no occupancy grid"); return MON_ERR_STATE; }
+    mon::model_leave_lane(m);
+    HIPCHECK(mon::use_device(m.device)); HIPCHECK(hipStreamSynchronize(m.train_stream));
+    constexpr size_t bytes = (size_t)mon::kOccWords * 4;
+    if (bits) {
+        HIPCHECK(hipMemcpy(m.d_occ, bits, bytes, hipMemcpyHostToDevice)); HIPCHECK(hipMemcpy(m.d_occ_tmp, bits, bytes, hipMemcpyHostToDevice));
+        m.occ_pinned = true; if (!m.occ_refreshed_iter) m.occ_refreshed_iter = m.h_state.iter > 1u ? m.h_state.iter : 1u;      // in use from now on
+    } else if (m.occ_pinned) {
+        m.occ_pinned = false;
+        if (m.h_state.iter < (uint32_t)mon::kOccWarmup) { HIPCHECK(hipMemset(m.d_occ, 0xff, bytes)); m.occ_refreshed_iter = 0; }
+        m.occ_next_refresh = 0;                              // (after the warm-up: due at the next iteration)
+    }
+    m.points_ready = false;                                  // the positions sampled ahead carry the old grid's live bits and lists, as after a refresh
+    return MON_OK;
+}
 int mon_debug_render_jobs(mon_object* o, int side, uint32_t* jobs) {
     if (!o || !o->m || !jobs) { mon::set_error("debug_render_jobs: null argument"); return MON_ERR_ARG; }
     if (!o->m->tile_ok) { mon::set_error("debug_render_jobs: this object does not render on level tiles"); return MON_ERR_STATE; }

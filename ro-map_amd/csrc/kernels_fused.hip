@@ -506,11 +506,17 @@ static void fused_train_t(hipStream_t s, const FusedArgs& a, uint32_t grid, int 
                 S::SMEM_BYTES);
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fused_train<EPAD, W, NH, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                 S::SMEM_BYTES);
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fused_train<EPAD, W, NH, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                S::SMEM_BYTES);
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fused_train<EPAD, W, NH, true, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                S::SMEM_BYTES);
     });
     const bool all_lds = a.lds_level_mask != 0u && (a.lds_level_mask == ((a.nd.L >= 32) ? 0xffffffffu : ((1u << a.nd.L) - 1u)));
-    // the benched chain's kernel with the debug dump compiled in (mon_object_set_debug_dump(obj, 2)): E / h / O / dO / dh / dE of every sample
+    // the benched chain's kernel with the debug dump compiled in (mon_object_set_debug_dump(obj, 2)): E / h / O / dO / dh / dE of every sample.  The dump
+    // honours the occupancy grid like the chain it copies: a dead sample's slot was not encoded, its features are zero and it carries no gradient
     if (a.e_soa && all_lds && dump) {
-        hipLaunchKernelGGL((k_fused_train<EPAD, W, NH, true, false, false, true>), dim3(grid), dim3(256), S::SMEM_BYTES, s, a);
+        if (a.occ_bits) hipLaunchKernelGGL((k_fused_train<EPAD, W, NH, true, false, true, true>), dim3(grid), dim3(256), S::SMEM_BYTES, s, a);
+        else hipLaunchKernelGGL((k_fused_train<EPAD, W, NH, true, false, false, true>), dim3(grid), dim3(256), S::SMEM_BYTES, s, a);
         return;
     }
     // features from k_encode_tiles (with the occupancy grid: a dead sample's features are there too, its alpha and gradient are zero all the same)
@@ -519,8 +525,9 @@ static void fused_train_t(hipStream_t s, const FusedArgs& a, uint32_t grid, int 
         else hipLaunchKernelGGL((k_fused_train<EPAD, W, NH, false, false, false, true>), dim3(grid), dim3(256), S::SMEM_BYTES, s, a);
         return;
     }
-    // (the debug dump evaluates every sample)
-    if (dump) hipLaunchKernelGGL((k_fused_train<EPAD, W, NH, true, true>), dim3(grid), dim3(256), S::SMEM_BYTES, s, a);
+    // (the debug dump of the gather chain; with the occupancy grid in use it masks the dead samples' loads, as the chain it copies does)
+    if (dump) { if (a.occ_bits) hipLaunchKernelGGL((k_fused_train<EPAD, W, NH, true, true, true>), dim3(grid), dim3(256), S::SMEM_BYTES, s, a);
+                else hipLaunchKernelGGL((k_fused_train<EPAD, W, NH, true, true>), dim3(grid), dim3(256), S::SMEM_BYTES, s, a); }
     else if (a.occ_bits) { if (all_lds) hipLaunchKernelGGL((k_fused_train<EPAD, W, NH, false, false, true>), dim3(grid), dim3(256), S::SMEM_BYTES, s, a);
                            else hipLaunchKernelGGL((k_fused_train<EPAD, W, NH, false, true, true>), dim3(grid), dim3(256), S::SMEM_BYTES, s, a); }
     else if (all_lds) hipLaunchKernelGGL((k_fused_train<EPAD, W, NH, false, false>), dim3(grid), dim3(256), S::SMEM_BYTES, s, a);

@@ -1063,7 +1063,7 @@ static void enqueue_iteration(Model& m, int stages) {
 static void maybe_refresh_occupancy(Model& m, uint32_t iter) {
     // due at the first iteration it is asked for at or after the next multiple of kOccInterval (the hipGraph path only asks at the start of a captured PAIR:
     // after an odd number of iterations an exact "iter % interval == 0" test was never true again and the grid was never refreshed)
-    if (!m.d_occ || m.backend != 1 || iter < (uint32_t)kOccWarmup || iter < m.occ_next_refresh) return;
+    if (!m.d_occ || m.occ_pinned || m.backend != 1 || iter < (uint32_t)kOccWarmup || iter < m.occ_next_refresh) return;
     launch_occupancy_update(m.train_stream, m.lf, m.nd, m.P.half, m.oc, m.d_frag_occ, m.occ_raw_threshold, m.d_occ_tmp, m.d_occ);
     // the density field settles: every kOccInterval iterations at first, every 4th / 16th of that rate later (a refresh costs ~60 us, 1.9 us per step at the
     // early rate -- more than the skipping saves once the level-tile chain has taken the gathers out of the forward pass; tools/occ_timing.py)

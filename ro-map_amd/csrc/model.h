@@ -438,6 +438,7 @@ struct Model {
     // occupancy grid (cfg.occupancy_skip)
     uint32_t *d_occ = nullptr, *d_occ_tmp = nullptr; uint16_t* d_frag_occ = nullptr; float occ_raw_threshold = 0.f;
     uint32_t occ_refreshed_iter = 0, occ_next_refresh = 0;
+    bool occ_pinned = false;                                    // a caller's grid (mon_debug_set_train_occupancy): no scheduled refreshes
     uint32_t *d_live_idx = nullptr, *d_live_cnt = nullptr;      // live-sample lists of the level-tile chain (LiveArgs)
     // whole-crop render outputs: ONE grow-only buffer, rgb | depth | mask of the current crop back to back
     float *d_out_all = nullptr, *d_out_rgb = nullptr, *d_out_depth = nullptr, *d_out_mask = nullptr; size_t out_cap = 0;

@@ -88,6 +88,14 @@ def test_rng_and_half(orc):
 
 
 # ------------------------------------------------------------------ encode vs fp64 NumPy
+def numpy_occ_live(bits, x):
+    """The occupancy grid's verdict for warped positions x [n, 3], restated in NumPy: cell = trunc(x * 64) per axis in fp32, clamped to [0, 63], x fastest;
+    bit n of word w = cell 32 w + n."""
+    c = np.clip(np.trunc(np.asarray(x, np.float32).reshape(-1, 3) * np.float32(64)), 0, 63).astype(np.int64)
+    cell = (c[:, 2] * 64 + c[:, 1]) * 64 + c[:, 0]
+    return ((np.asarray(bits, np.uint32)[cell >> 5] >> (cell & 31).astype(np.uint32)) & 1).astype(np.uint8)
+
+
 def _numpy_corners(cfg, x):
     """tcnn's grid walk re-derived in NumPy, independent of the oracle's level_corners: yields (level, corner k, global entry index [n], weight [n] fp64)
     for positions x [n, 3] -- fractional position from the kernel's fp32 `scale * x + 0.5`, everything after that in fp64 / exact integers."""
@@ -177,12 +185,15 @@ def test_composite_early_out_zeroes_gradient(orc):
 
 
 # ------------------------------------------------------------------ hand-derived gradient vs autograd
-def _torch_loss(v, t, tgt, tdepth, bg, is_obj):
+def _torch_loss(v, t, tgt, tdepth, bg, is_obj, live=None):
+    """live: None, or the occupancy grid's verdict per sample (float 0 / 1): a dead sample has alpha 0 and carries no gradient at all."""
     import torch
     c = torch.sigmoid(v[:, :3]); sig = torch.exp(v[:, 3])
     dt = t - torch.cat([torch.zeros(1, dtype=t.dtype), t[:-1]])
     def comp(sigma):
         alpha = 1 - torch.exp(-sigma * dt)
+        if live is not None:
+            alpha = alpha * live
         T = torch.cumprod(torch.cat([torch.ones(1, dtype=t.dtype), 1 - alpha]), 0)
         w = alpha * T[:-1]
         return (w[:, None] * c).sum(0) + T[-1] * bg, (w * t).sum(), 1 - T[-1]
@@ -194,7 +205,7 @@ def _torch_loss(v, t, tgt, tdepth, bg, is_obj):
         return loss
     # background rays: colour gradient only through the colours (density detached), opacity penalty + 0.01 * sum(sigma)
     rgb_c, _, _ = comp(sig.detach())
-    return ((rgb_c - tgt) ** 2).sum() + 0.5 * mask + 0.01 * sig.sum()
+    return ((rgb_c - tgt) ** 2).sum() + 0.5 * mask + 0.01 * (sig if live is None else sig * live).sum()
 
 
 @pytest.mark.parametrize("is_obj,tdepth", [(1, 0.0), (1, 1.05), (0, 0.0)])
@@ -303,6 +314,12 @@ def test_end_to_end_gradients_match_torch_autograd(orc, small_scene, kw, use_dep
     The oracle also rounds dL/dO, dh, dE and every scatter contribution to fp16 (tcnn's network precision): agreement is to a few 1e-3 of the gradient scale."""
     if _in_child_process(request):
         return
+    end_to_end_autograd(orc, small_scene, kw, use_depth)
+
+
+def end_to_end_autograd(orc, small_scene, kw, use_depth, occ_bits=None):
+    """The body of the test above; occ_bits: an occupancy grid the oracle evaluates with (dead samples: zero features, alpha 0, no gradient), restated
+    in the torch graph independently (cell look-up in NumPy)."""
     torch = pytest.importorskip("torch")
     import __graft_entry__ as ge
     kw = dict(kw, rays_per_batch=64)
@@ -311,6 +328,8 @@ def test_end_to_end_gradients_match_torch_autograd(orc, small_scene, kw, use_dep
     master = m.buffer("master"); master[m.n_mlp:] = rs.uniform(-0.5, 0.5, m.n_params - m.n_mlp).astype(np.float32)
     m.set_params(master)
     m.generate_batch(); assert m.n_valid > 0
+    if occ_bits is not None:
+        m.set_occupancy(occ_bits)
     m.forward_backward()
     W, NH, Ep, R, S = m.W, m.NH, m.Epad, m.R, m.S; B = R * S; L = m.cfg.n_levels
     half = orc.h2f(m.buffer("half")).astype(np.float64)
@@ -320,9 +339,14 @@ def test_end_to_end_gradients_match_torch_autograd(orc, small_scene, kw, use_dep
         rows = 16 if layer == NH else W; cols = Ep if layer == 0 else W
         mats.append(torch.tensor(half[o:o + rows * cols].reshape(rows, cols), dtype=torch.float64, requires_grad=True)); o += rows * cols
     pts = m.buffer("pts").reshape(B, 3)
+    live = np.ones(B)
+    if occ_bits is not None:
+        live = numpy_occ_live(occ_bits, pts).astype(np.float64)
+        assert np.array_equal(m.buffer("live"), live.astype(np.uint8)) and 0 < live.sum() < B
+    lv = torch.tensor(live)
     feats = [torch.zeros(B, 2, dtype=torch.float64) for _ in range(L)]
     for l, _, idx, w in _numpy_corners(m.cfg, pts):
-        feats[l] = feats[l] + torch.tensor(w)[:, None] * table[torch.tensor(idx)]
+        feats[l] = feats[l] + (torch.tensor(w) * lv)[:, None] * table[torch.tensor(idx)]
     # forward values rounded to fp16 where the oracle (tcnn's network precision) rounds them, with a straight-through derivative: without it ~0.02 % of the ReLU
     # units sit on the other side of zero in fp64 and the comparison measures those flips (a 2-3 % norm error), not the backward chain
     h16 = lambda v: v + (v.detach().to(torch.float16).to(torch.float64) - v.detach())
@@ -334,7 +358,9 @@ def test_end_to_end_gradients_match_torch_autograd(orc, small_scene, kw, use_dep
     tgt = torch.tensor(m.buffer("target").reshape(R, 3).astype(np.float64)); bg = torch.tensor(m.buffer("bgcol").reshape(R, 3).astype(np.float64))
     flag = m.buffer("ray_flag"); tdep = m.buffer("target_depth").astype(np.float64)
     assert use_depth == bool((tdep > 0).any())
-    total = sum(_torch_loss(out[r], t[r], tgt[r], float(tdep[r]), bg[r], int(flag[r])) for r in range(R)) * (m.cfg.loss_scale / R)
+    lvr = lv.reshape(R, S)
+    total = sum(_torch_loss(out[r], t[r], tgt[r], float(tdep[r]), bg[r], int(flag[r]), None if occ_bits is None else lvr[r]) for r in range(R)) * (
+            m.cfg.loss_scale / R)
     total.backward()
     # MLP matrices: the oracle's gmlp is the loss-scaled fp32 dW, layer by layer (pad rows / columns are zero)
     gm = m.buffer("gmlp").astype(np.float64); o = 0
