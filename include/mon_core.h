@@ -234,6 +234,37 @@ int mon_object_pose_loss(mon_object* obj, int side, const mon_frame_bbox* obs, s
  * whole refinement is enqueued at once (the pose lives on the device between steps); the call returns when it is done. */
 int mon_object_refine_pose(mon_object* obj, int side, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, float* Tow16_inout,
                            float* loss_trace);
+/* Coarse-to-fine pose refinement: the objective L, its samples, alpha, colour, the early cut and the held hash-grid corners are exactly
+ * those of mon_object_pose_loss; only the gradient is re-weighted by level.
+ * Level-weighted gradient.  g_k = sum_l g_{k,l}, g_{k,l} = level l's term of dL/dx_k (dL/dE_l . dfeat_l/dx over the 8 corners, times the level's scale,
+ * over the box extent).  For weights w_0..w_{L-1} >= 0: g_k(w) = sum_l w_l g_{k,l}, grad6(w) = (sum_k g_k(w), sum_k x_k x g_k(w)).  The loss does not depend
+ * on w; every w_l = 1 gives grad6 of mon_object_pose_loss bit for bit, every w_l = 0 gives grad6 = 0.
+ * Window (BARF; alpha in levels, level 0 the coarsest): w_l(alpha) = 0 for alpha <= l, (1 - cos(pi (alpha - l))) / 2 for l < alpha < l + 1, 1 for
+ * alpha >= l + 1.
+ * Schedule: step i of an iters-step refinement uses alpha(i) = level_start + (level_end - level_start) min(1, i / (ramp iters)); everything else is
+ * mon_object_refine_pose's (Adam on the twist, Tow <- exp(delta^) Tow, Gram-Schmidt, loss_trace[i] the loss before step i and loss_trace[iters] at the
+ * end; iters 0 takes no step).
+ * C2F defaults (mon_pose_c2f_default; chosen by a sweep on base.json objects of the synthetic scene, profiles/r09_pose_c2f.md): level_start 4, level_end 5,
+ * ramp 0.7.
+ * (base.json, 500 or 2000 training iterations, 100 default steps: 5 degrees / 5 % and 15 degrees / 10 % of the box diagonal off end at 0.12-0.33 degrees and
+ * <= 0.15 %, where plain mon_object_refine_pose drifts away; the floor is Adam's step, lr_rot = 0.23 degrees.)
+ * Returns MON_ERR_ARG, before any device work, for a NULL c or level_weights, a non-finite parameter or weight, level_start < 0, level_end < level_start,
+ * ramp outside (0, 1], a negative weight, and everything mon_object_pose_loss / mon_object_refine_pose reject; MON_ERR_STATE as they do.  Read-only. */
+typedef struct mon_pose_c2f_params {
+    float level_start;   /* alpha at step 0 (>= 0)                                                                                                   */
+    float level_end;     /* alpha from the end of the ramp on (>= level_start; values >= L weight every level 1)                                     */
+    float ramp;          /* fraction of p->iters over which alpha rises linearly, (0, 1]                                                             */
+} mon_pose_c2f_params;
+int mon_pose_c2f_default(mon_pose_c2f_params* c);
+/* host-only: w[0..n_levels) of step `step` of an `iters`-step refinement (the window and schedule above); MON_ERR_ARG for iters < 1 or step outside
+ * [0, iters) as well */
+int mon_pose_c2f_weights(const mon_pose_c2f_params* c, int n_levels, int iters, int step, float* w);
+/* mon_object_pose_loss with the level weights w[0..L) of the object (L = its n_levels) */
+int mon_object_pose_loss_levels(mon_object* obj, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16,
+                                const mon_pose_refine_params* p, uint32_t iteration, const float* level_weights, float* loss, float* grad6);
+/* mon_object_refine_pose with the schedule: step i uses mon_pose_c2f_weights(c, L, p->iters, i).  Still enqueued at once, one synchronisation. */
+int mon_object_refine_pose_c2f(mon_object* obj, int side, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p,
+                               const mon_pose_c2f_params* c, float* Tow16_inout, float* loss_trace);
 /* NeRF_Model::GetDensityOnGrid (nerf_model.cu:2007-2048): raw density channel on an rx*ry*rz lattice. */
 int mon_object_density_grid(mon_object* obj, int rx, int ry, int rz, float* out_host);
 
@@ -339,6 +370,9 @@ int mon_online_render_scene(mon_online* mgr, mon_frame_bbox rect, const float* T
  * nothing of it has been published. */
 int mon_online_refine_pose(mon_online* mgr, size_t idx, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, float* Tow16_inout,
                            float* loss_trace);
+/* mon_object_refine_pose_c2f(side 1) of object idx, as mon_online_refine_pose */
+int mon_online_refine_pose_c2f(mon_online* mgr, size_t idx, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p,
+                               const mon_pose_c2f_params* c, float* Tow16_inout, float* loss_trace);
 /* RenderNeRFsTest(out_path, idx, stamps, boxes, Twcs, radius) -> NeRF::RenderTestImg (nerf.cu:255-404): test images + test.txt +
  * train.txt + the 60-view 360-degree video (RenderVideo, nerf_model.cu:1832-1990) + obj.ply under <out_path>/<id>/ */
 int mon_online_render_nerfs_test(mon_online* mgr, const char* out_path, size_t idx, const char* const* timestamps, const mon_frame_bbox* boxes,

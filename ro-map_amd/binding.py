@@ -44,6 +44,11 @@ class PoseRefineParams(C.Structure):
                 ("w_mask", C.c_float), ("w_depth", C.c_float), ("depth_huber", C.c_float), ("seed", C.c_uint64)]
 
 
+class PoseC2FParams(C.Structure):
+    """mon_pose_c2f_params (include/mon_core.h): the coarse-to-fine window's alpha (in levels) at step 0, after the ramp, and the ramp's share of the steps."""
+    _fields_ = [("level_start", C.c_float), ("level_end", C.c_float), ("ramp", C.c_float)]
+
+
 class MonProfile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8)]
 
@@ -141,6 +146,14 @@ _SIGS = {
             C.POINTER(C.c_float), C.c_void_p]),
     "mon_object_refine_pose": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams), C.c_void_p, C.c_void_p]),
     "mon_online_refine_pose": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams), C.c_void_p, C.c_void_p]),
+    "mon_pose_c2f_default": (C.c_int, [C.POINTER(PoseC2FParams)]),
+    "mon_pose_c2f_weights": (C.c_int, [C.POINTER(PoseC2FParams), C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "mon_object_pose_loss_levels": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32,
+            C.c_void_p, C.POINTER(C.c_float), C.c_void_p]),
+    "mon_object_refine_pose_c2f": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams), C.POINTER(PoseC2FParams),
+            C.c_void_p, C.c_void_p]),
+    "mon_online_refine_pose_c2f": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams), C.POINTER(PoseC2FParams),
+            C.c_void_p, C.c_void_p]),
 }
 
 
@@ -595,6 +608,24 @@ class ObjectNeRF:
         _check(lib().mon_object_refine_pose(self.h, int(side), _p(b), b.shape[0], C.byref(prm), _p(pose), _p(trace)))
         return pose, trace
 
+    def pose_loss_levels(self, obs, Tow16, level_weights, params=None, side=0, iteration=0):
+        """mon_object_pose_loss_levels: pose_loss with level l's share of the position gradient scaled by level_weights[l] (one per level); the loss is
+        pose_loss's."""
+        b, prm = _pose_boxes(obs), _pose_params(params); pose = np.ascontiguousarray(Tow16, np.float32).reshape(16)
+        w = np.ascontiguousarray(level_weights, np.float32).reshape(-1)
+        if w.size != self.cfg.n_levels:
+            raise ValueError("level_weights: %d values for %d levels" % (w.size, self.cfg.n_levels))
+        loss = C.c_float(0); g = np.empty(6, np.float32)
+        _check(lib().mon_object_pose_loss_levels(self.h, int(side), _p(b), b.shape[0], _p(pose), C.byref(prm), int(iteration), _p(w), C.byref(loss), _p(g)))
+        return loss.value, g
+
+    def refine_pose_c2f(self, obs, Tow16, params=None, c2f=None, side=0):
+        """mon_object_refine_pose_c2f: refine_pose with the coarse-to-fine level schedule c2f (PoseC2FParams, a dict of overrides, or None = defaults)."""
+        b, prm, c = _pose_boxes(obs), _pose_params(params), _c2f_params(c2f); pose = np.array(Tow16, np.float32).reshape(16)
+        trace = np.empty(prm.iters + 1, np.float32)
+        _check(lib().mon_object_refine_pose_c2f(self.h, int(side), _p(b), b.shape[0], C.byref(prm), C.byref(c), _p(pose), _p(trace)))
+        return pose, trace
+
     def pose_samples(self, obs, Tow16, params=None, side=0, iteration=0):
         """mon_debug_pose_samples: per drawn ray of that evaluation, positions (n, 64, 3), raw outputs (n, 64, 4) and dL/dx (n, 64, 3), object frame."""
         b, prm = _pose_boxes(obs), _pose_params(params); pose = np.ascontiguousarray(Tow16, np.float32).reshape(16)
@@ -759,6 +790,13 @@ class OnlineManager:
         _check(lib().mon_online_refine_pose(self.h, int(idx), _p(b), b.shape[0], C.byref(prm), _p(pose), _p(trace)))
         return pose, trace
 
+    def refine_pose_c2f(self, idx, obs, Tow16, params=None, c2f=None):
+        """mon_online_refine_pose_c2f: refine_pose with the coarse-to-fine level schedule, on object idx's published snapshot."""
+        b, prm, c = _pose_boxes(obs), _pose_params(params), _c2f_params(c2f); pose = np.array(Tow16, np.float32).reshape(16)
+        trace = np.empty(prm.iters + 1, np.float32)
+        _check(lib().mon_online_refine_pose_c2f(self.h, int(idx), _p(b), b.shape[0], C.byref(prm), C.byref(c), _p(pose), _p(trace)))
+        return pose, trace
+
     def close(self):
         if self.h:
             lib().mon_online_destroy(self.h); self.h = None
@@ -780,6 +818,31 @@ def _pose_params(params):
     if isinstance(params, dict):
         return pose_refine_default(**params)
     return params
+
+
+def pose_c2f_default(**overrides):
+    """mon_pose_c2f_default, then any field overridden by keyword."""
+    c = PoseC2FParams(); _check(lib().mon_pose_c2f_default(C.byref(c)))
+    for k, v in overrides.items():
+        if k not in dict(PoseC2FParams._fields_):
+            raise KeyError(k)
+        setattr(c, k, v)
+    return c
+
+
+def pose_c2f_weights(n_levels, iters, step, c2f=None):
+    """mon_pose_c2f_weights: the level weights (n_levels float32) of step `step` of an `iters`-step coarse-to-fine refinement."""
+    c = _c2f_params(c2f); w = np.empty(int(n_levels), np.float32)
+    _check(lib().mon_pose_c2f_weights(C.byref(c), int(n_levels), int(iters), int(step), _p(w)))
+    return w
+
+
+def _c2f_params(c2f):
+    if c2f is None:
+        return pose_c2f_default()
+    if isinstance(c2f, dict):
+        return pose_c2f_default(**c2f)
+    return c2f
 
 
 def _pose_boxes(obs):

@@ -1,4 +1,6 @@
 // c_api.cpp -- extern "C" surface declared in include/mon_core.h.
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 #include "model.h"
@@ -34,6 +36,34 @@ int marching_cubes_host(int device, const float* density, int rx, int ry, int rz
                         float* verts, float* normals_raw, uint32_t* indices, uint32_t cap_verts, uint32_t cap_indices, uint32_t* n_verts,
                                 uint32_t* n_verts_real, uint32_t* n_indices);
 int microbench(int device, int mode, int pattern, uint32_t n_entries, uint32_t n_ops, float* ms_out);
+}  // namespace mon
+
+
+// ---- coarse-to-fine level weights (include/mon_core.h): the checks of a schedule, one row of weights, the table of a whole refinement
+namespace mon {
+int pose_c2f_check(const mon_pose_c2f_params* c) {
+    if (!c) { set_error("pose c2f: null params"); return MON_ERR_ARG; }
+    if (!std::isfinite(c->level_start) || !std::isfinite(c->level_end) || !std::isfinite(c->ramp)) { set_error("pose c2f: a non-finite parameter"); return MON_ERR_ARG; }
+    if (c->level_start < 0.f || c->level_end < c->level_start) { set_error("pose c2f: level_start %g, level_end %g (0 <= start <= end)", c->level_start,
+            c->level_end); return MON_ERR_ARG; }
+    if (!(c->ramp > 0.f && c->ramp <= 1.f)) { set_error("pose c2f: ramp %g outside (0, 1]", c->ramp); return MON_ERR_ARG; }
+    return MON_OK;
+}
+// the window and schedule of include/mon_core.h, in double, rounded once to float (also the table of mon_object_refine_pose_c2f)
+static void c2f_row(const mon_pose_c2f_params& c, int n_levels, int iters, int step, float* w) {
+    const double f = std::min(1.0, (double)step / ((double)c.ramp * (double)iters));
+    const double alpha = (double)c.level_start + ((double)c.level_end - (double)c.level_start) * f;
+    for (int l = 0; l < n_levels; ++l) {
+        const double a = alpha - l;
+        w[l] = a <= 0.0 ? 0.f : a >= 1.0 ? 1.f : (float)((1.0 - std::cos(M_PI * a)) / 2.0);
+    }
+}
+// the [iters][L] weight table of a scheduled refinement (empty for iters 0)
+std::vector<float> pose_c2f_table(const mon_pose_c2f_params& c, int n_levels, int iters) {
+    std::vector<float> t((size_t)iters * n_levels);
+    for (int i = 0; i < iters; ++i) c2f_row(c, n_levels, iters, i, t.data() + (size_t)i * n_levels);
+    return t;
+}
 }  // namespace mon
 
 using namespace mon;
@@ -145,6 +175,40 @@ int mon_object_refine_pose(mon_object* o, int side, const mon_frame_bbox* obs, s
     const int r2 = pose_refine(*o->m, side, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr);
     if (r2 == MON_OK) std::memcpy(Tow16_inout, pose, 64);
     return r2;
+}
+// ---- coarse-to-fine level weights (BARF window over the levels, alpha in levels from level_start to level_end over the first ramp * iters steps)
+int mon_pose_c2f_default(mon_pose_c2f_params* c) {
+    REQUIRE(c, "params");
+    c->level_start = 4.f; c->level_end = 5.f; c->ramp = 0.7f;
+    return MON_OK;
+}
+int mon_pose_c2f_weights(const mon_pose_c2f_params* c, int n_levels, int iters, int step, float* w) {
+    const int rc = pose_c2f_check(c); if (rc) return rc;
+    REQUIRE(w, "weights");
+    if (n_levels < 1 || iters < 1 || step < 0 || step >= iters) { set_error("pose c2f weights: n_levels %d, iters %d, step %d (n_levels >= 1, 0 <= step < iters)",
+            n_levels, iters, step); return MON_ERR_ARG; }
+    c2f_row(*c, n_levels, iters, step, w);
+    return MON_OK;
+}
+int mon_object_pose_loss_levels(mon_object* o, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params* p,
+        uint32_t iteration, const float* level_weights, float* loss, float* grad6) {
+    int rc = pose_args(o, side, obs, n_obs, Tow16, p); if (rc) return rc;
+    REQUIRE(level_weights, "level_weights");
+    const int L = (int)o->m->nd.L;
+    for (int l = 0; l < L; ++l)
+        if (!std::isfinite(level_weights[l]) || level_weights[l] < 0.f) { set_error("pose: level weight %d is %g (finite, >= 0)", l, level_weights[l]);
+            return MON_ERR_ARG; }
+    return pose_refine(*o->m, side, obs, n_obs, Tow16, *p, -1, iteration, nullptr, nullptr, loss, grad6, nullptr, level_weights);
+}
+int mon_object_refine_pose_c2f(mon_object* o, int side, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, const mon_pose_c2f_params* c,
+        float* Tow16_inout, float* loss_trace) {
+    int rc = pose_args(o, side, obs, n_obs, Tow16_inout, p); if (rc) return rc;
+    if ((rc = pose_c2f_check(c))) return rc;
+    const std::vector<float> table = pose_c2f_table(*c, (int)o->m->nd.L, p->iters);
+    float pose[16]; std::memcpy(pose, Tow16_inout, 64);
+    rc = pose_refine(*o->m, side, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr, table.empty() ? nullptr : table.data());
+    if (rc == MON_OK) std::memcpy(Tow16_inout, pose, 64);
+    return rc;
 }
 int mon_object_density_grid(mon_object* o, int rx, int ry, int rz, float* out_host) { REQUIRE(o, "object");
     return model_density_grid(*o->m, rx, ry, rz, out_host); }

@@ -2,6 +2,7 @@
 // gradient with respect to the sample positions (forward + composite backward + MLP backward on MFMA + hash-grid position gradient), and the Adam step on
 // the twist.  Instantiated for the fused shapes only (MON_FUSED_DISPATCH); the network runs through the tile_forward / mlp_forward of fused_device.h.
 // The objective is stated in include/mon_core.h and DESIGN.md 3.6.
+#include <type_traits>
 #include "fused_device.h"
 
 namespace mon {
@@ -58,8 +59,10 @@ __device__ __forceinline__ float huber_f(float x, float delta) { const float ax 
 
 // dL/dx (normalised box coordinates) of one level pair: the trilinear weights' derivative against the corner features, dotted with dL/dE of the level this
 // half-wave owns (de0, de1); the corners are the ones the encode gathered (encode_swap of the same window)
+// LW: the level's term times its weight (lw: lane il / 32 + il holds the weight of the level it holds in LevelRegs), after the term is formed in fp32
+template <bool LW>
 __device__ __forceinline__ void pose_level_grad(float (&g)[3], int il, const uint32_t (&c0)[4], const uint32_t (&c1)[4], const LevelRegs& lr, const float x[3],
-        int h, int L, float de0, float de1) {
+        int h, int L, float de0, float de1, float lw) {
     const int LPH = (L + 1) >> 1;
     const float scale = h ? lane_f(lr.scale, 32 + il) : lane_f(lr.scale, il);
     float pos[3];
@@ -76,7 +79,12 @@ __device__ __forceinline__ void pose_level_grad(float (&g)[3], int il, const uin
         gx = fmaf(sx * ay * az, f, gx); gy = fmaf(ax * sy * az, f, gy); gz = fmaf(ax * ay * sz, f, gz);
     }
     const bool real = il < LPH && h * LPH + il < L;
-    g[0] += real ? scale * gx : 0.f; g[1] += real ? scale * gy : 0.f; g[2] += real ? scale * gz : 0.f;
+    if constexpr (LW) {
+        const float wl = h ? lane_f(lw, 32 + il) : lane_f(lw, il);
+        g[0] += real ? wl * (scale * gx) : 0.f; g[1] += real ? wl * (scale * gy) : 0.f; g[2] += real ? wl * (scale * gz) : 0.f;
+    } else {
+        g[0] += real ? scale * gx : 0.f; g[1] += real ? scale * gy : 0.f; g[2] += real ? scale * gz : 0.f;
+    }
 }
 
 // One wavefront per ray, its 2S = 64 samples as two 32-sample tiles (k_fused_render's placement, jitter rand01(seed, stream, step, base + k), alpha,
@@ -84,8 +92,9 @@ __device__ __forceinline__ void pose_level_grad(float (&g)[3], int il, const uin
 // power of two so that fp16 neither overflows nor flushes) -> MLP backward on MFMA (the transposed fragments training uses) -> dL/dE -> position gradient
 // from a second gather of each level's corners.  Per lane: sum of g and x × g over its samples (its half-wave's levels); per wave: the ray losses; per
 // workgroup: one partial row of 8 floats {g, x × g, loss, 0} -- no atomics, so the sums are the same from run to run.
-template <int EPAD, int W, int NH>
-__global__ void __launch_bounds__(256) k_pose_grad(FusedArgs a, PoseGradArgs p) {
+// LW (mon_object_pose_loss_levels / the coarse-to-fine schedule): each level's term of g scaled by p.level_w[l]; the arguments of LW = false stay PoseGradArgs.
+template <int EPAD, int W, int NH, bool LW>
+__global__ void __launch_bounds__(256) k_pose_grad(FusedArgs a, std::conditional_t<LW, PoseGradArgsLW, PoseGradArgs> p) {
     using S = FusedShape<EPAD, W, NH>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     half_t* frags = reinterpret_cast<half_t*>(smem);
@@ -98,6 +107,11 @@ __global__ void __launch_bounds__(256) k_pose_grad(FusedArgs a, PoseGradArgs p) 
     const half2_t* table = reinterpret_cast<const half2_t*>(a.params + a.nd.n_mlp);
     const LevelRegs lregs = load_level_regs_uniform(a.lt, L, lane); const uint32_t table_bytes = a.lt.offset[L] * 4u;
     const __amdgpu_buffer_rsrc_t rsrc = table_rsrc(table, table_bytes);
+    float lw = 1.f;                                                                     // LW: the weight of this lane's level (LevelRegs' placement)
+    if constexpr (LW) {
+        const int LPH = (L + 1) >> 1, lv = lane < 32 ? lane : lane - 32 + LPH;
+        lw = ((lane & 31) < LPH && lv < L) ? p.level_w[lv] : 0.f;
+    }
     float ext[3];
 #pragma unroll
     for (int d = 0; d < 3; ++d) ext[d] = a.oc.aabb.mx[d] - a.oc.aabb.mn[d];
@@ -236,7 +250,7 @@ __global__ void __launch_bounds__(256) k_pose_grad(FusedArgs a, PoseGradArgs p) 
                     uint32_t c0[4], c1[4];
                     encode_swap<EPAD, W, NH>(g, il, c0, c1);
                     if (il + EB < S::LLV) encode_issue<EPAD, W, NH, false>(g, il + EB, lregs, rsrc, xk[tile], h, true);
-                    pose_level_grad(gl, il, c0, c1, lregs, xk[tile], h, L, de[2 * il], de[2 * il + 1]);
+                    pose_level_grad<LW>(gl, il, c0, c1, lregs, xk[tile], h, L, de[2 * il], de[2 * il + 1], lw);
                 }
 #pragma unroll
                 for (int d = 0; d < 3; ++d) gl[d] = gl[d] * down / ext[d];                   // object frame (this half-wave's levels)
@@ -343,11 +357,16 @@ __global__ void __launch_bounds__(256) k_pose_update(const float* __restrict__ p
 }
 
 template <int EPAD, int W, int NH>
-static void pose_grad_t(hipStream_t s, const FusedArgs& a, const PoseGradArgs& p, uint32_t grid, int build_image) {
+static void pose_grad_t(hipStream_t s, const FusedArgs& a, const PoseGradArgs& p, uint32_t grid, int build_image, const float* level_w) {
     using S = FusedShape<EPAD, W, NH>;
     if (build_image) hipLaunchKernelGGL((k_build_frag_image<EPAD, W, NH>), dim3((S::N_FRAGS * 512 + 255) / 256), dim3(256), 0, s, a.params, a.nd.L,
             const_cast<uint16_t*>(a.frag_image), (const DevState*)nullptr);
-    hipLaunchKernelGGL((k_pose_grad<EPAD, W, NH>), dim3(grid), dim3(256), S::FRAG_BYTES + 512 + S::WAVES * 32, s, a, p);
+    if (level_w) {
+        PoseGradArgsLW q; static_cast<PoseGradArgs&>(q) = p; q.level_w = level_w;
+        hipLaunchKernelGGL((k_pose_grad<EPAD, W, NH, true>), dim3(grid), dim3(256), S::FRAG_BYTES + 512 + S::WAVES * 32, s, a, q);
+    } else {
+        hipLaunchKernelGGL((k_pose_grad<EPAD, W, NH, false>), dim3(grid), dim3(256), S::FRAG_BYTES + 512 + S::WAVES * 32, s, a, p);
+    }
 }
 
 uint32_t pose_grad_grid(uint32_t n_rays) { uint32_t g = (n_rays + 3u) / 4u; if (g > kPoseMaxGrid) g = kPoseMaxGrid; return g ? g : 1u; }
@@ -357,10 +376,10 @@ void launch_pose_rays(hipStream_t s, const PoseRayArgs& a) {
     hipLaunchKernelGGL(k_pose_rays, dim3((a.n_rays + 255) / 256), dim3(256), 0, s, a);
 }
 void launch_pose_grad(hipStream_t s, const LevelFast& lt, const NetDims& nd, const ObjectConst& oc, const uint16_t* params, uint16_t* frag_image,
-        int build_image, const PoseGradArgs& p) {
+        int build_image, const PoseGradArgs& p, const float* level_w) {
     FusedArgs a{}; a.lt = lt; a.nd = nd; a.oc = oc; a.params = params; a.frag_image = frag_image;
     const uint32_t grid = pose_grad_grid(p.n_rays);
-    MON_FUSED_DISPATCH(pose_grad_t, s, a, p, grid, build_image);
+    MON_FUSED_DISPATCH(pose_grad_t, s, a, p, grid, build_image, level_w);
 }
 void launch_pose_update(hipStream_t s, const float* partials, uint32_t n_parts, float inv_n, float* out, float* trace, uint32_t it, int step, float lr_t,
         float lr_r, float* pose, float* moments) {

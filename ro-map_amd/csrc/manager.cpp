@@ -673,6 +673,20 @@ int mon_online_refine_pose(mon_online* h, size_t idx, const mon_frame_bbox* obs,
     if (rc == MON_OK) std::memcpy(Tow16_inout, pose, 64);
     return rc;
 }
+// ... with the coarse-to-fine level schedule (mon_object_refine_pose_c2f on side 1)
+int mon_online_refine_pose_c2f(mon_online* h, size_t idx, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p,
+        const mon_pose_c2f_params* c, float* Tow16_inout, float* loss_trace) {
+    REQ(h); REQ(obs); REQ(p); REQ(Tow16_inout);
+    if (n_obs == 0 || p->iters < 0) { set_error("refine_pose_c2f: no boxes or iters < 0"); return MON_ERR_ARG; }
+    { const int rc = pose_c2f_check(c); if (rc) return rc; }
+    OnlineObject* o = online_object(*h->m, idx); if (!o || !o->model) { set_error("NeRF Idx error ..."); return MON_ERR_ARG; }
+    const std::vector<float> table = pose_c2f_table(*c, (int)o->model->nd.L, p->iters);
+    float pose[16]; std::memcpy(pose, Tow16_inout, 64);
+    const int rc = pose_refine(*o->model, 1, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr,
+                               table.empty() ? nullptr : table.data());
+    if (rc == MON_OK) std::memcpy(Tow16_inout, pose, 64);
+    return rc;
+}
 // NerfManagerOnline::RenderNeRFsTest -> NeRF::RenderTestImg, nerf.cu:255-404: <out>/<id>/{test_img,test_depth,test_mask}/<stamp>.png,
 // test.txt, train.txt (object-centric poses), 60-view video_img / video_depth, obj.ply
 int mon_online_render_nerfs_test(mon_online* h, const char* out_path, size_t idx, const char* const* timestamps, const mon_frame_bbox* boxes,

@@ -1561,13 +1561,14 @@ struct PoseWs {
     float* small = nullptr;                                                       // partials [kPoseMaxGrid][8] | pose [16] | moments [12]
     uint16_t* frag = nullptr;                                                     // the A-fragment image, backward fragments included
     float* dbg = nullptr; size_t dbg_cap = 0;                                     // mon_debug_pose_samples: x | raw | dL/dx of every sample
+    float* lw = nullptr; size_t lw_cap = 0;                                       // level weights [evaluation][L] of the weighted calls
 };
 static std::mutex g_pose_mu;
 static PoseWs& pose_ws(Model& m, int side) { std::lock_guard<std::mutex> l(g_pose_mu); if (!m.pose_ws[side]) m.pose_ws[side] = new PoseWs(); return *m.pose_ws[side]; }
 void pose_ws_free(Model& m) {
     for (int k = 0; k < 2; ++k) {
         PoseWs* w = m.pose_ws[k]; if (!w) continue;
-        for (void* q : { (void*)w->rec, (void*)w->out, (void*)w->boxes, (void*)w->prefix, (void*)w->small, (void*)w->frag, (void*)w->dbg }) if (q) (void)hipFree(q);
+        for (void* q : { (void*)w->rec, (void*)w->out, (void*)w->boxes, (void*)w->prefix, (void*)w->small, (void*)w->frag, (void*)w->dbg, (void*)w->lw }) if (q) (void)hipFree(q);
         delete w; m.pose_ws[k] = nullptr;
     }
 }
@@ -1582,7 +1583,7 @@ uint32_t pose_n_rays(const mon_frame_bbox* obs, size_t n_obs, const mon_pose_ref
     return t > 0xffffffffull ? 0xffffffffu : (uint32_t)t;
 }
 int pose_refine(Model& m, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params& p, int iters,
-                uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const PoseDump* dump) {
+                uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const PoseDump* dump, const float* level_w) {
     if (!obs || n_obs == 0 || !Tow16) { set_error("pose: null or empty argument"); return MON_ERR_ARG; }
     if (side != 0 && side != 1) { set_error("pose: side must be 0 or 1"); return MON_ERR_ARG; }
     if (p.rays_per_iter > kPoseMaxRays) { set_error("pose: rays_per_iter %u above %u", p.rays_per_iter, kPoseMaxRays); return MON_ERR_ARG; }
@@ -1637,6 +1638,13 @@ int pose_refine(Model& m, int side, const mon_frame_bbox* obs, size_t n_obs, con
         if ((rc = grow_buf(w.dbg, w.dbg_cap, (size_t)n_rays * 64 * 10))) return rc;
         dx = w.dbg; draw = w.dbg + (size_t)n_rays * 64 * 3; dg = w.dbg + (size_t)n_rays * 64 * 7;
     }
+    // weighted: one row of L per evaluation that steps (or the one evaluation of iters < 0); the last evaluation of a refinement, whose gradient is not
+    // used, runs unweighted (the loss does not depend on the weights)
+    const int L = (int)m.nd.L, n_wrows = level_w ? (iters < 0 ? 1 : iters) : 0;
+    if (n_wrows) {
+        if ((rc = grow_buf(w.lw, w.lw_cap, (size_t)n_wrows * L))) return rc;
+        HIPCHECK(hipMemcpyAsync(w.lw, level_w, sizeof(float) * (size_t)n_wrows * L, hipMemcpyHostToDevice, s));
+    }
     HIPCHECK(hipMemcpyAsync(w.boxes, obs, sizeof(mon_frame_bbox) * n_obs, hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(w.prefix, prefix.data(), 4 * (n_obs + 1), hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(d_pose, Tow16, 64, hipMemcpyHostToDevice, s));
@@ -1652,7 +1660,7 @@ int pose_refine(Model& m, int side, const mon_frame_bbox* obs, size_t n_obs, con
         ga.seed = drawn ? p.seed : m.oc.sample_seed; ga.stream = drawn ? kStreamPose : (uint32_t)kStreamRender; ga.step = drawn ? key : 0u;
         ga.w_rgb = p.w_rgb; ga.w_mask = p.w_mask; ga.w_depth = p.w_depth; ga.huber = p.depth_huber; ga.inv_n = 1.f / (float)n_rays;
         ga.partials = partials; ga.dbg_x = dx; ga.dbg_raw = draw; ga.dbg_g = dg;
-        launch_pose_grad(s, m.lf, m.nd, m.oc, prm, w.frag, it == 0, ga);
+        launch_pose_grad(s, m.lf, m.nd, m.oc, prm, w.frag, it == 0, ga, it < n_wrows ? w.lw + (size_t)it * L : nullptr);
         launch_pose_update(s, partials, grid, 1.f / (float)n_rays, w.out, nullptr, (uint32_t)it, iters >= 0 && it < iters, p.lr_trans, p.lr_rot, d_pose, d_mom);
     }
     HIPCHECK(hipGetLastError());

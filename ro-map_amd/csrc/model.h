@@ -348,11 +348,13 @@ struct PoseGradArgs {
     float* partials;
     float *dbg_x, *dbg_raw, *dbg_g;                             // mon_debug_pose_samples: [ray][2S][3 | 4 | 3], or nullptr
 };
+struct PoseGradArgsLW : PoseGradArgs { const float* level_w; };   // k_pose_grad<.., LW = true>: level l's term of g times level_w[l]
 // (weak: the host-only ThreadSanitizer build, tests/tsan, links without kernels_pose.hip; pose_refine reports MON_ERR_STATE there)
 __attribute__((weak)) uint32_t pose_grad_grid(uint32_t n_rays);
 __attribute__((weak)) void launch_pose_rays(hipStream_t s, const PoseRayArgs& a);
+// level_w: nullptr = k_pose_grad<.., false>; else the device array of the nd.L level weights of this evaluation (k_pose_grad<.., true>)
 __attribute__((weak)) void launch_pose_grad(hipStream_t s, const LevelFast& lt, const NetDims& nd, const ObjectConst& oc, const uint16_t* params, uint16_t* frag_image,
-        int build_image, const PoseGradArgs& p);
+        int build_image, const PoseGradArgs& p, const float* level_w);
 __attribute__((weak)) void launch_pose_update(hipStream_t s, const float* partials, uint32_t n_parts, float inv_n, float* out, float* trace, uint32_t it, int step, float lr_t,
         float lr_r, float* pose, float* moments);
 // inference on feature-planar level tiles (kernels_tilerender.hip): Render / RenderVideo, GetDensityOnGrid, mesh vertex colours
@@ -511,10 +513,13 @@ bool model_has_snapshot(Model& m);      // the object has an inference side and 
 // Pose refinement: iters < 0 = one evaluation (mon_object_pose_loss: loss, grad6, jitter / draws of `iteration`), else iters Adam steps from Tow16
 // (mon_object_refine_pose: the final pose into pose_out, loss_trace[iters + 1] may be nullptr).  dump (mon_debug_pose_samples, may be nullptr): per drawn ray
 // of the evaluation, host arrays [ray][2S] of positions (object frame, 3), raw outputs (4) and dL/dx (3); any of them may be nullptr.
+// level_w (mon_object_pose_loss_levels / mon_object_refine_pose_c2f, may be nullptr): host weights [L] of the one evaluation, or [iters][L] of the steps.
 struct PoseDump { float* x; float* raw; float* dldx; };
 int pose_refine(Model& m, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params& p, int iters,
-                uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const PoseDump* dump);
+                uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const PoseDump* dump, const float* level_w = nullptr);
 uint32_t pose_n_rays(const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params& p);      // rays of one evaluation
+int pose_c2f_check(const mon_pose_c2f_params* c);                                                    // MON_ERR_ARG for a NULL or bad schedule
+std::vector<float> pose_c2f_table(const mon_pose_c2f_params& c, int n_levels, int iters);          // [iters][n_levels]: mon_pose_c2f_weights of every step
 int model_publish_snapshot(Model& m);
 int model_render_snapshot(Model& m, mon_frame_bbox box, const float* pose16, int pose_is_Toc, float* rgb, float* depth, float* mask, uint32_t* snapshot_step);
 int level_table_build(const mon_config& c, LevelTable& lt, NetDims& nd, uint32_t& n_grid);
