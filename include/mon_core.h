@@ -195,7 +195,9 @@ int mon_scene_render(mon_object* const* objs, size_t n_objs, int side, mon_frame
  * mon_object_render builds for it under the Tow evaluated, intersected with the object's box, and its 2S = 64 jittered distances t_k -- rays_per_iter = 0:
  * the render's own jitter, so that at the object's own Tow the samples, alpha and colour of each box are those of mon_debug_scene_samples for that box;
  * rays_per_iter > 0: counter-RNG stream 4 keyed by (seed, iteration, ray * 2S + k), the pixels drawn uniformly over the union of the boxes' pixels by
- * stream 5 keyed by (seed, iteration, ray).  Alpha and colour as the render computes them (sigma = exp(o3), c = logistic(o0..2), alpha_k = 1 - exp(-sigma_k
+ * stream 5 keyed by (seed, iteration, ray): with z that key's 64-bit mix (rand01's top 24 bits are z >> 40) and `total` the union's pixels (box b holds
+ * [prefix[b], prefix[b + 1]), box order, then row-major), pixel p = ((z >> 40) total) >> 24 for total <= 2^24 and ((z >> 32) total) >> 32 above, so
+ * that every pixel of a union of up to 2^28 can be drawn.  Alpha and colour as the render computes them (sigma = exp(o3), c = logistic(o0..2), alpha_k = 1 - exp(-sigma_k
  * dt_k), the first interval from 0, the early cut at T < 1e-4):
  *   w_k = alpha_k T_k, T_end what remains; r = sum_k w_k (c_k - c*) (the background counts as the target colour); O = 1 - T_end;
  *   D = sum_k w_k t_k / |camera ray|
@@ -215,7 +217,8 @@ int mon_scene_render(mon_object* const* objs, size_t n_objs, int side, mon_frame
  * the pose goes back to the caller only.  side as in mon_scene_render: 0 the train-side weights (EMA once trained) on the train stream, the caller
  * serialises against training; 1 the published snapshot on the inference stream, callable while the object trains.  Each side has its own scratch.
  * Returns MON_ERR_ARG for NULL obj / obs / pose / params, n_obs 0, iters < 0, side not 0 / 1, rays_per_iter above 2^22, a FrameId the dataset does not hold,
- * a box empty or outside its frame (checked before any device work); MON_ERR_STATE for objects outside the fused shapes, the XORWOW render mode, and side 1
+ * a box empty or outside its frame, boxes holding more than 2^28 pixels together, more than 2^22 of them with rays_per_iter = 0 (checked before any device
+ * work); MON_ERR_STATE for objects outside the fused shapes, the XORWOW render mode, and side 1
  * with nothing published. */
 typedef struct mon_pose_refine_params {
     int      iters;          /* Adam steps of mon_object_refine_pose (>= 0)                                                                         */

@@ -82,13 +82,17 @@ struct Intrinsics { float fx, fy, cx, cy; int H, W; };
 // ---------------------------------------------------------------- counter RNG (bit-exact host/device)
 // Replaces the three curandGenerateUniform streams of GenerateBatch (nerf_model.cu:1432,1434,1468).
 enum { kStreamXY = 0, kStreamColor = 1, kStreamDt = 2, kStreamRender = 3 };
-__host__ __device__ inline float rand01(uint64_t seed, uint32_t stream, uint32_t step, uint32_t idx) {
+// the 64-bit mix of key (seed, stream, step, idx); rand01 keeps its top 24 bits
+__host__ __device__ inline uint64_t rand_mix(uint64_t seed, uint32_t stream, uint32_t step, uint32_t idx) {
     uint64_t ctr = ((uint64_t)stream << 60) | ((uint64_t)step << 28) | (uint64_t)(idx & 0x0fffffffu);
     uint64_t z = ctr + seed * 0x9E3779B97F4A7C15ull;
     z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
     z ^= z >> 27; z *= 0x94D049BB133111EBull;
     z ^= z >> 31;
-    return (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
+    return z;
+}
+__host__ __device__ inline float rand01(uint64_t seed, uint32_t stream, uint32_t step, uint32_t idx) {
+    return (float)(uint32_t)(rand_mix(seed, stream, step, idx) >> 40) * (1.0f / 16777216.0f);
 }
 
 // ---------------------------------------------------------------- hash grid index (tcnn grid_index / grid_hash)

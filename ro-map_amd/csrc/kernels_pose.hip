@@ -1,7 +1,7 @@
 // kernels_pose.hip -- object pose refinement through a trained field (mon_object_pose_loss / mon_object_refine_pose): the pose's rays, the loss and its
 // gradient with respect to the sample positions (forward + composite backward + MLP backward on MFMA + hash-grid position gradient), and the Adam step on
 // the twist.  Instantiated for the fused shapes only (MON_FUSED_DISPATCH); the network runs through the tile_forward / mlp_forward of fused_device.h.
-// The objective is stated in include/mon_core.h and DESIGN.md 3.6.
+// The objective is stated in include/mon_core.h and DESIGN.md 3.4d.
 #include <type_traits>
 #include "fused_device.h"
 
@@ -11,13 +11,15 @@ namespace mon {
 // One thread per drawn ray.  Pixel p of the union of the boxes (box b holds [prefix[b], prefix[b + 1])): ray i itself (every pixel) or a draw of stream
 // kStreamPoseXY.  Reads the pose from the device (pose[16], world -> object), builds the ray mon_object_render builds for that pixel, intersects it with the
 // box and fetches the target.  Record (4 x float4): {o, t0} {d, t1} {|camera ray|, hit, m*, d*} {c*, jitter index base (bits)}.
+// The draw (include/mon_core.h): z = the key's 64-bit mix; p = ((z >> 40) total) >> 24 for total <= 2^24 (rand01's 24 bits), else ((z >> 32) total) >> 32
+// -- a step of total / 2^32 < 1 pixel between consecutive 32-bit values, so every pixel of a union of up to 2^28 can be drawn.
 __global__ void __launch_bounds__(256) k_pose_rays(PoseRayArgs a) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n_rays) return;
     uint32_t p = i;
     if (a.drawn) {
-        const uint32_t u24 = (uint32_t)(rand01(a.seed, kStreamPoseXY, a.iteration, i) * 16777216.0f);
-        p = (uint32_t)(((uint64_t)u24 * a.total) >> 24);
+        const uint64_t z = rand_mix(a.seed, kStreamPoseXY, a.iteration, i);
+        p = a.total <= (1u << 24) ? (uint32_t)(((z >> 40) * a.total) >> 24) : (uint32_t)(((z >> 32) * a.total) >> 32);
     }
     uint32_t lo = 0u, hi = a.n_obs - 1u;                                                // the box: last b with prefix[b] <= p
     while (lo < hi) { const uint32_t mid = (lo + hi + 1u) >> 1; if (a.prefix[mid] <= p) lo = mid; else hi = mid - 1u; }

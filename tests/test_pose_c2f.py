@@ -3,8 +3,6 @@ k_pose_grad<.., LW = true> instantiations in kernels_pose.hip).  The bars are th
 for bit, weights of 0 give none, the gradient is linear in the weights and equals an fp64 torch autograd graph in which each level's position dependence is
 scaled by its weight, step i of a refinement uses the weights of step i, and the schedule brings a perturbed base.json object back."""
 import os
-import subprocess
-import sys
 import threading
 import time
 
@@ -13,15 +11,14 @@ import pytest
 
 from conftest import ROOT                                    # (first: it puts the repository root on the path of the torch child process)
 import __graft_entry__ as ge                                # noqa: E402
-from test_pose_refine import (_crops, _perturb, _pose_errors, _mat, _six_boxes, _targets, _level_table, _rays, _slab, _rand01, _corners,  # noqa: E402
-                              _snapshot_state, EPS)
+import pose_reference as pref                               # noqa: E402
+from test_pose_refine import _crops, _perturb, _pose_errors, _mat, _six_boxes, _snapshot_state      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 BASE = dict(sample_seed=5, use_depth=1)                     # base.json: 16 levels, 64 x 1
 NARROW = dict(sample_seed=7, n_neurons=32, n_hidden_layers=2, use_depth=1)
 WIDE = dict(sample_seed=8, n_neurons=128, n_hidden_layers=1, use_depth=1)
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def _bits(a):
@@ -116,103 +113,23 @@ def test_weighted_gradient_matches_fp64_autograd(pkg, orc, ss, scene, trained, t
     diag = float(np.linalg.norm(2 * ob["half"]))
     poses = [ob["Tow"], _perturb(ob["Tow"], 3.0, 0.03 * diag, seed=11)]
     w = _window(L, 6.4).astype(np.float32)                             # levels 0-5 whole, level 6 in the ramp, the rest off
-    off, scl, res = _level_table(orc, orc.default_config(n_levels=cfg.n_levels, log2_hashmap_size=cfg.log2_hashmap_size, base_resolution=cfg.base_resolution,
-                                                        per_level_scale=cfg.per_level_scale, n_neurons=cfg.n_neurons, n_hidden_layers=cfg.n_hidden_layers))
-    info = o.info(); results = []
+    aabb = np.stack([-ob["half"], ob["half"]]).astype(np.float32)
+    results, cases = [], []
     for Tow in poses:
         T16 = ss.colmajor(Tow)
         loss, g6 = o.pose_loss_levels(boxes, T16, w, prm)
         x, _, _ = o.pose_samples(boxes, T16, prm)
         results.append(dict(loss=loss, g6=g6, x=x))
-    tg = [_targets(sc, b, ob["cls"]) for b in boxes]
-    data = dict(boxes=boxes, Twc=np.stack([sc.Twc[int(b[0])] for b in boxes]), K=np.array([sc.fx, sc.fy, sc.cx, sc.cy, sc.W, sc.H]),
-                poses=np.stack(poses), aabb=np.stack([-ob["half"], ob["half"]]).astype(np.float32), seed=np.uint64(cfg.sample_seed),
-                params=o.get_params(2), n_mlp=info.n_mlp_params, L=L, W=cfg.n_neurons, NH=cfg.n_hidden_layers, Ep=info.encoded_width,
-                off=off, scl=scl, res=res, w=np.array([prm.w_rgb, prm.w_mask, prm.w_depth, prm.depth_huber]), lw=w,
-                gx0=results[0]["x"], gx1=results[1]["x"], tgt=np.concatenate([np.concatenate([t[0], t[1][:, None], t[2][:, None]], 1) for t in tg]))
-    np.savez(tmp_path / "in.npz", **data)
-    r = subprocess.run([sys.executable, os.path.join(HERE, "test_pose_c2f.py"), str(tmp_path / "in.npz"), str(tmp_path / "out.npz")], capture_output=True,
-                       text=True, timeout=900, cwd=ROOT)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
-    ref = np.load(tmp_path / "out.npz")
+        rr = pref.pose_rays(sc, boxes, Tow, aabb, ob["cls"], sample_seed=cfg.sample_seed)
+        cases.append(dict(x=x, t=rr["t"], hit=rr["hit"], dn=rr["dn"], tgt=rr["tgt"], lw=w, pos=rr["pos"]))
+    refs = pref.reference(tmp_path, pref.net_inputs(o, orc, prm), aabb, cases)
     for i, got in enumerate(results):
-        want6 = ref["g6_%d" % i]; ev = ref["ev%d" % i] > 0
-        assert np.abs(got["x"][ev] - ref["x%d" % i][ev]).max() < 1e-5, "sample positions"
-        assert abs(got["loss"] - float(ref["loss%d" % i])) <= 1e-4 * abs(float(ref["loss%d" % i]))
+        want6 = refs[i]["g6"]; ev = refs[i]["ev"]
+        assert np.abs(got["x"][ev] - cases[i]["pos"][ev]).max() < 1e-5, "sample positions"
+        assert abs(got["loss"] - refs[i]["loss"]) <= 1e-4 * abs(refs[i]["loss"])
         rel = np.linalg.norm(got["g6"] - want6) / np.linalg.norm(want6)
         print("pose %d: grad6(w) %s ref %s rel %.2e" % (i, np.array2string(got["g6"], precision=5), np.array2string(want6, precision=5), rel))
         assert rel <= 1e-2, rel
-
-
-def _torch_reference_weighted(inp, outp):
-    """Child process (torch and the HIP library do not share a process): test_pose_refine's fp64 graph of the objective, with level l's dependence on the
-    position scaled by lw[l] (x_l = x.detach() + lw[l] (x - x.detach())); the loss is unchanged."""
-    import torch
-    z = np.load(inp)
-    K, L, W, NH, Ep, nm = z["K"], int(z["L"]), int(z["W"]), int(z["NH"]), int(z["Ep"]), int(z["n_mlp"])
-    w_rgb, w_mask, w_depth, hub = (float(v) for v in z["w"])
-    lw = z["lw"].astype(np.float64)
-    prm = z["params"].view(np.float16).astype(np.float64)
-    table = torch.tensor(prm[nm:].reshape(-1, 2)); mats = []; o = 0
-    for layer in range(NH + 1):
-        rows = 16 if layer == NH else W; cols = Ep if layer == 0 else W
-        mats.append(torch.tensor(prm[o:o + rows * cols].reshape(rows, cols))); o += rows * cols
-    h16 = lambda v: v + (v.detach().to(torch.float16).to(torch.float64) - v.detach())     # noqa: E731
-    aabb = z["aabb"]; ext = (aabb[1] - aabb[0]).astype(np.float32)
-    out = {}
-    for pi, Tow in enumerate(z["poses"]):
-        xs, ts, hits, dns = [], [], [], []
-        for b, box in enumerate(z["boxes"]):
-            o_, d_, dn = _rays(K, z["Twc"][b], Tow, box)
-            hit, t0, t1 = _slab(aabb, o_, d_)
-            P = d_.shape[0]; q = np.arange(P)[:, None] * 64 + np.arange(64)[None, :]
-            dtr = (t1 - t0) / np.float32(64.0)
-            t = (dtr[:, None] * (np.arange(64, dtype=np.float32)[None, :] + _rand01(int(z["seed"]), 3, 0, q)) + t0[:, None]).astype(np.float32)
-            xs.append((t[..., None] * d_[:, None, :] + o_[:, None, :]).astype(np.float32)); ts.append(t); hits.append(hit); dns.append(dn)
-        x = np.concatenate(xs); t = np.concatenate(ts).astype(np.float64); hit = np.concatenate(hits); dn = np.concatenate(dns).astype(np.float64)
-        P = x.shape[0]; tg = z["tgt"]
-        out["x%d" % pi] = x
-        xg = z["gx%d" % pi].reshape(-1, 3).astype(np.float32)           # the device's own fp32 positions (see test_pose_refine._torch_reference)
-        xl = torch.tensor(xg.astype(np.float64), requires_grad=True)
-        xn = (xl - torch.tensor(aabb[0].astype(np.float64))) / torch.tensor(ext.astype(np.float64))
-        dxn = xn - xn.detach()
-        xn32 = ((xg - aabb[0]) / ext).astype(np.float32)
-        feats = [torch.zeros(P * 64, 2, dtype=torch.float64) for _ in range(L)]
-        for l, k, idx, frac in _corners(z["off"], z["scl"], z["res"], L, xn32):
-            fr = torch.tensor(frac) + float(z["scl"][l]) * (lw[l] * dxn)
-            wk = torch.ones(P * 64, dtype=torch.float64)
-            for d in range(3):
-                wk = wk * (fr[:, d] if (k >> d) & 1 else 1 - fr[:, d])
-            feats[l] = feats[l] + wk[:, None] * table[torch.tensor(idx)]
-        a = h16(torch.cat(feats + [torch.zeros(P * 64, Ep - 2 * L, dtype=torch.float64)], 1))
-        for layer in range(NH):
-            a = h16(torch.relu(a @ mats[layer].T))
-        raw = h16((a @ mats[NH].T)[:, :4]).reshape(P, 64, 4)
-        sigma = torch.exp(raw[..., 3]); col = torch.sigmoid(raw[..., :3])
-        tt = torch.tensor(t); dt = tt - torch.cat([torch.zeros(P, 1, dtype=torch.float64), tt[:, :-1]], 1)
-        alpha = 1 - torch.exp(-sigma * dt)
-        with torch.no_grad():
-            incl = torch.cumprod(1 - alpha, 1); T = torch.cat([torch.ones(P, 1, dtype=torch.float64), incl[:, :-1]], 1)
-            ev = torch.ones(P, 64, dtype=torch.bool); ev[:, 32:] = (T[:, 32] >= EPS)[:, None]
-            act = (T >= EPS) & ev & torch.tensor(hit)[:, None]
-        a2 = torch.where(act, alpha, torch.zeros_like(alpha))
-        T2 = torch.cumprod(torch.cat([torch.ones(P, 1, dtype=torch.float64), 1 - a2[:, :-1]], 1), 1)
-        wgt = a2 * T2
-        Tend = T2[:, -1] * (1 - a2[:, -1])
-        c_t = torch.tensor(tg[:, :3]); m = torch.tensor(tg[:, 3]); dd = torch.tensor(tg[:, 4])
-        r = (wgt[..., None] * (col - c_t[:, None, :])).sum(1)
-        O = 1 - Tend; D = (wgt * tt).sum(1) / torch.tensor(dn)
-        err = D - dd; ae = err.abs()
-        hub_v = torch.where(ae <= hub, 0.5 * err * err, hub * (ae - 0.5 * hub))
-        l = w_rgb * m * (r * r).sum(1) / 3 + w_mask * (O - m) ** 2 + w_depth * m * (dd > 0).double() * hub_v
-        Lm = l.mean()
-        Lm.backward()
-        gx = xl.grad.numpy().reshape(-1, 3)
-        xo = xg.reshape(-1, 3).astype(np.float64)
-        out["g6_%d" % pi] = np.concatenate([gx.sum(0), np.cross(xo, gx).sum(0)])
-        out["loss%d" % pi] = float(Lm.detach())
-        out["ev%d" % pi] = (ev.numpy() & hit[:, None]).astype(np.uint8)
-    np.savez(outp, **out)
 
 
 # ------------------------------------------------------------------ 4. step i of a refinement uses the weights of step i
@@ -435,7 +352,3 @@ def test_c2f_errors(pkg, ss, scene, trained):
     finally:
         for q in (lk, x, fresh):
             q.close()
-
-
-if __name__ == "__main__":
-    _torch_reference_weighted(sys.argv[1], sys.argv[2])

@@ -4,23 +4,21 @@ samples, the gradient equals an fp64 torch autograd graph of the same objective 
 perturbed pose back, and nothing about the object changes."""
 import math
 import os
-import subprocess
-import sys
 import threading
 import time
 
 import numpy as np
 import pytest
 
-from conftest import ROOT                                    # (first: it puts the repository root on the path of the torch child process)
+from conftest import ROOT                                    # (first: it puts the repository root on the path)
 import __graft_entry__ as ge                                # noqa: E402
+import pose_reference as pref                               # noqa: E402
+from pose_reference import targets as _targets, EPS         # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-EPS = 1e-4                                                  # kTransmittanceEps
 BASE = dict(sample_seed=5, use_depth=1)                     # base.json: 16 levels, 64 x 1
 NARROW = dict(sample_seed=7, n_neurons=32, n_hidden_layers=2, use_depth=1)
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
@@ -93,14 +91,6 @@ def _dn(sc, box):
     return np.sqrt(a * a + b * b + np.float32(1.0)).reshape(-1)
 
 
-def _targets(sc, box, cls):
-    v, x0, y0, h, w = (int(q) for q in box)
-    rgb = sc.rgb[v, y0:y0 + h, x0:x0 + w].reshape(-1, 3).astype(np.float32) / np.float32(255.0)
-    m = (sc.instance[v, y0:y0 + h, x0:x0 + w].reshape(-1) == cls).astype(np.float64)
-    d = sc.depth[v, y0:y0 + h, x0:x0 + w].reshape(-1).astype(np.float64)
-    return rgb.astype(np.float64), m, d
-
-
 def _huber(x, delta):
     ax = np.abs(x)
     return np.where(ax <= delta, 0.5 * x * x, delta * (ax - 0.5 * delta))
@@ -137,13 +127,6 @@ def test_loss_equals_numpy_restatement(pkg, ss, scene, trained, name):
 
 
 # ------------------------------------------------------------------ 2. the gradient is fp64 autograd of the same objective
-def _level_table(orc, cfg):
-    import ctypes as C
-    off = np.zeros(17, np.uint32); sc = np.zeros(16, np.float32); res = np.zeros(16, np.uint32)
-    orc.lib().orc_level_table(C.byref(cfg), off.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), res.ctypes.data_as(C.c_void_p))
-    return off, sc, res
-
-
 @pytest.mark.parametrize("side", [0, 1])
 @pytest.mark.parametrize("name", ["base", "narrow"])
 def test_gradient_matches_fp64_autograd(pkg, orc, ss, scene, trained, name, side, tmp_path):
@@ -154,33 +137,21 @@ def test_gradient_matches_fp64_autograd(pkg, orc, ss, scene, trained, name, side
     boxes = _crops(sc); prm = pkg.pose_refine_default(rays_per_iter=0)
     diag = float(np.linalg.norm(2 * ob["half"]))
     poses = [ob["Tow"], _perturb(ob["Tow"], 3.0, 0.03 * diag, seed=11)]
-    cfg = o.cfg
-    off, scl, res = _level_table(orc, orc.default_config(n_levels=cfg.n_levels, log2_hashmap_size=cfg.log2_hashmap_size, base_resolution=cfg.base_resolution,
-                                                        per_level_scale=cfg.per_level_scale, n_neurons=cfg.n_neurons, n_hidden_layers=cfg.n_hidden_layers))
-    params = o.get_params(2)                                # EMA: side 0's weights, and the snapshot published at the end of train()
-    info = o.info()
-    results = []
+    aabb = np.stack([-ob["half"], ob["half"]]).astype(np.float32)
+    results, cases = [], []
     for Tow in poses:
         T16 = ss.colmajor(Tow)
         loss, g6 = o.pose_loss(boxes, T16, prm, side=side)
         x, raw, dldx = o.pose_samples(boxes, T16, prm, side=side)
         results.append(dict(loss=loss, g6=g6, x=x, raw=raw, dldx=dldx))
-    data = dict(boxes=boxes, Twc=np.stack([sc.Twc[int(b[0])] for b in boxes]), K=np.array([sc.fx, sc.fy, sc.cx, sc.cy, sc.W, sc.H]),
-                poses=np.stack(poses), aabb=np.stack([-ob["half"], ob["half"]]).astype(np.float32), seed=np.uint64(cfg.sample_seed),
-                params=params, n_mlp=info.n_mlp_params, L=cfg.n_levels, W=cfg.n_neurons, NH=cfg.n_hidden_layers, Ep=info.encoded_width,
-                off=off, scl=scl, res=res, w=np.array([prm.w_rgb, prm.w_mask, prm.w_depth, prm.depth_huber]),
-                gx0=results[0]["x"], gx1=results[1]["x"],
-                tgt=np.concatenate([np.concatenate([_targets(sc, b, ob["cls"])[0], _targets(sc, b, ob["cls"])[1][:, None],
-                                                    _targets(sc, b, ob["cls"])[2][:, None]], 1) for b in boxes]))
-    np.savez(tmp_path / "in.npz", **data)
-    r = subprocess.run([sys.executable, os.path.join(HERE, "test_pose_refine.py"), str(tmp_path / "in.npz"), str(tmp_path / "out.npz")], capture_output=True,
-                       text=True, timeout=900, cwd=ROOT)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
-    ref = np.load(tmp_path / "out.npz")
+        rr = pref.pose_rays(sc, boxes, Tow, aabb, ob["cls"], sample_seed=o.cfg.sample_seed)
+        cases.append(dict(x=x, t=rr["t"], hit=rr["hit"], dn=rr["dn"], tgt=rr["tgt"], pos=rr["pos"]))
+    refs = pref.reference(tmp_path, pref.net_inputs(o, orc, prm), aabb, cases)
     for i, got in enumerate(results):
-        xs = ref["x%d" % i]; want6 = ref["g6_%d" % i]; want_s = ref["gs%d" % i]; ev = ref["ev%d" % i] > 0
+        ref = refs[i]; xs = cases[i]["pos"]; want6 = ref["g6"]; ev = ref["ev"]
+        want_s = ref["gs"] / got["x"].shape[0]                             # the gradient of the mean
         assert np.abs(got["x"][ev] - xs[ev]).max() < 1e-5, "sample positions"
-        assert abs(got["loss"] - float(ref["loss%d" % i])) <= 1e-4 * abs(float(ref["loss%d" % i]))
+        assert abs(got["loss"] - ref["loss"]) <= 1e-4 * abs(ref["loss"])
         rel = np.linalg.norm(got["g6"] - want6) / np.linalg.norm(want6)
         gs = got["dldx"][ev]; ws = want_s[ev]
         scale = np.linalg.norm(ws, axis=-1).max()
@@ -190,137 +161,6 @@ def test_gradient_matches_fp64_autograd(pkg, orc, ss, scene, trained, name, side
               np.array2string(got["g6"], precision=5), np.array2string(want6, precision=5), rel, ok.mean(), ok.size))
         assert rel <= 1e-2, rel
         assert ok.mean() >= 0.999, ok.mean()
-
-
-def _rand01(seed, stream, step, idx):
-    """device_common.h rand01 in numpy uint64 arithmetic"""
-    M = np.uint64(0xFFFFFFFFFFFFFFFF)
-    idx = np.asarray(idx, np.uint64)
-    ctr = (np.uint64(stream) << np.uint64(60)) | (np.uint64(step) << np.uint64(28)) | (idx & np.uint64(0x0fffffff))
-    with np.errstate(over="ignore"):
-        z = ctr + np.uint64(seed) * np.uint64(0x9E3779B97F4A7C15)
-        z = z ^ (z >> np.uint64(30)); z = z * np.uint64(0xBF58476D1CE4E5B9)
-        z = z ^ (z >> np.uint64(27)); z = z * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-    return (z >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
-
-
-def _rays(K, Twc, Tow, box):
-    """pixel_ray + ray_intersect (device_common.h) in float32 numpy"""
-    f32 = np.float32
-    fx, fy, cx, cy = (f32(v) for v in K[:4])
-    v, x0, y0, h, w = (int(q) for q in box)
-    py, px = np.mgrid[y0:y0 + h, x0:x0 + w].astype(np.float32)
-    dc = np.stack([(px - cx) / fx, (py - cy) / fy, np.ones_like(px)], -1).reshape(-1, 3)
-    n = np.sqrt((dc * dc).sum(-1, dtype=np.float32)).astype(np.float32)
-    dn = dc / n[:, None]
-    Rwc = Twc[:3, :3].astype(np.float32); Row = Tow[:3, :3].astype(np.float32)
-    dw = dn @ Rwc.T; d = (dw @ Row.T).astype(np.float32)
-    o = (Row @ Twc[:3, 3].astype(np.float32) + Tow[:3, 3].astype(np.float32)).astype(np.float32)
-    return np.broadcast_to(o, d.shape).copy(), d, n
-
-
-def _slab(aabb, o, d):
-    with np.errstate(divide="ignore", invalid="ignore"):
-        a = (aabb[0][None] - o) / d; b = (aabb[1][None] - o) / d
-    lo = np.minimum(a, b); hi = np.maximum(a, b)
-    t0 = lo.max(1); t1 = hi.min(1)
-    return t0 <= t1, np.maximum(t0, np.float32(0.0)), t1
-
-
-def _corners(off, scl, res, L, x):
-    for l in range(L):
-        size = int(off[l + 1] - off[l]); r = int(res[l])
-        pos = (np.float64(scl[l]) * x.astype(np.float64) + 0.5).astype(np.float32).astype(np.float64)       # fmaf: the product is exact in fp64
-        g = np.floor(pos); gi = g.astype(np.int64)
-        for k in range(8):
-            q = [gi[:, d] + ((k >> d) & 1) for d in range(3)]
-            qx, qy, qz = (np.asarray(v, np.uint64) & np.uint64(0xffffffff) for v in q)
-            stride, dense = 1, np.zeros(x.shape[0], np.uint64)
-            for coord in (qx, qy, qz):
-                if stride <= size:
-                    dense = (dense + coord * np.uint64(stride)) & np.uint64(0xffffffff); stride = (stride * r) & 0xffffffff
-            if size < stride:
-                idx = ((qx ^ (qy * np.uint64(2654435761) & np.uint64(0xffffffff)) ^ (qz * np.uint64(805459861) & np.uint64(0xffffffff)))
-                       & np.uint64(0xffffffff)) % np.uint64(size)
-            else:
-                idx = dense % np.uint64(size)
-            yield l, k, idx.astype(np.int64) + int(off[l]), pos - g
-
-
-def _torch_reference(inp, outp):
-    """Child process (torch and the HIP library do not share a process): the objective as one fp64 autograd graph in the sample positions."""
-    import torch
-    z = np.load(inp)
-    K, L, W, NH, Ep, nm = z["K"], int(z["L"]), int(z["W"]), int(z["NH"]), int(z["Ep"]), int(z["n_mlp"])
-    w_rgb, w_mask, w_depth, hub = (float(v) for v in z["w"])
-    prm = z["params"].view(np.float16).astype(np.float64)
-    table = torch.tensor(prm[nm:].reshape(-1, 2)); mats = []; o = 0
-    for layer in range(NH + 1):
-        rows = 16 if layer == NH else W; cols = Ep if layer == 0 else W
-        mats.append(torch.tensor(prm[o:o + rows * cols].reshape(rows, cols))); o += rows * cols
-    h16 = lambda v: v + (v.detach().to(torch.float16).to(torch.float64) - v.detach())     # noqa: E731
-    aabb = z["aabb"]; ext = (aabb[1] - aabb[0]).astype(np.float32)
-    out = {}
-    for pi, Tow in enumerate(z["poses"]):
-        xs, ts, hits, dns = [], [], [], []
-        for b, box in enumerate(z["boxes"]):
-            o_, d_, dn = _rays(K, z["Twc"][b], Tow, box)
-            hit, t0, t1 = _slab(aabb, o_, d_)
-            P = d_.shape[0]; q = np.arange(P)[:, None] * 64 + np.arange(64)[None, :]
-            dtr = (t1 - t0) / np.float32(64.0)
-            t = (dtr[:, None] * (np.arange(64, dtype=np.float32)[None, :] + _rand01(int(z["seed"]), 3, 0, q)) + t0[:, None]).astype(np.float32)
-            x = (t[..., None] * d_[:, None, :] + o_[:, None, :]).astype(np.float32)
-            xs.append(x); ts.append(t); hits.append(hit); dns.append(dn)
-        x = np.concatenate(xs); t = np.concatenate(ts).astype(np.float64); hit = np.concatenate(hits); dn = np.concatenate(dns).astype(np.float64)
-        P = x.shape[0]; tg = z["tgt"]
-        out["x%d" % pi] = x
-        # the graph runs on the device's own fp32 positions (the restated ones agree to ~1e-7, checked by the parent): at the finest levels
-        # (scale 2^19) one ulp of x is a few hundredths of a cell, so the trilinear weights are taken from the same fp32 arithmetic the kernel does
-        # (normalised position by fp32 subtract / divide, fmaf(scale, x, 0.5) exactly), and only their derivative comes from the graph
-        xg = z["gx%d" % pi].reshape(-1, 3).astype(np.float32)
-        xl = torch.tensor(xg.astype(np.float64), requires_grad=True)
-        xn = (xl - torch.tensor(aabb[0].astype(np.float64))) / torch.tensor(ext.astype(np.float64))
-        dxn = xn - xn.detach()
-        xn32 = ((xg - aabb[0]) / ext).astype(np.float32)
-        x = xg.reshape(P, 64, 3)
-        feats = [torch.zeros(P * 64, 2, dtype=torch.float64) for _ in range(L)]
-        for l, k, idx, frac in _corners(z["off"], z["scl"], z["res"], L, xn32):
-            fr = torch.tensor(frac) + float(z["scl"][l]) * dxn
-            wk = torch.ones(P * 64, dtype=torch.float64)
-            for d in range(3):
-                wk = wk * (fr[:, d] if (k >> d) & 1 else 1 - fr[:, d])
-            feats[l] = feats[l] + wk[:, None] * table[torch.tensor(idx)]
-        a = h16(torch.cat(feats + [torch.zeros(P * 64, Ep - 2 * L, dtype=torch.float64)], 1))
-        for layer in range(NH):
-            a = h16(torch.relu(a @ mats[layer].T))
-        raw = h16((a @ mats[NH].T)[:, :4]).reshape(P, 64, 4)
-        sigma = torch.exp(raw[..., 3]); col = torch.sigmoid(raw[..., :3])
-        tt = torch.tensor(t); dt = tt - torch.cat([torch.zeros(P, 1, dtype=torch.float64), tt[:, :-1]], 1)
-        alpha = 1 - torch.exp(-sigma * dt)
-        # the early cut and the second tile's evaluation held at the forward's values
-        with torch.no_grad():
-            incl = torch.cumprod(1 - alpha, 1); T = torch.cat([torch.ones(P, 1, dtype=torch.float64), incl[:, :-1]], 1)
-            ev = torch.ones(P, 64, dtype=torch.bool); ev[:, 32:] = (T[:, 32] >= EPS)[:, None]
-            act = (T >= EPS) & ev & torch.tensor(hit)[:, None]
-        a2 = torch.where(act, alpha, torch.zeros_like(alpha))
-        T2 = torch.cumprod(torch.cat([torch.ones(P, 1, dtype=torch.float64), 1 - a2[:, :-1]], 1), 1)
-        wgt = a2 * T2
-        Tend = T2[:, -1] * (1 - a2[:, -1])
-        c_t = torch.tensor(tg[:, :3]); m = torch.tensor(tg[:, 3]); dd = torch.tensor(tg[:, 4])
-        r = (wgt[..., None] * (col - c_t[:, None, :])).sum(1)
-        O = 1 - Tend; D = (wgt * tt).sum(1) / torch.tensor(dn)
-        err = D - dd; ae = err.abs()
-        hub_v = torch.where(ae <= hub, 0.5 * err * err, hub * (ae - 0.5 * hub))
-        l = w_rgb * m * (r * r).sum(1) / 3 + w_mask * (O - m) ** 2 + w_depth * m * (dd > 0).double() * hub_v
-        Lm = l.mean()
-        Lm.backward()
-        gx = xl.grad.numpy().reshape(P, 64, 3)
-        xo = x.reshape(P, 64, 3).astype(np.float64)
-        out["g6_%d" % pi] = np.concatenate([gx.reshape(-1, 3).sum(0), np.cross(xo.reshape(-1, 3), gx.reshape(-1, 3)).sum(0)])
-        out["gs%d" % pi] = gx; out["loss%d" % pi] = float(Lm.detach())
-        out["ev%d" % pi] = (ev.numpy() & hit[:, None]).astype(np.uint8)
-    np.savez(outp, **out)
 
 
 # ------------------------------------------------------------------ 3. refinement pulls a perturbed pose back
@@ -472,7 +312,3 @@ def test_pose_refine_errors(pkg, ss, scene, trained):
     finally:
         for q in (c, x, fresh):
             q.close()
-
-
-if __name__ == "__main__":
-    _torch_reference(sys.argv[1], sys.argv[2])
