@@ -3,6 +3,7 @@
 #pragma once
 #include "device_common.h"
 #include "model.h"
+#include "store_policy.h"
 
 namespace mon {
 
@@ -52,7 +53,7 @@ __device__ __forceinline__ void points_sample(PointsLds& l, const BatchPtrs& b, 
 #pragma unroll
     for (int d = 0; d < 3; ++d) { const float p = fmaf(t, b.cand_d[3u * cand + d], b.cand_o[3u * cand + d]);
         x[d] = (p - oc.aabb.mn[d]) / (oc.aabb.mx[d] - oc.aabb.mn[d]); }
-    x_all[s] = float4_t{ x[0], x[1], x[2], t };
+    policy_store<MON_SP_XALL>(float4_t{ x[0], x[1], x[2], t }, x_all + s);
     uint32_t live_word = 0u;
     if constexpr (LIVE) {
         // (the cell lookup of k_fused_train's ray_sample and of the render's grid: device_common.h)
@@ -75,10 +76,11 @@ __device__ __forceinline__ void points_sample(PointsLds& l, const BatchPtrs& b, 
     }
     if (n == 0u && b.ray_rec) {          // the ray's record for k_fused_train<PRE> (the fields its load_record collects from the candidate arrays)
         float* r = b.ray_rec + 12u * (size_t)ray;
-        reinterpret_cast<float4_t*>(r)[0] = float4_t{ __builtin_bit_cast(float, b.cand_rgba[cand]), t0, t1, b.cand_d[3u * cand] };
-        reinterpret_cast<float4_t*>(r)[1] = float4_t{ b.cand_d[3u * cand + 1u], b.cand_d[3u * cand + 2u], b.cand_o[3u * cand], b.cand_o[3u * cand + 1u] };
-        reinterpret_cast<float4_t*>(r)[2] = float4_t{ b.cand_o[3u * cand + 2u], b.cand_depth[cand], __builtin_bit_cast(float, cand),
-                __builtin_bit_cast(float, live_word) };
+        float4_t* r4 = reinterpret_cast<float4_t*>(r);
+        policy_store<MON_SP_XALL>(float4_t{ __builtin_bit_cast(float, b.cand_rgba[cand]), t0, t1, b.cand_d[3u * cand] }, r4);
+        policy_store<MON_SP_XALL>(float4_t{ b.cand_d[3u * cand + 1u], b.cand_d[3u * cand + 2u], b.cand_o[3u * cand], b.cand_o[3u * cand + 1u] }, r4 + 1);
+        policy_store<MON_SP_XALL>(float4_t{ b.cand_o[3u * cand + 2u], b.cand_depth[cand], __builtin_bit_cast(float, cand), __builtin_bit_cast(float, live_word) },
+                r4 + 2);
     }
 }
 

@@ -36,6 +36,7 @@
 #include "frag_layout.h"
 #include "batch_device.h"
 #include "grid_walk.h"
+#include "store_policy.h"
 
 namespace mon {
 

@@ -21,6 +21,7 @@
 #include "batch_device.h"
 #include "encode_device.h"
 #include "tile_device.h"
+#include "store_policy.h"
 #include "xorwow.h"
 #ifdef MON_OVERLAP_PROBE
 #include <hip/hip_ext.h>
@@ -128,7 +129,7 @@ __device__ __forceinline__ void encode_whole(const uint32_t* tile, const EncodeA
 #pragma unroll
         for (int j = 0; j < 4; ++j) { c0[j] = tile[i0[j]]; c1[j] = tile[i1[j]]; }
         const half2_t e = enc_chain(c0, c1, pos);
-        if (slot[k] != 0xffffffffu) out[slot[k]] = e;
+        if (slot[k] != 0xffffffffu) policy_store<MON_SP_E>(e, out + slot[k]);
     }
 }
 
@@ -178,7 +179,7 @@ __device__ __forceinline__ void encode_parity(uint32_t* tile, const uint4* __res
                 c0[j] = odd0 ? vodd : veven[k][j]; c1[j] = odd0 ? veven[k][j] : vodd;
             }
             const half2_t e = enc_chain(c0, c1, pos[k]);
-            if (slot[k] != 0xffffffffu) out[slot[k]] = e;
+            if (slot[k] != 0xffffffffu) policy_store<MON_SP_E>(e, out + slot[k]);
         }
     }
 }

@@ -12,6 +12,9 @@ template <int EPAD, int W, int NH, bool DUMP, bool ATOMIC_LEVELS, bool OCC = fal
 // activations in up to 512 registers at one wave per SIMD)
 __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 : 2)) k_fused_train(FusedArgs a) {
     using S = FusedShape<EPAD, W, NH>;
+    // store policies of the hand-over buffers (store_policy.h); tables with global-atomic levels (HBM-bound, unmeasured) keep plain stores
+    constexpr int kSpX = ATOMIC_LEVELS ? MON_SP_PLAIN : MON_SP_XSOA, kSpDe = ATOMIC_LEVELS ? MON_SP_PLAIN : MON_SP_DE;
+    constexpr int kSpDw = ATOMIC_LEVELS ? MON_SP_PLAIN : MON_SP_DW, kSpRay = ATOMIC_LEVELS ? MON_SP_PLAIN : MON_SP_RAYOUT;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     half_t* frags = reinterpret_cast<half_t*>(smem);
     LevelLds* llt = reinterpret_cast<LevelLds*>(smem + S::FRAG_BYTES);
@@ -260,8 +263,9 @@ __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 :
         if (nz_cnt != 0u && lane == 0 && lds_level_mask) slot_base = atomicAdd(&a.st->n_scatter[scatter_counter(iter, ray & (n_bins - 1u))], nz_cnt);
         if (lane == 0) {
             loss_acc += loss;
-            a.b.rgb_ray[3 * ray] = rgb0; a.b.rgb_ray[3 * ray + 1] = rgb1; a.b.rgb_ray[3 * ray + 2] = rgb2;
-            a.b.depth_ray[ray] = dep; a.b.mask_ray[ray] = mask; a.b.loss_ray[ray] = loss;
+            policy_store<kSpRay>(rgb0, a.b.rgb_ray + 3 * ray); policy_store<kSpRay>(rgb1, a.b.rgb_ray + 3 * ray + 1);
+            policy_store<kSpRay>(rgb2, a.b.rgb_ray + 3 * ray + 2);
+            policy_store<kSpRay>(dep, a.b.depth_ray + ray); policy_store<kSpRay>(mask, a.b.mask_ray + ray); policy_store<kSpRay>(loss, a.b.loss_ray + ray);
         }
         if (DUMP) {
             if (lane == 0) {
@@ -407,7 +411,7 @@ __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 :
         const uint32_t slot = (ray & (n_bins - 1u)) * bin_cap + in_bin;                    // a bin holds the samples of R / n_bins rays at most
         const bool do_store = mine && in_bin < bin_cap;
         // one 16-byte store per sample
-        if (lds_level_mask && h == 0 && do_store) reinterpret_cast<float4_t*>(a.x_soa)[slot] = float4_t{ x[0], x[1], x[2], 0.f };
+        if (lds_level_mask && h == 0 && do_store) policy_store<kSpX>(float4_t{ x[0], x[1], x[2], 0.f }, reinterpret_cast<float4_t*>(a.x_soa) + slot);
 #pragma unroll
         for (int il = 0; il < S::LLV; ++il) {
             const int level = h * LPH + il;
@@ -415,8 +419,8 @@ __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 :
                 const half_t q0 = (half_t)de[2 * il], q1 = (half_t)de[2 * il + 1];
                 if (!ATOMIC_LEVELS || ((lds_level_mask >> level) & 1u)) {
                     // (clamped to the fixed-point range of the exact LDS accumulation, LevelFast::fix_clamp: |dL/dE| * fix_scale stays inside int32)
-                    if (do_store) a.de_soa[(size_t)level * Btot + slot] = half2_t{ (half_t)clamp_f((float)q0, -a.lt.fix_clamp, a.lt.fix_clamp),
-                            (half_t)clamp_f((float)q1, -a.lt.fix_clamp, a.lt.fix_clamp) };
+                    if (do_store) policy_store<kSpDe>(half2_t{ (half_t)clamp_f((float)q0, -a.lt.fix_clamp, a.lt.fix_clamp),
+                            (half_t)clamp_f((float)q1, -a.lt.fix_clamp, a.lt.fix_clamp) }, a.de_soa + (size_t)level * Btot + slot);
                 } else if constexpr (ATOMIC_LEVELS) {
                     const float gq0 = (float)q0, gq1 = (float)q1;
                     if (gq0 != 0.f || gq1 != 0.f) {
@@ -464,7 +468,7 @@ __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 :
         for (int i = threadIdx.x * 4; i < S::ACC_COLS; i += blockDim.x * 4) {
             const float4_t v0 = *reinterpret_cast<const float4_t*>(r0 + i), v1 = *reinterpret_cast<const float4_t*>(r0 + ST + i);
             const float4_t v2 = *reinterpret_cast<const float4_t*>(r0 + 2 * ST + i), v3 = *reinterpret_cast<const float4_t*>(r0 + 3 * ST + i);
-            *reinterpret_cast<float4_t*>(dst + i) = (v0 + v1) + (v2 + v3);
+            policy_store<kSpDw>((v0 + v1) + (v2 + v3), reinterpret_cast<float4_t*>(dst + i));
         }
         if (threadIdx.x == 0) dst[S::ACC_COLS] = (r0[S::ACC_COLS] + r0[ST + S::ACC_COLS]) + (r0[2 * ST + S::ACC_COLS] + r0[3 * ST + S::ACC_COLS]);
     }

@@ -19,16 +19,15 @@
 #include "frag_layout.h"
 #include "batch_device.h"
 #include "encode_device.h"
+#include "store_policy.h"
 
 namespace mon {
 
 // Optimizer state is not read again before the next step.  Small tables (everything streamed once per step, working set inside the Infinity Cache):
-// non-temporal stores, a wash against plain ones (round 2).  LARGE tables (T = 2^22: 2-3 GB of scattered 32-byte pieces per step, HBM-bound): plain stores --
+// policy MON_SP_STATE (store_policy.h; profiles/r10_store_policy.md).  LARGE tables (T = 2^22: 2-3 GB of scattered 32-byte pieces per step, HBM-bound): plain stores --
 // the L2 merges a chunk's pieces into whole lines before they leave; non-temporal ones cost 20 % of the kernel there (645-725 us against 535-550 us over steps
 // 20..40, four runs each).
-template <bool NT, class T> __device__ __forceinline__ void state_store(T v, T* p) {
-    if constexpr (NT) __builtin_nontemporal_store(v, p); else *p = v;
-}
+template <bool STREAM, class T> __device__ __forceinline__ void state_store(T v, T* p) { policy_store<STREAM ? MON_SP_STATE : MON_SP_PLAIN>(v, p); }
 
 __device__ __forceinline__ float adam_update(float g, float w, float& m1, float& m2, uint32_t& steps, float lr0, const OptimConst& oc, uint32_t step_cap) {
     const float gsq = g * g;
@@ -64,6 +63,9 @@ __global__ void __launch_bounds__(256) k_optimizer(ParamPtrs p, OptimConst oc, c
     const uint32_t n_extra = nx.cand_blocks + nx.pos_blocks, n_opt = gridDim.x - n_extra, vblock = blockIdx.x < n_opt ? blockIdx.x + n_extra
             : blockIdx.x - n_opt;
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    // store policies of what the next iteration's kernels read (store_policy.h): the small-table instantiations only; large tables (HBM-bound) keep plain stores
+    constexpr int kSpHalf = DENSE ? MON_SP_HALF : MON_SP_PLAIN, kSpTiles = DENSE ? MON_SP_TILES : MON_SP_PLAIN, kSpEma = DENSE ? MON_SP_EMA : MON_SP_PLAIN;
+    constexpr int kSpFrag = DENSE ? MON_SP_FRAG : MON_SP_PLAIN;
     // (chunk records exist for the lazy optimizer of large tables only: compile-time null in the dense instantiations, whose record branches fold away)
     float* const prec = LAZY ? p.rec : nullptr;
     const uint32_t step_cap = (p.steps16 || prec) ? 65535u : 0xffffffffu;
@@ -301,31 +303,31 @@ __global__ void __launch_bounds__(256) k_optimizer(ParamPtrs p, OptimConst oc, c
                         reinterpret_cast<u4v*>(st_steps16(c)));
                 else { state_store<!LAZY>(u4v{ sc[0], sc[1], sc[2], sc[3] }, reinterpret_cast<u4v*>(p.steps + i0));
                     state_store<!LAZY>(u4v{ sc[4], sc[5], sc[6], sc[7] }, reinterpret_cast<u4v*>(p.steps + i0 + 4)); }
-                *reinterpret_cast<half8_t*>(p.half + i0) = wh;
+                policy_store<kSpHalf>(wh, reinterpret_cast<half8_t*>(p.half + i0));
 #if defined(MON_OPT_ABLATE) && (MON_OPT_ABLATE & 8)
                 if (false) {
 #else
                 if (p.half_tiles && !is_matrix) {
 #endif                                     // the same four entries in tile order for k_encode_tiles (tile_slot): whole level = as they are, else evens | odds
                     const uint32_t e0 = (i0 - oc.n_mlp) >> 1, size = lvl_end - lvl_off, e_rel = e0 - lvl_off;
-                    if (size <= kEncWholeMax) *reinterpret_cast<half8_t*>(p.half_tiles + 2u * (size_t)e0) = wh;
+                    if (size <= kEncWholeMax) policy_store<kSpTiles>(wh, reinterpret_cast<half8_t*>(p.half_tiles + 2u * (size_t)e0));
                     else {
                         const size_t s0 = lvl_off + (e_rel >> 1);
-                        *reinterpret_cast<half4_t*>(p.half_tiles + 2u * s0) = half4_t{ wh[0], wh[1], wh[4], wh[5] };
-                        *reinterpret_cast<half4_t*>(p.half_tiles + 2u * (s0 + (size >> 1))) = half4_t{ wh[2], wh[3], wh[6], wh[7] };
+                        policy_store<kSpTiles>(half4_t{ wh[0], wh[1], wh[4], wh[5] }, reinterpret_cast<half4_t*>(p.half_tiles + 2u * s0));
+                        policy_store<kSpTiles>(half4_t{ wh[2], wh[3], wh[6], wh[7] }, reinterpret_cast<half4_t*>(p.half_tiles + 2u * (s0 + (size >> 1))));
                     }
                 }
                 if (is_matrix && nx.frag_image) {                                     // next iteration's A fragments
 #pragma unroll
                     for (int j = 0; j < 8; ++j) { int sl[2]; const int ns = frag_slots(nx.fd, (int)(i0 + j), sl);
-                        for (int q = 0; q < ns; ++q) reinterpret_cast<half_t*>(nx.frag_image)[sl[q]] = wh[j]; }
+                        for (int q = 0; q < ns; ++q) policy_store<kSpFrag>((half_t)wh[j], reinterpret_cast<half_t*>(nx.frag_image) + sl[q]); }
                 }
             }
             half8_t* ep = reinterpret_cast<half8_t*>(p.ema + i0);
             half8_t e = ema_in;
 #pragma unroll
             for (int j = 0; j < 8; ++j) e[j] = (half_t)((((float)e[j] * d) * deb_old + (float)wh[j] * (1.f - d)) * deb_new);
-            *ep = e;
+            policy_store<kSpEma>(e, ep);
         };
         if constexpr (LAZY) {
             // Few chunks carry a gradient, but nearly every wave has SOME lane that does in every iteration, so handling them in place makes

@@ -308,32 +308,18 @@ __global__ void __launch_bounds__(1024) k_grid_scatter(LevelFast lt, ScatterLeve
                                                        const DevState* __restrict__ st, DevState* st_rw, DevState* st_next, PartialsArgs pa,
                                                        float* __restrict__ timing) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const uint32_t iter = st->iter;
-    // (the last workgroup: the first ones hold the coarse dense levels, the kernel's critical path)
-    if (blockIdx.x == MON_HOUSEKEEPING_BLOCK && threadIdx.x < 64u) {
-        // slot-counter housekeeping (also for a skipped batch): clear the counters k_fused_train of the NEXT iteration counts in -- they live in the other
-        // DevState, which nobody reads during this iteration -- and note how many samples carried a gradient in this one (k_optimizer hands it to the next
-        // iteration as n_scatter_last; the large-table path decides on it)
-        uint32_t v = 0u;
-        for (uint32_t b = threadIdx.x; b < n_bins; b += 64u) { v += st->n_scatter[scatter_counter(iter, b)];
-            st_next->n_scatter[scatter_counter(iter + 1u, b)] = 0u; }
-        v = scan_add64_u32(v);
-        if (threadIdx.x == 63u) st_rw->n_scatter_now = v;
-    }
-    if (st->n_valid == 0u) return;
 #ifdef MON_SCATTER_TIMING
     long long tq[10]; int tn = 0;
 #define MON_ST_STAMP() do { __builtin_amdgcn_s_waitcnt(0); tq[tn++] = clock64(); } while (0)
+#define MON_ST_STAMP_NOWAIT() do { tq[tn++] = clock64(); } while (0)      // (between the entry loads and their first use: a wait would serialise what is measured)
 #else
 #define MON_ST_STAMP() do { } while (0)
+#define MON_ST_STAMP_NOWAIT() do { } while (0)
 #endif
     MON_ST_STAMP();
-    float4_t pacc[kPartialsMaxPasses];
-    bool pacc_loaded = false;
-    int* tab = reinterpret_cast<int*>(smem);
-    // scatter_item addresses the hashed levels' tiles from LDS offset 0
-    if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem != 0u) __builtin_trap();
-    float* red = reinterpret_cast<float*>(smem + (size_t)kScatterLdsBytes - 256u);     // 256 B behind the largest tile
+    // ---- entry: everything the kernel needs from memory is requested HERE, in one round trip, and the LDS tile is cleared under it; the first wait is the
+    //      skipped-batch test in front of the barrier.  (In series -- state, then counters, then clear -- they were 2.6 us in front of the first sample.)
+    const uint32_t iter = st->iter, n_valid = st->n_valid;
     // run lengths of the compacted ray bins, lane b of every wave holds bin b's and bin (b + 64)'s (read back with v_readlane: no memory access in the sample
     // loop)
     const uint32_t bin_cap = B / n_bins, lb = threadIdx.x & 63u;
@@ -341,9 +327,19 @@ __global__ void __launch_bounds__(1024) k_grid_scatter(LevelFast lt, ScatterLeve
     const uint32_t c_lo0 = (lb < n_bins) ? st->n_scatter[scatter_counter(0u, lb)] : 0u, c_lo1 = (lb < n_bins) ? st->n_scatter[scatter_counter(1u, lb)] : 0u;
     const uint32_t c_hi0 = (lb + 64u < n_bins) ? st->n_scatter[scatter_counter(0u, lb + 64u)] : 0u, c_hi1 = (lb + 64u < n_bins)
             ? st->n_scatter[scatter_counter(1u, lb + 64u)] : 0u;
-    const uint32_t cnt_lo = min((iter & 1u) ? c_lo1 : c_lo0, bin_cap), cnt_hi = min((iter & 1u) ? c_hi1 : c_hi0, bin_cap);
+    float4_t pacc[kPartialsMaxPasses];
+    bool pacc_loaded = false;
+    int* tab = reinterpret_cast<int*>(smem);
+    // scatter_item addresses the hashed levels' tiles from LDS offset 0
+    if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem != 0u) __builtin_trap();
+    float* red = reinterpret_cast<float*>(smem + (size_t)kScatterLdsBytes - 256u);     // 256 B behind the largest tile
+    // (the tile plan: argument segment only)
     const uint32_t slot = blockIdx.x / kScatterWgPerLevel, j = blockIdx.x - slot * kScatterWgPerLevel;
-    const int level = sl.level[slot]; const uint32_t P = sl.P[level];
+    // (the byte tables of the plan read as aligned words: scalar loads of the argument segment; byte-indexed they became two dependent VECTOR loads, each
+    // waited for with vmcnt(0) -- in front of the clear and behind the counter loads above)
+    const auto plan_byte = [](const uint8_t* tab8, uint32_t i) -> uint32_t {
+        uint32_t w; __builtin_memcpy(&w, __builtin_assume_aligned(tab8 + (i & ~3u), 4), 4); return (w >> (8u * (i & 3u))) & 0xffu; };
+    const int level = (int)plan_byte(sl.level, slot); const uint32_t P = plan_byte(sl.P, (uint32_t)level);
     const uint32_t part = j / P, p = j - part * P;
     const uint32_t off = lt.offset[level], size = lt.size[level], my = lt.my[level], mz = lt.mz[level], mask = lt.mask[level];
     const bool hashed = lt.hashed[level] != 0u, pow2 = mask != 0xffffffffu;
@@ -355,16 +351,31 @@ __global__ void __launch_bounds__(1024) k_grid_scatter(LevelFast lt, ScatterLeve
     const uint32_t half_size = size >> 1, base_half = mode == kTileParityRanged ? (part >> 2) * kScatterTile : 0u;
     // the index ignores y and z (tcnn's stride wrap-around at res = 65 536): the four pairs of a sample are one entry
     const bool degenerate = pow2 && (my & mask) == 0u && (mz & mask) == 0u && size > 1u;
-    MON_ST_STAMP();
     // (levels whose part count does not divide 16 leave workgroups without a tile)
-    if (mode != kTileParityRanged || base_half < half_size) {
-        const uint32_t tile = mode == kTileWhole64 ? size : min(mode == kTileParity64 ? kScatterTile64 : kScatterTile, half_size - base_half);      // entries
-        typedef int int4v __attribute__((ext_vector_type(4)));
-        {   // tiles are multiples of 4 entries (tcnn rounds level sizes up to 8): clear with 16-byte stores
-            int4v* t4 = reinterpret_cast<int4v*>(tab); const uint32_t n16 = both ? tile / 2u : tile / 4u;
-            for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) t4[i] = int4v{ 0, 0, 0, 0 };
-        }
-        MON_ST_STAMP();
+    const bool has_tile = mode != kTileParityRanged || base_half < half_size;
+    const uint32_t tile = !has_tile ? 0u
+        : (mode == kTileWhole64 ? size : min(mode == kTileParity64 ? kScatterTile64 : kScatterTile, half_size - base_half));      // entries
+    typedef int int4v __attribute__((ext_vector_type(4)));
+    MON_ST_STAMP_NOWAIT();
+    {   // tiles are multiples of 4 entries (tcnn rounds level sizes up to 8): clear with 16-byte stores (a skipped batch clears a tile it does not use)
+        int4v* t4 = reinterpret_cast<int4v*>(tab); const uint32_t n16 = both ? tile / 2u : tile / 4u;
+        for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) t4[i] = int4v{ 0, 0, 0, 0 };
+    }
+    MON_ST_STAMP_NOWAIT();
+    // (the last workgroup: the first ones hold the coarse dense levels, the kernel's critical path)
+    if (blockIdx.x == MON_HOUSEKEEPING_BLOCK && threadIdx.x < 64u) {
+        // slot-counter housekeeping (also for a skipped batch): clear the counters k_fused_train of the NEXT iteration counts in -- they live in the other
+        // DevState, which nobody reads during this iteration -- and note how many samples carried a gradient in this one (k_optimizer hands it to the next
+        // iteration as n_scatter_last; the large-table path decides on it)
+        uint32_t v = 0u;
+        for (uint32_t b = threadIdx.x; b < n_bins; b += 64u) { v += st->n_scatter[scatter_counter(iter, b)];
+            st_next->n_scatter[scatter_counter(iter + 1u, b)] = 0u; }
+        v = scan_add64_u32(v);
+        if (threadIdx.x == 63u) st_rw->n_scatter_now = v;
+    }
+    if (n_valid == 0u) return;
+    const uint32_t cnt_lo = min((iter & 1u) ? c_lo1 : c_lo0, bin_cap), cnt_hi = min((iter & 1u) ? c_hi1 : c_hi0, bin_cap);
+    if (has_tile) {
         __syncthreads();
         MON_ST_STAMP();
         // sample partition p of this level = the ray bins b = p, p + P, ... (16 bins, compacted by k_fused_train: only samples with a non-zero gradient)
@@ -399,10 +410,10 @@ __global__ void __launch_bounds__(1024) k_grid_scatter(LevelFast lt, ScatterLeve
                 const int4v a = t4[2u * i], c = t4[2u * i + 1u];                        // entries 4i, 4i+1 | 4i+2, 4i+3
                 float e0f0, e0f1, e1f0, e1f1, e2f0, e2f1, e3f0, e3f1; lo_hi(a[0], a[1], e0f0, e0f1); lo_hi(a[2], a[3], e1f0, e1f1);
                 lo_hi(c[0], c[1], e2f0, e2f1); lo_hi(c[2], c[3], e3f0, e3f1);
-                *reinterpret_cast<half2_t*>(pl + 0u * plane + 2u * i) = half2_t{ (half_t)e0f0, (half_t)e2f0 };      // feature 0, even entries
-                *reinterpret_cast<half2_t*>(pl + 1u * plane + 2u * i) = half2_t{ (half_t)e1f0, (half_t)e3f0 };      // feature 0, odd
-                *reinterpret_cast<half2_t*>(pl + 2u * plane + 2u * i) = half2_t{ (half_t)e0f1, (half_t)e2f1 };      // feature 1, even
-                *reinterpret_cast<half2_t*>(pl + 3u * plane + 2u * i) = half2_t{ (half_t)e1f1, (half_t)e3f1 };      // feature 1, odd
+                policy_store<MON_SP_GPART>(half2_t{ (half_t)e0f0, (half_t)e2f0 }, reinterpret_cast<half2_t*>(pl + 0u * plane + 2u * i));      // feature 0, even entries
+                policy_store<MON_SP_GPART>(half2_t{ (half_t)e1f0, (half_t)e3f0 }, reinterpret_cast<half2_t*>(pl + 1u * plane + 2u * i));      // feature 0, odd
+                policy_store<MON_SP_GPART>(half2_t{ (half_t)e0f1, (half_t)e2f1 }, reinterpret_cast<half2_t*>(pl + 2u * plane + 2u * i));      // feature 1, even
+                policy_store<MON_SP_GPART>(half2_t{ (half_t)e1f1, (half_t)e3f1 }, reinterpret_cast<half2_t*>(pl + 3u * plane + 2u * i));      // feature 1, odd
             }
         // one parity, both features: 4 entries (32 B) per thread and pass -> 4 halves into each of the two feature planes
         } else if (mode == kTileParity64) {
@@ -410,8 +421,8 @@ __global__ void __launch_bounds__(1024) k_grid_scatter(LevelFast lt, ScatterLeve
                 const int4v a = t4[2u * i], c = t4[2u * i + 1u];
                 float f0[4], f1[4]; lo_hi(a[0], a[1], f0[0], f1[0]); lo_hi(a[2], a[3], f0[1], f1[1]); lo_hi(c[0], c[1], f0[2], f1[2]);
                 lo_hi(c[2], c[3], f0[3], f1[3]);
-                *reinterpret_cast<half4_t*>(pl + (0u + parity) * plane + 4u * i) = half4_t{ (half_t)f0[0], (half_t)f0[1], (half_t)f0[2], (half_t)f0[3] };
-                *reinterpret_cast<half4_t*>(pl + (2u + parity) * plane + 4u * i) = half4_t{ (half_t)f1[0], (half_t)f1[1], (half_t)f1[2], (half_t)f1[3] };
+                policy_store<MON_SP_GPART>(half4_t{ (half_t)f0[0], (half_t)f0[1], (half_t)f0[2], (half_t)f0[3] }, reinterpret_cast<half4_t*>(pl + (0u + parity) * plane + 4u * i));
+                policy_store<MON_SP_GPART>(half4_t{ (half_t)f1[0], (half_t)f1[1], (half_t)f1[2], (half_t)f1[3] }, reinterpret_cast<half4_t*>(pl + (2u + parity) * plane + 4u * i));
             }
         } else {                               // int32 tile of one feature and parity: 8 entries per thread and pass, one 16-byte store of eight halves
             half_t* dst = pl + (feature * 2u + parity) * plane + base_half;
@@ -420,12 +431,12 @@ __global__ void __launch_bounds__(1024) k_grid_scatter(LevelFast lt, ScatterLeve
                 half8_t o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { o[e] = (half_t)((float)a0[e] * inv); o[4 + e] = (half_t)((float)a1[e] * inv); }
-                *reinterpret_cast<half8_t*>(dst + 8u * i) = o;
+                policy_store<MON_SP_GPART>(o, reinterpret_cast<half8_t*>(dst + 8u * i));
             }
             if ((tile & 4u) && threadIdx.x == 0u) {                                    // a parity half is a multiple of 4 entries, not always of 8
                 const int4v a0 = t4[tile / 4u - 1u];
-                *reinterpret_cast<half4_t*>(dst + (tile & ~7u)) = half4_t{ (half_t)((float)a0[0] * inv), (half_t)((float)a0[1] * inv),
-                        (half_t)((float)a0[2] * inv), (half_t)((float)a0[3] * inv) };
+                policy_store<MON_SP_GPART>(half4_t{ (half_t)((float)a0[0] * inv), (half_t)((float)a0[1] * inv), (half_t)((float)a0[2] * inv),
+                        (half_t)((float)a0[3] * inv) }, reinterpret_cast<half4_t*>(dst + (tile & ~7u)));
             }
         }
     }
