@@ -9,6 +9,7 @@ import pytest
 import __graft_entry__ as ge
 from conftest import C1, C2
 from parity import CFGS, SCENE, close_f32, close_half, grid_probe_indices, h2f, load_golden, pattern_params, psnr
+from stage_reference import ulp16 as _ulp16          # fp16 spacing at |x|, the subnormal spacing 2^-24 below 2^-14
 
 pytestmark = pytest.mark.gpu
 
@@ -801,11 +802,6 @@ LARGE = {"T19": dict(rays_per_batch=256, log2_hashmap_size=19, n_neurons=64, n_h
          "T20L8": dict(rays_per_batch=256, log2_hashmap_size=20, n_levels=8, per_level_scale=2.0, n_neurons=32, n_hidden_layers=2)}
 
 
-def _ulp16(x):
-    """fp16 ulp at |x| (normal range; the subnormal ulp 2^-24 below 2^-14)."""
-    return np.maximum(2.0 ** (np.floor(np.log2(np.maximum(np.abs(x), 2.0 ** -14))) - 10), 2.0 ** -24)
-
-
 @pytest.mark.parametrize("name", sorted(LARGE))
 def test_large_table_optimizer_matches_oracle(pkg, orc, small_scene, name):
     """Tables above 8 M parameters (BASELINE configs[4]'s regime) run k_optimizer<false, true>: untouched chunks are skipped altogether (lazy EMA, closed-form
@@ -915,6 +911,74 @@ def test_large_table_optimizer_follows_the_oracle_over_30_steps_on_its_own_gradi
     err = np.abs(ea - eb); tol = 2.0 ** -9 * (np.abs(eb) + np.abs(w)) + 3 * 2.0 ** -24
     assert (err > tol).mean() < 1e-3 and err.max() < 1e-3, (float((err > tol).mean()), float(err.max()))
     assert np.array_equal(h2f(obj.get_params(2)), ea)                 # reading the inference weights again changes nothing
+    obj.close(); ds.close(); ref.close()
+
+
+@pytest.mark.parametrize("chain", ["b0", "gather", "tiles"])
+def test_base_size_optimizer_follows_the_oracle_over_30_steps_on_its_own_gradients(pkg, orc, small_scene, chain):
+    """The base-size k_optimizer -- the kernel the benchmark times; otherwise compared with the oracle after one and three whole steps only, where Adam's
+    first steps are +-lr whatever the gradient -- judged like the large-table one above: every step the device's own gradients (gmlp, ggrid_f32) are handed
+    to the oracle's Trainer::optimizer_step, and master weights, both moments, the step counters and the fp16 copy are compared after 1, 2, 5 and 30 steps
+    with the same bars.  c2s on backend 0, the gather chain and the level-tile chain of backend 1.  After each checkpoint the optimizer's other outputs too:
+    half == h(master), the tile image == the fp16 grid in tile order (level-tile chain), the MFMA fragment image == one rebuilt from the weights (backend 1).
+    Then 30 further steps from parameters trained 150 steps on the device, on a fresh pair (set_params keeps the Adam state on both sides, so it is a fresh
+    object and a fresh oracle that start from empty moments -- checked): the same bars at gradients of the trained regime, mostly exact zeros."""
+    _need_gpu(pkg)
+    kw = dict(CFGS["c2s"])
+    def pair():
+        old = pkg.get_option("lds_encode")
+        try:
+            if chain == "tiles":
+                pkg.set_option("lds_encode", 2)
+            ds, obj = ge.make_problem(pkg, small_scene, kw)
+        finally:
+            pkg.set_option("lds_encode", old)                              # (read when the object is created)
+        obj.set_backend(0 if chain == "b0" else 1)
+        return ds, obj, ge.make_oracle(orc, small_scene, kw)
+    def follow(obj, ref, what):
+        nm = ref.n_mlp; ever = np.zeros(ref.n_params, bool); per_step = []
+        for name in ("m1", "m2", "steps"):
+            assert not obj.buffer(name).any() and not ref.buffer(name).any(), (what, name, "a fresh pair starts from empty Adam state")
+        for t in range(1, 31):
+            obj.train_stages(1 | 2)
+            gm = obj.buffer("gmlp"); gg = obj.buffer("ggrid_f32")
+            obj.train_stages(4); ref.optimizer_step_with(gm, gg)
+            ever[nm:] |= gg != 0; per_step.append(float((gg != 0).mean()))
+            if t in (1, 2, 5, 30):
+                a, b = obj.buffer("master"), ref.buffer("master")
+                assert np.array_equal(obj.buffer("steps"), ref.buffer("steps")), "%s: per-parameter step counters after %d steps" % (what, t)
+                d = np.abs(a - b); assert d.max() <= 5e-6 and float((d > 1e-6).mean()) < 1e-4, (what, t, float(d.max()))
+                for name, rel in (("m1", 1e-5), ("m2", 1e-5)):
+                    x, y = obj.buffer(name), ref.buffer(name)
+                    e = np.abs(x - y); assert float((e > rel * np.abs(y)).mean()) < 1e-5 and e.max() <= 1e-6 * np.abs(y).max(), (what, t, name, float(e.max()))
+                ha, hb = h2f(obj.get_params(1)), h2f(ref.buffer("half"))
+                assert float((ha != hb).mean()) < 1e-3 and (np.abs(ha - hb) <= _ulp16(hb)).all(), (what, t)
+                with np.errstate(over="ignore"):
+                    assert np.array_equal(ha, a.astype(np.float16).astype(np.float32)), "%s: fp16 copy == h(master) after %d steps" % (what, t)
+                if chain == "tiles":
+                    half = obj.buffer("half")[nm:].reshape(-1, 2); tiles = obj.buffer("half_tiles").reshape(-1, 2); off = 0
+                    for size in _level_sizes(obj.cfg):
+                        lv = half[off:off + size]
+                        want = lv if size <= 163840 // 4 else np.concatenate([lv[0::2], lv[1::2]])
+                        assert np.array_equal(tiles[off:off + size], want), "%s: tile image of the level at entry offset %d after %d steps" % (what, off, t)
+                        off += size
+                if chain != "b0":
+                    assert np.array_equal(obj.buffer("frag_train"), obj.buffer("frag_ref")), "%s: fragment image after %d steps" % (what, t)
+        st = ref.buffer("steps")
+        assert (st[:nm] == 30).all() and np.array_equal(st > 0, ever | (np.arange(st.size) < nm))       # exactly the entries that ever had a gradient
+        ea, eb = h2f(obj.get_params(2)), h2f(ref.buffer("ema")); w = h2f(ref.buffer("half"))
+        err = np.abs(ea - eb); tol = 2.0 ** -9 * (np.abs(eb) + np.abs(w)) + 3 * 2.0 ** -24
+        assert (err > tol).mean() < 1e-3 and err.max() < 1e-3, (what, float((err > tol).mean()), float(err.max()))
+        return per_step
+    ds, obj, ref = pair()
+    ref.set_params(obj.get_params(0))                                  # the same initial weights, taken from the device
+    dense = follow(obj, ref, "from the initial weights")
+    obj.close(); ds.close(); ref.close()
+    ds, obj = ge.make_problem(pkg, small_scene, kw); obj.train(150); p = obj.get_params(0); obj.close(); ds.close()
+    ds, obj, ref = pair()
+    obj.set_params(p); ref.set_params(p)
+    sparse = follow(obj, ref, "from trained weights")
+    assert np.mean(sparse) < np.mean(dense), (dense[:3], sparse[:3])   # the trained regime: fewer grid entries see a gradient than from the start
     obj.close(); ds.close(); ref.close()
 
 

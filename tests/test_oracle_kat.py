@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import C1
+from stage_reference import numpy_corners as _numpy_corners          # tcnn's grid walk re-derived in NumPy (shared with the stage references)
 
 
 def _p(a):
@@ -94,38 +95,6 @@ def numpy_occ_live(bits, x):
     c = np.clip(np.trunc(np.asarray(x, np.float32).reshape(-1, 3) * np.float32(64)), 0, 63).astype(np.int64)
     cell = (c[:, 2] * 64 + c[:, 1]) * 64 + c[:, 0]
     return ((np.asarray(bits, np.uint32)[cell >> 5] >> (cell & 31).astype(np.uint32)) & 1).astype(np.uint8)
-
-
-def _numpy_corners(cfg, x):
-    """tcnn's grid walk re-derived in NumPy, independent of the oracle's level_corners: yields (level, corner k, global entry index [n], weight [n] fp64)
-    for positions x [n, 3] -- fractional position from the kernel's fp32 `scale * x + 0.5`, everything after that in fp64 / exact integers."""
-    L = cfg.n_levels
-    off = np.zeros(17, np.uint32); sc = np.zeros(16, np.float32); res = np.zeros(16, np.uint32)
-    from oracle_binding import lib
-    lib().orc_level_table(C.byref(cfg), _p(off), _p(sc), _p(res))
-    for l in range(L):
-        size = int(off[l + 1] - off[l]); r = int(res[l])
-        pos = np.float32(sc[l]) * x.astype(np.float32) + np.float32(0.5)        # fp32 like the kernel; fmaf vs mul+add differ < 1 ulp
-        pos = pos.astype(np.float64)
-        g = np.floor(pos); fr = pos - g; g = g.astype(np.int64)
-        for k in range(8):
-            w = np.ones(x.shape[0]); q = []
-            for d in range(3):
-                if k & (1 << d):
-                    w = w * fr[:, d]; q.append(g[:, d] + 1)
-                else:
-                    w = w * (1 - fr[:, d]); q.append(g[:, d])
-            qx, qy, qz = (np.asarray(v, np.uint64) & 0xffffffff for v in q)
-            # tcnn grid_index: linear index while the running stride (uint32) fits the table, otherwise the prime hash
-            stride, dense = 1, np.zeros(x.shape[0], np.uint64)
-            for coord in (qx, qy, qz):
-                if stride <= size:
-                    dense = (dense + coord * stride) & 0xffffffff; stride = (stride * r) & 0xffffffff
-            if size < stride:
-                idx = ((qx ^ (qy * 2654435761 & 0xffffffff) ^ (qz * 805459861 & 0xffffffff)) & 0xffffffff) % size
-            else:
-                idx = dense % size
-            yield l, k, idx.astype(np.int64) + int(off[l]), w
 
 
 def _numpy_encode(cfg, table_f64, x):
