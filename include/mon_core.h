@@ -268,6 +268,50 @@ int mon_object_pose_loss_levels(mon_object* obj, int side, const mon_frame_bbox*
 /* mon_object_refine_pose with the schedule: step i uses mon_pose_c2f_weights(c, L, p->iters, i).  Still enqueued at once, one synchronisation. */
 int mon_object_refine_pose_c2f(mon_object* obj, int side, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p,
                                const mon_pose_c2f_params* c, float* Tow16_inout, float* loss_trace);
+/* Camera pose refinement against a scene of object NeRFs (the reference has no such call; opt-in, new): given a frame of the dataset and a
+ * predicted camera pose, follow the gradient of one photometric, silhouette and depth error of everything the object map holds with respect to Twc.
+ * Inputs.  objs[0..K): objects of one logical device and one dataset (equal intrinsics), fused shapes only, K <= 256; each uses its own Tow and box.  obs:
+ * boxes that all name the same FrameId.  A candidate camera pose Twc16 (column-major, camera -> world).  Targets of pixel (x, y) of that frame: colour c*,
+ * instance id i*, depth d* (0 without depth); m*_j = [i* == class_id_j], M* = max_j m*_j.
+ * Rays.  Pixels are drawn exactly as mon_object_pose_loss draws them (the union of the boxes, box order then row-major, stream 5 keyed (seed, iteration, ray),
+ * the 24- / 32-bit rule; rays_per_iter = 0 takes every pixel).  The world ray is the one mon_object_render builds for that pixel under the candidate Twc.  Per
+ * object j: the ray in j's frame under its Tow, its intersection with j's box, and 2S = 64 jittered distances t_{j,k} in [max(t0_j, 0), t1_j] --
+ * rays_per_iter = 0: object j's own render jitter (sample_seed_j, stream 3, index q * 64 + k, q the pixel inside its box), so that at the dataset's own Twc
+ * each object's t, alpha and colour for a box are those of mon_debug_scene_samples for that box as rect; rays_per_iter > 0: stream 4 keyed (seed, iteration,
+ * ray * 64 + k), the same draw for every object.  Alpha and colour are the render's (sigma = exp(o3), c = logistic(o0..2), alpha = 1 - exp(-sigma dt), the
+ * first interval from 0).  Each object evaluates its second 32-sample tile only if its own transmittance after the first is >= 1e-4.  Render skipping does not
+ * apply.
+ * Composite (mon_scene_render's).  All evaluated samples of the ray are merged by t; ties go to the lower index in objs, then the lower slot.  T_0 = 1,
+ * w_i = alpha_i T_i, T_{i+1} = T_i (1 - alpha_i); the first merged sample with T_i < 1e-4 and everything behind it get weight 0.
+ * Loss.  r = sum_i w_i (c_i - c*); W_j = sum_{i in j} w_i; D = sum_i w_i t_i / |camera ray|;
+ *   l = w_rgb M* |r|^2 / 3 + w_mask sum_{j < K} (W_j - m*_j)^2 + w_depth M* [d* > 0] Huber(D - d*)
+ *   L = mean of l over the drawn pixels (an object the ray misses has W_j = 0 and still counts in the mask sum).
+ * With K = 1 this is mon_object_pose_loss's l term for term (W_0 = O, M* = m*).
+ * Gradient.  grad6 = dL/dxi at xi = 0 for Twc(xi) = Twc exp(xi^) -- a camera-frame (right) perturbation, xi = (rho, phi), translation first.  A sample's
+ * camera-frame position x_c = t (unit camera ray) is rigid; its object-frame position is x_o = Toc_j exp(xi^) x_c with Toc_j = Tow_j Twc.  Held at their
+ * values at xi = 0: every t and dt, each box intersection, the merge order, both cuts and each sample's hash-grid corners; only the trilinear weights are
+ * differentiated (mon_object_pose_loss's rule).  dL/drho = sum g_c, dL/dphi = sum x_c x g_c with g_c = R_oc,j^T g_o and g_o = dL/dx_o of the sample;
+ * computed per object as G_j = (sum g_o, sum x_o x g_o) in the object frame and mapped with Toc_j = (R, p): grad_rho = sum_j R^T G_j,rho,
+ * grad_phi = sum_j R^T (G_j,phi - p x G_j,rho), the sum over j in index order.  Composite backward in merged order, with
+ * q_i = G_rgb . (c_i - c*) + G_D t_i + 2 w_mask (W_j(i) - m*_j(i)): dL/dsigma_i = dt_i (T_{i+1} q_i - sum_{n > i} w_n q_n), dL/dc_i = w_i G_rgb; there is no
+ * separate T_end term (opacity enters only through the W_j).
+ * Level weights (mon_object_pose_loss_levels's, by level index): object j uses level_weights[0..L_j); NULL = every weight 1.  Weights of 1 give the
+ * unweighted result bit for bit, weights of 0 give grad6 = 0 exactly; the loss does not depend on them.
+ * Refinement.  Adam (0.9, 0.999, 1e-8) on the twist, lr_trans / lr_rot; each step Twc <- Twc exp(delta^) in closed form, the rotation re-orthonormalised
+ * (Gram-Schmidt).  Step i evaluates with iteration = i; loss_trace[i] (iters + 1 values, may be NULL) is the loss before step i, loss_trace[iters] the loss
+ * at the end.  With a schedule c, step i uses mon_pose_c2f_weights(c, Lmax, iters, i), Lmax the largest n_levels in objs; c = NULL: plain.  The whole
+ * refinement is enqueued at once (the pose lives on the device between steps), one synchronisation.  No atomics: equal arguments give equal bits.
+ * Read-only.  Nothing about any object, the dataset or a manager changes (parameters, training state, RNG counters, render-skip caches and statistics,
+ * snapshots, the objects' pose scratch, the dataset's stored pose): the pose goes back to the caller only, who calls mon_online_update_dataset to store it.
+ * side as in mon_scene_render: 0 the train-side weights on the first object's train stream (the caller serialises against training), 1 the pinned snapshots
+ * on the device's inference stream (callable while the objects train).
+ * Returns MON_ERR_ARG, before any device work, for everything mon_object_pose_loss / mon_object_refine_pose / mon_object_refine_pose_c2f reject, n_objs 0 or
+ * above 256, a NULL element of objs, boxes naming different FrameIds, objects on different logical devices, with different intrinsics or on different
+ * datasets; MON_ERR_STATE for an object outside the fused shapes, the XORWOW render mode, and side 1 with nothing published. */
+int mon_scene_pose_loss(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16,
+                        const mon_pose_refine_params* p, uint32_t iteration, const float* level_weights /* NULL or Lmax */, float* loss, float* grad6);
+int mon_scene_refine_camera(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p,
+                            const mon_pose_c2f_params* c /* NULL: plain */, float* Twc16_inout, float* loss_trace);
 /* NeRF_Model::GetDensityOnGrid (nerf_model.cu:2007-2048): raw density channel on an rx*ry*rz lattice. */
 int mon_object_density_grid(mon_object* obj, int rx, int ry, int rz, float* out_host);
 
@@ -376,6 +420,11 @@ int mon_online_refine_pose(mon_online* mgr, size_t idx, const mon_frame_bbox* ob
 /* mon_object_refine_pose_c2f(side 1) of object idx, as mon_online_refine_pose */
 int mon_online_refine_pose_c2f(mon_online* mgr, size_t idx, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p,
                                const mon_pose_c2f_params* c, float* Tow16_inout, float* loss_trace);
+/* mon_scene_refine_camera(side 1) over every object of the manager that has published weights: a frontend's call for a new frame (mon_online_new_frame ->
+ * mon_online_refine_camera -> mon_online_update_dataset), safe while the objects train.  MON_ERR_STATE when no object has published yet or when those
+ * objects span more than one device (as mon_online_render_scene). */
+int mon_online_refine_camera(mon_online* mgr, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, const mon_pose_c2f_params* c,
+                             float* Twc16_inout, float* loss_trace);
 /* RenderNeRFsTest(out_path, idx, stamps, boxes, Twcs, radius) -> NeRF::RenderTestImg (nerf.cu:255-404): test images + test.txt +
  * train.txt + the 60-view 360-degree video (RenderVideo, nerf_model.cu:1832-1990) + obj.ply under <out_path>/<id>/ */
 int mon_online_render_nerfs_test(mon_online* mgr, const char* out_path, size_t idx, const char* const* timestamps, const mon_frame_bbox* boxes,

@@ -68,6 +68,20 @@ int mon_debug_scene_composite(int device, uint32_t n_rays, uint32_t n_lists, con
 int mon_debug_pose_samples(mon_object* obj, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params* p,
                            uint32_t iteration, float* x, float* raw, float* dldx);
 
+/* Camera refinement against a scene (mon_scene_pose_loss, the same arguments first).  mon_debug_scene_pose_samples: object k's share of that evaluation, per
+ * drawn ray: x_o[ray][64][3] the sample positions in k's frame, x_c[ray][64][3] in the camera frame (t x the unit camera ray), t[ray][64], raw[ray][64][4] the
+ * network's raw outputs, dldx[ray][64][3] = dL/dx_o (object frame, the 1/N of the mean included) and count[ray] (0: the ray missed k's box; else 32 per
+ * evaluated tile).  Samples not evaluated hold raw = dldx = 0 (and x = t = 0 for a miss).  Any output may be NULL.
+ * mon_debug_scene_composite_grad: the merged composite's forward and backward (k_scene_composite_grad) on caller lists laid out as mon_debug_scene_composite's,
+ * plus per-ray targets cstar[n_rays][3], mstar[n_lists][n_rays], dstar[n_rays], dn[n_rays] and the loss weights.  Outputs: l[n_rays], W[n_lists][n_rays],
+ * D[n_rays], dalpha[n_lists][n_rays][64] = dL/dalpha and dc[n_lists][n_rays][64][3] = dL/dc of every sample (0 for slots not merged or behind the cut). */
+int mon_debug_scene_pose_samples(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16,
+                                 const mon_pose_refine_params* p, uint32_t iteration, const float* level_weights, size_t k, float* x_o, float* x_c, float* t,
+                                 float* raw, float* dldx, uint32_t* count);
+int mon_debug_scene_composite_grad(int device, uint32_t n_rays, uint32_t n_lists, const float* t, const float* alpha, const float* rgb, const uint32_t* count,
+                                   const float* cstar, const float* mstar, const float* dstar, const float* dn, float w_rgb, float w_mask, float w_depth,
+                                   float huber, float* out_l, float* out_W, float* out_D, float* out_dalpha, float* out_dc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,12 @@ _SIGS = {
             C.c_void_p, C.c_void_p]),
     "mon_online_refine_pose_c2f": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams), C.POINTER(PoseC2FParams),
             C.c_void_p, C.c_void_p]),
+    "mon_scene_pose_loss": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32,
+            C.c_void_p, C.POINTER(C.c_float), C.c_void_p]),
+    "mon_scene_refine_camera": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams), C.POINTER(PoseC2FParams),
+            C.c_void_p, C.c_void_p]),
+    "mon_online_refine_camera": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams), C.POINTER(PoseC2FParams), C.c_void_p,
+            C.c_void_p]),
 }
 
 
@@ -177,6 +183,10 @@ _DIAG_SIGS = {
             C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_debug_pose_samples": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32, C.c_void_p,
             C.c_void_p, C.c_void_p]),
+    "mon_debug_scene_pose_samples": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32,
+            C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_debug_scene_composite_grad": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -797,6 +807,15 @@ class OnlineManager:
         _check(lib().mon_online_refine_pose_c2f(self.h, int(idx), _p(b), b.shape[0], C.byref(prm), C.byref(c), _p(pose), _p(trace)))
         return pose, trace
 
+    def refine_camera(self, obs, Twc16, params=None, c2f=None):
+        """mon_online_refine_camera: the camera pose of one frame refined against every object with published weights, safe while they train; c2f as
+        scene_refine_camera's.  Returns (refined Twc16, loss trace); the manager is not changed (update_dataset stores a pose)."""
+        b, prm = _pose_boxes(obs), _pose_params(params); pose = np.array(Twc16, np.float32).reshape(16)
+        c = None if c2f is None else _c2f_params(None if c2f is True else c2f)
+        trace = np.empty(prm.iters + 1, np.float32)
+        _check(lib().mon_online_refine_camera(self.h, _p(b), b.shape[0], C.byref(prm), None if c is None else C.byref(c), _p(pose), _p(trace)))
+        return pose, trace
+
     def close(self):
         if self.h:
             lib().mon_online_destroy(self.h); self.h = None
@@ -885,6 +904,64 @@ def scene_composite(t, alpha, rgb, count, dn, device=0):
     o_rgb = np.empty((R, 3), np.float32); o_d = np.empty(R, np.float32); o_o = np.empty(R, np.float32); o_i = np.empty(R, np.int32)
     _check(diag_lib().mon_debug_scene_composite(int(device), R, L, _p(t), _p(a), _p(c), _p(n), _p(d), _p(o_rgb), _p(o_d), _p(o_o), _p(o_i)))
     return o_rgb, o_d, o_o, o_i
+
+
+def _scene_level_weights(objects, level_weights):
+    if level_weights is None:
+        return None
+    w = np.ascontiguousarray(level_weights, np.float32).reshape(-1)
+    if w.size != max(o.cfg.n_levels for o in objects):
+        raise ValueError("level_weights: one weight per level of the finest object")
+    return w
+
+
+def scene_pose_loss(objects, obs, Twc16, params=None, side=0, iteration=0, level_weights=None):
+    """mon_scene_pose_loss: (loss, grad6 = dL/d(rho, phi) of Twc exp(xi^)) of the camera pose Twc16 (column-major) against the boxes obs [(FrameId, x, y, h, w)]
+    of one frame, through all the objects composited in depth order.  level_weights: None, or one weight per level of the finest object."""
+    b, prm = _pose_boxes(obs), _pose_params(params); pose = np.ascontiguousarray(Twc16, np.float32).reshape(16)
+    w = _scene_level_weights(objects, level_weights); loss = C.c_float(0); g = np.empty(6, np.float32)
+    _check(lib().mon_scene_pose_loss(_handles(objects), len(objects), int(side), _p(b), b.shape[0], _p(pose), C.byref(prm), int(iteration), _p(w),
+                                     C.byref(loss), _p(g)))
+    return loss.value, g
+
+
+def scene_refine_camera(objects, obs, Twc16, params=None, c2f=None, side=0):
+    """mon_scene_refine_camera: params.iters Adam steps on the camera pose from Twc16.  c2f: None = plain, True = the default coarse-to-fine schedule, or
+    PoseC2FParams / a dict of overrides.  Returns (refined Twc16, loss trace of iters + 1 values); nothing about the objects changes."""
+    b, prm = _pose_boxes(obs), _pose_params(params); pose = np.array(Twc16, np.float32).reshape(16)
+    c = None if c2f is None else _c2f_params(None if c2f is True else c2f)
+    trace = np.empty(prm.iters + 1, np.float32)
+    _check(lib().mon_scene_refine_camera(_handles(objects), len(objects), int(side), _p(b), b.shape[0], C.byref(prm), None if c is None else C.byref(c),
+                                         _p(pose), _p(trace)))
+    return pose, trace
+
+
+def scene_pose_samples(objects, obs, Twc16, k, params=None, side=0, iteration=0, level_weights=None):
+    """mon_debug_scene_pose_samples: object k's share of that evaluation per drawn ray: dict of x_o (n, 64, 3), x_c (n, 64, 3), t (n, 64), raw (n, 64, 4),
+    dldx (n, 64, 3; object frame, 1/N included) and count (n,)."""
+    b, prm = _pose_boxes(obs), _pose_params(params); pose = np.ascontiguousarray(Twc16, np.float32).reshape(16)
+    n = int(prm.rays_per_iter) or int((b[:, 3].astype(np.int64) * b[:, 4]).sum())
+    w = _scene_level_weights(objects, level_weights)
+    o = dict(x_o=np.empty((n, 64, 3), np.float32), x_c=np.empty((n, 64, 3), np.float32), t=np.empty((n, 64), np.float32), raw=np.empty((n, 64, 4), np.float32),
+             dldx=np.empty((n, 64, 3), np.float32), count=np.empty(n, np.uint32))
+    _check(diag_lib().mon_debug_scene_pose_samples(_handles(objects), len(objects), int(side), _p(b), b.shape[0], _p(pose), C.byref(prm), int(iteration), _p(w),
+                                                   int(k), _p(o["x_o"]), _p(o["x_c"]), _p(o["t"]), _p(o["raw"]), _p(o["dldx"]), _p(o["count"])))
+    return o
+
+
+def scene_composite_grad(t, alpha, rgb, count, cstar, mstar, dstar, dn, w_rgb=1.0, w_mask=1.0, w_depth=1.0, huber=0.05, device=0):
+    """mon_debug_scene_composite_grad: k_scene_composite_grad on lists laid out as scene_composite's, targets cstar (n_rays, 3), mstar (n_lists, n_rays),
+    dstar (n_rays,), dn (n_rays,).  Returns dict of l (n_rays,), W (n_lists, n_rays), D (n_rays,), dalpha (n_lists, n_rays, 64), dc (n_lists, n_rays, 64, 3)."""
+    t = np.ascontiguousarray(t, np.float32); L, R = t.shape[:2]
+    a = np.ascontiguousarray(alpha, np.float32).reshape(L, R, 64); c = np.ascontiguousarray(rgb, np.float32).reshape(L, R, 64, 3)
+    n = np.ascontiguousarray(count, np.uint32).reshape(L, R); d = np.ascontiguousarray(dn, np.float32).reshape(R)
+    cs = np.ascontiguousarray(cstar, np.float32).reshape(R, 3); ms = np.ascontiguousarray(mstar, np.float32).reshape(L, R)
+    dsr = np.ascontiguousarray(dstar, np.float32).reshape(R)
+    o = dict(l=np.empty(R, np.float32), W=np.empty((L, R), np.float32), D=np.empty(R, np.float32), dalpha=np.empty((L, R, 64), np.float32),
+             dc=np.empty((L, R, 64, 3), np.float32))
+    _check(diag_lib().mon_debug_scene_composite_grad(int(device), R, L, _p(t), _p(a), _p(c), _p(n), _p(cs), _p(ms), _p(dsr), _p(d), float(w_rgb), float(w_mask),
+                                                     float(w_depth), float(huber), _p(o["l"]), _p(o["W"]), _p(o["D"]), _p(o["dalpha"]), _p(o["dc"])))
+    return o
 
 
 def _borrowed_object(handle):

@@ -177,6 +177,38 @@ int mon_object_refine_pose(mon_object* o, int side, const mon_frame_bbox* obs, s
     return r2;
 }
 // ---- coarse-to-fine level weights (BARF window over the levels, alpha in levels from level_start to level_end over the first ramp * iters steps)
+// ---- camera refinement against a scene of objects
+static int scene_pose_models(mon_object* const* objs, size_t n_objs, std::vector<Model*>& ms) {
+    REQUIRE(objs, "objs");
+    if (n_objs == 0 || n_objs > kSceneMaxLists) { set_error("scene pose: %zu objects (1 to %u)", n_objs, kSceneMaxLists); return MON_ERR_ARG; }
+    ms.resize(n_objs);
+    for (size_t j = 0; j < n_objs; ++j) { if (!objs[j] || !objs[j]->m) { set_error("scene pose: null object %zu", j); return MON_ERR_ARG; } ms[j] = objs[j]->m; }
+    return MON_OK;
+}
+static int level_weights_check(const float* w, int n) {
+    for (int l = 0; l < n; ++l)
+        if (!std::isfinite(w[l]) || w[l] < 0.f) { set_error("scene pose: level weight %d is %g (finite, >= 0)", l, w[l]); return MON_ERR_ARG; }
+    return MON_OK;
+}
+int mon_scene_pose_loss(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16,
+                        const mon_pose_refine_params* p, uint32_t iteration, const float* level_weights, float* loss, float* grad6) {
+    std::vector<Model*> ms; int rc = scene_pose_models(objs, n_objs, ms); if (rc) return rc;
+    if ((rc = scene_pose_check(ms.data(), n_objs, side, obs, n_obs, Twc16, p))) return rc;
+    if (level_weights) { int Lmax = 0; for (Model* m : ms) Lmax = std::max(Lmax, (int)m->nd.L); if ((rc = level_weights_check(level_weights, Lmax))) return rc; }
+    return scene_pose(ms.data(), n_objs, side, obs, n_obs, Twc16, *p, -1, iteration, nullptr, nullptr, loss, grad6, nullptr, level_weights);
+}
+int mon_scene_refine_camera(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p,
+                            const mon_pose_c2f_params* c, float* Twc16_inout, float* loss_trace) {
+    std::vector<Model*> ms; int rc = scene_pose_models(objs, n_objs, ms); if (rc) return rc;
+    if ((rc = scene_pose_check(ms.data(), n_objs, side, obs, n_obs, Twc16_inout, p))) return rc;
+    if (c && (rc = pose_c2f_check(c))) return rc;
+    int Lmax = 0; for (Model* m : ms) Lmax = std::max(Lmax, (int)m->nd.L);
+    std::vector<float> table; if (c) table = pose_c2f_table(*c, Lmax, p->iters);
+    float pose[16]; std::memcpy(pose, Twc16_inout, 64);
+    rc = scene_pose(ms.data(), n_objs, side, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr, table.empty() ? nullptr : table.data());
+    if (rc == MON_OK) std::memcpy(Twc16_inout, pose, 64);
+    return rc;
+}
 int mon_pose_c2f_default(mon_pose_c2f_params* c) {
     REQUIRE(c, "params");
     c->level_start = 4.f; c->level_end = 5.f; c->ramp = 0.7f;

@@ -1,5 +1,6 @@
 // diag.cpp -- libmon_core_diag.so: diagnostics and test scaffolding (include/mon_core_diag.h).  Links against libmon_core.so and reads its objects
 // through the internal headers; nothing here is on the product path.
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -262,6 +263,73 @@ int mon_debug_pose_samples(mon_object* o, int side, const mon_frame_bbox* obs, s
     if (n_obs == 0) { set_error("debug_pose_samples: no boxes"); return MON_ERR_ARG; }
     const mon::PoseDump dump{ x, raw, dldx };
     return mon::pose_refine(*o->m, side, obs, n_obs, Tow16, *p, -1, iteration, nullptr, nullptr, nullptr, nullptr, &dump);
+}
+int mon_debug_scene_pose_samples(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16,
+                                 const mon_pose_refine_params* p, uint32_t iteration, const float* level_weights, size_t k, float* x_o, float* x_c, float* t,
+                                 float* raw, float* dldx, uint32_t* count) {
+    REQUIRE(objs, "objs"); REQUIRE(obs, "obs"); REQUIRE(Twc16, "Twc16"); REQUIRE(p, "params");
+    if (n_objs == 0 || n_objs > mon::kSceneMaxLists || k >= n_objs) { set_error("debug_scene_pose_samples: empty list or k out of range"); return MON_ERR_ARG; }
+    std::vector<mon::Model*> ms(n_objs);
+    for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
+    const mon::ScenePoseDump dump{ (uint32_t)k, x_o, x_c, t, raw, dldx, count };
+    return mon::scene_pose(ms.data(), n_objs, side, obs, n_obs, Twc16, *p, -1, iteration, nullptr, nullptr, nullptr, nullptr, &dump, level_weights);
+}
+int mon_debug_scene_composite_grad(int device, uint32_t n_rays, uint32_t n_lists, const float* t, const float* alpha, const float* rgb, const uint32_t* count,
+                                   const float* cstar, const float* mstar, const float* dstar, const float* dn, float w_rgb, float w_mask, float w_depth,
+                                   float huber, float* out_l, float* out_W, float* out_D, float* out_dalpha, float* out_dc) {
+    REQUIRE(t, "t"); REQUIRE(alpha, "alpha"); REQUIRE(rgb, "rgb"); REQUIRE(count, "count"); REQUIRE(cstar, "cstar"); REQUIRE(mstar, "mstar");
+    REQUIRE(dstar, "dstar"); REQUIRE(dn, "dn"); REQUIRE(out_l, "out_l"); REQUIRE(out_W, "out_W"); REQUIRE(out_D, "out_D"); REQUIRE(out_dalpha, "out_dalpha");
+    REQUIRE(out_dc, "out_dc");
+    if (n_rays == 0 || n_lists == 0 || n_lists > mon::kSceneMaxLists) { set_error("debug_scene_composite_grad: %u rays, %u lists", n_rays, n_lists);
+        return MON_ERR_ARG; }
+    const size_t nl = (size_t)n_lists * n_rays, ns = nl * mon::kSceneListLen;
+    for (size_t i = 0; i < nl; ++i) if (count[i] > mon::kSceneListLen) { set_error("debug_scene_composite_grad: count %u > 64", count[i]); return MON_ERR_ARG; }
+    std::vector<float> attr(4 * ns), ray(12 * (size_t)n_rays, 0.f);
+    for (size_t i = 0; i < ns; ++i) { attr[4 * i] = alpha[i]; attr[4 * i + 1] = rgb[3 * i]; attr[4 * i + 2] = rgb[3 * i + 1]; attr[4 * i + 3] = rgb[3 * i + 2]; }
+    for (size_t r = 0; r < n_rays; ++r) {
+        float M = 0.f; for (uint32_t k = 0; k < n_lists; ++k) M = std::max(M, mstar[(size_t)k * n_rays + r]);
+        float* q = ray.data() + 12 * r; q[0] = cstar[3 * r]; q[1] = cstar[3 * r + 1]; q[2] = cstar[3 * r + 2]; q[3] = dstar[r]; q[4] = dn[r]; q[5] = M;
+    }
+    if (!mon::launch_scene_composite_grad || !mon::scene_comp_grad_grid) { set_error("debug_scene_composite_grad: built without kernels_scene_pose.hip");
+        return MON_ERR_STATE; }
+    HIPCHECK(mon::use_device(device));
+    const uint32_t n_lp = mon::scene_comp_grad_grid(n_rays);
+    const size_t b_t = ns * 4, b_a = ns * 16, b_c = nl * 4, b_m = nl * 4, b_ray = (size_t)n_rays * 48, b_gw = ns * 8, b_grow = (size_t)n_rays * 16,
+                 b_lp = (size_t)n_lp * 4, b_W = nl * 4, b_D = (size_t)n_rays * 4;
+    const size_t sizes[] = { b_a, b_ray, b_grow, b_gw, b_t, b_c, b_m, b_lp, b_W, b_D };                   // (the 16-byte-aligned ones first)
+    size_t off[11] = { 0 }; for (int i = 0; i < 10; ++i) off[i + 1] = off[i] + ((sizes[i] + 15) & ~(size_t)15);
+    char* d = nullptr; HIPCHECK(hipMalloc((void**)&d, off[10]));
+    float* d_a = (float*)(d + off[0]); float* d_ray = (float*)(d + off[1]); float* d_grow = (float*)(d + off[2]); float* d_gw = (float*)(d + off[3]);
+    float* d_t = (float*)(d + off[4]); uint32_t* d_c = (uint32_t*)(d + off[5]); float* d_m = (float*)(d + off[6]); float* d_lp = (float*)(d + off[7]);
+    float* d_W = (float*)(d + off[8]); float* d_D = (float*)(d + off[9]);
+    hipError_t e = hipMemcpy(d_t, t, b_t, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_a, attr.data(), b_a, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_c, count, b_c, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_m, mstar, b_m, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_ray, ray.data(), b_ray, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_gw, 0, b_gw);
+    if (e == hipSuccess) {
+        mon::SceneCompGradArgs a{}; a.n_rays = n_rays; a.n_lists = n_lists; a.cap = n_rays; a.t = d_t; a.attr = reinterpret_cast<const float4*>(d_a); a.cnt = d_c;
+        a.mstar = d_m; a.ray = reinterpret_cast<const float4*>(d_ray); a.w_rgb = w_rgb; a.w_mask = w_mask; a.w_depth = w_depth; a.huber = huber;
+        a.gw = reinterpret_cast<float2*>(d_gw); a.grow = reinterpret_cast<float4*>(d_grow); a.loss_part = d_lp; a.out_W = d_W; a.out_D = d_D;
+        mon::launch_scene_composite_grad(nullptr, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    std::vector<float> gw(2 * ns), grow(4 * (size_t)n_rays);
+    if (e == hipSuccess) e = hipMemcpy(gw.data(), d_gw, b_gw, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(grow.data(), d_grow, b_grow, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_W, d_W, b_W, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_D, d_D, b_D, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIPCHECK(e);
+    for (size_t r = 0; r < n_rays; ++r) out_l[r] = grow[4 * r + 3];
+    for (size_t i = 0; i < ns; ++i) {                                     // dL/dc = w G_rgb, as the objects' backward forms it
+        const size_t r = (i / mon::kSceneListLen) % n_rays;
+        out_dalpha[i] = gw[2 * i];
+        for (int c = 0; c < 3; ++c) out_dc[3 * i + c] = gw[2 * i + 1] * grow[4 * r + c];
+    }
+    return MON_OK;
 }
 int mon_debug_yaml_number(const char* text, const char* key, double* value) {
     REQUIRE(text, "text"); REQUIRE(key, "key"); REQUIRE(value, "value");

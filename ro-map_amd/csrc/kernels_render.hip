@@ -1,6 +1,7 @@
 // kernels_render.hip -- k_fused_render (NeRF_Model::Render: one wavefront per pixel ray, 2 x 32 samples) and the occupancy grid kernels of the opt-in
 // forward-pass skipping; both evaluate the network with the tile_forward of fused_device.h (gathers + MFMA MLP).
 #include "fused_device.h"
+#include "scene_device.h"
 
 namespace mon {
 
@@ -200,46 +201,8 @@ __global__ void __launch_bounds__(64) k_scene_composite(uint32_t n_rays, uint32_
     float* s_w = s_tl + n_lists;                                                       // its summed weight
     const int lane = threadIdx.x;
     for (uint32_t ray = blockIdx.x; ray < n_rays; ray += gridDim.x) {
-        // ---- the ray's non-empty lists, in list order
-        uint32_t na = 0u, n_tot = 0u;
-        for (uint32_t g = 0; g < n_lists; g += 64u) {
-            const uint32_t k = g + (uint32_t)lane;
-            uint32_t c = k < n_lists ? cnt[(size_t)k * cap + ray] : 0u;
-            c = c < L2S ? c : L2S;
-            const unsigned long long b = __ballot(c > 0u);
-            if (c > 0u) {
-                const uint32_t pos = na + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-                const float* q = tl + ((size_t)k * cap + ray) * L2S;
-                s_id[pos] = k; s_c[pos] = c; s_tf[pos] = q[0]; s_tl[pos] = q[c - 1u]; s_w[pos] = 0.f;
-            }
-            na += (uint32_t)__popcll(b);
-            n_tot += (uint32_t)__builtin_amdgcn_readlane((int)scan_add64_u32(c), 63);
-        }
-        __syncthreads();
-        // ---- merged order: rank of every sample
-        for (uint32_t a = 0; a < na; ++a) {
-            const uint32_t c = s_c[a];
-            if ((uint32_t)lane < c) {
-                const float tv = tl[((size_t)s_id[a] * cap + ray) * L2S + lane];
-                uint32_t r = (uint32_t)lane;
-                for (uint32_t b = 0; b < na; ++b) {
-                    if (b == a) continue;
-                    const bool first = b < a;                                          // (list b's samples at an equal t come first)
-                    const uint32_t cb = s_c[b];
-                    const float lb = s_tl[b], fb = s_tf[b];
-                    if (first ? lb <= tv : lb < tv) r += cb;                           // all of list b is in front
-                    else if (first ? fb <= tv : fb < tv) {                             // part of it: count (binary search; the last one is not in front)
-                        const float* q = tl + ((size_t)s_id[b] * cap + ray) * L2S;
-                        uint32_t pos = 0u;
-                        for (uint32_t step = L2S / 2u; step; step >>= 1)
-                            if (pos + step <= cb) { const float v = q[pos + step - 1u]; if (first ? v <= tv : v < tv) pos += step; }
-                        r += pos;
-                    }
-                }
-                s_perm[r] = (uint16_t)((a << 6) | (uint32_t)lane);                     // (r <= n_tot - 1 whatever the lists hold)
-            }
-        }
-        __syncthreads();
+        uint32_t na, n_tot;
+        scene_merge_lists(ray, n_lists, cap, tl, cnt, lane, s_perm, s_id, s_c, s_tf, s_tl, s_w, na, n_tot);
         // ---- front-to-back composite of the merged sequence
         float Tc = 1.f, r0 = 0.f, r1 = 0.f, r2 = 0.f, dep = 0.f;
         for (uint32_t base = 0; base < n_tot; base += 64u) {

@@ -1,0 +1,449 @@
+// kernels_scene_pose.hip -- camera pose refinement against a scene of object NeRFs (mon_scene_pose_loss / mon_scene_refine_camera): the drawn rays under the
+// candidate camera pose in every object's frame, each object's sample lists (forward only), the merged composite with its loss and its backward, each
+// object's MLP backward and hash-grid position gradient from the gradients the composite left in the lists, and the Adam step on the camera twist.
+// The objective is stated in include/mon_core.h and DESIGN.md 3.4f.  No atomics anywhere: every sum runs in a fixed order.
+#include <type_traits>
+#include "pose_device.h"
+#include "scene_device.h"
+
+namespace mon {
+
+// ------------------------------------------------------------------ k_scene_pose_rays
+// One thread per drawn ray of the chunk (global ray i = ray0 + r): the pixel as k_pose_rays draws it, its targets, and for every object j the ray
+// mon_object_render builds for that pixel under the candidate Twc (device memory) and the object's Tow, intersected with the object's box.
+// Per ray (3 x float4): {c*, d*} {|camera ray|, M*, 0, 0} {unit camera ray, 0}.  Per object and ray (3 x float4 at (j * cap + r) * 3): {o, t0} {d, t1}
+// {hit, jitter index base (bits), 0, 0}; m*_j at j * cap + r.
+__global__ void __launch_bounds__(256) k_scene_pose_rays(ScenePoseRayArgs a) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.n_rays) return;
+    const uint32_t i = a.ray0 + r;
+    uint32_t p = i;
+    if (a.drawn) {
+        const uint64_t z = rand_mix(a.seed, kStreamPoseXY, a.iteration, i);
+        p = a.total <= (1u << 24) ? (uint32_t)(((z >> 40) * a.total) >> 24) : (uint32_t)(((z >> 32) * a.total) >> 32);
+    }
+    uint32_t lo = 0u, hi = a.n_obs - 1u;                                                // the box: last b with prefix[b] <= p
+    while (lo < hi) { const uint32_t mid = (lo + hi + 1u) >> 1; if (a.prefix[mid] <= p) lo = mid; else hi = mid - 1u; }
+    const mon_frame_bbox box = a.boxes[lo];
+    const uint32_t q = p - a.prefix[lo], x = box.x + q % box.w, y = box.y + q / box.w;
+    const size_t pix = ((size_t)box.FrameId * a.ds.K.H + y) * a.ds.K.W + x;
+    const uint32_t rgba = a.ds.rgba[pix], inst = rgba >> 24;
+    const float dstar = a.ds.depth ? a.ds.depth[pix] : 0.f;
+    const uint32_t base = a.drawn ? i * 64u : q * 64u;                                  // (2S = 64: the fused shapes)
+    float Twc[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) Twc[k] = a.pose[k];
+    float dn = 1.f, Mstar = 0.f;
+    for (uint32_t j = 0; j < a.n_objs; ++j) {
+        const SceneObjConst& oc = a.objs[j];
+        float o[3], d[3], t0 = 0.f, t1 = 0.f;
+        pixel_ray(a.ds.K, (float)x, (float)y, Twc, oc.Tow, false, o, d, dn);
+        const bool hit = ray_intersect(oc.aabb, o, d, t0, t1);
+        const float m = inst == oc.instance_id ? 1.f : 0.f;
+        Mstar = fmaxf(Mstar, m);
+        float4* rr = a.rec + 3 * ((size_t)j * a.cap + r);
+        rr[0] = make_float4(o[0], o[1], o[2], fmaxf(t0, 0.0f));
+        rr[1] = make_float4(d[0], d[1], d[2], t1);
+        rr[2] = make_float4(hit ? 1.f : 0.f, __builtin_bit_cast(float, base), 0.f, 0.f);
+        a.mstar[(size_t)j * a.cap + r] = m;
+    }
+    // the unit camera ray, as pixel_ray forms it
+    const float dc[3] = { ((float)x - a.ds.K.cx) / a.ds.K.fx, ((float)y - a.ds.K.cy) / a.ds.K.fy, 1.0f };
+    const float n = sqrtf(fmaf(dc[2], dc[2], fmaf(dc[1], dc[1], dc[0] * dc[0])));
+    float4* ray = a.ray + 3 * (size_t)r;
+    ray[0] = make_float4((float)(rgba & 0xffu) / 255.0f, (float)((rgba >> 8) & 0xffu) / 255.0f, (float)((rgba >> 16) & 0xffu) / 255.0f, dstar);
+    ray[1] = make_float4(n, Mstar, 0.f, 0.f);
+    ray[2] = make_float4(dc[0] / n, dc[1] / n, dc[2] / n, 0.f);
+}
+
+// ------------------------------------------------------------------ k_scene_pose_obj
+// One sample tile of one object's ray: position, network forward, sigma, colour, alpha (the render's arithmetic; the first interval from `tlast`)
+template <int EPAD, int W, int NH>
+struct SceneTile { TileState<EPAD, W, NH> ts; float t, x[3], p[3], dt, sigma, alpha, col[3]; };
+template <int EPAD, int W, int NH>
+__device__ __forceinline__ void scene_tile_forward(SceneTile<EPAD, W, NH>& q, int tile, int n, int lane, const float (&ro)[3], const float (&rd)[3], float t0,
+        float dtr, float jitter, float tlast, const Aabb& aabb, const float (&ext)[3], half_t* frags, const LevelRegs& lregs, const half2_t* table,
+        uint32_t table_bytes, int L) {
+    const uint32_t k = (uint32_t)tile * 32u + (uint32_t)n;
+    const float t = fmaf(dtr, (float)k + jitter, t0);
+    q.t = t;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { const float v = fmaf(t, rd[d], ro[d]); q.p[d] = v; q.x[d] = (v - aabb.mn[d]) / ext[d]; }
+    tile_forward<EPAD, W, NH>(q.ts, frags, lregs, table, table_bytes, L, q.x, lane);
+    q.sigma = __expf(q.ts.out4[3]);
+    q.col[0] = logistic_f(q.ts.out4[0]); q.col[1] = logistic_f(q.ts.out4[1]); q.col[2] = logistic_f(q.ts.out4[2]);
+    float tprev = lane_prev(t, tlast); if (n == 0) tprev = tlast;
+    q.dt = t - tprev;
+    q.alpha = 1.f - __expf(-q.sigma * q.dt);
+}
+
+// One wavefront per ray of one object, its 2S = 64 samples as two 32-sample tiles (k_fused_render's placement, jitter, alpha, colour; the second tile only
+// where the object's own transmittance after the first is >= eps).
+// BWD = false: the forward alone.  Writes the object's list of the ray in the EMIT format of the scene render: t, {alpha, r, g, b}, count (0 a miss, else
+// 32 per evaluated tile).
+// BWD = true: recomputes the forward of the tiles the count names, takes dL/dalpha and w of every sample from the list slots k_scene_composite_grad filled
+// and G_rgb from the ray's row, forms dL/dO (x the ray's power-of-two scale), and runs pose_tile_backward -- k_pose_grad's MLP backward and position
+// gradient.  Per lane: sums of g and x x g over its samples, object frame; per workgroup: one partial row of 8 floats {g, x x g, 0, 0}.
+template <int EPAD, int W, int NH, bool LW, bool BWD>
+__global__ void __launch_bounds__(256) k_scene_pose_obj(FusedArgs a, ScenePoseObjArgs p) {
+    using S = FusedShape<EPAD, W, NH>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    half_t* frags = reinterpret_cast<half_t*>(smem);
+    LevelLds* llt = reinterpret_cast<LevelLds*>(smem + S::FRAG_BYTES);
+    float* red = reinterpret_cast<float*>(smem + S::FRAG_BYTES + 512);                  // [WAVES][8]
+    build_fragments<EPAD, W, NH>(frags, llt, a, BWD);
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
+    const int L = a.nd.L;
+    const half2_t* table = reinterpret_cast<const half2_t*>(a.params + a.nd.n_mlp);
+    const LevelRegs lregs = load_level_regs_uniform(a.lt, L, lane); const uint32_t table_bytes = a.lt.offset[L] * 4u;
+    const __amdgpu_buffer_rsrc_t rsrc = table_rsrc(table, table_bytes);
+    float lw = 1.f;                                                                     // LW: the weight of this lane's level (LevelRegs' placement)
+    if constexpr (LW) {
+        const int LPH = (L + 1) >> 1, lv = lane < 32 ? lane : lane - 32 + LPH;
+        lw = ((lane & 31) < LPH && lv < L) ? p.level_w[lv] : 0.f;
+    }
+    float ext[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) ext[d] = a.oc.aabb.mx[d] - a.oc.aabb.mn[d];
+    float acc[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+    for (uint32_t ray = blockIdx.x * S::WAVES + wave; ray < p.n_rays; ray += gridDim.x * S::WAVES) {
+        const float4* rr = p.rec + 3 * (size_t)ray;
+        const float4 r0 = rr[0], r1 = rr[1], r2 = rr[2];
+        const float ro[3] = { r0.x, r0.y, r0.z }, rd[3] = { r1.x, r1.y, r1.z };
+        const float t0 = r0.w, t1 = r1.w;
+        const bool hit = r2.x != 0.f; const uint32_t base = __builtin_bit_cast(uint32_t, r2.y);
+        const float dtr = (t1 - t0) / 64.0f;
+        const size_t slot0 = (size_t)ray * 64u;
+        if constexpr (!BWD) {
+            if (!hit) { if (lane == 0) p.cnt[ray] = 0u; continue; }
+            float Tc = 1.f, tlast = 0.f; uint32_t n_emit = 0u;
+            for (int tile = 0; tile < 2; ++tile) {
+                if (tile == 1 && !(Tc >= kTransmittanceEps)) break;
+                SceneTile<EPAD, W, NH> q;
+                const uint32_t k = (uint32_t)tile * 32u + (uint32_t)n;
+                scene_tile_forward<EPAD, W, NH>(q, tile, n, lane, ro, rd, t0, dtr, rand01(p.seed, p.stream, p.step, base + k), tlast, a.oc.aabb, ext, frags,
+                        lregs, table, table_bytes, L);
+                if (lane < 32) { p.t[slot0 + k] = q.t; p.attr[slot0 + k] = make_float4(q.alpha, q.col[0], q.col[1], q.col[2]); }
+                n_emit += 32u;
+                const float tincl = scan_mul32(1.f - q.alpha) * Tc;
+                float T = lane_prev(tincl, Tc); if (n == 0) T = Tc;
+                const int nact = __popc((uint32_t)__ballot(T >= kTransmittanceEps));
+                Tc = (nact > 0) ? lane_bcast(tincl, nact > 0 ? nact - 1 : 0) : Tc;
+                tlast = lane_bcast(q.t, 31);
+            }
+            if (lane == 0) p.cnt[ray] = n_emit;
+        } else {
+            const uint32_t count = hit ? p.cnt[ray] : 0u;
+            if (count == 0u && !p.dbg) continue;                                        // nothing of this object on the ray
+            const float4 G = p.grow[ray];                                               // {G_rgb, l}
+            const float Gc[3] = { G.x, G.y, G.z };
+            SceneTile<EPAD, W, NH> q[2];
+            float dO[2][4]; float mx = 0.f, tlast = 0.f;
+#pragma unroll
+            for (int tile = 0; tile < 2; ++tile) {
+                const uint32_t k = (uint32_t)tile * 32u + (uint32_t)n;
+                if ((uint32_t)tile * 32u >= count) {
+                    const float t = fmaf(dtr, (float)k + rand01(p.seed, p.stream, p.step, base + k), t0);
+                    q[tile].t = t;
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) { q[tile].p[d] = fmaf(t, rd[d], ro[d]); q[tile].x[d] = 0.f; }
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) dO[tile][c] = 0.f;
+                    continue;
+                }
+                scene_tile_forward<EPAD, W, NH>(q[tile], tile, n, lane, ro, rd, t0, dtr, rand01(p.seed, p.stream, p.step, base + k), tlast, a.oc.aabb, ext,
+                        frags, lregs, table, table_bytes, L);
+                tlast = lane_bcast(q[tile].t, 31);
+                const float2 gw = p.gw[slot0 + (size_t)k];                              // {dL/dalpha, w} of this sample in the merged composite
+                const bool on = h == 0;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) dO[tile][c] = on ? Gc[c] * gw.y * (q[tile].col[c] * (1.f - q[tile].col[c])) : 0.f;
+                dO[tile][3] = on ? gw.x * (1.f - q[tile].alpha) * q[tile].dt * q[tile].sigma : 0.f;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) mx = fmaxf(mx, fabsf(dO[tile][c]));
+            }
+            mx = lane_bcast(max32(mx), 31);
+            // power-of-two scale: the largest |dL/dO| of the ray lands in [32, 64) -- exact to undo
+            int e = 0; (void)frexpf(mx, &e);
+            const float up = ldexpf(1.f, 6 - e), down = ldexpf(1.f, e - 6);
+            const float4 uc = p.dbg ? p.ray[3 * (size_t)ray + 2] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int tile = 0; tile < 2; ++tile) {
+                float gl[3] = { 0.f, 0.f, 0.f };
+                const bool ev = (uint32_t)tile * 32u < count;
+                if (ev && mx > 0.f)
+                    pose_tile_backward<EPAD, W, NH, LW>(gl, q[tile].ts, frags, lregs, rsrc, q[tile].x, dO[tile], up, down, ext, lane, h, L, lw);
+                acc[0] += gl[0]; acc[1] += gl[1]; acc[2] += gl[2];
+                const float* x = q[tile].p;
+                acc[3] += x[1] * gl[2] - x[2] * gl[1]; acc[4] += x[2] * gl[0] - x[0] * gl[2]; acc[5] += x[0] * gl[1] - x[1] * gl[0];
+                if (p.dbg) {
+                    float gf[3];
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) gf[d] = gl[d] + __shfl_xor(gl[d], 32);
+                    if (lane < 32) {                                                    // [ray][64][14]: x_o, x_c, t, raw, dL/dx
+                        float* o = p.dbg + ((size_t)(p.ray0 + ray) * 64u + (uint32_t)tile * 32u + (uint32_t)n) * 14u;
+                        const float tv = q[tile].t;
+                        for (int d = 0; d < 3; ++d) { o[d] = hit ? x[d] : 0.f; o[7 + 4 + d] = gf[d] * p.inv_n; }
+                        o[3] = hit ? tv * uc.x : 0.f; o[4] = hit ? tv * uc.y : 0.f; o[5] = hit ? tv * uc.z : 0.f; o[6] = hit ? tv : 0.f;
+                        for (int c = 0; c < 4; ++c) o[7 + c] = ev ? q[tile].ts.out4[c] : 0.f;
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (BWD) {
+        // ---- wave sums, then the workgroup's row in wave order
+        float tot6[6];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) tot6[j] = wave_sum(acc[j]);
+        if (lane == 0) {
+#pragma unroll
+            for (int j = 0; j < 6; ++j) red[wave * 8 + j] = tot6[j];
+            red[wave * 8 + 6] = 0.f; red[wave * 8 + 7] = 0.f;
+        }
+        __syncthreads();
+        if (threadIdx.x < 8) {
+            float s = 0.f;
+            for (int w = 0; w < S::WAVES; ++w) s += red[w * 8 + threadIdx.x];
+            p.partials[(size_t)blockIdx.x * 8 + threadIdx.x] = s;
+        }
+    }
+}
+
+// ------------------------------------------------------------------ k_scene_composite_grad
+// 64-lane inclusive suffix sum from the two half-wave suffix sums
+__device__ __forceinline__ float suffix_add64(float v) {
+    const float s = suffix_add32(v);
+    return s + ((threadIdx.x & 32) ? 0.f : lane_bcast(s, 32));
+}
+// One wavefront (= one workgroup) per ray: k_scene_composite's compaction and merged order (scene_merge_lists), then the composite forward in blocks of 64
+// with a carried transmittance (each block's entry transmittance kept in LDS), the per-list weight sums W_j, the ray's loss
+//   l = w_rgb M* |r|^2 / 3 + w_mask sum_j (W_j - m*_j)^2 + w_depth M* [d* > 0] Huber(D - d*),
+// and the blocks again in reverse with a carried suffix sum: with q_i = G_rgb . (c_i - c*) + G_D t_i + 2 w_mask (W_j(i) - m*_j(i)),
+//   dL/dalpha_i = T_i q_i - sum_{n > i} w_n q_n / (1 - alpha_i)       (so that dL/dsigma_i = dt_i (T_{i+1} q_i - sum_{n > i} w_n q_n))
+// Every merged sample's list slot receives {dL/dalpha, w} (0, 0 from the cut on); the ray's row receives {G_rgb, l}.  The workgroup's rays' losses are summed
+// in ray order into loss_part[blockIdx.x].
+__global__ void __launch_bounds__(64) k_scene_composite_grad(SceneCompGradArgs a) {
+    constexpr uint32_t L2S = kSceneListLen;
+    const uint32_t n_lists = a.n_lists, cap = a.cap;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint16_t* s_perm = reinterpret_cast<uint16_t*>(smem);                             // [L2S * n_lists] merged order: compact list << 6 | index
+    uint32_t* s_id = reinterpret_cast<uint32_t*>(smem + 2u * L2S * n_lists);          // [n_lists] compact list -> list
+    uint32_t* s_c = s_id + n_lists;                                                    // its count
+    float* s_tf = reinterpret_cast<float*>(s_c + n_lists);                             // its first t
+    float* s_tl = s_tf + n_lists;                                                      // its last t
+    float* s_w = s_tl + n_lists;                                                       // its summed weight W
+    float* s_q = s_w + n_lists;                                                        // its 2 w_mask (W - m*)
+    float* s_T = s_q + n_lists;                                                        // [n_lists] entry transmittance of each 64-sample block
+    const int lane = threadIdx.x;
+    float loss_acc = 0.f;
+    for (uint32_t ray = blockIdx.x; ray < a.n_rays; ray += gridDim.x) {
+        uint32_t na, n_tot;
+        scene_merge_lists(ray, n_lists, cap, a.t, a.cnt, lane, s_perm, s_id, s_c, s_tf, s_tl, s_w, na, n_tot);
+        const float4 tg = a.ray[3 * (size_t)ray], tg1 = a.ray[3 * (size_t)ray + 1];
+        const float cs[3] = { tg.x, tg.y, tg.z }, dstar = tg.w, dn = tg1.x, Mstar = tg1.y;
+        // ---- forward
+        float Tc = 1.f, res[3] = { 0.f, 0.f, 0.f }, dep = 0.f;
+        const uint32_t n_blocks = (n_tot + 63u) / 64u;
+        uint32_t n_done = 0u;                                                           // blocks composited (the cut lies in the last of them, or nowhere)
+        for (uint32_t blk = 0; blk < n_blocks; ++blk) {
+            const uint32_t pidx = blk * 64u + (uint32_t)lane;
+            float tv = 0.f, al = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f; uint32_t ac = ~0u;
+            if (pidx < n_tot) {
+                const uint32_t e = s_perm[pidx];
+                if ((e >> 6) < na) {
+                    ac = e >> 6;
+                    const size_t idx = ((size_t)s_id[ac] * cap + ray) * L2S + (e & 63u);
+                    const float4 v = a.attr[idx]; tv = a.t[idx]; al = v.x; c0 = v.y; c1 = v.z; c2 = v.w;
+                }
+            }
+            if (lane == 0) s_T[blk] = Tc;
+            const float omv = 1.f - al;
+            const float sc = scan_mul32(omv), lo = sc * Tc, mid = lane_bcast(lo, 31);
+            const float incl = lane < 32 ? lo : sc * mid;                              // (the second half-wave carries the first's transmittance)
+            float T = lane_prev(incl, Tc); if (lane == 0) T = Tc; if (lane == 32) T = mid;
+            const bool active = T >= kTransmittanceEps;
+            const int nact = __popcll(__ballot(active));
+            const float wgt = active ? al * T : 0.f;
+            const float x0 = scan_add32(wgt * (c0 - cs[0])), x1 = scan_add32(wgt * (c1 - cs[1])), x2 = scan_add32(wgt * (c2 - cs[2])), xd = scan_add32(wgt * tv);
+            res[0] += lane_bcast(x0, 31); res[1] += lane_bcast(x1, 31); res[2] += lane_bcast(x2, 31); dep += lane_bcast(xd, 31);
+            res[0] += lane_bcast(x0, 63); res[1] += lane_bcast(x1, 63); res[2] += lane_bcast(x2, 63); dep += lane_bcast(xd, 63);
+            // per-list weight sums: one reduction per list present in the block
+            unsigned long long pend = __ballot(ac != ~0u && wgt != 0.f);
+            while (pend) {
+                const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)ac, (int)__builtin_ctzll(pend));
+                const bool mine = ac == a0;
+                const float xs = scan_add32(mine ? wgt : 0.f);
+                const float sum = lane_bcast(xs, 31) + lane_bcast(xs, 63);
+                if (lane == 0) s_w[a0] += sum;
+                pend &= ~__ballot(mine);
+            }
+            Tc = nact > 0 ? lane_bcast(incl, nact > 0 ? nact - 1 : 0) : Tc;
+            n_done = blk + 1u;
+            if (nact < 64) break;                                                      // transmittance ran out inside this block
+        }
+        __syncthreads();
+        // ---- the ray's loss and the gradients of its terms
+        const float D = dep / dn;
+        const bool dep_on = a.w_depth != 0.f && Mstar != 0.f && dstar > 0.f;
+        float lmask = 0.f;                                                              // sum_j (W_j - m*_j)^2 over every list, in list order by wave
+        for (uint32_t g = 0; g < n_lists; g += 64u) {
+            const uint32_t k = g + (uint32_t)lane;
+            float term = 0.f;
+            if (k < n_lists) {
+                // compact index of list k, if it has one: binary search over s_id[0, na)
+                uint32_t lo2 = 0u, hi2 = na;
+                while (lo2 < hi2) { const uint32_t mid2 = (lo2 + hi2) >> 1; if (s_id[mid2] < k) lo2 = mid2 + 1u; else hi2 = mid2; }
+                const bool present = lo2 < na && s_id[lo2] == k;
+                const float Wk = present ? s_w[lo2] : 0.f, m = a.mstar[(size_t)k * cap + ray];
+                const float dW = Wk - m;
+                term = dW * dW;
+                if (present) s_q[lo2] = 2.f * a.w_mask * dW;
+                if (a.out_W) a.out_W[(size_t)k * cap + ray] = Wk;
+            }
+            lmask += wave_sum(term);
+        }
+        const float l = a.w_rgb * Mstar * (res[0] * res[0] + res[1] * res[1] + res[2] * res[2]) / 3.f + a.w_mask * lmask
+                + (dep_on ? a.w_depth * huber_f(D - dstar, a.huber) : 0.f);
+        loss_acc += l;
+        const float Gc[3] = { a.w_rgb * Mstar * 2.f * res[0] / 3.f, a.w_rgb * Mstar * 2.f * res[1] / 3.f, a.w_rgb * Mstar * 2.f * res[2] / 3.f };
+        const float GD = dep_on ? a.w_depth * clamp_f(D - dstar, -a.huber, a.huber) / dn : 0.f;
+        if (lane == 0) { a.grow[ray] = make_float4(Gc[0], Gc[1], Gc[2], l); if (a.out_D) a.out_D[ray] = D; }
+        __syncthreads();
+        // ---- backward: the blocks in reverse, the suffix sum of w q carried from block to block
+        float carry = 0.f;
+        for (uint32_t bb = n_blocks; bb > 0u; --bb) {
+            const uint32_t blk = bb - 1u, pidx = blk * 64u + (uint32_t)lane;
+            size_t idx = 0; bool have = false; uint32_t ac = 0u;
+            if (pidx < n_tot) {
+                const uint32_t e = s_perm[pidx];
+                if ((e >> 6) < na) { ac = e >> 6; idx = ((size_t)s_id[ac] * cap + ray) * L2S + (e & 63u); have = true; }
+            }
+            if (blk >= n_done) { if (have) a.gw[idx] = make_float2(0.f, 0.f); continue; }          // behind the cut
+            float tv = 0.f, al = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, qm = 0.f;
+            if (have) { const float4 v = a.attr[idx]; tv = a.t[idx]; al = v.x; c0 = v.y; c1 = v.z; c2 = v.w; qm = s_q[ac]; }
+            const float Tb = s_T[blk];
+            const float omv = 1.f - al;
+            const float sc = scan_mul32(omv), lo = sc * Tb, mid = lane_bcast(lo, 31);
+            const float incl = lane < 32 ? lo : sc * mid;
+            float T = lane_prev(incl, Tb); if (lane == 0) T = Tb; if (lane == 32) T = mid;
+            const bool active = T >= kTransmittanceEps;
+            const float wgt = active ? al * T : 0.f;
+            const float q = Gc[0] * (c0 - cs[0]) + Gc[1] * (c1 - cs[1]) + Gc[2] * (c2 - cs[2]) + GD * tv + qm;
+            const float sin = suffix_add64(wgt * q);                                   // inclusive
+            float sfx = lane_next(sin, 0.f); if (lane == 63) sfx = 0.f;               // samples behind this one, this block
+            sfx += carry;
+            const float g = (active && have) ? T * q - (omv > 0.f ? sfx / omv : 0.f) : 0.f;
+            if (have) a.gw[idx] = make_float2(g, wgt);
+            carry += lane_bcast(sin, 0);
+        }
+        __syncthreads();
+    }
+    if (lane == 0) a.loss_part[blockIdx.x] = loss_acc;
+}
+
+// ------------------------------------------------------------------ k_scene_pose_update
+// One workgroup.  Per object, in index order: its partial rows summed in k_pose_update's fixed order (32 strided groups per column, then the groups in
+// order), x 1/N -> G_j = (sum g_o, sum x_o x g_o) in the object frame; with Toc_j = Tow_j Twc = (R, p) mapped to the camera frame,
+// grad_rho += R^T G_rho, grad_phi += R^T (G_phi - p x G_rho).  The loss partials are summed 256-strided, then in order.  out[8 * it] = {loss, grad6, 0};
+// step != 0: Adam on the twist and Twc <- Twc exp(delta^), its rotation re-orthonormalised (Gram-Schmidt on the columns).
+__global__ void __launch_bounds__(256) k_scene_pose_update(ScenePoseUpdateArgs a) {
+    __shared__ float part[32][8];
+    __shared__ float lpart[256];
+    const uint32_t col = threadIdx.x & 7u, grp = threadIdx.x >> 3;
+    float grad[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+    for (uint32_t j = 0; j < a.n_objs; ++j) {
+        const float* rows = a.partials + (size_t)j * a.row_stride * 8;
+        float s = 0.f;
+        for (uint32_t b = grp; b < a.n_rows; b += 32u) s += rows[(size_t)b * 8 + col];
+        part[grp][col] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float v[6];
+            for (int k = 0; k < 6; ++k) { float q = 0.f; for (int g = 0; g < 32; ++g) q += part[g][k]; v[k] = q * a.inv_n; }
+            const float* Tow = a.objs[j].Tow; const float* Twc = a.pose;
+            float R[9], p[3];                                                           // Toc = Tow Twc, column-major 3x3
+            for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) {
+                float q = 0.f; for (int k = 0; k < 3; ++k) q += Tow[k * 4 + r] * Twc[c * 4 + k]; R[c * 3 + r] = q; }
+            for (int r = 0; r < 3; ++r) p[r] = Tow[r] * Twc[12] + Tow[4 + r] * Twc[13] + Tow[8 + r] * Twc[14] + Tow[12 + r];
+            const float m[3] = { v[3] - (p[1] * v[2] - p[2] * v[1]), v[4] - (p[2] * v[0] - p[0] * v[2]), v[5] - (p[0] * v[1] - p[1] * v[0]) };
+            for (int c = 0; c < 3; ++c) {                                               // R^T: row c of R^T is column c of R
+                grad[c] += R[c * 3] * v[0] + R[c * 3 + 1] * v[1] + R[c * 3 + 2] * v[2];
+                grad[3 + c] += R[c * 3] * m[0] + R[c * 3 + 1] * m[1] + R[c * 3 + 2] * m[2];
+            }
+        }
+        __syncthreads();
+    }
+    float ls = 0.f;
+    for (uint32_t b = threadIdx.x; b < a.n_loss_parts; b += 256u) ls += a.loss_part[b];
+    lpart[threadIdx.x] = ls;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    float loss = 0.f;
+    for (int g = 0; g < 256; ++g) loss += lpart[g];
+    loss *= a.inv_n;
+    float* o = a.out + 8 * (size_t)a.it;
+    o[0] = loss; for (int j = 0; j < 6; ++j) o[1 + j] = grad[j]; o[7] = 0.f;
+    if (!a.step) return;
+    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
+    const float tt = (float)(a.it + 1u);
+    const float c1 = 1.f - powf(b1, tt), c2 = 1.f - powf(b2, tt);
+    float delta[6];
+    for (int j = 0; j < 6; ++j) {
+        const float g = grad[j];
+        const float m = b1 * a.moments[j] + (1.f - b1) * g, w = b2 * a.moments[6 + j] + (1.f - b2) * g * g;
+        a.moments[j] = m; a.moments[6 + j] = w;
+        const float lr = j < 3 ? a.lr_t : a.lr_r;
+        delta[j] = -lr * (m / c1) / (sqrtf(w / c2) + eps);
+    }
+    float Rd[9], td[3];
+    se3_exp(delta, Rd, td);
+    float* pose = a.pose;
+    float Rn[9], tn[3];                                                                 // Twc exp(delta^): R <- R Rd, t <- R td + t
+    for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) {
+        float q = 0.f; for (int k = 0; k < 3; ++k) q += pose[k * 4 + r] * Rd[c * 3 + k]; Rn[c * 3 + r] = q; }
+    for (int r = 0; r < 3; ++r) tn[r] = pose[r] * td[0] + pose[4 + r] * td[1] + pose[8 + r] * td[2] + pose[12 + r];
+    // Gram-Schmidt: column 0 normalised, column 1 made orthogonal to it and normalised, column 2 = c0 x c1
+    float* a0 = Rn; float* a1 = Rn + 3; float* a2 = Rn + 6;
+    float nn = rsqrtf(a0[0] * a0[0] + a0[1] * a0[1] + a0[2] * a0[2]); for (int r = 0; r < 3; ++r) a0[r] *= nn;
+    const float dp = a0[0] * a1[0] + a0[1] * a1[1] + a0[2] * a1[2]; for (int r = 0; r < 3; ++r) a1[r] -= dp * a0[r];
+    nn = rsqrtf(a1[0] * a1[0] + a1[1] * a1[1] + a1[2] * a1[2]); for (int r = 0; r < 3; ++r) a1[r] *= nn;
+    a2[0] = a0[1] * a1[2] - a0[2] * a1[1]; a2[1] = a0[2] * a1[0] - a0[0] * a1[2]; a2[2] = a0[0] * a1[1] - a0[1] * a1[0];
+    for (int c = 0; c < 3; ++c) { for (int r = 0; r < 3; ++r) pose[c * 4 + r] = Rn[c * 3 + r]; pose[c * 4 + 3] = 0.f; }
+    for (int r = 0; r < 3; ++r) pose[12 + r] = tn[r];
+    pose[15] = 1.f;
+}
+
+// ------------------------------------------------------------------ launchers
+template <int EPAD, int W, int NH>
+static void scene_pose_obj_t(hipStream_t s, const FusedArgs& a, const ScenePoseObjArgs& p, uint32_t grid, int backward, int build_image) {
+    using S = FusedShape<EPAD, W, NH>;
+    const uint32_t smem = S::FRAG_BYTES + 512 + S::WAVES * 32;
+    if (build_image) hipLaunchKernelGGL((k_build_frag_image<EPAD, W, NH>), dim3((S::N_FRAGS * 512 + 255) / 256), dim3(256), 0, s, a.params, a.nd.L,
+            const_cast<uint16_t*>(a.frag_image), (const DevState*)nullptr);
+    if (!backward) hipLaunchKernelGGL((k_scene_pose_obj<EPAD, W, NH, false, false>), dim3(grid), dim3(256), smem, s, a, p);
+    else if (p.level_w) hipLaunchKernelGGL((k_scene_pose_obj<EPAD, W, NH, true, true>), dim3(grid), dim3(256), smem, s, a, p);
+    else hipLaunchKernelGGL((k_scene_pose_obj<EPAD, W, NH, false, true>), dim3(grid), dim3(256), smem, s, a, p);
+}
+
+void launch_scene_pose_rays(hipStream_t s, const ScenePoseRayArgs& a) {
+    if (!a.n_rays || !a.n_objs) return;
+    hipLaunchKernelGGL(k_scene_pose_rays, dim3((a.n_rays + 255) / 256), dim3(256), 0, s, a);
+}
+void launch_scene_pose_obj(hipStream_t s, const LevelFast& lt, const NetDims& nd, const ObjectConst& oc, const uint16_t* params, uint16_t* frag_image,
+        int build_image, int backward, uint32_t grid, const ScenePoseObjArgs& p) {
+    if (!p.n_rays) return;
+    FusedArgs a{}; a.lt = lt; a.nd = nd; a.oc = oc; a.params = params; a.frag_image = frag_image;
+    MON_FUSED_DISPATCH(scene_pose_obj_t, s, a, p, grid, backward, build_image);
+}
+uint32_t scene_comp_grad_grid(uint32_t n_rays) { return n_rays < kSceneLossParts ? (n_rays ? n_rays : 1u) : kSceneLossParts; }
+void launch_scene_composite_grad(hipStream_t s, const SceneCompGradArgs& a) {
+    if (!a.n_rays || !a.n_lists || a.n_lists > kSceneMaxLists) return;
+    hipLaunchKernelGGL(k_scene_composite_grad, dim3(scene_comp_grad_grid(a.n_rays)), dim3(64), scene_composite_grad_lds(a.n_lists), s, a);
+}
+void launch_scene_pose_update(hipStream_t s, const ScenePoseUpdateArgs& a) {
+    hipLaunchKernelGGL(k_scene_pose_update, dim3(1), dim3(256), 0, s, a);
+}
+
+}  // namespace mon

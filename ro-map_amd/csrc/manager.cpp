@@ -687,6 +687,26 @@ int mon_online_refine_pose_c2f(mon_online* h, size_t idx, const mon_frame_bbox* 
     if (rc == MON_OK) std::memcpy(Tow16_inout, pose, 64);
     return rc;
 }
+// camera refinement against every object of the manager that has published weights (mon_scene_refine_camera on side 1: a frontend's call, safe while they
+// train).  Nothing of the manager changes: the caller hands the pose to mon_online_update_dataset if the dataset is to hold it.
+int mon_online_refine_camera(mon_online* h, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, const mon_pose_c2f_params* c,
+        float* Twc16_inout, float* loss_trace) {
+    REQ(h); REQ(obs); REQ(p); REQ(Twc16_inout);
+    if (n_obs == 0 || p->iters < 0) { set_error("refine_camera: no boxes or iters < 0"); return MON_ERR_ARG; }
+    if (c) { const int rc = pose_c2f_check(c); if (rc) return rc; }
+    std::vector<Model*> ms;
+    const std::vector<OnlineObject*> objs = online_objects(*h->m);
+    for (size_t i = 0; i < objs.size() && ms.size() < kSceneMaxLists; ++i) if (objs[i]->model && model_has_snapshot(*objs[i]->model)) ms.push_back(objs[i]->model);
+    if (ms.empty()) { set_error("refine_camera: no object has published weights yet"); return MON_ERR_STATE; }
+    for (Model* m : ms) if (m->device != ms[0]->device) { set_error("refine_camera: the objects span more than one device"); return MON_ERR_STATE; }
+    int Lmax = 0; for (Model* m : ms) Lmax = std::max(Lmax, (int)m->nd.L);
+    std::vector<float> table; if (c) table = pose_c2f_table(*c, Lmax, p->iters);
+    float pose[16]; std::memcpy(pose, Twc16_inout, 64);
+    const int rc = scene_pose(ms.data(), ms.size(), 1, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr,
+                              table.empty() ? nullptr : table.data());
+    if (rc == MON_OK) std::memcpy(Twc16_inout, pose, 64);
+    return rc;
+}
 // NerfManagerOnline::RenderNeRFsTest -> NeRF::RenderTestImg, nerf.cu:255-404: <out>/<id>/{test_img,test_depth,test_mask}/<stamp>.png,
 // test.txt, train.txt (object-centric poses), 60-view video_img / video_depth, obj.ply
 int mon_online_render_nerfs_test(mon_online* h, const char* out_path, size_t idx, const char* const* timestamps, const mon_frame_bbox* boxes,

@@ -1684,6 +1684,207 @@ int pose_refine(Model& m, int side, const mon_frame_bbox* obs, size_t n_obs, con
     return MON_OK;
 }
 
+// ---- camera refinement against a scene of objects (mon_scene_pose_loss / mon_scene_refine_camera): per evaluation and chunk of rays k_scene_pose_rays ->
+// every object's k_scene_pose_obj (forward) -> k_scene_composite_grad -> every object's k_scene_pose_obj (backward), then k_scene_pose_update; the camera
+// pose lives in device memory between steps.  Per device and side, grow-only, never freed (like SceneWs, whose users are untouched).  A call holds `mu` until
+// its stream has been synchronised.
+struct ScenePoseWs {
+    std::mutex mu;
+    float* t = nullptr; size_t t_cap = 0; float4* attr = nullptr; size_t attr_cap = 0; float2* gw = nullptr; size_t gw_cap = 0;   // [objects][cap][64]
+    uint32_t* cnt = nullptr; size_t cnt_cap = 0; float* mstar = nullptr; size_t mstar_cap = 0; float4* rec = nullptr; size_t rec_cap = 0;   // [objects][cap]( x 3)
+    float4* ray = nullptr; size_t ray_cap = 0; float4* grow = nullptr; size_t grow_cap = 0;                                   // [cap] x 3, [cap]
+    float* partials = nullptr; size_t part_cap = 0; float* loss_part = nullptr; size_t lp_cap = 0;
+    SceneObjConst* objs = nullptr; size_t objs_cap = 0; uint16_t* frag = nullptr; size_t frag_cap = 0;
+    mon_frame_bbox* boxes = nullptr; size_t box_cap = 0; uint32_t* prefix = nullptr; size_t prefix_cap = 0;
+    float* small = nullptr; size_t small_cap = 0;                                 // pose [16] | moments [12]
+    float* out = nullptr; size_t out_cap = 0; float* h_out = nullptr; size_t h_out_cap = 0;   // {loss, grad6, 0} per evaluation | pose; pinned staging
+    float* lw = nullptr; size_t lw_cap = 0;                                       // level weights [evaluation][Lmax]
+    float* dbg = nullptr; size_t dbg_cap = 0; uint32_t* dbg_cnt = nullptr; size_t dbg_cnt_cap = 0;
+    std::vector<hipEvent_t> ev;
+};
+static std::mutex g_scene_pose_mu; static std::map<std::pair<int, int>, ScenePoseWs*> g_scene_pose_ws;
+static ScenePoseWs& scene_pose_ws(int device, int side) {
+    std::lock_guard<std::mutex> l(g_scene_pose_mu); ScenePoseWs*& w = g_scene_pose_ws[{ device, side }]; if (!w) w = new ScenePoseWs(); return *w;
+}
+int scene_pose_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16, const mon_pose_refine_params* p) {
+    if (!ms || !obs || !Twc16 || !p) { set_error("scene pose: null argument"); return MON_ERR_ARG; }
+    if (n == 0 || n > kSceneMaxLists) { set_error("scene pose: %zu objects (1 to %u)", n, kSceneMaxLists); return MON_ERR_ARG; }
+    for (size_t j = 0; j < n; ++j) if (!ms[j]) { set_error("scene pose: null object %zu", j); return MON_ERR_ARG; }
+    if (n_obs == 0) { set_error("scene pose: no boxes"); return MON_ERR_ARG; }
+    if (p->iters < 0) { set_error("scene pose: iters %d < 0", p->iters); return MON_ERR_ARG; }
+    if (side != 0 && side != 1) { set_error("scene pose: side %d (0 or 1)", side); return MON_ERR_ARG; }
+    if (p->rays_per_iter > kPoseMaxRays) { set_error("scene pose: rays_per_iter %u above %u", p->rays_per_iter, kPoseMaxRays); return MON_ERR_ARG; }
+    const Model& m0 = *ms[0]; const Intrinsics& K = m0.ds->K;
+    for (size_t j = 1; j < n; ++j) {
+        const Model& m = *ms[j]; const Intrinsics& k = m.ds->K;
+        if (m.device != m0.device) { set_error("scene pose: objects on logical devices %d and %d", m0.device, m.device); return MON_ERR_ARG; }
+        if (k.fx != K.fx || k.fy != K.fy || k.cx != K.cx || k.cy != K.cy || k.W != K.W || k.H != K.H) {
+            set_error("scene pose: object %zu has other intrinsics", j); return MON_ERR_ARG; }
+        if (m.ds != m0.ds) { set_error("scene pose: object %zu is on another dataset", j); return MON_ERR_ARG; }
+    }
+    uint64_t total = 0;
+    for (size_t i = 0; i < n_obs; ++i) {
+        const mon_frame_bbox& b = obs[i];
+        if (b.FrameId != obs[0].FrameId) { set_error("scene pose: boxes name frames %u and %u (one frame per call)", obs[0].FrameId, b.FrameId); return MON_ERR_ARG; }
+        if (b.FrameId >= m0.ds->max_frames || !m0.ds->present[b.FrameId]) { set_error("scene pose: box %zu names frame %u, which the dataset does not hold", i,
+            b.FrameId); return MON_ERR_ARG; }
+        if (b.w == 0 || b.h == 0 || (uint64_t)b.x + b.w > (uint64_t)K.W || (uint64_t)b.y + b.h > (uint64_t)K.H) {
+            set_error("scene pose: box %zu (frame %u, x %u y %u h %u w %u) empty or outside the %dx%d frame", i, b.FrameId, b.x, b.y, b.h, b.w, K.W, K.H);
+            return MON_ERR_ARG; }
+        total += (uint64_t)b.w * b.h;
+        if (total > kPoseMaxRays * 64ull) { set_error("scene pose: the boxes hold too many pixels"); return MON_ERR_ARG; }
+    }
+    if (!p->rays_per_iter && total > kPoseMaxRays) { set_error("scene pose: %llu pixels in the boxes (at most %u with rays_per_iter = 0)",
+        (unsigned long long)total, kPoseMaxRays); return MON_ERR_ARG; }
+    return MON_OK;
+}
+int scene_pose(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16, const mon_pose_refine_params& p, int iters,
+               uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const ScenePoseDump* dump, const float* level_w) {
+    { const int rc = scene_pose_check(ms, n, side, obs, n_obs, Twc16, &p); if (rc) return rc; }
+    if (dump && dump->k >= n) { set_error("scene pose: dump of object %u of %zu", dump->k, n); return MON_ERR_ARG; }
+    if (!launch_scene_pose_rays || !launch_scene_pose_obj || !launch_scene_composite_grad || !launch_scene_pose_update || !scene_comp_grad_grid || !pose_grad_grid) {
+        set_error("scene pose: built without kernels_scene_pose.hip"); return MON_ERR_STATE; }
+    int Lmax = 0;
+    for (size_t j = 0; j < n; ++j) {
+        Model& m = *ms[j];
+        if (!rskip_supported(m) || 2u * m.oc.S != kSceneListLen) { set_error("scene pose: object %zu does not run on the fused kernels", j); return MON_ERR_STATE; }
+        if (m.d_xw) { set_error("scene pose: object %zu renders with the XORWOW sample stream (rng_flags)", j); return MON_ERR_STATE; }
+        if (side == 1 && !model_has_snapshot(m)) { set_error("scene pose: object %zu has no published snapshot", j); return MON_ERR_STATE; }
+        Lmax = std::max(Lmax, (int)m.nd.L);
+    }
+    std::vector<uint32_t> prefix(n_obs + 1, 0u);
+    for (size_t i = 0; i < n_obs; ++i) prefix[i + 1] = prefix[i] + obs[i].w * obs[i].h;
+    const uint32_t total = prefix[n_obs], n_rays = p.rays_per_iter ? p.rays_per_iter : total;
+    const int device = ms[0]->device;
+    HIPCHECK(use_device(device));
+    const int n_eval = iters < 0 ? 1 : iters + 1;
+    // the weights of the side and its stream, as scene_render takes them
+    std::vector<const uint16_t*> prm(n);
+    std::unique_lock<std::mutex> dev_lock;
+    struct Pins { std::vector<std::pair<InferState*, int>> p; ~Pins() { for (auto& q : p) { std::lock_guard<std::mutex> l(q.first->mu); --q.first->readers[q.second]; } } } pins;
+    hipStream_t s;
+    if (side == 1) {
+        InferShared* sh = ms[0]->infer->shared; dev_lock = std::unique_lock<std::mutex>(sh->mu); s = sh->stream;
+        for (size_t j = 0; j < n; ++j) {
+            InferState* is = ms[j]->infer; is->wanted.store(true); int r;
+            {   std::lock_guard<std::mutex> l(is->mu); r = is->latest;
+                if (is->written[1 - r] && hipEventQuery(is->ready[r]) != hipSuccess && hipEventQuery(is->ready[1 - r]) == hipSuccess) r = 1 - r;
+                ++is->readers[r]; pins.p.emplace_back(is, r); }
+            HIPCHECK(hipStreamWaitEvent(s, is->ready[r], 0));
+            prm[j] = is->snap[r];
+        }
+    }
+    ScenePoseWs& w = scene_pose_ws(device, side); std::lock_guard<std::mutex> wl(w.mu);
+    if (side == 0) {
+        for (size_t j = 0; j < n; ++j) { Model& m = *ms[j]; model_leave_lane(m); int rc = ensure_ema_current(m); if (rc) return rc; }
+        s = ms[0]->train_stream;
+        while (w.ev.size() < n) { hipEvent_t e; HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); w.ev.push_back(e); }
+        for (size_t j = 0; j < n; ++j) {
+            Model& m = *ms[j];
+            if (m.train_stream != s) { HIPCHECK(hipEventRecord(w.ev[j], m.train_stream)); HIPCHECK(hipStreamWaitEvent(s, w.ev[j], 0)); }
+            prm[j] = (m.h_state.step > 0) ? m.P.ema : m.P.half;
+        }
+    }
+    // chunks of the rays (the cap scene_render chunks its rect by); each chunk's partial rows follow the previous chunk's
+    const uint32_t cap = std::min(n_rays, kRenderChunkRays), n_chunks = (n_rays + cap - 1u) / cap;
+    const uint32_t gridc = std::min(pose_grad_grid(cap), std::max(1u, kPoseMaxGrid / n_chunks)), n_rows = n_chunks * gridc;
+    uint32_t n_lp = 0; for (uint32_t c = 0; c < n_chunks; ++c) n_lp += scene_comp_grad_grid(std::min(cap, n_rays - c * cap));
+    std::vector<size_t> frag_off(n + 1, 0);
+    for (size_t j = 0; j < n; ++j) { const NetDims& nd = ms[j]->nd; const FragDims fd{ nd.Epad, nd.W, nd.NH, nd.L }; frag_off[j + 1] = frag_off[j] + (size_t)fd.N_FRAGS() * 512; }
+    const size_t lists = n * (size_t)cap;
+    int rc;
+    if ((rc = grow_buf(w.t, w.t_cap, lists * kSceneListLen)) || (rc = grow_buf(w.attr, w.attr_cap, lists * kSceneListLen)) ||
+        (rc = grow_buf(w.gw, w.gw_cap, lists * kSceneListLen)) || (rc = grow_buf(w.cnt, w.cnt_cap, lists)) || (rc = grow_buf(w.mstar, w.mstar_cap, lists)) ||
+        (rc = grow_buf(w.rec, w.rec_cap, lists * 3)) || (rc = grow_buf(w.ray, w.ray_cap, (size_t)cap * 3)) || (rc = grow_buf(w.grow, w.grow_cap, (size_t)cap)) ||
+        (rc = grow_buf(w.partials, w.part_cap, n * (size_t)n_rows * 8)) || (rc = grow_buf(w.loss_part, w.lp_cap, (size_t)n_lp)) ||
+        (rc = grow_buf(w.objs, w.objs_cap, n)) || (rc = grow_buf(w.frag, w.frag_cap, frag_off[n])) || (rc = grow_buf(w.boxes, w.box_cap, n_obs)) ||
+        (rc = grow_buf(w.prefix, w.prefix_cap, n_obs + 1)) || (rc = grow_buf(w.small, w.small_cap, (size_t)28)) ||
+        (rc = grow_buf(w.out, w.out_cap, 8 * (size_t)n_eval + 16))) return rc;
+    if (8 * (size_t)n_eval + 16 > w.h_out_cap) {
+        if (w.h_out) { (void)hipHostFree(w.h_out); w.h_out = nullptr; w.h_out_cap = 0; }
+        HIPCHECK(hipHostMalloc((void**)&w.h_out, (8 * (size_t)n_eval + 16) * 4, hipHostMallocDefault)); w.h_out_cap = 8 * (size_t)n_eval + 16;
+    }
+    if (dump) { if ((rc = grow_buf(w.dbg, w.dbg_cap, (size_t)n_rays * 64 * 14)) || (rc = grow_buf(w.dbg_cnt, w.dbg_cnt_cap, (size_t)n_rays))) return rc; }
+    const int n_wrows = level_w ? (iters < 0 ? 1 : iters) : 0;
+    if (n_wrows) {
+        if ((rc = grow_buf(w.lw, w.lw_cap, (size_t)n_wrows * Lmax))) return rc;
+        HIPCHECK(hipMemcpyAsync(w.lw, level_w, sizeof(float) * (size_t)n_wrows * Lmax, hipMemcpyHostToDevice, s));
+    }
+    std::vector<SceneObjConst> h_objs(n);
+    for (size_t j = 0; j < n; ++j) { const ObjectConst& oc = ms[j]->oc; std::memcpy(h_objs[j].Tow, oc.Tow.m, 64); h_objs[j].aabb = oc.aabb;
+        h_objs[j].instance_id = oc.instance_id; h_objs[j].pad = 0u; }
+    float* d_pose = w.small; float* d_mom = w.small + 16;
+    HIPCHECK(hipMemcpyAsync(w.objs, h_objs.data(), sizeof(SceneObjConst) * n, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(w.boxes, obs, sizeof(mon_frame_bbox) * n_obs, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(w.prefix, prefix.data(), 4 * (n_obs + 1), hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(d_pose, Twc16, 64, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(d_mom, 0, 48, s));
+    const bool drawn = p.rays_per_iter != 0;
+    const float inv_n = 1.f / (float)n_rays;
+    for (int it = 0; it < n_eval; ++it) {
+        const uint32_t key = iters < 0 ? iteration : (uint32_t)it;
+        const float* lw_row = it < n_wrows ? w.lw + (size_t)it * Lmax : nullptr;
+        uint32_t lp_off = 0;
+        for (uint32_t c = 0; c < n_chunks; ++c) {
+            const uint32_t p0 = c * cap, nc = std::min(cap, n_rays - p0);
+            ScenePoseRayArgs ra{}; ra.boxes = w.boxes; ra.prefix = w.prefix; ra.n_obs = (uint32_t)n_obs; ra.n_rays = nc; ra.ray0 = p0; ra.total = total;
+            ra.drawn = drawn ? 1u : 0u; ra.iteration = key; ra.seed = p.seed; ra.ds = ms[0]->ds->ptrs(); ra.objs = w.objs; ra.n_objs = (uint32_t)n; ra.cap = cap;
+            ra.pose = d_pose; ra.rec = w.rec; ra.mstar = w.mstar; ra.ray = w.ray;
+            launch_scene_pose_rays(s, ra);
+            std::vector<ScenePoseObjArgs> oa(n);
+            for (size_t j = 0; j < n; ++j) {
+                Model& m = *ms[j]; const size_t l0 = j * (size_t)cap; ScenePoseObjArgs& a = oa[j];
+                a = ScenePoseObjArgs{}; a.rec = w.rec + l0 * 3; a.n_rays = nc; a.ray0 = p0;
+                a.seed = drawn ? p.seed : m.oc.sample_seed; a.stream = drawn ? kStreamPose : (uint32_t)kStreamRender; a.step = drawn ? key : 0u;
+                a.t = w.t + l0 * kSceneListLen; a.attr = w.attr + l0 * kSceneListLen; a.cnt = w.cnt + l0; a.gw = w.gw + l0 * kSceneListLen; a.grow = w.grow;
+                a.ray = w.ray; a.inv_n = inv_n; a.partials = w.partials + ((size_t)j * n_rows + (size_t)c * gridc) * 8;
+                a.dbg = (dump && dump->k == j) ? w.dbg : nullptr; a.level_w = lw_row;
+                launch_scene_pose_obj(s, m.lf, m.nd, m.oc, prm[j], w.frag + frag_off[j], it == 0 && c == 0, 0, pose_grad_grid(nc), a);
+            }
+            SceneCompGradArgs ca{}; ca.n_rays = nc; ca.n_lists = (uint32_t)n; ca.cap = cap; ca.t = w.t; ca.attr = w.attr; ca.cnt = w.cnt; ca.mstar = w.mstar;
+            ca.ray = w.ray; ca.w_rgb = p.w_rgb; ca.w_mask = p.w_mask; ca.w_depth = p.w_depth; ca.huber = p.depth_huber; ca.gw = w.gw; ca.grow = w.grow;
+            ca.loss_part = w.loss_part + lp_off;
+            launch_scene_composite_grad(s, ca);
+            lp_off += scene_comp_grad_grid(nc);
+            for (size_t j = 0; j < n; ++j) { Model& m = *ms[j];
+                launch_scene_pose_obj(s, m.lf, m.nd, m.oc, prm[j], w.frag + frag_off[j], 0, 1, gridc, oa[j]); }
+            if (dump) HIPCHECK(hipMemcpyAsync(w.dbg_cnt + p0, w.cnt + dump->k * (size_t)cap, 4 * (size_t)nc, hipMemcpyDeviceToDevice, s));
+        }
+        ScenePoseUpdateArgs ua{}; ua.partials = w.partials; ua.n_objs = (uint32_t)n; ua.n_rows = n_rows; ua.row_stride = n_rows; ua.loss_part = w.loss_part;
+        ua.n_loss_parts = n_lp; ua.objs = w.objs; ua.inv_n = inv_n; ua.out = w.out; ua.it = (uint32_t)it; ua.step = iters >= 0 && it < iters;
+        ua.lr_t = p.lr_trans; ua.lr_r = p.lr_rot; ua.pose = d_pose; ua.moments = d_mom;
+        launch_scene_pose_update(s, ua);
+    }
+    HIPCHECK(hipGetLastError());
+    // results home through the pinned staging: {loss, grad6, 0} of every evaluation, then the pose
+    // (copy kernels on the call's stream, as the scene render's results go home)
+    launch_copy_params(s, reinterpret_cast<const uint16_t*>(d_pose), reinterpret_cast<uint16_t*>(w.out + 8 * (size_t)n_eval), 32u);
+    launch_copy_params(s, reinterpret_cast<const uint16_t*>(w.out), reinterpret_cast<uint16_t*>(w.h_out), (uint32_t)((8 * (size_t)n_eval + 16) * 2));
+    std::vector<float> h_dbg; std::vector<uint32_t> h_cnt;
+    if (dump) { h_dbg.resize((size_t)n_rays * 64 * 14); h_cnt.resize(n_rays);
+        HIPCHECK(hipMemcpyAsync(h_dbg.data(), w.dbg, h_dbg.size() * 4, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipMemcpyAsync(h_cnt.data(), w.dbg_cnt, (size_t)n_rays * 4, hipMemcpyDeviceToHost, s)); }
+    HIPCHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    const float* h = w.h_out;
+    if (loss) *loss = h[0];
+    if (grad6) for (int j = 0; j < 6; ++j) grad6[j] = h[1 + j];
+    if (loss_trace) for (int it = 0; it < n_eval; ++it) loss_trace[it] = h[8 * (size_t)it];
+    if (pose_out) std::memcpy(pose_out, h + 8 * (size_t)n_eval, 64);
+    if (dump) {
+        for (size_t i = 0; i < (size_t)n_rays * 64; ++i) {
+            const float* q = h_dbg.data() + 14 * i;
+            if (dump->x_o) std::memcpy(dump->x_o + 3 * i, q, 12);
+            if (dump->x_c) std::memcpy(dump->x_c + 3 * i, q + 3, 12);
+            if (dump->t) dump->t[i] = q[6];
+            if (dump->raw) std::memcpy(dump->raw + 4 * i, q + 7, 16);
+            if (dump->dldx) std::memcpy(dump->dldx + 3 * i, q + 11, 12);
+        }
+        if (dump->count) std::memcpy(dump->count, h_cnt.data(), 4 * (size_t)n_rays);
+    }
+    return MON_OK;
+}
+
 int model_get_params(Model& m, int which, void* dst, size_t bytes) {
     const void* src = nullptr; size_t need = 0;
     if (which == 0 && m.P.rec) {                             // chunk records: the master weights through a staging buffer

@@ -357,6 +357,49 @@ __attribute__((weak)) void launch_pose_grad(hipStream_t s, const LevelFast& lt, 
         int build_image, const PoseGradArgs& p, const float* level_w);
 __attribute__((weak)) void launch_pose_update(hipStream_t s, const float* partials, uint32_t n_parts, float inv_n, float* out, float* trace, uint32_t it, int step, float lr_t,
         float lr_r, float* pose, float* moments);
+// Camera refinement against a scene of objects (mon_scene_pose_loss / mon_scene_refine_camera, kernels_scene_pose.hip).  Per chunk of `cap` rays:
+// k_scene_pose_rays (targets, every object's ray record under the Twc in device memory) -> per object k_scene_pose_obj<.., BWD = false> (its sample lists, the
+// scene render's EMIT format) -> k_scene_composite_grad (merge, loss, composite backward: {dL/dalpha, w} into every list slot, {G_rgb, l} per ray, loss
+// partials per workgroup) -> per object k_scene_pose_obj<.., BWD = true> (MLP backward + position gradient, one partial row of 8 floats per workgroup);
+// per evaluation k_scene_pose_update (rows -> grad6 in the camera frame, Adam, Twc <- Twc exp(delta^)).
+constexpr uint32_t kSceneLossParts = 4096;
+constexpr uint32_t scene_composite_grad_lds(uint32_t n_lists) { return n_lists * (2u * kSceneListLen + 28u); }
+struct SceneObjConst { float Tow[16]; Aabb aabb; uint32_t instance_id; uint32_t pad; };
+struct ScenePoseRayArgs {
+    const mon_frame_bbox* boxes; const uint32_t* prefix;      // the boxes and the exclusive prefix sums of their areas
+    uint32_t n_obs, n_rays, ray0, total, drawn, iteration; uint64_t seed;
+    DatasetPtrs ds; const SceneObjConst* objs; uint32_t n_objs, cap; const float* pose;
+    float4* rec; float* mstar; float4* ray;                   // [n_objs][cap][3], [n_objs][cap], [cap][3]
+};
+struct ScenePoseObjArgs {
+    const float4* rec; uint32_t n_rays, ray0;                 // this object's records of the chunk; ray0 = the chunk's first ray (debug dump rows)
+    uint64_t seed; uint32_t stream, step;                     // jitter of sample k: rand01(seed, stream, step, base + k)
+    float* t; float4* attr; uint32_t* cnt;                    // this object's lists of the chunk [cap][64], counts [cap]
+    const float2* gw; const float4* grow; const float4* ray;  // {dL/dalpha, w} [cap][64] of this object; per ray {G_rgb, l}; the rays' rows
+    float inv_n; float* partials;
+    float* dbg;                                               // mon_debug_scene_pose_samples: [ray][64][14] x_o, x_c, t, raw, dL/dx, or nullptr
+    const float* level_w;                                     // nullptr, or the level weights of this evaluation (the object reads its first L)
+};
+struct SceneCompGradArgs {
+    uint32_t n_rays, n_lists, cap;
+    const float* t; const float4* attr; const uint32_t* cnt;  // the lists, as launch_scene_composite takes them
+    const float* mstar; const float4* ray;                    // m*_j [n_lists][cap]; per ray {c*, d*} {dn, M*, ..} {..}
+    float w_rgb, w_mask, w_depth, huber;
+    float2* gw; float4* grow; float* loss_part;               // outputs; loss_part[workgroup]
+    float* out_W; float* out_D;                               // mon_debug_scene_composite_grad: W [n_lists][cap], D [cap], or nullptr
+};
+struct ScenePoseUpdateArgs {
+    const float* partials; uint32_t n_objs, n_rows, row_stride;   // object j's rows at j * row_stride * 8
+    const float* loss_part; uint32_t n_loss_parts;
+    const SceneObjConst* objs; float inv_n; float* out; uint32_t it; int step; float lr_t, lr_r; float* pose; float* moments;
+};
+// (weak, as the pose launchers: the host-only ThreadSanitizer build links without the kernels)
+__attribute__((weak)) void launch_scene_pose_rays(hipStream_t s, const ScenePoseRayArgs& a);
+__attribute__((weak)) void launch_scene_pose_obj(hipStream_t s, const LevelFast& lt, const NetDims& nd, const ObjectConst& oc, const uint16_t* params, uint16_t* frag_image,
+        int build_image, int backward, uint32_t grid, const ScenePoseObjArgs& p);
+__attribute__((weak)) uint32_t scene_comp_grad_grid(uint32_t n_rays);
+__attribute__((weak)) void launch_scene_composite_grad(hipStream_t s, const SceneCompGradArgs& a);
+__attribute__((weak)) void launch_scene_pose_update(hipStream_t s, const ScenePoseUpdateArgs& a);
 // inference on feature-planar level tiles (kernels_tilerender.hip): Render / RenderVideo, GetDensityOnGrid, mesh vertex colours
 constexpr uint32_t kTileChunkJobs = 32768;          // rays (jobs of 2S = 64 samples) per chunk of the tile render
 bool tile_render_supported(const LevelTable& lt, const NetDims& nd);
@@ -517,6 +560,13 @@ bool model_has_snapshot(Model& m);      // the object has an inference side and 
 struct PoseDump { float* x; float* raw; float* dldx; };
 int pose_refine(Model& m, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params& p, int iters,
                 uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const PoseDump* dump, const float* level_w = nullptr);
+// Camera refinement against a scene of objects (mon_scene_pose_loss / mon_scene_refine_camera): pose_refine's conventions for iters, iteration, the outputs
+// and level_w (rows of Lmax = the largest n_levels among the objects; object j reads its first L_j).  scene_pose_check: every MON_ERR_ARG of the call, no
+// device work.  dump (mon_debug_scene_pose_samples, may be nullptr): object k's share per drawn ray, host arrays [ray][64][3 | 3 | 1 | 4 | 3] + count [ray].
+struct ScenePoseDump { uint32_t k; float* x_o; float* x_c; float* t; float* raw; float* dldx; uint32_t* count; };
+int scene_pose_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16, const mon_pose_refine_params* p);
+int scene_pose(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16, const mon_pose_refine_params& p, int iters,
+               uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const ScenePoseDump* dump, const float* level_w = nullptr);
 uint32_t pose_n_rays(const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params& p);      // rays of one evaluation
 int pose_c2f_check(const mon_pose_c2f_params* c);                                                    // MON_ERR_ARG for a NULL or bad schedule
 std::vector<float> pose_c2f_table(const mon_pose_c2f_params& c, int n_levels, int iters);          // [iters][n_levels]: mon_pose_c2f_weights of every step
