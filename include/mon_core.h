@@ -346,6 +346,35 @@ int mon_object_info_get(mon_object* obj, mon_object_info* info);
  * which: 0 fp32 master, 1 fp16 working copy, 2 fp16 EMA (inference) copy. */
 int mon_object_get_params(mon_object* obj, int which, void* dst, size_t bytes);
 int mon_object_set_params(mon_object* obj, const float* master, size_t n);
+/* ---- Checkpoints (the reference has no save / load; opt-in, new): one object per file, little-endian, versioned, independent of how
+ * the build lays the optimizer state out in device memory.  A saved object, loaded in another process onto any device, is the original bit for bit --
+ * parameters, Adam moments and step counters, EMA (a pending lazy EMA stays pending), learning rate, counters, the training occupancy grid and its refresh
+ * schedule, optionally the box list -- and training it further gives bit for bit what the uninterrupted object would have had.  Not stored: dataset frames
+ * and poses, meshes, render-skip switch and grids, profiles, process-wide options (mon_set_option: set them as they were before loading).
+ * Status codes of the three calls: MON_ERR_ARG a NULL argument, unknown flag bits; MON_ERR_IO unreadable, truncated, bad magic, newer version, any CRC
+ * mismatch, sizes inconsistent with the config, invalid config; MON_ERR_STATE as listed per call. */
+typedef struct mon_checkpoint_info {
+    uint32_t version; mon_config cfg; int32_t class_id; float Tow[16], aabb_min[3], aabb_max[3];
+    uint32_t n_params, n_mlp_params, n_grid_params, train_step, iter, n_boxes; int32_t backend;
+    uint32_t has_occupancy, lazy_ema; uint64_t file_bytes;
+} mon_checkpoint_info;
+/* host only, no device: header, object block and section table checked (CRC, sizes against the file length, the config through mon_object_create's checks,
+ * n_params recomputed).  verify != 0 also checks every section's CRC. */
+int mon_checkpoint_read_info(const char* path, int verify, mon_checkpoint_info* out);
+/* Writes <path>.tmp and renames it: a crash never leaves a truncated file under the final name.  Read-only: nothing about the object changes (parameters,
+ * a pending lazy EMA, render-skip caches, snapshots, counters, the weights stamp).  Runs on the train stream; the caller serialises against training, as for
+ * mon_object_render.  Streams through one pinned and one device staging buffer of at most 32 MB each.  MON_ERR_STATE: an object in the XORWOW "same inputs"
+ * mode (its generator state is not stored), and between the stage-wise calls of mon_object_train_stages.  A grid pinned through
+ * mon_debug_set_train_occupancy is saved as a grid; the pin is not. */
+int mon_object_save(mon_object* obj, const char* path);
+/* Everything mon_checkpoint_read_info(verify = 0) checks, the step-counter width and the box list (its CRC, and with MON_LOAD_BOXES every box against ds)
+ * are judged before any device work; the object is then created on ds's device whichever device saved it and its state streamed in, each section's CRC
+ * checked as it streams (a mismatch frees the half-built object: MON_ERR_IO).  Its derived images are rebuilt as mon_object_set_params does, the backend
+ * restored and a snapshot published (from the EMA once a step has been taken).  *out = NULL on any failure.  flags: MON_LOAD_BOXES restores the box list (MON_ERR_STATE when ds lacks one of its frames or a box does not fit ds's images); without it
+ * the object has no boxes -- it renders, meshes and refines, and trains once boxes are added.  use_depth follows mon_object_create's rule
+ * (cfg.use_depth && the dataset's).  MON_ERR_STATE also for a file whose step-counter width (16 / 32 bits) is not this build's for that config. */
+#define MON_LOAD_BOXES 1u
+int mon_object_load(mon_dataset* ds, const char* path, uint32_t flags, mon_object** out);
 /* Test hooks: split one iteration so intermediate buffers can be compared with the oracle.
  * stage bits: 1 GenerateBatch, 2 forward+backward, 4 optimizer_step(+step counter). */
 int mon_object_train_stages(mon_object* obj, int stage_bits);
@@ -425,6 +454,18 @@ int mon_online_refine_pose_c2f(mon_online* mgr, size_t idx, const mon_frame_bbox
  * objects span more than one device (as mon_online_render_scene). */
 int mon_online_refine_camera(mon_online* mgr, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, const mon_pose_c2f_params* c,
                              float* Twc16_inout, float* loss_trace);
+/* The object map as checkpoints: <dir>/map.txt, one line "index file class_id" per object, and one mon_object_save file per object next to it.  Each
+ * object's model lock is taken in turn (as mon_online_update_dataset does), so the call is safe while the objects train and every file is one consistent
+ * object; the map is NOT one global cut -- object 3 may be saved some training slices later than object 0. */
+/* dir is created if missing (its parent must exist: MON_ERR_IO otherwise).  When an object's save fails, the files this call wrote are removed and an
+ * earlier map.txt is left as it was.  mon_online_load_map reads map.txt in line order: the index column must count up from line to line and class_id must be
+ * the file's own (MON_ERR_IO otherwise); the objects get the manager's next free indices. */
+int mon_online_save_map(mon_online* mgr, const char* dir);
+/* Valid after mon_online_dataset_init: appends the map's objects, each with its training thread, as mon_online_create_nerf does -- object k of the call on
+ * device k mod nGPU continuing the manager's rotation, no box inflation (the file holds the box in use).  flags as mon_object_load: with MON_LOAD_BOXES the
+ * boxes count as uploaded, so the "> 10 boxes" gate of training behaves as before the save (the frames they name must have been handed over with
+ * mon_online_new_frame first).  *n_loaded (may be NULL) = objects appended; on an error the objects loaded before it stay. */
+int mon_online_load_map(mon_online* mgr, const char* dir, uint32_t flags, size_t* n_loaded);
 /* RenderNeRFsTest(out_path, idx, stamps, boxes, Twcs, radius) -> NeRF::RenderTestImg (nerf.cu:255-404): test images + test.txt +
  * train.txt + the 60-view 360-degree video (RenderVideo, nerf_model.cu:1832-1990) + obj.ply under <out_path>/<id>/ */
 int mon_online_render_nerfs_test(mon_online* mgr, const char* out_path, size_t idx, const char* const* timestamps, const mon_frame_bbox* boxes,

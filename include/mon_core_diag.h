@@ -81,6 +81,9 @@ int mon_debug_scene_pose_samples(mon_object* const* objs, size_t n_objs, int sid
 int mon_debug_scene_composite_grad(int device, uint32_t n_rays, uint32_t n_lists, const float* t, const float* alpha, const float* rgb, const uint32_t* count,
                                    const float* cstar, const float* mstar, const float* dstar, const float* dn, float w_rgb, float w_mask, float w_depth,
                                    float huber, float* out_l, float* out_W, float* out_D, float* out_dalpha, float* out_dc);
+/* HIP-event time of the pack / unpack kernels of mon_object_save / mon_object_load calls made by this thread (tools/checkpoint_timing.py): enable != 0
+ * starts collecting -- each kernel is bracketed by two events --, *kernel_ms (may be NULL) = the sum since the last call, which is then cleared. */
+int mon_debug_checkpoint_timing(int enable, double* kernel_ms);
 
 #ifdef __cplusplus
 }

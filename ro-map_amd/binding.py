@@ -49,6 +49,28 @@ class PoseC2FParams(C.Structure):
     _fields_ = [("level_start", C.c_float), ("level_end", C.c_float), ("ramp", C.c_float)]
 
 
+class CheckpointInfo(C.Structure):
+    """mon_checkpoint_info (include/mon_core.h): what mon_checkpoint_read_info reports of a checkpoint file, host only."""
+    _fields_ = [("version", C.c_uint32), ("cfg", MonConfig), ("class_id", C.c_int32), ("Tow", C.c_float * 16), ("aabb_min", C.c_float * 3),
+                ("aabb_max", C.c_float * 3), ("n_params", C.c_uint32), ("n_mlp_params", C.c_uint32), ("n_grid_params", C.c_uint32),
+                ("train_step", C.c_uint32), ("iter", C.c_uint32), ("n_boxes", C.c_uint32), ("backend", C.c_int32), ("has_occupancy", C.c_uint32),
+                ("lazy_ema", C.c_uint32), ("file_bytes", C.c_uint64)]
+
+
+MON_LOAD_BOXES = 1
+
+
+def checkpoint_info(path, verify=True):
+    """mon_checkpoint_read_info: the header, object block and section table of a checkpoint, checked on the host (no device); verify also checks every
+    section's CRC.  Raises MonError (code 4) for anything damaged."""
+    i = CheckpointInfo(); _check(lib().mon_checkpoint_read_info(os.fsencode(path), int(bool(verify)), C.byref(i))); return i
+
+
+def checkpoint_timing(enable=True):
+    """(diagnostics library) HIP-event milliseconds of the pack / unpack kernels of this thread's saves and loads since the last call; enable starts / stops."""
+    ms = C.c_double(0); _check(diag_lib().mon_debug_checkpoint_timing(int(bool(enable)), C.byref(ms))); return ms.value
+
+
 class MonProfile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8)]
 
@@ -160,6 +182,11 @@ _SIGS = {
             C.c_void_p, C.c_void_p]),
     "mon_online_refine_camera": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams), C.POINTER(PoseC2FParams), C.c_void_p,
             C.c_void_p]),
+    "mon_checkpoint_read_info": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p]),
+    "mon_object_save": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "mon_object_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "mon_online_save_map": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "mon_online_load_map": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_size_t)]),
 }
 
 
@@ -178,6 +205,7 @@ _DIAG_SIGS = {
     "mon_debug_occupancy_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "mon_debug_set_train_occupancy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mon_debug_set_render_grid": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "mon_debug_checkpoint_timing": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
     "mon_debug_scene_samples": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, MonBBox, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_debug_scene_composite": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -467,6 +495,20 @@ class ObjectNeRF:
     def add_boxes(self, boxes):
         b = np.ascontiguousarray(boxes, np.uint32).reshape(-1, 5)
         _check(lib().mon_object_add_boxes(self.h, _p(b), b.shape[0]))
+
+    def save(self, path):
+        """mon_object_save: the whole object -- parameters, optimizer state, EMA, counters, occupancy grid, boxes -- as one checkpoint file (written to
+        <path>.tmp, then renamed).  Read-only; serialise against training as for render."""
+        _check(lib().mon_object_save(self.h, os.fsencode(path)))
+
+    @classmethod
+    def load(cls, dataset, path, with_boxes=True):
+        """mon_object_load: the saved object on `dataset`'s device, bit for bit; with_boxes restores the box list (the dataset must hold its frames)."""
+        h = C.c_void_p()
+        _check(lib().mon_object_load(dataset.h, os.fsencode(path), MON_LOAD_BOXES if with_boxes else 0, C.byref(h)))
+        o = cls.__new__(cls); o.h = h; o.ds = dataset
+        o.cfg = MonConfig(); _check(lib().mon_object_get_config(h, C.byref(o.cfg))); o.R, o.S = o.cfg.rays_per_batch, o.cfg.n_samples
+        return o
 
     def train(self, iters):
         loss = C.c_float(0); _check(lib().mon_object_train(self.h, iters, C.byref(loss))); return loss.value
@@ -792,6 +834,15 @@ class OnlineManager:
         box, out = _scene_outputs(rect); pose = np.ascontiguousarray(Twc16, np.float32)
         _check(lib().mon_online_render_scene(self.h, box, _p(pose), *[_p(a) for a in out]))
         return out
+
+    def save_map(self, path):
+        """mon_online_save_map: <path>/map.txt + one checkpoint per object, each under its own model lock (safe while they train; not one global cut)."""
+        _check(lib().mon_online_save_map(self.h, os.fsencode(path)))
+
+    def load_map(self, path, with_boxes=True):
+        """mon_online_load_map (after dataset_init, and after new_frame of the frames the boxes name): appends the map's objects with their training
+        threads; returns how many."""
+        n = C.c_size_t(0); _check(lib().mon_online_load_map(self.h, os.fsencode(path), MON_LOAD_BOXES if with_boxes else 0, C.byref(n))); return n.value
 
     def refine_pose(self, idx, obs, Tow16, params=None):
         """mon_online_refine_pose: object idx's published snapshot, safe while the manager trains; returns (refined Tow16, loss trace)."""

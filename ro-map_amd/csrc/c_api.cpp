@@ -254,6 +254,14 @@ int mon_object_info_get(mon_object* o, mon_object_info* info) {
 }
 int mon_object_get_params(mon_object* o, int which, void* dst, size_t bytes) { REQUIRE(o, "object"); return model_get_params(*o->m, which, dst, bytes); }
 int mon_object_set_params(mon_object* o, const float* master, size_t n) { REQUIRE(o, "object"); return model_set_params(*o->m, master, n); }
+int mon_checkpoint_read_info(const char* path, int verify, mon_checkpoint_info* out) { return checkpoint_read_info(path, verify, out); }
+int mon_object_save(mon_object* o, const char* path) { REQUIRE(o, "object"); REQUIRE(path, "path"); return model_save(*o->m, path); }
+int mon_object_load(mon_dataset* ds, const char* path, uint32_t flags, mon_object** out) {
+    if (out) *out = nullptr;
+    REQUIRE(ds, "dataset"); REQUIRE(path, "path"); REQUIRE(out, "out"); Model* m = nullptr;
+    const int rc = model_load(ds->d, path, flags, &m); if (rc) return rc;
+    *out = new mon_object{ m }; return MON_OK;
+}
 int mon_object_set_backend(mon_object* o, int backend) {
     REQUIRE(o, "object");
     if (backend == 1 && !fused_supported(o->m->nd, o->m->oc.S, o->m->oc.R)) { set_error("fused backend does not support this network shape");

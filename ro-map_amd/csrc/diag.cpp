@@ -164,6 +164,7 @@ int mon_debug_acc_layout(int epad, int W, int NH, int L, int* param, int* n_cols
 }
 int mon_selftest_mfma(int device, const uint16_t* A, const uint16_t* B, float* D) { REQUIRE(A, "A"); REQUIRE(B, "B"); REQUIRE(D, "D");
     return selftest_mfma(device, A, B, D); }
+int mon_debug_checkpoint_timing(int enable, double* kernel_ms) { return mon::checkpoint_timing(enable, kernel_ms); }
 int mon_debug_occupancy_state(mon_object* o, uint32_t out[2]) {
     if (!o || !o->m || !out) { mon::set_error("debug_occupancy_state: null argument"); return MON_ERR_ARG; }
     out[0] = o->m->occ_refreshed_iter; out[1] = o->m->occ_next_refresh; return MON_OK;

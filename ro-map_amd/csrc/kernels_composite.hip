@@ -1,7 +1,7 @@
 // kernels_composite.hip -- volumetric compositing and the hand-derived loss gradient (backend 0).
 //   VolumeRender                        CORE/src/nerf_model.cu:735-815
 //   VolumeRenderGradient_No_Compacted   :817-954   (+ the dloss_dout memset :1578, folded in)
-//   SumLoss                             :1231-1253 (block reduce + one atomic)
+//   SumLoss                             :1231-1253 (k_loss_sum: the per-ray losses added in a fixed order by one workgroup, no atomics)
 //   VolumeRender_Render                 :1134-1229
 // One thread per ray, like the reference; the fused backend does the same arithmetic with one
 // wavefront lane per sample and wave scans (kernels_fused.hip).
@@ -61,12 +61,8 @@ __global__ void __launch_bounds__(1024) k_composite_grad_wave(BatchPtrs b, Objec
         if (n == 0u) { b.rgb_ray[3 * i] = rgb0; b.rgb_ray[3 * i + 1] = rgb1; b.rgb_ray[3 * i + 2] = rgb2; b.depth_ray[i] = dep; b.mask_ray[i] = mask;
             b.loss_ray[i] = loss; }
     }
-    // one atomic per WORKGROUP (its 32 rays' losses; one per wave was 2048 adds into one address: most of the kernel's 28 us)
-    __shared__ float wsum[16];
-    const float l0 = lane_bcast(ok && n == 0u ? loss : 0.f, 0), l1 = lane_bcast(ok && n == 0u ? loss : 0.f, 32);
-    if (lane == 0u) wsum[threadIdx.x >> 6] = l0 + l1;
-    __syncthreads();
-    if (threadIdx.x == 0u) { float a = 0.f; for (uint32_t w = 0; w < (blockDim.x >> 6); ++w) a += wsum[w]; atomicAdd(&st->loss_sum, a); }
+    // (the batch's loss is summed from loss_ray by k_loss_sum, in a fixed order: float atomics into one word -- one per workgroup here, before that one per
+    // wave -- made the REPORTED loss of two identical runs differ in its last bits, with identical parameters)
 }
 
 __global__ void __launch_bounds__(64) k_composite_grad(BatchPtrs b, ObjectConst oc, DevState* __restrict__ st) {
@@ -134,10 +130,20 @@ __global__ void __launch_bounds__(64) k_composite_grad(BatchPtrs b, ObjectConst 
         const half4_t z = { (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f };
         for (; n < S; ++n) dout[n] = z;         // samples after the early-out keep zero gradient (:1578 memset)
     }
-    // wave reduce + one atomic per wave
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) loss += __shfl_down(loss, off);
-    if ((threadIdx.x & 63) == 0) atomicAdd(&st->loss_sum, loss);
+    // (summed by k_loss_sum)
+}
+
+// SumLoss (:1231-1253) in a FIXED order: thread t adds loss_ray[t], loss_ray[t + 256], ... and a tree over the 256 partial sums follows -- equal batches give
+// equal bits (a resumed checkpoint reports the loss the uninterrupted run reports).  One workgroup: R is a few thousand floats.
+__global__ void __launch_bounds__(256) k_loss_sum(const float* __restrict__ loss_ray, uint32_t R, DevState* __restrict__ st) {
+    if (st->n_valid == 0u) return;
+    __shared__ float part[256];
+    float a = 0.f;
+    for (uint32_t i = threadIdx.x; i < R; i += 256u) a += loss_ray[i];
+    part[threadIdx.x] = a;
+    __syncthreads();
+    for (uint32_t off = 128u; off >= 1u; off >>= 1) { if (threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off]; __syncthreads(); }
+    if (threadIdx.x == 0u) st->loss_sum = part[0];
 }
 
 // One thread per pixel: rays that missed the box, or ended with opacity <= 0.5, become white / 0 / 0.
@@ -169,10 +175,14 @@ __global__ void __launch_bounds__(256) k_extract_density(const uint16_t* __restr
     if (i < n) out[i] = (float)reinterpret_cast<const half_t*>(O)[(size_t)i * kOut + 3];
 }
 
+void launch_loss_sum(hipStream_t s, const float* loss_ray, uint32_t R, DevState* st) {
+    hipLaunchKernelGGL(k_loss_sum, dim3(1), dim3(256), 0, s, loss_ray, R, st);
+}
 void launch_composite_grad(hipStream_t s, const BatchPtrs& b, const ObjectConst& oc, DevState* st) {
     // (a lane per sample where a ray's samples are a half-wave; the one-thread-per-ray kernel otherwise)
     if (oc.S == 32u) hipLaunchKernelGGL(k_composite_grad_wave, dim3((oc.R * 32u + 1023u) / 1024u), dim3(1024), 0, s, b, oc, st);
     else hipLaunchKernelGGL(k_composite_grad, dim3((oc.R + 63) / 64), dim3(64), 0, s, b, oc, st);
+    launch_loss_sum(s, b.loss_ray, oc.R, st);
 }
 void launch_composite_render(hipStream_t s, const BatchPtrs& b, uint32_t S, uint32_t n_rays, float* rgb, float* depth, float* mask) {
     hipLaunchKernelGGL(k_composite_render, dim3((n_rays + 63) / 64), dim3(64), 0, s, b, S, n_rays, rgb, depth, mask);

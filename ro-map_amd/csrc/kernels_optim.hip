@@ -567,6 +567,94 @@ void launch_state_unpack(hipStream_t s, const float* rec, int which, void* dst, 
 void launch_state_pack_master(hipStream_t s, const float* master, float* rec, uint32_t n) {
     hipLaunchKernelGGL(k_state_pack_master, dim3(2048), dim3(256), 0, s, master, rec, n);
 }
+// Checkpoints (model.cpp: model_save / model_load): RANGES of chunks between the optimizer state and a bounded flat staging buffer, 16 bytes per lane.
+// `which` as above, plus 4 = the lazy EMA's step of each chunk (word 28 of its record).  dst / src index 0 is chunk `first_chunk`.  Pieces:
+//   master / m1 / m2  a chunk's 8 floats are two 16-byte pieces of its record: one lane each, one 16-byte load, one 16-byte store
+//   steps             a chunk's 8 uint16 counters are ONE 16-byte piece <-> 8 uint32 (two 16-byte pieces of the flat array); one lane per chunk.  The same
+//                     piece is the unit of the array layout's 16-bit counters, so the base and stride of the 16-byte pieces are arguments: records
+//                     (rec + 24 floats, 8 pieces apart) or ParamPtrs::steps16 (1 piece apart)
+//   ema_step          one dword per chunk: a lane gathers four chunks' words into one 16-byte store (or scatters one 16-byte load)
+// Streaming rule: grid-stride, at most 2048 workgroups (launch_optimizer's cap).
+typedef uint32_t ck_u32x4 __attribute__((ext_vector_type(4)));
+__global__ void __launch_bounds__(256) k_state_unpack_range(const float* __restrict__ rec, int which, ck_u32x4* __restrict__ dst, uint32_t first_chunk,
+        uint32_t n_chunks) {
+    const uint32_t n_pieces = 2u * n_chunks;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_pieces; i += gridDim.x * blockDim.x) {
+        const float* r = rec + 32u * (size_t)(first_chunk + (i >> 1)) + 8u * (uint32_t)which + 4u * (i & 1u);
+        dst[i] = *reinterpret_cast<const ck_u32x4*>(r);
+    }
+}
+__global__ void __launch_bounds__(256) k_state_pack_range(float* __restrict__ rec, int which, const ck_u32x4* __restrict__ src, uint32_t first_chunk,
+        uint32_t n_chunks) {
+    const uint32_t n_pieces = 2u * n_chunks;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_pieces; i += gridDim.x * blockDim.x) {
+        float* r = rec + 32u * (size_t)(first_chunk + (i >> 1)) + 8u * (uint32_t)which + 4u * (i & 1u);
+        *reinterpret_cast<ck_u32x4*>(r) = src[i];
+    }
+}
+// piece c of the 16-bit counters sits at base16[(first_chunk + c) * stride16]
+__global__ void __launch_bounds__(256) k_steps_unpack_range(const ck_u32x4* __restrict__ base16, uint32_t stride16, ck_u32x4* __restrict__ dst,
+        uint32_t first_chunk, uint32_t n_chunks) {
+    for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks; c += gridDim.x * blockDim.x) {
+        const ck_u32x4 v = base16[(size_t)(first_chunk + c) * stride16];
+        dst[2u * c] = ck_u32x4{ v[0] & 0xffffu, v[0] >> 16, v[1] & 0xffffu, v[1] >> 16 };
+        dst[2u * c + 1u] = ck_u32x4{ v[2] & 0xffffu, v[2] >> 16, v[3] & 0xffffu, v[3] >> 16 };
+    }
+}
+// (a value above 65535 cannot come out of a 16-bit object's file; it saturates like the counter itself)
+__global__ void __launch_bounds__(256) k_steps_pack_range(ck_u32x4* __restrict__ base16, uint32_t stride16, const ck_u32x4* __restrict__ src,
+        uint32_t first_chunk, uint32_t n_chunks) {
+    for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks; c += gridDim.x * blockDim.x) {
+        const ck_u32x4 a = src[2u * c], b = src[2u * c + 1u];
+        const auto pk = [](uint32_t lo, uint32_t hi) -> uint32_t { return (lo < 65535u ? lo : 65535u) | ((hi < 65535u ? hi : 65535u) << 16); };
+        base16[(size_t)(first_chunk + c) * stride16] = ck_u32x4{ pk(a[0], a[1]), pk(a[2], a[3]), pk(b[0], b[1]), pk(b[2], b[3]) };
+    }
+}
+__global__ void __launch_bounds__(256) k_ema_step_unpack_range(const float* __restrict__ rec, uint32_t* __restrict__ dst, uint32_t first_chunk,
+        uint32_t n_chunks) {
+    const uint32_t n_quads = (n_chunks + 3u) >> 2;
+    for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < n_quads; q += gridDim.x * blockDim.x) {
+        const uint32_t c = 4u * q; const uint32_t* w = reinterpret_cast<const uint32_t*>(rec) + 32u * (size_t)(first_chunk + c) + 28u;
+        if (c + 4u <= n_chunks) reinterpret_cast<ck_u32x4*>(dst)[q] = ck_u32x4{ w[0], w[32], w[64], w[96] };
+        else for (uint32_t j = 0; c + j < n_chunks; ++j) dst[c + j] = w[32u * j];
+    }
+}
+__global__ void __launch_bounds__(256) k_ema_step_pack_range(float* __restrict__ rec, const uint32_t* __restrict__ src, uint32_t first_chunk,
+        uint32_t n_chunks) {
+    const uint32_t n_quads = (n_chunks + 3u) >> 2;
+    for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < n_quads; q += gridDim.x * blockDim.x) {
+        const uint32_t c = 4u * q; uint32_t* w = reinterpret_cast<uint32_t*>(rec) + 32u * (size_t)(first_chunk + c) + 28u;
+        if (c + 4u <= n_chunks) { const ck_u32x4 v = reinterpret_cast<const ck_u32x4*>(src)[q]; w[0] = v[0]; w[32] = v[1]; w[64] = v[2]; w[96] = v[3]; }
+        else for (uint32_t j = 0; c + j < n_chunks; ++j) w[32u * j] = src[c + j];
+    }
+}
+static uint32_t range_blocks(uint32_t lanes) { const uint32_t b = (lanes + 255u) / 256u; return b < 1u ? 1u : (b > 2048u ? 2048u : b); }
+void launch_state_unpack_range(hipStream_t s, const float* rec, int which, void* dst, uint32_t first_chunk, uint32_t n_chunks) {
+    if (n_chunks == 0u) return;
+    if (which < 3) hipLaunchKernelGGL(k_state_unpack_range, dim3(range_blocks(2u * n_chunks)), dim3(256), 0, s, rec, which, static_cast<ck_u32x4*>(dst),
+            first_chunk, n_chunks);
+    else if (which == 3) hipLaunchKernelGGL(k_steps_unpack_range, dim3(range_blocks(n_chunks)), dim3(256), 0, s,
+            reinterpret_cast<const ck_u32x4*>(rec + 24), 8u, static_cast<ck_u32x4*>(dst), first_chunk, n_chunks);
+    else hipLaunchKernelGGL(k_ema_step_unpack_range, dim3(range_blocks((n_chunks + 3u) >> 2)), dim3(256), 0, s, rec, static_cast<uint32_t*>(dst), first_chunk,
+            n_chunks);
+}
+void launch_state_pack_range(hipStream_t s, float* rec, int which, const void* src, uint32_t first_chunk, uint32_t n_chunks) {
+    if (n_chunks == 0u) return;
+    if (which < 3) hipLaunchKernelGGL(k_state_pack_range, dim3(range_blocks(2u * n_chunks)), dim3(256), 0, s, rec, which, static_cast<const ck_u32x4*>(src),
+            first_chunk, n_chunks);
+    else if (which == 3) hipLaunchKernelGGL(k_steps_pack_range, dim3(range_blocks(n_chunks)), dim3(256), 0, s, reinterpret_cast<ck_u32x4*>(rec + 24), 8u,
+            static_cast<const ck_u32x4*>(src), first_chunk, n_chunks);
+    else hipLaunchKernelGGL(k_ema_step_pack_range, dim3(range_blocks((n_chunks + 3u) >> 2)), dim3(256), 0, s, rec, static_cast<const uint32_t*>(src), first_chunk,
+            n_chunks);
+}
+void launch_steps16_unpack_range(hipStream_t s, const uint16_t* steps16, void* dst, uint32_t first_chunk, uint32_t n_chunks) {
+    if (n_chunks) hipLaunchKernelGGL(k_steps_unpack_range, dim3(range_blocks(n_chunks)), dim3(256), 0, s, reinterpret_cast<const ck_u32x4*>(steps16), 1u,
+            static_cast<ck_u32x4*>(dst), first_chunk, n_chunks);
+}
+void launch_steps16_pack_range(hipStream_t s, uint16_t* steps16, const void* src, uint32_t first_chunk, uint32_t n_chunks) {
+    if (n_chunks) hipLaunchKernelGGL(k_steps_pack_range, dim3(range_blocks(n_chunks)), dim3(256), 0, s, reinterpret_cast<ck_u32x4*>(steps16), 1u,
+            static_cast<const ck_u32x4*>(src), first_chunk, n_chunks);
+}
 void launch_master_to_half(hipStream_t s, const float* master, uint16_t* half, uint32_t n) {
     hipLaunchKernelGGL(k_master_to_half, dim3(1024), dim3(256), 0, s, master, half, n);
 }

@@ -89,9 +89,7 @@ __global__ void __launch_bounds__(64) k_step_gradient(BatchPtrs b, ObjectConst o
             dout[n] = dv;
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) loss += __shfl_down(loss, off);
-    if ((threadIdx.x & 63) == 0) atomicAdd(&st->loss_sum, loss);
+    // (summed from loss_ray in a fixed order by k_loss_sum, as on the Step_No_Compacted schedule)
 }
 // fill_rollover (positions) + fill_rollover_and_rescale (gradients): slots n .. B - 1 repeat the compacted batch cyclically, the copies' gradients times n / B
 __global__ void __launch_bounds__(256) k_step_rollover(const uint32_t* __restrict__ steps, uint32_t R, uint32_t B, float* __restrict__ pts_c,
@@ -113,6 +111,7 @@ void launch_step_compaction(hipStream_t s, const BatchPtrs& b, const ObjectConst
     hipLaunchKernelGGL(k_step_count, dim3((R + 63) / 64), dim3(64), 0, s, b, oc, st, steps);
     hipLaunchKernelGGL(k_step_scan, dim3(1), dim3(1024), 0, s, steps, R, st);
     hipLaunchKernelGGL(k_step_gradient, dim3((R + 63) / 64), dim3(64), 0, s, b, oc, st, steps, pts_c, b.dO);
+    launch_loss_sum(s, b.loss_ray, R, st);
     hipLaunchKernelGGL(k_step_rollover, dim3((B + 255) / 256), dim3(256), 0, s, steps, R, B, pts_c, b.dO, st);
 }
 

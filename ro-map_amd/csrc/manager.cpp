@@ -4,6 +4,7 @@
 // (object file, thread body: 10 x 500 iterations) and the test-image writer of nerf.cu:255-349.
 // One std::thread per object, object k on device k mod nGPU (nerf.cu:27-33), one dataset replica per device.
 #include <sys/stat.h>
+#include <cerrno>
 #include <unistd.h>
 #include <algorithm>
 #include <atomic>
@@ -603,6 +604,69 @@ int mon_online_create_nerf(mon_online* h, int cls, const float* Tow16, const flo
     o->handle.m = o->model; o->device_objects = m.dev_objects[o->device].get(); m.dev_objects[o->device]->fetch_add(1);
     { std::lock_guard<std::mutex> l(m.mu_objs); *idx_out = m.objs.size(); m.objs.push_back(o); }
     m.threads.emplace_back(train_online_thread, o);                      // thread per object, nerf_manager.cu:259
+    return MON_OK;
+}
+// The object map as one checkpoint per object + map.txt (include/mon_core.h).  Each object under its own model lock, announced so that a training slice
+// lets the save in: every file is one consistent object, the map is not one cut through all of them.
+int mon_online_save_map(mon_online* h, const char* dir) {
+    REQ(h); REQ(dir); OnlineManager& m = *h->m;
+    if (::mkdir(dir, 0755) != 0 && errno != EEXIST) { set_error("save_map: cannot create directory %s", dir); return MON_ERR_IO; }
+    const std::string root = dir, map_tmp = root + "/map.txt.tmp";
+    std::ofstream f(map_tmp);
+    if (!f) { set_error("save_map: cannot write %s", map_tmp.c_str()); return MON_ERR_IO; }
+    const std::vector<OnlineObject*> objs = online_objects(m);
+    std::vector<std::string> written;                                     // removed again when a later object fails: no files without a map naming them
+    for (size_t i = 0; i < objs.size(); ++i) {
+        OnlineObject* o = objs[i]; if (!o->model) continue;
+        char name[64]; std::snprintf(name, sizeof(name), "object_%04zu.monckpt", i);
+        const std::string path = root + "/" + name;
+        int rc;
+        { AnnouncedLock lm(o, o->mu_model); rc = model_save(*o->model, path.c_str()); }
+        if (rc) { f.close(); std::remove(map_tmp.c_str()); for (const std::string& w : written) std::remove(w.c_str()); return rc; }
+        written.push_back(path);
+        f << i << " " << name << " " << o->cls << "\n";
+    }
+    f.close();
+    if (!f || std::rename(map_tmp.c_str(), (root + "/map.txt").c_str()) != 0) {
+        std::remove(map_tmp.c_str()); for (const std::string& w : written) std::remove(w.c_str());
+        set_error("save_map: cannot write %s/map.txt", dir); return MON_ERR_IO; }
+    return MON_OK;
+}
+int mon_online_load_map(mon_online* h, const char* dir, uint32_t flags, size_t* n_loaded) {
+    if (n_loaded) *n_loaded = 0;
+    REQ(h); REQ(dir); OnlineManager& m = *h->m;
+    if (flags & ~MON_LOAD_BOXES) { set_error("load_map: unknown flag bits %#x", flags & ~MON_LOAD_BOXES); return MON_ERR_ARG; }
+    if (m.ds.empty()) { set_error("load_map before DatasetInit"); return MON_ERR_STATE; }
+    const std::string root = dir;
+    std::ifstream f(root + "/map.txt");
+    if (!f) { set_error("load_map: cannot read %s/map.txt", dir); return MON_ERR_IO; }
+    std::string line; size_t n = 0; long last_idx = -1;
+    while (std::getline(f, line)) {
+        if (line.empty() || line[0] == '#') continue;
+        std::istringstream ls(line); size_t idx = 0; std::string name; int cls = 0;
+        if (!(ls >> idx >> name >> cls) || name.find('/') != std::string::npos) { set_error("load_map: bad line \"%s\" in %s/map.txt", line.c_str(), dir);
+            return MON_ERR_IO; }
+        const std::string path = root + "/" + name;
+        if ((long)idx <= last_idx) { set_error("load_map: index %zu does not count up in %s/map.txt", idx, dir); return MON_ERR_IO; }
+        last_idx = (long)idx;
+        mon_checkpoint_info info; int rc = checkpoint_read_info(path.c_str(), 0, &info); if (rc) return rc;
+        if (info.class_id != cls) { set_error("load_map: %s/map.txt says class %d for %s, the file holds class %d", dir, cls, name.c_str(), info.class_id);
+            return MON_ERR_IO; }
+        OnlineObject* o = new OnlineObject(); o->id = (int)m.objs.size(); o->device = m.next_dev; o->cls = info.class_id; o->iterations = m.iters;
+        std::memcpy(o->Tow, info.Tow, 64);
+        for (int a = 0; a < 3; ++a) { o->amin[a] = info.aabb_min[a]; o->amax[a] = info.aabb_max[a]; }      // the box in use: no inflation
+        std::vector<mon_frame_bbox> boxes;
+        rc = model_load(m.ds[o->device], path.c_str(), flags, &o->model, &boxes);
+        if (rc) { delete o; return rc; }
+        m.next_dev = (m.next_dev + 1) % m.n_dev;
+        if (flags & MON_LOAD_BOXES) { o->boxes = boxes; o->n_boxes = o->n_uploaded = boxes.size(); }      // uploaded already: the "> 10" gate counts them
+        if (o->boxes.size() < m.n_images) o->boxes.resize(m.n_images);
+        m.ds_mutex[o->device].emplace_back(new std::mutex()); o->dataset_mutex = m.ds_mutex[o->device].back().get();
+        o->handle.m = o->model; o->device_objects = m.dev_objects[o->device].get(); m.dev_objects[o->device]->fetch_add(1);
+        { std::lock_guard<std::mutex> l(m.mu_objs); m.objs.push_back(o); }
+        m.threads.emplace_back(train_online_thread, o);
+        ++n; if (n_loaded) *n_loaded = n;
+    }
     return MON_OK;
 }
 // :298-303 + UpdateFrameBBox nerf.cu:406-421

@@ -248,12 +248,20 @@ void mlp_forward_inference(Model& m, hipStream_t s, const uint16_t* params, cons
 
 // composite / loss gradient (kernels_composite.hip)
 void launch_composite_grad(hipStream_t s, const BatchPtrs& b, const ObjectConst& oc, DevState* st);
+// DevState::loss_sum = the sum of loss_ray[0 .. R) in a fixed order (one workgroup; a skipped batch keeps its zero)
+void launch_loss_sum(hipStream_t s, const float* loss_ray, uint32_t R, DevState* st);
 void launch_composite_render(hipStream_t s, const BatchPtrs& b, uint32_t S, uint32_t n_rays, float* rgb, float* depth, float* mask);
 void launch_extract_density(hipStream_t s, const uint16_t* O, float* out, uint32_t n);
 void launch_master_to_half(hipStream_t s, const float* master, uint16_t* half, uint32_t n);
 // ParamPtrs::rec -> a flat array (0 master, 1 m1, 2 m2, 3 step counters as uint32)
 void launch_state_unpack(hipStream_t s, const float* rec, int which, void* dst, uint32_t n);
 void launch_state_pack_master(hipStream_t s, const float* master, float* rec, uint32_t n);
+// checkpoints: chunks [first_chunk, first_chunk + n_chunks) of the records <-> a flat staging array whose element 0 is the range's first (which: 0 master,
+// 1 m1, 2 m2, 3 step counters as uint32, 4 the lazy EMA's per-chunk step); 16 bytes per lane.  steps16: the array layout's 16-bit counters <-> uint32
+void launch_state_unpack_range(hipStream_t s, const float* rec, int which, void* dst, uint32_t first_chunk, uint32_t n_chunks);
+void launch_state_pack_range(hipStream_t s, float* rec, int which, const void* src, uint32_t first_chunk, uint32_t n_chunks);
+void launch_steps16_unpack_range(hipStream_t s, const uint16_t* steps16, void* dst, uint32_t first_chunk, uint32_t n_chunks);
+void launch_steps16_pack_range(hipStream_t s, uint16_t* steps16, const void* src, uint32_t first_chunk, uint32_t n_chunks);
 void launch_copy_params(hipStream_t s, const uint16_t* src, uint16_t* dst, uint32_t n);
 void model_leave_lane(struct Model& m);      // non-training work goes to the object's own stream (model.cpp, training lanes)
 // host (pinned) images -> packed RGBA8 | instance << 24
@@ -570,6 +578,14 @@ int scene_pose(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, 
 uint32_t pose_n_rays(const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params& p);      // rays of one evaluation
 int pose_c2f_check(const mon_pose_c2f_params* c);                                                    // MON_ERR_ARG for a NULL or bad schedule
 std::vector<float> pose_c2f_table(const mon_pose_c2f_params& c, int n_levels, int iters);          // [iters][n_levels]: mon_pose_c2f_weights of every step
+// Checkpoints (mon_object_save / mon_object_load / mon_checkpoint_read_info).  boxes_out (may be nullptr): the box list the file holds,
+// whether or not it was restored (the online manager's bookkeeping).
+int checkpoint_read_info(const char* path, int verify, mon_checkpoint_info* out);
+int model_save(Model& m, const char* path);
+int model_load(Dataset* ds, const char* path, uint32_t flags, Model** out, std::vector<mon_frame_bbox>* boxes_out = nullptr);
+// HIP-event time of the pack / unpack kernels of the calling thread's saves and loads (tools/checkpoint_timing.py through the diagnostics library):
+// enable != 0 starts collecting (each kernel bracketed by events), *kernel_ms = the sum since the last call, then cleared
+int checkpoint_timing(int enable, double* kernel_ms);
 int model_publish_snapshot(Model& m);
 int model_render_snapshot(Model& m, mon_frame_bbox box, const float* pose16, int pose_is_Toc, float* rgb, float* depth, float* mask, uint32_t* snapshot_step);
 int level_table_build(const mon_config& c, LevelTable& lt, NetDims& nd, uint32_t& n_grid);
