@@ -312,6 +312,51 @@ int mon_scene_pose_loss(mon_object* const* objs, size_t n_objs, int side, const 
                         const mon_pose_refine_params* p, uint32_t iteration, const float* level_weights /* NULL or Lmax */, float* loss, float* grad6);
 int mon_scene_refine_camera(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p,
                             const mon_pose_c2f_params* c /* NULL: plain */, float* Twc16_inout, float* loss_trace);
+/* ---- wide-basin relocalisation: many candidate camera poses scored in one enqueue, the best few refined.
+ * mon_scene_pose_loss_batch.  losses[h] (n_poses floats) is, bit for bit, the loss mon_scene_pose_loss(objs, n_objs, side, obs, n_obs, Twc16s + 16 h, p,
+ * iteration, NULL, &loss, NULL) returns -- for every h, whatever else the batch holds and wherever in it the pose stands.  Pixels and jitter are keyed by
+ * (seed, iteration, ray), not by the pose: every hypothesis sees the same pixels and targets, only the rays differ.  Forward only: no gradient, no level
+ * weights, no Adam step.  Read-only and `side` exactly as mon_scene_pose_loss (side 1 pins each object's snapshot once for the whole batch).  The call is
+ * enqueued at once -- passes of floor(16384 / n) hypotheses of n rays each, K + 3 launches per pass for K objects, in the list workspace of one
+ * evaluation -- with one synchronisation and one copy home of n_poses floats.  No atomics: equal arguments give equal bits.
+ * Returns MON_ERR_ARG, before any device work, for n_poses outside 1..4096, a NULL Twc16s or losses, more than 16384 rays per hypothesis (rays_per_iter
+ * above 16384, or rays_per_iter = 0 with boxes of more than 16384 pixels together: a hypothesis is never split across passes) and everything
+ * mon_scene_pose_loss rejects; MON_ERR_STATE as that call. */
+int mon_scene_pose_loss_batch(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s,
+                              size_t n_poses, const mon_pose_refine_params* p, uint32_t iteration, float* losses /* n_poses */);
+/* mon_pose_hypotheses (host only).  n candidate poses around Twc16, 16 floats each, column-major.  Hypothesis 0 is Twc16 bit for bit.  Hypothesis h >= 1:
+ * u_k = the counter RNG's stream 6 keyed (seed, step = h, idx = k), k = 0..5; rho_i = max_trans (2 u_i - 1), i = 0..2; phi = max_rot_rad cbrt(u_3) e with e
+ * the unit vector of z = 2 u_4 - 1 and azimuth 2 pi u_5 (uniform in the ball of radius max_rot_rad); D = [R(phi), c - R(phi) c + rho] with R by Rodrigues
+ * and c = pivot_cam3, a point in the camera frame (NULL: the camera centre); Twc_h = Twc D.  A pure rotation leaves the pivot where it was, so objects
+ * around the pivot stay in view.  Computed in double, rounded once to float.  MON_ERR_ARG for a NULL Twc16 or Twc16s_out, n = 0 or above 4096, and a
+ * negative or non-finite max_rot_rad or max_trans. */
+int mon_pose_hypotheses(const float* Twc16, const float* pivot_cam3 /* NULL: the camera centre */, float max_rot_rad, float max_trans, size_t n,
+                        uint64_t seed, float* Twc16s_out /* 16 n */);
+/* mon_scene_relocalise.  Candidate 0 is the caller's own guess.  The rule, every step a public call:
+ *   1. ps = *p with rays_per_iter = r->score_rays.
+ *   2. S = mon_scene_pose_loss_batch(candidates, ps, r->score_iteration); S goes to `scores` (n_candidates floats, may be NULL).
+ *   3. The kept set: candidate 0, then the other candidates by ascending S (ties to the lower index, a non-finite S last), min(keep, n_candidates) in all.
+ *   4. Each kept candidate is refined by what mon_scene_refine_camera(objs, .., p, c, pose, NULL) does from it, one after the other; bit for bit that call's.
+ *   5. F = mon_scene_pose_loss_batch([refined_0 .. refined_{k-1}, start_0 .. start_{k-1}], ps, r->score_iteration).
+ *   6. The entry of the lowest finite F wins (ties to the earlier entry); its pose goes to Twc16_out.  No finite F: candidate 0 as given, refined = 0, MON_OK.
+ * So score_final <= F of candidate 0 as given and <= F of candidate 0 after plain mon_scene_refine_camera: by the common score the call is never worse than
+ * local refinement from the caller's guess.  2 + min(keep, n_candidates) synchronisations (one per scoring round and per refinement).  Read-only as
+ * mon_scene_refine_camera.  MON_ERR_ARG, before any device work, for NULL objs, obs, candidates, p, r or Twc16_out, n_candidates outside 1..4096,
+ * score_rays outside 1..16384, keep outside 1..16, a bad schedule c and everything mon_scene_refine_camera rejects; MON_ERR_STATE as that call. */
+typedef struct mon_reloc_params {
+    uint32_t score_rays;       /* pixels drawn per hypothesis when scoring; 1..16384 */
+    uint32_t keep;             /* hypotheses refined, 1..16; candidate 0 is always one of them */
+    uint32_t score_iteration;  /* the iteration key of both scoring rounds */
+} mon_reloc_params;
+typedef struct mon_reloc_result {
+    uint32_t best_candidate;   /* index into the candidates of the pose returned */
+    uint32_t refined;          /* 1: its refined pose won, 0: the candidate as given */
+    float    score_candidate0, score_best_candidate, score_final;   /* S[0], S[best_candidate], F of the pose returned */
+} mon_reloc_result;
+int mon_reloc_default(mon_reloc_params* r);     /* 256, 4, 0 */
+int mon_scene_relocalise(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16_candidates,
+                         size_t n_candidates, const mon_pose_refine_params* p, const mon_pose_c2f_params* c /* NULL: plain */, const mon_reloc_params* r,
+                         float* Twc16_out, mon_reloc_result* result /* may be NULL */, float* scores /* n_candidates, may be NULL */);
 /* NeRF_Model::GetDensityOnGrid (nerf_model.cu:2007-2048): raw density channel on an rx*ry*rz lattice. */
 int mon_object_density_grid(mon_object* obj, int rx, int ry, int rz, float* out_host);
 
@@ -454,6 +499,12 @@ int mon_online_refine_pose_c2f(mon_online* mgr, size_t idx, const mon_frame_bbox
  * objects span more than one device (as mon_online_render_scene). */
 int mon_online_refine_camera(mon_online* mgr, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, const mon_pose_c2f_params* c,
                              float* Twc16_inout, float* loss_trace);
+/* mon_scene_relocalise(side 1) over every object of the manager that has published weights: a resumed session's call for a frame whose pose is only
+ * roughly known (mon_online_load_map -> mon_online_new_frame -> mon_pose_hypotheses -> mon_online_relocalise -> mon_online_update_dataset), safe while the
+ * objects train.  Nothing of the manager changes.  MON_ERR_STATE as mon_online_refine_camera. */
+int mon_online_relocalise(mon_online* mgr, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16_candidates, size_t n_candidates,
+                          const mon_pose_refine_params* p, const mon_pose_c2f_params* c, const mon_reloc_params* r, float* Twc16_out,
+                          mon_reloc_result* result, float* scores);
 /* The object map as checkpoints: <dir>/map.txt, one line "index file class_id" per object, and one mon_object_save file per object next to it.  Each
  * object's model lock is taken in turn (as mon_online_update_dataset does), so the call is safe while the objects train and every file is one consistent
  * object; the map is NOT one global cut -- object 3 may be saved some training slices later than object 0. */

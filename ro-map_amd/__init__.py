@@ -9,5 +9,6 @@ from .binding import (MonConfig, MonBBox, MonError, Dataset, ObjectNeRF, default
                               generate_toc, frag_layout, acc_layout, device_mem_info, set_logical_devices, set_offline_schedule, set_option, get_option, diag_lib, diag_lib_path,
                               diag_symbols, yaml_number, MonRenderSkipStats, render_scene, scene_samples, scene_composite, PoseRefineParams, pose_refine_default,
                       PoseC2FParams, pose_c2f_default, pose_c2f_weights, scene_pose_loss, scene_refine_camera, scene_pose_samples,
-                      scene_composite_grad, CheckpointInfo, checkpoint_info, checkpoint_timing, MON_LOAD_BOXES,
+                      scene_composite_grad, RelocParams, RelocResult, reloc_default, scene_pose_loss_batch, pose_hypotheses, scene_relocalise,
+                      CheckpointInfo, checkpoint_info, checkpoint_timing, MON_LOAD_BOXES,
                       rccl_lib, rccl_lib_path, rccl_symbols, gather_plan, Gather)

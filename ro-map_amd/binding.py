@@ -49,6 +49,17 @@ class PoseC2FParams(C.Structure):
     _fields_ = [("level_start", C.c_float), ("level_end", C.c_float), ("ramp", C.c_float)]
 
 
+class RelocParams(C.Structure):
+    """mon_reloc_params (include/mon_core.h): pixels drawn per hypothesis when scoring, hypotheses refined, the iteration key of both scoring rounds."""
+    _fields_ = [("score_rays", C.c_uint32), ("keep", C.c_uint32), ("score_iteration", C.c_uint32)]
+
+
+class RelocResult(C.Structure):
+    """mon_reloc_result (include/mon_core.h): which candidate won, whether its refined pose did, and the scores S[0], S[best], F[winner]."""
+    _fields_ = [("best_candidate", C.c_uint32), ("refined", C.c_uint32), ("score_candidate0", C.c_float), ("score_best_candidate", C.c_float),
+                ("score_final", C.c_float)]
+
+
 class CheckpointInfo(C.Structure):
     """mon_checkpoint_info (include/mon_core.h): what mon_checkpoint_read_info reports of a checkpoint file, host only."""
     _fields_ = [("version", C.c_uint32), ("cfg", MonConfig), ("class_id", C.c_int32), ("Tow", C.c_float * 16), ("aabb_min", C.c_float * 3),
@@ -182,6 +193,14 @@ _SIGS = {
             C.c_void_p, C.c_void_p]),
     "mon_online_refine_camera": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams), C.POINTER(PoseC2FParams), C.c_void_p,
             C.c_void_p]),
+    "mon_scene_pose_loss_batch": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams),
+            C.c_uint32, C.c_void_p]),
+    "mon_pose_hypotheses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_size_t, C.c_uint64, C.c_void_p]),
+    "mon_reloc_default": (C.c_int, [C.POINTER(RelocParams)]),
+    "mon_scene_relocalise": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams),
+            C.POINTER(PoseC2FParams), C.POINTER(RelocParams), C.c_void_p, C.POINTER(RelocResult), C.c_void_p]),
+    "mon_online_relocalise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams), C.POINTER(PoseC2FParams),
+            C.POINTER(RelocParams), C.c_void_p, C.POINTER(RelocResult), C.c_void_p]),
     "mon_checkpoint_read_info": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p]),
     "mon_object_save": (C.c_int, [C.c_void_p, C.c_char_p]),
     "mon_object_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]),
@@ -867,6 +886,17 @@ class OnlineManager:
         _check(lib().mon_online_refine_camera(self.h, _p(b), b.shape[0], C.byref(prm), None if c is None else C.byref(c), _p(pose), _p(trace)))
         return pose, trace
 
+    def relocalise(self, obs, candidates, params=None, c2f=None, reloc=None):
+        """mon_online_relocalise: scene_relocalise on side 1 over every object with published weights, safe while they train.  Returns (Twc16, RelocResult,
+        scores); the manager is not changed (update_dataset stores a pose)."""
+        b, prm, rp = _pose_boxes(obs), _pose_params(params), _reloc_params(reloc)
+        cand = np.ascontiguousarray(candidates, np.float32).reshape(-1, 16)
+        c = None if c2f is None else _c2f_params(None if c2f is True else c2f)
+        pose = np.empty(16, np.float32); res = RelocResult(); scores = np.empty(cand.shape[0], np.float32)
+        _check(lib().mon_online_relocalise(self.h, _p(b), b.shape[0], _p(cand), cand.shape[0], C.byref(prm), None if c is None else C.byref(c),
+                                           C.byref(rp), _p(pose), C.byref(res), _p(scores)))
+        return pose, res, scores
+
     def close(self):
         if self.h:
             lib().mon_online_destroy(self.h); self.h = None
@@ -985,6 +1015,55 @@ def scene_refine_camera(objects, obs, Twc16, params=None, c2f=None, side=0):
     _check(lib().mon_scene_refine_camera(_handles(objects), len(objects), int(side), _p(b), b.shape[0], C.byref(prm), None if c is None else C.byref(c),
                                          _p(pose), _p(trace)))
     return pose, trace
+
+
+def scene_pose_loss_batch(objects, obs, Twc16s, params=None, side=0, iteration=0):
+    """mon_scene_pose_loss_batch: the scene_pose_loss of every pose of Twc16s (n, 16), bit for bit, in one enqueue.  Returns the n losses (float32)."""
+    b, prm = _pose_boxes(obs), _pose_params(params); poses = np.ascontiguousarray(Twc16s, np.float32).reshape(-1, 16)
+    losses = np.empty(poses.shape[0], np.float32)
+    _check(lib().mon_scene_pose_loss_batch(_handles(objects), len(objects), int(side), _p(b), b.shape[0], _p(poses), poses.shape[0], C.byref(prm),
+                                           int(iteration), _p(losses)))
+    return losses
+
+
+def pose_hypotheses(Twc16, n, max_rot, max_trans, pivot=None, seed=1):
+    """mon_pose_hypotheses (host only): n candidate poses (n, 16) around Twc16 -- hypothesis 0 the pose itself, the others turned by at most max_rot
+    radians about pivot (a point in the camera frame; None: the camera centre) and moved by at most max_trans per axis."""
+    pose = np.ascontiguousarray(Twc16, np.float32).reshape(16); out = np.empty((int(n), 16), np.float32)
+    pv = None if pivot is None else np.ascontiguousarray(pivot, np.float32).reshape(3)
+    _check(lib().mon_pose_hypotheses(_p(pose), _p(pv), float(max_rot), float(max_trans), int(n), int(seed), _p(out)))
+    return out
+
+
+def reloc_default(**overrides):
+    """mon_reloc_default, then any field overridden by keyword."""
+    r = RelocParams(); _check(lib().mon_reloc_default(C.byref(r)))
+    for k, v in overrides.items():
+        if k not in dict(RelocParams._fields_):
+            raise KeyError(k)
+        setattr(r, k, v)
+    return r
+
+
+def _reloc_params(reloc):
+    if reloc is None:
+        return reloc_default()
+    if isinstance(reloc, dict):
+        return reloc_default(**reloc)
+    return reloc
+
+
+def scene_relocalise(objects, obs, candidates, params=None, c2f=None, reloc=None, side=0):
+    """mon_scene_relocalise: every candidate (n, 16; candidate 0 the caller's own guess) scored in one batch, the best reloc.keep refined as
+    scene_refine_camera refines them, the refined poses and their starts scored again, the lowest score returned.  Returns (Twc16, RelocResult, scores of
+    the candidates); nothing about the objects changes."""
+    b, prm, rp = _pose_boxes(obs), _pose_params(params), _reloc_params(reloc)
+    cand = np.ascontiguousarray(candidates, np.float32).reshape(-1, 16)
+    c = None if c2f is None else _c2f_params(None if c2f is True else c2f)
+    pose = np.empty(16, np.float32); res = RelocResult(); scores = np.empty(cand.shape[0], np.float32)
+    _check(lib().mon_scene_relocalise(_handles(objects), len(objects), int(side), _p(b), b.shape[0], _p(cand), cand.shape[0], C.byref(prm),
+                                      None if c is None else C.byref(c), C.byref(rp), _p(pose), C.byref(res), _p(scores)))
+    return pose, res, scores
 
 
 def scene_pose_samples(objects, obs, Twc16, k, params=None, side=0, iteration=0, level_weights=None):

@@ -209,6 +209,66 @@ int mon_scene_refine_camera(mon_object* const* objs, size_t n_objs, int side, co
     if (rc == MON_OK) std::memcpy(Twc16_inout, pose, 64);
     return rc;
 }
+// ---- wide-basin relocalisation: batched scoring, candidate poses, the driver
+int mon_scene_pose_loss_batch(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s,
+                              size_t n_poses, const mon_pose_refine_params* p, uint32_t iteration, float* losses) {
+    REQUIRE(objs, "objs"); REQUIRE(Twc16s, "Twc16s"); REQUIRE(losses, "losses");
+    if (n_poses == 0 || n_poses > kSceneScoreMaxPoses) { set_error("scene pose batch: %zu poses (1 to %u)", n_poses, kSceneScoreMaxPoses); return MON_ERR_ARG; }
+    if (p && p->rays_per_iter > kSceneScoreMaxRays) { set_error("scene pose batch: rays_per_iter %u (at most %u per hypothesis)", p->rays_per_iter,
+        kSceneScoreMaxRays); return MON_ERR_ARG; }
+    std::vector<Model*> ms; int rc = scene_pose_models(objs, n_objs, ms); if (rc) return rc;
+    if ((rc = scene_pose_batch_check(ms.data(), n_objs, side, obs, n_obs, Twc16s, n_poses, p, losses))) return rc;
+    return scene_pose_batch(ms.data(), n_objs, side, obs, n_obs, Twc16s, n_poses, *p, iteration, losses);
+}
+int mon_pose_hypotheses(const float* Twc16, const float* pivot_cam3, float max_rot_rad, float max_trans, size_t n, uint64_t seed, float* Twc16s_out) {
+    REQUIRE(Twc16, "Twc16"); REQUIRE(Twc16s_out, "Twc16s_out");
+    if (n == 0 || n > kSceneScoreMaxPoses) { set_error("pose hypotheses: n %zu (1 to %u)", n, kSceneScoreMaxPoses); return MON_ERR_ARG; }
+    if (!std::isfinite(max_rot_rad) || max_rot_rad < 0.f || !std::isfinite(max_trans) || max_trans < 0.f) {
+        set_error("pose hypotheses: max_rot_rad %g, max_trans %g (finite, >= 0)", max_rot_rad, max_trans); return MON_ERR_ARG; }
+    float T0[16]; std::memcpy(T0, Twc16, 64);                                       // (Twc16s_out may begin at Twc16)
+    std::memcpy(Twc16s_out, T0, 64);
+    const double c[3] = { pivot_cam3 ? (double)pivot_cam3[0] : 0.0, pivot_cam3 ? (double)pivot_cam3[1] : 0.0, pivot_cam3 ? (double)pivot_cam3[2] : 0.0 };
+    const double two_pi = 6.283185307179586476925286766559;
+    for (size_t h = 1; h < n; ++h) {
+        double u[6]; for (uint32_t k = 0; k < 6; ++k) u[k] = (double)rand01(seed, kStreamPoseHyp, (uint32_t)h, k);
+        const double rho[3] = { max_trans * (2.0 * u[0] - 1.0), max_trans * (2.0 * u[1] - 1.0), max_trans * (2.0 * u[2] - 1.0) };
+        const double z = 2.0 * u[4] - 1.0, sxy = std::sqrt(std::max(0.0, 1.0 - z * z)), az = two_pi * u[5];
+        const double e[3] = { sxy * std::cos(az), sxy * std::sin(az), z }, th = (double)max_rot_rad * std::cbrt(u[3]);
+        // Rodrigues: R = I + sin(th) K + (1 - cos(th)) K^2, K = e^ (row-major here)
+        const double K[9] = { 0.0, -e[2], e[1], e[2], 0.0, -e[0], -e[1], e[0], 0.0 }, sn = std::sin(th), cs1 = 1.0 - std::cos(th);
+        double R[9];
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
+            double k2 = 0.0; for (int q = 0; q < 3; ++q) k2 += K[i * 3 + q] * K[q * 3 + j];
+            R[i * 3 + j] = (i == j ? 1.0 : 0.0) + sn * K[i * 3 + j] + cs1 * k2; }
+        double t[3]; for (int i = 0; i < 3; ++i) t[i] = c[i] - (R[i * 3] * c[0] + R[i * 3 + 1] * c[1] + R[i * 3 + 2] * c[2]) + rho[i];
+        float* o = Twc16s_out + 16 * h;                                               // Twc D, column-major
+        for (int col = 0; col < 3; ++col) { for (int row = 0; row < 3; ++row) {
+            double v = 0.0; for (int q = 0; q < 3; ++q) v += (double)T0[q * 4 + row] * R[q * 3 + col];
+            o[col * 4 + row] = (float)v; } o[col * 4 + 3] = 0.f; }
+        for (int row = 0; row < 3; ++row) o[12 + row] = (float)((double)T0[row] * t[0] + (double)T0[4 + row] * t[1] + (double)T0[8 + row] * t[2] + (double)T0[12 + row]);
+        o[15] = 1.f;
+    }
+    return MON_OK;
+}
+int mon_reloc_default(mon_reloc_params* r) {
+    REQUIRE(r, "params");
+    r->score_rays = 256; r->keep = 4; r->score_iteration = 0;
+    return MON_OK;
+}
+int mon_scene_relocalise(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16_candidates,
+                         size_t n_candidates, const mon_pose_refine_params* p, const mon_pose_c2f_params* c, const mon_reloc_params* r, float* Twc16_out,
+                         mon_reloc_result* result, float* scores) {
+    REQUIRE(objs, "objs"); REQUIRE(obs, "obs"); REQUIRE(Twc16_candidates, "candidates"); REQUIRE(p, "params"); REQUIRE(r, "reloc params");
+    REQUIRE(Twc16_out, "Twc16_out");
+    if (n_candidates == 0 || n_candidates > kSceneScoreMaxPoses) { set_error("relocalise: %zu candidates (1 to %u)", n_candidates, kSceneScoreMaxPoses);
+        return MON_ERR_ARG; }
+    if (r->score_rays == 0 || r->score_rays > kSceneScoreMaxRays) { set_error("relocalise: score_rays %u (1 to %u)", r->score_rays, kSceneScoreMaxRays);
+        return MON_ERR_ARG; }
+    if (r->keep == 0 || r->keep > kRelocMaxKeep) { set_error("relocalise: keep %u (1 to %u)", r->keep, kRelocMaxKeep); return MON_ERR_ARG; }
+    std::vector<Model*> ms; int rc = scene_pose_models(objs, n_objs, ms); if (rc) return rc;
+    if ((rc = scene_reloc_check(ms.data(), n_objs, side, obs, n_obs, Twc16_candidates, n_candidates, p, c, r, Twc16_out))) return rc;
+    return scene_relocalise(ms.data(), n_objs, side, obs, n_obs, Twc16_candidates, n_candidates, *p, c, *r, Twc16_out, result, scores);
+}
 int mon_pose_c2f_default(mon_pose_c2f_params* c) {
     REQUIRE(c, "params");
     c->level_start = 4.f; c->level_end = 5.f; c->ramp = 0.7f;

@@ -9,51 +9,11 @@
 namespace mon {
 
 // ------------------------------------------------------------------ k_scene_pose_rays
-// One thread per drawn ray of the chunk (global ray i = ray0 + r): the pixel as k_pose_rays draws it, its targets, and for every object j the ray
-// mon_object_render builds for that pixel under the candidate Twc (device memory) and the object's Tow, intersected with the object's box.
-// Per ray (3 x float4): {c*, d*} {|camera ray|, M*, 0, 0} {unit camera ray, 0}.  Per object and ray (3 x float4 at (j * cap + r) * 3): {o, t0} {d, t1}
-// {hit, jitter index base (bits), 0, 0}; m*_j at j * cap + r.
+// One thread per drawn ray of the chunk (global ray i = ray0 + r): scene_pose_ray (scene_device.h) under the candidate Twc in device memory.
 __global__ void __launch_bounds__(256) k_scene_pose_rays(ScenePoseRayArgs a) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= a.n_rays) return;
-    const uint32_t i = a.ray0 + r;
-    uint32_t p = i;
-    if (a.drawn) {
-        const uint64_t z = rand_mix(a.seed, kStreamPoseXY, a.iteration, i);
-        p = a.total <= (1u << 24) ? (uint32_t)(((z >> 40) * a.total) >> 24) : (uint32_t)(((z >> 32) * a.total) >> 32);
-    }
-    uint32_t lo = 0u, hi = a.n_obs - 1u;                                                // the box: last b with prefix[b] <= p
-    while (lo < hi) { const uint32_t mid = (lo + hi + 1u) >> 1; if (a.prefix[mid] <= p) lo = mid; else hi = mid - 1u; }
-    const mon_frame_bbox box = a.boxes[lo];
-    const uint32_t q = p - a.prefix[lo], x = box.x + q % box.w, y = box.y + q / box.w;
-    const size_t pix = ((size_t)box.FrameId * a.ds.K.H + y) * a.ds.K.W + x;
-    const uint32_t rgba = a.ds.rgba[pix], inst = rgba >> 24;
-    const float dstar = a.ds.depth ? a.ds.depth[pix] : 0.f;
-    const uint32_t base = a.drawn ? i * 64u : q * 64u;                                  // (2S = 64: the fused shapes)
-    float Twc[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) Twc[k] = a.pose[k];
-    float dn = 1.f, Mstar = 0.f;
-    for (uint32_t j = 0; j < a.n_objs; ++j) {
-        const SceneObjConst& oc = a.objs[j];
-        float o[3], d[3], t0 = 0.f, t1 = 0.f;
-        pixel_ray(a.ds.K, (float)x, (float)y, Twc, oc.Tow, false, o, d, dn);
-        const bool hit = ray_intersect(oc.aabb, o, d, t0, t1);
-        const float m = inst == oc.instance_id ? 1.f : 0.f;
-        Mstar = fmaxf(Mstar, m);
-        float4* rr = a.rec + 3 * ((size_t)j * a.cap + r);
-        rr[0] = make_float4(o[0], o[1], o[2], fmaxf(t0, 0.0f));
-        rr[1] = make_float4(d[0], d[1], d[2], t1);
-        rr[2] = make_float4(hit ? 1.f : 0.f, __builtin_bit_cast(float, base), 0.f, 0.f);
-        a.mstar[(size_t)j * a.cap + r] = m;
-    }
-    // the unit camera ray, as pixel_ray forms it
-    const float dc[3] = { ((float)x - a.ds.K.cx) / a.ds.K.fx, ((float)y - a.ds.K.cy) / a.ds.K.fy, 1.0f };
-    const float n = sqrtf(fmaf(dc[2], dc[2], fmaf(dc[1], dc[1], dc[0] * dc[0])));
-    float4* ray = a.ray + 3 * (size_t)r;
-    ray[0] = make_float4((float)(rgba & 0xffu) / 255.0f, (float)((rgba >> 8) & 0xffu) / 255.0f, (float)((rgba >> 16) & 0xffu) / 255.0f, dstar);
-    ray[1] = make_float4(n, Mstar, 0.f, 0.f);
-    ray[2] = make_float4(dc[0] / n, dc[1] / n, dc[2] / n, 0.f);
+    scene_pose_ray(a, r, a.ray0 + r, a.pose);
 }
 
 // ------------------------------------------------------------------ k_scene_pose_obj
@@ -217,10 +177,10 @@ __device__ __forceinline__ float suffix_add64(float v) {
     const float s = suffix_add32(v);
     return s + ((threadIdx.x & 32) ? 0.f : lane_bcast(s, 32));
 }
-// One wavefront (= one workgroup) per ray: k_scene_composite's compaction and merged order (scene_merge_lists), then the composite forward in blocks of 64
-// with a carried transmittance (each block's entry transmittance kept in LDS), the per-list weight sums W_j, the ray's loss
-//   l = w_rgb M* |r|^2 / 3 + w_mask sum_j (W_j - m*_j)^2 + w_depth M* [d* > 0] Huber(D - d*),
-// and the blocks again in reverse with a carried suffix sum: with q_i = G_rgb . (c_i - c*) + G_D t_i + 2 w_mask (W_j(i) - m*_j(i)),
+// One wavefront (= one workgroup) per ray: scene_composite_ray (scene_device.h; k_scene_composite's compaction and merged order, then the composite forward
+// in blocks of 64 with a carried transmittance, each block's entry transmittance kept in LDS, the per-list weight sums W_j and the ray's loss
+//   l = w_rgb M* |r|^2 / 3 + w_mask sum_j (W_j - m*_j)^2 + w_depth M* [d* > 0] Huber(D - d*)),
+// then the blocks again in reverse with a carried suffix sum: with q_i = G_rgb . (c_i - c*) + G_D t_i + 2 w_mask (W_j(i) - m*_j(i)),
 //   dL/dalpha_i = T_i q_i - sum_{n > i} w_n q_n / (1 - alpha_i)       (so that dL/dsigma_i = dt_i (T_{i+1} q_i - sum_{n > i} w_n q_n))
 // Every merged sample's list slot receives {dL/dalpha, w} (0, 0 from the cut on); the ray's row receives {G_rgb, l}.  The workgroup's rays' losses are summed
 // in ray order into loss_part[blockIdx.x].
@@ -239,73 +199,12 @@ __global__ void __launch_bounds__(64) k_scene_composite_grad(SceneCompGradArgs a
     const int lane = threadIdx.x;
     float loss_acc = 0.f;
     for (uint32_t ray = blockIdx.x; ray < a.n_rays; ray += gridDim.x) {
-        uint32_t na, n_tot;
-        scene_merge_lists(ray, n_lists, cap, a.t, a.cnt, lane, s_perm, s_id, s_c, s_tf, s_tl, s_w, na, n_tot);
-        const float4 tg = a.ray[3 * (size_t)ray], tg1 = a.ray[3 * (size_t)ray + 1];
-        const float cs[3] = { tg.x, tg.y, tg.z }, dstar = tg.w, dn = tg1.x, Mstar = tg1.y;
-        // ---- forward
-        float Tc = 1.f, res[3] = { 0.f, 0.f, 0.f }, dep = 0.f;
-        const uint32_t n_blocks = (n_tot + 63u) / 64u;
-        uint32_t n_done = 0u;                                                           // blocks composited (the cut lies in the last of them, or nowhere)
-        for (uint32_t blk = 0; blk < n_blocks; ++blk) {
-            const uint32_t pidx = blk * 64u + (uint32_t)lane;
-            float tv = 0.f, al = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f; uint32_t ac = ~0u;
-            if (pidx < n_tot) {
-                const uint32_t e = s_perm[pidx];
-                if ((e >> 6) < na) {
-                    ac = e >> 6;
-                    const size_t idx = ((size_t)s_id[ac] * cap + ray) * L2S + (e & 63u);
-                    const float4 v = a.attr[idx]; tv = a.t[idx]; al = v.x; c0 = v.y; c1 = v.z; c2 = v.w;
-                }
-            }
-            if (lane == 0) s_T[blk] = Tc;
-            const float omv = 1.f - al;
-            const float sc = scan_mul32(omv), lo = sc * Tc, mid = lane_bcast(lo, 31);
-            const float incl = lane < 32 ? lo : sc * mid;                              // (the second half-wave carries the first's transmittance)
-            float T = lane_prev(incl, Tc); if (lane == 0) T = Tc; if (lane == 32) T = mid;
-            const bool active = T >= kTransmittanceEps;
-            const int nact = __popcll(__ballot(active));
-            const float wgt = active ? al * T : 0.f;
-            const float x0 = scan_add32(wgt * (c0 - cs[0])), x1 = scan_add32(wgt * (c1 - cs[1])), x2 = scan_add32(wgt * (c2 - cs[2])), xd = scan_add32(wgt * tv);
-            res[0] += lane_bcast(x0, 31); res[1] += lane_bcast(x1, 31); res[2] += lane_bcast(x2, 31); dep += lane_bcast(xd, 31);
-            res[0] += lane_bcast(x0, 63); res[1] += lane_bcast(x1, 63); res[2] += lane_bcast(x2, 63); dep += lane_bcast(xd, 63);
-            // per-list weight sums: one reduction per list present in the block
-            unsigned long long pend = __ballot(ac != ~0u && wgt != 0.f);
-            while (pend) {
-                const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)ac, (int)__builtin_ctzll(pend));
-                const bool mine = ac == a0;
-                const float xs = scan_add32(mine ? wgt : 0.f);
-                const float sum = lane_bcast(xs, 31) + lane_bcast(xs, 63);
-                if (lane == 0) s_w[a0] += sum;
-                pend &= ~__ballot(mine);
-            }
-            Tc = nact > 0 ? lane_bcast(incl, nact > 0 ? nact - 1 : 0) : Tc;
-            n_done = blk + 1u;
-            if (nact < 64) break;                                                      // transmittance ran out inside this block
-        }
-        __syncthreads();
-        // ---- the ray's loss and the gradients of its terms
-        const float D = dep / dn;
-        const bool dep_on = a.w_depth != 0.f && Mstar != 0.f && dstar > 0.f;
-        float lmask = 0.f;                                                              // sum_j (W_j - m*_j)^2 over every list, in list order by wave
-        for (uint32_t g = 0; g < n_lists; g += 64u) {
-            const uint32_t k = g + (uint32_t)lane;
-            float term = 0.f;
-            if (k < n_lists) {
-                // compact index of list k, if it has one: binary search over s_id[0, na)
-                uint32_t lo2 = 0u, hi2 = na;
-                while (lo2 < hi2) { const uint32_t mid2 = (lo2 + hi2) >> 1; if (s_id[mid2] < k) lo2 = mid2 + 1u; else hi2 = mid2; }
-                const bool present = lo2 < na && s_id[lo2] == k;
-                const float Wk = present ? s_w[lo2] : 0.f, m = a.mstar[(size_t)k * cap + ray];
-                const float dW = Wk - m;
-                term = dW * dW;
-                if (present) s_q[lo2] = 2.f * a.w_mask * dW;
-                if (a.out_W) a.out_W[(size_t)k * cap + ray] = Wk;
-            }
-            lmask += wave_sum(term);
-        }
-        const float l = a.w_rgb * Mstar * (res[0] * res[0] + res[1] * res[1] + res[2] * res[2]) / 3.f + a.w_mask * lmask
-                + (dep_on ? a.w_depth * huber_f(D - dstar, a.huber) : 0.f);
+        SceneRayFwd f;
+        scene_composite_ray<true>(a, ray, lane, s_perm, s_id, s_c, s_tf, s_tl, s_w, s_q, s_T, f);
+        const uint32_t na = f.na, n_tot = f.n_tot, n_blocks = f.n_blocks, n_done = f.n_done;
+        const float cs[3] = { f.cs[0], f.cs[1], f.cs[2] }, dstar = f.dstar, dn = f.dn, Mstar = f.Mstar, D = f.D, l = f.l;
+        const float res[3] = { f.res[0], f.res[1], f.res[2] };
+        const bool dep_on = f.dep_on;
         loss_acc += l;
         const float Gc[3] = { a.w_rgb * Mstar * 2.f * res[0] / 3.f, a.w_rgb * Mstar * 2.f * res[1] / 3.f, a.w_rgb * Mstar * 2.f * res[2] / 3.f };
         const float GD = dep_on ? a.w_depth * clamp_f(D - dstar, -a.huber, a.huber) / dn : 0.f;

@@ -771,6 +771,22 @@ int mon_online_refine_camera(mon_online* h, const mon_frame_bbox* obs, size_t n_
     if (rc == MON_OK) std::memcpy(Twc16_inout, pose, 64);
     return rc;
 }
+// wide-basin relocalisation against every object of the manager that has published weights (mon_scene_relocalise on side 1, safe while they train); the
+// objects are chosen as mon_online_refine_camera chooses them.  Nothing of the manager changes.
+int mon_online_relocalise(mon_online* h, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16_candidates, size_t n_candidates,
+        const mon_pose_refine_params* p, const mon_pose_c2f_params* c, const mon_reloc_params* r, float* Twc16_out, mon_reloc_result* result, float* scores) {
+    REQ(h); REQ(obs); REQ(Twc16_candidates); REQ(p); REQ(r); REQ(Twc16_out);
+    if (n_obs == 0 || p->iters < 0) { set_error("relocalise: no boxes or iters < 0"); return MON_ERR_ARG; }
+    if (n_candidates == 0 || n_candidates > kSceneScoreMaxPoses || r->score_rays == 0 || r->score_rays > kSceneScoreMaxRays || r->keep == 0 ||
+        r->keep > kRelocMaxKeep) { set_error("relocalise: %zu candidates, score_rays %u, keep %u", n_candidates, r->score_rays, r->keep); return MON_ERR_ARG; }
+    if (c) { const int rc = pose_c2f_check(c); if (rc) return rc; }
+    std::vector<Model*> ms;
+    const std::vector<OnlineObject*> objs = online_objects(*h->m);
+    for (size_t i = 0; i < objs.size() && ms.size() < kSceneMaxLists; ++i) if (objs[i]->model && model_has_snapshot(*objs[i]->model)) ms.push_back(objs[i]->model);
+    if (ms.empty()) { set_error("relocalise: no object has published weights yet"); return MON_ERR_STATE; }
+    for (Model* m : ms) if (m->device != ms[0]->device) { set_error("relocalise: the objects span more than one device"); return MON_ERR_STATE; }
+    return scene_relocalise(ms.data(), ms.size(), 1, obs, n_obs, Twc16_candidates, n_candidates, *p, c, *r, Twc16_out, result, scores);
+}
 // NerfManagerOnline::RenderNeRFsTest -> NeRF::RenderTestImg, nerf.cu:255-404: <out>/<id>/{test_img,test_depth,test_mask}/<stamp>.png,
 // test.txt, train.txt (object-centric poses), 60-view video_img / video_depth, obj.ply
 int mon_online_render_nerfs_test(mon_online* h, const char* out_path, size_t idx, const char* const* timestamps, const mon_frame_bbox* boxes,

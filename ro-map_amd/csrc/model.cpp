@@ -1719,6 +1719,8 @@ struct ScenePoseWs {
     float* out = nullptr; size_t out_cap = 0; float* h_out = nullptr; size_t h_out_cap = 0;   // {loss, grad6, 0} per evaluation | pose; pinned staging
     float* lw = nullptr; size_t lw_cap = 0;                                       // level weights [evaluation][Lmax]
     float* dbg = nullptr; size_t dbg_cap = 0; uint32_t* dbg_cnt = nullptr; size_t dbg_cnt_cap = 0;
+    float* poses = nullptr; size_t poses_cap = 0; float* scores = nullptr; size_t scores_cap = 0;   // scene_pose_batch: [hypotheses][16], [hypotheses]
+    float* h_scores = nullptr; size_t h_scores_cap = 0;                                             // ... and their pinned staging
     std::vector<hipEvent_t> ev;
 };
 static std::mutex g_scene_pose_mu; static std::map<std::pair<int, int>, ScenePoseWs*> g_scene_pose_ws;
@@ -1757,13 +1759,9 @@ int scene_pose_check(Model* const* ms, size_t n, int side, const mon_frame_bbox*
         (unsigned long long)total, kPoseMaxRays); return MON_ERR_ARG; }
     return MON_OK;
 }
-int scene_pose(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16, const mon_pose_refine_params& p, int iters,
-               uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const ScenePoseDump* dump, const float* level_w) {
-    { const int rc = scene_pose_check(ms, n, side, obs, n_obs, Twc16, &p); if (rc) return rc; }
-    if (dump && dump->k >= n) { set_error("scene pose: dump of object %u of %zu", dump->k, n); return MON_ERR_ARG; }
-    if (!launch_scene_pose_rays || !launch_scene_pose_obj || !launch_scene_composite_grad || !launch_scene_pose_update || !scene_comp_grad_grid || !pose_grad_grid) {
-        set_error("scene pose: built without kernels_scene_pose.hip"); return MON_ERR_STATE; }
-    int Lmax = 0;
+// every MON_ERR_STATE of a scene pose call that needs no device work; Lmax = the largest n_levels among the objects
+static int scene_pose_state_check(Model* const* ms, size_t n, int side, int& Lmax) {
+    Lmax = 0;
     for (size_t j = 0; j < n; ++j) {
         Model& m = *ms[j];
         if (!rskip_supported(m) || 2u * m.oc.S != kSceneListLen) { set_error("scene pose: object %zu does not run on the fused kernels", j); return MON_ERR_STATE; }
@@ -1771,39 +1769,59 @@ int scene_pose(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, 
         if (side == 1 && !model_has_snapshot(m)) { set_error("scene pose: object %zu has no published snapshot", j); return MON_ERR_STATE; }
         Lmax = std::max(Lmax, (int)m.nd.L);
     }
+    return MON_OK;
+}
+// The weights of the side and its stream, as scene_render takes them, and the workspace.  Side 1: the shared inference stream under its device lock, every
+// object's newest ready snapshot pinned.  Side 0: object 0's train stream after every object's.  Holds the lock, the pins and the workspace until it goes
+// (after the call's stream has been synchronised).
+struct ScenePoseSide {
+    std::vector<const uint16_t*> prm; hipStream_t s = nullptr; ScenePoseWs* w = nullptr;
+    std::unique_lock<std::mutex> dev_lock;
+    struct Pins { std::vector<std::pair<InferState*, int>> p; ~Pins() { for (auto& q : p) { std::lock_guard<std::mutex> l(q.first->mu); --q.first->readers[q.second]; } } } pins;
+    std::unique_lock<std::mutex> wl;
+    int enter(Model* const* ms, size_t n, int side, int device) {
+        prm.assign(n, nullptr);
+        if (side == 1) {
+            InferShared* sh = ms[0]->infer->shared; dev_lock = std::unique_lock<std::mutex>(sh->mu); s = sh->stream;
+            for (size_t j = 0; j < n; ++j) {
+                InferState* is = ms[j]->infer; is->wanted.store(true); int r;
+                {   std::lock_guard<std::mutex> l(is->mu); r = is->latest;
+                    if (is->written[1 - r] && hipEventQuery(is->ready[r]) != hipSuccess && hipEventQuery(is->ready[1 - r]) == hipSuccess) r = 1 - r;
+                    ++is->readers[r]; pins.p.emplace_back(is, r); }
+                HIPCHECK(hipStreamWaitEvent(s, is->ready[r], 0));
+                prm[j] = is->snap[r];
+            }
+        }
+        w = &scene_pose_ws(device, side); wl = std::unique_lock<std::mutex>(w->mu);
+        if (side == 0) {
+            for (size_t j = 0; j < n; ++j) { Model& m = *ms[j]; model_leave_lane(m); int rc = ensure_ema_current(m); if (rc) return rc; }
+            s = ms[0]->train_stream;
+            while (w->ev.size() < n) { hipEvent_t e; HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); w->ev.push_back(e); }
+            for (size_t j = 0; j < n; ++j) {
+                Model& m = *ms[j];
+                if (m.train_stream != s) { HIPCHECK(hipEventRecord(w->ev[j], m.train_stream)); HIPCHECK(hipStreamWaitEvent(s, w->ev[j], 0)); }
+                prm[j] = (m.h_state.step > 0) ? m.P.ema : m.P.half;
+            }
+        }
+        return MON_OK;
+    }
+};
+int scene_pose(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16, const mon_pose_refine_params& p, int iters,
+               uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const ScenePoseDump* dump, const float* level_w) {
+    { const int rc = scene_pose_check(ms, n, side, obs, n_obs, Twc16, &p); if (rc) return rc; }
+    if (dump && dump->k >= n) { set_error("scene pose: dump of object %u of %zu", dump->k, n); return MON_ERR_ARG; }
+    if (!launch_scene_pose_rays || !launch_scene_pose_obj || !launch_scene_composite_grad || !launch_scene_pose_update || !scene_comp_grad_grid || !pose_grad_grid) {
+        set_error("scene pose: built without kernels_scene_pose.hip"); return MON_ERR_STATE; }
+    int Lmax = 0;
+    { const int rc = scene_pose_state_check(ms, n, side, Lmax); if (rc) return rc; }
     std::vector<uint32_t> prefix(n_obs + 1, 0u);
     for (size_t i = 0; i < n_obs; ++i) prefix[i + 1] = prefix[i] + obs[i].w * obs[i].h;
     const uint32_t total = prefix[n_obs], n_rays = p.rays_per_iter ? p.rays_per_iter : total;
     const int device = ms[0]->device;
     HIPCHECK(use_device(device));
     const int n_eval = iters < 0 ? 1 : iters + 1;
-    // the weights of the side and its stream, as scene_render takes them
-    std::vector<const uint16_t*> prm(n);
-    std::unique_lock<std::mutex> dev_lock;
-    struct Pins { std::vector<std::pair<InferState*, int>> p; ~Pins() { for (auto& q : p) { std::lock_guard<std::mutex> l(q.first->mu); --q.first->readers[q.second]; } } } pins;
-    hipStream_t s;
-    if (side == 1) {
-        InferShared* sh = ms[0]->infer->shared; dev_lock = std::unique_lock<std::mutex>(sh->mu); s = sh->stream;
-        for (size_t j = 0; j < n; ++j) {
-            InferState* is = ms[j]->infer; is->wanted.store(true); int r;
-            {   std::lock_guard<std::mutex> l(is->mu); r = is->latest;
-                if (is->written[1 - r] && hipEventQuery(is->ready[r]) != hipSuccess && hipEventQuery(is->ready[1 - r]) == hipSuccess) r = 1 - r;
-                ++is->readers[r]; pins.p.emplace_back(is, r); }
-            HIPCHECK(hipStreamWaitEvent(s, is->ready[r], 0));
-            prm[j] = is->snap[r];
-        }
-    }
-    ScenePoseWs& w = scene_pose_ws(device, side); std::lock_guard<std::mutex> wl(w.mu);
-    if (side == 0) {
-        for (size_t j = 0; j < n; ++j) { Model& m = *ms[j]; model_leave_lane(m); int rc = ensure_ema_current(m); if (rc) return rc; }
-        s = ms[0]->train_stream;
-        while (w.ev.size() < n) { hipEvent_t e; HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); w.ev.push_back(e); }
-        for (size_t j = 0; j < n; ++j) {
-            Model& m = *ms[j];
-            if (m.train_stream != s) { HIPCHECK(hipEventRecord(w.ev[j], m.train_stream)); HIPCHECK(hipStreamWaitEvent(s, w.ev[j], 0)); }
-            prm[j] = (m.h_state.step > 0) ? m.P.ema : m.P.half;
-        }
-    }
+    ScenePoseSide sd; { const int rc = sd.enter(ms, n, side, device); if (rc) return rc; }
+    const std::vector<const uint16_t*>& prm = sd.prm; const hipStream_t s = sd.s; ScenePoseWs& w = *sd.w;
     // chunks of the rays (the cap scene_render chunks its rect by); each chunk's partial rows follow the previous chunk's
     const uint32_t cap = std::min(n_rays, kRenderChunkRays), n_chunks = (n_rays + cap - 1u) / cap;
     const uint32_t gridc = std::min(pose_grad_grid(cap), std::max(1u, kPoseMaxGrid / n_chunks)), n_rows = n_chunks * gridc;
@@ -1900,6 +1918,141 @@ int scene_pose(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, 
             if (dump->dldx) std::memcpy(dump->dldx + 3 * i, q + 11, 12);
         }
         if (dump->count) std::memcpy(dump->count, h_cnt.data(), 4 * (size_t)n_rays);
+    }
+    return MON_OK;
+}
+
+// ---- batched pose scoring (mon_scene_pose_loss_batch): the forward half of scene_pose's chain over n_poses camera poses.  A pass holds G = floor(cap / n)
+// hypotheses of n rays each as G n virtual rays in scene_pose's own list workspace (no more list memory than one evaluation of the chunk cap takes): K + 3
+// launches per pass, everything enqueued at once, one synchronisation, one copy home.
+static_assert(kSceneScoreMaxRays == kRenderChunkRays, "a hypothesis holds at most one chunk of scene_pose's rays");
+int scene_pose_batch_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, size_t n_poses,
+                           const mon_pose_refine_params* p, const float* losses) {
+    if (!Twc16s || !losses) { set_error("scene pose batch: null argument"); return MON_ERR_ARG; }
+    if (n_poses == 0 || n_poses > kSceneScoreMaxPoses) { set_error("scene pose batch: %zu poses (1 to %u)", n_poses, kSceneScoreMaxPoses); return MON_ERR_ARG; }
+    { const int rc = scene_pose_check(ms, n, side, obs, n_obs, Twc16s, p); if (rc) return rc; }
+    uint64_t total = 0; for (size_t i = 0; i < n_obs; ++i) total += (uint64_t)obs[i].w * obs[i].h;
+    const uint64_t n_rays = p->rays_per_iter ? p->rays_per_iter : total;
+    if (n_rays > kSceneScoreMaxRays) { set_error("scene pose batch: %llu rays per hypothesis (at most %u)", (unsigned long long)n_rays, kSceneScoreMaxRays);
+        return MON_ERR_ARG; }
+    return MON_OK;
+}
+int scene_pose_batch(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, size_t n_poses,
+                     const mon_pose_refine_params& p, uint32_t iteration, float* losses) {
+    { const int rc = scene_pose_batch_check(ms, n, side, obs, n_obs, Twc16s, n_poses, &p, losses); if (rc) return rc; }
+    if (!launch_scene_score_rays || !launch_scene_pose_obj || !launch_scene_composite_loss || !launch_scene_loss_reduce || !scene_comp_grad_grid || !pose_grad_grid) {
+        set_error("scene pose batch: built without kernels_scene_score.hip"); return MON_ERR_STATE; }
+    int Lmax = 0;
+    { const int rc = scene_pose_state_check(ms, n, side, Lmax); if (rc) return rc; }
+    std::vector<uint32_t> prefix(n_obs + 1, 0u);
+    for (size_t i = 0; i < n_obs; ++i) prefix[i + 1] = prefix[i] + obs[i].w * obs[i].h;
+    const uint32_t total = prefix[n_obs], n_rays = p.rays_per_iter ? p.rays_per_iter : total, H = (uint32_t)n_poses;
+    const int device = ms[0]->device;
+    HIPCHECK(use_device(device));
+    ScenePoseSide sd; { const int rc = sd.enter(ms, n, side, device); if (rc) return rc; }
+    const std::vector<const uint16_t*>& prm = sd.prm; const hipStream_t s = sd.s; ScenePoseWs& w = *sd.w;
+    // passes of Gmax whole hypotheses (n_rays <= the chunk cap, so Gmax >= 1); virtual ray v = g * n_rays + r at slot v of the lists
+    const uint32_t Gmax = std::min(H, kSceneScoreMaxRays / n_rays), cap = Gmax * n_rays, parts = scene_comp_grad_grid(n_rays);
+    std::vector<size_t> frag_off(n + 1, 0);
+    for (size_t j = 0; j < n; ++j) { const NetDims& nd = ms[j]->nd; const FragDims fd{ nd.Epad, nd.W, nd.NH, nd.L }; frag_off[j + 1] = frag_off[j] + (size_t)fd.N_FRAGS() * 512; }
+    const size_t lists = n * (size_t)cap;
+    int rc;
+    if ((rc = grow_buf(w.t, w.t_cap, lists * kSceneListLen)) || (rc = grow_buf(w.attr, w.attr_cap, lists * kSceneListLen)) ||
+        (rc = grow_buf(w.cnt, w.cnt_cap, lists)) || (rc = grow_buf(w.mstar, w.mstar_cap, lists)) || (rc = grow_buf(w.rec, w.rec_cap, lists * 3)) ||
+        (rc = grow_buf(w.ray, w.ray_cap, (size_t)cap * 3)) || (rc = grow_buf(w.loss_part, w.lp_cap, (size_t)Gmax * parts)) ||
+        (rc = grow_buf(w.objs, w.objs_cap, n)) || (rc = grow_buf(w.frag, w.frag_cap, frag_off[n])) || (rc = grow_buf(w.boxes, w.box_cap, n_obs)) ||
+        (rc = grow_buf(w.prefix, w.prefix_cap, n_obs + 1)) || (rc = grow_buf(w.poses, w.poses_cap, (size_t)H * 16)) ||
+        (rc = grow_buf(w.scores, w.scores_cap, (size_t)H))) return rc;
+    if (H > w.h_scores_cap) {
+        if (w.h_scores) { (void)hipHostFree(w.h_scores); w.h_scores = nullptr; w.h_scores_cap = 0; }
+        HIPCHECK(hipHostMalloc((void**)&w.h_scores, (size_t)H * 4, hipHostMallocDefault)); w.h_scores_cap = H;
+    }
+    std::vector<SceneObjConst> h_objs(n);
+    for (size_t j = 0; j < n; ++j) { const ObjectConst& oc = ms[j]->oc; std::memcpy(h_objs[j].Tow, oc.Tow.m, 64); h_objs[j].aabb = oc.aabb;
+        h_objs[j].instance_id = oc.instance_id; h_objs[j].pad = 0u; }
+    HIPCHECK(hipMemcpyAsync(w.objs, h_objs.data(), sizeof(SceneObjConst) * n, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(w.boxes, obs, sizeof(mon_frame_bbox) * n_obs, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(w.prefix, prefix.data(), 4 * (n_obs + 1), hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(w.poses, Twc16s, 64 * (size_t)H, hipMemcpyHostToDevice, s));
+    const bool drawn = p.rays_per_iter != 0;
+    const float inv_n = 1.f / (float)n_rays;
+    for (uint32_t h0 = 0; h0 < H; h0 += Gmax) {
+        const uint32_t G = std::min(Gmax, H - h0), nv = G * n_rays;
+        SceneScoreRayArgs ra{}; ra.boxes = w.boxes; ra.prefix = w.prefix; ra.n_obs = (uint32_t)n_obs; ra.n_rays = nv; ra.ray0 = 0u; ra.total = total;
+        ra.drawn = drawn ? 1u : 0u; ra.iteration = iteration; ra.seed = p.seed; ra.ds = ms[0]->ds->ptrs(); ra.objs = w.objs; ra.n_objs = (uint32_t)n; ra.cap = cap;
+        ra.pose = w.poses; ra.rec = w.rec; ra.mstar = w.mstar; ra.ray = w.ray; ra.n_per = n_rays; ra.h0 = h0;
+        launch_scene_score_rays(s, ra);
+        for (size_t j = 0; j < n; ++j) {
+            Model& m = *ms[j]; const size_t l0 = j * (size_t)cap;
+            ScenePoseObjArgs a{}; a.rec = w.rec + l0 * 3; a.n_rays = nv; a.ray0 = 0u;
+            a.seed = drawn ? p.seed : m.oc.sample_seed; a.stream = drawn ? kStreamPose : (uint32_t)kStreamRender; a.step = drawn ? iteration : 0u;
+            a.t = w.t + l0 * kSceneListLen; a.attr = w.attr + l0 * kSceneListLen; a.cnt = w.cnt + l0; a.ray = w.ray; a.inv_n = inv_n;
+            launch_scene_pose_obj(s, m.lf, m.nd, m.oc, prm[j], w.frag + frag_off[j], h0 == 0, 0, pose_grad_grid(nv), a);
+        }
+        SceneCompGradArgs ca{}; ca.n_rays = nv; ca.n_lists = (uint32_t)n; ca.cap = cap; ca.t = w.t; ca.attr = w.attr; ca.cnt = w.cnt; ca.mstar = w.mstar;
+        ca.ray = w.ray; ca.w_rgb = p.w_rgb; ca.w_mask = p.w_mask; ca.w_depth = p.w_depth; ca.huber = p.depth_huber; ca.loss_part = w.loss_part;
+        launch_scene_composite_loss(s, ca, n_rays);
+        launch_scene_loss_reduce(s, w.loss_part, G, parts, inv_n, w.scores + h0);
+    }
+    HIPCHECK(hipGetLastError());
+    // (a copy kernel on the call's stream into the pinned staging, as scene_pose's results go home)
+    launch_copy_params(s, reinterpret_cast<const uint16_t*>(w.scores), reinterpret_cast<uint16_t*>(w.h_scores), H * 2u);
+    HIPCHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    std::memcpy(losses, w.h_scores, (size_t)H * 4);
+    return MON_OK;
+}
+
+// ---- wide-basin relocalisation (mon_scene_relocalise / mon_online_relocalise): score every candidate, refine the best few with scene_pose, score the
+// refined poses and their starts together, return the winner.  2 + min(keep, n_cands) stream synchronisations: one per scoring round, one per refinement.
+int scene_reloc_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* cands, size_t n_cands,
+                      const mon_pose_refine_params* p, const mon_pose_c2f_params* c, const mon_reloc_params* r, const float* pose_out) {
+    if (!cands || !p || !r || !pose_out) { set_error("relocalise: null argument"); return MON_ERR_ARG; }
+    if (n_cands == 0 || n_cands > kSceneScoreMaxPoses) { set_error("relocalise: %zu candidates (1 to %u)", n_cands, kSceneScoreMaxPoses); return MON_ERR_ARG; }
+    if (r->score_rays == 0 || r->score_rays > kSceneScoreMaxRays) { set_error("relocalise: score_rays %u (1 to %u)", r->score_rays, kSceneScoreMaxRays);
+        return MON_ERR_ARG; }
+    if (r->keep == 0 || r->keep > kRelocMaxKeep) { set_error("relocalise: keep %u (1 to %u)", r->keep, kRelocMaxKeep); return MON_ERR_ARG; }
+    { const int rc = scene_pose_check(ms, n, side, obs, n_obs, cands, p); if (rc) return rc; }
+    if (c) { const int rc = pose_c2f_check(c); if (rc) return rc; }
+    return MON_OK;
+}
+int scene_relocalise(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* cands, size_t n_cands,
+                     const mon_pose_refine_params& p, const mon_pose_c2f_params* c, const mon_reloc_params& r, float* pose_out, mon_reloc_result* result,
+                     float* scores) {
+    { const int rc = scene_reloc_check(ms, n, side, obs, n_obs, cands, n_cands, &p, c, &r, pose_out); if (rc) return rc; }
+    int Lmax = 0;
+    { const int rc = scene_pose_state_check(ms, n, side, Lmax); if (rc) return rc; }
+    mon_pose_refine_params ps = p; ps.rays_per_iter = r.score_rays;
+    // 1. every candidate's score
+    std::vector<float> S(n_cands);
+    int rc = scene_pose_batch(ms, n, side, obs, n_obs, cands, n_cands, ps, r.score_iteration, S.data()); if (rc) return rc;
+    if (scores) std::memcpy(scores, S.data(), n_cands * 4);
+    // 2. the kept set: candidate 0, then the others by ascending score (ties to the lower index, a non-finite score last)
+    std::vector<uint32_t> order; for (uint32_t i = 1; i < n_cands; ++i) order.push_back(i);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        const bool fa = std::isfinite(S[a]), fb = std::isfinite(S[b]);
+        return fa != fb ? fa : (fa && S[a] < S[b]); });
+    const size_t k = std::min<size_t>(r.keep, n_cands);
+    std::vector<uint32_t> kept{ 0u }; kept.insert(kept.end(), order.begin(), order.begin() + (ptrdiff_t)(k - 1));
+    // 3. each of them refined as mon_scene_refine_camera refines it
+    std::vector<float> table; if (c) table = pose_c2f_table(*c, Lmax, p.iters);
+    std::vector<float> list(2 * k * 16);
+    for (size_t i = 0; i < k; ++i) {
+        const float* start = cands + 16 * (size_t)kept[i]; float* pose = list.data() + 16 * i;
+        std::memcpy(list.data() + 16 * (k + i), start, 64); std::memcpy(pose, start, 64);
+        rc = scene_pose(ms, n, side, obs, n_obs, pose, p, p.iters, 0u, pose, nullptr, nullptr, nullptr, nullptr, table.empty() ? nullptr : table.data());
+        if (rc) return rc;
+    }
+    // 4. the refined poses and their starts under the common key; the lowest finite score wins (ties to the earlier entry)
+    std::vector<float> F(2 * k);
+    rc = scene_pose_batch(ms, n, side, obs, n_obs, list.data(), 2 * k, ps, r.score_iteration, F.data()); if (rc) return rc;
+    size_t win = 2 * k;
+    for (size_t i = 0; i < 2 * k; ++i) if (std::isfinite(F[i]) && (win == 2 * k || F[i] < F[win])) win = i;
+    const bool none = win == 2 * k; if (none) win = k;                          // no finite score: candidate 0 as given
+    std::memcpy(pose_out, list.data() + 16 * win, 64);
+    if (result) {
+        result->best_candidate = kept[win % k]; result->refined = (!none && win < k) ? 1u : 0u;
+        result->score_candidate0 = S[0]; result->score_best_candidate = S[kept[win % k]]; result->score_final = F[win];
     }
     return MON_OK;
 }

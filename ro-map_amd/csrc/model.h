@@ -342,7 +342,7 @@ void launch_scene_composite(hipStream_t s, uint32_t n_rays, uint32_t n_lists, ui
 // device memory (pose[16], world -> object); k_pose_grad<shape>: loss and position gradient, one partial row of 8 floats {g, x x g, loss, 0} per workgroup
 // (pose_grad_grid of them); k_pose_update: the rows summed in a fixed order, x inv_n -> out[8 * it] = {loss, grad6, 0}, optionally the Adam step on pose.
 // Counter-RNG streams of the drawn rays: sample jitter (key ray * 2S + k) and pixel draws (key ray), both keyed by (seed, iteration).
-constexpr uint32_t kStreamPose = 4, kStreamPoseXY = 5;
+constexpr uint32_t kStreamPose = 4, kStreamPoseXY = 5, kStreamPoseHyp = 6;     // (6: mon_pose_hypotheses' draws, keyed (seed, hypothesis, 0..5))
 constexpr uint32_t kPoseMaxGrid = 1024, kPoseMaxRays = 1u << 22;
 struct PoseRayArgs {
     const mon_frame_bbox* boxes; const uint32_t* prefix;      // the boxes and the exclusive prefix sums of their areas
@@ -408,6 +408,15 @@ __attribute__((weak)) void launch_scene_pose_obj(hipStream_t s, const LevelFast&
 __attribute__((weak)) uint32_t scene_comp_grad_grid(uint32_t n_rays);
 __attribute__((weak)) void launch_scene_composite_grad(hipStream_t s, const SceneCompGradArgs& a);
 __attribute__((weak)) void launch_scene_pose_update(hipStream_t s, const ScenePoseUpdateArgs& a);
+// Batched pose scoring (mon_scene_pose_loss_batch, kernels_scene_score.hip).  A pass holds G hypotheses of n_per rays as G * n_per virtual rays
+// v = g * n_per + r in the lists of one evaluation (cap >= G * n_per): k_scene_score_rays (n_rays = G * n_per, pose = every hypothesis's Twc, 16 floats each;
+// ray0 unused) -> per object k_scene_pose_obj<.., false, false> over the virtual rays -> k_scene_composite_loss (grid (scene_comp_grad_grid(n_per), G), one
+// loss partial per workgroup, hypothesis-major) -> k_scene_loss_reduce (one workgroup per hypothesis, k_scene_pose_update's order, out[g] = loss).
+constexpr uint32_t kSceneScoreMaxPoses = 4096, kRelocMaxKeep = 16, kSceneScoreMaxRays = 16384;      // (rays: the chunk cap of the chain; a hypothesis is never split)
+struct SceneScoreRayArgs : ScenePoseRayArgs { uint32_t n_per, h0; };      // rays per hypothesis; the pass's first hypothesis
+__attribute__((weak)) void launch_scene_score_rays(hipStream_t s, const SceneScoreRayArgs& a);
+__attribute__((weak)) void launch_scene_composite_loss(hipStream_t s, const SceneCompGradArgs& a, uint32_t n_per);
+__attribute__((weak)) void launch_scene_loss_reduce(hipStream_t s, const float* loss_part, uint32_t n_hyp, uint32_t n_parts, float inv_n, float* out);
 // inference on feature-planar level tiles (kernels_tilerender.hip): Render / RenderVideo, GetDensityOnGrid, mesh vertex colours
 constexpr uint32_t kTileChunkJobs = 32768;          // rays (jobs of 2S = 64 samples) per chunk of the tile render
 bool tile_render_supported(const LevelTable& lt, const NetDims& nd);
@@ -576,6 +585,20 @@ int scene_pose_check(Model* const* ms, size_t n, int side, const mon_frame_bbox*
 int scene_pose(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16, const mon_pose_refine_params& p, int iters,
                uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const ScenePoseDump* dump, const float* level_w = nullptr);
 uint32_t pose_n_rays(const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params& p);      // rays of one evaluation
+// mon_scene_pose_loss_batch: losses[h] = scene_pose(.., Twc16s + 16 h, p, -1, iteration, ..)'s loss bit for bit, all in one enqueue with one synchronisation.
+// scene_pose_batch_check: every MON_ERR_ARG of the call (scene_pose_check's, n_poses outside 1..kSceneScoreMaxPoses, more than kSceneScoreMaxRays rays per
+// hypothesis), no device work.
+int scene_pose_batch_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, size_t n_poses,
+                           const mon_pose_refine_params* p, const float* losses);
+int scene_pose_batch(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, size_t n_poses,
+                     const mon_pose_refine_params& p, uint32_t iteration, float* losses);
+// mon_scene_relocalise / mon_online_relocalise: the rule of include/mon_core.h over scene_pose_batch and scene_pose.  scene_reloc_check: its MON_ERR_ARG
+// cases, no device work.
+int scene_reloc_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* cands, size_t n_cands,
+                      const mon_pose_refine_params* p, const mon_pose_c2f_params* c, const mon_reloc_params* r, const float* pose_out);
+int scene_relocalise(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* cands, size_t n_cands,
+                     const mon_pose_refine_params& p, const mon_pose_c2f_params* c, const mon_reloc_params& r, float* pose_out, mon_reloc_result* result,
+                     float* scores);
 int pose_c2f_check(const mon_pose_c2f_params* c);                                                    // MON_ERR_ARG for a NULL or bad schedule
 std::vector<float> pose_c2f_table(const mon_pose_c2f_params& c, int n_levels, int iters);          // [iters][n_levels]: mon_pose_c2f_weights of every step
 // Checkpoints (mon_object_save / mon_object_load / mon_checkpoint_read_info).  boxes_out (may be nullptr): the box list the file holds,
