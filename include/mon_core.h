@@ -357,6 +357,70 @@ int mon_reloc_default(mon_reloc_params* r);     /* 256, 4, 0 */
 int mon_scene_relocalise(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16_candidates,
                          size_t n_candidates, const mon_pose_refine_params* p, const mon_pose_c2f_params* c /* NULL: plain */, const mon_reloc_params* r,
                          float* Twc16_out, mon_reloc_result* result /* may be NULL */, float* scores /* n_candidates, may be NULL */);
+/* ---- joint refinement of a window of camera poses and object poses (the reference has no such call; opt-in, new): the step a SLAM back
+ * end takes between tracking and mapping -- a local window of keyframes and the objects they see, refined together.
+ * Window.  obs may name several FrameIds; the boxes of one frame must be contiguous in obs.  The frames of the window are the distinct FrameIds in order of
+ * first appearance ("window order"), F of them, 1 <= F <= 32; mon_window_frames (host only) returns that order.  Poses: Twc16s, F matrices in window order.
+ * Objects: Tow16s, K matrices in objs order; NULL = each object's own Tow.
+ * Objective.  For frame f, L_f and grad6_f are exactly what mon_scene_pose_loss(objs, .., the boxes of f, Twc_f, p, iteration, level_weights) defines: the
+ * same pixel draw over the union of f's boxes keyed (seed, iteration, ray) with rays_per_iter counting per frame, the same per-object samples, merged
+ * composite, both cuts and held quantities -- with Tow_j taken from Tow16s.  L = sum_f L_f, added in window order in fp32: a sum, not a mean, so each
+ * camera's gradient is its single-frame gradient unscaled.
+ * Gradients.  cam_grad6[6 f ..] = grad6_f.  obj_grad6[6 j ..] = sum_f G_{f,j}, added in window order, G_{f,j} = (sum g_o, sum x_o x g_o) / N_f in object
+ * j's frame over the N_f rays of frame f: obj_grad6_j = dL/dxi at xi = 0 for Tow_j(xi) = exp(xi^) Tow_j, translation first (mon_object_pose_loss's
+ * perturbation).  Held at their values at xi = 0 as there: every t and dt, the box intersections, the merge order, both cuts and the hash-grid corners.
+ * Level weights act on both gradients exactly as in mon_scene_pose_loss (1: the unweighted bits; 0: both gradients exactly 0; the loss does not depend on
+ * them).
+ * Bit rule.  For every frame f, frame_loss[f] and cam_grad6[6 f ..] are bit for bit what mon_scene_pose_loss returns for that frame alone with the same
+ * object poses -- whatever else the window holds, wherever the frame stands in it and however the frames are packed into passes.  No atomics anywhere:
+ * equal arguments give equal bits.
+ * Refinement (mon_scene_refine_window).  Adam (0.9, 0.999, 1e-8) on one twist per free camera and per object, moments per block.  Cameras: p->lr_trans /
+ * p->lr_rot and Twc_f <- Twc_f exp(delta^), mon_scene_refine_camera's step.  Objects: w->lr_obj_trans / w->lr_obj_rot and Tow_j <- exp(delta^) Tow_j,
+ * mon_object_refine_pose's step; Gram-Schmidt on both.  All gradients of a step are taken at the poses the step starts from, then everything moves at once.
+ * Step i evaluates with iteration = i; with a schedule c it uses mon_pose_c2f_weights(c, Lmax, iters, i).  loss_trace[i] (iters + 1 values, may be NULL) is L
+ * before step i, loss_trace[iters] L at the end; frame_trace[(iters + 1) * F] (may be NULL) holds the L_f, evaluation-major.  All poses live on the device
+ * between steps; the whole call is enqueued at once -- passes of whole frames, at most 16384 rays each, filled greedily in window order, in the list
+ * workspace of one mon_scene_pose_loss evaluation: passes x (2K + 2) + 1 launches per step -- with one synchronisation.
+ * The first n_fixed_frames frames in window order keep their pose (anchors) and come back bit for bit as given.  refine_objects = 0: the objects keep Tow16s
+ * and Tow16s_inout (which may then be NULL: each object's own Tow) comes back bit for bit as given.  refine_objects != 0 with n_fixed_frames = 0 is rejected:
+ * the objective is invariant under one common motion of every camera and object, so nothing would hold the map in place.
+ * Read-only, as mon_scene_refine_camera: nothing about any object, the dataset or a manager changes; the poses go back to the caller only, who stores them
+ * with mon_online_update_dataset (cameras) and mon_object_set_pose / mon_online_set_object_pose (objects).  side 0 / 1 as in that call.
+ * Returns MON_ERR_ARG, before any device work, for everything mon_scene_pose_loss / mon_scene_refine_camera reject per frame, non-contiguous frames, more
+ * than 32 frames, more than 16384 rays in one frame (a frame is never split across passes), n_fixed_frames above F, non-finite or negative object step
+ * sizes, refine_objects without a fixed frame or with a NULL Tow16s_inout, a non-finite Tow16s, a NULL Twc16s or w; MON_ERR_STATE as
+ * mon_scene_refine_camera. */
+typedef struct mon_window_params {
+    uint32_t n_fixed_frames;  /* the first n frames in window order keep their pose (anchors); 0..F */
+    int32_t  refine_objects;  /* 0: the objects keep Tow16s */
+    float    lr_obj_trans, lr_obj_rot;   /* Adam step sizes of the object twists (object-frame units, radians) */
+} mon_window_params;
+int mon_window_default(mon_window_params* w);   /* 1, 1, 2e-3, 4e-3 (mon_pose_refine_default's steps) */
+/* host only: the distinct FrameIds of obs in order of first appearance; MON_ERR_ARG for non-contiguous frames, more than 32 frames and NULL arguments */
+int mon_window_frames(const mon_frame_bbox* obs, size_t n_obs, uint32_t* frame_ids_out /* cap 32 */, size_t* n_frames_out);
+/* One evaluation.  Every output may be NULL: loss, frame_loss [F], cam_grad6 [6 F], obj_grad6 [6 K]. */
+int mon_scene_window_loss(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s /* 16 F */,
+                          const float* Tow16s /* 16 K, or NULL */, const mon_pose_refine_params* p, uint32_t iteration,
+                          const float* level_weights /* NULL or Lmax */, float* loss, float* frame_loss, float* cam_grad6, float* obj_grad6);
+int mon_scene_refine_window(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p,
+                            const mon_pose_c2f_params* c /* NULL: plain */, const mon_window_params* w, float* Twc16s_inout /* 16 F */,
+                            float* Tow16s_inout /* 16 K; NULL allowed only when refine_objects == 0 */, float* loss_trace /* iters + 1, may be NULL */,
+                            float* frame_trace /* (iters + 1) F, may be NULL */);
+/* Stores a new Tow (column-major, world -> object) in a trained object: replaces the object's pose and nothing else -- weights, optimizer state, counters,
+ * the occupancy grid and the render-skip grids live in the object frame and stay.  What was built under the old pose is marked stale: the candidate rays
+ * prepared for the coming iteration are generated again and a captured training graph is dropped; setting the pose the object already has therefore leaves
+ * training bit for bit as it was.  An object holds one Tow for both sides.  The pose is replaced under the device's inference lock, which every side 1
+ * call holds from start to end: a side 1 call running on another thread (a viewer's mon_online_render_scene, mon_online_refine_camera, ...) sees either
+ * the old pose or the new one, never a mixture, and needs no care by the caller.  The price is latency, not correctness: this call waits until a side 1
+ * call in flight on the device has ended (a 100-step mon_online_refine_window or a relocalisation may take tens of milliseconds), and
+ * mon_online_set_object_pose holds the object's model lock while it waits, so that object's training slice stalls for as long (lock order everywhere: model
+ * lock, then inference lock).  A back end that minds calls the setter between its own side 1 calls.
+ * Between this call and the object's next publication a side 1 call uses
+ * the NEW pose with the snapshot's weights as published -- consistent, since the weights are in the object frame; the next publication changes weights
+ * only.  Against training the caller serialises, as for mon_object_render (mon_online_set_object_pose does it with the model lock).  mon_object_save
+ * afterwards stores the new Tow.  MON_ERR_ARG for NULL arguments or a non-finite matrix; MON_ERR_STATE between stage-wise calls of
+ * mon_object_train_stages. */
+int mon_object_set_pose(mon_object* obj, const float* Tow16);
 /* NeRF_Model::GetDensityOnGrid (nerf_model.cu:2007-2048): raw density channel on an rx*ry*rz lattice. */
 int mon_object_density_grid(mon_object* obj, int rx, int ry, int rz, float* out_host);
 
@@ -505,6 +569,19 @@ int mon_online_refine_camera(mon_online* mgr, const mon_frame_bbox* obs, size_t 
 int mon_online_relocalise(mon_online* mgr, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16_candidates, size_t n_candidates,
                           const mon_pose_refine_params* p, const mon_pose_c2f_params* c, const mon_reloc_params* r, float* Twc16_out,
                           mon_reloc_result* result, float* scores);
+/* mon_scene_refine_window(side 1) over every object of the manager that has published weights, chosen as mon_online_refine_camera chooses them: a back
+ * end's call for a local window of keyframes already in the dataset (mon_online_refine_window -> accept by the trace -> mon_online_update_dataset for the
+ * cameras, mon_online_set_object_pose for the objects), safe while the objects train.  Tow16s_inout holds 16 floats per MANAGER object (n_objects of them, may
+ * be NULL when refine_objects == 0): the starting pose of every object that takes part is read from it and its refined pose written back; the others keep
+ * what the array held.  included[n_objects] (may be NULL) marks the objects that took part.  Nothing of the manager changes.  MON_ERR_ARG when n_objects is
+ * not the manager's object count; MON_ERR_STATE as mon_online_refine_camera. */
+int mon_online_refine_window(mon_online* mgr, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, const mon_pose_c2f_params* c,
+                             const mon_window_params* w, float* Twc16s_inout, float* Tow16s_inout, size_t n_objects, uint8_t* included, float* loss_trace,
+                             float* frame_trace);
+/* mon_object_set_pose of object idx under its model lock (as mon_online_update_dataset takes it): safe while the object trains; the manager's own record of
+ * the pose follows.  The snapshot side sees the new pose from the call on (one Tow per object, replaced under the device's inference lock: see
+ * mon_object_set_pose), so side 1 calls of other threads need not be held back. */
+int mon_online_set_object_pose(mon_online* mgr, size_t idx, const float* Tow16);
 /* The object map as checkpoints: <dir>/map.txt, one line "index file class_id" per object, and one mon_object_save file per object next to it.  Each
  * object's model lock is taken in turn (as mon_online_update_dataset does), so the call is safe while the objects train and every file is one consistent
  * object; the map is NOT one global cut -- object 3 may be saved some training slices later than object 0. */

@@ -54,6 +54,11 @@ class RelocParams(C.Structure):
     _fields_ = [("score_rays", C.c_uint32), ("keep", C.c_uint32), ("score_iteration", C.c_uint32)]
 
 
+class WindowParams(C.Structure):
+    """mon_window_params (include/mon_core.h): the anchors of a window refinement, whether the objects move, and the objects' Adam step sizes."""
+    _fields_ = [("n_fixed_frames", C.c_uint32), ("refine_objects", C.c_int32), ("lr_obj_trans", C.c_float), ("lr_obj_rot", C.c_float)]
+
+
 class RelocResult(C.Structure):
     """mon_reloc_result (include/mon_core.h): which candidate won, whether its refined pose did, and the scores S[0], S[best], F[winner]."""
     _fields_ = [("best_candidate", C.c_uint32), ("refined", C.c_uint32), ("score_candidate0", C.c_float), ("score_best_candidate", C.c_float),
@@ -201,6 +206,16 @@ _SIGS = {
             C.POINTER(PoseC2FParams), C.POINTER(RelocParams), C.c_void_p, C.POINTER(RelocResult), C.c_void_p]),
     "mon_online_relocalise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams), C.POINTER(PoseC2FParams),
             C.POINTER(RelocParams), C.c_void_p, C.POINTER(RelocResult), C.c_void_p]),
+    "mon_window_default": (C.c_int, [C.POINTER(WindowParams)]),
+    "mon_window_frames": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "mon_scene_window_loss": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(PoseRefineParams),
+            C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_scene_refine_window": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams), C.POINTER(PoseC2FParams),
+            C.POINTER(WindowParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_online_refine_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(PoseRefineParams), C.POINTER(PoseC2FParams),
+            C.POINTER(WindowParams), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_object_set_pose": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mon_online_set_object_pose": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "mon_checkpoint_read_info": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p]),
     "mon_object_save": (C.c_int, [C.c_void_p, C.c_char_p]),
     "mon_object_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]),
@@ -690,6 +705,10 @@ class ObjectNeRF:
         _check(lib().mon_object_pose_loss_levels(self.h, int(side), _p(b), b.shape[0], _p(pose), C.byref(prm), int(iteration), _p(w), C.byref(loss), _p(g)))
         return loss.value, g
 
+    def set_pose(self, Tow16):
+        """mon_object_set_pose: stores a new Tow (column-major) in the object; weights and training state stay."""
+        T = np.ascontiguousarray(Tow16, np.float32).reshape(16); _check(lib().mon_object_set_pose(self.h, _p(T)))
+
     def refine_pose_c2f(self, obs, Tow16, params=None, c2f=None, side=0):
         """mon_object_refine_pose_c2f: refine_pose with the coarse-to-fine level schedule c2f (PoseC2FParams, a dict of overrides, or None = defaults)."""
         b, prm, c = _pose_boxes(obs), _pose_params(params), _c2f_params(c2f); pose = np.array(Tow16, np.float32).reshape(16)
@@ -877,6 +896,22 @@ class OnlineManager:
         _check(lib().mon_online_refine_pose_c2f(self.h, int(idx), _p(b), b.shape[0], C.byref(prm), C.byref(c), _p(pose), _p(trace)))
         return pose, trace
 
+    def refine_window(self, obs, Twc16s, Tow16s, params=None, c2f=None, window=None):
+        """mon_online_refine_window: the window's camera poses Twc16s (F, 16) and the objects' poses Tow16s (one row of 16 per manager object) refined against every object with published weights, safe while they train.  Returns (Twc16s, Tow16s, included flags per
+        manager object, loss trace, frame trace (iters + 1, F)); the manager is not changed."""
+        b, prm, wp = _pose_boxes(obs), _pose_params(params), _window_params(window)
+        F = len(window_frames(b)); Twc = np.array(Twc16s, np.float32).reshape(F, 16)
+        Tow = np.array(Tow16s, np.float32).reshape(-1, 16); n = Tow.shape[0]
+        c = None if c2f is None else _c2f_params(None if c2f is True else c2f)
+        inc = np.zeros(n, np.uint8); trace = np.empty(prm.iters + 1, np.float32); ftrace = np.empty((prm.iters + 1, F), np.float32)
+        _check(lib().mon_online_refine_window(self.h, _p(b), b.shape[0], C.byref(prm), None if c is None else C.byref(c), C.byref(wp), _p(Twc), _p(Tow), n,
+                                              _p(inc), _p(trace), _p(ftrace)))
+        return Twc, Tow, inc, trace, ftrace
+
+    def set_object_pose(self, idx, Tow16):
+        """mon_online_set_object_pose: stores a refined Tow in object idx under its model lock (safe while it trains)."""
+        T = np.ascontiguousarray(Tow16, np.float32).reshape(16); _check(lib().mon_online_set_object_pose(self.h, int(idx), _p(T)))
+
     def refine_camera(self, obs, Twc16, params=None, c2f=None):
         """mon_online_refine_camera: the camera pose of one frame refined against every object with published weights, safe while they train; c2f as
         scene_refine_camera's.  Returns (refined Twc16, loss trace); the manager is not changed (update_dataset stores a pose)."""
@@ -1015,6 +1050,56 @@ def scene_refine_camera(objects, obs, Twc16, params=None, c2f=None, side=0):
     _check(lib().mon_scene_refine_camera(_handles(objects), len(objects), int(side), _p(b), b.shape[0], C.byref(prm), None if c is None else C.byref(c),
                                          _p(pose), _p(trace)))
     return pose, trace
+
+
+def window_default(**overrides):
+    """mon_window_default, then any field overridden by keyword."""
+    w = WindowParams(); _check(lib().mon_window_default(C.byref(w)))
+    for k, v in overrides.items():
+        if k not in dict(WindowParams._fields_):
+            raise KeyError(k)
+        setattr(w, k, v)
+    return w
+
+
+def _window_params(window):
+    if isinstance(window, WindowParams):
+        return window
+    return window_default(**(window or {}))
+
+
+def window_frames(obs):
+    """mon_window_frames (host only): the distinct FrameIds of obs [(FrameId, x, y, h, w)] in order of first appearance (uint32)."""
+    b = _pose_boxes(obs); ids = np.zeros(32, np.uint32); n = C.c_size_t(0)
+    _check(lib().mon_window_frames(_p(b), b.shape[0], _p(ids), C.byref(n)))
+    return ids[:n.value].copy()
+
+
+def scene_window_loss(objects, obs, Twc16s, Tow16s=None, params=None, side=0, iteration=0, level_weights=None):
+    """mon_scene_window_loss: one evaluation of a window -- obs names F frames (each frame's boxes contiguous), Twc16s (F, 16) in window order, Tow16s (K, 16)
+    or None = every object's own Tow.  Returns (L = sum of the frame losses, frame_loss (F,), cam_grad6 (F, 6), obj_grad6 (K, 6))."""
+    b, prm = _pose_boxes(obs), _pose_params(params); F = len(window_frames(b)); K = len(objects)
+    Twc = np.ascontiguousarray(Twc16s, np.float32).reshape(F, 16)
+    Tow = None if Tow16s is None else np.ascontiguousarray(Tow16s, np.float32).reshape(K, 16)
+    w = _scene_level_weights(objects, level_weights); loss = C.c_float(0)
+    fl = np.empty(F, np.float32); cg = np.empty((F, 6), np.float32); og = np.empty((K, 6), np.float32)
+    _check(lib().mon_scene_window_loss(_handles(objects), K, int(side), _p(b), b.shape[0], _p(Twc), _p(Tow), C.byref(prm), int(iteration), _p(w),
+                                       C.byref(loss), _p(fl), _p(cg), _p(og)))
+    return loss.value, fl, cg, og
+
+
+def scene_refine_window(objects, obs, Twc16s, Tow16s=None, params=None, c2f=None, window=None, side=0):
+    """mon_scene_refine_window: params.iters joint Adam steps on the window's free cameras and (window.refine_objects) the objects.  window: WindowParams, a
+    dict of overrides of mon_window_default, or None.  Tow16s None = every object's own Tow (only with refine_objects = 0).  Returns (Twc16s (F, 16),
+    Tow16s (K, 16) or None, loss trace (iters + 1,), frame trace (iters + 1, F)); nothing about the objects changes."""
+    b, prm, wp = _pose_boxes(obs), _pose_params(params), _window_params(window); F = len(window_frames(b)); K = len(objects)
+    Twc = np.array(Twc16s, np.float32).reshape(F, 16)
+    Tow = None if Tow16s is None else np.array(Tow16s, np.float32).reshape(K, 16)
+    c = None if c2f is None else _c2f_params(None if c2f is True else c2f)
+    trace = np.empty(prm.iters + 1, np.float32); ftrace = np.empty((prm.iters + 1, F), np.float32)
+    _check(lib().mon_scene_refine_window(_handles(objects), K, int(side), _p(b), b.shape[0], C.byref(prm), None if c is None else C.byref(c), C.byref(wp),
+                                         _p(Twc), _p(Tow), _p(trace), _p(ftrace)))
+    return Twc, Tow, trace, ftrace
 
 
 def scene_pose_loss_batch(objects, obs, Twc16s, params=None, side=0, iteration=0):

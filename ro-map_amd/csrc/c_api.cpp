@@ -209,6 +209,36 @@ int mon_scene_refine_camera(mon_object* const* objs, size_t n_objs, int side, co
     if (rc == MON_OK) std::memcpy(Twc16_inout, pose, 64);
     return rc;
 }
+// ---- joint refinement of a window of camera poses and object poses
+int mon_window_default(mon_window_params* w) {
+    REQUIRE(w, "params");
+    w->n_fixed_frames = 1; w->refine_objects = 1; w->lr_obj_trans = 2e-3f; w->lr_obj_rot = 4e-3f;
+    return MON_OK;
+}
+int mon_window_frames(const mon_frame_bbox* obs, size_t n_obs, uint32_t* frame_ids_out, size_t* n_frames_out) {
+    return window_frames(obs, n_obs, frame_ids_out, n_frames_out);
+}
+int mon_scene_window_loss(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const float* Tow16s,
+                          const mon_pose_refine_params* p, uint32_t iteration, const float* level_weights, float* loss, float* frame_loss, float* cam_grad6,
+                          float* obj_grad6) {
+    int rc = scene_window_params_check(obs, n_obs, Twc16s, p, nullptr, Tow16s, false); if (rc) return rc;
+    std::vector<Model*> ms; if ((rc = scene_pose_models(objs, n_objs, ms))) return rc;
+    if (level_weights) { int Lmax = 0; for (Model* m : ms) Lmax = std::max(Lmax, (int)m->nd.L); if ((rc = level_weights_check(level_weights, Lmax))) return rc; }
+    return scene_window(ms.data(), n_objs, side, obs, n_obs, Twc16s, Tow16s, *p, nullptr, -1, iteration, level_weights, nullptr, nullptr, nullptr, nullptr, loss,
+                        frame_loss, cam_grad6, obj_grad6);
+}
+int mon_scene_refine_window(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p,
+                            const mon_pose_c2f_params* c, const mon_window_params* w, float* Twc16s_inout, float* Tow16s_inout, float* loss_trace,
+                            float* frame_trace) {
+    int rc = scene_window_params_check(obs, n_obs, Twc16s_inout, p, w, Tow16s_inout, true); if (rc) return rc;
+    if (c && (rc = pose_c2f_check(c))) return rc;
+    std::vector<Model*> ms; if ((rc = scene_pose_models(objs, n_objs, ms))) return rc;
+    int Lmax = 0; for (Model* m : ms) Lmax = std::max(Lmax, (int)m->nd.L);
+    std::vector<float> table; if (c) table = pose_c2f_table(*c, Lmax, p->iters);
+    return scene_window(ms.data(), n_objs, side, obs, n_obs, Twc16s_inout, Tow16s_inout, *p, w, p->iters, 0u, table.empty() ? nullptr : table.data(),
+                        Twc16s_inout, Tow16s_inout, loss_trace, frame_trace, nullptr, nullptr, nullptr, nullptr);
+}
+int mon_object_set_pose(mon_object* o, const float* Tow16) { REQUIRE(o, "object"); REQUIRE(Tow16, "Tow16"); return model_set_pose(*o->m, Tow16); }
 // ---- wide-basin relocalisation: batched scoring, candidate poses, the driver
 int mon_scene_pose_loss_batch(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s,
                               size_t n_poses, const mon_pose_refine_params* p, uint32_t iteration, float* losses) {

@@ -2,6 +2,8 @@
 // candidate camera pose in every object's frame, each object's sample lists (forward only), the merged composite with its loss and its backward, each
 // object's MLP backward and hash-grid position gradient from the gradients the composite left in the lists, and the Adam step on the camera twist.
 // The objective is stated in include/mon_core.h and DESIGN.md 3.4f.  No atomics anywhere: every sum runs in a fixed order.
+// Window refinement runs the composite and the object backward over a pass of whole frames: k_scene_window_composite and k_scene_window_obj
+// stand next to the single-frame kernels and share their bodies, each workgroup confined to one frame's rays and to that frame's single-frame walk.
 #include <type_traits>
 #include "pose_device.h"
 #include "scene_device.h"
@@ -44,8 +46,11 @@ __device__ __forceinline__ void scene_tile_forward(SceneTile<EPAD, W, NH>& q, in
 // BWD = true: recomputes the forward of the tiles the count names, takes dL/dalpha and w of every sample from the list slots k_scene_composite_grad filled
 // and G_rgb from the ray's row, forms dL/dO (x the ray's power-of-two scale), and runs pose_tile_backward -- k_pose_grad's MLP backward and position
 // gradient.  Per lane: sums of g and x x g over its samples, object frame; per workgroup: one partial row of 8 floats {g, x x g, 0, 0}.
+// The body walks rays r = blk * WAVES + wave, + n_blk * WAVES, ... < n_rays of the lists' slots v0 + r and writes the row `row` of `partials`:
+// k_scene_pose_obj is (blockIdx.x, gridDim.x, p.n_rays, 0, blockIdx.x); k_scene_window_obj confines a workgroup to one frame of a window pass.
 template <int EPAD, int W, int NH, bool LW, bool BWD>
-__global__ void __launch_bounds__(256) k_scene_pose_obj(FusedArgs a, ScenePoseObjArgs p) {
+__device__ __forceinline__ void scene_pose_obj_body(const FusedArgs& a, const ScenePoseObjArgs& p, uint32_t blk, uint32_t n_blk, uint32_t n_rays, uint32_t v0,
+        size_t row) {
     using S = FusedShape<EPAD, W, NH>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     half_t* frags = reinterpret_cast<half_t*>(smem);
@@ -67,7 +72,8 @@ __global__ void __launch_bounds__(256) k_scene_pose_obj(FusedArgs a, ScenePoseOb
 #pragma unroll
     for (int d = 0; d < 3; ++d) ext[d] = a.oc.aabb.mx[d] - a.oc.aabb.mn[d];
     float acc[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
-    for (uint32_t ray = blockIdx.x * S::WAVES + wave; ray < p.n_rays; ray += gridDim.x * S::WAVES) {
+    for (uint32_t rl = blk * S::WAVES + wave; rl < n_rays; rl += n_blk * S::WAVES) {
+        const uint32_t ray = v0 + rl;
         const float4* rr = p.rec + 3 * (size_t)ray;
         const float4 r0 = rr[0], r1 = rr[1], r2 = rr[2];
         const float ro[3] = { r0.x, r0.y, r0.z }, rd[3] = { r1.x, r1.y, r1.z };
@@ -166,9 +172,22 @@ __global__ void __launch_bounds__(256) k_scene_pose_obj(FusedArgs a, ScenePoseOb
         if (threadIdx.x < 8) {
             float s = 0.f;
             for (int w = 0; w < S::WAVES; ++w) s += red[w * 8 + threadIdx.x];
-            p.partials[(size_t)blockIdx.x * 8 + threadIdx.x] = s;
+            p.partials[row * 8 + threadIdx.x] = s;
         }
     }
+}
+template <int EPAD, int W, int NH, bool LW, bool BWD>
+__global__ void __launch_bounds__(256) k_scene_pose_obj(FusedArgs a, ScenePoseObjArgs p) {
+    scene_pose_obj_body<EPAD, W, NH, LW, BWD>(a, p, blockIdx.x, gridDim.x, p.n_rays, 0u, (size_t)blockIdx.x);
+}
+// The backward of one pass of a window (mon_scene_window_loss / mon_scene_refine_window), grid (workgroups, frames of the pass): workgroup (b, f) is workgroup
+// b of the backward a single-frame call of frame f's N_f rays launches on gridc_f workgroups -- the same rays in the same order into the same sums -- and
+// writes row row0_f + b of the object's partial rows.  Workgroups beyond the frame's own grid leave before any barrier.
+template <int EPAD, int W, int NH, bool LW>
+__global__ void __launch_bounds__(256) k_scene_window_obj(FusedArgs a, ScenePoseObjArgs p, const SceneWinFrame* __restrict__ frames) {
+    const SceneWinFrame fr = frames[blockIdx.y];
+    if (blockIdx.x >= fr.gridc) return;
+    scene_pose_obj_body<EPAD, W, NH, LW, true>(a, p, blockIdx.x, fr.gridc, fr.n_rays, fr.v0, (size_t)fr.row0 + blockIdx.x);
 }
 
 // ------------------------------------------------------------------ k_scene_composite_grad
@@ -184,7 +203,8 @@ __device__ __forceinline__ float suffix_add64(float v) {
 //   dL/dalpha_i = T_i q_i - sum_{n > i} w_n q_n / (1 - alpha_i)       (so that dL/dsigma_i = dt_i (T_{i+1} q_i - sum_{n > i} w_n q_n))
 // Every merged sample's list slot receives {dL/dalpha, w} (0, 0 from the cut on); the ray's row receives {G_rgb, l}.  The workgroup's rays' losses are summed
 // in ray order into loss_part[blockIdx.x].
-__global__ void __launch_bounds__(64) k_scene_composite_grad(SceneCompGradArgs a) {
+// The walk: rays r = r0, r0 + stride, ... < n_rays at the lists' slots v0 + r; returns the sum of their losses in that order.
+__device__ __forceinline__ float scene_composite_grad_walk(const SceneCompGradArgs& a, uint32_t r0, uint32_t n_rays, uint32_t stride, uint32_t v0) {
     constexpr uint32_t L2S = kSceneListLen;
     const uint32_t n_lists = a.n_lists, cap = a.cap;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -198,7 +218,8 @@ __global__ void __launch_bounds__(64) k_scene_composite_grad(SceneCompGradArgs a
     float* s_T = s_q + n_lists;                                                        // [n_lists] entry transmittance of each 64-sample block
     const int lane = threadIdx.x;
     float loss_acc = 0.f;
-    for (uint32_t ray = blockIdx.x; ray < a.n_rays; ray += gridDim.x) {
+    for (uint32_t rl = r0; rl < n_rays; rl += stride) {
+        const uint32_t ray = v0 + rl;
         SceneRayFwd f;
         scene_composite_ray<true>(a, ray, lane, s_perm, s_id, s_c, s_tf, s_tl, s_w, s_q, s_T, f);
         const uint32_t na = f.na, n_tot = f.n_tot, n_blocks = f.n_blocks, n_done = f.n_done;
@@ -239,7 +260,20 @@ __global__ void __launch_bounds__(64) k_scene_composite_grad(SceneCompGradArgs a
         }
         __syncthreads();
     }
-    if (lane == 0) a.loss_part[blockIdx.x] = loss_acc;
+    return loss_acc;
+}
+__global__ void __launch_bounds__(64) k_scene_composite_grad(SceneCompGradArgs a) {
+    const float loss_acc = scene_composite_grad_walk(a, blockIdx.x, a.n_rays, gridDim.x, 0u);
+    if (threadIdx.x == 0) a.loss_part[blockIdx.x] = loss_acc;
+}
+// One pass of a window, grid (workgroups, frames of the pass): workgroup (b, f) walks rays b, b + parts_f, ... of frame f -- k_scene_composite_grad's walk of
+// a single-frame call of N_f rays on parts_f = scene_comp_grad_grid(N_f) workgroups -- and writes loss_part[lp0_f + b], as k_scene_composite_loss does per
+// hypothesis.  Workgroups beyond parts_f leave before any barrier.
+__global__ void __launch_bounds__(64) k_scene_window_composite(SceneCompGradArgs a, const SceneWinFrame* __restrict__ frames) {
+    const SceneWinFrame fr = frames[blockIdx.y];
+    if (blockIdx.x >= fr.parts) return;
+    const float loss_acc = scene_composite_grad_walk(a, blockIdx.x, fr.n_rays, fr.parts, fr.v0);
+    if (threadIdx.x == 0) a.loss_part[fr.lp0 + blockIdx.x] = loss_acc;
 }
 
 // ------------------------------------------------------------------ k_scene_pose_update
@@ -258,20 +292,7 @@ __global__ void __launch_bounds__(256) k_scene_pose_update(ScenePoseUpdateArgs a
         for (uint32_t b = grp; b < a.n_rows; b += 32u) s += rows[(size_t)b * 8 + col];
         part[grp][col] = s;
         __syncthreads();
-        if (threadIdx.x == 0) {
-            float v[6];
-            for (int k = 0; k < 6; ++k) { float q = 0.f; for (int g = 0; g < 32; ++g) q += part[g][k]; v[k] = q * a.inv_n; }
-            const float* Tow = a.objs[j].Tow; const float* Twc = a.pose;
-            float R[9], p[3];                                                           // Toc = Tow Twc, column-major 3x3
-            for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) {
-                float q = 0.f; for (int k = 0; k < 3; ++k) q += Tow[k * 4 + r] * Twc[c * 4 + k]; R[c * 3 + r] = q; }
-            for (int r = 0; r < 3; ++r) p[r] = Tow[r] * Twc[12] + Tow[4 + r] * Twc[13] + Tow[8 + r] * Twc[14] + Tow[12 + r];
-            const float m[3] = { v[3] - (p[1] * v[2] - p[2] * v[1]), v[4] - (p[2] * v[0] - p[0] * v[2]), v[5] - (p[0] * v[1] - p[1] * v[0]) };
-            for (int c = 0; c < 3; ++c) {                                               // R^T: row c of R^T is column c of R
-                grad[c] += R[c * 3] * v[0] + R[c * 3 + 1] * v[1] + R[c * 3 + 2] * v[2];
-                grad[3 + c] += R[c * 3] * m[0] + R[c * 3 + 1] * m[1] + R[c * 3 + 2] * m[2];
-            }
-        }
+        if (threadIdx.x == 0) { float v[6]; scene_rows_to_camera(part, a.inv_n, a.objs[j].Tow, a.pose, grad, v); }
         __syncthreads();
     }
     float ls = 0.f;
@@ -285,33 +306,7 @@ __global__ void __launch_bounds__(256) k_scene_pose_update(ScenePoseUpdateArgs a
     float* o = a.out + 8 * (size_t)a.it;
     o[0] = loss; for (int j = 0; j < 6; ++j) o[1 + j] = grad[j]; o[7] = 0.f;
     if (!a.step) return;
-    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
-    const float tt = (float)(a.it + 1u);
-    const float c1 = 1.f - powf(b1, tt), c2 = 1.f - powf(b2, tt);
-    float delta[6];
-    for (int j = 0; j < 6; ++j) {
-        const float g = grad[j];
-        const float m = b1 * a.moments[j] + (1.f - b1) * g, w = b2 * a.moments[6 + j] + (1.f - b2) * g * g;
-        a.moments[j] = m; a.moments[6 + j] = w;
-        const float lr = j < 3 ? a.lr_t : a.lr_r;
-        delta[j] = -lr * (m / c1) / (sqrtf(w / c2) + eps);
-    }
-    float Rd[9], td[3];
-    se3_exp(delta, Rd, td);
-    float* pose = a.pose;
-    float Rn[9], tn[3];                                                                 // Twc exp(delta^): R <- R Rd, t <- R td + t
-    for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) {
-        float q = 0.f; for (int k = 0; k < 3; ++k) q += pose[k * 4 + r] * Rd[c * 3 + k]; Rn[c * 3 + r] = q; }
-    for (int r = 0; r < 3; ++r) tn[r] = pose[r] * td[0] + pose[4 + r] * td[1] + pose[8 + r] * td[2] + pose[12 + r];
-    // Gram-Schmidt: column 0 normalised, column 1 made orthogonal to it and normalised, column 2 = c0 x c1
-    float* a0 = Rn; float* a1 = Rn + 3; float* a2 = Rn + 6;
-    float nn = rsqrtf(a0[0] * a0[0] + a0[1] * a0[1] + a0[2] * a0[2]); for (int r = 0; r < 3; ++r) a0[r] *= nn;
-    const float dp = a0[0] * a1[0] + a0[1] * a1[1] + a0[2] * a1[2]; for (int r = 0; r < 3; ++r) a1[r] -= dp * a0[r];
-    nn = rsqrtf(a1[0] * a1[0] + a1[1] * a1[1] + a1[2] * a1[2]); for (int r = 0; r < 3; ++r) a1[r] *= nn;
-    a2[0] = a0[1] * a1[2] - a0[2] * a1[1]; a2[1] = a0[2] * a1[0] - a0[0] * a1[2]; a2[2] = a0[0] * a1[1] - a0[1] * a1[0];
-    for (int c = 0; c < 3; ++c) { for (int r = 0; r < 3; ++r) pose[c * 4 + r] = Rn[c * 3 + r]; pose[c * 4 + 3] = 0.f; }
-    for (int r = 0; r < 3; ++r) pose[12 + r] = tn[r];
-    pose[15] = 1.f;
+    scene_camera_adam_step(grad, a.moments, a.lr_t, a.lr_r, a.it, a.pose);
 }
 
 // ------------------------------------------------------------------ launchers
@@ -326,6 +321,14 @@ static void scene_pose_obj_t(hipStream_t s, const FusedArgs& a, const ScenePoseO
     else hipLaunchKernelGGL((k_scene_pose_obj<EPAD, W, NH, false, true>), dim3(grid), dim3(256), smem, s, a, p);
 }
 
+template <int EPAD, int W, int NH>
+static void scene_window_obj_t(hipStream_t s, const FusedArgs& a, const ScenePoseObjArgs& p, uint32_t grid, uint32_t n_frames, const SceneWinFrame* frames) {
+    using S = FusedShape<EPAD, W, NH>;
+    const uint32_t smem = S::FRAG_BYTES + 512 + S::WAVES * 32;
+    if (p.level_w) hipLaunchKernelGGL((k_scene_window_obj<EPAD, W, NH, true>), dim3(grid, n_frames), dim3(256), smem, s, a, p, frames);
+    else hipLaunchKernelGGL((k_scene_window_obj<EPAD, W, NH, false>), dim3(grid, n_frames), dim3(256), smem, s, a, p, frames);
+}
+
 void launch_scene_pose_rays(hipStream_t s, const ScenePoseRayArgs& a) {
     if (!a.n_rays || !a.n_objs) return;
     hipLaunchKernelGGL(k_scene_pose_rays, dim3((a.n_rays + 255) / 256), dim3(256), 0, s, a);
@@ -336,10 +339,22 @@ void launch_scene_pose_obj(hipStream_t s, const LevelFast& lt, const NetDims& nd
     FusedArgs a{}; a.lt = lt; a.nd = nd; a.oc = oc; a.params = params; a.frag_image = frag_image;
     MON_FUSED_DISPATCH(scene_pose_obj_t, s, a, p, grid, backward, build_image);
 }
+// frames = the pass's first row of the device table; grid = the largest gridc among its n_frames frames
+void launch_scene_window_obj(hipStream_t s, const LevelFast& lt, const NetDims& nd, const ObjectConst& oc, const uint16_t* params, uint16_t* frag_image,
+        uint32_t grid, uint32_t n_frames, const SceneWinFrame* frames, const ScenePoseObjArgs& p) {
+    if (!grid || !n_frames) return;
+    FusedArgs a{}; a.lt = lt; a.nd = nd; a.oc = oc; a.params = params; a.frag_image = frag_image;
+    MON_FUSED_DISPATCH(scene_window_obj_t, s, a, p, grid, n_frames, frames);
+}
 uint32_t scene_comp_grad_grid(uint32_t n_rays) { return n_rays < kSceneLossParts ? (n_rays ? n_rays : 1u) : kSceneLossParts; }
 void launch_scene_composite_grad(hipStream_t s, const SceneCompGradArgs& a) {
     if (!a.n_rays || !a.n_lists || a.n_lists > kSceneMaxLists) return;
     hipLaunchKernelGGL(k_scene_composite_grad, dim3(scene_comp_grad_grid(a.n_rays)), dim3(64), scene_composite_grad_lds(a.n_lists), s, a);
+}
+// grid = the largest parts among the pass's n_frames frames
+void launch_scene_window_composite(hipStream_t s, const SceneCompGradArgs& a, uint32_t grid, uint32_t n_frames, const SceneWinFrame* frames) {
+    if (!grid || !n_frames || !a.n_lists || a.n_lists > kSceneMaxLists) return;
+    hipLaunchKernelGGL(k_scene_window_composite, dim3(grid, n_frames), dim3(64), scene_composite_grad_lds(a.n_lists), s, a, frames);
 }
 void launch_scene_pose_update(hipStream_t s, const ScenePoseUpdateArgs& a) {
     hipLaunchKernelGGL(k_scene_pose_update, dim3(1), dim3(256), 0, s, a);

@@ -771,6 +771,41 @@ int mon_online_refine_camera(mon_online* h, const mon_frame_bbox* obs, size_t n_
     if (rc == MON_OK) std::memcpy(Twc16_inout, pose, 64);
     return rc;
 }
+// joint refinement of a window of keyframes and the objects they see (mon_scene_refine_window on side 1), over the objects mon_online_refine_camera
+// chooses.  Tow16s_inout / included are indexed by the manager's object index.  Nothing of the manager changes.
+int mon_online_refine_window(mon_online* h, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, const mon_pose_c2f_params* c,
+        const mon_window_params* w, float* Twc16s_inout, float* Tow16s_inout, size_t n_objects, uint8_t* included, float* loss_trace, float* frame_trace) {
+    REQ(h); REQ(obs); REQ(p); REQ(w); REQ(Twc16s_inout);
+    if (n_obs == 0 || p->iters < 0) { set_error("refine_window: no boxes or iters < 0"); return MON_ERR_ARG; }
+    if (c) { const int rc = pose_c2f_check(c); if (rc) return rc; }
+    { const int rc = scene_window_params_check(obs, n_obs, Twc16s_inout, p, w, Tow16s_inout, true); if (rc) return rc; }
+    std::vector<Model*> ms; std::vector<size_t> idx;
+    const std::vector<OnlineObject*> objs = online_objects(*h->m);
+    if (n_objects != objs.size()) { set_error("refine_window: n_objects %zu, the manager holds %zu", n_objects, objs.size()); return MON_ERR_ARG; }
+    for (size_t i = 0; i < objs.size() && ms.size() < kSceneMaxLists; ++i)
+        if (objs[i]->model && model_has_snapshot(*objs[i]->model)) { ms.push_back(objs[i]->model); idx.push_back(i); }
+    if (ms.empty()) { set_error("refine_window: no object has published weights yet"); return MON_ERR_STATE; }
+    for (Model* m : ms) if (m->device != ms[0]->device) { set_error("refine_window: the objects span more than one device"); return MON_ERR_STATE; }
+    int Lmax = 0; for (Model* m : ms) Lmax = std::max(Lmax, (int)m->nd.L);
+    std::vector<float> table; if (c) table = pose_c2f_table(*c, Lmax, p->iters);
+    std::vector<float> tow; if (Tow16s_inout) { tow.resize(16 * ms.size()); for (size_t k = 0; k < ms.size(); ++k) std::memcpy(&tow[16 * k], Tow16s_inout + 16 * idx[k], 64); }
+    const int rc = scene_window(ms.data(), ms.size(), 1, obs, n_obs, Twc16s_inout, tow.empty() ? nullptr : tow.data(), *p, w, p->iters, 0u,
+                                table.empty() ? nullptr : table.data(), Twc16s_inout, tow.empty() ? nullptr : tow.data(), loss_trace, frame_trace, nullptr,
+                                nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    if (Tow16s_inout) for (size_t k = 0; k < ms.size(); ++k) std::memcpy(Tow16s_inout + 16 * idx[k], &tow[16 * k], 64);
+    if (included) { std::fill(included, included + n_objects, (uint8_t)0); for (size_t i : idx) included[i] = 1; }
+    return MON_OK;
+}
+// a refined object pose handed back to the object, under its model lock (announced so that a training slice lets the call in)
+int mon_online_set_object_pose(mon_online* h, size_t idx, const float* Tow16) {
+    REQ(h); REQ(Tow16);
+    OnlineObject* o = online_object(*h->m, idx); if (!o || !o->model) { set_error("NeRF Idx error ..."); return MON_ERR_ARG; }
+    AnnouncedLock lm(o, o->mu_model);
+    const int rc = model_set_pose(*o->model, Tow16); if (rc) return rc;
+    std::memcpy(o->Tow, Tow16, 64);
+    return MON_OK;
+}
 // wide-basin relocalisation against every object of the manager that has published weights (mon_scene_relocalise on side 1, safe while they train); the
 // objects are chosen as mon_online_refine_camera chooses them.  Nothing of the manager changes.
 int mon_online_relocalise(mon_online* h, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16_candidates, size_t n_candidates,

@@ -1721,6 +1721,7 @@ struct ScenePoseWs {
     float* dbg = nullptr; size_t dbg_cap = 0; uint32_t* dbg_cnt = nullptr; size_t dbg_cnt_cap = 0;
     float* poses = nullptr; size_t poses_cap = 0; float* scores = nullptr; size_t scores_cap = 0;   // scene_pose_batch: [hypotheses][16], [hypotheses]
     float* h_scores = nullptr; size_t h_scores_cap = 0;                                             // ... and their pinned staging
+    SceneWinFrame* wframes = nullptr; size_t wframes_cap = 0; float* wmom = nullptr; size_t wmom_cap = 0;   // scene_window: the frame table, moments [F + K][12]
     std::vector<hipEvent_t> ev;
 };
 static std::mutex g_scene_pose_mu; static std::map<std::pair<int, int>, ScenePoseWs*> g_scene_pose_ws;
@@ -2000,6 +2001,192 @@ int scene_pose_batch(Model* const* ms, size_t n, int side, const mon_frame_bbox*
     HIPCHECK(hipStreamSynchronize(s));
     HIPCHECK(hipGetLastError());
     std::memcpy(losses, w.h_scores, (size_t)H * 4);
+    return MON_OK;
+}
+
+// ---- window refinement (mon_scene_window_loss / mon_scene_refine_window): scene_pose's chain over the frames of a window, whole frames packed as virtual
+// rays into scene_pose's list workspace (passes of at most kWindowPassRays rays, greedily in window order): passes x (2K + 2) + 1 launches per evaluation,
+// every camera pose and every object's Tow on the device between steps, everything enqueued at once, one synchronisation.
+int window_frames(const mon_frame_bbox* obs, size_t n_obs, uint32_t* frame_ids, size_t* n_frames) {
+    if (!obs || !frame_ids || !n_frames) { set_error("window frames: null argument"); return MON_ERR_ARG; }
+    size_t F = 0;
+    for (size_t i = 0; i < n_obs; ++i) {
+        if (i && obs[i].FrameId == obs[i - 1].FrameId) continue;
+        for (size_t k = 0; k < F; ++k) if (frame_ids[k] == obs[i].FrameId) {
+            set_error("window frames: the boxes of frame %u are not contiguous (box %zu)", obs[i].FrameId, i); return MON_ERR_ARG; }
+        if (F == kWindowMaxFrames) { set_error("window frames: more than %u frames", kWindowMaxFrames); return MON_ERR_ARG; }
+        frame_ids[F++] = obs[i].FrameId;
+    }
+    *n_frames = F;
+    return MON_OK;
+}
+int scene_window_params_check(const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const mon_pose_refine_params* p, const mon_window_params* w,
+                              const float* Tow16s, bool refine) {
+    if (!obs || !Twc16s || !p || (refine && !w)) { set_error("scene window: null argument"); return MON_ERR_ARG; }
+    if (n_obs == 0) { set_error("scene window: no boxes"); return MON_ERR_ARG; }
+    if (p->iters < 0) { set_error("scene window: iters %d < 0", p->iters); return MON_ERR_ARG; }
+    uint32_t ids[kWindowMaxFrames]; size_t F = 0;
+    { const int rc = window_frames(obs, n_obs, ids, &F); if (rc) return rc; }
+    if (refine) {
+        if (w->n_fixed_frames > F) { set_error("scene window: n_fixed_frames %u of %zu frames", w->n_fixed_frames, F); return MON_ERR_ARG; }
+        if (!std::isfinite(w->lr_obj_trans) || !std::isfinite(w->lr_obj_rot) || w->lr_obj_trans < 0.f || w->lr_obj_rot < 0.f) {
+            set_error("scene window: object step sizes %g, %g (finite, >= 0)", w->lr_obj_trans, w->lr_obj_rot); return MON_ERR_ARG; }
+        if (w->refine_objects && w->n_fixed_frames == 0) {
+            set_error("scene window: refine_objects with no fixed frame (nothing would hold the map in place)"); return MON_ERR_ARG; }
+        if (w->refine_objects && !Tow16s) { set_error("scene window: refine_objects with a null Tow16s"); return MON_ERR_ARG; }
+    }
+    return MON_OK;
+}
+// the MON_ERR_ARG cases that need the objects; the caller has passed scene_window_params_check (the frames are contiguous, at most kWindowMaxFrames)
+int scene_window_frames_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const float* Tow16s,
+                              const mon_pose_refine_params* p) {
+    for (size_t i0 = 0, f = 0; i0 < n_obs; ++f) {
+        size_t i1 = i0 + 1; while (i1 < n_obs && obs[i1].FrameId == obs[i0].FrameId) ++i1;
+        { const int rc = scene_pose_check(ms, n, side, obs + i0, i1 - i0, Twc16s + 16 * f, p); if (rc) return rc; }
+        uint64_t total = 0; for (size_t i = i0; i < i1; ++i) total += (uint64_t)obs[i].w * obs[i].h;
+        const uint64_t n_rays = p->rays_per_iter ? p->rays_per_iter : total;
+        if (n_rays > kWindowPassRays) { set_error("scene window: %llu rays in frame %u (at most %u: a frame is never split across passes)",
+            (unsigned long long)n_rays, obs[i0].FrameId, kWindowPassRays); return MON_ERR_ARG; }
+        i0 = i1;
+    }
+    if (Tow16s) for (size_t k = 0; k < 16 * n; ++k) if (!std::isfinite(Tow16s[k])) {
+        set_error("scene window: Tow16s of object %zu is not finite", k / 16); return MON_ERR_ARG; }
+    return MON_OK;
+}
+int scene_window(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const float* Tow16s,
+                 const mon_pose_refine_params& p, const mon_window_params* wp, int iters, uint32_t iteration, const float* level_w, float* Twc16s_out,
+                 float* Tow16s_out, float* loss_trace, float* frame_trace, float* loss, float* frame_loss, float* cam_grad6, float* obj_grad6) {
+    { const int rc = scene_window_frames_check(ms, n, side, obs, n_obs, Twc16s, Tow16s, &p); if (rc) return rc; }
+    if (!launch_scene_window_rays || !launch_scene_pose_obj || !launch_scene_window_composite || !launch_scene_window_obj || !launch_scene_window_update ||
+        !scene_comp_grad_grid || !pose_grad_grid) { set_error("scene window: built without kernels_scene_window.hip"); return MON_ERR_STATE; }
+    int Lmax = 0;
+    { const int rc = scene_pose_state_check(ms, n, side, Lmax); if (rc) return rc; }
+    // the frames in window order, each with the grids a single-frame call of its rays uses; the passes
+    std::vector<SceneWinFrame> fr; std::vector<uint32_t> prefix; std::vector<uint32_t> pass0{ 0u };   // pass k holds frames [pass0[k], pass0[k + 1])
+    uint32_t row_stride = 0, n_lp = 0, cap = 0, v_next = 0;
+    for (size_t i0 = 0; i0 < n_obs; ) {
+        size_t i1 = i0 + 1; while (i1 < n_obs && obs[i1].FrameId == obs[i0].FrameId) ++i1;
+        SceneWinFrame f{}; f.pose = 16u * (uint32_t)fr.size(); f.box0 = (uint32_t)i0; f.n_box = (uint32_t)(i1 - i0); f.prefix0 = (uint32_t)prefix.size();
+        uint32_t total = 0; for (size_t i = i0; i < i1; ++i) { prefix.push_back(total); total += obs[i].w * obs[i].h; } prefix.push_back(total);
+        f.total = total; f.n_rays = p.rays_per_iter ? p.rays_per_iter : total; f.inv_n = 1.f / (float)f.n_rays;
+        if (v_next + f.n_rays > kWindowPassRays) { pass0.push_back((uint32_t)fr.size()); v_next = 0; }
+        f.v0 = v_next; v_next += f.n_rays; cap = std::max(cap, v_next);
+        f.gridc = pose_grad_grid(f.n_rays); f.row0 = row_stride; row_stride += f.gridc;
+        f.parts = scene_comp_grad_grid(f.n_rays); f.lp0 = n_lp; n_lp += f.parts;
+        fr.push_back(f); i0 = i1;
+    }
+    pass0.push_back((uint32_t)fr.size());
+    const uint32_t F = (uint32_t)fr.size(), n_pass = (uint32_t)pass0.size() - 1u;
+    const int device = ms[0]->device;
+    HIPCHECK(use_device(device));
+    const int n_eval = iters < 0 ? 1 : iters + 1;
+    ScenePoseSide sd; { const int rc = sd.enter(ms, n, side, device); if (rc) return rc; }
+    const std::vector<const uint16_t*>& prm = sd.prm; const hipStream_t s = sd.s; ScenePoseWs& w = *sd.w;
+    std::vector<size_t> frag_off(n + 1, 0);
+    for (size_t j = 0; j < n; ++j) { const NetDims& nd = ms[j]->nd; const FragDims fd{ nd.Epad, nd.W, nd.NH, nd.L }; frag_off[j + 1] = frag_off[j] + (size_t)fd.N_FRAGS() * 512; }
+    const size_t lists = n * (size_t)cap;
+    const uint32_t out_stride = 1u + 7u * F + 6u * (uint32_t)n;
+    constexpr size_t kObjFloats = sizeof(SceneObjConst) / 4;
+    const size_t out_floats = (size_t)out_stride * n_eval + 16 * (size_t)F + kObjFloats * n;      // the evaluations | every Twc | every SceneObjConst
+    int rc;
+    if ((rc = grow_buf(w.t, w.t_cap, lists * kSceneListLen)) || (rc = grow_buf(w.attr, w.attr_cap, lists * kSceneListLen)) ||
+        (rc = grow_buf(w.gw, w.gw_cap, lists * kSceneListLen)) || (rc = grow_buf(w.cnt, w.cnt_cap, lists)) || (rc = grow_buf(w.mstar, w.mstar_cap, lists)) ||
+        (rc = grow_buf(w.rec, w.rec_cap, lists * 3)) || (rc = grow_buf(w.ray, w.ray_cap, (size_t)cap * 3)) || (rc = grow_buf(w.grow, w.grow_cap, (size_t)cap)) ||
+        (rc = grow_buf(w.partials, w.part_cap, n * (size_t)row_stride * 8)) || (rc = grow_buf(w.loss_part, w.lp_cap, (size_t)n_lp)) ||
+        (rc = grow_buf(w.objs, w.objs_cap, n)) || (rc = grow_buf(w.frag, w.frag_cap, frag_off[n])) || (rc = grow_buf(w.boxes, w.box_cap, n_obs)) ||
+        (rc = grow_buf(w.prefix, w.prefix_cap, prefix.size())) || (rc = grow_buf(w.poses, w.poses_cap, (size_t)F * 16)) ||
+        (rc = grow_buf(w.wframes, w.wframes_cap, (size_t)F)) || (rc = grow_buf(w.wmom, w.wmom_cap, 12 * ((size_t)F + n))) ||
+        (rc = grow_buf(w.out, w.out_cap, out_floats))) return rc;
+    if (out_floats > w.h_out_cap) {
+        if (w.h_out) { (void)hipHostFree(w.h_out); w.h_out = nullptr; w.h_out_cap = 0; }
+        HIPCHECK(hipHostMalloc((void**)&w.h_out, out_floats * 4, hipHostMallocDefault)); w.h_out_cap = out_floats;
+    }
+    const int n_wrows = level_w ? (iters < 0 ? 1 : iters) : 0;
+    if (n_wrows) {
+        if ((rc = grow_buf(w.lw, w.lw_cap, (size_t)n_wrows * Lmax))) return rc;
+        HIPCHECK(hipMemcpyAsync(w.lw, level_w, sizeof(float) * (size_t)n_wrows * Lmax, hipMemcpyHostToDevice, s));
+    }
+    std::vector<SceneObjConst> h_objs(n);
+    for (size_t j = 0; j < n; ++j) { const ObjectConst& oc = ms[j]->oc; std::memcpy(h_objs[j].Tow, Tow16s ? Tow16s + 16 * j : oc.Tow.m, 64); h_objs[j].aabb = oc.aabb;
+        h_objs[j].instance_id = oc.instance_id; h_objs[j].pad = 0u; }
+    HIPCHECK(hipMemcpyAsync(w.objs, h_objs.data(), sizeof(SceneObjConst) * n, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(w.boxes, obs, sizeof(mon_frame_bbox) * n_obs, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(w.prefix, prefix.data(), 4 * prefix.size(), hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(w.poses, Twc16s, 64 * (size_t)F, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(w.wframes, fr.data(), sizeof(SceneWinFrame) * F, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(w.wmom, 0, 48 * ((size_t)F + n), s));
+    const bool drawn = p.rays_per_iter != 0;
+    for (int it = 0; it < n_eval; ++it) {
+        const uint32_t key = iters < 0 ? iteration : (uint32_t)it;
+        const float* lw_row = it < n_wrows ? w.lw + (size_t)it * Lmax : nullptr;
+        for (uint32_t k = 0; k < n_pass; ++k) {
+            const uint32_t f0 = pass0[k], nf = pass0[k + 1] - f0, nv = fr[f0 + nf - 1].v0 + fr[f0 + nf - 1].n_rays;
+            uint32_t gmax = 0, pmax = 0; for (uint32_t f = f0; f < f0 + nf; ++f) { gmax = std::max(gmax, fr[f].gridc); pmax = std::max(pmax, fr[f].parts); }
+            SceneWindowRayArgs ra{}; ra.boxes = w.boxes; ra.prefix = w.prefix; ra.n_rays = nv; ra.drawn = drawn ? 1u : 0u; ra.iteration = key; ra.seed = p.seed;
+            ra.ds = ms[0]->ds->ptrs(); ra.objs = w.objs; ra.n_objs = (uint32_t)n; ra.cap = cap; ra.pose = w.poses; ra.rec = w.rec; ra.mstar = w.mstar;
+            ra.ray = w.ray; ra.frames = w.wframes + f0; ra.n_frames = nf;
+            launch_scene_window_rays(s, ra);
+            std::vector<ScenePoseObjArgs> oa(n);
+            for (size_t j = 0; j < n; ++j) {
+                Model& m = *ms[j]; const size_t l0 = j * (size_t)cap; ScenePoseObjArgs& a = oa[j];
+                a = ScenePoseObjArgs{}; a.rec = w.rec + l0 * 3; a.n_rays = nv; a.ray0 = 0u;
+                a.seed = drawn ? p.seed : m.oc.sample_seed; a.stream = drawn ? kStreamPose : (uint32_t)kStreamRender; a.step = drawn ? key : 0u;
+                a.t = w.t + l0 * kSceneListLen; a.attr = w.attr + l0 * kSceneListLen; a.cnt = w.cnt + l0; a.gw = w.gw + l0 * kSceneListLen; a.grow = w.grow;
+                a.ray = w.ray; a.inv_n = 0.f; a.partials = w.partials + (size_t)j * row_stride * 8; a.level_w = lw_row;
+                launch_scene_pose_obj(s, m.lf, m.nd, m.oc, prm[j], w.frag + frag_off[j], it == 0 && k == 0, 0, pose_grad_grid(nv), a);
+            }
+            SceneCompGradArgs ca{}; ca.n_rays = nv; ca.n_lists = (uint32_t)n; ca.cap = cap; ca.t = w.t; ca.attr = w.attr; ca.cnt = w.cnt; ca.mstar = w.mstar;
+            ca.ray = w.ray; ca.w_rgb = p.w_rgb; ca.w_mask = p.w_mask; ca.w_depth = p.w_depth; ca.huber = p.depth_huber; ca.gw = w.gw; ca.grow = w.grow;
+            ca.loss_part = w.loss_part;
+            launch_scene_window_composite(s, ca, pmax, nf, w.wframes + f0);
+            for (size_t j = 0; j < n; ++j) { Model& m = *ms[j];
+                launch_scene_window_obj(s, m.lf, m.nd, m.oc, prm[j], w.frag + frag_off[j], gmax, nf, w.wframes + f0, oa[j]); }
+        }
+        SceneWindowUpdateArgs ua{}; ua.partials = w.partials; ua.n_objs = (uint32_t)n; ua.row_stride = row_stride; ua.loss_part = w.loss_part;
+        ua.frames = w.wframes; ua.n_frames = F; ua.n_fixed = wp ? wp->n_fixed_frames : F; ua.refine_objs = wp ? wp->refine_objects : 0; ua.objs = w.objs;
+        ua.poses = w.poses; ua.moments = w.wmom; ua.out = w.out; ua.out_stride = out_stride; ua.it = (uint32_t)it; ua.step = iters >= 0 && it < iters;
+        ua.lr_t = p.lr_trans; ua.lr_r = p.lr_rot; ua.lr_obj_t = wp ? wp->lr_obj_trans : 0.f; ua.lr_obj_r = wp ? wp->lr_obj_rot : 0.f;
+        launch_scene_window_update(s, ua);
+    }
+    HIPCHECK(hipGetLastError());
+    // results home through the pinned staging: every evaluation's row, then the poses, then the objects' constants (their Tow)
+    float* d_tail = w.out + (size_t)out_stride * n_eval;
+    launch_copy_params(s, reinterpret_cast<const uint16_t*>(w.poses), reinterpret_cast<uint16_t*>(d_tail), 32u * F);
+    launch_copy_params(s, reinterpret_cast<const uint16_t*>(w.objs), reinterpret_cast<uint16_t*>(d_tail + 16 * (size_t)F), (uint32_t)(2 * kObjFloats * n));
+    launch_copy_params(s, reinterpret_cast<const uint16_t*>(w.out), reinterpret_cast<uint16_t*>(w.h_out), (uint32_t)(out_floats * 2));
+    HIPCHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    const float* h = w.h_out;
+    if (loss) *loss = h[0];
+    if (frame_loss) std::memcpy(frame_loss, h + 1, 4 * (size_t)F);
+    if (cam_grad6) std::memcpy(cam_grad6, h + 1 + F, 24 * (size_t)F);
+    if (obj_grad6) std::memcpy(obj_grad6, h + 1 + 7 * (size_t)F, 24 * n);
+    for (int it = 0; it < n_eval; ++it) {
+        const float* r = h + (size_t)out_stride * it;
+        if (loss_trace) loss_trace[it] = r[0];
+        if (frame_trace) std::memcpy(frame_trace + (size_t)F * it, r + 1, 4 * (size_t)F);
+    }
+    const float* tail = h + (size_t)out_stride * n_eval;
+    if (Twc16s_out) for (uint32_t f = wp ? std::min(wp->n_fixed_frames, F) : F; f < F; ++f) std::memcpy(Twc16s_out + 16 * (size_t)f, tail + 16 * (size_t)f, 64);
+    if (Tow16s_out && wp && wp->refine_objects) for (size_t j = 0; j < n; ++j) std::memcpy(Tow16s_out + 16 * j, tail + 16 * (size_t)F + kObjFloats * j, 64);
+    return MON_OK;
+}
+
+// ---- storing an object pose (mon_object_set_pose): oc.Tow and nothing else.  Weights, optimizer state, counters, the occupancy grid and the render-skip grids
+// live in the object frame and stay; what was built under the old pose -- the candidate rays prepared for the coming iteration, a captured graph (its kernel
+// arguments hold oc by value) -- is dropped.
+int model_set_pose(Model& m, const float* Tow16) {
+    if (!Tow16) { set_error("set_pose: null Tow16"); return MON_ERR_ARG; }
+    for (int k = 0; k < 16; ++k) if (!std::isfinite(Tow16[k])) { set_error("set_pose: Tow16[%d] is not finite", k); return MON_ERR_ARG; }
+    if (m.scatter_pending) { set_error("set_pose: between the stages of an iteration (mon_object_train_stages)"); return MON_ERR_STATE; }
+    HIPCHECK(use_device(m.device));
+    {   // side 1 calls read oc.Tow under the device's inference lock, from any thread: the pose changes under it, between two of them
+        std::unique_lock<std::mutex> infer_lock;
+        if (m.infer && m.infer->shared) infer_lock = std::unique_lock<std::mutex>(m.infer->shared->mu);
+        std::memcpy(m.oc.Tow.m, Tow16, 64);
+    }
+    m.next_ready = false; m.points_ready = false;
+    drop_graph(m);
     return MON_OK;
 }
 

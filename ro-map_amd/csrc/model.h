@@ -417,6 +417,30 @@ struct SceneScoreRayArgs : ScenePoseRayArgs { uint32_t n_per, h0; };      // ray
 __attribute__((weak)) void launch_scene_score_rays(hipStream_t s, const SceneScoreRayArgs& a);
 __attribute__((weak)) void launch_scene_composite_loss(hipStream_t s, const SceneCompGradArgs& a, uint32_t n_per);
 __attribute__((weak)) void launch_scene_loss_reduce(hipStream_t s, const float* loss_part, uint32_t n_hyp, uint32_t n_parts, float inv_n, float* out);
+// Window refinement (mon_scene_window_loss / mon_scene_refine_window, kernels_scene_window.hip + the window kernels of kernels_scene_pose.hip).  A pass
+// packs whole frames as virtual rays v = v0_f + r into the list workspace of one evaluation, at most kWindowPassRays of them, greedily in window order.  One
+// row of the device table per frame; per pass k_scene_window_rays -> per object k_scene_pose_obj<.., false, false> over the virtual rays ->
+// k_scene_window_composite (grid (max parts_f, frames)) -> per object k_scene_window_obj (grid (max gridc_f, frames)); per evaluation k_scene_window_update.
+constexpr uint32_t kWindowMaxFrames = 32, kWindowPassRays = 16384;
+struct SceneWinFrame {
+    uint32_t pose;                                            // offset of its Twc in the pose array (floats)
+    uint32_t box0, n_box, prefix0, total;                     // its boxes, its own exclusive prefix sums (n_box + 1 entries at prefix0), its pixel total
+    uint32_t v0, n_rays; float inv_n;                         // its first virtual ray in its pass, N_f, 1 / N_f
+    uint32_t gridc, row0, parts, lp0;                         // a single-frame call's backward grid and loss partials; its first partial row / loss partial
+};
+struct SceneWindowRayArgs : ScenePoseRayArgs { const SceneWinFrame* frames; uint32_t n_frames; };   // the pass's rows; n_rays = its virtual rays; pose = every Twc
+struct SceneWindowUpdateArgs {
+    const float* partials; uint32_t n_objs, row_stride;       // object j's rows at j * row_stride * 8, frame f's from row0_f on
+    const float* loss_part; const SceneWinFrame* frames; uint32_t n_frames, n_fixed; int refine_objs;
+    SceneObjConst* objs; float* poses; float* moments;        // moments [n_frames + n_objs][12]: the cameras, then the objects
+    float* out; uint32_t out_stride, it; int step;            // out[out_stride * it] = {L, L_f [F], grad6_f [F][6], obj_grad6_j [K][6]}
+    float lr_t, lr_r, lr_obj_t, lr_obj_r;
+};
+__attribute__((weak)) void launch_scene_window_rays(hipStream_t s, const SceneWindowRayArgs& a);
+__attribute__((weak)) void launch_scene_window_composite(hipStream_t s, const SceneCompGradArgs& a, uint32_t grid, uint32_t n_frames, const SceneWinFrame* frames);
+__attribute__((weak)) void launch_scene_window_obj(hipStream_t s, const LevelFast& lt, const NetDims& nd, const ObjectConst& oc, const uint16_t* params,
+        uint16_t* frag_image, uint32_t grid, uint32_t n_frames, const SceneWinFrame* frames, const ScenePoseObjArgs& p);
+__attribute__((weak)) void launch_scene_window_update(hipStream_t s, const SceneWindowUpdateArgs& a);
 // inference on feature-planar level tiles (kernels_tilerender.hip): Render / RenderVideo, GetDensityOnGrid, mesh vertex colours
 constexpr uint32_t kTileChunkJobs = 32768;          // rays (jobs of 2S = 64 samples) per chunk of the tile render
 bool tile_render_supported(const LevelTable& lt, const NetDims& nd);
@@ -592,6 +616,20 @@ int scene_pose_batch_check(Model* const* ms, size_t n, int side, const mon_frame
                            const mon_pose_refine_params* p, const float* losses);
 int scene_pose_batch(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, size_t n_poses,
                      const mon_pose_refine_params& p, uint32_t iteration, float* losses);
+// mon_scene_window_loss / mon_scene_refine_window (include/mon_core.h): iters < 0 = one evaluation at `iteration` (wp may be nullptr; level_w one row of
+// Lmax or nullptr), else iters steps (level_w [iters][Lmax] or nullptr).  Tow16s nullptr = every object's own Tow.  Outputs may be nullptr; Twc16s_out /
+// Tow16s_out receive only the poses that moved.  window_frames: mon_window_frames.  The MON_ERR_ARG cases in two parts, neither with device work:
+// scene_window_params_check, what needs no object -- the caller of scene_window has passed it; scene_window_frames_check, what needs the objects (every
+// frame's scene_pose_check, the rays of a frame, a non-finite Tow16s) -- scene_window runs it.  model_set_pose: mon_object_set_pose.
+int window_frames(const mon_frame_bbox* obs, size_t n_obs, uint32_t* frame_ids, size_t* n_frames);
+int scene_window_params_check(const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const mon_pose_refine_params* p, const mon_window_params* w,
+                              const float* Tow16s, bool refine);
+int scene_window_frames_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const float* Tow16s,
+                              const mon_pose_refine_params* p);
+int scene_window(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const float* Tow16s,
+                 const mon_pose_refine_params& p, const mon_window_params* wp, int iters, uint32_t iteration, const float* level_w, float* Twc16s_out,
+                 float* Tow16s_out, float* loss_trace, float* frame_trace, float* loss, float* frame_loss, float* cam_grad6, float* obj_grad6);
+int model_set_pose(Model& m, const float* Tow16);
 // mon_scene_relocalise / mon_online_relocalise: the rule of include/mon_core.h over scene_pose_batch and scene_pose.  scene_reloc_check: its MON_ERR_ARG
 // cases, no device work.
 int scene_reloc_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* cands, size_t n_cands,

@@ -1,7 +1,8 @@
 // scene_device.h -- device code shared by the merge-composite kernels of the scene render (k_scene_composite, kernels_render.hip), of camera refinement
 // (k_scene_composite_grad, kernels_scene_pose.hip) and of batched pose scoring (k_scene_composite_loss, kernels_scene_score.hip): the compaction of one ray's
 // non-empty sample lists and the merged order of their samples; one drawn ray's targets and per-object records under a camera pose; the composite forward of
-// one ray with its loss.
+// one ray with its loss; the tail of an evaluation (rows -> camera-frame gradient, the Adam steps on a camera and on an object twist) shared with window
+// refinement (kernels_scene_window.hip).
 #pragma once
 #include "fused_device.h"
 #include "pose_device.h"
@@ -190,6 +191,71 @@ __device__ __forceinline__ void scene_composite_ray(const SceneCompGradArgs& a, 
     f.na = na; f.n_tot = n_tot; f.n_blocks = n_blocks; f.n_done = n_done;
     f.cs[0] = cs[0]; f.cs[1] = cs[1]; f.cs[2] = cs[2]; f.dstar = dstar; f.dn = dn; f.Mstar = Mstar;
     f.res[0] = res[0]; f.res[1] = res[1]; f.res[2] = res[2]; f.D = D; f.dep_on = dep_on;
+}
+
+// ---- the tail of an evaluation, shared by k_scene_pose_update and k_scene_window_update (one thread)
+// part = the 32 strided group sums of one object's partial rows: the groups in order, x 1/N -> v = G_j = (sum g_o, sum x_o x g_o) in the object frame; with
+// Toc_j = Tow_j Twc = (R, p): grad_rho += R^T G_rho, grad_phi += R^T (G_phi - p x G_rho).
+__device__ __forceinline__ void scene_rows_to_camera(const float (*part)[8], float inv_n, const float* Tow, const float* Twc, float (&grad)[6], float (&v)[6]) {
+    for (int k = 0; k < 6; ++k) { float q = 0.f; for (int g = 0; g < 32; ++g) q += part[g][k]; v[k] = q * inv_n; }
+    float R[9], p[3];                                                                   // Toc = Tow Twc, column-major 3x3
+    for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) {
+        float q = 0.f; for (int k = 0; k < 3; ++k) q += Tow[k * 4 + r] * Twc[c * 4 + k]; R[c * 3 + r] = q; }
+    for (int r = 0; r < 3; ++r) p[r] = Tow[r] * Twc[12] + Tow[4 + r] * Twc[13] + Tow[8 + r] * Twc[14] + Tow[12 + r];
+    const float m[3] = { v[3] - (p[1] * v[2] - p[2] * v[1]), v[4] - (p[2] * v[0] - p[0] * v[2]), v[5] - (p[0] * v[1] - p[1] * v[0]) };
+    for (int c = 0; c < 3; ++c) {                                                       // R^T: row c of R^T is column c of R
+        grad[c] += R[c * 3] * v[0] + R[c * 3 + 1] * v[1] + R[c * 3 + 2] * v[2];
+        grad[3 + c] += R[c * 3] * m[0] + R[c * 3 + 1] * m[1] + R[c * 3 + 2] * m[2];
+    }
+}
+// Adam (0.9, 0.999, 1e-8; bias correction by the step number it + 1) on a twist: moments[12] = m, v; delta = the step
+__device__ __forceinline__ void twist_adam(const float* grad, float* moments, float lr_t, float lr_r, uint32_t it, float (&delta)[6]) {
+    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
+    const float tt = (float)(it + 1u);
+    const float c1 = 1.f - powf(b1, tt), c2 = 1.f - powf(b2, tt);
+    for (int j = 0; j < 6; ++j) {
+        const float g = grad[j];
+        const float m = b1 * moments[j] + (1.f - b1) * g, w = b2 * moments[6 + j] + (1.f - b2) * g * g;
+        moments[j] = m; moments[6 + j] = w;
+        const float lr = j < 3 ? lr_t : lr_r;
+        delta[j] = -lr * (m / c1) / (sqrtf(w / c2) + eps);
+    }
+}
+// (Rn, tn) -> pose (column-major 4x4), the rotation re-orthonormalised by Gram-Schmidt: column 0 normalised, column 1 made orthogonal to it and normalised,
+// column 2 = c0 x c1
+__device__ __forceinline__ void pose_store_orthonormal(float (&Rn)[9], const float (&tn)[3], float* pose) {
+    float* a0 = Rn; float* a1 = Rn + 3; float* a2 = Rn + 6;
+    float nn = rsqrtf(a0[0] * a0[0] + a0[1] * a0[1] + a0[2] * a0[2]); for (int r = 0; r < 3; ++r) a0[r] *= nn;
+    const float dp = a0[0] * a1[0] + a0[1] * a1[1] + a0[2] * a1[2]; for (int r = 0; r < 3; ++r) a1[r] -= dp * a0[r];
+    nn = rsqrtf(a1[0] * a1[0] + a1[1] * a1[1] + a1[2] * a1[2]); for (int r = 0; r < 3; ++r) a1[r] *= nn;
+    a2[0] = a0[1] * a1[2] - a0[2] * a1[1]; a2[1] = a0[2] * a1[0] - a0[0] * a1[2]; a2[2] = a0[0] * a1[1] - a0[1] * a1[0];
+    for (int c = 0; c < 3; ++c) { for (int r = 0; r < 3; ++r) pose[c * 4 + r] = Rn[c * 3 + r]; pose[c * 4 + 3] = 0.f; }
+    for (int r = 0; r < 3; ++r) pose[12 + r] = tn[r];
+    pose[15] = 1.f;
+}
+// k_scene_pose_update's step: Adam on the camera twist and Twc <- Twc exp(delta^)
+__device__ __forceinline__ void scene_camera_adam_step(const float* grad, float* moments, float lr_t, float lr_r, uint32_t it, float* pose) {
+    float delta[6];
+    twist_adam(grad, moments, lr_t, lr_r, it, delta);
+    float Rd[9], td[3];
+    se3_exp(delta, Rd, td);
+    float Rn[9], tn[3];                                                                 // Twc exp(delta^): R <- R Rd, t <- R td + t
+    for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) {
+        float q = 0.f; for (int k = 0; k < 3; ++k) q += pose[k * 4 + r] * Rd[c * 3 + k]; Rn[c * 3 + r] = q; }
+    for (int r = 0; r < 3; ++r) tn[r] = pose[r] * td[0] + pose[4 + r] * td[1] + pose[8 + r] * td[2] + pose[12 + r];
+    pose_store_orthonormal(Rn, tn, pose);
+}
+// k_pose_update's step: Adam on the object twist and Tow <- exp(delta^) Tow
+__device__ __forceinline__ void scene_object_adam_step(const float* grad, float* moments, float lr_t, float lr_r, uint32_t it, float* pose) {
+    float delta[6];
+    twist_adam(grad, moments, lr_t, lr_r, it, delta);
+    float Rd[9], td[3];
+    se3_exp(delta, Rd, td);
+    float Rn[9], tn[3];
+    for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) {
+        float q = 0.f; for (int k = 0; k < 3; ++k) q += Rd[k * 3 + r] * pose[c * 4 + k]; Rn[c * 3 + r] = q; }
+    for (int r = 0; r < 3; ++r) tn[r] = Rd[r] * pose[12] + Rd[3 + r] * pose[13] + Rd[6 + r] * pose[14] + td[r];
+    pose_store_orthonormal(Rn, tn, pose);
 }
 
 }  // namespace mon
