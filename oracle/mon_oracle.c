@@ -958,11 +958,11 @@ void orc_density_grid(const orc_model* m, int rx, int ry, int rz, int use_ema, f
  * The reference has no such grid (it evaluates 32 uniform samples of every ray, nerf_model.cu:536-566): this restates the rule of THIS repository,
  *   cell look-up      device_common.h:31-40 occ_cell_live: cell = (int)(x * 64) per axis (truncation), clamped to [0, 63]; x fastest;
  *                     bit n of word w = cell 32 w + n
- *   threshold         model.cpp:659-672: dt = |box diagonal| / S, raw_threshold = logf(1e-3 / max(dt, 1e-6)) (alpha of one sample interval < 1e-3)
+ *   threshold         model.cpp model_init: dt = |box diagonal| / S, raw_threshold = logf(1e-3 / max(dt, 1e-6)) (alpha of one sample interval < 1e-3)
  *   grid update       kernels_render.hip:107-160 k_occ_density: raw density (output channel 3, fp16) of the CURRENT training weights at the cell centre
  *                     (c + 0.5) / 64, occupied when > threshold; k_occ_dilate: a cell is live when it or one of its 26 neighbours is occupied
  *   use               kernels_fused.hip k_fused_train<OCC>: a dead sample is not evaluated (zero features, alpha 0, dL/dO 0) -- forward_backward above
- *   schedule          model.cpp:1062-1075 maybe_refresh_occupancy, asked before every iteration (the eager path): the first refresh before iteration 256;
+ *   schedule          model.cpp maybe_refresh_occupancy, asked before every iteration (the eager path): the first refresh before iteration 256;
  *                     then due at the first iteration >= (iter / every + 1) every, every = 32 / 128 / 512 below 512 / below 2048 / after
  * Numerics: the HIP density sums the MLP in MFMA order, this restatement in one fmaf chain -- a cell whose density lies within a few fp16 ulp of the
  * threshold may come out differently (the ambiguity band the GPU tests allow). */

@@ -291,8 +291,6 @@ int mon_debug_scene_composite_grad(int device, uint32_t n_rays, uint32_t n_lists
         float M = 0.f; for (uint32_t k = 0; k < n_lists; ++k) M = std::max(M, mstar[(size_t)k * n_rays + r]);
         float* q = ray.data() + 12 * r; q[0] = cstar[3 * r]; q[1] = cstar[3 * r + 1]; q[2] = cstar[3 * r + 2]; q[3] = dstar[r]; q[4] = dn[r]; q[5] = M;
     }
-    if (!mon::launch_scene_composite_grad || !mon::scene_comp_grad_grid) { set_error("debug_scene_composite_grad: built without kernels_scene_pose.hip");
-        return MON_ERR_STATE; }
     HIPCHECK(mon::use_device(device));
     const uint32_t n_lp = mon::scene_comp_grad_grid(n_rays);
     const size_t b_t = ns * 4, b_a = ns * 16, b_c = nl * 4, b_m = nl * 4, b_ray = (size_t)n_rays * 48, b_gw = ns * 8, b_grow = (size_t)n_rays * 16,

@@ -14,7 +14,7 @@
 // Late in training (a few thousand samples) the per-tile fixed work outweighs ~10 us of atomics: every kernel here, and k_fused_train,
 // reads the previous iteration's gradient-carrying sample count from DevState and takes the same wave-uniform decision
 // (big_levels_binned, grid_walk.h) -- binned above `big_switch` samples, tcnn's global atomics inside k_fused_train below.  Once the
-// host has seen the count well below the switch it stops launching these kernels (model.cpp).  k_big_accum also sets the lazy
+// host has seen the count well below the switch it stops launching these kernels (model.cpp model_train).  k_big_accum also sets the lazy
 // optimizer's chunk flags (ParamPtrs::touched) next to every entry it writes.
 #include <atomic>
 #include <mutex>

@@ -567,7 +567,7 @@ void launch_state_unpack(hipStream_t s, const float* rec, int which, void* dst, 
 void launch_state_pack_master(hipStream_t s, const float* master, float* rec, uint32_t n) {
     hipLaunchKernelGGL(k_state_pack_master, dim3(2048), dim3(256), 0, s, master, rec, n);
 }
-// Checkpoints (model.cpp: model_save / model_load): RANGES of chunks between the optimizer state and a bounded flat staging buffer, 16 bytes per lane.
+// Checkpoints (checkpoint.cpp: model_save / model_load): RANGES of chunks between the optimizer state and a bounded flat staging buffer, 16 bytes per lane.
 // `which` as above, plus 4 = the lazy EMA's step of each chunk (word 28 of its record).  dst / src index 0 is chunk `first_chunk`.  Pieces:
 //   master / m1 / m2  a chunk's 8 floats are two 16-byte pieces of its record: one lane each, one 16-byte load, one 16-byte store
 //   steps             a chunk's 8 uint16 counters are ONE 16-byte piece <-> 8 uint32 (two 16-byte pieces of the flat array); one lane per chunk.  The same

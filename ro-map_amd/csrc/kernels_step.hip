@@ -1,14 +1,14 @@
 // kernels_step.hip -- NeRF_Model::Step (CORE/src/nerf_model.cu:1504-1550), the reference's schedule with per-ray SAMPLE compaction.
 // The reference marks it "unavailable, for reference only" and neither driver calls it; it is built here behind mon_set_option("step_variant", 1) on the
 // layer-at-a-time kernels (backend 0) so that the row exists and can be checked against a CPU restatement (tests/test_step_variant.py):
-//   1. inference of every sample with the training weights (:1509)                                   -> launch_encode + launch_mlp_forward (model.cpp)
+//   1. inference of every sample with the training weights (:1509)                                   -> launch_encode + launch_mlp_forward (model.cpp enqueue_iteration)
 //   2. VolumeRenderGradient (:957-1132), one thread per ray: composite until T < 1e-4 (numsteps), colour-only L2 loss, ONE background colour for all rays
 //      (the kernel's by-value copy of the generator: every thread draws the same three floats, :1038 -- here the iteration's first three RandColors), the
 //      numsteps positions and their dL/dO into a compacted batch.  Slots: the reference takes them with atomicAdd in arrival order; here an exclusive prefix
 //      sum over the rays (k_step_count -> k_step_scan -> k_step_gradient), so the batch -- and every result -- is deterministic.
 //   3. fill_rollover (:258-266) + fill_rollover_and_rescale (:269-279): the n compacted samples repeated cyclically up to the batch size B, the COPIES'
 //      gradients scaled by n / B (the originals keep theirs: `i < n * stride` returns early)            -> k_step_rollover
-//   4. forward + backward of the full-size compacted batch (:1545-1548) and the optimizer step           -> the backend-0 kernels (model.cpp)
+//   4. forward + backward of the full-size compacted batch (:1545-1548) and the optimizer step           -> the backend-0 kernels (model.cpp enqueue_iteration)
 #include "device_common.h"
 #include "model.h"
 

@@ -18,9 +18,7 @@
 #include <string>
 #include <vector>
 #include <dlfcn.h>
-#include <unistd.h>
-#include <zlib.h>
-#include "model.h"
+#include "model_internal.h"
 #include "xorwow.h"
 
 namespace mon {
@@ -30,10 +28,6 @@ void set_error(const char* fmt, ...) {
     char buf[1024]; va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap); g_err = buf;
 }
 const char* last_error() { return g_err.c_str(); }
-
-#define HIPCHECK(expr)                                                                                         \
-    do { hipError_t _e = (expr); if (_e != hipSuccess) {                                                       \
-        set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); return MON_ERR_HIP; } } while (0)
 
 static Options g_options;
 Options& options() { return g_options; }
@@ -88,12 +82,7 @@ int device_count(int* n) {
 
 // ------------------------------------------------------------------ dataset
 int dataset_destroy(Dataset* d);
-// One high-priority stream and one pinned result buffer per DEVICE, shared by the objects on it (viewer renders) and by the device's dataset (frame uploads):
-// created with the device's first object (CreateNeRF is a
-// milliseconds call anyway; created by the first render it was a 10 ms spike in front of the viewer), and only one more hardware-queue client however many
-// objects train (a high-priority queue per object measurably slowed sliced training).  Renders of one device take turns on it.
-// h_cap only grows; h_out / growth belong to mu
-struct InferShared { std::mutex mu; hipStream_t stream = nullptr; float* h_out = nullptr; std::atomic<size_t> h_cap{ 0 }; };
+// the devices' inference streams and pinned result buffers (InferShared, model_internal.h)
 static std::mutex g_infer_mu; static std::map<int, InferShared*> g_infer_shared;
 static int infer_shared_get(int device, size_t pixels_hint, InferShared** out) {
     InferShared* sh = nullptr;
@@ -436,30 +425,12 @@ int stream_pool_reserve(int device, int n) {
     return rc;
 }
 
-// ---- inference side of a model (the reference's second stream, nerf_model.cu:1268-1269).  The training thread PUBLISHES the inference weights
-// at the end of every train call / online slice: a device-to-device copy into one of two snapshot buffers, ordered on the train stream, with an
-// event.  A viewer thread renders from the latest published snapshot on the inference stream (created with the highest priority) and in a
-// workspace of its own: it takes no model mutex, never touches the train stream, and its kernels do not queue behind training slices.
-struct InferState {
-    InferShared* shared = nullptr;                                      // the device's inference stream (highest priority) and pinned result buffer
-    uint16_t* snap[2] = { nullptr, nullptr }; hipEvent_t ready[2] = { nullptr, nullptr }; uint32_t step_of[2] = { 0, 0 }; bool written[2] = { false, false };
-    int latest = -1, readers[2] = { 0, 0 }; std::mutex mu;              // which snapshot is current, who is reading which
-    // weights stamp of each snapshot (next_weights_epoch at publication: the tile render's image key)
-    uint64_t epoch_of[2] = { 0, 0 };
-    std::atomic<bool> wanted{ false }; std::chrono::steady_clock::time_point last_pub{};      // a viewer asked since the last publication; when that was
-    BatchPtrs rb{}; float *out_all = nullptr, *out_rgb = nullptr, *out_depth = nullptr, *out_mask = nullptr; size_t out_cap = 0; uint16_t* frag = nullptr;
-    std::vector<void*> grown;                                           // superseded output buffers, freed with the object
-    RenderSkipSide rskip;                                               // render skipping of the snapshot renders (under shared->mu, on its stream)
-};
-
 template <class T> static int dev_alloc(Model& m, T*& p, size_t n, bool zero = true) {
     void* q = nullptr; const size_t bytes = (n ? n : 1) * sizeof(T);
     HIPCHECK(hipMalloc(&q, bytes));
     if (zero) HIPCHECK(hipMemset(q, 0, bytes));
     m.allocs.push_back(q); p = (T*)q; return MON_OK;
 }
-
-static constexpr uint32_t kRenderChunkRays = 16384;   // rays per render pass (x 2S samples)
 
 // ---- render skipping (mon_object_set_render_skip): per side, a grid of the weights the render reads, cached per weights stamp and min_alpha
 static int rskip_alloc(Model& m, RenderSkipSide& k) {
@@ -469,9 +440,7 @@ static int rskip_alloc(Model& m, RenderSkipSide& k) {
     HIPCHECK(hipHostMalloc((void**)&k.h_stats, 16, hipHostMallocDefault)); std::memset(k.h_stats, 0, 16);
     return MON_OK;
 }
-// the side's grid of `prm` (stamp `epoch`) on stream s: the cached one, or built through the training grid's kernels into `frag`, the side's fragment image
-// of the same weights; nullptr when the side has no grid buffers
-static const uint32_t* rskip_grid(Model& m, RenderSkipSide& k, hipStream_t s, float alpha, const uint16_t* prm, uint64_t epoch, uint16_t* frag) {
+const uint32_t* rskip_grid(Model& m, RenderSkipSide& k, hipStream_t s, float alpha, const uint16_t* prm, uint64_t epoch, uint16_t* frag) {
     if (!k.d_grid) return nullptr;
     if (!k.pinned && (!k.built || k.epoch != epoch || k.alpha != alpha)) {
         if (alpha <= 0.f) {                                              // every cell live: no density pass
@@ -515,14 +484,11 @@ static int upload_master(Model& m, const float* master) {
     (void)hipFree(tmp); HIPCHECK(e); return MON_OK;
 }
 MeshState* mesh_state_create(int device);
-// (model_init's rule for the step counters; a checkpoint records which one its object kept)
-static bool steps16_exact(const mon_config& cfg) {
+bool steps16_exact(const mon_config& cfg) {
     const double kSteps16Bound = std::ldexp(1.0, -29);
     return kSteps16 && std::pow((double)cfg.beta1, 65535.0) < kSteps16Bound && std::pow((double)cfg.beta2, 65535.0) < kSteps16Bound;
 }
-// init_params = false (model_load): the parameters are left for the caller to stream in -- nothing of table size is staged
-static int model_init(Model& m, Dataset* ds, const mon_config& cfg, int class_id, const float* Tow, const float* amin, const float* amax,
-        bool init_params = true) {
+static int model_init(Model& m, Dataset* ds, const mon_config& cfg, int class_id, const float* Tow, const float* amin, const float* amax, bool init_params) {
     m.ds = ds; m.cfg = cfg; m.device = ds->device;
     int rc = level_table_build(cfg, m.lt, m.nd, m.n_grid);
     if (rc) return rc;
@@ -726,7 +692,7 @@ static int model_init(Model& m, Dataset* ds, const mon_config& cfg, int class_id
 // holds and make it the current one.  ~4 us of device-to-device copy at base.json size, ordered on the train stream.
 // A publication costs the owner thread ~15 us of host time (copy + event), which matters when the online manager trains in slices of a few
 // iterations: unless forced (long train calls, set_params), it happens when a viewer has asked since the last one or 10 ms have passed.
-static int publish_snapshot(Model& m, bool force = true) {
+int publish_snapshot(Model& m, bool force) {
     InferState* is = m.infer; if (!is) return MON_OK;
     const auto now = std::chrono::steady_clock::now();
     if (!force && is->latest >= 0 && !is->wanted.load() && now - is->last_pub < std::chrono::milliseconds(10)) return MON_OK;
@@ -746,9 +712,8 @@ static int publish_snapshot(Model& m, bool force = true) {
     return MON_OK;
 }
 
-int model_destroy(Model* mp);
-// what mon_object_create rejects before the level table is built (model_load runs a file's config through the same checks)
-static int config_check(const mon_config& cfg) {
+// (model_load runs a file's config through the same checks)
+int config_check(const mon_config& cfg) {
     if (cfg.rays_per_batch < 64 || (cfg.rays_per_batch % 64) != 0 || cfg.n_samples < 1 || cfg.n_samples > 64) {
         set_error("rays_per_batch must be a multiple of 64, n_samples 1..64"); return MON_ERR_ARG; }
     if ((cfg.rng_flags & 3u) == 3u || (cfg.rng_flags & ~0xffff0013u) != 0u || (cfg.rng_flags >> 16) > 1024u) {
@@ -760,8 +725,7 @@ static int config_check(const mon_config& cfg) {
         return MON_ERR_ARG; }
     return MON_OK;
 }
-static int model_create_impl(Dataset* ds, const mon_config& cfg, int class_id, const float* Tow, const float* amin, const float* amax, bool init_params,
-        Model** out) {
+int model_create_impl(Dataset* ds, const mon_config& cfg, int class_id, const float* Tow, const float* amin, const float* amax, bool init_params, Model** out) {
     if (!ds || !Tow || !amin || !amax) { set_error("object_create: bad argument"); return MON_ERR_ARG; }
     { const int rc = config_check(cfg); if (rc) return rc; }
     Model* mp = new Model();
@@ -776,7 +740,6 @@ int model_create(Dataset* ds, const mon_config& cfg, int class_id, const float* 
 static void drop_graph(Model& m) { if (m.graph_exec) { hipGraphExecDestroy(m.graph_exec); m.graph_exec = nullptr; m.graph_backend = -1; } }
 
 void model_mesh_free(Model& m);
-void pose_ws_free(Model& m);
 int model_destroy(Model* mp) {
     if (!mp) return MON_OK;
     Model& m = *mp; use_device(m.device);
@@ -1188,18 +1151,13 @@ int model_render_snapshot(Model& m, mon_frame_bbox box, const float* pose16, int
     if (!pose16 || !rgb || !depth || !mask || box.w == 0 || box.h == 0) { set_error("render: bad argument"); return MON_ERR_ARG; }
     InferState* is = m.infer; if (!is) { set_error("render_snapshot: this object renders on its train stream"); return MON_ERR_STATE; }
     InferShared* sh = is->shared; std::lock_guard<std::mutex> one(sh->mu);      // one snapshot render per device at a time
-    is->wanted.store(true);                                             // the training side refreshes the snapshot at the end of its current slice
-    int r;
-    {   std::lock_guard<std::mutex> l(is->mu); r = is->latest; if (r < 0) { set_error("render_snapshot: no weights published yet"); return MON_ERR_STATE; }
-        // the newest snapshot's copy may still be queued behind other objects' training kernels (it runs on the train stream, at normal priority: 1-2 ms on a
-        // busy device); the one before it is complete, and nobody writes it before the train stream has been synchronised again -- by which time the newest is
-        // complete and chosen here.  A viewer prefers a finished snapshot one slice older to waiting.
-        if (is->written[1 - r] && hipEventQuery(is->ready[r]) != hipSuccess && hipEventQuery(is->ready[1 - r]) == hipSuccess) r = 1 - r;
-        ++is->readers[r]; if (snapshot_step) *snapshot_step = is->step_of[r]; }
-    struct Release { InferState* is; int r; ~Release() { std::lock_guard<std::mutex> l(is->mu); --is->readers[r]; } } release{ is, r };
     HIPCHECK(use_device(m.device));
     hipStream_t s = sh->stream;
-    HIPCHECK(hipStreamWaitEvent(s, is->ready[r], 0));
+    SnapshotPin pin;
+    {   const int rc = pin.take(is, s);
+        if (rc == MON_ERR_STATE) set_error("render_snapshot: no weights published yet");
+        if (rc) return rc; }
+    const int r = pin.r; if (snapshot_step) *snapshot_step = pin.step;
     Mat4 pose; std::memcpy(pose.m, pose16, 64);
     const uint32_t n_pix = box.w * box.h, S2 = 2 * m.oc.S;
     // one buffer of 5 floats per pixel: rgb | depth | mask laid out back to back for THIS crop, so one copy brings them home
@@ -1216,7 +1174,7 @@ int model_render_snapshot(Model& m, mon_frame_bbox box, const float* pose16, int
     // 12 objects 0.58 / 3.1 against 0.67 / 1.7 -- so the tiles serve the viewer while few objects live on the device, the gathers once many do
     // (tile_ws_objects counts the tile-capable objects ALIVE on the device: in the online manager every live object has a training thread).
     TileWs* tws = nullptr; std::unique_lock<std::mutex> tile_lock;
-    uint64_t ep; { std::lock_guard<std::mutex> l(is->mu); ep = is->epoch_of[r]; }
+    const uint64_t ep = pin.epoch;
     // render skipping: the snapshot's own grid, built on this stream from the snapshot (stamp epoch_of[r]) through the side's fragment image
     const RenderSkipArgs sk = rskip_begin(m, is->rskip, s, m.rskip_on.load() != 0, m.rskip_alpha.load(), is->snap[r], ep, is->frag);
     // level tiles in LDS (kernels_tilerender.hip); the inference side's own workspace
@@ -1386,7 +1344,7 @@ int model_density_grid(Model& m, int rx, int ry, int rz, float* out_host) {
 }
 
 // ---- render skipping: the switch, its statistics, the grids
-static bool rskip_supported(const Model& m) { return m.backend == 1 && fused_supported(m.nd, m.oc.S, m.oc.R); }
+bool rskip_supported(const Model& m) { return m.backend == 1 && fused_supported(m.nd, m.oc.S, m.oc.R); }
 int model_set_render_skip(Model& m, int enable, float min_alpha) {
     if (!rskip_supported(m)) { set_error("set_render_skip: this object does not run on the fused kernels (layer-kernel backend)"); return MON_ERR_STATE; }
     if (!(min_alpha < 1.0f)) { set_error("set_render_skip: min_alpha must be < 1"); return MON_ERR_ARG; }
@@ -1436,740 +1394,9 @@ int model_debug_set_render_grid(Model& m, int side, const uint32_t* bits) {
     });
 }
 
-// ---- scene render (mon_scene_render): every object's sample lists of a chunk of the rect (k_fused_render<EMIT>), then one merge-composite launch
-// Per device and side, grow-only, never freed (like the tile workspaces): the lists of one chunk for every object, the rect's outputs, their pinned staging,
-// the events that order the objects' streams in front of side 0's render.  A render holds `mu` until its stream has been synchronised.
-struct SceneWs {
-    std::mutex mu;
-    float* t = nullptr; float* attr = nullptr; uint32_t* cnt = nullptr; size_t list_cap = 0;       // [lists][cap][kSceneListLen] t, float4 attr; [lists][cap]
-    float* out = nullptr; float* h_out = nullptr; size_t out_cap = 0;                                 // rgb 3n | depth n | opacity n | instance n (int32)
-    std::vector<hipEvent_t> ev;
-};
-static std::mutex g_scene_mu; static std::map<std::pair<int, int>, SceneWs*> g_scene_ws;
-static SceneWs& scene_ws(int device, int side) {
-    std::lock_guard<std::mutex> l(g_scene_mu); SceneWs*& w = g_scene_ws[{ device, side }]; if (!w) w = new SceneWs(); return *w;
-}
 bool model_has_snapshot(Model& m) {
     if (!m.infer) return false;
     std::lock_guard<std::mutex> l(m.infer->mu); return m.infer->latest >= 0;
-}
-int scene_render(Model* const* ms, size_t n, int side, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity, int32_t* instance,
-                 const int32_t* ids, const SceneDump* dump) {
-    if (!ms || n == 0 || !Twc16 || !rgb || !depth || rect.w == 0 || rect.h == 0) { set_error("scene_render: null or empty argument"); return MON_ERR_ARG; }
-    if (side != 0 && side != 1) { set_error("scene_render: side must be 0 or 1"); return MON_ERR_ARG; }
-    if (n > kSceneMaxLists) { set_error("scene_render: %zu objects (at most %u)", n, kSceneMaxLists); return MON_ERR_ARG; }
-    for (size_t j = 0; j < n; ++j) if (!ms[j]) { set_error("scene_render: null object %zu", j); return MON_ERR_ARG; }
-    const Intrinsics K = ms[0]->ds->K; const int device = ms[0]->device;
-    for (size_t j = 0; j < n; ++j) {
-        const Model& m = *ms[j]; const Intrinsics& k = m.ds->K;
-        if (m.device != device) { set_error("scene_render: objects on logical devices %d and %d", device, m.device); return MON_ERR_ARG; }
-        if (k.fx != K.fx || k.fy != K.fy || k.cx != K.cx || k.cy != K.cy || k.W != K.W || k.H != K.H) {
-            set_error("scene_render: object %zu has other intrinsics", j); return MON_ERR_ARG; }
-    }
-    for (size_t j = 0; j < n; ++j) {
-        const Model& m = *ms[j];
-        if (!rskip_supported(m) || 2u * m.oc.S != kSceneListLen) { set_error("scene_render: object %zu does not run on the fused kernels", j);
-            return MON_ERR_STATE; }
-        if (m.d_xw) { set_error("scene_render: object %zu renders with the XORWOW sample stream (rng_flags)", j); return MON_ERR_STATE; }
-        if (side == 1 && !model_has_snapshot(*ms[j])) { set_error("scene_render: object %zu has no published snapshot", j); return MON_ERR_STATE; }
-    }
-    HIPCHECK(use_device(device));
-    const uint32_t n_pix = rect.w * rect.h, cap = std::min(n_pix, kRenderChunkRays), L = (uint32_t)n;
-    Mat4 pose; std::memcpy(pose.m, Twc16, 64);
-    // what each object renders from: weights, their stamp, ray buffers, fragment image, render grid
-    struct Src { const uint16_t* prm; uint64_t epoch; BatchPtrs* b; uint16_t* frag; RenderSkipSide* rs; const uint32_t* bits; };
-    std::vector<Src> src(n);
-    std::unique_lock<std::mutex> dev_lock;                              // side 1: the device's snapshot-render mutex, then the workspace's
-    // side 1: the pinned snapshots, released on every way out
-    struct Pins { std::vector<std::pair<InferState*, int>> p; ~Pins() { for (auto& q : p) { std::lock_guard<std::mutex> l(q.first->mu); --q.first->readers[q.second]; } } } pins;
-    hipStream_t s;
-    if (side == 1) {
-        InferShared* sh = ms[0]->infer->shared; dev_lock = std::unique_lock<std::mutex>(sh->mu); s = sh->stream;
-        for (size_t j = 0; j < n; ++j) {
-            Model& m = *ms[j]; InferState* is = m.infer; is->wanted.store(true); int r;
-            {   std::lock_guard<std::mutex> l(is->mu); r = is->latest;
-                // (model_render_snapshot's rule: a finished older snapshot rather than waiting for a newer copy queued behind training)
-                if (is->written[1 - r] && hipEventQuery(is->ready[r]) != hipSuccess && hipEventQuery(is->ready[1 - r]) == hipSuccess) r = 1 - r;
-                ++is->readers[r]; pins.p.emplace_back(is, r); src[j].epoch = is->epoch_of[r]; }
-            HIPCHECK(hipStreamWaitEvent(s, is->ready[r], 0));
-            src[j].prm = is->snap[r]; src[j].b = &is->rb; src[j].frag = is->frag; src[j].rs = &is->rskip;
-        }
-    }
-    SceneWs& ws = scene_ws(device, side); std::lock_guard<std::mutex> wl(ws.mu);
-    if (side == 0) {
-        // the train side as model_render picks it (EMA once trained, brought up to date), every object's pending work ordered in front of object 0's stream
-        for (size_t j = 0; j < n; ++j) { Model& m = *ms[j]; model_leave_lane(m); int rc = ensure_ema_current(m); if (rc) return rc; }
-        s = ms[0]->train_stream;
-        while (ws.ev.size() < n) { hipEvent_t e; HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ws.ev.push_back(e); }
-        for (size_t j = 0; j < n; ++j) {
-            Model& m = *ms[j];
-            if (m.train_stream != s) { HIPCHECK(hipEventRecord(ws.ev[j], m.train_stream)); HIPCHECK(hipStreamWaitEvent(s, ws.ev[j], 0)); }
-            src[j].prm = (m.h_state.step > 0) ? m.P.ema : m.P.half; src[j].epoch = m.weights_epoch; src[j].b = &m.B; src[j].frag = m.d_frag_render;
-            src[j].rs = &m.rskip;
-        }
-    }
-    // render grids: the objects' own per-side caches (built if stale); the skip counters stay those of the objects' last own renders
-    for (size_t j = 0; j < n; ++j) {
-        Model& m = *ms[j];
-        src[j].bits = m.rskip_on.load() != 0 ? rskip_grid(m, *src[j].rs, s, m.rskip_alpha.load(), src[j].prm, src[j].epoch, src[j].frag) : nullptr;
-    }
-    // workspace (grow-only; nothing of it is in flight: every user synchronised before unlocking)
-    const size_t need_lists = (size_t)L * cap;
-    if (need_lists > ws.list_cap) {
-        if (ws.t) { (void)hipFree(ws.t); (void)hipFree(ws.attr); (void)hipFree(ws.cnt); ws.t = nullptr; ws.attr = nullptr; ws.cnt = nullptr; ws.list_cap = 0; }
-        HIPCHECK(hipMalloc((void**)&ws.t, need_lists * kSceneListLen * 4)); HIPCHECK(hipMalloc((void**)&ws.attr, need_lists * kSceneListLen * 16));
-        HIPCHECK(hipMalloc((void**)&ws.cnt, need_lists * 4)); ws.list_cap = need_lists;
-    }
-    if (n_pix > ws.out_cap) {
-        if (ws.out) { (void)hipFree(ws.out); (void)hipHostFree(ws.h_out); ws.out = nullptr; ws.h_out = nullptr; ws.out_cap = 0; }
-        HIPCHECK(hipMalloc((void**)&ws.out, 24 * (size_t)n_pix)); HIPCHECK(hipHostMalloc((void**)&ws.h_out, 24 * (size_t)n_pix, hipHostMallocDefault));
-        ws.out_cap = n_pix;
-    }
-    float* o_rgb = ws.out; float* o_depth = ws.out + 3 * (size_t)n_pix; float* o_op = ws.out + 4 * (size_t)n_pix;
-    int32_t* o_inst = reinterpret_cast<int32_t*>(ws.out + 5 * (size_t)n_pix);
-    std::vector<float> d_t, d_attr; std::vector<uint32_t> d_cnt;         // mon_debug_scene_samples: one list of the whole rect
-    if (dump) { d_t.resize((size_t)n_pix * kSceneListLen); d_attr.resize((size_t)n_pix * kSceneListLen * 4); d_cnt.resize(n_pix); }
-    for (uint32_t p0 = 0; p0 < n_pix; p0 += cap) {
-        const uint32_t nc = std::min(cap, n_pix - p0);
-        for (size_t j = 0; j < n; ++j) {
-            Model& m = *ms[j]; const size_t l0 = j * (size_t)cap;
-            launch_render_rays(s, *src[j].b, K, m.oc, rect, pose, 0, p0, nc);
-            launch_fused_render_emit(s, m.lf, m.nd, src[j].prm, *src[j].b, m.oc, nc, p0 * kSceneListLen, ws.t + l0 * kSceneListLen, ws.attr + l0 * kSceneListLen * 4,
-                    ws.cnt + l0, src[j].frag, p0 == 0u, src[j].bits);
-        }
-        // (every object's ray kernel wrote the same dn: it depends on the pixel and the intrinsics only)
-        launch_scene_composite(s, nc, L, cap, ws.t, ws.attr, ws.cnt, src[0].b->ray_dn, o_rgb + 3 * (size_t)p0, o_depth + p0, o_op + p0, o_inst + p0);
-        if (dump) {
-            const size_t l0 = dump->list * (size_t)cap;
-            HIPCHECK(hipMemcpyAsync(d_t.data() + (size_t)p0 * kSceneListLen, ws.t + l0 * kSceneListLen, (size_t)nc * kSceneListLen * 4, hipMemcpyDeviceToHost, s));
-            HIPCHECK(hipMemcpyAsync(d_attr.data() + (size_t)p0 * kSceneListLen * 4, ws.attr + l0 * kSceneListLen * 4, (size_t)nc * kSceneListLen * 16,
-                    hipMemcpyDeviceToHost, s));
-            HIPCHECK(hipMemcpyAsync(d_cnt.data() + p0, ws.cnt + l0, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
-            HIPCHECK(hipStreamSynchronize(s));
-        }
-    }
-    // results home through the pinned staging (a copy kernel on the render's stream, as the snapshot render does)
-    launch_copy_params(s, reinterpret_cast<const uint16_t*>(ws.out), reinterpret_cast<uint16_t*>(ws.h_out), (uint32_t)(12 * (size_t)n_pix));
-    HIPCHECK(hipStreamSynchronize(s));
-    HIPCHECK(hipGetLastError());
-    std::memcpy(rgb, ws.h_out, 12 * (size_t)n_pix); std::memcpy(depth, ws.h_out + 3 * (size_t)n_pix, 4 * (size_t)n_pix);
-    if (opacity) std::memcpy(opacity, ws.h_out + 4 * (size_t)n_pix, 4 * (size_t)n_pix);
-    if (instance) {
-        const int32_t* q = reinterpret_cast<const int32_t*>(ws.h_out + 5 * (size_t)n_pix);
-        for (uint32_t i = 0; i < n_pix; ++i) instance[i] = (q[i] >= 0 && ids) ? ids[q[i]] : q[i];
-    }
-    if (dump) {
-        for (size_t i = 0; i < (size_t)n_pix * kSceneListLen; ++i) {
-            if (dump->t) dump->t[i] = d_t[i];
-            if (dump->alpha) dump->alpha[i] = d_attr[4 * i];
-            if (dump->rgb) for (int c = 0; c < 3; ++c) dump->rgb[3 * i + c] = d_attr[4 * i + 1 + c];
-        }
-        if (dump->count) std::memcpy(dump->count, d_cnt.data(), 4 * (size_t)n_pix);
-    }
-    return MON_OK;
-}
-
-// ---- pose refinement (mon_object_pose_loss / mon_object_refine_pose): k_pose_rays -> k_pose_grad -> k_pose_update per evaluation, the pose in device memory
-// Per object and side, grow-only, freed with the object: a viewer (side 1) and the trainer (side 0) run at the same time.  A call holds `mu` until its stream
-// has been synchronised.
-struct PoseWs {
-    std::mutex mu;
-    float4* rec = nullptr; size_t rec_cap = 0;                                    // ray records, 4 float4 per drawn ray
-    float* out = nullptr; size_t out_cap = 0;                                     // {loss, grad6, 0} per evaluation
-    mon_frame_bbox* boxes = nullptr; uint32_t* prefix = nullptr; size_t box_cap = 0;
-    float* small = nullptr;                                                       // partials [kPoseMaxGrid][8] | pose [16] | moments [12]
-    uint16_t* frag = nullptr;                                                     // the A-fragment image, backward fragments included
-    float* dbg = nullptr; size_t dbg_cap = 0;                                     // mon_debug_pose_samples: x | raw | dL/dx of every sample
-    float* lw = nullptr; size_t lw_cap = 0;                                       // level weights [evaluation][L] of the weighted calls
-};
-static std::mutex g_pose_mu;
-static PoseWs& pose_ws(Model& m, int side) { std::lock_guard<std::mutex> l(g_pose_mu); if (!m.pose_ws[side]) m.pose_ws[side] = new PoseWs(); return *m.pose_ws[side]; }
-void pose_ws_free(Model& m) {
-    for (int k = 0; k < 2; ++k) {
-        PoseWs* w = m.pose_ws[k]; if (!w) continue;
-        for (void* q : { (void*)w->rec, (void*)w->out, (void*)w->boxes, (void*)w->prefix, (void*)w->small, (void*)w->frag, (void*)w->dbg, (void*)w->lw }) if (q) (void)hipFree(q);
-        delete w; m.pose_ws[k] = nullptr;
-    }
-}
-template <class T> static int grow_buf(T*& p, size_t& cap, size_t need) {
-    if (need <= cap && p) return MON_OK;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    HIPCHECK(hipMalloc((void**)&p, need * sizeof(T))); cap = need; return MON_OK;
-}
-uint32_t pose_n_rays(const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params& p) {
-    if (p.rays_per_iter) return p.rays_per_iter;
-    uint64_t t = 0; for (size_t i = 0; i < n_obs; ++i) t += (uint64_t)obs[i].w * obs[i].h;
-    return t > 0xffffffffull ? 0xffffffffu : (uint32_t)t;
-}
-int pose_refine(Model& m, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params& p, int iters,
-                uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const PoseDump* dump, const float* level_w) {
-    if (!obs || n_obs == 0 || !Tow16) { set_error("pose: null or empty argument"); return MON_ERR_ARG; }
-    if (side != 0 && side != 1) { set_error("pose: side must be 0 or 1"); return MON_ERR_ARG; }
-    if (p.rays_per_iter > kPoseMaxRays) { set_error("pose: rays_per_iter %u above %u", p.rays_per_iter, kPoseMaxRays); return MON_ERR_ARG; }
-    std::vector<uint32_t> prefix(n_obs + 1, 0u);
-    for (size_t i = 0; i < n_obs; ++i) {
-        const mon_frame_bbox& b = obs[i];
-        if (b.FrameId >= m.ds->max_frames || !m.ds->present[b.FrameId]) { set_error("pose: box %zu names frame %u, which the dataset does not hold", i, b.FrameId);
-            return MON_ERR_ARG; }
-        if (b.w == 0 || b.h == 0 || (uint64_t)b.x + b.w > (uint64_t)m.ds->K.W || (uint64_t)b.y + b.h > (uint64_t)m.ds->K.H) {
-            set_error("pose: box %zu (frame %u, x %u y %u h %u w %u) empty or outside the %dx%d frame", i, b.FrameId, b.x, b.y, b.h, b.w, m.ds->K.W, m.ds->K.H);
-            return MON_ERR_ARG; }
-        prefix[i + 1] = prefix[i] + b.w * b.h;                                      // (a frame is at most 2^31 pixels; 2^22 boxes of them would not fit)
-        if ((uint64_t)prefix[i] + (uint64_t)b.w * b.h > kPoseMaxRays * 64ull) { set_error("pose: the boxes hold too many pixels"); return MON_ERR_ARG; }
-    }
-    if (!launch_pose_rays || !launch_pose_grad || !launch_pose_update || !pose_grad_grid) { set_error("pose: built without kernels_pose.hip");
-        return MON_ERR_STATE; }
-    if (!rskip_supported(m) || 2u * m.oc.S != 64u) { set_error("pose: this object does not run on the fused kernels"); return MON_ERR_STATE; }
-    if (m.d_xw) { set_error("pose: this object renders with the XORWOW sample stream (rng_flags)"); return MON_ERR_STATE; }
-    if (side == 1 && !model_has_snapshot(m)) { set_error("pose: side 1 and nothing published yet"); return MON_ERR_STATE; }
-    const uint32_t total = prefix[n_obs], n_rays = p.rays_per_iter ? p.rays_per_iter : total;
-    if (!p.rays_per_iter && total > kPoseMaxRays) { set_error("pose: %u pixels in the boxes (at most %u with rays_per_iter = 0)", total, kPoseMaxRays);
-        return MON_ERR_ARG; }
-    HIPCHECK(use_device(m.device));
-    const int n_eval = iters < 0 ? 1 : iters + 1;
-    // the weights of the side, and its stream
-    hipStream_t s; const uint16_t* prm;
-    std::unique_lock<std::mutex> dev_lock;
-    struct Pin { InferState* is = nullptr; int r = 0; ~Pin() { if (is) { std::lock_guard<std::mutex> l(is->mu); --is->readers[r]; } } } pin;
-    if (side == 1) {
-        InferState* is = m.infer; InferShared* sh = is->shared; dev_lock = std::unique_lock<std::mutex>(sh->mu); s = sh->stream;
-        is->wanted.store(true); int r;
-        {   std::lock_guard<std::mutex> l(is->mu); r = is->latest;
-            if (is->written[1 - r] && hipEventQuery(is->ready[r]) != hipSuccess && hipEventQuery(is->ready[1 - r]) == hipSuccess) r = 1 - r;
-            ++is->readers[r]; pin.is = is; pin.r = r; }
-        HIPCHECK(hipStreamWaitEvent(s, is->ready[r], 0));
-        prm = is->snap[r];
-    } else {
-        model_leave_lane(m); { const int rc = ensure_ema_current(m); if (rc) return rc; }
-        s = m.train_stream; prm = (m.h_state.step > 0) ? m.P.ema : m.P.half;
-    }
-    PoseWs& w = pose_ws(m, side); std::lock_guard<std::mutex> wl(w.mu);
-    const FragDims fd{ m.nd.Epad, m.nd.W, m.nd.NH, m.nd.L };
-    int rc;
-    size_t c_small = 0, c_frag = 0, c_prefix = 0;
-    if ((rc = grow_buf(w.rec, w.rec_cap, 4 * (size_t)n_rays)) || (rc = grow_buf(w.out, w.out_cap, 8 * (size_t)n_eval))) return rc;
-    if (n_obs > w.box_cap || !w.boxes) { c_prefix = w.box_cap; if ((rc = grow_buf(w.prefix, c_prefix, n_obs + 1)) || (rc = grow_buf(w.boxes, w.box_cap, n_obs))) return rc; }
-    if (!w.small) { if ((rc = grow_buf(w.small, c_small, (size_t)kPoseMaxGrid * 8 + 16 + 12))) return rc; }
-    if (!w.frag) { if ((rc = grow_buf(w.frag, c_frag, (size_t)fd.N_FRAGS() * 512))) return rc; }
-    float* partials = w.small; float* d_pose = w.small + (size_t)kPoseMaxGrid * 8; float* d_mom = d_pose + 16;
-    float *dx = nullptr, *draw = nullptr, *dg = nullptr;
-    if (dump) {
-        if ((rc = grow_buf(w.dbg, w.dbg_cap, (size_t)n_rays * 64 * 10))) return rc;
-        dx = w.dbg; draw = w.dbg + (size_t)n_rays * 64 * 3; dg = w.dbg + (size_t)n_rays * 64 * 7;
-    }
-    // weighted: one row of L per evaluation that steps (or the one evaluation of iters < 0); the last evaluation of a refinement, whose gradient is not
-    // used, runs unweighted (the loss does not depend on the weights)
-    const int L = (int)m.nd.L, n_wrows = level_w ? (iters < 0 ? 1 : iters) : 0;
-    if (n_wrows) {
-        if ((rc = grow_buf(w.lw, w.lw_cap, (size_t)n_wrows * L))) return rc;
-        HIPCHECK(hipMemcpyAsync(w.lw, level_w, sizeof(float) * (size_t)n_wrows * L, hipMemcpyHostToDevice, s));
-    }
-    HIPCHECK(hipMemcpyAsync(w.boxes, obs, sizeof(mon_frame_bbox) * n_obs, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(w.prefix, prefix.data(), 4 * (n_obs + 1), hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(d_pose, Tow16, 64, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemsetAsync(d_mom, 0, 48, s));
-    const bool drawn = p.rays_per_iter != 0;
-    const uint32_t grid = pose_grad_grid(n_rays);
-    for (int it = 0; it < n_eval; ++it) {
-        const uint32_t key = iters < 0 ? iteration : (uint32_t)it;
-        PoseRayArgs ra{}; ra.boxes = w.boxes; ra.prefix = w.prefix; ra.n_obs = (uint32_t)n_obs; ra.n_rays = n_rays; ra.total = total; ra.drawn = drawn ? 1u : 0u;
-        ra.iteration = key; ra.seed = p.seed; ra.ds = m.ds->ptrs(); ra.aabb = m.oc.aabb; ra.instance_id = m.oc.instance_id; ra.pose = d_pose; ra.rec = w.rec;
-        launch_pose_rays(s, ra);
-        PoseGradArgs ga{}; ga.rec = w.rec; ga.n_rays = n_rays;
-        ga.seed = drawn ? p.seed : m.oc.sample_seed; ga.stream = drawn ? kStreamPose : (uint32_t)kStreamRender; ga.step = drawn ? key : 0u;
-        ga.w_rgb = p.w_rgb; ga.w_mask = p.w_mask; ga.w_depth = p.w_depth; ga.huber = p.depth_huber; ga.inv_n = 1.f / (float)n_rays;
-        ga.partials = partials; ga.dbg_x = dx; ga.dbg_raw = draw; ga.dbg_g = dg;
-        launch_pose_grad(s, m.lf, m.nd, m.oc, prm, w.frag, it == 0, ga, it < n_wrows ? w.lw + (size_t)it * L : nullptr);
-        launch_pose_update(s, partials, grid, 1.f / (float)n_rays, w.out, nullptr, (uint32_t)it, iters >= 0 && it < iters, p.lr_trans, p.lr_rot, d_pose, d_mom);
-    }
-    HIPCHECK(hipGetLastError());
-    std::vector<float> h_out(8 * (size_t)n_eval); float h_pose[16];
-    HIPCHECK(hipMemcpyAsync(h_out.data(), w.out, 32 * (size_t)n_eval, hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipMemcpyAsync(h_pose, d_pose, 64, hipMemcpyDeviceToHost, s));
-    std::vector<float> h_dbg;
-    if (dump) { h_dbg.resize((size_t)n_rays * 64 * 10); HIPCHECK(hipMemcpyAsync(h_dbg.data(), w.dbg, h_dbg.size() * 4, hipMemcpyDeviceToHost, s)); }
-    HIPCHECK(hipStreamSynchronize(s));
-    HIPCHECK(hipGetLastError());
-    if (loss) *loss = h_out[0];
-    if (grad6) for (int j = 0; j < 6; ++j) grad6[j] = h_out[1 + j];
-    if (loss_trace) for (int it = 0; it < n_eval; ++it) loss_trace[it] = h_out[8 * (size_t)it];
-    if (pose_out) std::memcpy(pose_out, h_pose, 64);
-    if (dump) {
-        const size_t ns = (size_t)n_rays * 64;
-        if (dump->x) std::memcpy(dump->x, h_dbg.data(), ns * 12);
-        if (dump->raw) std::memcpy(dump->raw, h_dbg.data() + ns * 3, ns * 16);
-        if (dump->dldx) std::memcpy(dump->dldx, h_dbg.data() + ns * 7, ns * 12);
-    }
-    return MON_OK;
-}
-
-// ---- camera refinement against a scene of objects (mon_scene_pose_loss / mon_scene_refine_camera): per evaluation and chunk of rays k_scene_pose_rays ->
-// every object's k_scene_pose_obj (forward) -> k_scene_composite_grad -> every object's k_scene_pose_obj (backward), then k_scene_pose_update; the camera
-// pose lives in device memory between steps.  Per device and side, grow-only, never freed (like SceneWs, whose users are untouched).  A call holds `mu` until
-// its stream has been synchronised.
-struct ScenePoseWs {
-    std::mutex mu;
-    float* t = nullptr; size_t t_cap = 0; float4* attr = nullptr; size_t attr_cap = 0; float2* gw = nullptr; size_t gw_cap = 0;   // [objects][cap][64]
-    uint32_t* cnt = nullptr; size_t cnt_cap = 0; float* mstar = nullptr; size_t mstar_cap = 0; float4* rec = nullptr; size_t rec_cap = 0;   // [objects][cap]( x 3)
-    float4* ray = nullptr; size_t ray_cap = 0; float4* grow = nullptr; size_t grow_cap = 0;                                   // [cap] x 3, [cap]
-    float* partials = nullptr; size_t part_cap = 0; float* loss_part = nullptr; size_t lp_cap = 0;
-    SceneObjConst* objs = nullptr; size_t objs_cap = 0; uint16_t* frag = nullptr; size_t frag_cap = 0;
-    mon_frame_bbox* boxes = nullptr; size_t box_cap = 0; uint32_t* prefix = nullptr; size_t prefix_cap = 0;
-    float* small = nullptr; size_t small_cap = 0;                                 // pose [16] | moments [12]
-    float* out = nullptr; size_t out_cap = 0; float* h_out = nullptr; size_t h_out_cap = 0;   // {loss, grad6, 0} per evaluation | pose; pinned staging
-    float* lw = nullptr; size_t lw_cap = 0;                                       // level weights [evaluation][Lmax]
-    float* dbg = nullptr; size_t dbg_cap = 0; uint32_t* dbg_cnt = nullptr; size_t dbg_cnt_cap = 0;
-    float* poses = nullptr; size_t poses_cap = 0; float* scores = nullptr; size_t scores_cap = 0;   // scene_pose_batch: [hypotheses][16], [hypotheses]
-    float* h_scores = nullptr; size_t h_scores_cap = 0;                                             // ... and their pinned staging
-    SceneWinFrame* wframes = nullptr; size_t wframes_cap = 0; float* wmom = nullptr; size_t wmom_cap = 0;   // scene_window: the frame table, moments [F + K][12]
-    std::vector<hipEvent_t> ev;
-};
-static std::mutex g_scene_pose_mu; static std::map<std::pair<int, int>, ScenePoseWs*> g_scene_pose_ws;
-static ScenePoseWs& scene_pose_ws(int device, int side) {
-    std::lock_guard<std::mutex> l(g_scene_pose_mu); ScenePoseWs*& w = g_scene_pose_ws[{ device, side }]; if (!w) w = new ScenePoseWs(); return *w;
-}
-int scene_pose_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16, const mon_pose_refine_params* p) {
-    if (!ms || !obs || !Twc16 || !p) { set_error("scene pose: null argument"); return MON_ERR_ARG; }
-    if (n == 0 || n > kSceneMaxLists) { set_error("scene pose: %zu objects (1 to %u)", n, kSceneMaxLists); return MON_ERR_ARG; }
-    for (size_t j = 0; j < n; ++j) if (!ms[j]) { set_error("scene pose: null object %zu", j); return MON_ERR_ARG; }
-    if (n_obs == 0) { set_error("scene pose: no boxes"); return MON_ERR_ARG; }
-    if (p->iters < 0) { set_error("scene pose: iters %d < 0", p->iters); return MON_ERR_ARG; }
-    if (side != 0 && side != 1) { set_error("scene pose: side %d (0 or 1)", side); return MON_ERR_ARG; }
-    if (p->rays_per_iter > kPoseMaxRays) { set_error("scene pose: rays_per_iter %u above %u", p->rays_per_iter, kPoseMaxRays); return MON_ERR_ARG; }
-    const Model& m0 = *ms[0]; const Intrinsics& K = m0.ds->K;
-    for (size_t j = 1; j < n; ++j) {
-        const Model& m = *ms[j]; const Intrinsics& k = m.ds->K;
-        if (m.device != m0.device) { set_error("scene pose: objects on logical devices %d and %d", m0.device, m.device); return MON_ERR_ARG; }
-        if (k.fx != K.fx || k.fy != K.fy || k.cx != K.cx || k.cy != K.cy || k.W != K.W || k.H != K.H) {
-            set_error("scene pose: object %zu has other intrinsics", j); return MON_ERR_ARG; }
-        if (m.ds != m0.ds) { set_error("scene pose: object %zu is on another dataset", j); return MON_ERR_ARG; }
-    }
-    uint64_t total = 0;
-    for (size_t i = 0; i < n_obs; ++i) {
-        const mon_frame_bbox& b = obs[i];
-        if (b.FrameId != obs[0].FrameId) { set_error("scene pose: boxes name frames %u and %u (one frame per call)", obs[0].FrameId, b.FrameId); return MON_ERR_ARG; }
-        if (b.FrameId >= m0.ds->max_frames || !m0.ds->present[b.FrameId]) { set_error("scene pose: box %zu names frame %u, which the dataset does not hold", i,
-            b.FrameId); return MON_ERR_ARG; }
-        if (b.w == 0 || b.h == 0 || (uint64_t)b.x + b.w > (uint64_t)K.W || (uint64_t)b.y + b.h > (uint64_t)K.H) {
-            set_error("scene pose: box %zu (frame %u, x %u y %u h %u w %u) empty or outside the %dx%d frame", i, b.FrameId, b.x, b.y, b.h, b.w, K.W, K.H);
-            return MON_ERR_ARG; }
-        total += (uint64_t)b.w * b.h;
-        if (total > kPoseMaxRays * 64ull) { set_error("scene pose: the boxes hold too many pixels"); return MON_ERR_ARG; }
-    }
-    if (!p->rays_per_iter && total > kPoseMaxRays) { set_error("scene pose: %llu pixels in the boxes (at most %u with rays_per_iter = 0)",
-        (unsigned long long)total, kPoseMaxRays); return MON_ERR_ARG; }
-    return MON_OK;
-}
-// every MON_ERR_STATE of a scene pose call that needs no device work; Lmax = the largest n_levels among the objects
-static int scene_pose_state_check(Model* const* ms, size_t n, int side, int& Lmax) {
-    Lmax = 0;
-    for (size_t j = 0; j < n; ++j) {
-        Model& m = *ms[j];
-        if (!rskip_supported(m) || 2u * m.oc.S != kSceneListLen) { set_error("scene pose: object %zu does not run on the fused kernels", j); return MON_ERR_STATE; }
-        if (m.d_xw) { set_error("scene pose: object %zu renders with the XORWOW sample stream (rng_flags)", j); return MON_ERR_STATE; }
-        if (side == 1 && !model_has_snapshot(m)) { set_error("scene pose: object %zu has no published snapshot", j); return MON_ERR_STATE; }
-        Lmax = std::max(Lmax, (int)m.nd.L);
-    }
-    return MON_OK;
-}
-// The weights of the side and its stream, as scene_render takes them, and the workspace.  Side 1: the shared inference stream under its device lock, every
-// object's newest ready snapshot pinned.  Side 0: object 0's train stream after every object's.  Holds the lock, the pins and the workspace until it goes
-// (after the call's stream has been synchronised).
-struct ScenePoseSide {
-    std::vector<const uint16_t*> prm; hipStream_t s = nullptr; ScenePoseWs* w = nullptr;
-    std::unique_lock<std::mutex> dev_lock;
-    struct Pins { std::vector<std::pair<InferState*, int>> p; ~Pins() { for (auto& q : p) { std::lock_guard<std::mutex> l(q.first->mu); --q.first->readers[q.second]; } } } pins;
-    std::unique_lock<std::mutex> wl;
-    int enter(Model* const* ms, size_t n, int side, int device) {
-        prm.assign(n, nullptr);
-        if (side == 1) {
-            InferShared* sh = ms[0]->infer->shared; dev_lock = std::unique_lock<std::mutex>(sh->mu); s = sh->stream;
-            for (size_t j = 0; j < n; ++j) {
-                InferState* is = ms[j]->infer; is->wanted.store(true); int r;
-                {   std::lock_guard<std::mutex> l(is->mu); r = is->latest;
-                    if (is->written[1 - r] && hipEventQuery(is->ready[r]) != hipSuccess && hipEventQuery(is->ready[1 - r]) == hipSuccess) r = 1 - r;
-                    ++is->readers[r]; pins.p.emplace_back(is, r); }
-                HIPCHECK(hipStreamWaitEvent(s, is->ready[r], 0));
-                prm[j] = is->snap[r];
-            }
-        }
-        w = &scene_pose_ws(device, side); wl = std::unique_lock<std::mutex>(w->mu);
-        if (side == 0) {
-            for (size_t j = 0; j < n; ++j) { Model& m = *ms[j]; model_leave_lane(m); int rc = ensure_ema_current(m); if (rc) return rc; }
-            s = ms[0]->train_stream;
-            while (w->ev.size() < n) { hipEvent_t e; HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); w->ev.push_back(e); }
-            for (size_t j = 0; j < n; ++j) {
-                Model& m = *ms[j];
-                if (m.train_stream != s) { HIPCHECK(hipEventRecord(w->ev[j], m.train_stream)); HIPCHECK(hipStreamWaitEvent(s, w->ev[j], 0)); }
-                prm[j] = (m.h_state.step > 0) ? m.P.ema : m.P.half;
-            }
-        }
-        return MON_OK;
-    }
-};
-int scene_pose(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16, const mon_pose_refine_params& p, int iters,
-               uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const ScenePoseDump* dump, const float* level_w) {
-    { const int rc = scene_pose_check(ms, n, side, obs, n_obs, Twc16, &p); if (rc) return rc; }
-    if (dump && dump->k >= n) { set_error("scene pose: dump of object %u of %zu", dump->k, n); return MON_ERR_ARG; }
-    if (!launch_scene_pose_rays || !launch_scene_pose_obj || !launch_scene_composite_grad || !launch_scene_pose_update || !scene_comp_grad_grid || !pose_grad_grid) {
-        set_error("scene pose: built without kernels_scene_pose.hip"); return MON_ERR_STATE; }
-    int Lmax = 0;
-    { const int rc = scene_pose_state_check(ms, n, side, Lmax); if (rc) return rc; }
-    std::vector<uint32_t> prefix(n_obs + 1, 0u);
-    for (size_t i = 0; i < n_obs; ++i) prefix[i + 1] = prefix[i] + obs[i].w * obs[i].h;
-    const uint32_t total = prefix[n_obs], n_rays = p.rays_per_iter ? p.rays_per_iter : total;
-    const int device = ms[0]->device;
-    HIPCHECK(use_device(device));
-    const int n_eval = iters < 0 ? 1 : iters + 1;
-    ScenePoseSide sd; { const int rc = sd.enter(ms, n, side, device); if (rc) return rc; }
-    const std::vector<const uint16_t*>& prm = sd.prm; const hipStream_t s = sd.s; ScenePoseWs& w = *sd.w;
-    // chunks of the rays (the cap scene_render chunks its rect by); each chunk's partial rows follow the previous chunk's
-    const uint32_t cap = std::min(n_rays, kRenderChunkRays), n_chunks = (n_rays + cap - 1u) / cap;
-    const uint32_t gridc = std::min(pose_grad_grid(cap), std::max(1u, kPoseMaxGrid / n_chunks)), n_rows = n_chunks * gridc;
-    uint32_t n_lp = 0; for (uint32_t c = 0; c < n_chunks; ++c) n_lp += scene_comp_grad_grid(std::min(cap, n_rays - c * cap));
-    std::vector<size_t> frag_off(n + 1, 0);
-    for (size_t j = 0; j < n; ++j) { const NetDims& nd = ms[j]->nd; const FragDims fd{ nd.Epad, nd.W, nd.NH, nd.L }; frag_off[j + 1] = frag_off[j] + (size_t)fd.N_FRAGS() * 512; }
-    const size_t lists = n * (size_t)cap;
-    int rc;
-    if ((rc = grow_buf(w.t, w.t_cap, lists * kSceneListLen)) || (rc = grow_buf(w.attr, w.attr_cap, lists * kSceneListLen)) ||
-        (rc = grow_buf(w.gw, w.gw_cap, lists * kSceneListLen)) || (rc = grow_buf(w.cnt, w.cnt_cap, lists)) || (rc = grow_buf(w.mstar, w.mstar_cap, lists)) ||
-        (rc = grow_buf(w.rec, w.rec_cap, lists * 3)) || (rc = grow_buf(w.ray, w.ray_cap, (size_t)cap * 3)) || (rc = grow_buf(w.grow, w.grow_cap, (size_t)cap)) ||
-        (rc = grow_buf(w.partials, w.part_cap, n * (size_t)n_rows * 8)) || (rc = grow_buf(w.loss_part, w.lp_cap, (size_t)n_lp)) ||
-        (rc = grow_buf(w.objs, w.objs_cap, n)) || (rc = grow_buf(w.frag, w.frag_cap, frag_off[n])) || (rc = grow_buf(w.boxes, w.box_cap, n_obs)) ||
-        (rc = grow_buf(w.prefix, w.prefix_cap, n_obs + 1)) || (rc = grow_buf(w.small, w.small_cap, (size_t)28)) ||
-        (rc = grow_buf(w.out, w.out_cap, 8 * (size_t)n_eval + 16))) return rc;
-    if (8 * (size_t)n_eval + 16 > w.h_out_cap) {
-        if (w.h_out) { (void)hipHostFree(w.h_out); w.h_out = nullptr; w.h_out_cap = 0; }
-        HIPCHECK(hipHostMalloc((void**)&w.h_out, (8 * (size_t)n_eval + 16) * 4, hipHostMallocDefault)); w.h_out_cap = 8 * (size_t)n_eval + 16;
-    }
-    if (dump) { if ((rc = grow_buf(w.dbg, w.dbg_cap, (size_t)n_rays * 64 * 14)) || (rc = grow_buf(w.dbg_cnt, w.dbg_cnt_cap, (size_t)n_rays))) return rc; }
-    const int n_wrows = level_w ? (iters < 0 ? 1 : iters) : 0;
-    if (n_wrows) {
-        if ((rc = grow_buf(w.lw, w.lw_cap, (size_t)n_wrows * Lmax))) return rc;
-        HIPCHECK(hipMemcpyAsync(w.lw, level_w, sizeof(float) * (size_t)n_wrows * Lmax, hipMemcpyHostToDevice, s));
-    }
-    std::vector<SceneObjConst> h_objs(n);
-    for (size_t j = 0; j < n; ++j) { const ObjectConst& oc = ms[j]->oc; std::memcpy(h_objs[j].Tow, oc.Tow.m, 64); h_objs[j].aabb = oc.aabb;
-        h_objs[j].instance_id = oc.instance_id; h_objs[j].pad = 0u; }
-    float* d_pose = w.small; float* d_mom = w.small + 16;
-    HIPCHECK(hipMemcpyAsync(w.objs, h_objs.data(), sizeof(SceneObjConst) * n, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(w.boxes, obs, sizeof(mon_frame_bbox) * n_obs, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(w.prefix, prefix.data(), 4 * (n_obs + 1), hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(d_pose, Twc16, 64, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemsetAsync(d_mom, 0, 48, s));
-    const bool drawn = p.rays_per_iter != 0;
-    const float inv_n = 1.f / (float)n_rays;
-    for (int it = 0; it < n_eval; ++it) {
-        const uint32_t key = iters < 0 ? iteration : (uint32_t)it;
-        const float* lw_row = it < n_wrows ? w.lw + (size_t)it * Lmax : nullptr;
-        uint32_t lp_off = 0;
-        for (uint32_t c = 0; c < n_chunks; ++c) {
-            const uint32_t p0 = c * cap, nc = std::min(cap, n_rays - p0);
-            ScenePoseRayArgs ra{}; ra.boxes = w.boxes; ra.prefix = w.prefix; ra.n_obs = (uint32_t)n_obs; ra.n_rays = nc; ra.ray0 = p0; ra.total = total;
-            ra.drawn = drawn ? 1u : 0u; ra.iteration = key; ra.seed = p.seed; ra.ds = ms[0]->ds->ptrs(); ra.objs = w.objs; ra.n_objs = (uint32_t)n; ra.cap = cap;
-            ra.pose = d_pose; ra.rec = w.rec; ra.mstar = w.mstar; ra.ray = w.ray;
-            launch_scene_pose_rays(s, ra);
-            std::vector<ScenePoseObjArgs> oa(n);
-            for (size_t j = 0; j < n; ++j) {
-                Model& m = *ms[j]; const size_t l0 = j * (size_t)cap; ScenePoseObjArgs& a = oa[j];
-                a = ScenePoseObjArgs{}; a.rec = w.rec + l0 * 3; a.n_rays = nc; a.ray0 = p0;
-                a.seed = drawn ? p.seed : m.oc.sample_seed; a.stream = drawn ? kStreamPose : (uint32_t)kStreamRender; a.step = drawn ? key : 0u;
-                a.t = w.t + l0 * kSceneListLen; a.attr = w.attr + l0 * kSceneListLen; a.cnt = w.cnt + l0; a.gw = w.gw + l0 * kSceneListLen; a.grow = w.grow;
-                a.ray = w.ray; a.inv_n = inv_n; a.partials = w.partials + ((size_t)j * n_rows + (size_t)c * gridc) * 8;
-                a.dbg = (dump && dump->k == j) ? w.dbg : nullptr; a.level_w = lw_row;
-                launch_scene_pose_obj(s, m.lf, m.nd, m.oc, prm[j], w.frag + frag_off[j], it == 0 && c == 0, 0, pose_grad_grid(nc), a);
-            }
-            SceneCompGradArgs ca{}; ca.n_rays = nc; ca.n_lists = (uint32_t)n; ca.cap = cap; ca.t = w.t; ca.attr = w.attr; ca.cnt = w.cnt; ca.mstar = w.mstar;
-            ca.ray = w.ray; ca.w_rgb = p.w_rgb; ca.w_mask = p.w_mask; ca.w_depth = p.w_depth; ca.huber = p.depth_huber; ca.gw = w.gw; ca.grow = w.grow;
-            ca.loss_part = w.loss_part + lp_off;
-            launch_scene_composite_grad(s, ca);
-            lp_off += scene_comp_grad_grid(nc);
-            for (size_t j = 0; j < n; ++j) { Model& m = *ms[j];
-                launch_scene_pose_obj(s, m.lf, m.nd, m.oc, prm[j], w.frag + frag_off[j], 0, 1, gridc, oa[j]); }
-            if (dump) HIPCHECK(hipMemcpyAsync(w.dbg_cnt + p0, w.cnt + dump->k * (size_t)cap, 4 * (size_t)nc, hipMemcpyDeviceToDevice, s));
-        }
-        ScenePoseUpdateArgs ua{}; ua.partials = w.partials; ua.n_objs = (uint32_t)n; ua.n_rows = n_rows; ua.row_stride = n_rows; ua.loss_part = w.loss_part;
-        ua.n_loss_parts = n_lp; ua.objs = w.objs; ua.inv_n = inv_n; ua.out = w.out; ua.it = (uint32_t)it; ua.step = iters >= 0 && it < iters;
-        ua.lr_t = p.lr_trans; ua.lr_r = p.lr_rot; ua.pose = d_pose; ua.moments = d_mom;
-        launch_scene_pose_update(s, ua);
-    }
-    HIPCHECK(hipGetLastError());
-    // results home through the pinned staging: {loss, grad6, 0} of every evaluation, then the pose
-    // (copy kernels on the call's stream, as the scene render's results go home)
-    launch_copy_params(s, reinterpret_cast<const uint16_t*>(d_pose), reinterpret_cast<uint16_t*>(w.out + 8 * (size_t)n_eval), 32u);
-    launch_copy_params(s, reinterpret_cast<const uint16_t*>(w.out), reinterpret_cast<uint16_t*>(w.h_out), (uint32_t)((8 * (size_t)n_eval + 16) * 2));
-    std::vector<float> h_dbg; std::vector<uint32_t> h_cnt;
-    if (dump) { h_dbg.resize((size_t)n_rays * 64 * 14); h_cnt.resize(n_rays);
-        HIPCHECK(hipMemcpyAsync(h_dbg.data(), w.dbg, h_dbg.size() * 4, hipMemcpyDeviceToHost, s));
-        HIPCHECK(hipMemcpyAsync(h_cnt.data(), w.dbg_cnt, (size_t)n_rays * 4, hipMemcpyDeviceToHost, s)); }
-    HIPCHECK(hipStreamSynchronize(s));
-    HIPCHECK(hipGetLastError());
-    const float* h = w.h_out;
-    if (loss) *loss = h[0];
-    if (grad6) for (int j = 0; j < 6; ++j) grad6[j] = h[1 + j];
-    if (loss_trace) for (int it = 0; it < n_eval; ++it) loss_trace[it] = h[8 * (size_t)it];
-    if (pose_out) std::memcpy(pose_out, h + 8 * (size_t)n_eval, 64);
-    if (dump) {
-        for (size_t i = 0; i < (size_t)n_rays * 64; ++i) {
-            const float* q = h_dbg.data() + 14 * i;
-            if (dump->x_o) std::memcpy(dump->x_o + 3 * i, q, 12);
-            if (dump->x_c) std::memcpy(dump->x_c + 3 * i, q + 3, 12);
-            if (dump->t) dump->t[i] = q[6];
-            if (dump->raw) std::memcpy(dump->raw + 4 * i, q + 7, 16);
-            if (dump->dldx) std::memcpy(dump->dldx + 3 * i, q + 11, 12);
-        }
-        if (dump->count) std::memcpy(dump->count, h_cnt.data(), 4 * (size_t)n_rays);
-    }
-    return MON_OK;
-}
-
-// ---- batched pose scoring (mon_scene_pose_loss_batch): the forward half of scene_pose's chain over n_poses camera poses.  A pass holds G = floor(cap / n)
-// hypotheses of n rays each as G n virtual rays in scene_pose's own list workspace (no more list memory than one evaluation of the chunk cap takes): K + 3
-// launches per pass, everything enqueued at once, one synchronisation, one copy home.
-static_assert(kSceneScoreMaxRays == kRenderChunkRays, "a hypothesis holds at most one chunk of scene_pose's rays");
-int scene_pose_batch_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, size_t n_poses,
-                           const mon_pose_refine_params* p, const float* losses) {
-    if (!Twc16s || !losses) { set_error("scene pose batch: null argument"); return MON_ERR_ARG; }
-    if (n_poses == 0 || n_poses > kSceneScoreMaxPoses) { set_error("scene pose batch: %zu poses (1 to %u)", n_poses, kSceneScoreMaxPoses); return MON_ERR_ARG; }
-    { const int rc = scene_pose_check(ms, n, side, obs, n_obs, Twc16s, p); if (rc) return rc; }
-    uint64_t total = 0; for (size_t i = 0; i < n_obs; ++i) total += (uint64_t)obs[i].w * obs[i].h;
-    const uint64_t n_rays = p->rays_per_iter ? p->rays_per_iter : total;
-    if (n_rays > kSceneScoreMaxRays) { set_error("scene pose batch: %llu rays per hypothesis (at most %u)", (unsigned long long)n_rays, kSceneScoreMaxRays);
-        return MON_ERR_ARG; }
-    return MON_OK;
-}
-int scene_pose_batch(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, size_t n_poses,
-                     const mon_pose_refine_params& p, uint32_t iteration, float* losses) {
-    { const int rc = scene_pose_batch_check(ms, n, side, obs, n_obs, Twc16s, n_poses, &p, losses); if (rc) return rc; }
-    if (!launch_scene_score_rays || !launch_scene_pose_obj || !launch_scene_composite_loss || !launch_scene_loss_reduce || !scene_comp_grad_grid || !pose_grad_grid) {
-        set_error("scene pose batch: built without kernels_scene_score.hip"); return MON_ERR_STATE; }
-    int Lmax = 0;
-    { const int rc = scene_pose_state_check(ms, n, side, Lmax); if (rc) return rc; }
-    std::vector<uint32_t> prefix(n_obs + 1, 0u);
-    for (size_t i = 0; i < n_obs; ++i) prefix[i + 1] = prefix[i] + obs[i].w * obs[i].h;
-    const uint32_t total = prefix[n_obs], n_rays = p.rays_per_iter ? p.rays_per_iter : total, H = (uint32_t)n_poses;
-    const int device = ms[0]->device;
-    HIPCHECK(use_device(device));
-    ScenePoseSide sd; { const int rc = sd.enter(ms, n, side, device); if (rc) return rc; }
-    const std::vector<const uint16_t*>& prm = sd.prm; const hipStream_t s = sd.s; ScenePoseWs& w = *sd.w;
-    // passes of Gmax whole hypotheses (n_rays <= the chunk cap, so Gmax >= 1); virtual ray v = g * n_rays + r at slot v of the lists
-    const uint32_t Gmax = std::min(H, kSceneScoreMaxRays / n_rays), cap = Gmax * n_rays, parts = scene_comp_grad_grid(n_rays);
-    std::vector<size_t> frag_off(n + 1, 0);
-    for (size_t j = 0; j < n; ++j) { const NetDims& nd = ms[j]->nd; const FragDims fd{ nd.Epad, nd.W, nd.NH, nd.L }; frag_off[j + 1] = frag_off[j] + (size_t)fd.N_FRAGS() * 512; }
-    const size_t lists = n * (size_t)cap;
-    int rc;
-    if ((rc = grow_buf(w.t, w.t_cap, lists * kSceneListLen)) || (rc = grow_buf(w.attr, w.attr_cap, lists * kSceneListLen)) ||
-        (rc = grow_buf(w.cnt, w.cnt_cap, lists)) || (rc = grow_buf(w.mstar, w.mstar_cap, lists)) || (rc = grow_buf(w.rec, w.rec_cap, lists * 3)) ||
-        (rc = grow_buf(w.ray, w.ray_cap, (size_t)cap * 3)) || (rc = grow_buf(w.loss_part, w.lp_cap, (size_t)Gmax * parts)) ||
-        (rc = grow_buf(w.objs, w.objs_cap, n)) || (rc = grow_buf(w.frag, w.frag_cap, frag_off[n])) || (rc = grow_buf(w.boxes, w.box_cap, n_obs)) ||
-        (rc = grow_buf(w.prefix, w.prefix_cap, n_obs + 1)) || (rc = grow_buf(w.poses, w.poses_cap, (size_t)H * 16)) ||
-        (rc = grow_buf(w.scores, w.scores_cap, (size_t)H))) return rc;
-    if (H > w.h_scores_cap) {
-        if (w.h_scores) { (void)hipHostFree(w.h_scores); w.h_scores = nullptr; w.h_scores_cap = 0; }
-        HIPCHECK(hipHostMalloc((void**)&w.h_scores, (size_t)H * 4, hipHostMallocDefault)); w.h_scores_cap = H;
-    }
-    std::vector<SceneObjConst> h_objs(n);
-    for (size_t j = 0; j < n; ++j) { const ObjectConst& oc = ms[j]->oc; std::memcpy(h_objs[j].Tow, oc.Tow.m, 64); h_objs[j].aabb = oc.aabb;
-        h_objs[j].instance_id = oc.instance_id; h_objs[j].pad = 0u; }
-    HIPCHECK(hipMemcpyAsync(w.objs, h_objs.data(), sizeof(SceneObjConst) * n, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(w.boxes, obs, sizeof(mon_frame_bbox) * n_obs, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(w.prefix, prefix.data(), 4 * (n_obs + 1), hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(w.poses, Twc16s, 64 * (size_t)H, hipMemcpyHostToDevice, s));
-    const bool drawn = p.rays_per_iter != 0;
-    const float inv_n = 1.f / (float)n_rays;
-    for (uint32_t h0 = 0; h0 < H; h0 += Gmax) {
-        const uint32_t G = std::min(Gmax, H - h0), nv = G * n_rays;
-        SceneScoreRayArgs ra{}; ra.boxes = w.boxes; ra.prefix = w.prefix; ra.n_obs = (uint32_t)n_obs; ra.n_rays = nv; ra.ray0 = 0u; ra.total = total;
-        ra.drawn = drawn ? 1u : 0u; ra.iteration = iteration; ra.seed = p.seed; ra.ds = ms[0]->ds->ptrs(); ra.objs = w.objs; ra.n_objs = (uint32_t)n; ra.cap = cap;
-        ra.pose = w.poses; ra.rec = w.rec; ra.mstar = w.mstar; ra.ray = w.ray; ra.n_per = n_rays; ra.h0 = h0;
-        launch_scene_score_rays(s, ra);
-        for (size_t j = 0; j < n; ++j) {
-            Model& m = *ms[j]; const size_t l0 = j * (size_t)cap;
-            ScenePoseObjArgs a{}; a.rec = w.rec + l0 * 3; a.n_rays = nv; a.ray0 = 0u;
-            a.seed = drawn ? p.seed : m.oc.sample_seed; a.stream = drawn ? kStreamPose : (uint32_t)kStreamRender; a.step = drawn ? iteration : 0u;
-            a.t = w.t + l0 * kSceneListLen; a.attr = w.attr + l0 * kSceneListLen; a.cnt = w.cnt + l0; a.ray = w.ray; a.inv_n = inv_n;
-            launch_scene_pose_obj(s, m.lf, m.nd, m.oc, prm[j], w.frag + frag_off[j], h0 == 0, 0, pose_grad_grid(nv), a);
-        }
-        SceneCompGradArgs ca{}; ca.n_rays = nv; ca.n_lists = (uint32_t)n; ca.cap = cap; ca.t = w.t; ca.attr = w.attr; ca.cnt = w.cnt; ca.mstar = w.mstar;
-        ca.ray = w.ray; ca.w_rgb = p.w_rgb; ca.w_mask = p.w_mask; ca.w_depth = p.w_depth; ca.huber = p.depth_huber; ca.loss_part = w.loss_part;
-        launch_scene_composite_loss(s, ca, n_rays);
-        launch_scene_loss_reduce(s, w.loss_part, G, parts, inv_n, w.scores + h0);
-    }
-    HIPCHECK(hipGetLastError());
-    // (a copy kernel on the call's stream into the pinned staging, as scene_pose's results go home)
-    launch_copy_params(s, reinterpret_cast<const uint16_t*>(w.scores), reinterpret_cast<uint16_t*>(w.h_scores), H * 2u);
-    HIPCHECK(hipStreamSynchronize(s));
-    HIPCHECK(hipGetLastError());
-    std::memcpy(losses, w.h_scores, (size_t)H * 4);
-    return MON_OK;
-}
-
-// ---- window refinement (mon_scene_window_loss / mon_scene_refine_window): scene_pose's chain over the frames of a window, whole frames packed as virtual
-// rays into scene_pose's list workspace (passes of at most kWindowPassRays rays, greedily in window order): passes x (2K + 2) + 1 launches per evaluation,
-// every camera pose and every object's Tow on the device between steps, everything enqueued at once, one synchronisation.
-int window_frames(const mon_frame_bbox* obs, size_t n_obs, uint32_t* frame_ids, size_t* n_frames) {
-    if (!obs || !frame_ids || !n_frames) { set_error("window frames: null argument"); return MON_ERR_ARG; }
-    size_t F = 0;
-    for (size_t i = 0; i < n_obs; ++i) {
-        if (i && obs[i].FrameId == obs[i - 1].FrameId) continue;
-        for (size_t k = 0; k < F; ++k) if (frame_ids[k] == obs[i].FrameId) {
-            set_error("window frames: the boxes of frame %u are not contiguous (box %zu)", obs[i].FrameId, i); return MON_ERR_ARG; }
-        if (F == kWindowMaxFrames) { set_error("window frames: more than %u frames", kWindowMaxFrames); return MON_ERR_ARG; }
-        frame_ids[F++] = obs[i].FrameId;
-    }
-    *n_frames = F;
-    return MON_OK;
-}
-int scene_window_params_check(const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const mon_pose_refine_params* p, const mon_window_params* w,
-                              const float* Tow16s, bool refine) {
-    if (!obs || !Twc16s || !p || (refine && !w)) { set_error("scene window: null argument"); return MON_ERR_ARG; }
-    if (n_obs == 0) { set_error("scene window: no boxes"); return MON_ERR_ARG; }
-    if (p->iters < 0) { set_error("scene window: iters %d < 0", p->iters); return MON_ERR_ARG; }
-    uint32_t ids[kWindowMaxFrames]; size_t F = 0;
-    { const int rc = window_frames(obs, n_obs, ids, &F); if (rc) return rc; }
-    if (refine) {
-        if (w->n_fixed_frames > F) { set_error("scene window: n_fixed_frames %u of %zu frames", w->n_fixed_frames, F); return MON_ERR_ARG; }
-        if (!std::isfinite(w->lr_obj_trans) || !std::isfinite(w->lr_obj_rot) || w->lr_obj_trans < 0.f || w->lr_obj_rot < 0.f) {
-            set_error("scene window: object step sizes %g, %g (finite, >= 0)", w->lr_obj_trans, w->lr_obj_rot); return MON_ERR_ARG; }
-        if (w->refine_objects && w->n_fixed_frames == 0) {
-            set_error("scene window: refine_objects with no fixed frame (nothing would hold the map in place)"); return MON_ERR_ARG; }
-        if (w->refine_objects && !Tow16s) { set_error("scene window: refine_objects with a null Tow16s"); return MON_ERR_ARG; }
-    }
-    return MON_OK;
-}
-// the MON_ERR_ARG cases that need the objects; the caller has passed scene_window_params_check (the frames are contiguous, at most kWindowMaxFrames)
-int scene_window_frames_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const float* Tow16s,
-                              const mon_pose_refine_params* p) {
-    for (size_t i0 = 0, f = 0; i0 < n_obs; ++f) {
-        size_t i1 = i0 + 1; while (i1 < n_obs && obs[i1].FrameId == obs[i0].FrameId) ++i1;
-        { const int rc = scene_pose_check(ms, n, side, obs + i0, i1 - i0, Twc16s + 16 * f, p); if (rc) return rc; }
-        uint64_t total = 0; for (size_t i = i0; i < i1; ++i) total += (uint64_t)obs[i].w * obs[i].h;
-        const uint64_t n_rays = p->rays_per_iter ? p->rays_per_iter : total;
-        if (n_rays > kWindowPassRays) { set_error("scene window: %llu rays in frame %u (at most %u: a frame is never split across passes)",
-            (unsigned long long)n_rays, obs[i0].FrameId, kWindowPassRays); return MON_ERR_ARG; }
-        i0 = i1;
-    }
-    if (Tow16s) for (size_t k = 0; k < 16 * n; ++k) if (!std::isfinite(Tow16s[k])) {
-        set_error("scene window: Tow16s of object %zu is not finite", k / 16); return MON_ERR_ARG; }
-    return MON_OK;
-}
-int scene_window(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const float* Tow16s,
-                 const mon_pose_refine_params& p, const mon_window_params* wp, int iters, uint32_t iteration, const float* level_w, float* Twc16s_out,
-                 float* Tow16s_out, float* loss_trace, float* frame_trace, float* loss, float* frame_loss, float* cam_grad6, float* obj_grad6) {
-    { const int rc = scene_window_frames_check(ms, n, side, obs, n_obs, Twc16s, Tow16s, &p); if (rc) return rc; }
-    if (!launch_scene_window_rays || !launch_scene_pose_obj || !launch_scene_window_composite || !launch_scene_window_obj || !launch_scene_window_update ||
-        !scene_comp_grad_grid || !pose_grad_grid) { set_error("scene window: built without kernels_scene_window.hip"); return MON_ERR_STATE; }
-    int Lmax = 0;
-    { const int rc = scene_pose_state_check(ms, n, side, Lmax); if (rc) return rc; }
-    // the frames in window order, each with the grids a single-frame call of its rays uses; the passes
-    std::vector<SceneWinFrame> fr; std::vector<uint32_t> prefix; std::vector<uint32_t> pass0{ 0u };   // pass k holds frames [pass0[k], pass0[k + 1])
-    uint32_t row_stride = 0, n_lp = 0, cap = 0, v_next = 0;
-    for (size_t i0 = 0; i0 < n_obs; ) {
-        size_t i1 = i0 + 1; while (i1 < n_obs && obs[i1].FrameId == obs[i0].FrameId) ++i1;
-        SceneWinFrame f{}; f.pose = 16u * (uint32_t)fr.size(); f.box0 = (uint32_t)i0; f.n_box = (uint32_t)(i1 - i0); f.prefix0 = (uint32_t)prefix.size();
-        uint32_t total = 0; for (size_t i = i0; i < i1; ++i) { prefix.push_back(total); total += obs[i].w * obs[i].h; } prefix.push_back(total);
-        f.total = total; f.n_rays = p.rays_per_iter ? p.rays_per_iter : total; f.inv_n = 1.f / (float)f.n_rays;
-        if (v_next + f.n_rays > kWindowPassRays) { pass0.push_back((uint32_t)fr.size()); v_next = 0; }
-        f.v0 = v_next; v_next += f.n_rays; cap = std::max(cap, v_next);
-        f.gridc = pose_grad_grid(f.n_rays); f.row0 = row_stride; row_stride += f.gridc;
-        f.parts = scene_comp_grad_grid(f.n_rays); f.lp0 = n_lp; n_lp += f.parts;
-        fr.push_back(f); i0 = i1;
-    }
-    pass0.push_back((uint32_t)fr.size());
-    const uint32_t F = (uint32_t)fr.size(), n_pass = (uint32_t)pass0.size() - 1u;
-    const int device = ms[0]->device;
-    HIPCHECK(use_device(device));
-    const int n_eval = iters < 0 ? 1 : iters + 1;
-    ScenePoseSide sd; { const int rc = sd.enter(ms, n, side, device); if (rc) return rc; }
-    const std::vector<const uint16_t*>& prm = sd.prm; const hipStream_t s = sd.s; ScenePoseWs& w = *sd.w;
-    std::vector<size_t> frag_off(n + 1, 0);
-    for (size_t j = 0; j < n; ++j) { const NetDims& nd = ms[j]->nd; const FragDims fd{ nd.Epad, nd.W, nd.NH, nd.L }; frag_off[j + 1] = frag_off[j] + (size_t)fd.N_FRAGS() * 512; }
-    const size_t lists = n * (size_t)cap;
-    const uint32_t out_stride = 1u + 7u * F + 6u * (uint32_t)n;
-    constexpr size_t kObjFloats = sizeof(SceneObjConst) / 4;
-    const size_t out_floats = (size_t)out_stride * n_eval + 16 * (size_t)F + kObjFloats * n;      // the evaluations | every Twc | every SceneObjConst
-    int rc;
-    if ((rc = grow_buf(w.t, w.t_cap, lists * kSceneListLen)) || (rc = grow_buf(w.attr, w.attr_cap, lists * kSceneListLen)) ||
-        (rc = grow_buf(w.gw, w.gw_cap, lists * kSceneListLen)) || (rc = grow_buf(w.cnt, w.cnt_cap, lists)) || (rc = grow_buf(w.mstar, w.mstar_cap, lists)) ||
-        (rc = grow_buf(w.rec, w.rec_cap, lists * 3)) || (rc = grow_buf(w.ray, w.ray_cap, (size_t)cap * 3)) || (rc = grow_buf(w.grow, w.grow_cap, (size_t)cap)) ||
-        (rc = grow_buf(w.partials, w.part_cap, n * (size_t)row_stride * 8)) || (rc = grow_buf(w.loss_part, w.lp_cap, (size_t)n_lp)) ||
-        (rc = grow_buf(w.objs, w.objs_cap, n)) || (rc = grow_buf(w.frag, w.frag_cap, frag_off[n])) || (rc = grow_buf(w.boxes, w.box_cap, n_obs)) ||
-        (rc = grow_buf(w.prefix, w.prefix_cap, prefix.size())) || (rc = grow_buf(w.poses, w.poses_cap, (size_t)F * 16)) ||
-        (rc = grow_buf(w.wframes, w.wframes_cap, (size_t)F)) || (rc = grow_buf(w.wmom, w.wmom_cap, 12 * ((size_t)F + n))) ||
-        (rc = grow_buf(w.out, w.out_cap, out_floats))) return rc;
-    if (out_floats > w.h_out_cap) {
-        if (w.h_out) { (void)hipHostFree(w.h_out); w.h_out = nullptr; w.h_out_cap = 0; }
-        HIPCHECK(hipHostMalloc((void**)&w.h_out, out_floats * 4, hipHostMallocDefault)); w.h_out_cap = out_floats;
-    }
-    const int n_wrows = level_w ? (iters < 0 ? 1 : iters) : 0;
-    if (n_wrows) {
-        if ((rc = grow_buf(w.lw, w.lw_cap, (size_t)n_wrows * Lmax))) return rc;
-        HIPCHECK(hipMemcpyAsync(w.lw, level_w, sizeof(float) * (size_t)n_wrows * Lmax, hipMemcpyHostToDevice, s));
-    }
-    std::vector<SceneObjConst> h_objs(n);
-    for (size_t j = 0; j < n; ++j) { const ObjectConst& oc = ms[j]->oc; std::memcpy(h_objs[j].Tow, Tow16s ? Tow16s + 16 * j : oc.Tow.m, 64); h_objs[j].aabb = oc.aabb;
-        h_objs[j].instance_id = oc.instance_id; h_objs[j].pad = 0u; }
-    HIPCHECK(hipMemcpyAsync(w.objs, h_objs.data(), sizeof(SceneObjConst) * n, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(w.boxes, obs, sizeof(mon_frame_bbox) * n_obs, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(w.prefix, prefix.data(), 4 * prefix.size(), hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(w.poses, Twc16s, 64 * (size_t)F, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(w.wframes, fr.data(), sizeof(SceneWinFrame) * F, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemsetAsync(w.wmom, 0, 48 * ((size_t)F + n), s));
-    const bool drawn = p.rays_per_iter != 0;
-    for (int it = 0; it < n_eval; ++it) {
-        const uint32_t key = iters < 0 ? iteration : (uint32_t)it;
-        const float* lw_row = it < n_wrows ? w.lw + (size_t)it * Lmax : nullptr;
-        for (uint32_t k = 0; k < n_pass; ++k) {
-            const uint32_t f0 = pass0[k], nf = pass0[k + 1] - f0, nv = fr[f0 + nf - 1].v0 + fr[f0 + nf - 1].n_rays;
-            uint32_t gmax = 0, pmax = 0; for (uint32_t f = f0; f < f0 + nf; ++f) { gmax = std::max(gmax, fr[f].gridc); pmax = std::max(pmax, fr[f].parts); }
-            SceneWindowRayArgs ra{}; ra.boxes = w.boxes; ra.prefix = w.prefix; ra.n_rays = nv; ra.drawn = drawn ? 1u : 0u; ra.iteration = key; ra.seed = p.seed;
-            ra.ds = ms[0]->ds->ptrs(); ra.objs = w.objs; ra.n_objs = (uint32_t)n; ra.cap = cap; ra.pose = w.poses; ra.rec = w.rec; ra.mstar = w.mstar;
-            ra.ray = w.ray; ra.frames = w.wframes + f0; ra.n_frames = nf;
-            launch_scene_window_rays(s, ra);
-            std::vector<ScenePoseObjArgs> oa(n);
-            for (size_t j = 0; j < n; ++j) {
-                Model& m = *ms[j]; const size_t l0 = j * (size_t)cap; ScenePoseObjArgs& a = oa[j];
-                a = ScenePoseObjArgs{}; a.rec = w.rec + l0 * 3; a.n_rays = nv; a.ray0 = 0u;
-                a.seed = drawn ? p.seed : m.oc.sample_seed; a.stream = drawn ? kStreamPose : (uint32_t)kStreamRender; a.step = drawn ? key : 0u;
-                a.t = w.t + l0 * kSceneListLen; a.attr = w.attr + l0 * kSceneListLen; a.cnt = w.cnt + l0; a.gw = w.gw + l0 * kSceneListLen; a.grow = w.grow;
-                a.ray = w.ray; a.inv_n = 0.f; a.partials = w.partials + (size_t)j * row_stride * 8; a.level_w = lw_row;
-                launch_scene_pose_obj(s, m.lf, m.nd, m.oc, prm[j], w.frag + frag_off[j], it == 0 && k == 0, 0, pose_grad_grid(nv), a);
-            }
-            SceneCompGradArgs ca{}; ca.n_rays = nv; ca.n_lists = (uint32_t)n; ca.cap = cap; ca.t = w.t; ca.attr = w.attr; ca.cnt = w.cnt; ca.mstar = w.mstar;
-            ca.ray = w.ray; ca.w_rgb = p.w_rgb; ca.w_mask = p.w_mask; ca.w_depth = p.w_depth; ca.huber = p.depth_huber; ca.gw = w.gw; ca.grow = w.grow;
-            ca.loss_part = w.loss_part;
-            launch_scene_window_composite(s, ca, pmax, nf, w.wframes + f0);
-            for (size_t j = 0; j < n; ++j) { Model& m = *ms[j];
-                launch_scene_window_obj(s, m.lf, m.nd, m.oc, prm[j], w.frag + frag_off[j], gmax, nf, w.wframes + f0, oa[j]); }
-        }
-        SceneWindowUpdateArgs ua{}; ua.partials = w.partials; ua.n_objs = (uint32_t)n; ua.row_stride = row_stride; ua.loss_part = w.loss_part;
-        ua.frames = w.wframes; ua.n_frames = F; ua.n_fixed = wp ? wp->n_fixed_frames : F; ua.refine_objs = wp ? wp->refine_objects : 0; ua.objs = w.objs;
-        ua.poses = w.poses; ua.moments = w.wmom; ua.out = w.out; ua.out_stride = out_stride; ua.it = (uint32_t)it; ua.step = iters >= 0 && it < iters;
-        ua.lr_t = p.lr_trans; ua.lr_r = p.lr_rot; ua.lr_obj_t = wp ? wp->lr_obj_trans : 0.f; ua.lr_obj_r = wp ? wp->lr_obj_rot : 0.f;
-        launch_scene_window_update(s, ua);
-    }
-    HIPCHECK(hipGetLastError());
-    // results home through the pinned staging: every evaluation's row, then the poses, then the objects' constants (their Tow)
-    float* d_tail = w.out + (size_t)out_stride * n_eval;
-    launch_copy_params(s, reinterpret_cast<const uint16_t*>(w.poses), reinterpret_cast<uint16_t*>(d_tail), 32u * F);
-    launch_copy_params(s, reinterpret_cast<const uint16_t*>(w.objs), reinterpret_cast<uint16_t*>(d_tail + 16 * (size_t)F), (uint32_t)(2 * kObjFloats * n));
-    launch_copy_params(s, reinterpret_cast<const uint16_t*>(w.out), reinterpret_cast<uint16_t*>(w.h_out), (uint32_t)(out_floats * 2));
-    HIPCHECK(hipStreamSynchronize(s));
-    HIPCHECK(hipGetLastError());
-    const float* h = w.h_out;
-    if (loss) *loss = h[0];
-    if (frame_loss) std::memcpy(frame_loss, h + 1, 4 * (size_t)F);
-    if (cam_grad6) std::memcpy(cam_grad6, h + 1 + F, 24 * (size_t)F);
-    if (obj_grad6) std::memcpy(obj_grad6, h + 1 + 7 * (size_t)F, 24 * n);
-    for (int it = 0; it < n_eval; ++it) {
-        const float* r = h + (size_t)out_stride * it;
-        if (loss_trace) loss_trace[it] = r[0];
-        if (frame_trace) std::memcpy(frame_trace + (size_t)F * it, r + 1, 4 * (size_t)F);
-    }
-    const float* tail = h + (size_t)out_stride * n_eval;
-    if (Twc16s_out) for (uint32_t f = wp ? std::min(wp->n_fixed_frames, F) : F; f < F; ++f) std::memcpy(Twc16s_out + 16 * (size_t)f, tail + 16 * (size_t)f, 64);
-    if (Tow16s_out && wp && wp->refine_objects) for (size_t j = 0; j < n; ++j) std::memcpy(Tow16s_out + 16 * j, tail + 16 * (size_t)F + kObjFloats * j, 64);
-    return MON_OK;
 }
 
 // ---- storing an object pose (mon_object_set_pose): oc.Tow and nothing else.  Weights, optimizer state, counters, the occupancy grid and the render-skip grids
@@ -2187,60 +1414,6 @@ int model_set_pose(Model& m, const float* Tow16) {
     }
     m.next_ready = false; m.points_ready = false;
     drop_graph(m);
-    return MON_OK;
-}
-
-// ---- wide-basin relocalisation (mon_scene_relocalise / mon_online_relocalise): score every candidate, refine the best few with scene_pose, score the
-// refined poses and their starts together, return the winner.  2 + min(keep, n_cands) stream synchronisations: one per scoring round, one per refinement.
-int scene_reloc_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* cands, size_t n_cands,
-                      const mon_pose_refine_params* p, const mon_pose_c2f_params* c, const mon_reloc_params* r, const float* pose_out) {
-    if (!cands || !p || !r || !pose_out) { set_error("relocalise: null argument"); return MON_ERR_ARG; }
-    if (n_cands == 0 || n_cands > kSceneScoreMaxPoses) { set_error("relocalise: %zu candidates (1 to %u)", n_cands, kSceneScoreMaxPoses); return MON_ERR_ARG; }
-    if (r->score_rays == 0 || r->score_rays > kSceneScoreMaxRays) { set_error("relocalise: score_rays %u (1 to %u)", r->score_rays, kSceneScoreMaxRays);
-        return MON_ERR_ARG; }
-    if (r->keep == 0 || r->keep > kRelocMaxKeep) { set_error("relocalise: keep %u (1 to %u)", r->keep, kRelocMaxKeep); return MON_ERR_ARG; }
-    { const int rc = scene_pose_check(ms, n, side, obs, n_obs, cands, p); if (rc) return rc; }
-    if (c) { const int rc = pose_c2f_check(c); if (rc) return rc; }
-    return MON_OK;
-}
-int scene_relocalise(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* cands, size_t n_cands,
-                     const mon_pose_refine_params& p, const mon_pose_c2f_params* c, const mon_reloc_params& r, float* pose_out, mon_reloc_result* result,
-                     float* scores) {
-    { const int rc = scene_reloc_check(ms, n, side, obs, n_obs, cands, n_cands, &p, c, &r, pose_out); if (rc) return rc; }
-    int Lmax = 0;
-    { const int rc = scene_pose_state_check(ms, n, side, Lmax); if (rc) return rc; }
-    mon_pose_refine_params ps = p; ps.rays_per_iter = r.score_rays;
-    // 1. every candidate's score
-    std::vector<float> S(n_cands);
-    int rc = scene_pose_batch(ms, n, side, obs, n_obs, cands, n_cands, ps, r.score_iteration, S.data()); if (rc) return rc;
-    if (scores) std::memcpy(scores, S.data(), n_cands * 4);
-    // 2. the kept set: candidate 0, then the others by ascending score (ties to the lower index, a non-finite score last)
-    std::vector<uint32_t> order; for (uint32_t i = 1; i < n_cands; ++i) order.push_back(i);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-        const bool fa = std::isfinite(S[a]), fb = std::isfinite(S[b]);
-        return fa != fb ? fa : (fa && S[a] < S[b]); });
-    const size_t k = std::min<size_t>(r.keep, n_cands);
-    std::vector<uint32_t> kept{ 0u }; kept.insert(kept.end(), order.begin(), order.begin() + (ptrdiff_t)(k - 1));
-    // 3. each of them refined as mon_scene_refine_camera refines it
-    std::vector<float> table; if (c) table = pose_c2f_table(*c, Lmax, p.iters);
-    std::vector<float> list(2 * k * 16);
-    for (size_t i = 0; i < k; ++i) {
-        const float* start = cands + 16 * (size_t)kept[i]; float* pose = list.data() + 16 * i;
-        std::memcpy(list.data() + 16 * (k + i), start, 64); std::memcpy(pose, start, 64);
-        rc = scene_pose(ms, n, side, obs, n_obs, pose, p, p.iters, 0u, pose, nullptr, nullptr, nullptr, nullptr, table.empty() ? nullptr : table.data());
-        if (rc) return rc;
-    }
-    // 4. the refined poses and their starts under the common key; the lowest finite score wins (ties to the earlier entry)
-    std::vector<float> F(2 * k);
-    rc = scene_pose_batch(ms, n, side, obs, n_obs, list.data(), 2 * k, ps, r.score_iteration, F.data()); if (rc) return rc;
-    size_t win = 2 * k;
-    for (size_t i = 0; i < 2 * k; ++i) if (std::isfinite(F[i]) && (win == 2 * k || F[i] < F[win])) win = i;
-    const bool none = win == 2 * k; if (none) win = k;                          // no finite score: candidate 0 as given
-    std::memcpy(pose_out, list.data() + 16 * win, 64);
-    if (result) {
-        result->best_candidate = kept[win % k]; result->refined = (!none && win < k) ? 1u : 0u;
-        result->score_candidate0 = S[0]; result->score_best_candidate = S[kept[win % k]]; result->score_final = F[win];
-    }
     return MON_OK;
 }
 
@@ -2273,379 +1446,6 @@ int model_set_params(Model& m, const float* master, size_t n) {
     { const int rc = publish_snapshot(m); if (rc) return rc; }   // (viewers of an untrained object see the weights just set:
     // the snapshot is complete before the call returns, so no render prefers the one before it)
     HIPCHECK(hipStreamSynchronize(m.train_stream)); return MON_OK;
-}
-
-// ------------------------------------------------------------------ checkpoints
-// One object per file, little-endian, every field written one by one (never a struct image):
-//   [0, 64)      header: magic "MONCKPT\0", version, section count, file bytes, table offset, CRC-32 of [0, table end) with the CRC field as zero
-//   [64, 320)    object block: every mon_config field, class id, Tow, box, parameter counts, backend, step-counter width, lazy-EMA and occupancy flags, box count
-//   [320, 448)   state block: what the next iteration and mon_object_info_get read (DevState's head as words, the occupancy schedule, the pending-EMA flag)
-//   [448, ..)    section table, 32 bytes per entry: tag[8], element type, CRC-32 of the section, element count, byte offset (a multiple of 64)
-// then the sections, each a flat array in parameter order whatever the layout in device memory (arrays or 128-byte chunk records).
-static_assert(__BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__, "the checkpoint writer stores host words as they are");
-namespace {
-constexpr char kCkMagic[8] = { 'M', 'O', 'N', 'C', 'K', 'P', 'T', 0 };
-constexpr uint32_t kCkVersion = 1, kCkHeaderBytes = 64, kCkObjectOff = 64, kCkStateOff = 320, kCkTableOff = 448, kCkEntryBytes = 32, kCkMaxSections = 16;
-// the one pinned and the one device staging buffer of a save / load: never more than this, whatever the table size
-constexpr size_t kCkStageBytes = (size_t)32 << 20;
-enum { CK_F32 = 1, CK_U32 = 2, CK_F16 = 3, CK_BBOX = 4 };
-constexpr size_t ck_elem_bytes(uint32_t type) { return type == CK_F16 ? 2 : type == CK_BBOX ? 20 : 4; }
-// state block words
-enum { CKS_STEP = 0, CKS_ITER, CKS_SKIPPED, CKS_LR, CKS_N_VALID, CKS_LOSS_SUM, CKS_N_VALID_PRE, CKS_SCATTER_NOW, CKS_SCATTER_LAST, CKS_SCATTER_TOTAL,
-       CKS_DEB_OLD, CKS_DEB_NEW, CKS_DEB_EVEN_OLD, CKS_DEB_EVEN_NEW, CKS_OCC_REFRESHED, CKS_OCC_NEXT, CKS_OCC_THRESHOLD, CKS_EMA_PENDING, CKS_WORDS = 32 };
-struct CkSection { std::string tag; uint32_t type = 0, crc = 0; uint64_t count = 0, offset = 0; size_t bytes() const { return (size_t)count * ck_elem_bytes(type); } };
-struct CkFile { mon_checkpoint_info info{}; uint32_t step_bits = 0, state[CKS_WORDS] = {}; std::vector<CkSection> sec;
-    const CkSection* find(const char* tag) const { for (const CkSection& s : sec) if (s.tag == tag) return &s; return nullptr; } };
-
-void put32(uint8_t* b, size_t off, uint32_t v) { std::memcpy(b + off, &v, 4); }
-void put64(uint8_t* b, size_t off, uint64_t v) { std::memcpy(b + off, &v, 8); }
-void putf(uint8_t* b, size_t off, float v) { std::memcpy(b + off, &v, 4); }
-uint32_t get32(const uint8_t* b, size_t off) { uint32_t v; std::memcpy(&v, b + off, 4); return v; }
-uint64_t get64(const uint8_t* b, size_t off) { uint64_t v; std::memcpy(&v, b + off, 8); return v; }
-float getf(const uint8_t* b, size_t off) { float v; std::memcpy(&v, b + off, 4); return v; }
-uint32_t f2u(float f) { uint32_t v; std::memcpy(&v, &f, 4); return v; }
-float u2f(uint32_t u) { float v; std::memcpy(&v, &u, 4); return v; }
-uint32_t ck_crc(uint32_t crc, const void* p, size_t n) {
-    const uint8_t* b = static_cast<const uint8_t*>(p);
-    while (n) { const size_t k = n < ((size_t)1 << 30) ? n : ((size_t)1 << 30); crc = (uint32_t)::crc32(crc, b, (uInt)k); b += k; n -= k; }
-    return crc;
-}
-
-// the sections a file of this object block holds, in file order
-std::vector<CkSection> ck_expected_sections(const mon_checkpoint_info& in) {
-    std::vector<CkSection> v; const uint64_t n = in.n_params;
-    auto add = [&](const char* tag, uint32_t type, uint64_t count) { CkSection s; s.tag = tag; s.type = type; s.count = count; v.push_back(s); };
-    add("master", CK_F32, n); add("m1", CK_F32, n); add("m2", CK_F32, n); add("steps", CK_U32, n); add("ema", CK_F16, n);
-    if (in.lazy_ema) add("ema_step", CK_U32, n >> 3);
-    if (in.has_occupancy) { add("occ", CK_U32, kOccWords); add("occ_raw", CK_U32, kOccWords); }
-    add("boxes", CK_BBOX, in.n_boxes);
-    return v;
-}
-void ck_layout(std::vector<CkSection>& sec, uint64_t* file_bytes) {
-    uint64_t off = kCkTableOff + (uint64_t)kCkEntryBytes * sec.size();
-    for (CkSection& s : sec) { off = (off + 63u) & ~(uint64_t)63u; s.offset = off; off += s.bytes(); }
-    *file_bytes = off;
-}
-// header + object block + state block + table, CRC included
-std::vector<uint8_t> ck_head_bytes(const CkFile& ck) {
-    const mon_checkpoint_info& in = ck.info; const mon_config& c = in.cfg;
-    std::vector<uint8_t> h(kCkTableOff + (size_t)kCkEntryBytes * ck.sec.size(), 0); uint8_t* b = h.data();
-    std::memcpy(b, kCkMagic, 8); put32(b, 8, kCkVersion); put32(b, 12, (uint32_t)ck.sec.size()); put64(b, 16, in.file_bytes); put32(b, 24, kCkTableOff);
-    size_t o = kCkObjectOff;
-    put32(b, o, (uint32_t)c.n_levels); put32(b, o + 4, (uint32_t)c.n_features); put32(b, o + 8, (uint32_t)c.log2_hashmap_size);
-    put32(b, o + 12, (uint32_t)c.base_resolution); putf(b, o + 16, c.per_level_scale); put32(b, o + 20, (uint32_t)c.n_neurons);
-    put32(b, o + 24, (uint32_t)c.n_hidden_layers); put32(b, o + 28, (uint32_t)c.rays_per_batch); put32(b, o + 32, (uint32_t)c.n_samples);
-    putf(b, o + 36, c.loss_scale); putf(b, o + 40, c.learning_rate); putf(b, o + 44, c.beta1); putf(b, o + 48, c.beta2); putf(b, o + 52, c.epsilon);
-    putf(b, o + 56, c.l2_reg); putf(b, o + 60, c.ema_decay); put32(b, o + 64, (uint32_t)c.decay_start); put32(b, o + 68, (uint32_t)c.decay_interval);
-    putf(b, o + 72, c.decay_base); put32(b, o + 76, c.param_seed); put32(b, o + 80, c.rng_flags); put32(b, o + 84, (uint32_t)c.use_depth);
-    put32(b, o + 88, (uint32_t)c.occupancy_skip); put32(b, o + 92, 0u); put64(b, o + 96, c.sample_seed);
-    put32(b, o + 104, (uint32_t)in.class_id);
-    for (int i = 0; i < 16; ++i) putf(b, o + 108 + 4 * i, in.Tow[i]);
-    for (int i = 0; i < 3; ++i) { putf(b, o + 172 + 4 * i, in.aabb_min[i]); putf(b, o + 184 + 4 * i, in.aabb_max[i]); }
-    put32(b, o + 196, in.n_params); put32(b, o + 200, in.n_mlp_params); put32(b, o + 204, in.n_grid_params); put32(b, o + 208, (uint32_t)in.backend);
-    put32(b, o + 212, ck.step_bits); put32(b, o + 216, in.lazy_ema); put32(b, o + 220, in.has_occupancy); put32(b, o + 224, in.n_boxes);
-    for (uint32_t i = 0; i < CKS_WORDS; ++i) put32(b, kCkStateOff + 4 * i, ck.state[i]);
-    for (size_t k = 0; k < ck.sec.size(); ++k) {
-        const CkSection& s = ck.sec[k]; const size_t e = kCkTableOff + kCkEntryBytes * k;
-        std::memcpy(b + e, s.tag.data(), std::min<size_t>(s.tag.size(), 8)); put32(b, e + 8, s.type); put32(b, e + 12, s.crc); put64(b, e + 16, s.count);
-        put64(b, e + 24, s.offset);
-    }
-    put32(b, 28, ck_crc(0u, b, h.size()));
-    return h;
-}
-
-struct FileCloser { FILE* f = nullptr; ~FileCloser() { if (f) std::fclose(f); } };
-
-// Everything that can be judged without a device: MON_ERR_IO with a message, or the parsed head.
-int ck_parse(FILE* f, const char* path, CkFile& ck) {
-#define CK_BAD(...) do { set_error(__VA_ARGS__); return MON_ERR_IO; } while (0)
-    if (std::fseek(f, 0, SEEK_END) != 0) CK_BAD("checkpoint %s: cannot seek", path);
-    const long flen = std::ftell(f);
-    if (flen < (long)kCkHeaderBytes) CK_BAD("checkpoint %s: truncated (%ld bytes, the header alone is %u)", path, flen, kCkHeaderBytes);
-    uint8_t hd[kCkHeaderBytes];
-    if (std::fseek(f, 0, SEEK_SET) != 0 || std::fread(hd, 1, kCkHeaderBytes, f) != kCkHeaderBytes) CK_BAD("checkpoint %s: cannot read the header", path);
-    if (std::memcmp(hd, kCkMagic, 8) != 0) CK_BAD("checkpoint %s: bad magic", path);
-    const uint32_t version = get32(hd, 8), n_sec = get32(hd, 12);
-    if (version == 0u || version > kCkVersion) CK_BAD("checkpoint %s: format version %u, this build reads up to %u", path, version, kCkVersion);
-    if (n_sec > kCkMaxSections || get32(hd, 24) != kCkTableOff) CK_BAD("checkpoint %s: %u sections / table offset %u", path, n_sec, get32(hd, 24));
-    const uint64_t file_bytes = get64(hd, 16); const size_t head_len = kCkTableOff + (size_t)kCkEntryBytes * n_sec;
-    if (file_bytes != (uint64_t)flen) CK_BAD("checkpoint %s: truncated or extended (%ld bytes, the header says %llu)", path, flen,
-            (unsigned long long)file_bytes);
-    if ((uint64_t)head_len > file_bytes) CK_BAD("checkpoint %s: truncated inside the section table", path);
-    std::vector<uint8_t> h(head_len);
-    if (std::fseek(f, 0, SEEK_SET) != 0 || std::fread(h.data(), 1, head_len, f) != head_len) CK_BAD("checkpoint %s: cannot read the section table", path);
-    const uint8_t* b = h.data();
-    { const uint32_t stored = get32(b, 28); put32(h.data(), 28, 0u);
-      if (ck_crc(0u, b, head_len) != stored) CK_BAD("checkpoint %s: header / section table CRC mismatch", path); }
-    mon_checkpoint_info& in = ck.info; mon_config& c = in.cfg; size_t o = kCkObjectOff;
-    in.version = version; in.file_bytes = file_bytes;
-    c.n_levels = (int32_t)get32(b, o); c.n_features = (int32_t)get32(b, o + 4); c.log2_hashmap_size = (int32_t)get32(b, o + 8);
-    c.base_resolution = (int32_t)get32(b, o + 12); c.per_level_scale = getf(b, o + 16); c.n_neurons = (int32_t)get32(b, o + 20);
-    c.n_hidden_layers = (int32_t)get32(b, o + 24); c.rays_per_batch = (int32_t)get32(b, o + 28); c.n_samples = (int32_t)get32(b, o + 32);
-    c.loss_scale = getf(b, o + 36); c.learning_rate = getf(b, o + 40); c.beta1 = getf(b, o + 44); c.beta2 = getf(b, o + 48); c.epsilon = getf(b, o + 52);
-    c.l2_reg = getf(b, o + 56); c.ema_decay = getf(b, o + 60); c.decay_start = (int32_t)get32(b, o + 64); c.decay_interval = (int32_t)get32(b, o + 68);
-    c.decay_base = getf(b, o + 72); c.param_seed = get32(b, o + 76); c.rng_flags = get32(b, o + 80); c.use_depth = (int32_t)get32(b, o + 84);
-    c.occupancy_skip = (int32_t)get32(b, o + 88); c.sample_seed = get64(b, o + 96);
-    in.class_id = (int32_t)get32(b, o + 104);
-    for (int i = 0; i < 16; ++i) in.Tow[i] = getf(b, o + 108 + 4 * i);
-    for (int i = 0; i < 3; ++i) { in.aabb_min[i] = getf(b, o + 172 + 4 * i); in.aabb_max[i] = getf(b, o + 184 + 4 * i); }
-    in.n_params = get32(b, o + 196); in.n_mlp_params = get32(b, o + 200); in.n_grid_params = get32(b, o + 204); in.backend = (int32_t)get32(b, o + 208);
-    ck.step_bits = get32(b, o + 212); in.lazy_ema = get32(b, o + 216); in.has_occupancy = get32(b, o + 220); in.n_boxes = get32(b, o + 224);
-    for (uint32_t i = 0; i < CKS_WORDS; ++i) ck.state[i] = get32(b, kCkStateOff + 4 * i);
-    in.train_step = ck.state[CKS_STEP]; in.iter = ck.state[CKS_ITER];
-    // the config, through mon_object_create's checks (their messages stand), and the sizes it implies
-    if (config_check(c) != MON_OK) return MON_ERR_IO;
-    if (rng_stream_mode(c.rng_flags)) CK_BAD("checkpoint %s: an object in the XORWOW sample-stream mode (not a checkpoint this library writes)", path);
-    LevelTable lt{}; NetDims nd{}; uint32_t n_grid = 0;
-    if (level_table_build(c, lt, nd, n_grid) != MON_OK) return MON_ERR_IO;
-    if (in.n_mlp_params != (uint32_t)nd.n_mlp || in.n_grid_params != n_grid || in.n_params != (uint32_t)nd.n_mlp + n_grid || (in.n_params & 7u) != 0u)
-        CK_BAD("checkpoint %s: %u = %u + %u parameters, its config has %u + %u", path, in.n_params, in.n_mlp_params, in.n_grid_params, (uint32_t)nd.n_mlp,
-                n_grid);
-    if (ck.step_bits != 16u && ck.step_bits != 32u) CK_BAD("checkpoint %s: step counters of %u bits", path, ck.step_bits);
-    if (in.lazy_ema > 1u || in.has_occupancy > 1u || (in.lazy_ema != 0u) != (n_grid > (8u << 20)) || (in.has_occupancy && !c.occupancy_skip))
-        CK_BAD("checkpoint %s: lazy-EMA / occupancy flags %u / %u do not fit its config", path, in.lazy_ema, in.has_occupancy);
-    if ((in.backend != 0 && in.backend != 1) || (in.backend == 1 && !fused_supported(nd, (uint32_t)c.n_samples, (uint32_t)c.rays_per_batch)))
-        CK_BAD("checkpoint %s: backend %d for this network shape", path, in.backend);
-    // the section table against what this object block implies
-    std::vector<CkSection> want = ck_expected_sections(in);
-    if (want.size() != n_sec) CK_BAD("checkpoint %s: %u sections, its object block implies %zu", path, n_sec, want.size());
-    ck.sec.clear();
-    for (uint32_t k = 0; k < n_sec; ++k) {
-        const size_t e = kCkTableOff + (size_t)kCkEntryBytes * k; CkSection s; char tag[9] = {}; std::memcpy(tag, b + e, 8); s.tag = tag;
-        s.type = get32(b, e + 8); s.crc = get32(b, e + 12); s.count = get64(b, e + 16); s.offset = get64(b, e + 24);
-        const CkSection* w = nullptr; for (const CkSection& q : want) if (q.tag == s.tag) w = &q;
-        if (!w || ck.find(tag)) CK_BAD("checkpoint %s: unexpected or repeated section \"%s\"", path, tag);
-        if (s.type != w->type || s.count != w->count) CK_BAD("checkpoint %s: section \"%s\" holds %llu elements of type %u, expected %llu of type %u", path, tag,
-                (unsigned long long)s.count, s.type, (unsigned long long)w->count, w->type);
-        if ((s.offset & 63u) != 0u || s.offset < head_len || s.offset > file_bytes || s.bytes() > file_bytes - s.offset)
-            CK_BAD("checkpoint %s: section \"%s\" at offset %llu (%zu bytes) does not lie inside the file's %llu bytes", path, tag,
-                    (unsigned long long)s.offset, s.bytes(), (unsigned long long)file_bytes);
-        // (no two sections share a byte: what lies between them is padding only)
-        for (const CkSection& q : ck.sec) if (s.offset < q.offset + q.bytes() && q.offset < s.offset + s.bytes())
-            CK_BAD("checkpoint %s: sections \"%s\" and \"%s\" overlap", path, q.tag.c_str(), tag);
-        ck.sec.push_back(s);
-    }
-    return MON_OK;
-}
-int ck_verify_sections(FILE* f, const char* path, const CkFile& ck) {
-    std::vector<uint8_t> buf((size_t)1 << 20);
-    for (const CkSection& s : ck.sec) {
-        if (std::fseek(f, (long)s.offset, SEEK_SET) != 0) CK_BAD("checkpoint %s: cannot seek to section \"%s\"", path, s.tag.c_str());
-        uint32_t crc = 0u;
-        for (size_t left = s.bytes(); left; ) { const size_t k = std::min(left, buf.size());
-            if (std::fread(buf.data(), 1, k, f) != k) CK_BAD("checkpoint %s: cannot read section \"%s\"", path, s.tag.c_str());
-            crc = ck_crc(crc, buf.data(), k); left -= k; }
-        if (crc != s.crc) CK_BAD("checkpoint %s: CRC mismatch in section \"%s\"", path, s.tag.c_str());
-    }
-    return MON_OK;
-}
-
-std::atomic<int> g_ck_timing{ 0 }; thread_local double g_ck_kernel_ms = 0.0;
-// the bounded staging of one save / load; everything is released when it goes out of scope
-struct CkStage {
-    uint8_t* h = nullptr; uint8_t* d = nullptr; size_t cap = 0; hipEvent_t e0 = nullptr, e1 = nullptr; bool timed = false, pending = false;
-    int init(size_t largest_section, bool need_device) {
-        cap = std::max<size_t>(std::min(kCkStageBytes, largest_section), 64); cap = (cap + 63) & ~(size_t)63;
-        HIPCHECK(hipHostMalloc((void**)&h, cap, hipHostMallocDefault));
-        if (need_device) HIPCHECK(hipMalloc((void**)&d, cap));
-        timed = g_ck_timing.load() != 0;
-        if (timed) { HIPCHECK(hipEventCreate(&e0)); HIPCHECK(hipEventCreate(&e1)); }
-        return MON_OK;
-    }
-    void before_kernel(hipStream_t s) { if (timed) { (void)hipEventRecord(e0, s); pending = true; } }
-    void after_kernel(hipStream_t s) { if (timed) (void)hipEventRecord(e1, s); }
-    // (after the stream has been synchronised)
-    void collect() { if (pending) { float ms = 0.f; if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) g_ck_kernel_ms += ms; pending = false; } }
-    ~CkStage() { if (h) (void)hipHostFree(h); if (d) (void)hipFree(d); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-};
-// where a section lives in this build's device memory: a plain array (`direct`), or something a kernel converts range by range
-struct CkDevSection { void* direct = nullptr; int rec_which = -1; bool steps16 = false; };
-CkDevSection ck_dev_section(Model& m, const std::string& tag) {
-    CkDevSection s;
-    if (tag == "ema") s.direct = m.P.ema;
-    else if (tag == "occ") s.direct = m.d_occ;
-    else if (tag == "occ_raw") s.direct = m.d_occ_tmp;
-    else if (tag == "boxes") s.direct = m.d_boxes;
-    else if (tag == "ema_step") { if (m.P.rec) s.rec_which = 4; else s.direct = m.d_ema_step; }
-    else if (tag == "steps") { if (m.P.rec) s.rec_which = 3; else if (m.P.steps16) s.steps16 = true; else s.direct = m.P.steps; }
-    else if (m.P.rec) s.rec_which = tag == "master" ? 0 : tag == "m1" ? 1 : 2;
-    else s.direct = tag == "master" ? (void*)m.P.master : tag == "m1" ? (void*)m.P.m1 : (void*)m.P.m2;
-    return s;
-}
-}  // namespace
-
-int checkpoint_timing(int enable, double* kernel_ms) {
-    g_ck_timing.store(enable ? 1 : 0); if (kernel_ms) *kernel_ms = g_ck_kernel_ms; g_ck_kernel_ms = 0.0; return MON_OK;
-}
-
-int checkpoint_read_info(const char* path, int verify, mon_checkpoint_info* out) {
-    if (!path || !out) { set_error("checkpoint_read_info: null argument"); return MON_ERR_ARG; }
-    FileCloser fc; fc.f = std::fopen(path, "rb");
-    if (!fc.f) { set_error("checkpoint %s: cannot open", path); return MON_ERR_IO; }
-    CkFile ck; int rc = ck_parse(fc.f, path, ck); if (rc) return rc;
-    if (verify && (rc = ck_verify_sections(fc.f, path, ck))) return rc;
-    *out = ck.info; return MON_OK;
-}
-
-int model_save(Model& m, const char* path) {
-    if (!path) { set_error("object_save: null path"); return MON_ERR_ARG; }
-    if (m.d_xw) { set_error("object_save: an object in the XORWOW sample-stream mode (its generator state is not stored)"); return MON_ERR_STATE; }
-    if (m.scatter_pending) { set_error("object_save: between the stages of an iteration (mon_object_train_stages)"); return MON_ERR_STATE; }
-    if (m.n_params & 7u) { set_error("object_save: %u parameters (not whole chunks of 8)", m.n_params); return MON_ERR_STATE; }
-    HIPCHECK(use_device(m.device)); model_leave_lane(m); HIPCHECK(hipStreamSynchronize(m.train_stream));
-    hipStream_t s = m.train_stream;
-    CkFile ck; mon_checkpoint_info& in = ck.info;
-    in.version = kCkVersion; in.cfg = m.cfg; in.class_id = (int32_t)m.oc.instance_id; std::memcpy(in.Tow, m.oc.Tow.m, 64);
-    for (int a = 0; a < 3; ++a) { in.aabb_min[a] = m.oc.aabb.mn[a]; in.aabb_max[a] = m.oc.aabb.mx[a]; }
-    in.n_params = m.n_params; in.n_mlp_params = (uint32_t)m.nd.n_mlp; in.n_grid_params = m.n_grid; in.train_step = m.h_state.step; in.iter = m.h_state.iter;
-    in.n_boxes = m.n_boxes; in.backend = m.backend; in.has_occupancy = (m.d_occ && m.occ_refreshed_iter) ? 1u : 0u; in.lazy_ema = m.lazy_ema ? 1u : 0u;
-    ck.step_bits = (m.P.rec || m.P.steps16) ? 16u : 32u;
-    const DevState& st = m.h_state; uint32_t* w = ck.state;
-    w[CKS_STEP] = st.step; w[CKS_ITER] = st.iter; w[CKS_SKIPPED] = st.skipped; w[CKS_LR] = f2u(st.lr); w[CKS_N_VALID] = st.n_valid;
-    w[CKS_LOSS_SUM] = f2u(st.loss_sum); w[CKS_N_VALID_PRE] = st.n_valid_pre; w[CKS_SCATTER_NOW] = st.n_scatter_now; w[CKS_SCATTER_LAST] = st.n_scatter_last;
-    w[CKS_SCATTER_TOTAL] = st.n_scatter_total; w[CKS_DEB_OLD] = f2u(st.ema_deb_old); w[CKS_DEB_NEW] = f2u(st.ema_deb_new);
-    w[CKS_DEB_EVEN_OLD] = f2u(st.ema_deb_even_old); w[CKS_DEB_EVEN_NEW] = f2u(st.ema_deb_even_new); w[CKS_OCC_REFRESHED] = m.occ_refreshed_iter;
-    w[CKS_OCC_NEXT] = m.occ_next_refresh; w[CKS_OCC_THRESHOLD] = f2u(m.occ_raw_threshold); w[CKS_EMA_PENDING] = m.ema_pending ? 1u : 0u;
-    ck.sec = ck_expected_sections(in); { uint64_t fb = 0; ck_layout(ck.sec, &fb); in.file_bytes = fb; }
-    size_t largest = 0; bool need_device = false;
-    for (const CkSection& q : ck.sec) { largest = std::max(largest, q.bytes()); const CkDevSection dv = ck_dev_section(m, q.tag); need_device |= !dv.direct; }
-    CkStage stage; { const int rc = stage.init(largest, need_device); if (rc) return rc; }
-
-    const std::string tmp = std::string(path) + ".tmp";
-    struct TmpFile { FileCloser fc; std::string name; bool keep = false; ~TmpFile() { if (fc.f) { std::fclose(fc.f); fc.f = nullptr; } if (!keep) std::remove(name.c_str()); } } out;
-    out.name = tmp; out.fc.f = std::fopen(tmp.c_str(), "wb");
-    if (!out.fc.f) { out.keep = true; set_error("object_save: cannot create %s", tmp.c_str()); return MON_ERR_IO; }
-    FILE* f = out.fc.f;
-#define CK_WRITE(ptr, n) do { if ((n) && std::fwrite((ptr), 1, (n), f) != (size_t)(n)) { set_error("object_save: write to %s failed", tmp.c_str()); \
-        return MON_ERR_IO; } } while (0)
-    uint64_t pos = 0; const std::vector<uint8_t> zeros(64, 0);
-    { const std::vector<uint8_t> head(kCkTableOff + (size_t)kCkEntryBytes * ck.sec.size(), 0); CK_WRITE(head.data(), head.size()); pos = head.size(); }
-    for (CkSection& q : ck.sec) {
-        CK_WRITE(zeros.data(), (size_t)(q.offset - pos)); pos = q.offset;
-        const CkDevSection dv = ck_dev_section(m, q.tag); const size_t total = q.bytes(); uint32_t crc = 0u;
-        for (size_t off = 0; off < total; off += stage.cap) {
-            const size_t n = std::min(stage.cap, total - off);
-            if (dv.direct) HIPCHECK(hipMemcpyAsync(stage.h, static_cast<const uint8_t*>(dv.direct) + off, n, hipMemcpyDeviceToHost, s));
-            else {
-                // (whole chunks: every section of a converted kind is 4 or 32 bytes per chunk, and the staging size is a multiple of both)
-                const size_t per_chunk = dv.rec_which == 4 ? 4 : 32; const uint32_t c0 = (uint32_t)(off / per_chunk), nc = (uint32_t)(n / per_chunk);
-                stage.before_kernel(s);
-                if (dv.steps16) launch_steps16_unpack_range(s, m.P.steps16, stage.d, c0, nc);
-                else launch_state_unpack_range(s, m.P.rec, dv.rec_which, stage.d, c0, nc);
-                stage.after_kernel(s);
-                HIPCHECK(hipMemcpyAsync(stage.h, stage.d, n, hipMemcpyDeviceToHost, s));
-            }
-            HIPCHECK(hipStreamSynchronize(s)); stage.collect();
-            crc = ck_crc(crc, stage.h, n); CK_WRITE(stage.h, n);
-        }
-        q.crc = crc; pos += total;
-    }
-    HIPCHECK(hipGetLastError());
-    const std::vector<uint8_t> head = ck_head_bytes(ck);
-    if (std::fseek(f, 0, SEEK_SET) != 0) { set_error("object_save: cannot seek in %s", tmp.c_str()); return MON_ERR_IO; }
-    CK_WRITE(head.data(), head.size());
-#undef CK_WRITE
-    if (std::fflush(f) != 0 || ::fsync(::fileno(f)) != 0) { set_error("object_save: flushing %s failed", tmp.c_str()); return MON_ERR_IO; }
-    { const int crc_close = std::fclose(f); out.fc.f = nullptr; if (crc_close != 0) { set_error("object_save: closing %s failed", tmp.c_str()); return MON_ERR_IO; } }
-    if (std::rename(tmp.c_str(), path) != 0) { set_error("object_save: cannot rename %s to %s", tmp.c_str(), path); return MON_ERR_IO; }
-    out.keep = true;
-    return MON_OK;
-}
-
-int model_load(Dataset* ds, const char* path, uint32_t flags, Model** out, std::vector<mon_frame_bbox>* boxes_out) {
-    if (out) *out = nullptr;
-    if (!ds || !path || !out) { set_error("object_load: null argument"); return MON_ERR_ARG; }
-    if (flags & ~MON_LOAD_BOXES) { set_error("object_load: unknown flag bits %#x", flags & ~MON_LOAD_BOXES); return MON_ERR_ARG; }
-    FileCloser fc; fc.f = std::fopen(path, "rb");
-    if (!fc.f) { set_error("checkpoint %s: cannot open", path); return MON_ERR_IO; }
-    FILE* f = fc.f;
-    CkFile ck; { const int rc = ck_parse(f, path, ck); if (rc) return rc; }
-    const mon_checkpoint_info& in = ck.info;
-    if (ck.step_bits != (steps16_exact(in.cfg) ? 16u : 32u)) {
-        set_error("checkpoint %s: %u-bit step counters, this build keeps %u-bit ones for that config", path, ck.step_bits, steps16_exact(in.cfg) ? 16u : 32u);
-        return MON_ERR_STATE; }
-    // the box list (small): read, checked against its CRC and -- when it is to be restored -- against the dataset, all before any device work
-    std::vector<mon_frame_bbox> boxes(in.n_boxes);
-    {   const CkSection* q = ck.find("boxes");
-        if (in.n_boxes) {
-            std::vector<uint8_t> raw(q->bytes());
-            if (std::fseek(f, (long)q->offset, SEEK_SET) != 0 || std::fread(raw.data(), 1, raw.size(), f) != raw.size()) {
-                set_error("checkpoint %s: cannot read section \"boxes\"", path); return MON_ERR_IO; }
-            if (ck_crc(0u, raw.data(), raw.size()) != q->crc) { set_error("checkpoint %s: CRC mismatch in section \"boxes\"", path); return MON_ERR_IO; }
-            for (uint32_t i = 0; i < in.n_boxes; ++i) { const uint8_t* r = raw.data() + 20 * (size_t)i;
-                boxes[i] = mon_frame_bbox{ get32(r, 0), get32(r, 4), get32(r, 8), get32(r, 12), get32(r, 16) }; }
-        } else if (q->crc != 0u) { set_error("checkpoint %s: CRC mismatch in section \"boxes\"", path); return MON_ERR_IO; }
-    }
-    const bool with_boxes = (flags & MON_LOAD_BOXES) != 0u && in.n_boxes != 0u;
-    if (with_boxes) for (uint32_t i = 0; i < in.n_boxes; ++i) {
-        const mon_frame_bbox& b = boxes[i];
-        if (b.FrameId >= ds->max_frames || !ds->present[b.FrameId]) {
-            set_error("object_load: box %u names frame %u, which the dataset does not hold", i, b.FrameId); return MON_ERR_STATE; }
-        if (b.w == 0 || b.h == 0 || b.x + b.w > (uint32_t)ds->K.W || b.y + b.h > (uint32_t)ds->K.H) {
-            set_error("object_load: box %u (x %u y %u h %u w %u) outside the dataset's %dx%d images", i, b.x, b.y, b.h, b.w, ds->K.W, ds->K.H);
-            return MON_ERR_STATE; }
-    }
-    if (boxes_out) *boxes_out = boxes;
-
-    Model* mp = nullptr;
-    { const int rc = model_create_impl(ds, in.cfg, in.class_id, in.Tow, in.aabb_min, in.aabb_max, false, &mp); if (rc) return rc; }
-    struct Guard { Model* m; ~Guard() { if (m) model_destroy(m); } } guard{ mp };
-    Model& m = *mp; hipStream_t s = m.train_stream;
-    if ((m.lazy_ema ? 1u : 0u) != in.lazy_ema || ((m.P.rec || m.P.steps16) ? 16u : 32u) != ck.step_bits) {
-        set_error("checkpoint %s: lazy-EMA / step-counter mode differs from the object this build creates for its config", path); return MON_ERR_STATE; }
-    size_t largest = 0; bool need_device = false;
-    for (const CkSection& q : ck.sec) if (q.tag != "boxes") { largest = std::max(largest, q.bytes()); need_device |= !ck_dev_section(m, q.tag).direct; }
-    CkStage stage; { const int rc = stage.init(largest, need_device); if (rc) return rc; }
-    for (const CkSection& q : ck.sec) {
-        if (q.tag == "boxes") continue;
-        const CkDevSection dv = ck_dev_section(m, q.tag); const size_t total = q.bytes(); uint32_t crc = 0u;
-        // (a grid in the file of an object that keeps none here -- a shape outside the fused kernels -- is checked and dropped)
-        const bool drop = (q.tag == "occ" || q.tag == "occ_raw") && !m.d_occ;
-        if (std::fseek(f, (long)q.offset, SEEK_SET) != 0) { set_error("checkpoint %s: cannot seek to section \"%s\"", path, q.tag.c_str()); return MON_ERR_IO; }
-        for (size_t off = 0; off < total; off += stage.cap) {
-            const size_t n = std::min(stage.cap, total - off);
-            if (std::fread(stage.h, 1, n, f) != n) { set_error("checkpoint %s: cannot read section \"%s\"", path, q.tag.c_str()); return MON_ERR_IO; }
-            crc = ck_crc(crc, stage.h, n);
-            if (drop) continue;
-            if (dv.direct) HIPCHECK(hipMemcpyAsync(static_cast<uint8_t*>(dv.direct) + off, stage.h, n, hipMemcpyHostToDevice, s));
-            else {
-                const size_t per_chunk = dv.rec_which == 4 ? 4 : 32; const uint32_t c0 = (uint32_t)(off / per_chunk), nc = (uint32_t)(n / per_chunk);
-                HIPCHECK(hipMemcpyAsync(stage.d, stage.h, n, hipMemcpyHostToDevice, s));
-                stage.before_kernel(s);
-                if (dv.steps16) launch_steps16_pack_range(s, m.P.steps16, stage.d, c0, nc);
-                else launch_state_pack_range(s, m.P.rec, dv.rec_which, stage.d, c0, nc);
-                stage.after_kernel(s);
-                // h(master) of the range while it sits in the staging buffer as a flat array (the records have no flat master to convert later)
-                if (dv.rec_which == 0) launch_master_to_half(s, reinterpret_cast<const float*>(stage.d), m.P.half + 8u * (size_t)c0, 8u * nc);
-            }
-            HIPCHECK(hipStreamSynchronize(s)); stage.collect();             // (the staging buffers are reused by the next range)
-        }
-        if (crc != q.crc) { set_error("checkpoint %s: CRC mismatch in section \"%s\"", path, q.tag.c_str()); return MON_ERR_IO; }
-        if (q.tag == "master" && dv.direct) launch_master_to_half(s, m.P.master, m.P.half, m.n_params);      // h(master), the rounding of every update
-    }
-    HIPCHECK(hipGetLastError()); HIPCHECK(hipStreamSynchronize(s));
-    if (with_boxes) { const int rc = model_add_boxes(m, boxes.data(), boxes.size()); if (rc) return rc; }
-    // the training state: both DevStates start as the saved one (iteration i reads one and writes everything that changes into the other; the slot counters
-    // of both parities are clear between iterations)
-    const uint32_t* w = ck.state;
-    DevState st{}; st.step = w[CKS_STEP]; st.iter = w[CKS_ITER]; st.skipped = w[CKS_SKIPPED]; st.lr = u2f(w[CKS_LR]); st.n_valid = w[CKS_N_VALID];
-    st.loss_sum = u2f(w[CKS_LOSS_SUM]); st.n_valid_pre = w[CKS_N_VALID_PRE]; st.n_scatter_now = w[CKS_SCATTER_NOW]; st.n_scatter_last = w[CKS_SCATTER_LAST];
-    st.n_scatter_total = w[CKS_SCATTER_TOTAL]; st.ema_deb_old = u2f(w[CKS_DEB_OLD]); st.ema_deb_new = u2f(w[CKS_DEB_NEW]);
-    st.ema_deb_even_old = u2f(w[CKS_DEB_EVEN_OLD]); st.ema_deb_even_new = u2f(w[CKS_DEB_EVEN_NEW]); st.n_boxes = m.n_boxes;
-    m.h_state = st;
-    HIPCHECK(hipMemcpy(m.d_state, &st, sizeof(DevState), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(m.d_state_next, &st, sizeof(DevState), hipMemcpyHostToDevice));
-    if (m.d_occ && in.has_occupancy) { m.occ_refreshed_iter = w[CKS_OCC_REFRESHED]; m.occ_next_refresh = w[CKS_OCC_NEXT]; }
-    if (m.d_occ) m.occ_raw_threshold = u2f(w[CKS_OCC_THRESHOLD]);
-    m.ema_pending = m.lazy_ema && w[CKS_EMA_PENDING] != 0u;
-    m.backend = in.backend;
-    // every derived image is rebuilt from the weights by the next iteration / render, as after set_params
-    m.next_ready = false; m.points_ready = false; m.b0_tiles_current = false; m.scatter_pending = false;
-    m.weights_epoch = next_weights_epoch();
-    { const int rc = publish_snapshot(m); if (rc) return rc; }
-    HIPCHECK(hipStreamSynchronize(nullptr)); HIPCHECK(hipStreamSynchronize(m.train_stream));
-    guard.m = nullptr; *out = mp; return MON_OK;
-#undef CK_BAD
 }
 
 }  // namespace mon

@@ -357,13 +357,12 @@ struct PoseGradArgs {
     float *dbg_x, *dbg_raw, *dbg_g;                             // mon_debug_pose_samples: [ray][2S][3 | 4 | 3], or nullptr
 };
 struct PoseGradArgsLW : PoseGradArgs { const float* level_w; };   // k_pose_grad<.., LW = true>: level l's term of g times level_w[l]
-// (weak: the host-only ThreadSanitizer build, tests/tsan, links without kernels_pose.hip; pose_refine reports MON_ERR_STATE there)
-__attribute__((weak)) uint32_t pose_grad_grid(uint32_t n_rays);
-__attribute__((weak)) void launch_pose_rays(hipStream_t s, const PoseRayArgs& a);
+uint32_t pose_grad_grid(uint32_t n_rays);
+void launch_pose_rays(hipStream_t s, const PoseRayArgs& a);
 // level_w: nullptr = k_pose_grad<.., false>; else the device array of the nd.L level weights of this evaluation (k_pose_grad<.., true>)
-__attribute__((weak)) void launch_pose_grad(hipStream_t s, const LevelFast& lt, const NetDims& nd, const ObjectConst& oc, const uint16_t* params, uint16_t* frag_image,
+void launch_pose_grad(hipStream_t s, const LevelFast& lt, const NetDims& nd, const ObjectConst& oc, const uint16_t* params, uint16_t* frag_image,
         int build_image, const PoseGradArgs& p, const float* level_w);
-__attribute__((weak)) void launch_pose_update(hipStream_t s, const float* partials, uint32_t n_parts, float inv_n, float* out, float* trace, uint32_t it, int step, float lr_t,
+void launch_pose_update(hipStream_t s, const float* partials, uint32_t n_parts, float inv_n, float* out, float* trace, uint32_t it, int step, float lr_t,
         float lr_r, float* pose, float* moments);
 // Camera refinement against a scene of objects (mon_scene_pose_loss / mon_scene_refine_camera, kernels_scene_pose.hip).  Per chunk of `cap` rays:
 // k_scene_pose_rays (targets, every object's ray record under the Twc in device memory) -> per object k_scene_pose_obj<.., BWD = false> (its sample lists, the
@@ -401,22 +400,21 @@ struct ScenePoseUpdateArgs {
     const float* loss_part; uint32_t n_loss_parts;
     const SceneObjConst* objs; float inv_n; float* out; uint32_t it; int step; float lr_t, lr_r; float* pose; float* moments;
 };
-// (weak, as the pose launchers: the host-only ThreadSanitizer build links without the kernels)
-__attribute__((weak)) void launch_scene_pose_rays(hipStream_t s, const ScenePoseRayArgs& a);
-__attribute__((weak)) void launch_scene_pose_obj(hipStream_t s, const LevelFast& lt, const NetDims& nd, const ObjectConst& oc, const uint16_t* params, uint16_t* frag_image,
+void launch_scene_pose_rays(hipStream_t s, const ScenePoseRayArgs& a);
+void launch_scene_pose_obj(hipStream_t s, const LevelFast& lt, const NetDims& nd, const ObjectConst& oc, const uint16_t* params, uint16_t* frag_image,
         int build_image, int backward, uint32_t grid, const ScenePoseObjArgs& p);
-__attribute__((weak)) uint32_t scene_comp_grad_grid(uint32_t n_rays);
-__attribute__((weak)) void launch_scene_composite_grad(hipStream_t s, const SceneCompGradArgs& a);
-__attribute__((weak)) void launch_scene_pose_update(hipStream_t s, const ScenePoseUpdateArgs& a);
+uint32_t scene_comp_grad_grid(uint32_t n_rays);
+void launch_scene_composite_grad(hipStream_t s, const SceneCompGradArgs& a);
+void launch_scene_pose_update(hipStream_t s, const ScenePoseUpdateArgs& a);
 // Batched pose scoring (mon_scene_pose_loss_batch, kernels_scene_score.hip).  A pass holds G hypotheses of n_per rays as G * n_per virtual rays
 // v = g * n_per + r in the lists of one evaluation (cap >= G * n_per): k_scene_score_rays (n_rays = G * n_per, pose = every hypothesis's Twc, 16 floats each;
 // ray0 unused) -> per object k_scene_pose_obj<.., false, false> over the virtual rays -> k_scene_composite_loss (grid (scene_comp_grad_grid(n_per), G), one
 // loss partial per workgroup, hypothesis-major) -> k_scene_loss_reduce (one workgroup per hypothesis, k_scene_pose_update's order, out[g] = loss).
 constexpr uint32_t kSceneScoreMaxPoses = 4096, kRelocMaxKeep = 16, kSceneScoreMaxRays = 16384;      // (rays: the chunk cap of the chain; a hypothesis is never split)
 struct SceneScoreRayArgs : ScenePoseRayArgs { uint32_t n_per, h0; };      // rays per hypothesis; the pass's first hypothesis
-__attribute__((weak)) void launch_scene_score_rays(hipStream_t s, const SceneScoreRayArgs& a);
-__attribute__((weak)) void launch_scene_composite_loss(hipStream_t s, const SceneCompGradArgs& a, uint32_t n_per);
-__attribute__((weak)) void launch_scene_loss_reduce(hipStream_t s, const float* loss_part, uint32_t n_hyp, uint32_t n_parts, float inv_n, float* out);
+void launch_scene_score_rays(hipStream_t s, const SceneScoreRayArgs& a);
+void launch_scene_composite_loss(hipStream_t s, const SceneCompGradArgs& a, uint32_t n_per);
+void launch_scene_loss_reduce(hipStream_t s, const float* loss_part, uint32_t n_hyp, uint32_t n_parts, float inv_n, float* out);
 // Window refinement (mon_scene_window_loss / mon_scene_refine_window, kernels_scene_window.hip + the window kernels of kernels_scene_pose.hip).  A pass
 // packs whole frames as virtual rays v = v0_f + r into the list workspace of one evaluation, at most kWindowPassRays of them, greedily in window order.  One
 // row of the device table per frame; per pass k_scene_window_rays -> per object k_scene_pose_obj<.., false, false> over the virtual rays ->
@@ -436,11 +434,11 @@ struct SceneWindowUpdateArgs {
     float* out; uint32_t out_stride, it; int step;            // out[out_stride * it] = {L, L_f [F], grad6_f [F][6], obj_grad6_j [K][6]}
     float lr_t, lr_r, lr_obj_t, lr_obj_r;
 };
-__attribute__((weak)) void launch_scene_window_rays(hipStream_t s, const SceneWindowRayArgs& a);
-__attribute__((weak)) void launch_scene_window_composite(hipStream_t s, const SceneCompGradArgs& a, uint32_t grid, uint32_t n_frames, const SceneWinFrame* frames);
-__attribute__((weak)) void launch_scene_window_obj(hipStream_t s, const LevelFast& lt, const NetDims& nd, const ObjectConst& oc, const uint16_t* params,
+void launch_scene_window_rays(hipStream_t s, const SceneWindowRayArgs& a);
+void launch_scene_window_composite(hipStream_t s, const SceneCompGradArgs& a, uint32_t grid, uint32_t n_frames, const SceneWinFrame* frames);
+void launch_scene_window_obj(hipStream_t s, const LevelFast& lt, const NetDims& nd, const ObjectConst& oc, const uint16_t* params,
         uint16_t* frag_image, uint32_t grid, uint32_t n_frames, const SceneWinFrame* frames, const ScenePoseObjArgs& p);
-__attribute__((weak)) void launch_scene_window_update(hipStream_t s, const SceneWindowUpdateArgs& a);
+void launch_scene_window_update(hipStream_t s, const SceneWindowUpdateArgs& a);
 // inference on feature-planar level tiles (kernels_tilerender.hip): Render / RenderVideo, GetDensityOnGrid, mesh vertex colours
 constexpr uint32_t kTileChunkJobs = 32768;          // rays (jobs of 2S = 64 samples) per chunk of the tile render
 bool tile_render_supported(const LevelTable& lt, const NetDims& nd);
@@ -477,7 +475,7 @@ struct Dataset {
 };
 
 struct MeshState;   // mesh.cpp
-struct InferState;  // model.cpp: inference stream, published weight snapshots and the render workspace of their own
+struct InferState;  // model_internal.h: inference stream, published weight snapshots and the render workspace of their own
 
 // Render skipping (mon_object_set_render_skip) of one side: the train stream's renders (Model) or the snapshot renders (InferState, inference stream).
 // Each side has its own grids: a viewer renders while the object trains, and training's occupancy grid (d_occ) is another thing altogether.
@@ -547,7 +545,7 @@ struct Model {
     bool tile_ok = false;        // the inference side may run on feature-planar level tiles (tile_render_supported)
     std::atomic<int> rskip_on{ 0 }; std::atomic<float> rskip_alpha{ 1e-3f };      // render skipping: the switch (read once per render call)
     RenderSkipSide rskip;                                                             // ... and its train-stream side
-    struct PoseWs* pose_ws[2] = { nullptr, nullptr };                                // pose refinement scratch per side (model.cpp), made on first use
+    struct PoseWs* pose_ws[2] = { nullptr, nullptr };                                // pose refinement scratch per side (pose.cpp), made on first use 
     uint64_t weights_epoch = 0;  // process-wide unique stamp of the weights' current content (a new one after every train call / set_params / EMA catch-up):
                                  // the tile render's per-device workspace keeps its tile image while the stamp it was built for is current
     bool next_ready = false;     // fused backend: candidates + fragment image of the coming iteration were already produced by the last k_optimizer

@@ -1,0 +1,92 @@
+// model_internal.h -- what model.cpp, pose.cpp, scene.cpp and checkpoint.cpp need from each other and nobody else needs (c_api.cpp, manager.cpp and
+// diag.cpp go through model.h).
+#pragma once
+#include <atomic>
+#include <chrono>
+#include <mutex>
+#include <vector>
+#include "model.h"
+
+namespace mon {
+
+void set_error(const char* fmt, ...);      // the calling thread's mon_last_error text
+#define HIPCHECK(expr)                                                                                         \
+    do { hipError_t _e = (expr); if (_e != hipSuccess) {                                                       \
+        set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); return MON_ERR_HIP; } } while (0)
+constexpr uint32_t kRenderChunkRays = 16384;   // rays per render pass (x 2S samples)
+
+// One high-priority stream and one pinned result buffer per DEVICE, shared by the objects on it (viewer renders) and by the device's dataset (frame uploads):
+// created with the device's first object (CreateNeRF is a
+// milliseconds call anyway; created by the first render it was a 10 ms spike in front of the viewer), and only one more hardware-queue client however many
+// objects train (a high-priority queue per object measurably slowed sliced training).  Renders of one device take turns on it.
+// h_cap only grows; h_out / growth belong to mu
+struct InferShared { std::mutex mu; hipStream_t stream = nullptr; float* h_out = nullptr; std::atomic<size_t> h_cap{ 0 }; };
+
+// ---- inference side of a model (the reference's second stream, nerf_model.cu:1268-1269).  The training thread PUBLISHES the inference weights
+// at the end of every train call / online slice: a device-to-device copy into one of two snapshot buffers, ordered on the train stream, with an
+// event.  A viewer thread renders from the latest published snapshot on the inference stream (created with the highest priority) and in a
+// workspace of its own: it takes no model mutex, never touches the train stream, and its kernels do not queue behind training slices.
+struct InferState {
+    InferShared* shared = nullptr;                                      // the device's inference stream (highest priority) and pinned result buffer
+    uint16_t* snap[2] = { nullptr, nullptr }; hipEvent_t ready[2] = { nullptr, nullptr }; uint32_t step_of[2] = { 0, 0 }; bool written[2] = { false, false };
+    int latest = -1, readers[2] = { 0, 0 }; std::mutex mu;              // which snapshot is current, who is reading which
+    // weights stamp of each snapshot (next_weights_epoch at publication: the tile render's image key)
+    uint64_t epoch_of[2] = { 0, 0 };
+    std::atomic<bool> wanted{ false }; std::chrono::steady_clock::time_point last_pub{};      // a viewer asked since the last publication; when that was
+    BatchPtrs rb{}; float *out_all = nullptr, *out_rgb = nullptr, *out_depth = nullptr, *out_mask = nullptr; size_t out_cap = 0; uint16_t* frag = nullptr;
+    std::vector<void*> grown;                                           // superseded output buffers, freed with the object
+    RenderSkipSide rskip;                                               // render skipping of the snapshot renders (under shared->mu, on its stream)
+};
+
+// The published snapshot a side-1 call reads, pinned (readers[r], which keeps publish_snapshot off the buffer) from take() until the pin goes: on every way
+// out of the call.  take() also tells the training side that a viewer asked (it refreshes the snapshot at the end of its current slice) and orders the
+// snapshot's copy in front of the caller's stream `s`.  Which snapshot:
+// the newest snapshot's copy may still be queued behind other objects' training kernels (it runs on the train stream, at normal priority: 1-2 ms on a
+// busy device); the one before it is complete, and nobody writes it before the train stream has been synchronised again -- by which time the newest is
+// complete and chosen here.  A viewer prefers a finished snapshot one slice older to waiting.
+struct SnapshotPin {
+    InferState* held = nullptr; int r = -1; uint32_t step = 0; uint64_t epoch = 0;      // step_of[r], epoch_of[r]: neither changes while the pin is held
+    SnapshotPin() = default; SnapshotPin(const SnapshotPin&) = delete; SnapshotPin& operator=(const SnapshotPin&) = delete;
+    // MON_ERR_STATE, with nothing pinned, while nothing has been published
+    int take(InferState* is, hipStream_t s) {
+        is->wanted.store(true);
+        {   std::lock_guard<std::mutex> l(is->mu); r = is->latest; if (r < 0) { set_error("no weights published yet"); return MON_ERR_STATE; }
+            if (is->written[1 - r] && hipEventQuery(is->ready[r]) != hipSuccess && hipEventQuery(is->ready[1 - r]) == hipSuccess) r = 1 - r;
+            ++is->readers[r]; held = is; step = is->step_of[r]; epoch = is->epoch_of[r]; }
+        HIPCHECK(hipStreamWaitEvent(s, is->ready[r], 0));
+        return MON_OK;
+    }
+    const uint16_t* snap() const { return held->snap[r]; }
+    ~SnapshotPin() { if (held) { std::lock_guard<std::mutex> l(held->mu); --held->readers[r]; } }
+};
+
+// Grow-only scratch in device memory (Pinned: in pinned host memory): growth frees and allocates, the contents are not carried over; freed with its owner.
+template <class T, bool Pinned = false> struct DevBuf {
+    T* p = nullptr; size_t cap = 0;
+    DevBuf() = default; DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+    void release() { if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
+    int grow(size_t n) {
+        if (n <= cap && p) return MON_OK;
+        release();
+        HIPCHECK(Pinned ? hipHostMalloc((void**)&p, n * sizeof(T), hipHostMallocDefault) : hipMalloc((void**)&p, n * sizeof(T))); cap = n; return MON_OK;
+    }
+    ~DevBuf() { release(); }
+};
+template <class T> using PinnedBuf = DevBuf<T, true>;
+
+bool rskip_supported(const Model& m);          // the object runs on the fused kernels
+// the side's grid of `prm` (stamp `epoch`) on stream s: the cached one, or built through the training grid's kernels into `frag`, the side's fragment image
+// of the same weights; nullptr when the side has no grid buffers
+const uint32_t* rskip_grid(Model& m, RenderSkipSide& k, hipStream_t s, float alpha, const uint16_t* prm, uint64_t epoch, uint16_t* frag);
+int config_check(const mon_config& cfg);       // what mon_object_create rejects before the level table is built
+bool steps16_exact(const mon_config& cfg);     // model_init's rule for the step counters; a checkpoint records which one its object kept
+// init_params = false (model_load): the parameters are left for the caller to stream in -- nothing of table size is staged
+int model_create_impl(Dataset* ds, const mon_config& cfg, int class_id, const float* Tow, const float* amin, const float* amax, bool init_params, Model** out);
+int publish_snapshot(Model& m, bool force = true); int model_destroy(Model* mp);
+int model_add_boxes(Model& m, const mon_frame_bbox* boxes, size_t n);
+void pose_ws_free(Model& m);                   // pose.cpp: the object's pose refinement scratch
+// pose.cpp: box i of a pose call names a frame the dataset holds and lies inside it; its pixels join `total` (at most 64 kPoseMaxRays).  `what`: the message
+// prefix ("pose", "scene pose")
+int pose_box_check(const char* what, const Dataset& ds, const mon_frame_bbox& b, size_t i, uint64_t& total);
+
+}  // namespace mon

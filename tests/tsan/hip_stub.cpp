@@ -1,6 +1,6 @@
 // hip_stub.cpp -- a stand-in for the HIP runtime for the ThreadSanitizer build of the HOST side (tests/tsan/build_and_run.sh).
 // "Device" memory is host memory, copies are memcpy, streams and events complete immediately, kernel launches do nothing: no result means anything, but every
-// lock, condition variable, atomic and thread of model.cpp / manager.cpp (training lanes, the online manager's protocol, snapshot publication, create / destroy
+// lock, condition variable, atomic and thread of the host sources (training lanes, the online manager's protocol, snapshot publication, create / destroy
 // under load) runs exactly as it does on the GPU box, and TSAN watches it.  TEST INFRASTRUCTURE: never linked into the product.
 #include <hip/hip_runtime.h>
 #include <atomic>

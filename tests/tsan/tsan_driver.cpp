@@ -1,6 +1,6 @@
 // tsan_driver.cpp -- drives the C ABI of a ThreadSanitizer build of the host side (linked against hip_stub.cpp) through the concurrent situations the
-// managers create on the GPU box: several objects trained from their own threads through the device's training lanes while the lane count flips, a viewer
-// rendering from published snapshots, objects created and destroyed meanwhile, and the online manager's whole protocol (frames, boxes, empty updates, renders,
+// managers create on the GPU box: several objects trained from their own threads through the device's training lanes while the lane count flips, viewers
+// rendering and evaluating poses from published snapshots, objects created and destroyed meanwhile, and the online manager's whole protocol (frames, boxes, empty updates, renders,
 // finish).  Exit status 0 and no TSAN report = pass.  TEST INFRASTRUCTURE.
 #include <atomic>
 #include <chrono>
@@ -45,6 +45,23 @@ int main(int argc, char** argv) {
                     const int rc = mon_object_render_snapshot(objs[k], mon_frame_bbox{ 0, 8, 8, 16, 16 }, pose, 0, c.data(), d.data(), m.data(), &step);
                     if (rc != MON_OK && rc != MON_ERR_STATE) std::exit(4); } }
         });
+        // a second viewer: every side-1 route that pins snapshots and takes the device's inference lock -- object pose, scene pose (one evaluation, a batch, a
+        // window of two frames) and the scene render -- over three of the objects.  The launches do nothing here: the values are not looked at.
+        const auto pose_routes = [&](bool must_succeed) {
+            mon_pose_refine_params pp; OK(mon_pose_refine_default(&pp)); pp.rays_per_iter = 48;
+            const mon_frame_bbox one[1] = { { 0, 8, 8, 8, 8 } }, two[2] = { { 0, 8, 8, 8, 8 }, { 1, 8, 8, 8, 8 } };
+            float Twc[3 * 16]; for (int f = 0; f < 3; ++f) std::memcpy(Twc + 16 * f, pose, 64);
+            float loss = 0.f, g6[6], losses[3], floss[2], cg[12], og[18]; std::vector<float> c(3 * 64), d(64), o(64); std::vector<int32_t> in(64);
+            const int rcs[5] = {
+                mon_object_pose_loss(objs[0], 1, one, 1, Tow, &pp, 0u, &loss, g6),
+                mon_scene_pose_loss(objs.data(), 3, 1, one, 1, Twc, &pp, 0u, nullptr, &loss, g6),
+                mon_scene_pose_loss_batch(objs.data(), 3, 1, one, 1, Twc, 3, &pp, 0u, losses),
+                mon_scene_window_loss(objs.data(), 3, 1, two, 2, Twc, nullptr, &pp, 0u, nullptr, &loss, floss, cg, og),
+                mon_scene_render(objs.data(), 3, 1, mon_frame_bbox{ 0, 8, 8, 8, 8 }, pose, c.data(), d.data(), o.data(), in.data()) };
+            for (int rc : rcs) if (rc != MON_OK && (must_succeed || rc != MON_ERR_STATE)) { std::fprintf(stderr, "pose route -> %d: %s\n", rc, mon_last_error());
+                std::exit(5); }
+        };
+        th.emplace_back([&] { while (!stop.load()) pose_routes(false); });
         th.emplace_back([&] {          // objects come and go
             for (int i = 0; i < 12; ++i) { mon_object* o = nullptr; float loss; OK(mon_object_create(ds, &cfg, 7, Tow, amin, amax, &o));
                 OK(mon_object_add_boxes(o, boxes.data(), 12)); OK(mon_object_train(o, 5, &loss)); OK(mon_object_destroy(o)); }
@@ -52,6 +69,7 @@ int main(int argc, char** argv) {
         for (int k = 0; k < K; ++k) th[k].join();
         th.back().join(); th.pop_back();
         stop.store(true); for (size_t k = K; k < th.size(); ++k) th[k].join();
+        pose_routes(true);          // (every object has published by now)
         for (auto& o : objs) OK(mon_object_destroy(o));
         OK(mon_dataset_destroy(ds));
     }
