@@ -152,6 +152,31 @@ __host__ __device__ inline void pixel_ray(const Intrinsics& K, float px, float p
 // product once -- one result in ~2^13 then differs by an fp16 ulp.  The product passes through an opaque register.
 __device__ __forceinline__ float opaque_f32(float v) { asm volatile("" : "+v"(v)); return v; }
 
+// ---------------------------------------------------------------- wave priority (compile-time: -DMON_WAVE_PRIO=0 builds the kernels without it)
+// The VALU of a SIMD goes to the wave of the highest priority, then to the OLDEST: of waves that share a SIMD and do equal work the youngest finishes last and
+// runs its tail alone, with nothing to hide its latencies behind.  Which waves share a SIMD is not architecturally fixed, so the priority is keyed on a wave's own
+// PROGRESS: it starts its loop at 3 and gives a level away with every quarter of its trips -- a wave that lags always outranks the ones ahead of it.
+// s_setprio is a scalar instruction and ignores EXEC: every call sits under control flow on readfirstlane'd scalars (a branch on a vector condition would lower
+// to an exec mask around an UNCONDITIONAL s_setprio), and takes an immediate, hence the branch chain.  Back to 0 before a barrier and before a kernel's epilogue.
+#ifndef MON_WAVE_PRIO
+#define MON_WAVE_PRIO 1
+#endif
+template <int P> __device__ __forceinline__ void wave_prio_set() {
+#if MON_WAVE_PRIO
+    __builtin_amdgcn_s_setprio(P);
+#endif
+}
+// trip `done` of `total` (both wave-uniform); constant arguments fold to one s_setprio
+__device__ __forceinline__ void wave_prio_graded(uint32_t done, uint32_t total) {
+#if MON_WAVE_PRIO
+    const uint32_t d4 = 4u * (uint32_t)__builtin_amdgcn_readfirstlane((int)done), t = (uint32_t)__builtin_amdgcn_readfirstlane((int)total);
+    if (d4 < t) __builtin_amdgcn_s_setprio(3);
+    else if (d4 < 2u * t) __builtin_amdgcn_s_setprio(2);
+    else if (d4 < 3u * t) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
+#endif
+}
+
 // ---------------------------------------------------------------- activations, nerf_model.cu:22-64
 __device__ inline float logistic_f(float x) { return 1.0f / (1.0f + __expf(-x)); }
 __device__ inline float clamp_f(float x, float a, float b) { return fminf(fmaxf(x, a), b); }

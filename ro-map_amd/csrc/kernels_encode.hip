@@ -76,7 +76,16 @@ struct EncodeArgs {
     // then turn them into next iteration's positions (gen_next = 0: nothing to prepare)
     uint32_t gen_next; BatchPtrs b_next; DatasetPtrs ds;  ObjectConst oc;
     LiveArgs live;                 // occupancy-grid skipping: walk each partition's list of live samples instead of all of its samples (idx == nullptr: all)
+#ifdef MON_ENCODE_TIMING
+    float* timing;                 // [workgroup][wave][4]: clock at the wave's entry (low 24 bits), cycles from there to the end of its first / second sample loop, SIMD
+#endif
 };
+// -DMON_ENCODE_TIMING (tools/encode_timing.py): a clock stamp per wave behind each of its sample loops, stores drained
+#ifdef MON_ENCODE_TIMING
+#define MON_ET_STAMP(et, k) do { __builtin_amdgcn_s_waitcnt(0); (et)[k] = clock64(); } while (0)
+#else
+#define MON_ET_STAMP(et, k) do { } while (0)
+#endif
 
 // the chain of encode_interp: corners in order k = x + 2y + 4z, c0[j] / c1[j] = x-corner 0 / 1 of pair j, weight ((wx * wy) * wz); the two x-corners of a pair
 // and the two features of a corner are worked on as pairs (v_pk_mul_f32 / v_pk_fma_f32: the same IEEE operations, two per instruction)
@@ -116,14 +125,22 @@ __device__ __forceinline__ void load_positions(float4_t (&xs)[kEncSpt], uint32_t
 template <bool LIVE> __device__ __forceinline__ bool round_on(uint32_t k, uint32_t count) {
     return !LIVE || k * kEncThreads + (threadIdx.x & ~63u) < count; }
 
+// wave priority by progress (device_common.h): round k of the rounds this wave walks -- all kEncSpt without the list, else those its part of the list reaches
+template <bool LIVE> __device__ __forceinline__ uint32_t rounds_on(uint32_t count) {
+    const uint32_t w0 = threadIdx.x & ~63u; return !LIVE ? kEncSpt : (count <= w0 ? 0u : min(kEncSpt, (count - w0 + kEncThreads - 1u) / kEncThreads)); }
+template <bool LIVE> __device__ __forceinline__ void round_prio(uint32_t k, uint32_t n_on) {
+    if (LIVE || (k & 1u) == 0u) wave_prio_graded(k, n_on); }      // (a constant trip count changes level every second round)
+
 template <bool HASHED, bool POW2, bool LIVE>
 __device__ __forceinline__ void encode_whole(const uint32_t* tile, const EncodeArgs& a, uint32_t s_base, uint32_t s_end, uint32_t count,
-        half2_t* __restrict__ out, float scale, uint32_t size, uint32_t my, uint32_t mz, uint32_t mask) {
+        half2_t* __restrict__ out, float scale, uint32_t size, uint32_t my, uint32_t mz, uint32_t mask, long long* et) {
     if (s_base + threadIdx.x >= s_end && !LIVE) return;
     float4_t xs[kEncSpt]; uint32_t slot[kEncSpt]; load_positions<LIVE>(xs, slot, a, s_base, s_end, count);
+    const uint32_t n_on = rounds_on<LIVE>(count);
 #pragma unroll
     for (uint32_t k = 0; k < kEncSpt; ++k) {
         if (!round_on<LIVE>(k, count)) continue;
+        round_prio<LIVE>(k, n_on);
         uint32_t i0[4], i1[4], c0[4], c1[4]; float pos[3];
         enc_indices<HASHED, POW2>(xs[k], scale, size, my, mz, mask, i0, i1, pos);
 #pragma unroll
@@ -131,12 +148,14 @@ __device__ __forceinline__ void encode_whole(const uint32_t* tile, const EncodeA
         const half2_t e = enc_chain(c0, c1, pos);
         if (slot[k] != 0xffffffffu) policy_store<MON_SP_E>(e, out + slot[k]);
     }
+    wave_prio_set<0>();
+    MON_ET_STAMP(et, 1);
 }
 
 template <bool HASHED, bool POW2, bool LIVE>
 // (src: the level in the tile image, evens then odds)
 __device__ __forceinline__ void encode_parity(uint32_t* tile, const uint4* __restrict__ src, const EncodeArgs& a, uint32_t s_base, uint32_t s_end, uint32_t count,
-                                              half2_t* __restrict__ out, float scale, uint32_t size, uint32_t my, uint32_t mz, uint32_t mask) {
+                                              half2_t* __restrict__ out, float scale, uint32_t size, uint32_t my, uint32_t mz, uint32_t mask, long long* et) {
     // pass 0: the even entries.  Per pair the even one of (i0, i1) is read now; the odd one is kept for pass 1 as 16 bits whose (always set) lowest bit is
     // replaced by "the odd one is x-corner 0"
     // (the position inside the cell is kept too: 24 registers against a second load + 9 instructions per sample)
@@ -144,12 +163,14 @@ __device__ __forceinline__ void encode_parity(uint32_t* tile, const uint4* __res
     const bool walk = LIVE ? (threadIdx.x & ~63u) < count : s_base + threadIdx.x < s_end;
     float4_t xs[kEncSpt]; uint32_t slot[kEncSpt];
     if (walk) load_positions<LIVE>(xs, slot, a, s_base, s_end, count);          // (the copy of the even half is under way: k_encode_tiles requested it at its entry)
+    const uint32_t n_on = rounds_on<LIVE>(count);
     __builtin_amdgcn_s_waitcnt(0x0f70);                                   // vmcnt(0): the LDS writes of the copy are counted there
     __syncthreads();
     if (walk) {
 #pragma unroll
         for (uint32_t k = 0; k < kEncSpt; ++k) {
             if (!round_on<LIVE>(k, count)) continue;
+            round_prio<LIVE>(k, n_on);
             uint32_t i0[4], i1[4], c[4];
             enc_indices<HASHED, POW2>(xs[k], scale, size, my, mz, mask, i0, i1, pos[k]);
 #pragma unroll
@@ -161,7 +182,9 @@ __device__ __forceinline__ void encode_parity(uint32_t* tile, const uint4* __res
             }
             cache[k][0] = c[0] | (c[1] << 16); cache[k][1] = c[2] | (c[3] << 16);
         }
+        wave_prio_set<0>();
     }
+    MON_ET_STAMP(et, 1);
     __syncthreads();
     tile_copy(tile, src + size / 8u, size / 8u);
     __builtin_amdgcn_s_waitcnt(0x0f70);
@@ -170,6 +193,7 @@ __device__ __forceinline__ void encode_parity(uint32_t* tile, const uint4* __res
 #pragma unroll
         for (uint32_t k = 0; k < kEncSpt; ++k) {
             if (!round_on<LIVE>(k, count)) continue;
+            round_prio<LIVE>(k, n_on);
             uint32_t c0[4], c1[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -181,12 +205,16 @@ __device__ __forceinline__ void encode_parity(uint32_t* tile, const uint4* __res
             const half2_t e = enc_chain(c0, c1, pos[k]);
             if (slot[k] != 0xffffffffu) policy_store<MON_SP_E>(e, out + slot[k]);
         }
+        wave_prio_set<0>();
     }
+    MON_ET_STAMP(et, 2);
 }
 
 __global__ void __launch_bounds__(kEncThreads) k_encode_tiles(EncodeArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t* tile = reinterpret_cast<uint32_t*>(smem);
+    long long et[3] = { 0, 0, 0 };
+    MON_ET_STAMP(et, 0);
     const uint32_t level = blockIdx.x / kEncWgPerLevel, part = blockIdx.x - level * kEncWgPerLevel;
     if (a.gen_next && level == 0u && blockIdx.y == 0u && threadIdx.x < 256u)
         for (uint32_t c0 = part * 256u; c0 < a.oc.R; c0 += kEncWgPerLevel * 256u) gen_candidate(a.b_next, a.ds, a.oc, a.st->n_boxes, a.st->iter + 1u,
@@ -215,15 +243,20 @@ __global__ void __launch_bounds__(kEncThreads) k_encode_tiles(EncodeArgs a) {
     if (size <= kEncWholeMax) {
         __builtin_amdgcn_s_waitcnt(0x0f70);
         __syncthreads();
-        if (hashed) { if (pow2) MON_ENC_CALL(encode_whole, true, true, tile, a, s_base, s_end, count, out, scale, size, my, mz, mask);
-            else MON_ENC_CALL(encode_whole, true, false, tile, a, s_base, s_end, count, out, scale, size, my, mz, mask); }
-        else MON_ENC_CALL(encode_whole, false, false, tile, a, s_base, s_end, count, out, scale, size, my, mz, mask);
+        if (hashed) { if (pow2) MON_ENC_CALL(encode_whole, true, true, tile, a, s_base, s_end, count, out, scale, size, my, mz, mask, et);
+            else MON_ENC_CALL(encode_whole, true, false, tile, a, s_base, s_end, count, out, scale, size, my, mz, mask, et); }
+        else MON_ENC_CALL(encode_whole, false, false, tile, a, s_base, s_end, count, out, scale, size, my, mz, mask, et);
     } else {
-        if (hashed) { if (pow2) MON_ENC_CALL(encode_parity, true, true, tile, src, a, s_base, s_end, count, out, scale, size, my, mz, mask);
-            else MON_ENC_CALL(encode_parity, true, false, tile, src, a, s_base, s_end, count, out, scale, size, my, mz, mask); }
-        else MON_ENC_CALL(encode_parity, false, false, tile, src, a, s_base, s_end, count, out, scale, size, my, mz, mask);
+        if (hashed) { if (pow2) MON_ENC_CALL(encode_parity, true, true, tile, src, a, s_base, s_end, count, out, scale, size, my, mz, mask, et);
+            else MON_ENC_CALL(encode_parity, true, false, tile, src, a, s_base, s_end, count, out, scale, size, my, mz, mask, et); }
+        else MON_ENC_CALL(encode_parity, false, false, tile, src, a, s_base, s_end, count, out, scale, size, my, mz, mask, et);
     }
 #undef MON_ENC_CALL
+#ifdef MON_ENCODE_TIMING
+    if (a.timing && blockIdx.y == 0u && (threadIdx.x & 63u) == 0u) { float* o = a.timing + ((size_t)blockIdx.x * 16u + (threadIdx.x >> 6)) * 4u;
+        o[0] = (float)(et[0] & 0xffffff); o[1] = (float)(et[1] - et[0]); o[2] = (float)(et[2] ? et[2] - et[0] : 0);
+        o[3] = (float)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4); }      // HW_ID.simd_id
+#endif
 }
 
 // the tile image from the fp16 working copy (object creation, set_params, backend switch: whenever the weights changed outside k_optimizer, which keeps it
@@ -268,6 +301,12 @@ void launch_xorwow_fill(hipStream_t s, void* lane_states, uint32_t lanes, int fl
             n0, out1, n1, out2, n2);
 }
 
+#ifdef MON_ENCODE_TIMING
+constexpr size_t kEncTimingBytes = (size_t)kMaxLevels * kEncWgPerLevel * 16 * 4 * sizeof(float);
+static float* g_enc_timing_buf = nullptr;
+extern "C" int mon_debug_encode_timing(float* out) { hipDeviceSynchronize();
+    return g_enc_timing_buf ? (int)hipMemcpy(out, g_enc_timing_buf, kEncTimingBytes, hipMemcpyDeviceToHost) : -1; }
+#endif
 uint32_t encode_tiles_spw(uint32_t B) {
     const uint32_t per_chunk = kEncWgPerLevel * kEncThreads * kEncSpt, chunks = (B + per_chunk - 1u) / per_chunk;
     return (B + kEncWgPerLevel * chunks - 1u) / (kEncWgPerLevel * chunks);
@@ -288,6 +327,9 @@ void launch_encode_tiles(hipStream_t s, const LevelFast& lf, const NetDims& nd, 
     const uint32_t spw = encode_tiles_spw(B);
     EncodeArgs a{ lf, nd.L, nd.n_mlp, half_tiles, reinterpret_cast<const float4_t*>(x_all), reinterpret_cast<half2_t*>(e_soa), B, spw, st,
             b_next ? 1u : 0u, b_next ? *b_next : BatchPtrs{}, ds, oc, live };
+#ifdef MON_ENCODE_TIMING
+    static float* g_timing = nullptr; if (!g_timing) hipMalloc((void**)&g_timing, kEncTimingBytes); a.timing = g_enc_timing_buf = g_timing;
+#endif
 #ifdef MON_OVERLAP_PROBE
     // (lds_bytes bit 0 = launch without the AQL barrier bit, hipExtAnyOrderLaunch: ignored on gfx950, HISTORY 7.9)
     if (lds_bytes & 1u) { hipExtLaunchKernelGGL(k_encode_tiles, dim3((uint32_t)nd.L * kEncWgPerLevel, chunks), dim3(kEncThreads), (lds_bytes & ~1u) ? (lds_bytes & ~1u)

@@ -227,6 +227,8 @@ __device__ __forceinline__ void scatter_samples(int* tab, const half2_t* __restr
 #pragma unroll
     for (int u = 0; u < kBatch; ++u) fetch(nxt[u], nv[u]);
     for (uint32_t s0 = 0; s0 < n_steps; s0 += kBatch) {
+        // wave priority by progress (device_common.h): scalar compares and branches around an s_setprio, nothing that waits
+        wave_prio_graded(s0, n_steps);
         ScatterItem cur[kBatch]; bool cv[kBatch];
 #pragma unroll
         for (int u = 0; u < kBatch; ++u) { cur[u] = nxt[u]; cv[u] = nv[u]; }
@@ -238,6 +240,7 @@ __device__ __forceinline__ void scatter_samples(int* tab, const half2_t* __restr
         for (int u = 0; u < kBatch; ++u) scatter_item<HASHED, POW2, MODE,
                 DEGEN>(tab, cur[u], cv[u], feature, scale, size, my, mz, mask, parity, base_half, tile, fs);
     }
+    wave_prio_set<0>();
 }
 
 // The weight-gradient partial rows of k_fused_train (one per workgroup) are summed here as well: every scatter workgroup
@@ -446,7 +449,8 @@ __global__ void __launch_bounds__(1024) k_grid_scatter(LevelFast lt, ScatterLeve
     MON_ST_STAMP();
 #ifdef MON_SCATTER_TIMING
     if (timing && (threadIdx.x & 63u) == 0u) { float* o = timing + ((size_t)blockIdx.x * 16u + (threadIdx.x >> 6)) * 8u;
-        for (int k = 0; k + 1 < tn && k < 6; ++k) o[k] = (float)(tq[k + 1] - tq[k]); o[6] = (float)(tq[0] & 0xffffff); o[7] = (float)level; }
+        for (int k = 0; k + 1 < tn && k < 6; ++k) o[k] = (float)(tq[k + 1] - tq[k]); o[6] = (float)(tq[0] & 0xffffff);
+        o[7] = (float)((uint32_t)level | (__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4) << 4)); }      // level | HW_ID.simd_id << 4
 #endif
 }
 

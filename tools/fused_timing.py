@@ -18,9 +18,10 @@ PH = ["prologue (frag image, compaction table)", "ray select + position", "encod
 
 
 def main():
-    out = os.path.join(ROOT, "ro-map_amd", "build_timing")
+    tag = os.environ.get("MON_TIMING_TAG", "timing"); flags = os.environ.get("MON_TIMING_FLAGS", "").split()      # e.g. timing_noprio, -DMON_WAVE_PRIO=0
+    out = os.path.join(ROOT, "ro-map_amd", "build_" + tag)
     if not os.path.exists(os.path.join(out, "libmon_core.so")) or os.environ.get("MON_TIMING_REBUILD"):
-        subprocess.check_call([os.path.join(ROOT, "tools", "variant_build.sh"), "timing", "-DMON_FUSED_TIMING"])
+        subprocess.check_call([os.path.join(ROOT, "tools", "variant_build.sh"), tag, "-DMON_FUSED_TIMING"] + flags)
     lib = os.path.join(out, "libmon_core.so")
     if os.environ.get("MON_TIMING_BUILD_ONLY"):
         return
@@ -50,6 +51,13 @@ def main():
     ids = np.unique(hw >> 8)
     per = np.array([dur[(hw >> 8) == i].max() for i in ids]); cnt = np.array([((hw >> 8) == i).sum() for i in ids])
     print("distinct (se, sh, cu) ids per XCD slice seen: %d; waves per id: min %d max %d; slowest-wave end per id: p10 %.2f p50 %.2f p90 %.2f max %.2f us" % (len(ids), cnt.min(), cnt.max(), *np.percentile(per, [10, 50, 90, 100])))
+    # the waves that share a SIMD: same XCD label (blockIdx % 8), same (se, sh, cu), same simd
+    key = ((np.arange(len(hw)) // 4 % 8).astype(np.int64) << 16) | ((hw >> 8) << 2) | ((hw >> 4) & 3); second = (hw & 1) != 0      # (HW_ID.wave_id & 1: the stagger's test)
+    pairs = [np.where(key == k)[0] for k in np.unique(key)]; pairs = [p for p in pairs if len(p) == 2]
+    if pairs:
+        e = np.array([sorted(dur[p]) for p in pairs])
+        print("wave end per SIMD (%d SIMDs with two waves): first %.2f second %.2f us, apart mean %.2f max %.2f;  by slot: even %.2f odd %.2f us" % (len(pairs),
+                e[:, 0].mean(), e[:, 1].mean(), (e[:, 1] - e[:, 0]).mean(), (e[:, 1] - e[:, 0]).max(), dur[~second].mean(), dur[second].mean()))
     wgt = tw.reshape(-1, 4).max(1)
     print("per-workgroup (slowest wave, without the epilogue wait): p50 %.0f p90 %.0f max %.0f;  by XCD (blockIdx %% 8) mean: %s" % (*np.percentile((tw - t[:,
             9]).reshape(-1, 4).max(1), [50, 90, 100]), " ".join("%.0f" % wgt[x::8].mean() for x in range(8))))

@@ -1,6 +1,7 @@
 #!/usr/bin/env bash
 # Builds a variant of libmon_core.so with extra compiler flags into ro-map_amd/build_<tag>/ (experiments / instrumentation).
 # Usage: tools/variant_build.sh <tag> [-DFLAG ...]     then run anything with MON_CORE_LIB=ro-map_amd/build_<tag>/libmon_core.so
+#        tools/variant_build.sh noprio -DMON_WAVE_PRIO=0      the kernels without wave priorities (device_common.h)
 set -euo pipefail
 TAG="$1"; shift
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")/../ro-map_amd" && pwd)"
