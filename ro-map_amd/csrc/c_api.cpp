@@ -6,39 +6,6 @@
 #include "model.h"
 #include "frag_layout.h"
 
-namespace mon {
-void set_error(const char* fmt, ...);
-const char* last_error();
-int device_count(int* n);
-int physical_device(int logical, int* phys_out);
-void config_default(mon_config& c);
-int config_from_json(const char* path, mon_config& c);
-int dataset_create(int device, int H, int W, float fx, float fy, float cx, float cy, uint32_t max_frames, int use_depth, Dataset** out);
-int dataset_add_frame(Dataset* d, uint32_t id, const uint8_t* rgb, int ch, int is_bgr, const uint8_t* inst, const float* depth, const float* Twc);
-int dataset_destroy(Dataset* d);
-int model_create(Dataset* ds, const mon_config& cfg, int class_id, const float* Tow, const float* amin, const float* amax, Model** out);
-int model_destroy(Model* m);
-int model_add_boxes(Model& m, const mon_frame_bbox* boxes, size_t n);
-int model_train(Model& m, int iters, float* loss, int stages);
-int model_render(Model& m, mon_frame_bbox box, const float* pose16, int pose_is_Toc, float* rgb, float* depth, float* mask, int dst_on_device);
-int model_density_grid(Model& m, int rx, int ry, int rz, float* out_host);
-int model_get_params(Model& m, int which, void* dst, size_t bytes);
-int model_set_params(Model& m, const float* master, size_t n);
-int model_debug_read(Model& m, int which, void* dst, size_t bytes);
-int model_generate_mesh(Model& m, int res, float thresh, uint32_t* n_verts, uint32_t* n_indices);
-int model_mesh_counts(Model& m, uint32_t* n_verts, uint32_t* n_verts_real, uint32_t* n_indices);
-int model_get_mesh(Model& m, float* verts, float* normals, uint8_t* colors, uint32_t* indices, float* normals_raw, float* colors_f32, int try_only);
-int model_save_mesh(Model& m, const char* path);
-int model_mesh_generation(Model& m, uint64_t* gen);
-int model_copy_mesh(Model& m, uint32_t cap_verts, uint32_t cap_indices, float* verts, float* normals, uint8_t* colors, uint32_t* indices,
-                    uint32_t* n_verts, uint32_t* n_verts_real, uint32_t* n_indices, int try_only);
-int marching_cubes_host(int device, const float* density, int rx, int ry, int rz, float thresh, const float* amin, const float* amax,
-                        float* verts, float* normals_raw, uint32_t* indices, uint32_t cap_verts, uint32_t cap_indices, uint32_t* n_verts,
-                                uint32_t* n_verts_real, uint32_t* n_indices);
-int microbench(int device, int mode, int pattern, uint32_t n_entries, uint32_t n_ops, float* ms_out);
-}  // namespace mon
-
-
 // ---- coarse-to-fine level weights (include/mon_core.h): the checks of a schedule, one row of weights, the table of a whole refinement
 namespace mon {
 int pose_c2f_check(const mon_pose_c2f_params* c) {
@@ -352,15 +319,8 @@ int mon_object_load(mon_dataset* ds, const char* path, uint32_t flags, mon_objec
     const int rc = model_load(ds->d, path, flags, &m); if (rc) return rc;
     *out = new mon_object{ m }; return MON_OK;
 }
-int mon_object_set_backend(mon_object* o, int backend) {
-    REQUIRE(o, "object");
-    if (backend == 1 && !fused_supported(o->m->nd, o->m->oc.S, o->m->oc.R)) { set_error("fused backend does not support this network shape");
-        return MON_ERR_ARG; }
-    if (backend != 0 && backend != 1) { set_error("backend must be 0 or 1"); return MON_ERR_ARG; }
-    o->m->backend = backend; o->m->next_ready = false; o->m->b0_tiles_current = false; return MON_OK;
-}
-int mon_object_set_debug_dump(mon_object* o, int enable) { REQUIRE(o, "object"); o->m->fused_dump = enable < 0 ? 0 : (enable > 2 ? 2 : enable);
-    o->m->graph_backend = -1; return MON_OK; }
+int mon_object_set_backend(mon_object* o, int backend) { REQUIRE(o, "object"); return model_set_backend(*o->m, backend); }
+int mon_object_set_debug_dump(mon_object* o, int enable) { REQUIRE(o, "object"); return model_set_debug_dump(*o->m, enable); }
 int mon_object_set_profiling(mon_object* o, int enable) { REQUIRE(o, "object"); o->m->profiling = enable != 0; return MON_OK; }
 int mon_object_get_profile(mon_object* o, mon_profile* out, int reset) {
     REQUIRE(o, "object"); REQUIRE(out, "out"); *out = o->m->prof; if (reset) std::memset(&o->m->prof, 0, sizeof(mon_profile)); return MON_OK;

@@ -232,7 +232,7 @@ int model_save(Model& m, const char* path) {
     in.version = kCkVersion; in.cfg = m.cfg; in.class_id = (int32_t)m.oc.instance_id; std::memcpy(in.Tow, m.oc.Tow.m, 64);
     for (int a = 0; a < 3; ++a) { in.aabb_min[a] = m.oc.aabb.mn[a]; in.aabb_max[a] = m.oc.aabb.mx[a]; }
     in.n_params = m.n_params; in.n_mlp_params = (uint32_t)m.nd.n_mlp; in.n_grid_params = m.n_grid; in.train_step = m.h_state.step; in.iter = m.h_state.iter;
-    in.n_boxes = m.n_boxes; in.backend = m.backend; in.has_occupancy = (m.d_occ && m.occ_refreshed_iter) ? 1u : 0u; in.lazy_ema = m.lazy_ema ? 1u : 0u;
+    in.n_boxes = m.n_boxes; in.backend = m.backend; in.has_occupancy = (m.d_occ && m.occ_refreshed_iter) ? 1u : 0u; in.lazy_ema = m.plan.lazy_ema ? 1u : 0u;
     ck.step_bits = (m.P.rec || m.P.steps16) ? 16u : 32u;
     const DevState& st = m.h_state; uint32_t* w = ck.state;
     w[CKS_STEP] = st.step; w[CKS_ITER] = st.iter; w[CKS_SKIPPED] = st.skipped; w[CKS_LR] = f2u(st.lr); w[CKS_N_VALID] = st.n_valid;
@@ -325,7 +325,7 @@ int model_load(Dataset* ds, const char* path, uint32_t flags, Model** out, std::
     { const int rc = model_create_impl(ds, in.cfg, in.class_id, in.Tow, in.aabb_min, in.aabb_max, false, &mp); if (rc) return rc; }
     struct Guard { Model* m; ~Guard() { if (m) model_destroy(m); } } guard{ mp };
     Model& m = *mp; hipStream_t s = m.train_stream;
-    if ((m.lazy_ema ? 1u : 0u) != in.lazy_ema || ((m.P.rec || m.P.steps16) ? 16u : 32u) != ck.step_bits) {
+    if ((m.plan.lazy_ema ? 1u : 0u) != in.lazy_ema || ((m.P.rec || m.P.steps16) ? 16u : 32u) != ck.step_bits) {
         set_error("checkpoint %s: lazy-EMA / step-counter mode differs from the object this build creates for its config", path); return MON_ERR_STATE; }
     size_t largest = 0; bool need_device = false;
     for (const CkSection& q : ck.sec) if (q.tag != "boxes") { largest = std::max(largest, q.bytes()); need_device |= !ck_dev_section(m, q.tag).direct; }
@@ -371,10 +371,10 @@ int model_load(Dataset* ds, const char* path, uint32_t flags, Model** out, std::
     HIPCHECK(hipMemcpy(m.d_state_next, &st, sizeof(DevState), hipMemcpyHostToDevice));
     if (m.d_occ && in.has_occupancy) { m.occ_refreshed_iter = w[CKS_OCC_REFRESHED]; m.occ_next_refresh = w[CKS_OCC_NEXT]; }
     if (m.d_occ) m.occ_raw_threshold = u2f(w[CKS_OCC_THRESHOLD]);
-    m.ema_pending = m.lazy_ema && w[CKS_EMA_PENDING] != 0u;
+    m.ema_pending = m.plan.lazy_ema && w[CKS_EMA_PENDING] != 0u;
     m.backend = in.backend;
     // every derived image is rebuilt from the weights by the next iteration / render, as after set_params
-    m.next_ready = false; m.points_ready = false; m.b0_tiles_current = false; m.scatter_pending = false;
+    model_mark_stale(m, kStaleRays | kStaleWeights); m.scatter_pending = false;
     m.weights_epoch = next_weights_epoch();
     { const int rc = publish_snapshot(m); if (rc) return rc; }
     HIPCHECK(hipStreamSynchronize(nullptr)); HIPCHECK(hipStreamSynchronize(m.train_stream));

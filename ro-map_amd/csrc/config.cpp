@@ -16,7 +16,22 @@
 
 namespace mon {
 
-void set_error(const char* fmt, ...);
+// ------------------------------------------------------------------ process-wide options (mon_set_option)
+static Options g_options;
+Options& options() { return g_options; }
+static std::atomic<long>* option_slot(const char* name) {
+    static const struct { const char* n; std::atomic<long> Options::*f; } tab[] = {
+        { "backend", &Options::backend }, { "use_graph", &Options::use_graph }, { "big_switch", &Options::big_switch }, { "lds_encode", &Options::lds_encode },
+        { "roctx", &Options::roctx }, { "step_variant", &Options::step_variant }, { "keep_zero_samples", &Options::keep_zero_samples },
+        { "train_lanes", &Options::train_lanes }, { "tile_render", &Options::tile_render },
+    };
+    for (const auto& e : tab) if (name && std::strcmp(name, e.n) == 0) return &(g_options.*(e.f));
+    return nullptr;
+}
+int option_set(const char* name, long value) { std::atomic<long>* p = option_slot(name); if (!p) {
+        set_error("set_option: unknown option '%s'", name ? name : "(null)"); return MON_ERR_ARG; } *p = value; return MON_OK; }
+int option_get(const char* name, long* value) { std::atomic<long>* p = option_slot(name); if (!p || !value) {
+        set_error("get_option: unknown option '%s'", name ? name : "(null)"); return MON_ERR_ARG; } *value = *p; return MON_OK; }
 
 // ------------------------------------------------------------------ minimal JSON (objects, arrays, strings, numbers, bools, null, // and /* */ comments)
 struct JVal {
@@ -146,6 +161,25 @@ int config_from_json(const char* path, mon_config& c) {
 }
 
 // ------------------------------------------------------------------ level table (tcnn grid.h; SURVEY TCNN-A1/A2/A4)
+// (model_load runs a file's config through the same checks)
+int config_check(const mon_config& cfg) {
+    if (cfg.rays_per_batch < 64 || (cfg.rays_per_batch % 64) != 0 || cfg.n_samples < 1 || cfg.n_samples > 64) {
+        set_error("rays_per_batch must be a multiple of 64, n_samples 1..64"); return MON_ERR_ARG; }
+    if ((cfg.rng_flags & 3u) == 3u || (cfg.rng_flags & ~0xffff0013u) != 0u || (cfg.rng_flags >> 16) > 1024u) {
+        set_error("rng_flags: bits 0-1 = 0 (counter RNG) | 1 (XORWOW, cuRAND flavour) | 2 (XORWOW, rocRAND flavour), bit 4 = tcnn init order, "
+                  "bits 16-31 = XORWOW lanes / 1024 (at most 1024)");
+        return MON_ERR_ARG;
+    }
+    if (!(cfg.loss_scale > 0.f) || !(cfg.loss_scale <= 65536.f)) { set_error("loss_scale must be in (0, 65536] (fp16 gradients; the reference uses 128)");
+        return MON_ERR_ARG; }
+    return MON_OK;
+}
+// model_init's rule for the step counters
+bool steps16_exact(const mon_config& cfg) {
+    const double kSteps16Bound = std::ldexp(1.0, -29);
+    return kSteps16 && std::pow((double)cfg.beta1, 65535.0) < kSteps16Bound && std::pow((double)cfg.beta2, 65535.0) < kSteps16Bound;
+}
+
 static uint32_t next_multiple(uint32_t v, uint32_t d) { return ((v + d - 1) / d) * d; }
 
 int level_table_build(const mon_config& c, LevelTable& lt, NetDims& nd, uint32_t& n_grid) {

@@ -9,9 +9,6 @@
 #include "../../include/mon_core_diag.h"
 
 namespace mon {
-void set_error(const char* fmt, ...);
-int ensure_ema_current(Model& m);
-int microbench(int device, int mode, int pattern, uint32_t n_entries, uint32_t n_ops, float* ms);
 int selftest_mfma(int device, const uint16_t* A, const uint16_t* B, float* D);
 bool read_yaml_number(const std::string& text, const char* key, double& v);
 
@@ -83,7 +80,7 @@ int model_debug_read(Model& m, int which, void* dst, size_t bytes) {
         std::vector<float> acc(m.n_grid);
         for (uint32_t i = 0; i < m.n_grid; ++i) { _Float16 h; std::memcpy(&h, &tab[i], 2); acc[i] = (float)h; }
         // whole steps of the shapes outside the fused kernels keep their partial tables too (hybrid_scatter); the dense optimizer then never reads the table
-        const bool parts = (m.backend == 1 && m.lds_mask) || (m.backend == 0 && m.hybrid_scatter && which == MON_BUF_GGRID_F32);
+        const bool parts = (m.backend == 1 && m.plan.lds_mask) || (m.backend == 0 && m.plan.hybrid_scatter && which == MON_BUF_GGRID_F32);
         if (parts) {
             // partial tables are planar: [partition][feature][parity][entry / 2], over the LDS-scattered levels' entries
             const uint32_t n_ent = m.part_halves / 2, n_half = n_ent / 2;
@@ -96,7 +93,7 @@ int model_debug_read(Model& m, int which, void* dst, size_t bytes) {
                         hipMemcpyDeviceToHost));
                 for (int l = 0; l < m.nd.L; ++l) {
                     // (a level with fewer partial tables: the rest of the buffer is not its data)
-                    const bool lds_level = m.backend == 1 ? ((m.lds_mask >> l) & 1u) != 0u : true;
+                    const bool lds_level = m.backend == 1 ? ((m.plan.lds_mask >> l) & 1u) != 0u : true;
                     if (q >= m.scatter.P[l] || !lds_level) continue;
                     const bool two = q + 1 < m.scatter.P[l];
                     for (uint32_t e = m.lt.offset[l]; e < m.lt.offset[l + 1]; ++e) for (uint32_t f = 0; f < 2; ++f)
@@ -198,12 +195,12 @@ int mon_debug_set_train_occupancy(mon_object* o, const uint32_t* bits) {
         if (m.h_state.iter < (uint32_t)mon::kOccWarmup) { HIPCHECK(hipMemset(m.d_occ, 0xff, bytes)); m.occ_refreshed_iter = 0; }
         m.occ_next_refresh = 0;                              // (after the warm-up: due at the next iteration)
     }
-    m.points_ready = false;                                  // the positions sampled ahead carry the old grid's live bits and lists, as after a refresh
+    mon::model_mark_stale(m, mon::kStaleOccupancy);          // the positions sampled ahead carry the old grid's live bits and lists, as after a refresh
     return MON_OK;
 }
 int mon_debug_render_jobs(mon_object* o, int side, uint32_t* jobs) {
     if (!o || !o->m || !jobs) { mon::set_error("debug_render_jobs: null argument"); return MON_ERR_ARG; }
-    if (!o->m->tile_ok) { mon::set_error("debug_render_jobs: this object does not render on level tiles"); return MON_ERR_STATE; }
+    if (!o->m->plan.tile_render) { mon::set_error("debug_render_jobs: this object does not render on level tiles"); return MON_ERR_STATE; }
     mon::TileWs* ws = nullptr; const int rc = mon::tile_ws_get(*o->m, side, 0, &ws); if (rc) return rc;
     std::lock_guard<std::mutex> l(ws->mu);
     if (!ws->counters) { mon::set_error("debug_render_jobs: no tile workspace on the object's device"); return MON_ERR_STATE; }

@@ -23,9 +23,6 @@
 #include "tile_device.h"
 #include "store_policy.h"
 #include "xorwow.h"
-#ifdef MON_OVERLAP_PROBE
-#include <hip/hip_ext.h>
-#endif
 
 namespace mon {
 
@@ -322,7 +319,7 @@ void launch_sample_points(hipStream_t s, const BatchPtrs& b, const ObjectConst& 
 
 void launch_encode_tiles(hipStream_t s, const LevelFast& lf, const NetDims& nd, const uint16_t* half_tiles, const float* x_all, uint16_t* e_soa, uint32_t B,
         const DevState* st,
-                         const BatchPtrs* b_next, const DatasetPtrs& ds, const ObjectConst& oc, uint32_t lds_bytes, const LiveArgs& live) {
+                         const BatchPtrs* b_next, const DatasetPtrs& ds, const ObjectConst& oc, const LiveArgs& live) {
     const uint32_t per_chunk = kEncWgPerLevel * kEncThreads * kEncSpt, chunks = (B + per_chunk - 1u) / per_chunk;
     const uint32_t spw = encode_tiles_spw(B);
     EncodeArgs a{ lf, nd.L, nd.n_mlp, half_tiles, reinterpret_cast<const float4_t*>(x_all), reinterpret_cast<half2_t*>(e_soa), B, spw, st,
@@ -330,12 +327,7 @@ void launch_encode_tiles(hipStream_t s, const LevelFast& lf, const NetDims& nd, 
 #ifdef MON_ENCODE_TIMING
     static float* g_timing = nullptr; if (!g_timing) hipMalloc((void**)&g_timing, kEncTimingBytes); a.timing = g_enc_timing_buf = g_timing;
 #endif
-#ifdef MON_OVERLAP_PROBE
-    // (lds_bytes bit 0 = launch without the AQL barrier bit, hipExtAnyOrderLaunch: ignored on gfx950, HISTORY 7.9)
-    if (lds_bytes & 1u) { hipExtLaunchKernelGGL(k_encode_tiles, dim3((uint32_t)nd.L * kEncWgPerLevel, chunks), dim3(kEncThreads), (lds_bytes & ~1u) ? (lds_bytes & ~1u)
-            : kEncLdsBytes, s, nullptr, nullptr, hipExtAnyOrderLaunch, a); return; }
-#endif
-    hipLaunchKernelGGL(k_encode_tiles, dim3((uint32_t)nd.L * kEncWgPerLevel, chunks), dim3(kEncThreads), lds_bytes ? lds_bytes : kEncLdsBytes, s, a);
+    hipLaunchKernelGGL(k_encode_tiles, dim3((uint32_t)nd.L * kEncWgPerLevel, chunks), dim3(kEncThreads), kEncLdsBytes, s, a);
 }
 
 }  // namespace mon

@@ -25,25 +25,6 @@
 
 namespace mon {
 
-void set_error(const char* fmt, ...);
-const char* last_error();
-int device_count(int* n);
-int config_from_json(const char* path, mon_config& c);
-int dataset_create(int device, int H, int W, float fx, float fy, float cx, float cy, uint32_t max_frames, int use_depth, Dataset** out);
-int dataset_add_frame(Dataset* d, uint32_t id, const uint8_t* rgb, int ch, int is_bgr, const uint8_t* inst, const float* depth, const float* Twc);
-int dataset_destroy(Dataset* d);
-int model_create(Dataset* ds, const mon_config& cfg, int class_id, const float* Tow, const float* amin, const float* amax, Model** out);
-int model_destroy(Model* m);
-int model_add_boxes(Model& m, const mon_frame_bbox* boxes, size_t n);
-int model_generate_mesh(Model& m, int res, float thresh, uint32_t* n_verts, uint32_t* n_indices);
-int model_save_mesh(Model& m, const char* path);
-int model_mesh_counts(Model& m, uint32_t* n_verts, uint32_t* n_verts_real, uint32_t* n_indices);
-int model_train(Model& m, int iters, float* loss, int stages);
-int stream_pool_reserve(int device, int n);
-int dataset_update_poses(Dataset* d, uint32_t first, uint32_t n, const float* Twc16s);
-int model_render(Model& m, mon_frame_bbox box, const float* pose16, int pose_is_Toc, float* rgb, float* depth, float* mask, int dst_on_device);
-int model_render_snapshot(Model& m, mon_frame_bbox box, const float* pose16, int pose_is_Toc, float* rgb, float* depth, float* mask, uint32_t* snapshot_step);
-
 // Eigen::Quaternionf(w,x,y,z).toRotationMatrix() + translation -> column-major 4x4 (nerf_data.cu:100-106)
 static void pose_from_tq(const float* t, float qx, float qy, float qz, float qw, float* M) {
     const float n = std::sqrt(qx * qx + qy * qy + qz * qz + qw * qw); qx /= n; qy /= n; qz /= n; qw /= n;
@@ -578,7 +559,7 @@ int mon_online_update_dataset(mon_online* h, uint32_t cur_id, uint32_t frame_num
         std::vector<std::unique_ptr<AnnouncedLock>> held, models;
         for (auto* o : online_objects(m)) if (o->device == g) held.emplace_back(new AnnouncedLock(o, *o->dataset_mutex));
         const int rc = dataset_update_poses(m.ds[g], head, frame_num, Twc16s); if (rc) return rc;
-        for (auto* o : online_objects(m)) if (o->device == g && o->model) { AnnouncedLock lm(o, o->mu_model); o->model->next_ready = false; }
+        for (auto* o : online_objects(m)) if (o->device == g && o->model) { AnnouncedLock lm(o, o->mu_model); model_mark_stale(*o->model, kStaleRays); }
     }
     for (uint32_t i = 0; i < frame_num; ++i) m.poses[head + i].assign(Twc16s + 16 * (size_t)i, Twc16s + 16 * (size_t)i + 16);
     return MON_OK;

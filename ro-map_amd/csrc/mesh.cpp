@@ -171,7 +171,7 @@ int model_generate_mesh(Model& m, int res, float thresh, uint32_t* n_verts, uint
         ~TileHold() { if (lock.owns_lock()) { (void)hipStreamSynchronize(s); lock.unlock(); } }
     };
     TileWs* ws = nullptr;
-    if (m.backend == 1 && m.tile_ok && options().tile_render != 0) { rc = tile_ws_get(m, 0, 0, &ws); if (rc) return rc; }
+    if (m.backend == 1 && m.plan.tile_render && options().tile_render != 0) { rc = tile_ws_get(m, 0, 0, &ws); if (rc) return rc; }
     const uint32_t chunk = ws ? ws->cap : m.ws_samples;
     {   TileHold hold(ws, s);
         if (ws) tile_ws_weights(m, *ws, s, prm, m.weights_epoch);

@@ -8,7 +8,6 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -28,28 +27,6 @@ void set_error(const char* fmt, ...) {
     char buf[1024]; va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap); g_err = buf;
 }
 const char* last_error() { return g_err.c_str(); }
-
-static Options g_options;
-Options& options() { return g_options; }
-static std::atomic<long>* option_slot(const char* name) {
-    static const struct { const char* n; std::atomic<long> Options::*f; } tab[] = {
-        { "backend", &Options::backend }, { "use_graph", &Options::use_graph }, { "big_switch", &Options::big_switch }, { "lds_encode", &Options::lds_encode },
-        { "roctx", &Options::roctx }, { "step_variant", &Options::step_variant }, { "keep_zero_samples", &Options::keep_zero_samples },
-        { "train_lanes", &Options::train_lanes }, { "tile_render", &Options::tile_render },
-#ifdef MON_OVERLAP_PROBE
-        { "overlap", &Options::overlap }, { "enc_lds_kb", &Options::enc_lds_kb },
-#endif
-    };
-    for (const auto& e : tab) if (name && std::strcmp(name, e.n) == 0) return &(g_options.*(e.f));
-    return nullptr;
-}
-int option_set(const char* name, long value) { std::atomic<long>* p = option_slot(name); if (!p) {
-        set_error("set_option: unknown option '%s'", name ? name : "(null)"); return MON_ERR_ARG; } *p = value; return MON_OK; }
-int option_get(const char* name, long* value) { std::atomic<long>* p = option_slot(name); if (!p || !value) {
-        set_error("get_option: unknown option '%s'", name ? name : "(null)"); return MON_ERR_ARG; } *value = *p; return MON_OK; }
-
-void config_default(mon_config& c);
-int config_from_json(const char* path, mon_config& c);
 
 // Logical devices: what the managers and the C ABI number 0 .. n-1.  By default they are the physical HIP devices; mon_set_logical_devices(n)
 // maps n logical devices round-robin onto the physical ones, so the multi-device code paths (object k -> device k mod nGPU, one dataset replica and
@@ -81,7 +58,6 @@ int device_count(int* n) {
 }
 
 // ------------------------------------------------------------------ dataset
-int dataset_destroy(Dataset* d);
 // the devices' inference streams and pinned result buffers (InferShared, model_internal.h)
 static std::mutex g_infer_mu; static std::map<int, InferShared*> g_infer_shared;
 static int infer_shared_get(int device, size_t pixels_hint, InferShared** out) {
@@ -213,123 +189,8 @@ static int tile_render_crop(Model& m, TileWs& ws, hipStream_t s, const ObjectCon
 // --, 2 always)
 static bool tile_render_wanted(const Model& m, size_t n_pix) {
     const long o = options().tile_render;
-    return m.backend == 1 && m.tile_ok && m.oc.S == 32u && o != 0 && (o >= 2 || n_pix >= 4096);
+    return m.backend == 1 && m.plan.tile_render && m.oc.S == 32u && o != 0 && (o >= 2 || n_pix >= 4096);
 }
-
-// ---- training lanes: the per-device scheduler behind "one host thread per object" (nerf_manager.cu:89,256-259).
-// Measured (tools/multi_object.py, base.json objects): two objects training concurrently fall into anti-phase on their own -- one gathers (k_fused_train,
-// bound by the L2 request path) while the other scatters and updates (LDS atomics, HBM) -- 1.75 G ray-samples/s against 1.38 G for one; with three or more streams in flight
-// the dispatcher mixes workgroups of kernels that exclude each other on a CU (k_grid_scatter takes a CU's whole LDS; streams beyond the hardware queues share
-// one and block each other) and the aggregate drops to 1.5 G.  So the training work of ALL objects of a device goes through `train_lanes` (2) shared streams: a
-// chunk of an object's iterations is enqueued on the lane with the least work in flight (the lane of the object's previous chunk while that is still running:
-// stream order then keeps the object's iterations in sequence; a change of lane is ordered by an event).  The device sees two streams of whole training steps
-// whatever the number of objects.
-// Lanes order work for speed only: no result depends on them.
-constexpr int kMaxLanes = 4; constexpr uint32_t kLaneRing = 256;
-// a lane's chunk events are only QUERIED (how much work is in flight): without the system-scope fence of a default event (an L2 write-back per chunk)
-constexpr unsigned kLaneEventFlags = hipEventDisableTiming | hipEventDisableSystemFence;
-struct TrainLanes {
-    std::mutex mu; std::atomic<int> objects{ 0 };      // live objects of the device
-    // per lane: `mu` orders the enqueueing of whole chunks; ev[tail .. head) = completion events of the chunks in flight (head: written by the enqueuer, tail:
-    // by whoever picks a lane, under TrainLanes::mu); pending = chunks that have picked the lane and not finished enqueueing
-    struct Lane { std::mutex mu; hipStream_t stream = nullptr; hipEvent_t ev[kLaneRing] = {}; std::atomic<uint32_t> head{ 0 }, pending{ 0 },
-            tail{ 0 }; } lane[kMaxLanes];
-};
-static std::mutex g_lanes_mu; static std::map<int, TrainLanes*> g_lanes;
-// (the device is current.)  The lane streams are created TOGETHER, with the device's dataset and before any object's own stream: the runtime places a new
-// stream on the hardware queue with the fewest users, so two streams created back to back get different queues -- created lazily, with object streams in
-// between, both lanes could land on one queue and run strictly one after the other.
-static TrainLanes* lanes_get(int device) {
-    std::lock_guard<std::mutex> l(g_lanes_mu); TrainLanes*& t = g_lanes[device];
-    if (!t) {
-        t = new TrainLanes();
-        const long want_lanes = options().train_lanes; const int n = want_lanes < kMaxLanes ? (int)want_lanes : kMaxLanes;
-        for (int i = 0; i < n; ++i) if (hipStreamCreateWithFlags(&t->lane[i].stream, hipStreamNonBlocking) != hipSuccess) { t->lane[i].stream = nullptr;
-            (void)hipGetLastError(); }
-    }
-    return t;
-}
-#ifdef MON_VARIANT_STALE_MARK          // (variant build for the regression test: the bug it guards against)
-#define MON_INVALIDATE_MARK(m) ((void)0)
-#else
-#define MON_INVALIDATE_MARK(m) ((m).tail_marked = false)
-#endif
-// marks the end of what the object has enqueued so far on its current stream (called where an entry point returns with work still in flight: the end of a train
-// call)
-static void mark_tail(Model& m) {
-    // (a DEFAULT event, with its release fence: this one orders the object's kernels across two hardware queues)
-    if (!m.switch_event && hipEventCreateWithFlags(&m.switch_event, hipEventDisableTiming) != hipSuccess) { m.switch_event = nullptr; m.tail_marked = false;
-        return; }
-    m.tail_marked = hipEventRecord(m.switch_event, m.train_stream) == hipSuccess;
-}
-// moves the object's work to stream `to`: everything it has enqueued so far is ordered before whatever follows on the new stream.  The wait is for the object's
-// OWN last work (mark_tail) -- an event recorded now would also stand behind every chunk other objects have queued on the old lane since, and tie the two lanes
-// together.
-static void switch_stream(Model& m, hipStream_t to);
-// Everything that is not a training chunk (renders on the train stream, density grids, meshes, parameter access, box uploads) runs on the object's OWN stream:
-// on a lane it would queue -- and its synchronisation would wait -- behind every chunk other objects have enqueued there.
-// (work follows: an earlier mark no longer stands for the object's last work)
-void model_leave_lane(Model& m) { switch_stream(m, m.own_stream); MON_INVALIDATE_MARK(m); }
-static void switch_stream(Model& m, hipStream_t to) {
-    if (m.train_stream == to) return;
-    if (!m.tail_marked) mark_tail(m);
-    if (m.tail_marked) (void)hipStreamWaitEvent(to, m.switch_event, 0);
-    else (void)hipStreamSynchronize(m.train_stream);
-    m.train_stream = to; m.tail_marked = false;
-}
-// One chunk of an object's iterations on a lane.  The lane is picked under the device-wide lock (short); the chunk is then ENQUEUED under the lane's own lock
-// (a few microseconds per launch), so the chunks of different objects do not interleave within a lane while the host threads of different lanes enqueue side by
-// side.
-struct LaneChunk {
-    Model& m; TrainLanes* tl = nullptr; std::unique_lock<std::mutex> lock; int l = -1;
-    explicit LaneChunk(Model& mm, bool enabled) : m(mm) {
-        const long want_lanes = options().train_lanes; const int n = want_lanes < kMaxLanes ? (int)want_lanes : kMaxLanes;
-        // (up to `n` objects: their own streams ARE the lanes)
-        if (!enabled || n <= 0 || !m.lanes || m.lanes->objects.load() <= n) { switch_stream(m, m.own_stream); MON_INVALIDATE_MARK(m); return; }
-        tl = m.lanes;
-        {   std::lock_guard<std::mutex> pick(tl->mu);
-            // previous chunk still in flight: same lane
-            if (m.lane >= 0 && m.lane < n && m.lane_event && m.train_stream == tl->lane[m.lane].stream
-                    && hipEventQuery(m.lane_event) == hipErrorNotReady) l = m.lane;
-            else {
-                uint32_t best = ~0u, mine = ~0u;
-                for (int i = 0; i < n; ++i) {
-                    TrainLanes::Lane& L = tl->lane[i];
-                    const uint32_t head = L.head.load(std::memory_order_acquire);
-                    uint32_t tail = L.tail.load(std::memory_order_relaxed);
-                    while (tail != head && hipEventQuery(L.ev[tail % kLaneRing]) == hipSuccess) ++tail;          // retire finished chunks
-                    L.tail.store(tail, std::memory_order_relaxed);
-                    const uint32_t load = head - tail + L.pending.load();
-                    if (i == m.lane && m.train_stream == L.stream) mine = load;
-                    if (load < best) { best = load; l = i; }
-                }
-                if (mine != ~0u && mine < best + 2u) l = m.lane;                                               // stay unless the other lane is clearly shorter
-            }
-            // (a hipErrorNotReady would otherwise be reported by the next hipGetLastError)
-            (void)hipGetLastError();
-            tl->lane[l].pending.fetch_add(1);
-        }
-        TrainLanes::Lane& L = tl->lane[l];
-        lock = std::unique_lock<std::mutex>(L.mu);
-        if (!L.stream && hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking) != hipSuccess) { L.stream = nullptr; L.pending.fetch_sub(1); tl = nullptr;
-            lock.unlock(); switch_stream(m, m.own_stream); MON_INVALIDATE_MARK(m); return; }
-        switch_stream(m, L.stream);
-        // work follows on this stream: the mark of an earlier call no longer stands for the object's last work
-        MON_INVALIDATE_MARK(m);
-    }
-    ~LaneChunk() {
-        if (!tl) return;
-        TrainLanes::Lane& L = tl->lane[l];
-        const uint32_t head = L.head.load(std::memory_order_relaxed);
-        // (a full ring -- 256 chunks in flight on one lane -- goes uncounted)
-        if (head - L.tail.load(std::memory_order_relaxed) < kLaneRing) {
-            hipEvent_t& e = L.ev[head % kLaneRing];
-            if ((e || hipEventCreateWithFlags(&e, kLaneEventFlags) == hipSuccess) && hipEventRecord(e, m.train_stream) == hipSuccess) {
-                L.head.store(head + 1u, std::memory_order_release); m.lane_event = e; }
-        }
-        m.lane = l; L.pending.fetch_sub(1);
-    }
-};
 
 int dataset_create(int device, int H, int W, float fx, float fy, float cx, float cy, uint32_t max_frames, int use_depth, Dataset** out) {
     int n = 0; int rc = device_count(&n); if (rc) return rc;
@@ -425,13 +286,6 @@ int stream_pool_reserve(int device, int n) {
     return rc;
 }
 
-template <class T> static int dev_alloc(Model& m, T*& p, size_t n, bool zero = true) {
-    void* q = nullptr; const size_t bytes = (n ? n : 1) * sizeof(T);
-    HIPCHECK(hipMalloc(&q, bytes));
-    if (zero) HIPCHECK(hipMemset(q, 0, bytes));
-    m.allocs.push_back(q); p = (T*)q; return MON_OK;
-}
-
 // ---- render skipping (mon_object_set_render_skip): per side, a grid of the weights the render reads, cached per weights stamp and min_alpha
 static int rskip_alloc(Model& m, RenderSkipSide& k) {
     if (k.d_grid) return MON_OK;
@@ -483,70 +337,89 @@ static int upload_master(Model& m, const float* master) {
         launch_master_to_half(m.train_stream, tmp, m.P.half, (uint32_t)n); e = hipStreamSynchronize(m.train_stream); }
     (void)hipFree(tmp); HIPCHECK(e); return MON_OK;
 }
-MeshState* mesh_state_create(int device);
-bool steps16_exact(const mon_config& cfg) {
-    const double kSteps16Bound = std::ldexp(1.0, -29);
-    return kSteps16 && std::pow((double)cfg.beta1, 65535.0) < kSteps16Bound && std::pow((double)cfg.beta2, 65535.0) < kSteps16Bound;
-}
-static int model_init(Model& m, Dataset* ds, const mon_config& cfg, int class_id, const float* Tow, const float* amin, const float* amax, bool init_params) {
-    m.ds = ds; m.cfg = cfg; m.device = ds->device;
-    int rc = level_table_build(cfg, m.lt, m.nd, m.n_grid);
-    if (rc) return rc;
-    m.n_params = m.nd.n_mlp + m.n_grid;
-    level_fast_build(m.lt, m.nd, m.lf);
-    {   // fixed-point unit of the exact LDS gradient accumulation: 2^-24 (every fp16 value is a multiple of it) up to the reference's loss scale of
-        // 128, coarser by the next power of two of loss_scale / 128 beyond it, so that the int32 range always spans un-scaled gradient sums below 1.0
-        int shift = 0; while (shift < 23 && 128.0f * (float)(1u << shift) < cfg.loss_scale) ++shift;
-        m.lf.fix_scale = 16777216.0f / (float)(1u << shift); m.lf.fix_clamp = 100.0f * (float)(1u << shift);
+// ---- the plan of an object (TrainPlan, model.h): every rule about which chains a shape can run, once.  No HIP calls.
+static uint32_t all_levels_mask(int L) { return (1u << L) - 1u; }          // (L <= kMaxLevels = 16)
+// level-tile encode (kernels_encode.hip), batch size: a workgroup's two tile copies, four barriers and the launch cost the same whatever it walks -- measured
+// (tools/kernel_times.py, both chains, same box):
+// R = 1024 (C1) 48.9 vs 41.3 us per step for the gather chain, R = 2048 75.1 vs 75.4, R = 4096 99 vs 107, R = 8192 166 vs 172.  Option lds_encode = 1
+// (default) takes the tile chain from 3072 rays (98 304 samples) up, 2 always (tests), 0 never.
+static bool level_tiles_pay(long lds_encode, uint32_t Btrain) { return lds_encode != 0 && (lds_encode >= 2 || Btrain >= 98304u); }
+TrainPlan train_plan(const mon_config& cfg, const LevelTable& lt, const NetDims& nd, uint32_t R, uint32_t S, bool lazy_ema, const PlanOptions& opt) {
+    TrainPlan p{}; const uint32_t Btrain = R * S;
+    p.lazy_ema = lazy_ema; p.fused = fused_supported(nd, S, R);
+    p.fused_backend = p.fused && opt.backend != 0;             // option backend: -1 what the shape allows, 0 the layer-at-a-time kernels
+    p.xorwow = rng_stream_mode(cfg.rng_flags) != 0;
+    ScatterLevels sl{}; const uint32_t mask = scatter_plan(lt, nd, sl); const bool all = mask == all_levels_mask(nd.L);
+    // every level must fit two LDS tiles and go through the LDS scatter (option lds_encode = 0: gathers inside k_fused_train)
+    const bool tiles_fit = level_tiles_pay(opt.lds_encode, Btrain) && all && encode_tiles_supported(lt, nd);
+    if (p.fused) {
+        p.lds_mask = mask; p.lds_all = all; p.level_tiles = tiles_fit;
+        // Levels beyond the LDS plan (more than 2^18 entries): binned exact scatter while many samples carry a gradient (kernels_bigscatter.hip).
+        // Option big_switch = gradient-carrying samples below which the global-atomic path takes over (0: atomics always).
+        p.big_scatter = mask && big_scatter_workspace_bytes(lt, nd, mask, Btrain) && opt.big_switch;
+        // chunk flags for the lazy optimizer (tables above 8 M parameters with levels outside the LDS plan); MON_VARIANT_NO_FLAGS: scan the gradient table
+        p.touched_flags = kTouchedFlags && lazy_ema && mask && !all;
+        p.occupancy = cfg.occupancy_skip != 0;
+        // (a position block's 256 samples lie in one sample partition of the encode, and a partition's list fits its spw slots)
+        const uint32_t spw = encode_tiles_spw(Btrain), parts = (Btrain + spw - 1u) / spw, blocks = (Btrain + 255u) / 256u;
+        p.live_lists = p.occupancy && p.level_tiles && Btrain % 256u == 0u && parts <= kLiveMaxParts && ((blocks + parts - 1u) / parts) * 256u <= spw;
+        p.tile_render = !lazy_ema && tile_render_supported(lt, nd);
+    } else {
+        p.layer_ws = (Btrain & 31u) == 0u;
+        // (16 neurons, 2 x 128, three / four hidden layers; tables up to 2^18 entries per level -- see k_rows_to_bins)
+        p.hybrid_scatter = S == 32u && !lazy_ema && all && (R % kDefaultScatterBins) == 0u;
+        // ... and their forward encode from LDS level tiles like the fused chain's (k_encode_tiles; same batch-size rule, option lds_encode)
+        p.level_tiles = p.hybrid_scatter && p.layer_ws && tiles_fit;
     }
-    HIPCHECK(use_device(m.device));
-    std::memcpy(m.oc.Tow.m, Tow, 64);
-    for (int a = 0; a < 3; ++a) { m.oc.aabb.mn[a] = amin[a]; m.oc.aabb.mx[a] = amax[a]; }
-    m.oc.instance_id = (uint32_t)(uint8_t)class_id;                 // nerf.cu:75,158
-    m.oc.R = (uint32_t)cfg.rays_per_batch; m.oc.S = (uint32_t)cfg.n_samples; m.oc.use_depth = cfg.use_depth && ds->use_depth;
-    m.oc.sample_seed = cfg.sample_seed; m.oc.loss_scale = cfg.loss_scale;
-    m.n_bins = kDefaultScatterBins;
-    m.opt = OptimConst{ cfg.beta1, cfg.beta2, cfg.epsilon, cfg.l2_reg, cfg.ema_decay, cfg.loss_scale, cfg.decay_base, std::log2(cfg.beta1),
-            std::log2(cfg.beta2), std::log2(cfg.ema_decay), cfg.decay_start, cfg.decay_interval, m.nd.n_mlp, m.n_params };
-    { const int rcs = stream_acquire(m.device, &m.own_stream); if (rcs) return rcs; }
-    m.train_stream = m.own_stream; m.lanes = lanes_get(m.device); m.lanes->objects.fetch_add(1);
-    // ---- parameters (ResetNetwork :1286-1342; Trainer init)
-    const size_t n = m.n_params;
+    p.inference_side = p.fused_backend && !lazy_ema && !p.xorwow;
+    return p;
+}
+// ---- model_init's pieces, one per group of buffers; each allocates what the plan says
+// parameters (ResetNetwork :1286-1342; Trainer init)
+static int init_parameters(Model& m, bool init_params) {
+    const size_t n = m.n_params; int rc;
     // per-parameter step counters in 16 bits, saturating, where that is EXACT: 1 - beta^t == 1.0f (beta^t < 2^-25) for every t >= 65535 and both betas
     // (variant build MON_VARIANT_STEPS32: always 32 bits).  The device evaluates 1 - exp2f(t * log2(beta)) in fp32; the host test runs in double, so it keeps a
     // margin of four binades (beta^65535 < 2^-29, i.e. beta <= 0.99969) instead of sitting on the rounding boundary.
-    const bool steps16 = steps16_exact(cfg);
-    // lazy EMA: only where the optimizer is not the dense variant anyway and the table is large (> 8 M parameters)
-    m.lazy_ema = m.n_grid > (8u << 20);
+    const bool steps16 = steps16_exact(m.cfg);
     // large tables (lazy EMA, 16-bit step counters): the optimizer state as one 128-byte record per chunk (ParamPtrs::rec) instead of four arrays
-    const bool records = m.lazy_ema && steps16 && kStateRecords && (n & 7u) == 0u;
+    const bool records = m.plan.lazy_ema && steps16 && kStateRecords && (n & 7u) == 0u;
     if (records) { if ((rc = dev_alloc(m, m.P.rec, 4 * n))) return rc; }
     else if ((rc = dev_alloc(m, m.P.master, n, false)) || (rc = dev_alloc(m, m.P.m1, n)) || (rc = dev_alloc(m, m.P.m2, n)) ||
              (rc = steps16 ? dev_alloc(m, m.P.steps16, n + 8) : dev_alloc(m, m.P.steps, n))) return rc;
-    if ((rc = dev_alloc(m, m.P.half, n, false)) || (rc = dev_alloc(m, m.P.ema, n)) || (rc = records ? MON_OK : dev_alloc(m, m.d_ema_step, n / 8 + 1)) ||      // (chunk records keep the EMA step in their pad word: no array, ParamPtrs::lazy says "lazy")
-        
+    // (chunk records keep the EMA step in their pad word: no array, ParamPtrs::lazy says "lazy")
+    if ((rc = dev_alloc(m, m.P.half, n, false)) || (rc = dev_alloc(m, m.P.ema, n)) || (rc = records ? MON_OK : dev_alloc(m, m.d_ema_step, n / 8 + 1)) ||
         (rc = dev_alloc(m, m.P.gmlp, m.nd.n_mlp)) || (rc = dev_alloc(m, m.P.ggrid, m.n_grid))) return rc;
     if (init_params) {
-        std::vector<float> master; init_params_host(cfg, m.nd, m.n_params, master);
+        std::vector<float> master; init_params_host(m.cfg, m.nd, m.n_params, master);
         const int urc = upload_master(m, master.data()); if (urc) return urc;
     }
-    // ---- workspace (AllocateBatchWorkspace :1344-1427), sized for max(train batch, render chunk)
-    const uint32_t R = m.oc.R, S = m.oc.S;
+    return MON_OK;
+}
+// a candidate set of R rays; the rays of a batch or render pass
+static int alloc_candidates(Model& m, BatchPtrs& b) {
+    const size_t R = m.oc.R; int rc;
+    if ((rc = dev_alloc(m, b.cand_o, 3 * R)) || (rc = dev_alloc(m, b.cand_d, 3 * R)) || (rc = dev_alloc(m, b.cand_dn, R)) || (rc = dev_alloc(m, b.cand_t0, R)) ||
+        (rc = dev_alloc(m, b.cand_t1, R)) || (rc = dev_alloc(m, b.cand_depth, R)) || (rc = dev_alloc(m, b.cand_rgba, R))) return rc;
+    return dev_alloc(m, b.mask, (R + 63) / 64 + 64);
+}
+static int alloc_rays(Model& m, BatchPtrs& b, size_t n) {
+    int rc; if ((rc = dev_alloc(m, b.ray_o, 3 * n)) || (rc = dev_alloc(m, b.ray_d, 3 * n)) || (rc = dev_alloc(m, b.ray_dn, n)) || (rc = dev_alloc(m, b.ray_t0, n)) ||
+        (rc = dev_alloc(m, b.ray_t1, n))) return rc;
+    return dev_alloc(m, b.ray_flag, n);
+}
+// batch workspace (AllocateBatchWorkspace :1344-1427), sized for max(train batch, render chunk)
+static int init_batch_workspace(Model& m) {
+    const uint32_t R = m.oc.R, S = m.oc.S; int rc;
     m.ws_rays = R > kRenderChunkRays ? R : kRenderChunkRays;
     // the layer-at-a-time buffers (pts, tdist, E, O) serve a render pass of the unfused backend; an object whose inference runs on the fused kernels / level
     // tiles only needs them at the training batch's size (64 + 12 + 8 + 4 MB less per base.json object: a render of the unfused backend then takes passes of
     // ws_samples / 2S rays)
-    const bool fused_inference = fused_supported(m.nd, S, R) && options().backend != 0;
-    const uint32_t Btrain = R * S, Brender = fused_inference ? Btrain : kRenderChunkRays * 2 * S;
+    const uint32_t Btrain = R * S, Brender = m.plan.fused_backend ? Btrain : kRenderChunkRays * 2 * S;
     m.ws_samples = Btrain > Brender ? Btrain : Brender;
     BatchPtrs& B = m.B;
-    if ((rc = dev_alloc(m, B.cand_o, 3 * (size_t)R)) || (rc = dev_alloc(m, B.cand_d, 3 * (size_t)R)) || (rc = dev_alloc(m, B.cand_dn, R)) ||
-        (rc = dev_alloc(m, B.cand_t0, R)) || (rc = dev_alloc(m, B.cand_t1, R)) || (rc = dev_alloc(m, B.cand_depth, R)) ||
-        (rc = dev_alloc(m, B.cand_rgba, R)) || (rc = dev_alloc(m, B.mask, (R + 63) / 64 + 64)) ||
-        (rc = dev_alloc(m, B.ray_o, 3 * (size_t)m.ws_rays)) || (rc = dev_alloc(m, B.ray_d, 3 * (size_t)m.ws_rays))
-                || (rc = dev_alloc(m, B.ray_dn, m.ws_rays)) ||
-        (rc = dev_alloc(m, B.ray_t0, m.ws_rays)) || (rc = dev_alloc(m, B.ray_t1, m.ws_rays)) || (rc = dev_alloc(m, B.target, 3 * (size_t)R)) ||
-        (rc = dev_alloc(m, B.target_depth, R)) || (rc = dev_alloc(m, B.bgcol, 3 * (size_t)R)) || (rc = dev_alloc(m, B.ray_flag, m.ws_rays)) ||
+    if ((rc = alloc_candidates(m, B)) || (rc = alloc_rays(m, B, m.ws_rays)) || (rc = dev_alloc(m, B.target, 3 * (size_t)R)) ||
+        (rc = dev_alloc(m, B.target_depth, R)) || (rc = dev_alloc(m, B.bgcol, 3 * (size_t)R)) ||
         (rc = dev_alloc(m, B.pts, 3 * (size_t)m.ws_samples)) || (rc = dev_alloc(m, B.tdist, m.ws_samples)) ||
         (rc = dev_alloc(m, B.E, (size_t)m.ws_samples * m.nd.Epad)) || (rc = dev_alloc(m, B.O, (size_t)m.ws_samples * kOut)) ||
         (rc = dev_alloc(m, B.Hid, (size_t)Btrain * m.nd.W * m.nd.NH)) || (rc = dev_alloc(m, B.dO, (size_t)Btrain * kOut)) ||
@@ -555,131 +428,127 @@ static int model_init(Model& m, Dataset* ds, const mon_config& cfg, int class_id
                 || (rc = dev_alloc(m, B.loss_ray, R)) ||
         (rc = dev_alloc(m, m.d_state, 2)) || (rc = dev_alloc(m, m.d_dw_partials, (size_t)(fused_partial_cols(m.nd) + 64) * kMaxFusedGrid)) ||
         (rc = dev_alloc(m, m.d_out_all, 5 * (size_t)kRenderChunkRays))) return rc;
-    m.out_cap = kRenderChunkRays;
-    if (rng_stream_mode(cfg.rng_flags)) {          // "same inputs" mode: the reference's XORWOW stream (xorwow.h) instead of the counter RNG
-        m.xw_lanes = rng_xorwow_lanes(cfg.rng_flags); m.xw_flavour = rng_stream_mode(cfg.rng_flags) == 2 ? kXorwowRocrand : kXorwowCurand;
-        std::vector<XorwowState> st; xorwow_lane_states(0ull /* the generator's default seed: nerf_model.cu never sets one */, m.xw_flavour, m.xw_lanes, st);
-        XorwowState *d_a = nullptr, *d_b = nullptr, *d_c = nullptr;
-        if ((rc = dev_alloc(m, d_a, m.xw_lanes, false)) || (rc = dev_alloc(m, d_b, m.xw_lanes, false)) || (rc = dev_alloc(m, d_c, m.xw_lanes, false)) ||
-            (rc = dev_alloc(m, m.d_xw, 2 * (size_t)(5 + S) * R))) return rc;
-        HIPCHECK(hipMemcpy(d_a, st.data(), sizeof(XorwowState) * m.xw_lanes, hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(d_c, st.data(), sizeof(XorwowState) * m.xw_lanes, hipMemcpyHostToDevice));
-        m.d_xw_states = d_a; m.d_xw_render_states = d_b; m.d_xw_render_init = d_c;
-        m.oc.xw[0] = m.d_xw; m.oc.xw[1] = m.d_xw + (size_t)(5 + S) * R;
+    m.out_cap = kRenderChunkRays; return MON_OK;
+}
+// "same inputs" mode: the reference's XORWOW stream (xorwow.h) instead of the counter RNG
+static int init_xorwow(Model& m) {
+    const uint32_t R = m.oc.R, S = m.oc.S; int rc;
+    m.xw_lanes = rng_xorwow_lanes(m.cfg.rng_flags); m.xw_flavour = rng_stream_mode(m.cfg.rng_flags) == 2 ? kXorwowRocrand : kXorwowCurand;
+    std::vector<XorwowState> st; xorwow_lane_states(0ull /* the generator's default seed: nerf_model.cu never sets one */, m.xw_flavour, m.xw_lanes, st);
+    XorwowState *d_a = nullptr, *d_b = nullptr, *d_c = nullptr;
+    if ((rc = dev_alloc(m, d_a, m.xw_lanes, false)) || (rc = dev_alloc(m, d_b, m.xw_lanes, false)) || (rc = dev_alloc(m, d_c, m.xw_lanes, false)) ||
+        (rc = dev_alloc(m, m.d_xw, 2 * (size_t)(5 + S) * R))) return rc;
+    HIPCHECK(hipMemcpy(d_a, st.data(), sizeof(XorwowState) * m.xw_lanes, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(d_c, st.data(), sizeof(XorwowState) * m.xw_lanes, hipMemcpyHostToDevice));
+    m.d_xw_states = d_a; m.d_xw_render_states = d_b; m.d_xw_render_init = d_c;
+    m.oc.xw[0] = m.d_xw; m.oc.xw[1] = m.d_xw + (size_t)(5 + S) * R; return MON_OK;
+}
+// k_grid_scatter's plan, hand-over buffers and partial tables for the levels of `mask` (a prefix: the fused chain's, or every level for the hybrid scatter)
+static int alloc_lds_scatter(Model& m, uint32_t mask) {
+    const size_t Btrain = (size_t)m.oc.R * m.oc.S; int rc;
+    (void)scatter_plan(m.lt, m.nd, m.scatter);
+    // a partial table spans the entries up to the end of the LAST LDS-scattered level (the plan covers a prefix of the levels: sizes grow with the level);
+    // sized by the whole table it was 16 x 211 MB = 3.4 GB of a T = 2^22 object for the 37 k entries of its two small levels
+    int last = -1; for (int l = 0; l < m.nd.L; ++l) if ((mask >> l) & 1u) last = l;
+    m.part_halves = last < 0 ? 0u : ((2u * m.lt.offset[last + 1] + 15u) & ~15u);
+    if (mask && ((rc = dev_alloc(m, m.d_de_soa, (size_t)m.nd.L * Btrain * 2)) || (rc = dev_alloc(m, m.d_x_soa, 4 * Btrain)))) return rc;
+    return mask ? dev_alloc(m, m.d_gpart, (size_t)m.scatter.max_P * m.part_halves) : MON_OK;
+}
+// level-tile encode: positions, encoded features, the fp16 grid in tile order
+static int alloc_level_tiles(Model& m) {
+    const size_t Btrain = (size_t)m.oc.R * m.oc.S; int rc;
+    if ((rc = dev_alloc(m, m.d_x_all, 4 * Btrain)) || (rc = dev_alloc(m, m.d_e_soa, (size_t)m.nd.L * Btrain * 2))
+            || (rc = dev_alloc(m, m.d_half_tiles, (size_t)m.n_grid + 64))) return rc;
+    encode_tiles_setup_device(); return MON_OK;
+}
+// fused-chain buffers
+static int init_fused_buffers(Model& m) {
+    const TrainPlan& p = m.plan; const uint32_t R = m.oc.R, Btrain = R * m.oc.S; int rc;
+    if ((rc = dev_alloc(m, m.d_frag_train, 64 * 512)) || (rc = dev_alloc(m, m.d_frag_render, 64 * 512))) return rc;       // <= 30 fragments of 512 halves
+    if ((rc = alloc_lds_scatter(m, p.lds_mask))) return rc;
+    if (p.big_scatter && (rc = dev_alloc(m, m.d_big_ws, big_scatter_workspace_bytes(m.lt, m.nd, p.lds_mask, Btrain)))) return rc;
+    if (p.level_tiles) {
+        if ((rc = dev_alloc(m, m.B.ray_rec, 12 * (size_t)R))) return rc;
+        m.B_alt = m.B;                             // (the second candidate set: cand_* / mask of its own, everything else shared)
+        if ((rc = alloc_candidates(m, m.B_alt)) || (rc = alloc_level_tiles(m))) return rc;
     }
-    if (fused_supported(m.nd, S, m.oc.R)) {
-        if ((rc = dev_alloc(m, m.d_frag_train, 64 * 512)) || (rc = dev_alloc(m, m.d_frag_render, 64 * 512))) return rc;       // <= 30 fragments of 512 halves
-        m.lds_mask = scatter_plan(m.lt, m.nd, m.scatter);
-        // a partial table spans the entries up to the end of the LAST LDS-scattered level (the plan covers a prefix of the levels: sizes grow with the level);
-        // sized by the whole table it was 16 x 211 MB = 3.4 GB of a T = 2^22 object for the 37 k entries of its two small levels
-        {
-            int last = -1; for (int l = 0; l < m.nd.L; ++l) if ((m.lds_mask >> l) & 1u) last = l;
-            m.part_halves = last < 0 ? 0u : ((2u * m.lt.offset[last + 1] + 15u) & ~15u);
-        }
-        if (m.lds_mask && ((rc = dev_alloc(m, m.d_de_soa, (size_t)m.nd.L * Btrain * 2)) || (rc = dev_alloc(m, m.d_x_soa, 4 * (size_t)Btrain)) ||
-                           (rc = dev_alloc(m, m.d_gpart, (size_t)m.scatter.max_P * m.part_halves)))) return rc;
-        // Levels beyond the LDS plan (more than 2^18 entries): binned exact scatter while many samples carry a gradient (kernels_bigscatter.hip).
-        // MON_BIG_SWITCH = gradient-carrying samples below which the global-atomic path takes over (0: atomics always).
-        const size_t big_bytes = m.lds_mask ? big_scatter_workspace_bytes(m.lt, m.nd, m.lds_mask, Btrain) : 0;
-        const uint32_t big_switch = (uint32_t)options().big_switch;
-        if (big_bytes && big_switch) { if ((rc = dev_alloc(m, m.d_big_ws, big_bytes))) return rc; m.big_switch = big_switch; }
-        // level-tile encode (kernels_encode.hip): every level must fit two LDS tiles and go through the LDS scatter (option lds_encode = 0: gathers inside
-        // k_fused_train)
-        // Batch size: a workgroup's two tile copies, four barriers and the launch cost the same whatever it walks -- measured (tools/kernel_times.py, both
-        // chains, same box):
-        // R = 1024 (C1) 48.9 vs 41.3 us per step for the gather chain, R = 2048 75.1 vs 75.4, R = 4096 99 vs 107, R = 8192 166 vs 172.  Option lds_encode = 1
-        // (default) takes the tile chain from 3072 rays (98 304 samples) up, 2 always (tests), 0 never.
-        const bool tiles_pay = options().lds_encode >= 2 || Btrain >= 98304u;
-        if (options().lds_encode && tiles_pay && m.lds_mask == ((1u << m.nd.L) - 1u) && encode_tiles_supported(m.lt, m.nd)) {
-            if ((rc = dev_alloc(m, B.ray_rec, 12 * (size_t)R))) return rc;
-            m.B_alt = B;                             // (cand_* / mask replaced below, after the workspace pointers are final)
-            if ((rc = dev_alloc(m, m.B_alt.cand_o, 3 * (size_t)R)) || (rc = dev_alloc(m, m.B_alt.cand_d, 3 * (size_t)R))
-                    || (rc = dev_alloc(m, m.B_alt.cand_dn, R)) ||
-                (rc = dev_alloc(m, m.B_alt.cand_t0, R)) || (rc = dev_alloc(m, m.B_alt.cand_t1, R)) || (rc = dev_alloc(m, m.B_alt.cand_depth, R)) ||
-                (rc = dev_alloc(m, m.B_alt.cand_rgba, R)) || (rc = dev_alloc(m, m.B_alt.mask, (R + 63) / 64 + 64))) return rc;
-            if ((rc = dev_alloc(m, m.d_x_all, 4 * (size_t)Btrain)) || (rc = dev_alloc(m, m.d_e_soa, (size_t)m.nd.L * Btrain * 2))
-                    || (rc = dev_alloc(m, m.d_half_tiles, (size_t)m.n_grid + 64))) return rc;
-            encode_tiles_setup_device();
-        }
-        // chunk flags for the lazy optimizer (tables above 8 M parameters with levels outside the LDS plan); MON_TOUCHED_FLAGS=0: scan the gradient table
-        const bool flags_on = kTouchedFlags;
-        if (flags_on && m.lazy_ema && m.lds_mask && m.lds_mask != ((m.nd.L >= 32) ? 0xffffffffu : ((1u << m.nd.L) - 1u))
-                && (rc = dev_alloc(m, m.d_touched, (m.n_params >> 3) + 16))) return rc;
-    }
-    if (!fused_supported(m.nd, S, m.oc.R) && (Btrain & 31u) == 0u) {
-        // shapes outside the fused kernels: the T-layout workspace of the MFMA layer kernels (kernels_layers.hip); without it kernels_net.hip's one-sample-per-
-        // thread kernels run
-        // (zeroed: k_wgrad_reduce sums whole partial rows, and the entries no job writes -- rows 4..15 of the padded output layer -- must not be whatever the
-        // allocation held before: they reach the pad weights' Adam state, and two identical objects then differ in get_params)
-        if ((rc = dev_alloc(m, m.d_layers_T, layers_workspace_halves(m.nd, Btrain)))) return rc;
-    }
-    if (fused_supported(m.nd, S, m.oc.R)) { }
-    else if (S == 32u && !m.lazy_ema) {
-        // Shapes the fused kernels do not take (16 neurons, 2 x 128, three / four hidden layers): the layer-at-a-time kernels, but their grid backward through
-        // k_grid_scatter when the plan covers every level (tables up to 2^18 entries per level) -- see k_rows_to_bins
-        ScatterLevels plan{}; const uint32_t mask = scatter_plan(m.lt, m.nd, plan);
-        if (mask == ((1u << m.nd.L) - 1u) && (R % kDefaultScatterBins) == 0u) {
-            m.scatter = plan; m.part_halves = (2u * m.lt.offset[m.nd.L] + 15u) & ~15u;
-            if ((rc = dev_alloc(m, m.d_de_soa, (size_t)m.nd.L * Btrain * 2)) || (rc = dev_alloc(m, m.d_x_soa, 4 * (size_t)Btrain)) ||
-                (rc = dev_alloc(m, m.d_gpart, (size_t)m.scatter.max_P * m.part_halves))) return rc;
-            m.hybrid_scatter = true;
-            // ... and their forward encode from LDS level tiles like the fused chain's (k_encode_tiles; same batch-size rule, option lds_encode)
-            const bool tiles_pay_b0 = options().lds_encode >= 2 || Btrain >= 98304u;
-            if (m.d_layers_T && options().lds_encode && tiles_pay_b0 && encode_tiles_supported(m.lt, m.nd)) {
-                if ((rc = dev_alloc(m, m.d_x_all, 4 * (size_t)Btrain)) || (rc = dev_alloc(m, m.d_e_soa, (size_t)m.nd.L * Btrain * 2))
-                        || (rc = dev_alloc(m, m.d_half_tiles, (size_t)m.n_grid + 64))) return rc;
-                encode_tiles_setup_device();
-            }
-        }
-    }
-    if (cfg.occupancy_skip && fused_supported(m.nd, S, m.oc.R)) {
-        constexpr size_t words = (size_t)kOccRes * kOccRes * kOccRes / 32;
-        if ((rc = dev_alloc(m, m.d_occ, words, false)) || (rc = dev_alloc(m, m.d_occ_tmp, words, false))
-                || (rc = dev_alloc(m, m.d_frag_occ, 64 * 512))) return rc;
-        HIPCHECK(hipMemset(m.d_occ, 0xff, words * 4));                       // warm-up: every cell counts as occupied
-        // a cell is empty when one sample interval through it would be transparent: alpha = 1 - exp(-sigma * dt) < 1e-3 with dt = box diagonal / samples
-        float diag2 = 0.f; for (int a = 0; a < 3; ++a) diag2 += (amax[a] - amin[a]) * (amax[a] - amin[a]);
-        const float dt = std::sqrt(diag2) / (float)S;
-        m.occ_raw_threshold = std::log(1e-3f / std::max(dt, 1e-6f));
-        // the level-tile chain with the grid in use: live-sample lists for k_encode_tiles (LiveArgs, model.h) -- a position block's 256 samples must lie in
-        // one of the encode's sample partitions
-        // (a list holds at most ceil(blocks / n_parts) * 256 entries: it must fit the partition's spw slots)
-        const uint32_t spw_l = encode_tiles_spw(Btrain), parts_l = (Btrain + spw_l - 1u) / spw_l, blocks_l = (Btrain + 255u) / 256u;
-        if (m.d_e_soa && Btrain % 256u == 0u && parts_l <= kLiveMaxParts && ((blocks_l + parts_l - 1u) / parts_l) * 256u <= spw_l) {
-            if ((rc = dev_alloc(m, m.d_live_idx, Btrain)) || (rc = dev_alloc(m, m.d_live_cnt, 2u * kLiveMaxParts * kLiveCntStride))) return rc;
-        }
-    }
-    m.boxes_cap = 1024;
-    if ((rc = dev_alloc(m, m.d_boxes, m.boxes_cap))) return rc;
-    B.boxes = m.d_boxes; m.B_alt.boxes = m.d_boxes;
+    return p.touched_flags ? dev_alloc(m, m.d_touched, (m.n_params >> 3) + 16) : MON_OK;
+}
+// layer-chain buffers (shapes outside the fused kernels)
+static int init_layer_buffers(Model& m) {
+    const TrainPlan& p = m.plan; int rc;
+    // (zeroed: k_wgrad_reduce sums whole partial rows, and the entries no job writes -- rows 4..15 of the padded output layer -- must not be whatever the
+    // allocation held before: they reach the pad weights' Adam state, and two identical objects then differ in get_params)
+    if (p.layer_ws && (rc = dev_alloc(m, m.d_layers_T, layers_workspace_halves(m.nd, m.oc.R * m.oc.S)))) return rc;
+    if (p.hybrid_scatter && (rc = alloc_lds_scatter(m, all_levels_mask(m.nd.L)))) return rc;
+    if (p.level_tiles && (rc = alloc_level_tiles(m))) return rc;
+    return MON_OK;
+}
+// occupancy grid (cfg.occupancy_skip) and the live-sample lists of the level-tile chain
+static int init_occupancy(Model& m) {
+    constexpr size_t words = (size_t)kOccRes * kOccRes * kOccRes / 32; int rc;
+    if ((rc = dev_alloc(m, m.d_occ, words, false)) || (rc = dev_alloc(m, m.d_occ_tmp, words, false))
+            || (rc = dev_alloc(m, m.d_frag_occ, 64 * 512))) return rc;
+    HIPCHECK(hipMemset(m.d_occ, 0xff, words * 4));                       // warm-up: every cell counts as occupied
+    // a cell is empty when one sample interval through it would be transparent: alpha = 1 - exp(-sigma * dt) < 1e-3 with dt = box diagonal / samples
+    float diag2 = 0.f; for (int a = 0; a < 3; ++a) diag2 += (m.oc.aabb.mx[a] - m.oc.aabb.mn[a]) * (m.oc.aabb.mx[a] - m.oc.aabb.mn[a]);
+    const float dt = std::sqrt(diag2) / (float)m.oc.S;
+    m.occ_raw_threshold = std::log(1e-3f / std::max(dt, 1e-6f));
+    if (m.plan.live_lists && ((rc = dev_alloc(m, m.d_live_idx, m.oc.R * m.oc.S)) || (rc = dev_alloc(m, m.d_live_cnt, 2u * kLiveMaxParts * kLiveCntStride))))
+        return rc;
+    return MON_OK;
+}
+// inference side: the published snapshots and a render workspace of their own (InferState, model_internal.h)
+static int init_inference_side(Model& m) {
+    InferState* is = new InferState(); m.infer = is; int rc;
+    // (a whole frame fits: no growth in front of a viewer)
+    if ((rc = infer_shared_get(m.device, (size_t)m.ds->K.W * (size_t)m.ds->K.H, &is->shared))) return rc;
+    for (int k = 0; k < 2; ++k) { if ((rc = dev_alloc(m, is->snap[k], m.n_params, false))) return rc;
+        HIPCHECK(hipEventCreateWithFlags(&is->ready[k], hipEventDisableTiming)); }
+    is->rb = m.B;
+    if ((rc = alloc_rays(m, is->rb, kRenderChunkRays)) || (rc = dev_alloc(m, is->out_all, 5 * (size_t)kRenderChunkRays)) ||
+        (rc = dev_alloc(m, is->frag, 64 * 512))) return rc;
+    is->out_cap = kRenderChunkRays; return MON_OK;
+}
+static int model_init(Model& m, Dataset* ds, const mon_config& cfg, int class_id, const float* Tow, const float* amin, const float* amax, bool init_params) {
+    m.ds = ds; m.cfg = cfg; m.device = ds->device;
+    int rc = level_table_build(cfg, m.lt, m.nd, m.n_grid); if (rc) return rc;
+    m.n_params = m.nd.n_mlp + m.n_grid;
+    level_fast_build(m.lt, m.nd, m.lf);
+    HIPCHECK(use_device(m.device));
+    // fixed-point unit of the exact LDS gradient accumulation: 2^-24 (every fp16 value is a multiple of it) up to the reference's loss scale of
+    // 128, coarser by the next power of two of loss_scale / 128 beyond it, so that the int32 range always spans un-scaled gradient sums below 1.0
+    int shift = 0; while (shift < 23 && 128.0f * (float)(1u << shift) < cfg.loss_scale) ++shift;
+    m.lf.fix_scale = 16777216.0f / (float)(1u << shift); m.lf.fix_clamp = 100.0f * (float)(1u << shift);
+    std::memcpy(m.oc.Tow.m, Tow, 64);
+    for (int a = 0; a < 3; ++a) { m.oc.aabb.mn[a] = amin[a]; m.oc.aabb.mx[a] = amax[a]; }
+    m.oc.instance_id = (uint32_t)(uint8_t)class_id;                 // nerf.cu:75,158
+    m.oc.R = (uint32_t)cfg.rays_per_batch; m.oc.S = (uint32_t)cfg.n_samples; m.oc.use_depth = cfg.use_depth && m.ds->use_depth;
+    m.oc.sample_seed = cfg.sample_seed; m.oc.loss_scale = cfg.loss_scale;
+    m.n_bins = kDefaultScatterBins;
+    m.opt = OptimConst{ cfg.beta1, cfg.beta2, cfg.epsilon, cfg.l2_reg, cfg.ema_decay, cfg.loss_scale, cfg.decay_base, std::log2(cfg.beta1),
+            std::log2(cfg.beta2), std::log2(cfg.ema_decay), cfg.decay_start, cfg.decay_interval, m.nd.n_mlp, m.n_params };
+    // lazy EMA: only where the optimizer is not the dense variant anyway and the table is large (> 8 M parameters)
+    const PlanOptions opt{ options().backend, options().lds_encode, (uint32_t)options().big_switch };
+    m.plan = train_plan(cfg, m.lt, m.nd, m.oc.R, m.oc.S, m.n_grid > (8u << 20), opt);
+    const TrainPlan& p = m.plan;
+    if (p.big_scatter) m.big_switch = opt.big_switch;
+    { const int rcs = stream_acquire(m.device, &m.own_stream); if (rcs) return rcs; }
+    m.train_stream = m.own_stream; m.lanes = lanes_get(m.device); lanes_objects_add(m.lanes, 1);
+    if ((rc = init_parameters(m, init_params)) || (rc = init_batch_workspace(m)) || (p.xorwow && (rc = init_xorwow(m))) ||
+        (rc = p.fused ? init_fused_buffers(m) : init_layer_buffers(m)) || (p.occupancy && (rc = init_occupancy(m)))) return rc;
+    m.boxes_cap = 1024; if ((rc = dev_alloc(m, m.d_boxes, m.boxes_cap))) return rc;
+    m.B.boxes = m.d_boxes; m.B_alt.boxes = m.d_boxes;
     m.h_state = DevState{}; m.h_state.lr = cfg.learning_rate;
     m.h_state.ema_deb_old = 0.0f; m.h_state.ema_deb_new = 1.0f / (1.0f - (float)std::pow((double)cfg.ema_decay, 1.0));   // step 1
     m.d_state_next = m.d_state + 1;                          // two states: iteration i runs on one, k_optimizer(i) writes the other for iteration i + 1
     HIPCHECK(hipMemcpy(m.d_state, &m.h_state, sizeof(DevState), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(m.d_state_next, &m.h_state, sizeof(DevState), hipMemcpyHostToDevice));
     HIPCHECK(hipHostMalloc((void**)&m.h_state_pinned, sizeof(DevState), hipHostMallocDefault));
-    m.backend = fused_supported(m.nd, S, m.oc.R) ? 1 : 0;
-    if (options().backend >= 0) m.backend = options().backend ? (fused_supported(m.nd, S, m.oc.R) ? 1 : 0) : 0;
-    m.mesh = mesh_state_create(m.device);
-    m.tile_ok = fused_supported(m.nd, S, m.oc.R) && !m.lazy_ema && tile_render_supported(m.lt, m.nd);
-    m.weights_epoch = next_weights_epoch();
-    if (m.tile_ok) { tile_ws_object_born(m.device); m.tile_counted = true; }
-    // (the XORWOW mode renders on the train stream: one generator per Render, like the reference; tables above 8 M parameters keep their EMA lazily and would
-    // cost 2 x 200 MB of snapshots: they render on the train stream)
-    if (m.backend == 1 && !m.lazy_ema && !m.d_xw) {
-        InferState* is = new InferState(); m.infer = is;
-        // (a whole frame fits: no growth in front of a viewer)
-        if ((rc = infer_shared_get(m.device, (size_t)ds->K.W * (size_t)ds->K.H, &is->shared))) return rc;
-        for (int k = 0; k < 2; ++k) { if ((rc = dev_alloc(m, is->snap[k], n, false))) return rc;
-            HIPCHECK(hipEventCreateWithFlags(&is->ready[k], hipEventDisableTiming)); }
-        is->rb = m.B;
-        if ((rc = dev_alloc(m, is->rb.ray_o, 3 * (size_t)kRenderChunkRays)) || (rc = dev_alloc(m, is->rb.ray_d, 3 * (size_t)kRenderChunkRays))
-                || (rc = dev_alloc(m, is->rb.ray_dn, kRenderChunkRays)) ||
-            (rc = dev_alloc(m, is->rb.ray_t0, kRenderChunkRays)) || (rc = dev_alloc(m, is->rb.ray_t1, kRenderChunkRays))
-                    || (rc = dev_alloc(m, is->rb.ray_flag, kRenderChunkRays)) ||
-            (rc = dev_alloc(m, is->out_all, 5 * (size_t)kRenderChunkRays)) || (rc = dev_alloc(m, is->frag, 64 * 512))) return rc;
-        is->out_cap = kRenderChunkRays;
-    }
+    m.backend = p.fused_backend ? 1 : 0;
+    m.mesh = mesh_state_create(m.device); m.weights_epoch = next_weights_epoch();
+    if (p.tile_render) { tile_ws_object_born(m.device); m.tile_counted = true; }
+    if (p.inference_side && (rc = init_inference_side(m))) return rc;
     // what this object's creation enqueued: the fills of its allocations (null stream) and its own stream's kernels.  NOT the device: with other objects'
     // training threads running, a device-wide wait stands behind everything they have queued -- a whole Train_Step of 500 iterations each in the offline
     // manager (CreateNeRF of the 8th object of a job took 125-140 ms, 9-23 ms with an idle device; eight objects 0.71-0.80 s -> 0.28-0.32 s of the caller's
@@ -712,19 +581,6 @@ int publish_snapshot(Model& m, bool force) {
     return MON_OK;
 }
 
-// (model_load runs a file's config through the same checks)
-int config_check(const mon_config& cfg) {
-    if (cfg.rays_per_batch < 64 || (cfg.rays_per_batch % 64) != 0 || cfg.n_samples < 1 || cfg.n_samples > 64) {
-        set_error("rays_per_batch must be a multiple of 64, n_samples 1..64"); return MON_ERR_ARG; }
-    if ((cfg.rng_flags & 3u) == 3u || (cfg.rng_flags & ~0xffff0013u) != 0u || (cfg.rng_flags >> 16) > 1024u) {
-        set_error("rng_flags: bits 0-1 = 0 (counter RNG) | 1 (XORWOW, cuRAND flavour) | 2 (XORWOW, rocRAND flavour), bit 4 = tcnn init order, "
-                  "bits 16-31 = XORWOW lanes / 1024 (at most 1024)");
-        return MON_ERR_ARG;
-    }
-    if (!(cfg.loss_scale > 0.f) || !(cfg.loss_scale <= 65536.f)) { set_error("loss_scale must be in (0, 65536] (fp16 gradients; the reference uses 128)");
-        return MON_ERR_ARG; }
-    return MON_OK;
-}
 int model_create_impl(Dataset* ds, const mon_config& cfg, int class_id, const float* Tow, const float* amin, const float* amax, bool init_params, Model** out) {
     if (!ds || !Tow || !amin || !amax) { set_error("object_create: bad argument"); return MON_ERR_ARG; }
     { const int rc = config_check(cfg); if (rc) return rc; }
@@ -737,9 +593,6 @@ int model_create(Dataset* ds, const mon_config& cfg, int class_id, const float* 
     return model_create_impl(ds, cfg, class_id, Tow, amin, amax, true, out);
 }
 
-static void drop_graph(Model& m) { if (m.graph_exec) { hipGraphExecDestroy(m.graph_exec); m.graph_exec = nullptr; m.graph_backend = -1; } }
-
-void model_mesh_free(Model& m);
 int model_destroy(Model* mp) {
     if (!mp) return MON_OK;
     Model& m = *mp; use_device(m.device);
@@ -762,7 +615,7 @@ int model_destroy(Model* mp) {
     if (m.h_state_pinned) hipHostFree(m.h_state_pinned);
     if (m.h_out) (void)hipHostFree(m.h_out);
     if (m.rskip.h_stats) (void)hipHostFree(m.rskip.h_stats);
-    if (m.lanes) m.lanes->objects.fetch_sub(1);
+    if (m.lanes) lanes_objects_add(m.lanes, -1);
     if (m.switch_event) hipEventDestroy(m.switch_event);
     if (m.sync_event) hipEventDestroy(m.sync_event);
     if (m.own_stream) { hipStreamSynchronize(m.own_stream); stream_release(m.device, m.own_stream); }        // idle: the next object of this device takes it
@@ -786,11 +639,12 @@ int model_add_boxes(Model& m, const mon_frame_bbox* boxes, size_t n) {
         }
     }
     model_leave_lane(m); HIPCHECK(hipStreamSynchronize(m.train_stream));
+    bool moved = false;
     if (m.n_boxes + n > m.boxes_cap) {
         uint32_t cap = m.boxes_cap; while (cap < m.n_boxes + n) cap *= 2;
         mon_frame_bbox* nb = nullptr; int rc = dev_alloc(m, nb, cap); if (rc) return rc;
         HIPCHECK(hipMemcpy(nb, m.d_boxes, sizeof(mon_frame_bbox) * m.n_boxes, hipMemcpyDeviceToDevice));
-        m.d_boxes = nb; m.B.boxes = nb; m.B_alt.boxes = nb; m.boxes_cap = cap; drop_graph(m);       // old buffer stays in allocs until destroy
+        m.d_boxes = nb; m.B.boxes = nb; m.B_alt.boxes = nb; m.boxes_cap = cap; moved = true;       // old buffer stays in allocs until destroy
     }
     HIPCHECK(hipMemcpy(m.d_boxes + m.n_boxes, boxes, sizeof(mon_frame_bbox) * n, hipMemcpyHostToDevice));   // nerf_model.cu:1625
     m.n_boxes += (uint32_t)n;
@@ -799,7 +653,7 @@ int model_add_boxes(Model& m, const mon_frame_bbox* boxes, size_t n) {
     // (the copies above ran on the null stream, which the object's non-blocking streams do not wait for: a grown box list's zero-fill and device-to-device copy
     // are done before the next batch reads it)
     HIPCHECK(hipStreamSynchronize(nullptr));
-    m.next_ready = false;                                   // candidates pre-generated for the next iteration used the old box list
+    model_mark_stale(m, kStaleRays, moved);                 // candidates pre-generated for the next iteration used the old box list; a captured pair its address
     return MON_OK;
 }
 
@@ -824,13 +678,10 @@ struct Roctx {
 static Roctx* roctx() { if (!options().roctx) return nullptr; static Roctx r; return r.push ? &r : nullptr; }
 static const char* const kPhaseName[MON_K_COUNT] = { "mon.batch (GenerateBatch)", "mon.fwd_bwd (k_fused_train)", "mon.optimizer (k_optimizer)", "mon.render",
         "mon.scatter (k_grid_scatter)", "mon.reduce_partials", "mon.encode (k_encode_tiles)", "mon.points (k_sample_points)" };
-struct ProfScope {
-    Model& m; int cls; hipEvent_t a = nullptr, b = nullptr; Roctx* rx;
-    ProfScope(Model& mm, int c) : m(mm), cls(c), rx(roctx()) { if (rx) rx->push(kPhaseName[c]); if (m.profiling) { a = get_event(m); b = get_event(m);
-            hipEventRecord(a, m.train_stream); } }
-    ~ProfScope() { if (m.profiling) { hipEventRecord(b, m.train_stream); m.ev_pending.push_back({ cls, { a, b } }); } if (rx) rx->pop(); }
-};
-static void collect_profile(Model& m) {
+ProfScope::ProfScope(Model& mm, int c) : m(mm), cls(c), rx(roctx()) { if (rx) rx->push(kPhaseName[c]); if (m.profiling) { a = get_event(m); b = get_event(m);
+        hipEventRecord(a, m.train_stream); } }
+ProfScope::~ProfScope() { if (m.profiling) { hipEventRecord(b, m.train_stream); m.ev_pending.push_back({ cls, { a, b } }); } if (rx) rx->pop(); }
+void collect_profile(Model& m) {
     for (auto& p : m.ev_pending) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, p.second.first, p.second.second) == hipSuccess) { m.prof.ms[p.first] += ms; m.prof.launches[p.first] += 1; }
@@ -845,304 +696,6 @@ void mlp_forward_inference(Model& m, hipStream_t s, const uint16_t* params, cons
     if (body && launch_mlp_forward_layers(s, m.nd, params, E, nullptr, O, body, nullptr, nullptr)) done = body;
     if (done < n) launch_mlp_forward(s, m.nd, params, E + (size_t)done * m.nd.Epad, nullptr, O + (size_t)done * kOut, n - done, nullptr);
 }
-
-// occupancy-grid skipping on the level-tile chain: what the position pass, k_encode_tiles and k_fused_train<PRE, OCC> share once the grid is in use
-static LiveArgs live_args(const Model& m) {
-    if (!(m.d_occ && m.occ_refreshed_iter && m.d_live_idx)) return LiveArgs{};
-    const uint32_t B = m.oc.R * m.oc.S, spw = encode_tiles_spw(B);
-    return LiveArgs{ m.d_occ, m.d_live_idx, m.d_live_cnt, spw, (B + spw - 1u) / spw };
-}
-
-// One iteration of Train_Step's loop body (nerf_model.cu:1637-1646), enqueued without host syncs.
-static void enqueue_iteration(Model& m, int stages) {
-    hipStream_t s = m.train_stream; const uint32_t B = m.oc.R * m.oc.S;
-    // XORWOW mode: the generate calls of this iteration and of the next one (whose candidates and positions are prepared during this one), in order, once each
-    if (m.d_xw) {
-        const uint32_t R = m.oc.R, n_it = (5u + m.oc.S) * R;
-        while (m.xw_filled <= m.enq_iter + 1u) {
-            float* set = m.d_xw + (size_t)(m.xw_filled & 1u) * n_it;
-            // :1432, :1434, :1468
-            launch_xorwow_fill(s, m.d_xw_states, m.xw_lanes, m.xw_flavour, (uint32_t)(m.xw_offset % m.xw_lanes), set, 2u * R, set + 2u * R, 3u * R,
-                    set + 5u * R, m.oc.S * R);
-            ++m.xw_filled; m.xw_offset += n_it;
-        }
-    }
-    if (stages & 1) {      // GenerateBatch :1429-1502
-        ProfScope ps(m, MON_K_BATCH);
-        // otherwise the last k_optimizer already did all of it
-        if (m.backend == 1) { if (!m.next_ready) { launch_candidates_and_frags(s, m.B, m.ds->ptrs(), m.oc, m.d_state, m.P.half, m.nd, m.d_frag_train);
-                if (m.d_half_tiles) launch_build_tiles_image(s, m.lf, m.nd, m.P.half, m.d_half_tiles); } }
-        else launch_gen_candidates(s, m.B, m.ds->ptrs(), m.oc, m.d_state);
-        if (m.backend == 0) {                       // the fused kernel compacts the rays itself
-            launch_build_rays(s, m.B, m.oc, m.d_state);
-            // (the layer-kernel shapes on the level-tile encode: the positions also as k_encode_tiles' float4)
-            launch_gen_samples(s, m.B, m.oc, m.d_state, m.oc.S, B, kStreamDt, 0u, 0, (m.d_layers_T && m.d_e_soa && m.d_half_tiles) ? m.d_x_all : nullptr);
-        }
-    }
-    // whole steps of a shape outside the fused kernels scatter through k_rows_to_bins -> k_grid_scatter into partial tables that the DENSE optimizer sums; the
-    // Step() schedule and the stage-wise debugging entry keep tcnn's global atomics into ggrid, which only the non-dense optimizer reads and clears.  ONE flag for
-    // both sites (the scatter site and the optimizer site disagreed under step_variant, and the grid stopped training)
-    const bool hybrid = m.backend == 0 && m.hybrid_scatter && stages == 7 && !options().step_variant;
-    if (stages & 2) {      // Step_No_Compacted :1552-1607
-        if (m.backend == 0 && options().step_variant) {
-            // NeRF_Model::Step (nerf_model.cu:1504-1550): inference of every sample, per-ray sample compaction + rollover (kernels_step.hip), then
-            // forward + backward of the compacted batch.  B.pts / B.dO hold the compacted batch afterwards.
-            ProfScope ps(m, MON_K_FWDBWD);
-            launch_encode(s, m.lt, m.nd, m.P.half, m.B.pts, m.B.E, B, m.d_state);
-            // :1509 inference_mixed_precision_impl, training weights
-            launch_mlp_forward(s, m.nd, m.P.half, m.B.E, nullptr, m.B.O, B, m.d_state);
-            launch_step_compaction(s, m.B, m.oc, m.d_state, m.d_step_counts, m.d_step_pts);
-            hipMemcpyAsync(m.B.pts, m.d_step_pts, 12 * (size_t)B, hipMemcpyDeviceToDevice, s);
-            launch_encode(s, m.lt, m.nd, m.P.half, m.B.pts, m.B.E, B, m.d_state);                             // :1545 forward of the compacted batch
-            // (this schedule's gradient scatter reads dE / dO row-major through tcnn-style atomics and is a checkable curiosity, not a fast path: row-major throughout)
-            if (!(m.d_layers_T && launch_mlp_forward_layers(s, m.nd, m.P.half, m.B.E, m.B.Hid, m.B.O, B, m.d_state, m.d_layers_T)))
-                launch_mlp_forward(s, m.nd, m.P.half, m.B.E, m.B.Hid, m.B.O, B, m.d_state);
-            if (m.d_layers_T && launch_mlp_backward_layers(s, m.nd, m.P.half, m.B.Hid, m.B.dO, m.B.dHid, m.B.dE, B, m.d_state, m.d_layers_T, true))
-                launch_weight_grads_layers(s, m.nd, m.P.gmlp, B, m.d_state, m.d_layers_T);
-            else {
-                launch_mlp_backward(s, m.nd, m.P.half, m.B.Hid, m.B.dO, m.B.dHid, m.B.dE, B, m.d_state);          // :1547
-                launch_weight_grads(s, m.nd, m.B.E, m.B.Hid, m.B.dHid, m.B.dO, m.P.gmlp, B, m.d_state);
-            }
-            if (m.hybrid_scatter) hipMemsetAsync(m.P.ggrid, 0, (size_t)m.n_grid * 2, s);           // (a whole step of the other schedule may have left partial sums)
-            launch_grid_backward(s, m.lt, m.nd, m.B.pts, m.B.dE, m.P.ggrid, B, m.d_state);
-        } else if (m.backend == 0) {
-            ProfScope ps(m, MON_K_FWDBWD);
-            // the layer-kernel shapes at base.json-sized batches: the encode from LDS level tiles (k_encode_tiles, bit-identical to the gathers) -- the tile image
-            // is kept current by k_optimizer in whole steps and rebuilt here after anything else touched the weights
-            const bool tiles_b0 = m.d_layers_T && m.d_e_soa && m.d_half_tiles && options().lds_encode != 0;
-            if (tiles_b0) {
-                if (!m.b0_tiles_current) { launch_build_tiles_image(s, m.lf, m.nd, m.P.half, m.d_half_tiles); m.b0_tiles_current = true; }
-                launch_encode_tiles(s, m.lf, m.nd, m.d_half_tiles, m.d_x_all, m.d_e_soa, B, m.d_state, nullptr, m.ds->ptrs(), m.oc);
-            } else
-            launch_encode(s, m.lt, m.nd, m.P.half, m.B.pts, m.B.E, B, m.d_state);
-            // (shapes outside the fused kernels: whole-network MFMA kernels, kernels_layers.hip)
-            if (tiles_b0) {
-                if (!launch_mlp_forward_layers(s, m.nd, m.P.half, m.B.E, m.B.Hid, m.B.O, B, m.d_state, m.d_layers_T, m.d_e_soa, m.B.E, stages != 7))
-                    launch_mlp_forward(s, m.nd, m.P.half, m.B.E, m.B.Hid, m.B.O, B, m.d_state);         // (not reached: the shapes with a T workspace are the kernels' shapes)
-            }
-            else if (!(m.d_layers_T && launch_mlp_forward_layers(s, m.nd, m.P.half, m.B.E, m.B.Hid, m.B.O, B, m.d_state, m.d_layers_T, nullptr, nullptr, stages != 7)))
-                launch_mlp_forward(s, m.nd, m.P.half, m.B.E, m.B.Hid, m.B.O, B, m.d_state);
-            launch_composite_grad(s, m.B, m.oc, m.d_state);
-            // (whole steps of the hybrid scatter with S = 32: the backward kernel writes k_grid_scatter's hand-over itself)
-            const bool fold_bins = hybrid && m.d_layers_T && m.oc.S == 32u;
-            const BinsOut bins{ m.d_de_soa, m.d_x_soa, m.B.pts, m.n_bins, m.lf.fix_clamp, m.d_state };
-            bool bins_done = false;
-            if (m.d_layers_T && launch_mlp_backward_layers(s, m.nd, m.P.half, m.B.Hid, m.B.dO, m.B.dHid, m.B.dE, B, m.d_state, m.d_layers_T, stages != 7,
-                    fold_bins ? &bins : nullptr)) {
-                launch_weight_grads_layers(s, m.nd, m.P.gmlp, B, m.d_state, m.d_layers_T); bins_done = fold_bins; }
-            else {
-                launch_mlp_backward(s, m.nd, m.P.half, m.B.Hid, m.B.dO, m.B.dHid, m.B.dE, B, m.d_state);
-                launch_weight_grads(s, m.nd, m.B.E, m.B.Hid, m.B.dHid, m.B.dO, m.P.gmlp, B, m.d_state);
-            }
-            // whole steps of a shape outside the fused kernels: the exact LDS scatter (partial tables, summed by the optimizer).  Stage-wise calls (the debugging
-            // entry that stops before the optimizer) keep tcnn's global atomics into ggrid, which only the non-dense optimizer clears: start from zeros there
-            if (hybrid) {
-                if (!bins_done) launch_rows_to_bins(s, m.lf, m.nd, m.B.dE, m.B.pts, m.oc.R, m.oc.S, m.n_bins, m.d_de_soa, m.d_x_soa, m.d_state);
-                launch_grid_scatter(s, m.lt, m.lf, m.nd, m.d_de_soa, m.d_x_soa, B, m.n_bins, m.d_gpart, m.part_halves / 2, m.d_state, nullptr, 0u, m.P.gmlp,
-                        m.d_state_next);
-            } else {
-                if (m.hybrid_scatter) hipMemsetAsync(m.P.ggrid, 0, (size_t)m.n_grid * 2, s);
-                launch_grid_backward(s, m.lt, m.nd, m.B.pts, m.B.dE, m.P.ggrid, B, m.d_state);
-            }
-        } else {
-            // stage-wise debugging: a forward/backward without an optimizer step after it
-            if (m.scatter_pending) hipMemsetAsync(m.d_state->n_scatter, 0, sizeof(m.d_state->n_scatter), s);
-            // the encode as LDS reads of level tiles; the fused kernel then loads the features
-            // (the grid in use without live-sample lists -- a batch size whose partitions do not hold whole position blocks --: the gather chain masks its loads)
-            const bool pre = m.d_e_soa && m.fused_dump != 1 && options().lds_encode && !m.gathers_preferred && !(m.d_occ && m.occ_refreshed_iter && !m.d_live_idx);
-            m.pre_active = pre;
-            const LiveArgs live = live_args(m);
-            if (pre) {
-                // positions of this batch: normally the last k_optimizer's position blocks already wrote them (and k_encode_tiles of the last iteration the
-                // candidates)
-                if (!(m.next_ready && m.points_ready)) { ProfScope pp(m, MON_K_POINTS); launch_sample_points(s, m.B, m.oc, m.d_state, m.d_x_all, live); }
-                // (the next iteration is always prepared ahead: the stand-alone kernels run after an invalidation only)
-                const bool gen_next = true;
-                { ProfScope pe(m, MON_K_ENCODE); launch_encode_tiles(s, m.lf, m.nd, m.d_half_tiles, m.d_x_all, m.d_e_soa, B, m.d_state, gen_next ? &m.B_alt
-                        : nullptr, m.ds->ptrs(), m.oc,
-#ifdef MON_OVERLAP_PROBE
-                        (uint32_t)options().enc_lds_kb * 1024u,
-#else
-                        0u,
-#endif
-                        live); }
-            }
-            ProfScope ps(m, MON_K_FWDBWD);
-            // (no grid look-ups before the first refresh: every cell is live during the warm-up)
-            launch_fused_train(s, m.lf, m.nd, m.P, m.B, m.oc, m.d_state, m.d_dw_partials, m.fused_dump, m.d_de_soa, m.d_x_soa, m.lds_mask, m.d_frag_train,
-                    m.big_active ? m.big_switch : 0u, m.d_touched, m.occ_refreshed_iter ? m.d_occ : nullptr, m.n_bins, pre ? m.d_e_soa : nullptr);
-            m.scatter_pending = true;
-        }
-    }
-    if ((stages & 2) && m.backend == 1) {
-        const bool folded = m.lds_mask && grid_scatter_sums_partials(m.lt, m.nd);   // the scatter workgroups also sum the dW partial rows
-        if (m.lds_mask) { ProfScope ps(m, MON_K_SCATTER);
-            launch_grid_scatter(s, m.lt, m.lf, m.nd, m.d_de_soa, m.d_x_soa, B, m.n_bins, m.d_gpart, m.part_halves / 2, m.d_state,
-                                                                                folded ? m.d_dw_partials : nullptr, fused_train_grid(m.nd, m.oc.R), m.P.gmlp,
-                                                                                        m.d_state_next); }
-        if (m.big_active) { ProfScope ps(m, MON_K_SCATTER);
-            launch_big_scatter(s, m.lt, m.lf, m.nd, m.lds_mask, m.d_de_soa, m.d_x_soa, B, m.n_bins, m.d_state, m.big_switch, m.d_big_ws, m.P.ggrid, m.d_touched
-                ? m.d_touched + (m.nd.n_mlp >> 3) : nullptr); }
-        if (!folded) { ProfScope ps(m, MON_K_REDUCE); launch_reduce_partials(s, m.d_dw_partials, fused_train_grid(m.nd, m.oc.R), m.nd, m.P.gmlp, m.d_state); }
-    }
-    if (stages & 4) {      // Trainer::optimizer_step :1644
-        ProfScope ps(m, MON_K_OPTIM);
-        ParamPtrs P = m.P;
-        if (m.backend == 1 && m.lds_mask) { P.gpart = m.d_gpart; P.part_stride = m.part_halves; P.sl = m.scatter;
-            P.all_levels_dense = (m.lds_mask == ((1u << m.nd.L) - 1u)) ? 1 : 0; }
-        if (hybrid) { P.gpart = m.d_gpart; P.part_stride = m.part_halves; P.sl = m.scatter; P.all_levels_dense = 1; }
-        P.half_tiles = ((m.backend == 1 || hybrid) && P.gpart && P.all_levels_dense) ? m.d_half_tiles : nullptr;
-        if (m.backend == 0) m.b0_tiles_current = hybrid && P.half_tiles != nullptr;        // (any other optimizer leaves the tile image behind the weights)
-        const bool lazy = m.lazy_ema && !(P.gpart && P.all_levels_dense);
-        P.ema_step = lazy ? m.d_ema_step : nullptr; P.lazy = lazy ? 1 : 0; if (lazy) m.ema_pending = true;
-        // (the LDS-scattered levels are a prefix: sizes grow with the level)              // every writer of ggrid on the fused path sets the chunk flags; the
-        // unfused grid backward does not
-        if (lazy && m.backend == 1 && m.d_touched && (m.lds_mask & (m.lds_mask + 1u)) == 0u) {
-            P.touched = m.d_touched; uint32_t first_big = 0; while (first_big < (uint32_t)m.nd.L && ((m.lds_mask >> first_big) & 1u)) ++first_big;
-            P.first_flag_chunk = (m.nd.n_mlp + 2u * m.lt.offset[first_big]) >> 3;
-        }
-        OptimNext nx{};
-        // (see gen_next above: options fold_next / fold_reduce / lds_scatter were measurement switches of rounds 1-2 and are gone)
-        const bool fold = true;
-        // k_encode_tiles generated the next candidates into B_alt; sample their positions here
-        const bool pos_mode = m.backend == 1 && fold && m.pre_active && m.d_e_soa;
-        if (m.backend == 1 && fold) {
-            nx.cand_blocks = pos_mode ? 0u : (m.oc.R + 255) / 256; nx.frag_image = m.d_frag_train; nx.fd = FragDims{ m.nd.Epad, m.nd.W, m.nd.NH, m.nd.L };
-            nx.b = pos_mode ? m.B_alt : m.B; nx.ds = m.ds->ptrs(); nx.oc = m.oc;
-            // one sample per thread up to 131 072 samples (two beyond: as many position blocks as optimizer blocks made the kernel 10 us longer at R = 8192): a
-            // thread's chain is select -> candidate loads -> store, ~5 us of latency that several samples per thread put in series (64 blocks of 8 samples per
-            // thread made these blocks the kernel's tail)
-            if (pos_mode) { nx.pos_blocks = std::min((B + 255u) / 256u, 512u); nx.x_all = m.d_x_all; nx.live = live_args(m); }
-        }
-#ifdef MON_OVERLAP_PROBE
-        // PROBE (option overlap): a second, throw-away k_encode_tiles of the CURRENT batch next to k_optimizer -- what would the pair cost side by side?
-        //   1 behind the optimizer on the same stream; 2 / 3 on a side stream, enqueued before / after the optimizer; 4 / 5 the same with a high-priority side
-        //   stream (its own hardware queue); 6 behind the optimizer on the same stream WITHOUT the barrier bit (hipExtAnyOrderLaunch)
-        const long ovl = pos_mode ? (long)options().overlap : 0; const uint32_t enc_lds = (uint32_t)options().enc_lds_kb * 1024u;
-        auto dummy_encode = [&](hipStream_t q, uint32_t any) { launch_encode_tiles(q, m.lf, m.nd, m.d_half_tiles, m.d_x_all, m.d_e_soa, B, m.d_state, nullptr,
-                m.ds->ptrs(), m.oc, enc_lds | any); };
-        const bool side = ovl >= 2 && ovl <= 5, enc_first = ovl == 2 || ovl == 4;
-        if (side && !m.side_stream) {
-            if (ovl >= 4) hipStreamCreateWithPriority(&m.side_stream, hipStreamNonBlocking, -1); else hipStreamCreateWithFlags(&m.side_stream, hipStreamNonBlocking);
-            hipEventCreateWithFlags(&m.ev_fork, hipEventDisableTiming); hipEventCreateWithFlags(&m.ev_join, hipEventDisableTiming); }
-        if (side) { hipEventRecord(m.ev_fork, s); hipStreamWaitEvent(m.side_stream, m.ev_fork, 0); }
-        if (side && enc_first) { dummy_encode(m.side_stream, 0u); hipEventRecord(m.ev_join, m.side_stream); }
-#endif
-        launch_optimizer(s, P, m.opt, m.d_state, m.d_state_next, nx, (m.oc.R * m.oc.S) / 8u); m.scatter_pending = false;
-#ifdef MON_OVERLAP_PROBE
-        if (side && !enc_first) { dummy_encode(m.side_stream, 0u); hipEventRecord(m.ev_join, m.side_stream); }
-        if (side) hipStreamWaitEvent(s, m.ev_join, 0);
-        if (ovl == 1) dummy_encode(s, 0u);
-        if (ovl == 6) dummy_encode(s, 1u);
-#endif
-        std::swap(m.d_state, m.d_state_next);                // the next iteration (and the host's read-back) uses the state this launch prepares
-        if (pos_mode) std::swap(m.B, m.B_alt);               // ... and the candidate set k_encode_tiles filled for it
-        m.next_ready = (m.backend == 1 && fold); m.points_ready = pos_mode; ++m.enq_iter;
-    }
-}
-
-// Occupancy grid refresh (cfg.occupancy_skip): before iteration `iter` when it is due.  Stream-ordered between two iterations, from the training weights.
-static void maybe_refresh_occupancy(Model& m, uint32_t iter) {
-    // due at the first iteration it is asked for at or after the next multiple of kOccInterval (the hipGraph path only asks at the start of a captured PAIR:
-    // after an odd number of iterations an exact "iter % interval == 0" test was never true again and the grid was never refreshed)
-    if (!m.d_occ || m.occ_pinned || m.backend != 1 || iter < (uint32_t)kOccWarmup || iter < m.occ_next_refresh) return;
-    launch_occupancy_update(m.train_stream, m.lf, m.nd, m.P.half, m.oc, m.d_frag_occ, m.occ_raw_threshold, m.d_occ_tmp, m.d_occ);
-    // the density field settles: every kOccInterval iterations at first, every 4th / 16th of that rate later (a refresh costs ~60 us, 1.9 us per step at the
-    // early rate -- more than the skipping saves once the level-tile chain has taken the gathers out of the forward pass; tools/occ_timing.py)
-    const uint32_t every = (uint32_t)kOccInterval * (iter < 512u ? 1u : iter < 2048u ? 4u : 16u);
-    m.occ_refreshed_iter = iter; m.occ_next_refresh = (iter / every + 1u) * every;
-    // the positions already sampled for this iteration carry the OLD grid's live bits and lists (or none: the first refresh): sample them again
-    if (m.d_live_idx) m.points_ready = false;
-}
-
-static int sync_state(Model& m) {
-    // :1645 (once per call instead of once per iteration); the state rides the same sync in a pinned buffer -- the online manager trains
-    // in slices of a few iterations, where a second blocking copy would be a visible share of the slice
-    // (only the head: the slot counters behind it are 16 KB the host never reads; written by a one-block kernel rather than hipMemcpyAsync, whose small-copy
-    // path costs the slicing online thread ~10 us per call)
-    launch_copy_params(m.train_stream, reinterpret_cast<const uint16_t*>(m.d_state), reinterpret_cast<uint16_t*>(m.h_state_pinned),
-            (uint32_t)(offsetof(DevState, n_scatter) / 2));
-    // (an event, not hipStreamSynchronize: the stream may be a lane other objects keep feeding)
-    if (!m.sync_event) HIPCHECK(hipEventCreateWithFlags(&m.sync_event, hipEventDisableTiming));
-    HIPCHECK(hipEventRecord(m.sync_event, m.train_stream)); HIPCHECK(hipEventSynchronize(m.sync_event));
-    std::memcpy(&m.h_state, m.h_state_pinned, offsetof(DevState, n_scatter));
-    collect_profile(m);
-    return MON_OK;
-}
-
-int model_train(Model& m, int iters, float* loss, int stages) {
-    if (iters < 0) { set_error("train: negative iteration count"); return MON_ERR_ARG; }
-    if (m.n_boxes == 0) { set_error("train: no 2-D boxes (UpdateFrameIdAndBbox was never called)"); return MON_ERR_STATE; }
-    HIPCHECK(use_device(m.device));
-    // workspace of the Step() schedule (enqueue_iteration cannot report a failed allocation)
-    if (m.backend == 0 && options().step_variant && !m.d_step_counts) {
-        int rc;
-        if ((rc = dev_alloc(m, m.d_step_counts, (size_t)m.oc.R + 1)) || (rc = dev_alloc(m, m.d_step_pts, 3 * (size_t)m.oc.R * m.oc.S))) return rc;
-    }
-    // Large-table scatter: the device picks binned / atomic per iteration from the previous iteration's gradient-carrying sample count;
-    // once the host has seen that count well below the switch point it stops launching the (then empty) binning kernels at all.
-    m.big_active = m.big_switch && (m.h_state.n_scatter_last == 0u || m.h_state.n_scatter_last > m.big_switch / 2u);
-    // Occupancy-grid skipping (opt-in): once the grid is in use and few samples are left, the gather chain wins -- k_fused_train skips the gathers of the
-    // samples in empty cells, k_encode_tiles encodes every sample (kernel_times, late window: 63.3 against 65.4 us per step; early, 99.6 against 92.1).  Both
-    // chains leave bit-identical parameters, so the choice is free per call; the host knows the regime from the last call's read-back.
-    m.gathers_preferred = m.d_occ && m.occ_refreshed_iter && m.h_state.n_scatter_last != 0u && 8u * m.h_state.n_scatter_last < m.oc.R * m.oc.S;
-#ifndef MON_OCC_PREFER_GATHERS      // (variant build for the A/B)
-    // round 6: with the live-sample lists k_encode_tiles walks the live samples only and the level tiles win in every regime
-    if (m.d_live_idx) m.gathers_preferred = false;
-#endif
-    const bool use_graph_env = options().use_graph != 0;
-    if (iters > 0) m.weights_epoch = next_weights_epoch();
-    // (nothing of this object is in flight between calls: the read-back at the end of the last one is current)
-    m.enq_iter = m.h_state.iter;
-    // (the first occupancy refresh changes a kernel argument)
-    const bool use_graph = use_graph_env && !m.profiling && stages == 7 && iters >= 2 && !(m.d_occ && !m.occ_refreshed_iter) && !m.d_xw;
-    // chunks of iterations go through the device's training lanes (whole steps only; big-table objects are HBM-bound in their optimizer and gain from more
-    // overlap, not less)
-    const bool lanes_on = stages == 7 && m.big_switch == 0u; const int chunk = kLaneChunk;
-    if (use_graph) {
-        // (the last bit: which forward chain the captured pair runs)
-        const int graph_key = m.backend | (m.big_active ? 256 : 0) | (m.occ_refreshed_iter ? 512 : 0)
-                | ((m.d_e_soa && options().lds_encode && !m.gathers_preferred) ? 1024 : 0);
-        // (the captured pair starts on this DevState and this candidate set)
-        if (!m.graph_exec || m.graph_backend != graph_key || m.graph_state != m.d_state || m.graph_mask != m.B.mask) {
-            drop_graph(m);
-            hipGraph_t g = nullptr;
-            // captured on the object's own stream (a lane is shared with other host threads), replayed on the current one
-            const hipStream_t cur = m.train_stream; m.train_stream = m.own_stream;
-            HIPCHECK(hipStreamBeginCapture(m.train_stream, hipStreamCaptureModeThreadLocal));
-            m.next_ready = false;                           // the captured iterations are self-contained
-            m.graph_state = m.d_state; m.graph_mask = m.B.mask;
-            // a PAIR: the two DevStates swap roles every iteration, after two the captured pointers are current again
-            enqueue_iteration(m, 7); enqueue_iteration(m, 7);
-            const hipError_t ce = hipStreamEndCapture(m.train_stream, &g); m.train_stream = cur; HIPCHECK(ce);
-            HIPCHECK(hipGraphInstantiate(&m.graph_exec, g, nullptr, nullptr, 0));
-            hipGraphDestroy(g); m.graph_backend = graph_key;
-        }
-        int i = 0;
-        while (i + 2 <= iters) {
-            LaneChunk lc(m, lanes_on);
-            for (int k = 0; k < chunk && i + 2 <= iters; k += 2, i += 2) { maybe_refresh_occupancy(m, m.h_state.iter + (uint32_t)i);
-                HIPCHECK(hipGraphLaunch(m.graph_exec, m.train_stream)); }
-        }
-        for (; i < iters; ++i) { LaneChunk lc(m, lanes_on); maybe_refresh_occupancy(m, m.h_state.iter + (uint32_t)i); m.next_ready = false;
-            enqueue_iteration(m, 7); }
-    } else {
-        for (int i = 0; i < iters; ) {
-            LaneChunk lc(m, lanes_on);
-            for (int k = 0; k < chunk && i < iters; ++k, ++i) { if (stages == 7) maybe_refresh_occupancy(m, m.h_state.iter + (uint32_t)i);
-                enqueue_iteration(m, stages); }
-        }
-    }
-    HIPCHECK(hipGetLastError());
-    int rc = sync_state(m); if (rc) return rc;
-    if (loss) *loss = m.h_state.loss_sum / (float)m.oc.R;       // :1650-1658
-    if (stages == 7 && iters > 0) rc = publish_snapshot(m, iters >= 64);
-    mark_tail(m);
-    return rc;
-}
-
-// owner thread: the end of a whole Train_Step_Online
-int model_publish_snapshot(Model& m) { HIPCHECK(use_device(m.device)); const int rc = publish_snapshot(m, true); mark_tail(m); return rc; }
 
 // Render of the latest PUBLISHED inference weights on the inference stream: callable from any thread while the owner trains (no model mutex,
 // no train-stream work).  MON_ERR_STATE when nothing has been published yet (or the model has no inference side): the caller falls back to
@@ -1316,7 +869,7 @@ int model_density_grid(Model& m, int rx, int ry, int rz, float* out_host) {
     HIPCHECK(hipMemcpy(&m.h_state, m.d_state, offsetof(DevState, n_scatter), hipMemcpyDeviceToHost));
     const uint16_t* prm = (m.h_state.step > 0) ? m.P.ema : m.P.half;
     const uint32_t total = (uint32_t)rx * ry * rz, chunk = m.ws_samples;
-    if (m.backend == 1 && m.tile_ok && options().tile_render != 0) {      // level tiles in LDS: the device's train-side workspace
+    if (m.backend == 1 && m.plan.tile_render && options().tile_render != 0) {      // level tiles in LDS: the device's train-side workspace
         TileWs* ws = nullptr; { const int rc = tile_ws_get(m, 0, 0, &ws); if (rc) return rc; }
         std::lock_guard<std::mutex> wl(ws->mu);
         tile_ws_weights(m, *ws, s, prm, m.weights_epoch);
@@ -1344,7 +897,7 @@ int model_density_grid(Model& m, int rx, int ry, int rz, float* out_host) {
 }
 
 // ---- render skipping: the switch, its statistics, the grids
-bool rskip_supported(const Model& m) { return m.backend == 1 && fused_supported(m.nd, m.oc.S, m.oc.R); }
+bool rskip_supported(const Model& m) { return m.backend == 1 && m.plan.fused; }
 int model_set_render_skip(Model& m, int enable, float min_alpha) {
     if (!rskip_supported(m)) { set_error("set_render_skip: this object does not run on the fused kernels (layer-kernel backend)"); return MON_ERR_STATE; }
     if (!(min_alpha < 1.0f)) { set_error("set_render_skip: min_alpha must be < 1"); return MON_ERR_ARG; }
@@ -1412,8 +965,7 @@ int model_set_pose(Model& m, const float* Tow16) {
         if (m.infer && m.infer->shared) infer_lock = std::unique_lock<std::mutex>(m.infer->shared->mu);
         std::memcpy(m.oc.Tow.m, Tow16, 64);
     }
-    m.next_ready = false; m.points_ready = false;
-    drop_graph(m);
+    model_mark_stale(m, kStaleRays, true);
     return MON_OK;
 }
 
@@ -1440,8 +992,7 @@ int model_set_params(Model& m, const float* master, size_t n) {
     HIPCHECK(use_device(m.device)); model_leave_lane(m); HIPCHECK(hipStreamSynchronize(m.train_stream));
     { const int urc = upload_master(m, master); if (urc) return urc; }
     HIPCHECK(hipStreamSynchronize(m.train_stream));
-    m.next_ready = false;                                   // the fragment image no longer matches the weights
-    m.b0_tiles_current = false;
+    model_mark_stale(m, kStaleWeights);                     // the fragment image and the tile image no longer match the weights
     m.weights_epoch = next_weights_epoch();
     { const int rc = publish_snapshot(m); if (rc) return rc; }   // (viewers of an untrained object see the weights just set:
     // the snapshot is complete before the call returns, so no render prefers the one before it)

@@ -170,9 +170,6 @@ struct Options {      // (atomics: tests and tools flip options while object thr
          tile_render{ 1 };      // inference on feature-planar level tiles: 0 never (gathers), 1 crops of 4096 rays and more + point queries, 2 always
     // NerfManagerOffline's 10 x 500 iterations (nerf_manager.cu:89): mon_offline_set_schedule, read by mon_offline_init
     std::atomic<long> offline_outer{ 10 }, offline_inner{ 500 };
-#ifdef MON_OVERLAP_PROBE        // variant build only (tools/variant_build.sh ovl -DMON_OVERLAP_PROBE; HISTORY 7.9): k_optimizer(i) next to a throw-away k_encode_tiles
-    std::atomic<long> overlap{ 0 }, enc_lds_kb{ 0 };
-#endif
 };
 // Round 6: the A/B switches whose losing setting only a measurement ever wanted are VARIANT BUILDS now (tools/variant_build.sh <tag> -DMON_VARIANT_...; the
 // oracle tests of the large-table optimizer run against each, tools/gpu_variants_large.sh), not runtime options of the shipping library:
@@ -294,7 +291,7 @@ void launch_sample_points(hipStream_t s, const BatchPtrs& b, const ObjectConst& 
 void launch_encode_tiles(hipStream_t s, const LevelFast& lf, const NetDims& nd, const uint16_t* half_tiles, const float* x_all, uint16_t* e_soa, uint32_t B,
         const DevState* st,
                          // b_next: the candidate set GenerateRays of the next iteration goes to
-                         const BatchPtrs* b_next_or_null, const DatasetPtrs& ds, const ObjectConst& oc, uint32_t lds_bytes = 0, const LiveArgs& live = LiveArgs{});
+                         const BatchPtrs* b_next_or_null, const DatasetPtrs& ds, const ObjectConst& oc, const LiveArgs& live = LiveArgs{});
 uint32_t encode_tiles_spw(uint32_t B);          // samples per sample partition of k_encode_tiles (a partition's live list starts at w * spw)
 // XORWOW sample stream (kernels_encode.hip k_xorwow_fill): one thread per lane, the generate calls of one iteration / one Render in the reference's order
 void launch_xorwow_fill(hipStream_t s, void* lane_states, uint32_t lanes, int flavour, uint32_t start_lane, float* out0, uint32_t n0, float* out1, uint32_t n1,
@@ -487,7 +484,38 @@ struct RenderSkipSide {
     uint64_t builds = 0; bool active = false; uint64_t samples_in_box = 0, samples_live = 0;
 };
 
+// What an object's shape, config and the options at its creation allow: which buffers model_init allocates and therefore which training chains the enqueue
+// code (train.cpp) CAN run.  Filled once by train_plan (model.cpp), a pure function; never changes.  What one iteration then takes among these is decided
+// per enqueued iteration (step_choice, train.cpp).
+struct PlanOptions { long backend, lds_encode; uint32_t big_switch; };      // the option values read at creation
+struct TrainPlan {
+    bool fused;             // the shape is one the fused kernels take (fused_supported); else the layer-at-a-time kernels, backend 0 by necessity
+    bool fused_backend;     // ... and option backend did not ask for the layer-at-a-time kernels: the backend the object starts on, its inference on the fused kernels
+    uint32_t lds_mask;      // fused: the levels k_grid_scatter covers (a prefix; d_de_soa, d_x_soa, d_gpart)
+    bool lds_all;           // ... every level: the dense optimizer
+    bool big_scatter;       // fused: levels beyond the LDS plan go through kernels_bigscatter.hip (d_big_ws, Model::big_switch)
+    bool touched_flags;     // fused: chunk flags for the lazy optimizer (d_touched)
+    bool level_tiles;       // level-tile encode (d_x_all, d_e_soa, d_half_tiles; fused: also B_alt, the second candidate set)
+    // not fused: T-layout workspace of the MFMA layer kernels (kernels_layers.hip; d_layers_T) -- without it kernels_net.hip's one-sample-per-thread kernels run
+    bool layer_ws;
+    // not fused (the layer-at-a-time kernels), every level in the LDS plan: the grid backward of whole training steps goes through k_grid_scatter (d_de_soa,
+    // d_x_soa, d_gpart)
+    bool hybrid_scatter;
+    bool occupancy;         // fused + cfg.occupancy_skip: the occupancy grid (d_occ, d_occ_tmp, d_frag_occ)
+    // ... and, for the level-tile chain with the grid in use, live-sample lists for k_encode_tiles (LiveArgs; d_live_idx, d_live_cnt): a position block's 256
+    // samples must lie in one of the encode's sample partitions, and a list -- at most ceil(blocks / n_parts) * 256 entries -- must fit the partition's spw slots
+    bool live_lists;
+    bool xorwow;            // the reference's XORWOW sample stream (d_xw*)
+    bool lazy_ema;          // tables above 8 M parameters: the lazy optimizer and EMA (d_ema_step or chunk records)
+    bool tile_render;       // the inference side may run on feature-planar level tiles (tile_render_supported)
+    // published snapshots and a render workspace of their own (InferState).  Not in the XORWOW mode (one generator per Render, like the reference) nor for
+    // tables above 8 M parameters (lazy EMA; 2 x 200 MB of snapshots): those render on the train stream
+    bool inference_side;
+};
+TrainPlan train_plan(const mon_config& cfg, const LevelTable& lt, const NetDims& nd, uint32_t R, uint32_t S, bool lazy_ema, const PlanOptions& opt);
+
 struct Model {
+    TrainPlan plan{};
     MeshState* mesh = nullptr;
     InferState* infer = nullptr;                // mpInferenceStream (nerf_model.cu:1269): renders for viewers that never queue behind training
     Dataset* ds = nullptr; mon_config cfg{}; int device = 0;
@@ -507,11 +535,9 @@ struct Model {
     uint16_t* d_de_soa = nullptr; float* d_x_soa = nullptr;       // compacted dL/dE rows [L][B] and positions [B] float4 for the scatter kernels
     // level-tile encode: positions [B] float4 of every sample, encoded features [L][B] half2 (nullptr: the fused kernel gathers)
     float* d_x_all = nullptr; uint16_t* d_e_soa = nullptr; uint16_t* d_half_tiles = nullptr;
-    // network shapes outside the fused kernels (backend 0 by necessity) whose levels all fit the LDS scatter plan: whole training steps scatter through k_grid_scatter
-    bool hybrid_scatter = false;
     bool b0_tiles_current = false;            // layer-kernel shapes on the level-tile encode: the tile image matches the fp16 weights (k_optimizer keeps it so in whole steps)
     uint16_t* d_layers_T = nullptr;          // T-layout workspace of the MFMA layer kernels (shapes outside the fused kernels)
-    uint16_t* d_gpart = nullptr; ScatterLevels scatter{}; uint32_t lds_mask = 0;   // k_grid_scatter: partial tables, plan, levels it covers
+    uint16_t* d_gpart = nullptr; ScatterLevels scatter{};   // k_grid_scatter: partial tables, plan (the levels it covers: plan.lds_mask)
     // halves of ONE partial table: the grid parameters of the LDS-scattered levels (a prefix of the levels), not of the whole table
     uint32_t part_halves = 0;
     uint16_t* d_frag_train = nullptr; uint16_t* d_frag_render = nullptr;           // MFMA A-fragment images (training weights / inference weights)
@@ -530,7 +556,7 @@ struct Model {
     float* h_out = nullptr; size_t h_out_cap = 0;
     std::vector<void*> allocs;
     DevState h_state{}; DevState* h_state_pinned = nullptr; int backend = 0; bool profiling = false; int fused_dump = 0;
-    bool lazy_ema = false, ema_pending = false;   // large tables: EMA of untouched chunks is brought up to date on demand (k_ema_finalize)
+    bool ema_pending = false;   // large tables (plan.lazy_ema): EMA of untouched chunks is brought up to date on demand (k_ema_finalize)
     bool scatter_pending = false;   // a fused forward/backward was enqueued whose slot counter has not been reset by an optimizer step yet
     // XORWOW sample stream: lane states of the training generator (device), the two per-parity array sets, the iteration the fills have reached, the per-Render
     // generator xw_offset: values the training generator has produced
@@ -542,7 +568,6 @@ struct Model {
     // gather chain (occupancy grid + few live samples)
     bool pre_active = false, points_ready = false, gathers_preferred = false;
     bool tile_counted = false;   // this object is counted in its device's tile workspace (freed with the device's last such object)
-    bool tile_ok = false;        // the inference side may run on feature-planar level tiles (tile_render_supported)
     std::atomic<int> rskip_on{ 0 }; std::atomic<float> rskip_alpha{ 1e-3f };      // render skipping: the switch (read once per render call)
     RenderSkipSide rskip;                                                             // ... and its train-stream side
     struct PoseWs* pose_ws[2] = { nullptr, nullptr };                                // pose refinement scratch per side (pose.cpp), made on first use 
@@ -554,13 +579,48 @@ struct Model {
     struct TrainLanes* lanes = nullptr; int lane = -1; hipEvent_t lane_event = nullptr, switch_event = nullptr, sync_event = nullptr;
     // the object's private stream; train_stream is the one its work currently goes to (this one or a lane's)
     bool tail_marked = false; hipStream_t own_stream = nullptr;
-#ifdef MON_OVERLAP_PROBE
-    hipStream_t side_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-#endif
     // (the state the captured pair of iterations starts on)
     hipGraphExec_t graph_exec = nullptr; int graph_backend = -1; const DevState* graph_state = nullptr; const void* graph_mask = nullptr;
 };
 
+// ---- the model layer's entry points (model.cpp, train.cpp, mesh.cpp, config.cpp, diag.cpp), as c_api.cpp, manager.cpp and diag.cpp call them
+void set_error(const char* fmt, ...);      // the calling thread's mon_last_error text
+const char* last_error();
+int device_count(int* n);
+int physical_device(int logical, int* phys_out);
+void config_default(mon_config& c);
+int config_from_json(const char* path, mon_config& c);
+int stream_pool_reserve(int device, int n);
+int dataset_create(int device, int H, int W, float fx, float fy, float cx, float cy, uint32_t max_frames, int use_depth, Dataset** out);
+int dataset_add_frame(Dataset* d, uint32_t id, const uint8_t* rgb, int ch, int is_bgr, const uint8_t* inst, const float* depth, const float* Twc);
+int dataset_update_poses(Dataset* d, uint32_t first, uint32_t n, const float* Twc16s);
+int dataset_destroy(Dataset* d);
+int model_create(Dataset* ds, const mon_config& cfg, int class_id, const float* Tow, const float* amin, const float* amax, Model** out);
+int model_destroy(Model* m);
+int model_add_boxes(Model& m, const mon_frame_bbox* boxes, size_t n);
+int model_train(Model& m, int iters, float* loss, int stages);
+int model_render(Model& m, mon_frame_bbox box, const float* pose16, int pose_is_Toc, float* rgb, float* depth, float* mask, int dst_on_device);
+int model_density_grid(Model& m, int rx, int ry, int rz, float* out_host);
+int model_get_params(Model& m, int which, void* dst, size_t bytes);
+int model_set_params(Model& m, const float* master, size_t n);
+int model_set_backend(Model& m, int backend);
+int model_set_debug_dump(Model& m, int enable);
+int model_debug_read(Model& m, int which, void* dst, size_t bytes);
+int model_generate_mesh(Model& m, int res, float thresh, uint32_t* n_verts, uint32_t* n_indices);
+int model_mesh_counts(Model& m, uint32_t* n_verts, uint32_t* n_verts_real, uint32_t* n_indices);
+int model_get_mesh(Model& m, float* verts, float* normals, uint8_t* colors, uint32_t* indices, float* normals_raw, float* colors_f32, int try_only);
+int model_save_mesh(Model& m, const char* path);
+int model_mesh_generation(Model& m, uint64_t* gen);
+int model_copy_mesh(Model& m, uint32_t cap_verts, uint32_t cap_indices, float* verts, float* normals, uint8_t* colors, uint32_t* indices,
+                    uint32_t* n_verts, uint32_t* n_verts_real, uint32_t* n_indices, int try_only);
+int marching_cubes_host(int device, const float* density, int rx, int ry, int rz, float thresh, const float* amin, const float* amax,
+                        float* verts, float* normals_raw, uint32_t* indices, uint32_t cap_verts, uint32_t cap_indices, uint32_t* n_verts,
+                                uint32_t* n_verts_real, uint32_t* n_indices);
+int microbench(int device, int mode, int pattern, uint32_t n_entries, uint32_t n_ops, float* ms_out);
+// What was prepared ahead of the next iteration goes stale for one of three reasons (train.cpp, where the flags live); graph_too: a captured pair of
+// iterations goes as well
+enum : unsigned { kStaleRays = 1u, kStaleWeights = 2u, kStaleOccupancy = 4u };
+void model_mark_stale(Model& m, unsigned why, bool graph_too = false);
 int ensure_ema_current(Model& m);
 uint64_t next_weights_epoch();
 int model_set_render_skip(Model& m, int enable, float min_alpha);

@@ -1,4 +1,4 @@
-// model_internal.h -- what model.cpp, pose.cpp, scene.cpp and checkpoint.cpp need from each other and nobody else needs (c_api.cpp, manager.cpp and
+// model_internal.h -- what model.cpp, train.cpp, pose.cpp, scene.cpp and checkpoint.cpp need from each other and nobody else needs (c_api.cpp, manager.cpp and
 // diag.cpp go through model.h).
 #pragma once
 #include <atomic>
@@ -9,7 +9,6 @@
 
 namespace mon {
 
-void set_error(const char* fmt, ...);      // the calling thread's mon_last_error text
 #define HIPCHECK(expr)                                                                                         \
     do { hipError_t _e = (expr); if (_e != hipSuccess) {                                                       \
         set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); return MON_ERR_HIP; } } while (0)
@@ -74,6 +73,21 @@ template <class T, bool Pinned = false> struct DevBuf {
 };
 template <class T> using PinnedBuf = DevBuf<T, true>;
 
+// device memory that lives as long as the object (freed by model_destroy)
+template <class T> int dev_alloc(Model& m, T*& p, size_t n, bool zero = true) {
+    void* q = nullptr; const size_t bytes = (n ? n : 1) * sizeof(T);
+    HIPCHECK(hipMalloc(&q, bytes));
+    if (zero) HIPCHECK(hipMemset(q, 0, bytes));
+    m.allocs.push_back(q); p = (T*)q; return MON_OK;
+}
+// train.cpp: the device's training lanes (made with its dataset), the objects counted on them; a captured pair of iterations
+struct TrainLanes* lanes_get(int device);
+void lanes_objects_add(struct TrainLanes* t, int n);
+void drop_graph(Model& m);
+// profiling (model.cpp): HIP events on the train stream around each kernel class (mon_object_set_profiling) and a roctx range per phase (option roctx)
+struct ProfScope { Model& m; int cls; hipEvent_t a = nullptr, b = nullptr; struct Roctx* rx; ProfScope(Model& mm, int c); ~ProfScope(); };
+void collect_profile(Model& m);
+
 bool rskip_supported(const Model& m);          // the object runs on the fused kernels
 // the side's grid of `prm` (stamp `epoch`) on stream s: the cached one, or built through the training grid's kernels into `frag`, the side's fragment image
 // of the same weights; nullptr when the side has no grid buffers
@@ -82,8 +96,8 @@ int config_check(const mon_config& cfg);       // what mon_object_create rejects
 bool steps16_exact(const mon_config& cfg);     // model_init's rule for the step counters; a checkpoint records which one its object kept
 // init_params = false (model_load): the parameters are left for the caller to stream in -- nothing of table size is staged
 int model_create_impl(Dataset* ds, const mon_config& cfg, int class_id, const float* Tow, const float* amin, const float* amax, bool init_params, Model** out);
-int publish_snapshot(Model& m, bool force = true); int model_destroy(Model* mp);
-int model_add_boxes(Model& m, const mon_frame_bbox* boxes, size_t n);
+int publish_snapshot(Model& m, bool force = true);
+struct MeshState* mesh_state_create(int device); void model_mesh_free(Model& m);      // mesh.cpp
 void pose_ws_free(Model& m);                   // pose.cpp: the object's pose refinement scratch
 // pose.cpp: box i of a pose call names a frame the dataset holds and lies inside it; its pixels join `total` (at most 64 kPoseMaxRays).  `what`: the message
 // prefix ("pose", "scene pose")
