@@ -188,6 +188,30 @@ int mon_object_render_occupancy(mon_object* obj, int side, int dilated, uint32_t
  *                  sample-stream bits); side 1 and an object without an inference side or with nothing published yet */
 int mon_scene_render(mon_object* const* objs, size_t n_objs, int side, mon_frame_bbox rect, const float* Twc16,
                      float* rgb, float* depth, float* opacity, int32_t* instance);
+/* Scene probe: what mon_scene_render returns, at a list of sub-pixel image points under one or several camera poses, in one enqueue, plus the depth at
+ * which each ray is actually stopped (a feature-based front end's question: depth and object id at keypoints under a predicted pose; the reference has no
+ * such call; opt-in, new).
+ * Query i looks through pose Twc16s + 16 q[i].pose (column-major, camera to world) at image point (u, v) -- any finite position, inside the image or not.
+ * For each object j its ray is the one mon_scene_render builds for a pixel at (u, v), intersected with j's box; its 2S = 64 samples are that render's, with
+ * the jitter index key * 64 + k of j's own render stream; the same termination, render grid (when render skipping is on) and dead samples.  The lists are
+ * merged and composited exactly as mon_scene_render does it.  Outputs per query, host pointers:
+ *   rgb, depth, opacity, instance   as mon_scene_render defines them
+ *   hit_depth    = t_i / |camera ray| of the first merged sample i with 1 - T_{i+1} > 0.5 (the transmittance the composite carries after it), else 0
+ *   hit_instance = the index in objs of that sample's object, else -1
+ * hit_depth is a sample distance, not interpolated inside the sample's interval; unlike depth (sum w t) it does not smear across an occlusion edge.
+ * Bit rule: a query with integer-valued u = x, v = y and key = (y - rect.y) * rect.w + (x - rect.x) returns in rgb, depth, opacity and instance the bits
+ * mon_scene_render(objs, n_objs, side, rect, Twc, ...) returns for that pixel.  The six outputs of a query do not depend on the other queries of the call,
+ * on its place in the list, on the number of poses or on how the list is cut into passes (16 384 queries each); no atomics: equal arguments, equal bits.
+ * key: any stable per-keypoint number below 2^26, or the pixel index when the result is to be compared with a render.
+ * Read-only, side as in mon_scene_render (0: the caller serialises against training; 1: the snapshots pinned once for the whole call, callable while the
+ * objects train).  Nothing about any object changes beyond building a stale render grid, as the scene render does.  Returns:
+ *   MON_ERR_ARG    objs or an element, Twc16s, q, rgb or depth NULL; n_objs 0 or above 256; n_poses outside 1..4096; n_q outside 1..2^22; a pose index
+ *                  >= n_poses; a key >= 2^26; a non-finite u, v or pose matrix; side not 0 / 1; objects on different logical devices or with different
+ *                  intrinsics -- all before any device work
+ *   MON_ERR_STATE  as mon_scene_render */
+typedef struct mon_scene_query { uint32_t pose; uint32_t key; float u, v; } mon_scene_query;   /* 16 bytes */
+int mon_scene_probe(mon_object* const* objs, size_t n_objs, int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q,
+                    float* rgb, float* depth, float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance);
 /* Object pose refinement through the trained field (iNeRF-style): align the object with observed frames by following the gradient of a photometric,
  * silhouette and depth error with respect to the 6-DoF pose Tow.
  * Objective.  obs names frames of the object's dataset (FrameId) and pixel boxes inside them; the target of a pixel is that frame's rgb c*, its instance map
@@ -551,6 +575,11 @@ int mon_online_render(mon_online* mgr, size_t idx, mon_frame_bbox box, const flo
 /* mon_scene_render(side 1) of every object of the manager that has published weights (the others are left out; none: the background); instance = the
  * manager's object index.  A viewer's call: safe while the objects train.  MON_ERR_STATE when those objects span more than one device (a follow-up). */
 int mon_online_render_scene(mon_online* mgr, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity, int32_t* instance);
+/* mon_scene_probe(side 1) of every object of the manager that has published weights, chosen as mon_online_render_scene chooses them; both instance outputs
+ * hold the manager's object indices.  A front end's call, safe while the objects train.  MON_ERR_STATE when no object has published yet or the objects
+ * span more than one device. */
+int mon_online_probe_scene(mon_online* mgr, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q,
+                           float* rgb, float* depth, float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance);
 /* mon_object_refine_pose(side 1) of object idx: its published snapshot, on the inference stream -- safe while the manager trains it.  MON_ERR_STATE while
  * nothing of it has been published. */
 int mon_online_refine_pose(mon_online* mgr, size_t idx, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, float* Tow16_inout,

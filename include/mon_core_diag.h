@@ -61,6 +61,16 @@ int mon_debug_scene_samples(mon_object* const* objs, size_t n_objs, int side, mo
 int mon_debug_scene_composite(int device, uint32_t n_rays, uint32_t n_lists, const float* t, const float* alpha, const float* rgb, const uint32_t* count,
                               const float* dn, float* out_rgb, float* out_depth, float* out_opacity, int32_t* out_instance);
 
+/* Scene probe (mon_scene_probe), its own two kernels one at a time.  mon_debug_scene_probe_rays: the ray rows k_scene_probe_rays writes for object k of that
+ * probe call (the same arguments first), rows[n_q][10] = o[3], d[3] (object frame), t0, t1, flag (1: the ray hits k's box), dn = |camera ray|; a row that
+ * misses the box holds flag 0, dn and zeros.  mon_debug_scene_probe_composite: k_scene_probe_composite on caller lists, the arguments of
+ * mon_debug_scene_composite plus the two hit outputs (hit_instance = list index). */
+int mon_debug_scene_probe_rays(mon_object* const* objs, size_t n_objs, int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q,
+                               size_t k, float* rows);
+int mon_debug_scene_probe_composite(int device, uint32_t n_rays, uint32_t n_lists, const float* t, const float* alpha, const float* rgb, const uint32_t* count,
+                                    const float* dn, float* out_rgb, float* out_depth, float* out_opacity, int32_t* out_instance, float* out_hit_depth,
+                                    int32_t* out_hit_instance);
+
 /* Pose refinement (mon_object_pose_loss, the same arguments): per drawn ray of that evaluation (rays_per_iter of them, or every pixel of every box in box
  * order), its 2S = 64 samples: x[ray][64][3] the positions in the object frame, raw[ray][64][4] the network's raw outputs, dldx[ray][64][3] = dL/dx_k in the
  * object frame (the 1/N of the mean included).  Samples not evaluated (a missed box, the second tile behind the early cut) hold 0 (x: the position it would

@@ -59,6 +59,14 @@ class WindowParams(C.Structure):
     _fields_ = [("n_fixed_frames", C.c_uint32), ("refine_objects", C.c_int32), ("lr_obj_trans", C.c_float), ("lr_obj_rot", C.c_float)]
 
 
+class SceneQuery(C.Structure):
+    """mon_scene_query (include/mon_core.h): one probe query -- the pose it looks through, its jitter key, the image point (u, v)."""
+    _fields_ = [("pose", C.c_uint32), ("key", C.c_uint32), ("u", C.c_float), ("v", C.c_float)]
+
+
+SCENE_QUERY_DTYPE = np.dtype([("pose", np.uint32), ("key", np.uint32), ("u", np.float32), ("v", np.float32)])
+
+
 class RelocResult(C.Structure):
     """mon_reloc_result (include/mon_core.h): which candidate won, whether its refined pose did, and the scores S[0], S[best], F[winner]."""
     _fields_ = [("best_candidate", C.c_uint32), ("refined", C.c_uint32), ("score_candidate0", C.c_float), ("score_best_candidate", C.c_float),
@@ -179,6 +187,10 @@ _SIGS = {
     "mon_object_render_occupancy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "mon_scene_render": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, MonBBox, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_online_render_scene": (C.c_int, [C.c_void_p, MonBBox, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_scene_probe": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_online_probe_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p]),
     "mon_pose_refine_default": (C.c_int, [C.POINTER(PoseRefineParams)]),
     "mon_object_pose_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32,
             C.POINTER(C.c_float), C.c_void_p]),
@@ -243,6 +255,9 @@ _DIAG_SIGS = {
     "mon_debug_scene_samples": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, MonBBox, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_debug_scene_composite": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_debug_scene_probe_rays": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "mon_debug_scene_probe_composite": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_debug_pose_samples": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32, C.c_void_p,
             C.c_void_p, C.c_void_p]),
     "mon_debug_scene_pose_samples": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32,
@@ -873,6 +888,13 @@ class OnlineManager:
         _check(lib().mon_online_render_scene(self.h, box, _p(pose), *[_p(a) for a in out]))
         return out
 
+    def probe_scene(self, queries, Twc16s):
+        """mon_online_probe_scene: probe_scene on side 1 over every object with published weights (a front end's call, safe while they train); both
+        instance outputs hold the manager's object indices."""
+        q, poses, out = _probe_args(queries, Twc16s)
+        _check(lib().mon_online_probe_scene(self.h, _p(poses), poses.shape[0], _p(q), q.shape[0], *[_p(a) for a in out]))
+        return out
+
     def save_map(self, path):
         """mon_online_save_map: <path>/map.txt + one checkpoint per object, each under its own model lock (safe while they train; not one global cut)."""
         _check(lib().mon_online_save_map(self.h, os.fsencode(path)))
@@ -999,6 +1021,54 @@ def render_scene(objects, rect, Twc16, side=0):
     side 0 the train-side weights, 1 the published snapshots.  Returns (rgb HxWx3, depth HxW, opacity HxW, instance HxW int32: index into objects, -1)."""
     box, out = _scene_outputs(rect); pose = np.ascontiguousarray(Twc16, np.float32)
     _check(lib().mon_scene_render(_handles(objects), len(objects), int(side), box, _p(pose), *[_p(a) for a in out]))
+    return out
+
+
+def scene_queries(pose, key, u, v):
+    """An array of mon_scene_query (SCENE_QUERY_DTYPE) from broadcastable pose indices, keys and image points."""
+    pose, key, u, v = np.broadcast_arrays(np.asarray(pose), np.asarray(key), np.asarray(u), np.asarray(v))
+    q = np.empty(pose.size, SCENE_QUERY_DTYPE)
+    q["pose"] = pose.reshape(-1); q["key"] = key.reshape(-1); q["u"] = u.reshape(-1); q["v"] = v.reshape(-1)
+    return q
+
+
+def rect_queries(rect, pose=0):
+    """Every pixel of rect = (FrameId, x, y, h, w) as a query, row-major, key = the pixel index: the queries whose probe equals render_scene of the rect."""
+    _, x, y, h, w = (int(a) for a in rect)
+    yy, xx = np.mgrid[0:h, 0:w]
+    return scene_queries(pose, yy * w + xx, x + xx, y + yy)
+
+
+def _probe_args(queries, Twc16s):
+    q = np.ascontiguousarray(queries, SCENE_QUERY_DTYPE).reshape(-1); poses = np.ascontiguousarray(Twc16s, np.float32).reshape(-1, 16); n = q.shape[0]
+    return q, poses, (np.empty((n, 3), np.float32), np.empty(n, np.float32), np.empty(n, np.float32), np.empty(n, np.int32), np.empty(n, np.float32),
+                      np.empty(n, np.int32))
+
+
+def probe_scene(objects, queries, Twc16s, side=0):
+    """mon_scene_probe: what render_scene returns at the queries' sub-pixel image points (SCENE_QUERY_DTYPE: pose index into Twc16s (n_poses, 16), key, u, v),
+    plus the first-hit depth and object.  Returns (rgb (n, 3), depth, opacity, instance, hit_depth, hit_instance)."""
+    q, poses, out = _probe_args(queries, Twc16s)
+    _check(lib().mon_scene_probe(_handles(objects), len(objects), int(side), _p(poses), poses.shape[0], _p(q), q.shape[0], *[_p(a) for a in out]))
+    return out
+
+
+def scene_probe_rays(objects, queries, Twc16s, k, side=0):
+    """mon_debug_scene_probe_rays: object k's ray rows of that probe, (n, 10) = o[3], d[3], t0, t1, flag, dn."""
+    q, poses, _ = _probe_args(queries, Twc16s); rows = np.empty((q.shape[0], 10), np.float32)
+    _check(diag_lib().mon_debug_scene_probe_rays(_handles(objects), len(objects), int(side), _p(poses), poses.shape[0], _p(q), q.shape[0], int(k), _p(rows)))
+    return rows
+
+
+def scene_probe_composite(t, alpha, rgb, count, dn, device=0):
+    """mon_debug_scene_probe_composite: the probe's composite kernel on lists laid out as scene_composite's.  Returns (rgb (n_rays, 3), depth, opacity,
+    instance, hit_depth, hit_instance)."""
+    t = np.ascontiguousarray(t, np.float32); L, R = t.shape[:2]
+    a = np.ascontiguousarray(alpha, np.float32).reshape(L, R, 64); c = np.ascontiguousarray(rgb, np.float32).reshape(L, R, 64, 3)
+    n = np.ascontiguousarray(count, np.uint32).reshape(L, R); d = np.ascontiguousarray(dn, np.float32).reshape(R)
+    out = (np.empty((R, 3), np.float32), np.empty(R, np.float32), np.empty(R, np.float32), np.empty(R, np.int32), np.empty(R, np.float32),
+           np.empty(R, np.int32))
+    _check(diag_lib().mon_debug_scene_probe_composite(int(device), R, L, _p(t), _p(a), _p(c), _p(n), _p(d), *[_p(o) for o in out]))
     return out
 
 

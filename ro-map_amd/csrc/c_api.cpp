@@ -116,6 +116,15 @@ int mon_scene_render(mon_object* const* objs, size_t n_objs, int side, mon_frame
     for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
     return scene_render(ms.data(), n_objs, side, rect, Twc16, rgb, depth, opacity, instance, nullptr, nullptr);
 }
+int mon_scene_probe(mon_object* const* objs, size_t n_objs, int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, float* rgb,
+        float* depth, float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance) {
+    REQUIRE(objs, "objs");
+    { const int rc = scene_probe_check(side, Twc16s, n_poses, q, n_q, rgb, depth); if (rc) return rc; }
+    if (n_objs == 0 || n_objs > kSceneMaxLists) { set_error("scene_probe: %zu objects (1 to %u)", n_objs, kSceneMaxLists); return MON_ERR_ARG; }
+    std::vector<Model*> ms(n_objs);
+    for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
+    return scene_probe(ms.data(), n_objs, side, Twc16s, n_poses, q, n_q, rgb, depth, opacity, instance, hit_depth, hit_instance, nullptr, nullptr);
+}
 int mon_pose_refine_default(mon_pose_refine_params* p) {
     REQUIRE(p, "params");
     p->iters = 100; p->rays_per_iter = 4096; p->lr_trans = 2e-3f; p->lr_rot = 4e-3f;

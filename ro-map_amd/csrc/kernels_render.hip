@@ -16,7 +16,9 @@ namespace mon {
 // rgb = t [ray][2S], depth = {alpha, r, g, b} [ray][2S] (float4), stats = the ray's sample count [ray] (0: missed the box; 32 per tile evaluated); mask is
 // unused.  The list stops where THIS object's transmittance ends the ray (the scene's is never larger).  A dead tile is emitted with alpha 0 and colour 0.
 // The skip counters are not touched.
-template <int EPAD, int W, int NH, bool OCC = false, bool EMIT = false>
+// KEYED (the scene probe, mon_scene_probe; with EMIT): the ray's jitter indices are key[ray] * 2S + k in place of idx_base + ray * 2S + k; mask = the keys
+// (uint32 [ray]), idx_base is unused.
+template <int EPAD, int W, int NH, bool OCC = false, bool EMIT = false, bool KEYED = false>
 __global__ void __launch_bounds__(256) k_fused_render(FusedArgs a, uint32_t n_rays, uint32_t idx_base, float* __restrict__ rgb, float* __restrict__ depth,
         float* __restrict__ mask, uint32_t* __restrict__ stats) {
     using S = FusedShape<EPAD, W, NH>;
@@ -38,12 +40,13 @@ __global__ void __launch_bounds__(256) k_fused_render(FusedArgs a, uint32_t n_ra
             const float t0 = a.b.ray_t0[ray], t1 = a.b.ray_t1[ray], dtr = (t1 - t0) / (float)S2;
             float Tc = 1.f, r0 = 0.f, r1 = 0.f, r2 = 0.f, dep = 0.f, tlast = 0.f;
             uint32_t lb0 = ~0u, lb1 = ~0u;                                              // (OCC, uniform) the ray's live samples of tile 0 / 1
+            const uint32_t jit0 = KEYED ? reinterpret_cast<const uint32_t*>(mask)[ray] * S2 : idx_base + ray * S2;      // the ray's first jitter index
             if constexpr (OCC) {
                 // both tiles up front: the count covers every sample in the box, evaluated or behind an opaque first tile (as on the tile path)
 #pragma unroll
                 for (uint32_t tile = 0; tile < 2u; ++tile) {
                     const uint32_t k = tile * 32u + (uint32_t)n;
-                    const float t = fmaf(dtr, (float)k + render_rand(a.oc, idx_base + ray * S2 + k), t0);
+                    const float t = fmaf(dtr, (float)k + render_rand(a.oc, jit0 + k), t0);
                     float x[3];
 #pragma unroll
                     for (int d = 0; d < 3; ++d) { const float p = fmaf(t, a.b.ray_d[3 * ray + d], a.b.ray_o[3 * ray + d]);
@@ -56,7 +59,7 @@ __global__ void __launch_bounds__(256) k_fused_render(FusedArgs a, uint32_t n_ra
             for (uint32_t tile = 0; tile < 2u; ++tile) {
                 if (Tc < kTransmittanceEps) break;
                 const uint32_t k = tile * 32u + (uint32_t)n;
-                const float t = fmaf(dtr, (float)k + render_rand(a.oc, idx_base + ray * S2 + k), t0);
+                const float t = fmaf(dtr, (float)k + render_rand(a.oc, jit0 + k), t0);
                 float x[3];
 #pragma unroll
                 for (int d = 0; d < 3; ++d) { const float p = fmaf(t, a.b.ray_d[3 * ray + d], a.b.ray_o[3 * ray + d]);
@@ -170,13 +173,18 @@ static void fused_render_t(hipStream_t s, const FusedArgs& a, uint32_t n_rays, u
 }
 
 template <int EPAD, int W, int NH>
-static void fused_emit_t(hipStream_t s, const FusedArgs& a, uint32_t n_rays, uint32_t idx_base, float* t, float* attr, uint32_t* cnt) {
+static void fused_emit_t(hipStream_t s, const FusedArgs& a, uint32_t n_rays, uint32_t idx_base, float* t, float* attr, uint32_t* cnt, const uint32_t* keys) {
     using S = FusedShape<EPAD, W, NH>;
     const uint32_t smem = S::FRAG_BYTES + S::LT_BYTES;
     uint32_t grid = (n_rays + 3) / 4; if (grid > 2048u) grid = 2048u;
     if (a.keep_zero & 1u) hipLaunchKernelGGL((k_build_frag_image<EPAD, W, NH>), dim3((S::F_WOT * 512 + 255) / 256), dim3(256), 0, s, a.params, a.nd.L,
             const_cast<uint16_t*>(a.frag_image), (const DevState*)nullptr);
-    if (a.occ_bits) hipLaunchKernelGGL((k_fused_render<EPAD, W, NH, true, true>), dim3(grid), dim3(256), smem, s, a, n_rays, idx_base, t, attr, nullptr, cnt);
+    float* kp = reinterpret_cast<float*>(const_cast<uint32_t*>(keys));                 // (KEYED reads its keys through the unused mask pointer)
+    if (keys) {
+        if (a.occ_bits) hipLaunchKernelGGL((k_fused_render<EPAD, W, NH, true, true, true>), dim3(grid), dim3(256), smem, s, a, n_rays, 0u, t, attr, kp, cnt);
+        else hipLaunchKernelGGL((k_fused_render<EPAD, W, NH, false, true, true>), dim3(grid), dim3(256), smem, s, a, n_rays, 0u, t, attr, kp, cnt);
+    }
+    else if (a.occ_bits) hipLaunchKernelGGL((k_fused_render<EPAD, W, NH, true, true>), dim3(grid), dim3(256), smem, s, a, n_rays, idx_base, t, attr, nullptr, cnt);
     else hipLaunchKernelGGL((k_fused_render<EPAD, W, NH, false, true>), dim3(grid), dim3(256), smem, s, a, n_rays, idx_base, t, attr, nullptr, cnt);
 }
 
@@ -203,52 +211,9 @@ __global__ void __launch_bounds__(64) k_scene_composite(uint32_t n_rays, uint32_
     for (uint32_t ray = blockIdx.x; ray < n_rays; ray += gridDim.x) {
         uint32_t na, n_tot;
         scene_merge_lists(ray, n_lists, cap, tl, cnt, lane, s_perm, s_id, s_c, s_tf, s_tl, s_w, na, n_tot);
-        // ---- front-to-back composite of the merged sequence
-        float Tc = 1.f, r0 = 0.f, r1 = 0.f, r2 = 0.f, dep = 0.f;
-        for (uint32_t base = 0; base < n_tot; base += 64u) {
-            const uint32_t p = base + (uint32_t)lane;
-            float tv = 0.f, al = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f; uint32_t a = ~0u;
-            if (p < n_tot) {
-                const uint32_t e = s_perm[p];
-                if ((e >> 6) < na) {
-                    a = e >> 6;
-                    const size_t idx = ((size_t)s_id[a] * cap + ray) * L2S + (e & 63u);
-                    const float4 v = attr[idx]; tv = tl[idx]; al = v.x; c0 = v.y; c1 = v.z; c2 = v.w;
-                }
-            }
-            const float omv = 1.f - al;
-            const float sc = scan_mul32(omv), lo = sc * Tc, mid = lane_bcast(lo, 31);
-            const float incl = lane < 32 ? lo : sc * mid;                              // (the second half-wave carries the first's transmittance)
-            float T = lane_prev(incl, Tc); if (lane == 0) T = Tc; if (lane == 32) T = mid;
-            const bool active = T >= kTransmittanceEps;
-            const unsigned long long am = __ballot(active);
-            const int nact = __popcll(am);
-            const float wgt = active ? al * T : 0.f;
-            const float x0 = scan_add32(wgt * c0), x1 = scan_add32(wgt * c1), x2 = scan_add32(wgt * c2), xd = scan_add32(wgt * tv);
-            r0 += lane_bcast(x0, 31); r1 += lane_bcast(x1, 31); r2 += lane_bcast(x2, 31); dep += lane_bcast(xd, 31);
-            r0 += lane_bcast(x0, 63); r1 += lane_bcast(x1, 63); r2 += lane_bcast(x2, 63); dep += lane_bcast(xd, 63);
-            // per-list weight sums: one reduction per list present in the block
-            unsigned long long pend = __ballot(a != ~0u && wgt != 0.f);
-            while (pend) {
-                const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)a, (int)__builtin_ctzll(pend));
-                const bool mine = a == a0;
-                const float xs = scan_add32(mine ? wgt : 0.f);
-                const float sum = lane_bcast(xs, 31) + lane_bcast(xs, 63);
-                if (lane == 0) s_w[a0] += sum;
-                pend &= ~__ballot(mine);
-            }
-            Tc = nact > 0 ? lane_bcast(incl, nact > 0 ? nact - 1 : 0) : Tc;
-            if (nact < 64) break;                                                      // transmittance ran out inside this block
-        }
-        if (lane == 0) {
-            const float op = 1.f - Tc;
-            out_rgb[3 * (size_t)ray] = r0 + Tc; out_rgb[3 * (size_t)ray + 1] = r1 + Tc; out_rgb[3 * (size_t)ray + 2] = r2 + Tc;
-            out_depth[ray] = op > 0.5f ? dep / dn[ray] : 0.f;
-            out_opacity[ray] = op;
-            int32_t inst = -1;
-            if (op > 0.5f) { float best = -1.f; for (uint32_t a = 0; a < na; ++a) if (s_w[a] > best) { best = s_w[a]; inst = (int32_t)s_id[a]; } }
-            out_instance[ray] = inst;
-        }
+        SceneWalk w;
+        scene_composite_walk<false>(ray, cap, na, n_tot, tl, attr, lane, s_perm, s_id, s_w, w);
+        if (lane == 0) scene_composite_store(ray, na, s_id, s_w, w, dn, out_rgb, out_depth, out_opacity, out_instance);
         __syncthreads();
     }
 }
@@ -264,10 +229,11 @@ void launch_fused_render(hipStream_t s, const LevelFast& lt, const NetDims& nd, 
 
 
 void launch_fused_render_emit(hipStream_t s, const LevelFast& lt, const NetDims& nd, const uint16_t* params, const BatchPtrs& b, const ObjectConst& oc,
-        uint32_t n_rays, uint32_t idx_base, float* t, float* attr, uint32_t* cnt, uint16_t* frag_image, int build_image, const uint32_t* skip_bits) {
+        uint32_t n_rays, uint32_t idx_base, float* t, float* attr, uint32_t* cnt, uint16_t* frag_image, int build_image, const uint32_t* skip_bits,
+        const uint32_t* keys) {
     FusedArgs a{ lt, nd, oc, b, params, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, frag_image, build_image ? 1u : 0u };
     a.occ_bits = skip_bits;
-    MON_FUSED_DISPATCH(fused_emit_t, s, a, n_rays, idx_base, t, attr, cnt);
+    MON_FUSED_DISPATCH(fused_emit_t, s, a, n_rays, idx_base, t, attr, cnt, keys);
 }
 
 void launch_scene_composite(hipStream_t s, uint32_t n_rays, uint32_t n_lists, uint32_t cap, const float* t, const float* attr, const uint32_t* cnt,

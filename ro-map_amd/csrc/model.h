@@ -332,9 +332,18 @@ void launch_build_frag_image(hipStream_t s, const uint16_t* params, const NetDim
 constexpr uint32_t kSceneListLen = 64, kSceneMaxLists = 256;
 constexpr uint32_t scene_composite_lds(uint32_t n_lists) { return n_lists * (2u * kSceneListLen + 20u); }
 void launch_fused_render_emit(hipStream_t s, const LevelFast& lt, const NetDims& nd, const uint16_t* params, const BatchPtrs& b, const ObjectConst& oc,
-        uint32_t n_rays, uint32_t idx_base, float* t, float* attr, uint32_t* cnt, uint16_t* frag_image, int build_image, const uint32_t* skip_bits);
+        uint32_t n_rays, uint32_t idx_base, float* t, float* attr, uint32_t* cnt, uint16_t* frag_image, int build_image, const uint32_t* skip_bits,
+        const uint32_t* keys = nullptr);
 void launch_scene_composite(hipStream_t s, uint32_t n_rays, uint32_t n_lists, uint32_t cap, const float* t, const float* attr, const uint32_t* cnt,
         const float* dn, float* rgb, float* depth, float* opacity, int32_t* instance);
+// Scene probe (mon_scene_probe, kernels_scene_probe.hip).  k_scene_probe_rays: one object's ray rows of n queries (their poses from `poses`; keys, where
+// given, receives the queries' keys); the keyed emit (launch_fused_render_emit with keys: jitter index keys[ray] * 2S + k, idx_base unused);
+// k_scene_probe_composite: k_scene_composite plus the depth and list of the first sample after which 1 - T > 0.5 (0 and -1: none).
+constexpr uint32_t kSceneProbeMaxPoses = 4096, kSceneProbeMaxQueries = 1u << 22, kSceneProbeMaxKey = 1u << 26;
+void launch_scene_probe_rays(hipStream_t s, const BatchPtrs& b, const Intrinsics& K, const ObjectConst& oc, const mon_scene_query* q, const float* poses,
+        uint32_t* keys, uint32_t n);
+void launch_scene_probe_composite(hipStream_t s, uint32_t n_rays, uint32_t n_lists, uint32_t cap, const float* t, const float* attr, const uint32_t* cnt,
+        const float* dn, float* rgb, float* depth, float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance);
 // Pose refinement (mon_object_pose_loss / mon_object_refine_pose, kernels_pose.hip).  k_pose_rays: one record of 4 float4 per drawn ray from the pose in
 // device memory (pose[16], world -> object); k_pose_grad<shape>: loss and position gradient, one partial row of 8 floats {g, x x g, loss, 0} per workgroup
 // (pose_grad_grid of them); k_pose_update: the rows summed in a fixed order, x inv_n -> out[8 * it] = {loss, grad6, 0}, optionally the Adam step on pose.
@@ -651,6 +660,13 @@ void tile_points_forward(Model& m, TileWs& ws, hipStream_t s, uint32_t n);
 struct SceneDump { uint32_t list; float* t; float* alpha; float* rgb; uint32_t* count; };
 int scene_render(Model* const* ms, size_t n, int side, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity, int32_t* instance,
                  const int32_t* ids, const SceneDump* dump);
+// Scene probe (mon_scene_probe): scene_render's conventions for side and ids (applied to both instance outputs).  scene_probe_check: every MON_ERR_ARG
+// that needs no object, no device work.  dump (mon_debug_scene_probe_rays, may be nullptr) = object k's ray rows per query, host array [n_q][10]:
+// o[3], d[3], t0, t1, flag, dn (a row that missed the box: flag 0, dn, the rest 0).
+struct SceneProbeDump { uint32_t k; float* rows; };
+int scene_probe_check(int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, const float* rgb, const float* depth);
+int scene_probe(Model* const* ms, size_t n, int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, float* rgb, float* depth,
+                float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance, const int32_t* ids, const SceneProbeDump* dump);
 bool model_has_snapshot(Model& m);      // the object has an inference side and has published weights
 // Pose refinement: iters < 0 = one evaluation (mon_object_pose_loss: loss, grad6, jitter / draws of `iteration`), else iters Adam steps from Tow16
 // (mon_object_refine_pose: the final pose into pose_out, loss_trace[iters + 1] may be nullptr).  dump (mon_debug_pose_samples, may be nullptr): per drawn ray

@@ -31,6 +31,16 @@ static int scene_state_check(const char* what, Model* const* ms, size_t n, int s
     }
     return MON_OK;
 }
+// what scene_render and scene_probe ask of side and objects: every MON_ERR_ARG, then every MON_ERR_STATE, no device work
+static int scene_objects_check(const char* what, Model* const* ms, size_t n, int side) {
+    if (side != 0 && side != 1) { set_error("%s: side must be 0 or 1", what); return MON_ERR_ARG; }
+    if (n == 0) { set_error("%s: no objects", what); return MON_ERR_ARG; }
+    if (n > kSceneMaxLists) { set_error("%s: %zu objects (at most %u)", what, n, kSceneMaxLists); return MON_ERR_ARG; }
+    { const int rc = scene_objects_present(what, ms, n); if (rc) return rc; }
+    for (size_t j = 0; j < n; ++j) { const int rc = scene_same_camera(what, *ms[0], *ms[j], j); if (rc) return rc; }
+    int Lmax = 0;
+    return scene_state_check(what, ms, n, side, Lmax);
+}
 
 // ---- entering a side of a scene: the weights every object is read from, their stamps, the stream of the call.  Side 1: the shared inference stream under
 // its device lock, every object's snapshot pinned.  Side 0: the train side as model_render picks it (EMA once trained, brought up to date), object 0's train
@@ -77,31 +87,32 @@ struct SceneWs {
     std::mutex mu;
     DevBuf<float> t, attr; DevBuf<uint32_t> cnt;                                  // [lists][cap][kSceneListLen] t, float4 attr; [lists][cap]
     DevBuf<float> out; PinnedBuf<float> h_out;                                    // rgb 3n | depth n | opacity n | instance n (int32)
+    DevBuf<mon_scene_query> q; DevBuf<float> poses; DevBuf<uint32_t> keys;        // scene_probe: the queries, the poses [n_poses][16], a pass's keys [cap]
     std::vector<hipEvent_t> ev;
 };
+// what each object renders with on a side; the render grids are the objects' own per-side caches, built if stale (their skip counters stay as they are)
+struct SceneSrc { BatchPtrs* b; uint16_t* frag; const uint32_t* bits; };
+static std::vector<SceneSrc> scene_sources(Model* const* ms, size_t n, int side, const SceneSide& sd) {
+    std::vector<SceneSrc> src(n);
+    for (size_t j = 0; j < n; ++j) {
+        Model& m = *ms[j]; RenderSkipSide& rs = side == 1 ? m.infer->rskip : m.rskip;
+        src[j].b = side == 1 ? &m.infer->rb : &m.B; src[j].frag = side == 1 ? m.infer->frag : m.d_frag_render;
+        src[j].bits = m.rskip_on.load() != 0 ? rskip_grid(m, rs, sd.s, m.rskip_alpha.load(), sd.prm[j], sd.epoch[j], src[j].frag) : nullptr;
+    }
+    return src;
+}
 int scene_render(Model* const* ms, size_t n, int side, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity, int32_t* instance,
                  const int32_t* ids, const SceneDump* dump) {
     if (!ms || n == 0 || !Twc16 || !rgb || !depth || rect.w == 0 || rect.h == 0) { set_error("scene_render: null or empty argument"); return MON_ERR_ARG; }
-    if (side != 0 && side != 1) { set_error("scene_render: side must be 0 or 1"); return MON_ERR_ARG; }
-    if (n > kSceneMaxLists) { set_error("scene_render: %zu objects (at most %u)", n, kSceneMaxLists); return MON_ERR_ARG; }
-    { const int rc = scene_objects_present("scene_render", ms, n); if (rc) return rc; }
+    { const int rc = scene_objects_check("scene_render", ms, n, side); if (rc) return rc; }
     const Intrinsics K = ms[0]->ds->K; const int device = ms[0]->device;
-    for (size_t j = 0; j < n; ++j) { const int rc = scene_same_camera("scene_render", *ms[0], *ms[j], j); if (rc) return rc; }
-    { int Lmax = 0; const int rc = scene_state_check("scene_render", ms, n, side, Lmax); if (rc) return rc; }
     HIPCHECK(use_device(device));
     const uint32_t n_pix = rect.w * rect.h, cap = std::min(n_pix, kRenderChunkRays), L = (uint32_t)n;
     Mat4 pose; std::memcpy(pose.m, Twc16, 64);
     SceneWs& ws = side_ws<SceneWs>(device, side);
     SceneSide sd; { const int rc = sd.enter(ms, n, side, ws.mu, ws.ev); if (rc) return rc; }
     const hipStream_t s = sd.s;
-    // what each object renders with on this side; the render grids are the objects' own per-side caches, built if stale (their skip counters stay as they are)
-    struct Src { BatchPtrs* b; uint16_t* frag; const uint32_t* bits; };
-    std::vector<Src> src(n);
-    for (size_t j = 0; j < n; ++j) {
-        Model& m = *ms[j]; RenderSkipSide& rs = side == 1 ? m.infer->rskip : m.rskip;
-        src[j].b = side == 1 ? &m.infer->rb : &m.B; src[j].frag = side == 1 ? m.infer->frag : m.d_frag_render;
-        src[j].bits = m.rskip_on.load() != 0 ? rskip_grid(m, rs, s, m.rskip_alpha.load(), sd.prm[j], sd.epoch[j], src[j].frag) : nullptr;
-    }
+    const std::vector<SceneSrc> src = scene_sources(ms, n, side, sd);
     // workspace (grow-only; nothing of it is in flight: every user synchronised before unlocking)
     const size_t need_lists = (size_t)L * cap;
     {   int rc;
@@ -147,6 +158,88 @@ int scene_render(Model* const* ms, size_t n, int side, mon_frame_bbox rect, cons
             if (dump->rgb) for (int c = 0; c < 3; ++c) dump->rgb[3 * i + c] = d_attr[4 * i + 1 + c];
         }
         if (dump->count) std::memcpy(dump->count, d_cnt.data(), 4 * (size_t)n_pix);
+    }
+    return MON_OK;
+}
+
+// ---- scene probe (mon_scene_probe): the scene render's chain over a list of sub-pixel queries under several poses.  Passes of at most kRenderChunkRays
+// queries in the render's list workspace; per pass and object k_scene_probe_rays + the keyed emit, then k_scene_probe_composite.  Everything is enqueued at
+// once; the eight output rows go home through the pinned staging (rgb 3n | depth | opacity | instance | hit_depth | hit_instance), one synchronisation.
+int scene_probe_check(int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, const float* rgb, const float* depth) {
+    if (!Twc16s || !q || !rgb || !depth) { set_error("scene_probe: null argument"); return MON_ERR_ARG; }
+    if (side != 0 && side != 1) { set_error("scene_probe: side must be 0 or 1"); return MON_ERR_ARG; }
+    if (n_poses == 0 || n_poses > kSceneProbeMaxPoses) { set_error("scene_probe: %zu poses (1 to %u)", n_poses, kSceneProbeMaxPoses); return MON_ERR_ARG; }
+    if (n_q == 0 || n_q > kSceneProbeMaxQueries) { set_error("scene_probe: %zu queries (1 to %u)", n_q, kSceneProbeMaxQueries); return MON_ERR_ARG; }
+    for (size_t k = 0; k < 16 * n_poses; ++k) if (!std::isfinite(Twc16s[k])) { set_error("scene_probe: pose %zu is not finite", k / 16); return MON_ERR_ARG; }
+    for (size_t i = 0; i < n_q; ++i) {
+        if (q[i].pose >= n_poses) { set_error("scene_probe: query %zu names pose %u of %zu", i, q[i].pose, n_poses); return MON_ERR_ARG; }
+        if (q[i].key >= kSceneProbeMaxKey) { set_error("scene_probe: query %zu has key %u (below %u)", i, q[i].key, kSceneProbeMaxKey); return MON_ERR_ARG; }
+        if (!std::isfinite(q[i].u) || !std::isfinite(q[i].v)) { set_error("scene_probe: query %zu is not finite", i); return MON_ERR_ARG; }
+    }
+    return MON_OK;
+}
+int scene_probe(Model* const* ms, size_t n, int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, float* rgb, float* depth,
+                float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance, const int32_t* ids, const SceneProbeDump* dump) {
+    if (!ms) { set_error("scene_probe: null argument"); return MON_ERR_ARG; }
+    { const int rc = scene_probe_check(side, Twc16s, n_poses, q, n_q, rgb, depth); if (rc) return rc; }
+    { const int rc = scene_objects_check("scene_probe", ms, n, side); if (rc) return rc; }
+    if (dump && dump->k >= n) { set_error("scene_probe: dump of object %u of %zu", dump->k, n); return MON_ERR_ARG; }
+    const Intrinsics K = ms[0]->ds->K; const int device = ms[0]->device;
+    HIPCHECK(use_device(device));
+    const uint32_t nq = (uint32_t)n_q, cap = std::min(nq, kRenderChunkRays), L = (uint32_t)n;
+    SceneWs& ws = side_ws<SceneWs>(device, side);
+    SceneSide sd; { const int rc = sd.enter(ms, n, side, ws.mu, ws.ev); if (rc) return rc; }
+    const hipStream_t s = sd.s;
+    const std::vector<SceneSrc> src = scene_sources(ms, n, side, sd);
+    const size_t need_lists = (size_t)L * cap;
+    {   int rc;
+        if ((rc = ws.t.grow(need_lists * kSceneListLen)) || (rc = ws.attr.grow(need_lists * kSceneListLen * 4)) || (rc = ws.cnt.grow(need_lists)) ||
+            (rc = ws.out.grow(8 * n_q)) || (rc = ws.h_out.grow(8 * n_q)) || (rc = ws.q.grow(n_q)) || (rc = ws.poses.grow(16 * n_poses)) ||
+            (rc = ws.keys.grow(cap))) return rc; }
+    HIPCHECK(hipMemcpyAsync(ws.q.p, q, sizeof(mon_scene_query) * n_q, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(ws.poses.p, Twc16s, 64 * n_poses, hipMemcpyHostToDevice, s));
+    float* o_rgb = ws.out.p; float* o_depth = o_rgb + 3 * n_q; float* o_op = o_depth + n_q; int32_t* o_inst = reinterpret_cast<int32_t*>(o_op + n_q);
+    float* o_hd = o_op + 2 * n_q; int32_t* o_hi = reinterpret_cast<int32_t*>(o_hd + n_q);
+    std::vector<float> d_o, d_d, d_t0, d_t1, d_dn; std::vector<uint8_t> d_flag;       // mon_debug_scene_probe_rays: object k's ray rows of every pass
+    if (dump) { d_o.resize(3 * n_q); d_d.resize(3 * n_q); d_t0.resize(n_q); d_t1.resize(n_q); d_dn.resize(n_q); d_flag.resize(n_q); }
+    for (uint32_t p0 = 0; p0 < nq; p0 += cap) {
+        const uint32_t nc = std::min(cap, nq - p0);
+        for (size_t j = 0; j < n; ++j) {
+            Model& m = *ms[j]; const size_t l0 = j * (size_t)cap;
+            launch_scene_probe_rays(s, *src[j].b, K, m.oc, ws.q.p + p0, ws.poses.p, j == 0 ? ws.keys.p : nullptr, nc);
+            launch_fused_render_emit(s, m.lf, m.nd, sd.prm[j], *src[j].b, m.oc, nc, 0u, ws.t.p + l0 * kSceneListLen, ws.attr.p + l0 * kSceneListLen * 4,
+                    ws.cnt.p + l0, src[j].frag, p0 == 0u, src[j].bits, ws.keys.p);
+        }
+        // (every object's ray kernel wrote the same dn: it depends on the query and the intrinsics only)
+        launch_scene_probe_composite(s, nc, L, cap, ws.t.p, ws.attr.p, ws.cnt.p, src[0].b->ray_dn, o_rgb + 3 * (size_t)p0, o_depth + p0, o_op + p0, o_inst + p0,
+                o_hd + p0, o_hi + p0);
+        if (dump) {
+            const BatchPtrs& b = *src[dump->k].b;
+            HIPCHECK(hipMemcpyAsync(d_o.data() + 3 * (size_t)p0, b.ray_o, 12 * (size_t)nc, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipMemcpyAsync(d_d.data() + 3 * (size_t)p0, b.ray_d, 12 * (size_t)nc, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipMemcpyAsync(d_t0.data() + p0, b.ray_t0, 4 * (size_t)nc, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipMemcpyAsync(d_t1.data() + p0, b.ray_t1, 4 * (size_t)nc, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipMemcpyAsync(d_dn.data() + p0, b.ray_dn, 4 * (size_t)nc, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipMemcpyAsync(d_flag.data() + p0, b.ray_flag, (size_t)nc, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipStreamSynchronize(s));
+        }
+    }
+    launch_copy_params(s, reinterpret_cast<const uint16_t*>(ws.out.p), reinterpret_cast<uint16_t*>(ws.h_out.p), (uint32_t)(16 * n_q));
+    HIPCHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    const float* h = ws.h_out.p;
+    std::memcpy(rgb, h, 12 * n_q); std::memcpy(depth, h + 3 * n_q, 4 * n_q);
+    if (opacity) std::memcpy(opacity, h + 4 * n_q, 4 * n_q);
+    if (hit_depth) std::memcpy(hit_depth, h + 6 * n_q, 4 * n_q);
+    const int32_t* h_inst = reinterpret_cast<const int32_t*>(h + 5 * n_q); const int32_t* h_hi = reinterpret_cast<const int32_t*>(h + 7 * n_q);
+    for (size_t i = 0; i < n_q; ++i) {
+        if (instance) instance[i] = (h_inst[i] >= 0 && ids) ? ids[h_inst[i]] : h_inst[i];
+        if (hit_instance) hit_instance[i] = (h_hi[i] >= 0 && ids) ? ids[h_hi[i]] : h_hi[i];
+    }
+    if (dump) for (size_t i = 0; i < n_q; ++i) {                                        // (a row that missed the box holds only flag and dn)
+        float* r = dump->rows + 10 * i; const bool hit = d_flag[i] != 0;
+        for (int a = 0; a < 3; ++a) { r[a] = hit ? d_o[3 * i + a] : 0.f; r[3 + a] = hit ? d_d[3 * i + a] : 0.f; }
+        r[6] = hit ? d_t0[i] : 0.f; r[7] = hit ? d_t1[i] : 0.f; r[8] = hit ? 1.f : 0.f; r[9] = d_dn[i];
     }
     return MON_OK;
 }
