@@ -198,7 +198,7 @@ int mon_scene_render(mon_object* const* objs, size_t n_objs, int side, mon_frame
  *   rgb, depth, opacity, instance   as mon_scene_render defines them
  *   hit_depth    = t_i / |camera ray| of the first merged sample i with 1 - T_{i+1} > 0.5 (the transmittance the composite carries after it), else 0
  *   hit_instance = the index in objs of that sample's object, else -1
- * hit_depth is a sample distance, not interpolated inside the sample's interval; unlike depth (sum w t) it does not smear across an occlusion edge.
+ * hit_depth is a sample distance, not interpolated inside the sample's interval (mon_scene_cast's hit_t is); unlike depth (sum w t) it does not smear across an occlusion edge.
  * Bit rule: a query with integer-valued u = x, v = y and key = (y - rect.y) * rect.w + (x - rect.x) returns in rgb, depth, opacity and instance the bits
  * mon_scene_render(objs, n_objs, side, rect, Twc, ...) returns for that pixel.  The six outputs of a query do not depend on the other queries of the call,
  * on its place in the list, on the number of poses or on how the list is cut into passes (16 384 queries each); no atomics: equal arguments, equal bits.
@@ -212,6 +212,48 @@ int mon_scene_render(mon_object* const* objs, size_t n_objs, int side, mon_frame
 typedef struct mon_scene_query { uint32_t pose; uint32_t key; float u, v; } mon_scene_query;   /* 16 bytes */
 int mon_scene_probe(mon_object* const* objs, size_t n_objs, int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q,
                     float* rgb, float* depth, float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance);
+/* Ray cast: the object map asked along world rays by a consumer that is not a camera of the dataset -- a planner's line-of-sight check between two points,
+ * a range sensor, a grasp query, the surface point along a map point's viewing ray (the reference has no such call; opt-in, new).  Forward only: surface
+ * normals, density gradients and queries at points rather than along rays are a follow-up.
+ * Ray i is x(t) = o + t d for 0 <= t <= t_max in the world frame; d must be unit (| |d|^2 - 1 | <= 1e-3, used as given: the device does not renormalise);
+ * t_max > 0, +inf allowed.  For object j the ray is taken into j's frame (R_ow d, R_ow o + t_ow) and intersected with j's box at [t0, t1]; j contributes iff
+ * the box is hit and lo < hi, lo = max(t0, 0), hi = min(t1, t_max).  Its 2S = 64 samples are the scene render's for a ray row {t0 = lo, t1 = hi}:
+ * t_k = fma((hi - lo) / 64, k + u_k, lo) with the jitter index key * 64 + k of j's own render stream; alpha, colour, termination, render grid (when render
+ * skipping is on) and dead samples as in mon_scene_render.  As there, the interval of an object's first sample is measured from t = 0 (the ray's origin),
+ * not from lo: a caller who means the segment from a to b puts o = a, so that nothing in front of the segment is counted.  The lists are merged and
+ * composited exactly as mon_scene_render does it.  Outputs per ray, host pointers (the last five may be NULL):
+ *   rgb, opacity, instance   as mon_scene_render defines them
+ *   dist          = sum w t where opacity > 0.5, else 0 (mon_scene_probe's depth without the division by |camera ray|)
+ *   hit_sample_t, hit_instance = t_i and the index in objs of the first merged sample i with 1 - T_{i+1} > hit_opacity, else 0 and -1
+ *   hit_t         = p + f (t_i - p): the crossing placed inside sample i's interval under the piecewise-constant density the composite assumes,
+ *                   f = clamp(ln(T_i / (1 - hit_opacity)) / (-ln(1 - alpha_i)), 0, 1), f = 0 when 1 - alpha_i == 0; p = the previous sample's t in the same
+ *                   object's list, or that object's lo for its first sample (never in front of the box); T_i = the merged transmittance in front of
+ *                   sample i.  p <= hit_t <= hit_sample_t; 0 where there is no hit.
+ * hit_opacity in (0, 0.999]: 0.5 is mon_scene_probe's rule; a planner takes about 0.1 for a conservative stop.
+ * Bit rule: with rays = mon_camera_rays(the dataset's intrinsics, poses, q) (t_max = +inf, the queries' keys) and hit_opacity = 0.5, rgb, opacity, instance
+ * and hit_instance are the bits of mon_scene_probe(q), and dist / dn, hit_sample_t / dn (fp32, dn = mon_camera_rays' dn_out) those of its depth and
+ * hit_depth -- except on a ray that meets an object's box only behind its origin (t1 < 0): mon_scene_probe, like mon_scene_render, samples such an object
+ * at negative t, here it is a miss (lo < hi fails) and the ray's outputs are those of the other objects.  A ray's outputs do not depend on the other rays of the call, on its place in the list or on how the list is cut into passes (16 384 rays
+ * each); no atomics: equal arguments, equal bits.  One enqueue, one synchronisation.  Read-only, side as in mon_scene_render.  The objects need not share
+ * a dataset or intrinsics: no camera is involved.
+ * Axis-aligned rays: a direction component that is exactly 0 in an object's frame (straight down onto an object whose rotation is the identity) gives
+ * infinite slab distances and the right answer: a miss when the origin lies outside that slab, no constraint from it when inside.  Only when the origin
+ * also lies exactly in one of that slab's two planes (0 / 0) is the answer for that object unspecified between a miss and a ray that runs inside the face;
+ * every output stays finite.
+ * Returns:
+ *   MON_ERR_ARG    objs or an element, rays, rgb or dist NULL; n_objs 0 or above 256; n_rays outside 1..2^22; a key >= 2^26; a non-finite o or d; a
+ *                  non-unit d; t_max <= 0 or NaN; hit_opacity outside (0, 0.999]; side not 0 / 1; objects on different logical devices -- all before
+ *                  any device work
+ *   MON_ERR_STATE  as mon_scene_render */
+typedef struct mon_scene_ray { float o[3]; float t_max; float d[3]; uint32_t key; } mon_scene_ray;   /* 32 bytes */
+int mon_scene_cast(mon_object* const* objs, size_t n_objs, int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity,
+                   float* rgb, float* dist, float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t, int32_t* hit_instance);
+/* Host only, no device: the world rays mon_scene_probe casts for the queries q under the camera-to-world poses Twc16s with the pinhole (fx, fy, cx, cy):
+ * rays_out[i] = { o = the camera centre, t_max = +inf, d = R_wc (dc / |dc|) with dc = ((u - cx) / fx, (v - cy) / fy, 1), key = q[i].key } and, where
+ * dn_out is not NULL, dn_out[i] = |dc| (a depth along the optical axis = a distance along the ray / dn).  The arithmetic is the device's, operation for
+ * operation.  MON_ERR_ARG: Twc16s, q or rays_out NULL; n_poses or n_q 0; a pose index >= n_poses; a non-finite intrinsic, pose, u or v; fx or fy 0. */
+int mon_camera_rays(float fx, float fy, float cx, float cy, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q,
+                    mon_scene_ray* rays_out, float* dn_out);
 /* Object pose refinement through the trained field (iNeRF-style): align the object with observed frames by following the gradient of a photometric,
  * silhouette and depth error with respect to the 6-DoF pose Tow.
  * Objective.  obs names frames of the object's dataset (FrameId) and pixel boxes inside them; the target of a pixel is that frame's rgb c*, its instance map
@@ -580,6 +622,11 @@ int mon_online_render_scene(mon_online* mgr, mon_frame_bbox rect, const float* T
  * span more than one device. */
 int mon_online_probe_scene(mon_online* mgr, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q,
                            float* rgb, float* depth, float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance);
+/* mon_scene_cast(side 1) of every object of the manager that has published weights, chosen as mon_online_render_scene chooses them; both instance outputs
+ * hold the manager's object indices.  A planner's call, safe while the objects train.  MON_ERR_STATE when no object has published yet or the objects
+ * span more than one device. */
+int mon_online_cast_rays(mon_online* mgr, const mon_scene_ray* rays, size_t n_rays, float hit_opacity,
+                         float* rgb, float* dist, float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t, int32_t* hit_instance);
 /* mon_object_refine_pose(side 1) of object idx: its published snapshot, on the inference stream -- safe while the manager trains it.  MON_ERR_STATE while
  * nothing of it has been published. */
 int mon_online_refine_pose(mon_online* mgr, size_t idx, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, float* Tow16_inout,

@@ -71,6 +71,16 @@ int mon_debug_scene_probe_composite(int device, uint32_t n_rays, uint32_t n_list
                                     const float* dn, float* out_rgb, float* out_depth, float* out_opacity, int32_t* out_instance, float* out_hit_depth,
                                     int32_t* out_hit_instance);
 
+/* Ray cast (mon_scene_cast), its own two kernels one at a time.  mon_debug_scene_cast_rays: the ray rows k_scene_cast_rays writes for object k of that cast
+ * (the same arguments first), rows[n_rays][10] = o[3], d[3] (object frame), t0 = lo, t1 = hi, flag (1: object k contributes), dn = 1, and entry[n_rays] = the
+ * entry row the composite reads (lo; 0 where flag is 0); a row with flag 0 holds zeros and dn.  mon_debug_scene_cast_composite: k_scene_cast_composite on
+ * caller lists laid out as mon_debug_scene_composite's, plus entry[n_lists][n_rays] and the threshold; out_dist is not divided by anything
+ * (hit_instance = list index). */
+int mon_debug_scene_cast_rays(mon_object* const* objs, size_t n_objs, int side, const mon_scene_ray* rays, size_t n_rays, size_t k, float* rows, float* entry);
+int mon_debug_scene_cast_composite(int device, uint32_t n_rays, uint32_t n_lists, const float* t, const float* alpha, const float* rgb, const uint32_t* count,
+                                   const float* entry, float hit_opacity, float* out_rgb, float* out_dist, float* out_opacity, int32_t* out_instance,
+                                   float* out_hit_t, float* out_hit_sample_t, int32_t* out_hit_instance);
+
 /* Pose refinement (mon_object_pose_loss, the same arguments): per drawn ray of that evaluation (rays_per_iter of them, or every pixel of every box in box
  * order), its 2S = 64 samples: x[ray][64][3] the positions in the object frame, raw[ray][64][4] the network's raw outputs, dldx[ray][64][3] = dL/dx_k in the
  * object frame (the 1/N of the mean included).  Samples not evaluated (a missed box, the second tile behind the early cut) hold 0 (x: the position it would

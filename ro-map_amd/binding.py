@@ -67,6 +67,14 @@ class SceneQuery(C.Structure):
 SCENE_QUERY_DTYPE = np.dtype([("pose", np.uint32), ("key", np.uint32), ("u", np.float32), ("v", np.float32)])
 
 
+class SceneRay(C.Structure):
+    """mon_scene_ray (include/mon_core.h): one world ray of a cast -- origin, segment length, unit direction, jitter key."""
+    _fields_ = [("o", C.c_float * 3), ("t_max", C.c_float), ("d", C.c_float * 3), ("key", C.c_uint32)]
+
+
+SCENE_RAY_DTYPE = np.dtype([("o", np.float32, 3), ("t_max", np.float32), ("d", np.float32, 3), ("key", np.uint32)])
+
+
 class RelocResult(C.Structure):
     """mon_reloc_result (include/mon_core.h): which candidate won, whether its refined pose did, and the scores S[0], S[best], F[winner]."""
     _fields_ = [("best_candidate", C.c_uint32), ("refined", C.c_uint32), ("score_candidate0", C.c_float), ("score_best_candidate", C.c_float),
@@ -191,6 +199,11 @@ _SIGS = {
             C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_online_probe_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_void_p]),
+    "mon_scene_cast": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_online_cast_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p]),
+    "mon_camera_rays": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "mon_pose_refine_default": (C.c_int, [C.POINTER(PoseRefineParams)]),
     "mon_object_pose_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32,
             C.POINTER(C.c_float), C.c_void_p]),
@@ -258,6 +271,9 @@ _DIAG_SIGS = {
     "mon_debug_scene_probe_rays": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
     "mon_debug_scene_probe_composite": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_debug_scene_cast_rays": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mon_debug_scene_cast_composite": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_debug_pose_samples": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32, C.c_void_p,
             C.c_void_p, C.c_void_p]),
     "mon_debug_scene_pose_samples": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32,
@@ -895,6 +911,13 @@ class OnlineManager:
         _check(lib().mon_online_probe_scene(self.h, _p(poses), poses.shape[0], _p(q), q.shape[0], *[_p(a) for a in out]))
         return out
 
+    def cast_rays(self, rays, hit_opacity=0.5):
+        """mon_online_cast_rays: cast_scene on side 1 over every object with published weights (a planner's call, safe while they train); both instance
+        outputs hold the manager's object indices."""
+        r, out = _cast_args(rays)
+        _check(lib().mon_online_cast_rays(self.h, _p(r), r.shape[0], float(hit_opacity), *[_p(a) for a in out]))
+        return out
+
     def save_map(self, path):
         """mon_online_save_map: <path>/map.txt + one checkpoint per object, each under its own model lock (safe while they train; not one global cut)."""
         _check(lib().mon_online_save_map(self.h, os.fsencode(path)))
@@ -1069,6 +1092,55 @@ def scene_probe_composite(t, alpha, rgb, count, dn, device=0):
     out = (np.empty((R, 3), np.float32), np.empty(R, np.float32), np.empty(R, np.float32), np.empty(R, np.int32), np.empty(R, np.float32),
            np.empty(R, np.int32))
     _check(diag_lib().mon_debug_scene_probe_composite(int(device), R, L, _p(t), _p(a), _p(c), _p(n), _p(d), *[_p(o) for o in out]))
+    return out
+
+
+def scene_rays(o, d, t_max=np.inf, key=0):
+    """An array of mon_scene_ray (SCENE_RAY_DTYPE) from origins (n, 3), unit directions (n, 3) and broadcastable segment lengths and keys."""
+    o = np.asarray(o, np.float32).reshape(-1, 3); d = np.asarray(d, np.float32).reshape(-1, 3)
+    r = np.empty(o.shape[0], SCENE_RAY_DTYPE)
+    r["o"] = o; r["d"] = d; r["t_max"] = np.broadcast_to(np.asarray(t_max, np.float32), o.shape[:1]); r["key"] = np.broadcast_to(np.asarray(key), o.shape[:1])
+    return r
+
+
+def camera_rays(K, Twc16s, queries):
+    """mon_camera_rays (host only): the world rays probe_scene casts for the queries under the pinhole K = (fx, fy, cx, cy).  Returns (rays, dn)."""
+    q = np.ascontiguousarray(queries, SCENE_QUERY_DTYPE).reshape(-1); poses = np.ascontiguousarray(Twc16s, np.float32).reshape(-1, 16)
+    rays = np.empty(q.shape[0], SCENE_RAY_DTYPE); dn = np.empty(q.shape[0], np.float32)
+    _check(lib().mon_camera_rays(float(K[0]), float(K[1]), float(K[2]), float(K[3]), _p(poses), poses.shape[0], _p(q), q.shape[0], _p(rays), _p(dn)))
+    return rays, dn
+
+
+def _cast_args(rays):
+    r = np.ascontiguousarray(rays, SCENE_RAY_DTYPE).reshape(-1); n = r.shape[0]
+    return r, (np.empty((n, 3), np.float32), np.empty(n, np.float32), np.empty(n, np.float32), np.empty(n, np.int32), np.empty(n, np.float32),
+               np.empty(n, np.float32), np.empty(n, np.int32))
+
+
+def cast_scene(objects, rays, hit_opacity=0.5, side=0):
+    """mon_scene_cast: the object map along world rays (SCENE_RAY_DTYPE: o, t_max, d unit, key).  Returns (rgb (n, 3), dist, opacity, instance, hit_t,
+    hit_sample_t, hit_instance): hit_t is the point at which 1 - T crosses hit_opacity, placed inside its sample's interval."""
+    r, out = _cast_args(rays)
+    _check(lib().mon_scene_cast(_handles(objects), len(objects), int(side), _p(r), r.shape[0], float(hit_opacity), *[_p(a) for a in out]))
+    return out
+
+
+def scene_cast_rays(objects, rays, k, side=0):
+    """mon_debug_scene_cast_rays: object k's ray rows of that cast, (n, 10) = o[3], d[3], lo, hi, flag, dn = 1, and its entry row (n,)."""
+    r, _ = _cast_args(rays); rows = np.empty((r.shape[0], 10), np.float32); entry = np.empty(r.shape[0], np.float32)
+    _check(diag_lib().mon_debug_scene_cast_rays(_handles(objects), len(objects), int(side), _p(r), r.shape[0], int(k), _p(rows), _p(entry)))
+    return rows, entry
+
+
+def scene_cast_composite(t, alpha, rgb, count, entry, hit_opacity=0.5, device=0):
+    """mon_debug_scene_cast_composite: the cast's composite kernel on lists laid out as scene_composite's, entry (n_lists, n_rays) = each list's box entry.
+    Returns (rgb (n_rays, 3), dist, opacity, instance, hit_t, hit_sample_t, hit_instance)."""
+    t = np.ascontiguousarray(t, np.float32); L, R = t.shape[:2]
+    a = np.ascontiguousarray(alpha, np.float32).reshape(L, R, 64); c = np.ascontiguousarray(rgb, np.float32).reshape(L, R, 64, 3)
+    n = np.ascontiguousarray(count, np.uint32).reshape(L, R); e = np.ascontiguousarray(entry, np.float32).reshape(L, R)
+    out = (np.empty((R, 3), np.float32), np.empty(R, np.float32), np.empty(R, np.float32), np.empty(R, np.int32), np.empty(R, np.float32),
+           np.empty(R, np.float32), np.empty(R, np.int32))
+    _check(diag_lib().mon_debug_scene_cast_composite(int(device), R, L, _p(t), _p(a), _p(c), _p(n), _p(e), float(hit_opacity), *[_p(o) for o in out]))
     return out
 
 

@@ -125,6 +125,19 @@ int mon_scene_probe(mon_object* const* objs, size_t n_objs, int side, const floa
     for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
     return scene_probe(ms.data(), n_objs, side, Twc16s, n_poses, q, n_q, rgb, depth, opacity, instance, hit_depth, hit_instance, nullptr, nullptr);
 }
+int mon_scene_cast(mon_object* const* objs, size_t n_objs, int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, float* rgb, float* dist,
+        float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t, int32_t* hit_instance) {
+    REQUIRE(objs, "objs");
+    { const int rc = scene_cast_check(side, rays, n_rays, hit_opacity, rgb, dist); if (rc) return rc; }
+    if (n_objs == 0 || n_objs > kSceneMaxLists) { set_error("scene_cast: %zu objects (1 to %u)", n_objs, kSceneMaxLists); return MON_ERR_ARG; }
+    std::vector<Model*> ms(n_objs);
+    for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
+    return scene_cast(ms.data(), n_objs, side, rays, n_rays, hit_opacity, rgb, dist, opacity, instance, hit_t, hit_sample_t, hit_instance, nullptr, nullptr);
+}
+int mon_camera_rays(float fx, float fy, float cx, float cy, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, mon_scene_ray* rays_out,
+        float* dn_out) {
+    return scene_camera_rays(fx, fy, cx, cy, Twc16s, n_poses, q, n_q, rays_out, dn_out);
+}
 int mon_pose_refine_default(mon_pose_refine_params* p) {
     REQUIRE(p, "params");
     p->iters = 100; p->rays_per_iter = 4096; p->lr_trans = 2e-3f; p->lr_rot = 4e-3f;

@@ -222,57 +222,68 @@ int mon_debug_scene_samples(mon_object* const* objs, size_t n_objs, int side, mo
     const mon::SceneDump dump{ (uint32_t)k, t, alpha, rgb, count };
     return mon::scene_render(ms.data(), n_objs, side, rect, Twc16, img.data(), dep.data(), nullptr, nullptr, nullptr, &dump);
 }
-// mon_debug_scene_composite, and with the hit outputs mon_debug_scene_probe_composite (the probe's kernel on the same lists)
-static int debug_scene_composite(int device, uint32_t n_rays, uint32_t n_lists, const float* t, const float* alpha, const float* rgb, const uint32_t* count,
-                                 const float* dn, float* out_rgb, float* out_depth, float* out_opacity, int32_t* out_instance, float* out_hit_depth,
-                                 int32_t* out_hit_instance) {
-    const bool probe = out_hit_depth != nullptr;
-    REQUIRE(t, "t"); REQUIRE(alpha, "alpha"); REQUIRE(rgb, "rgb"); REQUIRE(count, "count"); REQUIRE(dn, "dn"); REQUIRE(out_rgb, "out_rgb");
-    REQUIRE(out_depth, "out_depth"); REQUIRE(out_opacity, "out_opacity"); REQUIRE(out_instance, "out_instance");
+// mon_debug_scene_composite; with the hit outputs mon_debug_scene_probe_composite (the probe's kernel on the same lists); with an entry array
+// [n_lists][n_rays] in place of dn, the threshold and a third hit output mon_debug_scene_cast_composite (the cast's kernel).  aux = dn or entry.
+enum DebugComposite { kDebugRender = 0, kDebugProbe = 1, kDebugCast = 2 };
+static int debug_scene_composite(DebugComposite kind, int device, uint32_t n_rays, uint32_t n_lists, const float* t, const float* alpha, const float* rgb,
+                                 const uint32_t* count, const float* aux, float thr, float* out_rgb, float* out_depth, float* out_opacity,
+                                 int32_t* out_instance, float* out_hit_a, float* out_hit_b, int32_t* out_hit_instance) {
+    REQUIRE(t, "t"); REQUIRE(alpha, "alpha"); REQUIRE(rgb, "rgb"); REQUIRE(count, "count"); REQUIRE(aux, kind == kDebugCast ? "entry" : "dn");
+    REQUIRE(out_rgb, "out_rgb"); REQUIRE(out_depth, "out_depth"); REQUIRE(out_opacity, "out_opacity"); REQUIRE(out_instance, "out_instance");
     if (n_rays == 0 || n_lists == 0 || n_lists > mon::kSceneMaxLists) { set_error("debug_scene_composite: %u rays, %u lists", n_rays, n_lists);
         return MON_ERR_ARG; }
-    const size_t nl = (size_t)n_lists * n_rays, ns = nl * mon::kSceneListLen;
+    if (kind == kDebugCast && !(thr > 0.f && thr <= 0.999f)) { set_error("debug_scene_cast_composite: hit_opacity %g", (double)thr); return MON_ERR_ARG; }
+    const size_t nl = (size_t)n_lists * n_rays, ns = nl * mon::kSceneListLen, R = n_rays, rows = kind == kDebugCast ? 9 : kind == kDebugProbe ? 8 : 6;
     for (size_t i = 0; i < nl; ++i) if (count[i] > mon::kSceneListLen) { set_error("debug_scene_composite: count %u > 64", count[i]); return MON_ERR_ARG; }
     std::vector<float> attr(4 * ns);
     for (size_t i = 0; i < ns; ++i) { attr[4 * i] = alpha[i]; attr[4 * i + 1] = rgb[3 * i]; attr[4 * i + 2] = rgb[3 * i + 1]; attr[4 * i + 3] = rgb[3 * i + 2]; }
     HIPCHECK(mon::use_device(device));
-    char* d = nullptr; const size_t b_t = ns * 4, b_a = ns * 16, b_c = nl * 4, b_dn = (size_t)n_rays * 4, b_out = (size_t)n_rays * 32;
-    HIPCHECK(hipMalloc((void**)&d, b_t + b_a + b_c + b_dn + b_out));
-    float* d_t = (float*)d; float* d_a = (float*)(d + b_t); uint32_t* d_c = (uint32_t*)(d + b_t + b_a); float* d_dn = (float*)(d + b_t + b_a + b_c);
-    float* d_out = (float*)(d + b_t + b_a + b_c + b_dn);
+    char* d = nullptr; const size_t b_t = ns * 4, b_a = ns * 16, b_c = nl * 4, b_aux = (kind == kDebugCast ? nl : R) * 4, b_out = R * 4 * rows;
+    HIPCHECK(hipMalloc((void**)&d, b_t + b_a + b_c + b_aux + b_out));
+    float* d_t = (float*)d; float* d_a = (float*)(d + b_t); uint32_t* d_c = (uint32_t*)(d + b_t + b_a); float* d_aux = (float*)(d + b_t + b_a + b_c);
+    float* d_out = (float*)(d + b_t + b_a + b_c + b_aux);
     hipError_t e = hipMemcpy(d_t, t, b_t, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_a, attr.data(), b_a, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_c, count, b_c, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_dn, dn, b_dn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_aux, aux, b_aux, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        if (probe) mon::launch_scene_probe_composite(nullptr, n_rays, n_lists, n_rays, d_t, d_a, d_c, d_dn, d_out, d_out + 3 * (size_t)n_rays,
-                d_out + 4 * (size_t)n_rays, reinterpret_cast<int32_t*>(d_out + 5 * (size_t)n_rays), d_out + 6 * (size_t)n_rays,
-                reinterpret_cast<int32_t*>(d_out + 7 * (size_t)n_rays));
-        else mon::launch_scene_composite(nullptr, n_rays, n_lists, n_rays, d_t, d_a, d_c, d_dn, d_out, d_out + 3 * (size_t)n_rays, d_out + 4 * (size_t)n_rays,
-                reinterpret_cast<int32_t*>(d_out + 5 * (size_t)n_rays));
+        int32_t* d_inst = reinterpret_cast<int32_t*>(d_out + 5 * R);
+        if (kind == kDebugCast) mon::launch_scene_cast_composite(nullptr, n_rays, n_lists, n_rays, thr, d_t, d_a, d_c, d_aux, d_out, d_out + 3 * R, d_out + 4 * R,
+                d_inst, d_out + 6 * R, d_out + 7 * R, reinterpret_cast<int32_t*>(d_out + 8 * R));
+        else if (kind == kDebugProbe) mon::launch_scene_probe_composite(nullptr, n_rays, n_lists, n_rays, d_t, d_a, d_c, d_aux, d_out, d_out + 3 * R, d_out + 4 * R,
+                d_inst, d_out + 6 * R, reinterpret_cast<int32_t*>(d_out + 7 * R));
+        else mon::launch_scene_composite(nullptr, n_rays, n_lists, n_rays, d_t, d_a, d_c, d_aux, d_out, d_out + 3 * R, d_out + 4 * R, d_inst);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    std::vector<float> out(8 * (size_t)n_rays);
-    if (e == hipSuccess) e = hipMemcpy(out.data(), d_out, (size_t)n_rays * (probe ? 32 : 24), hipMemcpyDeviceToHost);
+    std::vector<float> out(rows * R);
+    if (e == hipSuccess) e = hipMemcpy(out.data(), d_out, b_out, hipMemcpyDeviceToHost);
     (void)hipFree(d);
     HIPCHECK(e);
-    std::memcpy(out_rgb, out.data(), 12 * (size_t)n_rays); std::memcpy(out_depth, out.data() + 3 * (size_t)n_rays, 4 * (size_t)n_rays);
-    std::memcpy(out_opacity, out.data() + 4 * (size_t)n_rays, 4 * (size_t)n_rays); std::memcpy(out_instance, out.data() + 5 * (size_t)n_rays, 4 * (size_t)n_rays);
-    if (probe) { std::memcpy(out_hit_depth, out.data() + 6 * (size_t)n_rays, 4 * (size_t)n_rays);
-        std::memcpy(out_hit_instance, out.data() + 7 * (size_t)n_rays, 4 * (size_t)n_rays); }
+    std::memcpy(out_rgb, out.data(), 12 * R); std::memcpy(out_depth, out.data() + 3 * R, 4 * R);
+    std::memcpy(out_opacity, out.data() + 4 * R, 4 * R); std::memcpy(out_instance, out.data() + 5 * R, 4 * R);
+    if (kind != kDebugRender) { std::memcpy(out_hit_a, out.data() + 6 * R, 4 * R); std::memcpy(out_hit_instance, out.data() + (rows - 1) * R, 4 * R); }
+    if (kind == kDebugCast) std::memcpy(out_hit_b, out.data() + 7 * R, 4 * R);
     return MON_OK;
 }
 int mon_debug_scene_composite(int device, uint32_t n_rays, uint32_t n_lists, const float* t, const float* alpha, const float* rgb, const uint32_t* count,
                               const float* dn, float* out_rgb, float* out_depth, float* out_opacity, int32_t* out_instance) {
-    return debug_scene_composite(device, n_rays, n_lists, t, alpha, rgb, count, dn, out_rgb, out_depth, out_opacity, out_instance, nullptr, nullptr);
+    return debug_scene_composite(kDebugRender, device, n_rays, n_lists, t, alpha, rgb, count, dn, 0.5f, out_rgb, out_depth, out_opacity, out_instance, nullptr,
+                                 nullptr, nullptr);
 }
 int mon_debug_scene_probe_composite(int device, uint32_t n_rays, uint32_t n_lists, const float* t, const float* alpha, const float* rgb, const uint32_t* count,
                                     const float* dn, float* out_rgb, float* out_depth, float* out_opacity, int32_t* out_instance, float* out_hit_depth,
                                     int32_t* out_hit_instance) {
     REQUIRE(out_hit_depth, "out_hit_depth"); REQUIRE(out_hit_instance, "out_hit_instance");
-    return debug_scene_composite(device, n_rays, n_lists, t, alpha, rgb, count, dn, out_rgb, out_depth, out_opacity, out_instance, out_hit_depth,
-                                 out_hit_instance);
+    return debug_scene_composite(kDebugProbe, device, n_rays, n_lists, t, alpha, rgb, count, dn, 0.5f, out_rgb, out_depth, out_opacity, out_instance,
+                                 out_hit_depth, nullptr, out_hit_instance);
+}
+int mon_debug_scene_cast_composite(int device, uint32_t n_rays, uint32_t n_lists, const float* t, const float* alpha, const float* rgb, const uint32_t* count,
+                                   const float* entry, float hit_opacity, float* out_rgb, float* out_dist, float* out_opacity, int32_t* out_instance,
+                                   float* out_hit_t, float* out_hit_sample_t, int32_t* out_hit_instance) {
+    REQUIRE(out_hit_t, "out_hit_t"); REQUIRE(out_hit_sample_t, "out_hit_sample_t"); REQUIRE(out_hit_instance, "out_hit_instance");
+    return debug_scene_composite(kDebugCast, device, n_rays, n_lists, t, alpha, rgb, count, entry, hit_opacity, out_rgb, out_dist, out_opacity, out_instance,
+                                 out_hit_t, out_hit_sample_t, out_hit_instance);
 }
 int mon_debug_scene_probe_rays(mon_object* const* objs, size_t n_objs, int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q,
                                size_t k, float* rows) {
@@ -282,8 +293,18 @@ int mon_debug_scene_probe_rays(mon_object* const* objs, size_t n_objs, int side,
     std::vector<mon::Model*> ms(n_objs);
     for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
     std::vector<float> img(3 * n_q), dep(n_q);
-    const mon::SceneProbeDump dump{ (uint32_t)k, rows };
+    const mon::SceneRaysDump dump{ (uint32_t)k, rows, nullptr };
     return mon::scene_probe(ms.data(), n_objs, side, Twc16s, n_poses, q, n_q, img.data(), dep.data(), nullptr, nullptr, nullptr, nullptr, nullptr, &dump);
+}
+int mon_debug_scene_cast_rays(mon_object* const* objs, size_t n_objs, int side, const mon_scene_ray* rays, size_t n_rays, size_t k, float* rows, float* entry) {
+    REQUIRE(objs, "objs"); REQUIRE(rows, "rows"); REQUIRE(entry, "entry");
+    if (n_objs == 0 || n_objs > mon::kSceneMaxLists || k >= n_objs) { set_error("debug_scene_cast_rays: empty list or k out of range"); return MON_ERR_ARG; }
+    { const int rc = mon::scene_cast_check(side, rays, n_rays, 0.5f, rows, rows); if (rc) return rc; }
+    std::vector<mon::Model*> ms(n_objs);
+    for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
+    std::vector<float> img(3 * n_rays), dep(n_rays);
+    const mon::SceneRaysDump dump{ (uint32_t)k, rows, entry };
+    return mon::scene_cast(ms.data(), n_objs, side, rays, n_rays, 0.5f, img.data(), dep.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &dump);
 }
 int mon_debug_pose_samples(mon_object* o, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params* p,
                            uint32_t iteration, float* x, float* raw, float* dldx) {

@@ -707,17 +707,31 @@ int mon_online_render_scene(mon_online* h, mon_frame_bbox rect, const float* Twc
     }
     return scene_render(ms.data(), ms.size(), 1, rect, Twc16, rgb, depth, opacity, instance, ids.data(), nullptr);
 }
+// the objects mon_online_probe_scene and mon_online_cast_rays ask: those with published weights, as mon_online_render_scene picks them, and their indices
+static int online_published(mon_online* h, const char* what, std::vector<Model*>& ms, std::vector<int32_t>& ids) {
+    const std::vector<OnlineObject*> objs = online_objects(*h->m);
+    for (size_t i = 0; i < objs.size(); ++i) if (objs[i]->model && model_has_snapshot(*objs[i]->model)) { ms.push_back(objs[i]->model); ids.push_back((int32_t)i); }
+    if (ms.empty()) { set_error("%s: no object has published weights yet", what); return MON_ERR_STATE; }
+    for (Model* m : ms) if (m->device != ms[0]->device) { set_error("%s: the objects span more than one device", what); return MON_ERR_STATE; }
+    return MON_OK;
+}
 // the map's prediction at a front end's keypoints: mon_scene_probe on side 1 over the objects mon_online_render_scene composites
 int mon_online_probe_scene(mon_online* h, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, float* rgb, float* depth, float* opacity,
         int32_t* instance, float* hit_depth, int32_t* hit_instance) {
     REQ(h);
     { const int rc = scene_probe_check(1, Twc16s, n_poses, q, n_q, rgb, depth); if (rc) return rc; }
     std::vector<Model*> ms; std::vector<int32_t> ids;
-    const std::vector<OnlineObject*> objs = online_objects(*h->m);
-    for (size_t i = 0; i < objs.size(); ++i) if (objs[i]->model && model_has_snapshot(*objs[i]->model)) { ms.push_back(objs[i]->model); ids.push_back((int32_t)i); }
-    if (ms.empty()) { set_error("probe_scene: no object has published weights yet"); return MON_ERR_STATE; }
-    for (Model* m : ms) if (m->device != ms[0]->device) { set_error("probe_scene: the objects span more than one device"); return MON_ERR_STATE; }
+    { const int rc = online_published(h, "probe_scene", ms, ids); if (rc) return rc; }
     return scene_probe(ms.data(), ms.size(), 1, Twc16s, n_poses, q, n_q, rgb, depth, opacity, instance, hit_depth, hit_instance, ids.data(), nullptr);
+}
+// the map asked along a planner's world rays: mon_scene_cast on side 1 over the objects mon_online_render_scene composites
+int mon_online_cast_rays(mon_online* h, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, float* rgb, float* dist, float* opacity, int32_t* instance,
+        float* hit_t, float* hit_sample_t, int32_t* hit_instance) {
+    REQ(h);
+    { const int rc = scene_cast_check(1, rays, n_rays, hit_opacity, rgb, dist); if (rc) return rc; }
+    std::vector<Model*> ms; std::vector<int32_t> ids;
+    { const int rc = online_published(h, "cast_rays", ms, ids); if (rc) return rc; }
+    return scene_cast(ms.data(), ms.size(), 1, rays, n_rays, hit_opacity, rgb, dist, opacity, instance, hit_t, hit_sample_t, hit_instance, ids.data(), nullptr);
 }
 // pose refinement of one object against new observations, from its published snapshot (a frontend's call, like mon_online_render: safe while it trains)
 int mon_online_refine_pose(mon_online* h, size_t idx, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, float* Tow16_inout,

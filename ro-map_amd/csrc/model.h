@@ -344,6 +344,13 @@ void launch_scene_probe_rays(hipStream_t s, const BatchPtrs& b, const Intrinsics
         uint32_t* keys, uint32_t n);
 void launch_scene_probe_composite(hipStream_t s, uint32_t n_rays, uint32_t n_lists, uint32_t cap, const float* t, const float* attr, const uint32_t* cnt,
         const float* dn, float* rgb, float* depth, float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance);
+// Ray cast (mon_scene_cast, kernels_scene_cast.hip).  k_scene_cast_rays: one object's ray rows of n world rays clipped to [0, t_max] (dn = 1), their box
+// entries lo into entry[n], and (keys given) their keys; the keyed emit as the probe uses it; k_scene_cast_composite: k_scene_probe_composite with the
+// threshold thr, the distance undivided, and the hit placed inside its sample's interval (entry = [lists][cap]).
+void launch_scene_cast_rays(hipStream_t s, const BatchPtrs& b, const ObjectConst& oc, const mon_scene_ray* rays, uint32_t* keys, float* entry, uint32_t n);
+void launch_scene_cast_composite(hipStream_t s, uint32_t n_rays, uint32_t n_lists, uint32_t cap, float thr, const float* t, const float* attr,
+        const uint32_t* cnt, const float* entry, float* rgb, float* dist, float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t,
+        int32_t* hit_instance);
 // Pose refinement (mon_object_pose_loss / mon_object_refine_pose, kernels_pose.hip).  k_pose_rays: one record of 4 float4 per drawn ray from the pose in
 // device memory (pose[16], world -> object); k_pose_grad<shape>: loss and position gradient, one partial row of 8 floats {g, x x g, loss, 0} per workgroup
 // (pose_grad_grid of them); k_pose_update: the rows summed in a fixed order, x inv_n -> out[8 * it] = {loss, grad6, 0}, optionally the Adam step on pose.
@@ -661,12 +668,19 @@ struct SceneDump { uint32_t list; float* t; float* alpha; float* rgb; uint32_t* 
 int scene_render(Model* const* ms, size_t n, int side, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity, int32_t* instance,
                  const int32_t* ids, const SceneDump* dump);
 // Scene probe (mon_scene_probe): scene_render's conventions for side and ids (applied to both instance outputs).  scene_probe_check: every MON_ERR_ARG
-// that needs no object, no device work.  dump (mon_debug_scene_probe_rays, may be nullptr) = object k's ray rows per query, host array [n_q][10]:
-// o[3], d[3], t0, t1, flag, dn (a row that missed the box: flag 0, dn, the rest 0).
-struct SceneProbeDump { uint32_t k; float* rows; };
+// that needs no object, no device work.  dump (mon_debug_scene_probe_rays / mon_debug_scene_cast_rays, may be nullptr) = object k's ray rows per query,
+// host array [n_q][10]: o[3], d[3], t0, t1, flag, dn (a row that missed the box: flag 0, dn, the rest 0); entry (the cast only) = its entry row [n_q].
+struct SceneRaysDump { uint32_t k; float* rows; float* entry; };
 int scene_probe_check(int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, const float* rgb, const float* depth);
 int scene_probe(Model* const* ms, size_t n, int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, float* rgb, float* depth,
-                float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance, const int32_t* ids, const SceneProbeDump* dump);
+                float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance, const int32_t* ids, const SceneRaysDump* dump);
+// Ray cast (mon_scene_cast): the probe's chain over world rays; the same conventions.  scene_cast_check: every MON_ERR_ARG that needs no object.
+// scene_camera_rays (mon_camera_rays): the probe's world rays on the host, pixel_ray's world-frame branch.
+int scene_cast_check(int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, const float* rgb, const float* dist);
+int scene_cast(Model* const* ms, size_t n, int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, float* rgb, float* dist, float* opacity,
+               int32_t* instance, float* hit_t, float* hit_sample_t, int32_t* hit_instance, const int32_t* ids, const SceneRaysDump* dump);
+int scene_camera_rays(float fx, float fy, float cx, float cy, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q,
+                      mon_scene_ray* rays_out, float* dn_out);
 bool model_has_snapshot(Model& m);      // the object has an inference side and has published weights
 // Pose refinement: iters < 0 = one evaluation (mon_object_pose_loss: loss, grad6, jitter / draws of `iteration`), else iters Adam steps from Tow16
 // (mon_object_refine_pose: the final pose into pose_out, loss_trace[iters + 1] may be nullptr).  dump (mon_debug_pose_samples, may be nullptr): per drawn ray

@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <map>
 #include "model_internal.h"
 
@@ -11,10 +12,11 @@ static int scene_objects_present(const char* what, Model* const* ms, size_t n) {
     for (size_t j = 0; j < n; ++j) if (!ms[j]) { set_error("%s: null object %zu", what, j); return MON_ERR_ARG; }
     return MON_OK;
 }
-// object j sits on object 0's device and looks through its camera
-static int scene_same_camera(const char* what, const Model& m0, const Model& m, size_t j) {
+// object j sits on object 0's device and (camera: every call but the ray cast, which has no camera) looks through its camera
+static int scene_same_camera(const char* what, const Model& m0, const Model& m, size_t j, bool camera = true) {
     const Intrinsics& K = m0.ds->K; const Intrinsics& k = m.ds->K;
     if (m.device != m0.device) { set_error("%s: objects on logical devices %d and %d", what, m0.device, m.device); return MON_ERR_ARG; }
+    if (!camera) return MON_OK;
     if (k.fx != K.fx || k.fy != K.fy || k.cx != K.cx || k.cy != K.cy || k.W != K.W || k.H != K.H) {
         set_error("%s: object %zu has other intrinsics", what, j); return MON_ERR_ARG; }
     return MON_OK;
@@ -31,13 +33,13 @@ static int scene_state_check(const char* what, Model* const* ms, size_t n, int s
     }
     return MON_OK;
 }
-// what scene_render and scene_probe ask of side and objects: every MON_ERR_ARG, then every MON_ERR_STATE, no device work
-static int scene_objects_check(const char* what, Model* const* ms, size_t n, int side) {
+// what scene_render, scene_probe and scene_cast (camera false) ask of side and objects: every MON_ERR_ARG, then every MON_ERR_STATE, no device work
+static int scene_objects_check(const char* what, Model* const* ms, size_t n, int side, bool camera = true) {
     if (side != 0 && side != 1) { set_error("%s: side must be 0 or 1", what); return MON_ERR_ARG; }
     if (n == 0) { set_error("%s: no objects", what); return MON_ERR_ARG; }
     if (n > kSceneMaxLists) { set_error("%s: %zu objects (at most %u)", what, n, kSceneMaxLists); return MON_ERR_ARG; }
     { const int rc = scene_objects_present(what, ms, n); if (rc) return rc; }
-    for (size_t j = 0; j < n; ++j) { const int rc = scene_same_camera(what, *ms[0], *ms[j], j); if (rc) return rc; }
+    for (size_t j = 0; j < n; ++j) { const int rc = scene_same_camera(what, *ms[0], *ms[j], j, camera); if (rc) return rc; }
     int Lmax = 0;
     return scene_state_check(what, ms, n, side, Lmax);
 }
@@ -88,6 +90,7 @@ struct SceneWs {
     DevBuf<float> t, attr; DevBuf<uint32_t> cnt;                                  // [lists][cap][kSceneListLen] t, float4 attr; [lists][cap]
     DevBuf<float> out; PinnedBuf<float> h_out;                                    // rgb 3n | depth n | opacity n | instance n (int32)
     DevBuf<mon_scene_query> q; DevBuf<float> poses; DevBuf<uint32_t> keys;        // scene_probe: the queries, the poses [n_poses][16], a pass's keys [cap]
+    DevBuf<mon_scene_ray> rays; DevBuf<float> entry;                              // scene_cast: the rays, a pass's box entries [lists][cap]
     std::vector<hipEvent_t> ev;
 };
 // what each object renders with on a side; the render grids are the objects' own per-side caches, built if stale (their skip counters stay as they are)
@@ -162,9 +165,78 @@ int scene_render(Model* const* ms, size_t n, int side, mon_frame_bbox rect, cons
     return MON_OK;
 }
 
-// ---- scene probe (mon_scene_probe): the scene render's chain over a list of sub-pixel queries under several poses.  Passes of at most kRenderChunkRays
-// queries in the render's list workspace; per pass and object k_scene_probe_rays + the keyed emit, then k_scene_probe_composite.  Everything is enqueued at
-// once; the eight output rows go home through the pinned staging (rgb 3n | depth | opacity | instance | hit_depth | hit_instance), one synchronisation.
+// ---- the chain scene_probe and scene_cast share: a list of n_items rays of some kind against the objects, in passes of at most kRenderChunkRays in the
+// render's list workspace.  Per pass and object `rays` (the call's ray kernel: object j's ray rows of items [p0, p0 + nc), for j == 0 also the keys into
+// ws.keys) + the keyed emit, then `composite` (the call's composite of the pass, outputs at ws.out + the item's place in `rows` rows of n_items floats).
+// `upload` grows and fills what the call keeps in the workspace beside the lists.  Everything is enqueued at once; the output rows go home through the pinned
+// staging with one synchronisation, and `home` unpacks them while the workspace is still locked.  dump: object k's ray rows of every pass (and its entry row).
+struct SceneListCall {
+    const char* what; Model* const* ms; size_t n; int side; size_t n_items; uint32_t rows; bool camera;
+    std::function<int(SceneWs&, hipStream_t, uint32_t cap)> upload;
+    std::function<void(SceneWs&, hipStream_t, const SceneSrc&, Model&, size_t j, uint32_t p0, uint32_t nc, uint32_t cap)> rays;
+    std::function<void(SceneWs&, hipStream_t, uint32_t L, uint32_t cap, const float* dn, uint32_t p0, uint32_t nc)> composite;
+    std::function<void(const float* h)> home;
+    const SceneRaysDump* dump;
+};
+static int scene_list_run(const SceneListCall& c) {
+    Model* const* ms = c.ms; const size_t n = c.n, n_q = c.n_items; const int side = c.side; const SceneRaysDump* dump = c.dump;
+    if (!ms) { set_error("%s: null argument", c.what); return MON_ERR_ARG; }
+    { const int rc = scene_objects_check(c.what, ms, n, side, c.camera); if (rc) return rc; }
+    if (dump && dump->k >= n) { set_error("%s: dump of object %u of %zu", c.what, dump->k, n); return MON_ERR_ARG; }
+    const int device = ms[0]->device;
+    HIPCHECK(use_device(device));
+    const uint32_t nq = (uint32_t)n_q, cap = std::min(nq, kRenderChunkRays), L = (uint32_t)n;
+    SceneWs& ws = side_ws<SceneWs>(device, side);
+    SceneSide sd; { const int rc = sd.enter(ms, n, side, ws.mu, ws.ev); if (rc) return rc; }
+    const hipStream_t s = sd.s;
+    const std::vector<SceneSrc> src = scene_sources(ms, n, side, sd);
+    const size_t need_lists = (size_t)L * cap;
+    {   int rc;
+        if ((rc = ws.t.grow(need_lists * kSceneListLen)) || (rc = ws.attr.grow(need_lists * kSceneListLen * 4)) || (rc = ws.cnt.grow(need_lists)) ||
+            (rc = ws.out.grow(c.rows * n_q)) || (rc = ws.h_out.grow(c.rows * n_q)) || (rc = ws.keys.grow(cap)) || (rc = c.upload(ws, s, cap))) return rc; }
+    std::vector<float> d_o, d_d, d_t0, d_t1, d_dn; std::vector<uint8_t> d_flag;       // the dump: object k's ray rows of every pass
+    if (dump) { d_o.resize(3 * n_q); d_d.resize(3 * n_q); d_t0.resize(n_q); d_t1.resize(n_q); d_dn.resize(n_q); d_flag.resize(n_q); }
+    for (uint32_t p0 = 0; p0 < nq; p0 += cap) {
+        const uint32_t nc = std::min(cap, nq - p0);
+        for (size_t j = 0; j < n; ++j) {
+            Model& m = *ms[j]; const size_t l0 = j * (size_t)cap;
+            c.rays(ws, s, src[j], m, j, p0, nc, cap);
+            launch_fused_render_emit(s, m.lf, m.nd, sd.prm[j], *src[j].b, m.oc, nc, 0u, ws.t.p + l0 * kSceneListLen, ws.attr.p + l0 * kSceneListLen * 4,
+                    ws.cnt.p + l0, src[j].frag, p0 == 0u, src[j].bits, ws.keys.p);
+        }
+        // (every object's ray kernel wrote the same dn: it depends on the item alone)
+        c.composite(ws, s, L, cap, src[0].b->ray_dn, p0, nc);
+        if (dump) {
+            const BatchPtrs& b = *src[dump->k].b;
+            HIPCHECK(hipMemcpyAsync(d_o.data() + 3 * (size_t)p0, b.ray_o, 12 * (size_t)nc, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipMemcpyAsync(d_d.data() + 3 * (size_t)p0, b.ray_d, 12 * (size_t)nc, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipMemcpyAsync(d_t0.data() + p0, b.ray_t0, 4 * (size_t)nc, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipMemcpyAsync(d_t1.data() + p0, b.ray_t1, 4 * (size_t)nc, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipMemcpyAsync(d_dn.data() + p0, b.ray_dn, 4 * (size_t)nc, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipMemcpyAsync(d_flag.data() + p0, b.ray_flag, (size_t)nc, hipMemcpyDeviceToHost, s));
+            if (dump->entry) HIPCHECK(hipMemcpyAsync(dump->entry + p0, ws.entry.p + dump->k * (size_t)cap, 4 * (size_t)nc, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipStreamSynchronize(s));
+        }
+    }
+    launch_copy_params(s, reinterpret_cast<const uint16_t*>(ws.out.p), reinterpret_cast<uint16_t*>(ws.h_out.p), (uint32_t)(2 * c.rows * n_q));
+    HIPCHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    c.home(ws.h_out.p);
+    if (dump) for (size_t i = 0; i < n_q; ++i) {                                        // (a row that missed the box holds only flag and dn)
+        float* r = dump->rows + 10 * i; const bool hit = d_flag[i] != 0;
+        for (int a = 0; a < 3; ++a) { r[a] = hit ? d_o[3 * i + a] : 0.f; r[3 + a] = hit ? d_d[3 * i + a] : 0.f; }
+        r[6] = hit ? d_t0[i] : 0.f; r[7] = hit ? d_t1[i] : 0.f; r[8] = hit ? 1.f : 0.f; r[9] = d_dn[i];
+    }
+    return MON_OK;
+}
+// an instance row home: the call's list indices, or the caller's ids for them
+static void scene_instances_home(int32_t* out, const float* row, size_t n, const int32_t* ids) {
+    const int32_t* q = reinterpret_cast<const int32_t*>(row);
+    if (out) for (size_t i = 0; i < n; ++i) out[i] = (q[i] >= 0 && ids) ? ids[q[i]] : q[i];
+}
+
+// ---- scene probe (mon_scene_probe): the chain over a list of sub-pixel queries under several poses: k_scene_probe_rays, k_scene_probe_composite; eight
+// output rows (rgb 3n | depth | opacity | instance | hit_depth | hit_instance).
 int scene_probe_check(int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, const float* rgb, const float* depth) {
     if (!Twc16s || !q || !rgb || !depth) { set_error("scene_probe: null argument"); return MON_ERR_ARG; }
     if (side != 0 && side != 1) { set_error("scene_probe: side must be 0 or 1"); return MON_ERR_ARG; }
@@ -179,67 +251,100 @@ int scene_probe_check(int side, const float* Twc16s, size_t n_poses, const mon_s
     return MON_OK;
 }
 int scene_probe(Model* const* ms, size_t n, int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, float* rgb, float* depth,
-                float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance, const int32_t* ids, const SceneProbeDump* dump) {
+                float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance, const int32_t* ids, const SceneRaysDump* dump) {
     if (!ms) { set_error("scene_probe: null argument"); return MON_ERR_ARG; }
     { const int rc = scene_probe_check(side, Twc16s, n_poses, q, n_q, rgb, depth); if (rc) return rc; }
-    { const int rc = scene_objects_check("scene_probe", ms, n, side); if (rc) return rc; }
-    if (dump && dump->k >= n) { set_error("scene_probe: dump of object %u of %zu", dump->k, n); return MON_ERR_ARG; }
-    const Intrinsics K = ms[0]->ds->K; const int device = ms[0]->device;
-    HIPCHECK(use_device(device));
-    const uint32_t nq = (uint32_t)n_q, cap = std::min(nq, kRenderChunkRays), L = (uint32_t)n;
-    SceneWs& ws = side_ws<SceneWs>(device, side);
-    SceneSide sd; { const int rc = sd.enter(ms, n, side, ws.mu, ws.ev); if (rc) return rc; }
-    const hipStream_t s = sd.s;
-    const std::vector<SceneSrc> src = scene_sources(ms, n, side, sd);
-    const size_t need_lists = (size_t)L * cap;
-    {   int rc;
-        if ((rc = ws.t.grow(need_lists * kSceneListLen)) || (rc = ws.attr.grow(need_lists * kSceneListLen * 4)) || (rc = ws.cnt.grow(need_lists)) ||
-            (rc = ws.out.grow(8 * n_q)) || (rc = ws.h_out.grow(8 * n_q)) || (rc = ws.q.grow(n_q)) || (rc = ws.poses.grow(16 * n_poses)) ||
-            (rc = ws.keys.grow(cap))) return rc; }
-    HIPCHECK(hipMemcpyAsync(ws.q.p, q, sizeof(mon_scene_query) * n_q, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(ws.poses.p, Twc16s, 64 * n_poses, hipMemcpyHostToDevice, s));
-    float* o_rgb = ws.out.p; float* o_depth = o_rgb + 3 * n_q; float* o_op = o_depth + n_q; int32_t* o_inst = reinterpret_cast<int32_t*>(o_op + n_q);
-    float* o_hd = o_op + 2 * n_q; int32_t* o_hi = reinterpret_cast<int32_t*>(o_hd + n_q);
-    std::vector<float> d_o, d_d, d_t0, d_t1, d_dn; std::vector<uint8_t> d_flag;       // mon_debug_scene_probe_rays: object k's ray rows of every pass
-    if (dump) { d_o.resize(3 * n_q); d_d.resize(3 * n_q); d_t0.resize(n_q); d_t1.resize(n_q); d_dn.resize(n_q); d_flag.resize(n_q); }
-    for (uint32_t p0 = 0; p0 < nq; p0 += cap) {
-        const uint32_t nc = std::min(cap, nq - p0);
-        for (size_t j = 0; j < n; ++j) {
-            Model& m = *ms[j]; const size_t l0 = j * (size_t)cap;
-            launch_scene_probe_rays(s, *src[j].b, K, m.oc, ws.q.p + p0, ws.poses.p, j == 0 ? ws.keys.p : nullptr, nc);
-            launch_fused_render_emit(s, m.lf, m.nd, sd.prm[j], *src[j].b, m.oc, nc, 0u, ws.t.p + l0 * kSceneListLen, ws.attr.p + l0 * kSceneListLen * 4,
-                    ws.cnt.p + l0, src[j].frag, p0 == 0u, src[j].bits, ws.keys.p);
+    SceneListCall c{ "scene_probe", ms, n, side, n_q, 8u, true, {}, {}, {}, {}, dump };
+    c.upload = [&](SceneWs& ws, hipStream_t s, uint32_t) -> int {
+        int rc; if ((rc = ws.q.grow(n_q)) || (rc = ws.poses.grow(16 * n_poses))) return rc;
+        HIPCHECK(hipMemcpyAsync(ws.q.p, q, sizeof(mon_scene_query) * n_q, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(ws.poses.p, Twc16s, 64 * n_poses, hipMemcpyHostToDevice, s));
+        return MON_OK;
+    };
+    c.rays = [&](SceneWs& ws, hipStream_t s, const SceneSrc& src, Model& m, size_t j, uint32_t p0, uint32_t nc, uint32_t) {
+        launch_scene_probe_rays(s, *src.b, ms[0]->ds->K, m.oc, ws.q.p + p0, ws.poses.p, j == 0 ? ws.keys.p : nullptr, nc);
+    };
+    c.composite = [&](SceneWs& ws, hipStream_t s, uint32_t L, uint32_t cap, const float* dn, uint32_t p0, uint32_t nc) {
+        float* o = ws.out.p;
+        launch_scene_probe_composite(s, nc, L, cap, ws.t.p, ws.attr.p, ws.cnt.p, dn, o + 3 * (size_t)p0, o + 3 * n_q + p0, o + 4 * n_q + p0,
+                reinterpret_cast<int32_t*>(o + 5 * n_q) + p0, o + 6 * n_q + p0, reinterpret_cast<int32_t*>(o + 7 * n_q) + p0);
+    };
+    c.home = [&](const float* h) {
+        std::memcpy(rgb, h, 12 * n_q); std::memcpy(depth, h + 3 * n_q, 4 * n_q);
+        if (opacity) std::memcpy(opacity, h + 4 * n_q, 4 * n_q);
+        if (hit_depth) std::memcpy(hit_depth, h + 6 * n_q, 4 * n_q);
+        scene_instances_home(instance, h + 5 * n_q, n_q, ids); scene_instances_home(hit_instance, h + 7 * n_q, n_q, ids);
+    };
+    return scene_list_run(c);
+}
+
+// ---- ray cast (mon_scene_cast): the chain over a list of world rays: k_scene_cast_rays, k_scene_cast_composite; nine output rows (rgb 3n | dist | opacity
+// | instance | hit_t | hit_sample_t | hit_instance).  No camera: the objects need only share a device.
+int scene_cast_check(int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, const float* rgb, const float* dist) {
+    if (!rays || !rgb || !dist) { set_error("scene_cast: null argument"); return MON_ERR_ARG; }
+    if (side != 0 && side != 1) { set_error("scene_cast: side must be 0 or 1"); return MON_ERR_ARG; }
+    if (n_rays == 0 || n_rays > kSceneProbeMaxQueries) { set_error("scene_cast: %zu rays (1 to %u)", n_rays, kSceneProbeMaxQueries); return MON_ERR_ARG; }
+    if (!(hit_opacity > 0.f && hit_opacity <= 0.999f)) { set_error("scene_cast: hit_opacity %g (above 0, at most 0.999)", (double)hit_opacity); return MON_ERR_ARG; }
+    for (size_t i = 0; i < n_rays; ++i) {
+        const mon_scene_ray& r = rays[i];
+        if (r.key >= kSceneProbeMaxKey) { set_error("scene_cast: ray %zu has key %u (below %u)", i, r.key, kSceneProbeMaxKey); return MON_ERR_ARG; }
+        float nn = 0.f;
+        for (int a = 0; a < 3; ++a) {
+            if (!std::isfinite(r.o[a]) || !std::isfinite(r.d[a])) { set_error("scene_cast: ray %zu is not finite", i); return MON_ERR_ARG; }
+            nn += r.d[a] * r.d[a];
         }
-        // (every object's ray kernel wrote the same dn: it depends on the query and the intrinsics only)
-        launch_scene_probe_composite(s, nc, L, cap, ws.t.p, ws.attr.p, ws.cnt.p, src[0].b->ray_dn, o_rgb + 3 * (size_t)p0, o_depth + p0, o_op + p0, o_inst + p0,
-                o_hd + p0, o_hi + p0);
-        if (dump) {
-            const BatchPtrs& b = *src[dump->k].b;
-            HIPCHECK(hipMemcpyAsync(d_o.data() + 3 * (size_t)p0, b.ray_o, 12 * (size_t)nc, hipMemcpyDeviceToHost, s));
-            HIPCHECK(hipMemcpyAsync(d_d.data() + 3 * (size_t)p0, b.ray_d, 12 * (size_t)nc, hipMemcpyDeviceToHost, s));
-            HIPCHECK(hipMemcpyAsync(d_t0.data() + p0, b.ray_t0, 4 * (size_t)nc, hipMemcpyDeviceToHost, s));
-            HIPCHECK(hipMemcpyAsync(d_t1.data() + p0, b.ray_t1, 4 * (size_t)nc, hipMemcpyDeviceToHost, s));
-            HIPCHECK(hipMemcpyAsync(d_dn.data() + p0, b.ray_dn, 4 * (size_t)nc, hipMemcpyDeviceToHost, s));
-            HIPCHECK(hipMemcpyAsync(d_flag.data() + p0, b.ray_flag, (size_t)nc, hipMemcpyDeviceToHost, s));
-            HIPCHECK(hipStreamSynchronize(s));
-        }
+        if (!(std::fabs(nn - 1.f) <= 1e-3f)) { set_error("scene_cast: the direction of ray %zu is not unit (|d|^2 = %g)", i, (double)nn); return MON_ERR_ARG; }
+        if (!(r.t_max > 0.f)) { set_error("scene_cast: ray %zu has t_max %g (above 0)", i, (double)r.t_max); return MON_ERR_ARG; }
     }
-    launch_copy_params(s, reinterpret_cast<const uint16_t*>(ws.out.p), reinterpret_cast<uint16_t*>(ws.h_out.p), (uint32_t)(16 * n_q));
-    HIPCHECK(hipStreamSynchronize(s));
-    HIPCHECK(hipGetLastError());
-    const float* h = ws.h_out.p;
-    std::memcpy(rgb, h, 12 * n_q); std::memcpy(depth, h + 3 * n_q, 4 * n_q);
-    if (opacity) std::memcpy(opacity, h + 4 * n_q, 4 * n_q);
-    if (hit_depth) std::memcpy(hit_depth, h + 6 * n_q, 4 * n_q);
-    const int32_t* h_inst = reinterpret_cast<const int32_t*>(h + 5 * n_q); const int32_t* h_hi = reinterpret_cast<const int32_t*>(h + 7 * n_q);
+    return MON_OK;
+}
+int scene_cast(Model* const* ms, size_t n, int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, float* rgb, float* dist, float* opacity,
+               int32_t* instance, float* hit_t, float* hit_sample_t, int32_t* hit_instance, const int32_t* ids, const SceneRaysDump* dump) {
+    if (!ms) { set_error("scene_cast: null argument"); return MON_ERR_ARG; }
+    { const int rc = scene_cast_check(side, rays, n_rays, hit_opacity, rgb, dist); if (rc) return rc; }
+    const size_t n_q = n_rays;
+    SceneListCall c{ "scene_cast", ms, n, side, n_q, 9u, false, {}, {}, {}, {}, dump };
+    c.upload = [&](SceneWs& ws, hipStream_t s, uint32_t cap) -> int {
+        int rc; if ((rc = ws.rays.grow(n_q)) || (rc = ws.entry.grow(n * (size_t)cap))) return rc;
+        HIPCHECK(hipMemcpyAsync(ws.rays.p, rays, sizeof(mon_scene_ray) * n_q, hipMemcpyHostToDevice, s));
+        return MON_OK;
+    };
+    c.rays = [&](SceneWs& ws, hipStream_t s, const SceneSrc& src, Model& m, size_t j, uint32_t p0, uint32_t nc, uint32_t cap) {
+        launch_scene_cast_rays(s, *src.b, m.oc, ws.rays.p + p0, j == 0 ? ws.keys.p : nullptr, ws.entry.p + j * (size_t)cap, nc);
+    };
+    c.composite = [&](SceneWs& ws, hipStream_t s, uint32_t L, uint32_t cap, const float*, uint32_t p0, uint32_t nc) {
+        float* o = ws.out.p;
+        launch_scene_cast_composite(s, nc, L, cap, hit_opacity, ws.t.p, ws.attr.p, ws.cnt.p, ws.entry.p, o + 3 * (size_t)p0, o + 3 * n_q + p0, o + 4 * n_q + p0,
+                reinterpret_cast<int32_t*>(o + 5 * n_q) + p0, o + 6 * n_q + p0, o + 7 * n_q + p0, reinterpret_cast<int32_t*>(o + 8 * n_q) + p0);
+    };
+    c.home = [&](const float* h) {
+        std::memcpy(rgb, h, 12 * n_q); std::memcpy(dist, h + 3 * n_q, 4 * n_q);
+        if (opacity) std::memcpy(opacity, h + 4 * n_q, 4 * n_q);
+        if (hit_t) std::memcpy(hit_t, h + 6 * n_q, 4 * n_q);
+        if (hit_sample_t) std::memcpy(hit_sample_t, h + 7 * n_q, 4 * n_q);
+        scene_instances_home(instance, h + 5 * n_q, n_q, ids); scene_instances_home(hit_instance, h + 8 * n_q, n_q, ids);
+    };
+    return scene_list_run(c);
+}
+// mon_camera_rays: pixel_ray's world-frame branch (pose_is_Toc: the pose alone, no object) on the host -- the operations k_scene_probe_rays runs before it
+// applies an object's Tow, which k_scene_cast_rays applies to these rays in the same way
+int scene_camera_rays(float fx, float fy, float cx, float cy, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q,
+                      mon_scene_ray* rays_out, float* dn_out) {
+    if (!Twc16s || !q || !rays_out) { set_error("camera_rays: null argument"); return MON_ERR_ARG; }
+    if (n_poses == 0 || n_q == 0) { set_error("camera_rays: no poses or no queries"); return MON_ERR_ARG; }
+    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy) || fx == 0.f || fy == 0.f) {
+        set_error("camera_rays: intrinsics not finite or a zero focal length"); return MON_ERR_ARG; }
+    for (size_t k = 0; k < 16 * n_poses; ++k) if (!std::isfinite(Twc16s[k])) { set_error("camera_rays: pose %zu is not finite", k / 16); return MON_ERR_ARG; }
     for (size_t i = 0; i < n_q; ++i) {
-        if (instance) instance[i] = (h_inst[i] >= 0 && ids) ? ids[h_inst[i]] : h_inst[i];
-        if (hit_instance) hit_instance[i] = (h_hi[i] >= 0 && ids) ? ids[h_hi[i]] : h_hi[i];
+        if (q[i].pose >= n_poses) { set_error("camera_rays: query %zu names pose %u of %zu", i, q[i].pose, n_poses); return MON_ERR_ARG; }
+        if (!std::isfinite(q[i].u) || !std::isfinite(q[i].v)) { set_error("camera_rays: query %zu is not finite", i); return MON_ERR_ARG; }
     }
-    if (dump) for (size_t i = 0; i < n_q; ++i) {                                        // (a row that missed the box holds only flag and dn)
-        float* r = dump->rows + 10 * i; const bool hit = d_flag[i] != 0;
-        for (int a = 0; a < 3; ++a) { r[a] = hit ? d_o[3 * i + a] : 0.f; r[3 + a] = hit ? d_d[3 * i + a] : 0.f; }
-        r[6] = hit ? d_t0[i] : 0.f; r[7] = hit ? d_t1[i] : 0.f; r[8] = hit ? 1.f : 0.f; r[9] = d_dn[i];
+    const Intrinsics K{ fx, fy, cx, cy, 0, 0 };
+    for (size_t i = 0; i < n_q; ++i) {
+        mon_scene_ray& r = rays_out[i]; float dn;
+        pixel_ray(K, q[i].u, q[i].v, Twc16s + 16 * (size_t)q[i].pose, nullptr, true, r.o, r.d, dn);
+        r.t_max = INFINITY; r.key = q[i].key;
+        if (dn_out) dn_out[i] = dn;
     }
     return MON_OK;
 }

@@ -1,7 +1,8 @@
 // scene_device.h -- device code shared by the merge-composite kernels of the scene render (k_scene_composite, kernels_render.hip), of camera refinement
 // (k_scene_composite_grad, kernels_scene_pose.hip) and of batched pose scoring (k_scene_composite_loss, kernels_scene_score.hip): the compaction of one ray's
 // non-empty sample lists and the merged order of their samples; the composite walk of the merged sequence and its outputs, shared by the render's composite
-// and the probe's (k_scene_probe_composite, kernels_scene_probe.hip), which adds the first hit; one drawn ray's targets and per-object records under a camera pose; the composite forward of
+// and the probe's (k_scene_probe_composite, kernels_scene_probe.hip), which adds the first hit, and the ray cast's (k_scene_cast_composite,
+// kernels_scene_cast.hip), which places the hit inside its sample's interval; one drawn ray's targets and per-object records under a camera pose; the composite forward of
 // one ray with its loss; the tail of an evaluation (rows -> camera-frame gradient, the Adam steps on a camera and on an object twist) shared with window
 // refinement (kernels_scene_window.hip).
 #pragma once
@@ -64,21 +65,26 @@ __device__ __forceinline__ void scene_merge_lists(uint32_t ray, uint32_t n_lists
 // carried transmittance.  Each half-wave scans its 32 samples as k_fused_render scans a tile, and the sums are added half by half, so one object's list
 // composites to exactly that render's arithmetic.  Per-list weight sums (one wave reduction per list present in a block) go to s_w.
 // HIT (the probe): also the first merged sample after which 1 - T > 0.5 -- one ballot per block, the wave stays uniform: its t and compact list.
+// CAST (the ray cast, k_scene_cast_composite; with HIT): the threshold is the argument thr in place of 0.5, and the crossing lane also yields, through
+// readlanes, the transmittance in front of its sample as the walk carries it (hit_T), the sample's alpha and its slot in its own list.
 // Every lane returns the same values.
-struct SceneWalk { float Tc, r0, r1, r2, dep, hit_t; uint32_t hit_a; bool hit; };
-template <bool HIT>
+struct SceneWalk { float Tc, r0, r1, r2, dep, hit_t; uint32_t hit_a; bool hit; float hit_T, hit_alpha; uint32_t hit_slot; };
+template <bool HIT, bool CAST = false>
 __device__ __forceinline__ void scene_composite_walk(uint32_t ray, uint32_t cap, uint32_t na, uint32_t n_tot, const float* __restrict__ tl,
-        const float4* __restrict__ attr, int lane, const uint16_t* s_perm, const uint32_t* s_id, float* s_w, SceneWalk& w) {
+        const float4* __restrict__ attr, int lane, const uint16_t* s_perm, const uint32_t* s_id, float* s_w, SceneWalk& w, float thr = 0.5f) {
+    static_assert(HIT || !CAST, "CAST extends HIT");
     constexpr uint32_t L2S = kSceneListLen;
     float Tc = 1.f, r0 = 0.f, r1 = 0.f, r2 = 0.f, dep = 0.f;
     w.hit = false; w.hit_t = 0.f; w.hit_a = 0u;
+    if constexpr (CAST) { w.hit_T = 1.f; w.hit_alpha = 0.f; w.hit_slot = 0u; }
     for (uint32_t base = 0; base < n_tot; base += 64u) {
         const uint32_t p = base + (uint32_t)lane;
-        float tv = 0.f, al = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f; uint32_t a = ~0u;
+        float tv = 0.f, al = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f; uint32_t a = ~0u, slot = 0u;
         if (p < n_tot) {
             const uint32_t e = s_perm[p];
             if ((e >> 6) < na) {
                 a = e >> 6;
+                if constexpr (CAST) slot = e & 63u;
                 const size_t idx = ((size_t)s_id[a] * cap + ray) * L2S + (e & 63u);
                 const float4 v = attr[idx]; tv = tl[idx]; al = v.x; c0 = v.y; c1 = v.z; c2 = v.w;
             }
@@ -96,10 +102,11 @@ __device__ __forceinline__ void scene_composite_walk(uint32_t ray, uint32_t cap,
         r0 += lane_bcast(x0, 63); r1 += lane_bcast(x1, 63); r2 += lane_bcast(x2, 63); dep += lane_bcast(xd, 63);
         if constexpr (HIT) {
             // (a slot that holds no sample has alpha 0 and cannot be the first to cross)
-            const unsigned long long cross = __ballot(a != ~0u && 1.f - incl > 0.5f);
+            const unsigned long long cross = __ballot(a != ~0u && 1.f - incl > (CAST ? thr : 0.5f));
             if (!w.hit && cross) {
                 const int l = (int)__builtin_ctzll(cross);
                 w.hit = true; w.hit_t = lane_bcast(tv, l); w.hit_a = (uint32_t)__builtin_amdgcn_readlane((int)a, l);
+                if constexpr (CAST) { w.hit_T = lane_bcast(T, l); w.hit_alpha = lane_bcast(al, l); w.hit_slot = (uint32_t)__builtin_amdgcn_readlane((int)slot, l); }
             }
         }
         // per-list weight sums: one reduction per list present in the block
@@ -117,13 +124,15 @@ __device__ __forceinline__ void scene_composite_walk(uint32_t ray, uint32_t cap,
     }
     w.Tc = Tc; w.r0 = r0; w.r1 = r1; w.r2 = r2; w.dep = dep;
 }
-// ... and what one lane writes of it: mon_scene_render's four outputs of the ray
+// ... and what one lane writes of it: mon_scene_render's four outputs of the ray (DN false, the ray cast: the distance sum w t itself, dn is not read)
+template <bool DN = true>
 __device__ __forceinline__ void scene_composite_store(uint32_t ray, uint32_t na, const uint32_t* s_id, const float* s_w, const SceneWalk& w,
         const float* __restrict__ dn, float* __restrict__ out_rgb, float* __restrict__ out_depth, float* __restrict__ out_opacity,
         int32_t* __restrict__ out_instance) {
     const float Tc = w.Tc, op = 1.f - Tc;
     out_rgb[3 * (size_t)ray] = w.r0 + Tc; out_rgb[3 * (size_t)ray + 1] = w.r1 + Tc; out_rgb[3 * (size_t)ray + 2] = w.r2 + Tc;
-    out_depth[ray] = op > 0.5f ? w.dep / dn[ray] : 0.f;
+    if constexpr (DN) out_depth[ray] = op > 0.5f ? w.dep / dn[ray] : 0.f;
+    else out_depth[ray] = op > 0.5f ? w.dep : 0.f;
     out_opacity[ray] = op;
     int32_t inst = -1;
     if (op > 0.5f) { float best = -1.f; for (uint32_t a = 0; a < na; ++a) if (s_w[a] > best) { best = s_w[a]; inst = (int32_t)s_id[a]; } }
