@@ -1,4 +1,5 @@
-// c_api.cpp -- extern "C" surface declared in include/mon_core.h.
+// c_api.cpp -- extern "C" surface declared in include/mon_core.h.  The scene and pose routes enter through the boundary of model.h: their checks are in
+// scene.cpp and pose.cpp, shared with manager.cpp and diag.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -108,30 +109,26 @@ int mon_object_render_skip_stats(mon_object* o, int side, mon_render_skip_stats*
     return model_render_skip_stats(*o->m, side, out); }
 int mon_object_render_occupancy(mon_object* o, int side, int dilated, uint32_t* bits) { REQUIRE(o, "object"); REQUIRE(bits, "bits");
     return model_render_occupancy(*o->m, side, dilated, bits); }
+// ---- the scene routes, each in the four steps of model.h's boundary: its check, the models, its objects' check, the route
 int mon_scene_render(mon_object* const* objs, size_t n_objs, int side, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity,
         int32_t* instance) {
-    REQUIRE(objs, "objs"); REQUIRE(Twc16, "Twc16"); REQUIRE(rgb, "rgb"); REQUIRE(depth, "depth");
-    if (n_objs == 0 || rect.w == 0 || rect.h == 0) { set_error("scene_render: empty object list or rect"); return MON_ERR_ARG; }
-    std::vector<Model*> ms(n_objs);
-    for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_render_check(side, rect, Twc16)) || (rc = scene_render_outputs_check(rgb, depth)) || (rc = scene_models("scene_render", objs, n_objs, ms)) ||
+        (rc = scene_objects_check("scene_render", ms.data(), n_objs))) return rc;
     return scene_render(ms.data(), n_objs, side, rect, Twc16, rgb, depth, opacity, instance, nullptr, nullptr);
 }
 int mon_scene_probe(mon_object* const* objs, size_t n_objs, int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, float* rgb,
         float* depth, float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance) {
-    REQUIRE(objs, "objs");
-    { const int rc = scene_probe_check(side, Twc16s, n_poses, q, n_q, rgb, depth); if (rc) return rc; }
-    if (n_objs == 0 || n_objs > kSceneMaxLists) { set_error("scene_probe: %zu objects (1 to %u)", n_objs, kSceneMaxLists); return MON_ERR_ARG; }
-    std::vector<Model*> ms(n_objs);
-    for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_probe_check(side, Twc16s, n_poses, q, n_q, rgb, depth)) || (rc = scene_models("scene_probe", objs, n_objs, ms)) ||
+        (rc = scene_objects_check("scene_probe", ms.data(), n_objs))) return rc;
     return scene_probe(ms.data(), n_objs, side, Twc16s, n_poses, q, n_q, rgb, depth, opacity, instance, hit_depth, hit_instance, nullptr, nullptr);
 }
 int mon_scene_cast(mon_object* const* objs, size_t n_objs, int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, float* rgb, float* dist,
         float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t, int32_t* hit_instance) {
-    REQUIRE(objs, "objs");
-    { const int rc = scene_cast_check(side, rays, n_rays, hit_opacity, rgb, dist); if (rc) return rc; }
-    if (n_objs == 0 || n_objs > kSceneMaxLists) { set_error("scene_cast: %zu objects (1 to %u)", n_objs, kSceneMaxLists); return MON_ERR_ARG; }
-    std::vector<Model*> ms(n_objs);
-    for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_cast_check(side, rays, n_rays, hit_opacity, rgb, dist)) || (rc = scene_models("scene_cast", objs, n_objs, ms)) ||
+        (rc = scene_objects_check("scene_cast", ms.data(), n_objs, false))) return rc;
     return scene_cast(ms.data(), n_objs, side, rays, n_rays, hit_opacity, rgb, dist, opacity, instance, hit_t, hit_sample_t, hit_instance, nullptr, nullptr);
 }
 int mon_camera_rays(float fx, float fy, float cx, float cy, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, mon_scene_ray* rays_out,
@@ -144,59 +141,36 @@ int mon_pose_refine_default(mon_pose_refine_params* p) {
     p->w_rgb = 1.f; p->w_mask = 1.f; p->w_depth = 1.f; p->depth_huber = 0.05f; p->seed = 1;
     return MON_OK;
 }
-// every argument that can be judged without the object is judged before it is touched
-static int pose_args(const mon_object* o, int side, const mon_frame_bbox* obs, size_t n_obs, const float* pose, const mon_pose_refine_params* p) {
-    REQUIRE(o, "object"); REQUIRE(obs, "obs"); REQUIRE(pose, "pose"); REQUIRE(p, "params");
-    if (n_obs == 0) { set_error("pose: no boxes"); return MON_ERR_ARG; }
-    if (p->iters < 0) { set_error("pose: iters %d < 0", p->iters); return MON_ERR_ARG; }
-    if (side != 0 && side != 1) { set_error("pose: side %d (0 or 1)", side); return MON_ERR_ARG; }
-    return MON_OK;
-}
 int mon_object_pose_loss(mon_object* o, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params* p,
         uint32_t iteration, float* loss, float* grad6) {
-    const int rc = pose_args(o, side, obs, n_obs, Tow16, p); if (rc) return rc;
+    REQUIRE(o, "object");
+    const int rc = pose_check(side, obs, n_obs, Tow16, p); if (rc) return rc;
     return pose_refine(*o->m, side, obs, n_obs, Tow16, *p, -1, iteration, nullptr, nullptr, loss, grad6, nullptr);
 }
 int mon_object_refine_pose(mon_object* o, int side, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, float* Tow16_inout,
         float* loss_trace) {
-    const int rc = pose_args(o, side, obs, n_obs, Tow16_inout, p); if (rc) return rc;
-    float pose[16]; std::memcpy(pose, Tow16_inout, 64);
-    const int r2 = pose_refine(*o->m, side, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr);
-    if (r2 == MON_OK) std::memcpy(Tow16_inout, pose, 64);
-    return r2;
+    REQUIRE(o, "object");
+    const int rc = pose_check(side, obs, n_obs, Tow16_inout, p); if (rc) return rc;
+    return pose_inout(Tow16_inout, [&](float* pose) {
+        return pose_refine(*o->m, side, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr); });
 }
-// ---- coarse-to-fine level weights (BARF window over the levels, alpha in levels from level_start to level_end over the first ramp * iters steps)
 // ---- camera refinement against a scene of objects
-static int scene_pose_models(mon_object* const* objs, size_t n_objs, std::vector<Model*>& ms) {
-    REQUIRE(objs, "objs");
-    if (n_objs == 0 || n_objs > kSceneMaxLists) { set_error("scene pose: %zu objects (1 to %u)", n_objs, kSceneMaxLists); return MON_ERR_ARG; }
-    ms.resize(n_objs);
-    for (size_t j = 0; j < n_objs; ++j) { if (!objs[j] || !objs[j]->m) { set_error("scene pose: null object %zu", j); return MON_ERR_ARG; } ms[j] = objs[j]->m; }
-    return MON_OK;
-}
-static int level_weights_check(const float* w, int n) {
-    for (int l = 0; l < n; ++l)
-        if (!std::isfinite(w[l]) || w[l] < 0.f) { set_error("scene pose: level weight %d is %g (finite, >= 0)", l, w[l]); return MON_ERR_ARG; }
-    return MON_OK;
-}
 int mon_scene_pose_loss(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16,
                         const mon_pose_refine_params* p, uint32_t iteration, const float* level_weights, float* loss, float* grad6) {
-    std::vector<Model*> ms; int rc = scene_pose_models(objs, n_objs, ms); if (rc) return rc;
-    if ((rc = scene_pose_check(ms.data(), n_objs, side, obs, n_obs, Twc16, p))) return rc;
-    if (level_weights) { int Lmax = 0; for (Model* m : ms) Lmax = std::max(Lmax, (int)m->nd.L); if ((rc = level_weights_check(level_weights, Lmax))) return rc; }
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_pose_check(side, obs, n_obs, Twc16, p)) || (rc = scene_models("scene pose", objs, n_objs, ms)) ||
+        (rc = scene_pose_objects_check(ms.data(), n_objs, obs, n_obs, p))) return rc;
+    if (level_weights && (rc = level_weights_check("scene pose", level_weights, scene_levels(ms.data(), n_objs).Lmax))) return rc;
     return scene_pose(ms.data(), n_objs, side, obs, n_obs, Twc16, *p, -1, iteration, nullptr, nullptr, loss, grad6, nullptr, level_weights);
 }
 int mon_scene_refine_camera(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p,
                             const mon_pose_c2f_params* c, float* Twc16_inout, float* loss_trace) {
-    std::vector<Model*> ms; int rc = scene_pose_models(objs, n_objs, ms); if (rc) return rc;
-    if ((rc = scene_pose_check(ms.data(), n_objs, side, obs, n_obs, Twc16_inout, p))) return rc;
-    if (c && (rc = pose_c2f_check(c))) return rc;
-    int Lmax = 0; for (Model* m : ms) Lmax = std::max(Lmax, (int)m->nd.L);
-    std::vector<float> table; if (c) table = pose_c2f_table(*c, Lmax, p->iters);
-    float pose[16]; std::memcpy(pose, Twc16_inout, 64);
-    rc = scene_pose(ms.data(), n_objs, side, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr, table.empty() ? nullptr : table.data());
-    if (rc == MON_OK) std::memcpy(Twc16_inout, pose, 64);
-    return rc;
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_pose_check(side, obs, n_obs, Twc16_inout, p)) || (rc = scene_models("scene pose", objs, n_objs, ms)) ||
+        (rc = scene_pose_objects_check(ms.data(), n_objs, obs, n_obs, p)) || (c && (rc = pose_c2f_check(c)))) return rc;
+    const SceneLevels lv = scene_levels(ms.data(), n_objs, c, p->iters);
+    return pose_inout(Twc16_inout, [&](float* pose) {
+        return scene_pose(ms.data(), n_objs, side, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr, lv.w()); });
 }
 // ---- joint refinement of a window of camera poses and object poses
 int mon_window_default(mon_window_params* w) {
@@ -210,33 +184,30 @@ int mon_window_frames(const mon_frame_bbox* obs, size_t n_obs, uint32_t* frame_i
 int mon_scene_window_loss(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const float* Tow16s,
                           const mon_pose_refine_params* p, uint32_t iteration, const float* level_weights, float* loss, float* frame_loss, float* cam_grad6,
                           float* obj_grad6) {
-    int rc = scene_window_params_check(obs, n_obs, Twc16s, p, nullptr, Tow16s, false); if (rc) return rc;
-    std::vector<Model*> ms; if ((rc = scene_pose_models(objs, n_objs, ms))) return rc;
-    if (level_weights) { int Lmax = 0; for (Model* m : ms) Lmax = std::max(Lmax, (int)m->nd.L); if ((rc = level_weights_check(level_weights, Lmax))) return rc; }
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_window_check(side, obs, n_obs, Twc16s, p, nullptr, Tow16s, false)) || (rc = scene_models("scene pose", objs, n_objs, ms)) ||
+        (rc = scene_window_objects_check(ms.data(), n_objs, obs, n_obs, Tow16s, p))) return rc;
+    if (level_weights && (rc = level_weights_check("scene pose", level_weights, scene_levels(ms.data(), n_objs).Lmax))) return rc;
     return scene_window(ms.data(), n_objs, side, obs, n_obs, Twc16s, Tow16s, *p, nullptr, -1, iteration, level_weights, nullptr, nullptr, nullptr, nullptr, loss,
                         frame_loss, cam_grad6, obj_grad6);
 }
 int mon_scene_refine_window(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p,
                             const mon_pose_c2f_params* c, const mon_window_params* w, float* Twc16s_inout, float* Tow16s_inout, float* loss_trace,
                             float* frame_trace) {
-    int rc = scene_window_params_check(obs, n_obs, Twc16s_inout, p, w, Tow16s_inout, true); if (rc) return rc;
-    if (c && (rc = pose_c2f_check(c))) return rc;
-    std::vector<Model*> ms; if ((rc = scene_pose_models(objs, n_objs, ms))) return rc;
-    int Lmax = 0; for (Model* m : ms) Lmax = std::max(Lmax, (int)m->nd.L);
-    std::vector<float> table; if (c) table = pose_c2f_table(*c, Lmax, p->iters);
-    return scene_window(ms.data(), n_objs, side, obs, n_obs, Twc16s_inout, Tow16s_inout, *p, w, p->iters, 0u, table.empty() ? nullptr : table.data(),
-                        Twc16s_inout, Tow16s_inout, loss_trace, frame_trace, nullptr, nullptr, nullptr, nullptr);
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_window_check(side, obs, n_obs, Twc16s_inout, p, w, Tow16s_inout, true)) || (rc = scene_models("scene pose", objs, n_objs, ms)) ||
+        (rc = scene_window_objects_check(ms.data(), n_objs, obs, n_obs, Tow16s_inout, p)) || (c && (rc = pose_c2f_check(c)))) return rc;
+    const SceneLevels lv = scene_levels(ms.data(), n_objs, c, p->iters);
+    return scene_window(ms.data(), n_objs, side, obs, n_obs, Twc16s_inout, Tow16s_inout, *p, w, p->iters, 0u, lv.w(), Twc16s_inout, Tow16s_inout, loss_trace,
+                        frame_trace, nullptr, nullptr, nullptr, nullptr);
 }
 int mon_object_set_pose(mon_object* o, const float* Tow16) { REQUIRE(o, "object"); REQUIRE(Tow16, "Tow16"); return model_set_pose(*o->m, Tow16); }
 // ---- wide-basin relocalisation: batched scoring, candidate poses, the driver
 int mon_scene_pose_loss_batch(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s,
                               size_t n_poses, const mon_pose_refine_params* p, uint32_t iteration, float* losses) {
-    REQUIRE(objs, "objs"); REQUIRE(Twc16s, "Twc16s"); REQUIRE(losses, "losses");
-    if (n_poses == 0 || n_poses > kSceneScoreMaxPoses) { set_error("scene pose batch: %zu poses (1 to %u)", n_poses, kSceneScoreMaxPoses); return MON_ERR_ARG; }
-    if (p && p->rays_per_iter > kSceneScoreMaxRays) { set_error("scene pose batch: rays_per_iter %u (at most %u per hypothesis)", p->rays_per_iter,
-        kSceneScoreMaxRays); return MON_ERR_ARG; }
-    std::vector<Model*> ms; int rc = scene_pose_models(objs, n_objs, ms); if (rc) return rc;
-    if ((rc = scene_pose_batch_check(ms.data(), n_objs, side, obs, n_obs, Twc16s, n_poses, p, losses))) return rc;
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_pose_batch_check(side, obs, n_obs, Twc16s, n_poses, p, losses)) || (rc = scene_models("scene pose", objs, n_objs, ms)) ||
+        (rc = scene_pose_batch_objects_check(ms.data(), n_objs, obs, n_obs, p))) return rc;
     return scene_pose_batch(ms.data(), n_objs, side, obs, n_obs, Twc16s, n_poses, *p, iteration, losses);
 }
 int mon_pose_hypotheses(const float* Twc16, const float* pivot_cam3, float max_rot_rad, float max_trans, size_t n, uint64_t seed, float* Twc16s_out) {
@@ -277,16 +248,11 @@ int mon_reloc_default(mon_reloc_params* r) {
 int mon_scene_relocalise(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16_candidates,
                          size_t n_candidates, const mon_pose_refine_params* p, const mon_pose_c2f_params* c, const mon_reloc_params* r, float* Twc16_out,
                          mon_reloc_result* result, float* scores) {
-    REQUIRE(objs, "objs"); REQUIRE(obs, "obs"); REQUIRE(Twc16_candidates, "candidates"); REQUIRE(p, "params"); REQUIRE(r, "reloc params");
-    REQUIRE(Twc16_out, "Twc16_out");
-    if (n_candidates == 0 || n_candidates > kSceneScoreMaxPoses) { set_error("relocalise: %zu candidates (1 to %u)", n_candidates, kSceneScoreMaxPoses);
-        return MON_ERR_ARG; }
-    if (r->score_rays == 0 || r->score_rays > kSceneScoreMaxRays) { set_error("relocalise: score_rays %u (1 to %u)", r->score_rays, kSceneScoreMaxRays);
-        return MON_ERR_ARG; }
-    if (r->keep == 0 || r->keep > kRelocMaxKeep) { set_error("relocalise: keep %u (1 to %u)", r->keep, kRelocMaxKeep); return MON_ERR_ARG; }
-    std::vector<Model*> ms; int rc = scene_pose_models(objs, n_objs, ms); if (rc) return rc;
-    if ((rc = scene_reloc_check(ms.data(), n_objs, side, obs, n_obs, Twc16_candidates, n_candidates, p, c, r, Twc16_out))) return rc;
-    return scene_relocalise(ms.data(), n_objs, side, obs, n_obs, Twc16_candidates, n_candidates, *p, c, *r, Twc16_out, result, scores);
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_reloc_check(side, obs, n_obs, Twc16_candidates, n_candidates, p, r, Twc16_out)) || (rc = scene_models("scene pose", objs, n_objs, ms)) ||
+        (rc = scene_pose_objects_check(ms.data(), n_objs, obs, n_obs, p)) || (c && (rc = pose_c2f_check(c)))) return rc;
+    const SceneLevels lv = scene_levels(ms.data(), n_objs, c, p->iters);
+    return scene_relocalise(ms.data(), n_objs, side, obs, n_obs, Twc16_candidates, n_candidates, *p, lv.w(), *r, Twc16_out, result, scores);
 }
 int mon_pose_c2f_default(mon_pose_c2f_params* c) {
     REQUIRE(c, "params");
@@ -303,23 +269,20 @@ int mon_pose_c2f_weights(const mon_pose_c2f_params* c, int n_levels, int iters, 
 }
 int mon_object_pose_loss_levels(mon_object* o, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params* p,
         uint32_t iteration, const float* level_weights, float* loss, float* grad6) {
-    int rc = pose_args(o, side, obs, n_obs, Tow16, p); if (rc) return rc;
+    REQUIRE(o, "object");
+    int rc = pose_check(side, obs, n_obs, Tow16, p); if (rc) return rc;
     REQUIRE(level_weights, "level_weights");
-    const int L = (int)o->m->nd.L;
-    for (int l = 0; l < L; ++l)
-        if (!std::isfinite(level_weights[l]) || level_weights[l] < 0.f) { set_error("pose: level weight %d is %g (finite, >= 0)", l, level_weights[l]);
-            return MON_ERR_ARG; }
+    if ((rc = level_weights_check("pose", level_weights, (int)o->m->nd.L))) return rc;
     return pose_refine(*o->m, side, obs, n_obs, Tow16, *p, -1, iteration, nullptr, nullptr, loss, grad6, nullptr, level_weights);
 }
 int mon_object_refine_pose_c2f(mon_object* o, int side, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, const mon_pose_c2f_params* c,
         float* Tow16_inout, float* loss_trace) {
-    int rc = pose_args(o, side, obs, n_obs, Tow16_inout, p); if (rc) return rc;
+    REQUIRE(o, "object");
+    int rc = pose_check(side, obs, n_obs, Tow16_inout, p); if (rc) return rc;
     if ((rc = pose_c2f_check(c))) return rc;
-    const std::vector<float> table = pose_c2f_table(*c, (int)o->m->nd.L, p->iters);
-    float pose[16]; std::memcpy(pose, Tow16_inout, 64);
-    rc = pose_refine(*o->m, side, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr, table.empty() ? nullptr : table.data());
-    if (rc == MON_OK) std::memcpy(Tow16_inout, pose, 64);
-    return rc;
+    const SceneLevels lv = scene_levels(&o->m, 1, c, p->iters);
+    return pose_inout(Tow16_inout, [&](float* pose) {
+        return pose_refine(*o->m, side, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr, lv.w()); });
 }
 int mon_object_density_grid(mon_object* o, int rx, int ry, int rz, float* out_host) { REQUIRE(o, "object");
     return model_density_grid(*o->m, rx, ry, rz, out_host); }

@@ -214,10 +214,10 @@ int mon_debug_set_render_grid(mon_object* o, int side, const uint32_t* bits) { R
     return mon::model_debug_set_render_grid(*o->m, side, bits); }
 int mon_debug_scene_samples(mon_object* const* objs, size_t n_objs, int side, mon_frame_bbox rect, const float* Twc16, size_t k, float* t, float* alpha,
                             float* rgb, uint32_t* count) {
-    REQUIRE(objs, "objs"); REQUIRE(Twc16, "Twc16");
-    if (n_objs == 0 || k >= n_objs || rect.w == 0 || rect.h == 0) { set_error("debug_scene_samples: empty list or rect, or k out of range"); return MON_ERR_ARG; }
-    std::vector<mon::Model*> ms(n_objs);
-    for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
+    std::vector<mon::Model*> ms; int rc;                                   // (the image and the depth are this call's own, made once the rect is known to be good)
+    if ((rc = mon::scene_render_check(side, rect, Twc16)) || (rc = mon::scene_models("scene_render", objs, n_objs, ms)) ||
+        (rc = mon::scene_objects_check("scene_render", ms.data(), n_objs))) return rc;
+    if (k >= n_objs) { set_error("debug_scene_samples: k out of range"); return MON_ERR_ARG; }
     const size_t px = (size_t)rect.w * rect.h; std::vector<float> img(3 * px), dep(px);
     const mon::SceneDump dump{ (uint32_t)k, t, alpha, rgb, count };
     return mon::scene_render(ms.data(), n_objs, side, rect, Twc16, img.data(), dep.data(), nullptr, nullptr, nullptr, &dump);
@@ -287,39 +287,39 @@ int mon_debug_scene_cast_composite(int device, uint32_t n_rays, uint32_t n_lists
 }
 int mon_debug_scene_probe_rays(mon_object* const* objs, size_t n_objs, int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q,
                                size_t k, float* rows) {
-    REQUIRE(objs, "objs"); REQUIRE(rows, "rows");
-    if (n_objs == 0 || n_objs > mon::kSceneMaxLists || k >= n_objs) { set_error("debug_scene_probe_rays: empty list or k out of range"); return MON_ERR_ARG; }
-    { const int rc = mon::scene_probe_check(side, Twc16s, n_poses, q, n_q, rows, rows); if (rc) return rc; }
-    std::vector<mon::Model*> ms(n_objs);
-    for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
+    REQUIRE(rows, "rows");
+    std::vector<mon::Model*> ms; int rc;
+    if ((rc = mon::scene_probe_check(side, Twc16s, n_poses, q, n_q, rows, rows)) || (rc = mon::scene_models("scene_probe", objs, n_objs, ms)) ||
+        (rc = mon::scene_objects_check("scene_probe", ms.data(), n_objs))) return rc;
+    if (k >= n_objs) { set_error("debug_scene_probe_rays: k out of range"); return MON_ERR_ARG; }
     std::vector<float> img(3 * n_q), dep(n_q);
     const mon::SceneRaysDump dump{ (uint32_t)k, rows, nullptr };
     return mon::scene_probe(ms.data(), n_objs, side, Twc16s, n_poses, q, n_q, img.data(), dep.data(), nullptr, nullptr, nullptr, nullptr, nullptr, &dump);
 }
 int mon_debug_scene_cast_rays(mon_object* const* objs, size_t n_objs, int side, const mon_scene_ray* rays, size_t n_rays, size_t k, float* rows, float* entry) {
-    REQUIRE(objs, "objs"); REQUIRE(rows, "rows"); REQUIRE(entry, "entry");
-    if (n_objs == 0 || n_objs > mon::kSceneMaxLists || k >= n_objs) { set_error("debug_scene_cast_rays: empty list or k out of range"); return MON_ERR_ARG; }
-    { const int rc = mon::scene_cast_check(side, rays, n_rays, 0.5f, rows, rows); if (rc) return rc; }
-    std::vector<mon::Model*> ms(n_objs);
-    for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
+    REQUIRE(rows, "rows"); REQUIRE(entry, "entry");
+    std::vector<mon::Model*> ms; int rc;
+    if ((rc = mon::scene_cast_check(side, rays, n_rays, 0.5f, rows, rows)) || (rc = mon::scene_models("scene_cast", objs, n_objs, ms)) ||
+        (rc = mon::scene_objects_check("scene_cast", ms.data(), n_objs, false))) return rc;
+    if (k >= n_objs) { set_error("debug_scene_cast_rays: k out of range"); return MON_ERR_ARG; }
     std::vector<float> img(3 * n_rays), dep(n_rays);
     const mon::SceneRaysDump dump{ (uint32_t)k, rows, entry };
     return mon::scene_cast(ms.data(), n_objs, side, rays, n_rays, 0.5f, img.data(), dep.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &dump);
 }
 int mon_debug_pose_samples(mon_object* o, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params* p,
                            uint32_t iteration, float* x, float* raw, float* dldx) {
-    REQUIRE(o, "object"); REQUIRE(obs, "obs"); REQUIRE(Tow16, "pose"); REQUIRE(p, "params");
-    if (n_obs == 0) { set_error("debug_pose_samples: no boxes"); return MON_ERR_ARG; }
+    REQUIRE(o, "object");
+    { const int rc = mon::pose_check(side, obs, n_obs, Tow16, p); if (rc) return rc; }
     const mon::PoseDump dump{ x, raw, dldx };
     return mon::pose_refine(*o->m, side, obs, n_obs, Tow16, *p, -1, iteration, nullptr, nullptr, nullptr, nullptr, &dump);
 }
 int mon_debug_scene_pose_samples(mon_object* const* objs, size_t n_objs, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16,
                                  const mon_pose_refine_params* p, uint32_t iteration, const float* level_weights, size_t k, float* x_o, float* x_c, float* t,
                                  float* raw, float* dldx, uint32_t* count) {
-    REQUIRE(objs, "objs"); REQUIRE(obs, "obs"); REQUIRE(Twc16, "Twc16"); REQUIRE(p, "params");
-    if (n_objs == 0 || n_objs > mon::kSceneMaxLists || k >= n_objs) { set_error("debug_scene_pose_samples: empty list or k out of range"); return MON_ERR_ARG; }
-    std::vector<mon::Model*> ms(n_objs);
-    for (size_t j = 0; j < n_objs; ++j) { REQUIRE(objs[j], "object"); ms[j] = objs[j]->m; }
+    std::vector<mon::Model*> ms; int rc;
+    if ((rc = mon::scene_pose_check(side, obs, n_obs, Twc16, p)) || (rc = mon::scene_models("scene pose", objs, n_objs, ms)) ||
+        (rc = mon::scene_pose_objects_check(ms.data(), n_objs, obs, n_obs, p))) return rc;
+    if (k >= n_objs) { set_error("debug_scene_pose_samples: k out of range"); return MON_ERR_ARG; }
     const mon::ScenePoseDump dump{ (uint32_t)k, x_o, x_c, t, raw, dldx, count };
     return mon::scene_pose(ms.data(), n_objs, side, obs, n_obs, Twc16, *p, -1, iteration, nullptr, nullptr, nullptr, nullptr, &dump, level_weights);
 }

@@ -690,14 +690,26 @@ int mon_online_render(mon_online* h, size_t idx, mon_frame_bbox box, const float
     AnnouncedLock lm(o, o->mu_model);         // nothing published yet / no inference side: let in between two slices of a running training step
     return model_render(*o->model, box, Twc16, 0, rgb, depth, mask, 0);
 }
+// ---- the routes against the map: model.h's boundary with the manager's own objects in place of a caller's handles.
+// The objects of such a call: those with published weights, in index order, on one device (MON_ERR_STATE otherwise), and, where asked, their indices.  `cap`: the routes
+// that refine a pose against the map (refine_camera, refine_window, relocalise) take the first kSceneMaxLists of them and leave the rest out; the routes that
+// show the map (render_scene, probe_scene, cast_rays; cap 0) take them all, so that a 257th published object fails the call in scene_objects_check.  Nobody
+// chose that difference -- it grew with the routes -- and it is kept on purpose: either way of settling it changes what some caller sees, which is for a
+// pull request of its own.  `none_ok`: render_scene alone goes on with no object (it paints the background).
+static int online_published(mon_online* h, const char* what, size_t cap, bool none_ok, std::vector<Model*>& ms, std::vector<int32_t>* ids = nullptr) {
+    const std::vector<OnlineObject*> objs = online_objects(*h->m);
+    for (size_t i = 0; i < objs.size() && (!cap || ms.size() < cap); ++i)
+        if (objs[i]->model && model_has_snapshot(*objs[i]->model)) { ms.push_back(objs[i]->model); if (ids) ids->push_back((int32_t)i); }
+    if (ms.empty() && !none_ok) { set_error("%s: no object has published weights yet", what); return MON_ERR_STATE; }
+    for (Model* m : ms) if (m->device != ms[0]->device) { set_error("%s: the objects span more than one device", what); return MON_ERR_STATE; }
+    return MON_OK;
+}
 // the map seen from a camera: every object with published weights, composited in depth order from the snapshots (a viewer's call, like mon_online_render)
 int mon_online_render_scene(mon_online* h, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity, int32_t* instance) {
-    REQ(h); REQ(Twc16); REQ(rgb); REQ(depth);
-    if (rect.w == 0 || rect.h == 0) { set_error("render_scene: empty rect"); return MON_ERR_ARG; }
-    std::vector<Model*> ms; std::vector<int32_t> ids;
-    const std::vector<OnlineObject*> objs = online_objects(*h->m);
-    for (size_t i = 0; i < objs.size(); ++i) if (objs[i]->model && model_has_snapshot(*objs[i]->model)) { ms.push_back(objs[i]->model); ids.push_back((int32_t)i); }
-    for (Model* m : ms) if (m->device != ms[0]->device) { set_error("render_scene: the objects span more than one device"); return MON_ERR_STATE; }
+    REQ(h);
+    std::vector<Model*> ms; std::vector<int32_t> ids; int rc;
+    if ((rc = scene_render_check(1, rect, Twc16)) || (rc = scene_render_outputs_check(rgb, depth)) ||
+        (rc = online_published(h, "render_scene", 0, true, ms, &ids))) return rc;
     if (ms.empty()) {                                                     // nothing published yet: the background
         const size_t px = (size_t)rect.w * rect.h;
         std::fill(rgb, rgb + 3 * px, 1.f); std::fill(depth, depth + px, 0.f);
@@ -705,103 +717,76 @@ int mon_online_render_scene(mon_online* h, mon_frame_bbox rect, const float* Twc
         if (instance) std::fill(instance, instance + px, -1);
         return MON_OK;
     }
+    if ((rc = scene_objects_check("scene_render", ms.data(), ms.size()))) return rc;
     return scene_render(ms.data(), ms.size(), 1, rect, Twc16, rgb, depth, opacity, instance, ids.data(), nullptr);
-}
-// the objects mon_online_probe_scene and mon_online_cast_rays ask: those with published weights, as mon_online_render_scene picks them, and their indices
-static int online_published(mon_online* h, const char* what, std::vector<Model*>& ms, std::vector<int32_t>& ids) {
-    const std::vector<OnlineObject*> objs = online_objects(*h->m);
-    for (size_t i = 0; i < objs.size(); ++i) if (objs[i]->model && model_has_snapshot(*objs[i]->model)) { ms.push_back(objs[i]->model); ids.push_back((int32_t)i); }
-    if (ms.empty()) { set_error("%s: no object has published weights yet", what); return MON_ERR_STATE; }
-    for (Model* m : ms) if (m->device != ms[0]->device) { set_error("%s: the objects span more than one device", what); return MON_ERR_STATE; }
-    return MON_OK;
 }
 // the map's prediction at a front end's keypoints: mon_scene_probe on side 1 over the objects mon_online_render_scene composites
 int mon_online_probe_scene(mon_online* h, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, float* rgb, float* depth, float* opacity,
         int32_t* instance, float* hit_depth, int32_t* hit_instance) {
     REQ(h);
-    { const int rc = scene_probe_check(1, Twc16s, n_poses, q, n_q, rgb, depth); if (rc) return rc; }
-    std::vector<Model*> ms; std::vector<int32_t> ids;
-    { const int rc = online_published(h, "probe_scene", ms, ids); if (rc) return rc; }
+    std::vector<Model*> ms; std::vector<int32_t> ids; int rc;
+    if ((rc = scene_probe_check(1, Twc16s, n_poses, q, n_q, rgb, depth)) || (rc = online_published(h, "probe_scene", 0, false, ms, &ids)) ||
+        (rc = scene_objects_check("scene_probe", ms.data(), ms.size()))) return rc;
     return scene_probe(ms.data(), ms.size(), 1, Twc16s, n_poses, q, n_q, rgb, depth, opacity, instance, hit_depth, hit_instance, ids.data(), nullptr);
 }
 // the map asked along a planner's world rays: mon_scene_cast on side 1 over the objects mon_online_render_scene composites
 int mon_online_cast_rays(mon_online* h, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, float* rgb, float* dist, float* opacity, int32_t* instance,
         float* hit_t, float* hit_sample_t, int32_t* hit_instance) {
     REQ(h);
-    { const int rc = scene_cast_check(1, rays, n_rays, hit_opacity, rgb, dist); if (rc) return rc; }
-    std::vector<Model*> ms; std::vector<int32_t> ids;
-    { const int rc = online_published(h, "cast_rays", ms, ids); if (rc) return rc; }
+    std::vector<Model*> ms; std::vector<int32_t> ids; int rc;
+    if ((rc = scene_cast_check(1, rays, n_rays, hit_opacity, rgb, dist)) || (rc = online_published(h, "cast_rays", 0, false, ms, &ids)) ||
+        (rc = scene_objects_check("scene_cast", ms.data(), ms.size(), false))) return rc;
     return scene_cast(ms.data(), ms.size(), 1, rays, n_rays, hit_opacity, rgb, dist, opacity, instance, hit_t, hit_sample_t, hit_instance, ids.data(), nullptr);
 }
 // pose refinement of one object against new observations, from its published snapshot (a frontend's call, like mon_online_render: safe while it trains)
 int mon_online_refine_pose(mon_online* h, size_t idx, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, float* Tow16_inout,
         float* loss_trace) {
-    REQ(h); REQ(obs); REQ(p); REQ(Tow16_inout);
-    if (n_obs == 0 || p->iters < 0) { set_error("refine_pose: no boxes or iters < 0"); return MON_ERR_ARG; }
+    REQ(h);
+    { const int rc = pose_check(1, obs, n_obs, Tow16_inout, p); if (rc) return rc; }
     OnlineObject* o = online_object(*h->m, idx); if (!o || !o->model) { set_error("NeRF Idx error ..."); return MON_ERR_ARG; }
-    float pose[16]; std::memcpy(pose, Tow16_inout, 64);
-    const int rc = pose_refine(*o->model, 1, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr);
-    if (rc == MON_OK) std::memcpy(Tow16_inout, pose, 64);
-    return rc;
+    return pose_inout(Tow16_inout, [&](float* pose) {
+        return pose_refine(*o->model, 1, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr); });
 }
 // ... with the coarse-to-fine level schedule (mon_object_refine_pose_c2f on side 1)
 int mon_online_refine_pose_c2f(mon_online* h, size_t idx, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p,
         const mon_pose_c2f_params* c, float* Tow16_inout, float* loss_trace) {
-    REQ(h); REQ(obs); REQ(p); REQ(Tow16_inout);
-    if (n_obs == 0 || p->iters < 0) { set_error("refine_pose_c2f: no boxes or iters < 0"); return MON_ERR_ARG; }
-    { const int rc = pose_c2f_check(c); if (rc) return rc; }
+    REQ(h);
+    int rc; if ((rc = pose_check(1, obs, n_obs, Tow16_inout, p)) || (rc = pose_c2f_check(c))) return rc;
     OnlineObject* o = online_object(*h->m, idx); if (!o || !o->model) { set_error("NeRF Idx error ..."); return MON_ERR_ARG; }
-    const std::vector<float> table = pose_c2f_table(*c, (int)o->model->nd.L, p->iters);
-    float pose[16]; std::memcpy(pose, Tow16_inout, 64);
-    const int rc = pose_refine(*o->model, 1, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr,
-                               table.empty() ? nullptr : table.data());
-    if (rc == MON_OK) std::memcpy(Tow16_inout, pose, 64);
-    return rc;
+    const SceneLevels lv = scene_levels(&o->model, 1, c, p->iters);
+    return pose_inout(Tow16_inout, [&](float* pose) {
+        return pose_refine(*o->model, 1, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr, lv.w()); });
 }
 // camera refinement against every object of the manager that has published weights (mon_scene_refine_camera on side 1: a frontend's call, safe while they
 // train).  Nothing of the manager changes: the caller hands the pose to mon_online_update_dataset if the dataset is to hold it.
 int mon_online_refine_camera(mon_online* h, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, const mon_pose_c2f_params* c,
         float* Twc16_inout, float* loss_trace) {
-    REQ(h); REQ(obs); REQ(p); REQ(Twc16_inout);
-    if (n_obs == 0 || p->iters < 0) { set_error("refine_camera: no boxes or iters < 0"); return MON_ERR_ARG; }
-    if (c) { const int rc = pose_c2f_check(c); if (rc) return rc; }
-    std::vector<Model*> ms;
-    const std::vector<OnlineObject*> objs = online_objects(*h->m);
-    for (size_t i = 0; i < objs.size() && ms.size() < kSceneMaxLists; ++i) if (objs[i]->model && model_has_snapshot(*objs[i]->model)) ms.push_back(objs[i]->model);
-    if (ms.empty()) { set_error("refine_camera: no object has published weights yet"); return MON_ERR_STATE; }
-    for (Model* m : ms) if (m->device != ms[0]->device) { set_error("refine_camera: the objects span more than one device"); return MON_ERR_STATE; }
-    int Lmax = 0; for (Model* m : ms) Lmax = std::max(Lmax, (int)m->nd.L);
-    std::vector<float> table; if (c) table = pose_c2f_table(*c, Lmax, p->iters);
-    float pose[16]; std::memcpy(pose, Twc16_inout, 64);
-    const int rc = scene_pose(ms.data(), ms.size(), 1, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr,
-                              table.empty() ? nullptr : table.data());
-    if (rc == MON_OK) std::memcpy(Twc16_inout, pose, 64);
-    return rc;
+    REQ(h);
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_pose_check(1, obs, n_obs, Twc16_inout, p)) || (c && (rc = pose_c2f_check(c))) ||
+        (rc = online_published(h, "refine_camera", kSceneMaxLists, false, ms)) || (rc = scene_pose_objects_check(ms.data(), ms.size(), obs, n_obs, p))) return rc;
+    const SceneLevels lv = scene_levels(ms.data(), ms.size(), c, p->iters);
+    return pose_inout(Twc16_inout, [&](float* pose) {
+        return scene_pose(ms.data(), ms.size(), 1, obs, n_obs, pose, *p, p->iters, 0u, pose, loss_trace, nullptr, nullptr, nullptr, lv.w()); });
 }
 // joint refinement of a window of keyframes and the objects they see (mon_scene_refine_window on side 1), over the objects mon_online_refine_camera
 // chooses.  Tow16s_inout / included are indexed by the manager's object index.  Nothing of the manager changes.
 int mon_online_refine_window(mon_online* h, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, const mon_pose_c2f_params* c,
         const mon_window_params* w, float* Twc16s_inout, float* Tow16s_inout, size_t n_objects, uint8_t* included, float* loss_trace, float* frame_trace) {
-    REQ(h); REQ(obs); REQ(p); REQ(w); REQ(Twc16s_inout);
-    if (n_obs == 0 || p->iters < 0) { set_error("refine_window: no boxes or iters < 0"); return MON_ERR_ARG; }
-    if (c) { const int rc = pose_c2f_check(c); if (rc) return rc; }
-    { const int rc = scene_window_params_check(obs, n_obs, Twc16s_inout, p, w, Tow16s_inout, true); if (rc) return rc; }
-    std::vector<Model*> ms; std::vector<size_t> idx;
-    const std::vector<OnlineObject*> objs = online_objects(*h->m);
-    if (n_objects != objs.size()) { set_error("refine_window: n_objects %zu, the manager holds %zu", n_objects, objs.size()); return MON_ERR_ARG; }
-    for (size_t i = 0; i < objs.size() && ms.size() < kSceneMaxLists; ++i)
-        if (objs[i]->model && model_has_snapshot(*objs[i]->model)) { ms.push_back(objs[i]->model); idx.push_back(i); }
-    if (ms.empty()) { set_error("refine_window: no object has published weights yet"); return MON_ERR_STATE; }
-    for (Model* m : ms) if (m->device != ms[0]->device) { set_error("refine_window: the objects span more than one device"); return MON_ERR_STATE; }
-    int Lmax = 0; for (Model* m : ms) Lmax = std::max(Lmax, (int)m->nd.L);
-    std::vector<float> table; if (c) table = pose_c2f_table(*c, Lmax, p->iters);
+    REQ(h);
+    std::vector<Model*> ms; std::vector<int32_t> idx; int rc;
+    if ((rc = scene_window_check(1, obs, n_obs, Twc16s_inout, p, w, Tow16s_inout, true)) || (c && (rc = pose_c2f_check(c)))) return rc;
+    const size_t n_held = online_objects(*h->m).size();
+    if (n_objects != n_held) { set_error("refine_window: n_objects %zu, the manager holds %zu", n_objects, n_held); return MON_ERR_ARG; }
+    if ((rc = online_published(h, "refine_window", kSceneMaxLists, false, ms, &idx))) return rc;
     std::vector<float> tow; if (Tow16s_inout) { tow.resize(16 * ms.size()); for (size_t k = 0; k < ms.size(); ++k) std::memcpy(&tow[16 * k], Tow16s_inout + 16 * idx[k], 64); }
-    const int rc = scene_window(ms.data(), ms.size(), 1, obs, n_obs, Twc16s_inout, tow.empty() ? nullptr : tow.data(), *p, w, p->iters, 0u,
-                                table.empty() ? nullptr : table.data(), Twc16s_inout, tow.empty() ? nullptr : tow.data(), loss_trace, frame_trace, nullptr,
-                                nullptr, nullptr, nullptr);
+    if ((rc = scene_window_objects_check(ms.data(), ms.size(), obs, n_obs, tow.empty() ? nullptr : tow.data(), p))) return rc;
+    const SceneLevels lv = scene_levels(ms.data(), ms.size(), c, p->iters);
+    rc = scene_window(ms.data(), ms.size(), 1, obs, n_obs, Twc16s_inout, tow.empty() ? nullptr : tow.data(), *p, w, p->iters, 0u, lv.w(), Twc16s_inout,
+                      tow.empty() ? nullptr : tow.data(), loss_trace, frame_trace, nullptr, nullptr, nullptr, nullptr);
     if (rc) return rc;
     if (Tow16s_inout) for (size_t k = 0; k < ms.size(); ++k) std::memcpy(Tow16s_inout + 16 * idx[k], &tow[16 * k], 64);
-    if (included) { std::fill(included, included + n_objects, (uint8_t)0); for (size_t i : idx) included[i] = 1; }
+    if (included) { std::fill(included, included + n_objects, (uint8_t)0); for (int32_t i : idx) included[i] = 1; }
     return MON_OK;
 }
 // a refined object pose handed back to the object, under its model lock (announced so that a training slice lets the call in)
@@ -817,17 +802,12 @@ int mon_online_set_object_pose(mon_online* h, size_t idx, const float* Tow16) {
 // objects are chosen as mon_online_refine_camera chooses them.  Nothing of the manager changes.
 int mon_online_relocalise(mon_online* h, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16_candidates, size_t n_candidates,
         const mon_pose_refine_params* p, const mon_pose_c2f_params* c, const mon_reloc_params* r, float* Twc16_out, mon_reloc_result* result, float* scores) {
-    REQ(h); REQ(obs); REQ(Twc16_candidates); REQ(p); REQ(r); REQ(Twc16_out);
-    if (n_obs == 0 || p->iters < 0) { set_error("relocalise: no boxes or iters < 0"); return MON_ERR_ARG; }
-    if (n_candidates == 0 || n_candidates > kSceneScoreMaxPoses || r->score_rays == 0 || r->score_rays > kSceneScoreMaxRays || r->keep == 0 ||
-        r->keep > kRelocMaxKeep) { set_error("relocalise: %zu candidates, score_rays %u, keep %u", n_candidates, r->score_rays, r->keep); return MON_ERR_ARG; }
-    if (c) { const int rc = pose_c2f_check(c); if (rc) return rc; }
-    std::vector<Model*> ms;
-    const std::vector<OnlineObject*> objs = online_objects(*h->m);
-    for (size_t i = 0; i < objs.size() && ms.size() < kSceneMaxLists; ++i) if (objs[i]->model && model_has_snapshot(*objs[i]->model)) ms.push_back(objs[i]->model);
-    if (ms.empty()) { set_error("relocalise: no object has published weights yet"); return MON_ERR_STATE; }
-    for (Model* m : ms) if (m->device != ms[0]->device) { set_error("relocalise: the objects span more than one device"); return MON_ERR_STATE; }
-    return scene_relocalise(ms.data(), ms.size(), 1, obs, n_obs, Twc16_candidates, n_candidates, *p, c, *r, Twc16_out, result, scores);
+    REQ(h);
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_reloc_check(1, obs, n_obs, Twc16_candidates, n_candidates, p, r, Twc16_out)) || (c && (rc = pose_c2f_check(c))) ||
+        (rc = online_published(h, "relocalise", kSceneMaxLists, false, ms)) || (rc = scene_pose_objects_check(ms.data(), ms.size(), obs, n_obs, p))) return rc;
+    const SceneLevels lv = scene_levels(ms.data(), ms.size(), c, p->iters);
+    return scene_relocalise(ms.data(), ms.size(), 1, obs, n_obs, Twc16_candidates, n_candidates, *p, lv.w(), *r, Twc16_out, result, scores);
 }
 // NerfManagerOnline::RenderNeRFsTest -> NeRF::RenderTestImg, nerf.cu:255-404: <out>/<id>/{test_img,test_depth,test_mask}/<stamp>.png,
 // test.txt, train.txt (object-centric poses), 60-view video_img / video_depth, obj.ply

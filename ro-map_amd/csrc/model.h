@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <cstring>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -662,19 +663,42 @@ int tile_ws_skip_buffers(TileWs& ws, size_t n_pix);
 void tile_ws_weights(Model& m, TileWs& ws, hipStream_t s, const uint16_t* prm, uint64_t epoch);
 // ws.x holds n points -> ws.O (raw fp16 outputs [n][4]); caller holds ws.mu and has called tile_ws_weights
 void tile_points_forward(Model& m, TileWs& ws, hipStream_t s, uint32_t n);
+// ---- The boundary of the scene and pose routes.  Every entry to a route -- the C ABI, the online manager, a dump entry of the diagnostics
+// library -- takes four steps: the route's <route>_check (every MON_ERR_ARG that can be judged without an object), the objects (scene_models from the
+// caller's handles, the manager's pick), the route's <route>_objects_check (every MON_ERR_ARG that needs them), the route.  A schedule's pose_c2f_check is a
+// call of its own: after the objects' check in the C ABI, before the manager picks its objects.  None of them does device work, and a route repeats none of
+// them; its MON_ERR_STATE cases (an object outside the fused kernels, nothing published on side 1) are the route's own.
+// scene_models: handles to models; MON_ERR_ARG for a NULL list, a count outside 1..kSceneMaxLists, a NULL element.  `what`: the message prefix.
+int scene_models(const char* what, mon_object* const* objs, size_t n, std::vector<Model*>& ms);
+// the objects of one call: the count again (the manager's lists come without handles), one device, one camera (not the ray cast), one dataset (the pose
+// routes, which read a frame's pixels)
+int scene_objects_check(const char* what, Model* const* ms, size_t n, bool camera = true, bool one_dataset = false);
+// Lmax = the largest n_levels among the objects (the row length of their level weights) and, with a schedule, its table [iters][Lmax] (w(): nullptr without)
+struct SceneLevels { int Lmax = 0; std::vector<float> table; const float* w() const { return table.empty() ? nullptr : table.data(); } };
+SceneLevels scene_levels(Model* const* ms, size_t n, const mon_pose_c2f_params* c = nullptr, int iters = 0);
+int level_weights_check(const char* what, const float* w, int n);                                 // n finite weights >= 0
+// an in-out pose: `run` refines a copy of it in place, which goes back to the caller only when it succeeds
+template <class F> int pose_inout(float* pose16, F run) {
+    float pose[16]; std::memcpy(pose, pose16, 64);
+    const int rc = run(pose);
+    if (rc == MON_OK) std::memcpy(pose16, pose, 64);
+    return rc;
+}
 // Scene render (mon_scene_render): side 0 the train-side weights, 1 the published snapshots; ids (may be nullptr) = the instance reported for each object;
 // dump (mon_debug_scene_samples, may be nullptr) = object `list`'s sample lists of the whole rect, host arrays [pixel][kSceneListLen] (rgb x 3) + count [pixel]
 struct SceneDump { uint32_t list; float* t; float* alpha; float* rgb; uint32_t* count; };
+int scene_render_check(int side, mon_frame_bbox rect, const float* Twc16);      // the view; the caller's image and depth: scene_render_outputs_check
+int scene_render_outputs_check(const float* rgb, const float* depth);
 int scene_render(Model* const* ms, size_t n, int side, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity, int32_t* instance,
                  const int32_t* ids, const SceneDump* dump);
-// Scene probe (mon_scene_probe): scene_render's conventions for side and ids (applied to both instance outputs).  scene_probe_check: every MON_ERR_ARG
-// that needs no object, no device work.  dump (mon_debug_scene_probe_rays / mon_debug_scene_cast_rays, may be nullptr) = object k's ray rows per query,
-// host array [n_q][10]: o[3], d[3], t0, t1, flag, dn (a row that missed the box: flag 0, dn, the rest 0); entry (the cast only) = its entry row [n_q].
+// Scene probe (mon_scene_probe): scene_render's conventions for side and ids (applied to both instance outputs).  dump (mon_debug_scene_probe_rays /
+// mon_debug_scene_cast_rays, may be nullptr) = object k's ray rows per query, host array [n_q][10]: o[3], d[3], t0, t1, flag, dn (a row that missed the
+// box: flag 0, dn, the rest 0); entry (the cast only) = its entry row [n_q].
 struct SceneRaysDump { uint32_t k; float* rows; float* entry; };
 int scene_probe_check(int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, const float* rgb, const float* depth);
 int scene_probe(Model* const* ms, size_t n, int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, float* rgb, float* depth,
                 float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance, const int32_t* ids, const SceneRaysDump* dump);
-// Ray cast (mon_scene_cast): the probe's chain over world rays; the same conventions.  scene_cast_check: every MON_ERR_ARG that needs no object.
+// Ray cast (mon_scene_cast): the probe's chain over world rays; the same conventions (its objects' check: no camera).
 // scene_camera_rays (mon_camera_rays): the probe's world rays on the host, pixel_ray's world-frame branch.
 int scene_cast_check(int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, const float* rgb, const float* dist);
 int scene_cast(Model* const* ms, size_t n, int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, float* rgb, float* dist, float* opacity,
@@ -687,43 +711,43 @@ bool model_has_snapshot(Model& m);      // the object has an inference side and 
 // of the evaluation, host arrays [ray][2S] of positions (object frame, 3), raw outputs (4) and dL/dx (3); any of them may be nullptr.
 // level_w (mon_object_pose_loss_levels / mon_object_refine_pose_c2f, may be nullptr): host weights [L] of the one evaluation, or [iters][L] of the steps.
 struct PoseDump { float* x; float* raw; float* dldx; };
+int pose_check(int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params* p);     // (the boxes are the object's part)
 int pose_refine(Model& m, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params& p, int iters,
                 uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const PoseDump* dump, const float* level_w = nullptr);
 // Camera refinement against a scene of objects (mon_scene_pose_loss / mon_scene_refine_camera): pose_refine's conventions for iters, iteration, the outputs
-// and level_w (rows of Lmax = the largest n_levels among the objects; object j reads its first L_j).  scene_pose_check: every MON_ERR_ARG of the call, no
-// device work.  dump (mon_debug_scene_pose_samples, may be nullptr): object k's share per drawn ray, host arrays [ray][64][3 | 3 | 1 | 4 | 3] + count [ray].
+// and level_w (rows of Lmax = the largest n_levels among the objects; object j reads its first L_j).  dump (mon_debug_scene_pose_samples, may be nullptr):
+// object k's share per drawn ray, host arrays [ray][64][3 | 3 | 1 | 4 | 3] + count [ray].
 struct ScenePoseDump { uint32_t k; float* x_o; float* x_c; float* t; float* raw; float* dldx; uint32_t* count; };
-int scene_pose_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16, const mon_pose_refine_params* p);
+int scene_pose_check(int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16, const mon_pose_refine_params* p);
+int scene_pose_objects_check(Model* const* ms, size_t n, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p);
 int scene_pose(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16, const mon_pose_refine_params& p, int iters,
                uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const ScenePoseDump* dump, const float* level_w = nullptr);
 uint32_t pose_n_rays(const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params& p);      // rays of one evaluation
 // mon_scene_pose_loss_batch: losses[h] = scene_pose(.., Twc16s + 16 h, p, -1, iteration, ..)'s loss bit for bit, all in one enqueue with one synchronisation.
-// scene_pose_batch_check: every MON_ERR_ARG of the call (scene_pose_check's, n_poses outside 1..kSceneScoreMaxPoses, more than kSceneScoreMaxRays rays per
-// hypothesis), no device work.
-int scene_pose_batch_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, size_t n_poses,
-                           const mon_pose_refine_params* p, const float* losses);
+// The checks: scene_pose's, n_poses outside 1..kSceneScoreMaxPoses, more than kSceneScoreMaxRays rays per hypothesis.
+int scene_pose_batch_check(int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, size_t n_poses, const mon_pose_refine_params* p,
+                           const float* losses);
+int scene_pose_batch_objects_check(Model* const* ms, size_t n, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p);
 int scene_pose_batch(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, size_t n_poses,
                      const mon_pose_refine_params& p, uint32_t iteration, float* losses);
 // mon_scene_window_loss / mon_scene_refine_window (include/mon_core.h): iters < 0 = one evaluation at `iteration` (wp may be nullptr; level_w one row of
 // Lmax or nullptr), else iters steps (level_w [iters][Lmax] or nullptr).  Tow16s nullptr = every object's own Tow.  Outputs may be nullptr; Twc16s_out /
-// Tow16s_out receive only the poses that moved.  window_frames: mon_window_frames.  The MON_ERR_ARG cases in two parts, neither with device work:
-// scene_window_params_check, what needs no object -- the caller of scene_window has passed it; scene_window_frames_check, what needs the objects (every
-// frame's scene_pose_check, the rays of a frame, a non-finite Tow16s) -- scene_window runs it.  model_set_pose: mon_object_set_pose.
+// Tow16s_out receive only the poses that moved.  window_frames: mon_window_frames.  scene_window_objects_check: every frame's boxes as scene_pose takes
+// them, the rays of a frame, a non-finite Tow16s.  model_set_pose: mon_object_set_pose.
 int window_frames(const mon_frame_bbox* obs, size_t n_obs, uint32_t* frame_ids, size_t* n_frames);
-int scene_window_params_check(const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const mon_pose_refine_params* p, const mon_window_params* w,
-                              const float* Tow16s, bool refine);
-int scene_window_frames_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const float* Tow16s,
-                              const mon_pose_refine_params* p);
+int scene_window_check(int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const mon_pose_refine_params* p, const mon_window_params* w,
+                       const float* Tow16s, bool refine);
+int scene_window_objects_check(Model* const* ms, size_t n, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16s, const mon_pose_refine_params* p);
 int scene_window(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const float* Tow16s,
                  const mon_pose_refine_params& p, const mon_window_params* wp, int iters, uint32_t iteration, const float* level_w, float* Twc16s_out,
                  float* Tow16s_out, float* loss_trace, float* frame_trace, float* loss, float* frame_loss, float* cam_grad6, float* obj_grad6);
 int model_set_pose(Model& m, const float* Tow16);
-// mon_scene_relocalise / mon_online_relocalise: the rule of include/mon_core.h over scene_pose_batch and scene_pose.  scene_reloc_check: its MON_ERR_ARG
-// cases, no device work.
-int scene_reloc_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* cands, size_t n_cands,
-                      const mon_pose_refine_params* p, const mon_pose_c2f_params* c, const mon_reloc_params* r, const float* pose_out);
+// mon_scene_relocalise / mon_online_relocalise: the rule of include/mon_core.h over scene_pose_batch and scene_pose.  Its objects' check is
+// scene_pose_objects_check; level_w: the table of the schedule every kept candidate is refined under (scene_levels), or nullptr.
+int scene_reloc_check(int side, const mon_frame_bbox* obs, size_t n_obs, const float* cands, size_t n_cands, const mon_pose_refine_params* p,
+                      const mon_reloc_params* r, const float* pose_out);
 int scene_relocalise(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* cands, size_t n_cands,
-                     const mon_pose_refine_params& p, const mon_pose_c2f_params* c, const mon_reloc_params& r, float* pose_out, mon_reloc_result* result,
+                     const mon_pose_refine_params& p, const float* level_w, const mon_reloc_params& r, float* pose_out, mon_reloc_result* result,
                      float* scores);
 int pose_c2f_check(const mon_pose_c2f_params* c);                                                    // MON_ERR_ARG for a NULL or bad schedule
 std::vector<float> pose_c2f_table(const mon_pose_c2f_params& c, int n_levels, int iters);          // [iters][n_levels]: mon_pose_c2f_weights of every step

@@ -12,6 +12,8 @@ namespace mon {
 #define HIPCHECK(expr)                                                                                         \
     do { hipError_t _e = (expr); if (_e != hipSuccess) {                                                       \
         set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); return MON_ERR_HIP; } } while (0)
+// a NULL pointer argument of a route's check, by the name the header gives it: "<what>: null <name>"
+#define REQUIRE_ARG(what, p, name) do { if (!(p)) { set_error("%s: null %s", what, name); return MON_ERR_ARG; } } while (0)
 constexpr uint32_t kRenderChunkRays = 16384;   // rays per render pass (x 2S samples)
 
 // One high-priority stream and one pinned result buffer per DEVICE, shared by the objects on it (viewer renders) and by the device's dataset (frame uploads):

@@ -1,4 +1,5 @@
 // pose.cpp -- object pose refinement through a trained object NeRF: the host side of kernels_pose.hip
+#include <cmath>
 #include <cstring>
 #include "model_internal.h"
 
@@ -34,10 +35,20 @@ uint32_t pose_n_rays(const mon_frame_bbox* obs, size_t n_obs, const mon_pose_ref
     uint64_t t = 0; for (size_t i = 0; i < n_obs; ++i) t += (uint64_t)obs[i].w * obs[i].h;
     return t > 0xffffffffull ? 0xffffffffu : (uint32_t)t;
 }
+int pose_check(int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params* p) {
+    REQUIRE_ARG("pose", obs, "obs"); REQUIRE_ARG("pose", Tow16, "pose"); REQUIRE_ARG("pose", p, "params");
+    if (n_obs == 0) { set_error("pose: no boxes"); return MON_ERR_ARG; }
+    if (p->iters < 0) { set_error("pose: iters %d < 0", p->iters); return MON_ERR_ARG; }
+    if (side != 0 && side != 1) { set_error("pose: side %d (0 or 1)", side); return MON_ERR_ARG; }
+    return MON_OK;
+}
+int level_weights_check(const char* what, const float* w, int n) {
+    for (int l = 0; l < n; ++l)
+        if (!std::isfinite(w[l]) || w[l] < 0.f) { set_error("%s: level weight %d is %g (finite, >= 0)", what, l, w[l]); return MON_ERR_ARG; }
+    return MON_OK;
+}
 int pose_refine(Model& m, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params& p, int iters,
                 uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const PoseDump* dump, const float* level_w) {
-    if (!obs || n_obs == 0 || !Tow16) { set_error("pose: null or empty argument"); return MON_ERR_ARG; }
-    if (side != 0 && side != 1) { set_error("pose: side must be 0 or 1"); return MON_ERR_ARG; }
     if (p.rays_per_iter > kPoseMaxRays) { set_error("pose: rays_per_iter %u above %u", p.rays_per_iter, kPoseMaxRays); return MON_ERR_ARG; }
     std::vector<uint32_t> prefix(n_obs + 1, 0u);
     {   uint64_t t = 0;

@@ -1,4 +1,5 @@
-// scene.cpp -- several object NeRFs under one camera: the scene render and the scene pose family (camera refinement, batched scoring, window, relocalisation)
+// scene.cpp -- several object NeRFs under one camera: the boundary every entry to a scene route passes (its checks, handles to models; model.h), the scene
+// render, the probe and the ray cast over one list chain, and the scene pose family (camera refinement, batched scoring, window, relocalisation)
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -7,41 +8,54 @@
 #include "model_internal.h"
 
 namespace mon {
-// ---- what every scene call asks of its objects.  `what`: the message prefix ("scene_render", "scene pose")
-static int scene_objects_present(const char* what, Model* const* ms, size_t n) {
-    for (size_t j = 0; j < n; ++j) if (!ms[j]) { set_error("%s: null object %zu", what, j); return MON_ERR_ARG; }
+// ---- the boundary of the scene routes.  Every entry to a route -- the C ABI, the online manager, a dump entry of the diagnostics library --
+// runs the same four steps: the route's *_check (what can be judged without an object), the objects (scene_models from handles, the manager's own pick), the
+// route's *_objects_check (what needs them), the route itself.  A schedule's pose_c2f_check is a call of its own.  None of them does device work; the routes
+// below repeat none of them.  `what`: the message prefix ("scene_render", "scene pose").
+static int scene_count_check(const char* what, size_t n) {
+    if (n == 0 || n > kSceneMaxLists) { set_error("%s: %zu objects (1 to %u)", what, n, kSceneMaxLists); return MON_ERR_ARG; }
     return MON_OK;
 }
-// object j sits on object 0's device and (camera: every call but the ray cast, which has no camera) looks through its camera
-static int scene_same_camera(const char* what, const Model& m0, const Model& m, size_t j, bool camera = true) {
-    const Intrinsics& K = m0.ds->K; const Intrinsics& k = m.ds->K;
-    if (m.device != m0.device) { set_error("%s: objects on logical devices %d and %d", what, m0.device, m.device); return MON_ERR_ARG; }
-    if (!camera) return MON_OK;
-    if (k.fx != K.fx || k.fy != K.fy || k.cx != K.cx || k.cy != K.cy || k.W != K.W || k.H != K.H) {
-        set_error("%s: object %zu has other intrinsics", what, j); return MON_ERR_ARG; }
+int scene_models(const char* what, mon_object* const* objs, size_t n, std::vector<Model*>& ms) {
+    if (!objs) { set_error("%s: null objs", what); return MON_ERR_ARG; }
+    { const int rc = scene_count_check(what, n); if (rc) return rc; }
+    ms.resize(n);
+    for (size_t j = 0; j < n; ++j) { if (!objs[j] || !objs[j]->m) { set_error("%s: null object %zu", what, j); return MON_ERR_ARG; } ms[j] = objs[j]->m; }
     return MON_OK;
 }
-// every MON_ERR_STATE of a scene call that needs no device work; Lmax = the largest n_levels among the objects
-static int scene_state_check(const char* what, Model* const* ms, size_t n, int side, int& Lmax) {
-    Lmax = 0;
+// the objects of one call: 1 to kSceneMaxLists of them on one device, looking through one camera (every call but the ray cast, which has no camera) and,
+// where the call reads a frame's pixels, of one dataset
+int scene_objects_check(const char* what, Model* const* ms, size_t n, bool camera, bool one_dataset) {
+    { const int rc = scene_count_check(what, n); if (rc) return rc; }
+    const Model& m0 = *ms[0]; const Intrinsics& K = m0.ds->K;
+    for (size_t j = 1; j < n; ++j) {
+        const Model& m = *ms[j]; const Intrinsics& k = m.ds->K;
+        if (m.device != m0.device) { set_error("%s: objects on logical devices %d and %d", what, m0.device, m.device); return MON_ERR_ARG; }
+        if (camera && (k.fx != K.fx || k.fy != K.fy || k.cx != K.cx || k.cy != K.cy || k.W != K.W || k.H != K.H)) {
+            set_error("%s: object %zu has other intrinsics", what, j); return MON_ERR_ARG; }
+        if (one_dataset && m.ds != m0.ds) { set_error("%s: object %zu is on another dataset", what, j); return MON_ERR_ARG; }
+    }
+    return MON_OK;
+}
+SceneLevels scene_levels(Model* const* ms, size_t n, const mon_pose_c2f_params* c, int iters) {
+    SceneLevels lv;
+    for (size_t j = 0; j < n; ++j) lv.Lmax = std::max(lv.Lmax, (int)ms[j]->nd.L);
+    if (c) lv.table = pose_c2f_table(*c, lv.Lmax, iters);
+    return lv;
+}
+// every MON_ERR_STATE of a scene call that needs no device work (the routes run it themselves: it is their own question, asked once)
+static int scene_state_check(const char* what, Model* const* ms, size_t n, int side) {
     for (size_t j = 0; j < n; ++j) {
         Model& m = *ms[j];
         if (!rskip_supported(m) || 2u * m.oc.S != kSceneListLen) { set_error("%s: object %zu does not run on the fused kernels", what, j); return MON_ERR_STATE; }
         if (m.d_xw) { set_error("%s: object %zu renders with the XORWOW sample stream (rng_flags)", what, j); return MON_ERR_STATE; }
         if (side == 1 && !model_has_snapshot(m)) { set_error("%s: object %zu has no published snapshot", what, j); return MON_ERR_STATE; }
-        Lmax = std::max(Lmax, (int)m.nd.L);
     }
     return MON_OK;
 }
-// what scene_render, scene_probe and scene_cast (camera false) ask of side and objects: every MON_ERR_ARG, then every MON_ERR_STATE, no device work
-static int scene_objects_check(const char* what, Model* const* ms, size_t n, int side, bool camera = true) {
-    if (side != 0 && side != 1) { set_error("%s: side must be 0 or 1", what); return MON_ERR_ARG; }
-    if (n == 0) { set_error("%s: no objects", what); return MON_ERR_ARG; }
-    if (n > kSceneMaxLists) { set_error("%s: %zu objects (at most %u)", what, n, kSceneMaxLists); return MON_ERR_ARG; }
-    { const int rc = scene_objects_present(what, ms, n); if (rc) return rc; }
-    for (size_t j = 0; j < n; ++j) { const int rc = scene_same_camera(what, *ms[0], *ms[j], j, camera); if (rc) return rc; }
-    int Lmax = 0;
-    return scene_state_check(what, ms, n, side, Lmax);
+static int side_check(const char* what, int side) {
+    if (side != 0 && side != 1) { set_error("%s: side %d (0 or 1)", what, side); return MON_ERR_ARG; }
+    return MON_OK;
 }
 
 // ---- entering a side of a scene: the weights every object is read from, their stamps, the stream of the call.  Side 1: the shared inference stream under
@@ -104,10 +118,18 @@ static std::vector<SceneSrc> scene_sources(Model* const* ms, size_t n, int side,
     }
     return src;
 }
+int scene_render_check(int side, mon_frame_bbox rect, const float* Twc16) {
+    REQUIRE_ARG("scene_render", Twc16, "Twc16");
+    if (rect.w == 0 || rect.h == 0) { set_error("scene_render: empty rect"); return MON_ERR_ARG; }
+    return side_check("scene_render", side);
+}
+int scene_render_outputs_check(const float* rgb, const float* depth) {
+    REQUIRE_ARG("scene_render", rgb, "rgb"); REQUIRE_ARG("scene_render", depth, "depth");
+    return MON_OK;
+}
 int scene_render(Model* const* ms, size_t n, int side, mon_frame_bbox rect, const float* Twc16, float* rgb, float* depth, float* opacity, int32_t* instance,
                  const int32_t* ids, const SceneDump* dump) {
-    if (!ms || n == 0 || !Twc16 || !rgb || !depth || rect.w == 0 || rect.h == 0) { set_error("scene_render: null or empty argument"); return MON_ERR_ARG; }
-    { const int rc = scene_objects_check("scene_render", ms, n, side); if (rc) return rc; }
+    { const int rc = scene_state_check("scene_render", ms, n, side); if (rc) return rc; }
     const Intrinsics K = ms[0]->ds->K; const int device = ms[0]->device;
     HIPCHECK(use_device(device));
     const uint32_t n_pix = rect.w * rect.h, cap = std::min(n_pix, kRenderChunkRays), L = (uint32_t)n;
@@ -171,7 +193,7 @@ int scene_render(Model* const* ms, size_t n, int side, mon_frame_bbox rect, cons
 // `upload` grows and fills what the call keeps in the workspace beside the lists.  Everything is enqueued at once; the output rows go home through the pinned
 // staging with one synchronisation, and `home` unpacks them while the workspace is still locked.  dump: object k's ray rows of every pass (and its entry row).
 struct SceneListCall {
-    const char* what; Model* const* ms; size_t n; int side; size_t n_items; uint32_t rows; bool camera;
+    const char* what; Model* const* ms; size_t n; int side; size_t n_items; uint32_t rows;
     std::function<int(SceneWs&, hipStream_t, uint32_t cap)> upload;
     std::function<void(SceneWs&, hipStream_t, const SceneSrc&, Model&, size_t j, uint32_t p0, uint32_t nc, uint32_t cap)> rays;
     std::function<void(SceneWs&, hipStream_t, uint32_t L, uint32_t cap, const float* dn, uint32_t p0, uint32_t nc)> composite;
@@ -180,9 +202,7 @@ struct SceneListCall {
 };
 static int scene_list_run(const SceneListCall& c) {
     Model* const* ms = c.ms; const size_t n = c.n, n_q = c.n_items; const int side = c.side; const SceneRaysDump* dump = c.dump;
-    if (!ms) { set_error("%s: null argument", c.what); return MON_ERR_ARG; }
-    { const int rc = scene_objects_check(c.what, ms, n, side, c.camera); if (rc) return rc; }
-    if (dump && dump->k >= n) { set_error("%s: dump of object %u of %zu", c.what, dump->k, n); return MON_ERR_ARG; }
+    { const int rc = scene_state_check(c.what, ms, n, side); if (rc) return rc; }
     const int device = ms[0]->device;
     HIPCHECK(use_device(device));
     const uint32_t nq = (uint32_t)n_q, cap = std::min(nq, kRenderChunkRays), L = (uint32_t)n;
@@ -239,7 +259,7 @@ static void scene_instances_home(int32_t* out, const float* row, size_t n, const
 // output rows (rgb 3n | depth | opacity | instance | hit_depth | hit_instance).
 int scene_probe_check(int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, const float* rgb, const float* depth) {
     if (!Twc16s || !q || !rgb || !depth) { set_error("scene_probe: null argument"); return MON_ERR_ARG; }
-    if (side != 0 && side != 1) { set_error("scene_probe: side must be 0 or 1"); return MON_ERR_ARG; }
+    { const int rc = side_check("scene_probe", side); if (rc) return rc; }
     if (n_poses == 0 || n_poses > kSceneProbeMaxPoses) { set_error("scene_probe: %zu poses (1 to %u)", n_poses, kSceneProbeMaxPoses); return MON_ERR_ARG; }
     if (n_q == 0 || n_q > kSceneProbeMaxQueries) { set_error("scene_probe: %zu queries (1 to %u)", n_q, kSceneProbeMaxQueries); return MON_ERR_ARG; }
     for (size_t k = 0; k < 16 * n_poses; ++k) if (!std::isfinite(Twc16s[k])) { set_error("scene_probe: pose %zu is not finite", k / 16); return MON_ERR_ARG; }
@@ -252,9 +272,7 @@ int scene_probe_check(int side, const float* Twc16s, size_t n_poses, const mon_s
 }
 int scene_probe(Model* const* ms, size_t n, int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q, float* rgb, float* depth,
                 float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance, const int32_t* ids, const SceneRaysDump* dump) {
-    if (!ms) { set_error("scene_probe: null argument"); return MON_ERR_ARG; }
-    { const int rc = scene_probe_check(side, Twc16s, n_poses, q, n_q, rgb, depth); if (rc) return rc; }
-    SceneListCall c{ "scene_probe", ms, n, side, n_q, 8u, true, {}, {}, {}, {}, dump };
+    SceneListCall c{ "scene_probe", ms, n, side, n_q, 8u, {}, {}, {}, {}, dump };
     c.upload = [&](SceneWs& ws, hipStream_t s, uint32_t) -> int {
         int rc; if ((rc = ws.q.grow(n_q)) || (rc = ws.poses.grow(16 * n_poses))) return rc;
         HIPCHECK(hipMemcpyAsync(ws.q.p, q, sizeof(mon_scene_query) * n_q, hipMemcpyHostToDevice, s));
@@ -282,7 +300,7 @@ int scene_probe(Model* const* ms, size_t n, int side, const float* Twc16s, size_
 // | instance | hit_t | hit_sample_t | hit_instance).  No camera: the objects need only share a device.
 int scene_cast_check(int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, const float* rgb, const float* dist) {
     if (!rays || !rgb || !dist) { set_error("scene_cast: null argument"); return MON_ERR_ARG; }
-    if (side != 0 && side != 1) { set_error("scene_cast: side must be 0 or 1"); return MON_ERR_ARG; }
+    { const int rc = side_check("scene_cast", side); if (rc) return rc; }
     if (n_rays == 0 || n_rays > kSceneProbeMaxQueries) { set_error("scene_cast: %zu rays (1 to %u)", n_rays, kSceneProbeMaxQueries); return MON_ERR_ARG; }
     if (!(hit_opacity > 0.f && hit_opacity <= 0.999f)) { set_error("scene_cast: hit_opacity %g (above 0, at most 0.999)", (double)hit_opacity); return MON_ERR_ARG; }
     for (size_t i = 0; i < n_rays; ++i) {
@@ -300,10 +318,8 @@ int scene_cast_check(int side, const mon_scene_ray* rays, size_t n_rays, float h
 }
 int scene_cast(Model* const* ms, size_t n, int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, float* rgb, float* dist, float* opacity,
                int32_t* instance, float* hit_t, float* hit_sample_t, int32_t* hit_instance, const int32_t* ids, const SceneRaysDump* dump) {
-    if (!ms) { set_error("scene_cast: null argument"); return MON_ERR_ARG; }
-    { const int rc = scene_cast_check(side, rays, n_rays, hit_opacity, rgb, dist); if (rc) return rc; }
     const size_t n_q = n_rays;
-    SceneListCall c{ "scene_cast", ms, n, side, n_q, 9u, false, {}, {}, {}, {}, dump };
+    SceneListCall c{ "scene_cast", ms, n, side, n_q, 9u, {}, {}, {}, {}, dump };
     c.upload = [&](SceneWs& ws, hipStream_t s, uint32_t cap) -> int {
         int rc; if ((rc = ws.rays.grow(n_q)) || (rc = ws.entry.grow(n * (size_t)cap))) return rc;
         HIPCHECK(hipMemcpyAsync(ws.rays.p, rays, sizeof(mon_scene_ray) * n_q, hipMemcpyHostToDevice, s));
@@ -369,28 +385,30 @@ struct ScenePoseWs {
     DevBuf<SceneWinFrame> wframes; DevBuf<float> wmom;                            // scene_window: the frame table, moments [F + K][12]
     std::vector<hipEvent_t> ev;
 };
-int scene_pose_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16, const mon_pose_refine_params* p) {
-    if (!ms || !obs || !Twc16 || !p) { set_error("scene pose: null argument"); return MON_ERR_ARG; }
-    if (n == 0 || n > kSceneMaxLists) { set_error("scene pose: %zu objects (1 to %u)", n, kSceneMaxLists); return MON_ERR_ARG; }
-    { const int rc = scene_objects_present("scene pose", ms, n); if (rc) return rc; }
+// what scene_pose asks of its arguments without an object ...
+int scene_pose_check(int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16, const mon_pose_refine_params* p) {
+    REQUIRE_ARG("scene pose", obs, "obs"); REQUIRE_ARG("scene pose", Twc16, "pose"); REQUIRE_ARG("scene pose", p, "params");
     if (n_obs == 0) { set_error("scene pose: no boxes"); return MON_ERR_ARG; }
     if (p->iters < 0) { set_error("scene pose: iters %d < 0", p->iters); return MON_ERR_ARG; }
-    if (side != 0 && side != 1) { set_error("scene pose: side %d (0 or 1)", side); return MON_ERR_ARG; }
-    if (p->rays_per_iter > kPoseMaxRays) { set_error("scene pose: rays_per_iter %u above %u", p->rays_per_iter, kPoseMaxRays); return MON_ERR_ARG; }
-    const Model& m0 = *ms[0];
-    for (size_t j = 1; j < n; ++j) {
-        { const int rc = scene_same_camera("scene pose", m0, *ms[j], j); if (rc) return rc; }
-        if (ms[j]->ds != m0.ds) { set_error("scene pose: object %zu is on another dataset", j); return MON_ERR_ARG; }
-    }
+    return side_check("scene pose", side);
+}
+// ... and of the rays: at most kPoseMaxRays of them, the boxes of one frame, each inside a frame the objects' dataset holds.  (The first two need no object.
+// They stand here because the online manager has always reported "nothing published yet", a MON_ERR_STATE, in front of them.)
+static int scene_boxes_check(const Dataset& ds, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params& p) {
+    if (p.rays_per_iter > kPoseMaxRays) { set_error("scene pose: rays_per_iter %u above %u", p.rays_per_iter, kPoseMaxRays); return MON_ERR_ARG; }
     uint64_t total = 0;
     for (size_t i = 0; i < n_obs; ++i) {
         if (obs[i].FrameId != obs[0].FrameId) { set_error("scene pose: boxes name frames %u and %u (one frame per call)", obs[0].FrameId, obs[i].FrameId);
             return MON_ERR_ARG; }
-        { const int rc = pose_box_check("scene pose", *m0.ds, obs[i], i, total); if (rc) return rc; }
+        { const int rc = pose_box_check("scene pose", ds, obs[i], i, total); if (rc) return rc; }
     }
-    if (!p->rays_per_iter && total > kPoseMaxRays) { set_error("scene pose: %llu pixels in the boxes (at most %u with rays_per_iter = 0)",
+    if (!p.rays_per_iter && total > kPoseMaxRays) { set_error("scene pose: %llu pixels in the boxes (at most %u with rays_per_iter = 0)",
         (unsigned long long)total, kPoseMaxRays); return MON_ERR_ARG; }
     return MON_OK;
+}
+int scene_pose_objects_check(Model* const* ms, size_t n, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p) {
+    { const int rc = scene_objects_check("scene pose", ms, n, true, true); if (rc) return rc; }
+    return scene_boxes_check(*ms[0]->ds, obs, n_obs, *p);
 }
 
 // ---- what scene_pose, scene_pose_batch and scene_window set up alike.
@@ -457,10 +475,8 @@ static SceneCompGradArgs scene_comp_args(const ScenePoseWs& w, size_t n, uint32_
 
 int scene_pose(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16, const mon_pose_refine_params& p, int iters,
                uint32_t iteration, float* pose_out, float* loss_trace, float* loss, float* grad6, const ScenePoseDump* dump, const float* level_w) {
-    { const int rc = scene_pose_check(ms, n, side, obs, n_obs, Twc16, &p); if (rc) return rc; }
-    if (dump && dump->k >= n) { set_error("scene pose: dump of object %u of %zu", dump->k, n); return MON_ERR_ARG; }
-    int Lmax = 0;
-    { const int rc = scene_state_check("scene pose", ms, n, side, Lmax); if (rc) return rc; }
+    { const int rc = scene_state_check("scene pose", ms, n, side); if (rc) return rc; }
+    const int Lmax = scene_levels(ms, n).Lmax;
     std::vector<uint32_t> prefix;
     const uint32_t total = append_prefix(prefix, obs, n_obs), n_rays = p.rays_per_iter ? p.rays_per_iter : total;
     const int device = ms[0]->device;
@@ -547,11 +563,16 @@ int scene_pose(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, 
 // hypotheses of n rays each as G n virtual rays in scene_pose's own list workspace (no more list memory than one evaluation of the chunk cap takes): K + 3
 // launches per pass, everything enqueued at once, one synchronisation, one copy home.
 static_assert(kSceneScoreMaxRays == kRenderChunkRays, "a hypothesis holds at most one chunk of scene_pose's rays");
-int scene_pose_batch_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, size_t n_poses,
-                           const mon_pose_refine_params* p, const float* losses) {
-    if (!Twc16s || !losses) { set_error("scene pose batch: null argument"); return MON_ERR_ARG; }
+int scene_pose_batch_check(int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, size_t n_poses, const mon_pose_refine_params* p,
+                           const float* losses) {
+    REQUIRE_ARG("scene pose batch", Twc16s, "Twc16s"); REQUIRE_ARG("scene pose batch", losses, "losses");
     if (n_poses == 0 || n_poses > kSceneScoreMaxPoses) { set_error("scene pose batch: %zu poses (1 to %u)", n_poses, kSceneScoreMaxPoses); return MON_ERR_ARG; }
-    { const int rc = scene_pose_check(ms, n, side, obs, n_obs, Twc16s, p); if (rc) return rc; }
+    if (p && p->rays_per_iter > kSceneScoreMaxRays) { set_error("scene pose batch: rays_per_iter %u (at most %u per hypothesis)", p->rays_per_iter,
+        kSceneScoreMaxRays); return MON_ERR_ARG; }
+    return scene_pose_check(side, obs, n_obs, Twc16s, p);
+}
+int scene_pose_batch_objects_check(Model* const* ms, size_t n, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p) {
+    { const int rc = scene_pose_objects_check(ms, n, obs, n_obs, p); if (rc) return rc; }
     const uint64_t n_rays = pose_n_rays(obs, n_obs, *p);
     if (n_rays > kSceneScoreMaxRays) { set_error("scene pose batch: %llu rays per hypothesis (at most %u)", (unsigned long long)n_rays, kSceneScoreMaxRays);
         return MON_ERR_ARG; }
@@ -559,9 +580,7 @@ int scene_pose_batch_check(Model* const* ms, size_t n, int side, const mon_frame
 }
 int scene_pose_batch(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, size_t n_poses,
                      const mon_pose_refine_params& p, uint32_t iteration, float* losses) {
-    { const int rc = scene_pose_batch_check(ms, n, side, obs, n_obs, Twc16s, n_poses, &p, losses); if (rc) return rc; }
-    int Lmax = 0;
-    { const int rc = scene_state_check("scene pose", ms, n, side, Lmax); if (rc) return rc; }
+    { const int rc = scene_state_check("scene pose", ms, n, side); if (rc) return rc; }
     std::vector<uint32_t> prefix;
     const uint32_t total = append_prefix(prefix, obs, n_obs), n_rays = p.rays_per_iter ? p.rays_per_iter : total, H = (uint32_t)n_poses;
     const int device = ms[0]->device;
@@ -574,7 +593,7 @@ int scene_pose_batch(Model* const* ms, size_t n, int side, const mon_frame_bbox*
     int rc;
     if ((rc = w.poses.grow((size_t)H * 16)) || (rc = w.scores.grow((size_t)H)) || (rc = w.h_scores.grow((size_t)H))) return rc;
     std::vector<size_t> frag_off;
-    if ((rc = scene_pose_prologue(w, s, ms, n, nullptr, obs, n_obs, prefix, cap, (size_t)Gmax * parts, nullptr, 0, Lmax, frag_off))) return rc;
+    if ((rc = scene_pose_prologue(w, s, ms, n, nullptr, obs, n_obs, prefix, cap, (size_t)Gmax * parts, nullptr, 0, 0, frag_off))) return rc;
     HIPCHECK(hipMemcpyAsync(w.poses.p, Twc16s, 64 * (size_t)H, hipMemcpyHostToDevice, s));
     const float inv_n = 1.f / (float)n_rays;
     for (uint32_t h0 = 0; h0 < H; h0 += Gmax) {
@@ -616,11 +635,13 @@ int window_frames(const mon_frame_bbox* obs, size_t n_obs, uint32_t* frame_ids, 
     *n_frames = F;
     return MON_OK;
 }
-int scene_window_params_check(const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const mon_pose_refine_params* p, const mon_window_params* w,
-                              const float* Tow16s, bool refine) {
-    if (!obs || !Twc16s || !p || (refine && !w)) { set_error("scene window: null argument"); return MON_ERR_ARG; }
+int scene_window_check(int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const mon_pose_refine_params* p, const mon_window_params* w,
+                       const float* Tow16s, bool refine) {
+    REQUIRE_ARG("scene window", obs, "obs"); REQUIRE_ARG("scene window", Twc16s, "Twc16s"); REQUIRE_ARG("scene window", p, "params");
+    if (refine) REQUIRE_ARG("scene window", w, "window params");
     if (n_obs == 0) { set_error("scene window: no boxes"); return MON_ERR_ARG; }
     if (p->iters < 0) { set_error("scene window: iters %d < 0", p->iters); return MON_ERR_ARG; }
+    { const int rc = side_check("scene pose", side); if (rc) return rc; }
     uint32_t ids[kWindowMaxFrames]; size_t F = 0;
     { const int rc = window_frames(obs, n_obs, ids, &F); if (rc) return rc; }
     if (refine) {
@@ -633,12 +654,12 @@ int scene_window_params_check(const mon_frame_bbox* obs, size_t n_obs, const flo
     }
     return MON_OK;
 }
-// the MON_ERR_ARG cases that need the objects; the caller has passed scene_window_params_check (the frames are contiguous, at most kWindowMaxFrames)
-int scene_window_frames_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const float* Tow16s,
-                              const mon_pose_refine_params* p) {
-    for (size_t i0 = 0, f = 0; i0 < n_obs; ++f) {
+// ... and what needs the objects (the frames are contiguous, at most kWindowMaxFrames): each frame's boxes as scene_pose takes them, its rays in one pass
+int scene_window_objects_check(Model* const* ms, size_t n, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16s, const mon_pose_refine_params* p) {
+    { const int rc = scene_objects_check("scene pose", ms, n, true, true); if (rc) return rc; }
+    for (size_t i0 = 0; i0 < n_obs; ) {
         size_t i1 = i0 + 1; while (i1 < n_obs && obs[i1].FrameId == obs[i0].FrameId) ++i1;
-        { const int rc = scene_pose_check(ms, n, side, obs + i0, i1 - i0, Twc16s + 16 * f, p); if (rc) return rc; }
+        { const int rc = scene_boxes_check(*ms[0]->ds, obs + i0, i1 - i0, *p); if (rc) return rc; }
         const uint64_t n_rays = pose_n_rays(obs + i0, i1 - i0, *p);
         if (n_rays > kWindowPassRays) { set_error("scene window: %llu rays in frame %u (at most %u: a frame is never split across passes)",
             (unsigned long long)n_rays, obs[i0].FrameId, kWindowPassRays); return MON_ERR_ARG; }
@@ -651,9 +672,8 @@ int scene_window_frames_check(Model* const* ms, size_t n, int side, const mon_fr
 int scene_window(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Twc16s, const float* Tow16s,
                  const mon_pose_refine_params& p, const mon_window_params* wp, int iters, uint32_t iteration, const float* level_w, float* Twc16s_out,
                  float* Tow16s_out, float* loss_trace, float* frame_trace, float* loss, float* frame_loss, float* cam_grad6, float* obj_grad6) {
-    { const int rc = scene_window_frames_check(ms, n, side, obs, n_obs, Twc16s, Tow16s, &p); if (rc) return rc; }
-    int Lmax = 0;
-    { const int rc = scene_state_check("scene pose", ms, n, side, Lmax); if (rc) return rc; }
+    { const int rc = scene_state_check("scene pose", ms, n, side); if (rc) return rc; }
+    const int Lmax = scene_levels(ms, n).Lmax;
     // the frames in window order, each with the grids a single-frame call of its rays uses; the passes
     std::vector<SceneWinFrame> fr; std::vector<uint32_t> prefix; std::vector<uint32_t> pass0{ 0u };   // pass k holds frames [pass0[k], pass0[k + 1])
     uint32_t row_stride = 0, n_lp = 0, cap = 0, v_next = 0;
@@ -740,23 +760,19 @@ int scene_window(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs
 
 // ---- wide-basin relocalisation (mon_scene_relocalise / mon_online_relocalise): score every candidate, refine the best few with scene_pose, score the
 // refined poses and their starts together, return the winner.  2 + min(keep, n_cands) stream synchronisations: one per scoring round, one per refinement.
-int scene_reloc_check(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* cands, size_t n_cands,
-                      const mon_pose_refine_params* p, const mon_pose_c2f_params* c, const mon_reloc_params* r, const float* pose_out) {
-    if (!cands || !p || !r || !pose_out) { set_error("relocalise: null argument"); return MON_ERR_ARG; }
+int scene_reloc_check(int side, const mon_frame_bbox* obs, size_t n_obs, const float* cands, size_t n_cands, const mon_pose_refine_params* p,
+                      const mon_reloc_params* r, const float* pose_out) {
+    REQUIRE_ARG("relocalise", cands, "candidates"); REQUIRE_ARG("relocalise", p, "params"); REQUIRE_ARG("relocalise", r, "reloc params");
+    REQUIRE_ARG("relocalise", pose_out, "Twc16_out");
     if (n_cands == 0 || n_cands > kSceneScoreMaxPoses) { set_error("relocalise: %zu candidates (1 to %u)", n_cands, kSceneScoreMaxPoses); return MON_ERR_ARG; }
     if (r->score_rays == 0 || r->score_rays > kSceneScoreMaxRays) { set_error("relocalise: score_rays %u (1 to %u)", r->score_rays, kSceneScoreMaxRays);
         return MON_ERR_ARG; }
     if (r->keep == 0 || r->keep > kRelocMaxKeep) { set_error("relocalise: keep %u (1 to %u)", r->keep, kRelocMaxKeep); return MON_ERR_ARG; }
-    { const int rc = scene_pose_check(ms, n, side, obs, n_obs, cands, p); if (rc) return rc; }
-    if (c) { const int rc = pose_c2f_check(c); if (rc) return rc; }
-    return MON_OK;
+    return scene_pose_check(side, obs, n_obs, cands, p);
 }
 int scene_relocalise(Model* const* ms, size_t n, int side, const mon_frame_bbox* obs, size_t n_obs, const float* cands, size_t n_cands,
-                     const mon_pose_refine_params& p, const mon_pose_c2f_params* c, const mon_reloc_params& r, float* pose_out, mon_reloc_result* result,
+                     const mon_pose_refine_params& p, const float* level_w, const mon_reloc_params& r, float* pose_out, mon_reloc_result* result,
                      float* scores) {
-    { const int rc = scene_reloc_check(ms, n, side, obs, n_obs, cands, n_cands, &p, c, &r, pose_out); if (rc) return rc; }
-    int Lmax = 0;
-    { const int rc = scene_state_check("scene pose", ms, n, side, Lmax); if (rc) return rc; }
     mon_pose_refine_params ps = p; ps.rays_per_iter = r.score_rays;
     // 1. every candidate's score
     std::vector<float> S(n_cands);
@@ -769,13 +785,12 @@ int scene_relocalise(Model* const* ms, size_t n, int side, const mon_frame_bbox*
         return fa != fb ? fa : (fa && S[a] < S[b]); });
     const size_t k = std::min<size_t>(r.keep, n_cands);
     std::vector<uint32_t> kept{ 0u }; kept.insert(kept.end(), order.begin(), order.begin() + (ptrdiff_t)(k - 1));
-    // 3. each of them refined as mon_scene_refine_camera refines it
-    std::vector<float> table; if (c) table = pose_c2f_table(*c, Lmax, p.iters);
+    // 3. each of them refined as mon_scene_refine_camera refines it (level_w: its schedule's table, or nullptr)
     std::vector<float> list(2 * k * 16);
     for (size_t i = 0; i < k; ++i) {
         const float* start = cands + 16 * (size_t)kept[i]; float* pose = list.data() + 16 * i;
         std::memcpy(list.data() + 16 * (k + i), start, 64); std::memcpy(pose, start, 64);
-        rc = scene_pose(ms, n, side, obs, n_obs, pose, p, p.iters, 0u, pose, nullptr, nullptr, nullptr, nullptr, table.empty() ? nullptr : table.data());
+        rc = scene_pose(ms, n, side, obs, n_obs, pose, p, p.iters, 0u, pose, nullptr, nullptr, nullptr, nullptr, level_w);
         if (rc) return rc;
     }
     // 4. the refined poses and their starts under the common key; the lowest finite score wins (ties to the earlier entry)

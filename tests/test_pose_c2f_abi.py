@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from abi_decl import p as pp
 
 MON_ERR_ARG = 1
 CORE = ("mon_pose_c2f_default", "mon_pose_c2f_weights", "mon_object_pose_loss_levels", "mon_object_refine_pose_c2f", "mon_online_refine_pose_c2f")
@@ -106,7 +107,6 @@ def test_pose_c2f_weights_edges(pkg):
 
 def test_pose_c2f_bad_arguments_fail_before_the_device(pkg):
     L = pkg.lib()
-    pp = lambda a: a.ctypes.data_as(C.c_void_p)           # noqa: E731
     fake = np.zeros(64, np.uint64)                         # stands in for an object / manager: every check below comes before it is looked at
     obj = pp(fake)
     obs = np.array([[0, 0, 0, 4, 4]], np.uint32); pose = np.eye(4, dtype=np.float32).reshape(16); g = np.zeros(6, np.float32)

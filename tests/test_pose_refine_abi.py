@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from abi_decl import p as pp
 
 MON_ERR_ARG = 1
 CORE = ("mon_pose_refine_default", "mon_object_pose_loss", "mon_object_refine_pose", "mon_online_refine_pose")
@@ -57,7 +58,6 @@ def test_pose_refine_params_layout_matches_c(pkg, tmp_path):
 
 def test_pose_refine_bad_arguments_fail_before_the_device(pkg):
     L = pkg.lib(); D = pkg.diag_lib()
-    pp = lambda a: a.ctypes.data_as(C.c_void_p)           # noqa: E731
     fake = np.zeros(64, np.uint64)                         # stands in for an object: every check below comes before it is looked at
     obj = pp(fake)
     obs = np.array([[0, 0, 0, 4, 4]], np.uint32); pose = np.eye(4, dtype=np.float32).reshape(16); g = np.zeros(6, np.float32)

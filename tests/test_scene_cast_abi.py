@@ -10,7 +10,7 @@ import re
 import numpy as np
 
 from conftest import ROOT
-from test_scene_probe_abi import _bound, _decl, _kind, _p
+from abi_decl import bound as _bound, decl as _decl, kind as _kind, p as _p
 
 NEW = ("mon_scene_cast", "mon_online_cast_rays", "mon_camera_rays")
 DIAG = ("mon_debug_scene_cast_rays", "mon_debug_scene_cast_composite")

@@ -4,6 +4,8 @@ import ctypes as C
 
 import numpy as np
 
+from abi_decl import p as pp
+
 MON_ERR_ARG = 1
 
 
@@ -20,7 +22,6 @@ def test_scene_render_null_and_empty_arguments(pkg):
     L = pkg.lib(); D = pkg.diag_lib()
     pose = np.eye(4, dtype=np.float32).reshape(16); out = np.zeros(64, np.float32); inst = np.zeros(16, np.int32)
     box = pkg.MonBBox(0, 0, 0, 4, 4); empty = pkg.MonBBox(0, 0, 0, 0, 4)
-    pp = lambda a: a.ctypes.data_as(C.c_void_p)           # noqa: E731
     one_null = (C.c_void_p * 1)(None)
     # no object list, an empty one, a null object, empty rect, null pose / outputs
     assert L.mon_scene_render(None, 1, 0, box, pp(pose), pp(out), pp(out), None, None) == MON_ERR_ARG

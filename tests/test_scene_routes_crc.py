@@ -1,0 +1,137 @@
+"""The scene and pose routes' outputs, bit for bit against the build of the commit before their host boundary was written once (scene.cpp's *_check
+functions, scene_models, scene_levels, pose_inout).
+
+That refactor touched no kernel and no launch line, and tests/test_launch_trace.py holds every launch, grid, stream and copy size of these routes.  What a
+launch trace cannot see is a kernel ARGUMENT: an offset into an output row, a pointer into the level-weight table, the in-out pose that is copied around a
+refinement.  So every public scene route and the object's coarse-to-fine refinement is called once on each side, and the CRC32 of every array it returns must
+equal the one recorded from the parent commit's build on an MI355X:
+
+    tools/variant_build.sh parent          # in a checkout of the parent commit
+    MON_CORE_LIB=<that checkout>/ro-map_amd/build_parent/libmon_core.so python tests/test_scene_routes_crc.py --record
+
+conftest's small_scene (120 x 160, 12 views), two base.json objects on its one object (the second on a box 1.5 times as large) with fixed sample seeds, 60
+steps each.  The shapes cross what the host computes offsets for: the full frame is 19 200 pixels (a pass boundary at 16 384), the probe and the cast take
+16 384 + 100 items, the batch scores 5 poses x 4000 drawn rays (passes of 4 and 1), the window has 3 frames and refines the objects, relocalisation keeps 2 of
+6 candidates.  Side 1 is compared only when render_snapshot reports step 60 for both objects; otherwise the case fails.  The online routes are left out:
+what their snapshots hold depends on thread timing.
+
+Bit equality is the condition: there is no tolerance."""
+import json
+import math
+import os
+import sys
+import zlib
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import __graft_entry__ as ge  # noqa: E402
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "scene_routes_parent_crc.json")
+SCENE = dict(n_views=12, H=120, W=160, f=130.0, seed=0)          # (conftest's small_scene)
+KW = (dict(sample_seed=5), dict(sample_seed=7))                  # base.json otherwise
+INFLATE = (1.0, 1.5)
+STEPS = 60
+VIEWS = (3, 4, 5)                                                # the window's frames; VIEWS[0]: the frame of the single-frame routes
+N_ITEMS = 16384 + 100                                            # probe queries and cast rays: one pass boundary
+ROUTES = ("render_scene", "probe_scene", "cast_scene", "scene_pose_loss", "scene_refine_camera", "scene_pose_loss_batch", "scene_refine_window",
+          "scene_relocalise", "refine_pose_c2f")
+
+
+def _crc(a):
+    return "%08x" % zlib.crc32(np.ascontiguousarray(a).tobytes())
+
+
+def make_objects(pkg, ss, sc):
+    """the dataset and the two objects, trained and published at step STEPS"""
+    ds, o0 = ge.make_problem(pkg, sc, KW[0])
+    ob = sc.objects[0]
+    o1 = pkg.ObjectNeRF(ds, pkg.default_config(**KW[1]), ob["cls"], ss.colmajor(ob["Tow"]), -ob["half"] * INFLATE[1], ob["half"] * INFLATE[1])
+    o1.add_boxes(ob["boxes"])
+    box = _boxes(sc, VIEWS[:1])[0]
+    for o in (o0, o1):
+        o.train(STEPS - 1)
+        try:                                                     # a viewer asks, so that the next train call publishes whatever the clock says
+            o.render_snapshot(box, ss.colmajor(sc.Twc[VIEWS[0]]))
+        except Exception:                                        # (nothing published yet: the request stands all the same)
+            pass
+        o.train(1)
+    return ds, [o0, o1]
+
+
+def _boxes(sc, views):
+    return np.array([[q for q in sc.objects[0]["boxes"] if int(q[0]) == v][0] for v in views], np.uint32)
+
+
+def run_routes(pkg, ss, sc, objs, side):
+    """{route: [CRC32 of every array it returns]} on one side"""
+    v0 = VIEWS[0]; T16 = ss.colmajor(sc.Twc[v0]); box = _boxes(sc, VIEWS[:1])
+    rs = np.random.RandomState(11)
+    q = pkg.scene_queries(rs.randint(0, 2, N_ITEMS), np.arange(N_ITEMS), rs.uniform(0, sc.W - 1, N_ITEMS), rs.uniform(0, sc.H - 1, N_ITEMS))
+    Twc2 = np.stack([ss.colmajor(sc.Twc[v]) for v in VIEWS[:2]])
+    rays, _ = pkg.camera_rays((sc.fx, sc.fy, sc.cx, sc.cy), Twc2, q)
+    off = pkg.pose_hypotheses(T16, 6, math.radians(6.0), 0.03, seed=4)          # candidate 0: the frame's pose, 1..5 around it
+    p3 = pkg.pose_refine_default(iters=3, rays_per_iter=512)
+    wobs = _boxes(sc, VIEWS); Twc3 = np.stack([off[1], off[2], off[3]]); Tow = np.stack([ss.colmajor(sc.objects[0]["Tow"])] * 2)
+    out = {}
+    out["render_scene"] = pkg.render_scene(objs, (v0, 0, 0, sc.H, sc.W), T16, side=side)
+    out["probe_scene"] = pkg.probe_scene(objs, q, Twc2, side=side)
+    out["cast_scene"] = pkg.cast_scene(objs, rays, side=side)
+    loss, g = pkg.scene_pose_loss(objs, box, off[1], pkg.pose_refine_default(rays_per_iter=512), side=side, iteration=5)
+    out["scene_pose_loss"] = (np.float32(loss), g)
+    out["scene_refine_camera"] = pkg.scene_refine_camera(objs, box, off[1], p3, c2f=True, side=side)
+    out["scene_pose_loss_batch"] = (pkg.scene_pose_loss_batch(objs, box, off[:5], pkg.pose_refine_default(rays_per_iter=4000), side=side, iteration=5),)
+    out["scene_refine_window"] = pkg.scene_refine_window(objs, wobs, Twc3, Tow, p3, window=dict(n_fixed_frames=1, refine_objects=1), side=side)
+    pose, res, scores = pkg.scene_relocalise(objs, box, off, p3, reloc=pkg.reloc_default(keep=2, score_rays=256), side=side)
+    out["scene_relocalise"] = (pose, np.array([res.best_candidate, res.refined], np.uint32),
+                               np.array([res.score_candidate0, res.score_best_candidate, res.score_final], np.float32), scores)
+    out["refine_pose_c2f"] = objs[0].refine_pose_c2f(box, Tow[0], p3, side=side)
+    assert set(out) == set(ROUTES)
+    return {k: [_crc(a) for a in v] for k, v in out.items()}
+
+
+def snapshot_steps(ss, sc, objs):
+    return [int(o.render_snapshot(_boxes(sc, VIEWS[:1])[0], ss.colmajor(sc.Twc[VIEWS[0]]))[-1]) for o in objs]
+
+
+@pytest.fixture(scope="module")
+def crcs(pkg, ss, small_scene):
+    """every route on both sides, once for all cases"""
+    assert pkg.device_count() >= 1, "no HIP device visible: the GPU tests must run on the MI355X box"
+    ds, objs = make_objects(pkg, ss, small_scene)
+    steps = snapshot_steps(ss, small_scene, objs)
+    got = {side: run_routes(pkg, ss, small_scene, objs, side) for side in (0, 1)}
+    for o in objs:
+        o.close()
+    ds.close()
+    return steps, got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("side", [0, 1])
+@pytest.mark.parametrize("route", ROUTES)
+def test_route_returns_the_parent_builds_bits(crcs, route, side):
+    steps, got = crcs
+    with open(GOLDEN) as f:
+        want = json.load(f)[str(side)][route]
+    print(route, side, got[side][route], want, steps)
+    if side == 1:
+        assert steps == [STEPS, STEPS], "side 1 does not hold the objects' final step: %s" % (steps,)
+    assert got[side][route] == want, (route, side, got[side][route], want)
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] != ["--record"]:
+        sys.exit("usage: MON_CORE_LIB=<library of the parent commit> python tests/test_scene_routes_crc.py --record")
+    pkg_, ss_ = ge.load_package(), ge.load_tools()
+    sc_ = ss_.make_scene(**SCENE)
+    ds_, objs_ = make_objects(pkg_, ss_, sc_)
+    assert snapshot_steps(ss_, sc_, objs_) == [STEPS, STEPS]
+    rec = {str(side): run_routes(pkg_, ss_, sc_, objs_, side) for side in (0, 1)}
+    print(json.dumps(rec))
+    with open(GOLDEN, "w") as f:
+        json.dump(rec, f, indent=1); f.write("\n")

@@ -9,41 +9,21 @@ import re
 import numpy as np
 
 from conftest import ROOT
+from abi_decl import bound as _bound, decl as _decl, kind as _kind, p as _p
 
 NEW = ("mon_scene_pose_loss", "mon_scene_refine_camera", "mon_online_refine_camera")
 NEW_DIAG = ("mon_debug_scene_pose_samples", "mon_debug_scene_composite_grad")
 MON_ERR_ARG = 1
 
 
-def _decl(header, name):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^;]*)\)\s*;" % name, txt)
-    assert m, "%s is not declared in %s" % (name, header)
-    return [a.strip() for a in m.group(1).split(",")]
-
-
-def _kind(arg):
-    """ctypes class a C parameter declaration binds to in binding.py's tables"""
-    if "*" in arg:
-        return "ptr"
-    return {"size_t": "size_t", "int": "int", "uint32_t": "uint32", "float": "float"}[arg.split()[0] if not arg.startswith("const") else arg.split()[1]]
-
-
-def _bound(t):
-    if t in (C.c_void_p, C.c_char_p) or (isinstance(t, type) and issubclass(t, C._Pointer)):
-        return "ptr"
-    return {C.c_size_t: "size_t", C.c_int: "int", C.c_uint32: "uint32", C.c_float: "float"}[t]
-
-
 def test_symbols_are_declared_exported_and_bound(pkg):
     core = C.CDLL(pkg.lib_path()); diag = pkg.diag_lib()
     for name in NEW:
         assert name in pkg.exported_symbols() and hasattr(core, name), name
-        _decl("mon_core.h", name)
+        _decl(name, "mon_core.h")
     for name in NEW_DIAG:
         assert name in pkg.diag_symbols() and hasattr(diag, name) and not hasattr(core, name), name
-        _decl("mon_core_diag.h", name)
+        _decl(name, "mon_core_diag.h")
     assert not set(NEW_DIAG) & set(pkg.exported_symbols())
 
 
@@ -51,13 +31,9 @@ def test_binding_tables_match_the_headers(pkg):
     import importlib
     b = importlib.import_module(pkg.__name__ + ".binding")
     for name in NEW:
-        assert [_kind(a) for a in _decl("mon_core.h", name)] == [_bound(t) for t in b._SIGS[name][1]], name
+        assert [_kind(a) for a in _decl(name, "mon_core.h")] == [_bound(t) for t in b._SIGS[name][1]], name
     for name in NEW_DIAG:
-        assert [_kind(a) for a in _decl("mon_core_diag.h", name)] == [_bound(t) for t in b._DIAG_SIGS[name][1]], name
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+        assert [_kind(a) for a in _decl(name, "mon_core_diag.h")] == [_bound(t) for t in b._DIAG_SIGS[name][1]], name
 
 
 def test_argument_errors_need_no_device(pkg):

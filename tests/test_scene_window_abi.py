@@ -10,34 +10,11 @@ import re
 import numpy as np
 
 from conftest import ROOT
+from abi_decl import bound as _bound, decl as _decl, kind as _kind, p as _p
 
 NEW = ("mon_window_default", "mon_window_frames", "mon_scene_window_loss", "mon_scene_refine_window", "mon_online_refine_window", "mon_object_set_pose",
        "mon_online_set_object_pose")
 MON_ERR_ARG = 1
-
-
-def _decl(name):
-    txt = open(os.path.join(ROOT, "include", "mon_core.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^;]*)\)\s*;" % name, txt)
-    assert m, "%s is not declared in mon_core.h" % name
-    return [a.strip() for a in m.group(1).split(",")]
-
-
-def _kind(arg):
-    if "*" in arg:
-        return "ptr"
-    return {"size_t": "u64", "int": "int", "uint32_t": "uint32", "uint64_t": "u64", "float": "float"}[arg.split()[1 if arg.startswith("const") else 0]]
-
-
-def _bound(t):
-    if t in (C.c_void_p, C.c_char_p) or (isinstance(t, type) and issubclass(t, C._Pointer)):
-        return "ptr"
-    return {C.c_size_t: "u64", C.c_uint64: "u64", C.c_int: "int", C.c_uint32: "uint32", C.c_float: "float"}[t]
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def test_symbols_are_declared_exported_and_bound(pkg):

@@ -1,7 +1,9 @@
 // trace_driver.cpp -- walks the C ABI single-threaded on the host side built --offload-host-only against tests/tsan/hip_stub.cpp (no sanitizer) with the
-// stub's launch trace on: every kernel launch and asynchronous fill / copy of every training path as one line of text, under a heading per case and per call.
+// stub's launch trace on: every kernel launch and asynchronous fill / copy of every training path as one line of text, under a heading per case and per call;
+// then (part two) of every scene and pose route on both sides and through the online manager, and a list of the calls those routes refuse, with code and message.
 // tests/test_launch_trace.py compares the output with tests/golden/launch_trace.txt.  Usage: trace_driver <scratch dir> <config json>.  TEST INFRASTRUCTURE.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -101,6 +103,249 @@ static void online_case(const char* cfg_json, const unsigned char* rgb, const un
     OK(mon_online_destroy(om));
 }
 
+// ---- part two: the inference routes.  Every argument of every route in one record: a route reads its own fields, a case changes one or two of them.
+struct Args {
+    mon_object* const* objs; size_t n_objs; int side;
+    mon_frame_bbox rect; const float* Twc; float* rgb; float* depth;                      // render (rgb, depth: the required outputs of probe and cast too)
+    const float* poses; size_t n_poses; const mon_scene_query* q; size_t n_q;             // probe; poses: also the batch's poses and the candidates
+    const mon_scene_ray* rays; size_t n_rays; float hit_opacity;                          // cast
+    const mon_frame_bbox* obs; size_t n_obs; const mon_pose_refine_params* p; const mon_pose_c2f_params* c; const float* lw; float* pose_io;
+    float* losses; const mon_reloc_params* r; float* pose_out;                            // batch, relocalise
+    const mon_frame_bbox* wobs; size_t n_wobs; float* wTwc; float* Tow16s; const mon_window_params* w;      // window
+    mon_object* obj; const mon_pose_c2f_params* cc; const float* lwl;                     // object pose routes (cc, lwl: the arguments the _c2f / _levels calls require)
+    mon_online* om; size_t idx; size_t n_online;
+    float* out;                                                                           // every optional output
+};
+static int32_t* as_i32(float* p) { return reinterpret_cast<int32_t*>(p); }
+static int scene_render(const Args& a) { return mon_scene_render(a.objs, a.n_objs, a.side, a.rect, a.Twc, a.rgb, a.depth, a.out, as_i32(a.out)); }
+static int scene_probe(const Args& a) { return mon_scene_probe(a.objs, a.n_objs, a.side, a.poses, a.n_poses, a.q, a.n_q, a.rgb, a.depth, a.out, as_i32(a.out), a.out,
+        as_i32(a.out)); }
+static int scene_cast(const Args& a) { return mon_scene_cast(a.objs, a.n_objs, a.side, a.rays, a.n_rays, a.hit_opacity, a.rgb, a.depth, a.out, as_i32(a.out), a.out,
+        a.out, as_i32(a.out)); }
+static int scene_pose_loss(const Args& a) { return mon_scene_pose_loss(a.objs, a.n_objs, a.side, a.obs, a.n_obs, a.Twc, a.p, 3u, a.lw, a.out, a.out + 8); }
+static int scene_refine_camera(const Args& a) { return mon_scene_refine_camera(a.objs, a.n_objs, a.side, a.obs, a.n_obs, a.p, a.c, a.pose_io, a.out); }
+static int scene_pose_loss_batch(const Args& a) { return mon_scene_pose_loss_batch(a.objs, a.n_objs, a.side, a.obs, a.n_obs, a.poses, a.n_poses, a.p, 3u, a.losses); }
+static int scene_relocalise(const Args& a) { mon_reloc_result res; return mon_scene_relocalise(a.objs, a.n_objs, a.side, a.obs, a.n_obs, a.poses, a.n_poses, a.p,
+        a.c, a.r, a.pose_out, &res, a.out); }
+static int scene_window_loss(const Args& a) { return mon_scene_window_loss(a.objs, a.n_objs, a.side, a.wobs, a.n_wobs, a.wTwc, a.Tow16s, a.p, 3u, a.lw, a.out,
+        a.out + 8, a.out + 64, a.out + 512); }
+static int scene_refine_window(const Args& a) { return mon_scene_refine_window(a.objs, a.n_objs, a.side, a.wobs, a.n_wobs, a.p, a.c, a.w, a.wTwc, a.Tow16s, a.out,
+        a.out + 64); }
+static int object_pose_loss(const Args& a) { return mon_object_pose_loss(a.obj, a.side, a.obs, a.n_obs, a.Twc, a.p, 3u, a.out, a.out + 8); }
+static int object_pose_loss_levels(const Args& a) { return mon_object_pose_loss_levels(a.obj, a.side, a.obs, a.n_obs, a.Twc, a.p, 3u, a.lwl, a.out, a.out + 8); }
+static int object_refine_pose(const Args& a) { return mon_object_refine_pose(a.obj, a.side, a.obs, a.n_obs, a.p, a.pose_io, a.out); }
+static int object_refine_pose_c2f(const Args& a) { return mon_object_refine_pose_c2f(a.obj, a.side, a.obs, a.n_obs, a.p, a.cc, a.pose_io, a.out); }
+static int online_render_scene(const Args& a) { return mon_online_render_scene(a.om, a.rect, a.Twc, a.rgb, a.depth, a.out, as_i32(a.out)); }
+static int online_probe_scene(const Args& a) { return mon_online_probe_scene(a.om, a.poses, a.n_poses, a.q, a.n_q, a.rgb, a.depth, a.out, as_i32(a.out), a.out,
+        as_i32(a.out)); }
+static int online_cast_rays(const Args& a) { return mon_online_cast_rays(a.om, a.rays, a.n_rays, a.hit_opacity, a.rgb, a.depth, a.out, as_i32(a.out), a.out, a.out,
+        as_i32(a.out)); }
+static int online_refine_camera(const Args& a) { return mon_online_refine_camera(a.om, a.obs, a.n_obs, a.p, a.c, a.pose_io, a.out); }
+static int online_refine_window(const Args& a) { uint8_t inc[8]; return mon_online_refine_window(a.om, a.wobs, a.n_wobs, a.p, a.c, a.w, a.wTwc, a.Tow16s, a.n_online,
+        inc, a.out, a.out + 64); }
+static int online_relocalise(const Args& a) { mon_reloc_result res; return mon_online_relocalise(a.om, a.obs, a.n_obs, a.poses, a.n_poses, a.p, a.c, a.r, a.pose_out,
+        &res, a.out); }
+static int online_refine_pose(const Args& a) { return mon_online_refine_pose(a.om, a.idx, a.obs, a.n_obs, a.p, a.pose_io, a.out); }
+static int online_refine_pose_c2f(const Args& a) { return mon_online_refine_pose_c2f(a.om, a.idx, a.obs, a.n_obs, a.p, a.cc, a.pose_io, a.out); }
+
+// a call that must fail, on one line with its code and message (no exit); `change` edits a copy `a` of the good arguments
+#define ERR(route, change) do { Args a = good; change; const int rc_ = route(a); \
+        std::printf("-- %s, %s -> %d: %s\n", #route, #change, rc_, rc_ != MON_OK ? mon_last_error() : "no error"); } while (0)
+// what every route with an object list refuses of it
+#define OBJS_ERRS(route) do { ERR(route, a.objs = nullptr); ERR(route, a.n_objs = 0); ERR(route, a.objs = many.data(); a.n_objs = 257); ERR(route, a.side = 2); \
+        ERR(route, a.objs = with_null); ERR(route, a.objs = other_K); ERR(route, a.objs = other_ds); ERR(route, a.objs = narrow); ERR(route, a.objs = xorwow); \
+        ERR(route, a.objs = unpublished; a.side = 1); } while (0)
+// ... and every route with boxes of one frame and refinement parameters (b_, p_: the fields the route reads them from)
+#define OBS_ERRS(route, b_, n_) do { ERR(route, a.b_ = nullptr); ERR(route, a.n_ = 0); ERR(route, a.p = nullptr); ERR(route, a.p = &p_neg); \
+        ERR(route, a.p = &p_many); ERR(route, a.b_ = &box_noframe; a.n_ = 1); ERR(route, a.b_ = &box_outside; a.n_ = 1); ERR(route, a.b_ = &box_empty; a.n_ = 1); \
+        } while (0)
+
+static mon_object* trained_object(mon_dataset* ds, const mon_config& cfg, float tx, int steps) {
+    float Tow[16]; std::memcpy(Tow, g_Tow, 64); Tow[12] = tx;
+    mon_object* o = nullptr; OK(mon_object_create(ds, &cfg, 7, Tow, g_amin, g_amax, &o));
+    const mon_frame_bbox b{ 0, 8, 8, 24, 32 }; OK(mon_object_add_boxes(o, &b, 1));
+    float loss = 0.f;
+    if (steps) { viewer_asks(o); hip_stub_trace(0); OK(mon_object_train(o, steps, &loss)); }      // (the viewer's request forces the publication)
+    return o;
+}
+static mon_dataset* make_dataset(float fx, const unsigned char* rgb, const unsigned char* inst) {
+    mon_dataset* ds = nullptr; OK(mon_dataset_create(0, H, W, fx, 60.f, 32.f, 24.f, kFrames, 0, &ds));
+    for (int v = 0; v < kFrames; ++v) OK(mon_dataset_add_frame(ds, v, rgb, 3, 0, inst, nullptr, g_pose));
+    return ds;
+}
+// an online manager of two objects over the driver's frames; publish: both get twelve boxes and train one Train_Step_Online, which ends with a publication
+// -- this thread waits for each (without a launch of its own), after which both object threads sleep
+static mon_online* make_online(const char* cfg_json, const unsigned char* rgb, const unsigned char* inst, bool publish) {
+    mon_online* om = nullptr; OK(mon_online_create(cfg_json, 0, 4, &om)); OK(mon_online_init(om));
+    OK(mon_online_dataset_init(om, 60.f, 60.f, 32.f, 24.f, H, W, kFrames));
+    for (int v = 0; v < kFrames; ++v) { char stamp[32]; std::snprintf(stamp, sizeof stamp, "%.6f", v * 0.1);
+        OK(mon_online_new_frame(om, (uint32_t)v, stamp, rgb, 3, inst, nullptr, g_pose)); }
+    const float bb[6] = { -0.3f, -0.3f, -0.3f, 0.3f, 0.3f, 0.3f };
+    std::vector<mon_frame_bbox> boxes; for (int v = 0; v < 12; ++v) boxes.push_back(mon_frame_bbox{ (uint32_t)v, 8, 8, 24, 32 });
+    for (int k = 0; k < 2; ++k) {
+        size_t idx = 0; OK(mon_online_create_nerf(om, 7, g_Tow, bb, bb + 3, &idx));
+        if (!publish) continue;
+        OK(mon_online_update_nerf_bbox(om, idx, boxes.data(), boxes.size(), 1));
+        for (;;) { int calls = 0; OK(mon_online_object_info(om, idx, nullptr, &calls, nullptr, nullptr)); if (calls >= 1) break;
+            std::this_thread::sleep_for(std::chrono::milliseconds(2)); }
+    }
+    return om;
+}
+
+static void inference_part(const char* cfg_json, const mon_config& base, const unsigned char* rgb, const unsigned char* inst) {
+    // ---- the set-up, untraced
+    hip_stub_trace(0);
+    mon_dataset* ds = make_dataset(60.f, rgb, inst); mon_dataset* ds_K = make_dataset(61.f, rgb, inst); mon_dataset* ds_2 = make_dataset(60.f, rgb, inst);
+    mon_object* o0 = trained_object(ds, base, 0.f, 2); mon_object* o1 = trained_object(ds, base, 0.05f, 2);
+    mon_object* o_K = trained_object(ds_K, base, 0.f, 2); mon_object* o_2 = trained_object(ds_2, base, 0.f, 2);
+    mon_config c16 = base; c16.n_neurons = 16; mon_config cxw = base; cxw.rng_flags = 1;
+    mon_object* o_16 = trained_object(ds, c16, 0.f, 2); mon_object* o_xw = trained_object(ds, cxw, 0.f, 2); mon_object* o_un = trained_object(ds, base, 0.f, 0);
+    hip_stub_trace(0);
+    mon_online* om = make_online(cfg_json, rgb, inst, true); mon_online* om_none = make_online(cfg_json, rgb, inst, false);
+    mon_object* objs[2] = { o0, o1 }; mon_object* with_null[2] = { o0, nullptr }; mon_object* other_K[2] = { o0, o_K }; mon_object* other_ds[2] = { o0, o_2 };
+    mon_object* narrow[2] = { o0, o_16 }; mon_object* xorwow[2] = { o0, o_xw }; mon_object* unpublished[2] = { o0, o_un };
+    std::vector<mon_object*> many(257, o0);
+    std::vector<float> out(1u << 20, 0.f), many_poses(16 * 4097);
+    for (size_t i = 0; i < many_poses.size(); i += 16) std::memcpy(&many_poses[i], g_pose, 64);
+    float poses3[3 * 16], pose_io[16], pose_out[16], wTwc[2 * 16], Tow16s[2 * 16], nan_pose[16], nan_Tow[2 * 16], lw[64], lw_neg[64];
+    for (int k = 0; k < 3; ++k) std::memcpy(poses3 + 16 * k, g_pose, 64);
+    std::memcpy(pose_io, g_pose, 64); std::memcpy(wTwc, poses3, 128); std::memcpy(Tow16s, g_Tow, 64); std::memcpy(Tow16s + 16, g_Tow, 64);
+    std::memcpy(nan_pose, g_pose, 64); nan_pose[13] = NAN; std::memcpy(nan_Tow, Tow16s, 128); nan_Tow[16 + 12] = INFINITY;
+    for (int l = 0; l < 64; ++l) { lw[l] = 1.f; lw_neg[l] = l == 1 ? -1.f : 1.f; }
+    const mon_scene_query q[5] = { { 0, 0, 10.5f, 8.25f }, { 1, 1, 32.f, 24.f }, { 0, 2, 40.f, 30.f }, { 1, 3, 0.f, 0.f }, { 0, 4, 63.f, 47.f } };
+    mon_scene_query q_nan[5], q_pose[5], q_key[5];
+    for (int i = 0; i < 5; ++i) q_nan[i] = q_pose[i] = q_key[i] = q[i];
+    q_nan[2].u = NAN; q_pose[3].pose = 2; q_key[4].key = 1u << 26;
+    const mon_scene_ray rays[4] = { { { 0, 0, -2 }, 10.f, { 0, 0, 1 }, 0 }, { { 0.1f, 0, -2 }, 10.f, { 0, 0, 1 }, 1 }, { { 0, 0.1f, -2 }, 1.f, { 0, 0, 1 }, 2 },
+                                    { { 0, 0, 2 }, INFINITY, { 0, 0, -1 }, 3 } };
+    mon_scene_ray r_nan[4], r_long[4], r_tmax[4], r_key[4];
+    for (int i = 0; i < 4; ++i) r_nan[i] = r_long[i] = r_tmax[i] = r_key[i] = rays[i];
+    r_nan[1].o[2] = NAN; r_long[2].d[2] = 1.1f; r_tmax[3].t_max = 0.f; r_key[0].key = 1u << 26;
+    const mon_frame_bbox obs[2] = { { 0, 8, 8, 16, 16 }, { 0, 30, 20, 8, 12 } };
+    const mon_frame_bbox wobs[3] = { { 0, 8, 8, 16, 16 }, { 0, 30, 20, 8, 12 }, { 1, 8, 8, 16, 16 } };          // a window of two frames, the first with two boxes
+    const mon_frame_bbox two_frames[2] = { { 0, 8, 8, 16, 16 }, { 1, 8, 8, 16, 16 } }, apart[3] = { { 0, 8, 8, 16, 16 }, { 1, 8, 8, 16, 16 }, { 0, 30, 20, 8, 12 } };
+    const mon_frame_bbox box_noframe{ 99, 8, 8, 16, 16 }, box_outside{ 0, 40, 8, 16, 32 }, box_empty{ 0, 8, 8, 0, 16 };
+    std::vector<mon_frame_bbox> frames33; for (uint32_t f = 0; f < 33; ++f) frames33.push_back(mon_frame_bbox{ f, 8, 8, 16, 16 });
+    mon_pose_refine_params p; OK(mon_pose_refine_default(&p)); p.iters = 2; p.rays_per_iter = 64;
+    mon_pose_refine_params p_neg = p, p_many = p, p_score = p; p_neg.iters = -1; p_many.rays_per_iter = (1u << 22) + 1u; p_score.rays_per_iter = 16385;
+    mon_pose_c2f_params c2f; OK(mon_pose_c2f_default(&c2f)); mon_pose_c2f_params c_bad = c2f; c_bad.ramp = 0.f;
+    mon_reloc_params r; OK(mon_reloc_default(&r)); r.score_rays = 32; r.keep = 2;
+    mon_reloc_params r_rays0 = r, r_rays_many = r, r_keep0 = r, r_keep17 = r; r_rays0.score_rays = 0; r_rays_many.score_rays = 16385; r_keep0.keep = 0; r_keep17.keep = 17;
+    mon_window_params w; OK(mon_window_default(&w));
+    mon_window_params w_fixed3 = w, w_free = w, w_lr = w; w_fixed3.n_fixed_frames = 3; w_free.n_fixed_frames = 0; w_lr.lr_obj_rot = -1.f;
+    float* const o = out.data();
+    const Args good{ objs, 2, 0, mon_frame_bbox{ 0, 4, 4, 16, 24 }, g_pose, o, o, poses3, 2, q, 5, rays, 4, 0.5f, obs, 2, &p, nullptr, nullptr, pose_io, o, &r, pose_out,
+                     wobs, 3, wTwc, Tow16s, &w, o0, &c2f, lw, om, 0, 2, o };
+
+    // ---- every route once, on both sides
+    std::printf("== inference routes\n");
+    hip_stub_trace(1);
+    for (int side = 0; side < 2; ++side) {
+        std::printf("-- side %d\n", side);
+        Args a = good; a.side = side; Args ac = a; ac.c = &c2f; Args al = a; al.lw = lw; Args a3 = a; a3.n_poses = 3;
+        CALL(scene_render(a)); CALL(scene_probe(a)); CALL(scene_cast(a)); CALL(scene_pose_loss(a)); CALL(scene_pose_loss(al));
+        CALL(scene_refine_camera(a)); CALL(scene_refine_camera(ac)); CALL(scene_pose_loss_batch(a3)); CALL(scene_relocalise(a3)); CALL(scene_relocalise(ac));
+        CALL(scene_window_loss(al)); CALL(scene_refine_window(a)); CALL(scene_refine_window(ac));
+        CALL(object_pose_loss(a)); CALL(object_pose_loss_levels(a)); CALL(object_refine_pose(a)); CALL(object_refine_pose_c2f(a));
+    }
+    {   std::printf("-- online manager, both objects published\n");
+        Args a = good; Args ac = a; ac.c = &c2f; Args a3 = a; a3.n_poses = 3;
+        CALL(online_render_scene(a)); CALL(online_probe_scene(a)); CALL(online_cast_rays(a)); CALL(online_refine_camera(a)); CALL(online_refine_camera(ac));
+        CALL(online_refine_window(a)); CALL(online_refine_window(ac)); CALL(online_relocalise(a3)); CALL(online_refine_pose(a)); CALL(online_refine_pose_c2f(a));
+    }
+
+    // ---- the calls every route refuses, with code and message; the trace stays on: none of them may reach the device
+    std::printf("== inference errors\n");
+    OBJS_ERRS(scene_render);
+    ERR(scene_render, a.Twc = nullptr); ERR(scene_render, a.rgb = nullptr); ERR(scene_render, a.depth = nullptr); ERR(scene_render, a.rect.w = 0);
+    ERR(scene_render, a.rect.h = 0); ERR(scene_render, a.objs = with_null; a.rect.w = 0);
+    OBJS_ERRS(scene_probe);
+    ERR(scene_probe, a.poses = nullptr); ERR(scene_probe, a.q = nullptr); ERR(scene_probe, a.rgb = nullptr); ERR(scene_probe, a.depth = nullptr);
+    ERR(scene_probe, a.n_poses = 0); ERR(scene_probe, a.poses = many_poses.data(); a.n_poses = 4097); ERR(scene_probe, a.n_q = 0); ERR(scene_probe, a.poses = nan_pose; a.n_poses = 1);
+    ERR(scene_probe, a.q = q_nan); ERR(scene_probe, a.q = q_pose); ERR(scene_probe, a.q = q_key);
+    ERR(scene_probe, a.objs = with_null; a.n_poses = 0); ERR(scene_probe, a.objs = with_null; a.n_q = 0); ERR(scene_probe, a.objs = with_null; a.q = q_nan);
+    ERR(scene_probe, a.n_objs = 0; a.n_q = 0);
+    OBJS_ERRS(scene_cast);
+    ERR(scene_cast, a.rays = nullptr); ERR(scene_cast, a.rgb = nullptr); ERR(scene_cast, a.depth = nullptr); ERR(scene_cast, a.n_rays = 0);
+    ERR(scene_cast, a.hit_opacity = 0.f); ERR(scene_cast, a.hit_opacity = 1.f); ERR(scene_cast, a.rays = r_nan); ERR(scene_cast, a.rays = r_long);
+    ERR(scene_cast, a.rays = r_tmax); ERR(scene_cast, a.rays = r_key); ERR(scene_cast, a.objs = with_null; a.n_rays = 0); ERR(scene_cast, a.objs = with_null; a.rays = r_long);
+    ERR(scene_cast, a.n_objs = 257; a.objs = many.data(); a.hit_opacity = 0.f);
+    OBJS_ERRS(scene_pose_loss); OBS_ERRS(scene_pose_loss, obs, n_obs);
+    ERR(scene_pose_loss, a.Twc = nullptr); ERR(scene_pose_loss, a.obs = two_frames); ERR(scene_pose_loss, a.lw = lw_neg);
+    ERR(scene_pose_loss, a.objs = with_null; a.n_obs = 0); ERR(scene_pose_loss, a.objs = with_null; a.lw = lw_neg);
+    OBJS_ERRS(scene_refine_camera); OBS_ERRS(scene_refine_camera, obs, n_obs);
+    ERR(scene_refine_camera, a.pose_io = nullptr); ERR(scene_refine_camera, a.c = &c_bad); ERR(scene_refine_camera, a.objs = with_null; a.c = &c_bad);
+    ERR(scene_refine_camera, a.objs = narrow; a.c = &c_bad); ERR(scene_refine_camera, a.obs = &box_noframe; a.n_obs = 1; a.c = &c_bad);
+    OBJS_ERRS(scene_pose_loss_batch); OBS_ERRS(scene_pose_loss_batch, obs, n_obs);
+    ERR(scene_pose_loss_batch, a.poses = nullptr); ERR(scene_pose_loss_batch, a.losses = nullptr); ERR(scene_pose_loss_batch, a.n_poses = 0);
+    ERR(scene_pose_loss_batch, a.poses = many_poses.data(); a.n_poses = 4097); ERR(scene_pose_loss_batch, a.p = &p_score);
+    ERR(scene_pose_loss_batch, a.objs = with_null; a.n_poses = 0); ERR(scene_pose_loss_batch, a.objs = with_null; a.p = &p_score);
+    ERR(scene_pose_loss_batch, a.objs = with_null; a.n_obs = 0);
+    OBJS_ERRS(scene_relocalise); OBS_ERRS(scene_relocalise, obs, n_obs);
+    ERR(scene_relocalise, a.poses = nullptr); ERR(scene_relocalise, a.r = nullptr); ERR(scene_relocalise, a.pose_out = nullptr); ERR(scene_relocalise, a.n_poses = 0);
+    ERR(scene_relocalise, a.poses = many_poses.data(); a.n_poses = 4097); ERR(scene_relocalise, a.r = &r_rays0); ERR(scene_relocalise, a.r = &r_rays_many);
+    ERR(scene_relocalise, a.r = &r_keep0); ERR(scene_relocalise, a.r = &r_keep17); ERR(scene_relocalise, a.c = &c_bad);
+    ERR(scene_relocalise, a.objs = with_null; a.r = &r_keep0); ERR(scene_relocalise, a.objs = with_null; a.r = &r_rays0); ERR(scene_relocalise, a.objs = with_null; a.n_poses = 0);
+    ERR(scene_relocalise, a.objs = with_null; a.c = &c_bad); ERR(scene_relocalise, a.objs = narrow; a.c = &c_bad); ERR(scene_relocalise, a.n_obs = 0; a.r = &r_keep17);
+    OBJS_ERRS(scene_window_loss); OBS_ERRS(scene_window_loss, wobs, n_wobs);
+    ERR(scene_window_loss, a.wTwc = nullptr); ERR(scene_window_loss, a.wobs = frames33.data(); a.n_wobs = 33); ERR(scene_window_loss, a.wobs = apart);
+    ERR(scene_window_loss, a.Tow16s = nan_Tow); ERR(scene_window_loss, a.lw = lw_neg); ERR(scene_window_loss, a.objs = with_null; a.wobs = apart);
+    ERR(scene_window_loss, a.objs = with_null; a.lw = lw_neg);
+    OBJS_ERRS(scene_refine_window); OBS_ERRS(scene_refine_window, wobs, n_wobs);
+    ERR(scene_refine_window, a.wTwc = nullptr); ERR(scene_refine_window, a.w = nullptr); ERR(scene_refine_window, a.wobs = frames33.data(); a.n_wobs = 33);
+    ERR(scene_refine_window, a.wobs = apart); ERR(scene_refine_window, a.w = &w_fixed3); ERR(scene_refine_window, a.w = &w_free); ERR(scene_refine_window, a.w = &w_lr);
+    ERR(scene_refine_window, a.Tow16s = nullptr); ERR(scene_refine_window, a.Tow16s = nan_Tow); ERR(scene_refine_window, a.c = &c_bad);
+    ERR(scene_refine_window, a.objs = with_null; a.c = &c_bad); ERR(scene_refine_window, a.objs = with_null; a.w = &w_free); ERR(scene_refine_window, a.objs = narrow; a.c = &c_bad);
+#define OBJECT_ERRS(route) do { ERR(route, a.obj = nullptr); ERR(route, a.side = 2); ERR(route, a.obj = o_16); ERR(route, a.obj = o_xw); ERR(route, a.obj = o_un; a.side = 1); \
+        ERR(route, a.obj = nullptr; a.n_obs = 0); ERR(route, a.obj = o_16; a.side = 2); ERR(route, a.obj = o_16; a.obs = &box_noframe; a.n_obs = 1); } while (0)
+    OBJECT_ERRS(object_pose_loss); OBS_ERRS(object_pose_loss, obs, n_obs); ERR(object_pose_loss, a.Twc = nullptr);
+    OBJECT_ERRS(object_pose_loss_levels); OBS_ERRS(object_pose_loss_levels, obs, n_obs); ERR(object_pose_loss_levels, a.Twc = nullptr);
+    ERR(object_pose_loss_levels, a.lwl = nullptr); ERR(object_pose_loss_levels, a.lwl = lw_neg); ERR(object_pose_loss_levels, a.lwl = nullptr; a.n_obs = 0);
+    OBJECT_ERRS(object_refine_pose); OBS_ERRS(object_refine_pose, obs, n_obs); ERR(object_refine_pose, a.pose_io = nullptr);
+    OBJECT_ERRS(object_refine_pose_c2f); OBS_ERRS(object_refine_pose_c2f, obs, n_obs); ERR(object_refine_pose_c2f, a.pose_io = nullptr);
+    ERR(object_refine_pose_c2f, a.cc = nullptr); ERR(object_refine_pose_c2f, a.cc = &c_bad); ERR(object_refine_pose_c2f, a.cc = &c_bad; a.obj = o_16);
+    ERR(object_refine_pose_c2f, a.cc = &c_bad; a.obs = &box_noframe; a.n_obs = 1);
+    // the online routes: a NULL manager, a manager none of whose objects has published, then the arguments of each
+#define ONLINE_ERRS(route) do { ERR(route, a.om = nullptr); ERR(route, a.om = om_none); } while (0)
+    ONLINE_ERRS(online_render_scene);
+    ERR(online_render_scene, a.Twc = nullptr); ERR(online_render_scene, a.rgb = nullptr); ERR(online_render_scene, a.depth = nullptr); ERR(online_render_scene, a.rect.w = 0);
+    ERR(online_render_scene, a.om = om_none; a.rect.h = 0);
+    ONLINE_ERRS(online_probe_scene);
+    ERR(online_probe_scene, a.poses = nullptr); ERR(online_probe_scene, a.q = nullptr); ERR(online_probe_scene, a.rgb = nullptr); ERR(online_probe_scene, a.depth = nullptr);
+    ERR(online_probe_scene, a.n_poses = 0); ERR(online_probe_scene, a.poses = many_poses.data(); a.n_poses = 4097); ERR(online_probe_scene, a.n_q = 0);
+    ERR(online_probe_scene, a.poses = nan_pose; a.n_poses = 1); ERR(online_probe_scene, a.q = q_nan); ERR(online_probe_scene, a.om = om_none; a.n_q = 0);
+    ONLINE_ERRS(online_cast_rays);
+    ERR(online_cast_rays, a.rays = nullptr); ERR(online_cast_rays, a.rgb = nullptr); ERR(online_cast_rays, a.depth = nullptr); ERR(online_cast_rays, a.n_rays = 0);
+    ERR(online_cast_rays, a.hit_opacity = 0.f); ERR(online_cast_rays, a.hit_opacity = 1.f); ERR(online_cast_rays, a.rays = r_nan); ERR(online_cast_rays, a.rays = r_long);
+    ERR(online_cast_rays, a.rays = r_tmax); ERR(online_cast_rays, a.om = om_none; a.n_rays = 0);
+    ONLINE_ERRS(online_refine_camera); OBS_ERRS(online_refine_camera, obs, n_obs);
+    ERR(online_refine_camera, a.pose_io = nullptr); ERR(online_refine_camera, a.c = &c_bad); ERR(online_refine_camera, a.obs = two_frames);
+    ERR(online_refine_camera, a.om = om_none; a.c = &c_bad); ERR(online_refine_camera, a.om = om_none; a.n_obs = 0); ERR(online_refine_camera, a.om = om_none; a.p = &p_many);
+    ONLINE_ERRS(online_refine_window); OBS_ERRS(online_refine_window, wobs, n_wobs);
+    ERR(online_refine_window, a.wTwc = nullptr); ERR(online_refine_window, a.w = nullptr); ERR(online_refine_window, a.wobs = frames33.data(); a.n_wobs = 33);
+    ERR(online_refine_window, a.wobs = apart); ERR(online_refine_window, a.w = &w_fixed3); ERR(online_refine_window, a.w = &w_free); ERR(online_refine_window, a.w = &w_lr);
+    ERR(online_refine_window, a.Tow16s = nullptr); ERR(online_refine_window, a.Tow16s = nan_Tow); ERR(online_refine_window, a.c = &c_bad);
+    ERR(online_refine_window, a.n_online = 3); ERR(online_refine_window, a.n_online = 3; a.om = om_none); ERR(online_refine_window, a.n_online = 3; a.w = &w_free);
+    ERR(online_refine_window, a.om = om_none; a.c = &c_bad);
+    ERR(online_refine_window, a.c = &c_bad; a.w = &w_free);
+    ONLINE_ERRS(online_relocalise); OBS_ERRS(online_relocalise, obs, n_obs);
+    ERR(online_relocalise, a.poses = nullptr); ERR(online_relocalise, a.r = nullptr); ERR(online_relocalise, a.pose_out = nullptr); ERR(online_relocalise, a.n_poses = 0);
+    ERR(online_relocalise, a.poses = many_poses.data(); a.n_poses = 4097); ERR(online_relocalise, a.r = &r_rays0); ERR(online_relocalise, a.r = &r_rays_many);
+    ERR(online_relocalise, a.r = &r_keep0); ERR(online_relocalise, a.r = &r_keep17); ERR(online_relocalise, a.c = &c_bad);
+    ERR(online_relocalise, a.om = om_none; a.r = &r_keep0); ERR(online_relocalise, a.om = om_none; a.c = &c_bad); ERR(online_relocalise, a.n_obs = 0; a.r = &r_keep17);
+    ONLINE_ERRS(online_refine_pose); OBS_ERRS(online_refine_pose, obs, n_obs);
+    ERR(online_refine_pose, a.pose_io = nullptr); ERR(online_refine_pose, a.idx = 2); ERR(online_refine_pose, a.idx = 2; a.n_obs = 0);
+    ONLINE_ERRS(online_refine_pose_c2f); OBS_ERRS(online_refine_pose_c2f, obs, n_obs);
+    ERR(online_refine_pose_c2f, a.pose_io = nullptr); ERR(online_refine_pose_c2f, a.idx = 2); ERR(online_refine_pose_c2f, a.cc = nullptr);
+    ERR(online_refine_pose_c2f, a.cc = &c_bad); ERR(online_refine_pose_c2f, a.idx = 2; a.cc = &c_bad); ERR(online_refine_pose_c2f, a.om = om_none; a.cc = &c_bad);
+    hip_stub_trace(0);
+    // (the trace ends here: two object threads sign off on stdout in the order they happen to end)
+    std::fflush(stdout); if (!std::freopen("/dev/null", "w", stdout)) std::exit(3);
+    OK(mon_online_wait_threads_end(om)); OK(mon_online_destroy(om)); OK(mon_online_wait_threads_end(om_none)); OK(mon_online_destroy(om_none));
+    for (mon_object* x : { o0, o1, o_K, o_2, o_16, o_xw, o_un }) OK(mon_object_destroy(x));
+    for (mon_dataset* d : { ds, ds_K, ds_2 }) OK(mon_dataset_destroy(d));
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) { std::fprintf(stderr, "usage: trace_driver <scratch dir> <config json>\n"); return 2; }
     g_dir = argv[1];
@@ -128,6 +373,7 @@ int main(int argc, char** argv) {
     object_case(ds, "rng_flags 1 (XORWOW)", c, {}, true);
     OK(mon_dataset_destroy(ds));
     online_case(argv[2], rgb.data(), inst.data());
+    inference_part(argv[2], base, rgb.data(), inst.data());
     hip_stub_trace(0);
     return 0;
 }
