@@ -214,7 +214,7 @@ int mon_scene_probe(mon_object* const* objs, size_t n_objs, int side, const floa
                     float* rgb, float* depth, float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance);
 /* Ray cast: the object map asked along world rays by a consumer that is not a camera of the dataset -- a planner's line-of-sight check between two points,
  * a range sensor, a grasp query, the surface point along a map point's viewing ray (the reference has no such call; opt-in, new).  Forward only: surface
- * normals, density gradients and queries at points rather than along rays are a follow-up.
+ * normals and density gradients are a follow-up; queries at points rather than along rays: mon_scene_query_points below.
  * Ray i is x(t) = o + t d for 0 <= t <= t_max in the world frame; d must be unit (| |d|^2 - 1 | <= 1e-3, used as given: the device does not renormalise);
  * t_max > 0, +inf allowed.  For object j the ray is taken into j's frame (R_ow d, R_ow o + t_ow) and intersected with j's box at [t0, t1]; j contributes iff
  * the box is hit and lo < hi, lo = max(t0, 0), hi = min(t1, t_max).  Its 2S = 64 samples are the scene render's for a ray row {t0 = lo, t1 = hi}:
@@ -254,6 +254,42 @@ int mon_scene_cast(mon_object* const* objs, size_t n_objs, int side, const mon_s
  * operation.  MON_ERR_ARG: Twc16s, q or rays_out NULL; n_poses or n_q 0; a pose index >= n_poses; a non-finite intrinsic, pose, u or v; fx or fy 0. */
 int mon_camera_rays(float fx, float fy, float cx, float cy, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q,
                     mon_scene_ray* rays_out, float* dn_out);
+/* Point queries: the object map asked about a place instead of a ray -- is this voxel free, which object owns this point, how dense is the field over
+ * this lattice (a planner's or a grasper's question; a ray costs 64 samples per answer, a point one; the reference has no such call; opt-in, new).  Forward
+ * only: normals and gradients are not computed; a caller differences six point queries.
+ * A world point x goes into object j's frame as mon_scene_cast takes a ray origin there, q = R_ow x + t_ow, and into j's unit cube by the operation the
+ * render applies to a sample point, u_a = (q_a - aabb_min_a) / (aabb_max_a - aabb_min_a); it is inside j iff 0 <= u_a <= 1 on all three axes.  For an
+ * inside point the network is evaluated at u exactly as the render evaluates a sample, with the render's weights of that side; sigma_j = exp(o3),
+ * c_j = logistic(o0..2), the render's two lines (sigma_j may be +inf for a saturated fp16 output; it is passed on as is).  Outside, sigma_j = 0.
+ * Outputs per point, host pointers (all but sigma may be NULL):
+ *   sigma       = the sum of sigma_j over the objects the point is inside, added in fp32 in the order of objs
+ *   owner       = the index in objs of the object with the largest sigma_j among those (ties: the lower index), -1 when the point is inside none
+ *   rgb         = the owner's colour, 0 0 0 without an owner
+ *   owner_sigma = the owner's sigma_j, 0 without an owner
+ *   n_inside    = the number of boxes the point lies in
+ * sigma is a density per unit of WORLD length (Tow is rigid: lengths in an object's frame are world lengths): the opacity of a step of length l through
+ * the point is 1 - exp(-sigma l), which is what a caller thresholds.
+ * A point's outputs depend on that point and the objects alone: not on the other points, its place in the list, how the list is cut into passes (16 384
+ * points each) or whether it came by list or by lattice; no atomics: equal arguments, equal bits.  One enqueue, one synchronisation.  Read-only; side as
+ * in mon_scene_render (0: the caller serialises against training; 1: the snapshots, callable while the objects train).  The objects need only share a
+ * device.  The sample count, render skipping and the XORWOW render mode play no part: nothing is sampled, skipped or jittered.
+ * mon_scene_query_lattice: the same at the points p(i, j, k) = (fmaf(i, step[0], origin[0]), fmaf(j, step[1], origin[1]), fmaf(k, step[2], origin[2])),
+ * 0 <= i < nx (fastest), j < ny, k < nz, formed on the device: nothing is uploaded but the six floats.  Output index (k * ny + j) * nx + i.
+ * mon_lattice_points (host only, no device): those points exactly as the device forms them, xyz_out[nx * ny * nz][3]; mon_scene_query_points of them
+ * returns the lattice call's bits.
+ * mon_object_query_points: one object, points given in its unit cube (the coordinates its encoder takes): raw4[n][4] = the network's four raw fp16
+ * outputs (o0..2 colour, o3 log density) widened to fp32, by the same kernel with the transform switched off.
+ * Returns:
+ *   MON_ERR_ARG    objs or an element, the points (origin3, step3) or sigma (raw4) NULL; n_objs 0 or above 256; n or nx * ny * nz outside 1..2^22; nx, ny
+ *                  or nz below 1; a non-finite point, origin or step, or a lattice that leaves the finite floats; side not 0 / 1; objects on different
+ *                  logical devices; mon_object_query_points: a point outside [0, 1]^3 -- all before any device work, the outputs untouched
+ *   MON_ERR_STATE  an object outside the fused shapes (the layer-kernel backend); side 1 and an object with nothing published yet */
+int mon_object_query_points(mon_object* obj, int side, const float* unit_xyz, size_t n, float* raw4);
+int mon_scene_query_points(mon_object* const* objs, size_t n_objs, int side, const float* world_xyz, size_t n,
+                           float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside);
+int mon_scene_query_lattice(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz,
+                            float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside);
+int mon_lattice_points(const float* origin3, const float* step3, int nx, int ny, int nz, float* xyz_out);
 /* Object pose refinement through the trained field (iNeRF-style): align the object with observed frames by following the gradient of a photometric,
  * silhouette and depth error with respect to the 6-DoF pose Tow.
  * Objective.  obs names frames of the object's dataset (FrameId) and pixel boxes inside them; the target of a pixel is that frame's rgb c*, its instance map
@@ -627,6 +663,13 @@ int mon_online_probe_scene(mon_online* mgr, const float* Twc16s, size_t n_poses,
  * span more than one device. */
 int mon_online_cast_rays(mon_online* mgr, const mon_scene_ray* rays, size_t n_rays, float hit_opacity,
                          float* rgb, float* dist, float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t, int32_t* hit_instance);
+/* mon_scene_query_points / mon_scene_query_lattice (side 1) of every object of the manager that has published weights, chosen as mon_online_render_scene
+ * chooses them; owner holds the manager's object indices.  A planner's call, safe while the objects train.  MON_ERR_STATE when no object has published
+ * yet or the objects span more than one device. */
+int mon_online_query_points(mon_online* mgr, const float* world_xyz, size_t n,
+                            float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside);
+int mon_online_query_lattice(mon_online* mgr, const float* origin3, const float* step3, int nx, int ny, int nz,
+                             float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside);
 /* mon_object_refine_pose(side 1) of object idx: its published snapshot, on the inference stream -- safe while the manager trains it.  MON_ERR_STATE while
  * nothing of it has been published. */
 int mon_online_refine_pose(mon_online* mgr, size_t idx, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, float* Tow16_inout,

@@ -12,6 +12,7 @@ from .binding import (MonConfig, MonBBox, MonError, Dataset, ObjectNeRF, default
                       scene_composite_grad, RelocParams, RelocResult, reloc_default, scene_pose_loss_batch, pose_hypotheses, scene_relocalise,
                       SceneQuery, SCENE_QUERY_DTYPE, scene_queries, rect_queries, probe_scene, scene_probe_rays, scene_probe_composite,
                       SceneRay, SCENE_RAY_DTYPE, scene_rays, camera_rays, cast_scene, scene_cast_rays, scene_cast_composite,
+                      query_object_points, query_scene_points, query_scene_lattice, lattice_points, scene_point_rows,
                       WindowParams, window_default, window_frames, scene_window_loss, scene_refine_window,
                       CheckpointInfo, checkpoint_info, checkpoint_timing, MON_LOAD_BOXES,
                       rccl_lib, rccl_lib_path, rccl_symbols, gather_plan, Gather)

@@ -204,6 +204,14 @@ _SIGS = {
     "mon_online_cast_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p]),
     "mon_camera_rays": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mon_object_query_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mon_scene_query_points": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_scene_query_lattice": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_lattice_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "mon_online_query_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_online_query_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p]),
     "mon_pose_refine_default": (C.c_int, [C.POINTER(PoseRefineParams)]),
     "mon_object_pose_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32,
             C.POINTER(C.c_float), C.c_void_p]),
@@ -274,6 +282,7 @@ _DIAG_SIGS = {
     "mon_debug_scene_cast_rays": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "mon_debug_scene_cast_composite": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_debug_scene_point_rows": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
     "mon_debug_pose_samples": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32, C.c_void_p,
             C.c_void_p, C.c_void_p]),
     "mon_debug_scene_pose_samples": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32,
@@ -918,6 +927,19 @@ class OnlineManager:
         _check(lib().mon_online_cast_rays(self.h, _p(r), r.shape[0], float(hit_opacity), *[_p(a) for a in out]))
         return out
 
+    def query_points(self, world_xyz):
+        """mon_online_query_points: query_scene_points on side 1 over every object with published weights (safe while they train); owner holds the
+        manager's object indices."""
+        x = np.ascontiguousarray(world_xyz, np.float32).reshape(-1, 3); out = _point_outputs(x.shape[0])
+        _check(lib().mon_online_query_points(self.h, _p(x), x.shape[0], *[_p(a) for a in out]))
+        return out
+
+    def query_lattice(self, origin, step, shape):
+        """mon_online_query_lattice: query_scene_lattice on side 1 over every object with published weights; owner holds the manager's object indices."""
+        o, s, nx, ny, nz = _lattice_args(origin, step, shape); out = _point_outputs(max(nx, 0) * max(ny, 0) * max(nz, 0))
+        _check(lib().mon_online_query_lattice(self.h, _p(o), _p(s), nx, ny, nz, *[_p(a) for a in out]))
+        return out
+
     def save_map(self, path):
         """mon_online_save_map: <path>/map.txt + one checkpoint per object, each under its own model lock (safe while they train; not one global cut)."""
         _check(lib().mon_online_save_map(self.h, os.fsencode(path)))
@@ -1142,6 +1164,51 @@ def scene_cast_composite(t, alpha, rgb, count, entry, hit_opacity=0.5, device=0)
            np.empty(R, np.float32), np.empty(R, np.int32))
     _check(diag_lib().mon_debug_scene_cast_composite(int(device), R, L, _p(t), _p(a), _p(c), _p(n), _p(e), float(hit_opacity), *[_p(o) for o in out]))
     return out
+
+
+def _point_outputs(n):
+    return (np.empty(n, np.float32), np.empty((n, 3), np.float32), np.empty(n, np.int32), np.empty(n, np.float32), np.empty(n, np.uint32))
+
+
+def _lattice_args(origin, step, shape):
+    o = np.ascontiguousarray(origin, np.float32).reshape(3); s = np.ascontiguousarray(step, np.float32).reshape(3)
+    nx, ny, nz = (int(v) for v in shape)
+    return o, s, nx, ny, nz
+
+
+def query_object_points(obj, unit_xyz, side=0):
+    """mon_object_query_points: the object's raw network outputs (n, 4) at points of its unit cube (the coordinates its encoder takes)."""
+    x = np.ascontiguousarray(unit_xyz, np.float32).reshape(-1, 3); raw = np.empty((x.shape[0], 4), np.float32)
+    _check(lib().mon_object_query_points(obj.h, int(side), _p(x), x.shape[0], _p(raw)))
+    return raw
+
+
+def query_scene_points(objects, world_xyz, side=0):
+    """mon_scene_query_points: the object map at world points (n, 3).  Returns (sigma, rgb (n, 3), owner: index into objects or -1, owner_sigma, n_inside)."""
+    x = np.ascontiguousarray(world_xyz, np.float32).reshape(-1, 3); out = _point_outputs(x.shape[0])
+    _check(lib().mon_scene_query_points(_handles(objects), len(objects), int(side), _p(x), x.shape[0], *[_p(a) for a in out]))
+    return out
+
+
+def query_scene_lattice(objects, origin, step, shape, side=0):
+    """mon_scene_query_lattice: query_scene_points at the lattice origin + (i, j, k) * step, shape = (nx, ny, nz), i fastest, formed on the device."""
+    o, s, nx, ny, nz = _lattice_args(origin, step, shape); out = _point_outputs(max(nx, 0) * max(ny, 0) * max(nz, 0))
+    _check(lib().mon_scene_query_lattice(_handles(objects), len(objects), int(side), _p(o), _p(s), nx, ny, nz, *[_p(a) for a in out]))
+    return out
+
+
+def lattice_points(origin, step, shape):
+    """mon_lattice_points (host only): the lattice's points (nx * ny * nz, 3) exactly as the device forms them."""
+    o, s, nx, ny, nz = _lattice_args(origin, step, shape); xyz = np.empty((max(nx, 0) * max(ny, 0) * max(nz, 0), 3), np.float32)
+    _check(lib().mon_lattice_points(_p(o), _p(s), nx, ny, nz, _p(xyz)))
+    return xyz
+
+
+def scene_point_rows(objects, world_xyz, k, side=0):
+    """mon_debug_scene_point_rows: object k's row of every point of that query, (n, 12) = u[3], inside, raw4, sigma_k, r, g, b."""
+    x = np.ascontiguousarray(world_xyz, np.float32).reshape(-1, 3); rows = np.empty((x.shape[0], 12), np.float32)
+    _check(diag_lib().mon_debug_scene_point_rows(_handles(objects), len(objects), int(side), _p(x), x.shape[0], int(k), _p(rows)))
+    return rows
 
 
 def scene_samples(objects, rect, Twc16, k, side=0):

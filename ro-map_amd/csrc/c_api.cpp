@@ -135,6 +135,30 @@ int mon_camera_rays(float fx, float fy, float cx, float cy, const float* Twc16s,
         float* dn_out) {
     return scene_camera_rays(fx, fy, cx, cy, Twc16s, n_poses, q, n_q, rays_out, dn_out);
 }
+int mon_object_query_points(mon_object* o, int side, const float* unit_xyz, size_t n, float* raw4) {
+    { const int rc = object_points_check(side, unit_xyz, n, raw4); if (rc) return rc; }
+    REQUIRE(o, "object");
+    return object_points(*o->m, side, unit_xyz, n, raw4);
+}
+int mon_scene_query_points(mon_object* const* objs, size_t n_objs, int side, const float* world_xyz, size_t n, float* sigma, float* rgb, int32_t* owner,
+        float* owner_sigma, uint32_t* n_inside) {
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_points_check(side, world_xyz, n, sigma)) || (rc = scene_models("scene_points", objs, n_objs, ms)) ||
+        (rc = scene_objects_check("scene_points", ms.data(), n_objs, false))) return rc;
+    ScenePoints q{}; q.xyz = world_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    return scene_points(ms.data(), n_objs, side, q, sigma, rgb, owner, owner_sigma, n_inside, nullptr, 0, nullptr);
+}
+int mon_scene_query_lattice(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz, float* sigma,
+        float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside) {
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_lattice_check(side, origin3, step3, nx, ny, nz, sigma)) || (rc = scene_models("scene_lattice", objs, n_objs, ms)) ||
+        (rc = scene_objects_check("scene_lattice", ms.data(), n_objs, false))) return rc;
+    const ScenePoints q = scene_lattice(origin3, step3, nx, ny, nz);
+    return scene_points(ms.data(), n_objs, side, q, sigma, rgb, owner, owner_sigma, n_inside, nullptr, 0, nullptr);
+}
+int mon_lattice_points(const float* origin3, const float* step3, int nx, int ny, int nz, float* xyz_out) {
+    return scene_lattice_points(origin3, step3, nx, ny, nz, xyz_out);
+}
 int mon_pose_refine_default(mon_pose_refine_params* p) {
     REQUIRE(p, "params");
     p->iters = 100; p->rays_per_iter = 4096; p->lr_trans = 2e-3f; p->lr_rot = 4e-3f;

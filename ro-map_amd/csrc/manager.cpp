@@ -738,6 +738,23 @@ int mon_online_cast_rays(mon_online* h, const mon_scene_ray* rays, size_t n_rays
         (rc = scene_objects_check("scene_cast", ms.data(), ms.size(), false))) return rc;
     return scene_cast(ms.data(), ms.size(), 1, rays, n_rays, hit_opacity, rgb, dist, opacity, instance, hit_t, hit_sample_t, hit_instance, ids.data(), nullptr);
 }
+// the map asked at a planner's places: mon_scene_query_points / mon_scene_query_lattice on side 1 over the objects mon_online_render_scene composites
+int mon_online_query_points(mon_online* h, const float* world_xyz, size_t n, float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside) {
+    REQ(h);
+    std::vector<Model*> ms; std::vector<int32_t> ids; int rc;
+    if ((rc = scene_points_check(1, world_xyz, n, sigma)) || (rc = online_published(h, "query_points", 0, false, ms, &ids)) ||
+        (rc = scene_objects_check("scene_points", ms.data(), ms.size(), false))) return rc;
+    ScenePoints q{}; q.xyz = world_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    return scene_points(ms.data(), ms.size(), 1, q, sigma, rgb, owner, owner_sigma, n_inside, ids.data(), 0, nullptr);
+}
+int mon_online_query_lattice(mon_online* h, const float* origin3, const float* step3, int nx, int ny, int nz, float* sigma, float* rgb, int32_t* owner,
+        float* owner_sigma, uint32_t* n_inside) {
+    REQ(h);
+    std::vector<Model*> ms; std::vector<int32_t> ids; int rc;
+    if ((rc = scene_lattice_check(1, origin3, step3, nx, ny, nz, sigma)) || (rc = online_published(h, "query_lattice", 0, false, ms, &ids)) ||
+        (rc = scene_objects_check("scene_lattice", ms.data(), ms.size(), false))) return rc;
+    return scene_points(ms.data(), ms.size(), 1, scene_lattice(origin3, step3, nx, ny, nz), sigma, rgb, owner, owner_sigma, n_inside, ids.data(), 0, nullptr);
+}
 // pose refinement of one object against new observations, from its published snapshot (a frontend's call, like mon_online_render: safe while it trains)
 int mon_online_refine_pose(mon_online* h, size_t idx, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, float* Tow16_inout,
         float* loss_trace) {

@@ -352,6 +352,15 @@ void launch_scene_cast_rays(hipStream_t s, const BatchPtrs& b, const ObjectConst
 void launch_scene_cast_composite(hipStream_t s, uint32_t n_rays, uint32_t n_lists, uint32_t cap, float thr, const float* t, const float* attr,
         const uint32_t* cnt, const float* entry, float* rgb, float* dist, float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t,
         int32_t* hit_instance);
+// Point queries (mon_scene_query_points / _lattice, mon_object_query_points; kernels_scene_points.hip).  k_scene_points: one object's rows [n][12] = u[3],
+// inside, raw4, sigma, r, g, b of the n points of a pass -- item i is point i of `pts` (device, [n][3]) or, with pts == nullptr, lattice point first + i
+// (ix fastest, fmaf(i_a, step_a, origin_a)); world = false: the points are unit-cube points of the object, taken as given.  build_image: build the
+// fragment image first (a call's first pass).  k_scene_points_fold: the K rows of each point ([K][cap][12]) -> the five outputs.
+struct ScenePointsArgs { const float* pts; float origin[3], step[3]; uint32_t nx, ny, first, n; float* rows; };
+void launch_scene_points(hipStream_t s, const LevelFast& lt, const NetDims& nd, const uint16_t* params, const ObjectConst& oc, uint16_t* frag_image,
+        int build_image, bool world, const ScenePointsArgs& p);
+void launch_scene_points_fold(hipStream_t s, uint32_t n, uint32_t n_objs, uint32_t cap, const float* rows, float* sigma, float* rgb, int32_t* owner,
+        float* owner_sigma, uint32_t* n_inside);
 // Pose refinement (mon_object_pose_loss / mon_object_refine_pose, kernels_pose.hip).  k_pose_rays: one record of 4 float4 per drawn ray from the pose in
 // device memory (pose[16], world -> object); k_pose_grad<shape>: loss and position gradient, one partial row of 8 floats {g, x x g, loss, 0} per workgroup
 // (pose_grad_grid of them); k_pose_update: the rows summed in a fixed order, x inv_n -> out[8 * it] = {loss, grad6, 0}, optionally the Adam step on pose.
@@ -705,6 +714,23 @@ int scene_cast(Model* const* ms, size_t n, int side, const mon_scene_ray* rays, 
                int32_t* instance, float* hit_t, float* hit_sample_t, int32_t* hit_instance, const int32_t* ids, const SceneRaysDump* dump);
 int scene_camera_rays(float fx, float fy, float cx, float cy, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q,
                       mon_scene_ray* rays_out, float* dn_out);
+// Point queries (mon_scene_query_points / mon_scene_query_lattice): the objects' check is the cast's (no camera); ids as scene_render's, applied to owner.
+// ScenePoints: xyz = the world points [n][3], or nullptr: the lattice origin / step / nx x ny x nz (n = its points).  rows (mon_debug_scene_point_rows, may be
+// nullptr) = object rows_k's rows of every point, host array [n][12].  scene_lattice_points (mon_lattice_points): the lattice's floats on the host.
+// object_points (mon_object_query_points): the same kernel on unit-cube points of one object, its raw outputs [n][4].
+struct ScenePoints { const float* xyz; size_t n; float origin[3], step[3]; int nx, ny, nz; };
+inline ScenePoints scene_lattice(const float* origin3, const float* step3, int nx, int ny, int nz) {      // (after scene_lattice_check)
+    ScenePoints q{}; q.n = (size_t)nx * ny * nz; q.nx = nx; q.ny = ny; q.nz = nz;
+    for (int a = 0; a < 3; ++a) { q.origin[a] = origin3[a]; q.step[a] = step3[a]; }
+    return q;
+}
+int scene_points_check(int side, const float* xyz, size_t n, const float* sigma);
+int scene_lattice_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, const float* sigma);
+int scene_points(Model* const* ms, size_t n, int side, const ScenePoints& q, float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside,
+                 const int32_t* ids, size_t rows_k, float* rows);
+int scene_lattice_points(const float* origin3, const float* step3, int nx, int ny, int nz, float* xyz_out);
+int object_points_check(int side, const float* unit_xyz, size_t n, const float* raw4);
+int object_points(Model& m, int side, const float* unit_xyz, size_t n, float* raw4);
 bool model_has_snapshot(Model& m);      // the object has an inference side and has published weights
 // Pose refinement: iters < 0 = one evaluation (mon_object_pose_loss: loss, grad6, jitter / draws of `iteration`), else iters Adam steps from Tow16
 // (mon_object_refine_pose: the final pose into pose_out, loss_trace[iters + 1] may be nullptr).  dump (mon_debug_pose_samples, may be nullptr): per drawn ray

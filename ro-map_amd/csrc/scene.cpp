@@ -105,16 +105,18 @@ struct SceneWs {
     DevBuf<float> out; PinnedBuf<float> h_out;                                    // rgb 3n | depth n | opacity n | instance n (int32)
     DevBuf<mon_scene_query> q; DevBuf<float> poses; DevBuf<uint32_t> keys;        // scene_probe: the queries, the poses [n_poses][16], a pass's keys [cap]
     DevBuf<mon_scene_ray> rays; DevBuf<float> entry;                              // scene_cast: the rays, a pass's box entries [lists][cap]
+    DevBuf<float> pts, rows;                                                      // scene_points: the points [n][3], a pass's rows [objects][cap][12]
     std::vector<hipEvent_t> ev;
 };
-// what each object renders with on a side; the render grids are the objects' own per-side caches, built if stale (their skip counters stay as they are)
+// what each object renders with on a side; the render grids are the objects' own per-side caches, built if stale (their skip counters stay as they are).
+// grids = false (the point queries, which consult no skipping): no grid is looked at or built, bits = nullptr
 struct SceneSrc { BatchPtrs* b; uint16_t* frag; const uint32_t* bits; };
-static std::vector<SceneSrc> scene_sources(Model* const* ms, size_t n, int side, const SceneSide& sd) {
+static std::vector<SceneSrc> scene_sources(Model* const* ms, size_t n, int side, const SceneSide& sd, bool grids = true) {
     std::vector<SceneSrc> src(n);
     for (size_t j = 0; j < n; ++j) {
         Model& m = *ms[j]; RenderSkipSide& rs = side == 1 ? m.infer->rskip : m.rskip;
         src[j].b = side == 1 ? &m.infer->rb : &m.B; src[j].frag = side == 1 ? m.infer->frag : m.d_frag_render;
-        src[j].bits = m.rskip_on.load() != 0 ? rskip_grid(m, rs, sd.s, m.rskip_alpha.load(), sd.prm[j], sd.epoch[j], src[j].frag) : nullptr;
+        src[j].bits = grids && m.rskip_on.load() != 0 ? rskip_grid(m, rs, sd.s, m.rskip_alpha.load(), sd.prm[j], sd.epoch[j], src[j].frag) : nullptr;
     }
     return src;
 }
@@ -362,6 +364,136 @@ int scene_camera_rays(float fx, float fy, float cx, float cy, const float* Twc16
         r.t_max = INFINITY; r.key = q[i].key;
         if (dn_out) dn_out[i] = dn;
     }
+    return MON_OK;
+}
+
+// ---- point queries (mon_scene_query_points, mon_scene_query_lattice, mon_object_query_points): the map asked at places.  A small sibling of
+// scene_list_run: no rays, no sample lists, no composite.  Per pass of at most kRenderChunkRays points every object's k_scene_points writes its rows
+// [objects][cap][12] (u[3], inside, raw4, sigma, r, g, b), then k_scene_points_fold writes the pass's slice of the seven output rows (sigma | rgb 3n | owner
+// | owner_sigma | n_inside).  Everything is enqueued at once; the outputs go home through the pinned staging with one synchronisation.  Render grids are
+// not consulted (nothing is skipped), and neither the sample count nor the XORWOW render mode matters: nothing is sampled or jittered.
+// The points of one pass: kRenderChunkRays, as the other scene routes.  A variant build (tools/variant_build.sh <tag> -DMON_POINTS_PASS=n) takes another
+// size for measurements (tools/scene_points_timing.py: a pass of 16 384 points is a grid of 64 workgroups); outputs do not depend on it.
+#ifndef MON_POINTS_PASS
+#define MON_POINTS_PASS kRenderChunkRays
+#endif
+constexpr uint32_t kScenePointsPass = MON_POINTS_PASS;
+static int points_outputs_check(const char* what, int side, const float* sigma) {
+    REQUIRE_ARG(what, sigma, "sigma");
+    return side_check(what, side);
+}
+int scene_points_check(int side, const float* xyz, size_t n, const float* sigma) {
+    REQUIRE_ARG("scene_points", xyz, "points");
+    { const int rc = points_outputs_check("scene_points", side, sigma); if (rc) return rc; }
+    if (n == 0 || n > kSceneProbeMaxQueries) { set_error("scene_points: %zu points (1 to %u)", n, kSceneProbeMaxQueries); return MON_ERR_ARG; }
+    for (size_t i = 0; i < 3 * n; ++i) if (!std::isfinite(xyz[i])) { set_error("scene_points: point %zu is not finite", i / 3); return MON_ERR_ARG; }
+    return MON_OK;
+}
+// the lattice's shape alone (mon_lattice_points, which has no side and no outputs) ...
+static int lattice_shape_check(const char* what, const float* origin3, const float* step3, int nx, int ny, int nz) {
+    REQUIRE_ARG(what, origin3, "origin"); REQUIRE_ARG(what, step3, "step");
+    if (nx < 1 || ny < 1 || nz < 1) { set_error("%s: lattice %d x %d x %d (each at least 1)", what, nx, ny, nz); return MON_ERR_ARG; }
+    // (each factor bounded before it is multiplied: three ints of up to 2^31 - 1 wrap a 64-bit product)
+    const uint64_t mx = kSceneProbeMaxQueries;
+    if ((uint64_t)nx > mx || (uint64_t)ny > mx / (uint64_t)nx || (uint64_t)nz > mx / ((uint64_t)nx * (uint64_t)ny)) { set_error("%s: lattice %d x %d x %d has more than %u points", what, nx, ny, nz,
+        kSceneProbeMaxQueries); return MON_ERR_ARG; }
+    const int dims[3] = { nx, ny, nz };
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(origin3[a]) || !std::isfinite(step3[a])) { set_error("%s: origin or step is not finite", what); return MON_ERR_ARG; }
+        // (fmaf is monotone in the index: the far end is finite iff every point of the axis is)
+        if (!std::isfinite(std::fmaf((float)(dims[a] - 1), step3[a], origin3[a]))) { set_error("%s: the lattice leaves the finite floats on axis %d", what, a);
+            return MON_ERR_ARG; }
+    }
+    return MON_OK;
+}
+// ... and the query on it
+int scene_lattice_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, const float* sigma) {
+    { const int rc = lattice_shape_check("scene_lattice", origin3, step3, nx, ny, nz); if (rc) return rc; }
+    return points_outputs_check("scene_lattice", side, sigma);
+}
+// mon_lattice_points: the floats k_scene_points forms from a lattice index, on the host (one fmaf per coordinate, ix fastest)
+int scene_lattice_points(const float* origin3, const float* step3, int nx, int ny, int nz, float* xyz_out) {
+    { const int rc = lattice_shape_check("lattice_points", origin3, step3, nx, ny, nz); if (rc) return rc; }
+    REQUIRE_ARG("lattice_points", xyz_out, "xyz_out");
+    float* o = xyz_out;
+    for (int iz = 0; iz < nz; ++iz) for (int iy = 0; iy < ny; ++iy) for (int ix = 0; ix < nx; ++ix, o += 3) {
+        o[0] = std::fmaf((float)ix, step3[0], origin3[0]); o[1] = std::fmaf((float)iy, step3[1], origin3[1]); o[2] = std::fmaf((float)iz, step3[2], origin3[2]); }
+    return MON_OK;
+}
+// the MON_ERR_STATE cases of a point query: the layer-kernel shapes and, on side 1, a missing snapshot
+static int scene_points_state_check(const char* what, Model* const* ms, size_t n, int side) {
+    for (size_t j = 0; j < n; ++j) {
+        Model& m = *ms[j];
+        if (!rskip_supported(m)) { set_error("%s: object %zu does not run on the fused kernels", what, j); return MON_ERR_STATE; }
+        if (side == 1 && !model_has_snapshot(m)) { set_error("%s: object %zu has no published snapshot", what, j); return MON_ERR_STATE; }
+    }
+    return MON_OK;
+}
+// q.xyz: the list ([q.n][3]; `world` false: unit-cube points of the one object), or nullptr: the lattice q.origin, q.step, q.nx x q.ny x q.nz (q.n its points).
+// rows (mon_debug_scene_point_rows, mon_object_query_points; may be nullptr) = object rows_k's rows of every point, host array [q.n][12].
+static int scene_points_run(const char* what, Model* const* ms, size_t n, int side, const ScenePoints& q, bool world, float* sigma, float* rgb, int32_t* owner,
+                            float* owner_sigma, uint32_t* n_inside, const int32_t* ids, size_t rows_k, float* rows) {
+    { const int rc = scene_points_state_check(what, ms, n, side); if (rc) return rc; }
+    const int device = ms[0]->device;
+    HIPCHECK(use_device(device));
+    const size_t n_q = q.n; const uint32_t nq = (uint32_t)n_q, cap = std::min(nq, kScenePointsPass), L = (uint32_t)n;
+    SceneWs& ws = side_ws<SceneWs>(device, side);
+    SceneSide sd; { const int rc = sd.enter(ms, n, side, ws.mu, ws.ev); if (rc) return rc; }
+    const hipStream_t s = sd.s;
+    const std::vector<SceneSrc> src = scene_sources(ms, n, side, sd, false);
+    // the output area: [the dumped rows 12 n_q |] sigma | rgb 3 n_q | owner | owner_sigma | n_inside (the rows first: every piece copied stays 16-byte aligned)
+    const size_t rows_floats = rows ? 12 * n_q : 0, out_floats = rows_floats + 7 * n_q;
+    {   int rc;
+        if ((rc = ws.rows.grow((size_t)L * cap * 12)) || (rc = ws.out.grow(out_floats)) || (rc = ws.h_out.grow(out_floats)) ||
+            (q.xyz && (rc = ws.pts.grow(3 * n_q)))) return rc; }
+    if (q.xyz) HIPCHECK(hipMemcpyAsync(ws.pts.p, q.xyz, 12 * n_q, hipMemcpyHostToDevice, s));
+    float* o = ws.out.p + rows_floats;
+    for (uint32_t p0 = 0; p0 < nq; p0 += cap) {
+        const uint32_t nc = std::min(cap, nq - p0);
+        for (size_t j = 0; j < n; ++j) {
+            Model& m = *ms[j];
+            ScenePointsArgs a{}; a.pts = q.xyz ? ws.pts.p + 3 * (size_t)p0 : nullptr; a.nx = (uint32_t)q.nx; a.ny = (uint32_t)q.ny; a.first = p0; a.n = nc;
+            for (int k = 0; k < 3; ++k) { a.origin[k] = q.origin[k]; a.step[k] = q.step[k]; }
+            a.rows = ws.rows.p + j * (size_t)cap * 12;
+            launch_scene_points(s, m.lf, m.nd, sd.prm[j], m.oc, src[j].frag, p0 == 0u, world, a);
+        }
+        launch_scene_points_fold(s, nc, L, cap, ws.rows.p, o + p0, o + n_q + 3 * (size_t)p0, reinterpret_cast<int32_t*>(o + 4 * n_q) + p0, o + 5 * n_q + p0,
+                reinterpret_cast<uint32_t*>(o + 6 * n_q) + p0);
+        if (rows) launch_copy_params(s, reinterpret_cast<const uint16_t*>(ws.rows.p + rows_k * (size_t)cap * 12),
+                reinterpret_cast<uint16_t*>(ws.out.p + 12 * (size_t)p0), 24u * nc);
+    }
+    launch_copy_params(s, reinterpret_cast<const uint16_t*>(ws.out.p), reinterpret_cast<uint16_t*>(ws.h_out.p), (uint32_t)(2 * out_floats));
+    HIPCHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    const float* h = ws.h_out.p + rows_floats;
+    if (rows) std::memcpy(rows, ws.h_out.p, 4 * rows_floats);
+    if (sigma) std::memcpy(sigma, h, 4 * n_q);
+    if (rgb) std::memcpy(rgb, h + n_q, 12 * n_q);
+    scene_instances_home(owner, h + 4 * n_q, n_q, ids);
+    if (owner_sigma) std::memcpy(owner_sigma, h + 5 * n_q, 4 * n_q);
+    if (n_inside) std::memcpy(n_inside, h + 6 * n_q, 4 * n_q);
+    return MON_OK;
+}
+int scene_points(Model* const* ms, size_t n, int side, const ScenePoints& q, float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside,
+                 const int32_t* ids, size_t rows_k, float* rows) {
+    return scene_points_run(q.xyz ? "scene_points" : "scene_lattice", ms, n, side, q, true, sigma, rgb, owner, owner_sigma, n_inside, ids, rows_k, rows);
+}
+// mon_object_query_points: the same kernel with the transform switched off, on points of the object's unit cube; raw4 out of its rows
+int object_points_check(int side, const float* unit_xyz, size_t n, const float* raw4) {
+    REQUIRE_ARG("object_points", unit_xyz, "points"); REQUIRE_ARG("object_points", raw4, "raw4");
+    { const int rc = side_check("object_points", side); if (rc) return rc; }
+    if (n == 0 || n > kSceneProbeMaxQueries) { set_error("object_points: %zu points (1 to %u)", n, kSceneProbeMaxQueries); return MON_ERR_ARG; }
+    for (size_t i = 0; i < 3 * n; ++i) if (!(unit_xyz[i] >= 0.f && unit_xyz[i] <= 1.f)) { set_error("object_points: point %zu lies outside the unit cube", i / 3);
+        return MON_ERR_ARG; }
+    return MON_OK;
+}
+int object_points(Model& m, int side, const float* unit_xyz, size_t n, float* raw4) {
+    Model* ms[1] = { &m };
+    ScenePoints q{}; q.xyz = unit_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    std::vector<float> rows(12 * n);
+    const int rc = scene_points_run("object_points", ms, 1, side, q, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, rows.data());
+    if (rc) return rc;
+    for (size_t i = 0; i < n; ++i) std::memcpy(raw4 + 4 * i, rows.data() + 12 * i + 4, 16);
     return MON_OK;
 }
 
