@@ -213,8 +213,8 @@ typedef struct mon_scene_query { uint32_t pose; uint32_t key; float u, v; } mon_
 int mon_scene_probe(mon_object* const* objs, size_t n_objs, int side, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q,
                     float* rgb, float* depth, float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance);
 /* Ray cast: the object map asked along world rays by a consumer that is not a camera of the dataset -- a planner's line-of-sight check between two points,
- * a range sensor, a grasp query, the surface point along a map point's viewing ray (the reference has no such call; opt-in, new).  Forward only: surface
- * normals and density gradients are a follow-up; queries at points rather than along rays: mon_scene_query_points below.
+ * a range sensor, a grasp query, the surface point along a map point's viewing ray (the reference has no such call; opt-in, new).  Forward only; the
+ * normal at the hit: mon_scene_cast_normals below; queries at points rather than along rays: mon_scene_query_points below.
  * Ray i is x(t) = o + t d for 0 <= t <= t_max in the world frame; d must be unit (| |d|^2 - 1 | <= 1e-3, used as given: the device does not renormalise);
  * t_max > 0, +inf allowed.  For object j the ray is taken into j's frame (R_ow d, R_ow o + t_ow) and intersected with j's box at [t0, t1]; j contributes iff
  * the box is hit and lo < hi, lo = max(t0, 0), hi = min(t1, t_max).  Its 2S = 64 samples are the scene render's for a ray row {t0 = lo, t1 = hi}:
@@ -256,7 +256,7 @@ int mon_camera_rays(float fx, float fy, float cx, float cy, const float* Twc16s,
                     mon_scene_ray* rays_out, float* dn_out);
 /* Point queries: the object map asked about a place instead of a ray -- is this voxel free, which object owns this point, how dense is the field over
  * this lattice (a planner's or a grasper's question; a ray costs 64 samples per answer, a point one; the reference has no such call; opt-in, new).  Forward
- * only: normals and gradients are not computed; a caller differences six point queries.
+ * only; the field's derivative at the same points: mon_scene_query_gradients below.
  * A world point x goes into object j's frame as mon_scene_cast takes a ray origin there, q = R_ow x + t_ow, and into j's unit cube by the operation the
  * render applies to a sample point, u_a = (q_a - aabb_min_a) / (aabb_max_a - aabb_min_a); it is inside j iff 0 <= u_a <= 1 on all three axes.  For an
  * inside point the network is evaluated at u exactly as the render evaluates a sample, with the render's weights of that side; sigma_j = exp(o3),
@@ -290,6 +290,50 @@ int mon_scene_query_points(mon_object* const* objs, size_t n_objs, int side, con
 int mon_scene_query_lattice(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz,
                             float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside);
 int mon_lattice_points(const float* origin3, const float* step3, int nx, int ny, int nz, float* xyz_out);
+/* Point gradients and surface normals: the point queries with the field's derivative -- the surface normal at a grasp contact, the direction that takes a
+ * path away from an object (the reference has no such call; opt-in, new, read-only; no existing call changes its bits).  Differencing point queries does
+ * not give it: the finest cells of a base.json grid are about 2e-6 of the box and the raw log density is fp16, so a difference inside a cell measures
+ * rounding.  The derivative here is analytic.
+ * Per object j and point: the point goes into j's unit cube and is judged inside exactly as in mon_scene_query_points; the forward is that call's, so
+ * raw4, sigma_j = exp(o3) and the colour are its values bit for bit.  The backward runs the pose routes' tile backward (dL/dO -> dL/dx) from the seed
+ * dO = (0, 0, 0, 1), scaled by 2^5 into fp16 and unscaled exactly: it yields d o3 / d q, the gradient of j's raw log density.  Held at their forward values:
+ * each level's hash-grid corners and the ReLU masks of the fp16 forward; only the trilinear weights are differentiated, which away from cell faces and
+ * ReLU kinks is the field's derivative.  Level l's term is multiplied by level_weights[l] (NULL: every weight 1, the exact gradient of the field; object j
+ * reads level_weights[0 .. L_j) of an array of Lmax = the largest n_levels among the objects).  g_obj = d o3 / d q per unit of object-frame length;
+ * g_j = R_ow^T g_obj in fp32 (g_a = fmaf(R(2,a), g_obj2, fmaf(R(1,a), g_obj1, R(0,a) g_obj0))) is the world gradient of j's log density -- Tow is rigid, so
+ * nothing is rescaled.  Outside j's box g_j = 0.
+ * On fine grids the gradient of every level is dominated by the finest ones and is noise as a surface direction: for a NORMAL pass
+ * a coarse window, level_weights[l] = 1 for the coarse levels and 0 above (mon_pose_c2f_weights forms such windows).
+ * Outputs per point: the five of mon_scene_query_points with the same bits (sigma required, the others may be NULL), and
+ *   grad_log[3]   (required) = g_j of the owner (of the selected object), 0 0 0 without one
+ *   grad_sigma[3] (may be NULL) = sum over the objects the point is inside, in the order of objs, per component acc = fmaf(sigma_j, g_j, acc): the world
+ *                 gradient of sigma.  A non-finite sigma_j is passed on as IEEE arithmetic gives it, as in sigma.
+ *   normal[3]     (may be NULL) = -grad_log / |grad_log|, the direction of falling density, outward from a surface; |g| = sqrtf(fmaf(g2, g2, fmaf(g1, g1,
+ *                 g0 g0))), one division per component.  0 0 0 without an owner, or when |g| is 0 or not finite (under- and overflow of the squares included).
+ * select: NULL, or n int32.  -1 keeps the owner rule; k >= 0 makes object k the one reported in owner, rgb, owner_sigma, grad_log and normal if the point
+ * lies in k's box, else those are reported as "no owner" (-1, zeros).  sigma, n_inside and grad_sigma do not depend on select.
+ * Independence, sides, passes (16 384 points), "no atomics: equal arguments, equal bits", one enqueue and one synchronisation: as mon_scene_query_points.
+ * mon_scene_query_lattice_gradients: the same over the lattice, formed on the device as mon_scene_query_lattice forms it; it takes no select.
+ * mon_object_query_gradients: one object, unit-cube points, the transform off: raw4[n][4] (may be NULL) = mon_object_query_points' bits,
+ * grad_unit[n][3] = d o3 / d u, the derivative per unit of the unit cube: the kernel's division by the extent is a division by 1, nothing is multiplied back.
+ * Returns MON_ERR_ARG and MON_ERR_STATE as the point queries do, and MON_ERR_ARG for grad_log (grad_unit) NULL, a select value outside [-1, n_objs), a
+ * level weight that is negative or not finite -- all before any device work, the outputs untouched.
+ * mon_scene_cast_normals: the normal at a ray's hit, a host-side rule whose every step is a public call:
+ *   1. mon_scene_cast (the same arguments and seven outputs);  2. for the rays with hit_instance >= 0, x_a = fmaf(hit_t, d_a, o_a) per axis in fp32;
+ *   3. mon_scene_query_gradients at those points, compacted in ray order, with select = hit_instance;  4. hit_xyz = x, normal, grad_log scattered back.
+ * A miss gets 0 0 0 in all three (hit_xyz and grad_log may be NULL).  Two enqueues and two synchronisations (one when no ray hits).  A hit point that fp32
+ * rounding puts outside the hit object's box (a hit exactly on the box's entry face) gets normal and grad_log 0 while hit_instance stays.  Errors: those
+ * of mon_scene_cast, a NULL normal, a bad level weight. */
+int mon_object_query_gradients(mon_object* obj, int side, const float* unit_xyz, size_t n, const float* level_weights, float* raw4, float* grad_unit);
+int mon_scene_query_gradients(mon_object* const* objs, size_t n_objs, int side, const float* world_xyz, size_t n, const float* level_weights,
+                              const int32_t* select, float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside,
+                              float* grad_log, float* grad_sigma, float* normal);
+int mon_scene_query_lattice_gradients(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz,
+                                      const float* level_weights, float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside,
+                                      float* grad_log, float* grad_sigma, float* normal);
+int mon_scene_cast_normals(mon_object* const* objs, size_t n_objs, int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity,
+                           const float* level_weights, float* rgb, float* dist, float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t,
+                           int32_t* hit_instance, float* hit_xyz, float* normal, float* grad_log);
 /* Object pose refinement through the trained field (iNeRF-style): align the object with observed frames by following the gradient of a photometric,
  * silhouette and depth error with respect to the 6-DoF pose Tow.
  * Objective.  obs names frames of the object's dataset (FrameId) and pixel boxes inside them; the target of a pixel is that frame's rgb c*, its instance map
@@ -670,6 +714,16 @@ int mon_online_query_points(mon_online* mgr, const float* world_xyz, size_t n,
                             float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside);
 int mon_online_query_lattice(mon_online* mgr, const float* origin3, const float* step3, int nx, int ny, int nz,
                              float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside);
+/* mon_scene_query_gradients / mon_scene_cast_normals (side 1) over the same objects, with the same refusals.  owner, instance and hit_instance hold the
+ * manager's object indices, and so does select: -1, or the index of an object with published weights; any other value is MON_ERR_ARG.
+ * mon_online_cast_normals picks the objects once for both steps of its rule.  There is no online lattice form of the gradients: a caller forms the lattice
+ * with mon_lattice_points and passes it as a list. */
+int mon_online_query_gradients(mon_online* mgr, const float* world_xyz, size_t n, const float* level_weights, const int32_t* select,
+                               float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside,
+                               float* grad_log, float* grad_sigma, float* normal);
+int mon_online_cast_normals(mon_online* mgr, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, const float* level_weights,
+                            float* rgb, float* dist, float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t, int32_t* hit_instance,
+                            float* hit_xyz, float* normal, float* grad_log);
 /* mon_object_refine_pose(side 1) of object idx: its published snapshot, on the inference stream -- safe while the manager trains it.  MON_ERR_STATE while
  * nothing of it has been published. */
 int mon_online_refine_pose(mon_online* mgr, size_t idx, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, float* Tow16_inout,

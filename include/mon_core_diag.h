@@ -85,6 +85,11 @@ int mon_debug_scene_cast_composite(int device, uint32_t n_rays, uint32_t n_lists
  * point in k's unit cube), inside (0 / 1), raw4 (the network's raw outputs), sigma_k, r, g, b; a point outside k's box holds u, 0 and eight zeros.  The scene
  * call's outputs are, bit for bit, a fold of these rows over k: the fp32 sum of sigma_k in list order, the first largest sigma_k for the owner. */
 int mon_debug_scene_point_rows(mon_object* const* objs, size_t n_objs, int side, const float* world_xyz, size_t n, size_t k, float* rows);
+/* Point gradients (mon_scene_query_gradients, the same arguments first, no select): object k's row of every point as k_scene_point_grads writes it,
+ * rows[n][16] = mon_debug_scene_point_rows' twelve floats (the same bits), g_k[3] = the world gradient of k's log density there, and one 0; a point
+ * outside k's box holds u, 0 and twelve zeros.  The scene call's outputs are, bit for bit, a fold of these rows over k. */
+int mon_debug_scene_gradient_rows(mon_object* const* objs, size_t n_objs, int side, const float* world_xyz, size_t n, const float* level_weights, size_t k,
+                                  float* rows);
 
 /* Pose refinement (mon_object_pose_loss, the same arguments): per drawn ray of that evaluation (rays_per_iter of them, or every pixel of every box in box
  * order), its 2S = 64 samples: x[ray][64][3] the positions in the object frame, raw[ray][64][4] the network's raw outputs, dldx[ray][64][3] = dL/dx_k in the

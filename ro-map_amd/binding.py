@@ -212,6 +212,17 @@ _SIGS = {
     "mon_online_query_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_online_query_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p]),
+    "mon_object_query_gradients": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_scene_query_gradients": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_scene_query_lattice_gradients": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_scene_cast_normals": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_online_query_gradients": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_online_cast_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_pose_refine_default": (C.c_int, [C.POINTER(PoseRefineParams)]),
     "mon_object_pose_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32,
             C.POINTER(C.c_float), C.c_void_p]),
@@ -283,6 +294,7 @@ _DIAG_SIGS = {
     "mon_debug_scene_cast_composite": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_debug_scene_point_rows": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "mon_debug_scene_gradient_rows": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mon_debug_pose_samples": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32, C.c_void_p,
             C.c_void_p, C.c_void_p]),
     "mon_debug_scene_pose_samples": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PoseRefineParams), C.c_uint32,
@@ -940,6 +952,21 @@ class OnlineManager:
         _check(lib().mon_online_query_lattice(self.h, _p(o), _p(s), nx, ny, nz, *[_p(a) for a in out]))
         return out
 
+    def query_gradients(self, world_xyz, level_weights=None, select=None):
+        """mon_online_query_gradients: query_scene_gradients on side 1 over every object with published weights (safe while they train); owner and
+        select hold the manager's object indices."""
+        x = np.ascontiguousarray(world_xyz, np.float32).reshape(-1, 3); out = _gradient_outputs(x.shape[0])
+        w = _weights_arg(level_weights); s = _select_arg(select, x.shape[0])
+        _check(lib().mon_online_query_gradients(self.h, _p(x), x.shape[0], _p(w), _p(s), *[_p(a) for a in out]))
+        return out
+
+    def cast_normals(self, rays, hit_opacity=0.5, level_weights=None):
+        """mon_online_cast_normals: cast_scene_normals on side 1 over every object with published weights; the instance outputs hold the manager's
+        object indices."""
+        r, out = _cast_args(rays); out = out + _normal_outputs(r.shape[0]); w = _weights_arg(level_weights)
+        _check(lib().mon_online_cast_normals(self.h, _p(r), r.shape[0], float(hit_opacity), _p(w), *[_p(a) for a in out]))
+        return out
+
     def save_map(self, path):
         """mon_online_save_map: <path>/map.txt + one checkpoint per object, each under its own model lock (safe while they train; not one global cut)."""
         _check(lib().mon_online_save_map(self.h, os.fsencode(path)))
@@ -1208,6 +1235,67 @@ def scene_point_rows(objects, world_xyz, k, side=0):
     """mon_debug_scene_point_rows: object k's row of every point of that query, (n, 12) = u[3], inside, raw4, sigma_k, r, g, b."""
     x = np.ascontiguousarray(world_xyz, np.float32).reshape(-1, 3); rows = np.empty((x.shape[0], 12), np.float32)
     _check(diag_lib().mon_debug_scene_point_rows(_handles(objects), len(objects), int(side), _p(x), x.shape[0], int(k), _p(rows)))
+    return rows
+
+
+def _gradient_outputs(n):
+    return _point_outputs(n) + (np.empty((n, 3), np.float32), np.empty((n, 3), np.float32), np.empty((n, 3), np.float32))
+
+
+def _weights_arg(level_weights):
+    return None if level_weights is None else np.ascontiguousarray(level_weights, np.float32).reshape(-1)
+
+
+def _select_arg(select, n):
+    if select is None:
+        return None
+    s = np.ascontiguousarray(select, np.int32).reshape(-1)
+    if s.shape[0] != n:
+        raise ValueError("select holds %d values for %d points" % (s.shape[0], n))
+    return s
+
+
+def query_object_gradients(obj, unit_xyz, level_weights=None, side=0):
+    """mon_object_query_gradients: (raw (n, 4), grad_unit (n, 3) = d raw3 / d u) at points of the object's unit cube; level_weights: n_levels floats."""
+    x = np.ascontiguousarray(unit_xyz, np.float32).reshape(-1, 3); w = _weights_arg(level_weights)
+    raw = np.empty((x.shape[0], 4), np.float32); g = np.empty((x.shape[0], 3), np.float32)
+    _check(lib().mon_object_query_gradients(obj.h, int(side), _p(x), x.shape[0], _p(w), _p(raw), _p(g)))
+    return raw, g
+
+
+def query_scene_gradients(objects, world_xyz, level_weights=None, select=None, side=0):
+    """mon_scene_query_gradients: query_scene_points' five outputs, then grad_log (n, 3) = the world gradient of the owner's (the selected object's) log
+    density, grad_sigma (n, 3) = the world gradient of sigma, normal (n, 3) = -grad_log / |grad_log|.  level_weights: Lmax floats (None: all 1; a coarse
+    window for normals); select: per point -1 (the owner rule) or the index of the object to report."""
+    x = np.ascontiguousarray(world_xyz, np.float32).reshape(-1, 3); out = _gradient_outputs(x.shape[0])
+    w = _weights_arg(level_weights); s = _select_arg(select, x.shape[0])
+    _check(lib().mon_scene_query_gradients(_handles(objects), len(objects), int(side), _p(x), x.shape[0], _p(w), _p(s), *[_p(a) for a in out]))
+    return out
+
+
+def query_scene_lattice_gradients(objects, origin, step, shape, level_weights=None, side=0):
+    """mon_scene_query_lattice_gradients: query_scene_gradients (no select) over the lattice of query_scene_lattice, formed on the device."""
+    o, s, nx, ny, nz = _lattice_args(origin, step, shape); out = _gradient_outputs(max(nx, 0) * max(ny, 0) * max(nz, 0)); w = _weights_arg(level_weights)
+    _check(lib().mon_scene_query_lattice_gradients(_handles(objects), len(objects), int(side), _p(o), _p(s), nx, ny, nz, _p(w), *[_p(a) for a in out]))
+    return out
+
+
+def _normal_outputs(n):
+    return (np.empty((n, 3), np.float32), np.empty((n, 3), np.float32), np.empty((n, 3), np.float32))
+
+
+def cast_scene_normals(objects, rays, hit_opacity=0.5, level_weights=None, side=0):
+    """mon_scene_cast_normals: cast_scene's seven outputs, then hit_xyz (n, 3), normal (n, 3) and grad_log (n, 3) of the hit object at the hit point
+    (0 0 0 for a miss)."""
+    r, out = _cast_args(rays); out = out + _normal_outputs(r.shape[0]); w = _weights_arg(level_weights)
+    _check(lib().mon_scene_cast_normals(_handles(objects), len(objects), int(side), _p(r), r.shape[0], float(hit_opacity), _p(w), *[_p(a) for a in out]))
+    return out
+
+
+def scene_gradient_rows(objects, world_xyz, k, level_weights=None, side=0):
+    """mon_debug_scene_gradient_rows: object k's row of every point of that query, (n, 16) = scene_point_rows' twelve floats, g_k[3], 0."""
+    x = np.ascontiguousarray(world_xyz, np.float32).reshape(-1, 3); rows = np.empty((x.shape[0], 16), np.float32); w = _weights_arg(level_weights)
+    _check(diag_lib().mon_debug_scene_gradient_rows(_handles(objects), len(objects), int(side), _p(x), x.shape[0], _p(w), int(k), _p(rows)))
     return rows
 
 

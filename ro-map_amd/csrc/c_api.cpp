@@ -159,6 +159,42 @@ int mon_scene_query_lattice(mon_object* const* objs, size_t n_objs, int side, co
 int mon_lattice_points(const float* origin3, const float* step3, int nx, int ny, int nz, float* xyz_out) {
     return scene_lattice_points(origin3, step3, nx, ny, nz, xyz_out);
 }
+int mon_object_query_gradients(mon_object* o, int side, const float* unit_xyz, size_t n, const float* level_weights, float* raw4, float* grad_unit) {
+    { const int rc = object_gradients_check(side, unit_xyz, n, level_weights, grad_unit); if (rc) return rc; }
+    REQUIRE(o, "object");
+    return object_gradients(*o->m, side, unit_xyz, n, level_weights, raw4, grad_unit);
+}
+int mon_scene_query_gradients(mon_object* const* objs, size_t n_objs, int side, const float* world_xyz, size_t n, const float* level_weights,
+        const int32_t* select, float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside, float* grad_log, float* grad_sigma,
+        float* normal) {
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_gradients_check(side, world_xyz, n, level_weights, select, n_objs, sigma, grad_log)) ||
+        (rc = scene_models("scene_gradients", objs, n_objs, ms)) || (rc = scene_objects_check("scene_gradients", ms.data(), n_objs, false)) ||
+        (rc = scene_gradients_weights_check(ms.data(), n_objs, level_weights))) return rc;
+    ScenePoints q{}; q.xyz = world_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    return scene_gradients(ms.data(), n_objs, side, q, level_weights, select, sigma, rgb, owner, owner_sigma, n_inside, grad_log, grad_sigma, normal, nullptr, 0,
+                           nullptr);
+}
+int mon_scene_query_lattice_gradients(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz,
+        const float* level_weights, float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside, float* grad_log, float* grad_sigma,
+        float* normal) {
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_lattice_gradients_check(side, origin3, step3, nx, ny, nz, level_weights, sigma, grad_log)) ||
+        (rc = scene_models("scene_lattice_gradients", objs, n_objs, ms)) || (rc = scene_objects_check("scene_lattice_gradients", ms.data(), n_objs, false)) ||
+        (rc = scene_gradients_weights_check(ms.data(), n_objs, level_weights))) return rc;
+    return scene_gradients(ms.data(), n_objs, side, scene_lattice(origin3, step3, nx, ny, nz), level_weights, nullptr, sigma, rgb, owner, owner_sigma, n_inside,
+                           grad_log, grad_sigma, normal, nullptr, 0, nullptr);
+}
+int mon_scene_cast_normals(mon_object* const* objs, size_t n_objs, int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity,
+        const float* level_weights, float* rgb, float* dist, float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t, int32_t* hit_instance,
+        float* hit_xyz, float* normal, float* grad_log) {
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_cast_normals_check(side, rays, n_rays, hit_opacity, level_weights, rgb, dist, normal)) ||
+        (rc = scene_models("scene_cast_normals", objs, n_objs, ms)) || (rc = scene_objects_check("scene_cast_normals", ms.data(), n_objs, false)) ||
+        (rc = scene_gradients_weights_check(ms.data(), n_objs, level_weights))) return rc;
+    return scene_cast_normals(ms.data(), n_objs, side, rays, n_rays, hit_opacity, level_weights, rgb, dist, opacity, instance, hit_t, hit_sample_t, hit_instance,
+                              hit_xyz, normal, grad_log, nullptr);
+}
 int mon_pose_refine_default(mon_pose_refine_params* p) {
     REQUIRE(p, "params");
     p->iters = 100; p->rays_per_iter = 4096; p->lr_trans = 2e-3f; p->lr_rot = 4e-3f;

@@ -315,6 +315,18 @@ int mon_debug_scene_point_rows(mon_object* const* objs, size_t n_objs, int side,
     mon::ScenePoints q{}; q.xyz = world_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
     return mon::scene_points(ms.data(), n_objs, side, q, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k, rows);
 }
+int mon_debug_scene_gradient_rows(mon_object* const* objs, size_t n_objs, int side, const float* world_xyz, size_t n, const float* level_weights, size_t k,
+                                  float* rows) {
+    REQUIRE(rows, "rows");
+    std::vector<mon::Model*> ms; int rc;
+    if ((rc = mon::scene_gradients_check(side, world_xyz, n, level_weights, nullptr, n_objs, rows, rows)) ||
+        (rc = mon::scene_models("scene_gradients", objs, n_objs, ms)) || (rc = mon::scene_objects_check("scene_gradients", ms.data(), n_objs, false)) ||
+        (rc = mon::scene_gradients_weights_check(ms.data(), n_objs, level_weights))) return rc;
+    if (k >= n_objs) { set_error("debug_scene_gradient_rows: k out of range"); return MON_ERR_ARG; }
+    mon::ScenePoints q{}; q.xyz = world_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    return mon::scene_gradients(ms.data(), n_objs, side, q, level_weights, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                k, rows);
+}
 int mon_debug_pose_samples(mon_object* o, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params* p,
                            uint32_t iteration, float* x, float* raw, float* dldx) {
     REQUIRE(o, "object");

@@ -755,6 +755,40 @@ int mon_online_query_lattice(mon_online* h, const float* origin3, const float* s
         (rc = scene_objects_check("scene_lattice", ms.data(), ms.size(), false))) return rc;
     return scene_points(ms.data(), ms.size(), 1, scene_lattice(origin3, step3, nx, ny, nz), sigma, rgb, owner, owner_sigma, n_inside, ids.data(), 0, nullptr);
 }
+// ... with the field's derivative: mon_scene_query_gradients on side 1 over the same objects.  select names objects as owner does, by the manager's index:
+// -1, or the index of an object with published weights (anything else is MON_ERR_ARG; what is below -1 is refused before the objects are looked at).
+int mon_online_query_gradients(mon_online* h, const float* world_xyz, size_t n, const float* level_weights, const int32_t* select, float* sigma, float* rgb,
+        int32_t* owner, float* owner_sigma, uint32_t* n_inside, float* grad_log, float* grad_sigma, float* normal) {
+    REQ(h);
+    std::vector<Model*> ms; std::vector<int32_t> ids; int rc;
+    if ((rc = scene_gradients_check(1, world_xyz, n, level_weights, select, (size_t)1 << 31, sigma, grad_log)) ||
+        (rc = online_published(h, "query_gradients", 0, false, ms, &ids)) || (rc = scene_objects_check("scene_gradients", ms.data(), ms.size(), false)) ||
+        (rc = scene_gradients_weights_check(ms.data(), ms.size(), level_weights))) return rc;
+    std::vector<int32_t> sel;
+    if (select) {
+        sel.resize(n);
+        for (size_t i = 0; i < n; ++i) {
+            const auto it = select[i] < 0 ? ids.end() : std::lower_bound(ids.begin(), ids.end(), select[i]);      // (ids: index order)
+            if (select[i] >= 0 && (it == ids.end() || *it != select[i])) { set_error("query_gradients: select[%zu] = %d is not an object with published weights",
+                i, select[i]); return MON_ERR_ARG; }
+            sel[i] = select[i] < 0 ? -1 : (int32_t)(it - ids.begin());
+        }
+    }
+    ScenePoints q{}; q.xyz = world_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    return scene_gradients(ms.data(), ms.size(), 1, q, level_weights, select ? sel.data() : nullptr, sigma, rgb, owner, owner_sigma, n_inside, grad_log, grad_sigma,
+                           normal, ids.data(), 0, nullptr);
+}
+// mon_scene_cast_normals on side 1 over the objects mon_online_cast_rays casts against (picked once for both steps of the rule)
+int mon_online_cast_normals(mon_online* h, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, const float* level_weights, float* rgb, float* dist,
+        float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t, int32_t* hit_instance, float* hit_xyz, float* normal, float* grad_log) {
+    REQ(h);
+    std::vector<Model*> ms; std::vector<int32_t> ids; int rc;
+    if ((rc = scene_cast_normals_check(1, rays, n_rays, hit_opacity, level_weights, rgb, dist, normal)) ||
+        (rc = online_published(h, "cast_normals", 0, false, ms, &ids)) || (rc = scene_objects_check("scene_cast_normals", ms.data(), ms.size(), false)) ||
+        (rc = scene_gradients_weights_check(ms.data(), ms.size(), level_weights))) return rc;
+    return scene_cast_normals(ms.data(), ms.size(), 1, rays, n_rays, hit_opacity, level_weights, rgb, dist, opacity, instance, hit_t, hit_sample_t, hit_instance,
+                              hit_xyz, normal, grad_log, ids.data());
+}
 // pose refinement of one object against new observations, from its published snapshot (a frontend's call, like mon_online_render: safe while it trains)
 int mon_online_refine_pose(mon_online* h, size_t idx, const mon_frame_bbox* obs, size_t n_obs, const mon_pose_refine_params* p, float* Tow16_inout,
         float* loss_trace) {

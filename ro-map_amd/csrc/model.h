@@ -361,6 +361,15 @@ void launch_scene_points(hipStream_t s, const LevelFast& lt, const NetDims& nd, 
         int build_image, bool world, const ScenePointsArgs& p);
 void launch_scene_points_fold(hipStream_t s, uint32_t n, uint32_t n_objs, uint32_t cap, const float* rows, float* sigma, float* rgb, int32_t* owner,
         float* owner_sigma, uint32_t* n_inside);
+// Point gradients (mon_scene_query_gradients / _lattice_gradients, mon_object_query_gradients; kernels_scene_gradients.hip).  k_scene_point_grads:
+// k_scene_points with rows [n][16] = its twelve floats (the same bits), g[3], 0 -- world: g = R_ow^T d raw3 / d q, the world gradient of the object's log
+// density; else g = d raw3 / d u.  frag_image: the FULL fragment image (N_FRAGS x 512 halves; built first when build_image), level_w: device, the
+// object's L weights.  k_scene_gradients_fold: the K rows of each point ([K][cap][16]) -> the five outputs, grad_log, grad_sigma, normal; select: device,
+// [n] or nullptr.
+void launch_scene_point_grads(hipStream_t s, const LevelFast& lt, const NetDims& nd, const uint16_t* params, const ObjectConst& oc, uint16_t* frag_image,
+        int build_image, bool world, const ScenePointsArgs& p, const float* level_w);
+void launch_scene_gradients_fold(hipStream_t s, uint32_t n, uint32_t n_objs, uint32_t cap, const float* rows, const int32_t* select, float* sigma, float* rgb,
+        int32_t* owner, float* owner_sigma, uint32_t* n_inside, float* grad_log, float* grad_sigma, float* normal);
 // Pose refinement (mon_object_pose_loss / mon_object_refine_pose, kernels_pose.hip).  k_pose_rays: one record of 4 float4 per drawn ray from the pose in
 // device memory (pose[16], world -> object); k_pose_grad<shape>: loss and position gradient, one partial row of 8 floats {g, x x g, loss, 0} per workgroup
 // (pose_grad_grid of them); k_pose_update: the rows summed in a fixed order, x inv_n -> out[8 * it] = {loss, grad6, 0}, optionally the Adam step on pose.
@@ -731,6 +740,25 @@ int scene_points(Model* const* ms, size_t n, int side, const ScenePoints& q, flo
 int scene_lattice_points(const float* origin3, const float* step3, int nx, int ny, int nz, float* xyz_out);
 int object_points_check(int side, const float* unit_xyz, size_t n, const float* raw4);
 int object_points(Model& m, int side, const float* unit_xyz, size_t n, float* raw4);
+// Point gradients (mon_scene_query_gradients / _lattice_gradients, mon_object_query_gradients): the point queries' conventions, plus level_w (host, may be
+// nullptr = all 1: Lmax floats, object j reads its first L_j; the *_check judges the first, scene_gradients_weights_check the rest once the objects are
+// known) and select (host, [n] or nullptr: -1 or an index into ms).  rows (mon_debug_scene_gradient_rows) = object rows_k's rows, host array [n][16].
+// scene_cast_normals (mon_scene_cast_normals): scene_cast, then scene_gradients at the hit points with select = the hit object; ids applied at the end.
+int scene_gradients_check(int side, const float* xyz, size_t n, const float* level_w, const int32_t* select, size_t n_objs, const float* sigma,
+                          const float* grad_log);
+int scene_lattice_gradients_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, const float* level_w, const float* sigma,
+                                  const float* grad_log);
+int scene_gradients_weights_check(Model* const* ms, size_t n, const float* level_w);
+int scene_gradients(Model* const* ms, size_t n, int side, const ScenePoints& q, const float* level_w, const int32_t* select, float* sigma, float* rgb,
+                    int32_t* owner, float* owner_sigma, uint32_t* n_inside, float* grad_log, float* grad_sigma, float* normal, const int32_t* ids,
+                    size_t rows_k, float* rows);
+int object_gradients_check(int side, const float* unit_xyz, size_t n, const float* level_w, const float* grad_unit);
+int object_gradients(Model& m, int side, const float* unit_xyz, size_t n, const float* level_w, float* raw4, float* grad_unit);
+int scene_cast_normals_check(int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, const float* level_w, const float* rgb, const float* dist,
+                             const float* normal);
+int scene_cast_normals(Model* const* ms, size_t n, int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, const float* level_w, float* rgb,
+                       float* dist, float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t, int32_t* hit_instance, float* hit_xyz, float* normal,
+                       float* grad_log, const int32_t* ids);
 bool model_has_snapshot(Model& m);      // the object has an inference side and has published weights
 // Pose refinement: iters < 0 = one evaluation (mon_object_pose_loss: loss, grad6, jitter / draws of `iteration`), else iters Adam steps from Tow16
 // (mon_object_refine_pose: the final pose into pose_out, loss_trace[iters + 1] may be nullptr).  dump (mon_debug_pose_samples, may be nullptr): per drawn ray

@@ -106,6 +106,7 @@ struct SceneWs {
     DevBuf<mon_scene_query> q; DevBuf<float> poses; DevBuf<uint32_t> keys;        // scene_probe: the queries, the poses [n_poses][16], a pass's keys [cap]
     DevBuf<mon_scene_ray> rays; DevBuf<float> entry;                              // scene_cast: the rays, a pass's box entries [lists][cap]
     DevBuf<float> pts, rows;                                                      // scene_points: the points [n][3], a pass's rows [objects][cap][12]
+    DevBuf<uint16_t> gfrag; DevBuf<float> lw; DevBuf<int32_t> sel;                // scene_gradients (rows of 16): full fragment images, weights [Lmax], select [n]
     std::vector<hipEvent_t> ev;
 };
 // what each object renders with on a side; the render grids are the objects' own per-side caches, built if stale (their skip counters stay as they are).
@@ -494,6 +495,159 @@ int object_points(Model& m, int side, const float* unit_xyz, size_t n, float* ra
     const int rc = scene_points_run("object_points", ms, 1, side, q, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, rows.data());
     if (rc) return rc;
     for (size_t i = 0; i < n; ++i) std::memcpy(raw4 + 4 * i, rows.data() + 12 * i + 4, 16);
+    return MON_OK;
+}
+
+// ---- point gradients (mon_scene_query_gradients, mon_scene_query_lattice_gradients, mon_object_query_gradients): scene_points_run's
+// sibling with rows of 16 floats (k_scene_point_grads) and the fold that adds grad_log, grad_sigma and normal.  Beside the points the call keeps in the
+// side's workspace every object's FULL fragment image (the backward reads the transposed matrices; the objects' own render images hold the forward set
+// only and are left alone), the level weights (ones for NULL) and `select`.  The same passes, one enqueue, one synchronisation.
+// What can be judged without an object: the points as scene_points_check judges them, the required outputs, select's range (n_objs is an argument) and
+// the first weight (every object has at least one level, so level_weights[0] is always read); the other weights need Lmax: scene_gradients_weights_check.
+static int weight_value_check(const char* what, const float* w, int l) {
+    if (!std::isfinite(w[l]) || w[l] < 0.f) { set_error("%s: level weight %d is %g (finite, >= 0)", what, l, (double)w[l]); return MON_ERR_ARG; }
+    return MON_OK;
+}
+static int gradients_args_check(const char* what, const float* level_w, const int32_t* select, size_t n_pts, size_t n_objs, const float* grad_log) {
+    REQUIRE_ARG(what, grad_log, "grad_log");
+    if (level_w) { const int rc = weight_value_check(what, level_w, 0); if (rc) return rc; }
+    if (select) for (size_t i = 0; i < n_pts; ++i) if (select[i] < -1 || (int64_t)select[i] >= (int64_t)n_objs) {
+        set_error("%s: select[%zu] = %d (-1 or an index below %zu)", what, i, select[i], n_objs); return MON_ERR_ARG; }
+    return MON_OK;
+}
+int scene_gradients_check(int side, const float* xyz, size_t n, const float* level_w, const int32_t* select, size_t n_objs, const float* sigma,
+                          const float* grad_log) {
+    { const int rc = scene_points_check(side, xyz, n, sigma); if (rc) return rc; }
+    return gradients_args_check("scene_gradients", level_w, select, n, n_objs, grad_log);
+}
+int scene_lattice_gradients_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, const float* level_w, const float* sigma,
+                                  const float* grad_log) {
+    { const int rc = scene_lattice_check(side, origin3, step3, nx, ny, nz, sigma); if (rc) return rc; }
+    return gradients_args_check("scene_lattice_gradients", level_w, nullptr, 0, 0, grad_log);
+}
+int scene_gradients_weights_check(Model* const* ms, size_t n, const float* level_w) {
+    return level_w ? level_weights_check("scene_gradients", level_w, scene_levels(ms, n).Lmax) : MON_OK;
+}
+// rows (mon_debug_scene_gradient_rows, mon_object_query_gradients; may be nullptr) = object rows_k's rows of every point, host array [q.n][16].
+static int scene_gradients_run(const char* what, Model* const* ms, size_t n, int side, const ScenePoints& q, bool world, const float* level_w,
+                               const int32_t* select, float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside, float* grad_log,
+                               float* grad_sigma, float* normal, const int32_t* ids, size_t rows_k, float* rows) {
+    { const int rc = scene_points_state_check(what, ms, n, side); if (rc) return rc; }
+    const int device = ms[0]->device;
+    HIPCHECK(use_device(device));
+    const size_t n_q = q.n; const uint32_t nq = (uint32_t)n_q, cap = std::min(nq, kScenePointsPass), L = (uint32_t)n;
+    const int Lmax = scene_levels(ms, n).Lmax;
+    std::vector<size_t> frag_off(n + 1, 0);
+    for (size_t j = 0; j < n; ++j) { const NetDims& nd = ms[j]->nd; const FragDims fd{ nd.Epad, nd.W, nd.NH, nd.L }; frag_off[j + 1] = frag_off[j] + (size_t)fd.N_FRAGS() * 512; }
+    const std::vector<float> ones(level_w ? 0 : (size_t)Lmax, 1.f);
+    SceneWs& ws = side_ws<SceneWs>(device, side);
+    SceneSide sd; { const int rc = sd.enter(ms, n, side, ws.mu, ws.ev); if (rc) return rc; }
+    const hipStream_t s = sd.s;
+    // the output area: [the dumped rows 16 n_q |] sigma | rgb 3 n_q | owner | owner_sigma | n_inside | grad_log 3 n_q | grad_sigma 3 n_q | normal 3 n_q
+    const size_t rows_floats = rows ? 16 * n_q : 0, out_floats = rows_floats + 16 * n_q;
+    {   int rc;
+        if ((rc = ws.rows.grow((size_t)L * cap * 16)) || (rc = ws.out.grow(out_floats)) || (rc = ws.h_out.grow(out_floats)) || (rc = ws.gfrag.grow(frag_off[n])) ||
+            (rc = ws.lw.grow((size_t)Lmax)) || (q.xyz && (rc = ws.pts.grow(3 * n_q))) || (select && (rc = ws.sel.grow(n_q)))) return rc; }
+    if (q.xyz) HIPCHECK(hipMemcpyAsync(ws.pts.p, q.xyz, 12 * n_q, hipMemcpyHostToDevice, s));
+    if (select) HIPCHECK(hipMemcpyAsync(ws.sel.p, select, 4 * n_q, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(ws.lw.p, level_w ? level_w : ones.data(), 4 * (size_t)Lmax, hipMemcpyHostToDevice, s));
+    float* o = ws.out.p + rows_floats;
+    for (uint32_t p0 = 0; p0 < nq; p0 += cap) {
+        const uint32_t nc = std::min(cap, nq - p0);
+        for (size_t j = 0; j < n; ++j) {
+            Model& m = *ms[j];
+            ScenePointsArgs a{}; a.pts = q.xyz ? ws.pts.p + 3 * (size_t)p0 : nullptr; a.nx = (uint32_t)q.nx; a.ny = (uint32_t)q.ny; a.first = p0; a.n = nc;
+            for (int k = 0; k < 3; ++k) { a.origin[k] = q.origin[k]; a.step[k] = q.step[k]; }
+            a.rows = ws.rows.p + j * (size_t)cap * 16;
+            launch_scene_point_grads(s, m.lf, m.nd, sd.prm[j], m.oc, ws.gfrag.p + frag_off[j], p0 == 0u, world, a, ws.lw.p);
+        }
+        launch_scene_gradients_fold(s, nc, L, cap, ws.rows.p, select ? ws.sel.p + p0 : nullptr, o + p0, o + n_q + 3 * (size_t)p0,
+                reinterpret_cast<int32_t*>(o + 4 * n_q) + p0, o + 5 * n_q + p0, reinterpret_cast<uint32_t*>(o + 6 * n_q) + p0, o + 7 * n_q + 3 * (size_t)p0,
+                o + 10 * n_q + 3 * (size_t)p0, o + 13 * n_q + 3 * (size_t)p0);
+        if (rows) launch_copy_params(s, reinterpret_cast<const uint16_t*>(ws.rows.p + rows_k * (size_t)cap * 16),
+                reinterpret_cast<uint16_t*>(ws.out.p + 16 * (size_t)p0), 32u * nc);
+    }
+    launch_copy_params(s, reinterpret_cast<const uint16_t*>(ws.out.p), reinterpret_cast<uint16_t*>(ws.h_out.p), (uint32_t)(2 * out_floats));
+    HIPCHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    const float* h = ws.h_out.p + rows_floats;
+    if (rows) std::memcpy(rows, ws.h_out.p, 4 * rows_floats);
+    if (sigma) std::memcpy(sigma, h, 4 * n_q);
+    if (rgb) std::memcpy(rgb, h + n_q, 12 * n_q);
+    scene_instances_home(owner, h + 4 * n_q, n_q, ids);
+    if (owner_sigma) std::memcpy(owner_sigma, h + 5 * n_q, 4 * n_q);
+    if (n_inside) std::memcpy(n_inside, h + 6 * n_q, 4 * n_q);
+    if (grad_log) std::memcpy(grad_log, h + 7 * n_q, 12 * n_q);
+    if (grad_sigma) std::memcpy(grad_sigma, h + 10 * n_q, 12 * n_q);
+    if (normal) std::memcpy(normal, h + 13 * n_q, 12 * n_q);
+    return MON_OK;
+}
+int scene_gradients(Model* const* ms, size_t n, int side, const ScenePoints& q, const float* level_w, const int32_t* select, float* sigma, float* rgb,
+                    int32_t* owner, float* owner_sigma, uint32_t* n_inside, float* grad_log, float* grad_sigma, float* normal, const int32_t* ids,
+                    size_t rows_k, float* rows) {
+    return scene_gradients_run(q.xyz ? "scene_gradients" : "scene_lattice_gradients", ms, n, side, q, true, level_w, select, sigma, rgb, owner, owner_sigma,
+                               n_inside, grad_log, grad_sigma, normal, ids, rows_k, rows);
+}
+// mon_object_query_gradients: the same kernel with the transform switched off and the extent taken as 1 (nothing is divided): raw4 and d raw3 / d u
+int object_gradients_check(int side, const float* unit_xyz, size_t n, const float* level_w, const float* grad_unit) {
+    REQUIRE_ARG("object_gradients", grad_unit, "grad_unit");
+    { const int rc = object_points_check(side, unit_xyz, n, grad_unit); if (rc) return rc; }
+    return level_w ? weight_value_check("object_gradients", level_w, 0) : MON_OK;
+}
+int object_gradients(Model& m, int side, const float* unit_xyz, size_t n, const float* level_w, float* raw4, float* grad_unit) {
+    if (level_w) { const int rc = level_weights_check("object_gradients", level_w, (int)m.nd.L); if (rc) return rc; }
+    Model* ms[1] = { &m };
+    ScenePoints q{}; q.xyz = unit_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    std::vector<float> rows(16 * n);
+    const int rc = scene_gradients_run("object_gradients", ms, 1, side, q, false, level_w, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                       nullptr, nullptr, 0, rows.data());
+    if (rc) return rc;
+    for (size_t i = 0; i < n; ++i) { if (raw4) std::memcpy(raw4 + 4 * i, rows.data() + 16 * i + 4, 16); std::memcpy(grad_unit + 3 * i, rows.data() + 16 * i + 12, 12); }
+    return MON_OK;
+}
+// mon_scene_cast_normals / mon_online_cast_normals: a host-side rule over two routes -- the cast; x = fmaf(hit_t, d, o) per axis for the rays with a hit;
+// the gradients at those points, compacted in ray order, with select = the hit object; scattered back, 0 0 0 for a miss.  Two enqueues, two
+// synchronisations (one when no ray hits).  ids: applied to both instance outputs at the end (the rule itself runs on indices into ms).
+int scene_cast_normals_check(int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, const float* level_w, const float* rgb, const float* dist,
+                             const float* normal) {
+    { const int rc = scene_cast_check(side, rays, n_rays, hit_opacity, rgb, dist); if (rc) return rc; }
+    REQUIRE_ARG("scene_cast_normals", normal, "normal");
+    return level_w ? weight_value_check("scene_cast_normals", level_w, 0) : MON_OK;
+}
+int scene_cast_normals(Model* const* ms, size_t n, int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, const float* level_w, float* rgb,
+                       float* dist, float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t, int32_t* hit_instance, float* hit_xyz, float* normal,
+                       float* grad_log, const int32_t* ids) {
+    std::vector<float> t_own; std::vector<int32_t> inst_own;
+    if (!hit_t) { t_own.resize(n_rays); hit_t = t_own.data(); }
+    if (!hit_instance) { inst_own.resize(n_rays); hit_instance = inst_own.data(); }
+    { const int rc = scene_cast(ms, n, side, rays, n_rays, hit_opacity, rgb, dist, opacity, instance, hit_t, hit_sample_t, hit_instance, nullptr, nullptr);
+      if (rc) return rc; }
+    std::vector<float> x; std::vector<int32_t> sel; std::vector<size_t> at;
+    for (size_t i = 0; i < n_rays; ++i) {
+        if (hit_instance[i] < 0) continue;
+        for (int a = 0; a < 3; ++a) x.push_back(std::fmaf(hit_t[i], rays[i].d[a], rays[i].o[a]));
+        sel.push_back(hit_instance[i]); at.push_back(i);
+    }
+    const size_t nh = at.size();
+    std::vector<float> sg(nh), gl(3 * nh), nr(3 * nh);
+    if (nh) {
+        ScenePoints q{}; q.xyz = x.data(); q.n = nh; q.nx = q.ny = q.nz = 1;
+        const int rc = scene_gradients(ms, n, side, q, level_w, sel.data(), sg.data(), nullptr, nullptr, nullptr, nullptr, gl.data(), nullptr, nr.data(), nullptr,
+                                       0, nullptr);
+        if (rc) return rc;
+    }
+    if (hit_xyz) std::fill(hit_xyz, hit_xyz + 3 * n_rays, 0.f);
+    if (grad_log) std::fill(grad_log, grad_log + 3 * n_rays, 0.f);
+    std::fill(normal, normal + 3 * n_rays, 0.f);
+    for (size_t k = 0; k < nh; ++k) for (int a = 0; a < 3; ++a) {
+        if (hit_xyz) hit_xyz[3 * at[k] + a] = x[3 * k + a];
+        if (grad_log) grad_log[3 * at[k] + a] = gl[3 * k + a];
+        normal[3 * at[k] + a] = nr[3 * k + a];
+    }
+    if (ids) for (size_t i = 0; i < n_rays; ++i) {
+        if (instance && instance[i] >= 0) instance[i] = ids[instance[i]];
+        if (hit_instance[i] >= 0) hit_instance[i] = ids[hit_instance[i]];
+    }
     return MON_OK;
 }
 
