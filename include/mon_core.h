@@ -334,6 +334,43 @@ int mon_scene_query_lattice_gradients(mon_object* const* objs, size_t n_objs, in
 int mon_scene_cast_normals(mon_object* const* objs, size_t n_objs, int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity,
                            const float* level_weights, float* rgb, float* dist, float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t,
                            int32_t* hit_instance, float* hit_xyz, float* normal, float* grad_log);
+/* Distance fields: clearance over a lattice -- how far each cell is from the nearest occupied cell, which cell that is and which object it belongs to; the
+ * quantity a path optimiser or a collision check works with (a Euclidean distance field of the voxblox / FIESTA kind; the reference has no such call;
+ * opt-in, new, read-only; no existing call changes its bits).  Exact, not approximate: the result is the minimum over ALL occupied cells.
+ * The lattice: nx x ny x nz cells, i fastest, cell (i, j, k) at index (k * ny + j) * nx + i; step3 = the spacing per axis, finite; a component may be
+ * negative (only its square matters) or 0 (that axis then adds nothing to a distance).
+ * The arithmetic, every operation a separately rounded fp32 one (nothing is contracted into an fma):
+ *   a_x = (float)(i - i') * step[0], likewise a_y, a_z;   d2(cell, cell') = ((a_x * a_x) + (a_y * a_y)) + (a_z * a_z)
+ *   d2(cell) = the least d2(cell, cell') over the occupied cells';   dist = sqrt(d2), the correctly rounded root.
+ * It is computed axis by axis -- v1 = min over occupied i' of a_x^2; v2 = min over j' of fl(a_y^2 + v1(i, j', k)); v3 = min over k' of fl(a_z^2 +
+ * v2(i, j, k')) -- which, rounding being monotone, is the minimum of the nested expression bit for bit.
+ * nearest = the flat index of the occupied cell that gives it.  The rule: in each of the three minimisations the candidates are taken in ascending index
+ * along that axis, a candidate replaces the best only when strictly smaller, and the site stored below a candidate is carried along.  Away from ties that
+ * rounding itself creates this is the occupied cell with the lowest flat index among the nearest.  Without an occupied cell: dist = +inf, nearest = -1.
+ * max_dist (above 0; +inf: no limit): where !(dist <= max_dist), dist = max_dist and nearest = -1; a cell at exactly max_dist keeps its site.
+ * No atomics: equal arguments, equal bits; a cell's outputs depend on the mask, the shape and the steps alone.
+ * mon_distance_transform: the transform of a host mask (occupied[nx * ny * nz], a cell counts iff its byte is not 0) on `device`, as mon_marching_cubes
+ * serves density lattices; dist[nx * ny * nz]; nearest may be NULL.
+ * mon_scene_distance_lattice: the object map's field over the lattice of mon_scene_query_lattice (the same points, sides, objects and passes).  A cell is
+ * occupied iff !(sigma <= sigma_min), sigma that call's output bit for bit: a NaN or +inf sigma counts as occupied, the conservative reading for a planner.
+ * sigma is a density per unit of world length: opacity a over a step of length l corresponds to sigma_min = -ln(1 - a) / l.  Mask, transform and owner
+ * lookup run on the device behind the query; one copy home, one synchronisation.  Outputs per cell (all but dist may be NULL):
+ *   dist          = the distance to the nearest occupied cell (0 on an occupied cell), truncated by max_dist
+ *   nearest       = that cell's flat index, -1 without one
+ *   nearest_owner = mon_scene_query_lattice's owner at that cell (an index into objs; -1 where the cell lies in no box, which a finite sigma_min >= 0
+ *                   never marks occupied), -1 without a nearest cell
+ *   free_dist     = the same transform of the complemented mask: the distance to the nearest FREE cell, 0 on a free cell, truncated by max_dist alike; a
+ *                   signed field is dist - free_dist
+ *   sigma         = mon_scene_query_lattice's sigma
+ * Returns:
+ *   MON_ERR_ARG    occupied, step3, origin3, dist, objs or an element NULL; nx, ny or nz below 1 or nx * ny * nz above 2^22; a non-finite step or origin
+ *                  (the scene call: a lattice that leaves the finite floats); sigma_min negative or not finite; max_dist <= 0 or NaN; side not 0 / 1;
+ *                  n_objs 0 or above 256; objects on different logical devices -- all before any device work, the outputs untouched
+ *   MON_ERR_STATE  as mon_scene_query_lattice;   MON_ERR_NO_DEVICE  mon_distance_transform without a device */
+int mon_distance_transform(int device, const uint8_t* occupied, int nx, int ny, int nz, const float* step3, float max_dist,
+                           float* dist, int32_t* nearest);
+int mon_scene_distance_lattice(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz,
+                               float sigma_min, float max_dist, float* dist, int32_t* nearest, int32_t* nearest_owner, float* free_dist, float* sigma);
 /* Object pose refinement through the trained field (iNeRF-style): align the object with observed frames by following the gradient of a photometric,
  * silhouette and depth error with respect to the 6-DoF pose Tow.
  * Objective.  obs names frames of the object's dataset (FrameId) and pixel boxes inside them; the target of a pixel is that frame's rgb c*, its instance map
@@ -714,6 +751,10 @@ int mon_online_query_points(mon_online* mgr, const float* world_xyz, size_t n,
                             float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside);
 int mon_online_query_lattice(mon_online* mgr, const float* origin3, const float* step3, int nx, int ny, int nz,
                              float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside);
+/* mon_scene_distance_lattice (side 1) over the same objects, with the same refusals; nearest_owner holds the manager's object indices.  A planner's
+ * call for the clearance field, safe while the objects train. */
+int mon_online_distance_lattice(mon_online* mgr, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float max_dist,
+                                float* dist, int32_t* nearest, int32_t* nearest_owner, float* free_dist, float* sigma);
 /* mon_scene_query_gradients / mon_scene_cast_normals (side 1) over the same objects, with the same refusals.  owner, instance and hit_instance hold the
  * manager's object indices, and so does select: -1, or the index of an object with published weights; any other value is MON_ERR_ARG.
  * mon_online_cast_normals picks the objects once for both steps of its rule.  There is no online lattice form of the gradients: a caller forms the lattice

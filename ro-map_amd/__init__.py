@@ -13,6 +13,7 @@ from .binding import (MonConfig, MonBBox, MonError, Dataset, ObjectNeRF, default
                       SceneQuery, SCENE_QUERY_DTYPE, scene_queries, rect_queries, probe_scene, scene_probe_rays, scene_probe_composite,
                       SceneRay, SCENE_RAY_DTYPE, scene_rays, camera_rays, cast_scene, scene_cast_rays, scene_cast_composite,
                       query_object_points, query_scene_points, query_scene_lattice, lattice_points, scene_point_rows,
+                      distance_transform, scene_distance_lattice,
                       query_object_gradients, query_scene_gradients, query_scene_lattice_gradients, cast_scene_normals, scene_gradient_rows,
                       WindowParams, window_default, window_frames, scene_window_loss, scene_refine_window,
                       CheckpointInfo, checkpoint_info, checkpoint_timing, MON_LOAD_BOXES,

@@ -212,6 +212,11 @@ _SIGS = {
     "mon_online_query_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_online_query_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p]),
+    "mon_distance_transform": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "mon_scene_distance_lattice": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_online_distance_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_object_query_gradients": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_scene_query_gradients": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -952,6 +957,13 @@ class OnlineManager:
         _check(lib().mon_online_query_lattice(self.h, _p(o), _p(s), nx, ny, nz, *[_p(a) for a in out]))
         return out
 
+    def distance_lattice(self, origin, step, shape, sigma_min, max_dist=np.inf, free=True):
+        """mon_online_distance_lattice: scene_distance_lattice on side 1 over every object with published weights (safe while they train);
+        nearest_owner holds the manager's object indices."""
+        o, s, nx, ny, nz = _lattice_args(origin, step, shape); out = _distance_outputs(max(nx, 0) * max(ny, 0) * max(nz, 0), free)
+        _check(lib().mon_online_distance_lattice(self.h, _p(o), _p(s), nx, ny, nz, float(sigma_min), float(max_dist), *[_p(a) for a in out]))
+        return out
+
     def query_gradients(self, world_xyz, level_weights=None, select=None):
         """mon_online_query_gradients: query_scene_gradients on side 1 over every object with published weights (safe while they train); owner and
         select hold the manager's object indices."""
@@ -1229,6 +1241,31 @@ def lattice_points(origin, step, shape):
     o, s, nx, ny, nz = _lattice_args(origin, step, shape); xyz = np.empty((max(nx, 0) * max(ny, 0) * max(nz, 0), 3), np.float32)
     _check(lib().mon_lattice_points(_p(o), _p(s), nx, ny, nz, _p(xyz)))
     return xyz
+
+
+def _distance_outputs(n, free):
+    return (np.empty(n, np.float32), np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32) if free else None, np.empty(n, np.float32))
+
+
+def distance_transform(occupied, step, max_dist=np.inf, device=0, nearest=True):
+    """mon_distance_transform: the exact Euclidean distance transform of a mask of shape (nz, ny, nx) (x fastest; a cell counts iff it is not 0) with
+    spacing step = (sx, sy, sz).  Returns (dist, nearest), both of the mask's shape: the distance to the nearest occupied cell, truncated by max_dist,
+    and that cell's flat index (-1: none); nearest=False passes NULL and returns (dist, None)."""
+    m = np.ascontiguousarray(occupied); assert m.ndim == 3, "mask of shape (nz, ny, nx)"
+    m = np.ascontiguousarray(m != 0, np.uint8); nz, ny, nx = m.shape
+    s = np.ascontiguousarray(step, np.float32).reshape(3)
+    dist = np.empty(m.shape, np.float32); near = np.empty(m.shape, np.int32) if nearest else None
+    _check(lib().mon_distance_transform(int(device), _p(m), nx, ny, nz, _p(s), float(max_dist), _p(dist), _p(near)))
+    return dist, near
+
+
+def scene_distance_lattice(objects, origin, step, shape, sigma_min, max_dist=np.inf, side=0, free=True):
+    """mon_scene_distance_lattice: the object map's distance field over the lattice of query_scene_lattice, a cell occupied iff not (sigma <= sigma_min).
+    Returns (dist, nearest, nearest_owner, free_dist (None with free=False), sigma), each of nx * ny * nz elements."""
+    o, s, nx, ny, nz = _lattice_args(origin, step, shape); out = _distance_outputs(max(nx, 0) * max(ny, 0) * max(nz, 0), free)
+    _check(lib().mon_scene_distance_lattice(_handles(objects), len(objects), int(side), _p(o), _p(s), nx, ny, nz, float(sigma_min), float(max_dist),
+                                            *[_p(a) for a in out]))
+    return out
 
 
 def scene_point_rows(objects, world_xyz, k, side=0):

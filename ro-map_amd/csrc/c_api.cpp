@@ -159,6 +159,18 @@ int mon_scene_query_lattice(mon_object* const* objs, size_t n_objs, int side, co
 int mon_lattice_points(const float* origin3, const float* step3, int nx, int ny, int nz, float* xyz_out) {
     return scene_lattice_points(origin3, step3, nx, ny, nz, xyz_out);
 }
+int mon_distance_transform(int device, const uint8_t* occupied, int nx, int ny, int nz, const float* step3, float max_dist, float* dist, int32_t* nearest) {
+    { const int rc = distance_transform_check(occupied, nx, ny, nz, step3, max_dist, dist); if (rc) return rc; }
+    return distance_transform(device, occupied, nx, ny, nz, step3, max_dist, dist, nearest);
+}
+int mon_scene_distance_lattice(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz,
+        float sigma_min, float max_dist, float* dist, int32_t* nearest, int32_t* nearest_owner, float* free_dist, float* sigma) {
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_distance_check(side, origin3, step3, nx, ny, nz, sigma_min, max_dist, dist)) || (rc = scene_models("scene_distance", objs, n_objs, ms)) ||
+        (rc = scene_objects_check("scene_distance", ms.data(), n_objs, false))) return rc;
+    return scene_distance(ms.data(), n_objs, side, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, max_dist, dist, nearest, nearest_owner, free_dist, sigma,
+                          nullptr);
+}
 int mon_object_query_gradients(mon_object* o, int side, const float* unit_xyz, size_t n, const float* level_weights, float* raw4, float* grad_unit) {
     { const int rc = object_gradients_check(side, unit_xyz, n, level_weights, grad_unit); if (rc) return rc; }
     REQUIRE(o, "object");

@@ -755,6 +755,16 @@ int mon_online_query_lattice(mon_online* h, const float* origin3, const float* s
         (rc = scene_objects_check("scene_lattice", ms.data(), ms.size(), false))) return rc;
     return scene_points(ms.data(), ms.size(), 1, scene_lattice(origin3, step3, nx, ny, nz), sigma, rgb, owner, owner_sigma, n_inside, ids.data(), 0, nullptr);
 }
+// clearance over a planner's lattice: mon_scene_distance_lattice on side 1 over the same objects; nearest_owner holds the manager's indices
+int mon_online_distance_lattice(mon_online* h, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float max_dist, float* dist,
+        int32_t* nearest, int32_t* nearest_owner, float* free_dist, float* sigma) {
+    REQ(h);
+    std::vector<Model*> ms; std::vector<int32_t> ids; int rc;
+    if ((rc = scene_distance_check(1, origin3, step3, nx, ny, nz, sigma_min, max_dist, dist)) || (rc = online_published(h, "distance_lattice", 0, false, ms, &ids)) ||
+        (rc = scene_objects_check("scene_distance", ms.data(), ms.size(), false))) return rc;
+    return scene_distance(ms.data(), ms.size(), 1, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, max_dist, dist, nearest, nearest_owner, free_dist, sigma,
+                          ids.data());
+}
 // ... with the field's derivative: mon_scene_query_gradients on side 1 over the same objects.  select names objects as owner does, by the manager's index:
 // -1, or the index of an object with published weights (anything else is MON_ERR_ARG; what is below -1 is refused before the objects are looked at).
 int mon_online_query_gradients(mon_online* h, const float* world_xyz, size_t n, const float* level_weights, const int32_t* select, float* sigma, float* rgb,

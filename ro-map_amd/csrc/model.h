@@ -370,6 +370,14 @@ void launch_scene_point_grads(hipStream_t s, const LevelFast& lt, const NetDims&
         int build_image, bool world, const ScenePointsArgs& p, const float* level_w);
 void launch_scene_gradients_fold(hipStream_t s, uint32_t n, uint32_t n_objs, uint32_t cap, const float* rows, const int32_t* select, float* sigma, float* rgb,
         int32_t* owner, float* owner_sigma, uint32_t* n_inside, float* grad_log, float* grad_sigma, float* normal);
+// Distance fields (mon_distance_transform, mon_scene_distance_lattice; kernels_distance.hip).  k_distance_mask: occ[i] = !(sigma[i] <= sigma_min).
+// launch_distance_passes: the x, y and z pass of k_distance_pass over the mask (`invert`: over its complement) -> the squared distance to the nearest
+// occupied cell in v[0 .. n) and that cell's flat index in site[0 .. n) (+inf and -1 without one); v and site hold 2 n elements, n = nx ny nz <= 2^22.
+// k_distance_finish: dist = the root, max_dist applied; nearest and nearest_owner (= owner[nearest]; owner: device, [n]) may be nullptr.
+void launch_distance_mask(hipStream_t s, uint32_t n, const float* sigma, float sigma_min, uint8_t* occ);
+void launch_distance_passes(hipStream_t s, const uint8_t* occ, bool invert, uint32_t nx, uint32_t ny, uint32_t nz, const float* step3, float* v, int32_t* site);
+void launch_distance_finish(hipStream_t s, uint32_t n, const float* d2, const int32_t* site, float max_dist, const int32_t* owner, float* dist,
+        int32_t* nearest, int32_t* nearest_owner);
 // Pose refinement (mon_object_pose_loss / mon_object_refine_pose, kernels_pose.hip).  k_pose_rays: one record of 4 float4 per drawn ray from the pose in
 // device memory (pose[16], world -> object); k_pose_grad<shape>: loss and position gradient, one partial row of 8 floats {g, x x g, loss, 0} per workgroup
 // (pose_grad_grid of them); k_pose_update: the rows summed in a fixed order, x inv_n -> out[8 * it] = {loss, grad6, 0}, optionally the Adam step on pose.
@@ -740,6 +748,15 @@ int scene_points(Model* const* ms, size_t n, int side, const ScenePoints& q, flo
 int scene_lattice_points(const float* origin3, const float* step3, int nx, int ny, int nz, float* xyz_out);
 int object_points_check(int side, const float* unit_xyz, size_t n, const float* raw4);
 int object_points(Model& m, int side, const float* unit_xyz, size_t n, float* raw4);
+// Distance fields (mon_distance_transform, mon_scene_distance_lattice): distance_transform = the three passes and the finish on a host mask, in buffers
+// of its own (MON_ERR_NO_DEVICE without a device, after its check).  scene_distance = the lattice query (q: scene_lattice's; the same objects' check and
+// MON_ERR_STATE cases) with the mask !(sigma <= sigma_min), the transform and, with free_dist, the complement's transform behind it on the device; every
+// output but dist may be nullptr; ids as scene_points', applied to nearest_owner.
+int distance_transform_check(const uint8_t* occupied, int nx, int ny, int nz, const float* step3, float max_dist, const float* dist);
+int distance_transform(int device, const uint8_t* occupied, int nx, int ny, int nz, const float* step3, float max_dist, float* dist, int32_t* nearest);
+int scene_distance_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float max_dist, const float* dist);
+int scene_distance(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, float max_dist, float* dist, int32_t* nearest,
+                   int32_t* nearest_owner, float* free_dist, float* sigma, const int32_t* ids);
 // Point gradients (mon_scene_query_gradients / _lattice_gradients, mon_object_query_gradients): the point queries' conventions, plus level_w (host, may be
 // nullptr = all 1: Lmax floats, object j reads its first L_j; the *_check judges the first, scene_gradients_weights_check the rest once the objects are
 // known) and select (host, [n] or nullptr: -1 or an index into ms).  rows (mon_debug_scene_gradient_rows) = object rows_k's rows, host array [n][16].

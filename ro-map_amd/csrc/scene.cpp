@@ -107,6 +107,7 @@ struct SceneWs {
     DevBuf<mon_scene_ray> rays; DevBuf<float> entry;                              // scene_cast: the rays, a pass's box entries [lists][cap]
     DevBuf<float> pts, rows;                                                      // scene_points: the points [n][3], a pass's rows [objects][cap][12]
     DevBuf<uint16_t> gfrag; DevBuf<float> lw; DevBuf<int32_t> sel;                // scene_gradients (rows of 16): full fragment images, weights [Lmax], select [n]
+    DevBuf<uint8_t> docc; DevBuf<float> dv; DevBuf<int32_t> dsite;                // scene_distance: the mask [n], the passes' squared distances and sites [2][n]
     std::vector<hipEvent_t> ev;
 };
 // what each object renders with on a side; the render grids are the objects' own per-side caches, built if stale (their skip counters stay as they are).
@@ -391,13 +392,17 @@ int scene_points_check(int side, const float* xyz, size_t n, const float* sigma)
     return MON_OK;
 }
 // the lattice's shape alone (mon_lattice_points, which has no side and no outputs) ...
-static int lattice_shape_check(const char* what, const float* origin3, const float* step3, int nx, int ny, int nz) {
-    REQUIRE_ARG(what, origin3, "origin"); REQUIRE_ARG(what, step3, "step");
+static int lattice_dims_check(const char* what, int nx, int ny, int nz) {
     if (nx < 1 || ny < 1 || nz < 1) { set_error("%s: lattice %d x %d x %d (each at least 1)", what, nx, ny, nz); return MON_ERR_ARG; }
     // (each factor bounded before it is multiplied: three ints of up to 2^31 - 1 wrap a 64-bit product)
     const uint64_t mx = kSceneProbeMaxQueries;
     if ((uint64_t)nx > mx || (uint64_t)ny > mx / (uint64_t)nx || (uint64_t)nz > mx / ((uint64_t)nx * (uint64_t)ny)) { set_error("%s: lattice %d x %d x %d has more than %u points", what, nx, ny, nz,
         kSceneProbeMaxQueries); return MON_ERR_ARG; }
+    return MON_OK;
+}
+static int lattice_shape_check(const char* what, const float* origin3, const float* step3, int nx, int ny, int nz) {
+    REQUIRE_ARG(what, origin3, "origin"); REQUIRE_ARG(what, step3, "step");
+    { const int rc = lattice_dims_check(what, nx, ny, nz); if (rc) return rc; }
     const int dims[3] = { nx, ny, nz };
     for (int a = 0; a < 3; ++a) {
         if (!std::isfinite(origin3[a]) || !std::isfinite(step3[a])) { set_error("%s: origin or step is not finite", what); return MON_ERR_ARG; }
@@ -495,6 +500,95 @@ int object_points(Model& m, int side, const float* unit_xyz, size_t n, float* ra
     const int rc = scene_points_run("object_points", ms, 1, side, q, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, rows.data());
     if (rc) return rc;
     for (size_t i = 0; i < n; ++i) std::memcpy(raw4 + 4 * i, rows.data() + 12 * i + 4, 16);
+    return MON_OK;
+}
+
+// ---- distance fields (mon_distance_transform, mon_scene_distance_lattice): clearance over a lattice.  scene_distance is the lattice
+// query's sibling: the same state check, side, passes of k_scene_points and fold, whose sigma and owner rows stay on the device; then the mask
+// (k_distance_mask), the three passes of k_distance_pass and k_distance_finish, once more on the complement when free_dist is asked for, one copy home
+// and one synchronisation.  The side's workspace keeps the mask (1 B per cell) and the passes' two halves of squared distance and site (16 B per cell),
+// shared by the two transforms, which run one after the other.
+static int distance_outputs_check(const char* what, float max_dist, const float* dist) {
+    REQUIRE_ARG(what, dist, "dist");
+    if (!(max_dist > 0.f)) { set_error("%s: max_dist %g (above 0; +inf for no limit)", what, (double)max_dist); return MON_ERR_ARG; }
+    return MON_OK;
+}
+int distance_transform_check(const uint8_t* occupied, int nx, int ny, int nz, const float* step3, float max_dist, const float* dist) {
+    REQUIRE_ARG("distance_transform", occupied, "occupied"); REQUIRE_ARG("distance_transform", step3, "step");
+    { const int rc = lattice_dims_check("distance_transform", nx, ny, nz); if (rc) return rc; }
+    for (int a = 0; a < 3; ++a) if (!std::isfinite(step3[a])) { set_error("distance_transform: step is not finite"); return MON_ERR_ARG; }
+    return distance_outputs_check("distance_transform", max_dist, dist);
+}
+int scene_distance_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float max_dist, const float* dist) {
+    { const int rc = lattice_shape_check("scene_distance", origin3, step3, nx, ny, nz); if (rc) return rc; }
+    { const int rc = side_check("scene_distance", side); if (rc) return rc; }
+    if (!std::isfinite(sigma_min) || sigma_min < 0.f) { set_error("scene_distance: sigma_min %g (finite, >= 0)", (double)sigma_min); return MON_ERR_ARG; }
+    return distance_outputs_check("scene_distance", max_dist, dist);
+}
+// mon_distance_transform: the transform alone on a host mask, in buffers of its own on the device's default stream
+int distance_transform(int device, const uint8_t* occupied, int nx, int ny, int nz, const float* step3, float max_dist, float* dist, int32_t* nearest) {
+    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available"); return MON_ERR_NO_DEVICE; }
+    HIPCHECK(use_device(device));
+    const size_t n = (size_t)nx * ny * nz;
+    DevBuf<uint8_t> occ; DevBuf<float> v; DevBuf<int32_t> site;                     // v, site: the passes' two halves, then the output row
+    { int rc; if ((rc = occ.grow(n)) || (rc = v.grow(3 * n)) || (rc = site.grow(3 * n))) return rc; }
+    HIPCHECK(hipMemcpy(occ.p, occupied, n, hipMemcpyHostToDevice));
+    launch_distance_passes(nullptr, occ.p, false, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, step3, v.p, site.p);
+    launch_distance_finish(nullptr, (uint32_t)n, v.p, site.p, max_dist, nullptr, v.p + 2 * n, nearest ? site.p + 2 * n : nullptr, nullptr);
+    HIPCHECK(hipGetLastError());
+    std::vector<float> h_dist(n); std::vector<int32_t> h_near(nearest ? n : 0);     // (the caller's arrays are written only once everything has succeeded)
+    HIPCHECK(hipMemcpy(h_dist.data(), v.p + 2 * n, 4 * n, hipMemcpyDeviceToHost));
+    if (nearest) HIPCHECK(hipMemcpy(h_near.data(), site.p + 2 * n, 4 * n, hipMemcpyDeviceToHost));
+    std::memcpy(dist, h_dist.data(), 4 * n);
+    if (nearest) std::memcpy(nearest, h_near.data(), 4 * n);
+    return MON_OK;
+}
+// q: a lattice (scene_lattice).  ids as scene_points', applied to nearest_owner.  max_dist truncates dist and free_dist alike.
+int scene_distance(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, float max_dist, float* dist, int32_t* nearest,
+                   int32_t* nearest_owner, float* free_dist, float* sigma, const int32_t* ids) {
+    { const int rc = scene_points_state_check("scene_distance", ms, n, side); if (rc) return rc; }
+    const int device = ms[0]->device;
+    HIPCHECK(use_device(device));
+    const size_t n_q = q.n; const uint32_t nq = (uint32_t)n_q, cap = std::min(nq, kScenePointsPass), L = (uint32_t)n;
+    SceneWs& ws = side_ws<SceneWs>(device, side);
+    SceneSide sd; { const int rc = sd.enter(ms, n, side, ws.mu, ws.ev); if (rc) return rc; }
+    const hipStream_t s = sd.s;
+    const std::vector<SceneSrc> src = scene_sources(ms, n, side, sd, false);
+    // the output area: sigma | dist | nearest | nearest_owner | free_dist (what may go home, from the front) | rgb 3 n_q | owner | owner_sigma | n_inside
+    const size_t out_floats = 11 * n_q, home_rows = free_dist ? 5 : nearest_owner ? 4 : nearest ? 3 : 2;
+    {   int rc;
+        if ((rc = ws.rows.grow((size_t)L * cap * 12)) || (rc = ws.out.grow(out_floats)) || (rc = ws.h_out.grow(home_rows * n_q)) || (rc = ws.docc.grow(n_q)) ||
+            (rc = ws.dv.grow(2 * n_q)) || (rc = ws.dsite.grow(2 * n_q))) return rc; }
+    float* o = ws.out.p; int32_t* o_owner = reinterpret_cast<int32_t*>(o + 8 * n_q);
+    for (uint32_t p0 = 0; p0 < nq; p0 += cap) {
+        const uint32_t nc = std::min(cap, nq - p0);
+        for (size_t j = 0; j < n; ++j) {
+            Model& m = *ms[j];
+            ScenePointsArgs a{}; a.pts = nullptr; a.nx = (uint32_t)q.nx; a.ny = (uint32_t)q.ny; a.first = p0; a.n = nc;
+            for (int k = 0; k < 3; ++k) { a.origin[k] = q.origin[k]; a.step[k] = q.step[k]; }
+            a.rows = ws.rows.p + j * (size_t)cap * 12;
+            launch_scene_points(s, m.lf, m.nd, sd.prm[j], m.oc, src[j].frag, p0 == 0u, true, a);
+        }
+        launch_scene_points_fold(s, nc, L, cap, ws.rows.p, o + p0, o + 5 * n_q + 3 * (size_t)p0, o_owner + p0, o + 9 * n_q + p0,
+                reinterpret_cast<uint32_t*>(o + 10 * n_q) + p0);
+    }
+    launch_distance_mask(s, nq, o, sigma_min, ws.docc.p);
+    launch_distance_passes(s, ws.docc.p, false, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, q.step, ws.dv.p, ws.dsite.p);
+    launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, max_dist, o_owner, o + n_q, nearest ? reinterpret_cast<int32_t*>(o + 2 * n_q) : nullptr,
+            nearest_owner ? reinterpret_cast<int32_t*>(o + 3 * n_q) : nullptr);
+    if (free_dist) {
+        launch_distance_passes(s, ws.docc.p, true, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, q.step, ws.dv.p, ws.dsite.p);
+        launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, max_dist, nullptr, o + 4 * n_q, nullptr, nullptr);
+    }
+    launch_copy_params(s, reinterpret_cast<const uint16_t*>(ws.out.p), reinterpret_cast<uint16_t*>(ws.h_out.p), (uint32_t)(2 * home_rows * n_q));
+    HIPCHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    const float* h = ws.h_out.p;
+    if (sigma) std::memcpy(sigma, h, 4 * n_q);
+    std::memcpy(dist, h + n_q, 4 * n_q);
+    if (nearest) std::memcpy(nearest, h + 2 * n_q, 4 * n_q);
+    if (nearest_owner) scene_instances_home(nearest_owner, h + 3 * n_q, n_q, ids);
+    if (free_dist) std::memcpy(free_dist, h + 4 * n_q, 4 * n_q);
     return MON_OK;
 }
 
