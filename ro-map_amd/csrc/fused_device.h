@@ -25,7 +25,7 @@
 //   * composite / loss gradient: lanes 0-31 are the ray's samples in order; transmittance is an
 //     exclusive multiplicative wave scan, colour/depth suffix sums are additive scans;
 //   * weight gradients need samples on K: activations are transposed through a per-wave LDS scratch
-//     ([unit][sample] fp16) and accumulated in MFMA accumulators across the wave's rays, then reduced
+//     ([sample][unit] fp16 images, packed stores and ds_read_b64_tr_b16; see tr_off) and accumulated in MFMA accumulators across the wave's rays, then reduced
 //     across the workgroup in LDS and written as one fp32 partial per workgroup (summed by the optimizer).
 #pragma once
 #include <atomic>
@@ -73,6 +73,13 @@ constexpr int kEncodeBatch = MON_ENCODE_BATCH;
 #define MON_V_STAGGER 0x20010
 #endif
 constexpr uint32_t kDefaultStagger = MON_V_STAGGER;
+// k_fused_train's ray chain, one compile-time switch per change (0 builds the kernel without it: tools/variant_build.sh <tag> -DMON_FUSED_TR=0 ...)
+#ifndef MON_FUSED_XLOAD
+#define MON_FUSED_XLOAD 1       // PRE: a sample's {x, y, z, t} is loaded from the position pass's x_all, not recomputed
+#endif
+#ifndef MON_FUSED_TR
+#define MON_FUSED_TR 1          // dW transposes: packed stores into [sample][unit] images, operands read back with ds_read_b64_tr_b16
+#endif
 
 template <int EPAD, int W, int NH> struct FusedShape {
     static constexpr int MB = W / 32;            // 32-row M blocks of a hidden layer
@@ -89,7 +96,7 @@ template <int EPAD, int W, int NH> struct FusedShape {
     static constexpr int N_FRAGS = F_W0T + KSW;
     static constexpr int FRAG_BYTES = N_FRAGS * 1024;
     static constexpr int LT_BYTES = 512 + 4096;                      // LevelLds (113 words) + ray-compaction table (256 ballot words, 257 prefixes)
-    // per-wave transpose scratch, fp16 [row][32 samples]
+    // per-wave transpose scratch, fp16: [row][32 samples], or with MON_FUSED_TR [32 samples][row] images of the same sizes (the dO rows: always the former)
     static constexpr int SCR_E = 0;                                  // EPAD rows
     static constexpr int SCR_HA = SCR_E + EPAD * 32;                 // W rows: last hidden layer / its gradient
     static constexpr int SCR_HB = SCR_HA + W * 32;                   // W rows: first hidden layer (NH == 2)
@@ -130,6 +137,9 @@ struct FusedArgs {
     // occupancy-grid skipping (mon_config::occupancy_skip, default off): kOccRes^3 bits, 1 = the cell may hold density; nullptr = evaluate every sample
     const uint32_t* occ_bits;
     const half2_t* e_soa;       // PRE variant: [L][B] encoded features written by k_encode_tiles (kernels_encode.hip); the kernel then issues no gathers at all
+    // PRE variant: [B] float4 {x, y, z, t} of the position pass (encode_device.h points_sample) -- the values k_encode_tiles encoded, and bit for bit what
+    // ray_sample would compute from the ray's record
+    const float4_t* x_all;
 };
 
 // A fragments: the weight matrices pre-permuted to K-slot order (see the header).  They depend only on the weights,
@@ -192,11 +202,57 @@ __device__ __forceinline__ void mask_pack(const float16_t& acc, const half8_t& f
 #pragma unroll
     for (int j = 0; j < 8; ++j) { lo[j] = (half_t)(((float)flo[j] > 0.f) ? acc[j] : 0.f); hi[j] = (half_t)(((float)fhi[j] > 0.f) ? acc[8 + j] : 0.f); }
 }
-// store one packed C/D fragment pair transposed into the scratch: scr[unit][sample]
-__device__ __forceinline__ void scratch_store_units(half_t* scr, int mb, int n, int h, const half8_t& lo, const half8_t& hi) {
+// store one packed C/D fragment pair transposed into the scratch: scr[unit][sample] (ROWH: unused, the signature of tr_store_units)
+template <int ROWH = 0> __device__ __forceinline__ void scratch_store_units(half_t* scr, int mb, int n, int h, const half8_t& lo, const half8_t& hi) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) { scr[(32 * mb + rho(h, j)) * 32 + n] = lo[j]; scr[(32 * mb + rho(h, 8 + j)) * 32 + n] = hi[j]; }
 }
+
+// ---- MON_FUSED_TR: the same transposes as [sample][unit] images.  A lane's packed C/D registers 4g .. 4g + 3 are four CONSECUTIVE units (rho), so they go
+// out as one 8-byte store into the row of the lane's sample, and ds_read_b64_tr_b16 hands the dW MFMAs their operands transposed: per 16-lane group a block of
+// 4 rows (samples) x 16 columns (units), lane 4q + p supplying the address of row q, columns 4p .. 4p + 3, lane i receiving column i with row q in element q.
+// Rows are ROWH halves wide without padding; the 8-byte chunks of row n sit at chunk ^ tr_swz(n).  Bank rule (per instruction): the stores are served in groups
+// of 16 consecutive lanes = 16 consecutive samples at one chunk, over 32 banks -- conflict-free when the swizzle spreads those samples over 16 distinct
+// chunk-pair positions; a transposed read is served per half-wave = 4 consecutive rows (first row a multiple of 4) x 8 consecutive chunks (first a multiple of
+// 8), over 64 banks -- conflict-free when rows of equal parity (128-byte rows) or all four rows (256-byte rows) land in different 8-chunk blocks:
+//   ROWH = 128 (256-byte rows, 32 chunks): bits 0-2 = n >> 1, bit 3 = n & 1, bit 4 = (n >> 1) & 1     stores and reads conflict-free
+//   ROWH = 64  (128-byte rows, 16 chunks): bit 0 = n & 1, bits 1-2 = n >> 2, bit 3 = (n >> 1) & 1     stores and reads conflict-free
+//   ROWH = 32  (64-byte rows, 8 chunks):   n >> 1                                                     stores and reads conflict-free (4 rows = all 64 banks)
+//   ROWH = 16  (32-byte rows, 4 chunks):   n >> 2                                                     (E rows only: 4-byte stores, 2-way; reads conflict-free)
+template <int ROWH> __device__ __forceinline__ int tr_swz(int n) {
+    if constexpr (ROWH == 128) return ((n >> 1) & 7) | ((n & 1) << 3) | (((n >> 1) & 1) << 4);
+    else if constexpr (ROWH == 64) return (n & 1) | (((n >> 2) & 3) << 1) | (((n >> 1) & 1) << 3);
+    else if constexpr (ROWH == 32) return (n >> 1) & 7;
+    else return (n >> 2) & 3;
+}
+// offset in halves of element (sample row, column col) of a [32][ROWH] image
+template <int ROWH> __device__ __forceinline__ int tr_off(int row, int col) { return row * ROWH + 4 * ((col >> 2) ^ tr_swz<ROWH>(row)) + (col & 3); }
+// store one packed C/D fragment pair into the image: four 8-byte stores
+template <int ROWH> __device__ __forceinline__ void tr_store_units(half_t* img, int mb, int n, int h, const half8_t& lo, const half8_t& hi) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const half8_t& v = g < 2 ? lo : hi; const int j = 4 * (g & 1);
+        *reinterpret_cast<half4_t*>(img + tr_off<ROWH>(n, 32 * mb + 8 * g + 4 * h)) = half4_t{ v[j], v[j + 1], v[j + 2], v[j + 3] };
+    }
+}
+// the 32x32x16 A / B operand of k-step s with samples on K: lane (m, h) receives column col0 + m (modulo ROWH), samples 16 s + 8 h + j in element j.  Every lane
+// supplies an in-bounds address, and EXEC must be full (the read gathers across lanes): call it under wave-uniform control flow only
+template <int ROWH> __device__ __forceinline__ half8_t tr_operand(const half_t* img, int col0, int s, int lane) {
+    typedef short short4_t __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) short4_t lds_short4_t;
+    const int m = lane & 31, h = lane >> 5, q = (m & 15) >> 2, col = (col0 + 16 * (m >> 4) + 4 * (m & 3)) & (ROWH - 1);
+    const short4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4_t*)(img + tr_off<ROWH>(16 * s + 8 * h + q, col)));
+    const short4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4_t*)(img + tr_off<ROWH>(16 * s + 8 * h + 4 + q, col)));
+    typedef short short8_t __attribute__((ext_vector_type(8)));
+    return __builtin_bit_cast(half8_t, short8_t{ a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w });
+}
+
+// the transposing store of the dW operands, either way: dw_store_units<ROWH>(image, mb, n, h, lo, hi)
+#if MON_FUSED_TR
+#define dw_store_units tr_store_units
+#else
+#define dw_store_units scratch_store_units
+#endif
 
 // Phase timing (tools/fused_timing.py builds a -DMON_FUSED_TIMING variant of the library): per-wave cycle totals per phase,
 // every stamp drains the memory counters first so a phase owns the latency it waits for.  Compiles to nothing otherwise.

@@ -46,8 +46,12 @@ __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 :
     const LevelRegs lregs = load_level_regs_uniform(a.lt, L, lane); const uint32_t table_bytes = a.lt.offset[L] * 4u;
     build_fragments<EPAD, W, NH>(frags, llt, a, true);
     half_t* scr = reinterpret_cast<half_t*>(dyn + wave * S::SCR_BYTES);
-    // pad feature rows stay zero; every other row is rewritten per ray before it is read
+    // pad feature rows stay zero; every other row is rewritten per ray before it is read (MON_FUSED_TR: pad COLUMNS of the [sample][feature] image)
+#if MON_FUSED_TR
+    for (int i = lane; i < EPAD * 4; i += 64) reinterpret_cast<uint4*>(scr + S::SCR_E)[i] = uint4{ 0u, 0u, 0u, 0u };      // (the whole image, 16 bytes a lane)
+#else
     for (int i = 2 * a.nd.L * 32 + lane; i < EPAD * 32; i += 64) scr[S::SCR_E + i] = (half_t)0.f;
+#endif
     uint32_t my_excl = 0u, nvalid = 0u;
     if (have_rec) nvalid = a.st->n_valid_pre;
     else if (small) { const uint32_t c = __popcll(my_word), inc = scan_add64_u32(c); my_excl = inc - c;
@@ -133,6 +137,10 @@ __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 :
     //      before ray k's MLP / composite / backward -- no gain, 48.4 vs 48.6 us without the stagger and 9 spilled registers: the gather phase is bound by the
     //      chip-wide L2 request rate, not by its start-up latency; an encode-only variant of this kernel took 39.5 us, profiles/r03_*.)
     struct RaySample { float t, x[3]; uint32_t rgba; float tdp, t0, t1; bool live, any; };
+    // PRE: lane (n, h) takes sample n's {x, y, z, t} from the position pass, one 16-byte load requested a ray ahead with the feature dwords
+    constexpr bool kXLoad = PRE && MON_FUSED_XLOAD != 0;
+    float4_t xpre = float4_t{ 0.f, 0.f, 0.f, 0.f };
+    const auto load_position = [&](uint32_t r) { if constexpr (kXLoad) xpre = a.x_all[(size_t)r * 32u + (uint32_t)n]; };
     // sample n of the ray described by record `recv` (GenerateInputPoints, nerf_model.cu:553-566)
     const auto ray_sample = [&](uint32_t recv, uint32_t ray) {
         RaySample q; q.rgba = lane_u(recv, 0); q.tdp = __builtin_bit_cast(float, lane_u(recv, 9));
@@ -141,10 +149,16 @@ __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 :
                 __builtin_bit_cast(float, lane_u(recv, 5)) };
         const float ro[3] = { __builtin_bit_cast(float, lane_u(recv, 6)), __builtin_bit_cast(float, lane_u(recv, 7)),
                 __builtin_bit_cast(float, lane_u(recv, 8)) };
-        const float dtr = (t1 - t0) / 32.0f; q.t0 = t0; q.t1 = t1;
-        q.t = fmaf(dtr, (float)n + batch_rand(a.oc, kStreamDt, iter, ray * 32u + (uint32_t)n), t0);
+        q.t0 = t0; q.t1 = t1;
+        if constexpr (kXLoad) {
+            // the position pass computed exactly this from the same record, seed and iteration (encode_device.h points_sample), and k_encode_tiles encoded it
+            q.t = xpre.w; q.x[0] = xpre.x; q.x[1] = xpre.y; q.x[2] = xpre.z;
+        } else {
+            const float dtr = (t1 - t0) / 32.0f;
+            q.t = fmaf(dtr, (float)n + batch_rand(a.oc, kStreamDt, iter, ray * 32u + (uint32_t)n), t0);
 #pragma unroll
-        for (int d = 0; d < 3; ++d) { const float p = fmaf(q.t, rd[d], ro[d]); q.x[d] = (p - a.oc.aabb.mn[d]) / (a.oc.aabb.mx[d] - a.oc.aabb.mn[d]); }
+            for (int d = 0; d < 3; ++d) { const float p = fmaf(q.t, rd[d], ro[d]); q.x[d] = (p - a.oc.aabb.mn[d]) / (a.oc.aabb.mx[d] - a.oc.aabb.mn[d]); }
+        }
         // occupancy-grid skipping (default off): a sample whose cell the grid marks empty is not evaluated -- no gathers, alpha = 0, no gradient
         q.live = true;
         // (level-tile chain: the position pass looked the cells up and left the ray's 32 live bits in word 11 of its record -- k_encode_tiles encoded exactly
@@ -166,7 +180,7 @@ __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 :
             if (il < LPH && level < L) epre[il] = reinterpret_cast<const uint32_t*>(a.e_soa)[(size_t)level * (R * 32u) + r * 32u + (uint32_t)n];
         }
     };
-    if constexpr (PRE) { if (ray0 < R) load_encoded(ray0); }
+    if constexpr (PRE) { if (ray0 < R) { load_position(ray0); load_encoded(ray0); } }
     for (uint32_t ray = ray0; ray < R; ray += ray_stride) {
         const RaySample cur = ray_sample(rec, ray); const uint32_t cand_this = have_rec ? lane_u(rec, 10) : cand;      // (only the debug dump reads it)
         const uint32_t kth = ray % nvalid, rgba = cur.rgba, s_idx = ray * 32u + (uint32_t)n;
@@ -185,7 +199,7 @@ __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 :
         // the next ray's candidate record is requested HERE, behind this ray's last gather: vmcnt retires in order, so a load issued before the gathers would
         // have to land before the first level pair can be consumed; now its latency runs under the MLP, composite and backward pass
         if (ray + ray_stride < R) { if (have_rec) rec = load_ray_rec(ray + ray_stride); else { cand = select((ray + ray_stride) % nvalid);
-                rec = load_record(cand); } if constexpr (PRE) load_encoded(ray + ray_stride); }
+                rec = load_record(cand); } if constexpr (PRE) { load_position(ray + ray_stride); load_encoded(ray + ray_stride); } }
         if (!OCC || __ballot(live) != 0ull) mlp_forward<EPAD, W, NH>(ts, frags, lane);
         else {
 #pragma unroll
@@ -296,17 +310,25 @@ __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 :
 
         if (nz_cnt != 0u || DUMP) {
         // ---- transposes needed by the weight gradients
+        // (MON_FUSED_TR: [sample][feature] and [sample][unit] images, fused_device.h tr_off -- a level's two features in one 4-byte store, a fragment's
+        // four consecutive units in one 8-byte store; this region is under wave-uniform control flow, which the transposed reads below need)
         {
 #pragma unroll
         for (int il = 0; il < S::LLV; ++il) {
             const int level = h * LPH + il;
-            if (il < LPH && level < L) { scr[S::SCR_E + (2 * level) * 32 + n] = ts.ef[2 * il]; scr[S::SCR_E + (2 * level + 1) * 32 + n] = ts.ef[2 * il + 1]; }
+            if (il < LPH && level < L) {
+#if MON_FUSED_TR
+                *reinterpret_cast<half2_t*>(scr + S::SCR_E + tr_off<EPAD>(n, 2 * level)) = half2_t{ ts.ef[2 * il], ts.ef[2 * il + 1] };
+#else
+                scr[S::SCR_E + (2 * level) * 32 + n] = ts.ef[2 * il]; scr[S::SCR_E + (2 * level + 1) * 32 + n] = ts.ef[2 * il + 1];
+#endif
+            }
         }
 #pragma unroll
         for (int mb = 0; mb < S::MB; ++mb) {
-            if constexpr (NH == 2) { scratch_store_units(scr + S::SCR_HB, mb, n, h, ts.h0[mb][0], ts.h0[mb][1]);
-                scratch_store_units(scr + S::SCR_HA, mb, n, h, ts.h1[mb][0], ts.h1[mb][1]); }
-            else scratch_store_units(scr + S::SCR_HA, mb, n, h, ts.h0[mb][0], ts.h0[mb][1]);
+            if constexpr (NH == 2) { dw_store_units<W>(scr + S::SCR_HB, mb, n, h, ts.h0[mb][0], ts.h0[mb][1]);
+                dw_store_units<W>(scr + S::SCR_HA, mb, n, h, ts.h1[mb][0], ts.h1[mb][1]); }
+            else dw_store_units<W>(scr + S::SCR_HA, mb, n, h, ts.h0[mb][0], ts.h0[mb][1]);
         }
         }
 
@@ -326,7 +348,11 @@ __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 :
             if (m < kOut) bcol = *reinterpret_cast<const half8_t*>(scr + S::SCR_DO + m * 32 + 16 * s + 8 * h);
 #pragma unroll
             for (int mb = 0; mb < S::MB; ++mb) {
+#if MON_FUSED_TR
+                const half8_t arow = tr_operand<W>(scr + S::SCR_HA, 32 * mb, s, lane);
+#else
                 const half8_t arow = *reinterpret_cast<const half8_t*>(scr + S::SCR_HA + (32 * mb + m) * 32 + 16 * s + 8 * h);
+#endif
                 dWo[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(arow, bcol, dWo[mb], 0, 0, 0);
             }
         }
@@ -339,7 +365,7 @@ __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 :
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(lds_frag(frags, S::F_WOT + mb, lane), bdo, acc, 0, 0, 0);
             if constexpr (NH == 2) mask_pack(acc, ts.h1[mb][0], ts.h1[mb][1], dhl[mb][0], dhl[mb][1]);
             else mask_pack(acc, ts.h0[mb][0], ts.h0[mb][1], dhl[mb][0], dhl[mb][1]);
-            scratch_store_units(scr + S::SCR_HA, mb, n, h, dhl[mb][0], dhl[mb][1]);       // H_last no longer needed: reuse as dH_last
+            dw_store_units<W>(scr + S::SCR_HA, mb, n, h, dhl[mb][0], dhl[mb][1]);                      // H_last no longer needed: reuse as dH_last
         }
         half8_t dh0[S::MB][2];
         if constexpr (NH == 2) {
@@ -348,10 +374,18 @@ __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 :
             for (int s = 0; s < 2; ++s)
 #pragma unroll
                 for (int nb = 0; nb < S::MB; ++nb) {
+#if MON_FUSED_TR
+                    const half8_t bcol = tr_operand<W>(scr + S::SCR_HB, 32 * nb, s, lane);
+#else
                     const half8_t bcol = *reinterpret_cast<const half8_t*>(scr + S::SCR_HB + (32 * nb + m) * 32 + 16 * s + 8 * h);
+#endif
 #pragma unroll
                     for (int mb = 0; mb < S::MB; ++mb) {
+#if MON_FUSED_TR
+                        const half8_t arow = tr_operand<W>(scr + S::SCR_HA, 32 * mb, s, lane);
+#else
                         const half8_t arow = *reinterpret_cast<const half8_t*>(scr + S::SCR_HA + (32 * mb + m) * 32 + 16 * s + 8 * h);
+#endif
                         dW1[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(arow, bcol, dW1[mb][nb], 0, 0, 0);
                     }
                 }
@@ -363,7 +397,7 @@ __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 :
                 for (int s = 0; s < S::KSW; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(lds_frag(frags, S::F_W1T + mb * S::KSW + s, lane),
                         dhl[s >> 1][s & 1], acc, 0, 0, 0);
                 mask_pack(acc, ts.h0[mb][0], ts.h0[mb][1], dh0[mb][0], dh0[mb][1]);
-                scratch_store_units(scr + S::SCR_HB, mb, n, h, dh0[mb][0], dh0[mb][1]);   // H0 no longer needed: reuse as dH0
+                dw_store_units<W>(scr + S::SCR_HB, mb, n, h, dh0[mb][0], dh0[mb][1]);                  // H0 no longer needed: reuse as dH0
             }
         } else {
 #pragma unroll
@@ -375,10 +409,18 @@ __global__ void __launch_bounds__(256, (((NH == 2 && W == 64) || W == 128) ? 1 :
             const half_t* dh0_scr = scr + (NH == 2 ? S::SCR_HB : S::SCR_HA);
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
+#if MON_FUSED_TR
+                const half8_t bcol = tr_operand<EPAD>(scr + S::SCR_E, 0, s, lane);
+#else
                 const half8_t bcol = *reinterpret_cast<const half8_t*>(scr + S::SCR_E + (m & (EPAD - 1)) * 32 + 16 * s + 8 * h);
+#endif
 #pragma unroll
                 for (int mb = 0; mb < S::MB; ++mb) {
+#if MON_FUSED_TR
+                    const half8_t arow = tr_operand<W>(dh0_scr, 32 * mb, s, lane);
+#else
                     const half8_t arow = *reinterpret_cast<const half8_t*>(dh0_scr + (32 * mb + m) * 32 + 16 * s + 8 * h);
+#endif
                     dW0[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(arow, bcol, dW0[mb], 0, 0, 0);
                 }
             }
@@ -549,12 +591,15 @@ static void candidates_frags_t(hipStream_t s, const BatchPtrs& b, const DatasetP
 void launch_fused_train(hipStream_t s, const LevelFast& lt, const NetDims& nd, const ParamPtrs& p, const BatchPtrs& b, const ObjectConst& oc, DevState* st,
         float* dw_partials, int debug_dump,
                         uint16_t* de_soa, float* x_soa, uint32_t lds_level_mask, uint16_t* frag_image, uint32_t big_switch, uint8_t* touched,
-                                const uint32_t* occ_bits, uint32_t n_bins, const uint16_t* e_soa) {
+                                const uint32_t* occ_bits, uint32_t n_bins, const uint16_t* e_soa, const float* x_all) {
     const uint32_t keep_zero = options().keep_zero_samples != 0 ? 1u : 0u;
     uint32_t stagger = kDefaultStagger;
     if (oc.R < 2u * 4u * fused_train_grid(nd, oc.R)) stagger = 0u;      // a wave with one ray has no second phase to interleave: the delay would only be lost
     FusedArgs a{ lt, nd, oc, b, p.half, p.ggrid, dw_partials, st, reinterpret_cast<half2_t*>(de_soa), x_soa, lds_level_mask, frag_image, keep_zero, touched
-            ? touched + (nd.n_mlp >> 3) : nullptr, big_switch, n_bins, stagger, occ_bits, reinterpret_cast<const half2_t*>(e_soa) };
+            ? touched + (nd.n_mlp >> 3) : nullptr, big_switch, n_bins, stagger, occ_bits, reinterpret_cast<const half2_t*>(e_soa),
+            reinterpret_cast<const float4_t*>(x_all) };
+    // (the pre-encoded kernel takes its positions from the pass that fed the encode)
+    if (MON_FUSED_XLOAD && e_soa && !x_all) { set_error("launch_fused_train: encoded features without the positions they were encoded from"); return; }
     if (e_soa) a.stagger = 0u;          // (the stagger interleaves gather phases with compute phases; a pre-encoded batch has no gather phase)
     const uint32_t grid = fused_train_grid(nd, oc.R);
     MON_FUSED_DISPATCH(fused_train_t, s, a, grid, debug_dump);

@@ -284,7 +284,7 @@ uint32_t fused_train_grid(const NetDims& nd, uint32_t R);
 void launch_fused_train(hipStream_t s, const LevelFast& lt, const NetDims& nd, const ParamPtrs& p, const BatchPtrs& b, const ObjectConst& oc, DevState* st,
         float* dw_partials, int debug_dump,
                         uint16_t* de_soa, float* x_soa, uint32_t lds_level_mask, uint16_t* frag_image, uint32_t big_switch, uint8_t* touched,
-                                const uint32_t* occ_bits, uint32_t n_bins, const uint16_t* e_soa_or_null);
+                                const uint32_t* occ_bits, uint32_t n_bins, const uint16_t* e_soa_or_null, const float* x_all_or_null);
 // level-tile encode (kernels_encode.hip): the forward gathers as LDS reads of a level tile, one workgroup per (level, sample partition)
 bool encode_tiles_supported(const LevelTable& lt, const NetDims& nd);
 void encode_tiles_setup_device();

@@ -269,7 +269,8 @@ static void enqueue_fused_chain(Model& m, hipStream_t s, uint32_t B, const StepC
     {   ProfScope ps(m, MON_K_FWDBWD);
         // (no grid look-ups before the first refresh: every cell is live during the warm-up)
         launch_fused_train(s, m.lf, m.nd, m.P, m.B, m.oc, m.d_state, m.d_dw_partials, m.fused_dump, m.d_de_soa, m.d_x_soa, p.lds_mask, m.d_frag_train,
-                m.big_active ? m.big_switch : 0u, m.d_touched, occupancy_in_use(m) ? m.d_occ : nullptr, m.n_bins, c.pre ? m.d_e_soa : nullptr);
+                m.big_active ? m.big_switch : 0u, m.d_touched, occupancy_in_use(m) ? m.d_occ : nullptr, m.n_bins, c.pre ? m.d_e_soa : nullptr,
+                c.pre ? m.d_x_all : nullptr);
         m.scatter_pending = true;
     }
     const uint32_t n_partials = fused_train_grid(m.nd, m.oc.R);

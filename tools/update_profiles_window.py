@@ -58,7 +58,7 @@ def main():
         kw = open(os.path.join(src, "kernel_window.md")).read(); pw = open(os.path.join(src, "pmc_window.md")).read()
         # the sources these numbers were measured on: bench.py recomputes the fingerprint and flags the numbers as stale when it differs (tools/fingerprint.py)
         sys.path.insert(0, os.path.join(ROOT, "tools")); from fingerprint import kernel_sources_sha16
-        v = parse(pw); du = durations(kw); d = {"source": "profiles/%s_window_%s.md (gpurun %s)" % (rnd, regime, tag), "kernel_sources_sha16": kernel_sources_sha16()}
+        v = parse(pw); du = durations(kw); d = {"source": "profiles/%s_window_%s.md (run %s)" % (rnd, regime, tag), "kernel_sources_sha16": kernel_sources_sha16()}
         for k in KERNELS:
             if (k, "FETCH_SIZE") not in v:
                 continue
@@ -85,7 +85,7 @@ def main():
         out[regime] = d
         with open(os.path.join(ROOT, "profiles", "%s_window_%s.md" % (rnd, regime)), "w") as fh:
             fh.write("# %s, regime '%s': %s\n\nCommand profiled: `python tools/profile_window.py --warmup 5 --steps 20%s` under `rocprofv3 --kernel-trace --stats` (durations) and, in separate runs, "
-                     "`rocprofv3 --kernel-trace --pmc <one counter set>` (tools/gpu_profile_window.sh, gpurun %s, MI355X). Per kernel, dispatches are put in order and the window's 20 are averaged "
+                     "`rocprofv3 --kernel-trace --pmc <one counter set>` (tools/gpu_profile_window.sh, run %s, MI355X). Per kernel, dispatches are put in order and the window's 20 are averaged "
                      "(tools/rocpd_window.py). The trace's VGPR column counts register pairs (x2 = the compiler's .vgpr_count).\n\n## Durations\n\n%s\n## Counters\n\nFETCH_SIZE / WRITE_SIZE in KB; TCC_* / TCP_* in requests; "
                      "SQ_WAVE_CYCLES, SQ_WAIT_*, SQ_ACTIVE_INST_* in quad-cycles summed over waves; SQ_BUSY_CYCLES summed over the 32 shader engines; SQ_LDS_* in LDS-array cycles summed over CUs; GRBM_GUI_ACTIVE summed over the 8 XCDs.\n\n%s\n"
                      "## Derived (also in profiles/pmc_traffic.json)\n\n```\n%s\n```\n" % (rnd, regime, WHAT.get(regime, regime),
