@@ -371,6 +371,43 @@ int mon_distance_transform(int device, const uint8_t* occupied, int nx, int ny, 
                            float* dist, int32_t* nearest);
 int mon_scene_distance_lattice(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz,
                                float sigma_min, float max_dist, float* dist, int32_t* nearest, int32_t* nearest_owner, float* free_dist, float* sigma);
+/* Connected components: which cells of a lattice belong together -- the global question the local calls above leave open: is the goal reachable from the
+ * start by a robot of radius r, which free pockets are sealed off, how many occupied blobs there are and how large each is (the reference has no such
+ * call; opt-in, new, read-only; no existing call changes its bits).  Integers only, and the result has a unique definition:
+ * The lattice is the distance calls': nx x ny x nz cells, i fastest, cell (i, j, k) at flat index (k * ny + j) * nx + i, nx * ny * nz in 1 .. 2^22.  A cell
+ * is in the mask iff its byte is not 0.  Two mask cells are adjacent iff they differ by at most 1 in every coordinate and by at most m in the sum of the
+ * absolute differences: connectivity 6 -> m = 1 (faces), 18 -> m = 2 (faces and edges), 26 -> m = 3 (faces, edges and corners).  Nothing wraps round the
+ * border.  A component is an equivalence class of the transitive closure of adjacency.  Outputs:
+ *   label[cell]   = the lowest flat index among the cells of its component (its representative: label[rep] == rep); -1 outside the mask
+ *   comp[cell]    = the rank of its component when the components are ordered by ascending representative, 0 .. n_components - 1; -1 outside the mask
+ *   n_components  = the number of components, the total even when cap is smaller (as mon_marching_cubes reports its counts)
+ *   table[c]      = one record per component c < min(n_components, cap): its representative, its number of cells and its inclusive bounding box
+ *                   lo <= (i, j, k) <= hi; the records from min(n_components, cap) on are not touched
+ * The result is a function of the mask, the shape and the connectivity alone: equal arguments give equal bits, whatever computes them.
+ * mon_label_components: the labelling of a host mask (mask[nx * ny * nz]) on `device`; comp, table and n_components may be NULL (table needs
+ * n_components).
+ * mon_scene_components_lattice: the object map's components over the lattice of mon_scene_query_lattice (the same points, sides, objects and passes).
+ *   region 0, occupied matter: the mask is !(sigma <= sigma_min), sigma that call's output bit for bit -- mon_scene_distance_lattice's mask (a NaN or
+ *     +inf sigma counts as occupied); clearance is ignored; dist must be NULL.  The table is the map's blobs: a main body and its floaters by size.
+ *   region 1, traversable space: the mask is dist > clearance, dist being mon_scene_distance_lattice's dist for the same arguments with max_dist = +inf,
+ *     bit for bit; clearance >= 0 and finite; clearance 0 gives exactly the free cells (under non-zero steps); a lattice without an occupied cell has
+ *     dist = +inf everywhere and is one component.  Two cell centres can be joined by a lattice path (of the chosen connectivity) along which a sphere of
+ *     radius clearance stays clear of every occupied cell centre iff their comp is equal and >= 0.
+ *   dist (region 1 only), sigma and owner are those calls' rows (owner: mon_scene_query_lattice's, an index into objs or -1), each copied home only when
+ *   asked for.  Mask, transform and labelling run on the device behind the query; one copy home, one synchronisation.
+ * Returns:
+ *   MON_ERR_ARG    everything mon_distance_transform / mon_scene_distance_lattice refuse for the arguments they share (mask, step3, origin3, objs or an
+ *                  element NULL; the shape; a non-finite step or origin; sigma_min; side; n_objs; devices); label NULL; table without n_components;
+ *                  connectivity not 6, 18 or 26; region not 0 or 1; region 1 with a negative or non-finite clearance; region 0 with dist -- all before
+ *                  any device work, the outputs untouched
+ *   MON_ERR_STATE  as mon_scene_query_lattice;   MON_ERR_NO_DEVICE  mon_label_components without a device */
+typedef struct mon_lattice_component { int32_t rep; uint32_t cells; int32_t lo[3]; int32_t hi[3]; } mon_lattice_component;   /* 32 bytes */
+int mon_label_components(int device, const uint8_t* mask, int nx, int ny, int nz, int connectivity,
+                         int32_t* label, int32_t* comp, mon_lattice_component* table, uint32_t cap, uint32_t* n_components);
+int mon_scene_components_lattice(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz,
+                                 float sigma_min, int region, float clearance, int connectivity,
+                                 int32_t* label, int32_t* comp, mon_lattice_component* table, uint32_t cap, uint32_t* n_components,
+                                 float* dist, float* sigma, int32_t* owner);
 /* Object pose refinement through the trained field (iNeRF-style): align the object with observed frames by following the gradient of a photometric,
  * silhouette and depth error with respect to the 6-DoF pose Tow.
  * Objective.  obs names frames of the object's dataset (FrameId) and pixel boxes inside them; the target of a pixel is that frame's rgb c*, its instance map
@@ -755,6 +792,12 @@ int mon_online_query_lattice(mon_online* mgr, const float* origin3, const float*
  * call for the clearance field, safe while the objects train. */
 int mon_online_distance_lattice(mon_online* mgr, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float max_dist,
                                 float* dist, int32_t* nearest, int32_t* nearest_owner, float* free_dist, float* sigma);
+/* mon_scene_components_lattice (side 1) over the same objects, with the same refusals; owner holds the manager's object indices.  A planner's call for
+ * reachability at a clearance and a mapper's for the blobs of the published map, safe while the objects train. */
+int mon_online_components_lattice(mon_online* mgr, const float* origin3, const float* step3, int nx, int ny, int nz,
+                                  float sigma_min, int region, float clearance, int connectivity,
+                                  int32_t* label, int32_t* comp, mon_lattice_component* table, uint32_t cap, uint32_t* n_components,
+                                  float* dist, float* sigma, int32_t* owner);
 /* mon_scene_query_gradients / mon_scene_cast_normals (side 1) over the same objects, with the same refusals.  owner, instance and hit_instance hold the
  * manager's object indices, and so does select: -1, or the index of an object with published weights; any other value is MON_ERR_ARG.
  * mon_online_cast_normals picks the objects once for both steps of its rule.  There is no online lattice form of the gradients: a caller forms the lattice

@@ -73,6 +73,8 @@ class SceneRay(C.Structure):
 
 
 SCENE_RAY_DTYPE = np.dtype([("o", np.float32, 3), ("t_max", np.float32), ("d", np.float32, 3), ("key", np.uint32)])
+# mon_lattice_component (include/mon_core.h): one record of a component table, 32 bytes
+LATTICE_COMPONENT_DTYPE = np.dtype([("rep", np.int32), ("cells", np.uint32), ("lo", np.int32, 3), ("hi", np.int32, 3)])
 
 
 class RelocResult(C.Structure):
@@ -217,6 +219,11 @@ _SIGS = {
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_online_distance_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_label_components": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mon_scene_components_lattice": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+            C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_online_components_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int,
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_object_query_gradients": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_scene_query_gradients": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -964,6 +971,14 @@ class OnlineManager:
         _check(lib().mon_online_distance_lattice(self.h, _p(o), _p(s), nx, ny, nz, float(sigma_min), float(max_dist), *[_p(a) for a in out]))
         return out
 
+    def components_lattice(self, origin, step, shape, sigma_min, region=0, clearance=0.0, connectivity=6, cap=None, rows=()):
+        """mon_online_components_lattice: scene_components_lattice on side 1 over every object with published weights (safe while they train); the
+        owner row holds the manager's object indices."""
+        o, s, nx, ny, nz = _lattice_args(origin, step, shape)
+        return _components_call(lambda *a: lib().mon_online_components_lattice(self.h, _p(o), _p(s), nx, ny, nz, float(sigma_min), int(region),
+                                                                                float(clearance), int(connectivity), *a),
+                                max(nx, 0) * max(ny, 0) * max(nz, 0), cap, rows)
+
     def query_gradients(self, world_xyz, level_weights=None, select=None):
         """mon_online_query_gradients: query_scene_gradients on side 1 over every object with published weights (safe while they train); owner and
         select hold the manager's object indices."""
@@ -1266,6 +1281,41 @@ def scene_distance_lattice(objects, origin, step, shape, sigma_min, max_dist=np.
     _check(lib().mon_scene_distance_lattice(_handles(objects), len(objects), int(side), _p(o), _p(s), nx, ny, nz, float(sigma_min), float(max_dist),
                                             *[_p(a) for a in out]))
     return out
+
+
+def _components_call(call, n, cap, rows):
+    """call(label, comp, table, cap, n_components, dist, sigma, owner) with fresh arrays of n cells; cap None: room for every component (n records);
+    rows: which of "dist", "sigma", "owner" to bring home.  -> (label, comp, table cut to the records written, n_components, {row: array})"""
+    assert set(rows) <= {"dist", "sigma", "owner"}, rows
+    cap = n if cap is None else int(cap)
+    label = np.empty(n, np.int32); comp = np.empty(n, np.int32); table = np.empty(min(cap, n), LATTICE_COMPONENT_DTYPE); nc = C.c_uint32(0)
+    opt = {k: np.empty(n, np.int32 if k == "owner" else np.float32) for k in rows}
+    _check(call(_p(label), _p(comp), _p(table), cap, C.byref(nc), *[_p(opt.get(k)) for k in ("dist", "sigma", "owner")]))
+    return label, comp, table[:min(nc.value, cap)], nc.value, opt
+
+
+def label_components(mask, connectivity=6, device=0, cap=None):
+    """mon_label_components: the connected components of a mask of shape (nz, ny, nx) (x fastest; a cell counts iff it is not 0) under 6-, 18- or
+    26-connectivity.  Returns (label, comp, table, n_components): label and comp of the mask's shape (the lowest flat index of the cell's component and
+    the component's rank by ascending representative; -1 outside the mask), table a structured array (LATTICE_COMPONENT_DTYPE: rep, cells, lo, hi) of
+    the first min(n_components, cap) components (cap None: all of them), n_components the total."""
+    m = np.ascontiguousarray(mask); assert m.ndim == 3, "mask of shape (nz, ny, nx)"
+    m = np.ascontiguousarray(m != 0, np.uint8); nz, ny, nx = m.shape
+    label, comp, table, nc, _ = _components_call(
+        lambda lab, cmp_, tab, cap_, n_, *_: lib().mon_label_components(int(device), _p(m), nx, ny, nz, int(connectivity), lab, cmp_, tab, cap_, n_),
+        m.size, cap, ())
+    return label.reshape(m.shape), comp.reshape(m.shape), table, nc
+
+
+def scene_components_lattice(objects, origin, step, shape, sigma_min, region=0, clearance=0.0, connectivity=6, side=0, cap=None, rows=()):
+    """mon_scene_components_lattice: the object map's connected components over the lattice of query_scene_lattice.  region 0: the occupied cells,
+    not (sigma <= sigma_min) -- the map's blobs; region 1: the cells a sphere of radius `clearance` may occupy, scene_distance_lattice's dist > clearance.
+    Returns (label, comp, table, n_components, rows), the first two of nx * ny * nz elements, as label_components'; rows = {name: array} for the names
+    asked for among "dist" (region 1 only), "sigma" and "owner"."""
+    o, s, nx, ny, nz = _lattice_args(origin, step, shape)
+    return _components_call(lambda *a: lib().mon_scene_components_lattice(_handles(objects), len(objects), int(side), _p(o), _p(s), nx, ny, nz,
+                                                                          float(sigma_min), int(region), float(clearance), int(connectivity), *a),
+                            max(nx, 0) * max(ny, 0) * max(nz, 0), cap, rows)
 
 
 def scene_point_rows(objects, world_xyz, k, side=0):

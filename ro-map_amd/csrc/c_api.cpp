@@ -171,6 +171,20 @@ int mon_scene_distance_lattice(mon_object* const* objs, size_t n_objs, int side,
     return scene_distance(ms.data(), n_objs, side, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, max_dist, dist, nearest, nearest_owner, free_dist, sigma,
                           nullptr);
 }
+int mon_label_components(int device, const uint8_t* mask, int nx, int ny, int nz, int connectivity, int32_t* label, int32_t* comp,
+        mon_lattice_component* table, uint32_t cap, uint32_t* n_components) {
+    { const int rc = label_components_check(mask, nx, ny, nz, connectivity, label, table, n_components); if (rc) return rc; }
+    return label_components(device, mask, nx, ny, nz, connectivity, label, comp, table, cap, n_components);
+}
+int mon_scene_components_lattice(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz,
+        float sigma_min, int region, float clearance, int connectivity, int32_t* label, int32_t* comp, mon_lattice_component* table, uint32_t cap,
+        uint32_t* n_components, float* dist, float* sigma, int32_t* owner) {
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_components_check(side, origin3, step3, nx, ny, nz, sigma_min, region, clearance, connectivity, label, table, n_components, dist)) ||
+        (rc = scene_models("scene_components", objs, n_objs, ms)) || (rc = scene_objects_check("scene_components", ms.data(), n_objs, false))) return rc;
+    return scene_components(ms.data(), n_objs, side, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, region, clearance, connectivity, label, comp, table,
+                            cap, n_components, dist, sigma, owner, nullptr);
+}
 int mon_object_query_gradients(mon_object* o, int side, const float* unit_xyz, size_t n, const float* level_weights, float* raw4, float* grad_unit) {
     { const int rc = object_gradients_check(side, unit_xyz, n, level_weights, grad_unit); if (rc) return rc; }
     REQUIRE(o, "object");

@@ -378,6 +378,16 @@ void launch_distance_mask(hipStream_t s, uint32_t n, const float* sigma, float s
 void launch_distance_passes(hipStream_t s, const uint8_t* occ, bool invert, uint32_t nx, uint32_t ny, uint32_t nz, const float* step3, float* v, int32_t* site);
 void launch_distance_finish(hipStream_t s, uint32_t n, const float* d2, const int32_t* site, float max_dist, const int32_t* owner, float* dist,
         int32_t* nearest, int32_t* nearest_owner);
+// Connected components (mon_label_components, mon_scene_components_lattice; kernels_components.hip).  launch_components: the mask occ[n] -> label[n] and
+// comp[n] (both required here), the count in meta[0] and the cap flag in meta[1] (meta: 2 words, cleared first; a flag other than 0 afterwards: a device
+// loop ran into its cap), the records of the components below cap in table (nullptr: none; room for min(cap, n) records).  scan: components_scan_words(n)
+// words.  connectivity is 6, 18 or 26 (checked by the caller).  launch_components_clear_mask: occ = dist > clearance.  launch_components_home: words
+// [0, n_words) of src -> dst, of the table's words (8 per record from word table_word on, table_cap records) only the records that were written.
+size_t components_scan_words(uint32_t n);
+void launch_components(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, int connectivity, int32_t* label, int32_t* comp,
+        uint32_t* scan, mon_lattice_component* table, uint32_t cap, uint32_t* meta);
+void launch_components_clear_mask(hipStream_t s, uint32_t n, const float* dist, float clearance, uint8_t* occ);
+void launch_components_home(hipStream_t s, const uint32_t* src, uint32_t* dst, uint32_t n_words, uint32_t table_word, uint32_t table_cap, const uint32_t* meta);
 // Pose refinement (mon_object_pose_loss / mon_object_refine_pose, kernels_pose.hip).  k_pose_rays: one record of 4 float4 per drawn ray from the pose in
 // device memory (pose[16], world -> object); k_pose_grad<shape>: loss and position gradient, one partial row of 8 floats {g, x x g, loss, 0} per workgroup
 // (pose_grad_grid of them); k_pose_update: the rows summed in a fixed order, x inv_n -> out[8 * it] = {loss, grad6, 0}, optionally the Adam step on pose.
@@ -757,6 +767,19 @@ int distance_transform(int device, const uint8_t* occupied, int nx, int ny, int 
 int scene_distance_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float max_dist, const float* dist);
 int scene_distance(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, float max_dist, float* dist, int32_t* nearest,
                    int32_t* nearest_owner, float* free_dist, float* sigma, const int32_t* ids);
+// Connected components (mon_label_components, mon_scene_components_lattice): label_components = the labelling of a host mask in buffers of its own
+// (MON_ERR_NO_DEVICE without a device, after its check).  scene_components = the lattice query with the mask !(sigma <= sigma_min) (region 0) or, behind
+// the untruncated distance transform of that mask, dist > clearance (region 1), and the labelling behind it on the device; every output but label may
+// be nullptr (table needs n_components; dist: region 1 only); ids as scene_points', applied to owner.  A device loop that ran into its cap: MON_ERR_STATE.
+int label_components_check(const uint8_t* mask, int nx, int ny, int nz, int connectivity, const int32_t* label, const mon_lattice_component* table,
+                           const uint32_t* n_components);
+int label_components(int device, const uint8_t* mask, int nx, int ny, int nz, int connectivity, int32_t* label, int32_t* comp, mon_lattice_component* table,
+                     uint32_t cap, uint32_t* n_components);
+int scene_components_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, int region, float clearance,
+                           int connectivity, const int32_t* label, const mon_lattice_component* table, const uint32_t* n_components, const float* dist);
+int scene_components(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, int region, float clearance, int connectivity,
+                     int32_t* label, int32_t* comp, mon_lattice_component* table, uint32_t cap, uint32_t* n_components, float* dist, float* sigma,
+                     int32_t* owner, const int32_t* ids);
 // Point gradients (mon_scene_query_gradients / _lattice_gradients, mon_object_query_gradients): the point queries' conventions, plus level_w (host, may be
 // nullptr = all 1: Lmax floats, object j reads its first L_j; the *_check judges the first, scene_gradients_weights_check the rest once the objects are
 // known) and select (host, [n] or nullptr: -1 or an index into ms).  rows (mon_debug_scene_gradient_rows) = object rows_k's rows, host array [n][16].

@@ -108,6 +108,7 @@ struct SceneWs {
     DevBuf<float> pts, rows;                                                      // scene_points: the points [n][3], a pass's rows [objects][cap][12]
     DevBuf<uint16_t> gfrag; DevBuf<float> lw; DevBuf<int32_t> sel;                // scene_gradients (rows of 16): full fragment images, weights [Lmax], select [n]
     DevBuf<uint8_t> docc; DevBuf<float> dv; DevBuf<int32_t> dsite;                // scene_distance: the mask [n], the passes' squared distances and sites [2][n]
+    DevBuf<uint32_t> cscan;                                                       // scene_components: the numbering's block sums (its mask is docc)
     std::vector<hipEvent_t> ev;
 };
 // what each object renders with on a side; the render grids are the objects' own per-side caches, built if stale (their skip counters stay as they are).
@@ -543,6 +544,23 @@ int distance_transform(int device, const uint8_t* occupied, int nx, int ny, int 
     if (nearest) std::memcpy(nearest, h_near.data(), 4 * n);
     return MON_OK;
 }
+// the lattice query's kernels as scene_distance and scene_components run them in front of their own: every pass's k_scene_points per object and its fold,
+// the five rows (sigma n_q | rgb 3 n_q | owner n_q | owner_sigma n_q | n_inside n_q) at the places given; rows: the pass's workspace [objects][cap][12]
+static void lattice_query_enqueue(hipStream_t s, Model* const* ms, size_t n, const ScenePoints& q, const SceneSide& sd, const std::vector<SceneSrc>& src,
+        float* rows, uint32_t cap, float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside) {
+    const uint32_t nq = (uint32_t)q.n, L = (uint32_t)n;
+    for (uint32_t p0 = 0; p0 < nq; p0 += cap) {
+        const uint32_t nc = std::min(cap, nq - p0);
+        for (size_t j = 0; j < n; ++j) {
+            Model& m = *ms[j];
+            ScenePointsArgs a{}; a.pts = nullptr; a.nx = (uint32_t)q.nx; a.ny = (uint32_t)q.ny; a.first = p0; a.n = nc;
+            for (int k = 0; k < 3; ++k) { a.origin[k] = q.origin[k]; a.step[k] = q.step[k]; }
+            a.rows = rows + j * (size_t)cap * 12;
+            launch_scene_points(s, m.lf, m.nd, sd.prm[j], m.oc, src[j].frag, p0 == 0u, true, a);
+        }
+        launch_scene_points_fold(s, nc, L, cap, rows, sigma + p0, rgb + 3 * (size_t)p0, owner + p0, owner_sigma + p0, n_inside + p0);
+    }
+}
 // q: a lattice (scene_lattice).  ids as scene_points', applied to nearest_owner.  max_dist truncates dist and free_dist alike.
 int scene_distance(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, float max_dist, float* dist, int32_t* nearest,
                    int32_t* nearest_owner, float* free_dist, float* sigma, const int32_t* ids) {
@@ -560,18 +578,7 @@ int scene_distance(Model* const* ms, size_t n, int side, const ScenePoints& q, f
         if ((rc = ws.rows.grow((size_t)L * cap * 12)) || (rc = ws.out.grow(out_floats)) || (rc = ws.h_out.grow(home_rows * n_q)) || (rc = ws.docc.grow(n_q)) ||
             (rc = ws.dv.grow(2 * n_q)) || (rc = ws.dsite.grow(2 * n_q))) return rc; }
     float* o = ws.out.p; int32_t* o_owner = reinterpret_cast<int32_t*>(o + 8 * n_q);
-    for (uint32_t p0 = 0; p0 < nq; p0 += cap) {
-        const uint32_t nc = std::min(cap, nq - p0);
-        for (size_t j = 0; j < n; ++j) {
-            Model& m = *ms[j];
-            ScenePointsArgs a{}; a.pts = nullptr; a.nx = (uint32_t)q.nx; a.ny = (uint32_t)q.ny; a.first = p0; a.n = nc;
-            for (int k = 0; k < 3; ++k) { a.origin[k] = q.origin[k]; a.step[k] = q.step[k]; }
-            a.rows = ws.rows.p + j * (size_t)cap * 12;
-            launch_scene_points(s, m.lf, m.nd, sd.prm[j], m.oc, src[j].frag, p0 == 0u, true, a);
-        }
-        launch_scene_points_fold(s, nc, L, cap, ws.rows.p, o + p0, o + 5 * n_q + 3 * (size_t)p0, o_owner + p0, o + 9 * n_q + p0,
-                reinterpret_cast<uint32_t*>(o + 10 * n_q) + p0);
-    }
+    lattice_query_enqueue(s, ms, n, q, sd, src, ws.rows.p, cap, o, o + 5 * n_q, o_owner, o + 9 * n_q, reinterpret_cast<uint32_t*>(o + 10 * n_q));
     launch_distance_mask(s, nq, o, sigma_min, ws.docc.p);
     launch_distance_passes(s, ws.docc.p, false, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, q.step, ws.dv.p, ws.dsite.p);
     launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, max_dist, o_owner, o + n_q, nearest ? reinterpret_cast<int32_t*>(o + 2 * n_q) : nullptr,
@@ -589,6 +596,110 @@ int scene_distance(Model* const* ms, size_t n, int side, const ScenePoints& q, f
     if (nearest) std::memcpy(nearest, h + 2 * n_q, 4 * n_q);
     if (nearest_owner) scene_instances_home(nearest_owner, h + 3 * n_q, n_q, ids);
     if (free_dist) std::memcpy(free_dist, h + 4 * n_q, 4 * n_q);
+    return MON_OK;
+}
+
+// ---- connected components (mon_label_components, mon_scene_components_lattice): which cells belong together.  scene_components is
+// scene_distance's sibling: the lattice query's kernels, k_distance_mask, for region 1 the untruncated transform and the mask dist > clearance (written
+// over the first mask, which the passes have consumed), the labelling (launch_components), one copy home (k_cc_home: the records that were written, not
+// the table's whole room) and one synchronisation.  Per cell the side's workspace keeps the mask (1 B, shared with the distance call) and, in the output
+// area, label and comp (8 B); region 1 also uses the distance call's passes (16 B).  The numbering's block sums are 4 B per 256 cells.
+static int components_outputs_check(const char* what, int connectivity, const int32_t* label, const mon_lattice_component* table, const uint32_t* n_components) {
+    REQUIRE_ARG(what, label, "label");
+    if (table && !n_components) { set_error("%s: a table without n_components (the count says how many records were written)", what); return MON_ERR_ARG; }
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26) { set_error("%s: connectivity %d (6, 18 or 26)", what, connectivity); return MON_ERR_ARG; }
+    return MON_OK;
+}
+int label_components_check(const uint8_t* mask, int nx, int ny, int nz, int connectivity, const int32_t* label, const mon_lattice_component* table,
+                           const uint32_t* n_components) {
+    REQUIRE_ARG("label_components", mask, "mask");
+    { const int rc = lattice_dims_check("label_components", nx, ny, nz); if (rc) return rc; }
+    return components_outputs_check("label_components", connectivity, label, table, n_components);
+}
+int scene_components_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, int region, float clearance,
+                           int connectivity, const int32_t* label, const mon_lattice_component* table, const uint32_t* n_components, const float* dist) {
+    { const int rc = lattice_shape_check("scene_components", origin3, step3, nx, ny, nz); if (rc) return rc; }
+    { const int rc = side_check("scene_components", side); if (rc) return rc; }
+    if (!std::isfinite(sigma_min) || sigma_min < 0.f) { set_error("scene_components: sigma_min %g (finite, >= 0)", (double)sigma_min); return MON_ERR_ARG; }
+    if (region != 0 && region != 1) { set_error("scene_components: region %d (0: occupied matter, 1: traversable space)", region); return MON_ERR_ARG; }
+    if (region == 1 && (!std::isfinite(clearance) || clearance < 0.f)) { set_error("scene_components: clearance %g (finite, >= 0)", (double)clearance);
+        return MON_ERR_ARG; }
+    if (region == 0 && dist) { set_error("scene_components: dist belongs to region 1 (region 0 runs no distance transform)"); return MON_ERR_ARG; }
+    return components_outputs_check("scene_components", connectivity, label, table, n_components);
+}
+static int components_flag_check(const char* what, uint32_t flag) {
+    if (flag) { set_error("%s: a device loop ran into its cap (flag %#x); no output was written", what, flag); return MON_ERR_STATE; }
+    return MON_OK;
+}
+// mon_label_components: the labelling alone on a host mask, in buffers of its own on the device's default stream.
+// w: label n | comp n | meta 8 (n_components, the cap flag) | the table's records, 8 words each | the numbering's block sums
+int label_components(int device, const uint8_t* mask, int nx, int ny, int nz, int connectivity, int32_t* label, int32_t* comp, mon_lattice_component* table,
+                     uint32_t cap, uint32_t* n_components) {
+    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available"); return MON_ERR_NO_DEVICE; }
+    HIPCHECK(use_device(device));
+    const size_t n = (size_t)nx * ny * nz, tcap = table ? std::min((size_t)cap, n) : 0, front = 2 * n + 8;
+    DevBuf<uint8_t> occ; DevBuf<uint32_t> w;
+    { int rc; if ((rc = occ.grow(n)) || (rc = w.grow(front + 8 * tcap + components_scan_words((uint32_t)n)))) return rc; }
+    HIPCHECK(hipMemcpy(occ.p, mask, n, hipMemcpyHostToDevice));
+    int32_t* d_label = reinterpret_cast<int32_t*>(w.p); uint32_t* d_meta = w.p + 2 * n;
+    launch_components(nullptr, occ.p, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, connectivity, d_label, d_label + n, w.p + front + 8 * tcap,
+            tcap ? reinterpret_cast<mon_lattice_component*>(w.p + front) : nullptr, (uint32_t)tcap, d_meta);
+    HIPCHECK(hipGetLastError());
+    std::vector<uint32_t> h(front);                                                 // (the caller's arrays are written only once everything has succeeded)
+    HIPCHECK(hipMemcpy(h.data(), w.p, 4 * front, hipMemcpyDeviceToHost));
+    { const int rc = components_flag_check("label_components", h[2 * n + 1]); if (rc) return rc; }
+    const size_t used = std::min((size_t)h[2 * n], tcap);
+    std::vector<uint32_t> h_table(8 * used);
+    if (used) HIPCHECK(hipMemcpy(h_table.data(), w.p + front, 32 * used, hipMemcpyDeviceToHost));
+    std::memcpy(label, h.data(), 4 * n);
+    if (comp) std::memcpy(comp, h.data() + n, 4 * n);
+    if (used) std::memcpy(table, h_table.data(), 32 * used);
+    if (n_components) *n_components = h[2 * n];
+    return MON_OK;
+}
+// q: a lattice (scene_lattice).  ids as scene_points', applied to owner.
+int scene_components(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, int region, float clearance, int connectivity,
+                     int32_t* label, int32_t* comp, mon_lattice_component* table, uint32_t cap, uint32_t* n_components, float* dist, float* sigma,
+                     int32_t* owner, const int32_t* ids) {
+    { const int rc = scene_points_state_check("scene_components", ms, n, side); if (rc) return rc; }
+    const int device = ms[0]->device;
+    HIPCHECK(use_device(device));
+    const size_t n_q = q.n; const uint32_t nq = (uint32_t)n_q, pass = std::min(nq, kScenePointsPass), L = (uint32_t)n;
+    SceneWs& ws = side_ws<SceneWs>(device, side);
+    SceneSide sd; { const int rc = sd.enter(ms, n, side, ws.mu, ws.ev); if (rc) return rc; }
+    const hipStream_t s = sd.s;
+    const std::vector<SceneSrc> src = scene_sources(ms, n, side, sd, false);
+    // the output area, what may go home from the front: label | comp | meta 8 | the table's records | (region 1: dist) | sigma | owner, then rgb 3 n_q |
+    // owner_sigma | n_inside
+    const size_t tcap = table ? std::min((size_t)cap, n_q) : 0, front = 2 * n_q + 8, rows0 = front + 8 * tcap, n_opt = region == 1 ? 3 : 2;
+    const size_t home = rows0 + (owner ? n_opt : sigma ? n_opt - 1 : dist ? 1 : 0) * n_q;
+    {   int rc;
+        if ((rc = ws.rows.grow((size_t)L * pass * 12)) || (rc = ws.out.grow(rows0 + (n_opt + 5) * n_q)) || (rc = ws.h_out.grow(home)) || (rc = ws.docc.grow(n_q)) ||
+            (rc = ws.cscan.grow(components_scan_words(nq))) || (region == 1 && ((rc = ws.dv.grow(2 * n_q)) || (rc = ws.dsite.grow(2 * n_q))))) return rc; }
+    float* o = ws.out.p; uint32_t* o_meta = reinterpret_cast<uint32_t*>(o + 2 * n_q);
+    float* o_dist = o + rows0; float* o_sigma = o + rows0 + (n_opt - 2) * n_q; int32_t* o_owner = reinterpret_cast<int32_t*>(o_sigma + n_q);
+    float* o_rest = o_sigma + 2 * n_q;
+    lattice_query_enqueue(s, ms, n, q, sd, src, ws.rows.p, pass, o_sigma, o_rest, o_owner, o_rest + 3 * n_q, reinterpret_cast<uint32_t*>(o_rest + 4 * n_q));
+    launch_distance_mask(s, nq, o_sigma, sigma_min, ws.docc.p);
+    if (region == 1) {
+        launch_distance_passes(s, ws.docc.p, false, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, q.step, ws.dv.p, ws.dsite.p);
+        launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, INFINITY, nullptr, o_dist, nullptr, nullptr);
+        launch_components_clear_mask(s, nq, o_dist, clearance, ws.docc.p);
+    }
+    launch_components(s, ws.docc.p, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, connectivity, reinterpret_cast<int32_t*>(o), reinterpret_cast<int32_t*>(o + n_q),
+            ws.cscan.p, tcap ? reinterpret_cast<mon_lattice_component*>(o + front) : nullptr, (uint32_t)tcap, o_meta);
+    launch_components_home(s, reinterpret_cast<const uint32_t*>(o), reinterpret_cast<uint32_t*>(ws.h_out.p), (uint32_t)home, (uint32_t)front, (uint32_t)tcap, o_meta);
+    HIPCHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    const float* h = ws.h_out.p; const uint32_t* h_meta = reinterpret_cast<const uint32_t*>(h + 2 * n_q);
+    { const int rc = components_flag_check("scene_components", h_meta[1]); if (rc) return rc; }
+    std::memcpy(label, h, 4 * n_q);
+    if (comp) std::memcpy(comp, h + n_q, 4 * n_q);
+    if (table) std::memcpy(table, h + front, 32 * std::min((size_t)h_meta[0], tcap));
+    if (n_components) *n_components = h_meta[0];
+    if (dist) std::memcpy(dist, h + rows0, 4 * n_q);
+    if (sigma) std::memcpy(sigma, h + rows0 + (n_opt - 2) * n_q, 4 * n_q);
+    if (owner) scene_instances_home(owner, h + rows0 + (n_opt - 1) * n_q, n_q, ids);
     return MON_OK;
 }
 
