@@ -1,5 +1,5 @@
 // c_api.cpp -- extern "C" surface declared in include/mon_core.h.  The scene and pose routes enter through the boundary of model.h: their checks are in
-// scene.cpp and pose.cpp, shared with manager.cpp and diag.cpp.
+// scene.cpp, scene_field.cpp, scene_pose.cpp and pose.cpp, shared with manager.cpp and diag.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>

@@ -1,8 +1,9 @@
-// model_internal.h -- what model.cpp, train.cpp, pose.cpp, scene.cpp and checkpoint.cpp need from each other and nobody else needs (c_api.cpp, manager.cpp and
+// model_internal.h -- what model.cpp, train.cpp, pose.cpp, scene.cpp, scene_field.cpp, scene_pose.cpp and checkpoint.cpp need from each other and nobody else needs (c_api.cpp, manager.cpp and
 // diag.cpp go through model.h).
 #pragma once
 #include <atomic>
 #include <chrono>
+#include <map>
 #include <mutex>
 #include <vector>
 #include "model.h"
@@ -104,5 +105,56 @@ void pose_ws_free(Model& m);                   // pose.cpp: the object's pose re
 // pose.cpp: box i of a pose call names a frame the dataset holds and lies inside it; its pixels join `total` (at most 64 kPoseMaxRays).  `what`: the message
 // prefix ("pose", "scene pose")
 int pose_box_check(const char* what, const Dataset& ds, const mon_frame_bbox& b, size_t i, uint64_t& total);
+
+// ---- scene.cpp: what the files of the scene routes (scene.cpp, scene_field.cpp, scene_pose.cpp) share
+int side_check(const char* what, int side);
+// every MON_ERR_STATE of a scene call that needs no device work (the routes run it themselves: it is their own question, asked once).  lists = false (the
+// field queries): nothing is sampled or jittered, so neither the sample count nor the XORWOW render mode matters
+int scene_state_check(const char* what, Model* const* ms, size_t n, int side, bool lists = true);
+// Entering a side of a scene: the weights every object is read from, their stamps, the stream of the call.  Side 1: the shared inference stream under
+// its device lock, every object's snapshot pinned.  Side 0: the train side as model_render picks it (EMA once trained, brought up to date), object 0's train
+// stream after every object's pending work (the workspace's events `ev`).  Lock order: the device's inference lock, then the workspace's `ws_mu`;
+// InferState::mu only inside SnapshotPin::take.  Holds the locks and the pins until it goes (after the call's stream has been synchronised).
+struct SceneSide {
+    hipStream_t s = nullptr; std::vector<const uint16_t*> prm; std::vector<uint64_t> epoch;
+    std::unique_lock<std::mutex> dev_lock; std::vector<SnapshotPin> pins; std::unique_lock<std::mutex> ws_lock;
+    int enter(Model* const* ms, size_t n, int side, std::mutex& ws_mu, std::vector<hipEvent_t>& ev);
+};
+// the workspace of type W of a device and side: made on first use, never freed
+template <class W> W& side_ws(int device, int side) {
+    static std::mutex mu; static std::map<std::pair<int, int>, W*> all;
+    std::lock_guard<std::mutex> l(mu); W*& w = all[{ device, side }]; if (!w) w = new W(); return *w;
+}
+// The workspace of the render, the list routes and the field queries.  Per device and side, grow-only, never freed (like the tile workspaces): the lists of
+// one chunk for every object, the call's outputs, their pinned staging, the events that order the objects' streams in front of side 0's call.  A call holds
+// `mu` until its stream has been synchronised, so the routes of one side take turns.
+struct SceneWs {
+    std::mutex mu;
+    DevBuf<float> t, attr; DevBuf<uint32_t> cnt;                                  // [lists][cap][kSceneListLen] t, float4 attr; [lists][cap]
+    DevBuf<float> out; PinnedBuf<float> h_out;                                    // rgb 3n | depth n | opacity n | instance n (int32)
+    DevBuf<mon_scene_query> q; DevBuf<float> poses; DevBuf<uint32_t> keys;        // scene_probe: the queries, the poses [n_poses][16], a pass's keys [cap]
+    DevBuf<mon_scene_ray> rays; DevBuf<float> entry;                              // scene_cast: the rays, a pass's box entries [lists][cap]
+    DevBuf<float> pts, rows;                                                      // field queries: the points [n][3], a pass's rows [objects][cap][12 or 16]
+    DevBuf<uint16_t> gfrag; DevBuf<float> lw; DevBuf<int32_t> sel;                // gradients (rows of 16): full fragment images, weights [Lmax], select [n]
+    DevBuf<uint8_t> docc; DevBuf<float> dv; DevBuf<int32_t> dsite;                // scene_distance: the mask [n], the passes' squared distances and sites [2][n]
+    DevBuf<uint32_t> cscan;                                                       // scene_components: the numbering's block sums (its mask is docc)
+    std::vector<hipEvent_t> ev;
+};
+// what each object renders with on a side; bits: its render grid (nullptr: none, or a call that consults no skipping)
+struct SceneSrc { BatchPtrs* b; uint16_t* frag; const uint32_t* bits; };
+// One call of a route over SceneWs, from its state check to its synchronisation.  enter: the state check, the device, the side's workspace and its locks
+// (SceneSide), every object's sources -- lists: the render, the probe and the cast, whose render grids are the objects' own per-side caches, built if stale
+// (their skip counters stay as they are); not lists: the field queries, which look at no grid.  grow_lists: the list workspace of `cap` rays per object.
+// finish: one synchronisation and the launches' error; home: ws.out's first `floats` to the pinned staging (a copy kernel on the call's stream, as the
+// snapshot render does), then finish.  The locks go with the object, after that.
+struct SceneCall {
+    SceneWs* ws = nullptr; SceneSide sd; std::vector<SceneSrc> src; hipStream_t s = nullptr;
+    int enter(const char* what, Model* const* ms, size_t n, int side, bool lists);
+    int grow_lists(size_t n, uint32_t cap);
+    int finish();
+    int home(size_t floats);
+};
+// an instance row home: the call's list indices, or the caller's ids for them
+void scene_instances_home(int32_t* out, const float* row, size_t n, const int32_t* ids);
 
 }  // namespace mon

@@ -1,0 +1,444 @@
+// scene_field.cpp -- the field queries: the object map asked at places instead of along rays.  Points and lattices (density, colour, owner), their
+// gradients and normals, normals at ray hits, distance fields and connected components over a lattice.  One host chain: a SceneCall
+// (scene.cpp) without lists or grids, the passes of field_passes_enqueue, each route's own kernels behind them, one copy home and one synchronisation.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include "model_internal.h"
+
+namespace mon {
+// ---- what the routes ask of their arguments without an object (mon_scene_query_points, mon_scene_query_lattice, mon_object_query_points, mon_lattice_points)
+static int points_outputs_check(const char* what, int side, const float* sigma) {
+    REQUIRE_ARG(what, sigma, "sigma");
+    return side_check(what, side);
+}
+int scene_points_check(int side, const float* xyz, size_t n, const float* sigma) {
+    REQUIRE_ARG("scene_points", xyz, "points");
+    { const int rc = points_outputs_check("scene_points", side, sigma); if (rc) return rc; }
+    if (n == 0 || n > kSceneProbeMaxQueries) { set_error("scene_points: %zu points (1 to %u)", n, kSceneProbeMaxQueries); return MON_ERR_ARG; }
+    for (size_t i = 0; i < 3 * n; ++i) if (!std::isfinite(xyz[i])) { set_error("scene_points: point %zu is not finite", i / 3); return MON_ERR_ARG; }
+    return MON_OK;
+}
+// the lattice's shape alone (mon_lattice_points, which has no side and no outputs) ...
+static int lattice_dims_check(const char* what, int nx, int ny, int nz) {
+    if (nx < 1 || ny < 1 || nz < 1) { set_error("%s: lattice %d x %d x %d (each at least 1)", what, nx, ny, nz); return MON_ERR_ARG; }
+    // (each factor bounded before it is multiplied: three ints of up to 2^31 - 1 wrap a 64-bit product)
+    const uint64_t mx = kSceneProbeMaxQueries;
+    if ((uint64_t)nx > mx || (uint64_t)ny > mx / (uint64_t)nx || (uint64_t)nz > mx / ((uint64_t)nx * (uint64_t)ny)) { set_error("%s: lattice %d x %d x %d has more than %u points", what, nx, ny, nz,
+        kSceneProbeMaxQueries); return MON_ERR_ARG; }
+    return MON_OK;
+}
+static int lattice_shape_check(const char* what, const float* origin3, const float* step3, int nx, int ny, int nz) {
+    REQUIRE_ARG(what, origin3, "origin"); REQUIRE_ARG(what, step3, "step");
+    { const int rc = lattice_dims_check(what, nx, ny, nz); if (rc) return rc; }
+    const int dims[3] = { nx, ny, nz };
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(origin3[a]) || !std::isfinite(step3[a])) { set_error("%s: origin or step is not finite", what); return MON_ERR_ARG; }
+        // (fmaf is monotone in the index: the far end is finite iff every point of the axis is)
+        if (!std::isfinite(std::fmaf((float)(dims[a] - 1), step3[a], origin3[a]))) { set_error("%s: the lattice leaves the finite floats on axis %d", what, a);
+            return MON_ERR_ARG; }
+    }
+    return MON_OK;
+}
+// ... and the query on it
+int scene_lattice_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, const float* sigma) {
+    { const int rc = lattice_shape_check("scene_lattice", origin3, step3, nx, ny, nz); if (rc) return rc; }
+    return points_outputs_check("scene_lattice", side, sigma);
+}
+// mon_lattice_points: the floats k_scene_points forms from a lattice index, on the host (one fmaf per coordinate, ix fastest)
+int scene_lattice_points(const float* origin3, const float* step3, int nx, int ny, int nz, float* xyz_out) {
+    { const int rc = lattice_shape_check("lattice_points", origin3, step3, nx, ny, nz); if (rc) return rc; }
+    REQUIRE_ARG("lattice_points", xyz_out, "xyz_out");
+    float* o = xyz_out;
+    for (int iz = 0; iz < nz; ++iz) for (int iy = 0; iy < ny; ++iy) for (int ix = 0; ix < nx; ++ix, o += 3) {
+        o[0] = std::fmaf((float)ix, step3[0], origin3[0]); o[1] = std::fmaf((float)iy, step3[1], origin3[1]); o[2] = std::fmaf((float)iz, step3[2], origin3[2]); }
+    return MON_OK;
+}
+
+// ---- the chain.  Per pass of at most kScenePointsPass points every object's point kernel writes its rows [objects][cap][width] -- k_scene_points: 12 floats
+// (u[3], inside, raw4, sigma, r, g, b); k_scene_point_grads: 16 (the same twelve, g[3], 0) -- then the fold writes the pass's slice of the output rows (sigma
+// | rgb 3 | owner | owner_sigma | n_inside, the gradient fold also grad_log 3 | grad_sigma 3 | normal 3).  Everything is enqueued at once; the outputs go home
+// through the pinned staging with one synchronisation.  Render grids are not consulted (nothing is skipped), and neither the sample count nor the XORWOW
+// render mode matters: nothing is sampled or jittered.
+// The points of one pass: kRenderChunkRays, as the other scene routes.  A variant build (tools/variant_build.sh <tag> -DMON_POINTS_PASS=n) takes another
+// size for measurements (tools/scene_points_timing.py: a pass of 16 384 points is a grid of 64 workgroups); outputs do not depend on it.
+#ifndef MON_POINTS_PASS
+#define MON_POINTS_PASS kRenderChunkRays
+#endif
+constexpr uint32_t kScenePointsPass = MON_POINTS_PASS;
+// A route's output area, described once: rows taken in order, each `width` floats per point.  The offsets serve the device pointers the kernels get (into
+// ws.out) and the unpacking (from the pinned staging) alike; a route sends home a prefix of its area.
+struct Area {
+    size_t n_q, end = 0;
+    size_t take(size_t floats) { const size_t at = end; end += floats; return at; }
+    size_t row(size_t width = 1) { return take(width * n_q); }
+};
+// where a route keeps the fold's output rows (grad_log, grad_sigma, normal: the gradient fold's)
+struct FoldRows { size_t sigma, rgb, owner, owner_sigma, n_inside, grad_log, grad_sigma, normal; };
+// what the gradient routes take beside the points: the caller's level weights (nullptr: ones) and select (may be nullptr), in ws.lw and ws.sel for the
+// kernels; every object's FULL fragment image at frag_off[j] of ws.gfrag (the backward reads the transposed matrices; the objects' own render images hold
+// the forward set only and are left alone)
+struct FieldGrads { const float* level_w; const int32_t* select; std::vector<size_t> frag_off; };
+// the passes' workspace: a pass's rows and, for a list, its points on the device
+static int field_passes_prepare(const SceneCall& c, size_t n, const ScenePoints& q, uint32_t cap, uint32_t width) {
+    SceneWs& ws = *c.ws; int rc;
+    if ((rc = ws.rows.grow(n * (size_t)cap * width)) || (q.xyz && (rc = ws.pts.grow(3 * q.n)))) return rc;
+    if (q.xyz) HIPCHECK(hipMemcpyAsync(ws.pts.p, q.xyz, 12 * q.n, hipMemcpyHostToDevice, c.s));
+    return MON_OK;
+}
+// The passes of every field query: q.xyz: the list ([q.n][3]; `world` false: unit-cube points of the one object), or nullptr: the lattice q.origin, q.step,
+// q.nx x q.ny x q.nz (q.n its points).  g: the gradient kernels and rows of 16, nullptr: the forward kernels and rows of 12.  f: the fold's rows in ws.out.
+// dump (may be nullptr): where in ws.out object rows_k's rows of every point go, [q.n][width].
+static void field_passes_enqueue(const SceneCall& c, Model* const* ms, size_t n, const ScenePoints& q, bool world, uint32_t cap, const FoldRows& f,
+                                 const FieldGrads* g, size_t rows_k, float* dump) {
+    SceneWs& ws = *c.ws; const hipStream_t s = c.s; float* o = ws.out.p;
+    const uint32_t nq = (uint32_t)q.n, L = (uint32_t)n, width = g ? 16u : 12u;
+    for (uint32_t p0 = 0; p0 < nq; p0 += cap) {
+        const uint32_t nc = std::min(cap, nq - p0);
+        for (size_t j = 0; j < n; ++j) {
+            Model& m = *ms[j];
+            ScenePointsArgs a{}; a.pts = q.xyz ? ws.pts.p + 3 * (size_t)p0 : nullptr; a.nx = (uint32_t)q.nx; a.ny = (uint32_t)q.ny; a.first = p0; a.n = nc;
+            for (int k = 0; k < 3; ++k) { a.origin[k] = q.origin[k]; a.step[k] = q.step[k]; }
+            a.rows = ws.rows.p + j * (size_t)cap * width;
+            if (g) launch_scene_point_grads(s, m.lf, m.nd, c.sd.prm[j], m.oc, ws.gfrag.p + g->frag_off[j], p0 == 0u, world, a, ws.lw.p);
+            else launch_scene_points(s, m.lf, m.nd, c.sd.prm[j], m.oc, c.src[j].frag, p0 == 0u, world, a);
+        }
+        float* sigma = o + f.sigma + p0; float* rgb = o + f.rgb + 3 * (size_t)p0; int32_t* owner = reinterpret_cast<int32_t*>(o + f.owner) + p0;
+        float* owner_sigma = o + f.owner_sigma + p0; uint32_t* n_inside = reinterpret_cast<uint32_t*>(o + f.n_inside) + p0;
+        if (g) launch_scene_gradients_fold(s, nc, L, cap, ws.rows.p, g->select ? ws.sel.p + p0 : nullptr, sigma, rgb, owner, owner_sigma, n_inside,
+                o + f.grad_log + 3 * (size_t)p0, o + f.grad_sigma + 3 * (size_t)p0, o + f.normal + 3 * (size_t)p0);
+        else launch_scene_points_fold(s, nc, L, cap, ws.rows.p, sigma, rgb, owner, owner_sigma, n_inside);
+        if (dump) launch_copy_params(s, reinterpret_cast<const uint16_t*>(ws.rows.p + rows_k * (size_t)cap * width),
+                reinterpret_cast<uint16_t*>(dump + width * (size_t)p0), 2u * width * nc);
+    }
+}
+
+// ---- point queries and point gradients (mon_scene_query_points, _lattice, _gradients, _lattice_gradients, mon_object_query_points, _gradients; DESIGN.md
+// 3.4c-4, 3.4c-5): the chain and nothing behind it.  The host arrays of a call, each may be nullptr
+struct FieldOut { float* sigma; float* rgb; int32_t* owner; float* owner_sigma; uint32_t* n_inside; float* grad_log; float* grad_sigma; float* normal; };
+// rows (the debug row dumps, mon_object_query_points, mon_object_query_gradients; may be nullptr) = object rows_k's rows of every point, host array
+// [q.n][12], with g [q.n][16].
+static int scene_field_run(const char* what, Model* const* ms, size_t n, int side, const ScenePoints& q, bool world, FieldGrads* g, const FieldOut& out,
+                           const int32_t* ids, size_t rows_k, float* rows) {
+    SceneCall c; { const int rc = c.enter(what, ms, n, side, false); if (rc) return rc; }
+    SceneWs& ws = *c.ws; const hipStream_t s = c.s;
+    const size_t n_q = q.n; const uint32_t cap = std::min((uint32_t)n_q, kScenePointsPass), width = g ? 16u : 12u;
+    // the output area: [the dumped rows |] the fold's rows (the dumped rows first: every piece copied stays 16-byte aligned)
+    Area A{ n_q }; const size_t r_dump = A.take(rows ? width * n_q : 0);
+    FoldRows f{}; f.sigma = A.row(); f.rgb = A.row(3); f.owner = A.row(); f.owner_sigma = A.row(); f.n_inside = A.row();
+    if (g) { f.grad_log = A.row(3); f.grad_sigma = A.row(3); f.normal = A.row(3); }
+    { int rc; if ((rc = field_passes_prepare(c, n, q, cap, width)) || (rc = ws.out.grow(A.end)) || (rc = ws.h_out.grow(A.end))) return rc; }
+    std::vector<float> ones;
+    if (g) {
+        const int Lmax = scene_levels(ms, n).Lmax;
+        g->frag_off.assign(n + 1, 0);
+        for (size_t j = 0; j < n; ++j) { const NetDims& nd = ms[j]->nd; const FragDims fd{ nd.Epad, nd.W, nd.NH, nd.L }; g->frag_off[j + 1] = g->frag_off[j] + (size_t)fd.N_FRAGS() * 512; }
+        if (!g->level_w) ones.assign((size_t)Lmax, 1.f);
+        { int rc; if ((rc = ws.gfrag.grow(g->frag_off[n])) || (rc = ws.lw.grow((size_t)Lmax)) || (g->select && (rc = ws.sel.grow(n_q)))) return rc; }
+        if (g->select) HIPCHECK(hipMemcpyAsync(ws.sel.p, g->select, 4 * n_q, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(ws.lw.p, g->level_w ? g->level_w : ones.data(), 4 * (size_t)Lmax, hipMemcpyHostToDevice, s));
+    }
+    field_passes_enqueue(c, ms, n, q, world, cap, f, g, rows_k, rows ? ws.out.p + r_dump : nullptr);
+    { const int rc = c.home(A.end); if (rc) return rc; }
+    const float* h = ws.h_out.p;
+    if (rows) std::memcpy(rows, h + r_dump, 4 * width * n_q);
+    if (out.sigma) std::memcpy(out.sigma, h + f.sigma, 4 * n_q);
+    if (out.rgb) std::memcpy(out.rgb, h + f.rgb, 12 * n_q);
+    scene_instances_home(out.owner, h + f.owner, n_q, ids);
+    if (out.owner_sigma) std::memcpy(out.owner_sigma, h + f.owner_sigma, 4 * n_q);
+    if (out.n_inside) std::memcpy(out.n_inside, h + f.n_inside, 4 * n_q);
+    if (out.grad_log) std::memcpy(out.grad_log, h + f.grad_log, 12 * n_q);
+    if (out.grad_sigma) std::memcpy(out.grad_sigma, h + f.grad_sigma, 12 * n_q);
+    if (out.normal) std::memcpy(out.normal, h + f.normal, 12 * n_q);
+    return MON_OK;
+}
+int scene_points(Model* const* ms, size_t n, int side, const ScenePoints& q, float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside,
+                 const int32_t* ids, size_t rows_k, float* rows) {
+    const FieldOut out{ sigma, rgb, owner, owner_sigma, n_inside, nullptr, nullptr, nullptr };
+    return scene_field_run(q.xyz ? "scene_points" : "scene_lattice", ms, n, side, q, true, nullptr, out, ids, rows_k, rows);
+}
+// mon_object_query_points: the same kernel with the transform switched off, on points of the object's unit cube; raw4 out of its rows
+int object_points_check(int side, const float* unit_xyz, size_t n, const float* raw4) {
+    REQUIRE_ARG("object_points", unit_xyz, "points"); REQUIRE_ARG("object_points", raw4, "raw4");
+    { const int rc = side_check("object_points", side); if (rc) return rc; }
+    if (n == 0 || n > kSceneProbeMaxQueries) { set_error("object_points: %zu points (1 to %u)", n, kSceneProbeMaxQueries); return MON_ERR_ARG; }
+    for (size_t i = 0; i < 3 * n; ++i) if (!(unit_xyz[i] >= 0.f && unit_xyz[i] <= 1.f)) { set_error("object_points: point %zu lies outside the unit cube", i / 3);
+        return MON_ERR_ARG; }
+    return MON_OK;
+}
+int object_points(Model& m, int side, const float* unit_xyz, size_t n, float* raw4) {
+    Model* ms[1] = { &m };
+    ScenePoints q{}; q.xyz = unit_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    std::vector<float> rows(12 * n);
+    const int rc = scene_field_run("object_points", ms, 1, side, q, false, nullptr, FieldOut{}, nullptr, 0, rows.data());
+    if (rc) return rc;
+    for (size_t i = 0; i < n; ++i) std::memcpy(raw4 + 4 * i, rows.data() + 12 * i + 4, 16);
+    return MON_OK;
+}
+
+// ---- what the gradient routes ask of their arguments.
+// What can be judged without an object: the points as scene_points_check judges them, the required outputs, select's range (n_objs is an argument) and
+// the first weight (every object has at least one level, so level_weights[0] is always read); the other weights need Lmax: scene_gradients_weights_check.
+static int weight_value_check(const char* what, const float* w, int l) {
+    if (!std::isfinite(w[l]) || w[l] < 0.f) { set_error("%s: level weight %d is %g (finite, >= 0)", what, l, (double)w[l]); return MON_ERR_ARG; }
+    return MON_OK;
+}
+static int gradients_args_check(const char* what, const float* level_w, const int32_t* select, size_t n_pts, size_t n_objs, const float* grad_log) {
+    REQUIRE_ARG(what, grad_log, "grad_log");
+    if (level_w) { const int rc = weight_value_check(what, level_w, 0); if (rc) return rc; }
+    if (select) for (size_t i = 0; i < n_pts; ++i) if (select[i] < -1 || (int64_t)select[i] >= (int64_t)n_objs) {
+        set_error("%s: select[%zu] = %d (-1 or an index below %zu)", what, i, select[i], n_objs); return MON_ERR_ARG; }
+    return MON_OK;
+}
+int scene_gradients_check(int side, const float* xyz, size_t n, const float* level_w, const int32_t* select, size_t n_objs, const float* sigma,
+                          const float* grad_log) {
+    { const int rc = scene_points_check(side, xyz, n, sigma); if (rc) return rc; }
+    return gradients_args_check("scene_gradients", level_w, select, n, n_objs, grad_log);
+}
+int scene_lattice_gradients_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, const float* level_w, const float* sigma,
+                                  const float* grad_log) {
+    { const int rc = scene_lattice_check(side, origin3, step3, nx, ny, nz, sigma); if (rc) return rc; }
+    return gradients_args_check("scene_lattice_gradients", level_w, nullptr, 0, 0, grad_log);
+}
+int scene_gradients_weights_check(Model* const* ms, size_t n, const float* level_w) {
+    return level_w ? level_weights_check("scene_gradients", level_w, scene_levels(ms, n).Lmax) : MON_OK;
+}
+int scene_gradients(Model* const* ms, size_t n, int side, const ScenePoints& q, const float* level_w, const int32_t* select, float* sigma, float* rgb,
+                    int32_t* owner, float* owner_sigma, uint32_t* n_inside, float* grad_log, float* grad_sigma, float* normal, const int32_t* ids,
+                    size_t rows_k, float* rows) {
+    FieldGrads g{ level_w, select, {} }; const FieldOut out{ sigma, rgb, owner, owner_sigma, n_inside, grad_log, grad_sigma, normal };
+    return scene_field_run(q.xyz ? "scene_gradients" : "scene_lattice_gradients", ms, n, side, q, true, &g, out, ids, rows_k, rows);
+}
+// mon_object_query_gradients: the same kernel with the transform switched off and the extent taken as 1 (nothing is divided): raw4 and d raw3 / d u
+int object_gradients_check(int side, const float* unit_xyz, size_t n, const float* level_w, const float* grad_unit) {
+    REQUIRE_ARG("object_gradients", grad_unit, "grad_unit");
+    { const int rc = object_points_check(side, unit_xyz, n, grad_unit); if (rc) return rc; }
+    return level_w ? weight_value_check("object_gradients", level_w, 0) : MON_OK;
+}
+int object_gradients(Model& m, int side, const float* unit_xyz, size_t n, const float* level_w, float* raw4, float* grad_unit) {
+    if (level_w) { const int rc = level_weights_check("object_gradients", level_w, (int)m.nd.L); if (rc) return rc; }
+    Model* ms[1] = { &m };
+    ScenePoints q{}; q.xyz = unit_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    std::vector<float> rows(16 * n); FieldGrads g{ level_w, nullptr, {} };
+    const int rc = scene_field_run("object_gradients", ms, 1, side, q, false, &g, FieldOut{}, nullptr, 0, rows.data());
+    if (rc) return rc;
+    for (size_t i = 0; i < n; ++i) { if (raw4) std::memcpy(raw4 + 4 * i, rows.data() + 16 * i + 4, 16); std::memcpy(grad_unit + 3 * i, rows.data() + 16 * i + 12, 12); }
+    return MON_OK;
+}
+// mon_scene_cast_normals / mon_online_cast_normals: a host-side rule over two routes -- the cast; x = fmaf(hit_t, d, o) per axis for the rays with a hit;
+// the gradients at those points, compacted in ray order, with select = the hit object; scattered back, 0 0 0 for a miss.  Two enqueues, two
+// synchronisations (one when no ray hits).  ids: applied to both instance outputs at the end (the rule itself runs on indices into ms).
+int scene_cast_normals_check(int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, const float* level_w, const float* rgb, const float* dist,
+                             const float* normal) {
+    { const int rc = scene_cast_check(side, rays, n_rays, hit_opacity, rgb, dist); if (rc) return rc; }
+    REQUIRE_ARG("scene_cast_normals", normal, "normal");
+    return level_w ? weight_value_check("scene_cast_normals", level_w, 0) : MON_OK;
+}
+int scene_cast_normals(Model* const* ms, size_t n, int side, const mon_scene_ray* rays, size_t n_rays, float hit_opacity, const float* level_w, float* rgb,
+                       float* dist, float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t, int32_t* hit_instance, float* hit_xyz, float* normal,
+                       float* grad_log, const int32_t* ids) {
+    std::vector<float> t_own; std::vector<int32_t> inst_own;
+    if (!hit_t) { t_own.resize(n_rays); hit_t = t_own.data(); }
+    if (!hit_instance) { inst_own.resize(n_rays); hit_instance = inst_own.data(); }
+    { const int rc = scene_cast(ms, n, side, rays, n_rays, hit_opacity, rgb, dist, opacity, instance, hit_t, hit_sample_t, hit_instance, nullptr, nullptr);
+      if (rc) return rc; }
+    std::vector<float> x; std::vector<int32_t> sel; std::vector<size_t> at;
+    for (size_t i = 0; i < n_rays; ++i) {
+        if (hit_instance[i] < 0) continue;
+        for (int a = 0; a < 3; ++a) x.push_back(std::fmaf(hit_t[i], rays[i].d[a], rays[i].o[a]));
+        sel.push_back(hit_instance[i]); at.push_back(i);
+    }
+    const size_t nh = at.size();
+    std::vector<float> sg(nh), gl(3 * nh), nr(3 * nh);
+    if (nh) {
+        ScenePoints q{}; q.xyz = x.data(); q.n = nh; q.nx = q.ny = q.nz = 1;
+        const int rc = scene_gradients(ms, n, side, q, level_w, sel.data(), sg.data(), nullptr, nullptr, nullptr, nullptr, gl.data(), nullptr, nr.data(), nullptr,
+                                       0, nullptr);
+        if (rc) return rc;
+    }
+    if (hit_xyz) std::fill(hit_xyz, hit_xyz + 3 * n_rays, 0.f);
+    if (grad_log) std::fill(grad_log, grad_log + 3 * n_rays, 0.f);
+    std::fill(normal, normal + 3 * n_rays, 0.f);
+    for (size_t k = 0; k < nh; ++k) for (int a = 0; a < 3; ++a) {
+        if (hit_xyz) hit_xyz[3 * at[k] + a] = x[3 * k + a];
+        if (grad_log) grad_log[3 * at[k] + a] = gl[3 * k + a];
+        normal[3 * at[k] + a] = nr[3 * k + a];
+    }
+    if (ids) for (size_t i = 0; i < n_rays; ++i) {
+        if (instance && instance[i] >= 0) instance[i] = ids[instance[i]];
+        if (hit_instance[i] >= 0) hit_instance[i] = ids[hit_instance[i]];
+    }
+    return MON_OK;
+}
+
+// ---- distance fields (mon_distance_transform, mon_scene_distance_lattice): clearance over a lattice.  scene_distance runs the chain over
+// the lattice, whose sigma and owner rows stay on the device; then the mask (k_distance_mask), the three passes of k_distance_pass and k_distance_finish,
+// once more on the complement when free_dist is asked for, one copy home and one synchronisation.  The side's workspace keeps the mask (1 B per cell) and
+// the passes' two halves of squared distance and site (16 B per cell), shared by the two transforms, which run one after the other.
+static int distance_outputs_check(const char* what, float max_dist, const float* dist) {
+    REQUIRE_ARG(what, dist, "dist");
+    if (!(max_dist > 0.f)) { set_error("%s: max_dist %g (above 0; +inf for no limit)", what, (double)max_dist); return MON_ERR_ARG; }
+    return MON_OK;
+}
+int distance_transform_check(const uint8_t* occupied, int nx, int ny, int nz, const float* step3, float max_dist, const float* dist) {
+    REQUIRE_ARG("distance_transform", occupied, "occupied"); REQUIRE_ARG("distance_transform", step3, "step");
+    { const int rc = lattice_dims_check("distance_transform", nx, ny, nz); if (rc) return rc; }
+    for (int a = 0; a < 3; ++a) if (!std::isfinite(step3[a])) { set_error("distance_transform: step is not finite"); return MON_ERR_ARG; }
+    return distance_outputs_check("distance_transform", max_dist, dist);
+}
+int scene_distance_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float max_dist, const float* dist) {
+    { const int rc = lattice_shape_check("scene_distance", origin3, step3, nx, ny, nz); if (rc) return rc; }
+    { const int rc = side_check("scene_distance", side); if (rc) return rc; }
+    if (!std::isfinite(sigma_min) || sigma_min < 0.f) { set_error("scene_distance: sigma_min %g (finite, >= 0)", (double)sigma_min); return MON_ERR_ARG; }
+    return distance_outputs_check("scene_distance", max_dist, dist);
+}
+// mon_distance_transform: the transform alone on a host mask, in buffers of its own on the device's default stream
+int distance_transform(int device, const uint8_t* occupied, int nx, int ny, int nz, const float* step3, float max_dist, float* dist, int32_t* nearest) {
+    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available"); return MON_ERR_NO_DEVICE; }
+    HIPCHECK(use_device(device));
+    const size_t n = (size_t)nx * ny * nz;
+    DevBuf<uint8_t> occ; DevBuf<float> v; DevBuf<int32_t> site;                     // v, site: the passes' two halves, then the output row
+    { int rc; if ((rc = occ.grow(n)) || (rc = v.grow(3 * n)) || (rc = site.grow(3 * n))) return rc; }
+    HIPCHECK(hipMemcpy(occ.p, occupied, n, hipMemcpyHostToDevice));
+    launch_distance_passes(nullptr, occ.p, false, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, step3, v.p, site.p);
+    launch_distance_finish(nullptr, (uint32_t)n, v.p, site.p, max_dist, nullptr, v.p + 2 * n, nearest ? site.p + 2 * n : nullptr, nullptr);
+    HIPCHECK(hipGetLastError());
+    std::vector<float> h_dist(n); std::vector<int32_t> h_near(nearest ? n : 0);     // (the caller's arrays are written only once everything has succeeded)
+    HIPCHECK(hipMemcpy(h_dist.data(), v.p + 2 * n, 4 * n, hipMemcpyDeviceToHost));
+    if (nearest) HIPCHECK(hipMemcpy(h_near.data(), site.p + 2 * n, 4 * n, hipMemcpyDeviceToHost));
+    std::memcpy(dist, h_dist.data(), 4 * n);
+    if (nearest) std::memcpy(nearest, h_near.data(), 4 * n);
+    return MON_OK;
+}
+// q: a lattice (scene_lattice).  ids as scene_points', applied to nearest_owner.  max_dist truncates dist and free_dist alike.
+int scene_distance(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, float max_dist, float* dist, int32_t* nearest,
+                   int32_t* nearest_owner, float* free_dist, float* sigma, const int32_t* ids) {
+    SceneCall c; { const int rc = c.enter("scene_distance", ms, n, side, false); if (rc) return rc; }
+    SceneWs& ws = *c.ws; const hipStream_t s = c.s;
+    const size_t n_q = q.n; const uint32_t nq = (uint32_t)n_q, cap = std::min(nq, kScenePointsPass);
+    // the output area: sigma | dist | nearest | nearest_owner | free_dist (what may go home, from the front: up to the last row asked for), then the fold's
+    // other rows
+    Area A{ n_q }; FoldRows f{}; f.sigma = A.row(); const size_t r_dist = A.row(), r_nearest = A.row(), r_nearest_owner = A.row(), r_free = A.row();
+    f.rgb = A.row(3); f.owner = A.row(); f.owner_sigma = A.row(); f.n_inside = A.row();
+    const size_t home = free_dist ? f.rgb : nearest_owner ? r_free : nearest ? r_nearest_owner : r_nearest;
+    {   int rc;
+        if ((rc = field_passes_prepare(c, n, q, cap, 12u)) || (rc = ws.out.grow(A.end)) || (rc = ws.h_out.grow(home)) || (rc = ws.docc.grow(n_q)) ||
+            (rc = ws.dv.grow(2 * n_q)) || (rc = ws.dsite.grow(2 * n_q))) return rc; }
+    float* o = ws.out.p;
+    field_passes_enqueue(c, ms, n, q, true, cap, f, nullptr, 0, nullptr);
+    launch_distance_mask(s, nq, o + f.sigma, sigma_min, ws.docc.p);
+    launch_distance_passes(s, ws.docc.p, false, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, q.step, ws.dv.p, ws.dsite.p);
+    launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, max_dist, reinterpret_cast<int32_t*>(o + f.owner), o + r_dist,
+            nearest ? reinterpret_cast<int32_t*>(o + r_nearest) : nullptr, nearest_owner ? reinterpret_cast<int32_t*>(o + r_nearest_owner) : nullptr);
+    if (free_dist) {
+        launch_distance_passes(s, ws.docc.p, true, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, q.step, ws.dv.p, ws.dsite.p);
+        launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, max_dist, nullptr, o + r_free, nullptr, nullptr);
+    }
+    { const int rc = c.home(home); if (rc) return rc; }
+    const float* h = ws.h_out.p;
+    if (sigma) std::memcpy(sigma, h + f.sigma, 4 * n_q);
+    std::memcpy(dist, h + r_dist, 4 * n_q);
+    if (nearest) std::memcpy(nearest, h + r_nearest, 4 * n_q);
+    if (nearest_owner) scene_instances_home(nearest_owner, h + r_nearest_owner, n_q, ids);
+    if (free_dist) std::memcpy(free_dist, h + r_free, 4 * n_q);
+    return MON_OK;
+}
+
+// ---- connected components (mon_label_components, mon_scene_components_lattice): which cells belong together.  scene_components runs the
+// chain over the lattice, k_distance_mask, for region 1 the untruncated transform and the mask dist > clearance (written over the first mask, which the
+// passes have consumed), the labelling (launch_components), one copy home (k_cc_home: the records that were written, not the table's whole room) and one
+// synchronisation.  Per cell the side's workspace keeps the mask (1 B, shared with the distance call) and, in the output area, label and comp (8 B);
+// region 1 also uses the distance call's passes (16 B).  The numbering's block sums are 4 B per 256 cells.
+static int components_outputs_check(const char* what, int connectivity, const int32_t* label, const mon_lattice_component* table, const uint32_t* n_components) {
+    REQUIRE_ARG(what, label, "label");
+    if (table && !n_components) { set_error("%s: a table without n_components (the count says how many records were written)", what); return MON_ERR_ARG; }
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26) { set_error("%s: connectivity %d (6, 18 or 26)", what, connectivity); return MON_ERR_ARG; }
+    return MON_OK;
+}
+int label_components_check(const uint8_t* mask, int nx, int ny, int nz, int connectivity, const int32_t* label, const mon_lattice_component* table,
+                           const uint32_t* n_components) {
+    REQUIRE_ARG("label_components", mask, "mask");
+    { const int rc = lattice_dims_check("label_components", nx, ny, nz); if (rc) return rc; }
+    return components_outputs_check("label_components", connectivity, label, table, n_components);
+}
+int scene_components_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, int region, float clearance,
+                           int connectivity, const int32_t* label, const mon_lattice_component* table, const uint32_t* n_components, const float* dist) {
+    { const int rc = lattice_shape_check("scene_components", origin3, step3, nx, ny, nz); if (rc) return rc; }
+    { const int rc = side_check("scene_components", side); if (rc) return rc; }
+    if (!std::isfinite(sigma_min) || sigma_min < 0.f) { set_error("scene_components: sigma_min %g (finite, >= 0)", (double)sigma_min); return MON_ERR_ARG; }
+    if (region != 0 && region != 1) { set_error("scene_components: region %d (0: occupied matter, 1: traversable space)", region); return MON_ERR_ARG; }
+    if (region == 1 && (!std::isfinite(clearance) || clearance < 0.f)) { set_error("scene_components: clearance %g (finite, >= 0)", (double)clearance);
+        return MON_ERR_ARG; }
+    if (region == 0 && dist) { set_error("scene_components: dist belongs to region 1 (region 0 runs no distance transform)"); return MON_ERR_ARG; }
+    return components_outputs_check("scene_components", connectivity, label, table, n_components);
+}
+static int components_flag_check(const char* what, uint32_t flag) {
+    if (flag) { set_error("%s: a device loop ran into its cap (flag %#x); no output was written", what, flag); return MON_ERR_STATE; }
+    return MON_OK;
+}
+// mon_label_components: the labelling alone on a host mask, in buffers of its own on the device's default stream.
+// w: label n | comp n | meta 8 (n_components, the cap flag) | the table's records, 8 words each | the numbering's block sums
+int label_components(int device, const uint8_t* mask, int nx, int ny, int nz, int connectivity, int32_t* label, int32_t* comp, mon_lattice_component* table,
+                     uint32_t cap, uint32_t* n_components) {
+    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available"); return MON_ERR_NO_DEVICE; }
+    HIPCHECK(use_device(device));
+    const size_t n = (size_t)nx * ny * nz, tcap = table ? std::min((size_t)cap, n) : 0, front = 2 * n + 8;
+    DevBuf<uint8_t> occ; DevBuf<uint32_t> w;
+    { int rc; if ((rc = occ.grow(n)) || (rc = w.grow(front + 8 * tcap + components_scan_words((uint32_t)n)))) return rc; }
+    HIPCHECK(hipMemcpy(occ.p, mask, n, hipMemcpyHostToDevice));
+    int32_t* d_label = reinterpret_cast<int32_t*>(w.p); uint32_t* d_meta = w.p + 2 * n;
+    launch_components(nullptr, occ.p, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, connectivity, d_label, d_label + n, w.p + front + 8 * tcap,
+            tcap ? reinterpret_cast<mon_lattice_component*>(w.p + front) : nullptr, (uint32_t)tcap, d_meta);
+    HIPCHECK(hipGetLastError());
+    std::vector<uint32_t> h(front);                                                 // (the caller's arrays are written only once everything has succeeded)
+    HIPCHECK(hipMemcpy(h.data(), w.p, 4 * front, hipMemcpyDeviceToHost));
+    { const int rc = components_flag_check("label_components", h[2 * n + 1]); if (rc) return rc; }
+    const size_t used = std::min((size_t)h[2 * n], tcap);
+    std::vector<uint32_t> h_table(8 * used);
+    if (used) HIPCHECK(hipMemcpy(h_table.data(), w.p + front, 32 * used, hipMemcpyDeviceToHost));
+    std::memcpy(label, h.data(), 4 * n);
+    if (comp) std::memcpy(comp, h.data() + n, 4 * n);
+    if (used) std::memcpy(table, h_table.data(), 32 * used);
+    if (n_components) *n_components = h[2 * n];
+    return MON_OK;
+}
+// q: a lattice (scene_lattice).  ids as scene_points', applied to owner.
+int scene_components(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, int region, float clearance, int connectivity,
+                     int32_t* label, int32_t* comp, mon_lattice_component* table, uint32_t cap, uint32_t* n_components, float* dist, float* sigma,
+                     int32_t* owner, const int32_t* ids) {
+    SceneCall c; { const int rc = c.enter("scene_components", ms, n, side, false); if (rc) return rc; }
+    SceneWs& ws = *c.ws; const hipStream_t s = c.s;
+    const size_t n_q = q.n, tcap = table ? std::min((size_t)cap, n_q) : 0; const uint32_t nq = (uint32_t)n_q, pass = std::min(nq, kScenePointsPass);
+    // the output area, what may go home from the front (up to the last row asked for): label | comp | meta 8 (n_components, the cap flag) | the table's
+    // records, 8 words each | (region 1: dist) | sigma | owner, then the fold's other rows
+    Area A{ n_q }; const size_t r_label = A.row(), r_comp = A.row(), r_meta = A.take(8), r_table = A.take(8 * tcap), r_dist = region == 1 ? A.row() : A.end;
+    FoldRows f{}; f.sigma = A.row(); f.owner = A.row(); f.rgb = A.row(3); f.owner_sigma = A.row(); f.n_inside = A.row();
+    const size_t home = owner ? f.rgb : sigma ? f.owner : dist ? r_dist + n_q : r_dist;
+    {   int rc;
+        if ((rc = field_passes_prepare(c, n, q, pass, 12u)) || (rc = ws.out.grow(A.end)) || (rc = ws.h_out.grow(home)) || (rc = ws.docc.grow(n_q)) ||
+            (rc = ws.cscan.grow(components_scan_words(nq))) || (region == 1 && ((rc = ws.dv.grow(2 * n_q)) || (rc = ws.dsite.grow(2 * n_q))))) return rc; }
+    float* o = ws.out.p; uint32_t* o_meta = reinterpret_cast<uint32_t*>(o + r_meta);
+    field_passes_enqueue(c, ms, n, q, true, pass, f, nullptr, 0, nullptr);
+    launch_distance_mask(s, nq, o + f.sigma, sigma_min, ws.docc.p);
+    if (region == 1) {
+        launch_distance_passes(s, ws.docc.p, false, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, q.step, ws.dv.p, ws.dsite.p);
+        launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, INFINITY, nullptr, o + r_dist, nullptr, nullptr);
+        launch_components_clear_mask(s, nq, o + r_dist, clearance, ws.docc.p);
+    }
+    launch_components(s, ws.docc.p, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, connectivity, reinterpret_cast<int32_t*>(o + r_label),
+            reinterpret_cast<int32_t*>(o + r_comp), ws.cscan.p, tcap ? reinterpret_cast<mon_lattice_component*>(o + r_table) : nullptr, (uint32_t)tcap, o_meta);
+    launch_components_home(s, reinterpret_cast<const uint32_t*>(o), reinterpret_cast<uint32_t*>(ws.h_out.p), (uint32_t)home, (uint32_t)r_table, (uint32_t)tcap, o_meta);
+    { const int rc = c.finish(); if (rc) return rc; }
+    const float* h = ws.h_out.p; const uint32_t* h_meta = reinterpret_cast<const uint32_t*>(h + r_meta);
+    { const int rc = components_flag_check("scene_components", h_meta[1]); if (rc) return rc; }
+    std::memcpy(label, h + r_label, 4 * n_q);
+    if (comp) std::memcpy(comp, h + r_comp, 4 * n_q);
+    if (table) std::memcpy(table, h + r_table, 32 * std::min((size_t)h_meta[0], tcap));
+    if (n_components) *n_components = h_meta[0];
+    if (dist) std::memcpy(dist, h + r_dist, 4 * n_q);
+    if (sigma) std::memcpy(sigma, h + f.sigma, 4 * n_q);
+    if (owner) scene_instances_home(owner, h + f.owner, n_q, ids);
+    return MON_OK;
+}
+
+}  // namespace mon

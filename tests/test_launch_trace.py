@@ -6,7 +6,11 @@ train(3), train_stages(1), (1|2), (4), (2|4); a fused and a hybrid-scatter objec
 set_pose, set_backend and set_debug_dump, a fused and a chunk-record object through a checkpoint save + load, every one followed by a train call -- and one
 online-manager update_dataset between two slices.  A second part ("== inference routes") walks every scene and object-pose route of the C ABI once on each
 side over two trained and published objects (camera and window refinement with and without a coarse-to-fine schedule, a window of two frames, one of them
-with two boxes) and every online counterpart on a manager whose two objects have published.  Every kernel launch (registered
+with two boxes) and every online counterpart on a manager whose two objects have published; then the field queries on each side: the object's and the
+scene's point queries and gradients (lists of 5 points, with and without level weights and select), the lattice query, the lattice gradients, the distance
+field and the components (region 0 with a table, region 1 with and without its optional outputs) on a lattice of 3 x 2 x 2 and, once per family, on one of
+33 x 32 x 16 cells (a pass boundary with a ragged tail of 512), the normals at ray hits, the six online counterparts, and with no side
+mon_distance_transform, mon_label_components, mon_lattice_points and mon_camera_rays.  Every kernel launch (registered
 name, grid, block, dynamic LDS bytes, stream by creation index) and every asynchronous fill / copy (bytes, stream) is one line.  The trace is folded without
 loss -- a block of up to 12 lines that repeats back to back is written once, followed by "x N" (fold) -- and must then equal tests/golden/launch_trace.txt line
 for line.  No GPU.
@@ -28,11 +32,16 @@ NOT covered: the stand-in runtime returns zeros for every read-back and refuses 
 choice of the gather chain under occupancy skipping (gathers_preferred) and the hipGraph replay (option use_graph) never change state here; the GPU suite
 holds them (test_gpu_parity.py, test_occupancy.py, test_occupancy_oracle.py, test_checkpoint.py).
 
+The field queries' lines, routes and refusals, were recorded from the commit before their host chain was written once ("Add connected components over a
+lattice of the object map"), with this driver and that commit's product sources; the lines above and between them came out as they stood.  (Their object
+lists need no common camera, dataset or sample stream: other_K, other_ds and xorwow are accepted there and their launches are in the trace.)
+
 A change that moves the schedule ON PURPOSE records the new trace: python tests/test_launch_trace.py --record
 A refactor shows that nothing moved by recording from the parent commit's product sources with this driver, and getting the committed file:
     MON_TRACE_SRC=<checkout of the parent commit> python tests/test_launch_trace.py --record
 A record from this tree's own sources (no MON_TRACE_SRC) writes the messages it prints into the golden itself and empties launch_trace_reworded.txt, which
-holds nothing but the difference between the golden and this tree; a record from another checkout leaves that file alone."""
+holds nothing but the difference between the golden and this tree; a record from another checkout leaves that file alone -- and prints that checkout's
+wording of the lines listed there, which go back to the recorded wording before the file is committed (git diff shows nothing else)."""
 import difflib
 import os
 import shutil

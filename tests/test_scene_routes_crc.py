@@ -12,7 +12,13 @@ equal the one recorded from the parent commit's build on an MI355X:
 conftest's small_scene (120 x 160, 12 views), two base.json objects on its one object (the second on a box 1.5 times as large) with fixed sample seeds, 60
 steps each.  The shapes cross what the host computes offsets for: the full frame is 19 200 pixels (a pass boundary at 16 384), the probe and the cast take
 16 384 + 100 items, the batch scores 5 poses x 4000 drawn rays (passes of 4 and 1), the window has 3 frames and refines the objects, relocalisation keeps 2 of
-6 candidates.  Side 1 is compared only when render_snapshot reports step 60 for both objects; otherwise the case fails.  The online routes are left out:
+6 candidates.  The field queries (scene_field.cpp) joined when their host chain was written once, recorded in the same way from the commit before that one ("Add
+connected components over a lattice of the object map"); the nine routes above came out of that record as they stood.  They take 16 384 + 100 world points
+over the larger box (the gradients with a select and level weights that are not all ones), as many unit-cube points on the first object, and one lattice of
+33 x 32 x 17 around the objects for the lattice query, the lattice gradients, the distance field (truncated with free_dist, untruncated without) and the
+components (region 0, 26-connected, with its table; region 1, 6-connected, with dist, sigma and owner).  sigma_min is the 90th percentile of the lattice
+query's own sigma; between 1 % and 99 % of the cells must be occupied before the distance and component calls are made.
+Side 1 is compared only when render_snapshot reports step 60 for both objects; otherwise the case fails.  The online routes are left out:
 what their snapshots hold depends on thread timing.
 
 Bit equality is the condition: there is no tolerance."""
@@ -39,7 +45,11 @@ STEPS = 60
 VIEWS = (3, 4, 5)                                                # the window's frames; VIEWS[0]: the frame of the single-frame routes
 N_ITEMS = 16384 + 100                                            # probe queries and cast rays: one pass boundary
 ROUTES = ("render_scene", "probe_scene", "cast_scene", "scene_pose_loss", "scene_refine_camera", "scene_pose_loss_batch", "scene_refine_window",
-          "scene_relocalise", "refine_pose_c2f")
+          "scene_relocalise", "refine_pose_c2f",
+          "query_scene_points", "query_scene_lattice", "query_scene_gradients", "query_scene_lattice_gradients", "cast_scene_normals",
+          "scene_distance_lattice", "scene_distance_lattice_untruncated", "scene_components_lattice", "scene_components_lattice_free",
+          "object_query_points", "object_query_gradients")
+LATTICE = (33, 32, 17)                                           # 17 952 cells: one pass boundary, the field routes' common lattice
 
 
 def _crc(a):
@@ -67,6 +77,50 @@ def _boxes(sc, views):
     return np.array([[q for q in sc.objects[0]["boxes"] if int(q[0]) == v][0] for v in views], np.uint32)
 
 
+def _field_inputs(sc):
+    """world points over the larger object's box, unit-cube points, the lattice around the objects (10 % margin)"""
+    ob = sc.objects[0]; rs = np.random.RandomState(23)
+    half = np.asarray(ob["half"], np.float64) * max(INFLATE); R, t = ob["Two"][:3, :3], ob["Two"][:3, 3]
+    world = (rs.uniform(-1.1, 1.1, (N_ITEMS, 3)) * half) @ R.T + t
+    unit = rs.uniform(0.0, 1.0, (N_ITEMS, 3))
+    select = rs.randint(-1, 2, N_ITEMS)
+    c = np.array([[sx, sy, sz] for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)], np.float64) * half @ R.T + t
+    lo, hi = c.min(0), c.max(0); pad = 0.1 * (hi - lo); lo -= pad; hi += pad
+    return world.astype(np.float32), unit.astype(np.float32), select.astype(np.int32), lo.astype(np.float32), ((hi - lo) / (np.array(LATTICE) - 1)).astype(np.float32)
+
+
+def _components_arrays(r):
+    label, comp, table, n, rows = r
+    return [label, comp, table, np.uint32(n)] + [rows[k] for k in sorted(rows)]
+
+
+def run_field_routes(pkg, objs, rays, side, sc):
+    """the field queries (scene_field.cpp): {route: every array it returns}"""
+    world, unit, select, origin, step = _field_inputs(sc)
+    L = max(o.cfg.n_levels for o in objs); lw = np.where(np.arange(L) % 2 == 0, 1.0, 0.5).astype(np.float32)
+    out = {}
+    out["query_scene_points"] = pkg.query_scene_points(objs, world, side=side)
+    out["query_scene_lattice"] = pkg.query_scene_lattice(objs, origin, step, LATTICE, side=side)
+    out["query_scene_gradients"] = pkg.query_scene_gradients(objs, world, level_weights=lw, select=select, side=side)
+    out["query_scene_lattice_gradients"] = pkg.query_scene_lattice_gradients(objs, origin, step, LATTICE, level_weights=lw, side=side)
+    out["cast_scene_normals"] = pkg.cast_scene_normals(objs, rays, side=side)
+    sigma = out["query_scene_lattice"][0]; n = sigma.size
+    smin = float(np.percentile(sigma, 90.0, method="lower"))          # (tests/test_scene_distance.py::_sigma_min)
+    n_occ = int((~(sigma <= np.float32(smin))).sum())
+    print("side %d: sigma_min %.5g, %d of %d cells occupied" % (side, smin, n_occ, n))
+    assert n // 100 <= n_occ <= n - n // 100, (n_occ, n)
+    diag = float(np.linalg.norm(step * (np.array(LATTICE) - 1)))
+    out["scene_distance_lattice"] = pkg.scene_distance_lattice(objs, origin, step, LATTICE, smin, max_dist=0.25 * diag, side=side, free=True)
+    out["scene_distance_lattice_untruncated"] = [a for a in pkg.scene_distance_lattice(objs, origin, step, LATTICE, smin, side=side, free=False)
+                                                 if a is not None]
+    out["scene_components_lattice"] = _components_arrays(pkg.scene_components_lattice(objs, origin, step, LATTICE, smin, region=0, connectivity=26, side=side))
+    out["scene_components_lattice_free"] = _components_arrays(pkg.scene_components_lattice(
+        objs, origin, step, LATTICE, smin, region=1, clearance=float(step.max()), connectivity=6, side=side, rows=("dist", "sigma", "owner")))
+    out["object_query_points"] = (pkg.query_object_points(objs[0], unit, side=side),)
+    out["object_query_gradients"] = pkg.query_object_gradients(objs[0], unit, level_weights=lw[:objs[0].cfg.n_levels], side=side)
+    return out
+
+
 def run_routes(pkg, ss, sc, objs, side):
     """{route: [CRC32 of every array it returns]} on one side"""
     v0 = VIEWS[0]; T16 = ss.colmajor(sc.Twc[v0]); box = _boxes(sc, VIEWS[:1])
@@ -90,6 +144,7 @@ def run_routes(pkg, ss, sc, objs, side):
     out["scene_relocalise"] = (pose, np.array([res.best_candidate, res.refined], np.uint32),
                                np.array([res.score_candidate0, res.score_best_candidate, res.score_final], np.float32), scores)
     out["refine_pose_c2f"] = objs[0].refine_pose_c2f(box, Tow[0], p3, side=side)
+    out.update(run_field_routes(pkg, objs, rays, side, sc))
     assert set(out) == set(ROUTES)
     return {k: [_crc(a) for a in v] for k, v in out.items()}
 

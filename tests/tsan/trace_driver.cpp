@@ -1,6 +1,7 @@
 // trace_driver.cpp -- walks the C ABI single-threaded on the host side built --offload-host-only against tests/tsan/hip_stub.cpp (no sanitizer) with the
 // stub's launch trace on: every kernel launch and asynchronous fill / copy of every training path as one line of text, under a heading per case and per call;
-// then (part two) of every scene and pose route on both sides and through the online manager, and a list of the calls those routes refuse, with code and message.
+// then (part two) of every scene, pose and field-query route on both sides and through the online manager, and a list of the calls those routes refuse, with
+// code and message.
 // tests/test_launch_trace.py compares the output with tests/golden/launch_trace.txt.  Usage: trace_driver <scratch dir> <config json>.  TEST INFRASTRUCTURE.
 #include <chrono>
 #include <cmath>
@@ -115,6 +116,11 @@ struct Args {
     mon_object* obj; const mon_pose_c2f_params* cc; const float* lwl;                     // object pose routes (cc, lwl: the arguments the _c2f / _levels calls require)
     mon_online* om; size_t idx; size_t n_online;
     float* out;                                                                           // every optional output
+    // the field queries: point lists (world, unit cube), the lattice, what gradients, distance and components add, their required outputs; opt: the optional
+    // outputs are asked for (each in a slice of `out` of its own: cast_normals reads its own instance row back) or all NULL
+    const float* pts; size_t n_pts; const float* upts; const float* origin; const float* step; int nx, ny, nz; const float* glw; const int32_t* sel;
+    float sigma_min, max_dist; int region; float clearance; int conn; mon_lattice_component* table; uint32_t cap; uint32_t* n_comp; const uint8_t* mask;
+    float* sigma; float* grad; float* raw4; float* normal; float* dist; int32_t* label; float* xyz_out; mon_scene_ray* rays_out; bool opt;
 };
 static int32_t* as_i32(float* p) { return reinterpret_cast<int32_t*>(p); }
 static int scene_render(const Args& a) { return mon_scene_render(a.objs, a.n_objs, a.side, a.rect, a.Twc, a.rgb, a.depth, a.out, as_i32(a.out)); }
@@ -147,6 +153,44 @@ static int online_relocalise(const Args& a) { mon_reloc_result res; return mon_o
         &res, a.out); }
 static int online_refine_pose(const Args& a) { return mon_online_refine_pose(a.om, a.idx, a.obs, a.n_obs, a.p, a.pose_io, a.out); }
 static int online_refine_pose_c2f(const Args& a) { return mon_online_refine_pose_c2f(a.om, a.idx, a.obs, a.n_obs, a.p, a.cc, a.pose_io, a.out); }
+
+// the field queries.  sl(a, k): optional output k of such a route
+static float* sl(const Args& a, int k) { return a.opt ? a.out + (size_t)k * 65536 : nullptr; }
+static uint32_t* as_u32(float* p) { return reinterpret_cast<uint32_t*>(p); }
+static int object_query_points(const Args& a) { return mon_object_query_points(a.obj, a.side, a.upts, a.n_pts, a.raw4); }
+static int scene_query_points(const Args& a) { return mon_scene_query_points(a.objs, a.n_objs, a.side, a.pts, a.n_pts, a.sigma, sl(a, 1), as_i32(sl(a, 2)), sl(a, 3),
+        as_u32(sl(a, 4))); }
+static int scene_query_lattice(const Args& a) { return mon_scene_query_lattice(a.objs, a.n_objs, a.side, a.origin, a.step, a.nx, a.ny, a.nz, a.sigma, sl(a, 1),
+        as_i32(sl(a, 2)), sl(a, 3), as_u32(sl(a, 4))); }
+static int object_query_gradients(const Args& a) { return mon_object_query_gradients(a.obj, a.side, a.upts, a.n_pts, a.glw, sl(a, 1), a.grad); }
+static int scene_query_gradients(const Args& a) { return mon_scene_query_gradients(a.objs, a.n_objs, a.side, a.pts, a.n_pts, a.glw, a.sel, a.sigma, sl(a, 1),
+        as_i32(sl(a, 2)), sl(a, 3), as_u32(sl(a, 4)), a.grad, sl(a, 13), sl(a, 14)); }
+static int scene_query_lattice_gradients(const Args& a) { return mon_scene_query_lattice_gradients(a.objs, a.n_objs, a.side, a.origin, a.step, a.nx, a.ny, a.nz, a.glw,
+        a.sigma, sl(a, 1), as_i32(sl(a, 2)), sl(a, 3), as_u32(sl(a, 4)), a.grad, sl(a, 13), sl(a, 14)); }
+static int scene_cast_normals(const Args& a) { return mon_scene_cast_normals(a.objs, a.n_objs, a.side, a.rays, a.n_rays, a.hit_opacity, a.glw, a.rgb, a.depth, sl(a, 1),
+        as_i32(sl(a, 2)), sl(a, 3), sl(a, 4), as_i32(sl(a, 13)), sl(a, 14), a.normal, sl(a, 15)); }
+static int scene_distance_lattice(const Args& a) { return mon_scene_distance_lattice(a.objs, a.n_objs, a.side, a.origin, a.step, a.nx, a.ny, a.nz, a.sigma_min,
+        a.max_dist, a.dist, as_i32(sl(a, 1)), as_i32(sl(a, 2)), sl(a, 3), sl(a, 4)); }
+// region 0 has no dist; the table (and its count) is an argument of its own
+static int scene_components_lattice(const Args& a) { return mon_scene_components_lattice(a.objs, a.n_objs, a.side, a.origin, a.step, a.nx, a.ny, a.nz, a.sigma_min,
+        a.region, a.clearance, a.conn, a.label, as_i32(sl(a, 1)), a.table, a.cap, a.n_comp, a.region == 1 ? sl(a, 2) : nullptr, sl(a, 3), as_i32(sl(a, 4))); }
+static int components_with_dist(const Args& a) { return mon_scene_components_lattice(a.objs, a.n_objs, a.side, a.origin, a.step, a.nx, a.ny, a.nz, a.sigma_min,
+        a.region, a.clearance, a.conn, a.label, nullptr, a.table, a.cap, a.n_comp, a.out + 2 * 65536, nullptr, nullptr); }
+static int distance_transform(const Args& a) { return mon_distance_transform(0, a.mask, a.nx, a.ny, a.nz, a.step, a.max_dist, a.dist, as_i32(sl(a, 1))); }
+static int label_components(const Args& a) { return mon_label_components(0, a.mask, a.nx, a.ny, a.nz, a.conn, a.label, as_i32(sl(a, 1)), a.table, a.cap, a.n_comp); }
+static int lattice_points(const Args& a) { return mon_lattice_points(a.origin, a.step, a.nx, a.ny, a.nz, a.xyz_out); }
+static int camera_rays(const Args& a) { return mon_camera_rays(60.f, 60.f, 32.f, 24.f, a.poses, a.n_poses, a.q, a.n_q, a.rays_out, sl(a, 1)); }
+static int online_query_points(const Args& a) { return mon_online_query_points(a.om, a.pts, a.n_pts, a.sigma, sl(a, 1), as_i32(sl(a, 2)), sl(a, 3), as_u32(sl(a, 4))); }
+static int online_query_lattice(const Args& a) { return mon_online_query_lattice(a.om, a.origin, a.step, a.nx, a.ny, a.nz, a.sigma, sl(a, 1), as_i32(sl(a, 2)), sl(a, 3),
+        as_u32(sl(a, 4))); }
+static int online_query_gradients(const Args& a) { return mon_online_query_gradients(a.om, a.pts, a.n_pts, a.glw, a.sel, a.sigma, sl(a, 1), as_i32(sl(a, 2)), sl(a, 3),
+        as_u32(sl(a, 4)), a.grad, sl(a, 13), sl(a, 14)); }
+static int online_cast_normals(const Args& a) { return mon_online_cast_normals(a.om, a.rays, a.n_rays, a.hit_opacity, a.glw, a.rgb, a.depth, sl(a, 1), as_i32(sl(a, 2)),
+        sl(a, 3), sl(a, 4), as_i32(sl(a, 13)), sl(a, 14), a.normal, sl(a, 15)); }
+static int online_distance_lattice(const Args& a) { return mon_online_distance_lattice(a.om, a.origin, a.step, a.nx, a.ny, a.nz, a.sigma_min, a.max_dist, a.dist,
+        as_i32(sl(a, 1)), as_i32(sl(a, 2)), sl(a, 3), sl(a, 4)); }
+static int online_components_lattice(const Args& a) { return mon_online_components_lattice(a.om, a.origin, a.step, a.nx, a.ny, a.nz, a.sigma_min, a.region, a.clearance,
+        a.conn, a.label, as_i32(sl(a, 1)), a.table, a.cap, a.n_comp, a.region == 1 ? sl(a, 2) : nullptr, sl(a, 3), as_i32(sl(a, 4))); }
 
 // a call that must fail, on one line with its code and message (no exit); `change` edits a copy `a` of the good arguments
 #define ERR(route, change) do { Args a = good; change; const int rc_ = route(a); \
@@ -205,7 +249,7 @@ static void inference_part(const char* cfg_json, const mon_config& base, const u
     mon_object* objs[2] = { o0, o1 }; mon_object* with_null[2] = { o0, nullptr }; mon_object* other_K[2] = { o0, o_K }; mon_object* other_ds[2] = { o0, o_2 };
     mon_object* narrow[2] = { o0, o_16 }; mon_object* xorwow[2] = { o0, o_xw }; mon_object* unpublished[2] = { o0, o_un };
     std::vector<mon_object*> many(257, o0);
-    std::vector<float> out(1u << 20, 0.f), many_poses(16 * 4097);
+    std::vector<float> out(1u << 21, 0.f), many_poses(16 * 4097);
     for (size_t i = 0; i < many_poses.size(); i += 16) std::memcpy(&many_poses[i], g_pose, 64);
     float poses3[3 * 16], pose_io[16], pose_out[16], wTwc[2 * 16], Tow16s[2 * 16], nan_pose[16], nan_Tow[2 * 16], lw[64], lw_neg[64];
     for (int k = 0; k < 3; ++k) std::memcpy(poses3 + 16 * k, g_pose, 64);
@@ -234,8 +278,24 @@ static void inference_part(const char* cfg_json, const mon_config& base, const u
     mon_window_params w; OK(mon_window_default(&w));
     mon_window_params w_fixed3 = w, w_free = w, w_lr = w; w_fixed3.n_fixed_frames = 3; w_free.n_fixed_frames = 0; w_lr.lr_obj_rot = -1.f;
     float* const o = out.data();
-    const Args good{ objs, 2, 0, mon_frame_bbox{ 0, 4, 4, 16, 24 }, g_pose, o, o, poses3, 2, q, 5, rays, 4, 0.5f, obs, 2, &p, nullptr, nullptr, pose_io, o, &r, pose_out,
-                     wobs, 3, wTwc, Tow16s, &w, o0, &c2f, lw, om, 0, 2, o };
+    // the field queries: five world points in and around the boxes, five of the unit cube, a lattice of 3 x 2 x 2 around the objects
+    const float pts[15] = { 0.f, 0.f, 0.f, 0.05f, 0.1f, -0.1f, 0.3f, 0.2f, 0.1f, -0.2f, 0.25f, 0.f, 1.f, 1.f, 1.f };
+    const float upts[15] = { 0.f, 0.f, 0.f, 0.5f, 0.5f, 0.5f, 1.f, 1.f, 1.f, 0.25f, 0.75f, 0.125f, 0.9f, 0.1f, 0.3f };
+    float pts_nan[15], upts_out[15]; std::memcpy(pts_nan, pts, 60); pts_nan[7] = NAN; std::memcpy(upts_out, upts, 60); upts_out[10] = 1.5f;
+    const float origin[3] = { -0.3f, -0.3f, -0.3f }, step[3] = { 0.3f, 0.6f, 0.6f }, origin_nan[3] = { -0.3f, NAN, -0.3f }, step_inf[3] = { 0.3f, 0.6f, INFINITY };
+    const float origin_far[3] = { 3e38f, 0.f, 0.f }, step_far[3] = { 3e38f, 0.6f, 0.6f };
+    const int32_t sel[5] = { 0, 1, -1, 1, 0 }, sel_2[5] = { 0, 1, -1, 2, 0 }, sel_m2[5] = { 0, -2, -1, 1, 0 };
+    float glw[64], lw_neg0[64]; for (int l = 0; l < 64; ++l) { glw[l] = l % 2 ? 0.5f : 1.f; lw_neg0[l] = l == 0 ? -1.f : 1.f; }
+    const uint8_t mask[12] = { 1, 0, 0, 0, 1, 1, 0, 0, 0, 0, 0, 1 };
+    uint32_t n_comp = 0;
+    Args g0{ objs, 2, 0, mon_frame_bbox{ 0, 4, 4, 16, 24 }, g_pose, o, o, poses3, 2, q, 5, rays, 4, 0.5f, obs, 2, &p, nullptr, nullptr, pose_io, o, &r, pose_out,
+             wobs, 3, wTwc, Tow16s, &w, o0, &c2f, lw, om, 0, 2, o };
+    g0.pts = pts; g0.n_pts = 5; g0.upts = upts; g0.origin = origin; g0.step = step; g0.nx = 3; g0.ny = 2; g0.nz = 2; g0.glw = nullptr; g0.sel = nullptr;
+    g0.sigma_min = 1.f; g0.max_dist = INFINITY; g0.region = 0; g0.clearance = 0.1f; g0.conn = 26; g0.table = nullptr; g0.cap = 64; g0.n_comp = nullptr; g0.mask = mask;
+    g0.sigma = o; g0.grad = o + 5 * 65536; g0.raw4 = o + 6 * 65536; g0.normal = o + 7 * 65536; g0.dist = o + 8 * 65536; g0.label = as_i32(o + 9 * 65536);
+    g0.xyz_out = o + 11 * 65536; g0.rays_out = reinterpret_cast<mon_scene_ray*>(o + 12 * 65536); g0.opt = true;
+    mon_lattice_component* const table = reinterpret_cast<mon_lattice_component*>(o + 10 * 65536);
+    const Args good = g0;
 
     // ---- every route once, on both sides
     std::printf("== inference routes\n");
@@ -247,11 +307,27 @@ static void inference_part(const char* cfg_json, const mon_config& base, const u
         CALL(scene_refine_camera(a)); CALL(scene_refine_camera(ac)); CALL(scene_pose_loss_batch(a3)); CALL(scene_relocalise(a3)); CALL(scene_relocalise(ac));
         CALL(scene_window_loss(al)); CALL(scene_refine_window(a)); CALL(scene_refine_window(ac));
         CALL(object_pose_loss(a)); CALL(object_pose_loss_levels(a)); CALL(object_refine_pose(a)); CALL(object_refine_pose_c2f(a));
+        // the field queries; big: 33 x 32 x 16 = 16 896 cells, one pass boundary with a ragged tail of 512; bare: every optional output NULL
+        Args big = a; big.nx = 33; big.ny = 32; big.nz = 16; Args ag = a; ag.glw = glw; ag.sel = sel; Args bare = a; bare.opt = false;
+        Args dt = a; dt.max_dist = 0.5f; Args c0 = a; c0.table = table; c0.n_comp = &n_comp; Args c1 = a; c1.region = 1; c1.conn = 6;
+        Args c1bare = c1; c1bare.opt = false; Args bigc = big; bigc.region = 1; bigc.table = table; bigc.n_comp = &n_comp;
+        CALL(object_query_points(a)); CALL(scene_query_points(a)); CALL(scene_query_lattice(a)); CALL(scene_query_lattice(big));
+        CALL(object_query_gradients(a)); CALL(scene_query_gradients(ag)); CALL(scene_query_gradients(a)); CALL(scene_query_lattice_gradients(a));
+        CALL(scene_query_lattice_gradients(big)); CALL(scene_cast_normals(a));
+        CALL(scene_distance_lattice(dt)); CALL(scene_distance_lattice(bare)); CALL(scene_distance_lattice(big));
+        CALL(scene_components_lattice(c0)); CALL(scene_components_lattice(c1)); CALL(scene_components_lattice(c1bare)); CALL(scene_components_lattice(bigc));
+    }
+    {   std::printf("-- no side\n");
+        Args a = good; Args c0 = a; c0.table = table; c0.n_comp = &n_comp;
+        CALL(distance_transform(a)); CALL(label_components(c0)); CALL(lattice_points(a)); CALL(camera_rays(a));
     }
     {   std::printf("-- online manager, both objects published\n");
         Args a = good; Args ac = a; ac.c = &c2f; Args a3 = a; a3.n_poses = 3;
         CALL(online_render_scene(a)); CALL(online_probe_scene(a)); CALL(online_cast_rays(a)); CALL(online_refine_camera(a)); CALL(online_refine_camera(ac));
         CALL(online_refine_window(a)); CALL(online_refine_window(ac)); CALL(online_relocalise(a3)); CALL(online_refine_pose(a)); CALL(online_refine_pose_c2f(a));
+        Args ag = a; ag.glw = glw; ag.sel = sel; Args c1 = a; c1.region = 1; c1.table = table; c1.n_comp = &n_comp;
+        CALL(online_query_points(a)); CALL(online_query_lattice(a)); CALL(online_query_gradients(ag)); CALL(online_cast_normals(a));
+        CALL(online_distance_lattice(a)); CALL(online_components_lattice(c1));
     }
 
     // ---- the calls every route refuses, with code and message; the trace stays on: none of them may reach the device
@@ -338,6 +414,57 @@ static void inference_part(const char* cfg_json, const mon_config& base, const u
     ONLINE_ERRS(online_refine_pose_c2f); OBS_ERRS(online_refine_pose_c2f, obs, n_obs);
     ERR(online_refine_pose_c2f, a.pose_io = nullptr); ERR(online_refine_pose_c2f, a.idx = 2); ERR(online_refine_pose_c2f, a.cc = nullptr);
     ERR(online_refine_pose_c2f, a.cc = &c_bad); ERR(online_refine_pose_c2f, a.idx = 2; a.cc = &c_bad); ERR(online_refine_pose_c2f, a.om = om_none; a.cc = &c_bad);
+    // the field queries.  Their object lists need no common camera (other_K) and no common dataset (other_ds), and no sample stream is drawn (xorwow)
+#define POINTS_ERRS(route, pts_, bad_) do { ERR(route, a.pts_ = nullptr); ERR(route, a.n_pts = 0); ERR(route, a.n_pts = (1u << 22) + 1u); ERR(route, a.pts_ = bad_); \
+        } while (0)
+#define LATTICE_ERRS(route) do { ERR(route, a.origin = nullptr); ERR(route, a.step = nullptr); ERR(route, a.nx = 0); ERR(route, a.ny = 0); ERR(route, a.nz = 0); \
+        ERR(route, a.nx = 2048; a.ny = 2048; a.nz = 2); ERR(route, a.origin = origin_nan); ERR(route, a.step = step_inf); \
+        ERR(route, a.origin = origin_far; a.step = step_far); } while (0)
+#define WEIGHTS_ERRS(route) do { ERR(route, a.glw = lw_neg0); ERR(route, a.glw = lw_neg); } while (0)
+#define OBJECT_FIELD_ERRS(route) do { ERR(route, a.obj = nullptr); ERR(route, a.side = 2); ERR(route, a.obj = o_16); ERR(route, a.obj = o_xw); \
+        ERR(route, a.obj = o_un; a.side = 1); } while (0)
+#define DISTANCE_ERRS(route) do { ERR(route, a.dist = nullptr); ERR(route, a.sigma_min = -1.f); ERR(route, a.sigma_min = NAN); ERR(route, a.max_dist = 0.f); } while (0)
+#define COMPONENTS_ERRS(route) do { ERR(route, a.label = nullptr); ERR(route, a.sigma_min = -1.f); ERR(route, a.region = 2); ERR(route, a.region = 1; a.clearance = -1.f); \
+        ERR(route, a.conn = 7); ERR(route, a.table = table); } while (0)
+    OBJECT_FIELD_ERRS(object_query_points); POINTS_ERRS(object_query_points, upts, upts_out); ERR(object_query_points, a.raw4 = nullptr);
+    ERR(object_query_points, a.obj = nullptr; a.n_pts = 0);
+    OBJS_ERRS(scene_query_points); POINTS_ERRS(scene_query_points, pts, pts_nan); ERR(scene_query_points, a.sigma = nullptr);
+    ERR(scene_query_points, a.objs = with_null; a.n_pts = 0);
+    OBJS_ERRS(scene_query_lattice); LATTICE_ERRS(scene_query_lattice); ERR(scene_query_lattice, a.sigma = nullptr); ERR(scene_query_lattice, a.objs = with_null; a.nx = 0);
+    OBJECT_FIELD_ERRS(object_query_gradients); POINTS_ERRS(object_query_gradients, upts, upts_out); WEIGHTS_ERRS(object_query_gradients);
+    ERR(object_query_gradients, a.grad = nullptr); ERR(object_query_gradients, a.obj = o_16; a.glw = lw_neg);
+    OBJS_ERRS(scene_query_gradients); POINTS_ERRS(scene_query_gradients, pts, pts_nan); WEIGHTS_ERRS(scene_query_gradients);
+    ERR(scene_query_gradients, a.sigma = nullptr); ERR(scene_query_gradients, a.grad = nullptr); ERR(scene_query_gradients, a.sel = sel_2);
+    ERR(scene_query_gradients, a.sel = sel_m2); ERR(scene_query_gradients, a.objs = with_null; a.sel = sel_2); ERR(scene_query_gradients, a.objs = with_null; a.glw = lw_neg);
+    OBJS_ERRS(scene_query_lattice_gradients); LATTICE_ERRS(scene_query_lattice_gradients); WEIGHTS_ERRS(scene_query_lattice_gradients);
+    ERR(scene_query_lattice_gradients, a.sigma = nullptr); ERR(scene_query_lattice_gradients, a.grad = nullptr);
+    OBJS_ERRS(scene_cast_normals); WEIGHTS_ERRS(scene_cast_normals);
+    ERR(scene_cast_normals, a.rays = nullptr); ERR(scene_cast_normals, a.rgb = nullptr); ERR(scene_cast_normals, a.depth = nullptr); ERR(scene_cast_normals, a.normal = nullptr);
+    ERR(scene_cast_normals, a.n_rays = 0); ERR(scene_cast_normals, a.n_rays = (1u << 22) + 1u); ERR(scene_cast_normals, a.hit_opacity = 0.f);
+    ERR(scene_cast_normals, a.rays = r_nan); ERR(scene_cast_normals, a.rays = r_long); ERR(scene_cast_normals, a.objs = with_null; a.glw = lw_neg);
+    OBJS_ERRS(scene_distance_lattice); LATTICE_ERRS(scene_distance_lattice); DISTANCE_ERRS(scene_distance_lattice);
+    ERR(scene_distance_lattice, a.objs = with_null; a.max_dist = 0.f);
+    OBJS_ERRS(scene_components_lattice); LATTICE_ERRS(scene_components_lattice); COMPONENTS_ERRS(scene_components_lattice);
+    ERR(components_with_dist, a.region = 0); ERR(scene_components_lattice, a.objs = with_null; a.conn = 7);
+    ERR(distance_transform, a.mask = nullptr); ERR(distance_transform, a.step = nullptr); ERR(distance_transform, a.dist = nullptr); ERR(distance_transform, a.nx = 0);
+    ERR(distance_transform, a.nx = 2048; a.ny = 2048; a.nz = 2); ERR(distance_transform, a.step = step_inf); ERR(distance_transform, a.max_dist = 0.f);
+    ERR(label_components, a.mask = nullptr); ERR(label_components, a.label = nullptr); ERR(label_components, a.nz = 0); ERR(label_components, a.nx = 2048; a.ny = 2048; a.nz = 2);
+    ERR(label_components, a.conn = 7); ERR(label_components, a.table = table);
+    LATTICE_ERRS(lattice_points); ERR(lattice_points, a.xyz_out = nullptr);
+    ERR(camera_rays, a.poses = nullptr); ERR(camera_rays, a.q = nullptr); ERR(camera_rays, a.rays_out = nullptr); ERR(camera_rays, a.n_poses = 0); ERR(camera_rays, a.n_q = 0);
+    ERR(camera_rays, a.poses = nan_pose; a.n_poses = 1); ERR(camera_rays, a.q = q_nan); ERR(camera_rays, a.q = q_pose);
+    ONLINE_ERRS(online_query_points); POINTS_ERRS(online_query_points, pts, pts_nan); ERR(online_query_points, a.sigma = nullptr);
+    ERR(online_query_points, a.om = om_none; a.n_pts = 0);
+    ONLINE_ERRS(online_query_lattice); LATTICE_ERRS(online_query_lattice); ERR(online_query_lattice, a.sigma = nullptr);
+    ONLINE_ERRS(online_query_gradients); POINTS_ERRS(online_query_gradients, pts, pts_nan); WEIGHTS_ERRS(online_query_gradients);
+    ERR(online_query_gradients, a.sigma = nullptr); ERR(online_query_gradients, a.grad = nullptr); ERR(online_query_gradients, a.sel = sel_2);
+    ERR(online_query_gradients, a.sel = sel_m2); ERR(online_query_gradients, a.om = om_none; a.sel = sel_2);
+    ONLINE_ERRS(online_cast_normals); WEIGHTS_ERRS(online_cast_normals);
+    ERR(online_cast_normals, a.rays = nullptr); ERR(online_cast_normals, a.rgb = nullptr); ERR(online_cast_normals, a.depth = nullptr); ERR(online_cast_normals, a.normal = nullptr);
+    ERR(online_cast_normals, a.n_rays = 0); ERR(online_cast_normals, a.hit_opacity = 1.f); ERR(online_cast_normals, a.rays = r_tmax);
+    ONLINE_ERRS(online_distance_lattice); LATTICE_ERRS(online_distance_lattice); DISTANCE_ERRS(online_distance_lattice);
+    ONLINE_ERRS(online_components_lattice); LATTICE_ERRS(online_components_lattice); COMPONENTS_ERRS(online_components_lattice);
+    ERR(online_components_lattice, a.om = om_none; a.region = 2);
     hip_stub_trace(0);
     // (the trace ends here: two object threads sign off on stdout in the order they happen to end)
     std::fflush(stdout); if (!std::freopen("/dev/null", "w", stdout)) std::exit(3);
