@@ -408,6 +408,54 @@ int mon_scene_components_lattice(mon_object* const* objs, size_t n_objs, int sid
                                  float sigma_min, int region, float clearance, int connectivity,
                                  int32_t* label, int32_t* comp, mon_lattice_component* table, uint32_t cap, uint32_t* n_components,
                                  float* dist, float* sigma, int32_t* owner);
+/* Shortest-path cost fields: how far the goal is through the space the robot may occupy, and which way to go -- the step a planner runs on the three
+ * calls above after every publication (the reference has no such call; opt-in, new, read-only; no existing call changes its bits).  The field has a unique
+ * definition in fp32:
+ * Lattice.  The distance calls': nx x ny x nz cells, i fastest, cell (i, j, k) at flat index (k * ny + j) * nx + i, nx * ny * nz in 1 .. 2^22, step3 finite;
+ *   a component of step3 may be negative or 0.
+ * Graph.  A cell is passable iff its mask byte is not 0.  Two passable cells are adjacent under connectivity 6 / 18 / 26 exactly as in
+ *   mon_label_components.  Nothing wraps round the border.  A diagonal move may pass between two blocked cells; the scene call's clearance is what keeps a
+ *   robot off them.
+ * Weights.  Every operation is a separately rounded fp32 one (fl), as in the distance rule.  For a move (di, dj, dk): a_x = (float)di * step3[0], a_y and
+ *   a_z likewise; len = sqrtf(((a_x * a_x) + (a_y * a_y)) + (a_z * a_z)), the correctly rounded root: mon_distance_transform's dist between the two cells.
+ *   Without cell_cost w(u, v) = len.  With cell_cost, a per-cell multiplier c that is finite and >= 0: w(u, v) = fl(len * fl(0.5f * fl(c[u] + c[v]))),
+ *   symmetric in u and v.
+ * Cost.  cost[v] = the least value of the left fold c_0 = 0, c_(i+1) = fl(c_i + w(p_i, p_(i+1))) over all walks p_0 .. p_k = v through passable cells that
+ *   start at a seed; +inf without such a walk and on a cell outside the mask; 0 at a passable seed.  A seed on a cell outside the mask contributes nothing;
+ *   duplicate seeds are allowed.  fp32 addition is monotone and fl(c + w) >= c for w >= 0, so this minimum is the fixed point that the
+ *   relaxations cost[v] = min(cost[v], fl(cost[u] + w(u, v))) reach from 0 at the seeds and +inf elsewhere under any order, bit for bit: equal arguments
+ *   give equal bits, whatever computes them.
+ * max_cost.  > 0; +inf: no limit.  Where !(cost <= max_cost): cost = +inf and next = -1; a cell at exactly max_cost keeps its value.
+ * next[v], the way to go: among the neighbours u of v, in ascending flat index, the first with cost[u] < cost[v] and fl(cost[u] + w(u, v)) == cost[v], taken
+ *   on the untruncated field; -1 at seeds, on unreachable, truncated and masked-out cells, and where no such neighbour exists (only where a weight is 0 or
+ *   absorbed by rounding, e.g. under a zero step).  Following next strictly lowers cost, so it ends: at a seed or at a -1.
+ * mon_shortest_paths: the field of a host mask (passable[nx * ny * nz]) on `device`; cell_cost [nx * ny * nz] or NULL (1 everywhere: w = len); seeds
+ *   [n_seeds] flat indices; next may be NULL.
+ * mon_scene_paths_lattice: the object map's field over the lattice of mon_scene_query_lattice (the same points, sides, objects and passes).  Passable is
+ *   dist > clearance, dist being mon_scene_distance_lattice's for the same arguments with max_dist = +inf, bit for bit: the mask of
+ *   mon_scene_components_lattice's region 1.  soft_weight == 0: no multiplier, soft_radius is ignored.  soft_weight > 0:
+ *   c[v] = fl(1 + fl(soft_weight * fl(fmaxf(0, fl(soft_radius - dist[v])) / soft_radius))): dearer near matter, 1 from soft_radius outward and where dist
+ *   is +inf.  dist, sigma and owner are those calls' rows (owner: an index into objs or -1), each copied home only when asked for; all outputs but cost may
+ *   be NULL.  Everything runs on the device behind the query with one copy home; the number of relaxation sweeps depends on the map, so the host reads one
+ *   small word back per batch of sweeps.
+ * mon_lattice_path (host only): the cells from start along next: path[0] = start, then next[start], ... up to the first -1; at most cap cells are written
+ *   (path may be NULL when cap is 0); *n_path is the whole length even when cap is smaller.
+ * Returns:
+ *   MON_ERR_ARG    everything mon_distance_transform / mon_scene_distance_lattice and the components calls refuse for the arguments they share (mask, step3,
+ *                  origin3, objs or an element NULL; the shape; a non-finite step or origin; sigma_min; side; n_objs; devices; connectivity not 6, 18 or 26);
+ *                  cost or seeds NULL; n_seeds 0 or above 2^22; a seed outside 0 .. nx * ny * nz - 1; max_cost <= 0 or NaN; clearance or soft_weight
+ *                  negative or not finite; soft_weight > 0 with soft_radius not finite or <= 0; mon_shortest_paths with a cell_cost entry negative or not
+ *                  finite -- all before any device work, the outputs untouched.  mon_lattice_path: next or n_path NULL, start or an entry met on the walk
+ *                  outside -1 .. n_cells - 1 (start: not -1), a walk longer than n_cells (a damaged array); path and n_path untouched
+ *   MON_ERR_STATE  as mon_scene_query_lattice; also a field that did not settle within nx * ny * nz + 1 sweeps (Bellman-Ford cannot need more), the
+ *                  outputs untouched;   MON_ERR_NO_DEVICE  mon_shortest_paths without a device, after its checks */
+int mon_shortest_paths(int device, const uint8_t* passable, int nx, int ny, int nz, const float* step3, int connectivity,
+                       const float* cell_cost, const int32_t* seeds, size_t n_seeds, float max_cost, float* cost, int32_t* next);
+int mon_scene_paths_lattice(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz,
+                            float sigma_min, float clearance, float soft_radius, float soft_weight, int connectivity,
+                            const int32_t* seeds, size_t n_seeds, float max_cost,
+                            float* cost, int32_t* next, float* dist, float* sigma, int32_t* owner);
+int mon_lattice_path(const int32_t* next, size_t n_cells, int32_t start, int32_t* path, size_t cap, size_t* n_path);
 /* Object pose refinement through the trained field (iNeRF-style): align the object with observed frames by following the gradient of a photometric,
  * silhouette and depth error with respect to the 6-DoF pose Tow.
  * Objective.  obs names frames of the object's dataset (FrameId) and pixel boxes inside them; the target of a pixel is that frame's rgb c*, its instance map
@@ -798,6 +846,12 @@ int mon_online_components_lattice(mon_online* mgr, const float* origin3, const f
                                   float sigma_min, int region, float clearance, int connectivity,
                                   int32_t* label, int32_t* comp, mon_lattice_component* table, uint32_t cap, uint32_t* n_components,
                                   float* dist, float* sigma, int32_t* owner);
+/* mon_scene_paths_lattice (side 1) over the same objects, with the same refusals; owner holds the manager's object indices.  A planner's call for the cost
+ * to its goal (seeds = the goal's cell) and the way there (mon_lattice_path from the robot's cell), safe while the objects train. */
+int mon_online_paths_lattice(mon_online* mgr, const float* origin3, const float* step3, int nx, int ny, int nz,
+                             float sigma_min, float clearance, float soft_radius, float soft_weight, int connectivity,
+                             const int32_t* seeds, size_t n_seeds, float max_cost,
+                             float* cost, int32_t* next, float* dist, float* sigma, int32_t* owner);
 /* mon_scene_query_gradients / mon_scene_cast_normals (side 1) over the same objects, with the same refusals.  owner, instance and hit_instance hold the
  * manager's object indices, and so does select: -1, or the index of an object with published weights; any other value is MON_ERR_ARG.
  * mon_online_cast_normals picks the objects once for both steps of its rule.  There is no online lattice form of the gradients: a caller forms the lattice

@@ -114,6 +114,9 @@ int mon_debug_scene_composite_grad(int device, uint32_t n_rays, uint32_t n_lists
 /* HIP-event time of the pack / unpack kernels of mon_object_save / mon_object_load calls made by this thread (tools/checkpoint_timing.py): enable != 0
  * starts collecting -- each kernel is bracketed by two events --, *kernel_ms (may be NULL) = the sum since the last call, which is then cleared. */
 int mon_debug_checkpoint_timing(int enable, double* kernel_ms);
+/* The sweeps of the process's latest shortest-path field (mon_shortest_paths, mon_scene_paths_lattice, mon_online_paths_lattice; tools/scene_paths_timing.py):
+ * out3 = { sweeps enqueued, batches (one read-back each), sweeps that left work for the next one }. */
+int mon_debug_paths_stats(uint32_t* out3);
 
 #ifdef __cplusplus
 }

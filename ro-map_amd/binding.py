@@ -224,6 +224,13 @@ _SIGS = {
             C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_online_components_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_shortest_paths": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p,
+            C.c_void_p]),
+    "mon_scene_paths_lattice": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
+            C.c_float, C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_online_paths_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+            C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_lattice_path": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mon_object_query_gradients": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_scene_query_gradients": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -296,6 +303,7 @@ _DIAG_SIGS = {
     "mon_debug_set_train_occupancy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mon_debug_set_render_grid": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mon_debug_checkpoint_timing": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
+    "mon_debug_paths_stats": (C.c_int, [C.c_void_p]),
     "mon_debug_scene_samples": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, MonBBox, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_debug_scene_composite": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -979,6 +987,16 @@ class OnlineManager:
                                                                                 float(clearance), int(connectivity), *a),
                                 max(nx, 0) * max(ny, 0) * max(nz, 0), cap, rows)
 
+    def paths_lattice(self, origin, step, shape, sigma_min, seeds, clearance=0.0, soft_radius=0.0, soft_weight=0.0, connectivity=26, max_cost=np.inf,
+                      rows=()):
+        """mon_online_paths_lattice: scene_paths_lattice on side 1 over every object with published weights (safe while they train); the owner row
+        holds the manager's object indices."""
+        o, s, nx, ny, nz = _lattice_args(origin, step, shape)
+        return _paths_call(lambda sd, ns, *a: lib().mon_online_paths_lattice(self.h, _p(o), _p(s), nx, ny, nz, float(sigma_min), float(clearance),
+                                                                              float(soft_radius), float(soft_weight), int(connectivity), sd, ns,
+                                                                              float(max_cost), *a),
+                           max(nx, 0) * max(ny, 0) * max(nz, 0), seeds, rows)
+
     def query_gradients(self, world_xyz, level_weights=None, select=None):
         """mon_online_query_gradients: query_scene_gradients on side 1 over every object with published weights (safe while they train); owner and
         select hold the manager's object indices."""
@@ -1316,6 +1334,60 @@ def scene_components_lattice(objects, origin, step, shape, sigma_min, region=0, 
     return _components_call(lambda *a: lib().mon_scene_components_lattice(_handles(objects), len(objects), int(side), _p(o), _p(s), nx, ny, nz,
                                                                           float(sigma_min), int(region), float(clearance), int(connectivity), *a),
                             max(nx, 0) * max(ny, 0) * max(nz, 0), cap, rows)
+
+
+def _paths_call(call, n, seeds, rows):
+    """call(seeds, n_seeds, cost, next, dist, sigma, owner) with fresh arrays of n cells; rows: which of "dist", "sigma", "owner" to bring home.
+    -> (cost, next, {row: array})"""
+    assert set(rows) <= {"dist", "sigma", "owner"}, rows
+    sd = np.ascontiguousarray(seeds, np.int32).reshape(-1)
+    cost = np.empty(n, np.float32); nxt = np.empty(n, np.int32)
+    opt = {k: np.empty(n, np.int32 if k == "owner" else np.float32) for k in rows}
+    _check(call(_p(sd), sd.size, _p(cost), _p(nxt), *[_p(opt.get(k)) for k in ("dist", "sigma", "owner")]))
+    return cost, nxt, opt
+
+
+def shortest_paths(mask, seeds, step, connectivity=26, cell_cost=None, max_cost=np.inf, device=0):
+    """mon_shortest_paths: the shortest-path cost field of a mask of shape (nz, ny, nx) (x fastest; a cell is passable iff it is not 0) from the seeds (flat
+    indices) with spacing step = (sx, sy, sz) under 6-, 18- or 26-connectivity; cell_cost: a per-cell multiplier of the mask's shape (None: 1).  Returns
+    (cost, next), both of the mask's shape: the least fp32 fold of the move weights over all walks from a seed (+inf: unreachable, outside the mask or
+    above max_cost) and the flat index of the neighbour to step to (-1: a seed, no way, or no strictly cheaper neighbour that explains the cost)."""
+    m = np.ascontiguousarray(mask); assert m.ndim == 3, "mask of shape (nz, ny, nx)"
+    m = np.ascontiguousarray(m != 0, np.uint8); nz, ny, nx = m.shape
+    s = np.ascontiguousarray(step, np.float32).reshape(3)
+    c = None if cell_cost is None else np.ascontiguousarray(cell_cost, np.float32)
+    assert c is None or c.size == m.size, "cell_cost of the mask's shape"
+    cost, nxt, _ = _paths_call(lambda sd, ns, co, nx_, *_: lib().mon_shortest_paths(int(device), _p(m), nx, ny, nz, _p(s), int(connectivity), _p(c), sd, ns,
+                                                                                     float(max_cost), co, nx_), m.size, seeds, ())
+    return cost.reshape(m.shape), nxt.reshape(m.shape)
+
+
+def scene_paths_lattice(objects, origin, step, shape, sigma_min, seeds, clearance=0.0, soft_radius=0.0, soft_weight=0.0, connectivity=26, max_cost=np.inf,
+                        side=0, rows=()):
+    """mon_scene_paths_lattice: the object map's shortest-path cost field over the lattice of query_scene_lattice: passable where scene_distance_lattice's
+    dist > clearance, a move dearer by up to 1 + soft_weight within soft_radius of matter.  Returns (cost, next, rows), the first two of nx * ny * nz
+    elements, as shortest_paths'; rows = {name: array} for the names asked for among "dist", "sigma" and "owner"."""
+    o, s, nx, ny, nz = _lattice_args(origin, step, shape)
+    return _paths_call(lambda sd, ns, *a: lib().mon_scene_paths_lattice(_handles(objects), len(objects), int(side), _p(o), _p(s), nx, ny, nz, float(sigma_min),
+                                                                        float(clearance), float(soft_radius), float(soft_weight), int(connectivity), sd, ns,
+                                                                        float(max_cost), *a),
+                       max(nx, 0) * max(ny, 0) * max(nz, 0), seeds, rows)
+
+
+def lattice_path(next, start):
+    """mon_lattice_path: the flat indices from start along next (as shortest_paths returns it) to the first -1, start included."""
+    nx_ = np.ascontiguousarray(next, np.int32).reshape(-1); n = C.c_size_t(0)
+    _check(lib().mon_lattice_path(_p(nx_), nx_.size, int(start), None, 0, C.byref(n)))
+    path = np.empty(n.value, np.int32)
+    _check(lib().mon_lattice_path(_p(nx_), nx_.size, int(start), _p(path), path.size, C.byref(n)))
+    return path
+
+
+def paths_stats():
+    """mon_debug_paths_stats: (sweeps enqueued, batches, sweeps that left work) of the process's latest shortest-path field."""
+    out = np.zeros(3, np.uint32)
+    _check(diag_lib().mon_debug_paths_stats(_p(out)))
+    return tuple(int(v) for v in out)
 
 
 def scene_point_rows(objects, world_xyz, k, side=0):

@@ -185,6 +185,23 @@ int mon_scene_components_lattice(mon_object* const* objs, size_t n_objs, int sid
     return scene_components(ms.data(), n_objs, side, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, region, clearance, connectivity, label, comp, table,
                             cap, n_components, dist, sigma, owner, nullptr);
 }
+int mon_shortest_paths(int device, const uint8_t* passable, int nx, int ny, int nz, const float* step3, int connectivity, const float* cell_cost,
+        const int32_t* seeds, size_t n_seeds, float max_cost, float* cost, int32_t* next) {
+    { const int rc = shortest_paths_check(passable, nx, ny, nz, step3, connectivity, cell_cost, seeds, n_seeds, max_cost, cost); if (rc) return rc; }
+    return shortest_paths(device, passable, nx, ny, nz, step3, connectivity, cell_cost, seeds, n_seeds, max_cost, cost, next);
+}
+int mon_scene_paths_lattice(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min,
+        float clearance, float soft_radius, float soft_weight, int connectivity, const int32_t* seeds, size_t n_seeds, float max_cost, float* cost,
+        int32_t* next, float* dist, float* sigma, int32_t* owner) {
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_paths_check(side, origin3, step3, nx, ny, nz, sigma_min, clearance, soft_radius, soft_weight, connectivity, seeds, n_seeds, max_cost, cost)) ||
+        (rc = scene_models("scene_paths", objs, n_objs, ms)) || (rc = scene_objects_check("scene_paths", ms.data(), n_objs, false))) return rc;
+    return scene_paths(ms.data(), n_objs, side, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, clearance, soft_radius, soft_weight, connectivity, seeds,
+                       n_seeds, max_cost, cost, next, dist, sigma, owner, nullptr);
+}
+int mon_lattice_path(const int32_t* next, size_t n_cells, int32_t start, int32_t* path, size_t cap, size_t* n_path) {
+    return lattice_path(next, n_cells, start, path, cap, n_path);
+}
 int mon_object_query_gradients(mon_object* o, int side, const float* unit_xyz, size_t n, const float* level_weights, float* raw4, float* grad_unit) {
     { const int rc = object_gradients_check(side, unit_xyz, n, level_weights, grad_unit); if (rc) return rc; }
     REQUIRE(o, "object");

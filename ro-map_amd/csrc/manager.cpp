@@ -776,6 +776,17 @@ int mon_online_components_lattice(mon_online* h, const float* origin3, const flo
     return scene_components(ms.data(), ms.size(), 1, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, region, clearance, connectivity, label, comp, table,
                             cap, n_components, dist, sigma, owner, ids.data());
 }
+// how far the goal is and which way to go over a planner's lattice: mon_scene_paths_lattice on side 1 over the same objects; owner holds the manager's indices
+int mon_online_paths_lattice(mon_online* h, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float clearance,
+        float soft_radius, float soft_weight, int connectivity, const int32_t* seeds, size_t n_seeds, float max_cost, float* cost, int32_t* next, float* dist,
+        float* sigma, int32_t* owner) {
+    REQ(h);
+    std::vector<Model*> ms; std::vector<int32_t> ids; int rc;
+    if ((rc = scene_paths_check(1, origin3, step3, nx, ny, nz, sigma_min, clearance, soft_radius, soft_weight, connectivity, seeds, n_seeds, max_cost, cost)) ||
+        (rc = online_published(h, "paths_lattice", 0, false, ms, &ids)) || (rc = scene_objects_check("scene_paths", ms.data(), ms.size(), false))) return rc;
+    return scene_paths(ms.data(), ms.size(), 1, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, clearance, soft_radius, soft_weight, connectivity, seeds,
+                       n_seeds, max_cost, cost, next, dist, sigma, owner, ids.data());
+}
 // ... with the field's derivative: mon_scene_query_gradients on side 1 over the same objects.  select names objects as owner does, by the manager's index:
 // -1, or the index of an object with published weights (anything else is MON_ERR_ARG; what is below -1 is refused before the objects are looked at).
 int mon_online_query_gradients(mon_online* h, const float* world_xyz, size_t n, const float* level_weights, const int32_t* select, float* sigma, float* rgb,

@@ -388,6 +388,19 @@ void launch_components(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t 
         uint32_t* scan, mon_lattice_component* table, uint32_t cap, uint32_t* meta);
 void launch_components_clear_mask(hipStream_t s, uint32_t n, const float* dist, float clearance, uint8_t* occ);
 void launch_components_home(hipStream_t s, const uint32_t* src, uint32_t* dst, uint32_t n_words, uint32_t table_word, uint32_t table_cap, const uint32_t* meta);
+// Shortest-path cost fields (mon_shortest_paths, mon_scene_paths_lattice; kernels_paths.hip).  occ: the passable cells; mult: the per-cell multiplier or
+// nullptr (none); flags: 2 * paths_tiles(nx, ny, nz) bytes.  launch_paths_init: cost = +inf, 0 at the passable seeds (device array, every entry below n), the
+// flags of sweep 0.  launch_paths_sweep: sweep number `sweep` (0, 1, ...: they alternate between the two rows of flags); *raised becomes 1 iff the sweep left
+// work for the next one (the caller clears it).  launch_paths_finish: next (may be nullptr) on the untruncated cost, then cost_out (another array than
+// cost) = cost cut at max_cost.  launch_paths_soft: the scene call's multiplier from a distance row.  connectivity is 6, 18 or 26 (checked by the caller).
+uint32_t paths_tiles(uint32_t nx, uint32_t ny, uint32_t nz);
+void launch_paths_init(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, const int32_t* seeds, uint32_t n_seeds, float* cost,
+        uint8_t* flags);
+void launch_paths_sweep(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, const float* step3, int connectivity, const float* mult,
+        float* cost, uint8_t* flags, uint32_t sweep, uint32_t* raised);
+void launch_paths_finish(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, const float* step3, int connectivity, const float* mult,
+        const float* cost, float max_cost, float* cost_out, int32_t* next);
+void launch_paths_soft(hipStream_t s, uint32_t n, const float* dist, float soft_radius, float soft_weight, float* mult);
 // Pose refinement (mon_object_pose_loss / mon_object_refine_pose, kernels_pose.hip).  k_pose_rays: one record of 4 float4 per drawn ray from the pose in
 // device memory (pose[16], world -> object); k_pose_grad<shape>: loss and position gradient, one partial row of 8 floats {g, x x g, loss, 0} per workgroup
 // (pose_grad_grid of them); k_pose_update: the rows summed in a fixed order, x inv_n -> out[8 * it] = {loss, grad6, 0}, optionally the Adam step on pose.
@@ -780,6 +793,23 @@ int scene_components_check(int side, const float* origin3, const float* step3, i
 int scene_components(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, int region, float clearance, int connectivity,
                      int32_t* label, int32_t* comp, mon_lattice_component* table, uint32_t cap, uint32_t* n_components, float* dist, float* sigma,
                      int32_t* owner, const int32_t* ids);
+// Shortest-path cost fields (mon_shortest_paths, mon_scene_paths_lattice, mon_lattice_path): shortest_paths = the field of a host mask in buffers of its own
+// (MON_ERR_NO_DEVICE without a device, after its check).  scene_paths = the lattice query, the untruncated distance transform of !(sigma <= sigma_min), the
+// mask dist > clearance, the multiplier (soft_weight > 0) and the field behind them on the device; every output but cost may be nullptr; ids as
+// scene_points', applied to owner.  The sweeps are enqueued in batches of kPathsBatch with one 4-byte read-back each; more than n + 1 sweeps: MON_ERR_STATE.
+// paths_last_stats: { sweeps enqueued, batches, sweeps that left work } of the process's latest field (mon_debug_paths_stats).  lattice_path: the walk
+// along next, on the host.
+int shortest_paths_check(const uint8_t* passable, int nx, int ny, int nz, const float* step3, int connectivity, const float* cell_cost, const int32_t* seeds,
+                         size_t n_seeds, float max_cost, const float* cost);
+int shortest_paths(int device, const uint8_t* passable, int nx, int ny, int nz, const float* step3, int connectivity, const float* cell_cost,
+                   const int32_t* seeds, size_t n_seeds, float max_cost, float* cost, int32_t* next);
+int scene_paths_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float clearance, float soft_radius,
+                      float soft_weight, int connectivity, const int32_t* seeds, size_t n_seeds, float max_cost, const float* cost);
+int scene_paths(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, float clearance, float soft_radius, float soft_weight,
+                int connectivity, const int32_t* seeds, size_t n_seeds, float max_cost, float* cost, int32_t* next, float* dist, float* sigma, int32_t* owner,
+                const int32_t* ids);
+void paths_last_stats(uint32_t out3[3]);
+int lattice_path(const int32_t* next, size_t n_cells, int32_t start, int32_t* path, size_t cap, size_t* n_path);
 // Point gradients (mon_scene_query_gradients / _lattice_gradients, mon_object_query_gradients): the point queries' conventions, plus level_w (host, may be
 // nullptr = all 1: Lmax floats, object j reads its first L_j; the *_check judges the first, scene_gradients_weights_check the rest once the objects are
 // known) and select (host, [n] or nullptr: -1 or an index into ms).  rows (mon_debug_scene_gradient_rows) = object rows_k's rows, host array [n][16].

@@ -138,6 +138,8 @@ struct SceneWs {
     DevBuf<uint16_t> gfrag; DevBuf<float> lw; DevBuf<int32_t> sel;                // gradients (rows of 16): full fragment images, weights [Lmax], select [n]
     DevBuf<uint8_t> docc; DevBuf<float> dv; DevBuf<int32_t> dsite;                // scene_distance: the mask [n], the passes' squared distances and sites [2][n]
     DevBuf<uint32_t> cscan;                                                       // scene_components: the numbering's block sums (its mask is docc)
+    DevBuf<float> pcost, pmul; DevBuf<int32_t> pseeds; DevBuf<uint8_t> pflags;    // scene_paths: the working cost [n], the multiplier [n], the seeds, two flag
+    DevBuf<uint32_t> praised; PinnedBuf<uint32_t> h_raised;                       // bytes per tile, a batch's "left work" words and their pinned copy (mask: docc)
     std::vector<hipEvent_t> ev;
 };
 // what each object renders with on a side; bits: its render grid (nullptr: none, or a call that consults no skipping)

@@ -1,7 +1,9 @@
 // scene_field.cpp -- the field queries: the object map asked at places instead of along rays.  Points and lattices (density, colour, owner), their
-// gradients and normals, normals at ray hits, distance fields and connected components over a lattice.  One host chain: a SceneCall
-// (scene.cpp) without lists or grids, the passes of field_passes_enqueue, each route's own kernels behind them, one copy home and one synchronisation.
+// gradients and normals, normals at ray hits, distance fields, connected components and shortest-path cost fields over a lattice.  One host chain
+// (DESIGN.md 3.4c-4): a SceneCall (scene.cpp) without lists or grids, the passes of field_passes_enqueue, each route's own kernels behind them, one copy
+// home and one synchronisation (the cost fields: one more per batch of sweeps).
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include "model_internal.h"
@@ -438,6 +440,155 @@ int scene_components(Model* const* ms, size_t n, int side, const ScenePoints& q,
     if (dist) std::memcpy(dist, h + r_dist, 4 * n_q);
     if (sigma) std::memcpy(sigma, h + f.sigma, 4 * n_q);
     if (owner) scene_instances_home(owner, h + f.owner, n_q, ids);
+    return MON_OK;
+}
+
+// ---- shortest-path cost fields (mon_shortest_paths, mon_scene_paths_lattice, mon_lattice_path): how far the goal is through the space the
+// robot may occupy, and which way to go.  scene_paths runs the chain over the lattice, k_distance_mask, the untruncated transform, the mask dist > clearance
+// (written over the first mask, as scene_components does), the multiplier, then the sweeps (paths_relax) and the finish, one copy home.  How many sweeps
+// the field needs depends on the data, so they are enqueued in batches of kPathsBatch, each sweep with a "left work" word of its own, and the words are
+// read back once per batch: one small synchronisation per batch, not per sweep.  The sweeps behind the first one that left no work found no flag and
+// returned at once.  A variant build (tools/variant_build.sh <tag> -DMON_PATHS_BATCH=n) takes another batch for measurements (tools/scene_paths_timing.py,
+// profiles/r21_scene_paths.md); outputs do not depend on it.
+#ifndef MON_PATHS_BATCH
+#define MON_PATHS_BATCH 32
+#endif
+constexpr uint32_t kPathsBatch = MON_PATHS_BATCH, kPathsMaxSeeds = 1u << 22;
+static std::atomic<uint32_t> g_paths_stats[3];                                      // (the sides' calls may overlap: the latest writer's figures)
+void paths_last_stats(uint32_t out3[3]) { for (int k = 0; k < 3; ++k) out3[k] = g_paths_stats[k].load(); }
+
+static int paths_args_check(const char* what, int connectivity, const int32_t* seeds, size_t n_seeds, size_t n_cells, float max_cost, const float* cost) {
+    REQUIRE_ARG(what, cost, "cost"); REQUIRE_ARG(what, seeds, "seeds");
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26) { set_error("%s: connectivity %d (6, 18 or 26)", what, connectivity); return MON_ERR_ARG; }
+    if (!(max_cost > 0.f)) { set_error("%s: max_cost %g (above 0; +inf for no limit)", what, (double)max_cost); return MON_ERR_ARG; }
+    if (n_seeds == 0 || n_seeds > kPathsMaxSeeds) { set_error("%s: %zu seeds (1 to %u)", what, n_seeds, kPathsMaxSeeds); return MON_ERR_ARG; }
+    for (size_t k = 0; k < n_seeds; ++k) if (seeds[k] < 0 || (size_t)seeds[k] >= n_cells) {
+        set_error("%s: seed %zu is cell %d (0 to %zu)", what, k, seeds[k], n_cells - 1); return MON_ERR_ARG; }
+    return MON_OK;
+}
+int shortest_paths_check(const uint8_t* passable, int nx, int ny, int nz, const float* step3, int connectivity, const float* cell_cost, const int32_t* seeds,
+                         size_t n_seeds, float max_cost, const float* cost) {
+    REQUIRE_ARG("shortest_paths", passable, "passable"); REQUIRE_ARG("shortest_paths", step3, "step");
+    { const int rc = lattice_dims_check("shortest_paths", nx, ny, nz); if (rc) return rc; }
+    for (int a = 0; a < 3; ++a) if (!std::isfinite(step3[a])) { set_error("shortest_paths: step is not finite"); return MON_ERR_ARG; }
+    const size_t n = (size_t)nx * ny * nz;
+    { const int rc = paths_args_check("shortest_paths", connectivity, seeds, n_seeds, n, max_cost, cost); if (rc) return rc; }
+    if (cell_cost) for (size_t i = 0; i < n; ++i) if (!std::isfinite(cell_cost[i]) || cell_cost[i] < 0.f) {
+        set_error("shortest_paths: cell_cost[%zu] is %g (finite, >= 0)", i, (double)cell_cost[i]); return MON_ERR_ARG; }
+    return MON_OK;
+}
+int scene_paths_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float clearance, float soft_radius,
+                      float soft_weight, int connectivity, const int32_t* seeds, size_t n_seeds, float max_cost, const float* cost) {
+    { const int rc = lattice_shape_check("scene_paths", origin3, step3, nx, ny, nz); if (rc) return rc; }
+    { const int rc = side_check("scene_paths", side); if (rc) return rc; }
+    if (!std::isfinite(sigma_min) || sigma_min < 0.f) { set_error("scene_paths: sigma_min %g (finite, >= 0)", (double)sigma_min); return MON_ERR_ARG; }
+    if (!std::isfinite(clearance) || clearance < 0.f) { set_error("scene_paths: clearance %g (finite, >= 0)", (double)clearance); return MON_ERR_ARG; }
+    if (!std::isfinite(soft_weight) || soft_weight < 0.f) { set_error("scene_paths: soft_weight %g (finite, >= 0)", (double)soft_weight); return MON_ERR_ARG; }
+    if (soft_weight > 0.f && (!std::isfinite(soft_radius) || !(soft_radius > 0.f))) {
+        set_error("scene_paths: soft_radius %g (finite, above 0, with a soft_weight above 0)", (double)soft_radius); return MON_ERR_ARG; }
+    return paths_args_check("scene_paths", connectivity, seeds, n_seeds, (size_t)nx * ny * nz, max_cost, cost);
+}
+// The sweeps on stream s until one leaves no work.  d_raised: kPathsBatch words on the device, h_raised: as many on the host (pinned in the scene call).
+// At most n + 1 sweeps: a sweep that leaves work has carried some cell's least walk across a tile border, and Bellman-Ford needs no more than n rounds.
+static int paths_relax(const char* what, hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, const float* step3, int connectivity,
+                       const float* mult, float* cost, uint8_t* flags, uint32_t* d_raised, uint32_t* h_raised) {
+    const uint64_t cap = (uint64_t)nx * ny * nz + 1u;
+    uint32_t sweeps = 0, batches = 0;
+    for (;;) {
+        const uint32_t b = (uint32_t)std::min<uint64_t>(kPathsBatch, cap - sweeps);
+        HIPCHECK(hipMemsetAsync(d_raised, 0, 4 * (size_t)b, s));
+        for (uint32_t k = 0; k < b; ++k) launch_paths_sweep(s, occ, nx, ny, nz, step3, connectivity, mult, cost, flags, sweeps + k, d_raised + k);
+        HIPCHECK(hipMemcpyAsync(h_raised, d_raised, 4 * (size_t)b, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));
+        HIPCHECK(hipGetLastError());
+        uint32_t busy = 0; while (busy < b && h_raised[busy]) ++busy;
+        g_paths_stats[0] = sweeps + b; g_paths_stats[1] = ++batches; g_paths_stats[2] = sweeps + busy;
+        if (busy < b) return MON_OK;
+        sweeps += b;
+        if (sweeps >= cap) { set_error("%s: the field did not settle within %llu sweeps; no output was written", what, (unsigned long long)cap); return MON_ERR_STATE; }
+    }
+}
+// mon_shortest_paths: the field alone on a host mask, in buffers of its own on the device's default stream.
+// w: working cost n | cost n | next n | multiplier n | seeds | a batch's words
+int shortest_paths(int device, const uint8_t* passable, int nx, int ny, int nz, const float* step3, int connectivity, const float* cell_cost,
+                   const int32_t* seeds, size_t n_seeds, float max_cost, float* cost, int32_t* next) {
+    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available"); return MON_ERR_NO_DEVICE; }
+    HIPCHECK(use_device(device));
+    const size_t n = (size_t)nx * ny * nz; const uint32_t ux = (uint32_t)nx, uy = (uint32_t)ny, uz = (uint32_t)nz;
+    DevBuf<uint8_t> occ, flags; DevBuf<uint32_t> w;
+    { int rc; if ((rc = occ.grow(n)) || (rc = flags.grow(2 * (size_t)paths_tiles(ux, uy, uz))) || (rc = w.grow(4 * n + n_seeds + kPathsBatch))) return rc; }
+    float* d_work = reinterpret_cast<float*>(w.p); float* d_cost = d_work + n; int32_t* d_next = reinterpret_cast<int32_t*>(w.p + 2 * n);
+    float* d_mult = cell_cost ? reinterpret_cast<float*>(w.p + 3 * n) : nullptr; int32_t* d_seeds = reinterpret_cast<int32_t*>(w.p + 4 * n);
+    uint32_t* d_raised = w.p + 4 * n + n_seeds;
+    HIPCHECK(hipMemcpy(occ.p, passable, n, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(d_seeds, seeds, 4 * n_seeds, hipMemcpyHostToDevice));
+    if (cell_cost) HIPCHECK(hipMemcpy(d_mult, cell_cost, 4 * n, hipMemcpyHostToDevice));
+    launch_paths_init(nullptr, occ.p, ux, uy, uz, d_seeds, (uint32_t)n_seeds, d_work, flags.p);
+    std::vector<uint32_t> h_raised(kPathsBatch);
+    { const int rc = paths_relax("shortest_paths", nullptr, occ.p, ux, uy, uz, step3, connectivity, d_mult, d_work, flags.p, d_raised, h_raised.data());
+      if (rc) return rc; }
+    launch_paths_finish(nullptr, occ.p, ux, uy, uz, step3, connectivity, d_mult, d_work, max_cost, d_cost, next ? d_next : nullptr);
+    HIPCHECK(hipGetLastError());
+    std::vector<uint32_t> h(next ? 2 * n : n);                                      // (the caller's arrays are written only once everything has succeeded)
+    HIPCHECK(hipMemcpy(h.data(), d_cost, 4 * h.size(), hipMemcpyDeviceToHost));
+    std::memcpy(cost, h.data(), 4 * n);
+    if (next) std::memcpy(next, h.data() + n, 4 * n);
+    return MON_OK;
+}
+// q: a lattice (scene_lattice).  ids as scene_points', applied to owner.
+int scene_paths(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, float clearance, float soft_radius, float soft_weight,
+                int connectivity, const int32_t* seeds, size_t n_seeds, float max_cost, float* cost, int32_t* next, float* dist, float* sigma, int32_t* owner,
+                const int32_t* ids) {
+    SceneCall c; { const int rc = c.enter("scene_paths", ms, n, side, false); if (rc) return rc; }
+    SceneWs& ws = *c.ws; const hipStream_t s = c.s;
+    const size_t n_q = q.n; const uint32_t nq = (uint32_t)n_q, pass = std::min(nq, kScenePointsPass);
+    const uint32_t nx = (uint32_t)q.nx, ny = (uint32_t)q.ny, nz = (uint32_t)q.nz;
+    // the output area, what may go home from the front (up to the last row asked for): cost | next | dist | sigma | owner, then the fold's other rows
+    Area A{ n_q }; const size_t r_cost = A.row(), r_next = A.row(), r_dist = A.row();
+    FoldRows f{}; f.sigma = A.row(); f.owner = A.row(); f.rgb = A.row(3); f.owner_sigma = A.row(); f.n_inside = A.row();
+    const size_t home = owner ? f.rgb : sigma ? f.owner : dist ? f.sigma : next ? r_dist : r_next;
+    {   int rc;
+        if ((rc = field_passes_prepare(c, n, q, pass, 12u)) || (rc = ws.out.grow(A.end)) || (rc = ws.h_out.grow(home)) || (rc = ws.docc.grow(n_q)) ||
+            (rc = ws.dv.grow(2 * n_q)) || (rc = ws.dsite.grow(2 * n_q)) || (rc = ws.pcost.grow(n_q)) || (soft_weight > 0.f && (rc = ws.pmul.grow(n_q))) ||
+            (rc = ws.pseeds.grow(n_seeds)) || (rc = ws.pflags.grow(2 * (size_t)paths_tiles(nx, ny, nz))) || (rc = ws.praised.grow(kPathsBatch)) ||
+            (rc = ws.h_raised.grow(kPathsBatch))) return rc; }
+    float* o = ws.out.p; const float* mult = soft_weight > 0.f ? ws.pmul.p : nullptr;
+    HIPCHECK(hipMemcpyAsync(ws.pseeds.p, seeds, 4 * n_seeds, hipMemcpyHostToDevice, s));
+    field_passes_enqueue(c, ms, n, q, true, pass, f, nullptr, 0, nullptr);
+    launch_distance_mask(s, nq, o + f.sigma, sigma_min, ws.docc.p);
+    launch_distance_passes(s, ws.docc.p, false, nx, ny, nz, q.step, ws.dv.p, ws.dsite.p);
+    launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, INFINITY, nullptr, o + r_dist, nullptr, nullptr);
+    launch_components_clear_mask(s, nq, o + r_dist, clearance, ws.docc.p);
+    if (mult) launch_paths_soft(s, nq, o + r_dist, soft_radius, soft_weight, ws.pmul.p);
+    launch_paths_init(s, ws.docc.p, nx, ny, nz, ws.pseeds.p, (uint32_t)n_seeds, ws.pcost.p, ws.pflags.p);
+    { const int rc = paths_relax("scene_paths", s, ws.docc.p, nx, ny, nz, q.step, connectivity, mult, ws.pcost.p, ws.pflags.p, ws.praised.p, ws.h_raised.p);
+      if (rc) return rc; }
+    launch_paths_finish(s, ws.docc.p, nx, ny, nz, q.step, connectivity, mult, ws.pcost.p, max_cost, o + r_cost,
+            next ? reinterpret_cast<int32_t*>(o + r_next) : nullptr);
+    { const int rc = c.home(home); if (rc) return rc; }
+    const float* h = ws.h_out.p;
+    std::memcpy(cost, h + r_cost, 4 * n_q);
+    if (next) std::memcpy(next, h + r_next, 4 * n_q);
+    if (dist) std::memcpy(dist, h + r_dist, 4 * n_q);
+    if (sigma) std::memcpy(sigma, h + f.sigma, 4 * n_q);
+    if (owner) scene_instances_home(owner, h + f.owner, n_q, ids);
+    return MON_OK;
+}
+// mon_lattice_path: the cells from start along next to the first -1.  A walk of more than n_cells cells has come by some cell twice: a damaged array.
+int lattice_path(const int32_t* next, size_t n_cells, int32_t start, int32_t* path, size_t cap, size_t* n_path) {
+    REQUIRE_ARG("lattice_path", next, "next"); REQUIRE_ARG("lattice_path", n_path, "n_path");
+    if (cap > 0) REQUIRE_ARG("lattice_path", path, "path");
+    if (start < 0 || (size_t)start >= n_cells) { set_error("lattice_path: start %d (0 to %zu)", start, n_cells ? n_cells - 1 : 0); return MON_ERR_ARG; }
+    size_t len = 0;
+    for (int32_t v = start; v != -1; v = next[v]) {                                 // first pass: the array is sound and the length known before path is touched
+        if (v < -1 || (size_t)v >= n_cells) { set_error("lattice_path: next holds %d behind cell %zu of the walk (-1, or 0 to %zu)", v, len, n_cells - 1);
+            return MON_ERR_ARG; }
+        if (++len > n_cells) { set_error("lattice_path: the walk from %d is longer than the lattice's %zu cells (next holds a cycle)", start, n_cells);
+            return MON_ERR_ARG; }
+    }
+    size_t k = 0;
+    for (int32_t v = start; v != -1 && k < cap; v = next[v]) path[k++] = v;
+    *n_path = len;
     return MON_OK;
 }
 
