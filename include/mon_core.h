@@ -456,6 +456,68 @@ int mon_scene_paths_lattice(mon_object* const* objs, size_t n_objs, int side, co
                             const int32_t* seeds, size_t n_seeds, float max_cost,
                             float* cost, int32_t* next, float* dist, float* sigma, int32_t* owner);
 int mon_lattice_path(const int32_t* next, size_t n_cells, int32_t start, int32_t* path, size_t cap, size_t* n_path);
+/* Device-resident distance fields and batched trajectory clearance: does this robot body, along these trajectories, stay clear of the map, by how much,
+ * where does it first touch, and which way should it be pushed -- asked many times per map publication by a planner that samples trajectories (the
+ * reference has no such call; opt-in, new, read-only; no existing call changes its bits).  A mon_dist_field is a SNAPSHOT of a distance field in device
+ * memory of its own, 4 bytes per cell: it holds no reference to objects or to a manager, does not follow later training, and outlives the objects and the
+ * manager it was made from; there is no cache to go stale.  Calls on one handle from several threads take turns on a mutex in the handle; different
+ * handles are independent.  No atomics: equal arguments give equal bits.  Every operation below is one separately rounded fp32 operation (fl); nothing is
+ * contracted.
+ * Field.  D[nx * ny * nz], i fastest, cell (i, j, k) at flat index (k * ny + j) * nx + i and at world point o + (i, j, k) * s (origin3 o, step3 s),
+ *   nx * ny * nz in 1 .. 2^22, every entry finite.  An axis with more than one cell has a finite step other than 0 (a negative one is fine); the step of
+ *   an axis of one cell is ignored.
+ * Sample of D at a world point p.  Per axis a with n_a > 1: g_a = fl(fl(p_a - o_a) / s_a); the point is inside on the axis iff 0 <= g_a <= (float)(n_a - 1)
+ *   (a NaN fails); i_a = min((int)floorf(g_a), n_a - 2); f_a = fl(g_a - (float)i_a).  An axis with n_a == 1 is neither interpolated nor range-checked:
+ *   i_a = 0, f_a = 0, its upper corner is the same cell and its gradient component is 0.  A point outside on any axis: d = outside, grad = 0.  Otherwise,
+ *   with lerp(a, b, f) = fl(a + fl(f * fl(b - a))):
+ *     along x  c_jk = lerp(D[i, j + dj, k + dk], D[i + 1, j + dj, k + dk], f_x)   (dj, dk in {0, 1}),     e_jk = fl(D[i + 1, ..] - D[i, ..])
+ *     along y  c_k = lerp(c_0k, c_1k, f_y),   h_k = fl(c_1k - c_0k),   e_k = lerp(e_0k, e_1k, f_y)
+ *     along z  d = lerp(c_0, c_1, f_z)
+ *     grad_x = fl(lerp(e_0, e_1, f_z) / s_x),   grad_y = fl(lerp(h_0, h_1, f_z) / s_y),   grad_z = fl(fl(c_1 - c_0) / s_z)     (world units)
+ * Body.  spheres[k] = { bx, by, bz, r } in the body frame, 1 <= n_spheres <= 32, offsets finite, r finite and >= 0.
+ * Waypoints.  ways[n_traj][n_way][way_floats]; the values are not checked, a centre that is not finite is simply outside.
+ *   way_floats 3: a position t; the centre of sphere b there is c = fl(t + b) per component (the body is not rotated).
+ *   way_floats 16: a row-major 4 x 4 matrix M, the layout of Twc16, its last row ignored; c_x = fl(fl(fl(fl(M00 b_x) + fl(M01 b_y)) + fl(M02 b_z)) + M03),
+ *     c_y and c_z likewise from rows 1 and 2.
+ * Samples.  Each of the n_way - 1 segments gives n_sub samples and the last waypoint one more: n_samp = (n_way - 1) * n_sub + 1.  Sample q = w * n_sub + u
+ *   (u < n_sub): for u == 0 the centre at waypoint w; otherwise fl(c_w + fl(tau * fl(c_(w+1) - c_w))) per component with tau = fl((float)u / (float)n_sub).
+ *   1 <= n_way <= 256, 1 <= n_sub <= 16, 1 <= n_traj <= 65 536, n_traj * n_samp <= 2^24.
+ * Outputs.  params = { outside, margin, safe }, all finite; clear(q, k) = fl(d - r_k), d the sample of D at the centre of sphere k at sample q.
+ *   min_clear[t]       = the least clear over all q and k (every value is finite, so the order cannot matter)
+ *   first_hit[t]       = the lowest q with some k where !(clear(q, k) > margin); -1 without one
+ *   cost[t]            = the pairwise tree over pen(0 .. n_samp - 1): pad with +0 to the next power of two, then level by level v'[i] = fl(v[2 i] +
+ *                        v[2 i + 1]) down to one value; pen(q) = the left fold over ascending k, from 0, of fl(h * h), h = fmaxf(0, fl(safe - clear(q, k)))
+ *   way_clear[t][w]    = the least clear(w * n_sub, k) over k
+ *   way_grad[t][w][3]  = the gradient of D at the centre of the lowest k that attains it; 0 0 0 when that centre is outside
+ * mon_dist_field_create: uploads a host field to `device`, as mon_marching_cubes serves density lattices.
+ * mon_scene_dist_field: mon_scene_distance_lattice's chain (the same sides, objects, points and passes) with dist kept in the handle's buffer: the handle's
+ *   cells are that call's dist for the same arguments bit for bit, and nothing per cell is copied home.  max_dist must be FINITE here, so that every value
+ *   lies in [0, max_dist].
+ * mon_dist_field_info: shape, origin, step, logical device and the largest value held.  mon_dist_field_read: the cells, dist_out[nx * ny * nz].
+ * mon_dist_field_sample: d (dist_out[n]) and grad (grad3_out[n][3], may be NULL) at xyz[n][3], 1 <= n <= 2^24; `outside` is returned as given.
+ * mon_dist_field_score: every output but min_clear may be NULL.  ways and spheres are uploaded per call; the outputs come home with one synchronisation.
+ * mon_dist_field_destroy: frees the handle and its device memory (NULL: nothing to do).
+ * Returns:
+ *   MON_ERR_ARG    field, dist, origin3, step3, objs or an element, xyz, dist_out, info, spheres, ways, params or min_clear NULL; the shape as the distance
+ *                  calls refuse it; a field entry or an origin that is not finite; an axis of more than one cell with a step that is 0 or not finite (the
+ *                  scene calls also refuse what mon_scene_distance_lattice refuses: any non-finite step, a lattice that leaves the finite floats,
+ *                  sigma_min, side, n_objs, objects on different logical devices); max_dist not finite or <= 0; n 0 or above 2^24; n_spheres, n_way, n_sub,
+ *                  n_traj or n_traj * n_samp outside their limits; way_floats not 3 or 16; a sphere that is not finite or has r < 0; a param that is not
+ *                  finite -- all before any device work, the outputs and *field untouched
+ *   MON_ERR_STATE  as mon_scene_query_lattice;   MON_ERR_NO_DEVICE  mon_dist_field_create without a device, after its checks */
+typedef struct mon_dist_field mon_dist_field;
+typedef struct mon_dist_field_desc { int32_t nx, ny, nz, device; float origin[3]; float step[3]; float max_value; } mon_dist_field_desc;   /* 44 bytes */
+typedef struct mon_traj_score_params { float outside, margin, safe; } mon_traj_score_params;
+int mon_dist_field_create(int device, const float* dist, int nx, int ny, int nz, const float* origin3, const float* step3, mon_dist_field** field);
+int mon_scene_dist_field(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz,
+                         float sigma_min, float max_dist, mon_dist_field** field);
+int mon_dist_field_info(mon_dist_field* field, mon_dist_field_desc* info);
+int mon_dist_field_read(mon_dist_field* field, float* dist_out);
+int mon_dist_field_sample(mon_dist_field* field, const float* xyz, size_t n, float outside, float* dist_out, float* grad3_out);
+int mon_dist_field_score(mon_dist_field* field, const float* spheres, size_t n_spheres, const float* ways, int way_floats, size_t n_traj, size_t n_way,
+                         size_t n_sub, const mon_traj_score_params* params, float* min_clear, int32_t* first_hit, float* cost, float* way_clear,
+                         float* way_grad);
+int mon_dist_field_destroy(mon_dist_field* field);
 /* Object pose refinement through the trained field (iNeRF-style): align the object with observed frames by following the gradient of a photometric,
  * silhouette and depth error with respect to the 6-DoF pose Tow.
  * Objective.  obs names frames of the object's dataset (FrameId) and pixel boxes inside them; the target of a pixel is that frame's rgb c*, its instance map
@@ -852,6 +914,11 @@ int mon_online_paths_lattice(mon_online* mgr, const float* origin3, const float*
                              float sigma_min, float clearance, float soft_radius, float soft_weight, int connectivity,
                              const int32_t* seeds, size_t n_seeds, float max_cost,
                              float* cost, int32_t* next, float* dist, float* sigma, int32_t* owner);
+/* mon_scene_dist_field (side 1) over the same objects, with the same refusals: the published map's clearance as a snapshot on the device, which a sampling
+ * planner scores its trajectories against (mon_dist_field_score) until the next publication.  The handle is the caller's: it does not follow the manager's
+ * training and stays valid after mon_online_destroy; mon_dist_field_destroy frees it. */
+int mon_online_dist_field(mon_online* mgr, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float max_dist,
+                          mon_dist_field** field);
 /* mon_scene_query_gradients / mon_scene_cast_normals (side 1) over the same objects, with the same refusals.  owner, instance and hit_instance hold the
  * manager's object indices, and so does select: -1, or the index of an object with published weights; any other value is MON_ERR_ARG.
  * mon_online_cast_normals picks the objects once for both steps of its rule.  There is no online lattice form of the gradients: a caller forms the lattice

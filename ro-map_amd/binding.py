@@ -77,6 +77,17 @@ SCENE_RAY_DTYPE = np.dtype([("o", np.float32, 3), ("t_max", np.float32), ("d", n
 LATTICE_COMPONENT_DTYPE = np.dtype([("rep", np.int32), ("cells", np.uint32), ("lo", np.int32, 3), ("hi", np.int32, 3)])
 
 
+class DistFieldDesc(C.Structure):
+    """mon_dist_field_desc (include/mon_core.h): what mon_dist_field_info reports of a field handle."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("device", C.c_int32), ("origin", C.c_float * 3), ("step", C.c_float * 3),
+                ("max_value", C.c_float)]
+
+
+class TrajScoreParams(C.Structure):
+    """mon_traj_score_params (include/mon_core.h): the value of a sample outside the field, the hit margin, the clearance below which a sample costs."""
+    _fields_ = [("outside", C.c_float), ("margin", C.c_float), ("safe", C.c_float)]
+
+
 class RelocResult(C.Structure):
     """mon_reloc_result (include/mon_core.h): which candidate won, whether its refined pose did, and the scores S[0], S[best], F[winner]."""
     _fields_ = [("best_candidate", C.c_uint32), ("refined", C.c_uint32), ("score_candidate0", C.c_float), ("score_best_candidate", C.c_float),
@@ -231,6 +242,16 @@ _SIGS = {
     "mon_online_paths_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
             C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_lattice_path": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mon_dist_field_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mon_scene_dist_field": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+            C.POINTER(C.c_void_p)]),
+    "mon_online_dist_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_void_p)]),
+    "mon_dist_field_info": (C.c_int, [C.c_void_p, C.POINTER(DistFieldDesc)]),
+    "mon_dist_field_read": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mon_dist_field_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
+    "mon_dist_field_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t,
+            C.POINTER(TrajScoreParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_dist_field_destroy": (C.c_int, [C.c_void_p]),
     "mon_object_query_gradients": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_scene_query_gradients": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -979,6 +1000,13 @@ class OnlineManager:
         _check(lib().mon_online_distance_lattice(self.h, _p(o), _p(s), nx, ny, nz, float(sigma_min), float(max_dist), *[_p(a) for a in out]))
         return out
 
+    def dist_field(self, origin, step, shape, sigma_min, max_dist):
+        """mon_online_dist_field: scene_dist_field on side 1 over every object with published weights -> DistField, which does not follow later training and
+        stays valid after the manager is gone"""
+        o, s, nx, ny, nz = _lattice_args(origin, step, shape); h = C.c_void_p()
+        _check(lib().mon_online_dist_field(self.h, _p(o), _p(s), nx, ny, nz, float(sigma_min), float(max_dist), C.byref(h)))
+        return DistField(h)
+
     def components_lattice(self, origin, step, shape, sigma_min, region=0, clearance=0.0, connectivity=6, cap=None, rows=()):
         """mon_online_components_lattice: scene_components_lattice on side 1 over every object with published weights (safe while they train); the
         owner row holds the manager's object indices."""
@@ -1299,6 +1327,80 @@ def scene_distance_lattice(objects, origin, step, shape, sigma_min, max_dist=np.
     _check(lib().mon_scene_distance_lattice(_handles(objects), len(objects), int(side), _p(o), _p(s), nx, ny, nz, float(sigma_min), float(max_dist),
                                             *[_p(a) for a in out]))
     return out
+
+
+class DistField:
+    """A mon_dist_field: a snapshot of a distance field in device memory (include/mon_core.h).  Made by dist_field_create, scene_dist_field or
+    OnlineManager.dist_field; it outlives the objects and the manager it came from.  close() (or the garbage collector) frees it."""
+
+    def __init__(self, handle):
+        self.h = handle
+
+    def close(self):
+        if self.h is not None and self.h.value:
+            _check(lib().mon_dist_field_destroy(self.h))
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        """mon_dist_field_info -> DistFieldDesc (nx, ny, nz, device, origin, step, max_value)"""
+        d = DistFieldDesc(); _check(lib().mon_dist_field_info(self.h, C.byref(d))); return d
+
+    def read(self):
+        """mon_dist_field_read: the cells, of shape (nz, ny, nx)"""
+        d = self.info(); out = np.empty((d.nz, d.ny, d.nx), np.float32)
+        _check(lib().mon_dist_field_read(self.h, _p(out))); return out
+
+    def sample(self, xyz, outside=0.0, grad=True):
+        """mon_dist_field_sample at world points (n, 3) -> (dist (n,), grad (n, 3), or None with grad=False)"""
+        x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3); n = x.shape[0]
+        dist = np.empty(n, np.float32); g = np.empty((n, 3), np.float32) if grad else None
+        _check(lib().mon_dist_field_sample(self.h, _p(x), n, float(outside), _p(dist), _p(g)))
+        return dist, g
+
+    def score(self, spheres, ways, n_sub=1, outside=0.0, margin=0.0, safe=0.0, outputs=("first_hit", "cost", "way_clear", "way_grad")):
+        """mon_dist_field_score.  spheres (n_spheres, 4) = (bx, by, bz, r); ways (n_traj, n_way, 3) positions or (n_traj, n_way, 16) / (n_traj, n_way, 4, 4)
+        row-major matrices.  -> a dict with min_clear (n_traj,) and those of first_hit (n_traj,) int32, cost (n_traj,), way_clear (n_traj, n_way) and way_grad
+        (n_traj, n_way, 3) that `outputs` names (the others are passed as NULL)."""
+        assert set(outputs) <= {"first_hit", "cost", "way_clear", "way_grad"}, outputs
+        b = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
+        w = np.ascontiguousarray(ways, np.float32); assert w.ndim in (3, 4), "ways of shape (n_traj, n_way, 3 | 16) or (n_traj, n_way, 4, 4)"
+        n_traj, n_way = w.shape[:2]; w = w.reshape(n_traj, n_way, -1); wf = w.shape[2]
+        prm = TrajScoreParams(float(outside), float(margin), float(safe))
+        out = {"min_clear": np.empty(n_traj, np.float32),
+               "first_hit": np.empty(n_traj, np.int32) if "first_hit" in outputs else None,
+               "cost": np.empty(n_traj, np.float32) if "cost" in outputs else None,
+               "way_clear": np.empty((n_traj, n_way), np.float32) if "way_clear" in outputs else None,
+               "way_grad": np.empty((n_traj, n_way, 3), np.float32) if "way_grad" in outputs else None}
+        _check(lib().mon_dist_field_score(self.h, _p(b), b.shape[0], _p(w), wf, n_traj, n_way, int(n_sub), C.byref(prm), _p(out["min_clear"]),
+                                          _p(out["first_hit"]), _p(out["cost"]), _p(out["way_clear"]), _p(out["way_grad"])))
+        return {k: v for k, v in out.items() if v is not None}
+
+
+def dist_field_create(dist, origin, step, device=0):
+    """mon_dist_field_create: a host field of shape (nz, ny, nx) (x fastest), cell (i, j, k) at origin + (i, j, k) * step, uploaded to `device` -> DistField"""
+    d = np.ascontiguousarray(dist, np.float32); assert d.ndim == 3, "field of shape (nz, ny, nx)"
+    nz, ny, nx = d.shape; o, s, _, _, _ = _lattice_args(origin, step, (nx, ny, nz)); h = C.c_void_p()
+    _check(lib().mon_dist_field_create(int(device), _p(d), nx, ny, nz, _p(o), _p(s), C.byref(h)))
+    return DistField(h)
+
+
+def scene_dist_field(objects, origin, step, shape, sigma_min, max_dist, side=0):
+    """mon_scene_dist_field: scene_distance_lattice's dist for the same arguments, kept on the device (nothing per cell comes home) -> DistField"""
+    o, s, nx, ny, nz = _lattice_args(origin, step, shape); h = C.c_void_p()
+    _check(lib().mon_scene_dist_field(_handles(objects), len(objects), int(side), _p(o), _p(s), nx, ny, nz, float(sigma_min), float(max_dist), C.byref(h)))
+    return DistField(h)
 
 
 def _components_call(call, n, cap, rows):

@@ -202,6 +202,31 @@ int mon_scene_paths_lattice(mon_object* const* objs, size_t n_objs, int side, co
 int mon_lattice_path(const int32_t* next, size_t n_cells, int32_t start, int32_t* path, size_t cap, size_t* n_path) {
     return lattice_path(next, n_cells, start, path, cap, n_path);
 }
+int mon_dist_field_create(int device, const float* dist, int nx, int ny, int nz, const float* origin3, const float* step3, mon_dist_field** field) {
+    { const int rc = dist_field_create_check(dist, nx, ny, nz, origin3, step3, field); if (rc) return rc; }
+    DistField* f = nullptr;
+    { const int rc = dist_field_create(device, dist, nx, ny, nz, origin3, step3, &f); if (rc) return rc; }
+    *field = new mon_dist_field{ f }; return MON_OK;
+}
+int mon_scene_dist_field(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min,
+        float max_dist, mon_dist_field** field) {
+    std::vector<Model*> ms; int rc; DistField* f = nullptr;
+    if ((rc = scene_dist_field_check(side, origin3, step3, nx, ny, nz, sigma_min, max_dist, field)) || (rc = scene_models("scene_dist_field", objs, n_objs, ms)) ||
+        (rc = scene_objects_check("scene_dist_field", ms.data(), n_objs, false)) ||
+        (rc = scene_dist_field(ms.data(), n_objs, side, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, max_dist, &f))) return rc;
+    *field = new mon_dist_field{ f }; return MON_OK;
+}
+int mon_dist_field_info(mon_dist_field* field, mon_dist_field_desc* info) { return dist_field_info(field ? field->f : nullptr, info); }
+int mon_dist_field_read(mon_dist_field* field, float* dist_out) { return dist_field_read(field ? field->f : nullptr, dist_out); }
+int mon_dist_field_sample(mon_dist_field* field, const float* xyz, size_t n, float outside, float* dist_out, float* grad3_out) {
+    return dist_field_sample(field ? field->f : nullptr, xyz, n, outside, dist_out, grad3_out);
+}
+int mon_dist_field_score(mon_dist_field* field, const float* spheres, size_t n_spheres, const float* ways, int way_floats, size_t n_traj, size_t n_way,
+        size_t n_sub, const mon_traj_score_params* params, float* min_clear, int32_t* first_hit, float* cost, float* way_clear, float* way_grad) {
+    return dist_field_score(field ? field->f : nullptr, spheres, n_spheres, ways, way_floats, n_traj, n_way, n_sub, params, min_clear, first_hit, cost, way_clear,
+                            way_grad);
+}
+int mon_dist_field_destroy(mon_dist_field* field) { if (field) { dist_field_free(field->f); delete field; } return MON_OK; }
 int mon_object_query_gradients(mon_object* o, int side, const float* unit_xyz, size_t n, const float* level_weights, float* raw4, float* grad_unit) {
     { const int rc = object_gradients_check(side, unit_xyz, n, level_weights, grad_unit); if (rc) return rc; }
     REQUIRE(o, "object");

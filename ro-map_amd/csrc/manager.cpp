@@ -787,6 +787,16 @@ int mon_online_paths_lattice(mon_online* h, const float* origin3, const float* s
     return scene_paths(ms.data(), ms.size(), 1, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, clearance, soft_radius, soft_weight, connectivity, seeds,
                        n_seeds, max_cost, cost, next, dist, sigma, owner, ids.data());
 }
+// the published map's clearance as a snapshot on the device: mon_scene_dist_field on side 1 over the same objects.  The handle refers to nothing of the
+// manager's
+int mon_online_dist_field(mon_online* h, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float max_dist,
+        mon_dist_field** field) {
+    REQ(h);
+    std::vector<Model*> ms; int rc; DistField* f = nullptr;
+    if ((rc = scene_dist_field_check(1, origin3, step3, nx, ny, nz, sigma_min, max_dist, field)) || (rc = online_published(h, "dist_field", 0, false, ms, nullptr)) || (rc = scene_objects_check("scene_dist_field", ms.data(), ms.size(), false)) ||
+        (rc = scene_dist_field(ms.data(), ms.size(), 1, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, max_dist, &f))) return rc;
+    *field = new mon_dist_field{ f }; return MON_OK;
+}
 // ... with the field's derivative: mon_scene_query_gradients on side 1 over the same objects.  select names objects as owner does, by the manager's index:
 // -1, or the index of an object with published weights (anything else is MON_ERR_ARG; what is below -1 is refused before the objects are looked at).
 int mon_online_query_gradients(mon_online* h, const float* world_xyz, size_t n, const float* level_weights, const int32_t* select, float* sigma, float* rgb,

@@ -401,6 +401,17 @@ void launch_paths_sweep(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t
 void launch_paths_finish(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, const float* step3, int connectivity, const float* mult,
         const float* cost, float max_cost, float* cost_out, int32_t* next);
 void launch_paths_soft(hipStream_t s, uint32_t n, const float* dist, float soft_radius, float soft_weight, float* mult);
+// Device-resident distance fields (mon_dist_field_*; kernels_clearance.hip).  DistFieldView: the field as the kernels take it (D: device, [nz][ny][nx]).
+// launch_field_sample: dist[n] and grad[n][3] (may be nullptr) at xyz[n][3].  launch_traj_score: the header's outputs of n_traj trajectories (device
+// arrays; all but min_clear may be nullptr); n_samp = (n_way - 1) n_sub + 1; the launch fills in pad.  launch_field_max: out[0] = the largest of v[0 .. n),
+// partial: kFieldMaxBlocks floats.
+struct DistFieldView { const float* D; int nx, ny, nz; float o[3], s[3]; };
+struct TrajScoreArgs { uint32_t n_traj, n_way, n_sub, n_samp, pad; float outside, margin, safe; float* min_clear; int32_t* first_hit; float* cost;
+                       float* way_clear; float* way_grad; };
+constexpr uint32_t kFieldMaxBlocks = 256;
+void launch_field_sample(hipStream_t s, const DistFieldView& F, const float* xyz, uint32_t n, float outside, float* dist, float* grad);
+void launch_traj_score(hipStream_t s, const DistFieldView& F, const float* spheres, uint32_t n_spheres, const float* ways, bool pose, TrajScoreArgs a);
+void launch_field_max(hipStream_t s, const float* v, uint32_t n, float* partial, float* out);
 // Pose refinement (mon_object_pose_loss / mon_object_refine_pose, kernels_pose.hip).  k_pose_rays: one record of 4 float4 per drawn ray from the pose in
 // device memory (pose[16], world -> object); k_pose_grad<shape>: loss and position gradient, one partial row of 8 floats {g, x x g, loss, 0} per workgroup
 // (pose_grad_grid of them); k_pose_update: the rows summed in a fixed order, x inv_n -> out[8 * it] = {loss, grad6, 0}, optionally the Adam step on pose.
@@ -810,6 +821,23 @@ int scene_paths(Model* const* ms, size_t n, int side, const ScenePoints& q, floa
                 const int32_t* ids);
 void paths_last_stats(uint32_t out3[3]);
 int lattice_path(const int32_t* next, size_t n_cells, int32_t start, int32_t* path, size_t cap, size_t* n_path);
+// Device-resident distance fields (mon_dist_field_*; dist_field.cpp): a snapshot of a field in device memory of its own, asked at world points and along
+// trajectories (the rule: include/mon_core.h).  DistField holds no reference to objects or to a manager; calls on one handle take turns on its mutex.
+// The *_check judge what needs no device; dist_field_create uploads a host field; scene_dist_field runs scene_distance's chain (scene_field.cpp) and keeps
+// dist on the device: nothing per cell goes home.  Every output of dist_field_score but min_clear may be nullptr, dist_field_sample's grad3 too.
+struct DistField;
+int dist_field_create_check(const float* dist, int nx, int ny, int nz, const float* origin3, const float* step3, const void* field_out);
+int dist_field_create(int device, const float* dist, int nx, int ny, int nz, const float* origin3, const float* step3, DistField** out);
+int scene_dist_field_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float max_dist, const void* field_out);
+int scene_dist_field(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, float max_dist, DistField** out);
+int dist_field_adopt(int device, const ScenePoints& q, DistField** out);          // scene_field.cpp's way in: the handle with its buffer, still empty
+float* dist_field_cells(DistField& f); void dist_field_set_max(DistField& f, float max_value);
+void dist_field_free(DistField* f);
+int dist_field_info(DistField* f, mon_dist_field_desc* info);
+int dist_field_read(DistField* f, float* dist_out);
+int dist_field_sample(DistField* f, const float* xyz, size_t n, float outside, float* dist_out, float* grad3_out);
+int dist_field_score(DistField* f, const float* spheres, size_t n_spheres, const float* ways, int way_floats, size_t n_traj, size_t n_way, size_t n_sub,
+                     const mon_traj_score_params* p, float* min_clear, int32_t* first_hit, float* cost, float* way_clear, float* way_grad);
 // Point gradients (mon_scene_query_gradients / _lattice_gradients, mon_object_query_gradients): the point queries' conventions, plus level_w (host, may be
 // nullptr = all 1: Lmax floats, object j reads its first L_j; the *_check judges the first, scene_gradients_weights_check the rest once the objects are
 // known) and select (host, [n] or nullptr: -1 or an index into ms).  rows (mon_debug_scene_gradient_rows) = object rows_k's rows, host array [n][16].
@@ -894,3 +922,4 @@ void init_params_host(const mon_config& c, const NetDims& nd, uint32_t n_params,
 // opaque C handles of include/mon_core.h
 struct mon_dataset { mon::Dataset* d; };
 struct mon_object { mon::Model* m; };
+struct mon_dist_field { mon::DistField* f; };

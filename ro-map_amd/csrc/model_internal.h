@@ -1,4 +1,4 @@
-// model_internal.h -- what model.cpp, train.cpp, pose.cpp, scene.cpp, scene_field.cpp, scene_pose.cpp and checkpoint.cpp need from each other and nobody else needs (c_api.cpp, manager.cpp and
+// model_internal.h -- what model.cpp, train.cpp, pose.cpp, scene.cpp, scene_field.cpp, dist_field.cpp, scene_pose.cpp and checkpoint.cpp need from each other and nobody else needs (c_api.cpp, manager.cpp and
 // diag.cpp go through model.h).
 #pragma once
 #include <atomic>

@@ -1,5 +1,6 @@
 // scene_field.cpp -- the field queries: the object map asked at places instead of along rays.  Points and lattices (density, colour, owner), their
-// gradients and normals, normals at ray hits, distance fields, connected components and shortest-path cost fields over a lattice.  One host chain
+// gradients and normals, normals at ray hits, distance fields (brought home, or kept on the device as a field handle: dist_field.cpp), connected components
+// and shortest-path cost fields over a lattice.  One host chain
 // (DESIGN.md 3.4c-4): a SceneCall (scene.cpp) without lists or grids, the passes of field_passes_enqueue, each route's own kernels behind them, one copy
 // home and one synchronisation (the cost fields: one more per batch of sweeps).
 #include <algorithm>
@@ -312,37 +313,82 @@ int distance_transform(int device, const uint8_t* occupied, int nx, int ny, int 
     if (nearest) std::memcpy(nearest, h_near.data(), 4 * n);
     return MON_OK;
 }
+// What scene_distance and scene_dist_field share: the workspace, then the chain over the lattice, the mask, the three passes and the finish.  The rows of
+// the output area: sigma | dist | nearest | nearest_owner | free_dist (what may go home, from the front: up to the last row asked for), then the fold's other
+// rows.  home: the floats of the pinned staging the call will ask for.
+struct DistanceRows { FoldRows f; size_t dist, nearest, nearest_owner, free; };
+static DistanceRows distance_rows(Area& A) {
+    DistanceRows r{}; r.f.sigma = A.row(); r.dist = A.row(); r.nearest = A.row(); r.nearest_owner = A.row(); r.free = A.row();
+    r.f.rgb = A.row(3); r.f.owner = A.row(); r.f.owner_sigma = A.row(); r.f.n_inside = A.row();
+    return r;
+}
+static int distance_chain(const SceneCall& c, Model* const* ms, size_t n, const ScenePoints& q, float sigma_min, float max_dist, const DistanceRows& r,
+                          size_t area_end, size_t home, bool nearest, bool nearest_owner) {
+    SceneWs& ws = *c.ws; const hipStream_t s = c.s;
+    const size_t n_q = q.n; const uint32_t nq = (uint32_t)n_q, cap = std::min(nq, kScenePointsPass);
+    {   int rc;
+        if ((rc = field_passes_prepare(c, n, q, cap, 12u)) || (rc = ws.out.grow(area_end)) || (rc = ws.h_out.grow(home)) || (rc = ws.docc.grow(n_q)) ||
+            (rc = ws.dv.grow(2 * n_q)) || (rc = ws.dsite.grow(2 * n_q))) return rc; }
+    float* o = ws.out.p;
+    field_passes_enqueue(c, ms, n, q, true, cap, r.f, nullptr, 0, nullptr);
+    launch_distance_mask(s, nq, o + r.f.sigma, sigma_min, ws.docc.p);
+    launch_distance_passes(s, ws.docc.p, false, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, q.step, ws.dv.p, ws.dsite.p);
+    launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, max_dist, reinterpret_cast<int32_t*>(o + r.f.owner), o + r.dist,
+            nearest ? reinterpret_cast<int32_t*>(o + r.nearest) : nullptr, nearest_owner ? reinterpret_cast<int32_t*>(o + r.nearest_owner) : nullptr);
+    return MON_OK;
+}
 // q: a lattice (scene_lattice).  ids as scene_points', applied to nearest_owner.  max_dist truncates dist and free_dist alike.
 int scene_distance(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, float max_dist, float* dist, int32_t* nearest,
                    int32_t* nearest_owner, float* free_dist, float* sigma, const int32_t* ids) {
     SceneCall c; { const int rc = c.enter("scene_distance", ms, n, side, false); if (rc) return rc; }
     SceneWs& ws = *c.ws; const hipStream_t s = c.s;
-    const size_t n_q = q.n; const uint32_t nq = (uint32_t)n_q, cap = std::min(nq, kScenePointsPass);
-    // the output area: sigma | dist | nearest | nearest_owner | free_dist (what may go home, from the front: up to the last row asked for), then the fold's
-    // other rows
-    Area A{ n_q }; FoldRows f{}; f.sigma = A.row(); const size_t r_dist = A.row(), r_nearest = A.row(), r_nearest_owner = A.row(), r_free = A.row();
-    f.rgb = A.row(3); f.owner = A.row(); f.owner_sigma = A.row(); f.n_inside = A.row();
-    const size_t home = free_dist ? f.rgb : nearest_owner ? r_free : nearest ? r_nearest_owner : r_nearest;
-    {   int rc;
-        if ((rc = field_passes_prepare(c, n, q, cap, 12u)) || (rc = ws.out.grow(A.end)) || (rc = ws.h_out.grow(home)) || (rc = ws.docc.grow(n_q)) ||
-            (rc = ws.dv.grow(2 * n_q)) || (rc = ws.dsite.grow(2 * n_q))) return rc; }
+    const size_t n_q = q.n; const uint32_t nq = (uint32_t)n_q;
+    Area A{ n_q }; const DistanceRows r = distance_rows(A);
+    const size_t home = free_dist ? r.f.rgb : nearest_owner ? r.free : nearest ? r.nearest_owner : r.nearest;
+    { const int rc = distance_chain(c, ms, n, q, sigma_min, max_dist, r, A.end, home, nearest != nullptr, nearest_owner != nullptr); if (rc) return rc; }
     float* o = ws.out.p;
-    field_passes_enqueue(c, ms, n, q, true, cap, f, nullptr, 0, nullptr);
-    launch_distance_mask(s, nq, o + f.sigma, sigma_min, ws.docc.p);
-    launch_distance_passes(s, ws.docc.p, false, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, q.step, ws.dv.p, ws.dsite.p);
-    launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, max_dist, reinterpret_cast<int32_t*>(o + f.owner), o + r_dist,
-            nearest ? reinterpret_cast<int32_t*>(o + r_nearest) : nullptr, nearest_owner ? reinterpret_cast<int32_t*>(o + r_nearest_owner) : nullptr);
     if (free_dist) {
         launch_distance_passes(s, ws.docc.p, true, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, q.step, ws.dv.p, ws.dsite.p);
-        launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, max_dist, nullptr, o + r_free, nullptr, nullptr);
+        launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, max_dist, nullptr, o + r.free, nullptr, nullptr);
     }
     { const int rc = c.home(home); if (rc) return rc; }
     const float* h = ws.h_out.p;
-    if (sigma) std::memcpy(sigma, h + f.sigma, 4 * n_q);
-    std::memcpy(dist, h + r_dist, 4 * n_q);
-    if (nearest) std::memcpy(nearest, h + r_nearest, 4 * n_q);
-    if (nearest_owner) scene_instances_home(nearest_owner, h + r_nearest_owner, n_q, ids);
-    if (free_dist) std::memcpy(free_dist, h + r_free, 4 * n_q);
+    if (sigma) std::memcpy(sigma, h + r.f.sigma, 4 * n_q);
+    std::memcpy(dist, h + r.dist, 4 * n_q);
+    if (nearest) std::memcpy(nearest, h + r.nearest, 4 * n_q);
+    if (nearest_owner) scene_instances_home(nearest_owner, h + r.nearest_owner, n_q, ids);
+    if (free_dist) std::memcpy(free_dist, h + r.free, 4 * n_q);
+    return MON_OK;
+}
+// mon_scene_dist_field / mon_online_dist_field: the same chain with dist kept on the device.  The output area opens with four words for
+// the field's largest value -- all that goes home -- and ends with the partial maxima; dist goes into the handle's buffer by a device-to-device copy.
+int scene_dist_field_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float max_dist, const void* field_out) {
+    REQUIRE_ARG("scene_dist_field", field_out, "field");
+    float unused = 0.f;
+    { const int rc = scene_distance_check(side, origin3, step3, nx, ny, nz, sigma_min, 1.f, &unused); if (rc) return rc; }
+    if (!std::isfinite(max_dist) || !(max_dist > 0.f)) { set_error("scene_dist_field: max_dist %g (finite, above 0)", (double)max_dist); return MON_ERR_ARG; }
+    const int dims[3] = { nx, ny, nz };
+    for (int a = 0; a < 3; ++a) if (dims[a] > 1 && step3[a] == 0.f) { set_error("scene_dist_field: step 0 on axis %d, which has %d cells", a, dims[a]);
+        return MON_ERR_ARG; }
+    return MON_OK;
+}
+int scene_dist_field(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, float max_dist, DistField** out) {
+    SceneCall c; { const int rc = c.enter("scene_dist_field", ms, n, side, false); if (rc) return rc; }
+    SceneWs& ws = *c.ws; const hipStream_t s = c.s;
+    const size_t n_q = q.n;
+    Area A{ n_q }; const size_t r_max = A.take(4); const DistanceRows r = distance_rows(A); const size_t r_part = A.take(kFieldMaxBlocks);
+    DistField* f = nullptr;
+    { const int rc = dist_field_adopt(ms[0]->device, q, &f); if (rc) return rc; }
+    int rc = distance_chain(c, ms, n, q, sigma_min, max_dist, r, A.end, 4, false, false);
+    if (!rc) {
+        float* o = ws.out.p;
+        const hipError_t e = hipMemcpyAsync(dist_field_cells(*f), o + r.dist, 4 * n_q, hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) { set_error("scene_dist_field: the copy into the handle failed: %s", hipGetErrorString(e)); rc = MON_ERR_HIP; }
+        else { launch_field_max(s, o + r.dist, (uint32_t)n_q, o + r_part, o + r_max); rc = c.home(4); }
+    }
+    if (rc) { dist_field_free(f); return rc; }
+    dist_field_set_max(*f, ws.h_out.p[r_max]);
+    *out = f;
     return MON_OK;
 }
 
