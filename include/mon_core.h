@@ -518,6 +518,59 @@ int mon_dist_field_score(mon_dist_field* field, const float* spheres, size_t n_s
                          size_t n_sub, const mon_traj_score_params* params, float* min_clear, int32_t* first_hit, float* cost, float* way_clear,
                          float* way_grad);
 int mon_dist_field_destroy(mon_dist_field* field);
+/* Scan matching against a device-resident distance field: where is this scan in the map -- asked by a consumer that brings only geometry (a lidar, a depth
+ * camera whose frames are not in a dataset, a second robot that loaded a saved map), where every other localisation call is photometric (the reference has no
+ * such call; opt-in, new, read-only; no existing call changes its bits).  One batched evaluation serves a particle filter's likelihood-field weights (the
+ * cost per pose) and a Gauss-Newton / Levenberg-Marquardt refinement (the cost and the 6 x 6 normal equations); the field is best a SIGNED distance
+ * (mon_dist_field_create), whose zero set the scan's end points lie on.  Every operation below is one separately rounded fp32 operation (fl); nothing is
+ * contracted.  No atomics: equal arguments give equal bits, and a pose's row does not depend on the other poses of the call.
+ * Inputs.  points[n][3], the scan in the sensor or body frame; the values are not checked: a point that lands outside the lattice, or is not finite, is
+ *   simply "outside".  poses16[H][16]: row-major 4 x 4 matrices, the layout of Twc16, the last row ignored, which map the points into the field's world;
+ *   the twelve entries used are finite.  pivots[H][3], finite, or NULL for (0, 0, 0).  params = { huber, outside }: huber > 0, +inf is allowed; outside is
+ *   finite.  1 <= n <= 2^20, 1 <= H <= 4 096, n * H <= 2^26.
+ * Per pose h and point p.
+ *   1. q = the centre formula of way_floats 16 above, applied to poses16[h] and points[p].
+ *   2. (d, g) = the sample of D at q and its gradient, by the rule above.
+ *   3. q outside: d = outside, every A and b term of the point is +0 (not computed), inside = 0.
+ *   4. Otherwise a = fl(q - pivot) per component, and
+ *        J = (g_x, g_y, g_z, fl(fl(a_y g_z) - fl(a_z g_y)), fl(fl(a_z g_x) - fl(a_x g_z)), fl(fl(a_x g_y) - fl(a_y g_x))),
+ *      the derivative of d under pose <- Exp(v, w) about the pivot, translation first: R' = Exp(w) R, t' = Exp(w) (t - pivot) + pivot + v.
+ *   5. m = |d|.  Where m <= huber: w = 1, rho = fl(d d), and the point is an inlier if it is inside.  Otherwise w = fl(huber / m) and
+ *      rho = fl(huber * fl(fl(2 m) - huber)).
+ *   6. A_ij = fl(fl(w J_i) J_j) for i <= j (21 terms, row-major upper triangle), b_i = fl(fl(w J_i) d) (6 terms), and rho (one term).  An outside point
+ *      contributes its rho too, so a pose cannot lower its cost by leaving the lattice.
+ * Sums.  Each of the 28 float sums of a pose is the pairwise tree over the points in ascending index: pad with +0 to the next power of two, then level by
+ *   level v'[i] = fl(v[2 i] + v[2 i + 1]) down to one value; a result of -0 is returned as +0.  n_inside and n_inlier are integer counts.
+ * mon_dist_field_match: cost[H]; n_inside[H] and n_inlier[H] (either may be NULL); normal[H][27] = the 21 A terms, then the 6 b terms (may be NULL: nothing
+ *   of A and b is then computed -- the particle filter's case).  Points, poses and pivots are uploaded per call; the outputs come home with one
+ *   synchronisation.
+ * mon_register_default: huber = 2 x the largest |step| among the axes of more than one cell (1 without such an axis), outside = the handle's max_value,
+ *   max_evals 30, lambda0 1e-3, lambda_up = lambda_down = 10, lambda_max 1e6, tol_trans = 1e-3 x that step, tol_rot 1e-4, min_inside 6.
+ * mon_dist_field_register: every one of the H hypotheses poses16_in is refined by Levenberg-Marquardt, all in lockstep: the points are uploaded once; per
+ *   round there is one match launch over the hypotheses still running and one read-back of 32 words per pose.  The pivot c of a hypothesis is its input pose
+ *   applied to the centroid of the scan's finite points, and stays fixed.  The first round evaluates the input poses.  Then, per hypothesis: the host solves
+ *   (A + lambda diag(A)) delta = -b in double by a Cholesky factorisation (a failed one counts as a rejected step), forms R' = Exp(w) R and
+ *   t' = Exp(w) (t - c) + c + v with delta = (v, w), rounds to fp32 and has the candidate evaluated.  A step is accepted iff its cost is strictly lower;
+ *   lambda is divided by lambda_down on acceptance and multiplied by lambda_up on rejection.  The host's double steps are not pinned bit for bit by this
+ *   text, but equal calls give equal bits, and a hypothesis's result does not depend on the others.
+ *   Outputs: poses16_out[H][16] (the last row is the input's) and cost[H]; and, each of which may be NULL: n_inside[H], n_inlier[H] (cost and counts are
+ *   mon_dist_field_match's at the returned pose with the hypothesis's pivot, bit for bit), evals[H] (the match evaluations of that hypothesis, the first
+ *   included), status[H] (0: an accepted step with |v| < tol_trans and |w| < tol_rot; 1: max_evals reached; 2: lambda above lambda_max; 3: fewer than
+ *   min_inside points inside at the input pose, which is returned bit for bit) and *best (the index of the lowest cost among status != 3, ties to the
+ *   lowest index; -1 without one).
+ * Returns:
+ *   MON_ERR_ARG    field, points, poses16, params, cost, poses16_in, poses16_out or p NULL; n, H or n * H outside their limits; a pose entry or a pivot
+ *                  that is not finite; huber <= 0 or NaN; outside, a lambda parameter or a tolerance that is not finite; lambda0 <= 0, lambda_max <= 0 or
+ *                  a tolerance < 0; lambda_up or lambda_down <= 1; max_evals < 1; min_inside < 0 -- all before any device work, the outputs untouched; the
+ *                  handle is judged last */
+typedef struct mon_scan_match_params { float huber, outside; } mon_scan_match_params;
+typedef struct mon_register_params { float huber, outside; int32_t max_evals; float lambda0, lambda_up, lambda_down, lambda_max, tol_trans, tol_rot;
+                                     int32_t min_inside; } mon_register_params;      /* 40 bytes */
+int mon_dist_field_match(mon_dist_field* field, const float* points, size_t n, const float* poses16, size_t n_poses, const float* pivots,
+                         const mon_scan_match_params* params, float* cost, int32_t* n_inside, int32_t* n_inlier, float* normal);
+int mon_register_default(mon_dist_field* field, mon_register_params* p);
+int mon_dist_field_register(mon_dist_field* field, const float* points, size_t n, const float* poses16_in, size_t n_poses, const mon_register_params* p,
+                            float* poses16_out, float* cost, int32_t* n_inside, int32_t* n_inlier, int32_t* evals, int32_t* status, int32_t* best);
 /* Object pose refinement through the trained field (iNeRF-style): align the object with observed frames by following the gradient of a photometric,
  * silhouette and depth error with respect to the 6-DoF pose Tow.
  * Objective.  obs names frames of the object's dataset (FrameId) and pixel boxes inside them; the target of a pixel is that frame's rgb c*, its instance map

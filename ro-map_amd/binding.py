@@ -88,6 +88,17 @@ class TrajScoreParams(C.Structure):
     _fields_ = [("outside", C.c_float), ("margin", C.c_float), ("safe", C.c_float)]
 
 
+class ScanMatchParams(C.Structure):
+    """mon_scan_match_params (include/mon_core.h): the Huber threshold on |d| (+inf: plain least squares) and the value of a point outside the field."""
+    _fields_ = [("huber", C.c_float), ("outside", C.c_float)]
+
+
+class RegisterParams(C.Structure):
+    """mon_register_params (include/mon_core.h): ScanMatchParams, then the Levenberg-Marquardt schedule of mon_dist_field_register."""
+    _fields_ = [("huber", C.c_float), ("outside", C.c_float), ("max_evals", C.c_int32), ("lambda0", C.c_float), ("lambda_up", C.c_float),
+                ("lambda_down", C.c_float), ("lambda_max", C.c_float), ("tol_trans", C.c_float), ("tol_rot", C.c_float), ("min_inside", C.c_int32)]
+
+
 class RelocResult(C.Structure):
     """mon_reloc_result (include/mon_core.h): which candidate won, whether its refined pose did, and the scores S[0], S[best], F[winner]."""
     _fields_ = [("best_candidate", C.c_uint32), ("refined", C.c_uint32), ("score_candidate0", C.c_float), ("score_best_candidate", C.c_float),
@@ -252,6 +263,11 @@ _SIGS = {
     "mon_dist_field_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t,
             C.POINTER(TrajScoreParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_dist_field_destroy": (C.c_int, [C.c_void_p]),
+    "mon_dist_field_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(ScanMatchParams), C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p]),
+    "mon_register_default": (C.c_int, [C.c_void_p, C.POINTER(RegisterParams)]),
+    "mon_dist_field_register": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(RegisterParams), C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_object_query_gradients": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_scene_query_gradients": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1386,6 +1402,43 @@ class DistField:
         _check(lib().mon_dist_field_score(self.h, _p(b), b.shape[0], _p(w), wf, n_traj, n_way, int(n_sub), C.byref(prm), _p(out["min_clear"]),
                                           _p(out["first_hit"]), _p(out["cost"]), _p(out["way_clear"]), _p(out["way_grad"])))
         return {k: v for k, v in out.items() if v is not None}
+
+    def match(self, points, poses, pivots=None, huber=np.inf, outside=0.0, normal=True, counts=True):
+        """mon_dist_field_match.  points (n, 3) in the body frame; poses (H, 16) or (H, 4, 4) row-major; pivots (H, 3) or None for the origin.  -> a dict
+        with cost (H,) and, with counts, n_inside and n_inlier (H,) int32, and, with normal, A (H, 21) (row-major upper triangle) and b (H, 6)."""
+        x = np.ascontiguousarray(points, np.float32).reshape(-1, 3); T = np.ascontiguousarray(poses, np.float32).reshape(-1, 16); H = T.shape[0]
+        c = None if pivots is None else np.ascontiguousarray(pivots, np.float32).reshape(H, 3)
+        prm = ScanMatchParams(float(huber), float(outside))
+        cost = np.empty(H, np.float32); ni = np.empty(H, np.int32) if counts else None; nl = np.empty(H, np.int32) if counts else None
+        nrm = np.empty((H, 27), np.float32) if normal else None
+        _check(lib().mon_dist_field_match(self.h, _p(x), x.shape[0], _p(T), H, _p(c), C.byref(prm), _p(cost), _p(ni), _p(nl), _p(nrm)))
+        out = {"cost": cost}
+        if counts:
+            out["n_inside"] = ni; out["n_inlier"] = nl
+        if normal:
+            out["A"] = nrm[:, :21].copy(); out["b"] = nrm[:, 21:].copy()
+        return out
+
+    def register_default(self):
+        """mon_register_default -> RegisterParams for this field"""
+        p = RegisterParams(); _check(lib().mon_register_default(self.h, C.byref(p))); return p
+
+    def register(self, points, poses, params=None, **overrides):
+        """mon_dist_field_register: every hypothesis of poses (H, 16) or (H, 4, 4) refined by Levenberg-Marquardt.  params: RegisterParams (default:
+        register_default()), with `overrides` set on a copy.  -> a dict with poses (H, 4, 4), cost, n_inside, n_inlier, evals, status (H,) and best."""
+        x = np.ascontiguousarray(points, np.float32).reshape(-1, 3); T = np.ascontiguousarray(poses, np.float32).reshape(-1, 16); H = T.shape[0]
+        base = params if params is not None else self.register_default()
+        prm = RegisterParams.from_buffer_copy(base)
+        for k, v in overrides.items():
+            assert k in dict(RegisterParams._fields_), k
+            setattr(prm, k, v)
+        out = {"poses": np.empty((H, 4, 4), np.float32), "cost": np.empty(H, np.float32), "n_inside": np.empty(H, np.int32), "n_inlier": np.empty(H, np.int32),
+               "evals": np.empty(H, np.int32), "status": np.empty(H, np.int32)}
+        best = C.c_int32(-2)
+        _check(lib().mon_dist_field_register(self.h, _p(x), x.shape[0], _p(T), H, C.byref(prm), _p(out["poses"]), _p(out["cost"]), _p(out["n_inside"]),
+                                             _p(out["n_inlier"]), _p(out["evals"]), _p(out["status"]), C.byref(best)))
+        out["best"] = int(best.value)
+        return out
 
 
 def dist_field_create(dist, origin, step, device=0):

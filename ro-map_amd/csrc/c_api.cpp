@@ -227,6 +227,15 @@ int mon_dist_field_score(mon_dist_field* field, const float* spheres, size_t n_s
                             way_grad);
 }
 int mon_dist_field_destroy(mon_dist_field* field) { if (field) { dist_field_free(field->f); delete field; } return MON_OK; }
+int mon_dist_field_match(mon_dist_field* field, const float* points, size_t n, const float* poses16, size_t n_poses, const float* pivots,
+        const mon_scan_match_params* params, float* cost, int32_t* n_inside, int32_t* n_inlier, float* normal) {
+    return dist_field_match(field ? field->f : nullptr, points, n, poses16, n_poses, pivots, params, cost, n_inside, n_inlier, normal);
+}
+int mon_register_default(mon_dist_field* field, mon_register_params* p) { return dist_field_register_default(field ? field->f : nullptr, p); }
+int mon_dist_field_register(mon_dist_field* field, const float* points, size_t n, const float* poses16_in, size_t n_poses, const mon_register_params* p,
+        float* poses16_out, float* cost, int32_t* n_inside, int32_t* n_inlier, int32_t* evals, int32_t* status, int32_t* best) {
+    return dist_field_register(field ? field->f : nullptr, points, n, poses16_in, n_poses, p, poses16_out, cost, n_inside, n_inlier, evals, status, best);
+}
 int mon_object_query_gradients(mon_object* o, int side, const float* unit_xyz, size_t n, const float* level_weights, float* raw4, float* grad_unit) {
     { const int rc = object_gradients_check(side, unit_xyz, n, level_weights, grad_unit); if (rc) return rc; }
     REQUIRE(o, "object");

@@ -2,7 +2,9 @@
 // DistField is a snapshot: its cells in device memory of its own, the lattice they sit on, a stream and the scratch of its calls.  It refers to no object
 // and to no manager.  A sample or score call uploads its inputs, enqueues one kernel and the copy of its outputs to the pinned staging on the handle's
 // stream, and synchronises once; calls on one handle take turns on its mutex.  (mon_scene_dist_field's chain is scene_field.cpp's: it fills a handle made by
-// dist_field_adopt.)
+// dist_field_adopt.)  Scan matching (mon_dist_field_match, mon_dist_field_register) is here too: the match call follows the same
+// pattern; the register call keeps the scan on the device and runs Levenberg-Marquardt over all hypotheses in lockstep, one match launch, one read-back and
+// one synchronisation per round, with the 6 x 6 solves and the pose updates on the host in double.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -173,6 +175,217 @@ int dist_field_score(DistField* f, const float* spheres, size_t n_spheres, const
     if (cost) std::memcpy(cost, h + r_cost, 4 * n_traj);
     if (way_clear) std::memcpy(way_clear, h + r_wc, 4 * n_ways);
     if (way_grad) std::memcpy(way_grad, h + r_wg, 12 * n_ways);
+    return MON_OK;
+}
+
+// ---- scan matching.  What the two calls ask of the scan and the poses, without a device
+constexpr size_t kMatchMaxPoints = (size_t)1 << 20, kMatchMaxPoses = 4096, kMatchMaxWork = (size_t)1 << 26;
+static int match_check(const char* what, const float* points, size_t n, const float* poses16, size_t H, const float* pivots, float huber, float outside) {
+    if (n == 0 || n > kMatchMaxPoints) { set_error("%s: %zu points (1 to %zu)", what, n, kMatchMaxPoints); return MON_ERR_ARG; }
+    if (H == 0 || H > kMatchMaxPoses) { set_error("%s: %zu poses (1 to %zu)", what, H, kMatchMaxPoses); return MON_ERR_ARG; }
+    if (n * H > kMatchMaxWork) { set_error("%s: %zu points under %zu poses (at most %zu pairs in all)", what, n, H, kMatchMaxWork); return MON_ERR_ARG; }
+    for (size_t h = 0; h < H; ++h) {
+        for (int k = 0; k < 12; ++k) if (!std::isfinite(poses16[16 * h + k])) { set_error("%s: pose %zu is not finite", what, h); return MON_ERR_ARG; }
+        for (int k = 0; pivots && k < 3; ++k) if (!std::isfinite(pivots[3 * h + k])) { set_error("%s: pivot %zu is not finite", what, h); return MON_ERR_ARG; }
+    }
+    if (!(huber > 0.f)) { set_error("%s: huber %g (above 0; +inf is allowed)", what, (double)huber); return MON_ERR_ARG; }
+    if (!std::isfinite(outside)) { set_error("%s: outside is not finite", what); return MON_ERR_ARG; }
+    return MON_OK;
+}
+// The device side of both calls, on the locked handle.  in: points (3 n floats, rounded up to a multiple of 4) | poses [H][16] | pivots [H][3]; out: the
+// kernels' scratch | rows.  match_room makes room for H poses; match_round uploads `live` poses (and pivots) and brings their rows home: 32 words per pose,
+// or 4 without the normal equations.
+struct MatchRoom { size_t at_pose, at_rows; };
+static size_t round4(size_t v) { return (v + 3) & ~(size_t)3; }
+static int match_room(DistField& f, size_t n, size_t H, MatchRoom& r) {
+    r.at_pose = round4(3 * n); r.at_rows = round4(scan_match_scratch((uint32_t)n, (uint32_t)H));
+    int rc;
+    if ((rc = f.in.grow(r.at_pose + 19 * H)) || (rc = f.out.grow(r.at_rows + kScanMatchRow * H)) || (rc = f.h_out.grow(kScanMatchRow * H))) return rc;
+    return MON_OK;
+}
+static int match_round(DistField& f, const MatchRoom& r, size_t n, const float* poses16, const float* pivots, size_t live, float huber, float outside,
+                       bool normal) {
+    float* d_pose = f.in.p + r.at_pose; float* d_piv = d_pose + 16 * live;
+    HIPCHECK(hipMemcpyAsync(d_pose, poses16, 64 * live, hipMemcpyHostToDevice, f.s));
+    if (pivots) HIPCHECK(hipMemcpyAsync(d_piv, pivots, 12 * live, hipMemcpyHostToDevice, f.s));
+    const ScanMatchArgs a{ f.in.p, d_pose, pivots ? d_piv : nullptr, (uint32_t)n, (uint32_t)live, huber, outside };
+    launch_scan_match(f.s, f.view(), a, normal, f.out.p, f.out.p + r.at_rows);
+    HIPCHECK(hipMemcpyAsync(f.h_out.p, f.out.p + r.at_rows, 4 * (normal ? kScanMatchRow : kScanMatchLite) * live, hipMemcpyDeviceToHost, f.s));
+    HIPCHECK(hipStreamSynchronize(f.s));
+    HIPCHECK(hipGetLastError());
+    return MON_OK;
+}
+constexpr int kRowCost = 27, kRowInside = 28, kRowInlier = 29;                      // a full row: 21 A terms, 6 b terms, then these
+
+int dist_field_match(DistField* f, const float* points, size_t n, const float* poses16, size_t H, const float* pivots, const mon_scan_match_params* p,
+                     float* cost, int32_t* n_inside, int32_t* n_inlier, float* normal) {
+    const char* what = "dist_field_match";
+    REQUIRE_ARG(what, points, "points"); REQUIRE_ARG(what, poses16, "poses16"); REQUIRE_ARG(what, p, "params"); REQUIRE_ARG(what, cost, "cost");
+    { const int rc = match_check(what, points, n, poses16, H, pivots, p->huber, p->outside); if (rc) return rc; }
+    REQUIRE_ARG(what, f, "field");                                                  // (last: what needs no handle is judged without one)
+    std::lock_guard<std::mutex> l(f->mu);
+    HIPCHECK(use_device(f->device));
+    MatchRoom r;
+    { const int rc = match_room(*f, n, H, r); if (rc) return rc; }
+    HIPCHECK(hipMemcpyAsync(f->in.p, points, 12 * n, hipMemcpyHostToDevice, f->s));
+    { const int rc = match_round(*f, r, n, poses16, pivots, H, p->huber, p->outside, normal != nullptr); if (rc) return rc; }
+    const size_t w = normal ? kScanMatchRow : kScanMatchLite, c0 = normal ? kRowCost : 0;
+    for (size_t h = 0; h < H; ++h) {
+        const float* row = f->h_out.p + w * h;
+        cost[h] = row[c0];
+        if (n_inside) n_inside[h] = (int32_t)row[c0 + 1];
+        if (n_inlier) n_inlier[h] = (int32_t)row[c0 + 2];
+        if (normal) std::memcpy(normal + 27 * h, row, 4 * 27);
+    }
+    return MON_OK;
+}
+
+int dist_field_register_default(DistField* f, mon_register_params* p) {
+    REQUIRE_ARG("register_default", p, "p"); REQUIRE_ARG("register_default", f, "field");
+    std::lock_guard<std::mutex> l(f->mu);
+    const int dims[3] = { f->nx, f->ny, f->nz };
+    float step = 0.f;
+    for (int a = 0; a < 3; ++a) if (dims[a] > 1) step = std::max(step, std::fabs(f->step[a]));
+    if (step == 0.f) step = 1.f;
+    *p = mon_register_params{ 2.f * step, f->max_value, 30, 1e-3f, 10.f, 10.f, 1e6f, 1e-3f * step, 1e-4f, 6 };
+    return MON_OK;
+}
+
+// (A + lambda diag(A)) delta = -b in double by Cholesky; row: 21 A terms (row-major upper triangle), then 6 b terms.  false: not positive definite
+static bool lm_solve(const float* row, double lambda, double delta[6]) {
+    double M[6][6], L[6][6] = {}, y[6];
+    for (int i = 0, k = 0; i < 6; ++i) for (int j = i; j < 6; ++j, ++k) M[i][j] = M[j][i] = (double)row[k];
+    for (int i = 0; i < 6; ++i) M[i][i] += lambda * M[i][i];
+    for (int j = 0; j < 6; ++j) {
+        double s = M[j][j];
+        for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
+        if (!(s > 0.0) || !std::isfinite(s)) return false;
+        L[j][j] = std::sqrt(s);
+        for (int i = j + 1; i < 6; ++i) {
+            double t = M[i][j];
+            for (int k = 0; k < j; ++k) t -= L[i][k] * L[j][k];
+            L[i][j] = t / L[j][j];
+        }
+    }
+    for (int i = 0; i < 6; ++i) { double t = -(double)row[21 + i]; for (int k = 0; k < i; ++k) t -= L[i][k] * y[k]; y[i] = t / L[i][i]; }
+    for (int i = 5; i >= 0; --i) { double t = y[i]; for (int k = i + 1; k < 6; ++k) t -= L[k][i] * delta[k]; delta[i] = t / L[i][i]; }
+    for (int i = 0; i < 6; ++i) if (!std::isfinite(delta[i])) return false;
+    return true;
+}
+// pose <- Exp(v, w) about the pivot c: R' = Exp(w) R, t' = Exp(w) (t - c) + c + v (Rodrigues in double), rounded to fp32; the last row is kept
+static void lm_step(const float* pose, const float* c, const double delta[6], float* out) {
+    const double wx = delta[3], wy = delta[4], wz = delta[5], th2 = wx * wx + wy * wy + wz * wz, th = std::sqrt(th2);
+    const double A = th < 1e-8 ? 1.0 - th2 / 6.0 : std::sin(th) / th, B = th < 1e-4 ? 0.5 - th2 / 24.0 : (1.0 - std::cos(th)) / th2;
+    const double K[3][3] = { { 0, -wz, wy }, { wz, 0, -wx }, { -wy, wx, 0 } };
+    double E[3][3];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
+        double kk = 0; for (int k = 0; k < 3; ++k) kk += K[i][k] * K[k][j];
+        E[i][j] = (i == j ? 1.0 : 0.0) + A * K[i][j] + B * kk;
+    }
+    const double t[3] = { (double)pose[3] - c[0], (double)pose[7] - c[1], (double)pose[11] - c[2] };
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) out[4 * i + j] = (float)(E[i][0] * pose[j] + E[i][1] * pose[4 + j] + E[i][2] * pose[8 + j]);
+        out[4 * i + 3] = (float)(E[i][0] * t[0] + E[i][1] * t[1] + E[i][2] * t[2] + (double)c[i] + delta[i]);
+    }
+    for (int j = 12; j < 16; ++j) out[j] = pose[j];
+}
+
+static int register_check(const char* what, const float* points, size_t n, const float* poses16_in, size_t H, const mon_register_params* p,
+                          const float* poses16_out, const float* cost) {
+    REQUIRE_ARG(what, points, "points"); REQUIRE_ARG(what, poses16_in, "poses16_in"); REQUIRE_ARG(what, p, "p"); REQUIRE_ARG(what, poses16_out, "poses16_out");
+    REQUIRE_ARG(what, cost, "cost");
+    { const int rc = match_check(what, points, n, poses16_in, H, nullptr, p->huber, p->outside); if (rc) return rc; }
+    if (!std::isfinite(p->lambda0) || !std::isfinite(p->lambda_up) || !std::isfinite(p->lambda_down) || !std::isfinite(p->lambda_max) || !(p->lambda0 > 0.f) ||
+        !(p->lambda_max > 0.f)) { set_error("%s: a lambda parameter is not finite or not above 0", what); return MON_ERR_ARG; }
+    if (!(p->lambda_up > 1.f) || !(p->lambda_down > 1.f)) {
+        set_error("%s: lambda factors %g and %g (each above 1)", what, (double)p->lambda_up, (double)p->lambda_down); return MON_ERR_ARG; }
+    if (!std::isfinite(p->tol_trans) || !std::isfinite(p->tol_rot) || p->tol_trans < 0.f || p->tol_rot < 0.f) {
+        set_error("%s: a tolerance is not finite or below 0", what); return MON_ERR_ARG; }
+    if (p->max_evals < 1) { set_error("%s: max_evals %d (at least 1)", what, p->max_evals); return MON_ERR_ARG; }
+    if (p->min_inside < 0) { set_error("%s: min_inside %d (at least 0)", what, p->min_inside); return MON_ERR_ARG; }
+    return MON_OK;
+}
+// one hypothesis of the lockstep: its pose so far with that pose's row, the candidate under evaluation and the step that led to it
+struct LmState { float pose[16], cand[16], pivot[3], row[kScanMatchRow]; double lambda, delta[6]; int32_t evals = 0, status = -1; };
+// the next candidate of a running hypothesis; false: lambda went above lambda_max over failed factorisations (status 2)
+static bool lm_propose(LmState& s, const mon_register_params& p) {
+    while (!lm_solve(s.row, s.lambda, s.delta)) {
+        s.lambda *= (double)p.lambda_up;
+        if (s.lambda > (double)p.lambda_max) { s.status = 2; return false; }
+    }
+    lm_step(s.pose, s.pivot, s.delta, s.cand);
+    return true;
+}
+int dist_field_register(DistField* f, const float* points, size_t n, const float* poses16_in, size_t H, const mon_register_params* p, float* poses16_out,
+                        float* cost, int32_t* n_inside, int32_t* n_inlier, int32_t* evals, int32_t* status, int32_t* best) {
+    const char* what = "dist_field_register";
+    { const int rc = register_check(what, points, n, poses16_in, H, p, poses16_out, cost); if (rc) return rc; }
+    REQUIRE_ARG(what, f, "field");                                                  // (last: what needs no handle is judged without one)
+    // the pivots: each input pose applied to the centroid of the finite points (the scan is read only now; still before any device work)
+    double cen[3] = { 0, 0, 0 }; size_t n_fin = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const float* q = points + 3 * i;
+        if (std::isfinite(q[0]) && std::isfinite(q[1]) && std::isfinite(q[2])) { cen[0] += q[0]; cen[1] += q[1]; cen[2] += q[2]; ++n_fin; }
+    }
+    for (int a = 0; a < 3; ++a) cen[a] = n_fin ? cen[a] / (double)n_fin : 0.0;
+    std::vector<LmState> st(H);
+    std::vector<size_t> live(H);
+    for (size_t h = 0; h < H; ++h) {
+        LmState& s = st[h]; live[h] = h;
+        std::memcpy(s.pose, poses16_in + 16 * h, 64); std::memcpy(s.cand, s.pose, 64);
+        for (int a = 0; a < 3; ++a) {
+            s.pivot[a] = (float)((double)s.pose[4 * a] * cen[0] + (double)s.pose[4 * a + 1] * cen[1] + (double)s.pose[4 * a + 2] * cen[2] + (double)s.pose[4 * a + 3]);
+            if (!std::isfinite(s.pivot[a])) { set_error("%s: the pivot of pose %zu is not finite", what, h); return MON_ERR_ARG; }
+        }
+        s.lambda = (double)p->lambda0;
+    }
+    std::lock_guard<std::mutex> l(f->mu);
+    HIPCHECK(use_device(f->device));
+    MatchRoom r;
+    { const int rc = match_room(*f, n, H, r); if (rc) return rc; }
+    HIPCHECK(hipMemcpyAsync(f->in.p, points, 12 * n, hipMemcpyHostToDevice, f->s));
+    std::vector<float> up(19 * H);
+    for (bool first = true; !live.empty(); first = false) {
+        // the candidates of the hypotheses still running: poses, then pivots, as match_round lays them out
+        for (size_t k = 0; k < live.size(); ++k) {
+            std::memcpy(up.data() + 16 * k, st[live[k]].cand, 64); std::memcpy(up.data() + 16 * live.size() + 3 * k, st[live[k]].pivot, 12);
+        }
+        { const int rc = match_round(*f, r, n, up.data(), up.data() + 16 * live.size(), live.size(), p->huber, p->outside, true); if (rc) return rc; }
+        std::vector<size_t> next;
+        for (size_t k = 0; k < live.size(); ++k) {
+            LmState& s = st[live[k]]; const float* row = f->h_out.p + kScanMatchRow * k;
+            ++s.evals;
+            bool small = false;
+            if (first) {
+                std::memcpy(s.row, row, 4 * kScanMatchRow);
+                if (row[kRowInside] < (float)p->min_inside) { s.status = 3; continue; }
+            } else if (row[kRowCost] < s.row[kRowCost]) {
+                std::memcpy(s.pose, s.cand, 64); std::memcpy(s.row, row, 4 * kScanMatchRow);
+                s.lambda /= (double)p->lambda_down;
+                small = std::sqrt(s.delta[0] * s.delta[0] + s.delta[1] * s.delta[1] + s.delta[2] * s.delta[2]) < (double)p->tol_trans &&
+                        std::sqrt(s.delta[3] * s.delta[3] + s.delta[4] * s.delta[4] + s.delta[5] * s.delta[5]) < (double)p->tol_rot;
+            } else {
+                s.lambda *= (double)p->lambda_up;
+            }
+            if (small) s.status = 0;
+            else if (s.lambda > (double)p->lambda_max) s.status = 2;
+            else if (s.evals >= p->max_evals) s.status = 1;
+            else if (lm_propose(s, *p)) next.push_back(live[k]);
+        }
+        live.swap(next);
+    }
+    int32_t b = -1;
+    for (size_t h = 0; h < H; ++h) {
+        const LmState& s = st[h];
+        std::memcpy(poses16_out + 16 * h, s.pose, 64);
+        cost[h] = s.row[kRowCost];
+        if (n_inside) n_inside[h] = (int32_t)s.row[kRowInside];
+        if (n_inlier) n_inlier[h] = (int32_t)s.row[kRowInlier];
+        if (evals) evals[h] = s.evals;
+        if (status) status[h] = s.status;
+        if (s.status != 3 && (b < 0 || s.row[kRowCost] < st[(size_t)b].row[kRowCost])) b = (int32_t)h;
+    }
+    if (best) *best = b;
     return MON_OK;
 }
 

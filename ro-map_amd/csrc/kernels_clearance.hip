@@ -7,57 +7,12 @@
 //                        in LDS in sample order, the cost tree there, the two minima by shuffles and through LDS across the waves
 //   k_field_max          the largest value of a field that was made on the device (mon_dist_field_info), in two launches of partial maxima
 // A lane owns a sample: the loop over the body's spheres runs inside it, so the fold over k and the minimum over k need no exchange.  A sample's two end
-// centres are recomputed from the waypoints (a few scalar-cached words) instead of being staged.  The corners of a cell come as four 8-byte loads where
-// n_x > 1 (the two x-neighbours are adjacent words; the address is 4-byte aligned only).  Plain C++, vector stores only, no atomics, no scratch; no
-// workgroup waits for another; every loop is bounded by an argument the host has checked.
-#include <cmath>
-#include "model.h"
+// centres are recomputed from the waypoints (a few scalar-cached words) instead of being staged.  The sample itself (fd_axis, fd_lerp, fd_sample, fd_centre)
+// is field_sample_device.h's, shared with kernels_scan_match.hip.  Plain C++, vector stores only, no atomics, no scratch; no workgroup waits for another;
+// every loop is bounded by an argument the host has checked.
+#include "field_sample_device.h"
 
 namespace mon {
-
-typedef float FdPair __attribute__((ext_vector_type(2), aligned(4)));                 // two adjacent words, loaded at once
-// one axis of a point: inside, the cell and the fraction.  An axis of one cell is neither interpolated nor range-checked.
-struct FdAxis { int i; float f; bool in; };
-__device__ __forceinline__ FdAxis fd_axis(float p, float o, float s, int n) {
-    FdAxis a{ 0, 0.f, true };
-    if (n > 1) {
-        const float g = __fdiv_rn(__fsub_rn(p, o), s);
-        a.in = g >= 0.f && g <= (float)(n - 1);                                     // (a NaN fails)
-        const float gi = a.in ? g : 0.f;
-        a.i = min((int)floorf(gi), n - 2);
-        a.f = __fsub_rn(gi, (float)a.i);
-    }
-    return a;
-}
-__device__ __forceinline__ float fd_lerp(float a, float d, float f) { return __fadd_rn(a, __fmul_rn(f, d)); }      // a + f * (b - a), d = fl(b - a)
-// The field at p.  false: p is outside on some axis (d and g are not written).  GRAD: the gradient in world units, 0 along an axis of one cell.
-template <bool GRAD> __device__ __forceinline__ bool fd_sample(const DistFieldView& F, float px, float py, float pz, float& d, float* g) {
-    const FdAxis ax = fd_axis(px, F.o[0], F.s[0], F.nx), ay = fd_axis(py, F.o[1], F.s[1], F.ny), az = fd_axis(pz, F.o[2], F.s[2], F.nz);
-    if (!(ax.in && ay.in && az.in)) return false;
-    const size_t base = ((size_t)az.i * (size_t)F.ny + (size_t)ay.i) * (size_t)F.nx + (size_t)ax.i;
-    const size_t dy = F.ny > 1 ? (size_t)F.nx : 0, dz = F.nz > 1 ? (size_t)F.nx * (size_t)F.ny : 0;
-    const size_t at[4] = { base, base + dy, base + dz, base + dy + dz };            // (j, k) = (0, 0), (1, 0), (0, 1), (1, 1)
-    float c[4], e[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        float lo, hi;
-        if (F.nx > 1) { const FdPair v = *reinterpret_cast<const FdPair*>(F.D + at[m]); lo = v.x; hi = v.y; }
-        else { lo = F.D[at[m]]; hi = lo; }
-        e[m] = __fsub_rn(hi, lo);
-        c[m] = fd_lerp(lo, e[m], ax.f);
-    }
-    const float h0 = __fsub_rn(c[1], c[0]), h1 = __fsub_rn(c[3], c[2]);
-    const float c0 = fd_lerp(c[0], h0, ay.f), c1 = fd_lerp(c[2], h1, ay.f);
-    const float w = __fsub_rn(c1, c0);
-    d = fd_lerp(c0, w, az.f);
-    if (GRAD) {
-        const float e0 = fd_lerp(e[0], __fsub_rn(e[1], e[0]), ay.f), e1 = fd_lerp(e[2], __fsub_rn(e[3], e[2]), ay.f);
-        g[0] = F.nx > 1 ? __fdiv_rn(fd_lerp(e0, __fsub_rn(e1, e0), az.f), F.s[0]) : 0.f;
-        g[1] = F.ny > 1 ? __fdiv_rn(fd_lerp(h0, __fsub_rn(h1, h0), az.f), F.s[1]) : 0.f;
-        g[2] = F.nz > 1 ? __fdiv_rn(w, F.s[2]) : 0.f;
-    }
-    return true;
-}
 
 __global__ void __launch_bounds__(256) k_field_sample(DistFieldView F, const float* __restrict__ xyz, uint32_t n, float outside, float* __restrict__ dist,
         float* __restrict__ grad) {
@@ -70,16 +25,7 @@ __global__ void __launch_bounds__(256) k_field_sample(DistFieldView F, const flo
     if (grad != nullptr) { grad[3 * (size_t)i] = g[0]; grad[3 * (size_t)i + 1] = g[1]; grad[3 * (size_t)i + 2] = g[2]; }
 }
 
-// ---- trajectories.  The centre of sphere b at waypoint `way` (3 floats: a position; 16: a row-major 4 x 4 matrix, its last row ignored)
-struct Fd3 { float x, y, z; };
-template <bool POSE> __device__ __forceinline__ Fd3 fd_centre(const float* __restrict__ way, float bx, float by, float bz) {
-    if (!POSE) return Fd3{ __fadd_rn(way[0], bx), __fadd_rn(way[1], by), __fadd_rn(way[2], bz) };
-    Fd3 c;
-    c.x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(way[0], bx), __fmul_rn(way[1], by)), __fmul_rn(way[2], bz)), way[3]);
-    c.y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(way[4], bx), __fmul_rn(way[5], by)), __fmul_rn(way[6], bz)), way[7]);
-    c.z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(way[8], bx), __fmul_rn(way[9], by)), __fmul_rn(way[10], bz)), way[11]);
-    return c;
-}
+// ---- trajectories.  A sample's sphere centres come from the waypoints by fd_centre (field_sample_device.h)
 // sample q of a trajectory (its waypoints at `ways`): the centre of sphere b
 template <bool POSE> __device__ __forceinline__ Fd3 fd_sample_centre(const float* __restrict__ ways, uint32_t w, uint32_t u, float tau, float bx, float by,
         float bz) {

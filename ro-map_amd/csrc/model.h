@@ -412,6 +412,13 @@ constexpr uint32_t kFieldMaxBlocks = 256;
 void launch_field_sample(hipStream_t s, const DistFieldView& F, const float* xyz, uint32_t n, float outside, float* dist, float* grad);
 void launch_traj_score(hipStream_t s, const DistFieldView& F, const float* spheres, uint32_t n_spheres, const float* ways, bool pose, TrajScoreArgs a);
 void launch_field_max(hipStream_t s, const float* v, uint32_t n, float* partial, float* out);
+// Scan matching against a distance field (mon_dist_field_match / _register; kernels_scan_match.hip).  launch_scan_match: rows[n_pose][32] = 21 A terms, 6 b
+// terms, cost, n_inside, n_inlier (counts as exact floats), 0, 0 per pose -- or, normal false, rows[n_pose][4] = cost, n_inside, n_inlier, 0.  All arrays
+// are the device's; points must be 16-byte aligned; pivots may be nullptr; scratch: scan_match_scratch(n, n_pose) floats.
+struct ScanMatchArgs { const float* points; const float* poses; const float* pivots; uint32_t n, n_pose; float huber, outside; };
+constexpr uint32_t kScanMatchChunk = 1024, kScanMatchFold = 64, kScanMatchRow = 32, kScanMatchLite = 4;
+size_t scan_match_scratch(uint32_t n, uint32_t n_pose);
+void launch_scan_match(hipStream_t s, const DistFieldView& F, const ScanMatchArgs& a, bool normal, float* scratch, float* rows);
 // Pose refinement (mon_object_pose_loss / mon_object_refine_pose, kernels_pose.hip).  k_pose_rays: one record of 4 float4 per drawn ray from the pose in
 // device memory (pose[16], world -> object); k_pose_grad<shape>: loss and position gradient, one partial row of 8 floats {g, x x g, loss, 0} per workgroup
 // (pose_grad_grid of them); k_pose_update: the rows summed in a fixed order, x inv_n -> out[8 * it] = {loss, grad6, 0}, optionally the Adam step on pose.
@@ -838,6 +845,14 @@ int dist_field_read(DistField* f, float* dist_out);
 int dist_field_sample(DistField* f, const float* xyz, size_t n, float outside, float* dist_out, float* grad3_out);
 int dist_field_score(DistField* f, const float* spheres, size_t n_spheres, const float* ways, int way_floats, size_t n_traj, size_t n_way, size_t n_sub,
                      const mon_traj_score_params* p, float* min_clear, int32_t* first_hit, float* cost, float* way_clear, float* way_grad);
+// Scan matching (dist_field.cpp; the rule: include/mon_core.h).  dist_field_match: cost and, where asked for, the counts and the normal equations of n points
+// under H poses.  dist_field_register: every hypothesis refined by Levenberg-Marquardt in lockstep, one match launch and one read-back of 32 words per pose
+// and round; the 6 x 6 solves and the pose updates are the host's, in double.
+int dist_field_match(DistField* f, const float* points, size_t n, const float* poses16, size_t n_pose, const float* pivots, const mon_scan_match_params* p,
+                     float* cost, int32_t* n_inside, int32_t* n_inlier, float* normal);
+int dist_field_register_default(DistField* f, mon_register_params* p);
+int dist_field_register(DistField* f, const float* points, size_t n, const float* poses16_in, size_t n_pose, const mon_register_params* p, float* poses16_out,
+                        float* cost, int32_t* n_inside, int32_t* n_inlier, int32_t* evals, int32_t* status, int32_t* best);
 // Point gradients (mon_scene_query_gradients / _lattice_gradients, mon_object_query_gradients): the point queries' conventions, plus level_w (host, may be
 // nullptr = all 1: Lmax floats, object j reads its first L_j; the *_check judges the first, scene_gradients_weights_check the rest once the objects are
 // known) and select (host, [n] or nullptr: -1 or an index into ms).  rows (mon_debug_scene_gradient_rows) = object rows_k's rows, host array [n][16].
