@@ -145,7 +145,7 @@ int mon_scene_query_points(mon_object* const* objs, size_t n_objs, int side, con
     std::vector<Model*> ms; int rc;
     if ((rc = scene_points_check(side, world_xyz, n, sigma)) || (rc = scene_models("scene_points", objs, n_objs, ms)) ||
         (rc = scene_objects_check("scene_points", ms.data(), n_objs, false))) return rc;
-    ScenePoints q{}; q.xyz = world_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    const ScenePoints q = scene_point_list(world_xyz, n);
     return scene_points(ms.data(), n_objs, side, q, sigma, rgb, owner, owner_sigma, n_inside, nullptr, 0, nullptr);
 }
 int mon_scene_query_lattice(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz, float* sigma,
@@ -248,7 +248,7 @@ int mon_scene_query_gradients(mon_object* const* objs, size_t n_objs, int side, 
     if ((rc = scene_gradients_check(side, world_xyz, n, level_weights, select, n_objs, sigma, grad_log)) ||
         (rc = scene_models("scene_gradients", objs, n_objs, ms)) || (rc = scene_objects_check("scene_gradients", ms.data(), n_objs, false)) ||
         (rc = scene_gradients_weights_check(ms.data(), n_objs, level_weights))) return rc;
-    ScenePoints q{}; q.xyz = world_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    const ScenePoints q = scene_point_list(world_xyz, n);
     return scene_gradients(ms.data(), n_objs, side, q, level_weights, select, sigma, rgb, owner, owner_sigma, n_inside, grad_log, grad_sigma, normal, nullptr, 0,
                            nullptr);
 }

@@ -312,7 +312,7 @@ int mon_debug_scene_point_rows(mon_object* const* objs, size_t n_objs, int side,
     if ((rc = mon::scene_points_check(side, world_xyz, n, rows)) || (rc = mon::scene_models("scene_points", objs, n_objs, ms)) ||
         (rc = mon::scene_objects_check("scene_points", ms.data(), n_objs, false))) return rc;
     if (k >= n_objs) { set_error("debug_scene_point_rows: k out of range"); return MON_ERR_ARG; }
-    mon::ScenePoints q{}; q.xyz = world_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    const mon::ScenePoints q = mon::scene_point_list(world_xyz, n);
     return mon::scene_points(ms.data(), n_objs, side, q, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k, rows);
 }
 int mon_debug_scene_gradient_rows(mon_object* const* objs, size_t n_objs, int side, const float* world_xyz, size_t n, const float* level_weights, size_t k,
@@ -323,7 +323,7 @@ int mon_debug_scene_gradient_rows(mon_object* const* objs, size_t n_objs, int si
         (rc = mon::scene_models("scene_gradients", objs, n_objs, ms)) || (rc = mon::scene_objects_check("scene_gradients", ms.data(), n_objs, false)) ||
         (rc = mon::scene_gradients_weights_check(ms.data(), n_objs, level_weights))) return rc;
     if (k >= n_objs) { set_error("debug_scene_gradient_rows: k out of range"); return MON_ERR_ARG; }
-    mon::ScenePoints q{}; q.xyz = world_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    const mon::ScenePoints q = mon::scene_point_list(world_xyz, n);
     return mon::scene_gradients(ms.data(), n_objs, side, q, level_weights, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                 k, rows);
 }

@@ -1,7 +1,8 @@
 // dist_field.cpp -- device-resident distance fields (mon_dist_field_*): the handle, the standalone calls and the launch wrappers.  A
 // DistField is a snapshot: its cells in device memory of its own, the lattice they sit on, a stream and the scratch of its calls.  It refers to no object
-// and to no manager.  A sample or score call uploads its inputs, enqueues one kernel and the copy of its outputs to the pinned staging on the handle's
-// stream, and synchronises once; calls on one handle take turns on its mutex.  (mon_scene_dist_field's chain is scene_field.cpp's: it fills a handle made by
+// and to no manager.  A call on a handle goes through FieldCall (the handle's lock and device, room for inputs, outputs and staging, one copy home): it uploads its
+// inputs, enqueues one kernel and the copy of its outputs to the pinned staging on the handle's stream, and synchronises once; calls on one handle take
+// turns on its mutex.  (mon_scene_dist_field's chain is scene_field.cpp's: it fills a handle made by
 // dist_field_adopt.)  Scan matching (mon_dist_field_match, mon_dist_field_register) is here too: the match call follows the same
 // pattern; the register call keeps the scan on the device and runs Levenberg-Marquardt over all hypotheses in lockstep, one match launch, one read-back and
 // one synchronisation per round, with the 6 x 6 solves and the pose updates on the host in double.
@@ -15,19 +16,6 @@ namespace mon {
 constexpr size_t kFieldMaxPoints = (size_t)1 << 24, kFieldMaxSpheres = 32, kFieldMaxWays = 256, kFieldMaxSub = 16, kFieldMaxTraj = 65536,
                  kFieldMaxSamples = (size_t)1 << 24, kFieldMaxCells = (size_t)1 << 22;
 
-struct DistField {
-    std::mutex mu;
-    int device = 0, nx = 1, ny = 1, nz = 1; float origin[3] = { 0, 0, 0 }, step[3] = { 0, 0, 0 }, max_value = 0.f;
-    float* cells = nullptr; hipStream_t s = nullptr;
-    DevBuf<float> in, out; PinnedBuf<float> h_out;                                   // a call's inputs, its outputs and their pinned staging
-    size_t n() const { return (size_t)nx * ny * nz; }
-    DistFieldView view() const {
-        DistFieldView v{ cells, nx, ny, nz, { origin[0], origin[1], origin[2] }, { step[0], step[1], step[2] } };
-        return v;
-    }
-};
-float* dist_field_cells(DistField& f) { return f.cells; }
-void dist_field_set_max(DistField& f, float max_value) { f.max_value = max_value; }
 void dist_field_free(DistField* f) {
     if (!f) return;
     if (use_device(f->device) == hipSuccess) {
@@ -38,30 +26,21 @@ void dist_field_free(DistField* f) {
     delete f;
 }
 // the handle of a lattice with its cells' room and its stream; the caller has set the device
-int dist_field_adopt(int device, const ScenePoints& q, DistField** out) {
+int dist_field_adopt(int device, const Lattice& g, DistField** out) {
     DistField* f = new DistField();
-    f->device = device; f->nx = q.nx; f->ny = q.ny; f->nz = q.nz;
-    for (int a = 0; a < 3; ++a) { f->origin[a] = q.origin[a]; f->step[a] = q.step[a]; }
-    hipError_t e = hipMalloc((void**)&f->cells, 4 * f->n());
+    f->device = device; f->g = g;
+    hipError_t e = hipMalloc((void**)&f->cells, 4 * g.n());
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&f->s, hipStreamNonBlocking);
-    if (e != hipSuccess) { set_error("dist_field: no room for a field of %zu cells: %s", f->n(), hipGetErrorString(e)); dist_field_free(f); return MON_ERR_HIP; }
+    if (e != hipSuccess) { set_error("dist_field: no room for a field of %zu cells: %s", g.n(), hipGetErrorString(e)); dist_field_free(f); return MON_ERR_HIP; }
     *out = f;
     return MON_OK;
 }
 
 // ---- what the calls ask of their arguments, without a device
-static int field_dims_check(const char* what, int nx, int ny, int nz) {
-    if (nx < 1 || ny < 1 || nz < 1) { set_error("%s: lattice %d x %d x %d (each at least 1)", what, nx, ny, nz); return MON_ERR_ARG; }
-    // (each factor bounded before it is multiplied: three ints of up to 2^31 - 1 wrap a 64-bit product)
-    const uint64_t mx = kFieldMaxCells;
-    if ((uint64_t)nx > mx || (uint64_t)ny > mx / (uint64_t)nx || (uint64_t)nz > mx / ((uint64_t)nx * (uint64_t)ny)) {
-        set_error("%s: lattice %d x %d x %d has more than %zu points", what, nx, ny, nz, kFieldMaxCells); return MON_ERR_ARG; }
-    return MON_OK;
-}
 int dist_field_create_check(const float* dist, int nx, int ny, int nz, const float* origin3, const float* step3, const void* field_out) {
     const char* what = "dist_field_create";
     REQUIRE_ARG(what, field_out, "field"); REQUIRE_ARG(what, dist, "dist"); REQUIRE_ARG(what, origin3, "origin"); REQUIRE_ARG(what, step3, "step");
-    { const int rc = field_dims_check(what, nx, ny, nz); if (rc) return rc; }
+    { const int rc = lattice_dims_check(what, nx, ny, nz, kFieldMaxCells); if (rc) return rc; }
     const int dims[3] = { nx, ny, nz };
     for (int a = 0; a < 3; ++a) {
         if (!std::isfinite(origin3[a])) { set_error("%s: origin is not finite", what); return MON_ERR_ARG; }
@@ -73,16 +52,15 @@ int dist_field_create_check(const float* dist, int nx, int ny, int nz, const flo
     return MON_OK;
 }
 int dist_field_create(int device, const float* dist, int nx, int ny, int nz, const float* origin3, const float* step3, DistField** out) {
-    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available"); return MON_ERR_NO_DEVICE; }
-    HIPCHECK(use_device(device));
-    ScenePoints q = scene_lattice(origin3, step3, nx, ny, nz);
+    { const int rc = device_enter(device); if (rc) return rc; }
+    Lattice g(origin3, step3, nx, ny, nz);
     const int dims[3] = { nx, ny, nz };
-    for (int a = 0; a < 3; ++a) if (dims[a] == 1) q.step[a] = 0.f;                  // (ignored; what mon_dist_field_info reports of it)
+    for (int a = 0; a < 3; ++a) if (dims[a] == 1) g.step[a] = 0.f;                  // (ignored; what mon_dist_field_info reports of it)
     DistField* f = nullptr;
-    { const int rc = dist_field_adopt(device, q, &f); if (rc) return rc; }
-    const hipError_t e = hipMemcpy(f->cells, dist, 4 * q.n, hipMemcpyHostToDevice);
+    { const int rc = dist_field_adopt(device, g, &f); if (rc) return rc; }
+    const hipError_t e = hipMemcpy(f->cells, dist, 4 * g.n(), hipMemcpyHostToDevice);
     if (e != hipSuccess) { set_error("dist_field_create: the upload failed: %s", hipGetErrorString(e)); dist_field_free(f); return MON_ERR_HIP; }
-    f->max_value = *std::max_element(dist, dist + q.n);
+    f->max_value = *std::max_element(dist, dist + g.n());
     *out = f;
     return MON_OK;
 }
@@ -90,45 +68,55 @@ int dist_field_create(int device, const float* dist, int nx, int ny, int nz, con
 int dist_field_info(DistField* f, mon_dist_field_desc* info) {
     REQUIRE_ARG("dist_field_info", f, "field"); REQUIRE_ARG("dist_field_info", info, "info");
     std::lock_guard<std::mutex> l(f->mu);
-    info->nx = f->nx; info->ny = f->ny; info->nz = f->nz; info->device = f->device; info->max_value = f->max_value;
-    for (int a = 0; a < 3; ++a) { info->origin[a] = f->origin[a]; info->step[a] = f->step[a]; }
+    info->nx = f->g.nx; info->ny = f->g.ny; info->nz = f->g.nz; info->device = f->device; info->max_value = f->max_value;
+    for (int a = 0; a < 3; ++a) { info->origin[a] = f->g.origin[a]; info->step[a] = f->g.step[a]; }
     return MON_OK;
 }
-// a call's outputs: out.p's first `floats` to the pinned staging, one synchronisation
-static int field_home(DistField& f, size_t floats) {
-    HIPCHECK(hipMemcpyAsync(f.h_out.p, f.out.p, 4 * floats, hipMemcpyDeviceToHost, f.s));
-    HIPCHECK(hipStreamSynchronize(f.s));
-    HIPCHECK(hipGetLastError());
+// One call on a handle, the counterpart of SceneCall (scene.cpp).  enter: the handle -- judged last, what needs no handle has been judged without one -- its
+// lock, which the call holds until it goes, and its device.  room: the call's inputs, outputs and their pinned staging (floats; 0: not used).  home: `floats`
+// from `from` (the handle's memory) to the staging, one synchronisation, the launches' error.
+struct FieldCall {
+    DistField* f = nullptr; std::unique_lock<std::mutex> lock;
+    int enter(const char* what, DistField* field) {
+        REQUIRE_ARG(what, field, "field");
+        f = field; lock = std::unique_lock<std::mutex>(f->mu);
+        HIPCHECK(use_device(f->device));
+        return MON_OK;
+    }
+    int room(size_t in, size_t out, size_t h_out) {
+        int rc; if ((in && (rc = f->in.grow(in))) || (out && (rc = f->out.grow(out))) || (rc = f->h_out.grow(h_out))) return rc;
+        return MON_OK;
+    }
+    int home(const float* from, size_t floats) {
+        HIPCHECK(hipMemcpyAsync(f->h_out.p, from, 4 * floats, hipMemcpyDeviceToHost, f->s));
+        HIPCHECK(hipStreamSynchronize(f->s));
+        HIPCHECK(hipGetLastError());
+        return MON_OK;
+    }
+};
+int dist_field_read(DistField* field, float* dist_out) {
+    FieldCall c; { const int rc = c.enter("dist_field_read", field); if (rc) return rc; }
+    REQUIRE_ARG("dist_field_read", dist_out, "dist_out");
+    DistField& f = *c.f; const size_t n = f.g.n();
+    { int rc; if ((rc = c.room(0, 0, n)) || (rc = c.home(f.cells, n))) return rc; }
+    std::memcpy(dist_out, f.h_out.p, 4 * n);                                        // (the caller's array is written only once everything has succeeded)
     return MON_OK;
 }
-int dist_field_read(DistField* f, float* dist_out) {
-    REQUIRE_ARG("dist_field_read", f, "field"); REQUIRE_ARG("dist_field_read", dist_out, "dist_out");
-    std::lock_guard<std::mutex> l(f->mu);
-    HIPCHECK(use_device(f->device));
-    const size_t n = f->n();
-    { const int rc = f->h_out.grow(n); if (rc) return rc; }
-    HIPCHECK(hipMemcpyAsync(f->h_out.p, f->cells, 4 * n, hipMemcpyDeviceToHost, f->s));
-    HIPCHECK(hipStreamSynchronize(f->s));
-    std::memcpy(dist_out, f->h_out.p, 4 * n);                                       // (the caller's array is written only once everything has succeeded)
-    return MON_OK;
-}
-int dist_field_sample(DistField* f, const float* xyz, size_t n, float outside, float* dist_out, float* grad3_out) {
+int dist_field_sample(DistField* field, const float* xyz, size_t n, float outside, float* dist_out, float* grad3_out) {
     const char* what = "dist_field_sample";
     REQUIRE_ARG(what, xyz, "xyz"); REQUIRE_ARG(what, dist_out, "dist_out");
     if (n == 0 || n > kFieldMaxPoints) { set_error("%s: %zu points (1 to %zu)", what, n, kFieldMaxPoints); return MON_ERR_ARG; }
-    REQUIRE_ARG(what, f, "field");                                                  // (last: what needs no handle is judged without one)
-    std::lock_guard<std::mutex> l(f->mu);
-    HIPCHECK(use_device(f->device));
-    const size_t n_out = grad3_out ? 4 * n : n;
-    { int rc; if ((rc = f->in.grow(3 * n)) || (rc = f->out.grow(n_out)) || (rc = f->h_out.grow(n_out))) return rc; }
-    HIPCHECK(hipMemcpyAsync(f->in.p, xyz, 12 * n, hipMemcpyHostToDevice, f->s));
-    launch_field_sample(f->s, f->view(), f->in.p, (uint32_t)n, outside, f->out.p, grad3_out ? f->out.p + n : nullptr);
-    { const int rc = field_home(*f, n_out); if (rc) return rc; }
-    std::memcpy(dist_out, f->h_out.p, 4 * n);
-    if (grad3_out) std::memcpy(grad3_out, f->h_out.p + n, 12 * n);
+    FieldCall c; { const int rc = c.enter(what, field); if (rc) return rc; }
+    DistField& f = *c.f; const size_t n_out = grad3_out ? 4 * n : n;
+    { const int rc = c.room(3 * n, n_out, n_out); if (rc) return rc; }
+    HIPCHECK(hipMemcpyAsync(f.in.p, xyz, 12 * n, hipMemcpyHostToDevice, f.s));
+    launch_field_sample(f.s, f.cells, f.g, f.in.p, (uint32_t)n, outside, f.out.p, grad3_out ? f.out.p + n : nullptr);
+    { const int rc = c.home(f.out.p, n_out); if (rc) return rc; }
+    std::memcpy(dist_out, f.h_out.p, 4 * n);
+    if (grad3_out) std::memcpy(grad3_out, f.h_out.p + n, 12 * n);
     return MON_OK;
 }
-static int score_check(const char* what, const DistField* f, const float* spheres, size_t n_spheres, const float* ways, int way_floats, size_t n_traj,
+static int score_check(const char* what, const float* spheres, size_t n_spheres, const float* ways, int way_floats, size_t n_traj,
                        size_t n_way, size_t n_sub, const mon_traj_score_params* p, const float* min_clear) {
     REQUIRE_ARG(what, spheres, "spheres"); REQUIRE_ARG(what, ways, "ways"); REQUIRE_ARG(what, p, "params");
     REQUIRE_ARG(what, min_clear, "min_clear");
@@ -146,30 +134,29 @@ static int score_check(const char* what, const DistField* f, const float* sphere
             set_error("%s: sphere %zu is (%g %g %g) r %g (finite, r >= 0)", what, k, (double)b[0], (double)b[1], (double)b[2], (double)b[3]); return MON_ERR_ARG; }
     }
     if (!std::isfinite(p->outside) || !std::isfinite(p->margin) || !std::isfinite(p->safe)) { set_error("%s: a param is not finite", what); return MON_ERR_ARG; }
-    REQUIRE_ARG(what, f, "field");                                                  // (last: what needs no handle is judged without one)
     return MON_OK;
 }
 // in: spheres [n_spheres][4] (padded to 32 records) | ways.  out: min_clear | first_hit | cost (n_traj each) | way_clear | way_grad, those asked for
-int dist_field_score(DistField* f, const float* spheres, size_t n_spheres, const float* ways, int way_floats, size_t n_traj, size_t n_way, size_t n_sub,
+int dist_field_score(DistField* field, const float* spheres, size_t n_spheres, const float* ways, int way_floats, size_t n_traj, size_t n_way, size_t n_sub,
                      const mon_traj_score_params* p, float* min_clear, int32_t* first_hit, float* cost, float* way_clear, float* way_grad) {
     const char* what = "dist_field_score";
-    { const int rc = score_check(what, f, spheres, n_spheres, ways, way_floats, n_traj, n_way, n_sub, p, min_clear); if (rc) return rc; }
-    std::lock_guard<std::mutex> l(f->mu);
-    HIPCHECK(use_device(f->device));
+    { const int rc = score_check(what, spheres, n_spheres, ways, way_floats, n_traj, n_way, n_sub, p, min_clear); if (rc) return rc; }
+    FieldCall c; { const int rc = c.enter(what, field); if (rc) return rc; }
+    DistField& f = *c.f;
     const size_t n_ways = n_traj * n_way, way_words = n_ways * (size_t)way_floats, at_ways = 4 * kFieldMaxSpheres;
     const size_t r_min = 0, r_hit = n_traj, r_cost = 2 * n_traj, r_wc = 3 * n_traj, r_wg = r_wc + (way_clear ? n_ways : 0), n_out = r_wg + (way_grad ? 3 * n_ways : 0);
-    { int rc; if ((rc = f->in.grow(at_ways + way_words)) || (rc = f->out.grow(n_out)) || (rc = f->h_out.grow(n_out))) return rc; }
-    HIPCHECK(hipMemcpyAsync(f->in.p, spheres, 16 * n_spheres, hipMemcpyHostToDevice, f->s));
-    HIPCHECK(hipMemcpyAsync(f->in.p + at_ways, ways, 4 * way_words, hipMemcpyHostToDevice, f->s));
-    float* o = f->out.p;
+    { const int rc = c.room(at_ways + way_words, n_out, n_out); if (rc) return rc; }
+    HIPCHECK(hipMemcpyAsync(f.in.p, spheres, 16 * n_spheres, hipMemcpyHostToDevice, f.s));
+    HIPCHECK(hipMemcpyAsync(f.in.p + at_ways, ways, 4 * way_words, hipMemcpyHostToDevice, f.s));
+    float* o = f.out.p;
     TrajScoreArgs a{};
     a.n_traj = (uint32_t)n_traj; a.n_way = (uint32_t)n_way; a.n_sub = (uint32_t)n_sub; a.n_samp = (uint32_t)((n_way - 1) * n_sub + 1);
     a.outside = p->outside; a.margin = p->margin; a.safe = p->safe;
     a.min_clear = o + r_min; a.first_hit = first_hit ? reinterpret_cast<int32_t*>(o + r_hit) : nullptr; a.cost = cost ? o + r_cost : nullptr;
     a.way_clear = way_clear ? o + r_wc : nullptr; a.way_grad = way_grad ? o + r_wg : nullptr;
-    launch_traj_score(f->s, f->view(), f->in.p, (uint32_t)n_spheres, f->in.p + at_ways, way_floats == 16, a);
-    { const int rc = field_home(*f, n_out); if (rc) return rc; }
-    const float* h = f->h_out.p;
+    launch_traj_score(f.s, f.cells, f.g, f.in.p, (uint32_t)n_spheres, f.in.p + at_ways, way_floats == 16, a);
+    { const int rc = c.home(f.out.p, n_out); if (rc) return rc; }
+    const float* h = f.h_out.p;
     std::memcpy(min_clear, h + r_min, 4 * n_traj);
     if (first_hit) std::memcpy(first_hit, h + r_hit, 4 * n_traj);
     if (cost) std::memcpy(cost, h + r_cost, 4 * n_traj);
@@ -197,38 +184,33 @@ static int match_check(const char* what, const float* points, size_t n, const fl
 // or 4 without the normal equations.
 struct MatchRoom { size_t at_pose, at_rows; };
 static size_t round4(size_t v) { return (v + 3) & ~(size_t)3; }
-static int match_room(DistField& f, size_t n, size_t H, MatchRoom& r) {
+static int match_room(FieldCall& c, const float* points, size_t n, size_t H, MatchRoom& r) {
     r.at_pose = round4(3 * n); r.at_rows = round4(scan_match_scratch((uint32_t)n, (uint32_t)H));
-    int rc;
-    if ((rc = f.in.grow(r.at_pose + 19 * H)) || (rc = f.out.grow(r.at_rows + kScanMatchRow * H)) || (rc = f.h_out.grow(kScanMatchRow * H))) return rc;
+    { const int rc = c.room(r.at_pose + 19 * H, r.at_rows + kScanMatchRow * H, kScanMatchRow * H); if (rc) return rc; }
+    HIPCHECK(hipMemcpyAsync(c.f->in.p, points, 12 * n, hipMemcpyHostToDevice, c.f->s));
     return MON_OK;
 }
-static int match_round(DistField& f, const MatchRoom& r, size_t n, const float* poses16, const float* pivots, size_t live, float huber, float outside,
+static int match_round(FieldCall& c, const MatchRoom& r, size_t n, const float* poses16, const float* pivots, size_t live, float huber, float outside,
                        bool normal) {
+    DistField& f = *c.f;
     float* d_pose = f.in.p + r.at_pose; float* d_piv = d_pose + 16 * live;
     HIPCHECK(hipMemcpyAsync(d_pose, poses16, 64 * live, hipMemcpyHostToDevice, f.s));
     if (pivots) HIPCHECK(hipMemcpyAsync(d_piv, pivots, 12 * live, hipMemcpyHostToDevice, f.s));
     const ScanMatchArgs a{ f.in.p, d_pose, pivots ? d_piv : nullptr, (uint32_t)n, (uint32_t)live, huber, outside };
-    launch_scan_match(f.s, f.view(), a, normal, f.out.p, f.out.p + r.at_rows);
-    HIPCHECK(hipMemcpyAsync(f.h_out.p, f.out.p + r.at_rows, 4 * (normal ? kScanMatchRow : kScanMatchLite) * live, hipMemcpyDeviceToHost, f.s));
-    HIPCHECK(hipStreamSynchronize(f.s));
-    HIPCHECK(hipGetLastError());
-    return MON_OK;
+    launch_scan_match(f.s, f.cells, f.g, a, normal, f.out.p, f.out.p + r.at_rows);
+    return c.home(f.out.p + r.at_rows, (normal ? kScanMatchRow : kScanMatchLite) * live);
 }
 constexpr int kRowCost = 27, kRowInside = 28, kRowInlier = 29;                      // a full row: 21 A terms, 6 b terms, then these
 
-int dist_field_match(DistField* f, const float* points, size_t n, const float* poses16, size_t H, const float* pivots, const mon_scan_match_params* p,
+int dist_field_match(DistField* field, const float* points, size_t n, const float* poses16, size_t H, const float* pivots, const mon_scan_match_params* p,
                      float* cost, int32_t* n_inside, int32_t* n_inlier, float* normal) {
     const char* what = "dist_field_match";
     REQUIRE_ARG(what, points, "points"); REQUIRE_ARG(what, poses16, "poses16"); REQUIRE_ARG(what, p, "params"); REQUIRE_ARG(what, cost, "cost");
     { const int rc = match_check(what, points, n, poses16, H, pivots, p->huber, p->outside); if (rc) return rc; }
-    REQUIRE_ARG(what, f, "field");                                                  // (last: what needs no handle is judged without one)
-    std::lock_guard<std::mutex> l(f->mu);
-    HIPCHECK(use_device(f->device));
-    MatchRoom r;
-    { const int rc = match_room(*f, n, H, r); if (rc) return rc; }
-    HIPCHECK(hipMemcpyAsync(f->in.p, points, 12 * n, hipMemcpyHostToDevice, f->s));
-    { const int rc = match_round(*f, r, n, poses16, pivots, H, p->huber, p->outside, normal != nullptr); if (rc) return rc; }
+    FieldCall c; { const int rc = c.enter(what, field); if (rc) return rc; }
+    DistField* const f = c.f; MatchRoom r;
+    { const int rc = match_room(c, points, n, H, r); if (rc) return rc; }
+    { const int rc = match_round(c, r, n, poses16, pivots, H, p->huber, p->outside, normal != nullptr); if (rc) return rc; }
     const size_t w = normal ? kScanMatchRow : kScanMatchLite, c0 = normal ? kRowCost : 0;
     for (size_t h = 0; h < H; ++h) {
         const float* row = f->h_out.p + w * h;
@@ -243,9 +225,9 @@ int dist_field_match(DistField* f, const float* points, size_t n, const float* p
 int dist_field_register_default(DistField* f, mon_register_params* p) {
     REQUIRE_ARG("register_default", p, "p"); REQUIRE_ARG("register_default", f, "field");
     std::lock_guard<std::mutex> l(f->mu);
-    const int dims[3] = { f->nx, f->ny, f->nz };
+    const int dims[3] = { f->g.nx, f->g.ny, f->g.nz };
     float step = 0.f;
-    for (int a = 0; a < 3; ++a) if (dims[a] > 1) step = std::max(step, std::fabs(f->step[a]));
+    for (int a = 0; a < 3; ++a) if (dims[a] > 1) step = std::max(step, std::fabs(f->g.step[a]));
     if (step == 0.f) step = 1.f;
     *p = mon_register_params{ 2.f * step, f->max_value, 30, 1e-3f, 10.f, 10.f, 1e6f, 1e-3f * step, 1e-4f, 6 };
     return MON_OK;
@@ -316,11 +298,11 @@ static bool lm_propose(LmState& s, const mon_register_params& p) {
     lm_step(s.pose, s.pivot, s.delta, s.cand);
     return true;
 }
-int dist_field_register(DistField* f, const float* points, size_t n, const float* poses16_in, size_t H, const mon_register_params* p, float* poses16_out,
+int dist_field_register(DistField* field, const float* points, size_t n, const float* poses16_in, size_t H, const mon_register_params* p, float* poses16_out,
                         float* cost, int32_t* n_inside, int32_t* n_inlier, int32_t* evals, int32_t* status, int32_t* best) {
     const char* what = "dist_field_register";
     { const int rc = register_check(what, points, n, poses16_in, H, p, poses16_out, cost); if (rc) return rc; }
-    REQUIRE_ARG(what, f, "field");                                                  // (last: what needs no handle is judged without one)
+    FieldCall c; { const int rc = c.enter(what, field); if (rc) return rc; }
     // the pivots: each input pose applied to the centroid of the finite points (the scan is read only now; still before any device work)
     double cen[3] = { 0, 0, 0 }; size_t n_fin = 0;
     for (size_t i = 0; i < n; ++i) {
@@ -339,18 +321,15 @@ int dist_field_register(DistField* f, const float* points, size_t n, const float
         }
         s.lambda = (double)p->lambda0;
     }
-    std::lock_guard<std::mutex> l(f->mu);
-    HIPCHECK(use_device(f->device));
-    MatchRoom r;
-    { const int rc = match_room(*f, n, H, r); if (rc) return rc; }
-    HIPCHECK(hipMemcpyAsync(f->in.p, points, 12 * n, hipMemcpyHostToDevice, f->s));
+    DistField* const f = c.f; MatchRoom r;
+    { const int rc = match_room(c, points, n, H, r); if (rc) return rc; }
     std::vector<float> up(19 * H);
     for (bool first = true; !live.empty(); first = false) {
         // the candidates of the hypotheses still running: poses, then pivots, as match_round lays them out
         for (size_t k = 0; k < live.size(); ++k) {
             std::memcpy(up.data() + 16 * k, st[live[k]].cand, 64); std::memcpy(up.data() + 16 * live.size() + 3 * k, st[live[k]].pivot, 12);
         }
-        { const int rc = match_round(*f, r, n, up.data(), up.data() + 16 * live.size(), live.size(), p->huber, p->outside, true); if (rc) return rc; }
+        { const int rc = match_round(c, r, n, up.data(), up.data() + 16 * live.size(), live.size(), p->huber, p->outside, true); if (rc) return rc; }
         std::vector<size_t> next;
         for (size_t k = 0; k < live.size(); ++k) {
             LmState& s = st[live[k]]; const float* row = f->h_out.p + kScanMatchRow * k;

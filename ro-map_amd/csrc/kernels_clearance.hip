@@ -149,11 +149,14 @@ __global__ void __launch_bounds__(256) k_field_max(const float* __restrict__ v, 
     if (threadIdx.x == 0u) out[blockIdx.x] = fmaxf(fmaxf(m_s[0], m_s[1]), fmaxf(m_s[2], m_s[3]));
 }
 
-void launch_field_sample(hipStream_t s, const DistFieldView& F, const float* xyz, uint32_t n, float outside, float* dist, float* grad) {
+void launch_field_sample(hipStream_t s, const float* D, const Lattice& g, const float* xyz, uint32_t n, float outside, float* dist, float* grad) {
+    const DistFieldView F = dist_field_view(D, g);
     hipLaunchKernelGGL(k_field_sample, dim3((n + 255u) / 256u), dim3(256), 0, s, F, xyz, n, outside, dist, grad);
 }
 uint32_t traj_score_pad(uint32_t n_samp) { uint32_t p = 1; while (p < n_samp) p <<= 1; return p; }
-void launch_traj_score(hipStream_t s, const DistFieldView& F, const float* spheres, uint32_t n_spheres, const float* ways, bool pose, TrajScoreArgs a) {
+void launch_traj_score(hipStream_t s, const float* D, const Lattice& g, const float* spheres, uint32_t n_spheres, const float* ways, bool pose,
+        TrajScoreArgs a) {
+    const DistFieldView F = dist_field_view(D, g);
     a.pad = traj_score_pad(a.n_samp);
     if (a.n_samp <= 64u) {
         const dim3 grid((a.n_traj + 3u) / 4u);

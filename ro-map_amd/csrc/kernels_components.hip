@@ -11,24 +11,20 @@
 // the flag word the host turns into MON_ERR_STATE.
 #include <algorithm>
 #include <climits>
-#include "model.h"
+#include "lattice_device.h"
 
 namespace mon {
 
-constexpr uint32_t kCcTX = 32, kCcTY = 8, kCcTZ = 4, kCcTile = kCcTX * kCcTY * kCcTZ, kCcPer = kCcTile / 256;
-static_assert(kCcPer * 256 == kCcTile, "every thread owns kCcPer cells of the tile");
-constexpr uint32_t kCcRoundCap = kCcTile + 1;                   // a tile's fixed point: at most one round per cell (see k_cc_local), one more to see it
+constexpr uint32_t kCcPer = kTileCells / 256;
+static_assert(kCcPer * 256 == kTileCells, "every thread owns kCcPer cells of the tile");
+constexpr uint32_t kCcRoundCap = kTileCells + 1;                   // a tile's fixed point: at most one round per cell (see k_cc_local), one more to see it
 constexpr uint32_t kCcWalkCap = (1u << 22) + 1;                 // a walk to the root strictly decreases an index below n <= 2^22
 constexpr uint32_t kCcUnionCap = (1u << 23) + 2;                // a union's rounds strictly decrease a + b < 2 n
 
 __device__ __forceinline__ int32_t cc_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void cc_fail(uint32_t* flag) { atomicOr(flag, 1u); }
 
-// the 13 neighbours of lower flat index, by (dx, dy, dz); CONN 6 / 18 / 26 admits those whose |dx| + |dy| + |dz| is at most 1 / 2 / 3
-template <int CONN> __device__ __forceinline__ constexpr bool cc_admits(int dx, int dy, int dz) {
-    return (dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy) + (dz < 0 ? -dz : dz) <= (CONN == 6 ? 1 : CONN == 18 ? 2 : 3);
-}
-// f(dx, dy, dz) for every admitted neighbour of lower flat index: dz = -1 with any dx, dy; dz = 0, dy = -1 with any dx; (-1, 0, 0)
+// f(dx, dy, dz) for every admitted neighbour among the 13 of lower flat index: dz = -1 with any dx, dy; dz = 0, dy = -1 with any dx; (-1, 0, 0)
 template <int CONN, class F> __device__ __forceinline__ void cc_lower_neighbours(F&& f) {
 #pragma unroll
     for (int dz = -1; dz <= 0; ++dz)
@@ -37,7 +33,7 @@ template <int CONN, class F> __device__ __forceinline__ void cc_lower_neighbours
 #pragma unroll
             for (int dx = -1; dx <= 1; ++dx) {
                 const bool lower = dz < 0 || (dz == 0 && (dy < 0 || (dy == 0 && dx < 0)));
-                if (lower && cc_admits<CONN>(dx, dy, dz)) f(dx, dy, dz);
+                if (lower && admits<CONN>(dx, dy, dz)) f(dx, dy, dz);
             }
 }
 
@@ -48,15 +44,15 @@ template <int CONN, class F> __device__ __forceinline__ void cc_lower_neighbours
 // The fixed point (no edge with two labels) gives every cell its component's lowest cell of the tile.
 template <int CONN> __global__ void __launch_bounds__(256) k_cc_local(const uint8_t* __restrict__ occ, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t tiles_x,
         uint32_t tiles_y, int32_t* __restrict__ label, uint32_t* __restrict__ flag) {
-    __shared__ int32_t lab[kCcTile];
+    __shared__ int32_t lab[kTileCells];
     const uint32_t tid = threadIdx.x;
-    const uint32_t tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, tz = blockIdx.x / (tiles_x * tiles_y);
-    const uint32_t lx = tid % kCcTX, ly = tid / kCcTX;                              // the thread's cells: (lx, ly, q), q < kCcPer = kCcTZ
-    const uint32_t x = tx * kCcTX + lx, y = ty * kCcTY + ly;
+    const Cell t = split(blockIdx.x, tiles_x, tiles_y); const uint32_t tx = t.x, ty = t.y, tz = t.z;
+    const uint32_t lx = tid % kTileX, ly = tid / kTileX;                              // the thread's cells: (lx, ly, q), q < kCcPer = kTileZ
+    const uint32_t x = tx * kTileX + lx, y = ty * kTileY + ly;
     bool on[kCcPer];                                                                // the cell lies in the lattice and in the mask
 #pragma unroll
     for (uint32_t q = 0; q < kCcPer; ++q) {
-        const uint32_t z = tz * kCcTZ + q, c = q * 256u + tid;
+        const uint32_t z = tz * kTileZ + q, c = q * 256u + tid;
         on[q] = x < nx && y < ny && z < nz && occ[((size_t)z * ny + y) * nx + x] != 0;
         lab[c] = on[q] ? (int32_t)c : -1;
     }
@@ -70,8 +66,8 @@ template <int CONN> __global__ void __launch_bounds__(256) k_cc_local(const uint
             const uint32_t c = q * 256u + tid;
             const int32_t a = lab[c];
             cc_lower_neighbours<CONN>([&](int dx, int dy, int dz) {
-                if ((int)lx + dx < 0 || (int)lx + dx >= (int)kCcTX || (int)ly + dy < 0 || (int)ly + dy >= (int)kCcTY || (int)q + dz < 0) return;
-                const int32_t b = lab[(int)c + (dz * (int)kCcTY + dy) * (int)kCcTX + dx];
+                if ((int)lx + dx < 0 || (int)lx + dx >= (int)kTileX || (int)ly + dy < 0 || (int)ly + dy >= (int)kTileY || (int)q + dz < 0) return;
+                const int32_t b = lab[(int)c + (dz * (int)kTileY + dy) * (int)kTileX + dx];
                 if (b >= 0 && b != a) { atomicMin(&lab[max(a, b)], min(a, b)); changed = true; }
             });
         }
@@ -81,7 +77,7 @@ template <int CONN> __global__ void __launch_bounds__(256) k_cc_local(const uint
             if (!on[q]) continue;
             const uint32_t c = q * 256u + tid;
             int32_t l = lab[c];
-            for (uint32_t it = 0; it < kCcTile; ++it) { const int32_t p = lab[l]; if (p == l) break; l = p; }      // strictly decreasing
+            for (uint32_t it = 0; it < kTileCells; ++it) { const int32_t p = lab[l]; if (p == l) break; l = p; }      // strictly decreasing
             lab[c] = l;
         }
         __syncthreads();
@@ -89,12 +85,12 @@ template <int CONN> __global__ void __launch_bounds__(256) k_cc_local(const uint
     if (round == kCcRoundCap && tid == 0) cc_fail(flag);
 #pragma unroll
     for (uint32_t q = 0; q < kCcPer; ++q) {
-        const uint32_t z = tz * kCcTZ + q;
+        const uint32_t z = tz * kTileZ + q;
         if (!(x < nx && y < ny && z < nz)) continue;
         int32_t out = -1;
         if (on[q]) {
             const uint32_t r = (uint32_t)lab[q * 256u + tid];
-            out = (int32_t)((((size_t)(tz * kCcTZ + r / 256u)) * ny + (ty * kCcTY + (r % 256u) / kCcTX)) * nx + (tx * kCcTX + r % kCcTX));
+            out = (int32_t)((((size_t)(tz * kTileZ + r / 256u)) * ny + (ty * kTileY + (r % 256u) / kTileX)) * nx + (tx * kTileX + r % kTileX));
         }
         label[((size_t)z * ny + y) * nx + x] = out;
     }
@@ -124,14 +120,14 @@ template <int CONN> __global__ void __launch_bounds__(256) k_cc_merge(uint32_t n
         uint32_t* __restrict__ flag) {
     const uint32_t n = nx * ny * nz, i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const uint32_t x = i % nx, y = (i / nx) % ny, z = i / (nx * ny);
+    const Cell c = split(i, nx, ny); const uint32_t x = c.x, y = c.y, z = c.z;
     // only a cell on a low face of its tile, or next to a tile's side in x or y, has a lower neighbour in another tile
-    if ((x % kCcTX) != 0 && (x % kCcTX) != kCcTX - 1 && (y % kCcTY) != 0 && (y % kCcTY) != kCcTY - 1 && (z % kCcTZ) != 0) return;
+    if ((x % kTileX) != 0 && (x % kTileX) != kTileX - 1 && (y % kTileY) != 0 && (y % kTileY) != kTileY - 1 && (z % kTileZ) != 0) return;
     if (label[i] < 0) return;
     cc_lower_neighbours<CONN>([&](int dx, int dy, int dz) {
         const int X = (int)x + dx, Y = (int)y + dy, Z = (int)z + dz;
         if (X < 0 || X >= (int)nx || Y < 0 || Y >= (int)ny || Z < 0) return;
-        if ((uint32_t)X / kCcTX == x / kCcTX && (uint32_t)Y / kCcTY == y / kCcTY && (uint32_t)Z / kCcTZ == z / kCcTZ) return;      // stage 1 did it
+        if ((uint32_t)X / kTileX == x / kTileX && (uint32_t)Y / kTileY == y / kTileY && (uint32_t)Z / kTileZ == z / kTileZ) return;      // stage 1 did it
         const uint32_t j = ((uint32_t)Z * ny + (uint32_t)Y) * nx + (uint32_t)X;
         if (label[j] >= 0) cc_union(label, (int32_t)i, (int32_t)j, flag);           // (in or out of the mask never changes: a plain load)
     });
@@ -237,7 +233,7 @@ __global__ void __launch_bounds__(256) k_cc_table(uint32_t nx, uint32_t ny, uint
             if (cur >= 0) cc_gather(slot, table, cur, cnt, lx, ly, lz, hx, hy, hz);
             cur = c; cnt = 0; lx = ly = lz = INT_MAX; hx = hy = hz = INT_MIN;
         }
-        const int32_t x = (int32_t)(i % nx), y = (int32_t)((i / nx) % ny), z = (int32_t)(i / (nx * ny));
+        const Cell at = split(i, nx, ny); const int32_t x = (int32_t)at.x, y = (int32_t)at.y, z = (int32_t)at.z;
         ++cnt; lx = min(lx, x); ly = min(ly, y); lz = min(lz, z); hx = max(hx, x); hy = max(hy, y); hz = max(hz, z);
     }
     if (cur >= 0) cc_gather(slot, table, cur, cnt, lx, ly, lz, hx, hy, hz);
@@ -267,22 +263,18 @@ __global__ void __launch_bounds__(256) k_cc_home(const uint32_t* __restrict__ sr
 
 size_t components_scan_words(uint32_t n) { return (n + 255u) / 256u + 1u; }
 
-void launch_components(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, int connectivity, int32_t* label, int32_t* comp,
-        uint32_t* scan, mon_lattice_component* table, uint32_t cap, uint32_t* meta) {
-    const uint32_t n = nx * ny * nz, nb = (n + 255u) / 256u;
-    const uint32_t tiles_x = (nx + kCcTX - 1u) / kCcTX, tiles_y = (ny + kCcTY - 1u) / kCcTY, tiles_z = (nz + kCcTZ - 1u) / kCcTZ;
-    const dim3 tiles(tiles_x * tiles_y * tiles_z), cells(nb), b(256);
+void launch_components(hipStream_t s, const uint8_t* occ, const Lattice& g, int connectivity, int32_t* label, int32_t* comp, uint32_t* scan,
+        mon_lattice_component* table, uint32_t cap, uint32_t* meta) {
+    const uint32_t nx = (uint32_t)g.nx, ny = (uint32_t)g.ny, nz = (uint32_t)g.nz, n = nx * ny * nz, nb = (n + 255u) / 256u;
+    const Tiles tl = tiles(g);
+    const dim3 cells(nb), b(256);
     uint32_t* flag = meta + 1;
     int32_t* t = reinterpret_cast<int32_t*>(table);
     (void)hipMemsetAsync(meta, 0, 2 * sizeof(uint32_t), s);
-    switch (connectivity) {
-        case 6:  hipLaunchKernelGGL(k_cc_local<6>, tiles, b, 0, s, occ, nx, ny, nz, tiles_x, tiles_y, label, flag);
-                 hipLaunchKernelGGL(k_cc_merge<6>, cells, b, 0, s, nx, ny, nz, label, flag); break;
-        case 18: hipLaunchKernelGGL(k_cc_local<18>, tiles, b, 0, s, occ, nx, ny, nz, tiles_x, tiles_y, label, flag);
-                 hipLaunchKernelGGL(k_cc_merge<18>, cells, b, 0, s, nx, ny, nz, label, flag); break;
-        default: hipLaunchKernelGGL(k_cc_local<26>, tiles, b, 0, s, occ, nx, ny, nz, tiles_x, tiles_y, label, flag);
-                 hipLaunchKernelGGL(k_cc_merge<26>, cells, b, 0, s, nx, ny, nz, label, flag); break;
-    }
+    dispatch_connectivity(connectivity, [&](auto conn) {
+        hipLaunchKernelGGL(k_cc_local<conn.value>, dim3(tl.n()), b, 0, s, occ, nx, ny, nz, tl.x, tl.y, label, flag);
+        hipLaunchKernelGGL(k_cc_merge<conn.value>, cells, b, 0, s, nx, ny, nz, label, flag);
+    });
     hipLaunchKernelGGL(k_cc_flatten, cells, b, 0, s, n, label, scan, flag);
     hipLaunchKernelGGL(k_cc_scan, dim3(1), dim3(1024), 0, s, scan, nb, meta);
     hipLaunchKernelGGL(k_cc_number, cells, b, 0, s, n, label, scan, comp, t, cap);

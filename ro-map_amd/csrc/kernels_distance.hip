@@ -145,8 +145,8 @@ void launch_distance_mask(hipStream_t s, uint32_t n, const float* sigma, float s
     hipLaunchKernelGGL(k_distance_mask, dim3((n + 255u) / 256u), dim3(256), 0, s, n, sigma, sigma_min, occ);
 }
 // the three passes: occ (inverted or not) -> d2, site in v[0 .. n), site[0 .. n); v and site hold 2 n elements each (the passes alternate between the halves)
-void launch_distance_passes(hipStream_t s, const uint8_t* occ, bool invert, uint32_t nx, uint32_t ny, uint32_t nz, const float* step3, float* v, int32_t* site) {
-    const uint32_t n = nx * ny * nz;
+void launch_distance_passes(hipStream_t s, const uint8_t* occ, bool invert, const Lattice& g, float* v, int32_t* site) {
+    const uint32_t nx = (uint32_t)g.nx, ny = (uint32_t)g.ny, nz = (uint32_t)g.nz, n = nx * ny * nz;
     const uint32_t len[3] = { nx, ny, nz }, lines[3] = { ny * nz, nx * nz, nx * ny }, stride[3] = { 1u, nx, nx * ny };
     const uint32_t cw[3] = { 1u, nx, nx * ny }, cs[3] = { nx, nx * ny, 0u };
     for (int ax = 0; ax < 3; ++ax) {
@@ -154,7 +154,7 @@ void launch_distance_passes(hipStream_t s, const uint8_t* occ, bool invert, uint
         const uint32_t in = ax == 1 ? 0u : n, out = ax == 1 ? n : 0u;       // x: mask -> low half; y: low -> high; z: high -> low
         if (ax == 0) { a.occ = occ; a.invert = invert ? 1u : 0u; } else { a.v_in = v + in; a.s_in = site + in; }
         a.v_out = v + out; a.s_out = site + out;
-        a.n = len[ax]; a.m = lines[ax]; a.stride = stride[ax]; a.cw = cw[ax]; a.cs = cs[ax]; a.step = step3[ax];
+        a.n = len[ax]; a.m = lines[ax]; a.stride = stride[ax]; a.cw = cw[ax]; a.cs = cs[ax]; a.step = g.step[ax];
         a.rows_fast = ax == 0 ? 1u : 0u;
         // x: the tile as long as the line allows (at least kDistOut rows: a thread's cells are rows of one line); y, z: up to 64 lines side by side
         a.logR = ax == 0 ? std::min(std::max(ceil_log2(a.n), ceil_log2(kDistOut)), ceil_log2(kDistTile)) : ceil_log2(kDistTile) - std::min(ceil_log2(a.m), 6u);

@@ -1,7 +1,7 @@
 // kernels_paths.hip -- shortest-path cost fields over a lattice (mon_shortest_paths, mon_scene_paths_lattice): per passable cell the least
 // fp32 left fold of the move weights over all walks from a seed (cost), and the neighbour to step to (next).  The rule is in include/mon_core.h.
 //   1  k_paths_init, k_paths_seed   cost = +inf; 0 at every passable seed, and sweep 0's flag of every tile that sees the seed
-//   2  k_paths_sweep<CONN, COST>    a launch per sweep, a workgroup per tile of 32 x 8 x 4 cells (the components tile).  A tile without a flag returns.  A
+//   2  k_paths_sweep<CONN, COST>    a launch per sweep, a workgroup per tile of 32 x 8 x 4 cells (lattice_device.h).  A tile without a flag returns.  A
 //                                   flagged one stages its cells and a one-cell halo in LDS, relaxes its own cells to the fixed point under that halo,
 //                                   stores the cells that fell and raises the next sweep's flag of every neighbour tile that can see one of them
 //   3  k_paths_finish<CONN, COST>   a thread per cell: next by the header's rule on the untruncated field, then the max_cost cut
@@ -13,24 +13,20 @@
 // w >= 0).  No workgroup waits for another; the tile's rounds are bounded (a tile that ran into the bound would raise its own flag again); plain C++, vector
 // stores only, no atomics, no scratch.
 #include <cmath>
-#include "model.h"
+#include "lattice_device.h"
 
 namespace mon {
 
-constexpr uint32_t kPtTX = 32, kPtTY = 8, kPtTZ = 4, kPtTile = kPtTX * kPtTY * kPtTZ, kPtPer = kPtTile / 256;
-constexpr uint32_t kPtHX = kPtTX + 2, kPtHY = kPtTY + 2, kPtHZ = kPtTZ + 2, kPtHalo = kPtHX * kPtHY * kPtHZ;      // 34 x 10 x 6 = 2 040 words
-static_assert(kPtPer == kPtTZ && kPtTX * kPtTY == 256, "a thread owns the column (lx, ly) of its tile");
+constexpr uint32_t kPtPer = kTileCells / 256;
+constexpr uint32_t kPtHX = kTileX + 2, kPtHY = kTileY + 2, kPtHZ = kTileZ + 2, kPtHalo = kPtHX * kPtHY * kPtHZ;      // 34 x 10 x 6 = 2 040 words
+static_assert(kPtPer == kTileZ && kTileX * kTileY == 256, "a thread owns the column (lx, ly) of its tile");
 // Rounds of a tile.  Under the values of its halo a cell's fixed point is the fold of a walk inside the tile from a halo cell or from a cell that keeps its
-// value; a least walk need not visit a cell twice (costs never fall along a walk), so it has at most kPtTile moves, and round r has settled the walks of r
+// value; a least walk need not visit a cell twice (costs never fall along a walk), so it has at most kTileCells moves, and round r has settled the walks of r
 // moves (a relaxation that reads a neighbour's newer value is only earlier).  One more round sees that nothing changed.
-constexpr uint32_t kPtRoundCap = kPtTile + 1;
+constexpr uint32_t kPtRoundCap = kTileCells + 1;
 
 __device__ __forceinline__ float pt_load(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-template <int CONN> __device__ __forceinline__ constexpr bool pt_admits(int dx, int dy, int dz) {
-    const int m = (dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy) + (dz < 0 ? -dz : dz);
-    return m != 0 && m <= (CONN == 6 ? 1 : CONN == 18 ? 2 : 3);
-}
 // f(dx, dy, dz) for every admitted neighbour, in ascending flat index
 template <int CONN, class F> __device__ __forceinline__ void pt_neighbours(F&& f) {
 #pragma unroll
@@ -39,7 +35,7 @@ template <int CONN, class F> __device__ __forceinline__ void pt_neighbours(F&& f
         for (int dy = -1; dy <= 1; ++dy)
 #pragma unroll
             for (int dx = -1; dx <= 1; ++dx)
-                if (pt_admits<CONN>(dx, dy, dz)) f(dx, dy, dz);
+                if (admits<CONN>(dx, dy, dz)) f(dx, dy, dz);
 }
 // The lengths of the moves by which axes they use: len[(dz != 0) * 4 + (dy != 0) * 2 + (dx != 0)] = sqrtf(((ax * ax) + (ay * ay)) + (az * az)), every
 // operation rounded on its own; an axis the move does not use adds an exact +0, and (-s) * (-s) == s * s.  (sqrtf: the IEEE root, as k_distance_finish.)
@@ -72,12 +68,12 @@ __global__ void __launch_bounds__(256) k_paths_seed(const uint8_t* __restrict__ 
     if (k >= n_seeds) return;
     const uint32_t i = (uint32_t)seeds[k];
     if (occ[i] == 0) return;
-    const int x = (int)(i % nx), y = (int)((i / nx) % ny), z = (int)(i / (nx * ny));
+    const Cell at = split(i, nx, ny); const int x = (int)at.x, y = (int)at.y, z = (int)at.z;
     cost[i] = 0.f;
     for (int dz = -1; dz <= 1; ++dz) for (int dy = -1; dy <= 1; ++dy) for (int dx = -1; dx <= 1; ++dx) {
         const int X = x + dx, Y = y + dy, Z = z + dz;
         if (X < 0 || X >= (int)nx || Y < 0 || Y >= (int)ny || Z < 0 || Z >= (int)nz) continue;
-        flags[(((uint32_t)Z / kPtTZ) * tiles_y + (uint32_t)Y / kPtTY) * tiles_x + (uint32_t)X / kPtTX] = 1;
+        flags[(((uint32_t)Z / kTileZ) * tiles_y + (uint32_t)Y / kTileY) * tiles_x + (uint32_t)X / kTileX] = 1;
     }
 }
 
@@ -91,21 +87,21 @@ template <int CONN, bool COST> __global__ void __launch_bounds__(256) k_paths_sw
     const uint32_t tile = blockIdx.x;
     if (cur[tile] == 0) return;
     const uint32_t tid = threadIdx.x;
-    const uint32_t tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, tz = tile / (tiles_x * tiles_y);
+    const uint32_t tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, tz = tile / (tiles_x * tiles_y);   // (split() here reorders the halo's compares)
     // the tile and its halo; outside the lattice: +inf, which no relaxation lowers and from which nothing is reached
     for (uint32_t h = tid; h < kPtHalo; h += 256u) {
-        const int X = (int)(tx * kPtTX + h % kPtHX) - 1, Y = (int)(ty * kPtTY + (h / kPtHX) % kPtHY) - 1, Z = (int)(tz * kPtTZ + h / (kPtHX * kPtHY)) - 1;
+        const int X = (int)(tx * kTileX + h % kPtHX) - 1, Y = (int)(ty * kTileY + (h / kPtHX) % kPtHY) - 1, Z = (int)(tz * kTileZ + h / (kPtHX * kPtHY)) - 1;
         const bool in = X >= 0 && X < (int)nx && Y >= 0 && Y < (int)ny && Z >= 0 && Z < (int)nz;
         const size_t g = ((size_t)(in ? Z : 0) * ny + (size_t)(in ? Y : 0)) * nx + (size_t)(in ? X : 0);
         c_s[h] = in ? pt_load(cost + g) : INFINITY;
         if (COST) m_s[h] = in ? mult[g] : 0.f;
     }
     if (tid < 27u) nb[tid] = 0u;
-    const uint32_t lx = tid % kPtTX, ly = tid / kPtTX, x = tx * kPtTX + lx, y = ty * kPtTY + ly;
+    const uint32_t lx = tid % kTileX, ly = tid / kTileX, x = tx * kTileX + lx, y = ty * kTileY + ly;
     bool on[kPtPer]; float first[kPtPer];
 #pragma unroll
     for (uint32_t q = 0; q < kPtPer; ++q) {
-        const uint32_t z = tz * kPtTZ + q;
+        const uint32_t z = tz * kTileZ + q;
         on[q] = x < nx && y < ny && z < nz && occ[((size_t)z * ny + y) * nx + x] != 0;
     }
     __syncthreads();                                                                // (every thread has read cur[tile])
@@ -140,13 +136,13 @@ template <int CONN, bool COST> __global__ void __launch_bounds__(256) k_paths_sw
         if (!on[q]) continue;
         const float v = c_s[((q + 1u) * kPtHY + ly + 1u) * kPtHX + lx + 1u];
         if (!(v < first[q])) continue;
-        cost[((size_t)(tz * kPtTZ + q) * ny + y) * nx + x] = v;
-        const int bx = lx == 0 ? -1 : lx == kPtTX - 1 ? 1 : 0, by = ly == 0 ? -1 : ly == kPtTY - 1 ? 1 : 0, bz = q == 0 ? -1 : q == kPtTZ - 1 ? 1 : 0;
+        cost[((size_t)(tz * kTileZ + q) * ny + y) * nx + x] = v;
+        const int bx = lx == 0 ? -1 : lx == kTileX - 1 ? 1 : 0, by = ly == 0 ? -1 : ly == kTileY - 1 ? 1 : 0, bz = q == 0 ? -1 : q == kTileZ - 1 ? 1 : 0;
 #pragma unroll
         for (int m = 1; m < 8; ++m) {
             const int ox = (m & 1) ? bx : 0, oy = (m & 2) ? by : 0, oz = (m & 4) ? bz : 0;
             if (((m & 1) && bx == 0) || ((m & 2) && by == 0) || ((m & 4) && bz == 0)) continue;
-            if (!pt_admits<CONN>(ox, oy, oz)) continue;
+            if (!admits<CONN>(ox, oy, oz)) continue;
             nb[(oz + 1) * 9 + (oy + 1) * 3 + (ox + 1)] = 1u;
         }
     }
@@ -172,7 +168,7 @@ template <int CONN, bool COST> __global__ void __launch_bounds__(256) k_paths_fi
     float cv = occ[i] != 0 ? cost[i] : INFINITY;
     int32_t to = -1;
     if (next != nullptr && cv < INFINITY && cv <= max_cost) {
-        const int x = (int)(i % nx), y = (int)((i / nx) % ny), z = (int)(i / (nx * ny));
+        const Cell at = split(i, nx, ny); const int x = (int)at.x, y = (int)at.y, z = (int)at.z;
         const PtLen len = pt_lengths(sx, sy, sz);
         const float mv = COST ? mult[i] : 0.f;
         pt_neighbours<CONN>([&](int dx, int dy, int dz) {
@@ -194,51 +190,33 @@ __global__ void __launch_bounds__(256) k_paths_soft(uint32_t n, const float* __r
     if (i < n) mult[i] = __fadd_rn(1.f, __fmul_rn(soft_weight, __fdiv_rn(fmaxf(0.f, __fsub_rn(soft_radius, dist[i])), soft_radius)));
 }
 
-uint32_t paths_tiles(uint32_t nx, uint32_t ny, uint32_t nz) {
-    return ((nx + kPtTX - 1u) / kPtTX) * ((ny + kPtTY - 1u) / kPtTY) * ((nz + kPtTZ - 1u) / kPtTZ);
-}
-void launch_paths_init(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, const int32_t* seeds, uint32_t n_seeds, float* cost,
-        uint8_t* flags) {
-    const uint32_t n = nx * ny * nz, tiles_x = (nx + kPtTX - 1u) / kPtTX, tiles_y = (ny + kPtTY - 1u) / kPtTY;
-    (void)hipMemsetAsync(flags, 0, 2 * (size_t)paths_tiles(nx, ny, nz), s);
+uint32_t paths_tiles(const Lattice& g) { return tiles(g).n(); }
+void launch_paths_init(hipStream_t s, const uint8_t* occ, const Lattice& g, const int32_t* seeds, uint32_t n_seeds, float* cost, uint8_t* flags) {
+    const uint32_t nx = (uint32_t)g.nx, ny = (uint32_t)g.ny, nz = (uint32_t)g.nz, n = nx * ny * nz; const Tiles tl = tiles(g);
+    (void)hipMemsetAsync(flags, 0, 2 * (size_t)tl.n(), s);
     hipLaunchKernelGGL(k_paths_init, dim3((n + 255u) / 256u), dim3(256), 0, s, n, cost);
-    hipLaunchKernelGGL(k_paths_seed, dim3((n_seeds + 255u) / 256u), dim3(256), 0, s, occ, nx, ny, nz, tiles_x, tiles_y, seeds, n_seeds, cost,
-            flags);
+    hipLaunchKernelGGL(k_paths_seed, dim3((n_seeds + 255u) / 256u), dim3(256), 0, s, occ, nx, ny, nz, tl.x, tl.y, seeds, n_seeds, cost, flags);
 }
-template <int CONN, bool COST> static void paths_sweep_as(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, const float* step3,
-        const float* mult, float* cost, uint8_t* cur, uint8_t* nxt, uint32_t* raised) {
-    const uint32_t tiles_x = (nx + kPtTX - 1u) / kPtTX, tiles_y = (ny + kPtTY - 1u) / kPtTY, tiles_z = (nz + kPtTZ - 1u) / kPtTZ;
-    hipLaunchKernelGGL((k_paths_sweep<CONN, COST>), dim3(tiles_x * tiles_y * tiles_z), dim3(256), 0, s, occ, nx, ny, nz, tiles_x, tiles_y, tiles_z, step3[0],
-            step3[1], step3[2], mult, cost, cur, nxt, raised);
+// f(connectivity and "with a multiplier" as compile-time constants)
+template <class F> static void paths_dispatch(int connectivity, bool cost, F&& f) {
+    dispatch_connectivity(connectivity, [&](auto conn) { cost ? f(conn, std::true_type{}) : f(conn, std::false_type{}); });
 }
-void launch_paths_sweep(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, const float* step3, int connectivity, const float* mult,
-        float* cost, uint8_t* flags, uint32_t sweep, uint32_t* raised) {
-    const uint32_t tiles = paths_tiles(nx, ny, nz);
-    uint8_t* cur = flags + (sweep & 1u) * (size_t)tiles; uint8_t* nxt = flags + ((sweep + 1u) & 1u) * (size_t)tiles;
-    switch (connectivity) {
-        case 6:  mult ? paths_sweep_as<6, true>(s, occ, nx, ny, nz, step3, mult, cost, cur, nxt, raised)
-                      : paths_sweep_as<6, false>(s, occ, nx, ny, nz, step3, mult, cost, cur, nxt, raised); break;
-        case 18: mult ? paths_sweep_as<18, true>(s, occ, nx, ny, nz, step3, mult, cost, cur, nxt, raised)
-                      : paths_sweep_as<18, false>(s, occ, nx, ny, nz, step3, mult, cost, cur, nxt, raised); break;
-        default: mult ? paths_sweep_as<26, true>(s, occ, nx, ny, nz, step3, mult, cost, cur, nxt, raised)
-                      : paths_sweep_as<26, false>(s, occ, nx, ny, nz, step3, mult, cost, cur, nxt, raised); break;
-    }
+void launch_paths_sweep(hipStream_t s, const uint8_t* occ, const Lattice& g, int connectivity, const float* mult, float* cost, uint8_t* flags, uint32_t sweep,
+        uint32_t* raised) {
+    const Tiles tl = tiles(g);
+    uint8_t* cur = flags + (sweep & 1u) * (size_t)tl.n(); uint8_t* nxt = flags + ((sweep + 1u) & 1u) * (size_t)tl.n();
+    paths_dispatch(connectivity, mult != nullptr, [&](auto conn, auto with) {
+        hipLaunchKernelGGL((k_paths_sweep<conn.value, with.value>), dim3(tl.n()), dim3(256), 0, s, occ, (uint32_t)g.nx, (uint32_t)g.ny, (uint32_t)g.nz, tl.x, tl.y,
+                tl.z, g.step[0], g.step[1], g.step[2], mult, cost, cur, nxt, raised);
+    });
 }
-template <int CONN, bool COST> static void paths_finish_as(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, const float* step3,
-        const float* mult, const float* cost, float max_cost, float* cost_out, int32_t* next) {
-    hipLaunchKernelGGL((k_paths_finish<CONN, COST>), dim3((nx * ny * nz + 255u) / 256u), dim3(256), 0, s, occ, nx, ny, nz, step3[0], step3[1], step3[2], mult,
-            cost, max_cost, cost_out, next);
-}
-void launch_paths_finish(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, const float* step3, int connectivity, const float* mult,
-        const float* cost, float max_cost, float* cost_out, int32_t* next) {
-    switch (connectivity) {
-        case 6:  mult ? paths_finish_as<6, true>(s, occ, nx, ny, nz, step3, mult, cost, max_cost, cost_out, next)
-                      : paths_finish_as<6, false>(s, occ, nx, ny, nz, step3, mult, cost, max_cost, cost_out, next); break;
-        case 18: mult ? paths_finish_as<18, true>(s, occ, nx, ny, nz, step3, mult, cost, max_cost, cost_out, next)
-                      : paths_finish_as<18, false>(s, occ, nx, ny, nz, step3, mult, cost, max_cost, cost_out, next); break;
-        default: mult ? paths_finish_as<26, true>(s, occ, nx, ny, nz, step3, mult, cost, max_cost, cost_out, next)
-                      : paths_finish_as<26, false>(s, occ, nx, ny, nz, step3, mult, cost, max_cost, cost_out, next); break;
-    }
+void launch_paths_finish(hipStream_t s, const uint8_t* occ, const Lattice& g, int connectivity, const float* mult, const float* cost, float max_cost,
+        float* cost_out, int32_t* next) {
+    const uint32_t nx = (uint32_t)g.nx, ny = (uint32_t)g.ny, nz = (uint32_t)g.nz;
+    paths_dispatch(connectivity, mult != nullptr, [&](auto conn, auto with) {
+        hipLaunchKernelGGL((k_paths_finish<conn.value, with.value>), dim3((nx * ny * nz + 255u) / 256u), dim3(256), 0, s, occ, nx, ny, nz, g.step[0], g.step[1],
+                g.step[2], mult, cost, max_cost, cost_out, next);
+    });
 }
 void launch_paths_soft(hipStream_t s, uint32_t n, const float* dist, float soft_radius, float soft_weight, float* mult) {
     hipLaunchKernelGGL(k_paths_soft, dim3((n + 255u) / 256u), dim3(256), 0, s, n, dist, soft_radius, soft_weight, mult);

@@ -120,7 +120,8 @@ size_t scan_match_scratch(uint32_t n, uint32_t n_pose) {
     const uint32_t chunks = ceil_div(n, kScanMatchChunk);
     return (size_t)n_pose * kScanMatchRow * ((size_t)chunks + (chunks > kScanMatchFold ? ceil_div(chunks, kScanMatchFold) : 0u));
 }
-void launch_scan_match(hipStream_t s, const DistFieldView& F, const ScanMatchArgs& a, bool normal, float* scratch, float* rows) {
+void launch_scan_match(hipStream_t s, const float* D, const Lattice& g, const ScanMatchArgs& a, bool normal, float* scratch, float* rows) {
+    const DistFieldView F = dist_field_view(D, g);
     uint32_t n_in = ceil_div(a.n, kScanMatchChunk);
     const dim3 grid(n_in, a.n_pose);
     if (normal) hipLaunchKernelGGL((k_scan_match<true>), grid, dim3(256), 0, s, F, a, scratch);

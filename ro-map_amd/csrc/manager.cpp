@@ -744,7 +744,7 @@ int mon_online_query_points(mon_online* h, const float* world_xyz, size_t n, flo
     std::vector<Model*> ms; std::vector<int32_t> ids; int rc;
     if ((rc = scene_points_check(1, world_xyz, n, sigma)) || (rc = online_published(h, "query_points", 0, false, ms, &ids)) ||
         (rc = scene_objects_check("scene_points", ms.data(), ms.size(), false))) return rc;
-    ScenePoints q{}; q.xyz = world_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    const ScenePoints q = scene_point_list(world_xyz, n);
     return scene_points(ms.data(), ms.size(), 1, q, sigma, rgb, owner, owner_sigma, n_inside, ids.data(), 0, nullptr);
 }
 int mon_online_query_lattice(mon_online* h, const float* origin3, const float* step3, int nx, int ny, int nz, float* sigma, float* rgb, int32_t* owner,
@@ -816,7 +816,7 @@ int mon_online_query_gradients(mon_online* h, const float* world_xyz, size_t n, 
             sel[i] = select[i] < 0 ? -1 : (int32_t)(it - ids.begin());
         }
     }
-    ScenePoints q{}; q.xyz = world_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    const ScenePoints q = scene_point_list(world_xyz, n);
     return scene_gradients(ms.data(), ms.size(), 1, q, level_weights, select ? sel.data() : nullptr, sigma, rgb, owner, owner_sigma, n_inside, grad_log, grad_sigma,
                            normal, ids.data(), 0, nullptr);
 }

@@ -268,8 +268,7 @@ int marching_cubes_host(int device, const float* density, int rx, int ry, int rz
                         float* verts, float* normals_raw, uint32_t* indices, uint32_t cap_verts, uint32_t cap_indices, uint32_t* n_verts,
                                 uint32_t* n_verts_real, uint32_t* n_indices) {
     if (!density || !amin || !amax || rx < 2 || ry < 2 || rz < 2) { set_error("marching_cubes: bad argument"); return MON_ERR_ARG; }
-    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available"); return MON_ERR_NO_DEVICE; }
-    HIPCHECK(use_device(device));
+    { const int rc = device_enter(device); if (rc) return rc; }
     MeshState* ms = mesh_state_create(device); const size_t res3 = (size_t)rx * ry * rz;
     int rc = mesh_reserve_lattice(*ms, res3);
     if (!rc) { if (hipMemcpy(ms->d_density, density, res3 * 4, hipMemcpyHostToDevice) != hipSuccess) { set_error("marching_cubes: upload failed");

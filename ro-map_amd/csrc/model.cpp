@@ -41,6 +41,11 @@ hipError_t use_device(int logical) {
     const int n = g_logical_devices.load(); if (logical < 0 || logical >= (n > 0 ? n : phys)) return hipErrorInvalidDevice;
     return hipSetDevice(logical % phys);
 }
+int device_enter(int device) {
+    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available"); return MON_ERR_NO_DEVICE; }
+    HIPCHECK(use_device(device));
+    return MON_OK;
+}
 int physical_device(int logical, int* phys_out) {
     const int phys = physical_count(); const int n = g_logical_devices.load();
     if (phys < 1 || logical < 0 || logical >= (n > 0 ? n : phys) || !phys_out) { set_error("physical_device: no such logical device %d", logical);

@@ -199,6 +199,7 @@ int option_set(const char* name, long value);
 int option_get(const char* name, long* value);
 
 hipError_t use_device(int logical_device);      // hipSetDevice through the logical-device map (model.cpp)
+int device_enter(int logical_device);            // a standalone call's way in: MON_ERR_NO_DEVICE without a device, then use_device
 int set_logical_devices(int n);
 
 // ---- kernel launchers (kernels_*.hip)
@@ -356,6 +357,15 @@ void launch_scene_cast_composite(hipStream_t s, uint32_t n_rays, uint32_t n_list
 // inside, raw4, sigma, r, g, b of the n points of a pass -- item i is point i of `pts` (device, [n][3]) or, with pts == nullptr, lattice point first + i
 // (ix fastest, fmaf(i_a, step_a, origin_a)); world = false: the points are unit-cube points of the object, taken as given.  build_image: build the
 // fragment image first (a call's first pass).  k_scene_points_fold: the K rows of each point ([K][cap][12]) -> the five outputs.
+// A lattice: nx x ny x nz cells, cell (i, j, k) at flat index (k * ny + j) * nx + i and at origin + (i, j, k) * step.  What the lattice queries ask, what a
+// distance-field handle sits on and what the launch wrappers of the kernels over a lattice take (the standalone calls have no origin: 0).
+struct Lattice {
+    int nx = 1, ny = 1, nz = 1; float origin[3] = { 0, 0, 0 }, step[3] = { 0, 0, 0 };
+    Lattice(const float* origin3 = nullptr, const float* step3 = nullptr, int nx_ = 1, int ny_ = 1, int nz_ = 1) : nx(nx_), ny(ny_), nz(nz_) {
+        for (int a = 0; a < 3; ++a) { origin[a] = origin3 ? origin3[a] : 0.f; step[a] = step3 ? step3[a] : 0.f; }
+    }
+    size_t n() const { return (size_t)nx * ny * nz; }
+};
 struct ScenePointsArgs { const float* pts; float origin[3], step[3]; uint32_t nx, ny, first, n; float* rows; };
 void launch_scene_points(hipStream_t s, const LevelFast& lt, const NetDims& nd, const uint16_t* params, const ObjectConst& oc, uint16_t* frag_image,
         int build_image, bool world, const ScenePointsArgs& p);
@@ -375,7 +385,7 @@ void launch_scene_gradients_fold(hipStream_t s, uint32_t n, uint32_t n_objs, uin
 // occupied cell in v[0 .. n) and that cell's flat index in site[0 .. n) (+inf and -1 without one); v and site hold 2 n elements, n = nx ny nz <= 2^22.
 // k_distance_finish: dist = the root, max_dist applied; nearest and nearest_owner (= owner[nearest]; owner: device, [n]) may be nullptr.
 void launch_distance_mask(hipStream_t s, uint32_t n, const float* sigma, float sigma_min, uint8_t* occ);
-void launch_distance_passes(hipStream_t s, const uint8_t* occ, bool invert, uint32_t nx, uint32_t ny, uint32_t nz, const float* step3, float* v, int32_t* site);
+void launch_distance_passes(hipStream_t s, const uint8_t* occ, bool invert, const Lattice& g, float* v, int32_t* site);
 void launch_distance_finish(hipStream_t s, uint32_t n, const float* d2, const int32_t* site, float max_dist, const int32_t* owner, float* dist,
         int32_t* nearest, int32_t* nearest_owner);
 // Connected components (mon_label_components, mon_scene_components_lattice; kernels_components.hip).  launch_components: the mask occ[n] -> label[n] and
@@ -384,33 +394,34 @@ void launch_distance_finish(hipStream_t s, uint32_t n, const float* d2, const in
 // words.  connectivity is 6, 18 or 26 (checked by the caller).  launch_components_clear_mask: occ = dist > clearance.  launch_components_home: words
 // [0, n_words) of src -> dst, of the table's words (8 per record from word table_word on, table_cap records) only the records that were written.
 size_t components_scan_words(uint32_t n);
-void launch_components(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, int connectivity, int32_t* label, int32_t* comp,
-        uint32_t* scan, mon_lattice_component* table, uint32_t cap, uint32_t* meta);
+void launch_components(hipStream_t s, const uint8_t* occ, const Lattice& g, int connectivity, int32_t* label, int32_t* comp, uint32_t* scan,
+        mon_lattice_component* table, uint32_t cap, uint32_t* meta);
 void launch_components_clear_mask(hipStream_t s, uint32_t n, const float* dist, float clearance, uint8_t* occ);
 void launch_components_home(hipStream_t s, const uint32_t* src, uint32_t* dst, uint32_t n_words, uint32_t table_word, uint32_t table_cap, const uint32_t* meta);
 // Shortest-path cost fields (mon_shortest_paths, mon_scene_paths_lattice; kernels_paths.hip).  occ: the passable cells; mult: the per-cell multiplier or
-// nullptr (none); flags: 2 * paths_tiles(nx, ny, nz) bytes.  launch_paths_init: cost = +inf, 0 at the passable seeds (device array, every entry below n), the
+// nullptr (none); flags: 2 * paths_tiles(g) bytes.  launch_paths_init: cost = +inf, 0 at the passable seeds (device array, every entry below n), the
 // flags of sweep 0.  launch_paths_sweep: sweep number `sweep` (0, 1, ...: they alternate between the two rows of flags); *raised becomes 1 iff the sweep left
 // work for the next one (the caller clears it).  launch_paths_finish: next (may be nullptr) on the untruncated cost, then cost_out (another array than
 // cost) = cost cut at max_cost.  launch_paths_soft: the scene call's multiplier from a distance row.  connectivity is 6, 18 or 26 (checked by the caller).
-uint32_t paths_tiles(uint32_t nx, uint32_t ny, uint32_t nz);
-void launch_paths_init(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, const int32_t* seeds, uint32_t n_seeds, float* cost,
-        uint8_t* flags);
-void launch_paths_sweep(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, const float* step3, int connectivity, const float* mult,
-        float* cost, uint8_t* flags, uint32_t sweep, uint32_t* raised);
-void launch_paths_finish(hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, const float* step3, int connectivity, const float* mult,
-        const float* cost, float max_cost, float* cost_out, int32_t* next);
+uint32_t paths_tiles(const Lattice& g);
+void launch_paths_init(hipStream_t s, const uint8_t* occ, const Lattice& g, const int32_t* seeds, uint32_t n_seeds, float* cost, uint8_t* flags);
+void launch_paths_sweep(hipStream_t s, const uint8_t* occ, const Lattice& g, int connectivity, const float* mult, float* cost, uint8_t* flags, uint32_t sweep,
+        uint32_t* raised);
+void launch_paths_finish(hipStream_t s, const uint8_t* occ, const Lattice& g, int connectivity, const float* mult, const float* cost, float max_cost,
+        float* cost_out, int32_t* next);
 void launch_paths_soft(hipStream_t s, uint32_t n, const float* dist, float soft_radius, float soft_weight, float* mult);
-// Device-resident distance fields (mon_dist_field_*; kernels_clearance.hip).  DistFieldView: the field as the kernels take it (D: device, [nz][ny][nx]).
+// Device-resident distance fields (mon_dist_field_*; kernels_clearance.hip).  DistFieldView: the cells D (device, [nz][ny][nx]) on their lattice g as the
+// kernels take them; the wrappers form it.
 // launch_field_sample: dist[n] and grad[n][3] (may be nullptr) at xyz[n][3].  launch_traj_score: the header's outputs of n_traj trajectories (device
 // arrays; all but min_clear may be nullptr); n_samp = (n_way - 1) n_sub + 1; the launch fills in pad.  launch_field_max: out[0] = the largest of v[0 .. n),
 // partial: kFieldMaxBlocks floats.
 struct DistFieldView { const float* D; int nx, ny, nz; float o[3], s[3]; };
+inline DistFieldView dist_field_view(const float* D, const Lattice& g) { return { D, g.nx, g.ny, g.nz, { g.origin[0], g.origin[1], g.origin[2] }, { g.step[0], g.step[1], g.step[2] } }; }
 struct TrajScoreArgs { uint32_t n_traj, n_way, n_sub, n_samp, pad; float outside, margin, safe; float* min_clear; int32_t* first_hit; float* cost;
                        float* way_clear; float* way_grad; };
 constexpr uint32_t kFieldMaxBlocks = 256;
-void launch_field_sample(hipStream_t s, const DistFieldView& F, const float* xyz, uint32_t n, float outside, float* dist, float* grad);
-void launch_traj_score(hipStream_t s, const DistFieldView& F, const float* spheres, uint32_t n_spheres, const float* ways, bool pose, TrajScoreArgs a);
+void launch_field_sample(hipStream_t s, const float* D, const Lattice& g, const float* xyz, uint32_t n, float outside, float* dist, float* grad);
+void launch_traj_score(hipStream_t s, const float* D, const Lattice& g, const float* spheres, uint32_t n_spheres, const float* ways, bool pose, TrajScoreArgs a);
 void launch_field_max(hipStream_t s, const float* v, uint32_t n, float* partial, float* out);
 // Scan matching against a distance field (mon_dist_field_match / _register; kernels_scan_match.hip).  launch_scan_match: rows[n_pose][32] = 21 A terms, 6 b
 // terms, cost, n_inside, n_inlier (counts as exact floats), 0, 0 per pose -- or, normal false, rows[n_pose][4] = cost, n_inside, n_inlier, 0.  All arrays
@@ -418,7 +429,7 @@ void launch_field_max(hipStream_t s, const float* v, uint32_t n, float* partial,
 struct ScanMatchArgs { const float* points; const float* poses; const float* pivots; uint32_t n, n_pose; float huber, outside; };
 constexpr uint32_t kScanMatchChunk = 1024, kScanMatchFold = 64, kScanMatchRow = 32, kScanMatchLite = 4;
 size_t scan_match_scratch(uint32_t n, uint32_t n_pose);
-void launch_scan_match(hipStream_t s, const DistFieldView& F, const ScanMatchArgs& a, bool normal, float* scratch, float* rows);
+void launch_scan_match(hipStream_t s, const float* D, const Lattice& g, const ScanMatchArgs& a, bool normal, float* scratch, float* rows);
 // Pose refinement (mon_object_pose_loss / mon_object_refine_pose, kernels_pose.hip).  k_pose_rays: one record of 4 float4 per drawn ray from the pose in
 // device memory (pose[16], world -> object); k_pose_grad<shape>: loss and position gradient, one partial row of 8 floats {g, x x g, loss, 0} per workgroup
 // (pose_grad_grid of them); k_pose_update: the rows summed in a fixed order, x inv_n -> out[8 * it] = {loss, grad6, 0}, optionally the Adam step on pose.
@@ -773,15 +784,12 @@ int scene_cast(Model* const* ms, size_t n, int side, const mon_scene_ray* rays, 
 int scene_camera_rays(float fx, float fy, float cx, float cy, const float* Twc16s, size_t n_poses, const mon_scene_query* q, size_t n_q,
                       mon_scene_ray* rays_out, float* dn_out);
 // Point queries (mon_scene_query_points / mon_scene_query_lattice): the objects' check is the cast's (no camera); ids as scene_render's, applied to owner.
-// ScenePoints: xyz = the world points [n][3], or nullptr: the lattice origin / step / nx x ny x nz (n = its points).  rows (mon_debug_scene_point_rows, may be
+// ScenePoints: xyz = the world points [n][3], or nullptr: the lattice g (n = its points).  rows (mon_debug_scene_point_rows, may be
 // nullptr) = object rows_k's rows of every point, host array [n][12].  scene_lattice_points (mon_lattice_points): the lattice's floats on the host.
 // object_points (mon_object_query_points): the same kernel on unit-cube points of one object, its raw outputs [n][4].
-struct ScenePoints { const float* xyz; size_t n; float origin[3], step[3]; int nx, ny, nz; };
-inline ScenePoints scene_lattice(const float* origin3, const float* step3, int nx, int ny, int nz) {      // (after scene_lattice_check)
-    ScenePoints q{}; q.n = (size_t)nx * ny * nz; q.nx = nx; q.ny = ny; q.nz = nz;
-    for (int a = 0; a < 3; ++a) { q.origin[a] = origin3[a]; q.step[a] = step3[a]; }
-    return q;
-}
+struct ScenePoints { const float* xyz; size_t n; Lattice g; };
+inline ScenePoints scene_point_list(const float* xyz, size_t n) { return { xyz, n, Lattice() }; }
+inline ScenePoints scene_lattice(const float* origin3, const float* step3, int nx, int ny, int nz) { const Lattice g(origin3, step3, nx, ny, nz); return { nullptr, g.n(), g }; }
 int scene_points_check(int side, const float* xyz, size_t n, const float* sigma);
 int scene_lattice_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, const float* sigma);
 int scene_points(Model* const* ms, size_t n, int side, const ScenePoints& q, float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside,
@@ -837,8 +845,7 @@ int dist_field_create_check(const float* dist, int nx, int ny, int nz, const flo
 int dist_field_create(int device, const float* dist, int nx, int ny, int nz, const float* origin3, const float* step3, DistField** out);
 int scene_dist_field_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float max_dist, const void* field_out);
 int scene_dist_field(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, float max_dist, DistField** out);
-int dist_field_adopt(int device, const ScenePoints& q, DistField** out);          // scene_field.cpp's way in: the handle with its buffer, still empty
-float* dist_field_cells(DistField& f); void dist_field_set_max(DistField& f, float max_value);
+int dist_field_adopt(int device, const Lattice& g, DistField** out);          // scene_field.cpp's way in: the handle with its buffer, still empty
 void dist_field_free(DistField* f);
 int dist_field_info(DistField* f, mon_dist_field_desc* info);
 int dist_field_read(DistField* f, float* dist_out);

@@ -125,7 +125,7 @@ template <class W> W& side_ws(int device, int side) {
     static std::mutex mu; static std::map<std::pair<int, int>, W*> all;
     std::lock_guard<std::mutex> l(mu); W*& w = all[{ device, side }]; if (!w) w = new W(); return *w;
 }
-// The workspace of the render, the list routes and the field queries.  Per device and side, grow-only, never freed (like the tile workspaces): the lists of
+// The workspace of the render, the list routes and the field queries (the lattice routes' shared stages, scene_field.cpp, own docc, dv and dsite).  Per device and side, grow-only, never freed (like the tile workspaces): the lists of
 // one chunk for every object, the call's outputs, their pinned staging, the events that order the objects' streams in front of side 0's call.  A call holds
 // `mu` until its stream has been synchronised, so the routes of one side take turns.
 struct SceneWs {
@@ -136,7 +136,7 @@ struct SceneWs {
     DevBuf<mon_scene_ray> rays; DevBuf<float> entry;                              // scene_cast: the rays, a pass's box entries [lists][cap]
     DevBuf<float> pts, rows;                                                      // field queries: the points [n][3], a pass's rows [objects][cap][12 or 16]
     DevBuf<uint16_t> gfrag; DevBuf<float> lw; DevBuf<int32_t> sel;                // gradients (rows of 16): full fragment images, weights [Lmax], select [n]
-    DevBuf<uint8_t> docc; DevBuf<float> dv; DevBuf<int32_t> dsite;                // scene_distance: the mask [n], the passes' squared distances and sites [2][n]
+    DevBuf<uint8_t> docc; DevBuf<float> dv; DevBuf<int32_t> dsite;                // lattice routes: the mask [n], the passes' squared distances and sites [2][n]
     DevBuf<uint32_t> cscan;                                                       // scene_components: the numbering's block sums (its mask is docc)
     DevBuf<float> pcost, pmul; DevBuf<int32_t> pseeds; DevBuf<uint8_t> pflags;    // scene_paths: the working cost [n], the multiplier [n], the seeds, two flag
     DevBuf<uint32_t> praised; PinnedBuf<uint32_t> h_raised;                       // bytes per tile, a batch's "left work" words and their pinned copy (mask: docc)
@@ -156,6 +156,15 @@ struct SceneCall {
     int finish();
     int home(size_t floats);
 };
+// dist_field.cpp: a distance field on the device (scene_field.cpp fills the cells and max_value of the one dist_field_adopt made)
+struct DistField {
+    std::mutex mu;
+    int device = 0; Lattice g; float max_value = 0.f;
+    float* cells = nullptr; hipStream_t s = nullptr;
+    DevBuf<float> in, out; PinnedBuf<float> h_out;                                   // a call's inputs, its outputs and their pinned staging
+};
+// scene_field.cpp: a lattice of at least one cell per axis and at most max_cells in all (the lattice routes; dist_field.cpp's handles)
+int lattice_dims_check(const char* what, int nx, int ny, int nz, size_t max_cells);
 // an instance row home: the call's list indices, or the caller's ids for them
 void scene_instances_home(int32_t* out, const float* row, size_t n, const int32_t* ids);
 

@@ -1,8 +1,9 @@
 // scene_field.cpp -- the field queries: the object map asked at places instead of along rays.  Points and lattices (density, colour, owner), their
 // gradients and normals, normals at ray hits, distance fields (brought home, or kept on the device as a field handle: dist_field.cpp), connected components
 // and shortest-path cost fields over a lattice.  One host chain
-// (DESIGN.md 3.4c-4): a SceneCall (scene.cpp) without lists or grids, the passes of field_passes_enqueue, each route's own kernels behind them, one copy
-// home and one synchronisation (the cost fields: one more per batch of sweeps).
+// (DESIGN.md 3.4c-4): a SceneCall (scene.cpp) without lists or grids, an output area described once (Area), the passes of field_passes_enqueue, each
+// route's own kernels behind them, one copy home and one synchronisation (the cost fields: one more per batch of sweeps).  The routes over a lattice share
+// their stages behind the passes too (the lattice routes' chain) and the checks they word alike.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -22,18 +23,31 @@ int scene_points_check(int side, const float* xyz, size_t n, const float* sigma)
     for (size_t i = 0; i < 3 * n; ++i) if (!std::isfinite(xyz[i])) { set_error("scene_points: point %zu is not finite", i / 3); return MON_ERR_ARG; }
     return MON_OK;
 }
-// the lattice's shape alone (mon_lattice_points, which has no side and no outputs) ...
-static int lattice_dims_check(const char* what, int nx, int ny, int nz) {
+// the lattice's shape alone (mon_lattice_points, which has no side and no outputs; the host-mask calls; max_cells: dist_field.cpp's handles hold fewer) ...
+int lattice_dims_check(const char* what, int nx, int ny, int nz, size_t max_cells) {
     if (nx < 1 || ny < 1 || nz < 1) { set_error("%s: lattice %d x %d x %d (each at least 1)", what, nx, ny, nz); return MON_ERR_ARG; }
     // (each factor bounded before it is multiplied: three ints of up to 2^31 - 1 wrap a 64-bit product)
-    const uint64_t mx = kSceneProbeMaxQueries;
-    if ((uint64_t)nx > mx || (uint64_t)ny > mx / (uint64_t)nx || (uint64_t)nz > mx / ((uint64_t)nx * (uint64_t)ny)) { set_error("%s: lattice %d x %d x %d has more than %u points", what, nx, ny, nz,
-        kSceneProbeMaxQueries); return MON_ERR_ARG; }
+    const uint64_t mx = max_cells;
+    if ((uint64_t)nx > mx || (uint64_t)ny > mx / (uint64_t)nx || (uint64_t)nz > mx / ((uint64_t)nx * (uint64_t)ny)) {
+        set_error("%s: lattice %d x %d x %d has more than %zu points", what, nx, ny, nz, max_cells); return MON_ERR_ARG; }
+    return MON_OK;
+}
+// ... and what several routes ask of one argument in the same words
+static int step_finite_check(const char* what, const float* step3) {
+    for (int a = 0; a < 3; ++a) if (!std::isfinite(step3[a])) { set_error("%s: step is not finite", what); return MON_ERR_ARG; }
+    return MON_OK;
+}
+static int nonneg_check(const char* what, const char* name, float v) {
+    if (!std::isfinite(v) || v < 0.f) { set_error("%s: %s %g (finite, >= 0)", what, name, (double)v); return MON_ERR_ARG; }
+    return MON_OK;
+}
+static int connectivity_check(const char* what, int connectivity) {
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26) { set_error("%s: connectivity %d (6, 18 or 26)", what, connectivity); return MON_ERR_ARG; }
     return MON_OK;
 }
 static int lattice_shape_check(const char* what, const float* origin3, const float* step3, int nx, int ny, int nz) {
     REQUIRE_ARG(what, origin3, "origin"); REQUIRE_ARG(what, step3, "step");
-    { const int rc = lattice_dims_check(what, nx, ny, nz); if (rc) return rc; }
+    { const int rc = lattice_dims_check(what, nx, ny, nz, kSceneProbeMaxQueries); if (rc) return rc; }
     const int dims[3] = { nx, ny, nz };
     for (int a = 0; a < 3; ++a) {
         if (!std::isfinite(origin3[a]) || !std::isfinite(step3[a])) { set_error("%s: origin or step is not finite", what); return MON_ERR_ARG; }
@@ -41,6 +55,12 @@ static int lattice_shape_check(const char* what, const float* origin3, const flo
         if (!std::isfinite(std::fmaf((float)(dims[a] - 1), step3[a], origin3[a]))) { set_error("%s: the lattice leaves the finite floats on axis %d", what, a);
             return MON_ERR_ARG; }
     }
+    return MON_OK;
+}
+// what every lattice route over the object map asks first: the lattice, the side, sigma_min
+static int lattice_route_check(const char* what, int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min) {
+    int rc;
+    if ((rc = lattice_shape_check(what, origin3, step3, nx, ny, nz)) || (rc = side_check(what, side)) || (rc = nonneg_check(what, "sigma_min", sigma_min))) return rc;
     return MON_OK;
 }
 // ... and the query on it
@@ -69,15 +89,37 @@ int scene_lattice_points(const float* origin3, const float* step3, int nx, int n
 #define MON_POINTS_PASS kRenderChunkRays
 #endif
 constexpr uint32_t kScenePointsPass = MON_POINTS_PASS;
-// A route's output area, described once: rows taken in order, each `width` floats per point.  The offsets serve the device pointers the kernels get (into
-// ws.out) and the unpacking (from the pinned staging) alike; a route sends home a prefix of its area.
+// A route's output area in ws.out, described once: pieces taken in order, whose offsets serve the device pointers the kernels get and the unpacking from the
+// pinned staging alike.  row: `width` floats per point.  out: a row the caller may ask for -- host: where it goes (nullptr: not asked for), instance: by way
+// of scene_instances_home.  keep: words the route itself reads at home.  `home`: the front of the area up to the last piece asked for or kept, all a call
+// brings home; unpack: the rows asked for, out of the staging.
 struct Area {
-    size_t n_q, end = 0;
+    struct Out { size_t at, floats; void* host; bool instance; };
+    size_t n_q, end = 0, home = 0; Out outs[8]; int n_outs = 0;
     size_t take(size_t floats) { const size_t at = end; end += floats; return at; }
     size_t row(size_t width = 1) { return take(width * n_q); }
+    size_t keep(size_t floats) { const size_t at = take(floats); home = end; return at; }
+    size_t out(void* host, size_t width = 1, bool instance = false) {
+        const size_t at = row(width);
+        if (host) { home = end; outs[n_outs++] = Out{ at, width * n_q, host, instance }; }
+        return at;
+    }
+    void unpack(const float* h, const int32_t* ids) const {
+        for (int k = 0; k < n_outs; ++k) {
+            const Out& o = outs[k];
+            if (o.instance) scene_instances_home(static_cast<int32_t*>(o.host), h + o.at, n_q, ids); else std::memcpy(o.host, h + o.at, 4 * o.floats);
+        }
+    }
 };
-// where a route keeps the fold's output rows (grad_log, grad_sigma, normal: the gradient fold's)
-struct FoldRows { size_t sigma, rgb, owner, owner_sigma, n_inside, grad_log, grad_sigma, normal; };
+// where a route keeps the fold's output rows (grad_log, grad_sigma, normal: the gradient fold's).  A route places the rows it sends home where its area
+// wants them; fold_rows_rest places the others behind, in this order
+constexpr size_t kNoRow = ~(size_t)0;
+struct FoldRows { size_t sigma = kNoRow, rgb = kNoRow, owner = kNoRow, owner_sigma = kNoRow, n_inside = kNoRow, grad_log = kNoRow, grad_sigma = kNoRow, normal = kNoRow; };
+static void fold_rows_rest(Area& A, FoldRows& f, bool grads) {
+    size_t* const at[8] = { &f.sigma, &f.rgb, &f.owner, &f.owner_sigma, &f.n_inside, &f.grad_log, &f.grad_sigma, &f.normal };
+    const size_t width[8] = { 1, 3, 1, 1, 1, 3, 3, 3 };
+    for (int k = 0; k < (grads ? 8 : 5); ++k) if (*at[k] == kNoRow) *at[k] = A.row(width[k]);
+}
 // what the gradient routes take beside the points: the caller's level weights (nullptr: ones) and select (may be nullptr), in ws.lw and ws.sel for the
 // kernels; every object's FULL fragment image at frag_off[j] of ws.gfrag (the backward reads the transposed matrices; the objects' own render images hold
 // the forward set only and are left alone)
@@ -89,8 +131,8 @@ static int field_passes_prepare(const SceneCall& c, size_t n, const ScenePoints&
     if (q.xyz) HIPCHECK(hipMemcpyAsync(ws.pts.p, q.xyz, 12 * q.n, hipMemcpyHostToDevice, c.s));
     return MON_OK;
 }
-// The passes of every field query: q.xyz: the list ([q.n][3]; `world` false: unit-cube points of the one object), or nullptr: the lattice q.origin, q.step,
-// q.nx x q.ny x q.nz (q.n its points).  g: the gradient kernels and rows of 16, nullptr: the forward kernels and rows of 12.  f: the fold's rows in ws.out.
+// The passes of every field query: q.xyz: the list ([q.n][3]; `world` false: unit-cube points of the one object), or nullptr: the lattice q.g
+// (q.n its points).  g: the gradient kernels and rows of 16, nullptr: the forward kernels and rows of 12.  f: the fold's rows in ws.out.
 // dump (may be nullptr): where in ws.out object rows_k's rows of every point go, [q.n][width].
 static void field_passes_enqueue(const SceneCall& c, Model* const* ms, size_t n, const ScenePoints& q, bool world, uint32_t cap, const FoldRows& f,
                                  const FieldGrads* g, size_t rows_k, float* dump) {
@@ -100,8 +142,8 @@ static void field_passes_enqueue(const SceneCall& c, Model* const* ms, size_t n,
         const uint32_t nc = std::min(cap, nq - p0);
         for (size_t j = 0; j < n; ++j) {
             Model& m = *ms[j];
-            ScenePointsArgs a{}; a.pts = q.xyz ? ws.pts.p + 3 * (size_t)p0 : nullptr; a.nx = (uint32_t)q.nx; a.ny = (uint32_t)q.ny; a.first = p0; a.n = nc;
-            for (int k = 0; k < 3; ++k) { a.origin[k] = q.origin[k]; a.step[k] = q.step[k]; }
+            ScenePointsArgs a{}; a.pts = q.xyz ? ws.pts.p + 3 * (size_t)p0 : nullptr; a.nx = (uint32_t)q.g.nx; a.ny = (uint32_t)q.g.ny; a.first = p0; a.n = nc;
+            for (int k = 0; k < 3; ++k) { a.origin[k] = q.g.origin[k]; a.step[k] = q.g.step[k]; }
             a.rows = ws.rows.p + j * (size_t)cap * width;
             if (g) launch_scene_point_grads(s, m.lf, m.nd, c.sd.prm[j], m.oc, ws.gfrag.p + g->frag_off[j], p0 == 0u, world, a, ws.lw.p);
             else launch_scene_points(s, m.lf, m.nd, c.sd.prm[j], m.oc, c.src[j].frag, p0 == 0u, world, a);
@@ -128,8 +170,9 @@ static int scene_field_run(const char* what, Model* const* ms, size_t n, int sid
     const size_t n_q = q.n; const uint32_t cap = std::min((uint32_t)n_q, kScenePointsPass), width = g ? 16u : 12u;
     // the output area: [the dumped rows |] the fold's rows (the dumped rows first: every piece copied stays 16-byte aligned)
     Area A{ n_q }; const size_t r_dump = A.take(rows ? width * n_q : 0);
-    FoldRows f{}; f.sigma = A.row(); f.rgb = A.row(3); f.owner = A.row(); f.owner_sigma = A.row(); f.n_inside = A.row();
-    if (g) { f.grad_log = A.row(3); f.grad_sigma = A.row(3); f.normal = A.row(3); }
+    FoldRows f; f.sigma = A.out(out.sigma); f.rgb = A.out(out.rgb, 3); f.owner = A.out(out.owner, 1, true); f.owner_sigma = A.out(out.owner_sigma);
+    f.n_inside = A.out(out.n_inside);
+    if (g) { f.grad_log = A.out(out.grad_log, 3); f.grad_sigma = A.out(out.grad_sigma, 3); f.normal = A.out(out.normal, 3); }
     { int rc; if ((rc = field_passes_prepare(c, n, q, cap, width)) || (rc = ws.out.grow(A.end)) || (rc = ws.h_out.grow(A.end))) return rc; }
     std::vector<float> ones;
     if (g) {
@@ -145,14 +188,7 @@ static int scene_field_run(const char* what, Model* const* ms, size_t n, int sid
     { const int rc = c.home(A.end); if (rc) return rc; }
     const float* h = ws.h_out.p;
     if (rows) std::memcpy(rows, h + r_dump, 4 * width * n_q);
-    if (out.sigma) std::memcpy(out.sigma, h + f.sigma, 4 * n_q);
-    if (out.rgb) std::memcpy(out.rgb, h + f.rgb, 12 * n_q);
-    scene_instances_home(out.owner, h + f.owner, n_q, ids);
-    if (out.owner_sigma) std::memcpy(out.owner_sigma, h + f.owner_sigma, 4 * n_q);
-    if (out.n_inside) std::memcpy(out.n_inside, h + f.n_inside, 4 * n_q);
-    if (out.grad_log) std::memcpy(out.grad_log, h + f.grad_log, 12 * n_q);
-    if (out.grad_sigma) std::memcpy(out.grad_sigma, h + f.grad_sigma, 12 * n_q);
-    if (out.normal) std::memcpy(out.normal, h + f.normal, 12 * n_q);
+    A.unpack(h, ids);
     return MON_OK;
 }
 int scene_points(Model* const* ms, size_t n, int side, const ScenePoints& q, float* sigma, float* rgb, int32_t* owner, float* owner_sigma, uint32_t* n_inside,
@@ -171,7 +207,7 @@ int object_points_check(int side, const float* unit_xyz, size_t n, const float* 
 }
 int object_points(Model& m, int side, const float* unit_xyz, size_t n, float* raw4) {
     Model* ms[1] = { &m };
-    ScenePoints q{}; q.xyz = unit_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    const ScenePoints q = scene_point_list(unit_xyz, n);
     std::vector<float> rows(12 * n);
     const int rc = scene_field_run("object_points", ms, 1, side, q, false, nullptr, FieldOut{}, nullptr, 0, rows.data());
     if (rc) return rc;
@@ -221,7 +257,7 @@ int object_gradients_check(int side, const float* unit_xyz, size_t n, const floa
 int object_gradients(Model& m, int side, const float* unit_xyz, size_t n, const float* level_w, float* raw4, float* grad_unit) {
     if (level_w) { const int rc = level_weights_check("object_gradients", level_w, (int)m.nd.L); if (rc) return rc; }
     Model* ms[1] = { &m };
-    ScenePoints q{}; q.xyz = unit_xyz; q.n = n; q.nx = q.ny = q.nz = 1;
+    const ScenePoints q = scene_point_list(unit_xyz, n);
     std::vector<float> rows(16 * n); FieldGrads g{ level_w, nullptr, {} };
     const int rc = scene_field_run("object_gradients", ms, 1, side, q, false, &g, FieldOut{}, nullptr, 0, rows.data());
     if (rc) return rc;
@@ -254,7 +290,7 @@ int scene_cast_normals(Model* const* ms, size_t n, int side, const mon_scene_ray
     const size_t nh = at.size();
     std::vector<float> sg(nh), gl(3 * nh), nr(3 * nh);
     if (nh) {
-        ScenePoints q{}; q.xyz = x.data(); q.n = nh; q.nx = q.ny = q.nz = 1;
+        const ScenePoints q = scene_point_list(x.data(), nh);
         const int rc = scene_gradients(ms, n, side, q, level_w, sel.data(), sg.data(), nullptr, nullptr, nullptr, nullptr, gl.data(), nullptr, nr.data(), nullptr,
                                        0, nullptr);
         if (rc) return rc;
@@ -274,10 +310,8 @@ int scene_cast_normals(Model* const* ms, size_t n, int side, const mon_scene_ray
     return MON_OK;
 }
 
-// ---- distance fields (mon_distance_transform, mon_scene_distance_lattice): clearance over a lattice.  scene_distance runs the chain over
-// the lattice, whose sigma and owner rows stay on the device; then the mask (k_distance_mask), the three passes of k_distance_pass and k_distance_finish,
-// once more on the complement when free_dist is asked for, one copy home and one synchronisation.  The side's workspace keeps the mask (1 B per cell) and
-// the passes' two halves of squared distance and site (16 B per cell), shared by the two transforms, which run one after the other.
+// ---- distance fields (mon_distance_transform, mon_scene_distance_lattice): clearance over a lattice.  scene_distance: the lattice chain
+// below with the transform behind the mask, once more on the complement when free_dist is asked for (the two run one after the other in the same halves).
 static int distance_outputs_check(const char* what, float max_dist, const float* dist) {
     REQUIRE_ARG(what, dist, "dist");
     if (!(max_dist > 0.f)) { set_error("%s: max_dist %g (above 0; +inf for no limit)", what, (double)max_dist); return MON_ERR_ARG; }
@@ -285,25 +319,21 @@ static int distance_outputs_check(const char* what, float max_dist, const float*
 }
 int distance_transform_check(const uint8_t* occupied, int nx, int ny, int nz, const float* step3, float max_dist, const float* dist) {
     REQUIRE_ARG("distance_transform", occupied, "occupied"); REQUIRE_ARG("distance_transform", step3, "step");
-    { const int rc = lattice_dims_check("distance_transform", nx, ny, nz); if (rc) return rc; }
-    for (int a = 0; a < 3; ++a) if (!std::isfinite(step3[a])) { set_error("distance_transform: step is not finite"); return MON_ERR_ARG; }
+    { int rc; if ((rc = lattice_dims_check("distance_transform", nx, ny, nz, kSceneProbeMaxQueries)) || (rc = step_finite_check("distance_transform", step3))) return rc; }
     return distance_outputs_check("distance_transform", max_dist, dist);
 }
 int scene_distance_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float max_dist, const float* dist) {
-    { const int rc = lattice_shape_check("scene_distance", origin3, step3, nx, ny, nz); if (rc) return rc; }
-    { const int rc = side_check("scene_distance", side); if (rc) return rc; }
-    if (!std::isfinite(sigma_min) || sigma_min < 0.f) { set_error("scene_distance: sigma_min %g (finite, >= 0)", (double)sigma_min); return MON_ERR_ARG; }
+    { const int rc = lattice_route_check("scene_distance", side, origin3, step3, nx, ny, nz, sigma_min); if (rc) return rc; }
     return distance_outputs_check("scene_distance", max_dist, dist);
 }
 // mon_distance_transform: the transform alone on a host mask, in buffers of its own on the device's default stream
 int distance_transform(int device, const uint8_t* occupied, int nx, int ny, int nz, const float* step3, float max_dist, float* dist, int32_t* nearest) {
-    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available"); return MON_ERR_NO_DEVICE; }
-    HIPCHECK(use_device(device));
+    { const int rc = device_enter(device); if (rc) return rc; }
     const size_t n = (size_t)nx * ny * nz;
     DevBuf<uint8_t> occ; DevBuf<float> v; DevBuf<int32_t> site;                     // v, site: the passes' two halves, then the output row
     { int rc; if ((rc = occ.grow(n)) || (rc = v.grow(3 * n)) || (rc = site.grow(3 * n))) return rc; }
     HIPCHECK(hipMemcpy(occ.p, occupied, n, hipMemcpyHostToDevice));
-    launch_distance_passes(nullptr, occ.p, false, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, step3, v.p, site.p);
+    launch_distance_passes(nullptr, occ.p, false, Lattice(nullptr, step3, nx, ny, nz), v.p, site.p);
     launch_distance_finish(nullptr, (uint32_t)n, v.p, site.p, max_dist, nullptr, v.p + 2 * n, nearest ? site.p + 2 * n : nullptr, nullptr);
     HIPCHECK(hipGetLastError());
     std::vector<float> h_dist(n); std::vector<int32_t> h_near(nearest ? n : 0);     // (the caller's arrays are written only once everything has succeeded)
@@ -313,51 +343,57 @@ int distance_transform(int device, const uint8_t* occupied, int nx, int ny, int 
     if (nearest) std::memcpy(nearest, h_near.data(), 4 * n);
     return MON_OK;
 }
-// What scene_distance and scene_dist_field share: the workspace, then the chain over the lattice, the mask, the three passes and the finish.  The rows of
-// the output area: sigma | dist | nearest | nearest_owner | free_dist (what may go home, from the front: up to the last row asked for), then the fold's other
-// rows.  home: the floats of the pinned staging the call will ask for.
+// ---- the lattice routes' chain: scene_distance, scene_dist_field, scene_components and scene_paths each declare their area -- the rows
+// they may send home at the front (Area::out, in the order a caller may ask for them), the fold's other rows behind (fold_rows_rest) -- run the stages below,
+// put their own kernels behind them, and bring A.home floats home (SceneCall::home, then Area::unpack).
+// Stage 1: the workspace, the passes over the lattice and the mask !(sigma <= sigma_min) in ws.docc.
+static int lattice_occupancy(const SceneCall& c, Model* const* ms, size_t n, const ScenePoints& q, const Area& A, const FoldRows& f, float sigma_min) {
+    SceneWs& ws = *c.ws; const uint32_t nq = (uint32_t)q.n, cap = std::min(nq, kScenePointsPass);
+    { int rc; if ((rc = field_passes_prepare(c, n, q, cap, 12u)) || (rc = ws.out.grow(A.end)) || (rc = ws.h_out.grow(A.home)) || (rc = ws.docc.grow(q.n))) return rc; }
+    field_passes_enqueue(c, ms, n, q, true, cap, f, nullptr, 0, nullptr);
+    launch_distance_mask(c.s, nq, ws.out.p + f.sigma, sigma_min, ws.docc.p);
+    return MON_OK;
+}
+// The transform of the mask (the passes' two halves of squared distance and site, 16 B per cell, are the side's): dist into row r_dist, cut at max_dist
+static int lattice_distance(const SceneCall& c, const ScenePoints& q, bool invert, float max_dist, const int32_t* owner, size_t r_dist, int32_t* nearest,
+                            int32_t* nearest_owner) {
+    SceneWs& ws = *c.ws;
+    { int rc; if ((rc = ws.dv.grow(2 * q.n)) || (rc = ws.dsite.grow(2 * q.n))) return rc; }
+    launch_distance_passes(c.s, ws.docc.p, invert, q.g, ws.dv.p, ws.dsite.p);
+    launch_distance_finish(c.s, (uint32_t)q.n, ws.dv.p, ws.dsite.p, max_dist, owner, ws.out.p + r_dist, nearest, nearest_owner);
+    return MON_OK;
+}
+// Stage 2: the untruncated transform, then the mask dist > clearance written over the first one, which the passes have consumed
+static int lattice_clearance(const SceneCall& c, const ScenePoints& q, size_t r_dist, float clearance) {
+    { const int rc = lattice_distance(c, q, false, INFINITY, nullptr, r_dist, nullptr, nullptr); if (rc) return rc; }
+    launch_components_clear_mask(c.s, (uint32_t)q.n, c.ws->out.p + r_dist, clearance, c.ws->docc.p);
+    return MON_OK;
+}
+static int32_t* as_i32(float* p) { return reinterpret_cast<int32_t*>(p); }
+
+// What scene_distance and scene_dist_field share.  The rows: sigma | dist | nearest | nearest_owner | free_dist, then the fold's other rows.
 struct DistanceRows { FoldRows f; size_t dist, nearest, nearest_owner, free; };
-static DistanceRows distance_rows(Area& A) {
-    DistanceRows r{}; r.f.sigma = A.row(); r.dist = A.row(); r.nearest = A.row(); r.nearest_owner = A.row(); r.free = A.row();
-    r.f.rgb = A.row(3); r.f.owner = A.row(); r.f.owner_sigma = A.row(); r.f.n_inside = A.row();
+static DistanceRows distance_rows(Area& A, float* sigma, float* dist, int32_t* nearest, int32_t* nearest_owner, float* free_dist) {
+    DistanceRows r; r.f.sigma = A.out(sigma); r.dist = A.out(dist); r.nearest = A.out(nearest); r.nearest_owner = A.out(nearest_owner, 1, true);
+    r.free = A.out(free_dist); fold_rows_rest(A, r.f, false);
     return r;
 }
-static int distance_chain(const SceneCall& c, Model* const* ms, size_t n, const ScenePoints& q, float sigma_min, float max_dist, const DistanceRows& r,
-                          size_t area_end, size_t home, bool nearest, bool nearest_owner) {
-    SceneWs& ws = *c.ws; const hipStream_t s = c.s;
-    const size_t n_q = q.n; const uint32_t nq = (uint32_t)n_q, cap = std::min(nq, kScenePointsPass);
-    {   int rc;
-        if ((rc = field_passes_prepare(c, n, q, cap, 12u)) || (rc = ws.out.grow(area_end)) || (rc = ws.h_out.grow(home)) || (rc = ws.docc.grow(n_q)) ||
-            (rc = ws.dv.grow(2 * n_q)) || (rc = ws.dsite.grow(2 * n_q))) return rc; }
-    float* o = ws.out.p;
-    field_passes_enqueue(c, ms, n, q, true, cap, r.f, nullptr, 0, nullptr);
-    launch_distance_mask(s, nq, o + r.f.sigma, sigma_min, ws.docc.p);
-    launch_distance_passes(s, ws.docc.p, false, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, q.step, ws.dv.p, ws.dsite.p);
-    launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, max_dist, reinterpret_cast<int32_t*>(o + r.f.owner), o + r.dist,
-            nearest ? reinterpret_cast<int32_t*>(o + r.nearest) : nullptr, nearest_owner ? reinterpret_cast<int32_t*>(o + r.nearest_owner) : nullptr);
-    return MON_OK;
+static int distance_chain(const SceneCall& c, Model* const* ms, size_t n, const ScenePoints& q, float sigma_min, float max_dist, const Area& A,
+                          const DistanceRows& r, bool nearest, bool nearest_owner) {
+    { const int rc = lattice_occupancy(c, ms, n, q, A, r.f, sigma_min); if (rc) return rc; }
+    float* o = c.ws->out.p;
+    return lattice_distance(c, q, false, max_dist, as_i32(o + r.f.owner), r.dist, nearest ? as_i32(o + r.nearest) : nullptr,
+                            nearest_owner ? as_i32(o + r.nearest_owner) : nullptr);
 }
 // q: a lattice (scene_lattice).  ids as scene_points', applied to nearest_owner.  max_dist truncates dist and free_dist alike.
 int scene_distance(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, float max_dist, float* dist, int32_t* nearest,
                    int32_t* nearest_owner, float* free_dist, float* sigma, const int32_t* ids) {
     SceneCall c; { const int rc = c.enter("scene_distance", ms, n, side, false); if (rc) return rc; }
-    SceneWs& ws = *c.ws; const hipStream_t s = c.s;
-    const size_t n_q = q.n; const uint32_t nq = (uint32_t)n_q;
-    Area A{ n_q }; const DistanceRows r = distance_rows(A);
-    const size_t home = free_dist ? r.f.rgb : nearest_owner ? r.free : nearest ? r.nearest_owner : r.nearest;
-    { const int rc = distance_chain(c, ms, n, q, sigma_min, max_dist, r, A.end, home, nearest != nullptr, nearest_owner != nullptr); if (rc) return rc; }
-    float* o = ws.out.p;
-    if (free_dist) {
-        launch_distance_passes(s, ws.docc.p, true, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, q.step, ws.dv.p, ws.dsite.p);
-        launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, max_dist, nullptr, o + r.free, nullptr, nullptr);
-    }
-    { const int rc = c.home(home); if (rc) return rc; }
-    const float* h = ws.h_out.p;
-    if (sigma) std::memcpy(sigma, h + r.f.sigma, 4 * n_q);
-    std::memcpy(dist, h + r.dist, 4 * n_q);
-    if (nearest) std::memcpy(nearest, h + r.nearest, 4 * n_q);
-    if (nearest_owner) scene_instances_home(nearest_owner, h + r.nearest_owner, n_q, ids);
-    if (free_dist) std::memcpy(free_dist, h + r.free, 4 * n_q);
+    Area A{ q.n }; const DistanceRows r = distance_rows(A, sigma, dist, nearest, nearest_owner, free_dist);
+    { const int rc = distance_chain(c, ms, n, q, sigma_min, max_dist, A, r, nearest != nullptr, nearest_owner != nullptr); if (rc) return rc; }
+    if (free_dist) { const int rc = lattice_distance(c, q, true, max_dist, nullptr, r.free, nullptr, nullptr); if (rc) return rc; }
+    { const int rc = c.home(A.home); if (rc) return rc; }
+    A.unpack(c.ws->h_out.p, ids);
     return MON_OK;
 }
 // mon_scene_dist_field / mon_online_dist_field: the same chain with dist kept on the device.  The output area opens with four words for
@@ -375,48 +411,40 @@ int scene_dist_field_check(int side, const float* origin3, const float* step3, i
 int scene_dist_field(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, float max_dist, DistField** out) {
     SceneCall c; { const int rc = c.enter("scene_dist_field", ms, n, side, false); if (rc) return rc; }
     SceneWs& ws = *c.ws; const hipStream_t s = c.s;
-    const size_t n_q = q.n;
-    Area A{ n_q }; const size_t r_max = A.take(4); const DistanceRows r = distance_rows(A); const size_t r_part = A.take(kFieldMaxBlocks);
-    DistField* f = nullptr;
-    { const int rc = dist_field_adopt(ms[0]->device, q, &f); if (rc) return rc; }
-    int rc = distance_chain(c, ms, n, q, sigma_min, max_dist, r, A.end, 4, false, false);
+    Area A{ q.n }; const size_t r_max = A.keep(4); const DistanceRows r = distance_rows(A, nullptr, nullptr, nullptr, nullptr, nullptr);
+    const size_t r_part = A.take(kFieldMaxBlocks); DistField* f = nullptr;
+    { const int rc = dist_field_adopt(ms[0]->device, q.g, &f); if (rc) return rc; }
+    int rc = distance_chain(c, ms, n, q, sigma_min, max_dist, A, r, false, false);
     if (!rc) {
         float* o = ws.out.p;
-        const hipError_t e = hipMemcpyAsync(dist_field_cells(*f), o + r.dist, 4 * n_q, hipMemcpyDeviceToDevice, s);
+        const hipError_t e = hipMemcpyAsync(f->cells, o + r.dist, 4 * q.n, hipMemcpyDeviceToDevice, s);
         if (e != hipSuccess) { set_error("scene_dist_field: the copy into the handle failed: %s", hipGetErrorString(e)); rc = MON_ERR_HIP; }
-        else { launch_field_max(s, o + r.dist, (uint32_t)n_q, o + r_part, o + r_max); rc = c.home(4); }
+        else { launch_field_max(s, o + r.dist, (uint32_t)q.n, o + r_part, o + r_max); rc = c.home(A.home); }
     }
     if (rc) { dist_field_free(f); return rc; }
-    dist_field_set_max(*f, ws.h_out.p[r_max]);
+    f->max_value = ws.h_out.p[r_max];
     *out = f;
     return MON_OK;
 }
 
-// ---- connected components (mon_label_components, mon_scene_components_lattice): which cells belong together.  scene_components runs the
-// chain over the lattice, k_distance_mask, for region 1 the untruncated transform and the mask dist > clearance (written over the first mask, which the
-// passes have consumed), the labelling (launch_components), one copy home (k_cc_home: the records that were written, not the table's whole room) and one
-// synchronisation.  Per cell the side's workspace keeps the mask (1 B, shared with the distance call) and, in the output area, label and comp (8 B);
-// region 1 also uses the distance call's passes (16 B).  The numbering's block sums are 4 B per 256 cells.
+// ---- connected components (mon_label_components, mon_scene_components_lattice): which cells belong together.  scene_components: the
+// lattice chain (region 1: with its second stage), the labelling (launch_components; its block sums are 4 B per 256 cells), k_cc_home and one synchronisation.
 static int components_outputs_check(const char* what, int connectivity, const int32_t* label, const mon_lattice_component* table, const uint32_t* n_components) {
     REQUIRE_ARG(what, label, "label");
     if (table && !n_components) { set_error("%s: a table without n_components (the count says how many records were written)", what); return MON_ERR_ARG; }
-    if (connectivity != 6 && connectivity != 18 && connectivity != 26) { set_error("%s: connectivity %d (6, 18 or 26)", what, connectivity); return MON_ERR_ARG; }
-    return MON_OK;
+    return connectivity_check(what, connectivity);
 }
 int label_components_check(const uint8_t* mask, int nx, int ny, int nz, int connectivity, const int32_t* label, const mon_lattice_component* table,
                            const uint32_t* n_components) {
     REQUIRE_ARG("label_components", mask, "mask");
-    { const int rc = lattice_dims_check("label_components", nx, ny, nz); if (rc) return rc; }
+    { const int rc = lattice_dims_check("label_components", nx, ny, nz, kSceneProbeMaxQueries); if (rc) return rc; }
     return components_outputs_check("label_components", connectivity, label, table, n_components);
 }
 int scene_components_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, int region, float clearance,
                            int connectivity, const int32_t* label, const mon_lattice_component* table, const uint32_t* n_components, const float* dist) {
-    { const int rc = lattice_shape_check("scene_components", origin3, step3, nx, ny, nz); if (rc) return rc; }
-    { const int rc = side_check("scene_components", side); if (rc) return rc; }
-    if (!std::isfinite(sigma_min) || sigma_min < 0.f) { set_error("scene_components: sigma_min %g (finite, >= 0)", (double)sigma_min); return MON_ERR_ARG; }
+    { const int rc = lattice_route_check("scene_components", side, origin3, step3, nx, ny, nz, sigma_min); if (rc) return rc; }
     if (region != 0 && region != 1) { set_error("scene_components: region %d (0: occupied matter, 1: traversable space)", region); return MON_ERR_ARG; }
-    if (region == 1 && (!std::isfinite(clearance) || clearance < 0.f)) { set_error("scene_components: clearance %g (finite, >= 0)", (double)clearance);
-        return MON_ERR_ARG; }
+    if (region == 1) { const int rc = nonneg_check("scene_components", "clearance", clearance); if (rc) return rc; }
     if (region == 0 && dist) { set_error("scene_components: dist belongs to region 1 (region 0 runs no distance transform)"); return MON_ERR_ARG; }
     return components_outputs_check("scene_components", connectivity, label, table, n_components);
 }
@@ -428,14 +456,13 @@ static int components_flag_check(const char* what, uint32_t flag) {
 // w: label n | comp n | meta 8 (n_components, the cap flag) | the table's records, 8 words each | the numbering's block sums
 int label_components(int device, const uint8_t* mask, int nx, int ny, int nz, int connectivity, int32_t* label, int32_t* comp, mon_lattice_component* table,
                      uint32_t cap, uint32_t* n_components) {
-    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available"); return MON_ERR_NO_DEVICE; }
-    HIPCHECK(use_device(device));
+    { const int rc = device_enter(device); if (rc) return rc; }
     const size_t n = (size_t)nx * ny * nz, tcap = table ? std::min((size_t)cap, n) : 0, front = 2 * n + 8;
     DevBuf<uint8_t> occ; DevBuf<uint32_t> w;
     { int rc; if ((rc = occ.grow(n)) || (rc = w.grow(front + 8 * tcap + components_scan_words((uint32_t)n)))) return rc; }
     HIPCHECK(hipMemcpy(occ.p, mask, n, hipMemcpyHostToDevice));
     int32_t* d_label = reinterpret_cast<int32_t*>(w.p); uint32_t* d_meta = w.p + 2 * n;
-    launch_components(nullptr, occ.p, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, connectivity, d_label, d_label + n, w.p + front + 8 * tcap,
+    launch_components(nullptr, occ.p, Lattice(nullptr, nullptr, nx, ny, nz), connectivity, d_label, d_label + n, w.p + front + 8 * tcap,
             tcap ? reinterpret_cast<mon_lattice_component*>(w.p + front) : nullptr, (uint32_t)tcap, d_meta);
     HIPCHECK(hipGetLastError());
     std::vector<uint32_t> h(front);                                                 // (the caller's arrays are written only once everything has succeeded)
@@ -456,46 +483,33 @@ int scene_components(Model* const* ms, size_t n, int side, const ScenePoints& q,
                      int32_t* owner, const int32_t* ids) {
     SceneCall c; { const int rc = c.enter("scene_components", ms, n, side, false); if (rc) return rc; }
     SceneWs& ws = *c.ws; const hipStream_t s = c.s;
-    const size_t n_q = q.n, tcap = table ? std::min((size_t)cap, n_q) : 0; const uint32_t nq = (uint32_t)n_q, pass = std::min(nq, kScenePointsPass);
-    // the output area, what may go home from the front (up to the last row asked for): label | comp | meta 8 (n_components, the cap flag) | the table's
-    // records, 8 words each | (region 1: dist) | sigma | owner, then the fold's other rows
-    Area A{ n_q }; const size_t r_label = A.row(), r_comp = A.row(), r_meta = A.take(8), r_table = A.take(8 * tcap), r_dist = region == 1 ? A.row() : A.end;
-    FoldRows f{}; f.sigma = A.row(); f.owner = A.row(); f.rgb = A.row(3); f.owner_sigma = A.row(); f.n_inside = A.row();
-    const size_t home = owner ? f.rgb : sigma ? f.owner : dist ? r_dist + n_q : r_dist;
-    {   int rc;
-        if ((rc = field_passes_prepare(c, n, q, pass, 12u)) || (rc = ws.out.grow(A.end)) || (rc = ws.h_out.grow(home)) || (rc = ws.docc.grow(n_q)) ||
-            (rc = ws.cscan.grow(components_scan_words(nq))) || (region == 1 && ((rc = ws.dv.grow(2 * n_q)) || (rc = ws.dsite.grow(2 * n_q))))) return rc; }
+    const size_t n_q = q.n, tcap = table ? std::min((size_t)cap, n_q) : 0; const uint32_t nq = (uint32_t)n_q;
+    // the area: label | comp | meta 8 (n_components, the cap flag) | the table's records, 8 words each | (region 1: dist) | sigma | owner, the fold's rest
+    Area A{ n_q }; const size_t r_label = A.out(label), r_comp = A.out(comp), r_meta = A.keep(8), r_table = A.keep(8 * tcap);
+    const size_t r_dist = region == 1 ? A.out(dist) : A.end;
+    FoldRows f; f.sigma = A.out(sigma); f.owner = A.out(owner, 1, true); fold_rows_rest(A, f, false);
+    { int rc; if ((rc = ws.cscan.grow(components_scan_words(nq))) || (rc = lattice_occupancy(c, ms, n, q, A, f, sigma_min))) return rc; }
+    if (region == 1) { const int rc = lattice_clearance(c, q, r_dist, clearance); if (rc) return rc; }
     float* o = ws.out.p; uint32_t* o_meta = reinterpret_cast<uint32_t*>(o + r_meta);
-    field_passes_enqueue(c, ms, n, q, true, pass, f, nullptr, 0, nullptr);
-    launch_distance_mask(s, nq, o + f.sigma, sigma_min, ws.docc.p);
-    if (region == 1) {
-        launch_distance_passes(s, ws.docc.p, false, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, q.step, ws.dv.p, ws.dsite.p);
-        launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, INFINITY, nullptr, o + r_dist, nullptr, nullptr);
-        launch_components_clear_mask(s, nq, o + r_dist, clearance, ws.docc.p);
-    }
-    launch_components(s, ws.docc.p, (uint32_t)q.nx, (uint32_t)q.ny, (uint32_t)q.nz, connectivity, reinterpret_cast<int32_t*>(o + r_label),
-            reinterpret_cast<int32_t*>(o + r_comp), ws.cscan.p, tcap ? reinterpret_cast<mon_lattice_component*>(o + r_table) : nullptr, (uint32_t)tcap, o_meta);
-    launch_components_home(s, reinterpret_cast<const uint32_t*>(o), reinterpret_cast<uint32_t*>(ws.h_out.p), (uint32_t)home, (uint32_t)r_table, (uint32_t)tcap, o_meta);
+    launch_components(s, ws.docc.p, q.g, connectivity, as_i32(o + r_label), as_i32(o + r_comp), ws.cscan.p,
+            tcap ? reinterpret_cast<mon_lattice_component*>(o + r_table) : nullptr, (uint32_t)tcap, o_meta);
+    // (k_cc_home: of the table's room only the records that were written)
+    launch_components_home(s, reinterpret_cast<const uint32_t*>(o), reinterpret_cast<uint32_t*>(ws.h_out.p), (uint32_t)A.home, (uint32_t)r_table, (uint32_t)tcap, o_meta);
     { const int rc = c.finish(); if (rc) return rc; }
     const float* h = ws.h_out.p; const uint32_t* h_meta = reinterpret_cast<const uint32_t*>(h + r_meta);
     { const int rc = components_flag_check("scene_components", h_meta[1]); if (rc) return rc; }
-    std::memcpy(label, h + r_label, 4 * n_q);
-    if (comp) std::memcpy(comp, h + r_comp, 4 * n_q);
+    A.unpack(h, ids);
     if (table) std::memcpy(table, h + r_table, 32 * std::min((size_t)h_meta[0], tcap));
     if (n_components) *n_components = h_meta[0];
-    if (dist) std::memcpy(dist, h + r_dist, 4 * n_q);
-    if (sigma) std::memcpy(sigma, h + f.sigma, 4 * n_q);
-    if (owner) scene_instances_home(owner, h + f.owner, n_q, ids);
     return MON_OK;
 }
 
 // ---- shortest-path cost fields (mon_shortest_paths, mon_scene_paths_lattice, mon_lattice_path): how far the goal is through the space the
-// robot may occupy, and which way to go.  scene_paths runs the chain over the lattice, k_distance_mask, the untruncated transform, the mask dist > clearance
-// (written over the first mask, as scene_components does), the multiplier, then the sweeps (paths_relax) and the finish, one copy home.  How many sweeps
-// the field needs depends on the data, so they are enqueued in batches of kPathsBatch, each sweep with a "left work" word of its own, and the words are
-// read back once per batch: one small synchronisation per batch, not per sweep.  The sweeps behind the first one that left no work found no flag and
-// returned at once.  A variant build (tools/variant_build.sh <tag> -DMON_PATHS_BATCH=n) takes another batch for measurements (tools/scene_paths_timing.py,
-// profiles/r21_scene_paths.md); outputs do not depend on it.
+// robot may occupy, and which way to go.  scene_paths: both stages of the lattice chain, the multiplier, then the sweeps (paths_relax) and the finish.  How
+// many sweeps the field needs depends on the data, so they are enqueued in batches of kPathsBatch, each sweep with a "left work" word of its own, and the
+// words are read back once per batch: one small synchronisation per batch, not per sweep.  The sweeps behind the first one that left no work found no flag
+// and returned at once.  A variant build (tools/variant_build.sh <tag> -DMON_PATHS_BATCH=n) takes another batch for measurements
+// (tools/scene_paths_timing.py, profiles/r21_scene_paths.md); outputs do not depend on it.
 #ifndef MON_PATHS_BATCH
 #define MON_PATHS_BATCH 32
 #endif
@@ -505,7 +519,7 @@ void paths_last_stats(uint32_t out3[3]) { for (int k = 0; k < 3; ++k) out3[k] = 
 
 static int paths_args_check(const char* what, int connectivity, const int32_t* seeds, size_t n_seeds, size_t n_cells, float max_cost, const float* cost) {
     REQUIRE_ARG(what, cost, "cost"); REQUIRE_ARG(what, seeds, "seeds");
-    if (connectivity != 6 && connectivity != 18 && connectivity != 26) { set_error("%s: connectivity %d (6, 18 or 26)", what, connectivity); return MON_ERR_ARG; }
+    { const int rc = connectivity_check(what, connectivity); if (rc) return rc; }
     if (!(max_cost > 0.f)) { set_error("%s: max_cost %g (above 0; +inf for no limit)", what, (double)max_cost); return MON_ERR_ARG; }
     if (n_seeds == 0 || n_seeds > kPathsMaxSeeds) { set_error("%s: %zu seeds (1 to %u)", what, n_seeds, kPathsMaxSeeds); return MON_ERR_ARG; }
     for (size_t k = 0; k < n_seeds; ++k) if (seeds[k] < 0 || (size_t)seeds[k] >= n_cells) {
@@ -515,8 +529,7 @@ static int paths_args_check(const char* what, int connectivity, const int32_t* s
 int shortest_paths_check(const uint8_t* passable, int nx, int ny, int nz, const float* step3, int connectivity, const float* cell_cost, const int32_t* seeds,
                          size_t n_seeds, float max_cost, const float* cost) {
     REQUIRE_ARG("shortest_paths", passable, "passable"); REQUIRE_ARG("shortest_paths", step3, "step");
-    { const int rc = lattice_dims_check("shortest_paths", nx, ny, nz); if (rc) return rc; }
-    for (int a = 0; a < 3; ++a) if (!std::isfinite(step3[a])) { set_error("shortest_paths: step is not finite"); return MON_ERR_ARG; }
+    { int rc; if ((rc = lattice_dims_check("shortest_paths", nx, ny, nz, kSceneProbeMaxQueries)) || (rc = step_finite_check("shortest_paths", step3))) return rc; }
     const size_t n = (size_t)nx * ny * nz;
     { const int rc = paths_args_check("shortest_paths", connectivity, seeds, n_seeds, n, max_cost, cost); if (rc) return rc; }
     if (cell_cost) for (size_t i = 0; i < n; ++i) if (!std::isfinite(cell_cost[i]) || cell_cost[i] < 0.f) {
@@ -525,25 +538,23 @@ int shortest_paths_check(const uint8_t* passable, int nx, int ny, int nz, const 
 }
 int scene_paths_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float clearance, float soft_radius,
                       float soft_weight, int connectivity, const int32_t* seeds, size_t n_seeds, float max_cost, const float* cost) {
-    { const int rc = lattice_shape_check("scene_paths", origin3, step3, nx, ny, nz); if (rc) return rc; }
-    { const int rc = side_check("scene_paths", side); if (rc) return rc; }
-    if (!std::isfinite(sigma_min) || sigma_min < 0.f) { set_error("scene_paths: sigma_min %g (finite, >= 0)", (double)sigma_min); return MON_ERR_ARG; }
-    if (!std::isfinite(clearance) || clearance < 0.f) { set_error("scene_paths: clearance %g (finite, >= 0)", (double)clearance); return MON_ERR_ARG; }
-    if (!std::isfinite(soft_weight) || soft_weight < 0.f) { set_error("scene_paths: soft_weight %g (finite, >= 0)", (double)soft_weight); return MON_ERR_ARG; }
+    {   int rc;
+        if ((rc = lattice_route_check("scene_paths", side, origin3, step3, nx, ny, nz, sigma_min)) || (rc = nonneg_check("scene_paths", "clearance", clearance)) ||
+            (rc = nonneg_check("scene_paths", "soft_weight", soft_weight))) return rc; }
     if (soft_weight > 0.f && (!std::isfinite(soft_radius) || !(soft_radius > 0.f))) {
         set_error("scene_paths: soft_radius %g (finite, above 0, with a soft_weight above 0)", (double)soft_radius); return MON_ERR_ARG; }
     return paths_args_check("scene_paths", connectivity, seeds, n_seeds, (size_t)nx * ny * nz, max_cost, cost);
 }
 // The sweeps on stream s until one leaves no work.  d_raised: kPathsBatch words on the device, h_raised: as many on the host (pinned in the scene call).
 // At most n + 1 sweeps: a sweep that leaves work has carried some cell's least walk across a tile border, and Bellman-Ford needs no more than n rounds.
-static int paths_relax(const char* what, hipStream_t s, const uint8_t* occ, uint32_t nx, uint32_t ny, uint32_t nz, const float* step3, int connectivity,
-                       const float* mult, float* cost, uint8_t* flags, uint32_t* d_raised, uint32_t* h_raised) {
-    const uint64_t cap = (uint64_t)nx * ny * nz + 1u;
+static int paths_relax(const char* what, hipStream_t s, const uint8_t* occ, const Lattice& g, int connectivity, const float* mult, float* cost, uint8_t* flags,
+                       uint32_t* d_raised, uint32_t* h_raised) {
+    const uint64_t cap = (uint64_t)g.n() + 1u;
     uint32_t sweeps = 0, batches = 0;
     for (;;) {
         const uint32_t b = (uint32_t)std::min<uint64_t>(kPathsBatch, cap - sweeps);
         HIPCHECK(hipMemsetAsync(d_raised, 0, 4 * (size_t)b, s));
-        for (uint32_t k = 0; k < b; ++k) launch_paths_sweep(s, occ, nx, ny, nz, step3, connectivity, mult, cost, flags, sweeps + k, d_raised + k);
+        for (uint32_t k = 0; k < b; ++k) launch_paths_sweep(s, occ, g, connectivity, mult, cost, flags, sweeps + k, d_raised + k);
         HIPCHECK(hipMemcpyAsync(h_raised, d_raised, 4 * (size_t)b, hipMemcpyDeviceToHost, s));
         HIPCHECK(hipStreamSynchronize(s));
         HIPCHECK(hipGetLastError());
@@ -558,22 +569,21 @@ static int paths_relax(const char* what, hipStream_t s, const uint8_t* occ, uint
 // w: working cost n | cost n | next n | multiplier n | seeds | a batch's words
 int shortest_paths(int device, const uint8_t* passable, int nx, int ny, int nz, const float* step3, int connectivity, const float* cell_cost,
                    const int32_t* seeds, size_t n_seeds, float max_cost, float* cost, int32_t* next) {
-    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available"); return MON_ERR_NO_DEVICE; }
-    HIPCHECK(use_device(device));
-    const size_t n = (size_t)nx * ny * nz; const uint32_t ux = (uint32_t)nx, uy = (uint32_t)ny, uz = (uint32_t)nz;
+    { const int rc = device_enter(device); if (rc) return rc; }
+    const Lattice g(nullptr, step3, nx, ny, nz); const size_t n = g.n();
     DevBuf<uint8_t> occ, flags; DevBuf<uint32_t> w;
-    { int rc; if ((rc = occ.grow(n)) || (rc = flags.grow(2 * (size_t)paths_tiles(ux, uy, uz))) || (rc = w.grow(4 * n + n_seeds + kPathsBatch))) return rc; }
+    { int rc; if ((rc = occ.grow(n)) || (rc = flags.grow(2 * (size_t)paths_tiles(g))) || (rc = w.grow(4 * n + n_seeds + kPathsBatch))) return rc; }
     float* d_work = reinterpret_cast<float*>(w.p); float* d_cost = d_work + n; int32_t* d_next = reinterpret_cast<int32_t*>(w.p + 2 * n);
     float* d_mult = cell_cost ? reinterpret_cast<float*>(w.p + 3 * n) : nullptr; int32_t* d_seeds = reinterpret_cast<int32_t*>(w.p + 4 * n);
     uint32_t* d_raised = w.p + 4 * n + n_seeds;
     HIPCHECK(hipMemcpy(occ.p, passable, n, hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(d_seeds, seeds, 4 * n_seeds, hipMemcpyHostToDevice));
     if (cell_cost) HIPCHECK(hipMemcpy(d_mult, cell_cost, 4 * n, hipMemcpyHostToDevice));
-    launch_paths_init(nullptr, occ.p, ux, uy, uz, d_seeds, (uint32_t)n_seeds, d_work, flags.p);
+    launch_paths_init(nullptr, occ.p, g, d_seeds, (uint32_t)n_seeds, d_work, flags.p);
     std::vector<uint32_t> h_raised(kPathsBatch);
-    { const int rc = paths_relax("shortest_paths", nullptr, occ.p, ux, uy, uz, step3, connectivity, d_mult, d_work, flags.p, d_raised, h_raised.data());
+    { const int rc = paths_relax("shortest_paths", nullptr, occ.p, g, connectivity, d_mult, d_work, flags.p, d_raised, h_raised.data());
       if (rc) return rc; }
-    launch_paths_finish(nullptr, occ.p, ux, uy, uz, step3, connectivity, d_mult, d_work, max_cost, d_cost, next ? d_next : nullptr);
+    launch_paths_finish(nullptr, occ.p, g, connectivity, d_mult, d_work, max_cost, d_cost, next ? d_next : nullptr);
     HIPCHECK(hipGetLastError());
     std::vector<uint32_t> h(next ? 2 * n : n);                                      // (the caller's arrays are written only once everything has succeeded)
     HIPCHECK(hipMemcpy(h.data(), d_cost, 4 * h.size(), hipMemcpyDeviceToHost));
@@ -587,37 +597,23 @@ int scene_paths(Model* const* ms, size_t n, int side, const ScenePoints& q, floa
                 const int32_t* ids) {
     SceneCall c; { const int rc = c.enter("scene_paths", ms, n, side, false); if (rc) return rc; }
     SceneWs& ws = *c.ws; const hipStream_t s = c.s;
-    const size_t n_q = q.n; const uint32_t nq = (uint32_t)n_q, pass = std::min(nq, kScenePointsPass);
-    const uint32_t nx = (uint32_t)q.nx, ny = (uint32_t)q.ny, nz = (uint32_t)q.nz;
-    // the output area, what may go home from the front (up to the last row asked for): cost | next | dist | sigma | owner, then the fold's other rows
-    Area A{ n_q }; const size_t r_cost = A.row(), r_next = A.row(), r_dist = A.row();
-    FoldRows f{}; f.sigma = A.row(); f.owner = A.row(); f.rgb = A.row(3); f.owner_sigma = A.row(); f.n_inside = A.row();
-    const size_t home = owner ? f.rgb : sigma ? f.owner : dist ? f.sigma : next ? r_dist : r_next;
+    const size_t n_q = q.n; const uint32_t nq = (uint32_t)n_q;
+    // the area: cost | next | dist | sigma | owner, then the fold's other rows
+    Area A{ n_q }; const size_t r_cost = A.out(cost), r_next = A.out(next), r_dist = A.out(dist);
+    FoldRows f; f.sigma = A.out(sigma); f.owner = A.out(owner, 1, true); fold_rows_rest(A, f, false);
     {   int rc;
-        if ((rc = field_passes_prepare(c, n, q, pass, 12u)) || (rc = ws.out.grow(A.end)) || (rc = ws.h_out.grow(home)) || (rc = ws.docc.grow(n_q)) ||
-            (rc = ws.dv.grow(2 * n_q)) || (rc = ws.dsite.grow(2 * n_q)) || (rc = ws.pcost.grow(n_q)) || (soft_weight > 0.f && (rc = ws.pmul.grow(n_q))) ||
-            (rc = ws.pseeds.grow(n_seeds)) || (rc = ws.pflags.grow(2 * (size_t)paths_tiles(nx, ny, nz))) || (rc = ws.praised.grow(kPathsBatch)) ||
-            (rc = ws.h_raised.grow(kPathsBatch))) return rc; }
-    float* o = ws.out.p; const float* mult = soft_weight > 0.f ? ws.pmul.p : nullptr;
+        if ((rc = ws.pcost.grow(n_q)) || (soft_weight > 0.f && (rc = ws.pmul.grow(n_q))) || (rc = ws.pseeds.grow(n_seeds)) ||
+            (rc = ws.pflags.grow(2 * (size_t)paths_tiles(q.g))) || (rc = ws.praised.grow(kPathsBatch)) || (rc = ws.h_raised.grow(kPathsBatch))) return rc; }
+    const float* mult = soft_weight > 0.f ? ws.pmul.p : nullptr;
     HIPCHECK(hipMemcpyAsync(ws.pseeds.p, seeds, 4 * n_seeds, hipMemcpyHostToDevice, s));
-    field_passes_enqueue(c, ms, n, q, true, pass, f, nullptr, 0, nullptr);
-    launch_distance_mask(s, nq, o + f.sigma, sigma_min, ws.docc.p);
-    launch_distance_passes(s, ws.docc.p, false, nx, ny, nz, q.step, ws.dv.p, ws.dsite.p);
-    launch_distance_finish(s, nq, ws.dv.p, ws.dsite.p, INFINITY, nullptr, o + r_dist, nullptr, nullptr);
-    launch_components_clear_mask(s, nq, o + r_dist, clearance, ws.docc.p);
+    { int rc; if ((rc = lattice_occupancy(c, ms, n, q, A, f, sigma_min)) || (rc = lattice_clearance(c, q, r_dist, clearance))) return rc; }
+    float* o = ws.out.p;
     if (mult) launch_paths_soft(s, nq, o + r_dist, soft_radius, soft_weight, ws.pmul.p);
-    launch_paths_init(s, ws.docc.p, nx, ny, nz, ws.pseeds.p, (uint32_t)n_seeds, ws.pcost.p, ws.pflags.p);
-    { const int rc = paths_relax("scene_paths", s, ws.docc.p, nx, ny, nz, q.step, connectivity, mult, ws.pcost.p, ws.pflags.p, ws.praised.p, ws.h_raised.p);
-      if (rc) return rc; }
-    launch_paths_finish(s, ws.docc.p, nx, ny, nz, q.step, connectivity, mult, ws.pcost.p, max_cost, o + r_cost,
-            next ? reinterpret_cast<int32_t*>(o + r_next) : nullptr);
-    { const int rc = c.home(home); if (rc) return rc; }
-    const float* h = ws.h_out.p;
-    std::memcpy(cost, h + r_cost, 4 * n_q);
-    if (next) std::memcpy(next, h + r_next, 4 * n_q);
-    if (dist) std::memcpy(dist, h + r_dist, 4 * n_q);
-    if (sigma) std::memcpy(sigma, h + f.sigma, 4 * n_q);
-    if (owner) scene_instances_home(owner, h + f.owner, n_q, ids);
+    launch_paths_init(s, ws.docc.p, q.g, ws.pseeds.p, (uint32_t)n_seeds, ws.pcost.p, ws.pflags.p);
+    { const int rc = paths_relax("scene_paths", s, ws.docc.p, q.g, connectivity, mult, ws.pcost.p, ws.pflags.p, ws.praised.p, ws.h_raised.p); if (rc) return rc; }
+    launch_paths_finish(s, ws.docc.p, q.g, connectivity, mult, ws.pcost.p, max_cost, o + r_cost, next ? as_i32(o + r_next) : nullptr);
+    { const int rc = c.home(A.home); if (rc) return rc; }
+    A.unpack(ws.h_out.p, ids);
     return MON_OK;
 }
 // mon_lattice_path: the cells from start along next to the first -1.  A walk of more than n_cells cells has come by some cell twice: a damaged array.

@@ -10,7 +10,14 @@ with two boxes) and every online counterpart on a manager whose two objects have
 scene's point queries and gradients (lists of 5 points, with and without level weights and select), the lattice query, the lattice gradients, the distance
 field and the components (region 0 with a table, region 1 with and without its optional outputs) on a lattice of 3 x 2 x 2 and, once per family, on one of
 33 x 32 x 16 cells (a pass boundary with a ragged tail of 512), the normals at ray hits, the six online counterparts, and with no side
-mon_distance_transform, mon_label_components, mon_lattice_points and mon_camera_rays.  Every kernel launch (registered
+mon_distance_transform, mon_label_components, mon_lattice_points and mon_camera_rays.  Behind them, in a section of its own ("-- lattice routes": a handle
+makes a stream, and the streams above keep their creation indices), the cost fields and the device-resident distance fields: per side
+mon_scene_paths_lattice (with a soft cost and every optional output, with neither, on 33 x 32 x 16) and mon_scene_dist_field (both lattices); with no side
+mon_shortest_paths (with and without cell_cost and next, both lattices), mon_lattice_path, mon_dist_field_create and, on its handle, _info, _read, _sample
+(with and without gradients), _score (way_floats 3 and 16, with and without the optional outputs), _match (with and without the normal equations and the
+pivots), mon_register_default, mon_dist_field_register and _destroy; mon_online_paths_lattice and mon_online_dist_field.  The stand-in runtime leaves every
+read-back 0, so a cost field settles after its first batch of sweeps and a registration ends in its first round: with status 3 under the default
+min_inside, with status 2 (no factorisation of an all-zero row) under min_inside 0; both are called.  Every kernel launch (registered
 name, grid, block, dynamic LDS bytes, stream by creation index) and every asynchronous fill / copy (bytes, stream) is one line.  The trace is folded without
 loss -- a block of up to 12 lines that repeats back to back is written once, followed by "x N" (fold) -- and must then equal tests/golden/launch_trace.txt line
 for line.  No GPU.
@@ -34,7 +41,10 @@ holds them (test_gpu_parity.py, test_occupancy.py, test_occupancy_oracle.py, tes
 
 The field queries' lines, routes and refusals, were recorded from the commit before their host chain was written once ("Add connected components over a
 lattice of the object map"), with this driver and that commit's product sources; the lines above and between them came out as they stood.  (Their object
-lists need no common camera, dataset or sample stream: other_K, other_ds and xorwow are accepted there and their launches are in the trace.)
+lists need no common camera, dataset or sample stream: other_K, other_ds and xorwow are accepted there and their launches are in the trace.)  The
+"-- lattice routes" lines and their refusals (every NULL argument, every count at 0 and one past its maximum, connectivity 7, max_cost 0, a seed outside
+the lattice, way_floats 4, huber 0, lambda_up 1, a NULL handle beside a bad count) were recorded in the same way from the commit before the lattice routes'
+chain was written once ("Add scan matching against a device-resident distance field").
 
 A change that moves the schedule ON PURPOSE records the new trace: python tests/test_launch_trace.py --record
 A refactor shows that nothing moved by recording from the parent commit's product sources with this driver, and getting the committed file:

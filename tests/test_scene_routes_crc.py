@@ -18,10 +18,20 @@ over the larger box (the gradients with a select and level weights that are not 
 33 x 32 x 17 around the objects for the lattice query, the lattice gradients, the distance field (truncated with free_dist, untruncated without) and the
 components (region 0, 26-connected, with its table; region 1, 6-connected, with dist, sigma and owner).  sigma_min is the 90th percentile of the lattice
 query's own sigma; between 1 % and 99 % of the cells must be occupied before the distance and component calls are made.
+The cost fields and the device-resident distance fields (scene_field.cpp, dist_field.cpp) joined before their host chains were written once, recorded in the
+same way from the commit before ("Add scan matching against a device-resident distance field"); every CRC above came out of that record as it stood.  On the
+same lattice and sigma_min: the cost field, 26-connected with clearance = the largest step, a soft cost of weight 2 within three such steps and every
+optional output, from the three traversable cells of lowest flat index; the same 6-connected without a soft cost, cost alone, cut at a quarter of the
+lattice's diagonal (between 1 % and 99 % of the cells must have a finite cost in either); the distance field kept on the device, cut at a quarter of the
+diagonal, read back with its description; and on that handle its samples with gradients at the first 1 000 world points, the scores of 8 trajectories of 5
+matrix waypoints (n_sub 3, two spheres, every output), the match of a scan under 4 pose hypotheses with the normal equations, and their registration
+(the defaults with max_evals 6, every output).  The scan is the first 1 000 lattice points whose distance is below one step (there must be 1 000), and at
+least one hypothesis must end with a status other than 3.  These kernels use no float atomics.
 Side 1 is compared only when render_snapshot reports step 60 for both objects; otherwise the case fails.  The online routes are left out:
 what their snapshots hold depends on thread timing.
 
 Bit equality is the condition: there is no tolerance."""
+import ctypes as C
 import json
 import math
 import os
@@ -48,7 +58,9 @@ ROUTES = ("render_scene", "probe_scene", "cast_scene", "scene_pose_loss", "scene
           "scene_relocalise", "refine_pose_c2f",
           "query_scene_points", "query_scene_lattice", "query_scene_gradients", "query_scene_lattice_gradients", "cast_scene_normals",
           "scene_distance_lattice", "scene_distance_lattice_untruncated", "scene_components_lattice", "scene_components_lattice_free",
-          "object_query_points", "object_query_gradients")
+          "object_query_points", "object_query_gradients",
+          "scene_paths_lattice", "scene_paths_lattice_plain", "scene_dist_field", "dist_field_sample", "dist_field_score", "dist_field_match",
+          "dist_field_register")
 LATTICE = (33, 32, 17)                                           # 17 952 cells: one pass boundary, the field routes' common lattice
 
 
@@ -94,6 +106,66 @@ def _components_arrays(r):
     return [label, comp, table, np.uint32(n)] + [rows[k] for k in sorted(rows)]
 
 
+def _paths_cost_only(pkg, objs, origin, step, smin, seeds, clearance, max_cost, side):
+    """mon_scene_paths_lattice, 6-connected without a soft cost, every output but cost NULL (the binding's call always asks for next)"""
+    P = lambda a: a.ctypes.data_as(C.c_void_p)          # noqa: E731
+    hs = (C.c_void_p * len(objs))(*[o.h for o in objs]); sd = np.ascontiguousarray(seeds, np.int32); cost = np.empty(int(np.prod(LATTICE)), np.float32)
+    rc = pkg.lib().mon_scene_paths_lattice(hs, len(objs), side, P(origin), P(step), *LATTICE, smin, clearance, 0.0, 0.0, 6, P(sd), sd.size, max_cost, P(cost),
+                                           None, None, None, None)
+    assert rc == 0, pkg.lib().mon_last_error()
+    return cost
+
+
+def _rotations(rs, n, max_angle):
+    """n rotation matrices by Rodrigues' formula: a random axis, an angle of up to max_angle"""
+    out = np.empty((n, 3, 3))
+    for k in range(n):
+        a = rs.normal(size=3); a /= np.linalg.norm(a); t = rs.uniform(-max_angle, max_angle)
+        K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+        out[k] = np.eye(3) + math.sin(t) * K + (1 - math.cos(t)) * (K @ K)
+    return out
+
+
+def run_lattice_routes(pkg, objs, side, origin, step, smin, dist, world):
+    """the cost fields and the device-resident distance field with its sample, score, match and register calls: {route: every array it returns}.
+    dist: scene_distance_lattice's untruncated row, which says where a seed may stand and where the scan lies."""
+    n = int(np.prod(LATTICE)); h = float(step.max()); diag = float(np.linalg.norm(step * (np.array(LATTICE) - 1)))
+    seeds = np.flatnonzero(dist > np.float32(h))[:3].astype(np.int32)
+    assert seeds.size == 3, seeds
+    out = {}
+    cost, nxt, rows = pkg.scene_paths_lattice(objs, origin, step, LATTICE, smin, seeds, clearance=h, soft_radius=3.0 * h, soft_weight=2.0, connectivity=26,
+                                              side=side, rows=("dist", "sigma", "owner"))
+    out["scene_paths_lattice"] = [cost, nxt, rows["dist"], rows["sigma"], rows["owner"]]
+    out["scene_paths_lattice_plain"] = [_paths_cost_only(pkg, objs, origin, step, smin, seeds, h, 0.25 * diag, side)]
+    for k in ("scene_paths_lattice", "scene_paths_lattice_plain"):
+        n_fin = int(np.isfinite(out[k][0]).sum())
+        print("side %d: %s: %d of %d cells have a finite cost" % (side, k, n_fin, n))
+        assert n // 100 <= n_fin <= n - n // 100, (k, n_fin, n)
+    scan = pkg.lattice_points(origin, step, LATTICE)[np.flatnonzero(dist < np.float32(h))[:1000]]
+    assert scan.shape == (1000, 3), scan.shape
+    rs = np.random.RandomState(29); centre = scan.mean(0, dtype=np.float64)
+    # 4 hypotheses about the identity (the scan is in world coordinates), turned about the scan's centre; row-major for the match calls
+    hyp = pkg.pose_hypotheses(np.eye(4, dtype=np.float32).reshape(16), 4, math.radians(2.0), 0.5 * h, pivot=centre, seed=4)
+    poses = np.ascontiguousarray(hyp.reshape(4, 4, 4).transpose(0, 2, 1))
+    lo = origin.astype(np.float64); ext = step.astype(np.float64) * (np.array(LATTICE) - 1)
+    ways = np.zeros((8, 5, 4, 4)); ways[:, :, 3, 3] = 1.0
+    ways[:, :, :3, :3] = _rotations(rs, 40, 0.5).reshape(8, 5, 3, 3); ways[:, :, :3, 3] = lo + rs.uniform(0.05, 0.95, (8, 5, 3)) * ext
+    spheres = np.array([[0.0, 0.0, 0.0, 0.5 * h], [h, 0.0, 0.5 * h, 0.25 * h]], np.float32)
+    with pkg.scene_dist_field(objs, origin, step, LATTICE, smin, 0.25 * diag, side=side) as f:
+        d = f.info()
+        out["scene_dist_field"] = [f.read(), np.array([d.nx, d.ny, d.nz, d.device, *d.origin, *d.step, d.max_value], np.float32)]
+        out["dist_field_sample"] = f.sample(world[:1000], outside=0.25 * diag, grad=True)
+        sc_ = f.score(spheres, ways.astype(np.float32), n_sub=3, outside=0.25 * diag, margin=0.5 * h, safe=2.0 * h)
+        out["dist_field_score"] = [sc_[k] for k in ("min_clear", "first_hit", "cost", "way_clear", "way_grad")]
+        m = f.match(scan, poses, pivots=np.tile(centre, (4, 1)), huber=2.0 * h, outside=0.25 * diag, normal=True)
+        out["dist_field_match"] = [m[k] for k in ("cost", "n_inside", "n_inlier", "A", "b")]
+        r = f.register(scan, poses, max_evals=6)
+        print("side %d: register: status %s, evals %s, best %d" % (side, r["status"], r["evals"], r["best"]))
+        assert (r["status"] != 3).any(), r["status"]
+        out["dist_field_register"] = [r[k] for k in ("poses", "cost", "n_inside", "n_inlier", "evals", "status")] + [np.int32(r["best"])]
+    return out
+
+
 def run_field_routes(pkg, objs, rays, side, sc):
     """the field queries (scene_field.cpp): {route: every array it returns}"""
     world, unit, select, origin, step = _field_inputs(sc)
@@ -118,6 +190,7 @@ def run_field_routes(pkg, objs, rays, side, sc):
         objs, origin, step, LATTICE, smin, region=1, clearance=float(step.max()), connectivity=6, side=side, rows=("dist", "sigma", "owner")))
     out["object_query_points"] = (pkg.query_object_points(objs[0], unit, side=side),)
     out["object_query_gradients"] = pkg.query_object_gradients(objs[0], unit, level_weights=lw[:objs[0].cfg.n_levels], side=side)
+    out.update(run_lattice_routes(pkg, objs, side, origin, step, smin, out["scene_distance_lattice_untruncated"][0], world))
     return out
 
 

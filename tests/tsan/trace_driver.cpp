@@ -1,7 +1,7 @@
 // trace_driver.cpp -- walks the C ABI single-threaded on the host side built --offload-host-only against tests/tsan/hip_stub.cpp (no sanitizer) with the
 // stub's launch trace on: every kernel launch and asynchronous fill / copy of every training path as one line of text, under a heading per case and per call;
-// then (part two) of every scene, pose and field-query route on both sides and through the online manager, and a list of the calls those routes refuse, with
-// code and message.
+// then (part two) of every scene, pose and field-query route on both sides and through the online manager, the cost fields and the device-resident distance
+// fields in a section of their own, and a list of the calls those routes refuse, with code and message.
 // tests/test_launch_trace.py compares the output with tests/golden/launch_trace.txt.  Usage: trace_driver <scratch dir> <config json>.  TEST INFRASTRUCTURE.
 #include <chrono>
 #include <cmath>
@@ -121,6 +121,13 @@ struct Args {
     const float* pts; size_t n_pts; const float* upts; const float* origin; const float* step; int nx, ny, nz; const float* glw; const int32_t* sel;
     float sigma_min, max_dist; int region; float clearance; int conn; mon_lattice_component* table; uint32_t cap; uint32_t* n_comp; const uint8_t* mask;
     float* sigma; float* grad; float* raw4; float* normal; float* dist; int32_t* label; float* xyz_out; mon_scene_ray* rays_out; bool opt;
+    // the cost fields (mask: the passable cells), a walk along next, and the device-resident distance fields: a handle with what its sample, score, match
+    // and register calls read (pts, n_pts: the sampled points and the scan; field_max: the scene calls' finite max_dist)
+    const float* cell_cost; const int32_t* seeds; size_t n_seeds; float max_cost, soft_radius, soft_weight; float* cost;
+    const int32_t* next; size_t n_cells; int32_t start; int32_t* path; size_t path_cap; size_t* n_path;
+    mon_dist_field* field; mon_dist_field** field_out; const float* fdist; mon_dist_field_desc* info; float field_max, outside;
+    const float* spheres; size_t n_spheres; const float* ways; int way_floats; size_t n_traj, n_way, n_sub; const mon_traj_score_params* tp; float* min_clear;
+    const float* mposes; size_t n_h; const float* pivots; const mon_scan_match_params* mp; mon_register_params* rp; float* poses_out;
 };
 static int32_t* as_i32(float* p) { return reinterpret_cast<int32_t*>(p); }
 static int scene_render(const Args& a) { return mon_scene_render(a.objs, a.n_objs, a.side, a.rect, a.Twc, a.rgb, a.depth, a.out, as_i32(a.out)); }
@@ -191,6 +198,29 @@ static int online_distance_lattice(const Args& a) { return mon_online_distance_l
         as_i32(sl(a, 1)), as_i32(sl(a, 2)), sl(a, 3), sl(a, 4)); }
 static int online_components_lattice(const Args& a) { return mon_online_components_lattice(a.om, a.origin, a.step, a.nx, a.ny, a.nz, a.sigma_min, a.region, a.clearance,
         a.conn, a.label, as_i32(sl(a, 1)), a.table, a.cap, a.n_comp, a.region == 1 ? sl(a, 2) : nullptr, sl(a, 3), as_i32(sl(a, 4))); }
+// the cost fields and the device-resident distance fields
+static int shortest_paths(const Args& a) { return mon_shortest_paths(0, a.mask, a.nx, a.ny, a.nz, a.step, a.conn, a.cell_cost, a.seeds, a.n_seeds, a.max_cost, a.cost,
+        as_i32(sl(a, 1))); }
+static int scene_paths_lattice(const Args& a) { return mon_scene_paths_lattice(a.objs, a.n_objs, a.side, a.origin, a.step, a.nx, a.ny, a.nz, a.sigma_min, a.clearance,
+        a.soft_radius, a.soft_weight, a.conn, a.seeds, a.n_seeds, a.max_cost, a.cost, as_i32(sl(a, 1)), sl(a, 2), sl(a, 3), as_i32(sl(a, 4))); }
+static int online_paths_lattice(const Args& a) { return mon_online_paths_lattice(a.om, a.origin, a.step, a.nx, a.ny, a.nz, a.sigma_min, a.clearance, a.soft_radius,
+        a.soft_weight, a.conn, a.seeds, a.n_seeds, a.max_cost, a.cost, as_i32(sl(a, 1)), sl(a, 2), sl(a, 3), as_i32(sl(a, 4))); }
+static int lattice_path(const Args& a) { return mon_lattice_path(a.next, a.n_cells, a.start, a.path, a.path_cap, a.n_path); }
+static int dist_field_create(const Args& a) { return mon_dist_field_create(0, a.fdist, a.nx, a.ny, a.nz, a.origin, a.step, a.field_out); }
+static int scene_dist_field(const Args& a) { return mon_scene_dist_field(a.objs, a.n_objs, a.side, a.origin, a.step, a.nx, a.ny, a.nz, a.sigma_min, a.field_max,
+        a.field_out); }
+static int online_dist_field(const Args& a) { return mon_online_dist_field(a.om, a.origin, a.step, a.nx, a.ny, a.nz, a.sigma_min, a.field_max, a.field_out); }
+static int dist_field_info(const Args& a) { return mon_dist_field_info(a.field, a.info); }
+static int dist_field_read(const Args& a) { return mon_dist_field_read(a.field, a.dist); }
+static int dist_field_destroy(const Args& a) { return mon_dist_field_destroy(a.field); }
+static int dist_field_sample(const Args& a) { return mon_dist_field_sample(a.field, a.pts, a.n_pts, a.outside, a.dist, sl(a, 1)); }
+static int dist_field_score(const Args& a) { return mon_dist_field_score(a.field, a.spheres, a.n_spheres, a.ways, a.way_floats, a.n_traj, a.n_way, a.n_sub, a.tp,
+        a.min_clear, as_i32(sl(a, 1)), sl(a, 2), sl(a, 3), sl(a, 4)); }
+static int dist_field_match(const Args& a) { return mon_dist_field_match(a.field, a.pts, a.n_pts, a.mposes, a.n_h, a.pivots, a.mp, a.cost, as_i32(sl(a, 1)),
+        as_i32(sl(a, 2)), sl(a, 3)); }
+static int register_default(const Args& a) { return mon_register_default(a.field, a.rp); }
+static int dist_field_register(const Args& a) { return mon_dist_field_register(a.field, a.pts, a.n_pts, a.mposes, a.n_h, a.rp, a.poses_out, a.cost, as_i32(sl(a, 1)),
+        as_i32(sl(a, 2)), as_i32(sl(a, 3)), as_i32(sl(a, 4)), as_i32(sl(a, 13))); }
 
 // a call that must fail, on one line with its code and message (no exit); `change` edits a copy `a` of the good arguments
 #define ERR(route, change) do { Args a = good; change; const int rc_ = route(a); \
@@ -295,7 +325,31 @@ static void inference_part(const char* cfg_json, const mon_config& base, const u
     g0.sigma = o; g0.grad = o + 5 * 65536; g0.raw4 = o + 6 * 65536; g0.normal = o + 7 * 65536; g0.dist = o + 8 * 65536; g0.label = as_i32(o + 9 * 65536);
     g0.xyz_out = o + 11 * 65536; g0.rays_out = reinterpret_cast<mon_scene_ray*>(o + 12 * 65536); g0.opt = true;
     mon_lattice_component* const table = reinterpret_cast<mon_lattice_component*>(o + 10 * 65536);
-    const Args good = g0;
+    // the cost fields and the distance-field handles: two seeds, a multiplier and a field per cell of either lattice, a walk of three cells, a body of two
+    // spheres on two trajectories of three waypoints (positions, matrices), the scan = pts under three poses
+    const size_t n_big = 33 * 32 * 16;
+    const int32_t seeds[2] = { 0, 11 }, seeds_out[2] = { 0, 12 }, next4[4] = { 1, 2, -1, 0 }, next_cycle[4] = { 1, 0, -1, 0 }, next_bad[4] = { 1, 9, -1, 0 };
+    float cell_cost[12], cost_neg[12], fdist[12], fdist_nan[12];
+    for (int i = 0; i < 12; ++i) { cell_cost[i] = cost_neg[i] = 1.5f; fdist[i] = fdist_nan[i] = 0.1f * (float)i; }
+    cost_neg[5] = -1.f; fdist_nan[7] = NAN;
+    const std::vector<uint8_t> big_mask(n_big, 1); const std::vector<float> big_cost(n_big, 1.f), big_fdist(n_big, 0.25f);
+    const float step_zero[3] = { 0.3f, 0.f, 0.6f };
+    const float spheres[8] = { 0.f, 0.f, 0.f, 0.05f, 0.1f, 0.f, 0.f, 0.02f }, sphere_neg[8] = { 0.f, 0.f, 0.f, 0.05f, 0.1f, 0.f, 0.f, -1.f };
+    float ways3[2 * 3 * 3], ways16[2 * 3 * 16];
+    for (int k = 0; k < 6; ++k) { for (int a = 0; a < 3; ++a) ways3[3 * k + a] = -0.2f + 0.1f * (float)k;
+        std::memcpy(ways16 + 16 * k, g_Tow, 64); ways16[16 * k + 3] = -0.2f + 0.1f * (float)k; }
+    const mon_traj_score_params tp{ 0.5f, 0.01f, 0.1f }, tp_nan{ 0.5f, NAN, 0.1f };
+    float pose_nan3[3 * 16], pivots[9], pivots_nan[9]; std::memcpy(pose_nan3, poses3, 192); pose_nan3[16 + 3] = NAN;
+    for (int k = 0; k < 9; ++k) pivots[k] = pivots_nan[k] = 0.01f * (float)k;
+    pivots_nan[4] = INFINITY;
+    const mon_scan_match_params mp{ 0.1f, 0.5f }, mp_huber0{ 0.f, 0.5f }, mp_nan{ 0.1f, NAN };
+    int32_t path[8]; size_t n_path = 0; mon_dist_field* fh = nullptr; mon_dist_field_desc info; mon_register_params rp{};
+    g0.cell_cost = cell_cost; g0.seeds = seeds; g0.n_seeds = 2; g0.max_cost = INFINITY; g0.soft_radius = 0.5f; g0.soft_weight = 2.f; g0.cost = o + 16 * 65536;
+    g0.next = next4; g0.n_cells = 4; g0.start = 3; g0.path = path; g0.path_cap = 8; g0.n_path = &n_path;
+    g0.field = nullptr; g0.field_out = &fh; g0.fdist = fdist; g0.info = &info; g0.field_max = 0.5f; g0.outside = 0.5f;
+    g0.spheres = spheres; g0.n_spheres = 2; g0.ways = ways3; g0.way_floats = 3; g0.n_traj = 2; g0.n_way = 3; g0.n_sub = 2; g0.tp = &tp; g0.min_clear = o + 17 * 65536;
+    g0.mposes = poses3; g0.n_h = 3; g0.pivots = pivots; g0.mp = &mp; g0.rp = &rp; g0.poses_out = o + 18 * 65536;
+    Args good = g0;
 
     // ---- every route once, on both sides
     std::printf("== inference routes\n");
@@ -329,6 +383,40 @@ static void inference_part(const char* cfg_json, const mon_config& base, const u
         CALL(online_query_points(a)); CALL(online_query_lattice(a)); CALL(online_query_gradients(ag)); CALL(online_cast_normals(a));
         CALL(online_distance_lattice(a)); CALL(online_components_lattice(c1));
     }
+    // ---- the lattice routes that joined later: cost fields and device-resident distance fields.  A section of its own behind the others: a handle makes a
+    // stream, and the streams above keep their creation indices.  big: as above.  The stand-in runtime leaves every read-back 0: a cost field settles after
+    // its first batch of sweeps, and a registration ends in its first round (status 3 under the default min_inside, status 2 under min_inside 0)
+    for (int side = 0; side < 2; ++side) {
+        std::printf("-- lattice routes, side %d\n", side);
+        Args a = good; a.side = side; Args big = a; big.nx = 33; big.ny = 32; big.nz = 16; Args bare = a; bare.opt = false; bare.soft_weight = 0.f;
+        CALL(scene_paths_lattice(a)); CALL(scene_paths_lattice(bare)); CALL(scene_paths_lattice(big));
+        Args f = a;
+        CALL(scene_dist_field(a)); f.field = fh; CALL(dist_field_destroy(f));
+        CALL(scene_dist_field(big)); f.field = fh; CALL(dist_field_destroy(f));
+    }
+    {   std::printf("-- lattice routes, no side\n");
+        Args a = good; Args bare = a; bare.opt = false; bare.cell_cost = nullptr;
+        Args big = a; big.nx = 33; big.ny = 32; big.nz = 16; big.mask = big_mask.data(); big.cell_cost = big_cost.data(); big.fdist = big_fdist.data();
+        CALL(shortest_paths(a)); CALL(shortest_paths(bare)); CALL(shortest_paths(big)); CALL(lattice_path(a));
+        CALL(dist_field_create(a));
+        Args f = a; f.field = fh; Args fbare = f; fbare.opt = false; Args f16 = f; f16.ways = ways16; f16.way_floats = 16;
+        Args fnopiv = f; fnopiv.pivots = nullptr;
+        CALL(dist_field_info(f)); CALL(dist_field_read(f)); CALL(dist_field_sample(f)); CALL(dist_field_sample(fbare));
+        CALL(dist_field_score(f)); CALL(dist_field_score(f16)); CALL(dist_field_score(fbare));
+        CALL(dist_field_match(f)); CALL(dist_field_match(fbare)); CALL(dist_field_match(fnopiv));
+        CALL(register_default(f)); CALL(dist_field_register(f)); rp.min_inside = 0; CALL(dist_field_register(f)); CALL(dist_field_register(fbare));
+        CALL(dist_field_destroy(f));
+        CALL(dist_field_create(big)); f.field = fh; CALL(dist_field_read(f)); CALL(dist_field_sample(f)); CALL(dist_field_destroy(f));
+    }
+    {   std::printf("-- lattice routes, online manager\n");
+        Args a = good; Args f = a;
+        CALL(online_paths_lattice(a)); CALL(online_dist_field(a)); f.field = fh; CALL(dist_field_destroy(f));
+    }
+    // a handle for the refusals below, made untraced; its register parameters are the defaults again
+    hip_stub_trace(0); OK(mon_dist_field_create(0, fdist, 3, 2, 2, origin, step, &fh)); OK(mon_register_default(fh, &rp)); hip_stub_trace(1);
+    mon_dist_field* const fh_err = fh; good.field = fh_err;
+    mon_register_params rp_huber0 = rp, rp_up1 = rp, rp_lambda0 = rp, rp_tol = rp, rp_evals0 = rp, rp_inside = rp;
+    rp_huber0.huber = 0.f; rp_up1.lambda_up = 1.f; rp_lambda0.lambda0 = 0.f; rp_tol.tol_rot = -1.f; rp_evals0.max_evals = 0; rp_inside.min_inside = -1;
 
     // ---- the calls every route refuses, with code and message; the trace stays on: none of them may reach the device
     std::printf("== inference errors\n");
@@ -465,7 +553,47 @@ static void inference_part(const char* cfg_json, const mon_config& base, const u
     ONLINE_ERRS(online_distance_lattice); LATTICE_ERRS(online_distance_lattice); DISTANCE_ERRS(online_distance_lattice);
     ONLINE_ERRS(online_components_lattice); LATTICE_ERRS(online_components_lattice); COMPONENTS_ERRS(online_components_lattice);
     ERR(online_components_lattice, a.om = om_none; a.region = 2);
+    // the cost fields and the device-resident distance fields (good.field: a live handle)
+#define PATHS_ERRS(route) do { ERR(route, a.cost = nullptr); ERR(route, a.seeds = nullptr); ERR(route, a.conn = 7); ERR(route, a.max_cost = 0.f); ERR(route, a.n_seeds = 0); \
+        ERR(route, a.n_seeds = (1u << 22) + 1u); ERR(route, a.seeds = seeds_out); } while (0)
+#define SCENE_PATHS_ERRS(route) do { ERR(route, a.sigma_min = -1.f); ERR(route, a.clearance = -1.f); ERR(route, a.clearance = NAN); ERR(route, a.soft_weight = -1.f); \
+        ERR(route, a.soft_radius = 0.f); } while (0)
+#define FIELD_ERRS(route) do { ERR(route, a.field_out = nullptr); ERR(route, a.sigma_min = -1.f); ERR(route, a.field_max = 0.f); ERR(route, a.field_max = INFINITY); \
+        ERR(route, a.step = step_zero); } while (0)
+    ERR(shortest_paths, a.mask = nullptr); ERR(shortest_paths, a.step = nullptr); ERR(shortest_paths, a.nx = 0); ERR(shortest_paths, a.nx = 2048; a.ny = 2048; a.nz = 2);
+    ERR(shortest_paths, a.step = step_inf); PATHS_ERRS(shortest_paths); ERR(shortest_paths, a.cell_cost = cost_neg); ERR(shortest_paths, a.mask = nullptr; a.conn = 7);
+    OBJS_ERRS(scene_paths_lattice); LATTICE_ERRS(scene_paths_lattice); SCENE_PATHS_ERRS(scene_paths_lattice); PATHS_ERRS(scene_paths_lattice);
+    ERR(scene_paths_lattice, a.objs = with_null; a.conn = 7); ERR(scene_paths_lattice, a.objs = with_null; a.seeds = seeds_out);
+    ONLINE_ERRS(online_paths_lattice); LATTICE_ERRS(online_paths_lattice); SCENE_PATHS_ERRS(online_paths_lattice); PATHS_ERRS(online_paths_lattice);
+    ERR(online_paths_lattice, a.om = om_none; a.max_cost = 0.f);
+    ERR(lattice_path, a.next = nullptr); ERR(lattice_path, a.n_path = nullptr); ERR(lattice_path, a.path = nullptr); ERR(lattice_path, a.start = -1);
+    ERR(lattice_path, a.start = 4); ERR(lattice_path, a.next = next_cycle); ERR(lattice_path, a.next = next_bad);
+    ERR(dist_field_create, a.field_out = nullptr); ERR(dist_field_create, a.fdist = nullptr); ERR(dist_field_create, a.origin = nullptr);
+    ERR(dist_field_create, a.step = nullptr); ERR(dist_field_create, a.nx = 0); ERR(dist_field_create, a.nx = 2048; a.ny = 2048; a.nz = 2);
+    ERR(dist_field_create, a.origin = origin_nan); ERR(dist_field_create, a.step = step_inf); ERR(dist_field_create, a.step = step_zero);
+    ERR(dist_field_create, a.fdist = fdist_nan); ERR(dist_field_create, a.field_out = nullptr; a.nx = 0);
+    OBJS_ERRS(scene_dist_field); LATTICE_ERRS(scene_dist_field); FIELD_ERRS(scene_dist_field); ERR(scene_dist_field, a.objs = with_null; a.field_max = INFINITY);
+    ONLINE_ERRS(online_dist_field); LATTICE_ERRS(online_dist_field); FIELD_ERRS(online_dist_field); ERR(online_dist_field, a.om = om_none; a.field_max = 0.f);
+    ERR(dist_field_info, a.field = nullptr); ERR(dist_field_info, a.info = nullptr); ERR(dist_field_read, a.field = nullptr); ERR(dist_field_read, a.dist = nullptr);
+    ERR(dist_field_destroy, a.field = nullptr);
+    ERR(dist_field_sample, a.pts = nullptr); ERR(dist_field_sample, a.dist = nullptr); ERR(dist_field_sample, a.n_pts = 0); ERR(dist_field_sample, a.n_pts = (1u << 24) + 1u);
+    ERR(dist_field_sample, a.field = nullptr); ERR(dist_field_sample, a.field = nullptr; a.n_pts = 0);
+    ERR(dist_field_score, a.spheres = nullptr); ERR(dist_field_score, a.ways = nullptr); ERR(dist_field_score, a.tp = nullptr); ERR(dist_field_score, a.min_clear = nullptr);
+    ERR(dist_field_score, a.n_spheres = 0); ERR(dist_field_score, a.n_spheres = 33); ERR(dist_field_score, a.way_floats = 4); ERR(dist_field_score, a.n_way = 0);
+    ERR(dist_field_score, a.n_way = 257); ERR(dist_field_score, a.n_sub = 0); ERR(dist_field_score, a.n_sub = 17); ERR(dist_field_score, a.n_traj = 0);
+    ERR(dist_field_score, a.n_traj = 65537); ERR(dist_field_score, a.n_traj = 65536; a.n_way = 256; a.n_sub = 16); ERR(dist_field_score, a.spheres = sphere_neg);
+    ERR(dist_field_score, a.tp = &tp_nan); ERR(dist_field_score, a.field = nullptr); ERR(dist_field_score, a.field = nullptr; a.way_floats = 4);
+#define MATCH_ERRS(route) do { ERR(route, a.pts = nullptr); ERR(route, a.mposes = nullptr); ERR(route, a.cost = nullptr); ERR(route, a.n_pts = 0); \
+        ERR(route, a.n_pts = (1u << 20) + 1u); ERR(route, a.n_h = 0); ERR(route, a.mposes = many_poses.data(); a.n_h = 4097); ERR(route, a.n_pts = 1u << 20; a.n_h = 65); \
+        ERR(route, a.mposes = pose_nan3); ERR(route, a.field = nullptr); ERR(route, a.field = nullptr; a.n_h = 0); } while (0)
+    MATCH_ERRS(dist_field_match); ERR(dist_field_match, a.mp = nullptr); ERR(dist_field_match, a.pivots = pivots_nan); ERR(dist_field_match, a.mp = &mp_huber0);
+    ERR(dist_field_match, a.mp = &mp_nan); ERR(dist_field_match, a.field = nullptr; a.mp = &mp_huber0);
+    ERR(register_default, a.rp = nullptr); ERR(register_default, a.field = nullptr);
+    MATCH_ERRS(dist_field_register); ERR(dist_field_register, a.rp = nullptr); ERR(dist_field_register, a.poses_out = nullptr); ERR(dist_field_register, a.rp = &rp_huber0);
+    ERR(dist_field_register, a.rp = &rp_up1); ERR(dist_field_register, a.rp = &rp_lambda0); ERR(dist_field_register, a.rp = &rp_tol); ERR(dist_field_register, a.rp = &rp_evals0);
+    ERR(dist_field_register, a.rp = &rp_inside); ERR(dist_field_register, a.field = nullptr; a.rp = &rp_up1);
     hip_stub_trace(0);
+    OK(mon_dist_field_destroy(fh_err));
     // (the trace ends here: two object threads sign off on stdout in the order they happen to end)
     std::fflush(stdout); if (!std::freopen("/dev/null", "w", stdout)) std::exit(3);
     OK(mon_online_wait_threads_end(om)); OK(mon_online_destroy(om)); OK(mon_online_wait_threads_end(om_none)); OK(mon_online_destroy(om_none));
