@@ -476,6 +476,17 @@ __device__ __forceinline__ float scan_mul32(float v) {
     v *= dpp_f<0x142, 0xA>(1.f, v);
     return v;
 }
+// scan_mul32 in two floats (h + l): each step keeps its product's rounding error (fma) and the cross terms, and the sum is rounded once at the end.
+// A plain scan multiplies neighbours first; where they lie within 2^-12 of 1 every such product drops its second-order term, a bias that grows with
+// the number of tiles multiplied together (scene_device.h, kSceneLongSeq).
+__device__ __forceinline__ float scan_mul32_comp(float v) {
+    float h = v, l = 0.f;
+#define MON_COMP_STEP(CTRL, MASK) { const float bh = dpp_f<CTRL, MASK>(1.f, h), bl = dpp_f<CTRL, MASK>(0.f, l); const float p = h * bh; \
+        l = fmaf(h, bh, -p) + fmaf(h, bl, l * bh); h = p; }
+    MON_COMP_STEP(0x111, 0xF) MON_COMP_STEP(0x112, 0xF) MON_COMP_STEP(0x114, 0xF) MON_COMP_STEP(0x118, 0xF) MON_COMP_STEP(0x142, 0xA)
+#undef MON_COMP_STEP
+    return h + l;
+}
 __device__ __forceinline__ float scan_add32(float v) {
     v += dpp_f<0x111, 0xF>(0.f, v); v += dpp_f<0x112, 0xF>(0.f, v); v += dpp_f<0x114, 0xF>(0.f, v); v += dpp_f<0x118, 0xF>(0.f, v);
     v += dpp_f<0x142, 0xA>(0.f, v);

@@ -245,7 +245,7 @@ __device__ __forceinline__ float scene_composite_grad_walk(const SceneCompGradAr
             if (have) { const float4 v = a.attr[idx]; tv = a.t[idx]; al = v.x; c0 = v.y; c1 = v.z; c2 = v.w; qm = s_q[ac]; }
             const float Tb = s_T[blk];
             const float omv = 1.f - al;
-            const float sc = scan_mul32(omv), lo = sc * Tb, mid = lane_bcast(lo, 31);
+            const float sc = scene_scan_mul32(omv, n_tot), lo = sc * Tb, mid = lane_bcast(lo, 31);
             const float incl = lane < 32 ? lo : sc * mid;
             float T = lane_prev(incl, Tb); if (lane == 0) T = Tb; if (lane == 32) T = mid;
             const bool active = T >= kTransmittanceEps;

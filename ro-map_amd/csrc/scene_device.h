@@ -11,6 +11,13 @@
 
 namespace mon {
 
+// The longest merged sequence 16 lists can make.  Up to here a block's transmittance is k_fused_render's tile scan (scan_mul32), which fixes the bits of
+// every render of up to 16 objects and makes one object's list composite to its own render.  That scan loses the term a b of every product
+// (1 - a)(1 - b) with a, b < 2^-12, so T comes out low by an amount that grows with the sample count (3.4e-5 in opacity at 16 384 samples of alpha 1e-4);
+// longer sequences take scan_mul32_comp, whose block product is rounded once.  Wave-uniform: n_tot is the ray's.
+constexpr uint32_t kSceneLongSeq = 16u * kSceneListLen;
+__device__ __forceinline__ float scene_scan_mul32(float omv, uint32_t n_tot) { return n_tot > kSceneLongSeq ? scan_mul32_comp(omv) : scan_mul32(omv); }
+
 // One wavefront (= one workgroup) per ray.  The ray's non-empty lists are compacted into LDS in list order (s_id: compact -> list, s_c its count, s_tf / s_tl
 // its first / last t, s_w zeroed), then every sample's place in the merged order is counted: its index in its own list + the samples of each other list that
 // come before it (ties to the lower list index) -- the whole list or none where the t ranges do not overlap, a binary search of that list where they do.
@@ -90,7 +97,7 @@ __device__ __forceinline__ void scene_composite_walk(uint32_t ray, uint32_t cap,
             }
         }
         const float omv = 1.f - al;
-        const float sc = scan_mul32(omv), lo = sc * Tc, mid = lane_bcast(lo, 31);
+        const float sc = scene_scan_mul32(omv, n_tot), lo = sc * Tc, mid = lane_bcast(lo, 31);
         const float incl = lane < 32 ? lo : sc * mid;                              // (the second half-wave carries the first's transmittance)
         float T = lane_prev(incl, Tc); if (lane == 0) T = Tc; if (lane == 32) T = mid;
         const bool active = T >= kTransmittanceEps;
@@ -220,7 +227,7 @@ __device__ __forceinline__ void scene_composite_ray(const SceneCompGradArgs& a, 
         }
         if constexpr (GRAD) { if (lane == 0) s_T[blk] = Tc; }
         const float omv = 1.f - al;
-        const float sc = scan_mul32(omv), lo = sc * Tc, mid = lane_bcast(lo, 31);
+        const float sc = scene_scan_mul32(omv, n_tot), lo = sc * Tc, mid = lane_bcast(lo, 31);
         const float incl = lane < 32 ? lo : sc * mid;                              // (the second half-wave carries the first's transmittance)
         float T = lane_prev(incl, Tc); if (lane == 0) T = Tc; if (lane == 32) T = mid;
         const bool active = T >= kTransmittanceEps;

@@ -54,11 +54,12 @@ def scene_rays(sc, boxes, Twc, objects, n_rays=0, seed=1, iteration=0, use_depth
 
 
 # ------------------------------------------------------------------ the merged composite, its loss and its backward (fp64 numpy)
-def np_composite_grad(t, alpha, rgb, count, cstar, mstar, dstar, dn, w):
+def np_composite_grad(t, alpha, rgb, count, cstar, mstar, dstar, dn, w, amb_u=0.0):
     """Lists [K, P, 64] (rgb [K, P, 64, 3]) with count [K, P], merged by (t, list, slot) and composited front to back with the cut at the first T < EPS;
     targets cstar [P, 3], mstar [K, P], dstar [P], dn [P]; w = (w_rgb, w_mask, w_depth, huber).  Returns dict of l [P], W [K, P], D [P], dalpha [K, P, 64]
     (dL/dalpha of each list slot, the cut held), dc [K, P, 64, 3], amb [P] (the stopping point within 0.1 % of EPS, as np_composite flags it), ncut [P]
-    (merged samples in front of the cut) and ntot [P]."""
+    (merged samples in front of the cut) and ntot [P].  amb_u > 0 (the unit roundoff of the arithmetic under test) widens amb's window for long
+    sequences as np_composite's does: max(1e-3, 4 (i + 1) amb_u) at merged sample i."""
     w_rgb, w_mask, w_depth, hub = (float(v) for v in w)
     K, P = count.shape; N = K * 64
     slot = np.arange(64)
@@ -97,9 +98,59 @@ def np_composite_grad(t, alpha, rgb, count, cstar, mstar, dstar, dn, w):
     fin = np.isfinite(tt)
     pi = np.broadcast_to(np.arange(P)[:, None], (P, N))
     dalpha[pi[fin], kk[fin], ii[fin]] = dal[fin]; dc[pi[fin], kk[fin], ii[fin]] = dcm[fin]
-    amb = (np.abs(T / EPS - 1.0) < 1e-3).any(1) | (np.abs(incl / EPS - 1.0) < 1e-3).any(1)
+    win = np.maximum(1e-3, 4.0 * amb_u * (np.arange(N) + 1.0))
+    amb = (np.abs(T / EPS - 1.0) < win).any(1) | (np.abs(incl / EPS - 1.0) < win).any(1)
     return dict(l=l, W=W, D=D, dalpha=dalpha.transpose(1, 0, 2), dc=dc.transpose(1, 0, 2, 3), amb=amb, ncut=(active & fin).sum(1), ntot=fin.sum(1),
                 order_k=kk, order_fin=fin, active=active)
+
+
+def np_composite_grad_seq32(t, alpha, rgb, count, cstar, mstar, dstar, dn, w):
+    """The fp32 sequential twin of np_composite_grad: the same merged order and the same formulas with every product and sum taken front to back in
+    float32 (np.cumprod / np.cumsum with dtype=float32; the suffix sums back to front).  Its distance from np_composite_grad is the rounding error of one
+    plain fp32 evaluation of these lists: the yardstick for a kernel that reorders the sums.  Returns l, W, D, dalpha, dc as np_composite_grad does."""
+    f32 = np.float32
+    w_rgb, w_mask, w_depth, hub = (f32(v) for v in w)
+    K, P = count.shape; N = K * 64
+    slot = np.arange(64)
+    valid = slot[None, None, :] < count[..., None]
+    tt = np.where(valid, t, np.inf).transpose(1, 0, 2).reshape(P, N).astype(f32)
+    aa = np.where(valid, alpha, 0.0).transpose(1, 0, 2).reshape(P, N).astype(f32)
+    cc = np.where(valid[..., None], rgb, 0.0).transpose(1, 0, 2, 3).reshape(P, N, 3).astype(f32)
+    kk = np.broadcast_to(np.arange(K)[:, None, None], (K, P, 64)).transpose(1, 0, 2).reshape(P, N)
+    ii = np.broadcast_to(slot, (P, K, 64)).reshape(P, N)
+    order = np.lexsort((ii, kk, tt), axis=-1)
+    tt, aa, kk, ii = (np.take_along_axis(v, order, 1) for v in (tt, aa, kk, ii))
+    cc = np.take_along_axis(cc, order[..., None], 1)
+    fin = np.isfinite(tt); tz = np.where(fin, tt, f32(0))
+    om = f32(1) - aa
+    incl = np.cumprod(om, axis=1, dtype=f32)
+    T = np.concatenate([np.ones((P, 1), f32), incl[:, :-1]], 1)
+    active = np.logical_and.accumulate(T >= f32(EPS), axis=1)
+    wgt = np.where(active, aa * T, f32(0))
+    cs = np.asarray(cstar, f32); ms = np.asarray(mstar, f32); ds = np.asarray(dstar, f32); dnn = np.asarray(dn, f32)
+    last = lambda v: np.cumsum(v, axis=1, dtype=f32)[:, -1]                               # noqa: E731
+    r = np.stack([last(wgt * (cc[..., c] - cs[:, None, c])) for c in range(3)], 1)
+    pi = np.broadcast_to(np.arange(P)[:, None], (P, N))
+    wl = np.zeros((P, K, 64), f32); wl[pi[fin], kk[fin], ii[fin]] = wgt[fin]               # (a list's samples keep their slot order in the merged one)
+    W = np.cumsum(wl, axis=2, dtype=f32)[..., -1].T
+    D = last(wgt * tz) / dnn
+    M = ms.max(0)
+    dep_on = (w_depth != 0) & (M != 0) & (ds > 0)
+    lmask = np.cumsum((W - ms) ** 2, axis=0, dtype=f32)[-1]
+    l = w_rgb * M * last(r * r) / f32(3) + w_mask * lmask + np.where(dep_on, w_depth * huber(D - ds, hub).astype(f32), f32(0))
+    G = w_rgb * M[:, None] * f32(2) * r / f32(3)
+    GD = np.where(dep_on, w_depth * np.clip(D - ds, -hub, hub) / dnn, f32(0)).astype(f32)
+    qm = f32(2) * w_mask * (W - ms)
+    q = np.cumsum(G[:, None, :] * (cc - cs[:, None, :]), axis=2, dtype=f32)[..., -1] + GD[:, None] * tz + np.take_along_axis(qm.T, kk, 1)
+    wq = wgt * q
+    sfx = np.concatenate([np.cumsum(wq[:, ::-1], 1, dtype=f32)[:, ::-1][:, 1:], np.zeros((P, 1), f32)], 1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dal = np.where(active, T * q - np.where(om > 0, sfx / np.where(om > 0, om, f32(1)), f32(0)), f32(0))
+    dcm = wgt[..., None] * G[:, None, :]
+    dalpha = np.zeros((P, K, 64), f32); dc = np.zeros((P, K, 64, 3), f32)
+    dalpha[pi[fin], kk[fin], ii[fin]] = dal[fin]; dc[pi[fin], kk[fin], ii[fin]] = dcm[fin]
+    assert all(v.dtype == f32 for v in (l, W, D, dal, dcm)), [v.dtype for v in (l, W, D, dal, dcm)]
+    return dict(l=l, W=W, D=D, dalpha=dalpha.transpose(1, 0, 2), dc=dc.transpose(1, 0, 2, 3))
 
 
 def lists_from_raw(raw, t, hit):

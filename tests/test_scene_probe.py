@@ -62,9 +62,10 @@ def setup(pkg, ss, scene, trained, overlap_view):       # noqa: F811
     return dict(sc=sc, objs=objs, objs3=objs3, pair=(i, j), v=v, rect=rect, pose=pose, q=q, base=base)
 
 
-def np_first_hit(t, alpha, count):
+def np_first_hit(t, alpha, count, with_index=False):
     """NumPy reference of the hit outputs: lists [K, P, 64] with count [K, P], merged by (t, list, slot); the transmittance after every merged sample in
-    fp64.  Returns per ray: has a crossing 1 - T_{i+1} > 0.5, the fp32 t of the first one, its list, and near = some T_{i+1} within TIE (relative) of 0.5."""
+    fp64.  Returns per ray: has a crossing 1 - T_{i+1} > 0.5, the fp32 t of the first one, its list, and near = some T_{i+1} within TIE (relative) of 0.5;
+    with_index: also the crossing's place i in the merged order (0 without a crossing)."""
     K, P = count.shape
     slot = np.arange(64)
     valid = slot[None, None, :] < count[..., None]
@@ -79,7 +80,8 @@ def np_first_hit(t, alpha, count):
     cross = vv & (1.0 - incl > 0.5)
     has = cross.any(1); first = cross.argmax(1); r = np.arange(P)
     near = (vv & (np.abs(incl / 0.5 - 1.0) < TIE)).any(1)
-    return has, np.where(has, tt[r, first], np.float32(0)).astype(np.float32), np.where(has, kk[r, first], -1).astype(np.int32), near
+    out = has, np.where(has, tt[r, first], np.float32(0)).astype(np.float32), np.where(has, kk[r, first], -1).astype(np.int32), near
+    return out + (np.where(has, first, 0),) if with_index else out
 
 
 def _check_hits(out, t, alpha, count, dn, cap=0.01):

@@ -93,10 +93,11 @@ def _dn(sc, rect):
     return np.sqrt(a * a + b * b + np.float32(1.0)).reshape(-1)
 
 
-def np_composite(t, alpha, rgb, count, dn):
+def np_composite(t, alpha, rgb, count, dn, amb_u=0.0):
     """numpy restatement (float64) of the merge-composite: lists [K, P, 64] (rgb [K, P, 64, 3]) with count [K, P]; merged by (t, list, slot), front to
     back, stopped at the first sample with T < EPS.  Returns rgb [P, 3], depth, opacity, instance, per-list weight sums [P, K] and a flag per ray whose
-    stopping point lies within 0.1 % of EPS (float32 and float64 may stop one sample apart there)."""
+    stopping point lies within 0.1 % of EPS (float32 and float64 may stop one sample apart there).  amb_u > 0 (the unit roundoff of the arithmetic under
+    test) widens that window for long sequences: max(1e-3, 4 (i + 1) amb_u) at merged sample i, the forward bound of a product of i + 1 rounded factors."""
     K, P = count.shape
     slot = np.arange(64)
     valid = slot[None, None, :] < count[..., None]
@@ -121,7 +122,8 @@ def np_composite(t, alpha, rgb, count, dn):
     depth = np.where(op > 0.5, dep / dn, 0.0)
     wk = np.stack([(w * (kk == k)).sum(1) for k in range(K)], 1)
     inst = np.where(op > 0.5, wk.argmax(1), -1)
-    ambiguous = (np.abs(T / EPS - 1.0) < 1e-3).any(1) | (np.abs(incl / EPS - 1.0) < 1e-3).any(1)
+    win = np.maximum(1e-3, 4.0 * amb_u * (np.arange(N) + 1.0))
+    ambiguous = (np.abs(T / EPS - 1.0) < win).any(1) | (np.abs(incl / EPS - 1.0) < win).any(1)
     return out_rgb, depth, op, inst, wk, ambiguous
 
 
