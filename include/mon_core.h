@@ -571,6 +571,57 @@ int mon_dist_field_match(mon_dist_field* field, const float* points, size_t n, c
 int mon_register_default(mon_dist_field* field, mon_register_params* p);
 int mon_dist_field_register(mon_dist_field* field, const float* points, size_t n, const float* poses16_in, size_t n_poses, const mon_register_params* p,
                             float* poses16_out, float* cost, int32_t* n_inside, int32_t* n_inlier, int32_t* evals, int32_t* status, int32_t* best);
+/* Ray tracing against a device-resident distance field: what range scan would a sensor at this pose see, is there a line of sight between two points, and
+ * how well do predicted ranges under several thousand pose hypotheses agree with measured ones -- the forward direction of the scan matching above, for a
+ * consumer that holds only a mon_dist_field (the reference has no such call; opt-in, new, read-only; no existing call changes its bits).  The rays are
+ * sphere-traced: the sampled distance bounds the free way ahead.  The field is best a SIGNED distance (mon_dist_field_create).  Every operation below is one
+ * separately rounded fp32 operation (fl); nothing is contracted.  No atomics: equal arguments give equal bits, and a ray's row does not depend on the other
+ * rays or poses of the call.
+ * Inputs.  rays[n][6] = origin o and direction u in the sensor frame; the values are not checked.  The direction is used as given and t is in units of its
+ *   length: pass unit directions.  poses16[H][16] as in mon_dist_field_match: the twelve entries used are finite, the last row is ignored.  poses16 may be
+ *   NULL: then n_poses must be 1 and the rays are world rays used as given, with no arithmetic.  1 <= n <= 2^20, 1 <= H <= 4 096; n * H <= 2^22 for
+ *   mon_dist_field_trace, whose outputs are [H][n] and come home; n * H <= 2^24 for mon_dist_field_beam_score, which brings home H words per output.
+ *   params = { t_min, t_max, eps, step_min, relax, step_outside, max_steps }: all finite, t_min <= t_max, step_min > 0, step_outside > 0, 0 < relax <= 1,
+ *   1 <= max_steps <= 4 096.
+ * Per pose h and ray r.
+ *   1. a = the centre formula of way_floats 16 above applied to poses16[h] and o.  w_x = fl(fl(fl(M00 u_x) + fl(M01 u_y)) + fl(M02 u_z)), w_y and w_z
+ *      likewise from rows 1 and 2: the translation is not added.
+ *   2. point(t) = fl(a + fl(t * w)) per component.
+ *   3. Start with t = t_min, k = 0, seen_inside = false.  Repeat:
+ *        if !(t <= t_max): status 1 (passed), range = t_max; end.
+ *        if k == max_steps: status 2 (out of steps), range = t; end.
+ *        sample D at point(t) by the rule above: d; k += 1.
+ *        outside the lattice, seen_inside set: status 3 (left: the lattice is convex), range = t_prev; end.
+ *        outside, seen_inside clear: t = fl(t + step_outside) and continue; nothing is remembered as previous.
+ *        inside: seen_inside = true.  If d <= eps: status 0 (hit); without a previous inside sample range = t, otherwise
+ *          range = fl(t_prev + fl(fl(t - t_prev) * fl(fl(d_prev - eps) / fl(d_prev - d)))),
+ *        the crossing of the level eps between the last two samples (both differences are positive, so nothing needs a clamp); end.
+ *        Else t_prev = t, d_prev = d, t = fl(t + fmaxf(fl(relax * d), step_min)).
+ *   4. steps = k.  normal3 = the gradient of D by the sample rule at point(range) on a hit; 0 0 0 on any other status or when that point is outside.
+ *   Trilinear interpolation of a 1-Lipschitz field has a gradient norm of up to sqrt 3, so relax <= 0.57 cannot step through a surface; a larger relax is
+ *   for fields known to be smoother.
+ * mon_trace_default: with c the smallest |step| among the axes of more than one cell (1 without such an axis): t_min 0, t_max = sqrtf of the left fold over
+ *   x, y, z of fl(e_a e_a), e_a = fl((float)(n_a - 1) * |s_a|) (the lattice's diagonal), eps = c / 8, step_min = c / 4, relax 0.5, step_outside = c / 2,
+ *   max_steps 256.
+ * mon_dist_field_trace: range[H][n]; status[H][n], steps[H][n] and normal3[H][n][3], each of which may be NULL (what was not asked for is neither computed
+ *   beyond the march nor copied home).  Rays and poses are uploaded per call; the outputs come home with one synchronisation.
+ * mon_dist_field_beam_score: measured[n], a NaN marks a beam without a return: its term is +0 and it is not valid.  Per pose and valid beam
+ *   e = fl(range - measured), range exactly what mon_dist_field_trace returns for that pose and ray, whatever its status; rho and the Huber split on
+ *   m = |e| are step 5 of the scan matching above with beam = { huber }.  cost[H] is ONE pairwise tree over the beams in ascending index, padded with +0 to
+ *   a power of two; -0 is returned as +0.  n_valid[H] and n_hit[H] (the valid beams with status 0) are integer counts; either may be NULL.  The ranges stay
+ *   on the device.
+ * Returns:
+ *   MON_ERR_ARG    field, rays, params, range, measured, beam or cost NULL; n, H or n * H outside their limits; poses16 NULL with H != 1; a used pose entry
+ *                  that is not finite; t_min, t_max, eps, step_min, relax or step_outside not finite; t_min > t_max; step_min <= 0 or step_outside <= 0;
+ *                  relax <= 0 or > 1; max_steps outside 1 .. 4 096; huber <= 0 or NaN (+inf is allowed) -- all before any device work, the outputs
+ *                  untouched; the handle is judged last */
+typedef struct mon_trace_params { float t_min, t_max, eps, step_min, relax, step_outside; int32_t max_steps; } mon_trace_params;   /* 28 bytes */
+typedef struct mon_beam_params { float huber; } mon_beam_params;
+int mon_trace_default(mon_dist_field* field, mon_trace_params* p);
+int mon_dist_field_trace(mon_dist_field* field, const float* rays, size_t n, const float* poses16, size_t n_poses, const mon_trace_params* p,
+                         float* range, int32_t* status, int32_t* steps, float* normal3);
+int mon_dist_field_beam_score(mon_dist_field* field, const float* rays, size_t n, const float* measured, const float* poses16, size_t n_poses,
+                              const mon_trace_params* p, const mon_beam_params* b, float* cost, int32_t* n_valid, int32_t* n_hit);
 /* Object pose refinement through the trained field (iNeRF-style): align the object with observed frames by following the gradient of a photometric,
  * silhouette and depth error with respect to the 6-DoF pose Tow.
  * Objective.  obs names frames of the object's dataset (FrameId) and pixel boxes inside them; the target of a pixel is that frame's rgb c*, its instance map

@@ -16,7 +16,7 @@ from .binding import (MonConfig, MonBBox, MonError, Dataset, ObjectNeRF, default
                       distance_transform, scene_distance_lattice,
                       label_components, scene_components_lattice, LATTICE_COMPONENT_DTYPE,
                       shortest_paths, scene_paths_lattice, lattice_path, paths_stats,
-                      DistField, DistFieldDesc, TrajScoreParams, ScanMatchParams, RegisterParams, dist_field_create, scene_dist_field,
+                      DistField, DistFieldDesc, TrajScoreParams, ScanMatchParams, RegisterParams, TraceParams, BeamParams, dist_field_create, scene_dist_field,
                       query_object_gradients, query_scene_gradients, query_scene_lattice_gradients, cast_scene_normals, scene_gradient_rows,
                       WindowParams, window_default, window_frames, scene_window_loss, scene_refine_window,
                       CheckpointInfo, checkpoint_info, checkpoint_timing, MON_LOAD_BOXES,

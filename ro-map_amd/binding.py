@@ -99,6 +99,18 @@ class RegisterParams(C.Structure):
                 ("lambda_down", C.c_float), ("lambda_max", C.c_float), ("tol_trans", C.c_float), ("tol_rot", C.c_float), ("min_inside", C.c_int32)]
 
 
+class TraceParams(C.Structure):
+    """mon_trace_params (include/mon_core.h): the march of mon_dist_field_trace: its range, the hit level, the least step, the step's share of the sampled
+    distance, the step before the lattice is entered, and the step budget."""
+    _fields_ = [("t_min", C.c_float), ("t_max", C.c_float), ("eps", C.c_float), ("step_min", C.c_float), ("relax", C.c_float), ("step_outside", C.c_float),
+                ("max_steps", C.c_int32)]
+
+
+class BeamParams(C.Structure):
+    """mon_beam_params (include/mon_core.h): the Huber threshold on |range - measured| (+inf: plain least squares)."""
+    _fields_ = [("huber", C.c_float)]
+
+
 class RelocResult(C.Structure):
     """mon_reloc_result (include/mon_core.h): which candidate won, whether its refined pose did, and the scores S[0], S[best], F[winner]."""
     _fields_ = [("best_candidate", C.c_uint32), ("refined", C.c_uint32), ("score_candidate0", C.c_float), ("score_best_candidate", C.c_float),
@@ -268,6 +280,11 @@ _SIGS = {
     "mon_register_default": (C.c_int, [C.c_void_p, C.POINTER(RegisterParams)]),
     "mon_dist_field_register": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(RegisterParams), C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_trace_default": (C.c_int, [C.c_void_p, C.POINTER(TraceParams)]),
+    "mon_dist_field_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(TraceParams), C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p]),
+    "mon_dist_field_beam_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TraceParams),
+            C.POINTER(BeamParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_object_query_gradients": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_scene_query_gradients": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1439,6 +1456,51 @@ class DistField:
                                              _p(out["n_inlier"]), _p(out["evals"]), _p(out["status"]), C.byref(best)))
         out["best"] = int(best.value)
         return out
+
+    def trace_default(self):
+        """mon_trace_default -> TraceParams for this field"""
+        p = TraceParams(); _check(lib().mon_trace_default(self.h, C.byref(p))); return p
+
+    def _trace_args(self, rays, poses, params):
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        T = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
+        prm = TraceParams.from_buffer_copy(params if params is not None else self.trace_default())
+        return r, T, (1 if T is None else T.shape[0]), prm
+
+    def trace(self, rays, poses=None, params=None, normals=False, status=True, steps=True):
+        """mon_dist_field_trace.  rays (n, 6) = origin and unit direction in the sensor frame; poses (H, 16) or (H, 4, 4) row-major, or None for world rays.
+        params: TraceParams (default: trace_default()).  -> a dict with range (H, n) and, unless turned off, status and steps (H, n) int32 (status 0: hit,
+        1: passed t_max, 2: out of steps, 3: left the lattice), and with normals normal (H, n, 3)."""
+        r, T, H, prm = self._trace_args(rays, poses, params); n = r.shape[0]
+        out = {"range": np.empty((H, n), np.float32), "status": np.empty((H, n), np.int32) if status else None,
+               "steps": np.empty((H, n), np.int32) if steps else None, "normal": np.empty((H, n, 3), np.float32) if normals else None}
+        _check(lib().mon_dist_field_trace(self.h, _p(r), n, _p(T), H, C.byref(prm), _p(out["range"]), _p(out["status"]), _p(out["steps"]), _p(out["normal"])))
+        return {k: v for k, v in out.items() if v is not None}
+
+    def beam_score(self, rays, measured, poses, params=None, huber=np.inf):
+        """mon_dist_field_beam_score.  measured (n,): the measured range of every beam, NaN for a beam without a return; rays, poses and params as trace
+        takes them.  -> a dict with cost (H,), the Huber cost of range - measured over the valid beams, and n_valid and n_hit (H,) int32."""
+        r, T, H, prm = self._trace_args(rays, poses, params); n = r.shape[0]
+        z = np.ascontiguousarray(measured, np.float32).reshape(-1); assert z.shape[0] == n, "one measured range per ray"
+        b = BeamParams(float(huber))
+        out = {"cost": np.empty(H, np.float32), "n_valid": np.empty(H, np.int32), "n_hit": np.empty(H, np.int32)}
+        _check(lib().mon_dist_field_beam_score(self.h, _p(r), n, _p(z), _p(T), H, C.byref(prm), C.byref(b), _p(out["cost"]), _p(out["n_valid"]),
+                                               _p(out["n_hit"])))
+        return out
+
+    def line_of_sight(self, a, b, params=None):
+        """Is the segment from a to b free?  a, b (3,) or (m, 3) world points.  A host-side helper over trace: the unit direction and t_max = |b - a| are
+        formed in float64 and rounded; one call per pair, since t_max is the call's.  -> bool, or (m,) bool: the ray passed t_max (status 1)."""
+        a64 = np.asarray(a, np.float64).reshape(-1, 3); b64 = np.asarray(b, np.float64).reshape(-1, 3); assert a64.shape == b64.shape
+        prm = TraceParams.from_buffer_copy(params if params is not None else self.trace_default())
+        free = np.zeros(a64.shape[0], bool); t_min = prm.t_min
+        for m in range(a64.shape[0]):
+            v = b64[m] - a64[m]; length = float(np.linalg.norm(v))
+            u = v / length if length > 0.0 else np.zeros(3)
+            prm.t_max = length; prm.t_min = min(t_min, prm.t_max)
+            got = self.trace(np.concatenate([a64[m], u]).astype(np.float32), None, prm, steps=False)
+            free[m] = got["status"][0, 0] == 1
+        return bool(free[0]) if np.ndim(a) == 1 else free
 
 
 def dist_field_create(dist, origin, step, device=0):

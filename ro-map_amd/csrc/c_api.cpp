@@ -231,6 +231,15 @@ int mon_dist_field_match(mon_dist_field* field, const float* points, size_t n, c
         const mon_scan_match_params* params, float* cost, int32_t* n_inside, int32_t* n_inlier, float* normal) {
     return dist_field_match(field ? field->f : nullptr, points, n, poses16, n_poses, pivots, params, cost, n_inside, n_inlier, normal);
 }
+int mon_trace_default(mon_dist_field* field, mon_trace_params* p) { return dist_field_trace_default(field ? field->f : nullptr, p); }
+int mon_dist_field_trace(mon_dist_field* field, const float* rays, size_t n, const float* poses16, size_t n_poses, const mon_trace_params* p, float* range,
+        int32_t* status, int32_t* steps, float* normal3) {
+    return dist_field_trace(field ? field->f : nullptr, rays, n, poses16, n_poses, p, range, status, steps, normal3);
+}
+int mon_dist_field_beam_score(mon_dist_field* field, const float* rays, size_t n, const float* measured, const float* poses16, size_t n_poses,
+        const mon_trace_params* p, const mon_beam_params* b, float* cost, int32_t* n_valid, int32_t* n_hit) {
+    return dist_field_beam_score(field ? field->f : nullptr, rays, n, measured, poses16, n_poses, p, b, cost, n_valid, n_hit);
+}
 int mon_register_default(mon_dist_field* field, mon_register_params* p) { return dist_field_register_default(field ? field->f : nullptr, p); }
 int mon_dist_field_register(mon_dist_field* field, const float* points, size_t n, const float* poses16_in, size_t n_poses, const mon_register_params* p,
         float* poses16_out, float* cost, int32_t* n_inside, int32_t* n_inlier, int32_t* evals, int32_t* status, int32_t* best) {

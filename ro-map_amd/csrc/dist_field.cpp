@@ -368,4 +368,106 @@ int dist_field_register(DistField* field, const float* points, size_t n, const f
     return MON_OK;
 }
 
+// ---- ray tracing.  What the two calls ask of the rays, the poses and the march, without a device
+constexpr size_t kTraceMaxRays = (size_t)1 << 20, kTraceMaxPoses = 4096, kTraceMaxHome = (size_t)1 << 22, kTraceMaxBeams = (size_t)1 << 24;
+constexpr int32_t kTraceMaxSteps = 4096;
+static int trace_check(const char* what, size_t n, const float* poses16, size_t H, size_t max_work, const mon_trace_params* p) {
+    if (n == 0 || n > kTraceMaxRays) { set_error("%s: %zu rays (1 to %zu)", what, n, kTraceMaxRays); return MON_ERR_ARG; }
+    if (H == 0 || H > kTraceMaxPoses) { set_error("%s: %zu poses (1 to %zu)", what, H, kTraceMaxPoses); return MON_ERR_ARG; }
+    if (n * H > max_work) { set_error("%s: %zu rays under %zu poses (at most %zu pairs in all)", what, n, H, max_work); return MON_ERR_ARG; }
+    if (!poses16 && H != 1) { set_error("%s: %zu poses without poses16 (world rays are one pose)", what, H); return MON_ERR_ARG; }
+    for (size_t h = 0; poses16 && h < H; ++h)
+        for (int k = 0; k < 12; ++k) if (!std::isfinite(poses16[16 * h + k])) { set_error("%s: pose %zu is not finite", what, h); return MON_ERR_ARG; }
+    if (!std::isfinite(p->t_min) || !std::isfinite(p->t_max) || !std::isfinite(p->eps) || !std::isfinite(p->step_min) || !std::isfinite(p->relax) ||
+        !std::isfinite(p->step_outside)) { set_error("%s: a march parameter is not finite", what); return MON_ERR_ARG; }
+    if (p->t_min > p->t_max) { set_error("%s: t_min %g above t_max %g", what, (double)p->t_min, (double)p->t_max); return MON_ERR_ARG; }
+    if (!(p->step_min > 0.f) || !(p->step_outside > 0.f)) {
+        set_error("%s: step_min %g, step_outside %g (each above 0)", what, (double)p->step_min, (double)p->step_outside); return MON_ERR_ARG; }
+    if (!(p->relax > 0.f) || p->relax > 1.f) { set_error("%s: relax %g (above 0, at most 1)", what, (double)p->relax); return MON_ERR_ARG; }
+    if (p->max_steps < 1 || p->max_steps > kTraceMaxSteps) { set_error("%s: max_steps %d (1 to %d)", what, p->max_steps, kTraceMaxSteps); return MON_ERR_ARG; }
+    return MON_OK;
+}
+int dist_field_trace_default(DistField* f, mon_trace_params* p) {
+    REQUIRE_ARG("trace_default", p, "p"); REQUIRE_ARG("trace_default", f, "field");
+    std::lock_guard<std::mutex> l(f->mu);
+    const int dims[3] = { f->g.nx, f->g.ny, f->g.nz };
+    float c = INFINITY, sum = 0.f;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] > 1) c = std::min(c, std::fabs(f->g.step[a]));
+        const float e = (float)(dims[a] - 1) * std::fabs(f->g.step[a]);
+        const float ee = e * e;
+        sum = a == 0 ? ee : sum + ee;
+    }
+    if (!(c < INFINITY)) c = 1.f;
+    *p = mon_trace_params{ 0.f, std::sqrt(sum), c / 8.f, c / 4.f, 0.5f, c / 2.f, 256 };
+    return MON_OK;
+}
+// The device side of both calls, on the locked handle: the rays, then the poses, uploaded; the march's arguments but for its outputs
+static int trace_upload(FieldCall& c, const float* rays, size_t n, const float* poses16, size_t H, size_t at_pose, const mon_trace_params* p,
+                        FieldTraceArgs& a) {
+    DistField& f = *c.f;
+    HIPCHECK(hipMemcpyAsync(f.in.p, rays, 24 * n, hipMemcpyHostToDevice, f.s));
+    if (poses16) HIPCHECK(hipMemcpyAsync(f.in.p + at_pose, poses16, 64 * H, hipMemcpyHostToDevice, f.s));
+    a = FieldTraceArgs{};
+    a.rays = f.in.p; a.poses = poses16 ? f.in.p + at_pose : nullptr; a.n = (uint32_t)n; a.n_pose = (uint32_t)H;
+    a.t_min = p->t_min; a.t_max = p->t_max; a.eps = p->eps; a.step_min = p->step_min; a.relax = p->relax; a.step_outside = p->step_outside;
+    a.max_steps = (uint32_t)p->max_steps;
+    return MON_OK;
+}
+// out: range | status | steps | normal ([H][n] each, the normal three floats per ray), those asked for
+int dist_field_trace(DistField* field, const float* rays, size_t n, const float* poses16, size_t H, const mon_trace_params* p, float* range, int32_t* status,
+                     int32_t* steps, float* normal3) {
+    const char* what = "dist_field_trace";
+    REQUIRE_ARG(what, rays, "rays"); REQUIRE_ARG(what, p, "params"); REQUIRE_ARG(what, range, "range");
+    { const int rc = trace_check(what, n, poses16, H, kTraceMaxHome, p); if (rc) return rc; }
+    FieldCall c; { const int rc = c.enter(what, field); if (rc) return rc; }
+    DistField& f = *c.f;
+    const size_t m = n * H, at_pose = round4(6 * n);
+    const size_t r_status = m, r_steps = r_status + (status ? m : 0), r_normal = r_steps + (steps ? m : 0), n_out = r_normal + (normal3 ? 3 * m : 0);
+    { const int rc = c.room(at_pose + 16 * H, n_out, n_out); if (rc) return rc; }
+    FieldTraceArgs a;
+    { const int rc = trace_upload(c, rays, n, poses16, H, at_pose, p, a); if (rc) return rc; }
+    float* o = f.out.p;
+    a.stride = (uint32_t)n; a.range = o; a.status = status ? reinterpret_cast<int32_t*>(o + r_status) : nullptr;
+    a.steps = steps ? reinterpret_cast<int32_t*>(o + r_steps) : nullptr; a.normal = normal3 ? o + r_normal : nullptr;
+    launch_field_trace(f.s, f.cells, f.g, a);
+    { const int rc = c.home(f.out.p, n_out); if (rc) return rc; }
+    const float* h = f.h_out.p;
+    std::memcpy(range, h, 4 * m);
+    if (status) std::memcpy(status, h + r_status, 4 * m);
+    if (steps) std::memcpy(steps, h + r_steps, 4 * m);
+    if (normal3) std::memcpy(normal3, h + r_normal, 12 * m);
+    return MON_OK;
+}
+// in: rays | measured | poses.  out: range | status ([H][stride] each, stride = n rounded up to a multiple of 4) | the fold's scratch | rows [H][4]; only
+// the rows come home
+int dist_field_beam_score(DistField* field, const float* rays, size_t n, const float* measured, const float* poses16, size_t H, const mon_trace_params* p,
+                          const mon_beam_params* b, float* cost, int32_t* n_valid, int32_t* n_hit) {
+    const char* what = "dist_field_beam_score";
+    REQUIRE_ARG(what, rays, "rays"); REQUIRE_ARG(what, measured, "measured"); REQUIRE_ARG(what, p, "params"); REQUIRE_ARG(what, b, "beam");
+    REQUIRE_ARG(what, cost, "cost");
+    { const int rc = trace_check(what, n, poses16, H, kTraceMaxBeams, p); if (rc) return rc; }
+    if (!(b->huber > 0.f)) { set_error("%s: huber %g (above 0; +inf is allowed)", what, (double)b->huber); return MON_ERR_ARG; }
+    FieldCall c; { const int rc = c.enter(what, field); if (rc) return rc; }
+    DistField& f = *c.f;
+    const size_t stride = round4(n), at_meas = round4(6 * n), at_pose = at_meas + stride;
+    const size_t r_status = H * stride, r_part = 2 * r_status, r_rows = r_part + round4(beam_score_scratch((uint32_t)n, (uint32_t)H));
+    { const int rc = c.room(at_pose + 16 * H, r_rows + kScanMatchLite * H, kScanMatchLite * H); if (rc) return rc; }
+    FieldTraceArgs a;
+    { const int rc = trace_upload(c, rays, n, poses16, H, at_pose, p, a); if (rc) return rc; }
+    HIPCHECK(hipMemcpyAsync(f.in.p + at_meas, measured, 4 * n, hipMemcpyHostToDevice, f.s));
+    float* o = f.out.p;
+    a.stride = (uint32_t)stride; a.range = o; a.status = reinterpret_cast<int32_t*>(o + r_status);
+    launch_field_trace(f.s, f.cells, f.g, a);
+    launch_beam_score(f.s, a.range, a.status, f.in.p + at_meas, (uint32_t)n, (uint32_t)H, (uint32_t)stride, b->huber, o + r_part, o + r_rows);
+    { const int rc = c.home(o + r_rows, kScanMatchLite * H); if (rc) return rc; }
+    for (size_t h = 0; h < H; ++h) {
+        const float* row = f.h_out.p + kScanMatchLite * h;
+        cost[h] = row[0];
+        if (n_valid) n_valid[h] = (int32_t)row[1];
+        if (n_hit) n_hit[h] = (int32_t)row[2];
+    }
+    return MON_OK;
+}
+
 }  // namespace mon

@@ -126,16 +126,20 @@ void launch_scan_match(hipStream_t s, const float* D, const Lattice& g, const Sc
     const dim3 grid(n_in, a.n_pose);
     if (normal) hipLaunchKernelGGL((k_scan_match<true>), grid, dim3(256), 0, s, F, a, scratch);
     else hipLaunchKernelGGL((k_scan_match<false>), grid, dim3(256), 0, s, F, a, scratch);
+    // the whole row, or without the normal equations the cost, the two counts and one 0
+    launch_scan_fold(s, scratch, n_in, a.n_pose, rows, normal ? 0u : (uint32_t)(kSmA + kSmB), normal ? kScanMatchRow : kScanMatchLite);
+}
+// scratch[n_pose][n_in][32], the part rows of a launch (scan_match_scratch's layout: the rows of a first fold go behind them) -> rows[n_pose][width], the
+// columns first .. first + width - 1 of each pose's folded row
+void launch_scan_fold(hipStream_t s, float* scratch, uint32_t n_in, uint32_t n_pose, float* rows, uint32_t first, uint32_t width) {
     const float* in = scratch;
     if (n_in > kScanMatchFold) {                                                    // (once: n <= 2^20 gives at most 1 024 chunks, 16 rows after it)
-        float* mid = scratch + (size_t)a.n_pose * kScanMatchRow * n_in;
+        float* mid = scratch + (size_t)n_pose * kScanMatchRow * n_in;
         const uint32_t n_out = ceil_div(n_in, kScanMatchFold);
-        hipLaunchKernelGGL(k_scan_fold, dim3(n_out, a.n_pose), dim3(256), 0, s, in, n_in, mid, 0u, kScanMatchRow);
+        hipLaunchKernelGGL(k_scan_fold, dim3(n_out, n_pose), dim3(256), 0, s, in, n_in, mid, 0u, kScanMatchRow);
         in = mid; n_in = n_out;
     }
-    // the whole row, or without the normal equations the cost, the two counts and one 0
-    hipLaunchKernelGGL(k_scan_fold, dim3(1, a.n_pose), dim3(256), 0, s, in, n_in, rows, normal ? 0u : (uint32_t)(kSmA + kSmB),
-                       normal ? kScanMatchRow : kScanMatchLite);
+    hipLaunchKernelGGL(k_scan_fold, dim3(1, n_pose), dim3(256), 0, s, in, n_in, rows, first, width);
 }
 
 }  // namespace mon

@@ -430,6 +430,18 @@ struct ScanMatchArgs { const float* points; const float* poses; const float* piv
 constexpr uint32_t kScanMatchChunk = 1024, kScanMatchFold = 64, kScanMatchRow = 32, kScanMatchLite = 4;
 size_t scan_match_scratch(uint32_t n, uint32_t n_pose);
 void launch_scan_match(hipStream_t s, const float* D, const Lattice& g, const ScanMatchArgs& a, bool normal, float* scratch, float* rows);
+// launch_scan_fold: the part rows scratch[n_pose][n_in][32] of such a launch folded by k_scan_fold to rows[n_pose][width], columns first .. of each row.
+void launch_scan_fold(hipStream_t s, float* scratch, uint32_t n_in, uint32_t n_pose, float* rows, uint32_t first, uint32_t width);
+// Ray tracing against a distance field (mon_dist_field_trace / _beam_score; kernels_field_trace.hip).  launch_field_trace: n rays [n][6] (8-byte aligned)
+// under n_pose poses (nullptr: one pose, world rays) marched by the header's rule; range, status, steps at [h * stride + ray], normal at 3 x that; status,
+// steps and normal may be nullptr.  launch_beam_score: rows[n_pose][4] = cost, n_valid, n_hit (counts as exact floats), 0 from the ranges and statuses such a
+// launch left at a stride that is a multiple of 4; range, status and measured 16-byte aligned; scratch: beam_score_scratch(n, n_pose) floats.
+struct FieldTraceArgs { const float* rays; const float* poses; uint32_t n, n_pose, stride; float t_min, t_max, eps, step_min, relax, step_outside;
+                        uint32_t max_steps; float* range; int32_t* status; int32_t* steps; float* normal; };
+void launch_field_trace(hipStream_t s, const float* D, const Lattice& g, const FieldTraceArgs& a);
+size_t beam_score_scratch(uint32_t n, uint32_t n_pose);
+void launch_beam_score(hipStream_t s, const float* range, const int32_t* status, const float* measured, uint32_t n, uint32_t n_pose, uint32_t stride,
+        float huber, float* scratch, float* rows);
 // Pose refinement (mon_object_pose_loss / mon_object_refine_pose, kernels_pose.hip).  k_pose_rays: one record of 4 float4 per drawn ray from the pose in
 // device memory (pose[16], world -> object); k_pose_grad<shape>: loss and position gradient, one partial row of 8 floats {g, x x g, loss, 0} per workgroup
 // (pose_grad_grid of them); k_pose_update: the rows summed in a fixed order, x inv_n -> out[8 * it] = {loss, grad6, 0}, optionally the Adam step on pose.
@@ -860,6 +872,14 @@ int dist_field_match(DistField* f, const float* points, size_t n, const float* p
 int dist_field_register_default(DistField* f, mon_register_params* p);
 int dist_field_register(DistField* f, const float* points, size_t n, const float* poses16_in, size_t n_pose, const mon_register_params* p, float* poses16_out,
                         float* cost, int32_t* n_inside, int32_t* n_inlier, int32_t* evals, int32_t* status, int32_t* best);
+// Ray tracing (dist_field.cpp; the rule: include/mon_core.h).  dist_field_trace: range and, where asked for, status, steps and the normal at the hit of n rays
+// under H poses ([H][n]; poses16 nullptr: world rays, H == 1).  dist_field_beam_score: per pose the Huber cost of range - measured over the beams and the two
+// counts, the ranges staying on the device.  One upload, the launches, one copy home and one synchronisation each.
+int dist_field_trace_default(DistField* f, mon_trace_params* p);
+int dist_field_trace(DistField* f, const float* rays, size_t n, const float* poses16, size_t n_pose, const mon_trace_params* p, float* range, int32_t* status,
+                     int32_t* steps, float* normal3);
+int dist_field_beam_score(DistField* f, const float* rays, size_t n, const float* measured, const float* poses16, size_t n_pose, const mon_trace_params* p,
+                          const mon_beam_params* b, float* cost, int32_t* n_valid, int32_t* n_hit);
 // Point gradients (mon_scene_query_gradients / _lattice_gradients, mon_object_query_gradients): the point queries' conventions, plus level_w (host, may be
 // nullptr = all 1: Lmax floats, object j reads its first L_j; the *_check judges the first, scene_gradients_weights_check the rest once the objects are
 // known) and select (host, [n] or nullptr: -1 or an index into ms).  rows (mon_debug_scene_gradient_rows) = object rows_k's rows, host array [n][16].
