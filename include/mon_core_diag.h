@@ -117,6 +117,9 @@ int mon_debug_checkpoint_timing(int enable, double* kernel_ms);
 /* The sweeps of the process's latest shortest-path field (mon_shortest_paths, mon_scene_paths_lattice, mon_online_paths_lattice; tools/scene_paths_timing.py):
  * out3 = { sweeps enqueued, batches (one read-back each), sweeps that left work for the next one }. */
 int mon_debug_paths_stats(uint32_t* out3);
+/* k_encode_tiles' workgroup order (ro-map_amd/csrc/model.h enc_block_decode, the function the kernel calls): workgroup `block` of a grid row of 16 n_levels
+ * workgroups walks partition *part (0..15) of level *level.  No device needed.  MON_ERR_ARG for n_levels outside 1..16 or block >= 16 n_levels. */
+int mon_debug_encode_block(uint32_t block, int n_levels, uint32_t* level, uint32_t* part);
 
 #ifdef __cplusplus
 }

@@ -358,6 +358,7 @@ _DIAG_SIGS = {
     "mon_debug_set_render_grid": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mon_debug_checkpoint_timing": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
     "mon_debug_paths_stats": (C.c_int, [C.c_void_p]),
+    "mon_debug_encode_block": (C.c_int, [C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mon_debug_scene_samples": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, MonBBox, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mon_debug_scene_composite": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -327,6 +327,12 @@ int mon_debug_scene_gradient_rows(mon_object* const* objs, size_t n_objs, int si
     return mon::scene_gradients(ms.data(), n_objs, side, q, level_weights, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                 k, rows);
 }
+int mon_debug_encode_block(uint32_t block, int n_levels, uint32_t* level, uint32_t* part) {
+    REQUIRE(level, "level"); REQUIRE(part, "part");
+    if (n_levels < 1 || n_levels > kMaxLevels || block >= (uint32_t)n_levels * kEncWgPerLevel) { set_error("encode_block: block %u of %d levels", block, n_levels);
+        return MON_ERR_ARG; }
+    const EncBlock eb = enc_block_decode(block, (uint32_t)n_levels); *level = eb.level; *part = eb.part; return MON_OK;
+}
 int mon_debug_paths_stats(uint32_t* out3) { REQUIRE(out3, "out3"); mon::paths_last_stats(out3); return MON_OK; }
 int mon_debug_pose_samples(mon_object* o, int side, const mon_frame_bbox* obs, size_t n_obs, const float* Tow16, const mon_pose_refine_params* p,
                            uint32_t iteration, float* x, float* raw, float* dldx) {

@@ -29,7 +29,6 @@ namespace mon {
 constexpr uint32_t kEncLdsBytes = 163840;                 // the CU's whole LDS
 static_assert(kEncWholeMax == kEncLdsBytes / 4u, "model.h: a whole-level tile is the CU's LDS");
 constexpr uint32_t kEncParityMax = 65536u;                // entries of a level walked as two parity tiles (cached indices are 16 bits)
-constexpr uint32_t kEncWgPerLevel = 16;                   // sample partitions per level and chunk
 constexpr uint32_t kEncSpt = 8;                           // samples per thread
 constexpr uint32_t kEncThreads = kTileThreads;
 
@@ -74,15 +73,53 @@ struct EncodeArgs {
     uint32_t gen_next; BatchPtrs b_next; DatasetPtrs ds;  ObjectConst oc;
     LiveArgs live;                 // occupancy-grid skipping: walk each partition's list of live samples instead of all of its samples (idx == nullptr: all)
 #ifdef MON_ENCODE_TIMING
-    float* timing;                 // [workgroup][wave][4]: clock at the wave's entry (low 24 bits), cycles from there to the end of its first / second sample loop, SIMD
+    float* timing;                 // [level * 16 + partition][wave][8]: clock at the wave's entry (low 24 bits), cycles from there to the end of its first / second
+                                   // sample loop, SIMD, cycles to the far side of the first barrier (first tile in place) / of the barrier behind the second
+                                   // copy, the workgroup's XCC_ID, 0
 #endif
 };
-// -DMON_ENCODE_TIMING (tools/encode_timing.py): a clock stamp per wave behind each of its sample loops, stores drained
+// -DMON_ENCODE_TIMING (tools/encode_timing.py): a clock stamp per wave behind each of its sample loops, stores drained, and one behind each barrier that ends a
+// tile copy (MON_ET_MARK: nothing drained, the wave's position loads may still be under way there)
 #ifdef MON_ENCODE_TIMING
 #define MON_ET_STAMP(et, k) do { __builtin_amdgcn_s_waitcnt(0); (et)[k] = clock64(); } while (0)
+#define MON_ET_MARK(et, k) do { (et)[k] = clock64(); } while (0)
 #else
 #define MON_ET_STAMP(et, k) do { } while (0)
+#define MON_ET_MARK(et, k) do { } while (0)
 #endif
+
+// MON_ENC_POSWAIT (compile-time, default on; 0 rebuilds the instruction stream without it): the barrier behind the first tile copy waits for the copy alone,
+// not for the wave's position loads, which go out right behind the copy; each round of the walk then waits for its own position.
+#ifndef MON_ENC_POSWAIT
+#define MON_ENC_POSWAIT 1
+#endif
+// a word of the training state (constant while this kernel runs) through the scalar cache
+__device__ __forceinline__ uint32_t enc_state_word(const uint32_t* p) {
+#if MON_ENC_POSWAIT
+    return *(const __attribute__((address_space(4))) uint32_t*)p;
+#else
+    return *p;
+#endif
+}
+// The first tile copy has landed in LDS: vmcnt retires in order, so a wave that issued its kEncSpt position loads BEHIND its share of the copy is done with the
+// copy once only those are outstanding.  vmcnt counts wave instructions: a wave none of whose lanes has a sample issued no position load and waits for everything,
+// hence the wave-uniform choice.  POS_BEHIND = false (the live-sample lists: positions hang on the index loads) waits for everything too.
+template <bool POS_BEHIND> __device__ __forceinline__ void enc_wait_copy(uint32_t s_base, uint32_t s_end) {
+    static_assert(kEncSpt == 8, "the counted wait below names kEncSpt");
+#if MON_ENC_POSWAIT
+    if (POS_BEHIND && __builtin_amdgcn_readfirstlane((int)(s_base + (threadIdx.x & ~63u) < s_end))) { __builtin_amdgcn_s_waitcnt(0x0f78); return; }   // vmcnt(8)
+#endif
+    __builtin_amdgcn_s_waitcnt(0x0f70);                                   // vmcnt(0): the LDS writes of the copy are counted there
+}
+// ... and the barrier behind that wait.  __syncthreads() fences first, and its fence waits vmcnt(0) while loads are under way: for the position loads, which the
+// counted wait has just left alone.  No wave has touched the LDS yet and the copy's writes are ordered by the wait above, so the bare barrier is enough.
+__device__ __forceinline__ void enc_barrier_copy() {
+#if MON_ENC_POSWAIT
+    __builtin_amdgcn_s_barrier();
+#else
+    __syncthreads();
+#endif
+}
 
 // the chain of encode_interp: corners in order k = x + 2y + 4z, c0[j] / c1[j] = x-corner 0 / 1 of pair j, weight ((wx * wy) * wz); the two x-corners of a pair
 // and the two features of a corner are worked on as pairs (v_pk_mul_f32 / v_pk_fma_f32: the same IEEE operations, two per instruction)
@@ -104,18 +141,26 @@ __device__ __forceinline__ half2_t enc_chain(const uint32_t (&c0)[4], const uint
 // A thread's kEncSpt sample slots and their positions, requested together (one load per loop trip put a global round trip in front of every sample).
 // LIVE (occupancy-grid skipping): the slots come from the partition's list of live samples -- entry threadIdx.x + k * kEncThreads of `count` -- and a wave whose
 // entries of round k all lie beyond the list skips that round altogether (wave-uniform: the unrolled rounds keep their static register arrays).
+// With MON_ENC_POSWAIT a position is fetched as the 12 bytes the walk reads: the dead fourth register of a 16-byte load is handed out again while the load is
+// under way, and the write to it waits for every load before it, the tile copy included -- the eight loads then went out two at a time, a round trip apart.
+#if MON_ENC_POSWAIT
+typedef float enc_pos_t __attribute__((ext_vector_type(3)));
+#else
+typedef float4_t enc_pos_t;
+#endif
+__device__ __forceinline__ enc_pos_t load_position(const float4_t* __restrict__ x) { return *reinterpret_cast<const enc_pos_t*>(x); }
 template <bool LIVE>
-__device__ __forceinline__ void load_positions(float4_t (&xs)[kEncSpt], uint32_t (&slot)[kEncSpt], const EncodeArgs& a, uint32_t s_base, uint32_t s_end,
+__device__ __forceinline__ void load_positions(enc_pos_t (&xs)[kEncSpt], uint32_t (&slot)[kEncSpt], const EncodeArgs& a, uint32_t s_base, uint32_t s_end,
         uint32_t count) {
     if constexpr (LIVE) {
 #pragma unroll
         for (uint32_t k = 0; k < kEncSpt; ++k) { const uint32_t j = threadIdx.x + k * kEncThreads; slot[k] = (j < count) ? a.live.idx[s_base + j] : 0xffffffffu; }
 #pragma unroll
-        for (uint32_t k = 0; k < kEncSpt; ++k) xs[k] = a.x_all[slot[k] != 0xffffffffu ? slot[k] : s_base];
+        for (uint32_t k = 0; k < kEncSpt; ++k) xs[k] = load_position(a.x_all + (slot[k] != 0xffffffffu ? slot[k] : s_base));
     } else {
 #pragma unroll
         for (uint32_t k = 0; k < kEncSpt; ++k) { const uint32_t s = s_base + threadIdx.x + k * kEncThreads; slot[k] = s < s_end ? s : 0xffffffffu;
-            xs[k] = a.x_all[min(s, s_end - 1u)]; }
+            xs[k] = load_position(a.x_all + min(s, s_end - 1u)); }
     }
 }
 // round k has work for this wave (uniform)
@@ -131,8 +176,15 @@ template <bool LIVE> __device__ __forceinline__ void round_prio(uint32_t k, uint
 template <bool HASHED, bool POW2, bool LIVE>
 __device__ __forceinline__ void encode_whole(const uint32_t* tile, const EncodeArgs& a, uint32_t s_base, uint32_t s_end, uint32_t count,
         half2_t* __restrict__ out, float scale, uint32_t size, uint32_t my, uint32_t mz, uint32_t mask, long long* et) {
-    if (s_base + threadIdx.x >= s_end && !LIVE) return;
-    float4_t xs[kEncSpt]; uint32_t slot[kEncSpt]; load_positions<LIVE>(xs, slot, a, s_base, s_end, count);
+    enc_pos_t xs[kEncSpt]; uint32_t slot[kEncSpt];
+    const bool walk = LIVE || s_base + threadIdx.x < s_end;
+    // (the tile copy is under way: k_encode_tiles requested it at its entry)
+    if (MON_ENC_POSWAIT && !LIVE && walk) load_positions<LIVE>(xs, slot, a, s_base, s_end, count);
+    enc_wait_copy<!LIVE>(s_base, s_end);
+    enc_barrier_copy();
+    MON_ET_MARK(et, 3);
+    if (!walk) return;
+    if (!MON_ENC_POSWAIT || LIVE) load_positions<LIVE>(xs, slot, a, s_base, s_end, count);
     const uint32_t n_on = rounds_on<LIVE>(count);
 #pragma unroll
     for (uint32_t k = 0; k < kEncSpt; ++k) {
@@ -158,11 +210,12 @@ __device__ __forceinline__ void encode_parity(uint32_t* tile, const uint4* __res
     // (the position inside the cell is kept too: 24 registers against a second load + 9 instructions per sample)
     uint32_t veven[kEncSpt][4], cache[kEncSpt][2]; float pos[kEncSpt][3];
     const bool walk = LIVE ? (threadIdx.x & ~63u) < count : s_base + threadIdx.x < s_end;
-    float4_t xs[kEncSpt]; uint32_t slot[kEncSpt];
+    enc_pos_t xs[kEncSpt]; uint32_t slot[kEncSpt];
     if (walk) load_positions<LIVE>(xs, slot, a, s_base, s_end, count);          // (the copy of the even half is under way: k_encode_tiles requested it at its entry)
     const uint32_t n_on = rounds_on<LIVE>(count);
-    __builtin_amdgcn_s_waitcnt(0x0f70);                                   // vmcnt(0): the LDS writes of the copy are counted there
-    __syncthreads();
+    enc_wait_copy<!LIVE>(s_base, s_end);
+    enc_barrier_copy();
+    MON_ET_MARK(et, 3);
     if (walk) {
 #pragma unroll
         for (uint32_t k = 0; k < kEncSpt; ++k) {
@@ -186,6 +239,7 @@ __device__ __forceinline__ void encode_parity(uint32_t* tile, const uint4* __res
     tile_copy(tile, src + size / 8u, size / 8u);
     __builtin_amdgcn_s_waitcnt(0x0f70);
     __syncthreads();
+    MON_ET_MARK(et, 4);
     if (walk) {
 #pragma unroll
         for (uint32_t k = 0; k < kEncSpt; ++k) {
@@ -210,9 +264,10 @@ __device__ __forceinline__ void encode_parity(uint32_t* tile, const uint4* __res
 __global__ void __launch_bounds__(kEncThreads) k_encode_tiles(EncodeArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t* tile = reinterpret_cast<uint32_t*>(smem);
-    long long et[3] = { 0, 0, 0 };
+    long long et[5] = { 0, 0, 0, 0, 0 };
     MON_ET_STAMP(et, 0);
-    const uint32_t level = blockIdx.x / kEncWgPerLevel, part = blockIdx.x - level * kEncWgPerLevel;
+    const EncBlock eb = enc_block_decode(blockIdx.x, (uint32_t)a.L);
+    const uint32_t level = eb.level, part = eb.part;                   // (everything below is keyed on these, never on blockIdx.x)
     if (a.gen_next && level == 0u && blockIdx.y == 0u && threadIdx.x < 256u)
         for (uint32_t c0 = part * 256u; c0 < a.oc.R; c0 += kEncWgPerLevel * 256u) gen_candidate(a.b_next, a.ds, a.oc, a.st->n_boxes, a.st->iter + 1u,
                 c0 + threadIdx.x);
@@ -226,20 +281,33 @@ __global__ void __launch_bounds__(kEncThreads) k_encode_tiles(EncodeArgs a) {
     half2_t* out = a.e_soa + (size_t)level * a.B;
     // the first tile is requested BEFORE the state is looked at (everything above comes from the argument segment): the round trip for n_valid_pre runs under
     // the copy
+#if MON_ENC_POSWAIT
+    // (kept out of the compiler's bookkeeping: with a copy it knows of under way it waits vmcnt(0) at the first use of a position, whatever enc_wait_copy counted.
+    // enc_wait_copy's count holds as long as a wave without the lists issues NO vector memory instruction between here and there but its position loads)
+    tile_copy_uncounted(tile, src, size <= kEncWholeMax ? size / 4u : size / 8u);
+#else
     tile_copy(tile, src, size <= kEncWholeMax ? size / 4u : size / 8u);
+#endif
     // occupancy-grid skipping: this partition's live-sample count -- both parity sets requested with the state, the iteration's one picked afterwards
     const bool live = a.live.idx != nullptr;
     uint32_t cnt0 = 0u, cnt1 = 0u;
     if (live) { cnt0 = a.live.cnt[(size_t)w * kLiveCntStride]; cnt1 = a.live.cnt[((size_t)kLiveMaxParts + w) * kLiveCntStride]; }
-    const uint32_t iter = a.st->iter;
-    if (live && blockIdx.x == 0u && blockIdx.y == 0u && threadIdx.x < kLiveMaxParts)      // (the set the next iteration's position pass counts in: nobody reads it now)
+    // (MON_ENC_POSWAIT: the two state words through the scalar cache.  Nothing writes the state while this kernel runs, but the compiler cannot know and fetches
+    // them with vector loads behind the copy: their wait is then a wait for the whole copy, in front of the position loads)
+    const uint32_t iter = enc_state_word(&a.st->iter), n_valid_pre = enc_state_word(&a.st->n_valid_pre);
+    if (live && level == 0u && part == 0u && blockIdx.y == 0u && threadIdx.x < kLiveMaxParts)      // (the set the next iteration's position pass counts in: nobody reads it now)
         a.live.cnt[((size_t)((iter + 1u) & 1u) * kLiveMaxParts + threadIdx.x) * kLiveCntStride] = 0u;
-    if (a.st->n_valid_pre == 0u) return;                               // batch skipped (the position pass wrote the count)
+    if (n_valid_pre == 0u) return;                                     // batch skipped (the position pass wrote the count)
+    // (the count is looked at on the live path alone: a use on the common path is a wait for the two loads above, and with them for the whole copy)
+#if MON_ENC_POSWAIT
+    uint32_t count = 0u;
+#define MON_ENC_CALL(FN, H, P2, ...) do { if (live) { count = min((iter & 1u) ? cnt1 : cnt0, s_end - s_base); FN<H, P2, true>(__VA_ARGS__); } \
+        else FN<H, P2, false>(__VA_ARGS__); } while (0)
+#else
     const uint32_t count = min((iter & 1u) ? cnt1 : cnt0, s_end - s_base);
 #define MON_ENC_CALL(FN, H, P2, ...) do { if (live) FN<H, P2, true>(__VA_ARGS__); else FN<H, P2, false>(__VA_ARGS__); } while (0)
+#endif
     if (size <= kEncWholeMax) {
-        __builtin_amdgcn_s_waitcnt(0x0f70);
-        __syncthreads();
         if (hashed) { if (pow2) MON_ENC_CALL(encode_whole, true, true, tile, a, s_base, s_end, count, out, scale, size, my, mz, mask, et);
             else MON_ENC_CALL(encode_whole, true, false, tile, a, s_base, s_end, count, out, scale, size, my, mz, mask, et); }
         else MON_ENC_CALL(encode_whole, false, false, tile, a, s_base, s_end, count, out, scale, size, my, mz, mask, et);
@@ -250,9 +318,11 @@ __global__ void __launch_bounds__(kEncThreads) k_encode_tiles(EncodeArgs a) {
     }
 #undef MON_ENC_CALL
 #ifdef MON_ENCODE_TIMING
-    if (a.timing && blockIdx.y == 0u && (threadIdx.x & 63u) == 0u) { float* o = a.timing + ((size_t)blockIdx.x * 16u + (threadIdx.x >> 6)) * 4u;
+    if (a.timing && blockIdx.y == 0u && (threadIdx.x & 63u) == 0u) { float* o = a.timing + ((size_t)(level * kEncWgPerLevel + part) * 16u + (threadIdx.x >> 6)) * 8u;
         o[0] = (float)(et[0] & 0xffffff); o[1] = (float)(et[1] - et[0]); o[2] = (float)(et[2] ? et[2] - et[0] : 0);
-        o[3] = (float)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4); }      // HW_ID.simd_id
+        o[3] = (float)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4);        // HW_ID.simd_id
+        o[4] = (float)(et[3] ? et[3] - et[0] : 0); o[5] = (float)(et[4] ? et[4] - et[0] : 0);
+        o[6] = (float)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20); o[7] = 0.f; }      // XCC_ID.xcc_id
 #endif
 }
 
@@ -299,7 +369,7 @@ void launch_xorwow_fill(hipStream_t s, void* lane_states, uint32_t lanes, int fl
 }
 
 #ifdef MON_ENCODE_TIMING
-constexpr size_t kEncTimingBytes = (size_t)kMaxLevels * kEncWgPerLevel * 16 * 4 * sizeof(float);
+constexpr size_t kEncTimingBytes = (size_t)kMaxLevels * kEncWgPerLevel * 16 * 8 * sizeof(float);
 static float* g_enc_timing_buf = nullptr;
 extern "C" int mon_debug_encode_timing(float* out) { hipDeviceSynchronize();
     return g_enc_timing_buf ? (int)hipMemcpy(out, g_enc_timing_buf, kEncTimingBytes, hipMemcpyDeviceToHost) : -1; }

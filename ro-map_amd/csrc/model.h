@@ -122,6 +122,23 @@ struct ParamPtrs {
 constexpr uint32_t kEncWholeMax = 163840u / 4u;                     // entries (half2) of a level that fits in one 160 KB tile
 __host__ __device__ inline uint32_t tile_slot(uint32_t off, uint32_t size, uint32_t e_rel) {
     return size <= kEncWholeMax ? off + e_rel : off + (e_rel & 1u) * (size >> 1) + (e_rel >> 1); }
+// Workgroup b of a row of k_encode_tiles' grid (16 L workgroups, one row per batch chunk) -> (level, sample partition).  Workgroups are dealt round-robin
+// over the chip's 8 XCDs, each with an L2 of its own, so b & 7 labels the workgroups that share one.  With level = b / 16 every label walks two partitions of
+// every level and every L2 fetches the whole tile image each step.  For L = 4, 8, 16 a label gets four levels x L / 2 partitions instead (L = 16: labels 2 g and
+// 2 g + 1 share levels 4 g .. 4 g + 3, partitions 0..7 and 8..15): an L2 then fetches a quarter of the image and half of the positions.  A permutation of
+// [0, 16 L) for every L (other L: the identity); where the workgroups really land only decides the traffic (-DMON_ENC_XCD=0: the identity throughout).
+#ifndef MON_ENC_XCD
+#define MON_ENC_XCD 1
+#endif
+constexpr uint32_t kEncWgPerLevel = 16;                             // sample partitions per level and chunk
+struct EncBlock { uint32_t level, part; };
+__host__ __device__ inline EncBlock enc_block_decode(uint32_t b, uint32_t L) {
+#if MON_ENC_XCD
+    if (L == 4u || L == 8u || L == 16u) { const uint32_t ppx = L / 2u, per = kEncWgPerLevel / ppx, x = b & 7u, s = b >> 3;
+        return EncBlock{ 4u * (x / per) + s / ppx, (x % per) * ppx + s % ppx }; }
+#endif
+    (void)L; return EncBlock{ b / kEncWgPerLevel, b % kEncWgPerLevel };
+}
 
 struct OptimConst {
     float beta1, beta2, epsilon, l2_reg, ema_decay, loss_scale, decay_base, log2_beta1, log2_beta2, log2_decay;

@@ -13,8 +13,8 @@ constexpr uint32_t kTileThreads = 1024;                    // threads of a tile 
 // (v_mul_lo_u32 runs at a quarter of it), and the two x-corners differ by the xor with dxm = (x ^ (x + 1)) & mask.
 typedef float float2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ int floor_to_int(float q) { int r; asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(r) : "v"(q)); return r; }      // (int)floorf(q)
-template <bool HASHED, bool POW2>
-__device__ __forceinline__ void enc_indices(const float4_t& xv, float scale, uint32_t size, uint32_t my, uint32_t mz, uint32_t mask, uint32_t (&i0)[4],
+template <bool HASHED, bool POW2, typename V>      // (V: a position as float4 or as its three coordinates)
+__device__ __forceinline__ void enc_indices(const V& xv, float scale, uint32_t size, uint32_t my, uint32_t mz, uint32_t mask, uint32_t (&i0)[4],
         uint32_t (&i1)[4], float (&pos)[3]) {
     uint32_t pg[3];
     // (v_fract_f32 = q - floor(q) exactly for q >= 0; one instruction each instead of floor + subtract + convert)
@@ -52,6 +52,23 @@ __device__ __forceinline__ void tile_copy(uint32_t* tile, const uint4* __restric
         // (lanes past the tile's end stay out: a lane's LDS address is its position in the wave, active or not)
         if (i < n16)
             __builtin_amdgcn_global_load_lds((gbl_void*)(src + i), (lds_void*)(base + (size_t)(i0 + wave0) * 16u), 16, 0, 0);
+    }
+}
+// The same copy, kept out of the compiler's wait bookkeeping, for a caller that waits for it by COUNT while loads issued behind it stay under way: with a copy
+// it knows of in flight the compiler waits vmcnt(0) at the first use of any loaded register and in front of the first LDS read, whatever the caller counted.
+// The caller owns the wait: an s_waitcnt vmcnt(n) that leaves only younger loads outstanding, then a barrier, before anything reads the tile.  The compiler's
+// own counted waits stay right with these loads outstanding: vmcnt retires in order, so loads it does not know of only make a count it chose stricter than it
+// had to be.  (M0, the LDS base of the copy, is the compiler's: saved and put back inside the statement.)
+__device__ __forceinline__ void tile_copy_uncounted(uint32_t* tile, const uint4* __restrict__ src, uint32_t n16) {
+    typedef __attribute__((address_space(3))) void lds_void;
+    const uint32_t base = (uint32_t)reinterpret_cast<uintptr_t>((lds_void*)tile), wave0 = threadIdx.x & ~63u;
+    for (uint32_t i0 = 0; i0 < n16; i0 += kTileThreads) {
+        const uint32_t i = i0 + threadIdx.x;
+        if (i < n16) {
+            const uint32_t dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)(base + (i0 + wave0) * 16u));
+            const uint4* g = src + i; uint32_t keep;
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(g), "s"(dst) : "memory");
+        }
     }
 }
 

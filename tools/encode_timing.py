@@ -32,6 +32,23 @@ def table(buf, col, name):
                     own.mean(), own.max()))
 
 
+def phases(buf):
+    """per level: workgroup means of the slowest wave's marks (a barrier lets the workgroup go when its last wave arrives), in clock64() counts like the table above"""
+    print("| level | copy 1 (+ positions): entry to behind the first barrier | walk 1: to the last wave's end of the first loop | copy 2: to behind the barrier "
+          "after the second copy | walk 2: to the last wave's end of the second loop | XCDs of the 16 workgroups (workgroups on each) |")
+    print("|---|---|---|---|---|---|")
+    for lv in range(buf.shape[0] // 16):
+        g = buf[16 * lv:16 * lv + 16]
+        if g[:, 0, 1].max() <= 0:
+            continue
+        b1, w1, b2, w2 = g[:, :, 4].max(1), g[:, :, 1].max(1), g[:, :, 5].max(1), g[:, :, 2].max(1)
+        xcd = g[:, 0, 6].astype(int); where = ", ".join("%d (%d)" % (x, (xcd == x).sum()) for x in sorted(set(xcd)))
+        if b2.max() > 0:
+            print("| %d | %.0f | %.0f | %.0f | %.0f | %s |" % (lv, b1.mean(), (w1 - b1).mean(), (b2 - w1).mean(), (w2 - b2).mean(), where))
+        else:
+            print("| %d (whole tile) | %.0f | %.0f | | | %s |" % (lv, b1.mean(), (w1 - b1).mean(), where))
+
+
 def main():
     pkg = ge.load_package(); ss = ge.load_tools()
     sc = ss.make_scene(n_views=40, H=480, W=640, f=525.0, seed=0)
@@ -39,10 +56,10 @@ def main():
     L = C.CDLL(os.environ["MON_CORE_LIB"])
     for steps, name in ((10, "dense (step 10)"), (800, "late (step 810)")):
         obj.train(steps)
-        buf = np.zeros((256, 16, 4), np.float32)
+        buf = np.zeros((256, 16, 8), np.float32)
         assert L.mon_debug_encode_timing(buf.ctypes.data_as(C.c_void_p)) == 0
         print("\n== %s: %s" % (name, os.environ["MON_CORE_LIB"]))
-        table(buf, 1, "first loop (whole tile: the only one)"); table(buf, 2, "second loop")
+        table(buf, 1, "first loop (whole tile: the only one)"); table(buf, 2, "second loop"); print(); phases(buf)
     obj.close(); ds.close()
 
 
