@@ -199,21 +199,15 @@ static void fused_emit_t(hipStream_t s, const FusedArgs& a, uint32_t n_rays, uin
 __global__ void __launch_bounds__(64) k_scene_composite(uint32_t n_rays, uint32_t n_lists, uint32_t cap, const float* __restrict__ tl,
         const float4* __restrict__ attr, const uint32_t* __restrict__ cnt, const float* __restrict__ dn, float* __restrict__ out_rgb,
         float* __restrict__ out_depth, float* __restrict__ out_opacity, int32_t* __restrict__ out_instance) {
-    constexpr uint32_t L2S = kSceneListLen;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint16_t* s_perm = reinterpret_cast<uint16_t*>(smem);                             // [L2S * n_lists] merged order: compact list << 6 | index
-    uint32_t* s_id = reinterpret_cast<uint32_t*>(smem + 2u * L2S * n_lists);          // [n_lists] compact list -> list
-    uint32_t* s_c = s_id + n_lists;                                                    // its count
-    float* s_tf = reinterpret_cast<float*>(s_c + n_lists);                             // its first t
-    float* s_tl = s_tf + n_lists;                                                      // its last t
-    float* s_w = s_tl + n_lists;                                                       // its summed weight
+    const SceneLds s = scene_lds(smem, n_lists);
     const int lane = threadIdx.x;
     for (uint32_t ray = blockIdx.x; ray < n_rays; ray += gridDim.x) {
         uint32_t na, n_tot;
-        scene_merge_lists(ray, n_lists, cap, tl, cnt, lane, s_perm, s_id, s_c, s_tf, s_tl, s_w, na, n_tot);
+        scene_merge_lists(s, ray, n_lists, cap, tl, cnt, lane, na, n_tot);
         SceneWalk w;
-        scene_composite_walk<false>(ray, cap, na, n_tot, tl, attr, lane, s_perm, s_id, s_w, w);
-        if (lane == 0) scene_composite_store(ray, na, s_id, s_w, w, dn, out_rgb, out_depth, out_opacity, out_instance);
+        scene_composite_walk<false>(s, ray, cap, na, n_tot, tl, attr, lane, w);
+        if (lane == 0) scene_composite_store(s, ray, na, w, dn, out_rgb, out_depth, out_opacity, out_instance);
         __syncthreads();
     }
 }
@@ -239,8 +233,7 @@ void launch_fused_render_emit(hipStream_t s, const LevelFast& lt, const NetDims&
 void launch_scene_composite(hipStream_t s, uint32_t n_rays, uint32_t n_lists, uint32_t cap, const float* t, const float* attr, const uint32_t* cnt,
         const float* dn, float* rgb, float* depth, float* opacity, int32_t* instance) {
     if (!n_rays || !n_lists || n_lists > kSceneMaxLists) return;
-    const uint32_t grid = n_rays < 8192u ? n_rays : 8192u;
-    hipLaunchKernelGGL(k_scene_composite, dim3(grid), dim3(64), scene_composite_lds(n_lists), s, n_rays, n_lists, cap, t,
+    hipLaunchKernelGGL(k_scene_composite, dim3(scene_composite_grid(n_rays)), dim3(64), scene_composite_lds(n_lists), s, n_rays, n_lists, cap, t,
             reinterpret_cast<const float4*>(attr), cnt, dn, rgb, depth, opacity, instance);
 }
 

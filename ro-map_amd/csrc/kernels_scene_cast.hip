@@ -51,28 +51,23 @@ __global__ void __launch_bounds__(64) k_scene_cast_composite(uint32_t n_rays, ui
         float* __restrict__ out_hit_sample_t, int32_t* __restrict__ out_hit_instance) {
     constexpr uint32_t L2S = kSceneListLen;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint16_t* s_perm = reinterpret_cast<uint16_t*>(smem);
-    uint32_t* s_id = reinterpret_cast<uint32_t*>(smem + 2u * L2S * n_lists);
-    uint32_t* s_c = s_id + n_lists;
-    float* s_tf = reinterpret_cast<float*>(s_c + n_lists);
-    float* s_tl = s_tf + n_lists;
-    float* s_w = s_tl + n_lists;
+    const SceneLds s = scene_lds(smem, n_lists);
     const int lane = threadIdx.x;
     for (uint32_t ray = blockIdx.x; ray < n_rays; ray += gridDim.x) {
         uint32_t na, n_tot;
-        scene_merge_lists(ray, n_lists, cap, tl, cnt, lane, s_perm, s_id, s_c, s_tf, s_tl, s_w, na, n_tot);
+        scene_merge_lists(s, ray, n_lists, cap, tl, cnt, lane, na, n_tot);
         SceneWalk w;
-        scene_composite_walk<true, true>(ray, cap, na, n_tot, tl, attr, lane, s_perm, s_id, s_w, w, thr);
+        scene_composite_walk<true, true>(s, ray, cap, na, n_tot, tl, attr, lane, w, thr);
         if (lane == 0) {
-            scene_composite_store<false>(ray, na, s_id, s_w, w, nullptr, out_rgb, out_dist, out_opacity, out_instance);
+            scene_composite_store<false>(s, ray, na, w, nullptr, out_rgb, out_dist, out_opacity, out_instance);
             float ht = 0.f, hs = 0.f; int32_t hi = -1;
             if (w.hit) {
-                const size_t row = (size_t)s_id[w.hit_a] * cap + ray;
+                const size_t row = (size_t)s.id[w.hit_a] * cap + ray;
                 const float p = w.hit_slot ? tl[row * L2S + w.hit_slot - 1u] : entry[row];
                 const float om = 1.f - w.hit_alpha;
                 float f = 0.f;
                 if (om != 0.f) f = fminf(fmaxf(logf(w.hit_T / (1.f - thr)) / -logf(om), 0.f), 1.f);
-                hs = w.hit_t; ht = fmaf(f, hs - p, p); hi = (int32_t)s_id[w.hit_a];
+                hs = w.hit_t; ht = fmaf(f, hs - p, p); hi = (int32_t)s.id[w.hit_a];
             }
             out_hit_t[ray] = ht; out_hit_sample_t[ray] = hs; out_hit_instance[ray] = hi;
         }
@@ -88,8 +83,7 @@ void launch_scene_cast_composite(hipStream_t s, uint32_t n_rays, uint32_t n_list
         const uint32_t* cnt, const float* entry, float* rgb, float* dist, float* opacity, int32_t* instance, float* hit_t, float* hit_sample_t,
         int32_t* hit_instance) {
     if (!n_rays || !n_lists || n_lists > kSceneMaxLists) return;
-    const uint32_t grid = n_rays < 8192u ? n_rays : 8192u;
-    hipLaunchKernelGGL(k_scene_cast_composite, dim3(grid), dim3(64), scene_composite_lds(n_lists), s, n_rays, n_lists, cap, thr, t,
+    hipLaunchKernelGGL(k_scene_cast_composite, dim3(scene_composite_grid(n_rays)), dim3(64), scene_composite_lds(n_lists), s, n_rays, n_lists, cap, thr, t,
             reinterpret_cast<const float4*>(attr), cnt, entry, rgb, dist, opacity, instance, hit_t, hit_sample_t, hit_instance);
 }
 

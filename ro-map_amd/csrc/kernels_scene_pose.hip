@@ -205,57 +205,37 @@ __device__ __forceinline__ float suffix_add64(float v) {
 // in ray order into loss_part[blockIdx.x].
 // The walk: rays r = r0, r0 + stride, ... < n_rays at the lists' slots v0 + r; returns the sum of their losses in that order.
 __device__ __forceinline__ float scene_composite_grad_walk(const SceneCompGradArgs& a, uint32_t r0, uint32_t n_rays, uint32_t stride, uint32_t v0) {
-    constexpr uint32_t L2S = kSceneListLen;
-    const uint32_t n_lists = a.n_lists, cap = a.cap;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint16_t* s_perm = reinterpret_cast<uint16_t*>(smem);                             // [L2S * n_lists] merged order: compact list << 6 | index
-    uint32_t* s_id = reinterpret_cast<uint32_t*>(smem + 2u * L2S * n_lists);          // [n_lists] compact list -> list
-    uint32_t* s_c = s_id + n_lists;                                                    // its count
-    float* s_tf = reinterpret_cast<float*>(s_c + n_lists);                             // its first t
-    float* s_tl = s_tf + n_lists;                                                      // its last t
-    float* s_w = s_tl + n_lists;                                                       // its summed weight W
-    float* s_q = s_w + n_lists;                                                        // its 2 w_mask (W - m*)
-    float* s_T = s_q + n_lists;                                                        // [n_lists] entry transmittance of each 64-sample block
+    const SceneLds s = scene_lds<true>(smem, a.n_lists);
     const int lane = threadIdx.x;
     float loss_acc = 0.f;
     for (uint32_t rl = r0; rl < n_rays; rl += stride) {
         const uint32_t ray = v0 + rl;
         SceneRayFwd f;
-        scene_composite_ray<true>(a, ray, lane, s_perm, s_id, s_c, s_tf, s_tl, s_w, s_q, s_T, f);
-        const uint32_t na = f.na, n_tot = f.n_tot, n_blocks = f.n_blocks, n_done = f.n_done;
-        const float cs[3] = { f.cs[0], f.cs[1], f.cs[2] }, dstar = f.dstar, dn = f.dn, Mstar = f.Mstar, D = f.D, l = f.l;
-        const float res[3] = { f.res[0], f.res[1], f.res[2] };
-        const bool dep_on = f.dep_on;
-        loss_acc += l;
-        const float Gc[3] = { a.w_rgb * Mstar * 2.f * res[0] / 3.f, a.w_rgb * Mstar * 2.f * res[1] / 3.f, a.w_rgb * Mstar * 2.f * res[2] / 3.f };
-        const float GD = dep_on ? a.w_depth * clamp_f(D - dstar, -a.huber, a.huber) / dn : 0.f;
-        if (lane == 0) { a.grow[ray] = make_float4(Gc[0], Gc[1], Gc[2], l); if (a.out_D) a.out_D[ray] = D; }
+        scene_composite_ray<true>(a, s, ray, lane, f);
+        loss_acc += f.l;
+        const float Gc[3] = { a.w_rgb * f.Mstar * 2.f * f.res[0] / 3.f, a.w_rgb * f.Mstar * 2.f * f.res[1] / 3.f, a.w_rgb * f.Mstar * 2.f * f.res[2] / 3.f };
+        const float GD = f.dep_on ? a.w_depth * clamp_f(f.D - f.dstar, -a.huber, a.huber) / f.dn : 0.f;
+        if (lane == 0) { a.grow[ray] = make_float4(Gc[0], Gc[1], Gc[2], f.l); if (a.out_D) a.out_D[ray] = f.D; }
         __syncthreads();
-        // ---- backward: the blocks in reverse, the suffix sum of w q carried from block to block
+        // ---- backward: the blocks in reverse (the forward's fetch and transmittance from each block's kept entry), the suffix sum of w q carried from
+        // block to block
         float carry = 0.f;
-        for (uint32_t bb = n_blocks; bb > 0u; --bb) {
-            const uint32_t blk = bb - 1u, pidx = blk * 64u + (uint32_t)lane;
-            size_t idx = 0; bool have = false; uint32_t ac = 0u;
-            if (pidx < n_tot) {
-                const uint32_t e = s_perm[pidx];
-                if ((e >> 6) < na) { ac = e >> 6; idx = ((size_t)s_id[ac] * cap + ray) * L2S + (e & 63u); have = true; }
-            }
-            if (blk >= n_done) { if (have) a.gw[idx] = make_float2(0.f, 0.f); continue; }          // behind the cut
-            float tv = 0.f, al = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, qm = 0.f;
-            if (have) { const float4 v = a.attr[idx]; tv = a.t[idx]; al = v.x; c0 = v.y; c1 = v.z; c2 = v.w; qm = s_q[ac]; }
-            const float Tb = s_T[blk];
-            const float omv = 1.f - al;
-            const float sc = scene_scan_mul32(omv, n_tot), lo = sc * Tb, mid = lane_bcast(lo, 31);
-            const float incl = lane < 32 ? lo : sc * mid;
-            float T = lane_prev(incl, Tb); if (lane == 0) T = Tb; if (lane == 32) T = mid;
-            const bool active = T >= kTransmittanceEps;
-            const float wgt = active ? al * T : 0.f;
-            const float q = Gc[0] * (c0 - cs[0]) + Gc[1] * (c1 - cs[1]) + Gc[2] * (c2 - cs[2]) + GD * tv + qm;
+        for (uint32_t bb = f.n_blocks; bb > 0u; --bb) {
+            const uint32_t blk = bb - 1u, p = blk * 64u + (uint32_t)lane;
+            SceneSample m = scene_fetch<false>(s, p, ray, a.cap, f.na, f.n_tot, a.t, a.attr);
+            const bool have = m.a != ~0u;
+            if (blk >= f.n_done) { if (have) a.gw[m.idx] = make_float2(0.f, 0.f); continue; }          // behind the cut
+            scene_load(m, a.t, a.attr);
+            const float qm = have ? s.q[m.a] : 0.f, omv = 1.f - m.al;
+            const SceneTrans x = scene_transmittance(omv, s.T[blk], f.n_tot, lane);
+            const float wgt = x.active ? m.al * x.T : 0.f;
+            const float q = Gc[0] * (m.c0 - f.cs[0]) + Gc[1] * (m.c1 - f.cs[1]) + Gc[2] * (m.c2 - f.cs[2]) + GD * m.t + qm;
             const float sin = suffix_add64(wgt * q);                                   // inclusive
             float sfx = lane_next(sin, 0.f); if (lane == 63) sfx = 0.f;               // samples behind this one, this block
             sfx += carry;
-            const float g = (active && have) ? T * q - (omv > 0.f ? sfx / omv : 0.f) : 0.f;
-            if (have) a.gw[idx] = make_float2(g, wgt);
+            const float g = (x.active && have) ? x.T * q - (omv > 0.f ? sfx / omv : 0.f) : 0.f;
+            if (have) a.gw[m.idx] = make_float2(g, wgt);
             carry += lane_bcast(sin, 0);
         }
         __syncthreads();

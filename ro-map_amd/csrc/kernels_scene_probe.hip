@@ -35,24 +35,18 @@ __global__ void __launch_bounds__(64) k_scene_probe_composite(uint32_t n_rays, u
         const float4* __restrict__ attr, const uint32_t* __restrict__ cnt, const float* __restrict__ dn, float* __restrict__ out_rgb,
         float* __restrict__ out_depth, float* __restrict__ out_opacity, int32_t* __restrict__ out_instance, float* __restrict__ out_hit_depth,
         int32_t* __restrict__ out_hit_instance) {
-    constexpr uint32_t L2S = kSceneListLen;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint16_t* s_perm = reinterpret_cast<uint16_t*>(smem);
-    uint32_t* s_id = reinterpret_cast<uint32_t*>(smem + 2u * L2S * n_lists);
-    uint32_t* s_c = s_id + n_lists;
-    float* s_tf = reinterpret_cast<float*>(s_c + n_lists);
-    float* s_tl = s_tf + n_lists;
-    float* s_w = s_tl + n_lists;
+    const SceneLds s = scene_lds(smem, n_lists);
     const int lane = threadIdx.x;
     for (uint32_t ray = blockIdx.x; ray < n_rays; ray += gridDim.x) {
         uint32_t na, n_tot;
-        scene_merge_lists(ray, n_lists, cap, tl, cnt, lane, s_perm, s_id, s_c, s_tf, s_tl, s_w, na, n_tot);
+        scene_merge_lists(s, ray, n_lists, cap, tl, cnt, lane, na, n_tot);
         SceneWalk w;
-        scene_composite_walk<true>(ray, cap, na, n_tot, tl, attr, lane, s_perm, s_id, s_w, w);
+        scene_composite_walk<true>(s, ray, cap, na, n_tot, tl, attr, lane, w);
         if (lane == 0) {
-            scene_composite_store(ray, na, s_id, s_w, w, dn, out_rgb, out_depth, out_opacity, out_instance);
+            scene_composite_store(s, ray, na, w, dn, out_rgb, out_depth, out_opacity, out_instance);
             out_hit_depth[ray] = w.hit ? w.hit_t / dn[ray] : 0.f;
-            out_hit_instance[ray] = w.hit ? (int32_t)s_id[w.hit_a] : -1;
+            out_hit_instance[ray] = w.hit ? (int32_t)s.id[w.hit_a] : -1;
         }
         __syncthreads();
     }
@@ -66,8 +60,7 @@ void launch_scene_probe_rays(hipStream_t s, const BatchPtrs& b, const Intrinsics
 void launch_scene_probe_composite(hipStream_t s, uint32_t n_rays, uint32_t n_lists, uint32_t cap, const float* t, const float* attr, const uint32_t* cnt,
         const float* dn, float* rgb, float* depth, float* opacity, int32_t* instance, float* hit_depth, int32_t* hit_instance) {
     if (!n_rays || !n_lists || n_lists > kSceneMaxLists) return;
-    const uint32_t grid = n_rays < 8192u ? n_rays : 8192u;
-    hipLaunchKernelGGL(k_scene_probe_composite, dim3(grid), dim3(64), scene_composite_lds(n_lists), s, n_rays, n_lists, cap, t,
+    hipLaunchKernelGGL(k_scene_probe_composite, dim3(scene_composite_grid(n_rays)), dim3(64), scene_composite_lds(n_lists), s, n_rays, n_lists, cap, t,
             reinterpret_cast<const float4*>(attr), cnt, dn, rgb, depth, opacity, instance, hit_depth, hit_instance);
 }
 

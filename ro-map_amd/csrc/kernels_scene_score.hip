@@ -23,21 +23,14 @@ __global__ void __launch_bounds__(256) k_scene_score_rays(SceneScoreRayArgs a) {
 // (b, g) walks rays b, b + parts, ... of hypothesis g in that order -- k_scene_composite_grad's walk of one evaluation on a grid of `parts` -- and writes
 // their summed losses to loss_part[g * parts + b].  Nothing else is stored.
 __global__ void __launch_bounds__(64) k_scene_composite_loss(SceneCompGradArgs a, uint32_t n_per) {
-    constexpr uint32_t L2S = kSceneListLen;
-    const uint32_t n_lists = a.n_lists;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint16_t* s_perm = reinterpret_cast<uint16_t*>(smem);                             // [L2S * n_lists] merged order: compact list << 6 | index
-    uint32_t* s_id = reinterpret_cast<uint32_t*>(smem + 2u * L2S * n_lists);          // [n_lists] compact list -> list
-    uint32_t* s_c = s_id + n_lists;                                                    // its count
-    float* s_tf = reinterpret_cast<float*>(s_c + n_lists);                             // its first t
-    float* s_tl = s_tf + n_lists;                                                      // its last t
-    float* s_w = s_tl + n_lists;                                                       // its summed weight W
+    const SceneLds s = scene_lds(smem, a.n_lists);
     const int lane = threadIdx.x;
     const uint32_t v0 = blockIdx.y * n_per;
     float loss_acc = 0.f;
     for (uint32_t r = blockIdx.x; r < n_per; r += gridDim.x) {
         SceneRayFwd f;
-        scene_composite_ray<false>(a, v0 + r, lane, s_perm, s_id, s_c, s_tf, s_tl, s_w, nullptr, nullptr, f);
+        scene_composite_ray<false>(a, s, v0 + r, lane, f);
         loss_acc += f.l;
         __syncthreads();
     }

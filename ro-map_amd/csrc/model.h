@@ -349,7 +349,18 @@ void launch_build_frag_image(hipStream_t s, const uint16_t* params, const NetDim
 // t [fp32], {alpha, r, g, b} [float4], and a count per (list, ray).  k_fused_render<EMIT> writes one object's lists (skip_bits: its render grid or nullptr;
 // the skip counters are not touched); k_scene_composite merges a ray's lists by t (ties to the lower list) and composites them front to back.
 constexpr uint32_t kSceneListLen = 64, kSceneMaxLists = 256;
-constexpr uint32_t scene_composite_lds(uint32_t n_lists) { return n_lists * (2u * kSceneListLen + 20u); }
+// The kernels' dynamic LDS (SceneLds, scene_device.h): the merged order, one uint16_t per sample slot, then kSceneLdsWords arrays of one 4-byte word per list
+// (kSceneLdsGradWords in the kernels that keep the composite gradient's two more).  scene_lds_word = the byte offset of word array i; that of the array
+// behind the last one is the size.
+constexpr uint32_t kSceneLdsWords = 5, kSceneLdsGradWords = kSceneLdsWords + 2;
+constexpr uint32_t scene_lds_word(uint32_t n_lists, uint32_t i) { return n_lists * (2u * kSceneListLen + 4u * i); }
+constexpr uint32_t scene_composite_lds(uint32_t n_lists) { return scene_lds_word(n_lists, kSceneLdsWords); }
+constexpr uint32_t scene_composite_grad_lds(uint32_t n_lists) { return scene_lds_word(n_lists, kSceneLdsGradWords); }
+static_assert(scene_composite_lds(1) == 2u * kSceneListLen + 20u && scene_composite_grad_lds(1) == 2u * kSceneListLen + 28u &&
+              scene_composite_lds(kSceneMaxLists) == kSceneMaxLists * (2u * kSceneListLen + 20u) &&
+              scene_composite_grad_lds(kSceneMaxLists) == kSceneMaxLists * (2u * kSceneListLen + 28u), "the LDS per list that profiles and DESIGN.md quote");
+// one workgroup per ray, at most 8 192 of them
+constexpr uint32_t scene_composite_grid(uint32_t n_rays) { return n_rays < 8192u ? n_rays : 8192u; }
 void launch_fused_render_emit(hipStream_t s, const LevelFast& lt, const NetDims& nd, const uint16_t* params, const BatchPtrs& b, const ObjectConst& oc,
         uint32_t n_rays, uint32_t idx_base, float* t, float* attr, uint32_t* cnt, uint16_t* frag_image, int build_image, const uint32_t* skip_bits,
         const uint32_t* keys = nullptr);
@@ -491,7 +502,6 @@ void launch_pose_update(hipStream_t s, const float* partials, uint32_t n_parts, 
 // partials per workgroup) -> per object k_scene_pose_obj<.., BWD = true> (MLP backward + position gradient, one partial row of 8 floats per workgroup);
 // per evaluation k_scene_pose_update (rows -> grad6 in the camera frame, Adam, Twc <- Twc exp(delta^)).
 constexpr uint32_t kSceneLossParts = 4096;
-constexpr uint32_t scene_composite_grad_lds(uint32_t n_lists) { return n_lists * (2u * kSceneListLen + 28u); }
 struct SceneObjConst { float Tow[16]; Aabb aabb; uint32_t instance_id; uint32_t pad; };
 struct ScenePoseRayArgs {
     const mon_frame_bbox* boxes; const uint32_t* prefix;      // the boxes and the exclusive prefix sums of their areas
