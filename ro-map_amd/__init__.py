@@ -14,6 +14,7 @@ from .binding import (MonConfig, MonBBox, MonError, Dataset, ObjectNeRF, default
                       SceneRay, SCENE_RAY_DTYPE, scene_rays, camera_rays, cast_scene, scene_cast_rays, scene_cast_composite,
                       query_object_points, query_scene_points, query_scene_lattice, lattice_points, scene_point_rows,
                       distance_transform, scene_distance_lattice,
+                      signed_distance_transform, scene_signed_distance_lattice, scene_signed_dist_field, edge_points, MON_SIGNED_LOG,
                       label_components, scene_components_lattice, LATTICE_COMPONENT_DTYPE,
                       shortest_paths, scene_paths_lattice, lattice_path, paths_stats,
                       DistField, DistFieldDesc, TrajScoreParams, ScanMatchParams, RegisterParams, TraceParams, BeamParams, dist_field_create, scene_dist_field,

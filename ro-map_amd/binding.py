@@ -269,6 +269,15 @@ _SIGS = {
     "mon_scene_dist_field": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
             C.POINTER(C.c_void_p)]),
     "mon_online_dist_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_void_p)]),
+    "mon_signed_distance_transform": (C.c_int, [C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "mon_scene_signed_distance_lattice": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint32,
+            C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_scene_signed_dist_field": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint32,
+            C.c_float, C.POINTER(C.c_void_p)]),
+    "mon_online_signed_distance_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint32, C.c_float,
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mon_online_signed_dist_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint32, C.c_float,
+            C.POINTER(C.c_void_p)]),
     "mon_dist_field_info": (C.c_int, [C.c_void_p, C.POINTER(DistFieldDesc)]),
     "mon_dist_field_read": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mon_dist_field_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
@@ -1041,6 +1050,22 @@ class OnlineManager:
         _check(lib().mon_online_dist_field(self.h, _p(o), _p(s), nx, ny, nz, float(sigma_min), float(max_dist), C.byref(h)))
         return DistField(h)
 
+    def signed_distance_lattice(self, origin, step, shape, sigma_min, max_dist=np.inf, log=True):
+        """mon_online_signed_distance_lattice: scene_signed_distance_lattice on side 1 over every object with published weights (safe while they train);
+        nearest_owner holds the manager's object indices."""
+        o, s, nx, ny, nz = _lattice_args(origin, step, shape); out = _signed_outputs(max(nx, 0) * max(ny, 0) * max(nz, 0))
+        _check(lib().mon_online_signed_distance_lattice(self.h, _p(o), _p(s), nx, ny, nz, float(sigma_min), MON_SIGNED_LOG if log else 0, float(max_dist),
+                                                        *[_p(a) for a in out]))
+        return out[:5] + (float(out[5][0]),)
+
+    def signed_dist_field(self, origin, step, shape, sigma_min, max_dist, log=True):
+        """mon_online_signed_dist_field: scene_signed_dist_field on side 1 over every object with published weights -> DistField, which does not follow
+        later training and stays valid after the manager is gone"""
+        o, s, nx, ny, nz = _lattice_args(origin, step, shape); h = C.c_void_p()
+        _check(lib().mon_online_signed_dist_field(self.h, _p(o), _p(s), nx, ny, nz, float(sigma_min), MON_SIGNED_LOG if log else 0, float(max_dist),
+                                                  C.byref(h)))
+        return DistField(h)
+
     def components_lattice(self, origin, step, shape, sigma_min, region=0, clearance=0.0, connectivity=6, cap=None, rows=()):
         """mon_online_components_lattice: scene_components_lattice on side 1 over every object with published weights (safe while they train); the
         owner row holds the manager's object indices."""
@@ -1361,6 +1386,59 @@ def scene_distance_lattice(objects, origin, step, shape, sigma_min, max_dist=np.
     _check(lib().mon_scene_distance_lattice(_handles(objects), len(objects), int(side), _p(o), _p(s), nx, ny, nz, float(sigma_min), float(max_dist),
                                             *[_p(a) for a in out]))
     return out
+
+
+MON_SIGNED_LOG = 1
+
+
+def _signed_outputs(n):
+    return (np.empty(n, np.float32), np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32), np.empty(n, np.float32), np.empty(1, np.float32))
+
+
+def signed_distance_transform(val, iso, step, max_dist=np.inf, device=0, nearest=True):
+    """mon_signed_distance_transform: the signed, sub-cell distance transform of values of shape (nz, ny, nx) (x fastest) with spacing step = (sx, sy, sz):
+    a cell is inside iff not (val <= iso), the surface crosses the lattice edges between cells of different sides at the linearly interpolated place.
+    Returns (sdist, nearest_edge), both of val's shape: the distance to the nearest crossing, negative inside, truncated by max_dist, and that edge as
+    3 * flat(lower cell) + axis (-1: none); nearest=False passes NULL and returns (sdist, None)."""
+    v = np.ascontiguousarray(val, np.float32); assert v.ndim == 3, "values of shape (nz, ny, nx)"
+    nz, ny, nx = v.shape; s = np.ascontiguousarray(step, np.float32).reshape(3)
+    sdist = np.empty(v.shape, np.float32); near = np.empty(v.shape, np.int32) if nearest else None
+    _check(lib().mon_signed_distance_transform(int(device), _p(v), float(iso), nx, ny, nz, _p(s), float(max_dist), _p(sdist), _p(near)))
+    return sdist, near
+
+
+def scene_signed_distance_lattice(objects, origin, step, shape, sigma_min, max_dist=np.inf, side=0, log=True):
+    """mon_scene_signed_distance_lattice: the object map's signed, sub-cell distance field over the lattice of query_scene_lattice: inside iff
+    not (sigma <= sigma_min); log: the crossings are placed in log density (MON_SIGNED_LOG), else in density.
+    Returns (sdist, nearest_edge, nearest_owner, sigma, val, iso): five arrays of nx * ny * nz elements and the level the device formed."""
+    o, s, nx, ny, nz = _lattice_args(origin, step, shape); out = _signed_outputs(max(nx, 0) * max(ny, 0) * max(nz, 0))
+    _check(lib().mon_scene_signed_distance_lattice(_handles(objects), len(objects), int(side), _p(o), _p(s), nx, ny, nz, float(sigma_min),
+                                                   MON_SIGNED_LOG if log else 0, float(max_dist), *[_p(a) for a in out]))
+    return out[:5] + (float(out[5][0]),)
+
+
+def edge_points(nearest_edge, val, iso, origin, step):
+    """Host helper: the world point of each cell's nearest crossing, (.., 3) float64, NaN where nearest_edge is -1.  val: the values of shape
+    (nz, ny, nx) the field was made from (scene_signed_distance_lattice's val), iso its level; the fraction along the edge is the header's f in fp32."""
+    v = np.ascontiguousarray(val, np.float32); nz, ny, nx = v.shape; flat = v.reshape(-1)
+    e = np.asarray(nearest_edge, np.int64); ok = e >= 0; ee = np.where(ok, e, 0)
+    a = ee % 3; q = ee // 3; other = np.minimum(q + np.asarray([1, nx, nx * ny])[a], flat.size - 1)
+    v0 = flat[q]; v1 = flat[other]
+    with np.errstate(all="ignore"):
+        f = (np.float32(iso) - v0) / (v1 - v0)
+    f = np.where((f >= 0) & (f <= 1), f, np.float32(0.5)).astype(np.float64)
+    ijk = np.stack([q % nx, (q // nx) % ny, q // (nx * ny)], -1).astype(np.float64) + f[..., None] * np.eye(3)[a]
+    pts = np.asarray(origin, np.float64) + ijk * np.asarray(step, np.float64)
+    pts[~ok] = np.nan
+    return pts
+
+
+def scene_signed_dist_field(objects, origin, step, shape, sigma_min, max_dist, side=0, log=True):
+    """mon_scene_signed_dist_field: scene_signed_distance_lattice's sdist for the same arguments, kept on the device -> DistField (defined below)"""
+    o, s, nx, ny, nz = _lattice_args(origin, step, shape); h = C.c_void_p()
+    _check(lib().mon_scene_signed_dist_field(_handles(objects), len(objects), int(side), _p(o), _p(s), nx, ny, nz, float(sigma_min),
+                                             MON_SIGNED_LOG if log else 0, float(max_dist), C.byref(h)))
+    return DistField(h)
 
 
 class DistField:

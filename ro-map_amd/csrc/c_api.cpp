@@ -216,6 +216,27 @@ int mon_scene_dist_field(mon_object* const* objs, size_t n_objs, int side, const
         (rc = scene_dist_field(ms.data(), n_objs, side, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, max_dist, &f))) return rc;
     *field = new mon_dist_field{ f }; return MON_OK;
 }
+int mon_signed_distance_transform(int device, const float* val, float iso, int nx, int ny, int nz, const float* step3, float max_dist, float* sdist,
+        int32_t* nearest_edge) {
+    { const int rc = signed_distance_transform_check(val, iso, nx, ny, nz, step3, max_dist, sdist); if (rc) return rc; }
+    return signed_distance_transform(device, val, iso, nx, ny, nz, step3, max_dist, sdist, nearest_edge);
+}
+int mon_scene_signed_distance_lattice(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz,
+        float sigma_min, uint32_t flags, float max_dist, float* sdist, int32_t* nearest_edge, int32_t* nearest_owner, float* sigma, float* val, float* iso_out) {
+    std::vector<Model*> ms; int rc;
+    if ((rc = scene_signed_distance_check(side, origin3, step3, nx, ny, nz, sigma_min, flags, max_dist, sdist)) ||
+        (rc = scene_models("scene_signed_distance", objs, n_objs, ms)) || (rc = scene_objects_check("scene_signed_distance", ms.data(), n_objs, false))) return rc;
+    return scene_signed_distance(ms.data(), n_objs, side, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, flags, max_dist, sdist, nearest_edge,
+                                 nearest_owner, sigma, val, iso_out, nullptr);
+}
+int mon_scene_signed_dist_field(mon_object* const* objs, size_t n_objs, int side, const float* origin3, const float* step3, int nx, int ny, int nz,
+        float sigma_min, uint32_t flags, float max_dist, mon_dist_field** field) {
+    std::vector<Model*> ms; int rc; DistField* f = nullptr;
+    if ((rc = scene_signed_dist_field_check(side, origin3, step3, nx, ny, nz, sigma_min, flags, max_dist, field)) ||
+        (rc = scene_models("scene_signed_dist_field", objs, n_objs, ms)) || (rc = scene_objects_check("scene_signed_dist_field", ms.data(), n_objs, false)) ||
+        (rc = scene_signed_dist_field(ms.data(), n_objs, side, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, flags, max_dist, &f))) return rc;
+    *field = new mon_dist_field{ f }; return MON_OK;
+}
 int mon_dist_field_info(mon_dist_field* field, mon_dist_field_desc* info) { return dist_field_info(field ? field->f : nullptr, info); }
 int mon_dist_field_read(mon_dist_field* field, float* dist_out) { return dist_field_read(field ? field->f : nullptr, dist_out); }
 int mon_dist_field_sample(mon_dist_field* field, const float* xyz, size_t n, float outside, float* dist_out, float* grad3_out) {

@@ -6,16 +6,11 @@
 // a^2).  Every product and sum is a __fmul_rn / __fadd_rn: nothing is contracted, so the bits are those of the brute force over all pairs
 // (tests/distance_reference.py).  k_distance_finish takes the root and applies max_dist.  No atomics, no scratch: equal arguments, equal bits.
 #include <algorithm>
-#include "model.h"
+#include "distance_device.h"
 
 namespace mon {
 
-// A line is cut into tiles of R = 2^logR cells; a workgroup owns a block of kDistTile cells, R along the lines by C = kDistTile / R lines side by side,
-// and every thread kDistOut of them, all on one line, in registers.  Input tiles of the same shape go through LDS one at a time.
-constexpr uint32_t kDistTile = 2048, kDistOut = kDistTile / 256;
-static_assert(kDistTile <= 4096, "a line tile holds at most 4 096 cells (a line may be 2^22 long: it is never held whole)");
-static_assert(kDistOut * 256 == kDistTile && kDistOut >= 1, "every thread owns kDistOut cells of the block");
-
+// The block shape (kDistTile, kDistOut), the block-wide maximum and an axis's lines and tile: distance_device.h, shared with the signed transform's seed pass.
 struct DistPassArgs {
     const uint8_t* occ; uint32_t invert;                        // the x pass: the mask (a cell counts iff (occ != 0) != invert); else nullptr and ...
     const float* v_in; const int32_t* s_in;                     // ... the pass before: squared distance so far (+inf: none) and its site (-1)
@@ -25,17 +20,6 @@ struct DistPassArgs {
     uint32_t logR, rows_fast;                                   // the tile; rows_fast: consecutive threads take consecutive cells of a line (the x pass)
     float step;
 };
-
-// the largest x of the workgroup (x >= 0, no NaN); `red`: four floats of LDS.  Two barriers.
-__device__ __forceinline__ float dist_block_max(float x, float* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x = fmaxf(x, __shfl_xor(x, off));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    x = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
-    return x;
-}
 
 // One pass.  Workgroup (line group cg, tile t_out of the lines): thread -> line c and rows r0 + o * dr of the tile, o < kDistOut.  With rows_fast the
 // threads of a line are consecutive (the x pass: a line is contiguous in memory); otherwise consecutive threads take consecutive lines (the y and z passes:
@@ -139,27 +123,28 @@ __global__ void __launch_bounds__(256) k_distance_finish(uint32_t n, const float
     if (nearest_owner) nearest_owner[i] = s >= 0 ? owner[s] : -1;
 }
 
-static uint32_t ceil_log2(uint32_t x) { uint32_t l = 0; while ((1u << l) < x) ++l; return l; }
-
 void launch_distance_mask(hipStream_t s, uint32_t n, const float* sigma, float sigma_min, uint8_t* occ) {
     hipLaunchKernelGGL(k_distance_mask, dim3((n + 255u) / 256u), dim3(256), 0, s, n, sigma, sigma_min, occ);
 }
+// one pass along axis ax: from the mask (occ; inverted or not), or with occ == nullptr from the values and sites of a pass before
+static void distance_axis_launch(hipStream_t s, int ax, const Lattice& g, const uint8_t* occ, bool invert, const float* v_in, const int32_t* s_in, float* v_out,
+        int32_t* s_out) {
+    const DistAxis x = dist_axis(g, ax);
+    DistPassArgs a{};
+    if (occ) { a.occ = occ; a.invert = invert ? 1u : 0u; } else { a.v_in = v_in; a.s_in = s_in; }
+    a.v_out = v_out; a.s_out = s_out;
+    a.n = x.n; a.m = x.m; a.stride = x.stride; a.cw = x.cw; a.cs = x.cs; a.step = x.step; a.rows_fast = x.rows_fast; a.logR = x.logR;
+    hipLaunchKernelGGL(k_distance_pass, dim3(x.blocks()), dim3(256), 0, s, a);
+}
+void launch_distance_axis(hipStream_t s, int ax, const Lattice& g, const float* v_in, const int32_t* s_in, float* v_out, int32_t* s_out) {
+    distance_axis_launch(s, ax, g, nullptr, false, v_in, s_in, v_out, s_out);
+}
 // the three passes: occ (inverted or not) -> d2, site in v[0 .. n), site[0 .. n); v and site hold 2 n elements each (the passes alternate between the halves)
 void launch_distance_passes(hipStream_t s, const uint8_t* occ, bool invert, const Lattice& g, float* v, int32_t* site) {
-    const uint32_t nx = (uint32_t)g.nx, ny = (uint32_t)g.ny, nz = (uint32_t)g.nz, n = nx * ny * nz;
-    const uint32_t len[3] = { nx, ny, nz }, lines[3] = { ny * nz, nx * nz, nx * ny }, stride[3] = { 1u, nx, nx * ny };
-    const uint32_t cw[3] = { 1u, nx, nx * ny }, cs[3] = { nx, nx * ny, 0u };
+    const uint32_t n = (uint32_t)g.n();
     for (int ax = 0; ax < 3; ++ax) {
-        DistPassArgs a{};
         const uint32_t in = ax == 1 ? 0u : n, out = ax == 1 ? n : 0u;       // x: mask -> low half; y: low -> high; z: high -> low
-        if (ax == 0) { a.occ = occ; a.invert = invert ? 1u : 0u; } else { a.v_in = v + in; a.s_in = site + in; }
-        a.v_out = v + out; a.s_out = site + out;
-        a.n = len[ax]; a.m = lines[ax]; a.stride = stride[ax]; a.cw = cw[ax]; a.cs = cs[ax]; a.step = g.step[ax];
-        a.rows_fast = ax == 0 ? 1u : 0u;
-        // x: the tile as long as the line allows (at least kDistOut rows: a thread's cells are rows of one line); y, z: up to 64 lines side by side
-        a.logR = ax == 0 ? std::min(std::max(ceil_log2(a.n), ceil_log2(kDistOut)), ceil_log2(kDistTile)) : ceil_log2(kDistTile) - std::min(ceil_log2(a.m), 6u);
-        const uint32_t R = 1u << a.logR, C = kDistTile >> a.logR;
-        hipLaunchKernelGGL(k_distance_pass, dim3(((a.m + C - 1u) / C) * ((a.n + R - 1u) / R)), dim3(256), 0, s, a);
+        distance_axis_launch(s, ax, g, ax == 0 ? occ : nullptr, invert, v + in, site + in, v + out, site + out);
     }
 }
 void launch_distance_finish(hipStream_t s, uint32_t n, const float* d2, const int32_t* site, float max_dist, const int32_t* owner, float* dist,

@@ -797,6 +797,28 @@ int mon_online_dist_field(mon_online* h, const float* origin3, const float* step
         (rc = scene_dist_field(ms.data(), ms.size(), 1, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, max_dist, &f))) return rc;
     *field = new mon_dist_field{ f }; return MON_OK;
 }
+// the published map's signed, sub-cell field: mon_scene_signed_distance_lattice and mon_scene_signed_dist_field on side 1 over the same objects;
+// nearest_owner holds the manager's indices, the handle refers to nothing of the manager's
+int mon_online_signed_distance_lattice(mon_online* h, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, uint32_t flags,
+        float max_dist, float* sdist, int32_t* nearest_edge, int32_t* nearest_owner, float* sigma, float* val, float* iso_out) {
+    REQ(h);
+    std::vector<Model*> ms; std::vector<int32_t> ids; int rc;
+    if ((rc = scene_signed_distance_check(1, origin3, step3, nx, ny, nz, sigma_min, flags, max_dist, sdist)) ||
+        (rc = online_published(h, "signed_distance_lattice", 0, false, ms, &ids)) ||
+        (rc = scene_objects_check("scene_signed_distance", ms.data(), ms.size(), false))) return rc;
+    return scene_signed_distance(ms.data(), ms.size(), 1, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, flags, max_dist, sdist, nearest_edge,
+                                 nearest_owner, sigma, val, iso_out, ids.data());
+}
+int mon_online_signed_dist_field(mon_online* h, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, uint32_t flags,
+        float max_dist, mon_dist_field** field) {
+    REQ(h);
+    std::vector<Model*> ms; int rc; DistField* f = nullptr;
+    if ((rc = scene_signed_dist_field_check(1, origin3, step3, nx, ny, nz, sigma_min, flags, max_dist, field)) ||
+        (rc = online_published(h, "signed_dist_field", 0, false, ms, nullptr)) ||
+        (rc = scene_objects_check("scene_signed_dist_field", ms.data(), ms.size(), false)) ||
+        (rc = scene_signed_dist_field(ms.data(), ms.size(), 1, scene_lattice(origin3, step3, nx, ny, nz), sigma_min, flags, max_dist, &f))) return rc;
+    *field = new mon_dist_field{ f }; return MON_OK;
+}
 // ... with the field's derivative: mon_scene_query_gradients on side 1 over the same objects.  select names objects as owner does, by the manager's index:
 // -1, or the index of an object with published weights (anything else is MON_ERR_ARG; what is below -1 is refused before the objects are looked at).
 int mon_online_query_gradients(mon_online* h, const float* world_xyz, size_t n, const float* level_weights, const int32_t* select, float* sigma, float* rgb,

@@ -416,6 +416,18 @@ void launch_distance_mask(hipStream_t s, uint32_t n, const float* sigma, float s
 void launch_distance_passes(hipStream_t s, const uint8_t* occ, bool invert, const Lattice& g, float* v, int32_t* site);
 void launch_distance_finish(hipStream_t s, uint32_t n, const float* d2, const int32_t* site, float max_dist, const int32_t* owner, float* dist,
         int32_t* nearest, int32_t* nearest_owner);
+// launch_distance_axis: one pass of k_distance_pass along axis ax (0, 1, 2) from the values and sites of a pass before (launch_distance_passes' y and z
+// pass; any axis may be run so).
+void launch_distance_axis(hipStream_t s, int ax, const Lattice& g, const float* v_in, const int32_t* s_in, float* v_out, int32_t* s_out);
+// Signed, sub-cell distance fields (mon_signed_distance_transform, mon_scene_signed_distance_lattice; kernels_signed_distance.hip).  k_signed_values:
+// ins[i] = !(sigma[i] <= sigma_min), val[i] = sigma[i] or logf(sigma[i]) (val nullptr: not written), iso_out[0] = sigma_min or logf(sigma_min) (nullptr:
+// not written).  launch_signed_passes (the level: iso_p[0] on the device, nullptr: iso): per axis k_surface_line_pass and two passes of k_distance_pass -> the three chains' squared distances and edges in
+// v[0 .. 3 n) and site[0 .. 3 n); v and site hold 4 n elements.  k_signed_finish: the least of the three, the root, max_dist, the sign from ins;
+// nearest_edge and nearest_owner (= owner[the inside end of the edge]; owner: device, [n]) may be nullptr.
+void launch_signed_values(hipStream_t s, uint32_t n, const float* sigma, float sigma_min, bool use_log, float* val, uint8_t* ins, float* iso_out);
+void launch_signed_passes(hipStream_t s, const float* val, const uint8_t* ins, const float* iso_p, float iso, const Lattice& g, float* v, int32_t* site);
+void launch_signed_finish(hipStream_t s, const Lattice& g, const float* v, const int32_t* site, const uint8_t* ins, float max_dist, const int32_t* owner,
+        float* sdist, int32_t* nearest_edge, int32_t* nearest_owner);
 // Connected components (mon_label_components, mon_scene_components_lattice; kernels_components.hip).  launch_components: the mask occ[n] -> label[n] and
 // comp[n] (both required here), the count in meta[0] and the cap flag in meta[1] (meta: 2 words, cleared first; a flag other than 0 afterwards: a device
 // loop ran into its cap), the records of the components below cap in table (nullptr: none; room for min(cap, n) records).  scan: components_scan_words(n)
@@ -845,6 +857,21 @@ int distance_transform(int device, const uint8_t* occupied, int nx, int ny, int 
 int scene_distance_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float max_dist, const float* dist);
 int scene_distance(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, float max_dist, float* dist, int32_t* nearest,
                    int32_t* nearest_owner, float* free_dist, float* sigma, const int32_t* ids);
+// Signed, sub-cell distance fields (mon_signed_distance_transform, mon_scene_signed_distance_lattice, mon_scene_signed_dist_field):
+// signed_distance_transform = the nine passes and the finish on host values, in buffers of its own.  scene_signed_distance = the lattice query, the
+// values (flags & MON_SIGNED_LOG: in log density) and the transform behind it on the device; every output but sdist may be nullptr; ids as scene_points',
+// applied to nearest_owner.  scene_signed_dist_field keeps sdist in a handle (dist_field.cpp): nothing per cell goes home.
+int signed_distance_transform_check(const float* val, float iso, int nx, int ny, int nz, const float* step3, float max_dist, const float* sdist);
+int signed_distance_transform(int device, const float* val, float iso, int nx, int ny, int nz, const float* step3, float max_dist, float* sdist,
+                              int32_t* nearest_edge);
+int scene_signed_distance_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, uint32_t flags, float max_dist,
+                                const float* sdist);
+int scene_signed_distance(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, uint32_t flags, float max_dist, float* sdist,
+                          int32_t* nearest_edge, int32_t* nearest_owner, float* sigma, float* val, float* iso_out, const int32_t* ids);
+struct DistField;
+int scene_signed_dist_field_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, uint32_t flags, float max_dist,
+                                  const void* field_out);
+int scene_signed_dist_field(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, uint32_t flags, float max_dist, DistField** out);
 // Connected components (mon_label_components, mon_scene_components_lattice): label_components = the labelling of a host mask in buffers of its own
 // (MON_ERR_NO_DEVICE without a device, after its check).  scene_components = the lattice query with the mask !(sigma <= sigma_min) (region 0) or, behind
 // the untruncated distance transform of that mask, dist > clearance (region 1), and the labelling behind it on the device; every output but label may

@@ -136,7 +136,7 @@ struct SceneWs {
     DevBuf<mon_scene_ray> rays; DevBuf<float> entry;                              // scene_cast: the rays, a pass's box entries [lists][cap]
     DevBuf<float> pts, rows;                                                      // field queries: the points [n][3], a pass's rows [objects][cap][12 or 16]
     DevBuf<uint16_t> gfrag; DevBuf<float> lw; DevBuf<int32_t> sel;                // gradients (rows of 16): full fragment images, weights [Lmax], select [n]
-    DevBuf<uint8_t> docc; DevBuf<float> dv; DevBuf<int32_t> dsite;                // lattice routes: the mask [n], the passes' squared distances and sites [2][n]
+    DevBuf<uint8_t> docc; DevBuf<float> dv; DevBuf<int32_t> dsite;                // lattice routes: the mask [n], the passes' squared distances and sites [2][n] (the signed routes: [4][n])
     DevBuf<uint32_t> cscan;                                                       // scene_components: the numbering's block sums (its mask is docc)
     DevBuf<float> pcost, pmul; DevBuf<int32_t> pseeds; DevBuf<uint8_t> pflags;    // scene_paths: the working cost [n], the multiplier [n], the seeds, two flag
     DevBuf<uint32_t> praised; PinnedBuf<uint32_t> h_raised;                       // bytes per tile, a batch's "left work" words and their pinned copy (mask: docc)

@@ -427,6 +427,109 @@ int scene_dist_field(Model* const* ms, size_t n, int side, const ScenePoints& q,
     return MON_OK;
 }
 
+// ---- signed, sub-cell distance fields (mon_signed_distance_transform, mon_scene_signed_distance_lattice, mon_scene_signed_dist_field; DESIGN.md
+// 3.4c-12): the distance to the density's level set placed inside the lattice edges, negative inside matter.  The scene calls: the lattice chain, the values
+// (k_signed_values: val, iso and the side, which replaces the mask in ws.docc by the same bits), the nine passes in ws.dv and ws.dsite ([4][n] here: three
+// chains' results and the passes' other half, 32 B per cell) and the finish; one copy home, one synchronisation.
+static int signed_flags_check(const char* what, uint32_t flags) {
+    if (flags & ~(uint32_t)MON_SIGNED_LOG) { set_error("%s: flags %#x (MON_SIGNED_LOG or 0)", what, flags); return MON_ERR_ARG; }
+    return MON_OK;
+}
+int signed_distance_transform_check(const float* val, float iso, int nx, int ny, int nz, const float* step3, float max_dist, const float* sdist) {
+    const char* what = "signed_distance_transform";
+    REQUIRE_ARG(what, val, "val"); REQUIRE_ARG(what, step3, "step");
+    { int rc; if ((rc = lattice_dims_check(what, nx, ny, nz, kSceneProbeMaxQueries)) || (rc = step_finite_check(what, step3))) return rc; }
+    if (std::isnan(iso)) { set_error("%s: iso is NaN", what); return MON_ERR_ARG; }
+    return distance_outputs_check(what, max_dist, sdist);
+}
+int scene_signed_distance_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, uint32_t flags, float max_dist,
+                                const float* sdist) {
+    const char* what = "scene_signed_distance";
+    int rc;
+    if ((rc = lattice_route_check(what, side, origin3, step3, nx, ny, nz, sigma_min)) || (rc = signed_flags_check(what, flags))) return rc;
+    return distance_outputs_check(what, max_dist, sdist);
+}
+// mon_signed_distance_transform: the transform alone on host values, in buffers of its own on the device's default stream
+int signed_distance_transform(int device, const float* val, float iso, int nx, int ny, int nz, const float* step3, float max_dist, float* sdist,
+                              int32_t* nearest_edge) {
+    { const int rc = device_enter(device); if (rc) return rc; }
+    const Lattice g(nullptr, step3, nx, ny, nz); const size_t n = g.n();
+    DevBuf<uint8_t> ins; DevBuf<float> v; DevBuf<int32_t> site;                     // v: val | the passes' four parts | sdist; site: the four parts | nearest_edge
+    { int rc; if ((rc = ins.grow(n)) || (rc = v.grow(6 * n)) || (rc = site.grow(5 * n))) return rc; }
+    HIPCHECK(hipMemcpy(v.p, val, 4 * n, hipMemcpyHostToDevice));
+    launch_signed_values(nullptr, (uint32_t)n, v.p, iso, false, nullptr, ins.p, nullptr);
+    launch_signed_passes(nullptr, v.p, ins.p, nullptr, iso, g, v.p + n, site.p);
+    launch_signed_finish(nullptr, g, v.p + n, site.p, ins.p, max_dist, nullptr, v.p + 5 * n, nearest_edge ? site.p + 4 * n : nullptr, nullptr);
+    HIPCHECK(hipGetLastError());
+    std::vector<float> h_dist(n); std::vector<int32_t> h_near(nearest_edge ? n : 0);   // (the caller's arrays are written only once everything has succeeded)
+    HIPCHECK(hipMemcpy(h_dist.data(), v.p + 5 * n, 4 * n, hipMemcpyDeviceToHost));
+    if (nearest_edge) HIPCHECK(hipMemcpy(h_near.data(), site.p + 4 * n, 4 * n, hipMemcpyDeviceToHost));
+    std::memcpy(sdist, h_dist.data(), 4 * n);
+    if (nearest_edge) std::memcpy(nearest_edge, h_near.data(), 4 * n);
+    return MON_OK;
+}
+// What the two scene calls share.  The rows: iso (four words) | sigma | sdist | nearest_edge | nearest_owner | val, then the fold's other rows.
+struct SignedRows { FoldRows f; size_t iso, sdist, edge, edge_owner, val; };
+static SignedRows signed_rows(Area& A, float* sigma, float* sdist, int32_t* nearest_edge, int32_t* nearest_owner, float* val, bool iso_home) {
+    SignedRows r; r.iso = iso_home ? A.keep(4) : A.take(4); r.f.sigma = A.out(sigma); r.sdist = A.out(sdist); r.edge = A.out(nearest_edge);
+    r.edge_owner = A.out(nearest_owner, 1, true); r.val = A.out(val); fold_rows_rest(A, r.f, false);
+    return r;
+}
+static int signed_chain(const SceneCall& c, Model* const* ms, size_t n, const ScenePoints& q, float sigma_min, uint32_t flags, float max_dist, const Area& A,
+                        const SignedRows& r, bool nearest_edge, bool nearest_owner) {
+    { const int rc = lattice_occupancy(c, ms, n, q, A, r.f, sigma_min); if (rc) return rc; }
+    SceneWs& ws = *c.ws; float* o = ws.out.p;
+    { int rc; if ((rc = ws.dv.grow(4 * q.n)) || (rc = ws.dsite.grow(4 * q.n))) return rc; }
+    launch_signed_values(c.s, (uint32_t)q.n, o + r.f.sigma, sigma_min, (flags & MON_SIGNED_LOG) != 0u, o + r.val, ws.docc.p, o + r.iso);
+    launch_signed_passes(c.s, o + r.val, ws.docc.p, o + r.iso, 0.f, q.g, ws.dv.p, ws.dsite.p);
+    launch_signed_finish(c.s, q.g, ws.dv.p, ws.dsite.p, ws.docc.p, max_dist, as_i32(o + r.f.owner), o + r.sdist, nearest_edge ? as_i32(o + r.edge) : nullptr,
+            nearest_owner ? as_i32(o + r.edge_owner) : nullptr);
+    return MON_OK;
+}
+// q: a lattice (scene_lattice).  ids as scene_points', applied to nearest_owner.
+int scene_signed_distance(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, uint32_t flags, float max_dist, float* sdist,
+                          int32_t* nearest_edge, int32_t* nearest_owner, float* sigma, float* val, float* iso_out, const int32_t* ids) {
+    SceneCall c; { const int rc = c.enter("scene_signed_distance", ms, n, side, false); if (rc) return rc; }
+    Area A{ q.n }; const SignedRows r = signed_rows(A, sigma, sdist, nearest_edge, nearest_owner, val, iso_out != nullptr);
+    { const int rc = signed_chain(c, ms, n, q, sigma_min, flags, max_dist, A, r, nearest_edge != nullptr, nearest_owner != nullptr); if (rc) return rc; }
+    { const int rc = c.home(A.home); if (rc) return rc; }
+    A.unpack(c.ws->h_out.p, ids);
+    if (iso_out) *iso_out = c.ws->h_out.p[r.iso];
+    return MON_OK;
+}
+// mon_scene_signed_dist_field / mon_online_signed_dist_field: the same chain with sdist kept on the device, as scene_dist_field keeps dist: four words for
+// the field's largest value go home, sdist goes into the handle's buffer by a device-to-device copy.
+int scene_signed_dist_field_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, uint32_t flags, float max_dist,
+                                  const void* field_out) {
+    const char* what = "scene_signed_dist_field";
+    REQUIRE_ARG(what, field_out, "field");
+    int rc;
+    if ((rc = lattice_route_check(what, side, origin3, step3, nx, ny, nz, sigma_min)) || (rc = signed_flags_check(what, flags))) return rc;
+    if (!std::isfinite(max_dist) || !(max_dist > 0.f)) { set_error("%s: max_dist %g (finite, above 0)", what, (double)max_dist); return MON_ERR_ARG; }
+    const int dims[3] = { nx, ny, nz };
+    for (int a = 0; a < 3; ++a) if (dims[a] > 1 && step3[a] == 0.f) { set_error("%s: step 0 on axis %d, which has %d cells", what, a, dims[a]);
+        return MON_ERR_ARG; }
+    return MON_OK;
+}
+int scene_signed_dist_field(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, uint32_t flags, float max_dist, DistField** out) {
+    SceneCall c; { const int rc = c.enter("scene_signed_dist_field", ms, n, side, false); if (rc) return rc; }
+    SceneWs& ws = *c.ws; const hipStream_t s = c.s;
+    Area A{ q.n }; const size_t r_max = A.keep(4); const SignedRows r = signed_rows(A, nullptr, nullptr, nullptr, nullptr, nullptr, false);
+    const size_t r_part = A.take(kFieldMaxBlocks); DistField* f = nullptr;
+    { const int rc = dist_field_adopt(ms[0]->device, q.g, &f); if (rc) return rc; }
+    int rc = signed_chain(c, ms, n, q, sigma_min, flags, max_dist, A, r, false, false);
+    if (!rc) {
+        float* o = ws.out.p;
+        const hipError_t e = hipMemcpyAsync(f->cells, o + r.sdist, 4 * q.n, hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) { set_error("scene_signed_dist_field: the copy into the handle failed: %s", hipGetErrorString(e)); rc = MON_ERR_HIP; }
+        else { launch_field_max(s, o + r.sdist, (uint32_t)q.n, o + r_part, o + r_max); rc = c.home(A.home); }
+    }
+    if (rc) { dist_field_free(f); return rc; }
+    f->max_value = ws.h_out.p[r_max];
+    *out = f;
+    return MON_OK;
+}
+
 // ---- connected components (mon_label_components, mon_scene_components_lattice): which cells belong together.  scene_components: the
 // lattice chain (region 1: with its second stage), the labelling (launch_components; its block sums are 4 B per 256 cells), k_cc_home and one synchronisation.
 static int components_outputs_check(const char* what, int connectivity, const int32_t* label, const mon_lattice_component* table, const uint32_t* n_components) {
