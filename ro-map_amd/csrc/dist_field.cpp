@@ -2,7 +2,8 @@
 // DistField is a snapshot: its cells in device memory of its own, the lattice they sit on, a stream and the scratch of its calls.  It refers to no object
 // and to no manager.  A call on a handle goes through FieldCall (the handle's lock and device, room for inputs, outputs and staging, one copy home): it uploads its
 // inputs, enqueues one kernel and the copy of its outputs to the pinned staging on the handle's stream, and synchronises once; calls on one handle take
-// turns on its mutex.  (mon_scene_dist_field's chain is scene_field.cpp's: it fills a handle made by
+// turns on its mutex.  The sample, score and trace calls describe their outputs once, as an Area (model_internal.h): the pieces' offsets give the kernels'
+// pointers, A.end sizes room and home, A.unpack fills the caller's arrays.  (mon_scene_dist_field's chain is scene_field.cpp's: it fills a handle made by
 // dist_field_adopt.)  Scan matching (mon_dist_field_match, mon_dist_field_register) is here too: the match call follows the same
 // pattern; the register call keeps the scan on the device and runs Levenberg-Marquardt over all hypotheses in lockstep, one match launch, one read-back and
 // one synchronisation per round, with the 6 x 6 solves and the pose updates on the host in double.
@@ -107,13 +108,13 @@ int dist_field_sample(DistField* field, const float* xyz, size_t n, float outsid
     REQUIRE_ARG(what, xyz, "xyz"); REQUIRE_ARG(what, dist_out, "dist_out");
     if (n == 0 || n > kFieldMaxPoints) { set_error("%s: %zu points (1 to %zu)", what, n, kFieldMaxPoints); return MON_ERR_ARG; }
     FieldCall c; { const int rc = c.enter(what, field); if (rc) return rc; }
-    DistField& f = *c.f; const size_t n_out = grad3_out ? 4 * n : n;
-    { const int rc = c.room(3 * n, n_out, n_out); if (rc) return rc; }
+    DistField& f = *c.f;
+    Area A; const size_t r_dist = A.piece(dist_out, n), r_grad = A.piece(grad3_out, grad3_out ? 3 * n : 0);
+    { const int rc = c.room(3 * n, A.end, A.end); if (rc) return rc; }
     HIPCHECK(hipMemcpyAsync(f.in.p, xyz, 12 * n, hipMemcpyHostToDevice, f.s));
-    launch_field_sample(f.s, f.cells, f.g, f.in.p, (uint32_t)n, outside, f.out.p, grad3_out ? f.out.p + n : nullptr);
-    { const int rc = c.home(f.out.p, n_out); if (rc) return rc; }
-    std::memcpy(dist_out, f.h_out.p, 4 * n);
-    if (grad3_out) std::memcpy(grad3_out, f.h_out.p + n, 12 * n);
+    launch_field_sample(f.s, f.cells, f.g, f.in.p, (uint32_t)n, outside, f.out.p + r_dist, grad3_out ? f.out.p + r_grad : nullptr);
+    { const int rc = c.home(f.out.p, A.end); if (rc) return rc; }
+    A.unpack(f.h_out.p, nullptr);
     return MON_OK;
 }
 static int score_check(const char* what, const float* spheres, size_t n_spheres, const float* ways, int way_floats, size_t n_traj,
@@ -136,7 +137,8 @@ static int score_check(const char* what, const float* spheres, size_t n_spheres,
     if (!std::isfinite(p->outside) || !std::isfinite(p->margin) || !std::isfinite(p->safe)) { set_error("%s: a param is not finite", what); return MON_ERR_ARG; }
     return MON_OK;
 }
-// in: spheres [n_spheres][4] (padded to 32 records) | ways.  out: min_clear | first_hit | cost (n_traj each) | way_clear | way_grad, those asked for
+// in: spheres [n_spheres][4] (padded to 32 records) | ways.  out: min_clear | first_hit | cost (n_traj each, asked for or not) | way_clear | way_grad, those
+// asked for; the whole area comes home
 int dist_field_score(DistField* field, const float* spheres, size_t n_spheres, const float* ways, int way_floats, size_t n_traj, size_t n_way, size_t n_sub,
                      const mon_traj_score_params* p, float* min_clear, int32_t* first_hit, float* cost, float* way_clear, float* way_grad) {
     const char* what = "dist_field_score";
@@ -144,8 +146,9 @@ int dist_field_score(DistField* field, const float* spheres, size_t n_spheres, c
     FieldCall c; { const int rc = c.enter(what, field); if (rc) return rc; }
     DistField& f = *c.f;
     const size_t n_ways = n_traj * n_way, way_words = n_ways * (size_t)way_floats, at_ways = 4 * kFieldMaxSpheres;
-    const size_t r_min = 0, r_hit = n_traj, r_cost = 2 * n_traj, r_wc = 3 * n_traj, r_wg = r_wc + (way_clear ? n_ways : 0), n_out = r_wg + (way_grad ? 3 * n_ways : 0);
-    { const int rc = c.room(at_ways + way_words, n_out, n_out); if (rc) return rc; }
+    Area A; const size_t r_min = A.piece(min_clear, n_traj), r_hit = A.piece(first_hit, n_traj), r_cost = A.piece(cost, n_traj);
+    const size_t r_wc = A.piece(way_clear, way_clear ? n_ways : 0), r_wg = A.piece(way_grad, way_grad ? 3 * n_ways : 0);
+    { const int rc = c.room(at_ways + way_words, A.end, A.end); if (rc) return rc; }
     HIPCHECK(hipMemcpyAsync(f.in.p, spheres, 16 * n_spheres, hipMemcpyHostToDevice, f.s));
     HIPCHECK(hipMemcpyAsync(f.in.p + at_ways, ways, 4 * way_words, hipMemcpyHostToDevice, f.s));
     float* o = f.out.p;
@@ -155,13 +158,8 @@ int dist_field_score(DistField* field, const float* spheres, size_t n_spheres, c
     a.min_clear = o + r_min; a.first_hit = first_hit ? reinterpret_cast<int32_t*>(o + r_hit) : nullptr; a.cost = cost ? o + r_cost : nullptr;
     a.way_clear = way_clear ? o + r_wc : nullptr; a.way_grad = way_grad ? o + r_wg : nullptr;
     launch_traj_score(f.s, f.cells, f.g, f.in.p, (uint32_t)n_spheres, f.in.p + at_ways, way_floats == 16, a);
-    { const int rc = c.home(f.out.p, n_out); if (rc) return rc; }
-    const float* h = f.h_out.p;
-    std::memcpy(min_clear, h + r_min, 4 * n_traj);
-    if (first_hit) std::memcpy(first_hit, h + r_hit, 4 * n_traj);
-    if (cost) std::memcpy(cost, h + r_cost, 4 * n_traj);
-    if (way_clear) std::memcpy(way_clear, h + r_wc, 4 * n_ways);
-    if (way_grad) std::memcpy(way_grad, h + r_wg, 12 * n_ways);
+    { const int rc = c.home(f.out.p, A.end); if (rc) return rc; }
+    A.unpack(f.h_out.p, nullptr);
     return MON_OK;
 }
 
@@ -201,6 +199,15 @@ static int match_round(FieldCall& c, const MatchRoom& r, size_t n, const float* 
     return c.home(f.out.p + r.at_rows, (normal ? kScanMatchRow : kScanMatchLite) * live);
 }
 constexpr int kRowCost = 27, kRowInside = 28, kRowInlier = 29;                      // a full row: 21 A terms, 6 b terms, then these
+// H rows of `width` words at home: the cost at column c0 and the two counts behind it (either may not be asked for)
+static void rows_unpack(const float* rows, size_t H, size_t width, size_t c0, float* cost, int32_t* count1, int32_t* count2) {
+    for (size_t h = 0; h < H; ++h) {
+        const float* row = rows + width * h;
+        cost[h] = row[c0];
+        if (count1) count1[h] = (int32_t)row[c0 + 1];
+        if (count2) count2[h] = (int32_t)row[c0 + 2];
+    }
+}
 
 int dist_field_match(DistField* field, const float* points, size_t n, const float* poses16, size_t H, const float* pivots, const mon_scan_match_params* p,
                      float* cost, int32_t* n_inside, int32_t* n_inlier, float* normal) {
@@ -211,14 +218,8 @@ int dist_field_match(DistField* field, const float* points, size_t n, const floa
     DistField* const f = c.f; MatchRoom r;
     { const int rc = match_room(c, points, n, H, r); if (rc) return rc; }
     { const int rc = match_round(c, r, n, poses16, pivots, H, p->huber, p->outside, normal != nullptr); if (rc) return rc; }
-    const size_t w = normal ? kScanMatchRow : kScanMatchLite, c0 = normal ? kRowCost : 0;
-    for (size_t h = 0; h < H; ++h) {
-        const float* row = f->h_out.p + w * h;
-        cost[h] = row[c0];
-        if (n_inside) n_inside[h] = (int32_t)row[c0 + 1];
-        if (n_inlier) n_inlier[h] = (int32_t)row[c0 + 2];
-        if (normal) std::memcpy(normal + 27 * h, row, 4 * 27);
-    }
+    rows_unpack(f->h_out.p, H, normal ? kScanMatchRow : kScanMatchLite, normal ? kRowCost : 0, cost, n_inside, n_inlier);
+    for (size_t h = 0; normal && h < H; ++h) std::memcpy(normal + 27 * h, f->h_out.p + kScanMatchRow * h, 4 * 27);
     return MON_OK;
 }
 
@@ -423,20 +424,17 @@ int dist_field_trace(DistField* field, const float* rays, size_t n, const float*
     FieldCall c; { const int rc = c.enter(what, field); if (rc) return rc; }
     DistField& f = *c.f;
     const size_t m = n * H, at_pose = round4(6 * n);
-    const size_t r_status = m, r_steps = r_status + (status ? m : 0), r_normal = r_steps + (steps ? m : 0), n_out = r_normal + (normal3 ? 3 * m : 0);
-    { const int rc = c.room(at_pose + 16 * H, n_out, n_out); if (rc) return rc; }
+    Area A; const size_t r_range = A.piece(range, m), r_status = A.piece(status, status ? m : 0), r_steps = A.piece(steps, steps ? m : 0);
+    const size_t r_normal = A.piece(normal3, normal3 ? 3 * m : 0);
+    { const int rc = c.room(at_pose + 16 * H, A.end, A.end); if (rc) return rc; }
     FieldTraceArgs a;
     { const int rc = trace_upload(c, rays, n, poses16, H, at_pose, p, a); if (rc) return rc; }
     float* o = f.out.p;
-    a.stride = (uint32_t)n; a.range = o; a.status = status ? reinterpret_cast<int32_t*>(o + r_status) : nullptr;
+    a.stride = (uint32_t)n; a.range = o + r_range; a.status = status ? reinterpret_cast<int32_t*>(o + r_status) : nullptr;
     a.steps = steps ? reinterpret_cast<int32_t*>(o + r_steps) : nullptr; a.normal = normal3 ? o + r_normal : nullptr;
     launch_field_trace(f.s, f.cells, f.g, a);
-    { const int rc = c.home(f.out.p, n_out); if (rc) return rc; }
-    const float* h = f.h_out.p;
-    std::memcpy(range, h, 4 * m);
-    if (status) std::memcpy(status, h + r_status, 4 * m);
-    if (steps) std::memcpy(steps, h + r_steps, 4 * m);
-    if (normal3) std::memcpy(normal3, h + r_normal, 12 * m);
+    { const int rc = c.home(f.out.p, A.end); if (rc) return rc; }
+    A.unpack(f.h_out.p, nullptr);
     return MON_OK;
 }
 // in: rays | measured | poses.  out: range | status ([H][stride] each, stride = n rounded up to a multiple of 4) | the fold's scratch | rows [H][4]; only
@@ -461,12 +459,7 @@ int dist_field_beam_score(DistField* field, const float* rays, size_t n, const f
     launch_field_trace(f.s, f.cells, f.g, a);
     launch_beam_score(f.s, a.range, a.status, f.in.p + at_meas, (uint32_t)n, (uint32_t)H, (uint32_t)stride, b->huber, o + r_part, o + r_rows);
     { const int rc = c.home(o + r_rows, kScanMatchLite * H); if (rc) return rc; }
-    for (size_t h = 0; h < H; ++h) {
-        const float* row = f.h_out.p + kScanMatchLite * h;
-        cost[h] = row[0];
-        if (n_valid) n_valid[h] = (int32_t)row[1];
-        if (n_hit) n_hit[h] = (int32_t)row[2];
-    }
+    rows_unpack(f.h_out.p, H, kScanMatchLite, 0, cost, n_valid, n_hit);
     return MON_OK;
 }
 

@@ -1,7 +1,8 @@
 // field_sample_device.h -- the sample of a device-resident distance field at a world point and a body point under a pose, as every kernel that asks a
-// mon_dist_field takes them (kernels_clearance.hip, kernels_scan_match.hip).  The rule is in include/mon_core.h: trilinear interpolation with every fp32
-// operation rounded on its own (nothing is contracted), the gradient from the same intermediates.  The corners of a cell come as four 8-byte loads where
-// n_x > 1 (the two x-neighbours are adjacent words; the address is 4-byte aligned only).
+// mon_dist_field takes them (kernels_clearance.hip, kernels_scan_match.hip, kernels_field_trace.hip).  The rule is in include/mon_core.h: trilinear
+// interpolation with every fp32 operation rounded on its own (nothing is contracted), the gradient from the same intermediates.  The corners of a cell come
+// as four 8-byte loads where n_x > 1 (the two x-neighbours are adjacent words; the address is 4-byte aligned only).  Behind the sample: the two steps of the
+// calls' summation tree that more than one kernel takes (fd_block_row, fd_lds_fold).
 #pragma once
 #include <cmath>
 #include "model.h"
@@ -61,6 +62,49 @@ template <bool POSE> __device__ __forceinline__ Fd3 fd_centre(const float* __res
     c.y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(way[4], bx), __fmul_rn(way[5], by)), __fmul_rn(way[6], bz)), way[7]);
     c.z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(way[8], bx), __fmul_rn(way[9], by)), __fmul_rn(way[10], bz)), way[11]);
     return c;
+}
+
+// ---- the two shared steps of the rule's pairwise tree (padded with +0 to a power of two, v'[i] = fl(v[2 i] + v[2 i + 1]) level by level).
+// The block row, for a block of 256 threads over kScanMatchChunk = 1 024 consecutive items: item(k, t) writes the NV terms of this lane's item k = 0 .. 3 (a
+// padding item gives +0 throughout).  A lane trees its four consecutive items in registers; lanes hold consecutive subtrees, so __shfl_down by 1, 2 .. 32
+// continues the same tree (level m pairs lane l with lane l + m; lane 0 ends with the wave's node over 256 items); the four waves combine through LDS.
+// row[kScanMatchRow]: +0 but for the NV sums in the columns 32 - 2 - NV .. 29 (the row's last two words are 0).  A row is a node of the tree whatever the
+// chunk size: the levels above the items' own power of two add +0, which changes no bit of a sum except -0 (k_scan_fold returns -0 as +0).
+template <int NV, typename Item> __device__ __forceinline__ void fd_block_row(Item item, float* __restrict__ row) {
+    constexpr int FIRST = (int)kScanMatchRow - 2 - NV;
+    __shared__ float wave_s[4][NV];
+    float s[NV], t[NV], u[NV];
+    item(0, s);
+    item(1, t);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) s[j] = __fadd_rn(s[j], t[j]);
+    item(2, t);
+    item(3, u);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) s[j] = __fadd_rn(s[j], __fadd_rn(t[j], u[j]));
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1)
+#pragma unroll
+        for (int j = 0; j < NV; ++j) s[j] = __fadd_rn(s[j], __shfl_down(s[j], m));
+    if ((threadIdx.x & 63u) == 0u)
+#pragma unroll
+        for (int j = 0; j < NV; ++j) wave_s[threadIdx.x >> 6][j] = s[j];
+    __syncthreads();
+    if (threadIdx.x < kScanMatchRow) {
+        const int c = (int)threadIdx.x - FIRST;
+        float r = 0.f;
+        if (c >= 0 && c < NV) r = __fadd_rn(__fadd_rn(wave_s[0][c], wave_s[1][c]), __fadd_rn(wave_s[2][c], wave_s[3][c]));
+        row[threadIdx.x] = r;
+    }
+}
+// The tree over v[0], v[stride] .. v[(pad - 1) * stride] in LDS (pad a power of two), in place, by `n_who` threads of which this one is `who`; the sum
+// ends in v[0].  Level m keeps its sums at the multiples of 2 m and reads nothing another thread writes; one barrier per level, which every thread of the
+// block reaches: pad is uniform.  The caller has synchronised after writing v.
+__device__ __forceinline__ void fd_lds_fold(float* v, uint32_t stride, uint32_t pad, uint32_t who, uint32_t n_who) {
+    for (uint32_t m = 1; m < pad; m <<= 1) {
+        for (uint32_t i = who * 2u * m; i < pad; i += n_who * 2u * m) v[i * stride] = __fadd_rn(v[i * stride], v[(i + m) * stride]);
+        __syncthreads();
+    }
 }
 
 }  // namespace mon

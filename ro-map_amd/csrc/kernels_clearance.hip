@@ -4,11 +4,11 @@
 //   k_field_sample       a thread per point: d and, when asked for, the gradient
 //   k_traj_score<false>  n_samp <= 64: a wave per trajectory (four to a workgroup), a lane per sample; min_clear, first_hit and the cost tree by shuffles
 //   k_traj_score<true>   longer ones: a workgroup per trajectory (128 threads up to 128 samples, 256 above), a thread per sample and round; the penalties
-//                        in LDS in sample order, the cost tree there, the two minima by shuffles and through LDS across the waves
+//                        in LDS in sample order, the cost tree there (fd_lds_fold), the two minima by shuffles and through LDS across the waves
 //   k_field_max          the largest value of a field that was made on the device (mon_dist_field_info), in two launches of partial maxima
 // A lane owns a sample: the loop over the body's spheres runs inside it, so the fold over k and the minimum over k need no exchange.  A sample's two end
 // centres are recomputed from the waypoints (a few scalar-cached words) instead of being staged.  The sample itself (fd_axis, fd_lerp, fd_sample, fd_centre)
-// is field_sample_device.h's, shared with kernels_scan_match.hip.  Plain C++, vector stores only, no atomics, no scratch; no workgroup waits for another;
+// is field_sample_device.h's, shared with kernels_scan_match.hip and kernels_field_trace.hip.  Plain C++, vector stores only, no atomics, no scratch; no workgroup waits for another;
 // every loop is bounded by an argument the host has checked.
 #include "field_sample_device.h"
 
@@ -123,11 +123,7 @@ template <bool WG, bool POSE> __global__ void __launch_bounds__(256) k_traj_scor
     clear = fd_wave_min(clear); first = fd_wave_min(first);
     if (lane == 0u) { min_s[wave] = clear; hit_s[wave] = first; }
     __syncthreads();
-    // v'[i] = fl(v[2 i] + v[2 i + 1]) level by level, in place: level `m` keeps its sums at the multiples of 2 m and reads nothing another thread writes
-    for (uint32_t m = 1; m < a.pad; m <<= 1) {
-        for (uint32_t i = threadIdx.x * 2u * m; i < a.pad; i += blockDim.x * 2u * m) pen_s[i] = __fadd_rn(pen_s[i], pen_s[i + m]);
-        __syncthreads();
-    }
+    fd_lds_fold(pen_s, 1u, a.pad, threadIdx.x, blockDim.x);
     if (threadIdx.x == 0u) {
         const uint32_t waves = blockDim.x >> 6;
         for (uint32_t k = 1; k < waves; ++k) { clear = fminf(clear, min_s[k]); first = min(first, hit_s[k]); }

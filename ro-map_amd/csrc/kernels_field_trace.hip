@@ -6,11 +6,11 @@
 //                          [h * stride + ray]; NORMAL: one more sample, with its gradient, at the hit.  Consecutive rays are consecutive beams of a scan, so
 //                          neighbouring lanes walk neighbouring cells and share 64-byte lines.  A wave runs as long as its slowest ray.
 //   k_beam_terms           block (c, h): the run of kScanMatchChunk = 1 024 consecutive beams c of pose h, read from the ranges and statuses a trace launch
-//                          left at stride (a multiple of 4).  The lane and shuffle layout is k_scan_match<false>'s: a lane takes four consecutive beams and
-//                          trees them in registers, __shfl_down by 1, 2 .. 32 continues the same tree, the four waves combine through LDS.  The block's row
-//                          of kScanMatchRow = 32 words goes to part[h][c]: +0 but for the lite columns 27 .. 30 = cost, n_valid, n_hit, 0.
+//                          left at stride (a multiple of 4), four consecutive beams to a lane, summed by fd_block_row (field_sample_device.h), as
+//                          k_scan_match sums its points.  The block's row of kScanMatchRow = 32 words goes to part[h][c]: +0 but for the lite columns
+//                          27 .. 30 = cost, n_valid, n_hit, 0.
 // The rows are folded by k_scan_fold (kernels_scan_match.hip), launched as it is through launch_scan_fold.  The sample (fd_sample, fd_centre) is
-// field_sample_device.h's.  The pose is uniform per block (scalar loads).  Plain C++, vector stores only, no atomics, no scratch; no workgroup waits for
+// field_sample_device.h's too.  The pose is uniform per block (scalar loads).  Plain C++, vector stores only, no atomics, no scratch; no workgroup waits for
 // another; every loop is bounded by an argument the host has checked: the march by max_steps.
 #include "field_sample_device.h"
 
@@ -89,9 +89,7 @@ __device__ __forceinline__ void ft_beam(float huber, bool live, float range, int
 
 __global__ void __launch_bounds__(256) k_beam_terms(const float* __restrict__ range, const int32_t* __restrict__ status, const float* __restrict__ measured,
         uint32_t n, uint32_t stride, float huber, float* __restrict__ part) {
-    constexpr int NV = 3, FIRST = (int)kScanMatchRow - 2 - NV;                      // the row's last two words are 0
-    __shared__ float wave_s[4][NV];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, chunk = blockIdx.x, h = blockIdx.y;
+    const uint32_t chunk = blockIdx.x, h = blockIdx.y;
     // the lane's four consecutive beams: 16 bytes at a multiple of 16 (the stride and the host's offsets are multiples of 4 words), or what is left of them
     const uint32_t i0 = chunk * kScanMatchChunk + threadIdx.x * 4u;
     const size_t at = (size_t)h * stride + i0;
@@ -106,30 +104,8 @@ __global__ void __launch_bounds__(256) k_beam_terms(const float* __restrict__ ra
         for (int k = 0; k < 4; ++k)
             if (i0 + (uint32_t)k < n) { rg[k] = range[at + k]; st[k] = status[at + k]; me[k] = measured[i0 + (uint32_t)k]; }
     }
-    float s[NV], t[NV], u[NV];
-    ft_beam(huber, i0 < n, rg[0], st[0], me[0], s);
-    ft_beam(huber, i0 + 1u < n, rg[1], st[1], me[1], t);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) s[j] = __fadd_rn(s[j], t[j]);
-    ft_beam(huber, i0 + 2u < n, rg[2], st[2], me[2], t);
-    ft_beam(huber, i0 + 3u < n, rg[3], st[3], me[3], u);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) s[j] = __fadd_rn(s[j], __fadd_rn(t[j], u[j]));
-    // lane l holds the node over beams 4 l .. 4 l + 3 of the wave's 256: level m pairs lane l with lane l + m; lane 0 ends with the wave's node
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1)
-#pragma unroll
-        for (int j = 0; j < NV; ++j) s[j] = __fadd_rn(s[j], __shfl_down(s[j], m));
-    if (lane == 0u)
-#pragma unroll
-        for (int j = 0; j < NV; ++j) wave_s[wave][j] = s[j];
-    __syncthreads();
-    if (threadIdx.x < kScanMatchRow) {
-        const int c = (int)threadIdx.x - FIRST;
-        float r = 0.f;
-        if (c >= 0 && c < NV) r = __fadd_rn(__fadd_rn(wave_s[0][c], wave_s[1][c]), __fadd_rn(wave_s[2][c], wave_s[3][c]));
-        part[((size_t)h * gridDim.x + chunk) * kScanMatchRow + threadIdx.x] = r;
-    }
+    fd_block_row<3>([&](int k, float* __restrict__ t) { ft_beam(huber, i0 + (uint32_t)k < n, rg[k], st[k], me[k], t); },
+        part + ((size_t)h * gridDim.x + chunk) * kScanMatchRow);
 }
 
 void launch_field_trace(hipStream_t s, const float* D, const Lattice& g, const FieldTraceArgs& a) {

@@ -2,13 +2,12 @@
 // mon_dist_field_register).  The rule is in include/mon_core.h: per pose and point the field's sample and gradient at the posed point, a
 // Huber weight, and the 21 + 6 + 1 terms of the Gauss-Newton normal equations and the cost, each summed over the points by ONE pairwise tree in ascending
 // index, padded with +0 to a power of two.
-//   k_scan_match<NORMAL>  block (c, h): the run of kScanMatchChunk = 1 024 consecutive points c of pose h.  A lane takes four consecutive points and trees
-//                         them in registers; lanes hold consecutive subtrees, so __shfl_down by 1, 2 .. 32 continues the same tree; the four waves
-//                         combine through LDS.  The block's row of kScanMatchRow = 32 words goes to part[h][c]: 21 A terms (row-major upper triangle),
-//                         6 b terms, the cost, n_inside, n_inlier, 0, 0.  NORMAL false: the last five columns only; the others are written as +0.
-//   k_scan_fold           block (g, h): kScanMatchFold = 64 consecutive rows of pose h folded to one by the same tree in LDS, padded with +0.
-// A block's row is a node of the rule's tree whatever the chunk size: the levels above the points' own power of two add +0, which changes no bit of a sum
-// except -0, and the fold returns -0 as +0 as the rule asks.  The two counts ride the same tree as floats: a count is at most 2^20 and so exact.  The pose
+//   k_scan_match<NORMAL>  block (c, h): the run of kScanMatchChunk = 1 024 consecutive points c of pose h, four consecutive points to a lane, summed by
+//                         fd_block_row (field_sample_device.h).  The block's row of kScanMatchRow = 32 words goes to part[h][c]: 21 A terms (row-major
+//                         upper triangle), 6 b terms, the cost, n_inside, n_inlier, 0, 0.  NORMAL false: the last five columns only; the others are +0.
+//   k_scan_fold           block (g, h): kScanMatchFold = 64 consecutive rows of pose h folded to one by the same tree in LDS (fd_lds_fold per column),
+//                         padded with +0; it returns -0 as +0 as the rule asks.
+// The two counts ride the same tree as floats: a count is at most 2^20 and so exact.  The pose
 // and the pivot are uniform per block (scalar loads).  Plain C++, vector stores only, no atomics, no scratch; no workgroup waits for another; every loop is
 // bounded by an argument the host has checked.
 #include "field_sample_device.h"
@@ -50,9 +49,8 @@ template <bool NORMAL> __device__ __forceinline__ void sm_point(const DistFieldV
 }
 
 template <bool NORMAL> __global__ void __launch_bounds__(256) k_scan_match(DistFieldView F, ScanMatchArgs a, float* __restrict__ part) {
-    constexpr int NV = NORMAL ? kSmA + kSmB + 3 : 3, FIRST = (int)kScanMatchRow - 2 - NV;      // the row's last two words are 0
-    __shared__ float wave_s[4][NV];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, chunk = blockIdx.x, h = blockIdx.y;
+    constexpr int NV = NORMAL ? kSmA + kSmB + 3 : 3;
+    const uint32_t chunk = blockIdx.x, h = blockIdx.y;
     const float* __restrict__ pose = a.poses + 16 * (size_t)h;
     float cx = 0.f, cy = 0.f, cz = 0.f;
     if (a.pivots != nullptr) { cx = a.pivots[3 * (size_t)h]; cy = a.pivots[3 * (size_t)h + 1]; cz = a.pivots[3 * (size_t)h + 2]; }
@@ -70,30 +68,9 @@ template <bool NORMAL> __global__ void __launch_bounds__(256) k_scan_match(DistF
 #pragma unroll
             for (int c = 0; c < 3; ++c) p[3 * k + c] = i0 + (uint32_t)k < a.n ? a.points[3 * (size_t)(i0 + (uint32_t)k) + c] : 0.f;
     }
-    float s[NV], t[NV], u[NV];
-    sm_point<NORMAL>(F, pose, cx, cy, cz, a.huber, a.outside, i0 < a.n, p[0], p[1], p[2], s);
-    sm_point<NORMAL>(F, pose, cx, cy, cz, a.huber, a.outside, i0 + 1u < a.n, p[3], p[4], p[5], t);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) s[j] = __fadd_rn(s[j], t[j]);
-    sm_point<NORMAL>(F, pose, cx, cy, cz, a.huber, a.outside, i0 + 2u < a.n, p[6], p[7], p[8], t);
-    sm_point<NORMAL>(F, pose, cx, cy, cz, a.huber, a.outside, i0 + 3u < a.n, p[9], p[10], p[11], u);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) s[j] = __fadd_rn(s[j], __fadd_rn(t[j], u[j]));
-    // lane l holds the node over points 4 l .. 4 l + 3 of the wave's 256: level m pairs lane l with lane l + m; lane 0 ends with the wave's node
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1)
-#pragma unroll
-        for (int j = 0; j < NV; ++j) s[j] = __fadd_rn(s[j], __shfl_down(s[j], m));
-    if (lane == 0u)
-#pragma unroll
-        for (int j = 0; j < NV; ++j) wave_s[wave][j] = s[j];
-    __syncthreads();
-    if (threadIdx.x < kScanMatchRow) {
-        const int c = (int)threadIdx.x - FIRST;
-        float r = 0.f;
-        if (c >= 0 && c < NV) r = __fadd_rn(__fadd_rn(wave_s[0][c], wave_s[1][c]), __fadd_rn(wave_s[2][c], wave_s[3][c]));
-        part[((size_t)h * gridDim.x + chunk) * kScanMatchRow + threadIdx.x] = r;
-    }
+    fd_block_row<NV>([&](int k, float* __restrict__ t) {
+        sm_point<NORMAL>(F, pose, cx, cy, cz, a.huber, a.outside, i0 + (uint32_t)k < a.n, p[3 * k], p[3 * k + 1], p[3 * k + 2], t); },
+        part + ((size_t)h * gridDim.x + chunk) * kScanMatchRow);
 }
 
 // in[pose][n_in][32] -> out[pose][gridDim.x][width]: block (g, h) folds rows 64 g .. of pose h and writes the columns first .. first + width - 1
@@ -105,11 +82,7 @@ __global__ void __launch_bounds__(256) k_scan_fold(const float* __restrict__ in,
     while (pad < cnt) pad <<= 1;                                                    // (at most 64)
     for (uint32_t r = sub; r < pad; r += 8u) v_s[r][col] = r < cnt ? in[((size_t)h * n_in + base + r) * kScanMatchRow + col] : 0.f;
     __syncthreads();
-    // v'[i] = fl(v[2 i] + v[2 i + 1]) level by level, in place: level `m` keeps its sums at the multiples of 2 m and reads nothing another thread writes
-    for (uint32_t m = 1; m < pad; m <<= 1) {
-        for (uint32_t i = sub * 2u * m; i < pad; i += 16u * m) v_s[i][col] = __fadd_rn(v_s[i][col], v_s[i + m][col]);
-        __syncthreads();
-    }
+    fd_lds_fold(&v_s[0][col], kScanMatchRow, pad, sub, 8u);
     if (sub == 0u && col >= first && col < first + width)
         out[((size_t)h * gridDim.x + g) * width + (col - first)] = __fadd_rn(v_s[0][col], 0.f);      // (-0 leaves as +0)
 }

@@ -167,5 +167,29 @@ struct DistField {
 int lattice_dims_check(const char* what, int nx, int ny, int nz, size_t max_cells);
 // an instance row home: the call's list indices, or the caller's ids for them
 void scene_instances_home(int32_t* out, const float* row, size_t n, const int32_t* ids);
+// A call's output area on the device (a scene route's in ws.out, a handle call's in its `out`), described once: pieces taken in order, whose offsets serve
+// the device pointers the kernels get and the unpacking from the pinned staging alike.  row: `width` floats per point.  piece: `floats` floats the caller may
+// ask for -- host: where they go (nullptr: not asked for; the room is taken all the same, so a call that gives such a piece no room passes 0 floats),
+// instance: by way of scene_instances_home.  out: a piece that is a row.  keep: words the route itself reads at home.  `home`: the front of the area up to
+// the last piece asked for or kept, all a scene route brings home; unpack: the pieces asked for, out of the staging.
+struct Area {
+    struct Out { size_t at, floats; void* host; bool instance; };
+    size_t n_q = 0, end = 0, home = 0; Out outs[8]; int n_outs = 0;
+    size_t take(size_t floats) { const size_t at = end; end += floats; return at; }
+    size_t row(size_t width = 1) { return take(width * n_q); }
+    size_t keep(size_t floats) { const size_t at = take(floats); home = end; return at; }
+    size_t piece(void* host, size_t floats, bool instance = false) {
+        const size_t at = take(floats);
+        if (host) { home = end; outs[n_outs++] = Out{ at, floats, host, instance }; }
+        return at;
+    }
+    size_t out(void* host, size_t width = 1, bool instance = false) { return piece(host, width * n_q, instance); }
+    void unpack(const float* h, const int32_t* ids) const {
+        for (int k = 0; k < n_outs; ++k) {
+            const Out& o = outs[k];
+            if (o.instance) scene_instances_home(static_cast<int32_t*>(o.host), h + o.at, n_q, ids); else std::memcpy(o.host, h + o.at, 4 * o.floats);
+        }
+    }
+};
 
 }  // namespace mon

@@ -89,28 +89,7 @@ int scene_lattice_points(const float* origin3, const float* step3, int nx, int n
 #define MON_POINTS_PASS kRenderChunkRays
 #endif
 constexpr uint32_t kScenePointsPass = MON_POINTS_PASS;
-// A route's output area in ws.out, described once: pieces taken in order, whose offsets serve the device pointers the kernels get and the unpacking from the
-// pinned staging alike.  row: `width` floats per point.  out: a row the caller may ask for -- host: where it goes (nullptr: not asked for), instance: by way
-// of scene_instances_home.  keep: words the route itself reads at home.  `home`: the front of the area up to the last piece asked for or kept, all a call
-// brings home; unpack: the rows asked for, out of the staging.
-struct Area {
-    struct Out { size_t at, floats; void* host; bool instance; };
-    size_t n_q, end = 0, home = 0; Out outs[8]; int n_outs = 0;
-    size_t take(size_t floats) { const size_t at = end; end += floats; return at; }
-    size_t row(size_t width = 1) { return take(width * n_q); }
-    size_t keep(size_t floats) { const size_t at = take(floats); home = end; return at; }
-    size_t out(void* host, size_t width = 1, bool instance = false) {
-        const size_t at = row(width);
-        if (host) { home = end; outs[n_outs++] = Out{ at, width * n_q, host, instance }; }
-        return at;
-    }
-    void unpack(const float* h, const int32_t* ids) const {
-        for (int k = 0; k < n_outs; ++k) {
-            const Out& o = outs[k];
-            if (o.instance) scene_instances_home(static_cast<int32_t*>(o.host), h + o.at, n_q, ids); else std::memcpy(o.host, h + o.at, 4 * o.floats);
-        }
-    }
-};
+// (A route's output area in ws.out is an Area, model_internal.h.)
 // where a route keeps the fold's output rows (grad_log, grad_sigma, normal: the gradient fold's).  A route places the rows it sends home where its area
 // wants them; fold_rows_rest places the others behind, in this order
 constexpr size_t kNoRow = ~(size_t)0;
@@ -326,6 +305,17 @@ int scene_distance_check(int side, const float* origin3, const float* step3, int
     { const int rc = lattice_route_check("scene_distance", side, origin3, step3, nx, ny, nz, sigma_min); if (rc) return rc; }
     return distance_outputs_check("scene_distance", max_dist, dist);
 }
+// The tail of the two standalone transforms: the launches' error, then the value array and, where asked for, the index array read back; the caller's
+// arrays are written only once everything has succeeded
+static int transform_home(size_t n, const float* d_val, float* val, const int32_t* d_index, int32_t* index) {
+    HIPCHECK(hipGetLastError());
+    std::vector<float> h_val(n); std::vector<int32_t> h_index(index ? n : 0);
+    HIPCHECK(hipMemcpy(h_val.data(), d_val, 4 * n, hipMemcpyDeviceToHost));
+    if (index) HIPCHECK(hipMemcpy(h_index.data(), d_index, 4 * n, hipMemcpyDeviceToHost));
+    std::memcpy(val, h_val.data(), 4 * n);
+    if (index) std::memcpy(index, h_index.data(), 4 * n);
+    return MON_OK;
+}
 // mon_distance_transform: the transform alone on a host mask, in buffers of its own on the device's default stream
 int distance_transform(int device, const uint8_t* occupied, int nx, int ny, int nz, const float* step3, float max_dist, float* dist, int32_t* nearest) {
     { const int rc = device_enter(device); if (rc) return rc; }
@@ -335,13 +325,7 @@ int distance_transform(int device, const uint8_t* occupied, int nx, int ny, int 
     HIPCHECK(hipMemcpy(occ.p, occupied, n, hipMemcpyHostToDevice));
     launch_distance_passes(nullptr, occ.p, false, Lattice(nullptr, step3, nx, ny, nz), v.p, site.p);
     launch_distance_finish(nullptr, (uint32_t)n, v.p, site.p, max_dist, nullptr, v.p + 2 * n, nearest ? site.p + 2 * n : nullptr, nullptr);
-    HIPCHECK(hipGetLastError());
-    std::vector<float> h_dist(n); std::vector<int32_t> h_near(nearest ? n : 0);     // (the caller's arrays are written only once everything has succeeded)
-    HIPCHECK(hipMemcpy(h_dist.data(), v.p + 2 * n, 4 * n, hipMemcpyDeviceToHost));
-    if (nearest) HIPCHECK(hipMemcpy(h_near.data(), site.p + 2 * n, 4 * n, hipMemcpyDeviceToHost));
-    std::memcpy(dist, h_dist.data(), 4 * n);
-    if (nearest) std::memcpy(nearest, h_near.data(), 4 * n);
-    return MON_OK;
+    return transform_home(n, v.p + 2 * n, dist, site.p + 2 * n, nearest);
 }
 // ---- the lattice routes' chain: scene_distance, scene_dist_field, scene_components and scene_paths each declare their area -- the rows
 // they may send home at the front (Area::out, in the order a caller may ask for them), the fold's other rows behind (fold_rows_rest) -- run the stages below,
@@ -396,35 +380,46 @@ int scene_distance(Model* const* ms, size_t n, int side, const ScenePoints& q, f
     A.unpack(c.ws->h_out.p, ids);
     return MON_OK;
 }
-// mon_scene_dist_field / mon_online_dist_field: the same chain with dist kept on the device.  The output area opens with four words for
-// the field's largest value -- all that goes home -- and ends with the partial maxima; dist goes into the handle's buffer by a device-to-device copy.
+// mon_scene_dist_field / mon_online_dist_field: the same chain with dist kept on the device.  What a fill asks beyond its lattice route:
+// a finite max_dist, so that every value lies within it, and no step 0 on an axis of several cells (a handle's sample divides by the step)
+static int field_fill_check(const char* what, const float* step3, int nx, int ny, int nz, float max_dist) {
+    if (!std::isfinite(max_dist) || !(max_dist > 0.f)) { set_error("%s: max_dist %g (finite, above 0)", what, (double)max_dist); return MON_ERR_ARG; }
+    const int dims[3] = { nx, ny, nz };
+    for (int a = 0; a < 3; ++a) if (dims[a] > 1 && step3[a] == 0.f) { set_error("%s: step 0 on axis %d, which has %d cells", what, a, dims[a]);
+        return MON_ERR_ARG; }
+    return MON_OK;
+}
 int scene_dist_field_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, float max_dist, const void* field_out) {
     REQUIRE_ARG("scene_dist_field", field_out, "field");
     float unused = 0.f;
     { const int rc = scene_distance_check(side, origin3, step3, nx, ny, nz, sigma_min, 1.f, &unused); if (rc) return rc; }
-    if (!std::isfinite(max_dist) || !(max_dist > 0.f)) { set_error("scene_dist_field: max_dist %g (finite, above 0)", (double)max_dist); return MON_ERR_ARG; }
-    const int dims[3] = { nx, ny, nz };
-    for (int a = 0; a < 3; ++a) if (dims[a] > 1 && step3[a] == 0.f) { set_error("scene_dist_field: step 0 on axis %d, which has %d cells", a, dims[a]);
-        return MON_ERR_ARG; }
+    return field_fill_check("scene_dist_field", step3, nx, ny, nz, max_dist);
+}
+// The fill of a handle, for scene_dist_field and scene_signed_dist_field.  The route's area opens with four words for the field's largest value (r_max) --
+// all that goes home -- and ends with the partial maxima (r_part).  The handle is made before `chain` enqueues the route's stages; then the row r_keep goes
+// into the handle's buffer by a device-to-device copy, the largest value is formed, and A.home floats come home.  The handle is freed on every failure.
+template <class Chain> static int lattice_field_fill(const char* what, SceneCall& c, int device, const Lattice& g, const Area& A, size_t r_keep, size_t r_max,
+                                                     size_t r_part, Chain chain, DistField** out) {
+    DistField* f = nullptr;
+    { const int rc = dist_field_adopt(device, g, &f); if (rc) return rc; }
+    int rc = chain();
+    if (!rc) {
+        float* o = c.ws->out.p;
+        const hipError_t e = hipMemcpyAsync(f->cells, o + r_keep, 4 * g.n(), hipMemcpyDeviceToDevice, c.s);
+        if (e != hipSuccess) { set_error("%s: the copy into the handle failed: %s", what, hipGetErrorString(e)); rc = MON_ERR_HIP; }
+        else { launch_field_max(c.s, o + r_keep, (uint32_t)g.n(), o + r_part, o + r_max); rc = c.home(A.home); }
+    }
+    if (rc) { dist_field_free(f); return rc; }
+    f->max_value = c.ws->h_out.p[r_max];
+    *out = f;
     return MON_OK;
 }
 int scene_dist_field(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, float max_dist, DistField** out) {
     SceneCall c; { const int rc = c.enter("scene_dist_field", ms, n, side, false); if (rc) return rc; }
-    SceneWs& ws = *c.ws; const hipStream_t s = c.s;
     Area A{ q.n }; const size_t r_max = A.keep(4); const DistanceRows r = distance_rows(A, nullptr, nullptr, nullptr, nullptr, nullptr);
-    const size_t r_part = A.take(kFieldMaxBlocks); DistField* f = nullptr;
-    { const int rc = dist_field_adopt(ms[0]->device, q.g, &f); if (rc) return rc; }
-    int rc = distance_chain(c, ms, n, q, sigma_min, max_dist, A, r, false, false);
-    if (!rc) {
-        float* o = ws.out.p;
-        const hipError_t e = hipMemcpyAsync(f->cells, o + r.dist, 4 * q.n, hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) { set_error("scene_dist_field: the copy into the handle failed: %s", hipGetErrorString(e)); rc = MON_ERR_HIP; }
-        else { launch_field_max(s, o + r.dist, (uint32_t)q.n, o + r_part, o + r_max); rc = c.home(A.home); }
-    }
-    if (rc) { dist_field_free(f); return rc; }
-    f->max_value = ws.h_out.p[r_max];
-    *out = f;
-    return MON_OK;
+    const size_t r_part = A.take(kFieldMaxBlocks);
+    return lattice_field_fill("scene_dist_field", c, ms[0]->device, q.g, A, r.dist, r_max, r_part,
+                              [&] { return distance_chain(c, ms, n, q, sigma_min, max_dist, A, r, false, false); }, out);
 }
 
 // ---- signed, sub-cell distance fields (mon_signed_distance_transform, mon_scene_signed_distance_lattice, mon_scene_signed_dist_field; DESIGN.md
@@ -460,13 +455,7 @@ int signed_distance_transform(int device, const float* val, float iso, int nx, i
     launch_signed_values(nullptr, (uint32_t)n, v.p, iso, false, nullptr, ins.p, nullptr);
     launch_signed_passes(nullptr, v.p, ins.p, nullptr, iso, g, v.p + n, site.p);
     launch_signed_finish(nullptr, g, v.p + n, site.p, ins.p, max_dist, nullptr, v.p + 5 * n, nearest_edge ? site.p + 4 * n : nullptr, nullptr);
-    HIPCHECK(hipGetLastError());
-    std::vector<float> h_dist(n); std::vector<int32_t> h_near(nearest_edge ? n : 0);   // (the caller's arrays are written only once everything has succeeded)
-    HIPCHECK(hipMemcpy(h_dist.data(), v.p + 5 * n, 4 * n, hipMemcpyDeviceToHost));
-    if (nearest_edge) HIPCHECK(hipMemcpy(h_near.data(), site.p + 4 * n, 4 * n, hipMemcpyDeviceToHost));
-    std::memcpy(sdist, h_dist.data(), 4 * n);
-    if (nearest_edge) std::memcpy(nearest_edge, h_near.data(), 4 * n);
-    return MON_OK;
+    return transform_home(n, v.p + 5 * n, sdist, site.p + 4 * n, nearest_edge);
 }
 // What the two scene calls share.  The rows: iso (four words) | sigma | sdist | nearest_edge | nearest_owner | val, then the fold's other rows.
 struct SignedRows { FoldRows f; size_t iso, sdist, edge, edge_owner, val; };
@@ -497,37 +486,22 @@ int scene_signed_distance(Model* const* ms, size_t n, int side, const ScenePoint
     if (iso_out) *iso_out = c.ws->h_out.p[r.iso];
     return MON_OK;
 }
-// mon_scene_signed_dist_field / mon_online_signed_dist_field: the same chain with sdist kept on the device, as scene_dist_field keeps dist: four words for
-// the field's largest value go home, sdist goes into the handle's buffer by a device-to-device copy.
+// mon_scene_signed_dist_field / mon_online_signed_dist_field: the same chain with sdist kept on the device, as scene_dist_field keeps dist
+// (lattice_field_fill).
 int scene_signed_dist_field_check(int side, const float* origin3, const float* step3, int nx, int ny, int nz, float sigma_min, uint32_t flags, float max_dist,
                                   const void* field_out) {
     const char* what = "scene_signed_dist_field";
     REQUIRE_ARG(what, field_out, "field");
     int rc;
     if ((rc = lattice_route_check(what, side, origin3, step3, nx, ny, nz, sigma_min)) || (rc = signed_flags_check(what, flags))) return rc;
-    if (!std::isfinite(max_dist) || !(max_dist > 0.f)) { set_error("%s: max_dist %g (finite, above 0)", what, (double)max_dist); return MON_ERR_ARG; }
-    const int dims[3] = { nx, ny, nz };
-    for (int a = 0; a < 3; ++a) if (dims[a] > 1 && step3[a] == 0.f) { set_error("%s: step 0 on axis %d, which has %d cells", what, a, dims[a]);
-        return MON_ERR_ARG; }
-    return MON_OK;
+    return field_fill_check(what, step3, nx, ny, nz, max_dist);
 }
 int scene_signed_dist_field(Model* const* ms, size_t n, int side, const ScenePoints& q, float sigma_min, uint32_t flags, float max_dist, DistField** out) {
     SceneCall c; { const int rc = c.enter("scene_signed_dist_field", ms, n, side, false); if (rc) return rc; }
-    SceneWs& ws = *c.ws; const hipStream_t s = c.s;
     Area A{ q.n }; const size_t r_max = A.keep(4); const SignedRows r = signed_rows(A, nullptr, nullptr, nullptr, nullptr, nullptr, false);
-    const size_t r_part = A.take(kFieldMaxBlocks); DistField* f = nullptr;
-    { const int rc = dist_field_adopt(ms[0]->device, q.g, &f); if (rc) return rc; }
-    int rc = signed_chain(c, ms, n, q, sigma_min, flags, max_dist, A, r, false, false);
-    if (!rc) {
-        float* o = ws.out.p;
-        const hipError_t e = hipMemcpyAsync(f->cells, o + r.sdist, 4 * q.n, hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) { set_error("scene_signed_dist_field: the copy into the handle failed: %s", hipGetErrorString(e)); rc = MON_ERR_HIP; }
-        else { launch_field_max(s, o + r.sdist, (uint32_t)q.n, o + r_part, o + r_max); rc = c.home(A.home); }
-    }
-    if (rc) { dist_field_free(f); return rc; }
-    f->max_value = ws.h_out.p[r_max];
-    *out = f;
-    return MON_OK;
+    const size_t r_part = A.take(kFieldMaxBlocks);
+    return lattice_field_fill("scene_signed_dist_field", c, ms[0]->device, q.g, A, r.sdist, r_max, r_part,
+                              [&] { return signed_chain(c, ms, n, q, sigma_min, flags, max_dist, A, r, false, false); }, out);
 }
 
 // ---- connected components (mon_label_components, mon_scene_components_lattice): which cells belong together.  scene_components: the

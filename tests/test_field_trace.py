@@ -236,10 +236,12 @@ def _check_beam(pkg, n, H, seed):
     return want
 
 
-@pytest.mark.parametrize("n", [1, 4, 255, 1024, 1025, 4099])
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 255, 256, 257, 1023, 1024, 1025, 4099])
 def test_beam_score_equals_the_reference(pkg, n):
     """cost, n_valid and n_hit in every bit at H = 1 and 17, with and without a Huber threshold, NaN beams included; the cost is the reference's tree over
-    the ranges mon_dist_field_trace itself returns for the same call; poses16 NULL"""
+    the ranges mon_dist_field_trace itself returns for the same call; poses16 NULL.  The sizes are test_match_equals_the_reference's boundaries of the
+    block row the two kernels share (fd_block_row): a ragged quad at the start, a full wave, one lane into the next wave, one short of a chunk, a chunk,
+    one past it.  (The reference alone, on the CPU, meets the condition below at 256, 257 and 1 023 too: 44 to 241 hits of 204 to 818 valid beams.)"""
     for H in (1, 17):
         want = _check_beam(pkg, n, H, 300 + 10 * n + H)
         if n >= 255:

@@ -17,7 +17,11 @@ mon_shortest_paths (with and without cell_cost and next, both lattices), mon_lat
 (with and without gradients), _score (way_floats 3 and 16, with and without the optional outputs), _match (with and without the normal equations and the
 pivots), mon_register_default, mon_dist_field_register and _destroy; mon_online_paths_lattice and mon_online_dist_field.  The stand-in runtime leaves every
 read-back 0, so a cost field settles after its first batch of sweeps and a registration ends in its first round: with status 3 under the default
-min_inside, with status 2 (no factorisation of an all-zero row) under min_inside 0; both are called.  Every kernel launch (registered
+min_inside, with status 2 (no factorisation of an all-zero row) under min_inside 0; both are called.  On the created handle also mon_trace_default, mon_dist_field_trace (range alone, every optional
+output, poses16 NULL with one pose, three poses) and mon_dist_field_beam_score (with and without its counts); with no side mon_signed_distance_transform (with
+and without nearest_edge, both lattices); mon_online_signed_distance_lattice and mon_online_signed_dist_field; and behind them, per side ("-- lattice routes,
+signed distance": their handles' streams take the creation indices after every handle above), mon_scene_signed_distance_lattice (every optional output,
+none, MON_SIGNED_LOG, 33 x 32 x 16) and mon_scene_signed_dist_field (both lattices).  Every kernel launch (registered
 name, grid, block, dynamic LDS bytes, stream by creation index) and every asynchronous fill / copy (bytes, stream) is one line.  The trace is folded without
 loss -- a block of up to 12 lines that repeats back to back is written once, followed by "x N" (fold) -- and must then equal tests/golden/launch_trace.txt line
 for line.  No GPU.
@@ -44,7 +48,11 @@ lattice of the object map"), with this driver and that commit's product sources;
 lists need no common camera, dataset or sample stream: other_K, other_ds and xorwow are accepted there and their launches are in the trace.)  The
 "-- lattice routes" lines and their refusals (every NULL argument, every count at 0 and one past its maximum, connectivity 7, max_cost 0, a seed outside
 the lattice, way_floats 4, huber 0, lambda_up 1, a NULL handle beside a bad count) were recorded in the same way from the commit before the lattice routes'
-chain was written once ("Add scan matching against a device-resident distance field").
+chain was written once ("Add scan matching against a device-resident distance field").  The ray tracing, beam score and signed-field lines and their
+refusals (every NULL argument; rays, poses, rays x poses and max_steps at 0 and one past their maxima; t_min above t_max, relax 0 and 1.5, step_min 0, a
+NaN march parameter, beam huber 0, two poses without poses16; flags 2, max_dist 0 and +inf, step 0 on an axis of several cells, iso NaN; a NULL handle beside
+a bad count) were recorded in the same way from the commit before the handle calls' output plan, the block row and the fill were written once ("Add signed,
+sub-cell distance fields from the map's density"); every line recorded before came out as it stood.
 
 A change that moves the schedule ON PURPOSE records the new trace: python tests/test_launch_trace.py --record
 A refactor shows that nothing moved by recording from the parent commit's product sources with this driver, and getting the committed file:

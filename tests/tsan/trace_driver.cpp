@@ -1,7 +1,7 @@
 // trace_driver.cpp -- walks the C ABI single-threaded on the host side built --offload-host-only against tests/tsan/hip_stub.cpp (no sanitizer) with the
 // stub's launch trace on: every kernel launch and asynchronous fill / copy of every training path as one line of text, under a heading per case and per call;
 // then (part two) of every scene, pose and field-query route on both sides and through the online manager, the cost fields and the device-resident distance
-// fields in a section of their own, and a list of the calls those routes refuse, with code and message.
+// fields (ray tracing, beam scores and the signed fields included) in a section of their own, and a list of the calls those routes refuse, with code and message.
 // tests/test_launch_trace.py compares the output with tests/golden/launch_trace.txt.  Usage: trace_driver <scratch dir> <config json>.  TEST INFRASTRUCTURE.
 #include <chrono>
 #include <cmath>
@@ -128,6 +128,9 @@ struct Args {
     mon_dist_field* field; mon_dist_field** field_out; const float* fdist; mon_dist_field_desc* info; float field_max, outside;
     const float* spheres; size_t n_spheres; const float* ways; int way_floats; size_t n_traj, n_way, n_sub; const mon_traj_score_params* tp; float* min_clear;
     const float* mposes; size_t n_h; const float* pivots; const mon_scan_match_params* mp; mon_register_params* rp; float* poses_out;
+    // ray tracing on a handle (frays[n][6]; tposes NULL: world rays) and the signed fields (val: host values per cell; max_dist and field_max as above)
+    const float* frays; size_t n_frays; const float* tposes; size_t n_tposes; mon_trace_params* trp; const float* measured; const mon_beam_params* bp; float* range;
+    const float* val; float iso; uint32_t flags;
 };
 static int32_t* as_i32(float* p) { return reinterpret_cast<int32_t*>(p); }
 static int scene_render(const Args& a) { return mon_scene_render(a.objs, a.n_objs, a.side, a.rect, a.Twc, a.rgb, a.depth, a.out, as_i32(a.out)); }
@@ -221,6 +224,22 @@ static int dist_field_match(const Args& a) { return mon_dist_field_match(a.field
 static int register_default(const Args& a) { return mon_register_default(a.field, a.rp); }
 static int dist_field_register(const Args& a) { return mon_dist_field_register(a.field, a.pts, a.n_pts, a.mposes, a.n_h, a.rp, a.poses_out, a.cost, as_i32(sl(a, 1)),
         as_i32(sl(a, 2)), as_i32(sl(a, 3)), as_i32(sl(a, 4)), as_i32(sl(a, 13))); }
+static int trace_default(const Args& a) { return mon_trace_default(a.field, a.trp); }
+static int dist_field_trace(const Args& a) { return mon_dist_field_trace(a.field, a.frays, a.n_frays, a.tposes, a.n_tposes, a.trp, a.range, as_i32(sl(a, 1)),
+        as_i32(sl(a, 2)), sl(a, 3)); }
+static int dist_field_beam_score(const Args& a) { return mon_dist_field_beam_score(a.field, a.frays, a.n_frays, a.measured, a.tposes, a.n_tposes, a.trp, a.bp, a.cost,
+        as_i32(sl(a, 1)), as_i32(sl(a, 2))); }
+// the signed distance fields
+static int signed_distance_transform(const Args& a) { return mon_signed_distance_transform(0, a.val, a.iso, a.nx, a.ny, a.nz, a.step, a.max_dist, a.dist,
+        as_i32(sl(a, 1))); }
+static int scene_signed_distance_lattice(const Args& a) { return mon_scene_signed_distance_lattice(a.objs, a.n_objs, a.side, a.origin, a.step, a.nx, a.ny, a.nz,
+        a.sigma_min, a.flags, a.max_dist, a.dist, as_i32(sl(a, 1)), as_i32(sl(a, 2)), sl(a, 3), sl(a, 4), sl(a, 13)); }
+static int scene_signed_dist_field(const Args& a) { return mon_scene_signed_dist_field(a.objs, a.n_objs, a.side, a.origin, a.step, a.nx, a.ny, a.nz, a.sigma_min,
+        a.flags, a.field_max, a.field_out); }
+static int online_signed_distance_lattice(const Args& a) { return mon_online_signed_distance_lattice(a.om, a.origin, a.step, a.nx, a.ny, a.nz, a.sigma_min, a.flags,
+        a.max_dist, a.dist, as_i32(sl(a, 1)), as_i32(sl(a, 2)), sl(a, 3), sl(a, 4), sl(a, 13)); }
+static int online_signed_dist_field(const Args& a) { return mon_online_signed_dist_field(a.om, a.origin, a.step, a.nx, a.ny, a.nz, a.sigma_min, a.flags, a.field_max,
+        a.field_out); }
 
 // a call that must fail, on one line with its code and message (no exit); `change` edits a copy `a` of the good arguments
 #define ERR(route, change) do { Args a = good; change; const int rc_ = route(a); \
@@ -333,6 +352,7 @@ static void inference_part(const char* cfg_json, const mon_config& base, const u
     for (int i = 0; i < 12; ++i) { cell_cost[i] = cost_neg[i] = 1.5f; fdist[i] = fdist_nan[i] = 0.1f * (float)i; }
     cost_neg[5] = -1.f; fdist_nan[7] = NAN;
     const std::vector<uint8_t> big_mask(n_big, 1); const std::vector<float> big_cost(n_big, 1.f), big_fdist(n_big, 0.25f);
+    std::vector<float> big_val(n_big); for (size_t i = 0; i < n_big; ++i) big_val[i] = (float)(i % 33) / 32.f;
     const float step_zero[3] = { 0.3f, 0.f, 0.6f };
     const float spheres[8] = { 0.f, 0.f, 0.f, 0.05f, 0.1f, 0.f, 0.f, 0.02f }, sphere_neg[8] = { 0.f, 0.f, 0.f, 0.05f, 0.1f, 0.f, 0.f, -1.f };
     float ways3[2 * 3 * 3], ways16[2 * 3 * 16];
@@ -349,6 +369,12 @@ static void inference_part(const char* cfg_json, const mon_config& base, const u
     g0.field = nullptr; g0.field_out = &fh; g0.fdist = fdist; g0.info = &info; g0.field_max = 0.5f; g0.outside = 0.5f;
     g0.spheres = spheres; g0.n_spheres = 2; g0.ways = ways3; g0.way_floats = 3; g0.n_traj = 2; g0.n_way = 3; g0.n_sub = 2; g0.tp = &tp; g0.min_clear = o + 17 * 65536;
     g0.mposes = poses3; g0.n_h = 3; g0.pivots = pivots; g0.mp = &mp; g0.rp = &rp; g0.poses_out = o + 18 * 65536;
+    // four rays into the lattice from its corner and from outside, one beam without a return; the signed fields read fdist as values around iso 0.45
+    const float frays[24] = { -0.3f, -0.3f, -0.3f, 1.f, 0.f, 0.f, -0.3f, 0.f, 0.f, 0.f, 1.f, 0.f, -1.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 2.f, 0.f, 0.f, -1.f };
+    const float measured[4] = { 0.2f, NAN, 0.5f, 0.1f };
+    mon_trace_params trp{}; const mon_beam_params bp{ 0.1f }, bp_huber0{ 0.f };
+    g0.frays = frays; g0.n_frays = 4; g0.tposes = poses3; g0.n_tposes = 1; g0.trp = &trp; g0.measured = measured; g0.bp = &bp; g0.range = o + 19 * 65536;
+    g0.val = fdist; g0.iso = 0.45f; g0.flags = 0u;
     Args good = g0;
 
     // ---- every route once, on both sides
@@ -405,18 +431,39 @@ static void inference_part(const char* cfg_json, const mon_config& base, const u
         CALL(dist_field_score(f)); CALL(dist_field_score(f16)); CALL(dist_field_score(fbare));
         CALL(dist_field_match(f)); CALL(dist_field_match(fbare)); CALL(dist_field_match(fnopiv));
         CALL(register_default(f)); CALL(dist_field_register(f)); rp.min_inside = 0; CALL(dist_field_register(f)); CALL(dist_field_register(fbare));
+        // ray tracing: range alone, every optional output, world rays, three poses; the beam score with and without its counts
+        Args ftbare = fbare; Args ftworld = f; ftworld.tposes = nullptr; Args ft3 = f; ft3.n_tposes = 3; Args ft3bare = ft3; ft3bare.opt = false;
+        CALL(trace_default(f)); CALL(dist_field_trace(ftbare)); CALL(dist_field_trace(f)); CALL(dist_field_trace(ftworld)); CALL(dist_field_trace(ft3));
+        CALL(dist_field_beam_score(ft3)); CALL(dist_field_beam_score(ft3bare));
         CALL(dist_field_destroy(f));
         CALL(dist_field_create(big)); f.field = fh; CALL(dist_field_read(f)); CALL(dist_field_sample(f)); CALL(dist_field_destroy(f));
+        Args sbig = big; sbig.val = big_val.data(); sbig.iso = 0.5f;
+        CALL(signed_distance_transform(a)); CALL(signed_distance_transform(bare)); CALL(signed_distance_transform(sbig));
     }
     {   std::printf("-- lattice routes, online manager\n");
         Args a = good; Args f = a;
         CALL(online_paths_lattice(a)); CALL(online_dist_field(a)); f.field = fh; CALL(dist_field_destroy(f));
+        CALL(online_signed_distance_lattice(a)); CALL(online_signed_dist_field(a)); f.field = fh; CALL(dist_field_destroy(f));
+    }
+    // the signed fields per side, behind every handle above: their handles' streams take the next creation indices
+    for (int side = 0; side < 2; ++side) {
+        std::printf("-- lattice routes, signed distance, side %d\n", side);
+        Args a = good; a.side = side; Args big = a; big.nx = 33; big.ny = 32; big.nz = 16; Args bare = a; bare.opt = false; Args lg = a; lg.flags = MON_SIGNED_LOG;
+        Args f = a;
+        CALL(scene_signed_distance_lattice(a)); CALL(scene_signed_distance_lattice(bare)); CALL(scene_signed_distance_lattice(lg));
+        CALL(scene_signed_distance_lattice(big));
+        CALL(scene_signed_dist_field(a)); f.field = fh; CALL(dist_field_destroy(f));
+        CALL(scene_signed_dist_field(big)); f.field = fh; CALL(dist_field_destroy(f));
     }
     // a handle for the refusals below, made untraced; its register parameters are the defaults again
-    hip_stub_trace(0); OK(mon_dist_field_create(0, fdist, 3, 2, 2, origin, step, &fh)); OK(mon_register_default(fh, &rp)); hip_stub_trace(1);
+    hip_stub_trace(0); OK(mon_dist_field_create(0, fdist, 3, 2, 2, origin, step, &fh)); OK(mon_register_default(fh, &rp)); OK(mon_trace_default(fh, &trp));
+    hip_stub_trace(1);
     mon_dist_field* const fh_err = fh; good.field = fh_err;
     mon_register_params rp_huber0 = rp, rp_up1 = rp, rp_lambda0 = rp, rp_tol = rp, rp_evals0 = rp, rp_inside = rp;
     rp_huber0.huber = 0.f; rp_up1.lambda_up = 1.f; rp_lambda0.lambda0 = 0.f; rp_tol.tol_rot = -1.f; rp_evals0.max_evals = 0; rp_inside.min_inside = -1;
+    mon_trace_params trp_tmin = trp, trp_relax0 = trp, trp_relax2 = trp, trp_step0 = trp, trp_steps0 = trp, trp_steps_many = trp, trp_nan = trp;
+    trp_tmin.t_min = trp.t_max + 1.f; trp_relax0.relax = 0.f; trp_relax2.relax = 1.5f; trp_step0.step_min = 0.f; trp_steps0.max_steps = 0;
+    trp_steps_many.max_steps = 4097; trp_nan.eps = NAN;
 
     // ---- the calls every route refuses, with code and message; the trace stays on: none of them may reach the device
     std::printf("== inference errors\n");
@@ -592,6 +639,31 @@ static void inference_part(const char* cfg_json, const mon_config& base, const u
     MATCH_ERRS(dist_field_register); ERR(dist_field_register, a.rp = nullptr); ERR(dist_field_register, a.poses_out = nullptr); ERR(dist_field_register, a.rp = &rp_huber0);
     ERR(dist_field_register, a.rp = &rp_up1); ERR(dist_field_register, a.rp = &rp_lambda0); ERR(dist_field_register, a.rp = &rp_tol); ERR(dist_field_register, a.rp = &rp_evals0);
     ERR(dist_field_register, a.rp = &rp_inside); ERR(dist_field_register, a.field = nullptr; a.rp = &rp_up1);
+    // ray tracing (kTraceMaxRays 2^20, kTraceMaxPoses 4 096, kTraceMaxHome 2^22, kTraceMaxBeams 2^24, max_steps 1 to 4 096) and the signed fields
+#define TRACE_ERRS(route) do { ERR(route, a.frays = nullptr); ERR(route, a.trp = nullptr); ERR(route, a.n_frays = 0); ERR(route, a.n_frays = (1u << 20) + 1u); \
+        ERR(route, a.n_tposes = 0); ERR(route, a.tposes = many_poses.data(); a.n_tposes = 4097); ERR(route, a.tposes = nullptr; a.n_tposes = 2); \
+        ERR(route, a.tposes = pose_nan3; a.n_tposes = 3); ERR(route, a.trp = &trp_nan); ERR(route, a.trp = &trp_tmin); ERR(route, a.trp = &trp_step0); \
+        ERR(route, a.trp = &trp_relax0); ERR(route, a.trp = &trp_relax2); ERR(route, a.trp = &trp_steps0); ERR(route, a.trp = &trp_steps_many); \
+        ERR(route, a.field = nullptr); ERR(route, a.field = nullptr; a.n_frays = 0); } while (0)
+    ERR(trace_default, a.trp = nullptr); ERR(trace_default, a.field = nullptr);
+    TRACE_ERRS(dist_field_trace); ERR(dist_field_trace, a.range = nullptr);
+    ERR(dist_field_trace, a.n_frays = 1u << 20; a.tposes = many_poses.data(); a.n_tposes = 5);
+    TRACE_ERRS(dist_field_beam_score); ERR(dist_field_beam_score, a.measured = nullptr); ERR(dist_field_beam_score, a.bp = nullptr); ERR(dist_field_beam_score, a.cost = nullptr);
+    ERR(dist_field_beam_score, a.n_frays = 1u << 20; a.tposes = many_poses.data(); a.n_tposes = 17); ERR(dist_field_beam_score, a.bp = &bp_huber0);
+    ERR(dist_field_beam_score, a.field = nullptr; a.bp = &bp_huber0);
+#define SIGNED_ERRS(route) do { ERR(route, a.dist = nullptr); ERR(route, a.sigma_min = -1.f); ERR(route, a.sigma_min = NAN); ERR(route, a.flags = 2u); \
+        ERR(route, a.max_dist = 0.f); } while (0)
+#define SIGNED_FIELD_ERRS(route) do { FIELD_ERRS(route); ERR(route, a.flags = 2u); } while (0)
+    ERR(signed_distance_transform, a.val = nullptr); ERR(signed_distance_transform, a.step = nullptr); ERR(signed_distance_transform, a.dist = nullptr);
+    ERR(signed_distance_transform, a.nx = 0); ERR(signed_distance_transform, a.nx = 2048; a.ny = 2048; a.nz = 2); ERR(signed_distance_transform, a.step = step_inf);
+    ERR(signed_distance_transform, a.iso = NAN); ERR(signed_distance_transform, a.max_dist = 0.f); ERR(signed_distance_transform, a.val = nullptr; a.iso = NAN);
+    OBJS_ERRS(scene_signed_distance_lattice); LATTICE_ERRS(scene_signed_distance_lattice); SIGNED_ERRS(scene_signed_distance_lattice);
+    ERR(scene_signed_distance_lattice, a.objs = with_null; a.flags = 2u);
+    OBJS_ERRS(scene_signed_dist_field); LATTICE_ERRS(scene_signed_dist_field); SIGNED_FIELD_ERRS(scene_signed_dist_field);
+    ERR(scene_signed_dist_field, a.objs = with_null; a.field_max = INFINITY);
+    ONLINE_ERRS(online_signed_distance_lattice); LATTICE_ERRS(online_signed_distance_lattice); SIGNED_ERRS(online_signed_distance_lattice);
+    ONLINE_ERRS(online_signed_dist_field); LATTICE_ERRS(online_signed_dist_field); SIGNED_FIELD_ERRS(online_signed_dist_field);
+    ERR(online_signed_dist_field, a.om = om_none; a.field_max = 0.f);
     hip_stub_trace(0);
     OK(mon_dist_field_destroy(fh_err));
     // (the trace ends here: two object threads sign off on stdout in the order they happen to end)
