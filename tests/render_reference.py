@@ -7,6 +7,11 @@ list, restated for any subset of a rect's rays.  NumPy only; not imported by the
                a running first-order error bound delta of the device's evaluation, made of counted terms only (below)
   intervals    alpha and colour intervals in fp64 from raw +- delta, widened by the counted activation bound of test_scene_points.test_fold_and_activations
   count_rule   0 / 32 / 64 from given alphas, with np_composite's ambiguity window
+and, for the layer chain (k_render_rays .. k_composite_render, k_grid_points, k_mesh_warp; tests/test_layer_inference*.py):
+  lattice_u, mesh_warp   the lattice and the warped mesh vertices from the kernels' own operations
+  slab_edge              rays whose slab test the restated ray row cannot decide
+  composite_render64     k_composite_render in fp64 with a counted bound next to every output and an ambiguity flag per ray
+  chain_regime           how hard a render is, from the reference's wanted values
 
 The bound (U = 2^-24, the unit roundoff of fp32; every rounding is at most U relative to its result):
   encoding     K_ENC U sum_k |w_k f_k|: a corner weight is two products of factors of which each may be a rounded 1 - frac (5 roundings), its term passes
@@ -50,11 +55,7 @@ def position_bound(sc, view, Tow, rr, aabb, t):
     """Counted bound [P, 64, 3] on the unit-cube point's disagreement between pose_reference.camera_rays (fp32 sums) and the kernels' pixel_ray (fmaf
     chains) at equal t: the camera direction's norm (4 roundings a side), the division by it (1), two rot3 (3 each) -> E_d = 22 U |Row| |Rwc| |dn|;
     o: one rot3 and one add a side -> E_o = 8 U (|Row| |twc| + |tow|); p = fmaf(t, d, o) and p - amin one rounding a side each; the division two."""
-    Rwc = np.abs(np.asarray(sc.Twc[view], np.float64)[:3, :3]); twc = np.abs(np.asarray(sc.Twc[view], np.float64)[:3, 3])
-    Row = np.abs(np.asarray(Tow, np.float64)[:3, :3]); tow = np.abs(np.asarray(Tow, np.float64)[:3, 3])
-    fx, fy, cx, cy = (float(v) for v in (sc.fx, sc.fy, sc.cx, sc.cy))
-    dc = np.stack([(rr["x"] - cx) / fx, (rr["y"] - cy) / fy, np.ones(rr["x"].shape[0])], -1); dn = np.abs(dc) / np.linalg.norm(dc, axis=1, keepdims=True)
-    E_d = 22 * U * (dn @ Rwc.T @ Row.T); E_o = 8 * U * (Row @ twc + tow)
+    E_d, E_o = ray_row_bound(sc, view, Tow, rr["x"], rr["y"])
     mn = np.asarray(aabb[0], np.float64); ext = np.asarray(aabb[1], np.float64) - mn
     t = np.asarray(t, np.float64); p = t[..., None] * rr["d"].astype(np.float64)[:, None, :] + rr["o"].astype(np.float64)[:, None, :]
     return (np.abs(t)[..., None] * E_d[:, None, :] + E_o + 2 * U * (np.abs(p) + np.abs(p - mn))) / ext + 4 * U * np.abs((p - mn) / ext)
@@ -199,3 +200,89 @@ def regime(raw, alpha, count, hit):
     return dict(raw_max=float(raw[..., 3][ev].max()) if ev.any() else -np.inf, cut_share=float((count[hit] == 32).mean()) if hit.any() else 0.0,
                 n32=int((count == 32).sum()), n64=int((count == 64).sum()), n0=int((count == 0).sum()),
                 one_share=float((a.astype(f32) == f32(1.0)).mean()), tiny_share=float((a < 2.0 ** -24).mean()))
+
+
+# ------------------------------------------------------------------ (d) the layer chain: lattice points, mesh warp, slab margin, composite
+def lattice_u(rx, ry, rz):
+    """k_grid_points bit for bit: point p = (x, y, z), x fastest, at fp32(i) / fp32(r - 1) per axis (one correctly rounded division) -> [rx ry rz, 3] fp32"""
+    ax = [(np.arange(r, dtype=f32) / f32(r - 1)).astype(f32) for r in (rx, ry, rz)]
+    z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    return np.stack([x.reshape(-1), y.reshape(-1), z.reshape(-1)], -1)
+
+
+def mesh_warp(verts, aabb):
+    """k_mesh_warp from its own operations, (v - mn) / (mx - mn) in fp32 on the device's vertices -> (u [n, 3] fp32, pos_err [n, 3]).  The bound counts
+    the two subtractions and the division, one U each relative to the quotient: 3 U |u|.  Where every operation is correctly rounded the restated u is
+    the device's own and the term only widens; it covers a division that is not."""
+    v = np.asarray(verts, f32).reshape(-1, 3); aabb = np.asarray(aabb, f32)
+    u = ((v - aabb[0]) / (aabb[1] - aabb[0])).astype(f32)
+    return u, 3 * U * np.abs(u.astype(np.float64))
+
+
+def ray_row_bound(sc, view, Tow, x, y):
+    """(E_d [P, 3], E_o [3]) of position_bound: the counted distance of a restated ray row's direction and origin from the kernels' pixel_ray"""
+    Rwc = np.abs(np.asarray(sc.Twc[view], np.float64)[:3, :3]); twc = np.abs(np.asarray(sc.Twc[view], np.float64)[:3, 3])
+    Row = np.abs(np.asarray(Tow, np.float64)[:3, :3]); tow = np.abs(np.asarray(Tow, np.float64)[:3, 3])
+    fx, fy, cx, cy = (float(v) for v in (sc.fx, sc.fy, sc.cx, sc.cy))
+    dc = np.stack([(x - cx) / fx, (y - cy) / fy, np.ones(np.shape(x)[0])], -1); dn = np.abs(dc) / np.linalg.norm(dc, axis=1, keepdims=True)
+    return 22 * U * (dn @ Rwc.T @ Row.T), 8 * U * (Row @ twc + tow)
+
+
+def slab_edge(sc, view, Tow, aabb, rr):
+    """Rays the restated slab test cannot decide [P]: a plane distance a = (m - o) / d of a row known within E_o, E_d moves by at most
+    (E_o + |a| E_d) / |d| + 3 U |a| (the subtraction and the division on either side, the other side's own rounding of the quotient); a ray whose
+    entry and exit distance lie within twice the largest such movement of its six planes is set aside."""
+    E_d, E_o = ray_row_bound(sc, view, Tow, rr["x"], rr["y"])
+    o = rr["o"].astype(np.float64); d = rr["d"].astype(np.float64); aabb = np.asarray(aabb, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a = np.stack([(aabb[0][None] - o) / d, (aabb[1][None] - o) / d], 0)
+        mv = (E_o[None, None] + np.abs(a) * E_d[None]) / np.abs(d)[None] + 3 * U * np.abs(a)
+    lo = np.minimum(a[0], a[1]).max(1); hi = np.maximum(a[0], a[1]).min(1)
+    mv = np.where(np.isfinite(mv), mv, 0.0).max((0, 2))
+    return np.abs(hi - lo) <= 2 * mv
+
+
+def composite_render64(O, tdist, flag, dn):
+    """k_composite_render in fp64 for P rays of 64 samples: O [P, 64, 4] the fp16 raw outputs (uint16 bit patterns or their values), tdist [P, 64], flag
+    [P], dn [P].  Serial over the samples, the break where T < EPS before a sample, alpha and colour formed from the fp16 O as the kernel forms them,
+    rgb + T where 1 - T > 0.5 and white / 0 / 0 elsewhere, depth = dep / dn.
+    Next to every output a running first-order bound of the kernel's fp32 evaluation, counted terms only: alpha_of / colour_of's activation terms (they
+    cover __expf and the subtraction that forms dt), one U per product, per sum and per update of T, one for 1 - alpha, one for the division by dn.
+    Returns a dict: rgb [P, 3], depth, mask [P] (the image); e_rgb [P, 3], e_depth [P] (its bound; 0 on a pixel the rule whitens); amb [P] (the bound
+    cannot decide the break at some sample, T against EPS, or the mask, 1 - T against 0.5); n_used [P] (samples composited); and before the rule
+    r [P, 3] (= rgb sums + T), dep [P], T [P] with e_r, e_dep, e_T."""
+    O = np.asarray(O)
+    v = (O.view(np.float16) if O.dtype == np.uint16 else O).astype(np.float64).reshape(-1, 64, 4); P = v.shape[0]
+    t = np.asarray(tdist, np.float64).reshape(P, 64); hit = np.asarray(flag).reshape(P) != 0; dn = np.asarray(dn, np.float64).reshape(P)
+    v = np.where(hit[:, None, None], v, 0.0); t = np.where(hit[:, None], t, 0.0)                # (a missed ray's rows hold nothing)
+    c, ec = colour_of(v[..., :3]); alpha, ea = alpha_of(v[..., 3], intervals_dt(t))
+    T = np.ones(P); eT = np.zeros(P); r = np.zeros((P, 3)); er = np.zeros((P, 3)); dep = np.zeros(P); edep = np.zeros(P)
+    alive = hit.copy(); amb = np.zeros(P, bool); n_used = np.zeros(P, np.int64)
+    for n in range(64):
+        amb |= alive & (np.abs(T - EPS) <= eT)
+        alive = alive & (T >= EPS); n_used += alive
+        a = alpha[:, n]; w = a * T; ew = ea[:, n] * T + a * eT + U * w
+        wc = w[:, None] * c[:, n]; ewc = ew[:, None] * c[:, n] + w[:, None] * ec[:, n] + U * wc
+        r2 = r + wc; er2 = er + ewc + U * r2
+        wt = w * t[:, n]; d2 = dep + wt; ed2 = edep + ew * t[:, n] + U * wt + U * d2
+        om = 1.0 - a; eom = ea[:, n] + U * om
+        T2 = T * om; eT2 = eT * om + T * eom + U * T2
+        r = np.where(alive[:, None], r2, r); er = np.where(alive[:, None], er2, er); dep = np.where(alive, d2, dep); edep = np.where(alive, ed2, edep)
+        T = np.where(alive, T2, T); eT = np.where(alive, eT2, eT)
+    op = 1.0 - T; eop = eT + U * op
+    amb |= hit & (np.abs(op - 0.5) <= eop)
+    r_out = r + T[:, None]; e_r = er + eT[:, None] + U * r_out
+    depth = dep / dn; e_depth = edep / dn + U * depth
+    m = hit & (op > 0.5)
+    return dict(rgb=np.where(m[:, None], r_out, 1.0), depth=np.where(m, depth, 0.0), mask=m.astype(np.float64), e_rgb=np.where(m[:, None], e_r, 0.0),
+                e_depth=np.where(m, e_depth, 0.0), amb=amb, n_used=n_used, r=r_out, e_r=e_r, dep=dep, e_dep=edep, T=T, e_T=eT, hit=hit)
+
+
+def chain_regime(raw, tdist, flag, dn):
+    """the regime figures of a layer-chain render from the reference's wanted raw outputs [P, 64, 4]: largest raw density of a composited sample, share of
+    the hit rays that break before sample 64, rays masked in / masked out / missed, the reference's own ambiguous rays"""
+    cr = composite_render64(raw, tdist, flag, dn); hit = cr["hit"]
+    used = np.arange(64)[None, :] < cr["n_used"][:, None]
+    return dict(raw_max=float(np.asarray(raw, np.float64).reshape(-1, 64, 4)[..., 3][used].max()) if used.any() else -np.inf,
+                cut_share=float((cr["n_used"][hit] < 64).mean()) if hit.any() else 0.0, n_in=int((cr["mask"] > 0).sum()),
+                n_out=int((hit & (cr["mask"] == 0)).sum()), n_miss=int((~hit).sum()), n_amb=int(cr["amb"].sum()), n_hit=int(hit.sum()))
